@@ -77,7 +77,11 @@ def parse_args():
     ap.add_argument("--scan-projections", type=int, default=894, help="projections of the end_to_end leg")
     ap.add_argument("--ascii-projections", type=int, default=894, help="projections of the end_to_end_ascii leg (63 MB of text each; 0: skip)")
     ap.add_argument("--workdir", default=None)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write the detector tally of its last step as DIR/tally.npy (float64, exact)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
     if args.gpus is None:  # `torchrun ... bench.py` without --gpus: the launcher's rank count is the GPU count
         args.gpus = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus < 1:
@@ -117,6 +121,34 @@ def init_ranks(args, torch):
     # route after an RCCL collective has failed (the verdicts are a few bytes of host data)
     ctl = dist.new_group(backend="gloo") if (dist and backend == "nccl") else None
     return rank, world, device, dist, backend, ctl, bool(share and world > n_dev)
+
+
+DUMP_LIMIT_BYTES = 64 << 20  # all .npy files of one dump together
+
+
+def dump_outputs(out_dir, route, ctx, rank):
+    """--dump-outputs: the tally of the last timed step -- the uint64[4, Nz, Nx] words a caller of the timed launch gets back -- as
+    float64 (exact below 2^53), written by the rank that holds the complete sum of that step (the exchange owner, else rank 0).
+    Above DUMP_LIMIT_BYTES a fixed, seeded sample of 2^21 words is written instead (tally_sample.npy + tally_sample_index.npy)."""
+    if route.x:
+        if rank != route.x.owner(route.n_step - 1):
+            return
+        words = ctx.download_image(route.last_reduced, route.stream)
+    else:
+        if rank != 0:
+            return
+        words = route.last_reduced.cpu().numpy().view(np.uint64)
+    if int(words.max()) >= 2 ** 53:
+        raise SystemExit("bench.py: --dump-outputs: a tally word does not fit float64 exactly")
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    flat = words.astype(np.float64).reshape(-1)
+    if flat.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(out_dir / "tally.npy", flat.reshape(words.shape))
+        return
+    idx = np.sort(np.random.default_rng(0).choice(flat.size, 1 << 21, replace=False))
+    np.save(out_dir / "tally_sample.npy", flat[idx])
+    np.save(out_dir / "tally_sample_index.npy", idx.astype(np.float64))
 
 
 def main():
@@ -179,6 +211,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:  # before the check below, which runs a projection of its own through the same route
+        dump_outputs(args.dump_outputs, route, ctx, rank)
 
     multi = route.check(float(np.mean(kernel_ms))) if dist else None
     collectives = route.collectives_comparison() if (dist and not args.no_collectives) else None

@@ -1,19 +1,22 @@
-"""Phantom geometries against the reference's bundled assets.  Development-container checks (skipped where the reference
-tree is absent, i.e. on the GPU box): the procedural Catphan604 generator reproduces
+"""Phantom geometries against the reference's bundled assets: the procedural Catphan604 generator reproduces
 cbctmc/assets/geometries/catphan604_geometry.pkl.gz voxel for voxel, and the shipped CIRS base geometry
-(assets/geometries/base_cirs_geometry.npz) equals base_cirs_geometry.pkl.gz.  Everywhere: the shipped CIRS asset is
-pinned by its SHA-256, and the insert builders are checked against independent restatements of geo.py:749-878."""
+(assets/geometries/base_cirs_geometry.npz) equals base_cirs_geometry.pkl.gz.  The reference's assets are held by their shape,
+spacing and the SHA-256 of their voxel arrays (tests/golden/reference_geometry_assets.json, written by
+`python tests/test_phantom_vs_reference_asset.py <reference tree>`).  The shipped CIRS asset is pinned by its SHA-256 too, and
+the insert builders are checked against independent restatements of geo.py:749-878."""
 import hashlib
 import gzip
+import json
 import pickle
+import sys
 from pathlib import Path
 
 import numpy as np
-import pytest
 
 import cases
 
-ASSET = Path("/root/reference/cbctmc/assets/geometries/catphan604_geometry.pkl.gz")
+ASSETS_PIN = cases.GOLDEN / "reference_geometry_assets.json"
+ASSET_FILES = {"catphan604": "cbctmc/assets/geometries/catphan604_geometry.pkl.gz", "base_cirs": "cbctmc/assets/geometries/base_cirs_geometry.pkl.gz"}
 
 
 class _Stub:
@@ -31,27 +34,35 @@ class _Unpickler(pickle.Unpickler):
         return super().find_class(module, name)
 
 
-@pytest.mark.skipif(not ASSET.exists(), reason="reference assets not present")
+def voxel_digest(materials, densities, spacing=None):
+    """Shape, spacing and SHA-256 of the voxel arrays (materials as uint8, densities as float32, C order)."""
+    m = np.asarray(materials)
+    m8 = np.ascontiguousarray(m, dtype=np.uint8)
+    assert np.array_equal(m8, m), "material numbers beyond uint8"
+    return {"shape": list(m.shape), "spacing": None if spacing is None else [float(v) for v in spacing],
+            "materials_sha256": hashlib.sha256(m8.tobytes()).hexdigest(),
+            "densities_sha256": hashlib.sha256(np.ascontiguousarray(densities, dtype=np.float32).tobytes()).hexdigest()}
+
+
+def reference_asset(name):
+    return json.loads(ASSETS_PIN.read_text())[name]
+
+
 def test_catphan_generator_matches_bundled_asset():
-    with gzip.open(ASSET, "rb") as f:
-        ref = _Unpickler(f).load()
+    ref = reference_asset("catphan604")
     mine = cases.geometry.MCCatPhan604Geometry()
-    assert ref.materials.shape == (500, 500, 500)
-    assert np.array_equal(np.asarray(ref.materials), mine.materials)
-    assert np.array_equal(np.asarray(ref.densities, dtype=np.float32), mine.densities)
+    assert ref["shape"] == [500, 500, 500]
+    got = voxel_digest(mine.materials, mine.densities)
+    assert got["shape"] == ref["shape"]
+    assert got["materials_sha256"] == ref["materials_sha256"]
+    assert got["densities_sha256"] == ref["densities_sha256"]
 
 
-CIRS_ASSET = Path("/root/reference/cbctmc/assets/geometries/base_cirs_geometry.pkl.gz")
-
-
-@pytest.mark.skipif(not CIRS_ASSET.exists(), reason="reference assets not present")
 def test_shipped_cirs_base_geometry_equals_bundled_asset():
-    with gzip.open(CIRS_ASSET, "rb") as f:
-        ref = _Unpickler(f).load()
+    ref = reference_asset("base_cirs")
     mine = cases.geometry.MCCIRSPhantomGeometry.from_base_geometry()
-    assert mine.image_shape == (305, 300, 152) and mine.image_spacing == tuple(ref.image_spacing)
-    assert np.array_equal(np.asarray(ref.materials), mine.materials)
-    assert np.array_equal(np.asarray(ref.densities, dtype=np.float32), mine.densities)
+    assert mine.image_shape == (305, 300, 152) and list(mine.image_spacing) == ref["spacing"]
+    assert voxel_digest(mine.materials, mine.densities, mine.image_spacing) == ref
 
 
 def test_shipped_cirs_base_geometry_is_pinned():
@@ -93,3 +104,14 @@ def test_cirs_inserts_follow_the_reference_recipes():
     lung_eq = (lp.materials == M.material_number("h2o")) & np.isclose(lp.densities, 0.207)
     assert lung_eq[xs.min() + 16: xs.min() + 32, 141, 71].all()
     assert np.array_equal(lp.materials[::4][:222], base.materials[:222])  # untouched in front of the insert
+
+
+if __name__ == "__main__":  # regenerate the pin: python tests/test_phantom_vs_reference_asset.py <reference tree>
+    out = {}
+    for name, rel in ASSET_FILES.items():
+        with gzip.open(Path(sys.argv[1]) / rel, "rb") as f:
+            ref = _Unpickler(f).load()
+        spacing = getattr(ref, "image_spacing", None)
+        out[name] = voxel_digest(ref.materials, ref.densities, None if spacing is None else tuple(spacing))
+    ASSETS_PIN.write_text(json.dumps(out, indent=1) + "\n")
+    print("wrote", ASSETS_PIN)

@@ -2,11 +2,14 @@
 template `cbctmc/assets/templates/mcgpu_input.jinja2` with the parameter dictionary of `MCSimulation.create_mcgpu_input`
 (`cbctmc/mc/simulation.py:314-346`, restated below: mm -> cm rounded to six digits, gpu id -1 for several GPUs, YES/NO for explicit
 angles), loaded by the engine's host model (`mcgpu_create(device = -1)`) and by the reference build itself (`oracle/_ref`):
-source / detector structs byte for byte, output file names, trajectory scalars.  The template is read where it lies under
-/root/reference (development container; skipped elsewhere); what travels to the GPU box are digests
-(tests/golden/reference_template_pin.json, written by this file run as a script) that the engine must reproduce from the
-package's own formatter.  And the consumer's side of the boundary: `np.loadtxt -> reshape(nz, nx, 4) -> flip -> [:, :crop]`
-(`cbctmc/mc/projection.py:42-51`) of an engine-written ASCII projection equals `mcgpu_finalize_projection_host`."""
+source / detector structs byte for byte, output file names, trajectory scalars.  What the template renders for the three scans is
+stored as data: its value lines only, file paths as placeholders (tests/golden/reference_template_values.json), set line for line
+into the data lines of the package's own input file of the same scan.  Beside them lie the digests the engine must reproduce
+from the package's own formatter (tests/golden/reference_template_pin.json) and those of what the reference build read from the
+same text (tests/golden/reference_template_build_pin.json; checked live where oracle/_ref is built).  `python
+tests/test_reference_template.py <mcgpu_input.jinja2>` writes all three from the reference's template.  And the consumer's side
+of the boundary: `np.loadtxt -> reshape(nz, nx, 4) -> flip -> [:, :crop]` (`cbctmc/mc/projection.py:42-51`)
+of an engine-written ASCII projection equals `mcgpu_finalize_projection_host`."""
 import hashlib
 import json
 import os
@@ -17,8 +20,9 @@ import pytest
 
 import cases
 
-TEMPLATE = Path("/root/reference/cbctmc/assets/templates/mcgpu_input.jinja2")
 PIN = cases.GOLDEN / "reference_template_pin.json"
+VALUES = cases.GOLDEN / "reference_template_values.json"
+BUILD_PIN = cases.GOLDEN / "reference_template_build_pin.json"
 
 # what MCSimulation.run_simulation hands to create_mcgpu_input (sim.py:142-166), for three shapes of scan
 SCANS = {
@@ -52,8 +56,34 @@ def reference_parameters(geometry_file, material_files, spectrum, source_positio
     }
 
 
-def scan_inputs(name, folder, template_text=None):
-    """(input written by the package's formatter, input rendered from the reference's template or None), same scan, same geometry file."""
+def path_placeholders(folder):
+    """Placeholder -> path of the scan's files, as the stored values spell them."""
+    out = {"@FOLDER@": str(folder), "@SPECTRUM@": str(cases.spectrum_file())}
+    out.update({f"@MATERIAL_{i:02d}@": str(p) for i, p in enumerate(cases.material_files())})
+    return out
+
+
+def data_lines(text):
+    """The value part of every line of an input file that has one (comments and section markers dropped)."""
+    return [v.strip() for v in (line.partition("#")[0] for line in text.splitlines()) if v.strip()]
+
+
+def reference_template_values(name, template_text):
+    """The value lines the reference's template renders for scan `name`, file paths left as placeholders (path_placeholders)."""
+    import jinja2
+    s = SCANS[name]
+    geo = cases.CASES[s["case"]][0]()
+    d = cases.pkg.defaults.DEFAULTS
+    src = cases.simulation.source_position_for(geo.image_size, d.source_to_isocenter_distance)
+    ph = {v: k for k, v in path_placeholders("@FOLDER@").items()}
+    ctx = reference_parameters(Path("@FOLDER@") / "geometry.vox.gz", [ph[str(p)] for p in cases.material_files()], "@SPECTRUM@", src, "@FOLDER@",
+                               int(2.4e9), list(s["projection_angles"]), s["n_projections"], s["angle_between_projections"])
+    return data_lines(jinja2.Environment().from_string(template_text).render(ctx))
+
+
+def scan_inputs(name, folder, reference_values=None):
+    """(input written by the package's formatter, the same file with its data lines replaced one for one by the reference
+    template's `reference_values` or None), same scan, same geometry file."""
     s = SCANS[name]
     factory, _ = cases.CASES[s["case"]]
     geo = factory()
@@ -63,15 +93,30 @@ def scan_inputs(name, folder, template_text=None):
                                         angle_between_projections=s["angle_between_projections"], projection_angles=list(s["projection_angles"]))
     mine = sim.prepare_simulation(folder, compress_geometry=True)
     rendered = None
-    if template_text is not None:
-        import jinja2
-        d = cases.pkg.defaults.DEFAULTS
-        src = cases.simulation.source_position_for(geo.image_size, d.source_to_isocenter_distance)
-        ctx = reference_parameters(folder / "geometry.vox.gz", cases.material_files(), cases.spectrum_file(), src, folder, int(2.4e9),
-                                   list(s["projection_angles"]), s["n_projections"], s["angle_between_projections"])
+    if reference_values is not None:
+        paths = path_placeholders(folder)
+        values = iter(reference_values)
+        lines = []
+        for line in Path(mine).read_text().splitlines():
+            data, sep, comment = line.partition("#")
+            if data.strip():
+                v = next(values)
+                for k, p in paths.items():
+                    v = v.replace(k, p)
+                line = v + ("  " + sep + comment if sep else "")
+            lines.append(line)
+        assert next(values, None) is None, "the reference template renders more data lines than the package's input file has"
         rendered = folder / "input_from_reference_template.in"
-        rendered.write_text(jinja2.Environment().from_string(template_text).render(ctx))
+        rendered.write_text("\n".join(lines) + "\n")
     return mine, rendered
+
+
+def reference_build_facts(ref, scalar_names):
+    """Projections, SHA-256 of the source / detector structs and the scalars the reference build (oracle/_ref) read from an input."""
+    n = int(ref.scalars["num_projections"])
+    return {"num_projections": n, "source_data": hashlib.sha256(ref.get("source_data")[: 80 * n].tobytes()).hexdigest(),
+            "detector_data": hashlib.sha256(ref.get("detector_data")[: 100 * n].tobytes()).hexdigest(),
+            "scalars": {k: int(ref.scalars[k]) for k in scalar_names}}
 
 
 def facts(ctx):
@@ -83,12 +128,10 @@ def facts(ctx):
             "scalars": {k: ctx.geti(k) for k in ("total_histories", "seed", "gpu_id", "threads_per_block", "histories_per_thread", "enable_specific_angles")}}
 
 
-@pytest.mark.skipif(not TEMPLATE.exists(), reason="the reference tree is not present (GPU box): the committed digests stand in for it")
 @pytest.mark.parametrize("name", list(SCANS))
 def test_engine_reads_the_reference_template_like_the_reference_build(name, engine, tmp_path):
-    pytest.importorskip("jinja2")
     import oracle_lib as ol
-    mine, rendered = scan_inputs(name, tmp_path, TEMPLATE.read_text())
+    mine, rendered = scan_inputs(name, tmp_path, json.loads(VALUES.read_text())[name])
     with engine.create(rendered, device=-1) as a, engine.create(mine, device=-1) as b:
         fa, fb = facts(a), facts(b)
         assert fa == fb, "the package's formatter and the reference's template describe different scans"
@@ -98,14 +141,16 @@ def test_engine_reads_the_reference_template_like_the_reference_build(name, engi
         assert all(cases.simulation.PROJECTION_FILE_PATTERN.match(n) for n in names)
         if SCANS[name]["projection_angles"]:
             assert names[0] == names[1], "the doubled first angle gives the same file twice (the reference's 4-D driver relies on it)"
-    if not ol.reference_available():
-        pytest.skip("oracle/_ref not built")
-    ref = ol.Reference().load(rendered)
-    n = int(ref.scalars["num_projections"])
+    # what the reference build reads from the same text: live where oracle/_ref is built, else as pinned from such a run
+    want = json.loads(BUILD_PIN.read_text())[name]
+    if ol.reference_available():
+        assert reference_build_facts(ol.Reference().load(rendered), fa["scalars"]) == want, \
+            "tests/golden/reference_template_build_pin.json is stale: python tests/test_reference_template.py"
+    n = want["num_projections"]
     assert n == fa["num_projections"]
-    assert np.array_equal(ref.get("source_data")[: 80 * n], src) and np.array_equal(ref.get("detector_data")[: 100 * n], det)
-    for k, v in fa["scalars"].items():
-        assert int(ref.scalars[k]) == v, k
+    assert want["source_data"] == hashlib.sha256(src[: 80 * n].tobytes()).hexdigest()
+    assert want["detector_data"] == hashlib.sha256(det[: 100 * n].tobytes()).hexdigest()
+    assert want["scalars"] == fa["scalars"]
 
 
 @pytest.mark.parametrize("name", list(SCANS))
@@ -137,14 +182,22 @@ def test_reference_consumer_recipe_on_an_engine_written_projection(engine, case_
         assert planes[0].max() > 0
 
 
-if __name__ == "__main__":  # regenerate the pin (development container: needs /root/reference and jinja2)
+if __name__ == "__main__":  # regenerate the values and the pins: python tests/test_reference_template.py <mcgpu_input.jinja2>
+    import sys                # (needs jinja2 and oracle/_ref)
     import tempfile
+
+    import oracle_lib as ol
+    template_text = Path(sys.argv[1]).read_text()
     eng = cases.pkg.engine
-    out = {}
+    values, out, built = {}, {}, {}
     for name in SCANS:
+        values[name] = reference_template_values(name, template_text)
         with tempfile.TemporaryDirectory() as tmp:
-            _, rendered = scan_inputs(name, tmp, TEMPLATE.read_text())
+            _, rendered = scan_inputs(name, tmp, values[name])
             with eng.create(rendered, device=-1) as ctx:
                 out[name] = facts(ctx)
+            built[name] = reference_build_facts(ol.Reference().load(rendered), out[name]["scalars"])
+    VALUES.write_text(json.dumps(values, indent=1) + "\n")
     PIN.write_text(json.dumps(out, indent=1) + "\n")
-    print("wrote", PIN)
+    BUILD_PIN.write_text(json.dumps(built, indent=1) + "\n")
+    print("wrote", VALUES, PIN, BUILD_PIN)
