@@ -1,0 +1,346 @@
+// forward_project.hip -- ray-driven Joseph forward projection on a circular cone-beam geometry for MI355X (what the reference obtains
+// from RTK's JosephForwardProjectionImageFilter, cbctmc/forward_projection.py: project_forward).  Geometry model as fdk.hip
+// (rotation axis Y, source at Ry(gantry) (0, 0, sid), u = sdd x'/(sid - z') - proj_offset_x); the scheme as RTK documents it,
+// restated in float64 by tests/joseph_ref.py (parity against RTK's own border handling is unpinned: RTK is absent here):
+//   - one lane per detector pixel; a wave covers an 8x8 pixel tile, a workgroup 2x2 tiles, the grid one batch of projections
+//     (per-projection constants in the kernarg block: wave-uniform scalar loads)
+//   - per ray (float64, once): clip the segment source -> pixel to the volume box, which spans half a voxel beyond the outer voxel
+//     centres; main axis = the largest component of the ray direction in index coordinates (ties: x before y before z)
+//   - samples where the ray crosses the voxel-centre planes k = ns..fs of the main axis; each is a bilinear interpolation in the
+//     other two axes with explicit float32 weights, taps outside the volume read 0; the first and last steps are weighted by the
+//     fraction of a step the clipped segment covers, and the sum is scaled by the length in mm of one main-axis step
+//   - float32 accumulation (RTK's float pixel type)
+// The traversal runs in the index frame of the IEC volume [nz][ny][nx]; only the voxel fetch differs between volume sources
+// (template parameter): a float volume uploaded from the host, or the context's own representation (u8 tiled / u16 palette
+// indices with the palette densities in LDS, raw {density, material} float2), read in the .vox frame.  All sources run the same
+// arithmetic, so the same densities give bit-identical sums.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "engine_internal.hpp"
+
+extern "C" void mcgpu_set_last_error_(const char* message);
+
+namespace {
+
+using namespace mcgpu;
+
+constexpr int kBatch = 16;       // projections per launch (blockIdx.z)
+constexpr int kChunk = 64;       // projections resident in the device output buffer (downloaded per chunk)
+constexpr int kPalLds = 8192;    // palette densities staged in LDS up to this many entries (32 KB)
+
+struct FpProj {
+  double c, s, off_x, off_y;
+};
+
+struct FpArgs {
+  int nu, nv, nb;
+  int n[3];                        // IEC volume size (x fastest)
+  double u0, v0, du, dv, sid, sdd;
+  double o[3], sp[3];              // origin (centre of voxel 0) and spacing, mm
+  FpProj pp[kBatch];
+};
+
+// ---- voxel sources: density at IEC index (x, y, z), all inside the volume ------------------------------------------------
+struct SrcFloat {
+  static constexpr bool kPalette = false;
+  static constexpr int kLdsN = 1;
+  const float* v;
+  int nx, nxy;
+  __device__ float operator()(int x, int y, int z, const float*) const { return v[(size_t)z * nxy + (size_t)y * nx + x]; }
+};
+
+// The context's volume is stored in the .vox frame (geometry.py: mcgpu_arrays, rot90(k=3) of the MCGeometry arrays); with the IEC
+// mapping of prepare_image_for_rtk (IEC X = MC x, Y = -MC z, Z = -MC y) an IEC voxel (x, y, z) is vox voxel
+// (vnx - 1 - z, vny - 1 - x, vnz - 1 - y), where (vnx, vny, vnz) = (NZ, NX, NY).
+struct VoxFrame {
+  int vnx, vny, vnz;
+  __device__ void map(int x, int y, int z, unsigned& vx, unsigned& vy, unsigned& vz) const {
+    vx = (unsigned)(vnx - 1 - z); vy = (unsigned)(vny - 1 - x); vz = (unsigned)(vnz - 1 - y);
+  }
+};
+
+struct SrcU8 {  // tiled palette indices (device_model.hpp: tiled_voxel), palette densities in LDS
+  static constexpr bool kPalette = true;
+  static constexpr int kLdsN = 256;
+  const unsigned char* v;
+  VoxFrame f;
+  unsigned sub_nx, sub_nxy;
+  __device__ float operator()(int x, int y, int z, const float* pal) const {
+    unsigned vx, vy, vz;
+    f.map(x, y, z, vx, vy, vz);
+    return pal[v[tiled_voxel(vx, vy, vz, sub_nx, sub_nxy)]];
+  }
+};
+
+template <bool kLds>
+struct SrcU16 {  // x-fastest palette indices; densities in LDS when the palette fits, else read from the float2 palette
+  static constexpr bool kPalette = kLds;
+  static constexpr int kLdsN = kLds ? kPalLds : 1;
+  const unsigned short* v;
+  const float* pal2;
+  VoxFrame f;
+  __device__ float operator()(int x, int y, int z, const float* pal) const {
+    unsigned vx, vy, vz;
+    f.map(x, y, z, vx, vy, vz);
+    const unsigned i = v[((size_t)vz * f.vny + vy) * f.vnx + vx];
+    return kLds ? pal[i] : pal2[2 * (size_t)i];
+  }
+};
+
+struct SrcRaw {  // {density, material} per voxel, x fastest
+  static constexpr bool kPalette = false;
+  static constexpr int kLdsN = 1;
+  const float2* v;
+  VoxFrame f;
+  __device__ float operator()(int x, int y, int z, const float*) const {
+    unsigned vx, vy, vz;
+    f.map(x, y, z, vx, vy, vz);
+    return v[((size_t)vz * f.vny + vy) * f.vnx + vx].x;
+  }
+};
+
+// element m of (v0, v1, v2) by selects: a per-lane index into a private array would put the array in scratch
+template <class T>
+__device__ inline T sel3(int m, T v0, T v1, T v2) { return m == 0 ? v0 : (m == 1 ? v1 : v2); }
+
+template <class Src>
+__global__ __launch_bounds__(256) void joseph_fp_kernel(float* __restrict__ out /*[nb][nv][nu]*/, const FpArgs A, const Src src,
+                                                        const float* __restrict__ pal2, int pal_n) {
+  __shared__ float pal[Src::kLdsN];
+  if constexpr (Src::kPalette) {
+    for (int i = threadIdx.x; i < pal_n; i += blockDim.x) pal[i] = pal2[2 * i];
+    __syncthreads();
+  }
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  const int iu = blockIdx.x * 16 + (w & 1) * 8 + (l & 7), iv = blockIdx.y * 16 + (w >> 1) * 8 + (l >> 3);
+  if (iu >= A.nu || iv >= A.nv) return;
+  const FpProj P = A.pp[blockIdx.z];
+  // ray source -> pixel in world coordinates, then in index coordinates of the volume
+  const double xr = A.u0 + A.du * iu + P.off_x, yr = A.v0 + A.dv * iv + P.off_y, zr = A.sid - A.sdd;
+  const double S[3] = {P.s * A.sid, 0.0, P.c * A.sid};
+  const double D[3] = {P.c * xr + P.s * zr - S[0], yr - S[1], -P.s * xr + P.c * zr - S[2]};
+  double Si[3], Di[3];
+  double t0 = 0.0, t1 = 1.0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    Si[a] = (S[a] - A.o[a]) / A.sp[a];
+    Di[a] = D[a] / A.sp[a];
+    const double lo = -0.5, hi = A.n[a] - 0.5;
+    if (Di[a] != 0.0) {
+      double ta = (lo - Si[a]) / Di[a], tb = (hi - Si[a]) / Di[a];
+      if (ta > tb) { const double t = ta; ta = tb; tb = t; }
+      t0 = fmax(t0, ta); t1 = fmin(t1, tb);
+    } else if (Si[a] < lo || Si[a] > hi) {
+      t1 = -1.0;
+    }
+  }
+  float acc = 0.f;
+  if (t0 < t1) {
+    int m = 0;
+    if (fabs(Di[1]) > fabs(Di[0])) m = 1;
+    if (fabs(Di[2]) > fabs(sel3(m, Di[0], Di[1], Di[2]))) m = 2;
+    // (a1, a2) = the other two axes in increasing order
+    const double Sm = sel3(m, Si[0], Si[1], Si[2]), Dm = sel3(m, Di[0], Di[1], Di[2]);
+    const double S1 = (m == 0) ? Si[1] : Si[0], D1 = (m == 0) ? Di[1] : Di[0];
+    const double S2 = (m == 2) ? Si[1] : Si[2], D2 = (m == 2) ? Di[1] : Di[2];
+    const int nm = sel3(m, A.n[0], A.n[1], A.n[2]), na = (m == 0) ? A.n[1] : A.n[0], nb = (m == 2) ? A.n[1] : A.n[2];
+    const double e0 = Sm + t0 * Dm, e1 = Sm + t1 * Dm;
+    const double lo = fmin(e0, e1), hi = fmax(e0, e1);
+    const int ns = max((int)floor(lo + 0.5), 0), fs = min((int)floor(hi + 0.5), nm - 1);
+    if (ns <= fs) {
+      const double r1 = D1 / Dm, r2 = D2 / Dm;
+      const float w_first = (float)(ns == fs ? hi - lo : ns + 0.5 - lo), w_last = (float)(hi - fs + 0.5);
+      const float A0 = (float)(S1 + (ns - Sm) * r1), B0 = (float)(S2 + (ns - Sm) * r2);
+      const float fr1 = (float)r1, fr2 = (float)r2;
+      for (int k = ns; k <= fs; ++k) {
+        const float dk = (float)(k - ns);
+        const float a = fmaf(dk, fr1, A0), b = fmaf(dk, fr2, B0);
+        const float fa0 = floorf(a), fb0 = floorf(b);
+        const int ia = (int)fa0, ib = (int)fb0;
+        const float fa = a - fa0, fb = b - fb0;
+        float v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int qa = ia + (q & 1), qb = ib + (q >> 1);
+          v[q] = 0.f;
+          if ((unsigned)qa < (unsigned)na && (unsigned)qb < (unsigned)nb) {
+            const int x = (m == 0) ? k : qa;
+            const int y = (m == 1) ? k : (m == 0 ? qa : qb);
+            const int z = (m == 2) ? k : qb;
+            v[q] = src(x, y, z, pal);
+          }
+        }
+        const float ga = 1.f - fa, gb = 1.f - fb;
+        const float s = gb * (ga * v[0] + fa * v[1]) + fb * (ga * v[2] + fa * v[3]);
+        const float wk = (k == ns) ? w_first : (k == fs ? w_last : 1.f);
+        acc = fmaf(wk, s, acc);
+      }
+      const double len = sqrt(D[0] * D[0] + D[1] * D[1] + D[2] * D[2]) / fabs(Dm);  // mm per main-axis step
+      acc *= (float)len;
+    }
+  }
+  out[((size_t)blockIdx.z * A.nv + iv) * A.nu + iu] = acc;
+}
+
+struct FpError { int code; std::string msg; };
+#define FP_HIP(expr)                                                                                      \
+  do {                                                                                                    \
+    hipError_t _e = (expr);                                                                               \
+    if (_e != hipSuccess) throw FpError{-1, std::string("!!HIP ERROR!! ") + #expr + ": " + hipGetErrorString(_e)}; \
+  } while (0)
+
+bool read_options(const char* fn, const mcgpu_fp_options* caller, mcgpu_fp_options& o) {
+  if (!caller || caller->struct_size == 0) {
+    mcgpu_set_last_error_((std::string("!!ERROR!! ") + fn + ": set mcgpu_fp_options.struct_size = sizeof(mcgpu_fp_options)").c_str());
+    return false;
+  }
+  memset(&o, 0, sizeof o);  // a caller built against an older header passes a shorter struct: what it does not have reads as zero
+  memcpy(&o, caller, std::min<size_t>(caller->struct_size, sizeof o));
+  if (o.n_proj < 1 || o.nu < 1 || o.nv < 1 || !o.gantry_deg || !(o.du > 0) || !(o.dv > 0) || !(o.sid > 0) || !(o.sdd > 0)) {
+    mcgpu_set_last_error_((std::string("!!ERROR!! ") + fn + ": bad argument").c_str());
+    return false;
+  }
+  return true;
+}
+
+// FpArgs of the volume; the per-projection block is filled per launch
+FpArgs volume_args(const mcgpu_fp_options& o, const int n[3], const double sp[3]) {
+  FpArgs A;
+  memset(&A, 0, sizeof A);
+  A.nu = o.nu; A.nv = o.nv;
+  const double org[3] = {o.ox, o.oy, o.oz};
+  for (int a = 0; a < 3; ++a) {
+    A.n[a] = n[a];
+    A.sp[a] = sp[a];
+    A.o[a] = std::isnan(org[a]) ? -(n[a] - 1) / 2.0 * sp[a] : org[a];
+  }
+  A.u0 = o.u0; A.v0 = o.v0; A.du = o.du; A.dv = o.dv; A.sid = o.sid; A.sdd = o.sdd;
+  return A;
+}
+
+// all projections through one source; projections [n_proj][nv][nu] on the host
+template <class Src>
+void project_all(const mcgpu_fp_options& o, FpArgs A, const Src& src, const float* pal2, int pal_n, float* projections, double& ms_kernel) {
+  const size_t plane = (size_t)o.nu * o.nv;
+  const int chunk = std::min(o.n_proj, kChunk);
+  float* d_out = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  try {
+    FP_HIP(hipMalloc(&d_out, (size_t)chunk * plane * 4));
+    FP_HIP(hipEventCreate(&e0));
+    FP_HIP(hipEventCreate(&e1));
+    for (int first = 0; first < o.n_proj; first += chunk) {
+      const int m = std::min(chunk, o.n_proj - first);
+      FP_HIP(hipEventRecord(e0, nullptr));
+      for (int b = 0; b < m; b += kBatch) {
+        A.nb = std::min(kBatch, m - b);
+        for (int k = 0; k < A.nb; ++k) {
+          const int p = first + b + k;
+          const double t = o.gantry_deg[p] * M_PI / 180.0;
+          A.pp[k] = {std::cos(t), std::sin(t), o.proj_offset_x ? o.proj_offset_x[p] : 0.0, o.proj_offset_y ? o.proj_offset_y[p] : 0.0};
+        }
+        hipLaunchKernelGGL(joseph_fp_kernel<Src>, dim3((unsigned)((o.nu + 15) / 16), (unsigned)((o.nv + 15) / 16), (unsigned)A.nb), dim3(256), 0, nullptr,
+                           d_out + (size_t)b * plane, A, src, pal2, pal_n);
+      }
+      FP_HIP(hipGetLastError());
+      FP_HIP(hipEventRecord(e1, nullptr));
+      FP_HIP(hipEventSynchronize(e1));
+      float ms = 0.f;
+      FP_HIP(hipEventElapsedTime(&ms, e0, e1));
+      ms_kernel += ms;
+      FP_HIP(hipMemcpy(projections + (size_t)first * plane, d_out, (size_t)m * plane * 4, hipMemcpyDeviceToHost));
+    }
+  } catch (...) {
+    if (d_out) (void)hipFree(d_out);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    throw;
+  }
+  (void)hipFree(d_out);
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+}
+
+}  // namespace
+
+extern "C" int mcgpu_forward_project(const mcgpu_fp_options* caller_o, const float* volume, float* projections, mcgpu_fp_report* report) {
+  mcgpu_fp_options o;
+  if (!read_options("mcgpu_forward_project", caller_o, o)) return -1;
+  if (!volume || !projections || o.nx < 1 || o.ny < 1 || o.nz < 1 || !(o.sx > 0) || !(o.sy > 0) || !(o.sz > 0)) {
+    mcgpu_set_last_error_("!!ERROR!! mcgpu_forward_project: bad volume argument");
+    return -1;
+  }
+  float* d_vol = nullptr;
+  int rc = 0;
+  try {
+    FP_HIP(hipSetDevice(o.device));
+    const size_t nvox = (size_t)o.nx * o.ny * o.nz;
+    const auto t0 = std::chrono::steady_clock::now();
+    FP_HIP(hipMalloc(&d_vol, nvox * 4));
+    FP_HIP(hipMemcpy(d_vol, volume, nvox * 4, hipMemcpyHostToDevice));
+    const double ms_upload = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const int n[3] = {o.nx, o.ny, o.nz};
+    const double sp[3] = {o.sx, o.sy, o.sz};
+    SrcFloat src{d_vol, o.nx, o.nx * o.ny};
+    double ms_kernel = 0.0;
+    project_all(o, volume_args(o, n, sp), src, nullptr, 0, projections, ms_kernel);
+    if (report) { report->ms_kernel = ms_kernel; report->ms_upload = ms_upload; }
+  } catch (const FpError& e) {
+    mcgpu_set_last_error_(e.msg.c_str());
+    rc = e.code;
+  }
+  if (d_vol) (void)hipFree(d_vol);
+  return rc;
+}
+
+extern "C" int mcgpu_forward_project_context(mcgpu_ctx* ctx, const mcgpu_fp_options* caller_o, float* projections, mcgpu_fp_report* report) {
+  mcgpu_fp_options o;
+  if (!read_options("mcgpu_forward_project_context", caller_o, o)) return -1;
+  if (!ctx || !ctx->has_device || !projections) {
+    mcgpu_set_last_error_("!!ERROR!! mcgpu_forward_project_context: bad argument (the context needs a device)");
+    return -1;
+  }
+  const HostModel& H = ctx->host;
+  const DeviceModel& D = ctx->dev;
+  const int vn[3] = {H.voxels.n[0], H.voxels.n[1], H.voxels.n[2]};
+  const int n[3] = {vn[1], vn[2], vn[0]};  // IEC (X, Y, Z) = (vox y, vox z, vox x), each reversed
+  if ((o.nx || o.ny || o.nz) && (o.nx != n[0] || o.ny != n[1] || o.nz != n[2])) {
+    mcgpu_set_last_error_(("!!ERROR!! mcgpu_forward_project_context: volume size " + std::to_string(o.nx) + "x" + std::to_string(o.ny) + "x" +
+                           std::to_string(o.nz) + " is not the context's IEC size " + std::to_string(n[0]) + "x" + std::to_string(n[1]) + "x" +
+                           std::to_string(n[2])).c_str());
+    return -1;
+  }
+  // spacing: the caller's (mm, IEC order) when given, else the context's voxel size (cm)
+  const double sp[3] = {o.sx > 0 ? o.sx : 10.0 * H.voxels.voxel_size[1], o.sy > 0 ? o.sy : 10.0 * H.voxels.voxel_size[2],
+                        o.sz > 0 ? o.sz : 10.0 * H.voxels.voxel_size[0]};
+  int rc = 0;
+  try {
+    FP_HIP(hipSetDevice(D.device_id));
+    const FpArgs A = volume_args(o, n, sp);
+    const VoxFrame f{vn[0], vn[1], vn[2]};
+    double ms_kernel = 0.0;
+    if (D.vol_kind == kVolU8) {
+      SrcU8 src{(const unsigned char*)D.vol, f, (unsigned)((vn[0] + 3) >> 2), (unsigned)(((vn[0] + 3) >> 2) * ((vn[1] + 3) >> 2))};
+      project_all(o, A, src, D.palette, D.palette_size, projections, ms_kernel);
+    } else if (D.vol_kind == kVolU16 && D.palette_size <= kPalLds) {
+      SrcU16<true> src{(const unsigned short*)D.vol, D.palette, f};
+      project_all(o, A, src, D.palette, D.palette_size, projections, ms_kernel);
+    } else if (D.vol_kind == kVolU16) {
+      SrcU16<false> src{(const unsigned short*)D.vol, D.palette, f};
+      project_all(o, A, src, D.palette, D.palette_size, projections, ms_kernel);
+    } else {
+      SrcRaw src{(const float2*)D.vol, f};
+      project_all(o, A, src, nullptr, 0, projections, ms_kernel);
+    }
+    if (report) { report->ms_kernel = ms_kernel; report->ms_upload = 0.0; }
+  } catch (const FpError& e) {
+    mcgpu_set_last_error_(e.msg.c_str());
+    rc = e.code;
+  }
+  return rc;
+}

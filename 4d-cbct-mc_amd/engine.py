@@ -29,7 +29,7 @@ ABI_SYMBOLS = (
     "mcgpu_finalize_projection", "mcgpu_finalize_projection_host", "mcgpu_stack_create", "mcgpu_stack_append", "mcgpu_stack_write_slice", "mcgpu_stack_finish",
     "mcgpu_stack_read", "mcgpu_normalize_stack", "mcgpu_run_scan", "mcgpu_run_scan_multi", "mcgpu_set_projection_angles", "mcgpu_set_geometry_arrays",
     "mcgpu_warp_volume", "mcgpu_warp_geometry",
-    "mcgpu_write_voxel_file", "mcgpu_write_voxel_binary", "mcgpu_kat_rng", "mcgpu_kat_rng_streams", "mcgpu_microbench", "mcgpu_kat_math", "mcgpu_kat_expf", "mcgpu_kat_f32", "mcgpu_kat_fast64", "mcgpu_kat_tile_records", "mcgpu_fdk_reconstruct", "mcgpu_set_fast_schedule", "mcgpu_reload_env_knobs",
+    "mcgpu_write_voxel_file", "mcgpu_write_voxel_binary", "mcgpu_kat_rng", "mcgpu_kat_rng_streams", "mcgpu_microbench", "mcgpu_kat_math", "mcgpu_kat_expf", "mcgpu_kat_f32", "mcgpu_kat_fast64", "mcgpu_kat_tile_records", "mcgpu_fdk_reconstruct", "mcgpu_forward_project", "mcgpu_forward_project_context", "mcgpu_set_fast_schedule", "mcgpu_reload_env_knobs",
     "mcgpu_exchange_shared_bytes", "mcgpu_exchange_card_bytes", "mcgpu_exchange_create", "mcgpu_exchange_card", "mcgpu_exchange_connect",
     "mcgpu_exchange_connect_local", "mcgpu_exchange_probe", "mcgpu_exchange_owner", "mcgpu_exchange_begin", "mcgpu_exchange_submit", "mcgpu_exchange_collect",
     "mcgpu_exchange_stats", "mcgpu_exchange_destroy", "mcgpu_copy_to_host",
@@ -544,6 +544,24 @@ class Context:
         if u.shape != want:
             raise ValueError(f"displacement of shape {u.shape}, expected {want} for frame '{frame}'")
         _check(self.lib.mcgpu_warp_geometry(self.h, u.ctypes.data, 1 if frame == "geometry" else 0, int(default_material), float(default_density)))
+
+    def project_forward(self, angles_deg, detector_size=(1024, 768), detector_pixel_spacing=(0.388, 0.388), detector_offset_x=None,
+                        detector_offset_y=0.0, source_to_isocenter=None, source_to_detector=None, spacing_iec=None, origin_iec=None):
+        """Joseph forward projection of the context's CURRENT geometry (after set_geometry / warp_geometry), read in place on
+        the device (mcgpu_forward_project_context): -> (projections [n][nv][nu] float32, report dict).  Same geometry model and
+        detector grid as forward_projection.project_forward (RTK geometry; pixel origin -0.5 n spacing, the reference's
+        ConstantImageSource).  spacing_iec / origin_iec: the IEC spacing (mm) and origin forward_projection.prepare_image_for_rtk
+        gives the same volume (default: the context's voxel size, volume centred)."""
+        from . import defaults, forward_projection
+        from .reconstruction import create_geometry
+        d = defaults.DEFAULTS
+        angles = np.atleast_1d(np.asarray(angles_deg, dtype=np.float64))
+        geo = create_geometry(0, source_to_isocenter=d.source_to_isocenter_distance if source_to_isocenter is None else source_to_isocenter,
+                              source_to_detector=d.source_to_detector_distance if source_to_detector is None else source_to_detector)
+        off_x = d.detector_lateral_displacement if detector_offset_x is None else detector_offset_x
+        for a in angles:
+            geo.add_projection(float(a), off_x, detector_offset_y)
+        return forward_projection._project(self.lib, geo, detector_size, detector_pixel_spacing, spacing_iec, origin_iec, context=self.h)
 
     def warp_volume(self, material_zyx: np.ndarray, density_zyx: np.ndarray, displacement: np.ndarray, default_material: int, default_density: float):
         """Nearest-neighbour warp on the GPU: out[x] = in[rint(x + u(x))]; displacement [3, nz, ny, nx] (x, y, z components, voxels)."""

@@ -187,14 +187,39 @@ class MCSimulation:
     def _already_simulated(output_folder) -> bool:
         return (Path(output_folder) / "projections_total.mha").is_file()  # sim.py:89-93
 
+    def write_forward_projection(self, output_folder, engine, gpu_id: int = 0, detector_size=DEFAULTS.n_detector_pixels_half_fan,
+                                 detector_pixel_spacing=DEFAULTS.detector_pixel_size):
+        """`run-mc --forward-projection` (scripts/run_mc_simulations.py:442-461): geometry.xml (create_geometry, start angle
+        90 degrees, this scan's projection count) and density_fp.mha, the Joseph forward projection of the geometry's densities
+        (g/cm^3 x mm) on that geometry.  An existing density_fp.mha is left alone.  Returns its path."""
+        from .forward_projection import create_geometry, prepare_image_for_rtk, project_forward, save_geometry, stack_metadata
+        output_folder = Path(output_folder)
+        output_folder.mkdir(parents=True, exist_ok=True)
+        fp_geometry = create_geometry(start_angle=90, n_projections=self.n_projections)
+        save_geometry(fp_geometry, output_folder / "geometry.xml")
+        path = output_folder / "density_fp.mha"
+        if not path.exists():
+            image = prepare_image_for_rtk(self.geometry.densities, image_spacing=self.geometry.image_spacing, input_value_range=None,
+                                          output_value_range=None)
+            fp = project_forward(image, fp_geometry, detector_size=detector_size, detector_pixel_spacing=detector_pixel_spacing, gpu_id=gpu_id)
+            spacing, _ = stack_metadata(detector_size, detector_pixel_spacing)
+            w = engine.StackWriter(path, int(detector_size[0]), int(detector_size[1]), fp.array.shape[0], spacing[:2])
+            for plane in fp.array:
+                w.append(plane)
+            w.finish(replace_zeros=False)
+        return path
+
     def run_simulation(self, output_folder, engine, gpu_ids=(0,), mode="fast", run_air_simulation=False,
                        air_projection_denoise_kernel_size=(10, 10), clean=True, stack_projections=True, force_rerun=False,
-                       air_n_histories=int(5e10), **prepare_kwargs):
+                       air_n_histories=int(5e10), forward_projection=False, **prepare_kwargs):
         """`BaseMCSimulation.run_simulation` (sim.py:370-427) on the in-process engine: the docker/mpirun launch and the
         ASCII -> numpy -> SimpleITK post-processing are replaced by the engine's scan pipeline, which writes
         projections_{total,unscattered,scattered}.mha (and projections_total_normalized.mha with an air scan) directly.
-        `clean=False` additionally keeps the reference's per-projection ASCII files.  Returns the scan report."""
+        `clean=False` additionally keeps the reference's per-projection ASCII files.  `forward_projection=True` also writes
+        geometry.xml and density_fp.mha into `output_folder` (write_forward_projection).  Returns the scan report."""
         output_folder = Path(output_folder)
+        if forward_projection:
+            self.write_forward_projection(output_folder, engine, gpu_id=gpu_ids if isinstance(gpu_ids, int) else gpu_ids[0])
         if self._already_simulated(output_folder) and not force_rerun:
             return None
         if run_air_simulation and not stack_projections:
@@ -309,7 +334,11 @@ class MCSimulation4D:
 
     def run_simulation(self, respiratory_signal, respiratory_signal_quantization, output_folder, engine, gpu_ids=(0,), mode="fast",
                        run_air_simulation=False, air_projection_denoise_kernel_size=(10, 10), air_n_histories=int(5e10), start_angle=270.0,
-                       force_rerun=False):
+                       force_rerun=False, forward_projection=False, fp_detector_size=DEFAULTS.n_detector_pixels_half_fan,
+                       fp_detector_pixel_spacing=DEFAULTS.detector_pixel_size):
+        """`forward_projection=True`: also density_fp_4d.mha (scripts/run_mc_simulations.py:491-556), one slice per projection:
+        the Joseph forward projection of that projection's warped geometry at FP angle = MC angle - 180 degrees, projected from
+        the resident context right after the state is applied (the warped volume never leaves the device)."""
         import numpy as np
         from .respiratory import RespiratorySignal
         output_folder = Path(output_folder)
@@ -343,10 +372,22 @@ class MCSimulation4D:
         stacks = [engine.StackWriter(output_folder / f"projections_{m}.mha", cx, nz_det, n_proj, MCSimulation.STACK_PIXEL_SPACING)
                   for m in ("total", "unscattered", "scattered")]
         geometries = {}
+        fp_stack = fp_frame = None
+        if forward_projection:
+            from .forward_projection import rtk_frame
+            fp_stack = engine.StackWriter(output_folder / "density_fp_4d.mha", int(fp_detector_size[0]), int(fp_detector_size[1]), n_proj,
+                                          fp_detector_pixel_spacing)
+            fp_frame = rtk_frame(self.geometry.image_shape, self.geometry.image_spacing)
         ctx = engine.create(str(input_filepath), device=gpu_ids[0])
         try:
             for (s, ds), indices in unique.items():
                 self.apply_state(ctx, engine, s, ds)
+                if fp_stack is not None:
+                    fp, _ = ctx.project_forward([start_angle + i * self.angle_between_projections - 180.0 for i in indices],
+                                                detector_size=fp_detector_size, detector_pixel_spacing=fp_detector_pixel_spacing,
+                                                spacing_iec=fp_frame[0], origin_iec=fp_frame[1])
+                    for i, plane in zip(indices, fp):
+                        fp_stack.write_slice(i, plane)
                 angles = [start_angle + i * self.angle_between_projections for i in indices]
                 ctx.set_projection_angles(angles[0:1] + angles)  # pose 0 is the input file's: skipped below (sim.py:658-660)
                 ctx.run_scan(mode=mode, first_projection=1, num_projections=len(angles), crop_nx=half_fan, write_stacks=False,
@@ -357,6 +398,8 @@ class MCSimulation4D:
             ctx.close()
         for w in stacks:
             w.finish(replace_zeros=True)
+        if fp_stack is not None:
+            fp_stack.finish(replace_zeros=False)
         if air_stack is not None:
             engine.normalize_stack(output_folder / "projections_total.mha", air_stack, output_folder / "projections_total_normalized.mha",
                                    sigma=air_projection_denoise_kernel_size, spacing=MCSimulation.STACK_PIXEL_SPACING)

@@ -403,6 +403,36 @@ typedef struct mcgpu_fdk_report {
 } mcgpu_fdk_report;
 int mcgpu_fdk_reconstruct(const mcgpu_fdk_options *options, const float *projections, float *volume, mcgpu_fdk_report *report);
 
+/* ------------------------------------------------------------------------------------------------
+ * Joseph forward projection on the circular cone-beam geometry of the FDK options above: what the reference obtains from RTK's
+ * JosephForwardProjectionImageFilter, cbctmc/forward_projection.py: project_forward (csrc/forward_project.hip).  Output
+ * [n_proj][nv][nu] line integrals (sum of density x mm), pixel (i, j) centred at (u0 + i du, v0 + j dv).  The volume
+ * [nz][ny][nx] is in RTK's IEC frame, voxel (0,0,0) centred at (ox, oy, oz) (NaN = volume centred on the isocentre); it spans
+ * half a voxel beyond its outer voxel centres and is 0 outside.  Parity against RTK's own border handling is unpinned. */
+typedef struct mcgpu_fp_options {
+  unsigned int struct_size;     /* sizeof(mcgpu_fp_options) as the caller was compiled (later fields read as zero); 0 is refused */
+  int n_proj, nu, nv;
+  double du, dv, u0, v0;
+  double sid, sdd;
+  const double *gantry_deg;     /* [n_proj] */
+  const double *proj_offset_x;  /* [n_proj] or NULL (0) */
+  const double *proj_offset_y;  /* [n_proj] or NULL (0) */
+  int nx, ny, nz;               /* mcgpu_forward_project_context: 0 = the context's size, else must equal it */
+  double sx, sy, sz;            /* mm; mcgpu_forward_project_context: 0 = the context's voxel size */
+  double ox, oy, oz;
+  int device;                   /* mcgpu_forward_project only (a context projects on its own device) */
+} mcgpu_fp_options;
+typedef struct mcgpu_fp_report {
+  double ms_kernel;  /* projection kernels */
+  double ms_upload;  /* host -> device copy of the volume (0 for a context) */
+} mcgpu_fp_report;
+/* A float volume from the host; no context needed. */
+int mcgpu_forward_project(const mcgpu_fp_options *options, const float *volume, float *projections, mcgpu_fp_report *report);
+/* The context's current geometry (after mcgpu_set_geometry_arrays or mcgpu_warp_geometry), read in place on the device.  Its
+ * volume is stored in the .vox frame (vox x, y, z = MC y, -MC x, MC z); IEC (X, Y, Z) = (-vox y, -vox z, -vox x), i.e. the
+ * IEC size is (vox ny, vox nz, vox nx). */
+int mcgpu_forward_project_context(mcgpu_ctx *ctx, const mcgpu_fp_options *options, float *projections, mcgpu_fp_report *report);
+
 #ifdef __cplusplus
 }
 #endif
