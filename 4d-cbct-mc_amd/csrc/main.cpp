@@ -3,7 +3,8 @@
 // Same command line, same input/output files and the same progress line on stdout
 // ("<< Simulating Projection i of n >>", parsed by cbctmc/mc/simulation.py:200-219); the word "error"
 // is only ever printed on failure (simulation.py:204 greps for it).  Options after the input file:
-//   --mode fast|compat   kernel personality (default fast)
+//   --mode fast|fast64|compat   kernel personality (default fast; fast64: the FAST kernel with the reference's double-precision
+//                        sub-steps)
 //   --gpus N             history-shard every projection over devices 0..N-1 of this node (default 1: the input file's
 //                        GPU number); the per-device tallies are summed through the tally exchange (exchange.cpp: copy-engine
 //                        pushes to the projection's owner device, one fused add; integers: order-independent)
@@ -13,13 +14,15 @@
 //                        tallies summed through the exchange) or give every device whole projections (no traffic between the
 //                        devices at all: the fallback for nodes without working peer access; same output bytes)
 //   --reduce exchange|rccl   with several devices sharing histories: sum the per-device tallies through the tally exchange (default; falls
-//                        back to RCCL, then to projection sharding, where the devices cannot reach each other) or with ONE
-//                        ncclReduce(uint64, sum) per projection (the reference's MPI_Reduce, MC-GPU_v1.3.cu:1019; RCCL is opened with dlopen)
+//                        back to projection sharding where the devices cannot reach each other) or with ONE ncclReduce(uint64, sum)
+//                        per projection (the reference's MPI_Reduce, MC-GPU_v1.3.cu:1019; RCCL is opened with dlopen; falls back to
+//                        projection sharding where RCCL cannot be set up)
 //   --no-output          skip the ASCII projection files (timing runs, or stacks only)
 //   --stacks             also write projections_{total,unscattered,scattered}.mha next to the projection files
 //                        (what cbctmc/mc/simulation.py:235-277 builds from the ASCII files afterwards)
 //   --crop N             half-fan crop of the stacks (default 1024 when the detector has 1848 columns, else none)
 //   --air FILE           air scan's projections_total.mha: also write projections_total_normalized.mha
+// A value of --mode, --shard or --reduce outside these sets prints the usage and exits before anything is read.
 // Everything runs through the pipelined scan driver (mcgpu_run_scan_multi, scan.cpp).
 #include <chrono>
 #include <cstdio>
@@ -33,6 +36,23 @@
 
 static double now_s() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+struct Choice {
+  const char* name;
+  int value;
+};
+static const Choice kModes[] = {{"fast", MCGPU_MODE_FAST}, {"fast64", MCGPU_MODE_FAST_F64}, {"compat", MCGPU_MODE_COMPAT}, {nullptr, 0}};
+static const Choice kShards[] = {{"histories", MCGPU_SHARD_HISTORIES}, {"projections", MCGPU_SHARD_PROJECTIONS}, {nullptr, 0}};
+static const Choice kReduces[] = {{"exchange", MCGPU_REDUCE_AUTO}, {"rccl", MCGPU_REDUCE_RCCL}, {nullptr, 0}};
+
+// the value named `arg` among `choices` of `option`; anything else prints the usage and exits
+static int choose(const char* option, const char* arg, const Choice* choices) {
+  for (const Choice* c = choices; c->name; ++c)
+    if (!strcmp(arg, c->name)) return c->value;
+  printf("\n\n   !!ERROR!! unknown value '%s' of %s\n   usage: MC-GPU_v1.3.x <input.in> [--mode fast|fast64|compat] [--gpus N] [--devices a,b,...]\n"
+         "          [--shard histories|projections] [--reduce exchange|rccl] [--no-output] [--stacks] [--crop N] [--air FILE]\n\n", arg, option);
+  exit(255);
 }
 
 int main(int argc, char** argv) {
@@ -61,10 +81,10 @@ int main(int argc, char** argv) {
     } else if (!strcmp(argv[i], "--stacks")) stacks = true;
     else if (!strcmp(argv[i], "--crop") && i + 1 < argc) crop = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--air") && i + 1 < argc) air = argv[++i];
-    else if (!strcmp(argv[i], "--mode") && i + 1 < argc) { ++i; mode = !strcmp(argv[i], "compat") ? MCGPU_MODE_COMPAT : (!strcmp(argv[i], "fast64") ? MCGPU_MODE_FAST_F64 : MCGPU_MODE_FAST); }
+    else if (!strcmp(argv[i], "--mode") && i + 1 < argc) { mode = choose(argv[i], argv[i + 1], kModes); ++i; }
     else if (!strcmp(argv[i], "--gpus") && i + 1 < argc) ngpu = atoi(argv[++i]);
-    else if (!strcmp(argv[i], "--shard") && i + 1 < argc) shard = !strcmp(argv[++i], "projections") ? MCGPU_SHARD_PROJECTIONS : MCGPU_SHARD_HISTORIES;
-    else if (!strcmp(argv[i], "--reduce") && i + 1 < argc) reduce = !strcmp(argv[++i], "rccl") ? MCGPU_REDUCE_RCCL : MCGPU_REDUCE_AUTO;
+    else if (!strcmp(argv[i], "--shard") && i + 1 < argc) { shard = choose(argv[i], argv[i + 1], kShards); ++i; }
+    else if (!strcmp(argv[i], "--reduce") && i + 1 < argc) { reduce = choose(argv[i], argv[i + 1], kReduces); ++i; }
     else if (!strcmp(argv[i], "--no-output")) write_out = false;
   }
   if (!device_list.empty()) ngpu = (int)device_list.size();

@@ -36,9 +36,10 @@
 
 #include "../../include/mcgpu_amd.h"
 #include "knobs.hpp"
-using mcgpu::knob_int;
 using mcgpu::knob_set;
 using mcgpu::knob_str;
+
+extern "C" void mcgpu_set_last_error_(const char* message);  // engine.cpp (not part of the public ABI)
 
 namespace {
 
@@ -63,570 +64,639 @@ struct ScanError {
     if (_rc != 0) throw ScanError{_rc, std::string(mcgpu_last_error())}; \
   } while (0)
 
-struct DeviceLane {  // per device
-  mcgpu_ctx* ctx = nullptr;
+// A HIP object that remembers its device and is released there.  make(dev) hands the create call its out-parameter.
+template <class T, hipError_t (*Release)(T)>
+struct Owned {
+  T h = nullptr;
   int dev = -1;
-  hipStream_t stream = nullptr;
-  mcgpu_exchange* x = nullptr;                 // this device's end of the tally exchange (owns the tally buffers)
-  void* planes_dev[2] = {nullptr, nullptr};    // float32 planes of the projections this device owns
-  hipStream_t copy = nullptr;                  // their download: a copy engine, beside the next tracking kernel
-  hipEvent_t finalized[2] = {nullptr, nullptr};  // planes_dev[b] has been written (tracking stream)
-  hipEvent_t done[2] = {nullptr, nullptr};     // planes of pinned buffer b are on the host (system-scope release; copy stream)
-  bool done_valid[2] = {false, false};
-  unsigned long long lo = 0, hi = 0;           // shard of the units of every projection
-  // RCCL route (reduce_rccl.cpp): the collective runs on a stream of its own, beside the next projection's kernel
-  hipStream_t reduce = nullptr;
-  void* tally[2] = {nullptr, nullptr};         // this device's tally of the projection with that parity
-  hipEvent_t tracked[2] = {nullptr, nullptr};  // the tracking kernel of that projection has run (tracking stream)
-  hipEvent_t reduced[2] = {nullptr, nullptr};  // the collective over that tally has run here (reduce stream)
-  bool reduced_valid[2] = {false, false};
+  Owned() = default;
+  Owned(const Owned&) = delete;
+  ~Owned() { reset(); }
+  T* make(int device) { reset(); dev = device; return &h; }
+  void reset() { if (h) { (void)hipSetDevice(dev); (void)Release(h); h = nullptr; } }
+  operator T() const { return h; }
+};
+using DeviceBuffer = Owned<void*, hipFree>;
+using PinnedBuffer = Owned<void*, hipHostFree>;
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+
+// ---- what both sharding paths derive from the contexts' configuration and the options, validated once
+struct ScanPlan {
+  std::vector<mcgpu_ctx*> ctxs;  // ctxs[0]: configuration, file names, calibration
+  std::vector<int> devs;         // device of every context
+  int mode = MCGPU_MODE_FAST, first = 0, range = 0, phase = 0;
+  long long nproj_all = 1, hist_in = 0, seed = 0, tpb = 128, hpt = 150, nx = 0, nz = 0, fast_scheduler = 0;
+  double d_angle = -1.0, angle0 = 0.0, roi0 = 0.0, roi1 = 0.0;
+  bool by_time = false;  // the input's history count is a time budget in seconds per projection
+  // offsets within the range of the projections this scan simulates, and their ordinal among ALL simulated projections of the
+  // trajectory (a projection-sharded scan takes every stride-th of them: the COMPAT seed still moves on once per simulated
+  // projection, whoever simulates it)
+  std::vector<int> sim, ord;
+  int cx = 0;                   // columns of the stacks (half-fan crop)
+  size_t words = 0, plane = 0;  // uint64 words of one tally, floats of one cropped plane
+  double sx = 0.0, sy = 0.0;    // MetaImage spacing
+  std::string folder;
+
+  int count() const { return (int)sim.size(); }
+  // projections outside the input's angular region of interest are not simulated (MC-GPU_v1.3.cu:670-677; like the
+  // reference, the test uses initial_angle + p * D_angle even when specific angles are given)
+  bool outside_roi(int p) const {
+    const double a = angle0 + p * d_angle;
+    return a < roi0 || a > roi1;
+  }
 };
 
-}  // namespace
-
-extern "C" void mcgpu_set_last_error_(const char* message);  // engine.cpp (not part of the public ABI)
-
-namespace {
-
-// An input history count below 95000 is a time budget in seconds per projection (MC-GPU_v1.3.cu:650-655, :689-809: the reference
-// runs a speed test and converts).  Two throw-away launches on `ctx`'s device; returns its rate in x-rays per second.
-double calibrate_rate(mcgpu_ctx* ctx, int dev, int projection, int mode, long long seed, long long hpt, size_t words, void** probe_image, hipStream_t stream) {
-  const unsigned long long probe = 4000000ULL;
-  const unsigned long long probe_units = mode == MCGPU_MODE_COMPAT ? (probe + (unsigned long long)hpt - 1) / (unsigned long long)hpt : probe;
-  float ms = 0.f;
-  HIP_OK(hipSetDevice(dev));
-  if (!*probe_image) HIP_OK(hipMalloc(probe_image, words * 8));
-  HIP_OK(hipMemsetAsync(*probe_image, 0, words * 8, stream));
-  for (int rep = 0; rep < 2; ++rep) {  // the first launch pays one-off costs
-    ABI_OK(mcgpu_launch_projection(ctx, projection, mode, (int)seed, 0, probe_units, (int)hpt, *probe_image, stream));
-    ABI_OK(mcgpu_last_kernel_ms(ctx, &ms));
+// Checks in this order: the mode, the devices, then the range and the stride / phase.
+ScanPlan plan_scan(mcgpu_ctx* const* ctxs, int n_ctx, const mcgpu_scan_options* opt) {
+  if (opt->mode != MCGPU_MODE_FAST && opt->mode != MCGPU_MODE_COMPAT && opt->mode != MCGPU_MODE_FAST_F64)
+    throw ScanError{-1, "!!ERROR!! mcgpu_run_scan: unknown mode " + std::to_string(opt->mode) +
+                            " (MCGPU_MODE_FAST, MCGPU_MODE_COMPAT or MCGPU_MODE_FAST_F64)"};
+  ScanPlan s;
+  s.mode = opt->mode;
+  s.ctxs.assign(ctxs, ctxs + n_ctx);
+  for (mcgpu_ctx* c : s.ctxs) {
+    long long dev = -1;
+    ABI_OK(mcgpu_config_i64(c, "device_id", &dev));
+    if (dev < 0) throw ScanError{-1, "!!ERROR!! mcgpu_run_scan: a context has no device"};
+    s.devs.push_back((int)dev);
   }
-  ABI_OK(mcgpu_dose_clear(ctx));
-  return (double)probe / (ms > 0.f ? ms * 1e-3 : 1e-3);
+  mcgpu_ctx* const ctx = ctxs[0];
+  double px_x = 0, px_z = 0;
+  const std::pair<const char*, long long*> i64[] = {{"num_projections", &s.nproj_all}, {"total_histories", &s.hist_in}, {"seed", &s.seed},
+      {"threads_per_block", &s.tpb}, {"histories_per_thread", &s.hpt}, {"num_pixels_x", &s.nx}, {"num_pixels_z", &s.nz}, {"fast_scheduler", &s.fast_scheduler}};
+  const std::pair<const char*, double*> f64[] = {{"pixel_size_x_mm", &px_x}, {"pixel_size_z_mm", &px_z}, {"D_angle", &s.d_angle},
+      {"initial_angle", &s.angle0}, {"angularROI_0", &s.roi0}, {"angularROI_1", &s.roi1}};
+  for (const auto& c : i64) ABI_OK(mcgpu_config_i64(ctx, c.first, c.second));
+  for (const auto& c : f64) ABI_OK(mcgpu_config_f64(ctx, c.first, c.second));
+  s.first = opt->first_projection > 0 ? opt->first_projection : 0;
+  s.range = (opt->num_projections > 0) ? opt->num_projections : (int)s.nproj_all - s.first;
+  if (s.first + s.range > s.nproj_all || s.range <= 0) throw ScanError{-1, "!!ERROR!! mcgpu_run_scan: projection range outside the trajectory"};
+  const int stride = opt->projection_stride > 1 ? opt->projection_stride : 1;
+  s.phase = stride > 1 ? opt->projection_phase : 0;
+  if (s.phase < 0 || s.phase >= stride) throw ScanError{-1, "!!ERROR!! mcgpu_run_scan: projection_phase outside [0, projection_stride)"};
+  if (opt->shared_stacks && !opt->slice_of_projection) throw ScanError{-1, "!!ERROR!! mcgpu_run_scan: shared_stacks needs slice_of_projection"};
+  int before = 0;  // simulated projections of the trajectory before the range
+  for (int p = 0; p < s.first; ++p) before += !s.outside_roi(p);
+  for (int k = 0, n_sim = 0; k < s.range; ++k)
+    if (!s.outside_roi(s.first + k)) {
+      if (n_sim % stride == s.phase) { s.sim.push_back(k); s.ord.push_back(before + n_sim); }
+      ++n_sim;
+    }
+  s.by_time = !opt->histories_per_projection && s.hist_in < 95000;
+  s.cx = (opt->crop_nx > 0 && opt->crop_nx < s.nx) ? opt->crop_nx : (int)s.nx;
+  s.words = (size_t)4 * s.nx * s.nz;
+  s.plane = (size_t)s.cx * s.nz;
+  s.sx = opt->pixel_spacing_x > 0 ? opt->pixel_spacing_x : px_x;
+  s.sy = opt->pixel_spacing_y > 0 ? opt->pixel_spacing_y : px_z;
+  if (opt->output_folder) s.folder = opt->output_folder;
+  else {
+    char name[1024];
+    ABI_OK(mcgpu_projection_file_name(ctx, 0, name, sizeof name));
+    s.folder = name;
+    const size_t slash = s.folder.find_last_of('/');
+    s.folder = slash == std::string::npos ? "." : s.folder.substr(0, slash);
+  }
+  return s;
 }
 
-// One scan over n_ctx devices that share every projection's histories (n_ctx = 1: the plain single-device pipeline).
-// `use_rccl`: the per-device tallies of a projection are summed by one ncclReduce to the projection's owner (reduce_rccl.cpp) instead
-// of through the tally exchange.
-int run_scan_sharing_histories(mcgpu_ctx* const* ctxs, int n_ctx, const mcgpu_scan_options* opt, mcgpu_scan_report* report, bool use_rccl = false) {
-  std::vector<DeviceLane> D((size_t)n_ctx);
-  mcgpu_rccl* rccl = nullptr;
-  float* planes_host[2] = {nullptr, nullptr};
-  uint64_t* image_host[2] = {nullptr, nullptr};
-  void* probe_image = nullptr;  // tally of the throw-away launches (time calibration, preset choice)
-  std::vector<unsigned char> mailboxes;  // host region of the exchange (contexts of one process: plain memory)
-  mcgpu_stack* stacks[3] = {nullptr, nullptr, nullptr};
-  std::thread writer;
-  struct Shared {
-    std::mutex mu;
-    std::condition_variable cv;
-    int queued = 0, written = 0;  // projections handed to / finished by the writer
-    bool abort = false;
-    std::string error;
-    double writer_s = 0.0;
-    // ASCII files of the device formatter: one worker per slot, so that several files are written side by side (writes
-    // to ONE file do not scale with threads -- they serialise on its inode lock -- writes to different files do)
-    bool ascii_busy[kAsciiSlots] = {};
-    int ascii_p[kAsciiSlots] = {};
-    mcgpu_ctx* ascii_ctx[kAsciiSlots] = {};  // the context (device) that formatted the slot's text
-    double ascii_seconds[kAsciiSlots] = {};
-    bool ascii_quit = false;
-  } sh;
-  std::thread ascii_worker[kAsciiSlots];
-  int n_ascii = kAsciiSlots;  // formatter slots in use = files written side by side
-  mcgpu_ctx* ctx = ctxs[0];
-  int rc = 0;
-  try {
-    long long nproj_all = 1, hist_in = 0, seed = 0, tpb = 128, hpt = 150, nx = 0, nz = 0;
-    ABI_OK(mcgpu_config_i64(ctx, "num_projections", &nproj_all));
-    ABI_OK(mcgpu_config_i64(ctx, "total_histories", &hist_in));
-    ABI_OK(mcgpu_config_i64(ctx, "seed", &seed));
-    ABI_OK(mcgpu_config_i64(ctx, "threads_per_block", &tpb));
-    ABI_OK(mcgpu_config_i64(ctx, "histories_per_thread", &hpt));
-    ABI_OK(mcgpu_config_i64(ctx, "num_pixels_x", &nx));
-    ABI_OK(mcgpu_config_i64(ctx, "num_pixels_z", &nz));
-    for (int g = 0; g < n_ctx; ++g) {
-      long long dev = -1;
-      if (!ctxs[g]) throw ScanError{-1, "!!ERROR!! mcgpu_run_scan: null context"};
-      ABI_OK(mcgpu_config_i64(ctxs[g], "device_id", &dev));
-      if (dev < 0) throw ScanError{-1, "!!ERROR!! mcgpu_run_scan: a context has no device"};
-      D[g].ctx = ctxs[g];
-      D[g].dev = (int)dev;
-    }
-    double px_x = 0, px_z = 0;
-    ABI_OK(mcgpu_config_f64(ctx, "pixel_size_x_mm", &px_x));
-    ABI_OK(mcgpu_config_f64(ctx, "pixel_size_z_mm", &px_z));
-    const int mode = opt->mode == MCGPU_MODE_COMPAT ? MCGPU_MODE_COMPAT : (opt->mode == MCGPU_MODE_FAST_F64 ? MCGPU_MODE_FAST_F64 : MCGPU_MODE_FAST);
-    const int first = opt->first_projection > 0 ? opt->first_projection : 0;
-    const int range = (opt->num_projections > 0) ? opt->num_projections : (int)nproj_all - first;
-    if (first + range > nproj_all || range <= 0) throw ScanError{-1, "!!ERROR!! mcgpu_run_scan: projection range outside the trajectory"};
-    // projections outside the input's angular region of interest are not simulated (MC-GPU_v1.3.cu:670-677; like the
-    // reference, the test uses initial_angle + p * D_angle even when specific angles are given)
-    double d_angle = -1.0, angle0 = 0.0, roi0 = 0.0, roi1 = 0.0;
-    ABI_OK(mcgpu_config_f64(ctx, "D_angle", &d_angle));
-    ABI_OK(mcgpu_config_f64(ctx, "initial_angle", &angle0));
-    ABI_OK(mcgpu_config_f64(ctx, "angularROI_0", &roi0));
-    ABI_OK(mcgpu_config_f64(ctx, "angularROI_1", &roi1));
-    auto outside_roi = [&](int p) { const double a = angle0 + p * d_angle; return a < roi0 || a > roi1; };
-    // offsets within the range of the projections this scan simulates, and their ordinal among ALL simulated projections of the
-    // range (a projection-sharded scan takes every stride-th of them: the COMPAT seed still moves on once per simulated
-    // projection, whoever simulates it)
-    const int stride = opt->projection_stride > 1 ? opt->projection_stride : 1, phase = stride > 1 ? opt->projection_phase : 0;
-    if (phase < 0 || phase >= stride) throw ScanError{-1, "!!ERROR!! mcgpu_run_scan: projection_phase outside [0, projection_stride)"};
-    std::vector<int> sim, ord;
-    {
-      int n_sim = 0;
-      for (int k = 0; k < range; ++k)
-        if (!outside_roi(first + k)) {
-          if (n_sim % stride == phase) { sim.push_back(k); ord.push_back(n_sim); }
-          ++n_sim;
-        }
-    }
-    const int count = (int)sim.size();
-    unsigned long long H = opt->histories_per_projection ? opt->histories_per_projection : (unsigned long long)hist_in;
-    // An input value below 95000 is a time budget in seconds per projection, not a history count (MC-GPU_v1.3.cu:650-655,
-    // :689-809: the reference runs a speed test and converts).  Calibrate on device 0 with a throw-away launch.
-    const bool by_time = !opt->histories_per_projection && hist_in < 95000;
-    int blocks = 1, hpt_eff = (int)hpt;
-    unsigned long long total = H;
-    if (mode == MCGPU_MODE_COMPAT) ABI_OK(mcgpu_launch_shape(H, (int)tpb, (int)hpt, &blocks, &hpt_eff, &total));
-    unsigned long long units = mode == MCGPU_MODE_COMPAT ? (unsigned long long)blocks * (unsigned long long)tpb : total;
-    const int cx = (opt->crop_nx > 0 && opt->crop_nx < nx) ? opt->crop_nx : (int)nx;
-    const size_t words = (size_t)4 * nx * nz, plane = (size_t)cx * nz;
-    const double sx = opt->pixel_spacing_x > 0 ? opt->pixel_spacing_x : px_x, sy = opt->pixel_spacing_y > 0 ? opt->pixel_spacing_y : px_z;
-    std::string folder;
-    if (opt->output_folder) folder = opt->output_folder;
-    else {
-      char name[1024];
-      ABI_OK(mcgpu_projection_file_name(ctx, 0, name, sizeof name));
-      folder = name;
-      const size_t slash = folder.find_last_of('/');
-      folder = slash == std::string::npos ? "." : folder.substr(0, slash);
-    }
+// Launch shape of H histories per projection: COMPAT rounds to the reference's grid and launches blocks * tpb units.
+struct Shape { int blocks, hpt; unsigned long long total, units; };
+Shape launch_shape(const ScanPlan& plan, unsigned long long H) {
+  Shape s{1, (int)plan.hpt, H, H};
+  if (plan.mode == MCGPU_MODE_COMPAT) {
+    ABI_OK(mcgpu_launch_shape(H, (int)plan.tpb, (int)plan.hpt, &s.blocks, &s.hpt, &s.total));
+    s.units = (unsigned long long)s.blocks * (unsigned long long)plan.tpb;
+  }
+  return s;
+}
 
-    // ---- device resources
-    // pinned buffers are read by the writer thread and filled from whichever device owns the projection: portable
-    const unsigned int pinned_flags = (knob_set("MCGPU_PINNED_COHERENT") ? hipHostMallocDefault : hipHostMallocNonCoherent) | hipHostMallocPortable;
-    const bool ascii_on_host = knob_set("MCGPU_ASCII_HOST");  // A/B: the threaded host formatter of report.cpp
-    if (const char* w = knob_str("MCGPU_ASCII_WRITERS")) n_ascii = std::min(std::max(atoi(w), 1), kAsciiSlots);
-    const bool single = (n_ctx == 1);
-    int policy = MCGPU_EXCHANGE_LOCAL | MCGPU_EXCHANGE_ROTATE;
+// An input history count below 95000 is a time budget in seconds per projection (MC-GPU_v1.3.cu:650-655, :689-809: the reference
+// runs a speed test and converts).  Two throw-away launches on the first device measure its rate.  n_share devices share every
+// projection's histories (their rates add up); `per_device`: every device simulates whole projections alone.
+unsigned long long budget_histories(const ScanPlan& plan, hipStream_t stream, int n_share, bool per_device, bool progress) {
+  const unsigned long long probe = 4000000ULL;
+  const unsigned long long probe_units = plan.mode == MCGPU_MODE_COMPAT ? (probe + (unsigned long long)plan.hpt - 1) / (unsigned long long)plan.hpt : probe;
+  DeviceBuffer tally;
+  float ms = 0.f;
+  HIP_OK(hipSetDevice(plan.devs[0]));
+  HIP_OK(hipMalloc(tally.make(plan.devs[0]), plan.words * 8));
+  HIP_OK(hipMemsetAsync(tally, 0, plan.words * 8, stream));
+  for (int rep = 0; rep < 2; ++rep) {  // the first launch pays one-off costs
+    ABI_OK(mcgpu_launch_projection(plan.ctxs[0], plan.first, plan.mode, (int)plan.seed, 0, probe_units, (int)plan.hpt, tally, stream));
+    ABI_OK(mcgpu_last_kernel_ms(plan.ctxs[0], &ms));
+  }
+  ABI_OK(mcgpu_dose_clear(plan.ctxs[0]));
+  HIP_OK(hipStreamSynchronize(stream));
+  const double rate = (double)probe / (ms > 0.f ? ms * 1e-3 : 1e-3) * n_share;
+  const unsigned long long H = std::max(100000ULL, (unsigned long long)(rate * (double)plan.hist_in));
+  if (progress) {
+    printf("       Time-limited run: %lld s per projection at %.3e x-rays/s%s -> %llu histories per projection\n", plan.hist_in, rate,
+           per_device ? " per device" : "", per_device ? H : launch_shape(plan, H).total);
+    fflush(stdout);
+  }
+  return H;
+}
+
+// FAST batching thresholds: a few presets timed with throw-away launches on the first simulated projection (the best one
+// differs between geometries by 5-7 %; the tallies do not depend on the choice), then set on every context.  Skipped for short
+// scans and when the environment pins the knobs; the presets are per-wave pool thresholds, the workgroup-level pool
+// (fast_scheduler) keeps its own defaults.
+void choose_fast_preset(const ScanPlan& plan, unsigned long long total, hipStream_t stream, bool progress) {
+  if (plan.mode == MCGPU_MODE_COMPAT || plan.fast_scheduler != 0 || total < 20000000ULL || knob_set("MCGPU_THRESH_COMPTON") ||
+      knob_set("MCGPU_THRESH_NEW") || knob_set("MCGPU_SWAP_BATCH") || knob_set("MCGPU_NO_AUTOTUNE"))
+    return;
+  static const int presets[3][5] = {{40, 12, 44, 12, 40}, {32, 8, 36, 12, 40}, {36, 16, 44, 12, 44}};  // profiles/r05o_*, r05p_*
+  const unsigned long long probe = 6000000ULL;
+  mcgpu_ctx* const ctx = plan.ctxs[0];
+  const int p = plan.first + (plan.count() > 0 ? plan.sim[0] : 0);
+  DeviceBuffer tally;
+  HIP_OK(hipSetDevice(plan.devs[0]));
+  HIP_OK(hipMalloc(tally.make(plan.devs[0]), plan.words * 8));
+  HIP_OK(hipMemsetAsync(tally, 0, plan.words * 8, stream));
+  int best = 0;
+  float best_ms = 1e30f;
+  for (int c = 0; c < 3; ++c) {
+    ABI_OK(mcgpu_set_fast_schedule(ctx, presets[c][0], presets[c][1], presets[c][2], presets[c][3], presets[c][4]));
+    float ms = 0.f, fastest = 1e30f;
+    for (int rep = 0; rep < 3; ++rep) {  // the first launch of a preset pays the parameter upload
+      ABI_OK(mcgpu_launch_projection(ctx, p, plan.mode, (int)plan.seed, 0, probe, (int)plan.hpt, tally, stream));
+      ABI_OK(mcgpu_last_kernel_ms(ctx, &ms));
+      if (rep > 0 && ms < fastest) fastest = ms;
+    }
+    if (fastest < best_ms) { best_ms = fastest; best = c; }
+  }
+  for (mcgpu_ctx* c : plan.ctxs) ABI_OK(mcgpu_set_fast_schedule(c, presets[best][0], presets[best][1], presets[best][2], presets[best][3], presets[best][4]));
+  HIP_OK(hipSetDevice(plan.devs[0]));
+  ABI_OK(mcgpu_dose_clear(ctx));
+  if (progress) {
+    printf("       FAST batching preset %d of 3 (thresholds %d/%d/%d, %d, %d)\n", best + 1, presets[best][0], presets[best][1], presets[best][2],
+           presets[best][3], presets[best][4]);
+    fflush(stdout);
+  }
+  HIP_OK(hipStreamSynchronize(stream));
+}
+
+// f(0), f(1), f(2) side by side (page-cache work on three different files): 0, or the code of the first that failed with its
+// message as this thread's last error.
+template <class F>
+int side_by_side(const F& f) {
+  int rc[3] = {0, 0, 0};
+  std::string err[3];
+  auto one = [&](int k) { if ((rc[k] = f(k)) != 0) err[k] = mcgpu_last_error(); };  // the last error is per thread
+  std::thread side[2] = {std::thread(one, 1), std::thread(one, 2)};
+  one(0);
+  for (auto& t : side) t.join();
+  for (int k = 0; k < 3; ++k)
+    if (rc[k] != 0) { mcgpu_set_last_error_(err[k].c_str()); return rc[k]; }
+  return 0;
+}
+
+// The scan's own MetaImage stacks {total, unscattered, scattered}: stacks that are not finished are closed when this goes.
+struct OutputStacks {
+  mcgpu_stack* stack[3] = {nullptr, nullptr, nullptr};
+  ~OutputStacks() {
+    for (mcgpu_stack* st : stack)
+      if (st) (void)mcgpu_stack_finish(st, 0, nullptr);  // error path: close the files
+  }
+  bool open() const { return stack[0] != nullptr; }
+  void create(const ScanPlan& plan) {
+    static const char* kNames[3] = {"projections_total.mha", "projections_unscattered.mha", "projections_scattered.mha"};
+    for (int k = 0; k < 3; ++k) ABI_OK(mcgpu_stack_create((plan.folder + "/" + kNames[k]).c_str(), plan.cx, (int)plan.nz, plan.count(), plan.sx, plan.sy, &stack[k]));
+  }
+  // a projection's three planes, side by side (each append scans its plane for zeros and copies it into the page cache)
+  int append(const float* planes, size_t plane) {
+    return side_by_side([&](int k) { return mcgpu_stack_append(stack[k], planes + (size_t)k * plane); });
+  }
+  // zero replacement and close side by side, then the air normalisation of the total stack
+  void finish(const ScanPlan& plan, const mcgpu_scan_options* opt, float repl[3]) {
+    mcgpu_stack* st[3] = {stack[0], stack[1], stack[2]};
+    stack[0] = stack[1] = stack[2] = nullptr;
+    if (const int rc = side_by_side([&](int k) { return mcgpu_stack_finish(st[k], 1, &repl[k]); })) throw ScanError{rc, mcgpu_last_error()};
+    if (opt->air_stack)
+      ABI_OK(mcgpu_normalize_stack((plan.folder + "/projections_total.mha").c_str(), opt->air_stack, opt->air_sigma_y, opt->air_sigma_x,
+                                   (plan.folder + "/projections_total_normalized.mha").c_str(), plan.sx, plan.sy));
+  }
+};
+
+// The host end of the pipeline.  The writer thread takes the projections in order as they are published: it waits for their
+// download, writes the planes to the stacks and the ASCII file (host formatter) or hands the file to the worker of its formatter
+// slot.  One worker per slot, so that several files are written side by side (writes to ONE file do not scale with threads --
+// they serialise on its inode lock -- writes to different files do).
+struct Output {
+  struct Projection {                 // what the writer needs of one projection, final when it is published
+    int p = 0, offset = 0;            // index in the trajectory; offset within the scan's range
+    int dev = -1;                     // the owner device, whose event `downloaded` says the planes (and image) are on the host
+    hipEvent_t downloaded = nullptr;
+    const float* planes = nullptr;
+    const uint64_t* image = nullptr;  // the tally (host ASCII formatter only)
+    mcgpu_ctx* formatter = nullptr;   // the context whose formatter slot holds the device-formatted text
+    double seconds = 0.0;             // kernel time
+  };
+  const mcgpu_scan_options* const opt;
+  mcgpu_ctx* const ctx;
+  const size_t plane;
+  OutputStacks* const stacks;
+  const bool ascii_on_host = knob_set("MCGPU_ASCII_HOST");  // A/B: the threaded host formatter of report.cpp
+  const int n_ascii = [] {  // formatter slots in use = files written side by side
+    const char* w = knob_str("MCGPU_ASCII_WRITERS");
+    return w ? std::min(std::max(atoi(w), 1), kAsciiSlots) : kAsciiSlots;
+  }();
+  unsigned long long total = 0;
+  std::thread writer, ascii_worker[kAsciiSlots];
+  std::mutex mu;  // guards everything below
+  std::condition_variable cv;
+  std::vector<Projection> queue;
+  int queued = 0, written = 0;  // projections handed to / finished by the writer
+  bool aborted = false, ascii_quit = false;
+  std::string error;
+  double busy_s = 0.0;
+  bool ascii_busy[kAsciiSlots] = {};
+  Projection ascii[kAsciiSlots];
+
+  ~Output() { abort(); }
+  void start(int count, unsigned long long total_histories) {
+    total = total_histories;
+    queue.assign((size_t)count, Projection{});
+    if (opt->write_ascii && !ascii_on_host)
+      for (int a = 0; a < n_ascii; ++a) ascii_worker[a] = std::thread(&Output::write_ascii, this, a);
+    writer = std::thread(&Output::write_all, this);
+  }
+  // Pinned buffer j & 1 is free once projection j - 2 has been written.  Formatter slot j % n_ascii was last used by projection
+  // j - n_ascii: that one must have been HANDED to its worker (the writer sets the slot busy when it has written the
+  // projection's stacks, together with `written`) and the worker must be done.  With one slot the previous projection itself is
+  // the slot's last user, so `written >= j - 1` is not enough (it would let projection j be formatted over the text of j - 1
+  // before j - 1 was even handed over).
+  void wait_for_buffers(int j) {
+    const int handed = j - std::min(1, n_ascii - 1);
+    std::unique_lock<std::mutex> lk(mu);
+    cv.wait(lk, [&] { return (written >= handed && !ascii_busy[j % n_ascii]) || aborted; });
+    if (aborted) throw ScanError{-3, error};
+  }
+  void publish(int j, const Projection& pr) {
+    std::lock_guard<std::mutex> lk(mu);
+    queue[(size_t)j] = pr;
+    queued = j + 1;
+    cv.notify_all();
+  }
+  // normal end: the writer is done, then every worker finishes the file it holds; the first failure is thrown
+  void join() {
+    writer.join();
+    stop(ascii_quit);
+    std::lock_guard<std::mutex> lk(mu);
+    if (aborted) throw ScanError{-3, error};
+  }
+  void abort() { stop(aborted); }  // error path: the threads stop where they are
+  void stop(bool& flag) {
+    { std::lock_guard<std::mutex> lk(mu); flag = true; cv.notify_all(); }
+    if (writer.joinable()) writer.join();
+    for (auto& w : ascii_worker)
+      if (w.joinable()) w.join();
+  }
+  void write_all() {
+    for (int i = 0; i < (int)queue.size(); ++i) {
+      Projection pr;
+      {
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return queued > i || aborted; });
+        if (aborted) return;
+        pr = queue[(size_t)i];
+      }
+      if (hipSetDevice(pr.dev) != hipSuccess || hipEventSynchronize(pr.downloaded) != hipSuccess) {
+        std::lock_guard<std::mutex> lk(mu);
+        error = "!!HIP ERROR!! waiting for projection results";
+        aborted = true;
+        cv.notify_all();
+        return;
+      }
+      const double tw0 = now_s();
+      int wrc = 0;
+      if (opt->shared_stacks)
+        for (int k = 0; k < 3 && wrc == 0; ++k)
+          wrc = mcgpu_stack_write_slice(opt->shared_stacks[k], opt->slice_of_projection[pr.offset], pr.planes + (size_t)k * plane);
+      else if (opt->write_stacks)
+        wrc = stacks->append(pr.planes, plane);
+      if (wrc == 0 && opt->write_ascii && ascii_on_host) wrc = mcgpu_write_projection(ctx, pr.p, pr.image, total, pr.seconds, nullptr);
+      std::lock_guard<std::mutex> lk(mu);
+      if (wrc == 0 && opt->write_ascii && !ascii_on_host) {  // the slot is free: the projection loop waited for that before it formatted into it
+        ascii[i % n_ascii] = pr;
+        ascii_busy[i % n_ascii] = true;
+      }
+      busy_s += now_s() - tw0;
+      if (wrc != 0) { error = mcgpu_last_error(); aborted = true; }
+      written = i + 1;
+      cv.notify_all();
+      if (wrc != 0) return;
+    }
+  }
+  void write_ascii(int a) {
+    for (;;) {
+      Projection pr;
+      {
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return ascii_busy[a] || ascii_quit || aborted; });
+        if (!ascii_busy[a]) return;
+        pr = ascii[a];
+      }
+      const double tw0 = now_s();
+      const int wrc = mcgpu_write_formatted_projection(pr.formatter, pr.p, a, total, pr.seconds, nullptr);
+      std::lock_guard<std::mutex> lk(mu);
+      busy_s += now_s() - tw0;
+      if (wrc != 0) { error = mcgpu_last_error(); aborted = true; }
+      ascii_busy[a] = false;
+      cv.notify_all();
+      if (wrc != 0) return;
+    }
+  }
+};
+
+// One scan over n devices that share every projection's histories (n = 1: the plain single-device pipeline).  `use_rccl`: the
+// per-device tallies of a projection are summed by one ncclReduce to the projection's owner (reduce_rccl.cpp) instead of through
+// the tally exchange.
+struct HistoryScan {
+  struct Lane {  // per device
+    mcgpu_ctx* ctx = nullptr;
+    int dev = -1;
+    Stream stream;                        // the tracking stream
+    mcgpu_exchange* x = nullptr;          // this device's end of the tally exchange (owns the tally buffers)
+    DeviceBuffer planes_dev[2];           // float32 planes of the projections this device owns
+    Stream copy;                          // their download: a copy engine, beside the next tracking kernel
+    Event finalized[2];                   // planes_dev[b] has been written (tracking stream)
+    Event done[2];                        // planes of pinned buffer b are on the host (system-scope release; copy stream)
+    bool done_valid[2] = {false, false};
+    unsigned long long lo = 0, hi = 0;    // shard of the units of every projection
+    // RCCL route (reduce_rccl.cpp): the collective runs on a stream of its own, beside the next projection's kernel
+    Stream reduce;
+    void* tally[2] = {nullptr, nullptr};  // this device's tally of the projection with that parity
+    Event tracked[2];                     // the tracking kernel of that projection has run (tracking stream)
+    Event reduced[2];                     // the collective over that tally has run here (reduce stream)
+    bool reduced_valid[2] = {false, false};
+  };
+  const mcgpu_scan_options* const opt;
+  const ScanPlan plan;
+  const int n;
+  const bool use_rccl;
+  int policy = MCGPU_EXCHANGE_LOCAL | MCGPU_EXCHANGE_ROTATE;
+  Shape shape{};
+  std::vector<unsigned char> mailboxes;  // host region of the exchange (contexts of one process: plain memory)
+  std::vector<Lane> lanes;
+  mcgpu_rccl* rccl = nullptr;
+  PinnedBuffer planes_host[2], image_host[2];
+  std::vector<float> kms;  // kernel time per projection (final before the projection is published)
+  OutputStacks stacks;
+  Output out{opt, plan.ctxs[0], plan.plane, &stacks};
+
+  HistoryScan(mcgpu_ctx* const* ctxs, int n_ctx, const mcgpu_scan_options* o, bool rccl_route)
+      : opt(o), plan(plan_scan(ctxs, n_ctx, o)), n(n_ctx), use_rccl(rccl_route), lanes((size_t)n_ctx) {
     if (const char* v = knob_str("MCGPU_EXCHANGE_POLICY")) policy = MCGPU_EXCHANGE_LOCAL | (atoi(v) ? MCGPU_EXCHANGE_ROTATE : 0);
-    mailboxes.assign(mcgpu_exchange_shared_bytes(n_ctx) * (size_t)(use_rccl ? n_ctx : 1), 0);
-    void* const mailbox_region = mailboxes.data();
-    const bool rotate_owner = (policy & MCGPU_EXCHANGE_ROTATE) != 0;
-    // owner of projection j of this scan: the device that holds the summed tally, finalizes and downloads it
-    auto owner_of = [&](int j) { return use_rccl ? (rotate_owner ? j % n_ctx : 0) : mcgpu_exchange_owner(D[0].x, j); };
-    for (int g = 0; g < n_ctx; ++g) {
-      HIP_OK(hipSetDevice(D[g].dev));
-      HIP_OK(hipStreamCreate(&D[g].stream));
-      if (use_rccl) {
-        // every device keeps its double-buffered tally in an exchange end of its own (a world of one: begin / submit / collect stay local)
-        ABI_OK(mcgpu_exchange_create(D[g].dev, 0, 1, words, MCGPU_EXCHANGE_LOCAL, mailboxes.data() + (size_t)g * mcgpu_exchange_shared_bytes(n_ctx), &D[g].x));
-        HIP_OK(hipStreamCreateWithFlags(&D[g].reduce, hipStreamNonBlocking));
-        for (int b = 0; b < 2; ++b) {
-          HIP_OK(hipEventCreateWithFlags(&D[g].tracked[b], hipEventDisableTiming));
-          HIP_OK(hipEventCreateWithFlags(&D[g].reduced[b], hipEventDisableTiming));
-        }
-      } else {
-        ABI_OK(mcgpu_exchange_create(D[g].dev, g, n_ctx, words, policy, mailbox_region, &D[g].x));
+    for (int g = 0; g < n; ++g) { lanes[g].ctx = ctxs[g]; lanes[g].dev = plan.devs[g]; }
+  }
+
+  // Teardown, error path and normal end alike, in the one order that is safe:
+  //   1. stop the writer and ASCII threads, before anything they read is freed;
+  //   2. drain every stream of every device;
+  //   3. destroy the RCCL communicator;
+  //   4. free the buffers and events;
+  //   5. destroy the exchange ends -- only now that EVERY device has drained: peers push into their memory;
+  //   6. destroy the tracking streams.
+  ~HistoryScan() {
+    out.abort();
+    for (Lane& l : lanes) {
+      if (!l.stream) continue;
+      (void)hipSetDevice(l.dev);
+      for (hipStream_t s : {(hipStream_t)l.stream, (hipStream_t)l.copy, (hipStream_t)l.reduce})
+        if (s) (void)hipStreamSynchronize(s);
+    }
+    if (rccl) mcgpu_rccl_destroy(rccl);
+    for (int b = 0; b < 2; ++b) {
+      planes_host[b].reset();
+      image_host[b].reset();
+      for (Lane& l : lanes) { l.planes_dev[b].reset(); l.done[b].reset(); l.finalized[b].reset(); l.tracked[b].reset(); l.reduced[b].reset(); }
+    }
+    for (Lane& l : lanes) { l.copy.reset(); l.reduce.reset(); }
+    for (Lane& l : lanes)
+      if (l.x) mcgpu_exchange_destroy(l.x);
+    for (Lane& l : lanes) l.stream.reset();
+  }
+
+  // Tracking streams and exchange ends; then the route of the sum, tried before anything is simulated or written.
+  void connect() {
+    const size_t shared_bytes = mcgpu_exchange_shared_bytes(n);
+    mailboxes.assign(shared_bytes * (size_t)(use_rccl ? n : 1), 0);
+    for (int g = 0; g < n; ++g) {
+      Lane& l = lanes[g];
+      HIP_OK(hipSetDevice(l.dev));
+      HIP_OK(hipStreamCreate(l.stream.make(l.dev)));
+      if (!use_rccl) {
+        ABI_OK(mcgpu_exchange_create(l.dev, g, n, plan.words, policy, mailboxes.data(), &l.x));
+        continue;
+      }
+      // every device keeps its double-buffered tally in an exchange end of its own (a world of one: begin / submit / collect stay local)
+      ABI_OK(mcgpu_exchange_create(l.dev, 0, 1, plan.words, MCGPU_EXCHANGE_LOCAL, mailboxes.data() + (size_t)g * shared_bytes, &l.x));
+      HIP_OK(hipStreamCreateWithFlags(l.reduce.make(l.dev), hipStreamNonBlocking));
+      for (int b = 0; b < 2; ++b) {
+        HIP_OK(hipEventCreateWithFlags(l.tracked[b].make(l.dev), hipEventDisableTiming));
+        HIP_OK(hipEventCreateWithFlags(l.reduced[b].make(l.dev), hipEventDisableTiming));
       }
     }
     if (use_rccl) {
-      std::vector<int> devs((size_t)n_ctx);
-      for (int g = 0; g < n_ctx; ++g) devs[(size_t)g] = D[g].dev;
-      if (mcgpu_rccl_create(devs.data(), n_ctx, &rccl) != 0) throw ScanError{kRcclUnavailable, mcgpu_last_error()};
-    } else try {
+      if (mcgpu_rccl_create(plan.devs.data(), n, &rccl) != 0) throw ScanError{kRcclUnavailable, mcgpu_last_error()};
+      return;
+    }
+    try {
       // peer access between every pair of devices, and one small copy-engine transfer into every peer's landing buffer: a node
       // on which either fails is reported with kExchangeUnavailable BEFORE anything has been simulated or written, and
       // mcgpu_run_scan_multi then shards the scan by projection instead (same output bytes, nothing crosses between devices)
-      if (n_ctx > 1 && knob_set("MCGPU_EXCHANGE_FAIL_PROBE")) throw ScanError{-1, "!!ERROR!! tally exchange: probe failure requested (MCGPU_EXCHANGE_FAIL_PROBE)"};  // test hook
-      for (int g = 0; g < n_ctx; ++g)
-        for (int h = 0; h < n_ctx; ++h)
-          if (g != h) ABI_OK(mcgpu_exchange_connect_local(D[g].x, D[h].x));
-      for (int g = 0; g < n_ctx; ++g) ABI_OK(mcgpu_exchange_probe(D[g].x));
+      if (n > 1 && knob_set("MCGPU_EXCHANGE_FAIL_PROBE")) throw ScanError{-1, "!!ERROR!! tally exchange: probe failure requested (MCGPU_EXCHANGE_FAIL_PROBE)"};  // test hook
+      for (int g = 0; g < n; ++g)
+        for (int h = 0; h < n; ++h)
+          if (g != h) ABI_OK(mcgpu_exchange_connect_local(lanes[g].x, lanes[h].x));
+      for (Lane& l : lanes) ABI_OK(mcgpu_exchange_probe(l.x));
     } catch (const ScanError& e) {
       throw ScanError{kExchangeUnavailable, e.msg};
     }
-    HIP_OK(hipSetDevice(D[0].dev));
-    if (by_time) {
-      const double rate = calibrate_rate(ctx, D[0].dev, first, mode, seed, hpt, words, &probe_image, D[0].stream) * n_ctx;
-      H = (unsigned long long)(rate * (double)hist_in);
-      if (H < 100000ULL) H = 100000ULL;
-      total = H;
-      if (mode == MCGPU_MODE_COMPAT) ABI_OK(mcgpu_launch_shape(H, (int)tpb, (int)hpt, &blocks, &hpt_eff, &total));
-      units = mode == MCGPU_MODE_COMPAT ? (unsigned long long)blocks * (unsigned long long)tpb : total;
-      if (opt->progress) {
-        printf("       Time-limited run: %lld s per projection at %.3e x-rays/s -> %llu histories per projection\n", hist_in, rate, total);
-        fflush(stdout);
-      }
-    }
-    // FAST batching thresholds: a few presets timed with throw-away launches on the first simulated projection (the best
-    // one differs between geometries by 5-7 %; the tallies do not depend on the choice).  Skipped for short scans and when
-    // the environment pins the knobs.
-    long long fast_scheduler = 0;  // the presets are per-wave pool thresholds; the workgroup-level pool keeps its own defaults
-    ABI_OK(mcgpu_config_i64(ctx, "fast_scheduler", &fast_scheduler));
-    if (mode != MCGPU_MODE_COMPAT && fast_scheduler == 0 && total >= 20000000ULL && !knob_set("MCGPU_THRESH_COMPTON") && !knob_set("MCGPU_THRESH_NEW") &&
-        !knob_set("MCGPU_SWAP_BATCH") && !knob_set("MCGPU_NO_AUTOTUNE")) {
-      static const int presets[3][5] = {{40, 12, 44, 12, 40}, {32, 8, 36, 12, 40}, {36, 16, 44, 12, 44}};  // profiles/r05o_*, r05p_*
-      const unsigned long long probe = 6000000ULL;
-      if (!probe_image) HIP_OK(hipMalloc(&probe_image, words * 8));
-      HIP_OK(hipMemsetAsync(probe_image, 0, words * 8, D[0].stream));
-      int best = 0;
-      float best_ms = 1e30f;
-      for (int c = 0; c < 3; ++c) {
-        ABI_OK(mcgpu_set_fast_schedule(ctx, presets[c][0], presets[c][1], presets[c][2], presets[c][3], presets[c][4]));
-        float ms = 0.f, fastest = 1e30f;
-        for (int rep = 0; rep < 3; ++rep) {  // the first launch of a preset pays the parameter upload
-          ABI_OK(mcgpu_launch_projection(ctx, first + (count > 0 ? sim[0] : 0), mode, (int)seed, 0, probe, (int)hpt, probe_image, D[0].stream));
-          ABI_OK(mcgpu_last_kernel_ms(ctx, &ms));
-          if (rep > 0 && ms < fastest) fastest = ms;
-        }
-        if (fastest < best_ms) { best_ms = fastest; best = c; }
-      }
-      for (int g = 0; g < n_ctx; ++g)
-        ABI_OK(mcgpu_set_fast_schedule(D[g].ctx, presets[best][0], presets[best][1], presets[best][2], presets[best][3], presets[best][4]));
-      HIP_OK(hipSetDevice(D[0].dev));
-      ABI_OK(mcgpu_dose_clear(ctx));
-      if (opt->progress) {
-        printf("       FAST batching preset %d of 3 (thresholds %d/%d/%d, %d, %d)\n", best + 1, presets[best][0], presets[best][1], presets[best][2],
-               presets[best][3], presets[best][4]);
-        fflush(stdout);
-      }
-    }
-    for (int g = 0; g < n_ctx; ++g) { D[g].lo = units * g / n_ctx; D[g].hi = units * (g + 1) / n_ctx; }
-    if (probe_image) {
-      HIP_OK(hipStreamSynchronize(D[0].stream));
-      HIP_OK(hipFree(probe_image));
-      probe_image = nullptr;
-    }
-    for (int g = 0; g < n_ctx; ++g) {  // every device that can own a projection finalizes it
+  }
+
+  // Download resources of every device that can own a projection, the pinned buffers, and the scan's own stacks.
+  void allocate() {
+    for (int g = 0; g < n; ++g) {
       if (g > 0 && !(policy & MCGPU_EXCHANGE_ROTATE)) break;
-      HIP_OK(hipSetDevice(D[g].dev));
-      HIP_OK(hipStreamCreateWithFlags(&D[g].copy, hipStreamNonBlocking));
+      Lane& l = lanes[g];
+      HIP_OK(hipSetDevice(l.dev));
+      HIP_OK(hipStreamCreateWithFlags(l.copy.make(l.dev), hipStreamNonBlocking));
       for (int b = 0; b < 2; ++b) {
-        HIP_OK(hipEventCreateWithFlags(&D[g].finalized[b], hipEventDisableTiming));
-        HIP_OK(hipMalloc(&D[g].planes_dev[b], 3 * plane * 4));
+        HIP_OK(hipEventCreateWithFlags(l.finalized[b].make(l.dev), hipEventDisableTiming));
+        HIP_OK(hipMalloc(l.planes_dev[b].make(l.dev), 3 * plan.plane * 4));
         // the writer thread reads non-coherent pinned memory after waiting on this event: that needs a SYSTEM-scope release,
         // which a default event does not promise (device scope only)
-        HIP_OK(hipEventCreateWithFlags(&D[g].done[b], hipEventDisableTiming | hipEventReleaseToSystem));
+        HIP_OK(hipEventCreateWithFlags(l.done[b].make(l.dev), hipEventDisableTiming | hipEventReleaseToSystem));
       }
     }
-    HIP_OK(hipSetDevice(D[0].dev));
+    // non-coherent (CPU-cacheable) pinned memory: the writer thread reads every byte (ordering: see the event above); portable:
+    // it is filled from whichever device owns the projection
+    const unsigned int pinned_flags = (knob_set("MCGPU_PINNED_COHERENT") ? hipHostMallocDefault : hipHostMallocNonCoherent) | hipHostMallocPortable;
+    const int dev0 = lanes[0].dev;
+    HIP_OK(hipSetDevice(dev0));
     for (int b = 0; b < 2; ++b) {
-      // non-coherent (CPU-cacheable) pinned memory: the writer thread reads every byte (ordering: see the event above)
-      HIP_OK(hipHostMalloc((void**)&planes_host[b], 3 * plane * 4, pinned_flags));
-      if (opt->write_ascii && ascii_on_host) HIP_OK(hipHostMalloc((void**)&image_host[b], words * 8, pinned_flags));
+      HIP_OK(hipHostMalloc(planes_host[b].make(dev0), 3 * plan.plane * 4, pinned_flags));
+      if (opt->write_ascii && out.ascii_on_host) HIP_OK(hipHostMalloc(image_host[b].make(dev0), plan.words * 8, pinned_flags));
     }
-    const bool shared = opt->shared_stacks != nullptr;  // 4-D: the caller owns stacks that several scans fill by slice index
-    if (shared && !opt->slice_of_projection) throw ScanError{-1, "!!ERROR!! mcgpu_run_scan: shared_stacks needs slice_of_projection"};
-    if (opt->write_stacks && !shared && count > 0) {
-      static const char* kNames[3] = {"projections_total.mha", "projections_unscattered.mha", "projections_scattered.mha"};
-      for (int k = 0; k < 3; ++k) ABI_OK(mcgpu_stack_create((folder + "/" + kNames[k]).c_str(), cx, (int)nz, count, sx, sy, &stacks[k]));
-    }
+    if (opt->write_stacks && !opt->shared_stacks && plan.count() > 0) stacks.create(plan);
+  }
 
-    std::vector<float> kms(count, 0.f);  // kernel time per projection (written before the projection is queued)
-    const bool ascii_async = opt->write_ascii && !ascii_on_host;
-    if (ascii_async)
-      for (int b = 0; b < n_ascii; ++b)
-        ascii_worker[b] = std::thread([&, b]() {
-          for (;;) {
-            int p;
-            double secs;
-            mcgpu_ctx* fctx;
-            {
-              std::unique_lock<std::mutex> lk(sh.mu);
-              sh.cv.wait(lk, [&] { return sh.ascii_busy[b] || sh.ascii_quit || sh.abort; });
-              if (!sh.ascii_busy[b]) return;
-              p = sh.ascii_p[b];
-              secs = sh.ascii_seconds[b];
-              fctx = sh.ascii_ctx[b];
-            }
-            const double tw0 = now_s();
-            const int wrc = mcgpu_write_formatted_projection(fctx, p, b, total, secs, nullptr);
-            std::lock_guard<std::mutex> lk(sh.mu);
-            sh.writer_s += now_s() - tw0;
-            if (wrc != 0) { sh.error = mcgpu_last_error(); sh.abort = true; }
-            sh.ascii_busy[b] = false;
-            sh.cv.notify_all();
-            if (wrc != 0) return;
-          }
-        });
-    // ---- writer thread: consumes buffers in order
-    writer = std::thread([&]() {
-      for (int i = 0; i < count; ++i) {
-        {
-          std::unique_lock<std::mutex> lk(sh.mu);
-          sh.cv.wait(lk, [&] { return sh.queued > i || sh.abort; });
-          if (sh.abort) return;
-        }
-        const int b = i & 1, p = first + sim[i], o = owner_of(i);
-        if (hipSetDevice(D[o].dev) != hipSuccess || hipEventSynchronize(D[o].done[b]) != hipSuccess) {
-          std::lock_guard<std::mutex> lk(sh.mu);
-          sh.error = "!!HIP ERROR!! waiting for projection results";
-          sh.abort = true;
-          sh.cv.notify_all();
-          return;
-        }
-        const double tw0 = now_s();
-        int wrc = 0;
-        if (shared)
-          for (int k = 0; k < 3 && wrc == 0; ++k)
-            wrc = mcgpu_stack_write_slice(opt->shared_stacks[k], opt->slice_of_projection[sim[i]], planes_host[b] + (size_t)k * plane);
-        else if (opt->write_stacks) {
-          // the three stacks side by side (each append scans its plane for zeros and copies it into the page cache)
-          int rc3[3] = {0, 0, 0};
-          std::string err3[3];
-          std::thread side[2];
-          for (int k = 1; k < 3; ++k)
-            side[k - 1] = std::thread([&, k] {
-              rc3[k] = mcgpu_stack_append(stacks[k], planes_host[b] + (size_t)k * plane);
-              if (rc3[k] != 0) err3[k] = mcgpu_last_error();  // the last error is per thread
-            });
-          rc3[0] = mcgpu_stack_append(stacks[0], planes_host[b]);
-          for (auto& t : side) t.join();
-          for (int k = 2; k >= 0; --k)
-            if (rc3[k] != 0) { wrc = rc3[k]; if (k > 0) mcgpu_set_last_error_(err3[k].c_str()); }
-        }
-        if (wrc == 0 && opt->write_ascii && ascii_on_host) wrc = mcgpu_write_projection(ctx, p, image_host[b], total, (double)kms[i] * 1e-3, nullptr);
-        std::lock_guard<std::mutex> lk(sh.mu);
-        if (wrc == 0 && ascii_async) {  // the slot is free: the projection loop waited for that before it formatted into it
-          const int a = i % n_ascii;
-          sh.ascii_p[a] = p;
-          sh.ascii_ctx[a] = D[o].ctx;
-          sh.ascii_seconds[a] = (double)kms[i] * 1e-3;
-          sh.ascii_busy[a] = true;
-        }
-        sh.writer_s += now_s() - tw0;
-        if (wrc != 0) { sh.error = mcgpu_last_error(); sh.abort = true; }
-        sh.written = i + 1;
-        sh.cv.notify_all();
-        if (wrc != 0) return;
+  int owner_of(int j) const {  // the device that holds the summed tally of projection j, finalizes and downloads it
+    return use_rccl ? ((policy & MCGPU_EXCHANGE_ROTATE) ? j % n : 0) : mcgpu_exchange_owner(lanes[0].x, j);
+  }
+
+  // Every device tracks its shard of projection i into a zeroed tally buffer; the devices that do not own the projection then
+  // push theirs to the owner (copy engine, beside the next projection's kernel).
+  void track(int i, int seed) {
+    const int b = i & 1, p = plan.first + plan.sim[i];
+    for (Lane& l : lanes) {
+      HIP_OK(hipSetDevice(l.dev));
+      void* tally = nullptr;
+      if (use_rccl && l.reduced_valid[b]) HIP_OK(hipStreamWaitEvent(l.stream, l.reduced[b], 0));  // begin() zeroes the buffer the collective of i - 2 read
+      ABI_OK(mcgpu_exchange_begin(l.x, i, l.stream, &tally));
+      ABI_OK(mcgpu_launch_projection(l.ctx, p, plan.mode, seed, l.lo, l.hi - l.lo, shape.hpt, tally, l.stream));
+      ABI_OK(mcgpu_exchange_submit(l.x, i, l.stream));
+      if (use_rccl) {
+        l.tally[b] = tally;
+        HIP_OK(hipEventRecord(l.tracked[b], l.stream));
       }
-    });
+    }
+  }
 
-    // ---- projection loop
+  // Sum + finalize of projection j on its owner's tracking stream, then the download of its planes.
+  void reduce_and_download(int j) {
+    const int b = j & 1, o = owner_of(j);
+    out.wait_for_buffers(j);
+    if (use_rccl) {
+      // one ncclReduce(uint64, sum, root = owner) over the devices' tallies of projection j (the reference's MPI_Reduce,
+      // MC-GPU_v1.3.cu:1019), on the reduce streams: behind kernel j of each device, beside its kernel j + 1
+      std::vector<void*> bufs((size_t)n), streams((size_t)n);
+      for (int g = 0; g < n; ++g) {
+        HIP_OK(hipSetDevice(lanes[g].dev));
+        HIP_OK(hipStreamWaitEvent(lanes[g].reduce, lanes[g].tracked[b], 0));
+        bufs[(size_t)g] = lanes[g].tally[b];
+        streams[(size_t)g] = (void*)(hipStream_t)lanes[g].reduce;
+      }
+      ABI_OK(mcgpu_rccl_reduce_u64(rccl, bufs.data(), plan.words, o, streams.data()));
+      for (Lane& l : lanes) {
+        HIP_OK(hipSetDevice(l.dev));
+        HIP_OK(hipEventRecord(l.reduced[b], l.reduce));
+        l.reduced_valid[b] = true;
+      }
+      HIP_OK(hipSetDevice(lanes[o].dev));
+      HIP_OK(hipStreamWaitEvent(lanes[o].stream, lanes[o].reduced[b], 0));  // the owner's tracking stream goes on with the summed tally
+      for (int g = 0; g < n; ++g)
+        if (g != o) { void* unused = nullptr; ABI_OK(mcgpu_exchange_collect(lanes[g].x, j, lanes[g].stream, &unused)); }  // bookkeeping of the local ends
+    }
+    Lane& l = lanes[o];
+    HIP_OK(hipSetDevice(l.dev));
+    hipStream_t const so = l.stream;
+    void* tally = nullptr;
+    ABI_OK(mcgpu_exchange_collect(l.x, j, so, &tally));  // exchange: the landed tallies of the other devices, added in one pass
+    if (!tally) throw ScanError{-1, "!!ERROR!! mcgpu_run_scan: the owner of a projection got no tally"};
+    // the reference's ASCII file: its 63 MB of text are formatted on the device (ascii_device.hip) while the tally is there; the
+    // writer thread downloads and writes them while the next projection is tracked
+    if (opt->write_ascii) {
+      if (out.ascii_on_host) HIP_OK(hipMemcpyAsync(image_host[b], tally, plan.words * 8, hipMemcpyDeviceToHost, so));
+      else ABI_OK(mcgpu_format_projection(l.ctx, tally, shape.total, j % out.n_ascii, so));
+    }
+    // planes_dev[b] was last downloaded two projections ago (by this device, if it owned that one)
+    if (l.done_valid[b]) HIP_OK(hipStreamWaitEvent(so, l.done[b], 0));
+    ABI_OK(mcgpu_finalize_projection(l.ctx, tally, shape.total, plan.cx, l.planes_dev[b], 0, so));  // begin() zeroes the buffer for its next user
+    // the 9 MB of planes go to the host on a copy engine, beside the next tracking kernel (on the tracking stream the copy held
+    // the next launch back by 0.17 ms per projection)
+    HIP_OK(hipEventRecord(l.finalized[b], so));
+    HIP_OK(hipStreamWaitEvent(l.copy, l.finalized[b], 0));
+    HIP_OK(hipMemcpyAsync(planes_host[b], l.planes_dev[b], 3 * plan.plane * 4, hipMemcpyDeviceToHost, l.copy));
+    HIP_OK(hipEventRecord(l.done[b], l.copy));
+    l.done_valid[b] = true;
+  }
+
+  void publish(int j) {  // kms[j] is final: the writer may take projection j
+    const Lane& l = lanes[owner_of(j)];
+    out.publish(j, {plan.first + plan.sim[j], plan.sim[j], l.dev, l.done[j & 1], static_cast<const float*>((void*)planes_host[j & 1]),
+                    static_cast<const uint64_t*>((void*)image_host[j & 1]), l.ctx, (double)kms[j] * 1e-3});
+  }
+
+  void print_skipped(int from, int to) const {  // offsets [from, to) of the range
+    for (int k = from; k < to && opt->progress && plan.phase == 0; ++k)
+      if (plan.outside_roi(plan.first + k))
+        printf("         << Skipping projection #%d of %d >> Angle %f degrees: outside angular region of interest.\n", plan.first + k + 1, (int)plan.nproj_all,
+               (plan.angle0 + (plan.first + k) * plan.d_angle) * (180.0 / 3.14159265358979323846));
+  }
+
+  void run(mcgpu_scan_report* report) {
+    connect();
+    HIP_OK(hipSetDevice(lanes[0].dev));
+    unsigned long long H = opt->histories_per_projection ? opt->histories_per_projection : (unsigned long long)plan.hist_in;
+    if (plan.by_time) H = budget_histories(plan, lanes[0].stream, n, false, opt->progress);  // calibrated on device 0
+    shape = launch_shape(plan, H);
+    choose_fast_preset(plan, shape.total, lanes[0].stream, opt->progress);
+    for (int g = 0; g < n; ++g) { lanes[g].lo = shape.units * g / n; lanes[g].hi = shape.units * (g + 1) / n; }
+    allocate();
+    const int count = plan.count();
+    kms.assign((size_t)count, 0.f);
+    out.start(count, shape.total);
+
+    // the pipeline of the file header: kernel i on every device, then the sum + finalize + download of the previous projection
+    // on its owner (one device: of this projection), then the kernel time -- waiting for it also paces the host
+    const bool single = n == 1;
     const double t0 = now_s();
     double kernel_s = 0.0, t_last_kernel = t0;
-    int cur_seed = (int)seed;
-    if (mode == MCGPU_MODE_COMPAT) {  // the seed moves on per SIMULATED projection (MC-GPU_v1.3.cu:869)
-      for (int p = 0; p < first; ++p)
-        if (!outside_roi(p)) cur_seed = mcgpu_advance_seed(1, total, cur_seed);
-      for (int k = 0; k < (count > 0 ? ord[0] : 0); ++k) cur_seed = mcgpu_advance_seed(1, total, cur_seed);
-    }
-    // sum + finalize of projection j on its owner's stream, then hand it to the writer
-    auto enqueue_reduce = [&](int j) {
-      const int b = j & 1, o = owner_of(j);
-      {  // pinned buffer b is free once projection j-2 has been written.  Formatter slot j % n_ascii was last used by
-         // projection j - n_ascii: that one must have been HANDED to its worker (the writer sets ascii_busy when it has
-         // written the projection's stacks, together with `written`) and the worker must be done.  With one slot the
-         // previous projection itself is the slot's last user, so `written >= j - 1` is not enough (it would let
-         // projection j be formatted over the text of j - 1 before j - 1 was even handed over).
-        const int handed = j - std::min(1, n_ascii - 1);
-        std::unique_lock<std::mutex> lk(sh.mu);
-        sh.cv.wait(lk, [&] { return (sh.written >= handed && !sh.ascii_busy[j % n_ascii]) || sh.abort; });
-        if (sh.abort) throw ScanError{-3, sh.error};
-      }
-      if (use_rccl) {
-        // one ncclReduce(uint64, sum, root = owner) over the devices' tallies of projection j (the reference's MPI_Reduce,
-        // MC-GPU_v1.3.cu:1019), on the reduce streams: behind kernel j of each device, beside its kernel j + 1
-        std::vector<void*> bufs((size_t)n_ctx), streams((size_t)n_ctx);
-        for (int g = 0; g < n_ctx; ++g) {
-          HIP_OK(hipSetDevice(D[g].dev));
-          HIP_OK(hipStreamWaitEvent(D[g].reduce, D[g].tracked[b], 0));
-          bufs[(size_t)g] = D[g].tally[b];
-          streams[(size_t)g] = (void*)D[g].reduce;
-        }
-        ABI_OK(mcgpu_rccl_reduce_u64(rccl, bufs.data(), words, o, streams.data()));
-        for (int g = 0; g < n_ctx; ++g) {
-          HIP_OK(hipSetDevice(D[g].dev));
-          HIP_OK(hipEventRecord(D[g].reduced[b], D[g].reduce));
-          D[g].reduced_valid[b] = true;
-        }
-        HIP_OK(hipSetDevice(D[o].dev));
-        HIP_OK(hipStreamWaitEvent(D[o].stream, D[o].reduced[b], 0));  // the owner's tracking stream goes on with the summed tally
-        for (int g = 0; g < n_ctx; ++g)
-          if (g != o) { void* unused = nullptr; ABI_OK(mcgpu_exchange_collect(D[g].x, j, D[g].stream, &unused)); }  // bookkeeping of the local ends
-      }
-      HIP_OK(hipSetDevice(D[o].dev));
-      hipStream_t const so = D[o].stream;
-      void* tally = nullptr;
-      ABI_OK(mcgpu_exchange_collect(D[o].x, j, so, &tally));  // exchange: the landed tallies of the other devices, added in one pass
-      if (!tally) throw ScanError{-1, "!!ERROR!! mcgpu_run_scan: the owner of a projection got no tally"};
-      // the reference's ASCII file: its 63 MB of text are formatted on the device (ascii_device.hip) while the tally is
-      // there; the writer thread downloads and writes them while the next projection is tracked
-      if (opt->write_ascii) {
-        if (ascii_on_host) HIP_OK(hipMemcpyAsync(image_host[b], tally, words * 8, hipMemcpyDeviceToHost, so));
-        else ABI_OK(mcgpu_format_projection(D[o].ctx, tally, total, j % n_ascii, so));
-      }
-      // planes_dev[b] was last downloaded two projections ago (by this device, if it owned that one)
-      if (D[o].done_valid[b]) HIP_OK(hipStreamWaitEvent(so, D[o].done[b], 0));
-      ABI_OK(mcgpu_finalize_projection(D[o].ctx, tally, total, cx, D[o].planes_dev[b], 0, so));  // begin() zeroes the buffer for its next user
-      // the 9 MB of planes go to the host on a copy engine, beside the next tracking kernel (on the tracking stream the copy
-      // held the next launch back by 0.17 ms per projection)
-      HIP_OK(hipEventRecord(D[o].finalized[b], so));
-      HIP_OK(hipStreamWaitEvent(D[o].copy, D[o].finalized[b], 0));
-      HIP_OK(hipMemcpyAsync(planes_host[b], D[o].planes_dev[b], 3 * plane * 4, hipMemcpyDeviceToHost, D[o].copy));
-      HIP_OK(hipEventRecord(D[o].done[b], D[o].copy));
-      D[o].done_valid[b] = true;
-    };
-    auto publish = [&](int j) {  // kms[j] is final: the writer may take projection j
-      std::lock_guard<std::mutex> lk(sh.mu);
-      sh.queued = j + 1;
-      sh.cv.notify_all();
-    };
-    const double kRad2Deg = 180.0 / 3.14159265358979323846;
-    auto print_skipped = [&](int from, int to) {  // offsets [from, to) of the range
-      for (int k = from; k < to && opt->progress && phase == 0; ++k)
-        if (outside_roi(first + k))
-          printf("         << Skipping projection #%d of %d >> Angle %f degrees: outside angular region of interest.\n", first + k + 1, (int)nproj_all,
-               (angle0 + (first + k) * d_angle) * kRad2Deg);
-    };
+    int seed = (int)plan.seed, seed_ord = 0;  // seed_ord: simulated projections the seed has moved on past
     for (int i = 0; i < count; ++i) {
-      const int p = first + sim[i];
-      print_skipped(i ? sim[i - 1] + 1 : 0, sim[i]);
-      if (nproj_all != 1 && opt->progress) {
-        printf("\n\n\n   << Simulating Projection %d of %d >>\n\n\n", p + 1, (int)nproj_all);  // cbctmc/mc/simulation.py:200-219 parses this
+      const int p = plan.first + plan.sim[i];
+      print_skipped(i ? plan.sim[i - 1] + 1 : 0, plan.sim[i]);
+      if (plan.nproj_all != 1 && opt->progress) {
+        printf("\n\n\n   << Simulating Projection %d of %d >>\n\n\n", p + 1, (int)plan.nproj_all);  // cbctmc/mc/simulation.py:200-219 parses this
         fflush(stdout);
       }
-      // every device tracks its shard into a zeroed tally buffer; the devices that do not own the projection then push theirs
-      // to the owner (copy engine, beside the next projection's kernel)
-      for (int g = 0; g < n_ctx; ++g) {
-        HIP_OK(hipSetDevice(D[g].dev));
-        void* tally = nullptr;
-        if (use_rccl && D[g].reduced_valid[i & 1]) HIP_OK(hipStreamWaitEvent(D[g].stream, D[g].reduced[i & 1], 0));  // begin() zeroes the buffer the collective of i - 2 read
-        ABI_OK(mcgpu_exchange_begin(D[g].x, i, D[g].stream, &tally));
-        ABI_OK(mcgpu_launch_projection(D[g].ctx, p, mode, cur_seed, D[g].lo, D[g].hi - D[g].lo, hpt_eff, tally, D[g].stream));
-        ABI_OK(mcgpu_exchange_submit(D[g].x, i, D[g].stream));
-        if (use_rccl) {
-          D[g].tally[i & 1] = tally;
-          HIP_OK(hipEventRecord(D[g].tracked[i & 1], D[g].stream));
-        }
-      }
-      // the owner of the previous projection, behind its own kernel i (one device: this projection)
-      if (single) enqueue_reduce(i);
-      else if (i >= 1) { enqueue_reduce(i - 1); publish(i - 1); }
-      // kernel time of this projection = the slowest device's launch; waiting for it also paces the host
-      float ms = 0.f;
-      for (int g = 0; g < n_ctx; ++g) {
+      if (plan.mode == MCGPU_MODE_COMPAT)  // the seed moves on per SIMULATED projection (MC-GPU_v1.3.cu:869)
+        for (; seed_ord < plan.ord[i]; ++seed_ord) seed = mcgpu_advance_seed(1, shape.total, seed);
+      track(i, seed);
+      if (single) reduce_and_download(i);
+      else if (i >= 1) { reduce_and_download(i - 1); publish(i - 1); }
+      float ms = 0.f;  // the slowest device's launch
+      for (const Lane& l : lanes) {
         float m = 0.f;
-        ABI_OK(mcgpu_last_kernel_ms(D[g].ctx, &m));
+        ABI_OK(mcgpu_last_kernel_ms(l.ctx, &m));
         ms = m > ms ? m : ms;
       }
       kms[i] = ms;
       kernel_s += ms * 1e-3;
       t_last_kernel = now_s();
       if (single) publish(i);
-      if (mode == MCGPU_MODE_COMPAT)
-        for (int k = ord[i]; k < (i + 1 < count ? ord[i + 1] : ord[i] + 1); ++k) cur_seed = mcgpu_advance_seed(1, total, cur_seed);
     }
-    print_skipped(count ? sim[count - 1] + 1 : 0, range);
-    if (!single && count > 0) { enqueue_reduce(count - 1); publish(count - 1); }
-    writer.join();
-    {
-      std::unique_lock<std::mutex> lk(sh.mu);
-      sh.cv.wait(lk, [&] {
-        bool busy = false;
-        for (bool b : sh.ascii_busy) busy = busy || b;
-        return !busy || sh.abort;
-      });
-      sh.ascii_quit = true;
-      sh.cv.notify_all();
-    }
-    for (auto& w : ascii_worker)
-      if (w.joinable()) w.join();
-    {
-      std::lock_guard<std::mutex> lk(sh.mu);
-      if (sh.abort) throw ScanError{-3, sh.error};
-    }
+    print_skipped(count ? plan.sim[count - 1] + 1 : 0, plan.range);
+    if (!single && count > 0) { reduce_and_download(count - 1); publish(count - 1); }
+    out.join();
     float repl[3] = {0.f, 0.f, 0.f};
-    if (opt->write_stacks && !shared && count > 0) {
-      // zero replacement and close of the three stacks side by side (page-cache work on three different files)
-      int rc3[3] = {0, 0, 0};
-      std::string err3[3];
-      std::thread fin[3];
-      for (int k = 0; k < 3; ++k) {
-        mcgpu_stack* s = stacks[k];
-        stacks[k] = nullptr;
-        fin[k] = std::thread([&, k, s] {
-          rc3[k] = mcgpu_stack_finish(s, 1, &repl[k]);
-          if (rc3[k] != 0) err3[k] = mcgpu_last_error();  // the last error is per thread
-        });
-      }
-      for (auto& t : fin) t.join();
-      for (int k = 0; k < 3; ++k)
-        if (rc3[k] != 0) throw ScanError{rc3[k], err3[k]};
-      if (opt->air_stack)
-        ABI_OK(mcgpu_normalize_stack((folder + "/projections_total.mha").c_str(), opt->air_stack, opt->air_sigma_y, opt->air_sigma_x,
-                                     (folder + "/projections_total_normalized.mha").c_str(), sx, sy));
-    }
+    if (stacks.open()) stacks.finish(plan, opt, repl);
     if (report) {
       report->projections = count;
-      report->histories_per_projection = total;
+      report->histories_per_projection = shape.total;
       report->seconds_total = now_s() - t0;
       report->seconds_kernels = kernel_s;
       report->seconds_after_last_kernel = now_s() - t_last_kernel;
-      report->seconds_writer = sh.writer_s;
-      report->kernel_ms_min = report->kernel_ms_max = count > 0 ? (double)kms[0] : 0.0;
-      for (int i = 1; i < count; ++i) {
-        report->kernel_ms_min = std::min(report->kernel_ms_min, (double)kms[i]);
-        report->kernel_ms_max = std::max(report->kernel_ms_max, (double)kms[i]);
-      }
+      report->seconds_writer = out.busy_s;
+      report->kernel_ms_min = count > 0 ? *std::min_element(kms.begin(), kms.end()) : 0.0;
+      report->kernel_ms_max = count > 0 ? *std::max_element(kms.begin(), kms.end()) : 0.0;
       for (int k = 0; k < 3; ++k) report->zero_replacement[k] = repl[k];
     }
+  }
+};
+
+int run_scan_sharing_histories(mcgpu_ctx* const* ctxs, int n_ctx, const mcgpu_scan_options* opt, mcgpu_scan_report* report, bool use_rccl = false) {
+  try {
+    HistoryScan(ctxs, n_ctx, opt, use_rccl).run(report);
+    return 0;
   } catch (const ScanError& e) {
     mcgpu_set_last_error_(e.msg.c_str());
-    rc = e.code ? e.code : -1;
-    {
-      std::lock_guard<std::mutex> lk(sh.mu);
-      sh.abort = true;
-      sh.cv.notify_all();
-    }
-    if (writer.joinable()) writer.join();
-    for (auto& w : ascii_worker)
-      if (w.joinable()) w.join();
+    return e.code ? e.code : -1;
   }
-  for (int k = 0; k < 3; ++k)
-    if (stacks[k]) (void)mcgpu_stack_finish(stacks[k], 0, nullptr);  // error path: close the files
-  for (auto& d : D) {
-    if (d.dev < 0) continue;
-    (void)hipSetDevice(d.dev);
-    if (d.stream) (void)hipStreamSynchronize(d.stream);
-    if (d.copy) (void)hipStreamSynchronize(d.copy);
-    if (d.reduce) (void)hipStreamSynchronize(d.reduce);
-  }
-  if (rccl) mcgpu_rccl_destroy(rccl);
-  if (D[0].dev >= 0) {
-    (void)hipSetDevice(D[0].dev);
-    if (probe_image) (void)hipFree(probe_image);
-    for (int b = 0; b < 2; ++b) {
-      if (planes_host[b]) (void)hipHostFree(planes_host[b]);
-      if (image_host[b]) (void)hipHostFree(image_host[b]);
-    }
-  }
-  for (auto& d : D) {
-    if (d.dev < 0) continue;
-    (void)hipSetDevice(d.dev);
-    for (int b = 0; b < 2; ++b) {
-      if (d.planes_dev[b]) (void)hipFree(d.planes_dev[b]);
-      if (d.done[b]) (void)hipEventDestroy(d.done[b]);
-      if (d.finalized[b]) (void)hipEventDestroy(d.finalized[b]);
-    }
-    if (d.copy) (void)hipStreamDestroy(d.copy);
-    if (d.reduce) (void)hipStreamDestroy(d.reduce);
-    for (int b = 0; b < 2; ++b) {
-      if (d.tracked[b]) (void)hipEventDestroy(d.tracked[b]);
-      if (d.reduced[b]) (void)hipEventDestroy(d.reduced[b]);
-    }
-  }
-  for (auto& d : D)  // after every device has drained: an exchange end frees memory its peers push into
-    if (d.x) mcgpu_exchange_destroy(d.x);
-  for (auto& d : D) {
-    if (d.dev < 0) continue;
-    (void)hipSetDevice(d.dev);
-    if (d.stream) (void)hipStreamDestroy(d.stream);
-  }
-  return rc;
 }
 
 // Projection sharding (SURVEY.md 8e's fallback mode; the reference has no counterpart -- its ranks always share a projection,
@@ -635,79 +705,21 @@ int run_scan_sharing_histories(mcgpu_ctx* const* ctxs, int n_ctx, const mcgpu_sc
 // collective.  The MetaImage stacks are shared and filled by slice index; ASCII files are per projection anyway.  Every output
 // byte equals a one-device scan's (per-history streams / per-projection seeds do not depend on who simulates a projection).
 int run_scan_sharing_projections(mcgpu_ctx* const* ctxs, int n_ctx, const mcgpu_scan_options* opt, mcgpu_scan_report* report) {
-  mcgpu_stack* stacks[3] = {nullptr, nullptr, nullptr};
-  int rc = 0;
-  std::string error;
   try {
-    mcgpu_ctx* ctx = ctxs[0];
-    long long nproj_all = 1, nx = 0, nz = 0;
-    ABI_OK(mcgpu_config_i64(ctx, "num_projections", &nproj_all));
-    ABI_OK(mcgpu_config_i64(ctx, "num_pixels_x", &nx));
-    ABI_OK(mcgpu_config_i64(ctx, "num_pixels_z", &nz));
-    double px_x = 0, px_z = 0, d_angle = -1.0, angle0 = 0.0, roi0 = 0.0, roi1 = 0.0;
-    ABI_OK(mcgpu_config_f64(ctx, "pixel_size_x_mm", &px_x));
-    ABI_OK(mcgpu_config_f64(ctx, "pixel_size_z_mm", &px_z));
-    ABI_OK(mcgpu_config_f64(ctx, "D_angle", &d_angle));
-    ABI_OK(mcgpu_config_f64(ctx, "initial_angle", &angle0));
-    ABI_OK(mcgpu_config_f64(ctx, "angularROI_0", &roi0));
-    ABI_OK(mcgpu_config_f64(ctx, "angularROI_1", &roi1));
-    const int first = opt->first_projection > 0 ? opt->first_projection : 0;
-    const int range = (opt->num_projections > 0) ? opt->num_projections : (int)nproj_all - first;
-    if (first + range > nproj_all || range <= 0) throw ScanError{-1, "!!ERROR!! mcgpu_run_scan: projection range outside the trajectory"};
+    const ScanPlan plan = plan_scan(ctxs, n_ctx, opt);
     if (opt->projection_stride > 1) throw ScanError{-1, "!!ERROR!! mcgpu_run_scan_multi: MCGPU_SHARD_PROJECTIONS sets the projection stride itself"};
+    const int count = plan.count();
     // slice of every offset of the range: its ordinal among the simulated projections (the order a one-device scan appends in)
-    std::vector<int> slice_of((size_t)range, -1);
-    int count = 0;
-    for (int k = 0; k < range; ++k) {
-      const double a = angle0 + (first + k) * d_angle;
-      if (!(a < roi0 || a > roi1)) slice_of[(size_t)k] = count++;
-    }
-    const int cx = (opt->crop_nx > 0 && opt->crop_nx < nx) ? opt->crop_nx : (int)nx;
-    const double sx = opt->pixel_spacing_x > 0 ? opt->pixel_spacing_x : px_x, sy = opt->pixel_spacing_y > 0 ? opt->pixel_spacing_y : px_z;
-    std::string folder;
-    if (opt->output_folder) folder = opt->output_folder;
-    else {
-      char name[1024];
-      ABI_OK(mcgpu_projection_file_name(ctx, 0, name, sizeof name));
-      folder = name;
-      const size_t slash = folder.find_last_of('/');
-      folder = slash == std::string::npos ? "." : folder.substr(0, slash);
-    }
-    const bool own_stacks = opt->write_stacks && !opt->shared_stacks && count > 0;
-    if (own_stacks) {
-      static const char* kNames[3] = {"projections_total.mha", "projections_unscattered.mha", "projections_scattered.mha"};
-      for (int k = 0; k < 3; ++k) ABI_OK(mcgpu_stack_create((folder + "/" + kNames[k]).c_str(), cx, (int)nz, count, sx, sy, &stacks[k]));
-    }
+    std::vector<int> slice_of((size_t)plan.range, -1);
+    for (int i = 0; i < count; ++i) slice_of[(size_t)plan.sim[i]] = i;
+    OutputStacks stacks;
+    if (opt->write_stacks && !opt->shared_stacks && count > 0) stacks.create(plan);
     std::vector<mcgpu_scan_options> o((size_t)n_ctx, *opt);
-    // a time-limited run (history count below 95000 = seconds per projection): ONE calibration, on device 0, for all the shards
-    // -- each device calibrating by itself would simulate its own history count and the files would depend on who wrote them
-    {
-      long long hist_in = 0, seed = 0, hpt = 150, dev0 = -1;
-      ABI_OK(mcgpu_config_i64(ctx, "total_histories", &hist_in));
-      ABI_OK(mcgpu_config_i64(ctx, "seed", &seed));
-      ABI_OK(mcgpu_config_i64(ctx, "histories_per_thread", &hpt));
-      ABI_OK(mcgpu_config_i64(ctx, "device_id", &dev0));
-      if (!opt->histories_per_projection && hist_in < 95000 && count > 0) {
-        if (dev0 < 0) throw ScanError{-1, "!!ERROR!! mcgpu_run_scan: a context has no device"};
-        const int mode = opt->mode == MCGPU_MODE_COMPAT ? MCGPU_MODE_COMPAT : (opt->mode == MCGPU_MODE_FAST_F64 ? MCGPU_MODE_FAST_F64 : MCGPU_MODE_FAST);
-        void* probe_image = nullptr;
-        double rate = 0.0;
-        try {
-          rate = calibrate_rate(ctx, (int)dev0, first, mode, seed, hpt, (size_t)4 * nx * nz, &probe_image, nullptr);
-          HIP_OK(hipDeviceSynchronize());
-        } catch (...) {
-          if (probe_image) (void)hipFree(probe_image);
-          throw;
-        }
-        (void)hipFree(probe_image);
-        unsigned long long H = (unsigned long long)(rate * (double)hist_in);  // a device simulates a projection alone: its own rate
-        if (H < 100000ULL) H = 100000ULL;
-        for (int g = 0; g < n_ctx; ++g) o[(size_t)g].histories_per_projection = H;
-        if (opt->progress) {
-          printf("       Time-limited run: %lld s per projection at %.3e x-rays/s per device -> %llu histories per projection\n", hist_in, rate, H);
-          fflush(stdout);
-        }
-      }
+    // a time-limited run: ONE calibration, on device 0, for all the shards -- each device calibrating by itself would simulate
+    // its own history count and the files would depend on who wrote them
+    if (plan.by_time && count > 0) {
+      const unsigned long long H = budget_histories(plan, nullptr, 1, true, opt->progress);  // a device simulates a projection alone
+      for (auto& og : o) og.histories_per_projection = H;
     }
     std::vector<mcgpu_scan_report> r((size_t)n_ctx);
     std::vector<int> rcs((size_t)n_ctx, 0);
@@ -715,13 +727,12 @@ int run_scan_sharing_projections(mcgpu_ctx* const* ctxs, int n_ctx, const mcgpu_
     std::vector<std::thread> th;
     const double t0 = now_s();
     for (int g = 0; g < n_ctx; ++g) {
-      memset(&r[(size_t)g], 0, sizeof(mcgpu_scan_report));
       o[(size_t)g].shard = MCGPU_SHARD_HISTORIES;  // a single-context scan
       o[(size_t)g].projection_stride = n_ctx;
       o[(size_t)g].projection_phase = g;
       o[(size_t)g].air_stack = nullptr;  // normalisation runs once, below, over the finished stack
-      if (own_stacks) {
-        o[(size_t)g].shared_stacks = stacks;
+      if (stacks.open()) {
+        o[(size_t)g].shared_stacks = stacks.stack;
         o[(size_t)g].slice_of_projection = slice_of.data();
       }
       th.emplace_back([&, g] {
@@ -733,16 +744,7 @@ int run_scan_sharing_projections(mcgpu_ctx* const* ctxs, int n_ctx, const mcgpu_
     for (int g = 0; g < n_ctx; ++g)
       if (rcs[(size_t)g] != 0) throw ScanError{rcs[(size_t)g], errs[(size_t)g]};
     float repl[3] = {0.f, 0.f, 0.f};
-    if (own_stacks) {
-      for (int k = 0; k < 3; ++k) {
-        mcgpu_stack* st = stacks[k];
-        stacks[k] = nullptr;
-        ABI_OK(mcgpu_stack_finish(st, 1, &repl[k]));
-      }
-      if (opt->air_stack)
-        ABI_OK(mcgpu_normalize_stack((folder + "/projections_total.mha").c_str(), opt->air_stack, opt->air_sigma_y, opt->air_sigma_x,
-                                     (folder + "/projections_total_normalized.mha").c_str(), sx, sy));
-    }
+    if (stacks.open()) stacks.finish(plan, opt, repl);
     if (report) {
       memset(report, 0, sizeof *report);
       report->histories_per_projection = r[0].histories_per_projection;
@@ -761,14 +763,11 @@ int run_scan_sharing_projections(mcgpu_ctx* const* ctxs, int n_ctx, const mcgpu_
       if (report->projections == 0) report->kernel_ms_min = 0.0;
       for (int k = 0; k < 3; ++k) report->zero_replacement[k] = repl[k];
     }
+    return 0;
   } catch (const ScanError& e) {
-    error = e.msg;
-    rc = e.code ? e.code : -1;
+    mcgpu_set_last_error_(e.msg.c_str());
+    return e.code ? e.code : -1;
   }
-  for (int k = 0; k < 3; ++k)
-    if (stacks[k]) (void)mcgpu_stack_finish(stacks[k], 0, nullptr);  // error path: close the files
-  if (rc != 0) mcgpu_set_last_error_(error.c_str());
-  return rc;
 }
 
 }  // namespace

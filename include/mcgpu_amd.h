@@ -199,7 +199,7 @@ typedef struct mcgpu_scan_options {
   /* sizeof(mcgpu_scan_options) as the CALLER was compiled: fields the caller's header did not have yet read as zero (their
    * defaults), instead of whatever follows the shorter struct in memory.  0 is refused. */
   unsigned int struct_size;
-  int mode;                                     /* MCGPU_MODE_FAST (default) or MCGPU_MODE_COMPAT */
+  int mode;                                     /* MCGPU_MODE_FAST (default), MCGPU_MODE_FAST_F64 or MCGPU_MODE_COMPAT; any other value is refused */
   int first_projection, num_projections;        /* num_projections 0 = all remaining */
   unsigned long long histories_per_projection;  /* 0 = the input file's value */
   int crop_nx;                                  /* half-fan crop of the stacks (reference default 1024); 0 = full width */
@@ -224,8 +224,8 @@ typedef struct mcgpu_scan_options {
   int projection_stride, projection_phase;
   /* mcgpu_run_scan_multi with MCGPU_SHARD_HISTORIES: how the per-device tallies of a projection are summed (the reference's
    * MPI_Reduce, MC-GPU_v1.3.cu:1006-1024).  MCGPU_REDUCE_AUTO (0): the tally exchange; where the devices cannot reach each other,
-   * one RCCL reduction per projection; where that is not available either, projection sharding -- unless the environment says
-   * MCGPU_REDUCE=rccl.  MCGPU_REDUCE_RCCL: one ncclReduce(uint64, sum, root = the projection's owner) per projection on a stream of
+   * projection sharding (no RCCL in between) -- unless the environment says MCGPU_REDUCE=rccl, which makes it MCGPU_REDUCE_RCCL.
+   * MCGPU_REDUCE_RCCL: one ncclReduce(uint64, sum, root = the projection's owner) per projection on a stream of
    * its own beside the next projection's kernel (then projection sharding if RCCL cannot be set up).  Same output bytes on every route. */
   int reduce;
 } mcgpu_scan_options;

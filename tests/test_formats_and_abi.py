@@ -291,7 +291,8 @@ def test_option_structs_carry_their_size(engine, case_dir):
     """mcgpu_scan_options / mcgpu_fdk_options begin with `struct_size`: a caller that forgot to set it is refused (its fields would
     otherwise be read at the wrong offsets), one that was compiled against a SHORTER struct gets the defaults of the fields it does
     not know -- here a scan-options struct cut before `shard`, handed to a host-only context, fails for the right reason (no
-    device), not for a garbage shard mode."""
+    device), not for a garbage shard mode.  An unknown kernel mode is refused by name before anything else is looked at (it once ran
+    the FAST kernel instead)."""
     import ctypes as C
     lib = engine.load_library()
     with engine.create(case_dir("air"), device=-1) as ctx:
@@ -305,6 +306,11 @@ def test_option_structs_carry_their_size(engine, case_dir):
         assert lib.mcgpu_run_scan(ctx.h, C.byref(o), C.byref(r)) != 0
         msg = lib.mcgpu_last_error().decode()
         assert "no device" in msg and "projection_phase" not in msg, msg
+        o.struct_size = C.sizeof(engine.ScanOptions)
+        o.shard, o.projection_stride, o.projection_phase, o.mode = 0, 0, 0, 77
+        assert lib.mcgpu_run_scan(ctx.h, C.byref(o), C.byref(r)) != 0
+        msg = lib.mcgpu_last_error().decode()
+        assert "unknown mode 77" in msg and "no device" not in msg, msg
     recon = __import__("cases").pkg.reconstruction
     fo = recon._FdkOptions()
     lib.mcgpu_fdk_reconstruct.restype = C.c_int
@@ -435,6 +441,10 @@ def test_environment_knobs_go_through_one_registry(engine, tmp_path):
     r = subprocess.run([str(exe), str(tmp_path / "missing.in")], capture_output=True, text=True, timeout=60, env=env)
     warn = [l for l in r.stdout.split("\n") if "MCGPU_THRESH_COMPTN" in l]
     assert len(warn) == 1 and "ignored" in warn[0] and not re.search("(?i)error", warn[0]) and "MCGPU_SWAP_BATCH" not in r.stdout
+    # a value outside an option's documented set is refused with the usage, before the input is read (`--mode f64` once ran FAST)
+    for option, value in (("--mode", "f64"), ("--shard", "projection"), ("--reduce", "nccl")):
+        r = subprocess.run([str(exe), str(tmp_path / "missing.in"), option, value], capture_output=True, text=True, timeout=60)
+        assert r.returncode != 0 and "usage:" in r.stdout and f"'{value}' of {option}" in r.stdout and "read_input" not in r.stdout, r.stdout
 
 
 def test_bench_builds_its_inputs_without_tests_and_oracle(tmp_path):

@@ -229,7 +229,7 @@ def test_device_finalize_and_scan_pipeline(engine, case_dir, tmp_path):
 @pytest.mark.parametrize("writers", [1, 2])
 def test_scan_ascii_files_with_few_formatter_slots(engine, case_dir, tmp_path, monkeypatch, writers):
     """MCGPU_ASCII_WRITERS=1: every projection is formatted into the ONE slot its predecessor used -- the projection loop
-    must wait until that predecessor has been handed to the slot's worker and written (scan.cpp: enqueue_reduce).  The files
+    must wait until that predecessor has been handed to the slot's worker and written (scan.cpp: Output::wait_for_buffers).  The files
     of the scan equal the host formatter's for the same tallies."""
     n_hist = 200_000
     monkeypatch.setenv("MCGPU_ASCII_WRITERS", str(writers))
