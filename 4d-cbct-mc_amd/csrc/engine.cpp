@@ -27,7 +27,7 @@ int mcgpu_create(const char* input_path, int device_id, mcgpu_ctx** out) {
   std::unique_ptr<mcgpu_ctx> c(new mcgpu_ctx);
   load_model(input_path, c->host);
   if (device_id >= 0) {
-    upload_model(*c, device_id);
+    c->dev = upload_model(c->host, device_id);
     c->has_device = true;
   }
   *out = c.release();
@@ -42,7 +42,7 @@ int mcgpu_clone(const mcgpu_ctx* src, int device_id, mcgpu_ctx** out) {
   sync_host_voxels(*const_cast<mcgpu_ctx*>(src));
   c->host = src->host;
   if (device_id >= 0) {
-    upload_model(*c, device_id);
+    c->dev = upload_model(c->host, device_id);
     c->has_device = true;
   }
   *out = c.release();
@@ -50,14 +50,7 @@ int mcgpu_clone(const mcgpu_ctx* src, int device_id, mcgpu_ctx** out) {
   ABI_END
 }
 
-void mcgpu_destroy(mcgpu_ctx* ctx) {
-  if (!ctx) return;
-  if (ctx->has_device) {
-    (void)hipSetDevice(ctx->dev.device_id);
-    ctx->dev.release();
-  }
-  delete ctx;
-}
+void mcgpu_destroy(mcgpu_ctx* ctx) { delete ctx; }
 
 int mcgpu_config_i64(const mcgpu_ctx* ctx, const char* key, long long* value) {
   ABI_BEGIN
@@ -356,15 +349,12 @@ int mcgpu_format_projection(mcgpu_ctx* ctx, const void* image_dev, unsigned long
     // room for 11 integer digits per number (values below 1e11 eV/cm^2 per history; a tally of 1e8 125-keV photons in one
     // 0.04 cm pixel would be 3e5): the formatter flags a projection that needs more
     D.ascii_capacity = npix * (4 * (11 + 9) + 4) + (size_t)nz + 64;
-    void* t = nullptr;
-    HIP_TRY(hipMalloc(&t, D.ascii_capacity));
-    D.allocations.push_back(t);  // freed by release()
-    S.text_dev = (char*)t;
     S.rows_dev = D.put(std::vector<unsigned long long>(words, 0ULL));
-    HIP_TRY(hipHostMalloc((void**)&S.text_host, D.ascii_capacity, hipHostMallocNonCoherent));
-    HIP_TRY(hipHostMalloc((void**)&S.rows_host, words * 8, hipHostMallocDefault));
-    HIP_TRY(hipStreamCreateWithFlags(&S.copy_stream, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&S.ready, hipEventDisableTiming));
+    S.text_host = (char*)D.mem.pinned_bytes(D.ascii_capacity, hipHostMallocNonCoherent);
+    S.rows_host = (unsigned long long*)D.mem.pinned_bytes(words * 8, hipHostMallocDefault);
+    S.copy_stream = D.mem.stream(hipStreamNonBlocking);
+    S.ready = D.mem.event(hipEventDisableTiming);
+    S.text_dev = (char*)D.mem.device_bytes(D.ascii_capacity);  // last: a slot with text_dev is complete
   }
   AsciiArgs a;
   a.image = (const unsigned long long*)image_dev;

@@ -23,8 +23,12 @@ int mcgpu_set_projection_angles(mcgpu_ctx* ctx, int n, const float* angles_deg) 
     DeviceModel& D = ctx->dev;
     HIP_TRY(hipSetDevice(D.device_id));
     HIP_TRY(hipDeviceSynchronize());
-    D.src_all = D.put(H.source);  // the old arrays stay allocated until the context is destroyed (180 B per projection)
+    SourcePose* old_src = D.src_all;
+    DetectorPose* old_det = D.det_all;
+    D.src_all = D.put(H.source);
     D.det_all = D.put(H.detector);
+    D.mem.free(old_src);
+    D.mem.free(old_det);
   }
   return 0;
   ABI_END
@@ -80,25 +84,21 @@ int mcgpu_set_geometry_arrays(mcgpu_ctx* ctx, const int n[3], const float spacin
   int roi_old[6];
   for (int k = 0; k < 6; ++k) { roi_old[k] = H.cfg.dose_roi[k]; H.cfg.dose_roi[k] = roi[k]; }
   if (ctx->has_device) {
-    const int dev = ctx->dev.device_id;
-    HIP_TRY(hipSetDevice(dev));
+    HIP_TRY(hipSetDevice(ctx->dev.device_id));
     HIP_TRY(hipDeviceSynchronize());
-    DeviceModel old = std::move(ctx->dev);  // stays allocated until the new model is up
-    ctx->dev = DeviceModel();
+    DeviceModel fresh;
     try {
-      upload_model(*ctx, dev);
+      fresh = upload_model(H, ctx->dev.device_id);
+      for (int k = 0; k < 5; ++k) fresh.sched[k] = ctx->dev.sched[k];  // the tuned FAST schedule survives a geometry change
+      fresh.sched_set = ctx->dev.sched_set;
+      apply_schedule(fresh);
     } catch (...) {
-      ctx->dev.release();
-      ctx->dev = std::move(old);
       std::swap(H.voxels, v);
       std::swap(H.mat, mat);
       for (int k = 0; k < 6; ++k) H.cfg.dose_roi[k] = roi_old[k];
       throw;
     }
-    for (int k = 0; k < 5; ++k) ctx->dev.sched[k] = old.sched[k];  // the tuned FAST schedule survives a geometry change
-    ctx->dev.sched_set = old.sched_set;
-    apply_schedule(ctx->dev);
-    old.release();  // NB: the dose tallies belong to a geometry and restart from zero with the new one
+    ctx->dev = std::move(fresh);  // `fresh` now holds the superseded model and frees it.  NB: the dose tallies belong to a geometry and restart from zero with the new one
   }
   ctx->host_voxels_stale = false;
   ctx->table_cache.clear();
@@ -165,42 +165,15 @@ int mcgpu_warp_geometry(mcgpu_ctx* ctx, const float* displacement, int frame, in
         if (D.compact_of[m] == mc) H.voxels.density_max[m] = std::max(H.voxels.density_max[m], D.palette_host[2 * e]);
     }
   rebuild_woodcock(H.mat, H.voxels.density_max);
-  {
-    std::vector<float> wood(2 * (size_t)H.mat.num_values);
-    for (int i = 0; i < H.mat.num_values; ++i) { wood[2 * i] = H.mat.woodcock[i].x; wood[2 * i + 1] = H.mat.woodcock[i].y; }
-    HIP_TRY(hipMemcpy(D.woodcock, wood.data(), wood.size() * 4, hipMemcpyHostToDevice));
-    const std::vector<float> coarse = coarse_woodcock(H);  // the FAST kernel's LDS copy of the majorant follows the table
-    HIP_TRY(hipMemcpy(D.wood_coarse, coarse.data(), coarse.size() * 4, hipMemcpyHostToDevice));
-  }
+  refresh_woodcock(H, D);
   D.sub_mixed = (int)out[16];
   // The object region (box and, where it pays, elliptic cylinder) and the first-level codes follow from the bricks' classification
-  // exactly as at upload (mark_exterior_region): 64 KB of `brick_first` come down, 16 KB of codes go up.
-  {
-    const int had_exterior = D.has_exterior;
-    std::vector<unsigned short> bf((size_t)D.brick_count);
-    HIP_TRY(hipMemcpy(bf.data(), D.brick_first, bf.size() * 2, hipMemcpyDeviceToHost));
-    std::vector<unsigned char> object((size_t)D.brick_count), exterior;
-    for (int b = 0; b < D.brick_count; ++b) object[(size_t)b] = (bf[(size_t)b] == 0x100 || (int)bf[(size_t)b] != D.background) ? 1 : 0;
-    mark_exterior_region(H, D, object, true, exterior);
-    std::vector<unsigned char> bricks((size_t)D.brick_bytes, 0xFF);
-    D.bricks_mixed = 0;
-    for (int b = 0; b < D.brick_count; ++b) {
-      const int code = exterior[(size_t)b] ? 14 : (bf[(size_t)b] == 0x100 ? 0xF : (int)D.code_of[bf[(size_t)b]]);
-      D.bricks_mixed += (code == 0xF);
-      const int sh = (b & 1) * 4;
-      bricks[(size_t)(b >> 1)] = (unsigned char)((bricks[(size_t)(b >> 1)] & ~(0xF << sh)) | (code << sh));
-    }
-    HIP_TRY(hipMemcpy(D.bricks, bricks.data(), bricks.size(), hipMemcpyHostToDevice));
-    for (int a = 0; a < 3; ++a) { D.cold_host.objbox_lo[a] = D.objbox_lo[a]; D.cold_host.objbox_hi[a] = D.objbox_hi[a]; }
-    for (int a = 0; a < 2; ++a) { D.cold_host.ell_c[a] = D.ell_c[a]; D.cold_host.ell_inv[a] = D.ell_inv[a]; }
-    if (D.has_exterior) {
-      // code 14 means "background outside the object region": its palette slot must name the background even when the BASE
-      // geometry had no exterior (its object box spanned the whole brick grid) and the warp made one
-      D.brick_palette[14] = D.background;
-      D.cold_host.brick_palette[14] = D.background;
-    }
-    if (D.has_exterior || had_exterior) HIP_TRY(hipMemcpy(D.cold, &D.cold_host, sizeof D.cold_host, hipMemcpyHostToDevice));
-  }
+  // exactly as at upload (brick_codes): 64 KB of `brick_first` come down, 16 KB of codes go up.
+  std::vector<unsigned short> bf((size_t)D.brick_count);
+  HIP_TRY(hipMemcpy(bf.data(), D.brick_first, bf.size() * 2, hipMemcpyDeviceToHost));
+  const std::vector<unsigned char> bricks = brick_codes(H, D, bf, true);
+  HIP_TRY(hipMemcpy(D.bricks, bricks.data(), bricks.size(), hipMemcpyHostToDevice));
+  refresh_cold_geometry(D);
   ctx->host_voxels_stale = true;
   ctx->table_cache.clear();
   return 0;

@@ -1,7 +1,7 @@
 #pragma once
 // engine_internal.hpp -- what the translation units of the engine library share: the device model, the context, error plumbing.
-// (engine.cpp: the C ABI of a context; model_device.cpp: device upload and launch arguments; engine_geometry.cpp: geometry changes of
-// a resident context; engine_kat.cpp: known-answer and micro-benchmark hooks.)
+// (engine.cpp: the C ABI of a context; model_device.cpp: the device model's memory, its upload in stages (upload_model) and launch
+// arguments; engine_geometry.cpp: geometry changes of a resident context; engine_kat.cpp: known-answer and micro-benchmark hooks.)
 //
 // Replaces init_CUDA_device (docker/mcgpu/MC-GPU_v1.3.cu:2454-2724) and the per-projection driver of
 // main() (:667-1056).  Compiled with hipcc; every HIP call lives here or in the kernel TUs.
@@ -56,6 +56,31 @@ int set_error(int code, const std::string& msg);  // engine.cpp: records the cal
     if (_e != hipSuccess) throw Error(-1, std::string("!!HIP ERROR!! ") + #expr + ": " + hipGetErrorString(_e)); \
   } while (0)
 
+// What a device model allocated -- device buffers, pinned host buffers, streams, events -- released on its device (the one current at
+// the first allocation) when the owner goes.  Move-only: a move assignment hands the previous contents to the source, which frees them.
+class DeviceOwner {
+ public:
+  DeviceOwner() = default;
+  DeviceOwner(const DeviceOwner&) = delete;
+  DeviceOwner& operator=(const DeviceOwner&) = delete;
+  DeviceOwner(DeviceOwner&& o) noexcept { swap(o); }
+  DeviceOwner& operator=(DeviceOwner&& o) noexcept { swap(o); return *this; }
+  ~DeviceOwner();
+  void* device_bytes(size_t bytes);
+  void* pinned_bytes(size_t bytes, unsigned int flags);
+  hipStream_t stream(unsigned int flags);
+  hipEvent_t event(unsigned int flags);
+  void free(void* device_buffer);  // one device buffer before the owner goes
+
+ private:
+  void claim();
+  void swap(DeviceOwner& o) noexcept;
+  int device_ = -1;
+  std::vector<void*> buffers_, pinned_;
+  std::vector<hipStream_t> streams_;
+  std::vector<hipEvent_t> events_;
+};
+
 struct DeviceModel {
   int device_id = -1;
   void* vol = nullptr;
@@ -94,8 +119,6 @@ struct DeviceModel {
   int has_exterior = 0, bricks_exterior = 0;
   float objbox_lo[3] = {0, 0, 0}, objbox_hi[3] = {0, 0, 0};
   float ell_c[2] = {0, 0}, ell_inv[2] = {0, 0};  // elliptic cylinder around the object (TrackCold::ell_*); inv 0: none
-  int num_spectrum_bins = 0;
-  int shell_first[kMaxMaterials] = {0};
   LdsLayout lds;
   TrackCold* cold = nullptr;      // device copy of the rarely used table pointers
   TrackCold cold_host;            // its host image (re-uploaded when a tuning knob changes)
@@ -111,9 +134,7 @@ struct DeviceModel {
   unsigned long long* scratch_image = nullptr;  // device tally of mcgpu_run_projection (allocated on first use)
   float *woodcock = nullptr, *mfp = nullptr, *mfp_tot = nullptr;
   float* wood_coarse = nullptr;  // FAST: majorant per coarse energy bin (LdsLayout::wood), rebuilt with the Woodcock table
-  unsigned short* sig_mid = nullptr;  // cross-section brackets (FAST flight step), see upload_model
-  float* sig_w = nullptr;
-  int sig_shift = -1, sig_coarse = 0;
+  int sig_shift = -1;            // cross-section brackets of the FAST flight step (model_device.cpp: sigma_brackets), -1: none
   int sched[5] = {40, 12, 44, 12, 40};  // FAST batching thresholds {compton, rayleigh, new, flyable_low, swap_batch} (mcgpu_set_fast_schedule; re-tuned in round 5: profiles/r05p_*)
   bool sched_set = false;              // mcgpu_set_fast_schedule has been called (else the scheduler's own defaults apply)
   // Tuning knobs of the environment.  Read when the device model is built and again only by
@@ -130,46 +151,18 @@ struct DeviceModel {
     int segment_loop = -1;                           // MCGPU_SEGMENT_LOOP: -1 chosen from the model (make_args), 0 / 1 forced
     int fast_sched = 0;                              // MCGPU_FAST_SCHED: 0 per-wave pools, 1 workgroup-level pool (fixes the LDS layout: read at upload)
   } knobs;
-  std::vector<float> sig_tot_host;    // copy of mfp_tot for the bracket builder
-  float *xco = nullptr, *pco = nullptr, *aco = nullptr, *bco = nullptr;
-  unsigned char *itl = nullptr, *itu = nullptr;
-  float *fco = nullptr, *uico = nullptr, *fj0 = nullptr;
-  float* s0_bounds = nullptr;  // COMPAT: TrackCold::s0_bounds
-  float s0_emin = 0.f, s0_inv_w = 0.f;
-  int* noscco = nullptr;
-  float* shell_cut = nullptr;      // FAST: alias table of the Compton shell weights
-  unsigned char* shell_alias = nullptr;
-  float *espc = nullptr, *cutoff = nullptr;
-  short* alias = nullptr;
   int nmat = 0;
   int compact_of[kMaxMaterials];
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;
   bool timed = false;
   int num_cus = 256;
-  std::vector<void*> allocations;
+  DeviceOwner mem;  // everything above that points to device or pinned memory, streams and events; freed with the model
 
   template <typename T>
   T* put(const std::vector<T>& host) {
-    void* d = nullptr;
-    const size_t bytes = std::max<size_t>(host.size() * sizeof(T), 16);
-    HIP_TRY(hipMalloc(&d, bytes));
-    allocations.push_back(d);
+    void* d = mem.device_bytes(std::max<size_t>(host.size() * sizeof(T), 16));
     if (!host.empty()) HIP_TRY(hipMemcpy(d, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
     return (T*)d;
-  }
-  void release() {
-    for (void* p : allocations) (void)hipFree(p);
-    allocations.clear();
-    for (AsciiSlot& a : ascii) {
-      if (a.text_host) (void)hipHostFree(a.text_host);
-      if (a.rows_host) (void)hipHostFree(a.rows_host);
-      if (a.copy_stream) (void)hipStreamDestroy(a.copy_stream);
-      if (a.ready) (void)hipEventDestroy(a.ready);
-      a = AsciiSlot();
-    }
-    if (ev_start) (void)hipEventDestroy(ev_start);
-    if (ev_stop) (void)hipEventDestroy(ev_stop);
-    ev_start = ev_stop = nullptr;
   }
 };
 
@@ -186,11 +179,15 @@ struct mcgpu_ctx {
 namespace mcgpu {
 // model_device.cpp
 std::vector<float> coarse_woodcock(const HostModel& H);  // LdsLayout::wood from the host's Woodcock table
-void mark_exterior_region(const HostModel& H, DeviceModel& D, const std::vector<unsigned char>& object, bool have_background,
-                          std::vector<unsigned char>& exterior);  // object box + elliptic cylinder, exterior bricks (upload and device-side warp)
+// Shared by the upload of a geometry and the device-side geometry change (mcgpu_warp_geometry):
+constexpr unsigned short kMixedBrick = 0x100;  // brick_first entry of a brick that holds more than one palette entry (as geometry_device.hip writes it)
+std::vector<unsigned char> brick_codes(const HostModel& H, DeviceModel& D, const std::vector<unsigned short>& brick_first,
+                                       bool have_background);  // object region, exterior bricks, packed first-level codes
+void refresh_woodcock(const HostModel& H, DeviceModel& D);      // the Woodcock table and its coarse LDS copy, from H
+void refresh_cold_geometry(DeviceModel& D);                     // object region and brick palette into TrackCold, uploaded if changed
 void read_env_knobs(DeviceModel& D);
 void apply_schedule(DeviceModel& D);
-void upload_model(mcgpu_ctx& C, int device_id);
+DeviceModel upload_model(const HostModel& H, int device_id);
 void require(bool ok, int code, const char* msg);
 TrackArgs make_args(const mcgpu_ctx& C, int p);
 void sync_host_voxels(mcgpu_ctx& C);

@@ -27,9 +27,9 @@ std::vector<float> coarse_woodcock(const HostModel& H) {
 // is corner air -- an elliptic cylinder (axis z) with the centre and the aspect of that box, scaled until every corner of every
 // object brick is inside; kept only if it puts at least 5 % of the box's bricks outside (else the kernel would pay its quadratic
 // for nothing; MCGPU_NO_ELLIPSE: never).  Sets D.objbox_*, D.ell_*, D.has_exterior, D.bricks_exterior; exterior[b] != 0: brick b lies
-// wholly outside the region.  Shared by the upload of a geometry and by the device-side geometry change (mcgpu_warp_geometry).
-void mark_exterior_region(const HostModel& H, DeviceModel& D, const std::vector<unsigned char>& object, bool have_background,
-                          std::vector<unsigned char>& exterior) {
+// wholly outside the region.  Shared by the upload of a geometry and by the device-side geometry change (brick_codes).
+static void mark_exterior_region(const HostModel& H, DeviceModel& D, const std::vector<unsigned char>& object, bool have_background,
+                                 std::vector<unsigned char>& exterior) {
   const int k = D.brick_shift, nvx[3] = {H.voxels.n[0], H.voxels.n[1], H.voxels.n[2]};
   exterior.assign((size_t)D.brick_count, 0);
   D.has_exterior = 0;
@@ -212,290 +212,490 @@ static std::vector<float> build_s0_bounds(const HostModel& H, const int* compact
   return bounds;
 }
 
-// Build the palette-compressed volume and the compact-material tables and upload everything.
-void upload_model(mcgpu_ctx& C, int device_id) {
-  const HostModel& H = C.host;
-  DeviceModel& D = C.dev;
+// ---- device memory of a model
+void DeviceOwner::claim() {
+  if (device_ < 0) HIP_TRY(hipGetDevice(&device_));
+}
+void* DeviceOwner::device_bytes(size_t bytes) {
+  claim();
+  void* p = nullptr;
+  HIP_TRY(hipMalloc(&p, bytes));
+  buffers_.push_back(p);
+  return p;
+}
+void* DeviceOwner::pinned_bytes(size_t bytes, unsigned int flags) {
+  claim();
+  void* p = nullptr;
+  HIP_TRY(hipHostMalloc(&p, bytes, flags));
+  pinned_.push_back(p);
+  return p;
+}
+hipStream_t DeviceOwner::stream(unsigned int flags) {
+  claim();
+  hipStream_t s = nullptr;
+  HIP_TRY(hipStreamCreateWithFlags(&s, flags));
+  streams_.push_back(s);
+  return s;
+}
+hipEvent_t DeviceOwner::event(unsigned int flags) {
+  claim();
+  hipEvent_t e = nullptr;
+  HIP_TRY(hipEventCreateWithFlags(&e, flags));
+  events_.push_back(e);
+  return e;
+}
+void DeviceOwner::free(void* device_buffer) {
+  auto it = std::find(buffers_.begin(), buffers_.end(), device_buffer);
+  if (it == buffers_.end()) return;
+  buffers_.erase(it);
+  HIP_TRY(hipFree(device_buffer));
+}
+void DeviceOwner::swap(DeviceOwner& o) noexcept {
+  std::swap(device_, o.device_);
+  buffers_.swap(o.buffers_);
+  pinned_.swap(o.pinned_);
+  streams_.swap(o.streams_);
+  events_.swap(o.events_);
+}
+DeviceOwner::~DeviceOwner() {
+  if (device_ < 0) return;
+  int current = -1;
+  const bool restore = hipGetDevice(&current) == hipSuccess && current != device_;
+  (void)hipSetDevice(device_);
+  for (void* p : buffers_) (void)hipFree(p);
+  for (void* p : pinned_) (void)hipHostFree(p);
+  for (hipStream_t s : streams_) (void)hipStreamDestroy(s);
+  for (hipEvent_t e : events_) (void)hipEventDestroy(e);
+  if (restore) (void)hipSetDevice(current);
+}
+
+// ---- stages of upload_model
+static void select_device(DeviceModel& D, int device_id) {
   HIP_TRY(hipSetDevice(device_id));
   D.device_id = device_id;
   hipDeviceProp_t prop;
   HIP_TRY(hipGetDeviceProperties(&prop, device_id));
   D.num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   read_env_knobs(D);
+}
 
-  // compact material numbering
-  D.nmat = 0;
-  for (int m = 0; m < kMaxMaterials; ++m) D.compact_of[m] = H.mat.used[m] ? D.nmat++ : -1;
-  const int nmat = D.nmat, nv = H.mat.num_values;
+static int compact_numbering(const HostModel& H, int compact_of[kMaxMaterials]) {
+  int n = 0;
+  for (int m = 0; m < kMaxMaterials; ++m) compact_of[m] = H.mat.used[m] ? n++ : -1;
+  return n;
+}
 
-  // ---- volume -> palette indices
+static int total_shells(const HostModel& H, const int* compact_of) {
+  int shells = 0;
+  for (int m = 0; m < kMaxMaterials; ++m)
+    if (compact_of[m] >= 0) shells += std::min(H.mat.noscco[m], kMaxShells);
+  return shells;
+}
+
+// One entry {density, bits(compact material)} per distinct (material, density) pair of the volume, and each voxel's entry.
+struct Palette {
+  std::vector<float> entries;
+  std::vector<uint16_t> index;  // incomplete when `overflow`
+  bool overflow = false;        // more than 65536 pairs: the volume is stored raw
+  int size() const { return (int)(entries.size() / 2); }
+};
+
+static Palette build_palette(const HostModel& H, const int* compact_of) {
   const size_t nvox = H.voxels.count();
+  Palette P;
+  P.index.resize(nvox);
   std::unordered_map<uint64_t, int> index_of;
-  std::vector<float> palette;  // {density, bits(mat_c)}
-  std::vector<uint16_t> idx16(nvox);
-  bool overflow = false;
-  {
-    uint64_t last_key = ~0ull;
-    int last_idx = -1;
-    for (size_t i = 0; i < nvox; ++i) {
-      uint32_t db;
-      memcpy(&db, &H.voxels.density[i], 4);
-      const uint64_t key = ((uint64_t)H.voxels.material[i] << 32) | db;
-      if (key != last_key) {
-        auto it = index_of.find(key);
-        if (it == index_of.end()) {
-          if (index_of.size() >= 65536) { overflow = true; break; }
-          const int mc = D.compact_of[H.voxels.material[i] - 1];
-          if (mc < 0) throw Error(-2, "!!ERROR!! A voxel uses material " + std::to_string((int)H.voxels.material[i]) + " but no data file was given for it.");
-          float mcf;
-          memcpy(&mcf, &mc, 4);
-          last_idx = (int)index_of.size();
-          index_of.emplace(key, last_idx);
-          palette.push_back(H.voxels.density[i]);
-          palette.push_back(mcf);
-        } else {
-          last_idx = it->second;
-        }
-        last_key = key;
+  auto key_of = [](int material, float density) { uint32_t db; memcpy(&db, &density, 4); return ((uint64_t)material << 32) | db; };
+  auto add = [&](uint64_t key, float density, int mc) {
+    float mcf;
+    memcpy(&mcf, &mc, 4);
+    const int at = (int)index_of.size();
+    index_of.emplace(key, at);
+    P.entries.push_back(density);
+    P.entries.push_back(mcf);
+    return at;
+  };
+  uint64_t last_key = ~0ull;
+  int last_idx = -1;
+  for (size_t i = 0; i < nvox; ++i) {
+    const uint64_t key = key_of(H.voxels.material[i], H.voxels.density[i]);
+    if (key != last_key) {
+      auto it = index_of.find(key);
+      if (it != index_of.end()) {
+        last_idx = it->second;
+      } else {
+        if (index_of.size() >= 65536) { P.overflow = true; return P; }
+        const int mc = compact_of[H.voxels.material[i] - 1];
+        if (mc < 0) throw Error(-2, "!!ERROR!! A voxel uses material " + std::to_string((int)H.voxels.material[i]) + " but no data file was given for it.");
+        last_idx = add(key, H.voxels.density[i], mc);
       }
-      idx16[i] = (uint16_t)last_idx;
+      last_key = key;
     }
+    P.index[i] = (uint16_t)last_idx;
   }
-  if (overflow) {
-    D.vol_kind = kVolRaw;
-    std::vector<float> raw(2 * nvox);
-    for (size_t i = 0; i < nvox; ++i) {
-      const int mc = D.compact_of[H.voxels.material[i] - 1];
-      if (mc < 0) throw Error(-2, "!!ERROR!! A voxel uses a material without data file.");
-      raw[2 * i] = H.voxels.density[i];
-      memcpy(&raw[2 * i + 1], &mc, 4);
+  // the reference's default for voxels warped in from outside the volume (air: material 1 at 0.0013 g/cm^3,
+  // cbctmc/mc/geometry.py:403-418) gets an entry of a u8 palette even when no voxel holds it yet, so that a geometry can be
+  // warped on the device without touching the palette (mcgpu_warp_geometry)
+  const uint64_t air = key_of(1, 0.0013f);
+  if (P.size() < 256 && compact_of[0] >= 0 && !index_of.count(air)) add(air, 0.0013f, compact_of[0]);
+  return P;
+}
+
+static std::vector<float> raw_volume(const HostModel& H, const int* compact_of) {
+  const size_t nvox = H.voxels.count();
+  std::vector<float> raw(2 * nvox);
+  for (size_t i = 0; i < nvox; ++i) {
+    const int mc = compact_of[H.voxels.material[i] - 1];
+    if (mc < 0) throw Error(-2, "!!ERROR!! A voxel uses a material without data file.");
+    raw[2 * i] = H.voxels.density[i];
+    memcpy(&raw[2 * i + 1], &mc, 4);
+  }
+  return raw;
+}
+
+// Device layout of a u8 volume: tiles of 4x4x4 voxels = one 64-byte sector = one sub-brick of the second level (device_model.hpp:
+// tiled_voxel); the padding voxels of edge tiles repeat the tile's first voxel and are never addressed.
+static std::vector<uint8_t> tiled_volume(const VoxelGrid& V, const std::vector<uint8_t>& idx8) {
+  const int nx = V.n[0], ny = V.n[1], nz = V.n[2];
+  const unsigned int snx = (unsigned int)((nx + 3) >> 2), sny = (unsigned int)((ny + 3) >> 2), snz = (unsigned int)((nz + 3) >> 2);
+  const size_t tiles = (size_t)snx * sny * snz;
+  if (tiles * 64 >= (1ULL << 31)) throw Error(-2, "!!ERROR!! voxel grid too large for the 32-bit voxel index of the kernel");
+  std::vector<uint8_t> tiled(tiles * 64);
+  for (size_t t = 0; t < tiles; ++t) {
+    const int x0 = (int)(t % snx) << 2, y0 = (int)((t / snx) % sny) << 2, z0 = (int)(t / ((size_t)snx * sny)) << 2;
+    const uint8_t pad = idx8[((size_t)z0 * ny + y0) * nx + x0];
+    for (int dz = 0; dz < 4; ++dz)
+      for (int dy = 0; dy < 4; ++dy)
+        for (int dx = 0; dx < 4; ++dx) {
+          const int x = x0 + dx, y = y0 + dy, z = z0 + dz;
+          tiled[t * 64 + (size_t)(dz * 16 + dy * 4 + dx)] = (x < nx && y < ny && z < nz) ? idx8[((size_t)z * ny + y) * nx + x] : pad;
+        }
+  }
+  return tiled;
+}
+
+// ---- LDS image of the kernels (byte offsets; track_common.inc: stage_tables): its regions in order, each on 16 bytes, closed by
+// the FAST kernel's cross-section brackets at their shift.  One description for the brick-grid budget and for the layout.
+constexpr int kLdsPerWorkgroup = 160 * 1024 / 2;  // two 1024-thread workgroups per CU
+// The budget that picks brick_shift bounds the image instead of laying it out: every region start and the end may round up by
+// 16 bytes -- 13 such boundaries counted in full -- so that the choice never depends on the padding between the regions.
+constexpr int kLdsAlignSlack = 13 * 16;
+
+struct LdsPlan {
+  struct Region {
+    int LdsLayout::*at;
+    int bytes;
+  };
+  std::vector<Region> regions;  // the brackets excluded
+  int nv = 0, nmat = 0;
+};
+
+static int coarse_bins(int nv, int shift) { return (nv + (1 << shift) - 1) >> shift; }
+
+static LdsPlan plan_lds(const HostModel& H, const DeviceModel& D, int brick_bytes) {
+  const int ns = std::min(H.spectrum.num_bins + 1, kMaxSpectrumBins) + 1;
+  const bool u8 = D.vol_kind == kVolU8;
+  LdsPlan P;
+  P.nv = H.mat.num_values;
+  P.nmat = D.nmat;
+  P.regions = {{&LdsLayout::shells, std::max(total_shells(H, D.compact_of), 1) * 16},
+               {&LdsLayout::nosc, std::max(D.nmat, 1) * 8},
+               {&LdsLayout::espc, ns * 4},
+               {&LdsLayout::cutoff, ns * 4},
+               {&LdsLayout::alias, ns * 2},
+               {&LdsLayout::pal, u8 ? (16 + D.palette_size) * 8 : 0},
+               {&LdsLayout::brick, u8 ? brick_bytes : 0},
+               {&LdsLayout::dose_mat, 2 * kMaxMaterials * 8},
+               {&LdsLayout::slots, kSlotWords * kPoolParked * kPoolBlockThreads * 4}};  // the COMPAT kernel's image ends at `slots`
+  if (D.knobs.fast_sched == 1) P.regions.push_back({&LdsLayout::queues, kPoolQueueBytes});
+  P.regions.push_back({&LdsLayout::wood, coarse_bins(P.nv, kWoodShift) * 4});
+  return P;
+}
+
+// sig_shift < 0: no brackets
+static LdsLayout lay_out_lds(const LdsPlan& P, int sig_shift) {
+  LdsLayout Y{};
+  int off = 0;
+  auto take = [&](int bytes) { off = (off + 15) / 16 * 16; const int at = off; off += bytes; return at; };
+  for (const LdsPlan::Region& r : P.regions) Y.*r.at = take(r.bytes);
+  Y.sig_mid = Y.sig_w = off;
+  if (sig_shift >= 0) {
+    const int nc = coarse_bins(P.nv, sig_shift);
+    Y.sig_mid = take(nc * P.nmat * 2);
+    Y.sig_w = take(nc * 4);
+  }
+  Y.total = (off + 15) / 16 * 16;
+  return Y;
+}
+
+// Bound of the image without its brick grid, with brackets no coarser than 2^9 table bins.
+static long lds_bytes_without_bricks(const LdsPlan& P) {
+  const int nc = coarse_bins(P.nv, 9);
+  long bytes = kLdsAlignSlack + (long)nc * P.nmat * 2 + nc * 4;
+  for (const LdsPlan::Region& r : P.regions) bytes += r.bytes;
+  return bytes;
+}
+
+// Brick grid: the smallest power-of-two brick (>= 4 voxels) that keeps the grid within the LDS budget.  The FAST kernel wants two
+// 1024-thread workgroups per CU, i.e. an LDS image of at most 80 KB.  Everything but the brick grid is fixed by the materials in
+// use (22 tissue materials: 458 Compton shells = 7.3 KB against 1.4 KB for the Catphan set), so the grid gets what is left after
+// the tables, the history slots and a coarse bracket table.
+static int choose_brick_shift(const HostModel& H, const DeviceModel& D) {
+  auto nb = [](int n, int sh) { return (n + (1 << sh) - 1) >> sh; };
+  const char* mb = knob_str("MCGPU_MAX_BRICKS");  // tuning knob: a coarser grid frees LDS
+  long max_bricks = mb ? std::min<long>(std::max<long>(atol(mb), 1), kMaxBricks) : kMaxBricks;
+  const long left = kLdsPerWorkgroup - lds_bytes_without_bricks(plan_lds(H, D, 0));
+  if (left > 0) max_bricks = std::min(max_bricks, std::max(2 * left, 512L));
+  int k = 2;
+  while ((long)nb(H.voxels.n[0], k) * nb(H.voxels.n[1], k) * nb(H.voxels.n[2], k) > max_bricks) ++k;
+  return k;
+}
+
+// Per brick and per sub-brick of 4^3 voxels: the palette entry of a homogeneous one, kMixedBrick for one that holds more.  One pass
+// over the voxels (134 M at 512^3).
+struct BrickClasses {
+  std::vector<unsigned short> brick, sub;
+};
+
+static BrickClasses classify_bricks(const HostModel& H, const DeviceModel& D, const std::vector<uint8_t>& idx8) {
+  const int nx = H.voxels.n[0], ny = H.voxels.n[1], nz = H.voxels.n[2], k = D.brick_shift;
+  BrickClasses c;
+  c.brick.assign((size_t)D.brick_count, 0xFFFF);
+  c.sub.assign((size_t)D.sub_n[0] * D.sub_n[1] * D.sub_n[2], 0xFFFF);
+  auto see = [](unsigned short& f, int v) {
+    if (f == 0xFFFF) f = (unsigned short)v;
+    else if (f != v) f = kMixedBrick;
+  };
+  for (int z = 0; z < nz; ++z)
+    for (int y = 0; y < ny; ++y) {
+      const size_t row = ((size_t)z * ny + y) * nx;
+      unsigned short* brow = &c.brick[((size_t)(z >> k) * D.brick_n[1] + (y >> k)) * D.brick_n[0]];
+      unsigned short* srow = &c.sub[((size_t)(z >> 2) * D.sub_n[1] + (y >> 2)) * D.sub_n[0]];
+      for (int x = 0; x < nx; ++x) {
+        const int v = idx8[row + x];
+        see(brow[x >> k], v);
+        see(srow[x >> 2], v);
+      }
     }
+  return c;
+}
+
+// 4-bit codes: the 14 most frequent palette entries among homogeneous bricks get codes 0..13, every other brick (mixed, or a rarer
+// homogeneous one) is 0xF = "read the voxel"; code 14 = EXTERIOR (brick_codes).  Returns whether any brick is homogeneous background.
+static bool assign_codes(DeviceModel& D, const std::vector<unsigned short>& brick_first) {
+  std::vector<long> homogeneous(256, 0);
+  for (unsigned short f : brick_first)
+    if (f < kMixedBrick) ++homogeneous[f];
+  std::vector<int> order(256);
+  for (int i = 0; i < 256; ++i) order[i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return homogeneous[a] > homogeneous[b]; });
+  for (int i = 0; i < 256; ++i) D.code_of[i] = 0xF;
+  for (int c = 0; c < 16; ++c) D.brick_palette[c] = 0;
+  for (int c = 0; c < 14; ++c)
+    if (homogeneous[order[c]] > 0) { D.code_of[order[c]] = (unsigned char)c; D.brick_palette[c] = order[c]; }
+  D.background = order[0];
+  return homogeneous[order[0]] > 0;
+}
+
+// 4-bit code tables (bricks, sub-bricks): code i in the low nibble of byte i / 2 for even i, in the high one for odd i; a spare
+// nibble is 0xF.
+static std::vector<unsigned char> pack_codes(const std::vector<unsigned char>& codes) {
+  std::vector<unsigned char> packed((codes.size() + 1) / 2, 0xFF);
+  for (size_t i = 0; i < codes.size(); ++i) {
+    const int sh = (int)(i & 1) * 4;
+    packed[i >> 1] = (unsigned char)((packed[i >> 1] & ~(0xF << sh)) | (codes[i] << sh));
+  }
+  return packed;
+}
+
+// Exterior (mark_exterior_region): outside the object region every brick is homogeneous background, and the FAST kernel crosses
+// it with one exact free-path sample instead of delta-tracking through it (track_pool.inc: exterior_hop).  Sets the region,
+// D.bricks_mixed and D.bricks_exterior.
+std::vector<unsigned char> brick_codes(const HostModel& H, DeviceModel& D, const std::vector<unsigned short>& brick_first,
+                                       bool have_background) {
+  std::vector<unsigned char> object((size_t)D.brick_count), exterior;
+  for (int b = 0; b < D.brick_count; ++b) object[(size_t)b] = brick_first[(size_t)b] != D.background ? 1 : 0;
+  mark_exterior_region(H, D, object, have_background, exterior);
+  std::vector<unsigned char> codes((size_t)D.brick_count);
+  D.bricks_mixed = 0;
+  for (int b = 0; b < D.brick_count; ++b) {
+    const unsigned short f = brick_first[(size_t)b];
+    codes[(size_t)b] = exterior[(size_t)b] ? 14 : (f == kMixedBrick ? 0xF : D.code_of[f]);
+    D.bricks_mixed += (codes[(size_t)b] == 0xF);
+  }
+  // code 14 means "background outside the object region": its palette slot must name the background even when the BASE
+  // geometry of a warp had no exterior (its object box spanned the whole brick grid) and the warp made one
+  if (D.has_exterior) D.brick_palette[14] = D.background;
+  return pack_codes(codes);
+}
+
+static void upload_sub_bricks(DeviceModel& D, const std::vector<unsigned short>& sub_first) {
+  // Second-level codes (same 4-bit coding, no EXTERIOR): a flight step that lands in a mixed brick asks this table,
+  // which stays in L2 (0.5-1 MB), before it asks the volume (64-128 MiB: Infinity Cache / HBM).  On a body-filling
+  // volume 78 % of the tissue voxels lie in mixed 16^3 bricks but only 24 % in mixed 4^3 sub-bricks, and the voxel
+  // gathers of the flight step were what bound that workload (1.45 KB of fabric traffic per history at 5e9 histories/s).
+  // Round 2 (x-fastest rows): worth its dependent L2 round trip where most bricks a photon meets are mixed (thorax +24 %).
+  // Round 3: the volume is stored in 4x4x4 TILES, one tile = one 64-byte sector = one sub-brick -- asking the volume
+  // directly now costs one sector like asking this table, without the second dependent round trip, and the tile it
+  // brings in serves the neighbouring voxels of later photons.  Measured on one box (tools/ab_second_level.sh): thorax 14.27
+  // -> 13.68 ms, CIRS 6.52 -> 6.25, Catphan 4.17 -> 4.09 with the table OFF.  So it is off unless MCGPU_SUB_BRICKS=1
+  // asks for it (kept: it halves the fabric traffic where that is what binds, and the tests hold both routes to the
+  // same tallies).
+  const char* knob = knob_str("MCGPU_SUB_BRICKS");
+  const bool on = knob && atoi(knob) != 0;
+  std::vector<unsigned char> codes(sub_first.size());
+  D.sub_mixed = 0;
+  for (size_t b = 0; b < sub_first.size(); ++b) {
+    codes[b] = (on && sub_first[b] < kMixedBrick) ? D.code_of[sub_first[b]] : 0xF;
+    D.sub_mixed += (codes[b] == 0xF);
+  }
+  D.sub = on ? D.put(pack_codes(codes)) : nullptr;
+}
+
+static void upload_tile_records(const HostModel& H, DeviceModel& D, const std::vector<uint8_t>& idx8, const std::vector<unsigned short>& brick_first) {
+  // Tile records (device_model.hpp: TileRecord): the hot set of the voxel gathers is every 64-byte tile of every MIXED brick.
+  // Where that set is far beyond the L2 (4 MB per XCD) -- body-filling tissue volumes: thorax 22 MB -- the launch is bound by
+  // the line fills of those gathers (profiles/r04p_*: ONE more cold line per mixed step doubles the thorax's kernel time, one
+  // more load from the SAME line costs 2 %), and the records shrink the set fourfold.  MCGPU_TILE_RECORDS=0/1 overrides.
+  const int nx = H.voxels.n[0], ny = H.voxels.n[1], nz = H.voxels.n[2], k = D.brick_shift;
+  const size_t nsub = (size_t)D.sub_n[0] * D.sub_n[1] * D.sub_n[2];
+  long long hot_tiles = 0;
+  for (size_t b = 0; b < nsub; ++b) {
+    const int bx = (int)((b % D.sub_n[0]) << 2) >> k, by = (int)(((b / D.sub_n[0]) % D.sub_n[1]) << 2) >> k, bz = (int)((b / ((size_t)D.sub_n[0] * D.sub_n[1])) << 2) >> k;
+    hot_tiles += brick_first[((size_t)bz * D.brick_n[1] + by) * D.brick_n[0] + bx] == kMixedBrick ? 1 : 0;
+  }
+  D.tiles_in_mixed_bricks = hot_tiles;
+  const char* knob = knob_str("MCGPU_TILE_RECORDS");
+  const bool on = knob ? atoi(knob) != 0 : hot_tiles * 64 > (8LL << 20);
+  D.rec_n[0] = (D.sub_n[0] + 1) >> 1; D.rec_n[1] = (D.sub_n[1] + 1) >> 1; D.rec_n[2] = (D.sub_n[2] + 1) >> 1;
+  D.tile_rec = nullptr;
+  if (!on) return;
+  std::vector<TileRecord> rec((size_t)D.rec_n[0] * D.rec_n[1] * D.rec_n[2] * 8, TileRecord{0u, 0u, 0ULL});
+  for (size_t t = 0; t < nsub; ++t) {
+    const unsigned int tx = (unsigned int)(t % D.sub_n[0]), ty = (unsigned int)((t / D.sub_n[0]) % D.sub_n[1]), tz = (unsigned int)(t / ((size_t)D.sub_n[0] * D.sub_n[1]));
+    short v64[64];
+    for (int v = 0; v < 64; ++v) {
+      const int x = (int)(tx << 2) + (v & 3), y = (int)(ty << 2) + ((v >> 2) & 3), z = (int)(tz << 2) + (v >> 4);
+      v64[v] = (x >= nx || y >= ny || z >= nz) ? (short)-1 : (short)idx8[((size_t)z * ny + y) * nx + x];  // padding of an edge tile: never addressed
+    }
+    rec[tile_record_index(tx, ty, tz, (unsigned int)D.rec_n[0], (unsigned int)(D.rec_n[0] * D.rec_n[1]))] = encode_tile_record(v64);
+  }
+  D.tile_rec = D.put(rec);
+}
+
+// u8 volumes: brick grid, first- and second-level codes, tile records
+static void upload_brick_grids(const HostModel& H, DeviceModel& D, const std::vector<uint8_t>& idx8) {
+  const int k = choose_brick_shift(H, D);
+  D.brick_shift = k;
+  for (int a = 0; a < 3; ++a) {
+    D.brick_n[a] = (H.voxels.n[a] + (1 << k) - 1) >> k;
+    D.sub_n[a] = (H.voxels.n[a] + 3) >> 2;
+  }
+  D.brick_count = D.brick_n[0] * D.brick_n[1] * D.brick_n[2];
+  D.brick_bytes = (D.brick_count + 1) / 2;
+  const BrickClasses c = classify_bricks(H, D, idx8);
+  const bool have_background = assign_codes(D, c.brick);
+  D.bricks = D.put(brick_codes(H, D, c.brick, have_background));
+  upload_sub_bricks(D, c.sub);
+  upload_tile_records(H, D, idx8, c.brick);
+}
+
+// The palette-compressed volume: u8 (tiled, with brick grids) up to 256 palette entries, u16 up to 65536, else raw.
+static void upload_volume(const HostModel& H, DeviceModel& D) {
+  const Palette P = build_palette(H, D.compact_of);
+  if (P.overflow) {
+    const std::vector<float> raw = raw_volume(H, D.compact_of);
+    D.vol_kind = kVolRaw;
     D.vol = D.put(raw);
     D.vol_bytes = raw.size() * 4;
     D.palette_size = 0;
     D.palette = D.put(std::vector<float>(2, 0.f));
-  } else if (index_of.size() <= 256) {
-    D.vol_kind = kVolU8;
-    {
-      // the reference's default for voxels warped in from outside the volume (air: material 1 at 0.0013 g/cm^3,
-      // cbctmc/mc/geometry.py:403-418) gets a palette entry even when no voxel holds it yet, so that a geometry can be
-      // warped on the device without touching the palette (mcgpu_warp_geometry)
-      const float air = 0.0013f;
-      uint32_t db;
-      memcpy(&db, &air, 4);
-      const uint64_t key = ((uint64_t)1 << 32) | db;
-      if (!index_of.count(key) && index_of.size() < 256 && D.compact_of[0] >= 0) {
-        const int mc = D.compact_of[0];
-        float mcf;
-        memcpy(&mcf, &mc, 4);
-        index_of.emplace(key, (int)index_of.size());
-        palette.push_back(air);
-        palette.push_back(mcf);
-      }
-    }
-    D.palette_host = palette;
-    std::vector<uint8_t> idx8(nvox);
-    for (size_t i = 0; i < nvox; ++i) idx8[i] = (uint8_t)idx16[i];
-    D.palette_size = (int)index_of.size();
-    D.palette = D.put(palette);
-    // brick grid: smallest power-of-two brick (>= 4 voxels) that keeps the grid within the LDS budget
-    const int nx = H.voxels.n[0], ny = H.voxels.n[1], nz = H.voxels.n[2];
-    {
-      // device layout: tiles of 4x4x4 voxels = one 64-byte sector = one sub-brick of the second level (device_model.hpp:
-      // tiled_voxel); the padding voxels of edge tiles repeat the tile's first voxel and are never addressed
-      const unsigned int snx = (unsigned int)((nx + 3) >> 2), sny = (unsigned int)((ny + 3) >> 2), snz = (unsigned int)((nz + 3) >> 2);
-      const size_t tiles = (size_t)snx * sny * snz;
-      if (tiles * 64 >= (1ULL << 31)) throw Error(-2, "!!ERROR!! voxel grid too large for the 32-bit voxel index of the kernel");
-      std::vector<uint8_t> tiled(tiles * 64);
-      for (size_t t = 0; t < tiles; ++t) {
-        const int x0 = (int)(t % snx) << 2, y0 = (int)((t / snx) % sny) << 2, z0 = (int)(t / ((size_t)snx * sny)) << 2;
-        const uint8_t pad = idx8[((size_t)z0 * ny + y0) * nx + x0];
-        for (int dz = 0; dz < 4; ++dz)
-          for (int dy = 0; dy < 4; ++dy)
-            for (int dx = 0; dx < 4; ++dx) {
-              const int x = x0 + dx, y = y0 + dy, z = z0 + dz;
-              tiled[t * 64 + (size_t)(dz * 16 + dy * 4 + dx)] = (x < nx && y < ny && z < nz) ? idx8[((size_t)z * ny + y) * nx + x] : pad;
-            }
-      }
-      D.vol = D.put(tiled);
-      D.vol_bytes = tiled.size();
-    }
-    int k = 2;
-    auto nb = [&](int n, int sh) { return (n + (1 << sh) - 1) >> sh; };
-    const char* mb = knob_str("MCGPU_MAX_BRICKS");  // tuning knob: a coarser grid frees LDS
-    long max_bricks = mb ? std::min<long>(std::max<long>(atol(mb), 1), kMaxBricks) : kMaxBricks;
-    {
-      // The FAST kernel wants two 1024-thread workgroups per CU, i.e. an LDS image of at most 80 KB.  Everything but the
-      // brick grid is fixed by the materials in use (22 tissue materials: 458 Compton shells = 7.3 KB against 1.4 KB for
-      // the Catphan set), so the grid gets what is left after the tables, the history slots and a coarse bracket table.
-      int shells = 0;
-      for (int m = 0; m < kMaxMaterials; ++m)
-        if (D.compact_of[m] >= 0) shells += std::min(H.mat.noscco[m], kMaxShells);
-      const int ns = std::min(H.spectrum.num_bins + 1, kMaxSpectrumBins) + 1;
-      const int nc = (nv + (1 << 9) - 1) >> 9;  // brackets no coarser than 2^9 table bins
-      const long fixed = std::max(shells, 1) * 16 + std::max(nmat, 1) * 8 + ns * 10 + (16 + (long)index_of.size()) * 8 + 2 * kMaxMaterials * 8 +
-                         (long)kSlotWords * kPoolParked * kPoolBlockThreads * 4 + (D.knobs.fast_sched == 1 ? kPoolQueueBytes : 0) + nc * nmat * 2 + nc * 4 +
-                         12 * 16 +
-                         (((nv + (1 << kWoodShift) - 1) >> kWoodShift) * 4 + 16);
-      const long left = 160 * 1024 / 2 - fixed;
-      if (left > 0) max_bricks = std::min(max_bricks, std::max(2 * left, 512L));
-    }
-    while ((long)nb(nx, k) * nb(ny, k) * nb(nz, k) > max_bricks) ++k;
-    D.brick_shift = k;
-    D.brick_n[0] = nb(nx, k); D.brick_n[1] = nb(ny, k); D.brick_n[2] = nb(nz, k);
-    D.brick_count = D.brick_n[0] * D.brick_n[1] * D.brick_n[2];
-    std::vector<int> first(D.brick_count, -1);
-    std::vector<unsigned char> mixed(D.brick_count, 0);
-    // second level: sub-bricks of 4^3 voxels, dense over the volume (first2: palette entry, 0x100 = mixed)
-    D.sub_n[0] = (nx + 3) >> 2; D.sub_n[1] = (ny + 3) >> 2; D.sub_n[2] = (nz + 3) >> 2;
-    const size_t nsub = (size_t)D.sub_n[0] * D.sub_n[1] * D.sub_n[2];
-    std::vector<short> first2(nsub, -1);
-    for (int z = 0; z < nz; ++z)
-      for (int y = 0; y < ny; ++y) {
-        const size_t row = ((size_t)z * ny + y) * nx;
-        const size_t brow = ((size_t)(z >> k) * D.brick_n[1] + (y >> k)) * D.brick_n[0];
-        const size_t srow = ((size_t)(z >> 2) * D.sub_n[1] + (y >> 2)) * D.sub_n[0];
-        for (int x = 0; x < nx; ++x) {
-          const int b = (int)(brow + (x >> k)), v = idx8[row + x];
-          if (first[b] < 0) first[b] = v;
-          else if (first[b] != v) mixed[b] = 1;
-          short& f2 = first2[srow + (x >> 2)];
-          if (f2 < 0) f2 = (short)v;
-          else if (f2 != v) f2 = 0x100;
-        }
-      }
-    // 4-bit codes: the 14 most frequent palette entries among homogeneous bricks get codes 0..13, every other
-    // brick (mixed, or a rarer homogeneous one) is 0xF = "read the voxel"; code 14 = EXTERIOR (below)
-    std::vector<long> homogeneous(256, 0);
-    for (int b = 0; b < D.brick_count; ++b)
-      if (!mixed[b] && first[b] >= 0) ++homogeneous[first[b]];
-    std::vector<int> order(256);
-    for (int i = 0; i < 256; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return homogeneous[a] > homogeneous[b]; });
-    int code_of[256];
-    for (int i = 0; i < 256; ++i) code_of[i] = 0xF;
-    for (int c = 0; c < 14; ++c) {
-      D.brick_palette[c] = 0;
-      if (homogeneous[order[c]] > 0) { code_of[order[c]] = c; D.brick_palette[c] = order[c]; }
-    }
-    D.brick_palette[14] = D.brick_palette[15] = 0;
-    for (int i = 0; i < 256; ++i) D.code_of[i] = (unsigned char)code_of[i];
-    D.background = order[0];
-    // Exterior (mark_exterior_region): outside the object region every brick is homogeneous background, and the FAST kernel crosses
-    // it with one exact free-path sample instead of delta-tracking through it (track_pool.inc: exterior_hop).
-    {
-      const int bg = order[0];
-      std::vector<unsigned char> object((size_t)D.brick_count, 0);
-      for (int b = 0; b < D.brick_count; ++b) object[(size_t)b] = (mixed[b] || first[b] != bg) ? 1 : 0;
-      std::vector<unsigned char> exterior;
-      mark_exterior_region(H, D, object, homogeneous[bg] > 0, exterior);
-      for (int b = 0; b < D.brick_count; ++b)
-        if (exterior[(size_t)b]) first[b] = -2;  // marks EXTERIOR for the encoder below
-      if (D.has_exterior) D.brick_palette[14] = bg;
-    }
-    D.brick_bytes = (D.brick_count + 1) / 2;
-    std::vector<unsigned char> bricks(D.brick_bytes, 0xFF);
-    D.bricks_mixed = 0;
-    D.bricks_exterior = 0;
-    for (int b = 0; b < D.brick_count; ++b) {
-      int code = 0xF;
-      if (first[b] == -2) { code = 14; ++D.bricks_exterior; }
-      else if (!mixed[b] && first[b] >= 0) code = code_of[first[b]];
-      D.bricks_mixed += (code == 0xF);
-      const int sh = (b & 1) * 4;
-      bricks[b >> 1] = (unsigned char)((bricks[b >> 1] & ~(0xF << sh)) | (code << sh));
-    }
-    D.bricks = D.put(bricks);
-    {
-      // Second-level codes (same 4-bit coding, no EXTERIOR): a flight step that lands in a mixed brick asks this table,
-      // which stays in L2 (0.5-1 MB), before it asks the volume (64-128 MiB: Infinity Cache / HBM).  On a body-filling
-      // volume 78 % of the tissue voxels lie in mixed 16^3 bricks but only 24 % in mixed 4^3 sub-bricks, and the voxel
-      // gathers of the flight step were what bound that workload (1.45 KB of fabric traffic per history at 5e9 histories/s).
-      std::vector<unsigned char> sub((nsub + 1) / 2, 0xFF);
-      D.sub_mixed = 0;
-      // Round 2 (x-fastest rows): worth its dependent L2 round trip where most bricks a photon meets are mixed (thorax +24 %).
-      // Round 3: the volume is stored in 4x4x4 TILES, one tile = one 64-byte sector = one sub-brick -- asking the volume
-      // directly now costs one sector like asking this table, without the second dependent round trip, and the tile it
-      // brings in serves the neighbouring voxels of later photons.  Measured on one box (tools/ab_second_level.sh): thorax 14.27
-      // -> 13.68 ms, CIRS 6.52 -> 6.25, Catphan 4.17 -> 4.09 with the table OFF.  So it is off unless MCGPU_SUB_BRICKS=1
-      // asks for it (kept: it halves the fabric traffic where that is what binds, and the tests hold both routes to the
-      // same tallies).
-      const char* knob = knob_str("MCGPU_SUB_BRICKS");
-      const bool off = knob ? atoi(knob) == 0 : true;
-      for (size_t b = 0; b < nsub; ++b) {
-        const int code = (!off && first2[b] >= 0 && first2[b] < 0x100) ? code_of[first2[b]] : 0xF;
-        D.sub_mixed += (code == 0xF);
-        const int sh = (int)(b & 1) * 4;
-        sub[b >> 1] = (unsigned char)((sub[b >> 1] & ~(0xF << sh)) | (code << sh));
-      }
-      D.sub = off ? nullptr : D.put(sub);
-    }
-    {
-      // Tile records (device_model.hpp: TileRecord): the hot set of the voxel gathers is every 64-byte tile of every MIXED brick.
-      // Where that set is far beyond the L2 (4 MB per XCD) -- body-filling tissue volumes: thorax 22 MB -- the launch is bound by
-      // the line fills of those gathers (profiles/r04p_*: ONE more cold line per mixed step doubles the thorax's kernel time, one
-      // more load from the SAME line costs 2 %), and the records shrink the set fourfold.  MCGPU_TILE_RECORDS=0/1 overrides.
-      long long hot_tiles = 0;
-      for (size_t b = 0; b < nsub; ++b) {
-        const int bx = (int)((b % D.sub_n[0]) << 2) >> k, by = (int)(((b / D.sub_n[0]) % D.sub_n[1]) << 2) >> k, bz = (int)((b / ((size_t)D.sub_n[0] * D.sub_n[1])) << 2) >> k;
-        hot_tiles += mixed[((size_t)bz * D.brick_n[1] + by) * D.brick_n[0] + bx] ? 1 : 0;
-      }
-      D.tiles_in_mixed_bricks = hot_tiles;
-      const char* knob = knob_str("MCGPU_TILE_RECORDS");
-      const bool on = knob ? atoi(knob) != 0 : hot_tiles * 64 > (8LL << 20);
-      D.rec_n[0] = (D.sub_n[0] + 1) >> 1; D.rec_n[1] = (D.sub_n[1] + 1) >> 1; D.rec_n[2] = (D.sub_n[2] + 1) >> 1;
-      D.tile_rec = nullptr;
-      if (on) {
-        std::vector<TileRecord> rec((size_t)D.rec_n[0] * D.rec_n[1] * D.rec_n[2] * 8, TileRecord{0u, 0u, 0ULL});
-        for (size_t t = 0; t < nsub; ++t) {
-          const unsigned int tx = (unsigned int)(t % D.sub_n[0]), ty = (unsigned int)((t / D.sub_n[0]) % D.sub_n[1]), tz = (unsigned int)(t / ((size_t)D.sub_n[0] * D.sub_n[1]));
-          short v64[64];
-          for (int v = 0; v < 64; ++v) {
-            const int x = (int)(tx << 2) + (v & 3), y = (int)(ty << 2) + ((v >> 2) & 3), z = (int)(tz << 2) + (v >> 4);
-            v64[v] = (x >= nx || y >= ny || z >= nz) ? (short)-1 : (short)idx8[((size_t)z * ny + y) * nx + x];  // padding of an edge tile: never addressed
-          }
-          const TileRecord r = encode_tile_record(v64);
-          rec[tile_record_index(tx, ty, tz, (unsigned int)D.rec_n[0], (unsigned int)(D.rec_n[0] * D.rec_n[1]))] = r;
-        }
-        D.tile_rec = D.put(rec);
-      }
-    }
-  } else {
-    D.vol_kind = kVolU16;
-    D.vol = D.put(idx16);
-    D.vol_bytes = nvox * 2;
-    D.palette_size = (int)index_of.size();
-    D.palette = D.put(palette);
+    return;
   }
+  D.palette_size = P.size();
+  D.palette = D.put(P.entries);
+  if (P.size() > 256) {
+    D.vol_kind = kVolU16;
+    D.vol = D.put(P.index);
+    D.vol_bytes = P.index.size() * 2;
+    return;
+  }
+  D.vol_kind = kVolU8;
+  D.palette_host = P.entries;
+  const std::vector<uint8_t> idx8(P.index.begin(), P.index.end());
+  const std::vector<uint8_t> tiled = tiled_volume(H.voxels, idx8);
+  D.vol = D.put(tiled);
+  D.vol_bytes = tiled.size();
+  upload_brick_grids(H, D, idx8);
+}
 
-  // ---- cross-section records
-  std::vector<float> wood(2 * (size_t)nv), rec(8 * (size_t)nv * nmat, 0.f);
-  for (int i = 0; i < nv; ++i) { wood[2 * i] = H.mat.woodcock[i].x; wood[2 * i + 1] = H.mat.woodcock[i].y; }
+// Cross-section records: 8 floats {a, b, pmax, 0} per (compact material, table bin), material-major rows (track_common.inc: table_row)
+static std::vector<float> cross_section_records(const HostModel& H, const int* compact_of, int nmat) {
+  const int nv = H.mat.num_values;
+  std::vector<float> rec(8 * (size_t)nv * nmat, 0.f);
   for (int i = 0; i < nv; ++i)
     for (int m = 0; m < kMaxMaterials; ++m) {
-      const int mc = D.compact_of[m];
+      const int mc = compact_of[m];
       if (mc < 0) continue;
-      float* r = &rec[8 * ((size_t)mc * nv + i)];  // material-major rows (track_common.inc: table_row)
+      float* r = &rec[8 * ((size_t)mc * nv + i)];
       const Float3& a = H.mat.a[(size_t)i * kMaxMaterials + m];
       const Float3& b = H.mat.b[(size_t)i * kMaxMaterials + m];
       r[0] = a.x; r[1] = a.y; r[2] = a.z; r[3] = b.x; r[4] = b.y; r[5] = b.z;
       r[6] = H.mat.pmax[(size_t)(i + 1) * kMaxMaterials + m];
-      r[7] = 0.f;
     }
-  D.woodcock = D.put(wood);
-  D.wood_coarse = D.put(coarse_woodcock(H));
-  D.mfp = D.put(rec);
-  {
-    std::vector<float> tot(2 * (size_t)nv * nmat);
-    for (size_t k = 0; k < (size_t)nv * nmat; ++k) { tot[2 * k] = rec[8 * k]; tot[2 * k + 1] = rec[8 * k + 3]; }
-    D.mfp_tot = D.put(tot);
-    // Brackets of the total cross section for the FAST flight step: per (coarse energy bin = 2^shift table bins,
-    // material) the centre of [min, max] of a_tot + b_tot * E over the coarse bin as fp16, and per coarse bin one
-    // relative half width covering every material.  A step whose random number falls outside
-    // [1 - m*hi, 1 - m*lo) is decided from LDS alone; only the narrow band in between fetches the exact value, so the
-    // decisions are those of the exact test.  The LDS image takes the finest table that still leaves two workgroups per CU.
-    D.sig_tot_host = tot;
+  return rec;
+}
+
+// {a_tot, b_tot} of every record
+static std::vector<float> total_cross_sections(const std::vector<float>& rec) {
+  std::vector<float> tot(rec.size() / 4);
+  for (size_t k = 0; k < rec.size() / 8; ++k) { tot[2 * k] = rec[8 * k]; tot[2 * k + 1] = rec[8 * k + 3]; }
+  return tot;
+}
+
+// The Woodcock table and the FAST kernel's LDS copy of its majorant (coarse_woodcock): allocated at upload, overwritten when a
+// geometry change rebuilds the table.
+void refresh_woodcock(const HostModel& H, DeviceModel& D) {
+  std::vector<float> wood(2 * (size_t)H.mat.num_values);
+  for (int i = 0; i < H.mat.num_values; ++i) { wood[2 * i] = H.mat.woodcock[i].x; wood[2 * i + 1] = H.mat.woodcock[i].y; }
+  const std::vector<float> coarse = coarse_woodcock(H);
+  if (!D.woodcock) {
+    D.woodcock = D.put(wood);
+    D.wood_coarse = D.put(coarse);
+    return;
   }
+  HIP_TRY(hipMemcpy(D.woodcock, wood.data(), wood.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(D.wood_coarse, coarse.data(), coarse.size() * 4, hipMemcpyHostToDevice));
+}
+
+// FAST Compton sampler (track_common.inc: compton_draw): Walker alias table of the shell weights f_i of material m (Vose's
+// construction, in double): column s keeps shell s below cut[s] and maps the rest of the column to alias[s].  Entries at
+// [shell * nmat + mc].
+static void shell_alias_table(const HostModel& H, int m, int mc, int nmat, float* cut, unsigned char* alias) {
+  const int n = std::min(H.mat.noscco[m], kMaxShells);
+  double F = 0.0;
+  for (int s = 0; s < n; ++s) F += (double)H.mat.fco[m + s * kMaxMaterials];
+  std::vector<double> q(n);
+  std::vector<int> small, large;
+  for (int s = 0; s < n; ++s) {
+    q[s] = F > 0.0 ? (double)H.mat.fco[m + s * kMaxMaterials] * n / F : 1.0;
+    (q[s] < 1.0 ? small : large).push_back(s);
+    cut[s * nmat + mc] = 1.0f;
+    alias[s * nmat + mc] = (unsigned char)s;
+  }
+  while (!small.empty() && !large.empty()) {
+    const int a = small.back(), b = large.back();
+    small.pop_back();
+    cut[a * nmat + mc] = (float)q[a];
+    alias[a * nmat + mc] = (unsigned char)b;
+    q[b] -= 1.0 - q[a];
+    if (q[b] < 1.0) { large.pop_back(); small.push_back(b); }
+  }
+}
+
+// Rayleigh and Compton tables per compact material, the shell alias table and the COMPAT kernel's S0 bounds, into TrackCold
+static void upload_interaction_tables(const HostModel& H, DeviceModel& D) {
+  const int nmat = D.nmat;
   std::vector<float> xco(kRayleighPoints * nmat), pco(xco), aco(xco), bco(xco);
   std::vector<unsigned char> itl(kRayleighPoints * nmat), itu(itl);
   std::vector<float> fco(kMaxShells * nmat, 0.f), uico(fco), fj0(fco);
@@ -519,182 +719,185 @@ void upload_model(mcgpu_ctx& C, int device_id) {
       fj0[s * nmat + mc] = H.mat.fj0[m + s * kMaxMaterials];
     }
     nosc[mc] = H.mat.noscco[m];
-    {
-      // FAST Compton sampler (track_common.inc: compton_draw): Walker alias table of the shell weights f_i (Vose's
-      // construction, in double): column k keeps shell k below cut[k] and maps the rest of the column to alias[k]
-      const int n = std::min(H.mat.noscco[m], kMaxShells);
-      double F = 0.0;
-      for (int s = 0; s < n; ++s) F += (double)H.mat.fco[m + s * kMaxMaterials];
-      std::vector<double> q(n);
-      std::vector<int> small, large;
-      for (int s = 0; s < n; ++s) {
-        q[s] = F > 0.0 ? (double)H.mat.fco[m + s * kMaxMaterials] * n / F : 1.0;
-        (q[s] < 1.0 ? small : large).push_back(s);
-        shell_cut[s * nmat + mc] = 1.0f;
-        shell_alias[s * nmat + mc] = (unsigned char)s;
-      }
-      while (!small.empty() && !large.empty()) {
-        const int a = small.back(), b = large.back();
-        small.pop_back();
-        shell_cut[a * nmat + mc] = (float)q[a];
-        shell_alias[a * nmat + mc] = (unsigned char)b;
-        q[b] -= 1.0 - q[a];
-        if (q[b] < 1.0) { large.pop_back(); small.push_back(b); }
-      }
-    }
+    shell_alias_table(H, m, mc, nmat, shell_cut.data(), shell_alias.data());
   }
-  D.xco = D.put(xco); D.pco = D.put(pco); D.aco = D.put(aco); D.bco = D.put(bco);
-  D.itl = D.put(itl); D.itu = D.put(itu);
-  D.fco = D.put(fco); D.uico = D.put(uico); D.fj0 = D.put(fj0);
-  D.s0_bounds = D.put(build_s0_bounds(H, D.compact_of, nmat, &D.s0_emin, &D.s0_inv_w));  // COMPAT: bounds of S0 per (material, energy bin)
-  D.noscco = D.put(nosc);
-  D.shell_cut = D.put(shell_cut);
-  D.shell_alias = D.put(shell_alias);
-  D.espc = D.put(std::vector<float>(H.spectrum.espc, H.spectrum.espc + kMaxSpectrumBins));
-  D.cutoff = D.put(std::vector<float>(H.spectrum.cutoff, H.spectrum.cutoff + kMaxSpectrumBins));
-  D.alias = D.put(std::vector<short>(H.spectrum.alias, H.spectrum.alias + kMaxSpectrumBins));
-  // ---- LDS image of the kernels (byte offsets; track_common.inc: stage_tables)
-  {
-    LdsLayout& Y = D.lds;
-    int off = 0;
-    auto take = [&](int bytes, int align) { off = (off + align - 1) / align * align; const int at = off; off += bytes; return at; };
-    const int ns = std::min(H.spectrum.num_bins + 1, kMaxSpectrumBins) + 1;
-    int total_shells = 0;
-    for (int m = 0; m < kMaxMaterials; ++m)
-      if (D.compact_of[m] >= 0) { D.shell_first[D.compact_of[m]] = total_shells; total_shells += std::min(H.mat.noscco[m], kMaxShells); }
-    Y.shells = take(std::max(total_shells, 1) * 16, 16);
-    Y.nosc = take(std::max(nmat, 1) * 8, 16);
-    Y.espc = take(ns * 4, 16);
-    Y.cutoff = take(ns * 4, 16);
-    Y.alias = take(ns * 2, 16);
-    Y.pal = take(D.vol_kind == kVolU8 ? (16 + D.palette_size) * 8 : 0, 16);
-    Y.brick = take(D.vol_kind == kVolU8 ? D.brick_bytes : 0, 16);
-    Y.dose_mat = take(2 * kMaxMaterials * 8, 16);
-    Y.slots = take(0, 16);  // the COMPAT kernel's image ends here
-    take(kSlotWords * kPoolParked * kPoolBlockThreads * 4, 16);
-    Y.queues = D.knobs.fast_sched == 1 ? take(kPoolQueueBytes, 16) : 0;
-    Y.wood = take(((nv + (1 << kWoodShift) - 1) >> kWoodShift) * 4, 16);
-    Y.sig_mid = Y.sig_w = off;
-    D.sig_shift = -1;
-    if (!knob_set("MCGPU_NO_BRACKETS") && nmat > 0) {
-      const int budget = 160 * 1024 / 2;  // two 1024-thread workgroups per CU
-      for (int shift = 6; shift <= 12; ++shift) {
-        const int nc = (nv + (1 << shift) - 1) >> shift;
-        const int need = (off + 15) / 16 * 16 + (nc * nmat * 2 + 15) / 16 * 16 + (nc * 4 + 15) / 16 * 16;
-        if (need > budget) continue;
-        D.sig_shift = shift;
-        D.sig_coarse = nc;
-        Y.sig_mid = take(nc * nmat * 2, 16);
-        Y.sig_w = take(nc * 4, 16);
-        break;
+  TrackCold& cold = D.cold_host;
+  cold.xco = D.put(xco); cold.pco = D.put(pco); cold.aco = D.put(aco); cold.bco = D.put(bco);
+  cold.itl = D.put(itl); cold.itu = D.put(itu);
+  cold.fco = D.put(fco); cold.uico = D.put(uico); cold.fj0 = D.put(fj0);
+  cold.s0_bounds = D.put(build_s0_bounds(H, D.compact_of, nmat, &cold.s0_emin, &cold.s0_inv_w));  // COMPAT: bounds of S0 per (material, energy bin)
+  cold.noscco = D.put(nosc);
+  cold.shell_cut = D.put(shell_cut);
+  cold.shell_alias = D.put(shell_alias);
+}
+
+static void upload_spectrum(const HostModel& H, DeviceModel& D) {
+  TrackCold& cold = D.cold_host;
+  cold.espc = D.put(std::vector<float>(H.spectrum.espc, H.spectrum.espc + kMaxSpectrumBins));
+  cold.cutoff = D.put(std::vector<float>(H.spectrum.cutoff, H.spectrum.cutoff + kMaxSpectrumBins));
+  cold.alias = D.put(std::vector<short>(H.spectrum.alias, H.spectrum.alias + kMaxSpectrumBins));
+}
+
+static unsigned short to_half(float f) {  // round to nearest even; inputs are positive normal numbers
+  uint32_t x;
+  memcpy(&x, &f, 4);
+  const int e = (int)((x >> 23) & 0xFF) - 127 + 15;
+  uint32_t m = x & 0x7FFFFF;
+  if (e <= 0) return 0;
+  if (e >= 31) return 0x7BFF;
+  uint32_t h = ((uint32_t)e << 10) | (m >> 13);
+  const uint32_t rem = m & 0x1FFF;
+  if (rem > 0x1000 || (rem == 0x1000 && (h & 1))) ++h;
+  return (unsigned short)std::min<uint32_t>(h, 0x7BFF);
+}
+
+static double from_half(unsigned short h) { return std::ldexp((double)((h & 0x3FF) | 0x400), (int)(h >> 10) - 25); }
+
+// Brackets of the total cross section for the FAST flight step: per (coarse energy bin = 2^shift table bins, material) the centre
+// of [min, max] of a_tot + b_tot * E over the coarse bin as fp16, and per coarse bin one relative half width covering every
+// material.  A step whose random number falls outside [1 - m*hi, 1 - m*lo) is decided from LDS alone; only the narrow band in
+// between fetches the exact value, so the decisions are those of the exact test.  The LDS image takes the finest table that still
+// leaves two workgroups per CU (lay_out_lds_and_brackets).
+struct SigmaBrackets {
+  std::vector<unsigned short> mid;  // [coarse bin * nmat + mc]
+  std::vector<float> w;             // [coarse bin]
+};
+
+static SigmaBrackets sigma_brackets(const HostModel& H, const std::vector<float>& tot, int nmat, int shift) {
+  const int nv = H.mat.num_values, nc = coarse_bins(nv, shift);
+  const double e0 = H.mat.e0, ide = H.mat.ide;
+  SigmaBrackets B{std::vector<unsigned short>((size_t)nc * nmat, 0), std::vector<float>(nc, 0.f)};
+  for (int c = 0; c < nc; ++c) {
+    double wmax = 0.0;
+    for (int mc = 0; mc < nmat; ++mc) {
+      double lo = 1e300, hi = -1e300;
+      for (int i = c << shift; i < std::min(nv, (c + 1) << shift); ++i) {
+        const double a = tot[2 * ((size_t)mc * nv + i)], b = tot[2 * ((size_t)mc * nv + i) + 1];
+        // the kernel evaluates a + b * E for E in [E_i, E_{i+1}) (one table bin; a little beyond for float rounding)
+        const double ea = e0 + (i - 0.01) / ide, eb = e0 + (i + 1.01) / ide;
+        lo = std::min(lo, std::min(a + b * ea, a + b * eb));
+        hi = std::max(hi, std::max(a + b * ea, a + b * eb));
       }
+      if (!(lo > 0.0)) lo = std::min(1e-30, hi > 0.0 ? hi : 1e-30);
+      const unsigned short hbits = to_half((float)(0.5 * (lo + hi)));
+      B.mid[(size_t)c * nmat + mc] = hbits;
+      const double m = from_half(hbits);
+      if (hbits == 0 || hbits == 0x7BFF || !(m > 0.0)) { wmax = 1e30; continue; }  // not representable: the band is everything
+      wmax = std::max(wmax, std::max((hi - m) / m, (m - lo) / m));
     }
-    Y.total = (off + 15) / 16 * 16;
+    B.w[c] = (float)std::min(wmax * 1.001 + 1e-5, 1e30);
   }
-  if (D.sig_shift >= 0) {
-    const int nc = D.sig_coarse, shift = D.sig_shift;
-    auto to_half = [](float f) -> unsigned short {  // round to nearest even; inputs are positive normal numbers
-      uint32_t x; memcpy(&x, &f, 4);
-      const int e = (int)((x >> 23) & 0xFF) - 127 + 15;
-      uint32_t m = x & 0x7FFFFF;
-      if (e <= 0) return 0;
-      if (e >= 31) return 0x7BFF;
-      uint32_t h = ((uint32_t)e << 10) | (m >> 13);
-      const uint32_t rem = m & 0x1FFF;
-      if (rem > 0x1000 || (rem == 0x1000 && (h & 1))) ++h;
-      return (unsigned short)std::min<uint32_t>(h, 0x7BFF);
-    };
-    auto from_half = [](unsigned short h) -> double { return std::ldexp((double)((h & 0x3FF) | 0x400), (int)(h >> 10) - 25); };
-    std::vector<unsigned short> mid((size_t)nc * nmat, 0);
-    std::vector<float> wv(nc, 0.f);
-    const double e0 = H.mat.e0, ide = H.mat.ide;
-    for (int c = 0; c < nc; ++c) {
-      double wmax = 0.0;
-      for (int mc = 0; mc < nmat; ++mc) {
-        double lo = 1e300, hi = -1e300;
-        for (int i = c << shift; i < std::min(nv, (c + 1) << shift); ++i) {
-          const double a = D.sig_tot_host[2 * ((size_t)mc * nv + i)], b = D.sig_tot_host[2 * ((size_t)mc * nv + i) + 1];
-          // the kernel evaluates a + b * E for E in [E_i, E_{i+1}) (one table bin; a little beyond for float rounding)
-          const double ea = e0 + (i - 0.01) / ide, eb = e0 + (i + 1.01) / ide;
-          lo = std::min(lo, std::min(a + b * ea, a + b * eb));
-          hi = std::max(hi, std::max(a + b * ea, a + b * eb));
-        }
-        if (!(lo > 0.0)) lo = std::min(1e-30, hi > 0.0 ? hi : 1e-30);
-        const unsigned short hbits = to_half((float)(0.5 * (lo + hi)));
-        mid[(size_t)c * nmat + mc] = hbits;
-        const double m = from_half(hbits);
-        if (hbits == 0 || hbits == 0x7BFF || !(m > 0.0)) { wmax = 1e30; continue; }  // not representable: the band is everything
-        wmax = std::max(wmax, std::max((hi - m) / m, (m - lo) / m));
-      }
-      wv[c] = (float)std::min(wmax * 1.001 + 1e-5, 1e30);
-    }
-    D.sig_mid = D.put(mid);
-    D.sig_w = D.put(wv);
+  return B;
+}
+
+// The final LDS image with the finest bracket table that fits kLdsPerWorkgroup (MCGPU_NO_BRACKETS: none), and the brackets
+static void lay_out_lds_and_brackets(const HostModel& H, DeviceModel& D, const std::vector<float>& tot) {
+  const LdsPlan P = plan_lds(H, D, D.brick_bytes);
+  D.sig_shift = -1;
+  if (!knob_set("MCGPU_NO_BRACKETS") && D.nmat > 0)
+    for (int shift = 6; shift <= 12 && D.sig_shift < 0; ++shift)
+      if (lay_out_lds(P, shift).total <= kLdsPerWorkgroup) D.sig_shift = shift;
+  D.lds = lay_out_lds(P, D.sig_shift);
+  if (D.sig_shift < 0) return;
+  const SigmaBrackets B = sigma_brackets(H, tot, D.nmat, D.sig_shift);
+  D.cold_host.sig_mid = D.put(B.mid);
+  D.cold_host.sig_w = D.put(B.w);
+}
+
+// dose tallies (read_input :1868-1893, init_CUDA_device :2636-2657,2694-2720)
+static void upload_dose_tallies(const HostModel& H, DeviceModel& D) {
+  const SimConfig& cfg = H.cfg;
+  if (cfg.flag_material_dose == 1) {
+    D.dose_materials = D.put(std::vector<unsigned long long>(2 * kMaxMaterials, 0ULL));
+    D.dose_flags |= kDoseMaterials;
   }
-  D.num_spectrum_bins = H.spectrum.num_bins;
-  {
-    TrackCold cold;
-    memset(&cold, 0, sizeof cold);
-    cold.xco = D.xco; cold.pco = D.pco; cold.aco = D.aco; cold.bco = D.bco; cold.itl = D.itl; cold.itu = D.itu;
-    cold.fco = D.fco; cold.uico = D.uico; cold.fj0 = D.fj0; cold.noscco = D.noscco;
-    cold.s0_bounds = D.s0_bounds; cold.s0_emin = D.s0_emin; cold.s0_inv_w = D.s0_inv_w;
-    cold.shell_cut = D.shell_cut; cold.shell_alias = D.shell_alias;
-    cold.espc = D.espc; cold.cutoff = D.cutoff; cold.alias = D.alias;
-    cold.bricks = D.bricks;
-    cold.sig_mid = D.sig_mid; cold.sig_w = D.sig_w;
-    cold.wood_coarse = D.wood_coarse;
-    cold.woodcock = D.woodcock;
-    cold.lds = D.lds;
-    for (int c = 0; c < 16; ++c) cold.brick_palette[c] = D.brick_palette[c];
-    // dose tallies (read_input :1868-1893, init_CUDA_device :2636-2657,2694-2720)
-    const SimConfig& cfg = H.cfg;
-    if (cfg.flag_material_dose == 1) {
-      D.dose_materials = D.put(std::vector<unsigned long long>(2 * kMaxMaterials, 0ULL));
-      D.dose_flags |= kDoseMaterials;
-    }
-    if (cfg.dose_roi[1] > -1) {
-      D.dose_roi_voxels = (size_t)(cfg.dose_roi[1] - cfg.dose_roi[0] + 1) * (size_t)(cfg.dose_roi[3] - cfg.dose_roi[2] + 1) *
-                          (size_t)(cfg.dose_roi[5] - cfg.dose_roi[4] + 1);
-      D.dose_voxels = D.put(std::vector<unsigned long long>(2 * D.dose_roi_voxels, 0ULL));
-      D.dose_flags |= kDoseVoxels;
-    }
-    cold.dose_voxels = D.dose_voxels;
-    cold.dose_materials = D.dose_materials;
-    cold.mfp = D.mfp; cold.e0 = H.mat.e0; cold.ide = H.mat.ide;
-    for (int k = 0; k < 3; ++k) cold.bbox[k] = H.voxels.size_bbox[k];
-    for (int k = 0; k < 6; ++k) cold.dose_roi[k] = cfg.dose_roi[k];
-    for (int m = 0; m < kMaxMaterials; ++m)
-      if (D.compact_of[m] >= 0) cold.material_of_compact[D.compact_of[m]] = m;
-    for (int m = 0; m < kMaxMaterials; ++m) cold.shell_first[m] = D.shell_first[m];
-    for (int k = 0; k < 3; ++k) { cold.objbox_lo[k] = D.objbox_lo[k]; cold.objbox_hi[k] = D.objbox_hi[k]; }
-    for (int k = 0; k < 2; ++k) { cold.ell_c[k] = D.ell_c[k]; cold.ell_inv[k] = D.ell_inv[k]; }
-    cold.thresh_compton = cold.thresh_rayleigh = cold.thresh_new = cold.flyable_low = cold.swap_batch = cold.trade_slots = -1;  // apply_schedule
-    {
-      // azimuthal aperture of the beam (the same for every projection: the pose rotates the beam frame, MC-GPU_v1.3.cu:3280-3434)
-      cold.fan_ratio_lo = -3.0e38f;
-      cold.fan_ratio_hi = 3.0e38f;
-      bool same = !H.source.empty();
-      for (const SourcePose& sp : H.source) same = same && sp.phi_low == H.source[0].phi_low && sp.D_phi == H.source[0].D_phi;
-      if (same) {
-        const double lo = (double)H.source[0].phi_low, hi = lo + (double)H.source[0].D_phi;
-        if (lo > 1.0e-3 && hi < 3.14159265358979323846 - 1.0e-3 && hi > lo) {
-          const double r_hi = std::cos(lo) / std::sin(lo), r_lo = std::cos(hi) / std::sin(hi);  // cot decreases on (0, pi)
-          const double margin = 2.0e-6 * (r_hi - r_lo);
-          cold.fan_ratio_lo = (float)(r_lo + margin);
-          cold.fan_ratio_hi = (float)(r_hi - margin);
-        }
-      }
-    }
-    D.cold_host = cold;
-    D.cold = D.put(std::vector<TrackCold>(1, cold));
-    D.src_all = D.put(H.source);
-    D.det_all = D.put(H.detector);
+  if (cfg.dose_roi[1] > -1) {
+    D.dose_roi_voxels = (size_t)(cfg.dose_roi[1] - cfg.dose_roi[0] + 1) * (size_t)(cfg.dose_roi[3] - cfg.dose_roi[2] + 1) *
+                        (size_t)(cfg.dose_roi[5] - cfg.dose_roi[4] + 1);
+    D.dose_voxels = D.put(std::vector<unsigned long long>(2 * D.dose_roi_voxels, 0ULL));
+    D.dose_flags |= kDoseVoxels;
   }
+}
+
+// Azimuthal aperture of the beam (the same for every projection: the pose rotates the beam frame, MC-GPU_v1.3.cu:3280-3434)
+static void fan_ratio(const HostModel& H, float& lo_out, float& hi_out) {
+  lo_out = -3.0e38f;
+  hi_out = 3.0e38f;
+  bool same = !H.source.empty();
+  for (const SourcePose& sp : H.source) same = same && sp.phi_low == H.source[0].phi_low && sp.D_phi == H.source[0].D_phi;
+  if (!same) return;
+  const double lo = (double)H.source[0].phi_low, hi = lo + (double)H.source[0].D_phi;
+  if (lo > 1.0e-3 && hi < 3.14159265358979323846 - 1.0e-3 && hi > lo) {
+    const double r_hi = std::cos(lo) / std::sin(lo), r_lo = std::cos(hi) / std::sin(hi);  // cot decreases on (0, pi)
+    const double margin = 2.0e-6 * (r_hi - r_lo);
+    lo_out = (float)(r_lo + margin);
+    hi_out = (float)(r_hi - margin);
+  }
+}
+
+// The object region (box, elliptic cylinder) and the brick palette of D into its TrackCold image, uploaded when the image is on
+// the device and changed.
+void refresh_cold_geometry(DeviceModel& D) {
+  TrackCold& ch = D.cold_host;
+  TrackCold before;
+  memcpy(&before, &ch, sizeof ch);
+  for (int k = 0; k < 3; ++k) { ch.objbox_lo[k] = D.objbox_lo[k]; ch.objbox_hi[k] = D.objbox_hi[k]; }
+  for (int k = 0; k < 2; ++k) { ch.ell_c[k] = D.ell_c[k]; ch.ell_inv[k] = D.ell_inv[k]; }
+  for (int c = 0; c < 16; ++c) ch.brick_palette[c] = D.brick_palette[c];
+  if (D.cold && memcmp(&before, &ch, sizeof ch) != 0) HIP_TRY(hipMemcpy(D.cold, &ch, sizeof ch, hipMemcpyHostToDevice));
+}
+
+// The rest of TrackCold (the table stages have set their pointers) and its device copy
+static void upload_cold(const HostModel& H, DeviceModel& D) {
+  upload_dose_tallies(H, D);
+  TrackCold& cold = D.cold_host;
+  cold.bricks = D.bricks;
+  cold.wood_coarse = D.wood_coarse;
+  cold.woodcock = D.woodcock;
+  cold.lds = D.lds;
+  cold.dose_voxels = D.dose_voxels;
+  cold.dose_materials = D.dose_materials;
+  cold.mfp = D.mfp; cold.e0 = H.mat.e0; cold.ide = H.mat.ide;
+  for (int k = 0; k < 3; ++k) cold.bbox[k] = H.voxels.size_bbox[k];
+  for (int k = 0; k < 6; ++k) cold.dose_roi[k] = H.cfg.dose_roi[k];
+  int shells = 0;
+  for (int m = 0; m < kMaxMaterials; ++m) {
+    const int mc = D.compact_of[m];
+    if (mc < 0) continue;
+    cold.material_of_compact[mc] = m;
+    cold.shell_first[mc] = shells;
+    shells += std::min(H.mat.noscco[m], kMaxShells);
+  }
+  cold.thresh_compton = cold.thresh_rayleigh = cold.thresh_new = cold.flyable_low = cold.swap_batch = cold.trade_slots = -1;  // apply_schedule
+  fan_ratio(H, cold.fan_ratio_lo, cold.fan_ratio_hi);
+  refresh_cold_geometry(D);
+  D.cold = D.put(std::vector<TrackCold>(1, cold));
+}
+
+// Build the palette-compressed volume and the compact-material tables and upload everything.
+DeviceModel upload_model(const HostModel& H, int device_id) {
+  DeviceModel D{};
+  select_device(D, device_id);
+  memset(&D.cold_host, 0, sizeof D.cold_host);
+  D.nmat = compact_numbering(H, D.compact_of);
+  upload_volume(H, D);
+  const std::vector<float> rec = cross_section_records(H, D.compact_of, D.nmat);
+  const std::vector<float> tot = total_cross_sections(rec);
+  refresh_woodcock(H, D);
+  D.mfp = D.put(rec);
+  D.mfp_tot = D.put(tot);
+  upload_interaction_tables(H, D);
+  upload_spectrum(H, D);
+  lay_out_lds_and_brackets(H, D, tot);
+  upload_cold(H, D);
+  D.src_all = D.put(H.source);
+  D.det_all = D.put(H.detector);
   D.work_counter = D.put(std::vector<unsigned long long>((size_t)kNumCounters * kCounterStride, 0ULL));
-  HIP_TRY(hipEventCreate(&D.ev_start));
-  HIP_TRY(hipEventCreate(&D.ev_stop));
+  D.ev_start = D.mem.event(hipEventDefault);
+  D.ev_stop = D.mem.event(hipEventDefault);
   apply_schedule(D);
   HIP_TRY(hipDeviceSynchronize());
+  return D;
 }
 
 void require(bool ok, int code, const char* msg) { if (!ok) throw Error(code, msg); }
