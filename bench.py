@@ -20,14 +20,18 @@ rank 0's line -- like the reference's `mpirun -n N` inside `MCSimulation.run_sim
 MC-GPU_v1.3.cu:389-391).  A rank count that cannot be honoured (fewer GPUs than ranks) exits non-zero; `BENCH_SHARE_GPU=1`
 lets the ranks share the GPUs there are (development: two ranks on a one-GPU box exercise the whole N > 1 path).
 
-Prints ONE JSON line on rank 0 (driver contract) carrying `roofline` and `cpu_baseline`.  At N = 1 the line also carries
-driver-timed legs measured after the timed region: `compat` (the bit-exact personality), `check` (FAST against the oracle;
-a failed check exits non-zero), `end_to_end` (the whole 894-projection scan with the MetaImage stacks on disk),
-`end_to_end_ascii` (the drop-in default: the reference's 63 MB text file per projection) and `workloads` (the same kernel
-measurement on the CIRS phantom and the patient-like thorax, configs 3-5).  At N > 1: `reduce` (bytes, copy-engine time,
-the exposed add), `check.sharded_equals_single` (the summed sharded tally against one rank simulating the same history
-ids alone, bit for bit) and `collectives` (a short leg per route after the timed region: the exchange and north_star's literal
-per-projection `ncclReduce`, the peer-access matrix and each rank's device -- one `--gpus N` command yields both).
+Prints ONE JSON line on rank 0 (driver contract).  A plain run does only what the headline needs: it builds the workload's inputs
+afresh in a temporary directory of its own (removed at exit; `--workdir DIR` keeps them and reuses what it finds there), warms up,
+times the steps, writes `--dump-outputs` and prints the line with `roofline` (the committed PMC summary over the timed kernels)
+and `cpu_baseline: null`.  `--full` adds everything measured or checked after the timed region.  At N = 1: `measured_ceilings`
+(micro-benchmarks), `value_reference_arithmetic` (mode fast64), `compat` (the bit-exact personality), `check` (FAST against
+COMPAT and against the oracle; a failed check exits non-zero), `end_to_end` (the whole 894-projection scan with the MetaImage
+stacks on disk), `end_to_end_ascii` (the drop-in default: the reference's 63 MB text file per projection), `workloads` (the same
+kernel measurement on the CIRS phantom and the patient-like thorax, configs 3-5), `fdk` and `cpu_baseline`.  At N > 1: `reduce`
+(bytes, copy-engine time, the exposed add), `check.sharded_equals_single` (the summed sharded tally against one rank simulating
+the same history ids alone, bit for bit) and `collectives` (a short leg per route after the timed region: the exchange and
+north_star's literal per-projection `ncclReduce`, the peer-access matrix and each rank's device -- one `--gpus N` command yields
+both).  The `--no-*` switches leave out single legs of a `--full` run.
 
 This file holds the headline path and the JSON line; the legs live in `bench_legs/` (common: workloads and kernel identity,
 roofline, cpu, checks, legs, multi: the N > 1 tally routes, launch: starting the ranks).
@@ -35,8 +39,10 @@ roofline, cpu, checks, legs, multi: the N > 1 tally routes, launch: starting the
 from __future__ import annotations
 
 import argparse
+import atexit
 import json
 import os
+import shutil
 import sys
 import tempfile
 import time
@@ -66,6 +72,9 @@ def parse_args():
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="catphan")
     ap.add_argument("--voxels", type=int, default=512, help="catphan workload: cube edge")
     ap.add_argument("--projections", type=int, default=894)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the legs the headline does not need: ceilings, fast64, COMPAT, checks, scans, "
+                         "other workloads, FDK, CPU baseline (N > 1: the sharded-sum check and the route comparison)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=16.0, help="host time budget of the cpu_baseline leg (bounded sample of the same workload)")
     ap.add_argument("--no-end-to-end", action="store_true", help="skip the pipelined-scan measurements after the timed region")
@@ -76,7 +85,8 @@ def parse_args():
     ap.add_argument("--no-collectives", action="store_true", help="N > 1: skip the exchange-vs-RCCL comparison leg after the timed region")
     ap.add_argument("--scan-projections", type=int, default=894, help="projections of the end_to_end leg")
     ap.add_argument("--ascii-projections", type=int, default=894, help="projections of the end_to_end_ascii leg (63 MB of text each; 0: skip)")
-    ap.add_argument("--workdir", default=None)
+    ap.add_argument("--workdir", default=None,
+                    help="keep the inputs and scan outputs in this directory and reuse inputs found there (default: a fresh temporary directory per run, removed at exit)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed region, write the detector tally of its last step as DIR/tally.npy (float64, exact)")
     args = ap.parse_args()
@@ -121,6 +131,22 @@ def init_ranks(args, torch):
     # route after an RCCL collective has failed (the verdicts are a few bytes of host data)
     ctl = dist.new_group(backend="gloo") if (dist and backend == "nccl") else None
     return rank, world, device, dist, backend, ctl, bool(share and world > n_dev)
+
+
+def run_workdir(args, rank, dist, ctl):
+    """Where this run keeps its inputs and scan outputs.  `--workdir` names a directory that outlives the run (inputs found there are
+    reused).  Otherwise rank 0 makes a temporary directory of its own, shares its path with the other ranks and removes it at exit:
+    every run builds its inputs, material tables included, afresh and reads nothing an earlier run wrote."""
+    if args.workdir:
+        return Path(args.workdir)
+    path = [tempfile.mkdtemp(prefix=f"mcgpu_bench_{args.workload}_") if rank == 0 else None]
+    if dist:
+        dist.broadcast_object_list(path, src=0, group=ctl)
+    workdir = Path(path[0])
+    os.environ.setdefault("MCGPU_TEST_CACHE", str(workdir / "cache"))  # where workloads.material_files unpacks the tables
+    if rank == 0:
+        atexit.register(shutil.rmtree, workdir, True)
+    return workdir
 
 
 DUMP_LIMIT_BYTES = 64 << 20  # all .npy files of one dump together
@@ -174,7 +200,7 @@ def main():
     H = int(args.histories)
     label, algo_bytes, algo_src = WORKLOADS[args.workload]
     label = label.format(v=args.voxels)
-    workdir = Path(args.workdir or os.path.join(tempfile.gettempdir(), f"mcgpu_bench_{args.workload}_{args.voxels}_{args.projections}"))
+    workdir = run_workdir(args, rank, dist, ctl)
     inp = workdir / "input.in"
     t_prep0 = time.perf_counter()
     if rank == 0 and not (inp.exists() and (workdir / "geometry.vox").exists() and (workdir / "geometry.voxbin").exists()):
@@ -214,8 +240,8 @@ def main():
     if args.dump_outputs:  # before the check below, which runs a projection of its own through the same route
         dump_outputs(args.dump_outputs, route, ctx, rank)
 
-    multi = route.check(float(np.mean(kernel_ms))) if dist else None
-    collectives = route.collectives_comparison() if (dist and not args.no_collectives) else None
+    multi = route.check(float(np.mean(kernel_ms))) if (dist and args.full) else None
+    collectives = route.collectives_comparison() if (dist and args.full and not args.no_collectives) else None
     detected = 0
     if route.last_reduced is not None and (not dist):
         detected = int(route.last_reduced.sum().item())
@@ -225,7 +251,7 @@ def main():
         total_hist = float(H) * world * args.steps
         value = total_hist / elapsed
         k_ms = float(np.mean(kernel_ms))
-        ceilings = measured_ceilings(ctx) if world == 1 else None
+        ceilings = measured_ceilings(ctx) if (world == 1 and args.full) else None
         roof, valu = roofline_block(args.workload, H, k_ms, ceilings, ctx)
         out = {
             "metric": "photon histories/sec (512^3 vol, 894 proj)", "value": value, "unit": "histories/s", "n_gpus": world,
@@ -272,7 +298,7 @@ def main():
                 out["check"]["every_route_sharded_equals_single"] = route_ok
                 out["check"]["passed"] = bool(out["check"]["passed"] and route_ok)
                 failed = failed or not route_ok
-        if world == 1:
+        if world == 1 and args.full:
             # the headline kernel at the reference's arithmetic: same launches (warm-up + steps at the same angles), same HIP-event timing
             if not args.no_reference_arithmetic:
                 k64, k64_min, _ = timed_launches(ctx, torch, H, launches=args.steps, warm=args.warmup, mode="fast64")
@@ -297,13 +323,13 @@ def main():
                 out["timing"]["load_and_upload_s_text_geometry"] = text_geometry_load(eng, inp, device)
                 out["timing"]["geometry_text_bytes"] = (workdir / "geometry.vox").stat().st_size
             if not args.no_workloads and args.workload == "catphan":
-                out["workloads"] = other_workloads(eng, torch, H, args.projections, device, ceilings, scans=not args.no_end_to_end)
+                out["workloads"] = other_workloads(eng, torch, H, args.projections, device, workdir, ceilings, scans=not args.no_end_to_end)
                 kd = out["workloads"]["thorax"].get("entry_face_shell")
                 out["check"]["known_deviations"] = {"beam_edge_column": (out["check"].get("fast_vs_compat") or {}).get("beam_edge_column"), "entry_face": kd}
                 failed = failed or not (kd is None or kd["passed"])
                 if not args.no_fdk:
                     out["fdk"] = fdk_leg(pkg, device)
-        if not args.no_cpu_baseline and world == 1:  # the CPU baseline is timed at N = 1 only (the other ranks would idle meanwhile)
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU baseline is timed at N = 1 only (the other ranks would idle meanwhile)
             base, img_cpu, w2_cpu, n_cpu = cpu_baseline(ctx, seconds_budget=args.cpu_seconds)
             out["cpu_baseline"] = base
             # a second ceiling: one scattered 64-bit atomic add per detected photon, rate measured in this run

@@ -1,8 +1,7 @@
-"""Driver-timed legs measured after the timed region at N = 1: COMPAT kernel, pipelined scans, the other workloads, 4-D, FDK."""
+"""Driver-timed legs of a `bench.py --full` run, measured after the timed region at N = 1: COMPAT kernel, pipelined scans, the other workloads, 4-D, FDK."""
 from __future__ import annotations
 
 import os
-import tempfile
 import time
 from pathlib import Path
 
@@ -141,16 +140,16 @@ def fdk_leg(pkg, device, n=894, nu=1024, nv=768, du=0.388, pad=1.0):
             "ms_kernels": r["ms_filter"] + r["ms_backproject"], "voxel_updates_per_s": upd / (r["ms_backproject"] * 1e-3),
             "wall_s_including_host_transfers": wall, "finite": bool(np.isfinite(vol).all()), "parity": "unpinned against RTK (DESIGN.md 2)"}
 
-def other_workloads(eng, torch, H, projections, device, ceilings=None, scans=True):
+def other_workloads(eng, torch, H, projections, device, root, ceilings=None, scans=True):
     """Configs 3-5 under the driver's clock: the same kernel measurement (8 launches of H histories at angles (i 149) mod 894) on the
     bundled CIRS phantom, on the patient-like thorax and on the same thorax with the voxel-level bone texture of the reference's bone
     mapper -- and, because those kernels vary with the angle, the WHOLE 894-projection scan of each with its stacks on disk
     (`end_to_end`, `sustained_value`: what the metric means by a scan, MC-GPU_v1.3.cu:667) with the fastest / mean / slowest kernel
-    of the arc; config 5 as 10 respiratory states x 894 projections."""
+    of the arc; config 5 as 10 respiratory states x 894 projections.  Each workload's inputs live in `root`/<workload>."""
     out = {}
     for wl in ("cirs", "thorax", "thorax_textured"):
         t0 = time.perf_counter()
-        wd = Path(os.path.join(tempfile.gettempdir(), f"mcgpu_bench_{wl}_512_{projections}"))
+        wd = Path(root) / wl
         inp = wd / "input.in"
         if not (inp.exists() and (wd / "geometry.voxbin").exists()):
             wd.mkdir(parents=True, exist_ok=True)

@@ -309,13 +309,13 @@ def test_executable_time_limited_run_sharded_by_projection_calibrates_once(engin
 
 
 def test_bench_line_keeps_the_driver_contract(tmp_path):
-    """`python bench.py` prints ONE JSON line on stdout with the fields the driver and the judge read (metric / value / unit / n_gpus /
+    """`python bench.py --full` prints ONE JSON line on stdout with the fields the driver and the judge read (metric / value / unit / n_gpus /
     steps / warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload) plus `roofline`
     {bound, achieved, peak, unit, frac, traffic} and `cpu_baseline` {value, unit, cores, kind, sample}; a reduced run here (small
     CPU budget, no scan legs) -- the line must parse, the check must pass, the exit code must be 0."""
     import json
     import sys
-    r = subprocess.run([sys.executable, str(cases.ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--no-end-to-end", "--no-workloads", "--no-compat",
+    r = subprocess.run([sys.executable, str(cases.ROOT / "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--no-end-to-end", "--no-workloads", "--no-compat",
                         "--no-fdk", "--cpu-seconds", "4"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.split("\n") if l.strip()]
@@ -339,3 +339,27 @@ def test_bench_line_keeps_the_driver_contract(tmp_path):
         assert k in cpu, k
     assert cpu["kind"] == "port" and cpu["cores"] >= 1 and cpu["value"] > 1e4
     assert d["measured_ceilings"]["scattered_64bit_atomic_adds_per_s"] > 5e9 and d["check"]["passed"] is True
+
+
+def test_plain_bench_line_runs_only_the_headline(tmp_path):
+    """A plain `python bench.py` (no `--full`) does only what its headline needs: the same driver fields, `roofline` from the timed
+    kernels, `cpu_baseline: null` and none of the legs `--full` adds.  It builds its inputs in a temporary directory of its own and
+    removes that directory before it exits."""
+    import json
+    import os
+    import sys
+    r = subprocess.run([sys.executable, str(cases.ROOT / "bench.py"), "--steps", "3", "--warmup", "1"], capture_output=True, text=True, timeout=600,
+                       env=dict(os.environ, TMPDIR=str(tmp_path)))
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.split("\n") if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
+        assert k in d, k
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "histories/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["value"] > 1e9 and abs(d["value"] - 1e8 * 3 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
+    assert d["roofline"]["kernel_ms_avg"] > 0 and d["cpu_baseline"] is None and d["check"]["detected_energy_units_last_projection"] > 0
+    for k in ("measured_ceilings", "value_reference_arithmetic", "compat", "end_to_end", "end_to_end_ascii", "workloads", "fdk", "atomic_roofline"):
+        assert d.get(k) is None, k
+    assert "passed" not in d["check"] and "oracle_histories" not in d["check"]
+    assert not list(tmp_path.glob("mcgpu_bench_*")), "the run's input directory outlived it"

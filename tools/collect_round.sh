@@ -11,8 +11,8 @@ mkdir -p "$OUT"
 LIGHT="--steps 2 --warmup 1 --no-cpu-baseline --no-end-to-end --no-compat --no-workloads --no-reference-arithmetic"
 bash tools/pmc_collect.sh $OUT/pmc > /dev/null 2>&1; cp $OUT/pmc/summary.json $OUT/pmc_summary_catphan.json; cp $OUT/pmc/summary.json profiles/pmc_summary_latest.json
 for wl in thorax cirs thorax_textured; do bash tools/pmc_collect.sh $OUT/pmc_$wl --workload $wl $LIGHT > /dev/null 2>&1; cp $OUT/pmc_$wl/summary.json $OUT/pmc_summary_$wl.json; cp $OUT/pmc_$wl/summary.json profiles/pmc_summary_$wl.json; done
-python bench.py > $OUT/bench_line.json 2> $OUT/bench_line.err
-for wl in cirs thorax; do python bench.py --workload $wl --no-workloads > $OUT/bench_line_$wl.json 2> $OUT/bench_line_$wl.err; done
+python bench.py --full --workdir /tmp/mcgpu_bench_catphan_512_894 > $OUT/bench_line.json 2> $OUT/bench_line.err
+for wl in cirs thorax; do python bench.py --full --workload $wl --no-workloads > $OUT/bench_line_$wl.json 2> $OUT/bench_line_$wl.err; done
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 bench.py --steps 12 --warmup 3 --no-cpu-baseline --no-end-to-end --no-compat --no-workloads --no-reference-arithmetic > $OUT/bench_line_under_rocprof.json 2> $OUT/prof.err
 cp $(find $OUT/prof -name "*kernel_stats.csv" | head -1) $OUT/bench_kernel_stats.csv
 head -1 $(find $OUT/prof -name "*kernel_trace.csv" | head -1) > $OUT/bench_kernel_trace_track.csv; grep track_ $(find $OUT/prof -name "*kernel_trace.csv" | head -1) >> $OUT/bench_kernel_trace_track.csv
@@ -20,11 +20,11 @@ head -1 $(find $OUT/prof -name "*kernel_trace.csv" | head -1) > $OUT/bench_kerne
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_ascii -- python3 tools/scan_ascii.py 24 > $OUT/scan_ascii.log 2> $OUT/scan_ascii.err
 cp $(find $OUT/prof_ascii -name "*kernel_stats.csv" | head -1) $OUT/scan_ascii_kernel_stats.csv
 python3 tools/scan_ascii.py 200 > $OUT/scan_ascii_200.log 2>&1
-BENCH_SHARE_GPU=1 python bench.py --gpus 2 --steps 8 --warmup 2 > $OUT/bench_line_2_ranks_sharing_one_gpu.json 2> $OUT/two_ranks.err
+BENCH_SHARE_GPU=1 python bench.py --full --gpus 2 --steps 8 --warmup 2 > $OUT/bench_line_2_ranks_sharing_one_gpu.json 2> $OUT/two_ranks.err
 # the third route of the N > 1 path: projection sharding (no exchange, no collective); RCCL itself refuses two ranks on one device
-BENCH_SHARE_GPU=1 BENCH_EXCHANGE=none python bench.py --gpus 2 --steps 8 --warmup 2 > $OUT/bench_line_2_ranks_projection_sharded_one_gpu.json 2> $OUT/two_ranks_none.err
+BENCH_SHARE_GPU=1 BENCH_EXCHANGE=none python bench.py --full --gpus 2 --steps 8 --warmup 2 > $OUT/bench_line_2_ranks_projection_sharded_one_gpu.json 2> $OUT/two_ranks_none.err
 # six ranks on the one GPU: as many processes as the pool admits on a card (eight ranks: in-process, tests/test_exchange.py, tests/test_gpu_dropin.py)
-BENCH_SHARE_GPU=1 python bench.py --gpus 6 --steps 8 --warmup 2 > $OUT/bench_line_6_ranks_sharing_one_gpu.json 2> $OUT/six_ranks.err
+BENCH_SHARE_GPU=1 python bench.py --full --gpus 6 --steps 8 --warmup 2 > $OUT/bench_line_6_ranks_sharing_one_gpu.json 2> $OUT/six_ranks.err
 # the FAST kernel in single precision against the variant with the reference's double-precision sub-steps (mode fast64), one box
 python tools/arith_ab.py > $OUT/fast_vs_fast64_ab.txt 2> $OUT/fast_vs_fast64_ab.err
 # kernel stats of the tissue workloads, the FAST section statistics (diagnostic library) and the long version of the RNG test

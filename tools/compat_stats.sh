@@ -8,6 +8,6 @@ W=$(mktemp -d); mkdir -p "$W/pkg"; cp -rp 4d-cbct-mc_amd/csrc "$W/pkg/csrc"; cp 
 cp "$W/pkg/libmcgpu_amd.so" build/ab/compat_stats.so
 B="--steps 2 --warmup 1 --no-workloads --no-cpu-baseline --no-end-to-end --no-compat"
 for wl in catphan cirs thorax; do
-  [ -d /tmp/mcgpu_bench_${wl}_512_894 ] || timeout 300 python bench.py $B --workload $wl > /dev/null 2>&1
+  [ -d /tmp/mcgpu_bench_${wl}_512_894 ] || timeout 300 python bench.py $B --workload $wl --workdir /tmp/mcgpu_bench_${wl}_512_894 > /dev/null 2>&1
   echo -n "$wl " ; MCGPU_AMD_LIB=$ROOT/build/ab/compat_stats.so MCGPU_COMPAT_STATS=1 timeout 200 python tools/compat_stats.py /tmp/mcgpu_bench_${wl}_512_894 2e7 2>&1 | tail -1
 done | tee gpurun_out/compat_stats.txt
