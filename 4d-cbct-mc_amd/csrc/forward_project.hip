@@ -13,7 +13,7 @@
 // The traversal runs in the index frame of the IEC volume [nz][ny][nx]; only the voxel fetch differs between volume sources
 // (template parameter): a float volume uploaded from the host, or the context's own representation (u8 tiled / u16 palette
 // indices with the palette densities in LDS, raw {density, material} float2), read in the .vox frame.  All sources run the same
-// arithmetic, so the same densities give bit-identical sums.
+// arithmetic, so the same densities give bit-identical sums.  The per-ray body lives in joseph_ray.inc, shared with rooster4d.hip.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "engine_internal.hpp"
+#include "joseph_ray.inc"
 
 extern "C" void mcgpu_set_last_error_(const char* message);
 
@@ -32,10 +33,6 @@ using namespace mcgpu;
 constexpr int kBatch = 16;       // projections per launch (blockIdx.z)
 constexpr int kChunk = 64;       // projections resident in the device output buffer (downloaded per chunk)
 constexpr int kPalLds = 8192;    // palette densities staged in LDS up to this many entries (32 KB)
-
-struct FpProj {
-  double c, s, off_x, off_y;
-};
 
 struct FpArgs {
   int nu, nv, nb;
@@ -104,10 +101,6 @@ struct SrcRaw {  // {density, material} per voxel, x fastest
   }
 };
 
-// element m of (v0, v1, v2) by selects: a per-lane index into a private array would put the array in scratch
-template <class T>
-__device__ inline T sel3(int m, T v0, T v1, T v2) { return m == 0 ? v0 : (m == 1 ? v1 : v2); }
-
 template <class Src>
 __global__ __launch_bounds__(256) void joseph_fp_kernel(float* __restrict__ out /*[nb][nv][nu]*/, const FpArgs A, const Src src,
                                                         const float* __restrict__ pal2, int pal_n) {
@@ -119,71 +112,7 @@ __global__ __launch_bounds__(256) void joseph_fp_kernel(float* __restrict__ out 
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
   const int iu = blockIdx.x * 16 + (w & 1) * 8 + (l & 7), iv = blockIdx.y * 16 + (w >> 1) * 8 + (l >> 3);
   if (iu >= A.nu || iv >= A.nv) return;
-  const FpProj P = A.pp[blockIdx.z];
-  // ray source -> pixel in world coordinates, then in index coordinates of the volume
-  const double xr = A.u0 + A.du * iu + P.off_x, yr = A.v0 + A.dv * iv + P.off_y, zr = A.sid - A.sdd;
-  const double S[3] = {P.s * A.sid, 0.0, P.c * A.sid};
-  const double D[3] = {P.c * xr + P.s * zr - S[0], yr - S[1], -P.s * xr + P.c * zr - S[2]};
-  double Si[3], Di[3];
-  double t0 = 0.0, t1 = 1.0;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    Si[a] = (S[a] - A.o[a]) / A.sp[a];
-    Di[a] = D[a] / A.sp[a];
-    const double lo = -0.5, hi = A.n[a] - 0.5;
-    if (Di[a] != 0.0) {
-      double ta = (lo - Si[a]) / Di[a], tb = (hi - Si[a]) / Di[a];
-      if (ta > tb) { const double t = ta; ta = tb; tb = t; }
-      t0 = fmax(t0, ta); t1 = fmin(t1, tb);
-    } else if (Si[a] < lo || Si[a] > hi) {
-      t1 = -1.0;
-    }
-  }
-  float acc = 0.f;
-  if (t0 < t1) {
-    int m = 0;
-    if (fabs(Di[1]) > fabs(Di[0])) m = 1;
-    if (fabs(Di[2]) > fabs(sel3(m, Di[0], Di[1], Di[2]))) m = 2;
-    // (a1, a2) = the other two axes in increasing order
-    const double Sm = sel3(m, Si[0], Si[1], Si[2]), Dm = sel3(m, Di[0], Di[1], Di[2]);
-    const double S1 = (m == 0) ? Si[1] : Si[0], D1 = (m == 0) ? Di[1] : Di[0];
-    const double S2 = (m == 2) ? Si[1] : Si[2], D2 = (m == 2) ? Di[1] : Di[2];
-    const int nm = sel3(m, A.n[0], A.n[1], A.n[2]), na = (m == 0) ? A.n[1] : A.n[0], nb = (m == 2) ? A.n[1] : A.n[2];
-    const double e0 = Sm + t0 * Dm, e1 = Sm + t1 * Dm;
-    const double lo = fmin(e0, e1), hi = fmax(e0, e1);
-    const int ns = max((int)floor(lo + 0.5), 0), fs = min((int)floor(hi + 0.5), nm - 1);
-    if (ns <= fs) {
-      const double r1 = D1 / Dm, r2 = D2 / Dm;
-      const float w_first = (float)(ns == fs ? hi - lo : ns + 0.5 - lo), w_last = (float)(hi - fs + 0.5);
-      const float A0 = (float)(S1 + (ns - Sm) * r1), B0 = (float)(S2 + (ns - Sm) * r2);
-      const float fr1 = (float)r1, fr2 = (float)r2;
-      for (int k = ns; k <= fs; ++k) {
-        const float dk = (float)(k - ns);
-        const float a = fmaf(dk, fr1, A0), b = fmaf(dk, fr2, B0);
-        const float fa0 = floorf(a), fb0 = floorf(b);
-        const int ia = (int)fa0, ib = (int)fb0;
-        const float fa = a - fa0, fb = b - fb0;
-        float v[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int qa = ia + (q & 1), qb = ib + (q >> 1);
-          v[q] = 0.f;
-          if ((unsigned)qa < (unsigned)na && (unsigned)qb < (unsigned)nb) {
-            const int x = (m == 0) ? k : qa;
-            const int y = (m == 1) ? k : (m == 0 ? qa : qb);
-            const int z = (m == 2) ? k : qb;
-            v[q] = src(x, y, z, pal);
-          }
-        }
-        const float ga = 1.f - fa, gb = 1.f - fb;
-        const float s = gb * (ga * v[0] + fa * v[1]) + fb * (ga * v[2] + fa * v[3]);
-        const float wk = (k == ns) ? w_first : (k == fs ? w_last : 1.f);
-        acc = fmaf(wk, s, acc);
-      }
-      const double len = sqrt(D[0] * D[0] + D[1] * D[1] + D[2] * D[2]) / fabs(Dm);  // mm per main-axis step
-      acc *= (float)len;
-    }
-  }
+  const float acc = joseph_ray(A, A.pp[blockIdx.z], iu, iv, src, pal);
   out[((size_t)blockIdx.z * A.nv + iv) * A.nu + iu] = acc;
 }
 

@@ -1,0 +1,686 @@
+// rooster4d.hip -- 4-D ROOSTER reconstruction for MI355X (what the reference obtains from RTK's `rtkfourdrooster`,
+// cbctmc/reconstruction/reconstruction.py: reconstruct_4d).  Geometry model as fdk.hip / forward_project.hip
+// (rotation axis Y, source at Ry(gantry) (0, 0, sid), u = sdd x'/(sid - z') - proj_offset_x).  Restated in float64 by
+// tests/rooster_ref.py.  Parity against rtkfourdrooster itself is unpinned: RTK is absent here.
+//
+// Unknowns: N frames x_f, f = 0..N-1, each on the FDK grid [nz][ny][nx] (IEC frame); projections p_k are line integrals after the
+// optional water pre-correction (the polynomial sum_j c_j p^j of rtkfdk --wpc, fdk.hip: weight_kernel).
+//   S   (phase -> interpolation weights, host: interpolation_weights): phi_k in [0, 1], t = phi_k N, l = floor(t) mod N,
+//       h = (l + 1) mod N, w_h = t - floor(t), w_l = 1 - w_h.  S blends frames l and h for projection k, S^T distributes into them.
+//   R   Joseph forward projection (joseph_ray.inc, unchanged: float64 ray setup, float32 accumulation), reading the blend
+//       w_l x_l + w_h x_h at every tap (SrcBlend).
+//   B   voxel-driven bilinear back-projection like fdk.hip's backproject_kernel (a detector sample counts only with both columns
+//       and both rows inside the detector), without ramp filter or angular-gap weights, with the weight (sdd / U)^2 sx sy sz / (du dv),
+//       U = sid - z_rot.  That weight makes B ~ R^T (the Joseph sum over the rays through a voxel, per unit of detector area at the
+//       voxel's magnification), so the CG operator below is close to symmetric -- a deliberate departure from RTK's unweighted
+//       CudaVoxelBased back-projector, whose operator S^T B R S is not symmetric and which CG only tolerates.
+//   main iteration (niter times, from x = 0):
+//     1. cgiter conjugate-gradient steps on A = S^T B R S, b = S^T B p, restarted from the current x (r = b - A x, direction = r)
+//     2. positivity x = max(x, 0) (rtkfourdrooster without --nopositivity)
+//     3. spatial TV denoising of every frame, 4. temporal TV denoising of every voxel's N-sample series (periodic)
+//   TV denoising, min 1/2 |u - f|^2 + gamma TV(u), tviter iterations of the dual projected gradient (RTK's BPDQ family):
+//     p = 0; repeat { u = f + div p; p <- Pi_gamma(p + tau grad u) }; u = f + div p.  grad = forward differences in index units,
+//     Neumann in space (the last difference of an axis is 0), periodic in time; div = -grad^T exactly; Pi_gamma scales each
+//     voxel's gradient vector to Euclidean norm <= gamma (3 spatial components together); tau = 1 / (4 d), d = 3 space, 1 time.
+//   Dot products in float64, reduced in two fixed stages (a fixed grid of partial sums, then one block) without atomics: a run is
+//   bit-reproducible.
+// Kernels: fp4_kernel (R S, one lane per detector pixel as forward_project.hip), bp4_kernel (S^T B over a batch of projections
+// that share their frame pair: two accumulators per voxel, frames l and h written once per batch), the CG vector kernels with
+// float4 loads and the dot-product stages, positivity, tv_space_div / tv_space_grad (per frame: the spatial dual is 3 x one
+// frame) and tv_time_kernel (a voxel's whole series and its dual in registers: one read and one write of the 4-D volume).
+// Residency: the projection stack and the 4-D vectors x, b, r, d, A d stay on the device for the whole run.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/mcgpu_amd.h"
+#include "joseph_ray.inc"
+
+extern "C" void mcgpu_set_last_error_(const char* message);
+
+namespace {
+
+constexpr int kFpBatch = 16;     // projections per forward launch (blockIdx.z)
+constexpr int kBpBatch = 8;      // projections per back-projection launch (fdk.hip's measured optimum)
+constexpr int kMaxFrames = 32;   // frames of the temporal TV kernel's register arrays
+constexpr int kRedBlocks = 1024; // blocks of the first reduction stage (fixed: the summation order does not depend on the device)
+constexpr int kThreads = 256;
+
+// ---- R S -----------------------------------------------------------------------------------------------------------------
+struct Fp4Args {  // field names as joseph_ray.inc expects them
+  int nu, nv, nb;
+  int n[3];
+  double u0, v0, du, dv, sid, sdd;
+  double o[3], sp[3];
+  FpProj pp[kFpBatch];
+  int fl[kFpBatch], fh[kFpBatch];  // frame pair of each projection
+  float wl[kFpBatch], wh[kFpBatch];
+};
+
+struct SrcBlend {  // w_l x_l + w_h x_h at IEC index (x, y, z)
+  const float* a;
+  const float* b;
+  float wa, wb;
+  int nx, nxy;
+  __device__ float operator()(int x, int y, int z, const float*) const {
+    const size_t i = (size_t)z * nxy + (size_t)y * nx + x;
+    return wa * a[i] + wb * b[i];
+  }
+};
+
+__global__ __launch_bounds__(256) void fp4_kernel(float* __restrict__ out /*[nb][nv][nu]*/, const Fp4Args A, const float* __restrict__ x4, size_t frame) {
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  const int iu = blockIdx.x * 16 + (w & 1) * 8 + (l & 7), iv = blockIdx.y * 16 + (w >> 1) * 8 + (l >> 3);
+  if (iu >= A.nu || iv >= A.nv) return;
+  const int k = blockIdx.z;
+  const SrcBlend src{x4 + (size_t)A.fl[k] * frame, x4 + (size_t)A.fh[k] * frame, A.wl[k], A.wh[k], A.n[0], A.n[0] * A.n[1]};
+  out[((size_t)k * A.nv + iv) * A.nu + iu] = joseph_ray(A, A.pp[k], iu, iv, src, nullptr);
+}
+
+// ---- S^T B -----------------------------------------------------------------------------------------------------------------
+struct Bp4Args {
+  int nx, ny, nz, nu, nv, nb;
+  int fl, fh;                // the frame pair all projections of the batch share
+  double x0, z0, sx, sz;     // column position (float64: computed once per column and projection)
+  float y0, sy;
+  double sid, sdd, inv_du, inv_dv, u0, v0;
+  double K;                  // sx sy sz / (du dv)
+  double c[kBpBatch], s[kBpBatch], off_x[kBpBatch];
+  float av_b[kBpBatch];      // fv = mag / dv Y + av_b (wave-uniform: scalar registers)
+  float wl[kBpBatch], wh[kBpBatch];
+};
+
+// a thread owns one (x, z) column and walks y (fdk.hip: backproject_kernel); x4 += S^T B q for the batch
+__global__ __launch_bounds__(256, 4) void bp4_kernel(float* __restrict__ x4, size_t frame, const float* __restrict__ q /*[nb][nv][nu]*/, const Bp4Args A) {
+  const int ix = blockIdx.x * blockDim.x + threadIdx.x, iz = blockIdx.y;
+  if (ix >= A.nx) return;
+  const double X = A.x0 + A.sx * ix, Z = A.z0 + A.sz * iz;
+  int iu[kBpBatch];
+  float au[kBpBatch], g[kBpBatch], av_a[kBpBatch];
+#pragma unroll
+  for (int k = 0; k < kBpBatch; ++k) {
+    iu[k] = -1; au[k] = 0.f; g[k] = 0.f; av_a[k] = 0.f;
+    if (k < A.nb) {
+      const double xr = X * A.c[k] - Z * A.s[k], zr = X * A.s[k] + Z * A.c[k];
+      const double U = A.sid - zr;
+      if (U > 0.0) {
+        const double mag = A.sdd / U;
+        const double fu = (mag * xr - A.off_x[k] - A.u0) * A.inv_du;
+        const double fl = floor(fu);
+        if (fl >= 0.0 && fl < A.nu - 1) {
+          iu[k] = (int)fl;
+          au[k] = (float)(fu - fl);
+          g[k] = (float)(mag * mag * A.K);
+          av_a[k] = (float)(mag * A.inv_dv);  // fv = av_a Y + av_b
+        }
+      }
+    }
+  }
+  const size_t plane = (size_t)A.nu * A.nv;
+  const size_t col = (size_t)iz * A.ny * A.nx + ix;
+  float* out_l = x4 + (size_t)A.fl * frame + col;
+  float* out_h = x4 + (size_t)A.fh * frame + col;
+  for (int iy = 0; iy < A.ny; ++iy) {
+    const float Y = A.y0 + A.sy * iy;
+    float acc_l = 0.f, acc_h = 0.f;
+#pragma unroll
+    for (int k = 0; k < kBpBatch; ++k) {
+      if (iu[k] >= 0) {
+        const float fv = fmaf(av_a[k], Y, A.av_b[k]);
+        const float fl = floorf(fv);
+        const int iv = (int)fl;
+        if (iv >= 0 && iv < A.nv - 1) {
+          const float av = fv - fl;
+          const float* r0 = q + (size_t)k * plane + (size_t)iv * A.nu + iu[k];
+          float2 lo, hi;  // (iu, iu + 1) of both rows with one 8-byte load each
+          __builtin_memcpy(&lo, r0, 8);
+          __builtin_memcpy(&hi, r0 + A.nu, 8);
+          const float top = fmaf(au[k], lo.y - lo.x, lo.x), bot = fmaf(au[k], hi.y - hi.x, hi.x);
+          const float val = fmaf(av, bot - top, top);
+          const float gv = g[k] * val;
+          acc_l = fmaf(A.wl[k], gv, acc_l);
+          acc_h = fmaf(A.wh[k], gv, acc_h);
+        }
+      }
+    }
+    const size_t o = (size_t)iy * A.nx;
+    out_l[o] += acc_l;
+    out_h[o] += acc_h;  // frame l == h (N = 1): the same thread adds both, in order
+  }
+}
+
+// ---- vectors: n4 float4 groups (every 4-D vector is allocated and zero-padded to a multiple of 4 floats) --------------------
+__device__ inline double dot4(float4 a, float4 b) {
+  return (double)a.x * b.x + (double)a.y * b.y + (double)a.z * b.z + (double)a.w * b.w;
+}
+
+// fixed-order block sum of one double per thread (tree in LDS); thread 0 gets the total
+__device__ inline double block_sum(double v) {
+  __shared__ double red[kThreads];
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = kThreads / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// part[block] = sum of a . b over the block's grid-stride share
+__global__ __launch_bounds__(256) void dot_partial_kernel(const float4* __restrict__ a, const float4* __restrict__ b, size_t n4, double* __restrict__ part) {
+  double acc = 0.0;
+  for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n4; i += (size_t)kRedBlocks * kThreads) acc += dot4(a[i], b[i]);
+  const double s = block_sum(acc);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// out = sum of the kRedBlocks partials (second stage, one block)
+__global__ __launch_bounds__(256) void sum_partials_kernel(const double* __restrict__ part, double* __restrict__ out) {
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < kRedBlocks; i += kThreads) acc += part[i];
+  const double s = block_sum(acc);
+  if (threadIdx.x == 0) *out = s;
+}
+
+// r = b - Ad; d = r; partial r . r
+__global__ __launch_bounds__(256) void cg_restart_kernel(const float4* __restrict__ b, const float4* __restrict__ Ax, float4* __restrict__ r, float4* __restrict__ d,
+                                                         size_t n4, double* __restrict__ part) {
+  double acc = 0.0;
+  for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n4; i += (size_t)kRedBlocks * kThreads) {
+    const float4 bb = b[i], aa = Ax[i];
+    const float4 v = make_float4(bb.x - aa.x, bb.y - aa.y, bb.z - aa.z, bb.w - aa.w);
+    r[i] = v;
+    d[i] = v;
+    acc += dot4(v, v);
+  }
+  const double s = block_sum(acc);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// x += alpha d; r -= alpha Ad; partial r . r
+__global__ __launch_bounds__(256) void cg_update_kernel(float4* __restrict__ x, float4* __restrict__ r, const float4* __restrict__ d, const float4* __restrict__ Ad,
+                                                        float alpha, size_t n4, double* __restrict__ part) {
+  double acc = 0.0;
+  for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n4; i += (size_t)kRedBlocks * kThreads) {
+    float4 xv = x[i], rv = r[i];
+    const float4 dv = d[i], av = Ad[i];
+    xv.x = fmaf(alpha, dv.x, xv.x); xv.y = fmaf(alpha, dv.y, xv.y); xv.z = fmaf(alpha, dv.z, xv.z); xv.w = fmaf(alpha, dv.w, xv.w);
+    rv.x = fmaf(-alpha, av.x, rv.x); rv.y = fmaf(-alpha, av.y, rv.y); rv.z = fmaf(-alpha, av.z, rv.z); rv.w = fmaf(-alpha, av.w, rv.w);
+    x[i] = xv;
+    r[i] = rv;
+    acc += dot4(rv, rv);
+  }
+  const double s = block_sum(acc);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// d = r + beta d
+__global__ __launch_bounds__(256) void cg_direction_kernel(const float4* __restrict__ r, float4* __restrict__ d, float beta, size_t n4) {
+  for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n4; i += (size_t)kRedBlocks * kThreads) {
+    const float4 rv = r[i];
+    float4 dv = d[i];
+    dv.x = fmaf(beta, dv.x, rv.x); dv.y = fmaf(beta, dv.y, rv.y); dv.z = fmaf(beta, dv.z, rv.z); dv.w = fmaf(beta, dv.w, rv.w);
+    d[i] = dv;
+  }
+}
+
+__global__ __launch_bounds__(256) void positivity_kernel(float4* __restrict__ x, size_t n4) {
+  for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n4; i += (size_t)kRedBlocks * kThreads) {
+    float4 v = x[i];
+    v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+    x[i] = v;
+  }
+}
+
+// rtkfdk --wpc on the resident projections: p <- sum_j c_j p^j (fdk.hip: weight_kernel)
+__global__ __launch_bounds__(256) void wpc_kernel(float* __restrict__ p, size_t n, const float* __restrict__ wpc, int n_wpc) {
+  for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (size_t)kRedBlocks * kThreads) {
+    const float v = p[i];
+    float acc = 0.f, pw = 1.f;
+    for (int j = 0; j < n_wpc; ++j) { acc += wpc[j] * pw; pw *= v; }
+    p[i] = acc;
+  }
+}
+
+// ---- spatial TV of one frame ------------------------------------------------------------------------------------------------
+// u = f + div p, div p (i) = p(i) [i < n - 1] - p(i - 1) [i >= 1] per axis (= -grad^T p).  u may be f (the final step, in place).
+__global__ __launch_bounds__(256) void tv_space_div_kernel(const float* f, const float* __restrict__ px, const float* __restrict__ py, const float* __restrict__ pz,
+                                                           float* u, int nx, int ny, int nz) {
+  const size_t nxy = (size_t)nx * ny, nvox = nxy * nz;
+  for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < nvox; i += (size_t)gridDim.x * kThreads) {
+    const int x = (int)(i % nx), y = (int)((i / nx) % ny), z = (int)(i / nxy);
+    float d = 0.f;
+    if (x < nx - 1) d += px[i];
+    if (x > 0) d -= px[i - 1];
+    if (y < ny - 1) d += py[i];
+    if (y > 0) d -= py[i - nx];
+    if (z < nz - 1) d += pz[i];
+    if (z > 0) d -= pz[i - nxy];
+    u[i] = f[i] + d;
+  }
+}
+
+// p <- Pi_gamma(p + tau grad u): the 3-vector scaled to norm <= gamma
+__global__ __launch_bounds__(256) void tv_space_grad_kernel(const float* __restrict__ u, float* __restrict__ px, float* __restrict__ py, float* __restrict__ pz,
+                                                            int nx, int ny, int nz, float tau, float gamma) {
+  const size_t nxy = (size_t)nx * ny, nvox = nxy * nz;
+  for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < nvox; i += (size_t)gridDim.x * kThreads) {
+    const int x = (int)(i % nx), y = (int)((i / nx) % ny), z = (int)(i / nxy);
+    const float c = u[i];
+    const float gx = x < nx - 1 ? u[i + 1] - c : 0.f, gy = y < ny - 1 ? u[i + nx] - c : 0.f, gz = z < nz - 1 ? u[i + nxy] - c : 0.f;
+    float qx = fmaf(tau, gx, px[i]), qy = fmaf(tau, gy, py[i]), qz = fmaf(tau, gz, pz[i]);
+    const float nrm = sqrtf(qx * qx + qy * qy + qz * qz);
+    if (nrm > gamma) {
+      const float s = gamma / nrm;
+      qx *= s; qy *= s; qz *= s;
+    }
+    px[i] = qx; py[i] = qy; pz[i] = qz;
+  }
+}
+
+// ---- temporal TV: a voxel's N-sample series and its dual in registers (indices are compile-time: no scratch) --------------------
+template <int NM>
+__global__ __launch_bounds__(256) void tv_time_kernel(float* __restrict__ x4, size_t frame, int N, int iters, float tau, float gamma) {
+  const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= frame) return;
+  float f[NM], p[NM], u[NM];
+#pragma unroll
+  for (int t = 0; t < NM; ++t) { f[t] = t < N ? x4[(size_t)t * frame + i] : 0.f; p[t] = 0.f; }
+  for (int it = 0; it <= iters; ++it) {
+    float plast = 0.f;  // p(N - 1): the periodic predecessor of t = 0
+#pragma unroll
+    for (int t = 0; t < NM; ++t) if (t == N - 1) plast = p[t];
+#pragma unroll
+    for (int t = 0; t < NM; ++t) u[t] = f[t] + (p[t] - (t == 0 ? plast : p[t > 0 ? t - 1 : 0]));  // u = f + div p
+    if (it == iters) break;
+    const float u0 = u[0];
+#pragma unroll
+    for (int t = 0; t < NM; ++t) {
+      if (t < N) {
+        const float next = (t == N - 1) ? u0 : u[t + 1 < NM ? t + 1 : 0];
+        const float q = fmaf(tau, next - u[t], p[t]);
+        p[t] = fminf(fmaxf(q, -gamma), gamma);  // |q| <= gamma
+      }
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < NM; ++t) if (t < N) x4[(size_t)t * frame + i] = u[t];
+}
+
+// ---- host --------------------------------------------------------------------------------------------------------------------
+struct RsError { std::string msg; };
+#define RS_HIP(expr)                                                                                      \
+  do {                                                                                                    \
+    hipError_t _e = (expr);                                                                               \
+    if (_e != hipSuccess) throw RsError{std::string("!!HIP ERROR!! ") + #expr + ": " + hipGetErrorString(_e)}; \
+  } while (0)
+
+// RTK's signal-to-weights rule for a periodic N-frame sequence: phase phi in [0, 1] lies between frames l = floor(phi N) mod N and
+// h = l + 1 mod N with linear weights; phi = 1 is frame 0 again.  This is the rule as RTK documents it (rtkfourdrooster --signal,
+// rtk::PhasesToInterpolationWeights); its exact match with RTK's code cannot be checked here (RTK is absent).
+void interpolation_weights(double phase, int N, int& l, int& h, double& wl, double& wh) {
+  const double t = phase * N, ft = std::floor(t);
+  l = (int)(((long long)ft % N + N) % N);
+  h = (l + 1) % N;
+  wh = t - ft;
+  wl = 1.0 - wh;
+}
+
+bool fail(const char* fn, const std::string& what) {
+  mcgpu_set_last_error_((std::string("!!ERROR!! ") + fn + ": " + what).c_str());
+  return false;
+}
+
+bool read_options(const char* fn, const mcgpu_rooster4d_options* caller, mcgpu_rooster4d_options& o) {
+  if (!caller || caller->struct_size == 0) return fail(fn, "set mcgpu_rooster4d_options.struct_size = sizeof(mcgpu_rooster4d_options)");
+  memset(&o, 0, sizeof o);  // a caller built against an older header passes a shorter struct: what it does not have reads as zero
+  memcpy(&o, caller, std::min<size_t>(caller->struct_size, sizeof o));
+  if (o.n_proj < 1 || o.nu < 2 || o.nv < 2 || !o.gantry_deg || !(o.du > 0) || !(o.dv > 0) || !(o.sid > 0) || !(o.sdd > 0))
+    return fail(fn, "bad geometry argument");
+  if (o.nx < 1 || o.ny < 1 || o.nz < 1 || !(o.sx > 0) || !(o.sy > 0) || !(o.sz > 0)) return fail(fn, "bad volume argument");
+  if (o.n_frames < 1 || o.n_frames > kMaxFrames) return fail(fn, "n_frames must be 1.." + std::to_string(kMaxFrames));
+  if (!o.phase) return fail(fn, "phase is NULL");
+  for (int k = 0; k < o.n_proj; ++k)
+    if (!(o.phase[k] >= 0.0 && o.phase[k] <= 1.0)) return fail(fn, "phase[" + std::to_string(k) + "] is not in [0, 1]");
+  if (o.niter < 0 || o.cgiter < 0 || o.tviter < 0) return fail(fn, "niter, cgiter and tviter must be >= 0");
+  if (!(o.gamma_space >= 0.0) || !(o.gamma_time >= 0.0) || !std::isfinite(o.gamma_space) || !std::isfinite(o.gamma_time))
+    return fail(fn, "gamma_space and gamma_time must be finite and >= 0");
+  if (o.n_wpc < 0 || (o.n_wpc > 0 && !o.wpc)) return fail(fn, "bad wpc argument");
+  return true;
+}
+
+// device buffers and events of one call; frees everything it made, tracks the peak of the bytes it holds
+struct Device {
+  std::vector<void*> bufs;
+  std::vector<size_t> sizes;
+  size_t held = 0, peak = 0;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  template <class T>
+  T* alloc(size_t bytes) {
+    void* p = nullptr;
+    RS_HIP(hipMalloc(&p, bytes));
+    bufs.push_back(p);
+    sizes.push_back(bytes);
+    held += bytes;
+    peak = std::max(peak, held);
+    RS_HIP(hipMemset(p, 0, bytes));
+    return (T*)p;
+  }
+  void release(void* p) {
+    for (size_t i = 0; i < bufs.size(); ++i)
+      if (bufs[i] == p) { (void)hipFree(p); held -= sizes[i]; bufs.erase(bufs.begin() + i); sizes.erase(sizes.begin() + i); return; }
+  }
+  ~Device() {
+    for (void* p : bufs) (void)hipFree(p);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+};
+
+struct Stage {  // times a block of launches on the null stream into one report field
+  Device& dev;
+  double& ms;
+  Stage(Device& d, double& m) : dev(d), ms(m) { RS_HIP(hipEventRecord(dev.e0, nullptr)); }
+  void done() {
+    RS_HIP(hipGetLastError());
+    RS_HIP(hipEventRecord(dev.e1, nullptr));
+    RS_HIP(hipEventSynchronize(dev.e1));
+    float t = 0.f;
+    RS_HIP(hipEventElapsedTime(&t, dev.e0, dev.e1));
+    ms += t;
+  }
+};
+
+struct Problem {
+  mcgpu_rooster4d_options o;
+  int N;
+  size_t frame, n4d, n4, plane;         // voxels per frame, 4-D floats, float4 groups (padded), pixels per projection
+  std::vector<int> fl, fh;
+  std::vector<double> wl, wh;
+  Fp4Args fa;                           // per-launch fields filled in forward()
+  std::vector<Bp4Args> bp;              // one per back-projection batch, with the first projection of each
+  std::vector<int> bp_first;
+  mcgpu_rooster4d_report rep;
+  Device dev;
+  double* d_part = nullptr;
+  double* d_sum = nullptr;
+
+  explicit Problem(const mcgpu_rooster4d_options& opt) : o(opt), N(opt.n_frames) {
+    memset(&rep, 0, sizeof rep);
+    frame = (size_t)o.nx * o.ny * o.nz;
+    n4d = frame * N;
+    n4 = (n4d + 3) / 4;
+    plane = (size_t)o.nu * o.nv;
+    fl.resize(o.n_proj); fh.resize(o.n_proj); wl.resize(o.n_proj); wh.resize(o.n_proj);
+    for (int k = 0; k < o.n_proj; ++k) interpolation_weights(o.phase[k], N, fl[k], fh[k], wl[k], wh[k]);
+    const double org[3] = {o.ox, o.oy, o.oz}, sp[3] = {o.sx, o.sy, o.sz};
+    const int n[3] = {o.nx, o.ny, o.nz};
+    double origin[3];
+    memset(&fa, 0, sizeof fa);
+    fa.nu = o.nu; fa.nv = o.nv;
+    for (int a = 0; a < 3; ++a) {
+      origin[a] = std::isnan(org[a]) ? -(n[a] - 1) / 2.0 * sp[a] : org[a];
+      fa.n[a] = n[a]; fa.sp[a] = sp[a]; fa.o[a] = origin[a];
+    }
+    fa.u0 = o.u0; fa.v0 = o.v0; fa.du = o.du; fa.dv = o.dv; fa.sid = o.sid; fa.sdd = o.sdd;
+    // back-projection batches: consecutive projections with the same frame pair, at most kBpBatch
+    for (int k = 0; k < o.n_proj;) {
+      Bp4Args A;
+      memset(&A, 0, sizeof A);
+      A.nx = o.nx; A.ny = o.ny; A.nz = o.nz; A.nu = o.nu; A.nv = o.nv;
+      A.fl = fl[k]; A.fh = fh[k];
+      A.x0 = origin[0]; A.z0 = origin[2]; A.sx = o.sx; A.sz = o.sz; A.y0 = (float)origin[1]; A.sy = (float)o.sy;
+      A.sid = o.sid; A.sdd = o.sdd; A.inv_du = 1.0 / o.du; A.inv_dv = 1.0 / o.dv; A.u0 = o.u0; A.v0 = o.v0;
+      A.K = o.sx * o.sy * o.sz / (o.du * o.dv);
+      int m = 0;
+      while (k + m < o.n_proj && m < kBpBatch && fl[k + m] == A.fl && fh[k + m] == A.fh) {
+        const int p = k + m;
+        const double t = o.gantry_deg[p] * M_PI / 180.0;
+        A.c[m] = std::cos(t); A.s[m] = std::sin(t);
+        A.off_x[m] = o.proj_offset_x ? o.proj_offset_x[p] : 0.0;
+        A.av_b[m] = (float)((-(o.proj_offset_y ? o.proj_offset_y[p] : 0.0) - o.v0) / o.dv);
+        A.wl[m] = (float)wl[p]; A.wh[m] = (float)wh[p];
+        ++m;
+      }
+      A.nb = m;
+      bp.push_back(A);
+      bp_first.push_back(k);
+      k += m;
+    }
+  }
+
+  void init() {
+    RS_HIP(hipSetDevice(o.device));
+    RS_HIP(hipEventCreate(&dev.e0));
+    RS_HIP(hipEventCreate(&dev.e1));
+    d_part = dev.alloc<double>(kRedBlocks * sizeof(double));
+    d_sum = dev.alloc<double>(sizeof(double));
+  }
+  float* alloc4d() { return dev.alloc<float>(n4 * 16); }
+  float* alloc_proj() { return dev.alloc<float>((size_t)o.n_proj * plane * 4); }
+
+  // proj = R S x4
+  void forward(const float* x4, float* proj) {
+    Stage st(dev, rep.ms_forward);
+    Fp4Args A = fa;
+    for (int b = 0; b < o.n_proj; b += kFpBatch) {
+      A.nb = std::min(kFpBatch, o.n_proj - b);
+      for (int k = 0; k < A.nb; ++k) {
+        const int p = b + k;
+        const double t = o.gantry_deg[p] * M_PI / 180.0;
+        A.pp[k] = {std::cos(t), std::sin(t), o.proj_offset_x ? o.proj_offset_x[p] : 0.0, o.proj_offset_y ? o.proj_offset_y[p] : 0.0};
+        A.fl[k] = fl[p]; A.fh[k] = fh[p]; A.wl[k] = (float)wl[p]; A.wh[k] = (float)wh[p];
+      }
+      hipLaunchKernelGGL(fp4_kernel, dim3((unsigned)((o.nu + 15) / 16), (unsigned)((o.nv + 15) / 16), (unsigned)A.nb), dim3(256), 0, nullptr,
+                         proj + (size_t)b * plane, A, x4, frame);
+    }
+    st.done();
+  }
+
+  // x4 = S^T B proj
+  void back(const float* proj, float* x4) {
+    Stage st(dev, rep.ms_back);
+    RS_HIP(hipMemsetAsync(x4, 0, n4 * 16, nullptr));
+    for (size_t i = 0; i < bp.size(); ++i)
+      hipLaunchKernelGGL(bp4_kernel, dim3((unsigned)((o.nx + 255) / 256), (unsigned)o.nz), dim3(256), 0, nullptr, x4, frame,
+                         proj + (size_t)bp_first[i] * plane, bp[i]);
+    st.done();
+  }
+
+  double reduce() {  // second stage of a dot product whose partials are in d_part
+    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(kThreads), 0, nullptr, d_part, d_sum);
+    double s = 0.0;
+    RS_HIP(hipMemcpy(&s, d_sum, sizeof s, hipMemcpyDeviceToHost));
+    return s;
+  }
+
+  double dot(const float* a, const float* b) {
+    Stage st(dev, rep.ms_cg_vectors);
+    hipLaunchKernelGGL(dot_partial_kernel, dim3(kRedBlocks), dim3(kThreads), 0, nullptr, (const float4*)a, (const float4*)b, n4, d_part);
+    const double s = reduce();
+    st.done();
+    return s;
+  }
+
+  void tv_space(float* x4, float* work /*4 frames*/, int iters, float gamma) {
+    Stage st(dev, rep.ms_tv_space);
+    float *px = work, *py = work + frame, *pz = work + 2 * frame, *u = work + 3 * frame;
+    const float tau = 1.f / 12.f;
+    const unsigned g = (unsigned)std::min<size_t>((frame + kThreads - 1) / kThreads, 65536);
+    for (int f = 0; f < N; ++f) {
+      float* x = x4 + (size_t)f * frame;
+      RS_HIP(hipMemsetAsync(work, 0, 3 * frame * 4, nullptr));
+      for (int it = 0; it < iters; ++it) {
+        hipLaunchKernelGGL(tv_space_div_kernel, dim3(g), dim3(kThreads), 0, nullptr, x, px, py, pz, u, o.nx, o.ny, o.nz);
+        hipLaunchKernelGGL(tv_space_grad_kernel, dim3(g), dim3(kThreads), 0, nullptr, u, px, py, pz, o.nx, o.ny, o.nz, tau, gamma);
+      }
+      hipLaunchKernelGGL(tv_space_div_kernel, dim3(g), dim3(kThreads), 0, nullptr, x, px, py, pz, x, o.nx, o.ny, o.nz);
+    }
+    st.done();
+  }
+
+  void tv_time(float* x4, int iters, float gamma) {
+    Stage st(dev, rep.ms_tv_time);
+    const dim3 g((unsigned)((frame + kThreads - 1) / kThreads));
+    if (N <= 16) hipLaunchKernelGGL(tv_time_kernel<16>, g, dim3(kThreads), 0, nullptr, x4, frame, N, iters, 0.25f, gamma);
+    else hipLaunchKernelGGL(tv_time_kernel<kMaxFrames>, g, dim3(kThreads), 0, nullptr, x4, frame, N, iters, 0.25f, gamma);
+    st.done();
+  }
+
+  float* upload_projections(const float* projections, bool wpc) {
+    const auto t0 = std::chrono::steady_clock::now();
+    float* d = alloc_proj();
+    RS_HIP(hipMemcpy(d, projections, (size_t)o.n_proj * plane * 4, hipMemcpyHostToDevice));
+    if (wpc && o.n_wpc > 0) {
+      std::vector<float> c(o.wpc, o.wpc + o.n_wpc);
+      float* d_c = dev.alloc<float>(c.size() * 4);
+      RS_HIP(hipMemcpy(d_c, c.data(), c.size() * 4, hipMemcpyHostToDevice));
+      hipLaunchKernelGGL(wpc_kernel, dim3(kRedBlocks), dim3(kThreads), 0, nullptr, d, (size_t)o.n_proj * plane, d_c, o.n_wpc);
+      RS_HIP(hipGetLastError());
+      RS_HIP(hipDeviceSynchronize());
+    }
+    rep.ms_upload += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return d;
+  }
+
+  float* upload_4d(const float* v) {
+    const auto t0 = std::chrono::steady_clock::now();
+    float* d = alloc4d();
+    RS_HIP(hipMemcpy(d, v, n4d * 4, hipMemcpyHostToDevice));
+    rep.ms_upload += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return d;
+  }
+
+  void run(const float* projections, float* volume4d) {
+    float* q = upload_projections(projections, true);     // measured projections; after b they hold R S d
+    float* x = alloc4d();
+    float* b = alloc4d();
+    float* r = alloc4d();
+    float* d = alloc4d();
+    float* Ad = alloc4d();
+    float* work = dev.alloc<float>(4 * frame * 4);
+    back(q, b);
+    const unsigned g = kRedBlocks;
+    bool x_zero = true;
+    for (int it = 0; it < o.niter; ++it) {
+      double* res = o.residuals ? o.residuals + (size_t)it * (o.cgiter + 1) : nullptr;
+      if (x_zero) {
+        RS_HIP(hipMemsetAsync(Ad, 0, n4 * 16, nullptr));  // A 0 = 0
+      } else {
+        forward(x, q);
+        back(q, Ad);
+      }
+      double rr;
+      {
+        Stage st(dev, rep.ms_cg_vectors);
+        hipLaunchKernelGGL(cg_restart_kernel, dim3(g), dim3(kThreads), 0, nullptr, (const float4*)b, (const float4*)Ad, (float4*)r, (float4*)d, n4, d_part);
+        rr = reduce();
+        st.done();
+      }
+      if (res) res[0] = std::sqrt(rr);
+      for (int j = 0; j < o.cgiter; ++j) {
+        double alpha = 0.0, rr_new = rr;
+        if (rr > 0.0) {
+          forward(d, q);
+          back(q, Ad);
+          const double dAd = dot(d, Ad);
+          if (dAd > 0.0) {
+            alpha = rr / dAd;
+            Stage st(dev, rep.ms_cg_vectors);
+            hipLaunchKernelGGL(cg_update_kernel, dim3(g), dim3(kThreads), 0, nullptr, (float4*)x, (float4*)r, (const float4*)d, (const float4*)Ad, (float)alpha,
+                               n4, d_part);
+            rr_new = reduce();
+            const double beta = rr > 0.0 ? rr_new / rr : 0.0;
+            hipLaunchKernelGGL(cg_direction_kernel, dim3(g), dim3(kThreads), 0, nullptr, (const float4*)r, (float4*)d, (float)beta, n4);
+            st.done();
+            x_zero = false;
+          }
+        }
+        rr = rr_new;
+        if (res) res[j + 1] = std::sqrt(rr);
+      }
+      if (o.positivity) {
+        Stage st(dev, rep.ms_cg_vectors);
+        hipLaunchKernelGGL(positivity_kernel, dim3(g), dim3(kThreads), 0, nullptr, (float4*)x, n4);
+        st.done();
+      }
+      if (o.tviter > 0) {
+        tv_space(x, work, o.tviter, (float)o.gamma_space);
+        tv_time(x, o.tviter, (float)o.gamma_time);
+      }
+    }
+    RS_HIP(hipMemcpy(volume4d, x, n4d * 4, hipMemcpyDeviceToHost));
+  }
+
+  void stage(int which, const float* in, float* out) {
+    if (which == MCGPU_ROOSTER4D_STAGE_FORWARD) {
+      float* x = upload_4d(in);
+      float* q = alloc_proj();
+      forward(x, q);
+      RS_HIP(hipMemcpy(out, q, (size_t)o.n_proj * plane * 4, hipMemcpyDeviceToHost));
+      return;
+    }
+    if (which == MCGPU_ROOSTER4D_STAGE_BACK) {
+      float* q = upload_projections(in, false);
+      float* x = alloc4d();
+      back(q, x);
+      RS_HIP(hipMemcpy(out, x, n4d * 4, hipMemcpyDeviceToHost));
+      return;
+    }
+    float* x = upload_4d(in);
+    if (which == MCGPU_ROOSTER4D_STAGE_TV_SPACE) {
+      float* work = dev.alloc<float>(4 * frame * 4);
+      tv_space(x, work, o.tviter, (float)o.gamma_space);
+    } else {
+      tv_time(x, o.tviter, (float)o.gamma_time);
+    }
+    RS_HIP(hipMemcpy(out, x, n4d * 4, hipMemcpyDeviceToHost));
+  }
+};
+
+}  // namespace
+
+extern "C" int mcgpu_rooster4d_reconstruct(const mcgpu_rooster4d_options* caller_o, const float* projections, float* volume4d, mcgpu_rooster4d_report* report) {
+  mcgpu_rooster4d_options o;
+  if (!read_options("mcgpu_rooster4d_reconstruct", caller_o, o)) return -1;
+  if (!projections || !volume4d) return fail("mcgpu_rooster4d_reconstruct", "projections or volume is NULL"), -1;
+  try {
+    const auto t0 = std::chrono::steady_clock::now();
+    Problem P(o);
+    P.init();
+    P.run(projections, volume4d);
+    P.rep.peak_device_bytes = P.dev.peak;
+    P.rep.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (report) *report = P.rep;
+  } catch (const RsError& e) {
+    mcgpu_set_last_error_(e.msg.c_str());
+    return -1;
+  }
+  return 0;
+}
+
+extern "C" int mcgpu_rooster4d_stage(const mcgpu_rooster4d_options* caller_o, int stage, const float* in, float* out, mcgpu_rooster4d_report* report) {
+  mcgpu_rooster4d_options o;
+  if (!read_options("mcgpu_rooster4d_stage", caller_o, o)) return -1;
+  if (stage < MCGPU_ROOSTER4D_STAGE_FORWARD || stage > MCGPU_ROOSTER4D_STAGE_TV_TIME)
+    return fail("mcgpu_rooster4d_stage", "unknown stage " + std::to_string(stage)), -1;
+  if (!in || !out) return fail("mcgpu_rooster4d_stage", "in or out is NULL"), -1;
+  try {
+    const auto t0 = std::chrono::steady_clock::now();
+    Problem P(o);
+    P.init();
+    P.stage(stage, in, out);
+    P.rep.peak_device_bytes = P.dev.peak;
+    P.rep.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (report) *report = P.rep;
+  } catch (const RsError& e) {
+    mcgpu_set_last_error_(e.msg.c_str());
+    return -1;
+  }
+  return 0;
+}

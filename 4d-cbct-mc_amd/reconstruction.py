@@ -150,7 +150,8 @@ def fdk(projections: np.ndarray, geometry: CircularGeometry, pixel_spacing: Tupl
 
 
 def read_mha(path):
-    """(array [n2, n1, n0] float32, spacing, origin) of an uncompressed MetaImage written by this engine or SimpleITK."""
+    """(array [n2, n1, n0] float32, spacing, origin) of an uncompressed MetaImage written by this engine or SimpleITK; a 4-D
+    image gives [n3, n2, n1, n0] and 4 spacings and offsets."""
     raw = Path(path).read_bytes()
     head_end = raw.index(b"ElementDataFile")
     head_end = raw.index(b"\n", head_end) + 1
@@ -169,15 +170,27 @@ def read_mha(path):
 
 
 def write_mha(path, volume: np.ndarray, spacing, origin) -> Path:
-    """float32 [n2, n1, n0] -> uncompressed MetaImage (what SimpleITK.WriteImage produces for such an image)."""
+    """float32 [n2, n1, n0] -> uncompressed MetaImage (what SimpleITK.WriteImage produces for such an image).  A 4-D array
+    [n3, n2, n1, n0] (e.g. the frames of reconstruct_4d) is written with NDims = 4; spacing and origin then have 4 entries."""
     path = Path(path)
     v = np.ascontiguousarray(volume, dtype="<f4")
     d = v.shape[::-1]
-    head = ("ObjectType = Image\nNDims = 3\nBinaryData = True\nBinaryDataByteOrderMSB = False\nCompressedData = False\n"
-            "TransformMatrix = 1 0 0 0 1 0 0 0 1\n"
-            f"Offset = {origin[0]:.15g} {origin[1]:.15g} {origin[2]:.15g}\nCenterOfRotation = 0 0 0\nAnatomicalOrientation = RAI\n"
-            f"ElementSpacing = {spacing[0]:.15g} {spacing[1]:.15g} {spacing[2]:.15g}\nDimSize = {d[0]} {d[1]} {d[2]}\n"
-            "ElementType = MET_FLOAT\nElementDataFile = LOCAL\n")
+    if v.ndim == 3:
+        head = ("ObjectType = Image\nNDims = 3\nBinaryData = True\nBinaryDataByteOrderMSB = False\nCompressedData = False\n"
+                "TransformMatrix = 1 0 0 0 1 0 0 0 1\n"
+                f"Offset = {origin[0]:.15g} {origin[1]:.15g} {origin[2]:.15g}\nCenterOfRotation = 0 0 0\nAnatomicalOrientation = RAI\n"
+                f"ElementSpacing = {spacing[0]:.15g} {spacing[1]:.15g} {spacing[2]:.15g}\nDimSize = {d[0]} {d[1]} {d[2]}\n"
+                "ElementType = MET_FLOAT\nElementDataFile = LOCAL\n")
+    elif v.ndim == 4:
+        if len(spacing) != 4 or len(origin) != 4:
+            raise ValueError("a 4-D MetaImage needs 4 spacings and 4 offsets")
+        eye = " ".join("1" if i == j else "0" for i in range(4) for j in range(4))
+        head = ("ObjectType = Image\nNDims = 4\nBinaryData = True\nBinaryDataByteOrderMSB = False\nCompressedData = False\n"
+                f"TransformMatrix = {eye}\nOffset = {' '.join(f'{float(o):.15g}' for o in origin)}\nCenterOfRotation = 0 0 0 0\n"
+                f"ElementSpacing = {' '.join(f'{float(x):.15g}' for x in spacing)}\nDimSize = {' '.join(str(n) for n in d)}\n"
+                "ElementType = MET_FLOAT\nElementDataFile = LOCAL\n")
+    else:
+        raise ValueError(f"write_mha: {v.ndim}-D arrays are not supported (3 or 4)")
     with open(path, "wb") as f:
         f.write(head.encode())
         f.write(v.tobytes())
@@ -216,3 +229,154 @@ def reconstruct_3d(projections_filepath, geometry_filepath, output_folder=None, 
     with open((output_folder / output_filename).with_suffix(".yaml"), "w") as f:
         yaml.dump(params, f)
     return output_folder / output_filename, report
+
+
+# ---------------------------------------------------------------------------------------------------------------- 4-D ROOSTER
+class _RoosterOptions(C.Structure):
+    """mcgpu_rooster4d_options (include/mcgpu_amd.h)."""
+    _fields_ = [("struct_size", C.c_uint), ("n_proj", C.c_int), ("nu", C.c_int), ("nv", C.c_int), ("du", C.c_double), ("dv", C.c_double),
+                ("u0", C.c_double), ("v0", C.c_double), ("sid", C.c_double), ("sdd", C.c_double), ("gantry_deg", C.POINTER(C.c_double)),
+                ("proj_offset_x", C.POINTER(C.c_double)), ("proj_offset_y", C.POINTER(C.c_double)), ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int),
+                ("sx", C.c_double), ("sy", C.c_double), ("sz", C.c_double), ("ox", C.c_double), ("oy", C.c_double), ("oz", C.c_double),
+                ("n_frames", C.c_int), ("phase", C.POINTER(C.c_double)), ("niter", C.c_int), ("cgiter", C.c_int), ("tviter", C.c_int),
+                ("gamma_space", C.c_double), ("gamma_time", C.c_double), ("positivity", C.c_int), ("wpc", C.POINTER(C.c_double)),
+                ("n_wpc", C.c_int), ("device", C.c_int), ("residuals", C.POINTER(C.c_double))]
+
+
+class _RoosterReport(C.Structure):
+    _fields_ = [("ms_forward", C.c_double), ("ms_back", C.c_double), ("ms_cg_vectors", C.c_double), ("ms_tv_space", C.c_double),
+                ("ms_tv_time", C.c_double), ("ms_upload", C.c_double), ("ms_total", C.c_double), ("peak_device_bytes", C.c_ulonglong)]
+
+
+ROOSTER4D_STAGES = {"forward": 0, "back": 1, "tv_space": 2, "tv_time": 3}
+
+
+def _rooster_call(n_proj, nu, nv, geometry, pixel_spacing, pixel_origin, phase, dimension, spacing, origin, frames, niter, cgiter, tviter,
+                  gamma_time, gamma_space, water_pre_correction, positivity, gpu_id):
+    """(options, the arrays it points into) for mcgpu_rooster4d_*."""
+    from . import engine
+    lib = engine.load_library()
+    lib.mcgpu_rooster4d_reconstruct.argtypes = [C.POINTER(_RoosterOptions), C.c_void_p, C.c_void_p, C.POINTER(_RoosterReport)]
+    lib.mcgpu_rooster4d_stage.argtypes = [C.POINTER(_RoosterOptions), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(_RoosterReport)]
+    if n_proj != len(geometry.gantry_angles):
+        raise ValueError(f"{n_proj} projections but {len(geometry.gantry_angles)} geometry entries")
+    ph = np.ascontiguousarray(phase, dtype=np.float64).ravel()
+    if ph.size != n_proj:
+        raise ValueError(f"{n_proj} projections but {ph.size} phase values")
+    du, dv = float(pixel_spacing[0]), float(pixel_spacing[1])
+    u0, v0 = pixel_origin if pixel_origin is not None else (-(nu - 1) / 2 * du, -(nv - 1) / 2 * dv)
+    keep = dict(ang=np.ascontiguousarray(geometry.gantry_angles, dtype=np.float64), ox=np.ascontiguousarray(geometry.projection_offsets_x, dtype=np.float64),
+                oy=np.ascontiguousarray(geometry.projection_offsets_y, dtype=np.float64), phase=ph,
+                wpc=np.ascontiguousarray(water_pre_correction if water_pre_correction is not None else [], dtype=np.float64),
+                residuals=np.zeros(max(int(niter), 0) * (max(int(cgiter), 0) + 1), dtype=np.float64))
+    dp = C.POINTER(C.c_double)
+    o = _RoosterOptions(C.sizeof(_RoosterOptions), int(n_proj), int(nu), int(nv), du, dv, float(u0), float(v0), float(geometry.source_to_isocenter),
+                        float(geometry.source_to_detector), keep["ang"].ctypes.data_as(dp), keep["ox"].ctypes.data_as(dp), keep["oy"].ctypes.data_as(dp),
+                        int(dimension[0]), int(dimension[1]), int(dimension[2]), float(spacing[0]), float(spacing[1]), float(spacing[2]),
+                        *(tuple(float(v) for v in origin) if origin is not None else (float("nan"),) * 3), int(frames), keep["phase"].ctypes.data_as(dp),
+                        int(niter), int(cgiter), int(tviter), float(gamma_space), float(gamma_time), int(bool(positivity)),
+                        keep["wpc"].ctypes.data_as(dp) if keep["wpc"].size else None, int(keep["wpc"].size), int(gpu_id),
+                        keep["residuals"].ctypes.data_as(dp) if keep["residuals"].size else None)
+    return lib, o, keep
+
+
+def _rooster_report(rep: _RoosterReport) -> dict:
+    return {name: getattr(rep, name) for name, _ in _RoosterReport._fields_}
+
+
+def rooster4d(projections: np.ndarray, geometry: CircularGeometry, pixel_spacing: Tuple[float, float], pixel_origin: Optional[Tuple[float, float]],
+              phase: Sequence[float], dimension: Tuple[int, int, int] = (464, 250, 464), spacing: Tuple[float, float, float] = (1.0, 1.0, 1.0),
+              origin: Optional[Tuple[float, float, float]] = None, frames: int = 10, niter: int = 10, cgiter: int = 4, tviter: int = 10,
+              gamma_time: float = 0.0002, gamma_space: float = 0.00007, water_pre_correction: Optional[Sequence[float]] = None,
+              positivity: bool = True, gpu_id: int = 0):
+    """4-D ROOSTER (csrc/rooster4d.hip, whose header spells out the algorithm; what `rtkfourdrooster` computes for the reference):
+    projections [n, nv, nu] (line integrals), phase [n] in [0, 1] -> (volume [frames, nz, ny, nx] float32 in RTK's IEC frame on
+    the FDK grid, report dict).
+
+    Frame f of the result is the volume at phase f / frames; a projection at phase phi sees the linear blend of frames
+    floor(phi N) mod N and the next one (periodic).  Each of `niter` main iterations runs `cgiter` conjugate-gradient steps on
+    S^T B R S x = S^T B p from the current x (R = the Joseph forward projector, B = a voxel-driven back-projector weighted to be
+    close to R^T, S = the phase interpolation), then x = max(x, 0) when `positivity`, then `tviter` iterations of spatial TV
+    denoising (gamma_space, per frame) and of temporal TV denoising (gamma_time, per voxel, periodic).  `water_pre_correction`
+    is rtkfdk's --wpc polynomial, applied to the projections first.  frames = 10 is taken to be rtkfourdrooster's --frames
+    default; that could not be confirmed here (neither RTK nor its documentation is available).  Parity against RTK itself is
+    unpinned; tests/rooster_ref.py restates the algorithm in float64.
+
+    report: ms per stage (ms_forward, ms_back, ms_cg_vectors, ms_tv_space, ms_tv_time, ms_upload, ms_total), peak_device_bytes,
+    and residuals [niter][cgiter + 1] (|r| at each CG restart and after each CG step)."""
+    from . import engine
+    p = np.ascontiguousarray(projections, dtype=np.float32)
+    n, nv, nu = p.shape
+    lib, o, keep = _rooster_call(n, nu, nv, geometry, pixel_spacing, pixel_origin, phase, dimension, spacing, origin, frames, niter, cgiter, tviter,
+                                 gamma_time, gamma_space, water_pre_correction, positivity, gpu_id)
+    vol = np.zeros((int(frames), int(dimension[2]), int(dimension[1]), int(dimension[0])), dtype=np.float32)
+    rep = _RoosterReport()
+    engine._check(lib.mcgpu_rooster4d_reconstruct(C.byref(o), p.ctypes.data, vol.ctypes.data, C.byref(rep)))
+    out = _rooster_report(rep)
+    out["residuals"] = keep["residuals"].reshape(max(int(niter), 0), max(int(cgiter), 0) + 1).copy()
+    return vol, out
+
+
+def rooster4d_stage(stage: str, data: np.ndarray, geometry: CircularGeometry, detector: Tuple[int, int], pixel_spacing, pixel_origin, phase,
+                    dimension, spacing, origin=None, frames: int = 10, tviter: int = 10, gamma_time: float = 0.0002, gamma_space: float = 0.00007,
+                    gpu_id: int = 0):
+    """One operator of rooster4d alone (mcgpu_rooster4d_stage): 'forward' (R S: [frames, nz, ny, nx] -> [n, nv, nu]), 'back'
+    (S^T B: projections -> 4-D), 'tv_space' / 'tv_time' (4-D -> 4-D, `tviter` iterations).  detector = (nu, nv)."""
+    from . import engine
+    nu, nv = int(detector[0]), int(detector[1])
+    n = len(geometry.gantry_angles)
+    lib, o, keep = _rooster_call(n, nu, nv, geometry, pixel_spacing, pixel_origin, phase, dimension, spacing, origin, frames, 0, 0, tviter,
+                                 gamma_time, gamma_space, None, True, gpu_id)
+    shape4 = (int(frames), int(dimension[2]), int(dimension[1]), int(dimension[0]))
+    code = ROOSTER4D_STAGES[stage]
+    src = np.ascontiguousarray(data, dtype=np.float32)
+    if src.shape != ((n, nv, nu) if stage == "back" else shape4):
+        raise ValueError(f"rooster4d_stage {stage}: input shape {src.shape}")
+    out = np.zeros((n, nv, nu) if stage == "forward" else shape4, dtype=np.float32)
+    rep = _RoosterReport()
+    engine._check(lib.mcgpu_rooster4d_stage(C.byref(o), code, src.ctypes.data, out.ctypes.data, C.byref(rep)))
+    return out, _rooster_report(rep)
+
+
+def reconstruct_4d(projections_filepath, geometry_filepath, output_folder=None, output_filename: Optional[str] = None,
+                   dimension: Tuple[int, int, int] = (464, 250, 464), spacing: Tuple[float, float, float] = (1.0, 1.0, 1.0),
+                   amplitude_signal: Optional[np.ndarray] = None, phase_signal: Optional[np.ndarray] = None,
+                   water_pre_correction: Optional[Sequence[float]] = None, gpu_id: int = 0, **kwargs):
+    """cbctmc/reconstruction/reconstruction.py:72-125 with `rtkfourdrooster` replaced by the in-process kernels (rooster4d).
+    Exactly one of `amplitude_signal` (one breathing amplitude per projection; its phase comes from phase.calculate_phase) and
+    `phase_signal` is given, else ValueError.  The phase is min-max scaled to [0, 1] as the reference does before it hands the
+    signal to RTK (reconstructors.py:150-151).  The reference's parameters: niter 10, cgiter 4, tviter 10, gamma_time 0.0002,
+    gamma_space 0.00007 (keyword arguments override them, as do `frames` and `positivity`).  Writes `recon_rooster4d.mha`, a 4-D
+    MetaImage [frames][nz][ny][nx] with spacing (sx, sy, sz, 1) and offset (ox, oy, oz, 0) in the frame of reconstruct_3d's
+    output, and a .yaml of the parameters next to it (fp / bp record what ran: Joseph / VoxelBased)."""
+    from . import phase as phase_mod
+    if (amplitude_signal is None) == (phase_signal is None):
+        raise ValueError("give exactly one of amplitude_signal and phase_signal")
+    if phase_signal is None:
+        phase_signal = np.hstack(phase_mod.calculate_phase(np.asarray(amplitude_signal)))
+    ph = np.array(phase_signal, dtype=np.float64)
+    ph -= ph.min()
+    span = ph.max()
+    if not span > 0:
+        raise ValueError("the phase signal is constant: it cannot be scaled to [0, 1]")
+    ph /= span
+    projections_filepath, geometry_filepath = Path(projections_filepath), Path(geometry_filepath)
+    output_folder = Path(output_folder) if output_folder else projections_filepath.parent / "reconstructions"
+    output_filename = output_filename or "recon_rooster4d.mha"
+    output_folder.mkdir(parents=True, exist_ok=True)
+    params = dict(niter=10, cgiter=4, tviter=10, gamma_time=0.0002, gamma_space=0.00007, frames=10, positivity=True)
+    params.update({k: kwargs.pop(k) for k in list(kwargs) if k in params})
+    proj, pspacing, porigin = read_mha(projections_filepath)
+    geometry = CircularGeometry.read(geometry_filepath)
+    vol, report = rooster4d(proj, geometry, (pspacing[0], pspacing[1]), (porigin[0], porigin[1]), ph, dimension, spacing, None,
+                            water_pre_correction=water_pre_correction, gpu_id=gpu_id, **params)
+    origin = tuple(-(n - 1) / 2 * s for n, s in zip(dimension, spacing))
+    out = output_folder / output_filename
+    write_mha(out, vol, tuple(spacing) + (1.0,), origin + (0.0,))
+    import yaml
+    record = dict(path=str(projections_filepath.parent), regexp=projections_filepath.name, geometry=str(geometry_filepath), fp="Joseph",
+                  bp="VoxelBased", hardware="hip", dimension=list(dimension), spacing=list(spacing),
+                  wpc=list(water_pre_correction) if water_pre_correction is not None else None, output_filepath=str(out), **params, **kwargs)
+    with open(out.with_suffix(".yaml"), "w") as f:
+        yaml.dump(record, f)
+    return out, report

@@ -433,6 +433,53 @@ int mcgpu_forward_project(const mcgpu_fp_options *options, const float *volume, 
  * IEC size is (vox ny, vox nz, vox nx). */
 int mcgpu_forward_project_context(mcgpu_ctx *ctx, const mcgpu_fp_options *options, float *projections, mcgpu_fp_report *report);
 
+/* ------------------------------------------------------------------------------------------------
+ * Row f6: 4-D ROOSTER reconstruction (what the reference obtains from RTK's `rtkfourdrooster`,
+ * cbctmc/reconstruction/reconstruction.py: reconstruct_4d; csrc/rooster4d.hip, whose header spells out the algorithm).
+ * Geometry, detector grid, volume grid and wpc as mcgpu_fdk_options; the result is n_frames volumes [n_frames][nz][ny][nx]
+ * of the FDK grid.  phase[k] in [0, 1] places projection k between frames floor(phase N) mod N and the next one (periodic).
+ * Each of niter main iterations runs cgiter conjugate-gradient steps on S^T B R S x = S^T B p (R = Joseph forward projection,
+ * B = its approximate adjoint, S = the phase interpolation), then positivity (when `positivity` is non-zero), then tviter
+ * iterations of spatial TV denoising (gamma_space) of every frame and of temporal TV denoising (gamma_time, periodic) of every
+ * voxel's series.  Parity against rtkfourdrooster itself is unpinned (RTK is absent here). */
+typedef struct mcgpu_rooster4d_options {
+  unsigned int struct_size;     /* sizeof(mcgpu_rooster4d_options) as the caller was compiled (later fields read as zero); 0 is refused */
+  int n_proj, nu, nv;           /* nu, nv >= 2 */
+  double du, dv, u0, v0;
+  double sid, sdd;
+  const double *gantry_deg;     /* [n_proj] */
+  const double *proj_offset_x;  /* [n_proj] or NULL (0) */
+  const double *proj_offset_y;  /* [n_proj] or NULL (0) */
+  int nx, ny, nz;
+  double sx, sy, sz, ox, oy, oz; /* mm; origin = centre of voxel (0,0,0), NaN = volume centred on the isocentre */
+  int n_frames;                 /* 1..32 */
+  const double *phase;          /* [n_proj], each in [0, 1] */
+  int niter, cgiter, tviter;
+  double gamma_space, gamma_time;
+  int positivity;               /* non-zero: x = max(x, 0) after the CG steps of every main iteration */
+  const double *wpc;            /* water pre-correction polynomial (rtkfdk --wpc) applied to the projections, or NULL */
+  int n_wpc;
+  int device;
+  double *residuals;            /* optional [niter][cgiter + 1]: |r| at the restart and after each CG step of every main iteration */
+} mcgpu_rooster4d_options;
+typedef struct mcgpu_rooster4d_report {
+  double ms_forward;            /* R S: 4-D forward projection kernels */
+  double ms_back;               /* S^T B: 4-D back-projection kernels */
+  double ms_cg_vectors;         /* CG vector updates, dot products, positivity */
+  double ms_tv_space;           /* spatial TV kernels */
+  double ms_tv_time;            /* temporal TV kernel */
+  double ms_upload;             /* host -> device copies (and the water pre-correction) */
+  double ms_total;              /* wall time of the call */
+  unsigned long long peak_device_bytes;  /* most device memory the call held at once */
+} mcgpu_rooster4d_report;
+int mcgpu_rooster4d_reconstruct(const mcgpu_rooster4d_options *options, const float *projections /*[n_proj][nv][nu]*/,
+                                float *volume4d /*[n_frames][nz][ny][nx]*/, mcgpu_rooster4d_report *report);
+/* One operator alone (for tests): FORWARD in = 4-D volume -> out = projections (R S); BACK in = projections -> out = 4-D volume
+ * (S^T B; no water pre-correction); TV_SPACE / TV_TIME in = 4-D volume -> out = 4-D volume (tviter iterations, gamma_space /
+ * gamma_time).  niter, cgiter, positivity and residuals are not used. */
+enum { MCGPU_ROOSTER4D_STAGE_FORWARD = 0, MCGPU_ROOSTER4D_STAGE_BACK = 1, MCGPU_ROOSTER4D_STAGE_TV_SPACE = 2, MCGPU_ROOSTER4D_STAGE_TV_TIME = 3 };
+int mcgpu_rooster4d_stage(const mcgpu_rooster4d_options *options, int stage, const float *in, float *out, mcgpu_rooster4d_report *report);
+
 #ifdef __cplusplus
 }
 #endif
