@@ -1,10 +1,12 @@
 """Float64 numpy restatement of 4-D ROOSTER (csrc/rooster4d.hip; its header spells out the algorithm), the oracle of
-tests/test_rooster4d.py.  R is joseph_ref.project on the phase blend of two frames; everything else is restated here:
+tests/test_rooster4d.py and tests/test_rooster4d_configs.py.  R is joseph_ref.project on the phase blend of two frames; everything
+else is restated here:
   weights   phase -> (l, h, w_l, w_h):  t = phi N, l = floor(t) mod N, h = (l + 1) mod N, w_h = t - floor(t), w_l = 1 - w_h
   back      S^T B: voxel-driven bilinear gather (a sample counts only with both detector columns and both rows inside), weight
             (sdd / U)^2 sx sy sz / (du dv), U = sid - z_rot, distributed into frames l and h with w_l and w_h
   tv_*      min 1/2 |u - f|^2 + gamma TV(u) by tviter dual projected-gradient steps from p = 0, tau = 1 / (4 d)
-  rooster   niter x (cgiter CG steps restarted from x, positivity, spatial TV per frame, temporal TV per voxel)
+  rooster   optional water pre-correction p <- sum_j c_j p^j, then niter x (cgiter CG steps restarted from x, positivity,
+            spatial TV per frame, temporal TV per voxel)
 Vectors are [N][nz][ny][nx]; projections [n][nv][nu]."""
 from __future__ import annotations
 
@@ -159,7 +161,15 @@ def cg(apply_A, b, x, iters, residuals=None):
     return x
 
 
-def rooster(g: Geometry, projections, niter, cgiter, tviter, gamma_space, gamma_time, positivity=True, residuals=None):
+def water_precorrection(p, wpc):
+    """sum_j c_j p^j (rtkfdk --wpc), in float64."""
+    p = np.asarray(p, dtype=np.float64)
+    return sum(c * p ** j for j, c in enumerate(wpc))
+
+
+def rooster(g: Geometry, projections, niter, cgiter, tviter, gamma_space, gamma_time, positivity=True, residuals=None, wpc=None):
+    if wpc is not None and len(wpc) > 0:  # applied to the projections before b, as the kernel does
+        projections = water_precorrection(projections, wpc)
     b = back(g, projections)
     A = lambda v: back(g, forward(g, v))  # noqa: E731
     x = np.zeros(g.shape4())
