@@ -4,8 +4,9 @@
 // (parity unpinned against RTK, pinned by analytic phantoms) and implemented here as four kernels:
 //   weight      : water pre-correction polynomial, cosine weight, displaced-detector (half-fan) weight, zero padding of the
 //                 short side to a detector symmetric about the central ray                                     (streaming)
-//   ramp        : rows zero-extended to L = 4096, batched hipFFT R2C -> multiply by the real spectrum of the (Hann-apodised)
-//                 ramp -> C2R (HBM streaming); ramp_rows = the direct LDS convolution kept for A/B (MCGPU_FDK_DIRECT_RAMP)
+//   ramp        : rows zero-extended to L (7500 at the reference's size), batched hipFFT R2C -> multiply by the real spectrum of
+//                 the (Hann-apodised) ramp -> C2R (HBM streaming); ramp_rows = the direct LDS convolution kept for A/B
+//                 (MCGPU_FDK_DIRECT_RAMP)
 //   extend_rows : --pad (RTK TruncationCorrection): every row continued on both sides by next = ceil(pad x width) columns with
 //                 the feathered point reflection 2 p(border) - p(mirror), so that a truncated edge does not ring     (streaming)
 //   smooth_cols : --hannY low-pass along v (3 taps for 1.0)                                                     (streaming)
@@ -363,11 +364,17 @@ extern "C" int mcgpu_fdk_reconstruct(const mcgpu_fdk_options* caller_o, const fl
     }
     const double ox0 = std::isnan(o->ox) ? -(o->nx - 1) / 2.0 * o->sx : o->ox, oy0 = std::isnan(o->oy) ? -(o->ny - 1) / 2.0 * o->sy : o->oy,
                  oz0 = std::isnan(o->oz) ? -(o->nz - 1) / 2.0 * o->sz : o->oz;
-    // symmetric padding of an off-centre detector (oracle/fdk_oracle.py: symmetric_padding)
+    // symmetric padding of an off-centre detector (oracle/fdk_oracle.py: symmetric_padding), from the double offsets as the Wang
+    // weights take them: the float offsets of pp[] can move the ceiling by one column where -2 off / du is an integer (the reference's
+    // -159.856 mm at 0.388 mm pixels)
     int pad_l = 0, pad_r = 0;
     {
       double off_min = 1e300, off_max = -1e300;
-      for (int k = 0; k < n; ++k) { off_min = std::min(off_min, (double)pp[k].off_x); off_max = std::max(off_max, (double)pp[k].off_x); }
+      for (int k = 0; k < n; ++k) {
+        const double ox = o->proj_offset_x ? o->proj_offset_x[k] : 0.0;
+        off_min = std::min(off_min, ox);
+        off_max = std::max(off_max, ox);
+      }
       const double last = o->u0 + (nu - 1) * o->du;
       const double lo = o->u0 + off_min, hi = last + off_max;
       if (lo < 0.0 && hi > 0.0) {
@@ -388,7 +395,8 @@ extern "C" int mcgpu_fdk_reconstruct(const mcgpu_fdk_options* caller_o, const fl
     // The ramp is a linear convolution evaluated as a circular one of length L.  Only the nu_p detector columns in the middle of
     // a row are ever read, and for those the lag between an output and any of the nu_e data columns is at most M = nu_p + next - 1:
     // with the kernel cut to |lag| <= M, L >= 2 M + 1 keeps every lag distinct (and L >= nu_e holds the row).  L = the smallest
-    // even 2^a 3^b 5^c at or above that -- 7680 instead of 16384 for the reference's half-fan rows with pad = 1.
+    // even 2^a 3^b 5^c at or above that -- 7500 for the reference's half-fan rows with pad = 1 (nu_e = 5545, M = 3696), where
+    // L >= 2 nu_e - 1 rounded up to a power of two would be 16384.
     const int max_lag = nu_p + next - 1;
     int L = std::max(2 * max_lag + 1, nu_e);
     for (;; ++L) {

@@ -123,22 +123,71 @@ def angular_gaps(gantry_deg):
     return np.deg2rad(gaps[inverse] / counts[inverse])
 
 
-def reconstruct(proj, du, dv, u0, v0, sid, sdd, gantry_deg, off_x, off_y, dim, spacing, origin=None, hann=0.0, hann_y=0.0, wpc=None, pad=0.0):
-    """proj [n][nv][nu] line integrals -> volume [nz][ny][nx] (float64).  origin = centre of voxel (0,0,0); None = centred.
-    pad: rtkfdk --pad (truncation correction, see truncation_extension); 0 = rows are zero-padded only."""
-    proj = np.asarray(proj, dtype=np.float64)
-    n, nv, nu = proj.shape
+def fast_length(n: int) -> int:
+    """Smallest 2^a 3^b 5^c >= n (a length numpy's FFT handles quickly)."""
+    m = max(int(n), 1)
+    while True:
+        r = m
+        for f in (2, 3, 5):
+            while r % f == 0:
+                r //= f
+        if r == 1:
+            return m
+        m += 1
+
+
+def ramp_rows(rows, h, first, count, method="direct"):
+    """Rows [..., nu_e] convolved with the kernel h [2 nu_e - 1] (lags -(nu_e - 1) .. nu_e - 1, zero beyond the row): columns
+    first .. first + count of the linear convolution, in float64.  'direct' = np.convolve row by row; 'fft' = the same linear
+    convolution as a circular one of length N >= 2 nu_e - 1 (so that every lag between two columns of a row is distinct modulo N),
+    for rows too long for 'direct' (the reference's half-fan rows with pad = 1: nu_e = 5545)."""
+    rows = np.asarray(rows, dtype=np.float64)
+    nu_e = rows.shape[-1]
+    assert h.size == 2 * nu_e - 1
+    if method == "direct":
+        flat = rows.reshape(-1, nu_e)
+        out = np.stack([np.convolve(row, h, mode="full")[nu_e - 1 + first: nu_e - 1 + first + count] for row in flat])
+        return out.reshape(rows.shape[:-1] + (count,))
+    if method != "fft":
+        raise ValueError(method)
+    N = fast_length(2 * nu_e - 1)
+    hc = np.zeros(N)
+    hc[:nu_e] = h[nu_e - 1:]                 # lag 0 .. nu_e - 1
+    hc[N - (nu_e - 1):] = h[: nu_e - 1]      # lag -(nu_e - 1) .. -1
+    out = np.fft.irfft(np.fft.rfft(rows, N, axis=-1) * np.fft.rfft(hc), N, axis=-1)
+    return out[..., first: first + count]
+
+
+def volume_axes(dim, spacing, origin=None, ix=None, iy=None, iz=None):
+    """Voxel-centre coordinates X, Y, Z of the voxel indices ix, iy, iz (None = all) of a [nz][ny][nx] grid; origin = centre of
+    voxel (0, 0, 0), None = centred on the isocentre."""
     nx, ny, nz = dim
     sx, sy, sz = spacing
     if origin is None:
         origin = (-(nx - 1) / 2 * sx, -(ny - 1) / 2 * sy, -(nz - 1) / 2 * sz)
-    if wpc is not None and len(wpc):
-        acc = np.zeros_like(proj)
-        pw = np.ones_like(proj)
-        for c in wpc:
-            acc += c * pw
-            pw *= proj
-        proj = acc
+    ix, iy, iz = (np.arange(n) if i is None else np.asarray(i, dtype=np.int64) for n, i in zip(dim, (ix, iy, iz)))
+    return origin[0] + sx * ix, origin[1] + sy * iy, origin[2] + sz * iz
+
+
+def _column_geometry(X, Z, gantry_deg, sid, sdd):
+    """Rotated coordinates of the (z, x) columns for one gantry angle: xr, magnification sdd / U and U = sid - zr  ([nz][nx])."""
+    t = np.deg2rad(gantry_deg)
+    c, s = np.cos(t), np.sin(t)
+    xr = X[None, :] * c - Z[:, None] * s
+    zr = X[None, :] * s + Z[:, None] * c
+    U = sid - zr                                   # distance from the source along the central axis
+    return xr, sdd / U, U
+
+
+def reconstruct(proj, du, dv, u0, v0, sid, sdd, gantry_deg, off_x, off_y, dim, spacing, origin=None, hann=0.0, hann_y=0.0, wpc=None, pad=0.0,
+                ramp="direct", ix=None, iy=None, iz=None):
+    """proj [n][nv][nu] line integrals -> volume [nz][ny][nx] (float64).  origin = centre of voxel (0,0,0); None = centred.
+    pad: rtkfdk --pad (truncation correction, see truncation_extension); 0 = rows are zero-padded only.
+    ramp: 'direct' or 'fft', how the row ramp is evaluated (ramp_rows; the same linear convolution in float64).
+    ix, iy, iz: voxel indices along x, y, z (None = all): the result is then [len(iz)][len(iy)][len(ix)], those voxels of the full
+    volume, computed with the same arithmetic."""
+    proj = np.asarray(proj)
+    n, nv, nu = proj.shape
     off_x = np.broadcast_to(np.asarray(off_x, dtype=np.float64), (n,))
     off_y = np.broadcast_to(np.asarray(off_y, dtype=np.float64), (n,))
     # An off-centre detector is first padded with zero columns on its short side until it is symmetric about the central
@@ -150,40 +199,41 @@ def reconstruct(proj, du, dv, u0, v0, sid, sdd, gantry_deg, off_x, off_y, dim, s
     nu_e = nu_p + 2 * nxt  # row length the ramp sees
     h = ramp_kernel(nu_e - 1, hann)
     ky = hann_y_kernel(hann_y)
-    vol = np.zeros((nz, ny, nx), dtype=np.float64)
-    X = origin[0] + sx * np.arange(nx)
-    Y = origin[1] + sy * np.arange(ny)
-    Z = origin[2] + sz * np.arange(nz)
+    X, Y, Z = volume_axes(dim, spacing, origin, ix, iy, iz)
+    vol = np.zeros((Z.size, Y.size, X.size), dtype=np.float64)
     dbeta = angular_gaps(gantry_deg)  # [rad] per projection
     for k in range(n):
+        pk = proj[k].astype(np.float64)
+        if wpc is not None and len(wpc):
+            acc = np.zeros_like(pk)
+            pw = np.ones_like(pk)
+            for c in wpc:
+                acc += c * pw
+                pw *= pk
+            pk = acc
         # physical coordinates of the pixel centres relative to the central ray
         up = u0 + du * np.arange(nu) + off_x[k]
         vp = v0 + dv * np.arange(nv) + off_y[k]
         w_cos = sdd / np.sqrt(sdd * sdd + up[None, :] ** 2 + vp[:, None] ** 2)
         w_dis = displaced_weights(up, sdd)
-        p = np.pad(proj[k] * w_cos * w_dis[None, :], ((0, 0), (pad_l, pad_r)))
+        p = np.pad(pk * w_cos * w_dis[None, :], ((0, 0), (pad_l, pad_r)))
         p, _ = truncation_extension(p, pad)
         # ramp along u (linear convolution, zero padded), scaled to the real detector: 1/du * SDD/SID; only the columns of the
         # (symmetrically padded) detector are kept
-        q = np.stack([np.convolve(row, h, mode="full")[nu_e - 1 + nxt: nu_e - 1 + nxt + nu_p] for row in p])
+        q = ramp_rows(p, h, nxt, nu_p, ramp)
         q *= (sdd / sid) / du
         if ky.size > 1:
             hk = ky.size // 2
             qp = np.pad(q, ((hk, hk), (0, 0)), mode="edge")
             q = sum(ky[j] * qp[j: j + nv] for j in range(ky.size))
-        t = np.deg2rad(gantry_deg[k])
-        c, s = np.cos(t), np.sin(t)
-        xr = X[None, :] * c - Z[:, None] * s          # [nz][nx]
-        zr = X[None, :] * s + Z[:, None] * c
-        U = sid - zr                                   # distance from the source along the central axis
-        mag = sdd / U
+        xr, mag, U = _column_geometry(X, Z, gantry_deg[k], sid, sdd)
         fu = (mag * xr - off_x[k] - u0_p) / du         # fractional column index of the padded rows  [nz][nx]
         wgt = dbeta[k] * (sid / U) ** 2
         iu = np.floor(fu).astype(np.int64)
         au = fu - iu
         ok_u = (iu >= 0) & (iu < nu_p - 1)
         iu_c = np.clip(iu, 0, nu_p - 2)
-        for j in range(ny):
+        for j in range(Y.size):
             fv = (mag * Y[j] - off_y[k] - v0) / dv
             iv = np.floor(fv).astype(np.int64)
             av = fv - iv
@@ -192,6 +242,31 @@ def reconstruct(proj, du, dv, u0, v0, sid, sdd, gantry_deg, off_x, off_y, dim, s
             val = ((1 - av) * ((1 - au) * q[iv_c, iu_c] + au * q[iv_c, iu_c + 1]) + av * ((1 - au) * q[iv_c + 1, iu_c] + au * q[iv_c + 1, iu_c + 1]))
             vol[:, j, :] += np.where(ok, wgt * val, 0.0)
     return vol
+
+
+def ambiguous_voxels(nu, nv, du, dv, u0, v0, sid, sdd, gantry_deg, off_x, off_y, dim, spacing, origin=None, ix=None, iy=None, iz=None, delta=1e-3):
+    """[len(iz)][len(iy)][len(ix)] mask of the voxels for which some projection puts the bilinear sample within `delta` pixel of an
+    inclusion limit of reconstruct: fu of the padded detector at 0 or nu_p - 1, or fv at 0 or nv - 1, with the other coordinate
+    inside its range (or as close to it).  There a float32 back-projector and this float64 one may legitimately disagree about
+    whether a whole contribution dbeta (sid / U)^2 q counts."""
+    n = len(gantry_deg)
+    off_x = np.broadcast_to(np.asarray(off_x, dtype=np.float64), (n,))
+    off_y = np.broadcast_to(np.asarray(off_y, dtype=np.float64), (n,))
+    pad_l, pad_r = symmetric_padding(nu, du, u0, float(off_x.min()), float(off_x.max()))
+    nu_p, u0_p = nu + pad_l + pad_r, u0 - pad_l * du
+    X, Y, Z = volume_axes(dim, spacing, origin, ix, iy, iz)
+    out = np.zeros((Z.size, Y.size, X.size), dtype=bool)
+    for k in range(n):
+        xr, mag, _ = _column_geometry(X, Z, gantry_deg[k], sid, sdd)
+        fu = (mag * xr - off_x[k] - u0_p) / du
+        u_edge = (np.abs(fu) < delta) | (np.abs(fu - (nu_p - 1)) < delta)
+        u_wide = (fu > -delta) & (fu < nu_p - 1 + delta)
+        for j in range(Y.size):
+            fv = (mag * Y[j] - off_y[k] - v0) / dv
+            v_edge = (np.abs(fv) < delta) | (np.abs(fv - (nv - 1)) < delta)
+            v_wide = (fv > -delta) & (fv < nv - 1 + delta)
+            out[:, j, :] |= (u_edge & v_wide) | (v_edge & u_wide)
+    return out
 
 
 def sphere_projections(mu, radius, centre, n, nu, nv, du, dv, u0, v0, sid, sdd, gantry_deg, off_x, off_y):
