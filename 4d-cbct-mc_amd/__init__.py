@@ -5,11 +5,12 @@ The directory name (`4d-cbct-mc_amd`) is not a Python identifier; import it thro
 
 Layout: `csrc/` holds the HIP kernels, the C++ host model and the C ABI (`include/mcgpu_amd.h`);
 the Python modules mirror the reference's host-side interface for this path
-(`cbctmc/mc/simulation.py`, `geometry.py`, `materials.py`, `defaults.py`, `projection.py`).
+(`cbctmc/mc/simulation.py`, `geometry.py`, `materials.py`, `defaults.py`, `projection.py`,
+`cbctmc/registration/correspondence.py`).
 """
-from . import defaults, forward_projection, geometry, materials, phase, reconstruction, respiratory, sharding, simulation, workloads  # noqa: F401
+from . import correspondence, defaults, forward_projection, geometry, materials, phase, reconstruction, respiratory, sharding, simulation, workloads  # noqa: F401
 
-__all__ = ["defaults", "forward_projection", "geometry", "materials", "phase", "reconstruction", "respiratory", "sharding", "simulation", "workloads", "engine"]
+__all__ = ["correspondence", "defaults", "forward_projection", "geometry", "materials", "phase", "reconstruction", "respiratory", "sharding", "simulation", "workloads", "engine"]
 
 
 def __getattr__(name):

@@ -4,6 +4,120 @@
 
 using namespace mcgpu;
 
+namespace {
+
+void drop_correspondence(DeviceModel& D) {
+  if (D.corr_mean) D.mem.free(D.corr_mean);
+  if (D.corr_coef) D.mem.free(D.corr_coef);
+  D.corr_mean = nullptr;
+  D.corr_coef = nullptr;
+  D.corr_k = 0;
+}
+
+void alloc_correspondence(DeviceModel& D, size_t n, int K, bool mean_is_f64, int frame, const double* mean_signal) {
+  D.corr_mean = D.mem.device_bytes(n * (mean_is_f64 ? 8 : 4));
+  D.corr_coef = (double*)D.mem.device_bytes(n * K * 8);
+  D.corr_k = K;
+  D.corr_mean_is_f64 = mean_is_f64 ? 1 : 0;
+  D.corr_frame = frame;
+  for (int k = 0; k < K; ++k) D.corr_mean_signal[k] = mean_signal[k];
+}
+
+// the resident model as the field source of one respiratory state: d = signal - mean_signal, in double on the host
+FieldModelArgs correspondence_args(const DeviceModel& D, const double* signal) {
+  FieldModelArgs m;
+  m.mean = D.corr_mean; m.coef = D.corr_coef; m.k = D.corr_k; m.mean_is_f64 = D.corr_mean_is_f64;
+  for (int k = 0; k < D.corr_k; ++k) m.d[k] = signal[k] - D.corr_mean_signal[k];
+  return m;
+}
+
+// What mcgpu_warp_geometry and mcgpu_warp_geometry_signal share -- everything but where the field comes from: `displacement` (host
+// floats, copied to the device) or, when it is null, the resident correspondence model at `signal` (nothing is copied).
+void warp_resident_geometry(mcgpu_ctx* ctx, const char* who, const float* displacement, const double* signal, int frame, int default_material,
+                            float default_density) {
+  const std::string pre = std::string("!!ERROR!! ") + who + ": ";
+  HostModel& H = ctx->host;
+  DeviceModel& D = ctx->dev;
+  require(D.vol_kind == kVolU8, -5, (pre + "needs a palette volume (<= 256 distinct (material, density) pairs); use mcgpu_set_geometry_arrays").c_str());
+  require(default_material >= 1 && default_material <= kMaxMaterials && D.compact_of[default_material - 1] >= 0, -5,
+          (pre + "the default material has no data file in this simulation").c_str());
+  int default_index = -1;
+  {
+    char t[64];
+    snprintf(t, sizeof t, "%.6f", (double)default_density);  // densities as a voxel file would carry them
+    const float dq = strtof(t, nullptr);
+    for (int e = 0; e < D.palette_size && default_index < 0; ++e) {
+      int mc;
+      memcpy(&mc, &D.palette_host[2 * e + 1], 4);
+      if (mc == D.compact_of[default_material - 1] && D.palette_host[2 * e] == dq) default_index = e;
+    }
+  }
+  require(default_index >= 0, -5, (pre + "the default (material, density) is not in the palette; use mcgpu_set_geometry_arrays").c_str());
+  HIP_TRY(hipSetDevice(D.device_id));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t nvox = H.voxels.count();
+  const size_t nsub = (size_t)D.sub_n[0] * D.sub_n[1] * D.sub_n[2];
+  if (!D.vol_base) {  // first call: what is resident now is the base geometry of every later warp
+    D.vol_base = D.put(std::vector<unsigned char>(D.vol_bytes, 0));
+    HIP_TRY(hipMemcpy(D.vol_base, D.vol, D.vol_bytes, hipMemcpyDeviceToDevice));
+    D.sub_first = D.put(std::vector<unsigned short>(nsub, 0));
+    D.brick_first = D.put(std::vector<unsigned short>((size_t)D.brick_count, 0));
+    D.code_of_dev = D.put(std::vector<unsigned char>(D.code_of, D.code_of + 256));
+    D.rebuild_out = D.put(std::vector<unsigned int>(32, 0u));
+  }
+  GeometryRebuild g;
+  D.warp_field_bytes = 0;
+  D.warp_field_copy_ms = 0.f;
+  if (displacement) {  // the field buffer exists only on this route
+    if (!D.dvf) D.dvf = D.put(std::vector<float>(3 * nvox, 0.f));
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipMemcpy(D.dvf, displacement, 3 * nvox * 4, hipMemcpyHostToDevice));
+    D.warp_field_copy_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    D.warp_field_bytes = 3 * nvox * 4;
+  } else {
+    g.model = correspondence_args(D, signal);
+  }
+  g.nx = H.voxels.n[0]; g.ny = H.voxels.n[1]; g.nz = H.voxels.n[2];
+  g.brick_shift = D.brick_shift;
+  for (int k = 0; k < 3; ++k) { g.bn[k] = D.brick_n[k]; g.sn[k] = D.sub_n[k]; }
+  g.base_idx = D.vol_base; g.dvf = D.dvf; g.default_index = (unsigned char)default_index;
+  g.idx = (unsigned char*)D.vol;
+  g.sub_first = D.sub_first; g.brick_first = D.brick_first;
+  g.sub = D.sub; g.bricks = D.bricks; g.code_of = D.code_of_dev; g.background = D.background;
+  g.rec = D.tile_rec;
+  for (int k = 0; k < 3; ++k) g.rn[k] = D.rec_n[k];
+  g.out = D.rebuild_out;
+  const bool allow_exterior = !D.knobs.no_exterior;
+  if (!D.warp_ev[0]) { D.warp_ev[0] = D.mem.event(hipEventDefault); D.warp_ev[1] = D.mem.event(hipEventDefault); }
+  HIP_TRY(launch_geometry_rebuild(g, frame, allow_exterior, nullptr, D.warp_ev[0], D.warp_ev[1]));
+  unsigned int out[17];
+  HIP_TRY(hipMemcpy(out, D.rebuild_out, sizeof out, hipMemcpyDeviceToHost));  // waits for the kernels
+  HIP_TRY(hipEventElapsedTime(&D.warp_kernel_ms, D.warp_ev[0], D.warp_ev[1]));
+  // largest density per material among the palette entries that occur -> Woodcock majorant (the only table that depends on it)
+  for (int m = 0; m < kMaxMaterials; ++m) H.voxels.density_max[m] = -999.0f;
+  for (int e = 0; e < D.palette_size; ++e)
+    if (out[e >> 5] & (1u << (e & 31))) {
+      int mc;
+      memcpy(&mc, &D.palette_host[2 * e + 1], 4);
+      for (int m = 0; m < kMaxMaterials; ++m)
+        if (D.compact_of[m] == mc) H.voxels.density_max[m] = std::max(H.voxels.density_max[m], D.palette_host[2 * e]);
+    }
+  rebuild_woodcock(H.mat, H.voxels.density_max);
+  refresh_woodcock(H, D);
+  D.sub_mixed = (int)out[16];
+  // The object region (box and, where it pays, elliptic cylinder) and the first-level codes follow from the bricks' classification
+  // exactly as at upload (brick_codes): 64 KB of `brick_first` come down, 16 KB of codes go up.
+  std::vector<unsigned short> bf((size_t)D.brick_count);
+  HIP_TRY(hipMemcpy(bf.data(), D.brick_first, bf.size() * 2, hipMemcpyDeviceToHost));
+  const std::vector<unsigned char> bricks = brick_codes(H, D, bf, true);
+  HIP_TRY(hipMemcpy(D.bricks, bricks.data(), bricks.size(), hipMemcpyHostToDevice));
+  refresh_cold_geometry(D);
+  ctx->host_voxels_stale = true;
+  ctx->table_cache.clear();
+}
+
+}  // namespace
+
 extern "C" {
 
 // ---- 4-D support: one resident context, many (geometry, projection angle) jobs (cbctmc/mc/simulation.py:527-710)
@@ -109,73 +223,110 @@ int mcgpu_set_geometry_arrays(mcgpu_ctx* ctx, const int n[3], const float spacin
 int mcgpu_warp_geometry(mcgpu_ctx* ctx, const float* displacement, int frame, int default_material, float default_density) {
   ABI_BEGIN
   require(ctx && ctx->has_device && displacement && (frame == 0 || frame == 1), -1, "!!ERROR!! mcgpu_warp_geometry: bad argument (the context needs a device)");
-  HostModel& H = ctx->host;
+  warp_resident_geometry(ctx, "mcgpu_warp_geometry", displacement, nullptr, frame, default_material, default_density);
+  return 0;
+  ABI_END
+}
+
+// ---- the correspondence model resident on the device (cbctmc/registration/correspondence.py:149-226; kernels: correspondence.hip)
+int mcgpu_correspondence_clear(mcgpu_ctx* ctx) {
+  ABI_BEGIN
+  require(ctx && ctx->has_device, -1, "!!ERROR!! mcgpu_correspondence_clear: bad argument (the context needs a device)");
+  HIP_TRY(hipSetDevice(ctx->dev.device_id));
+  HIP_TRY(hipDeviceSynchronize());
+  drop_correspondence(ctx->dev);
+  return 0;
+  ABI_END
+}
+
+int mcgpu_correspondence_set(mcgpu_ctx* ctx, const void* mean, int mean_is_f64, const double* coefficients, const double* mean_signal, int K, int frame) {
+  ABI_BEGIN
+  require(ctx && ctx->has_device && mean && coefficients && mean_signal && K >= 1 && (frame == 0 || frame == 1), -1,
+          "!!ERROR!! mcgpu_correspondence_set: bad argument (the context needs a device)");
   DeviceModel& D = ctx->dev;
-  require(D.vol_kind == kVolU8, -5, "!!ERROR!! mcgpu_warp_geometry: needs a palette volume (<= 256 distinct (material, density) pairs); use mcgpu_set_geometry_arrays");
-  require(default_material >= 1 && default_material <= kMaxMaterials && D.compact_of[default_material - 1] >= 0, -5,
-          "!!ERROR!! mcgpu_warp_geometry: the default material has no data file in this simulation");
-  int default_index = -1;
-  {
-    char t[64];
-    snprintf(t, sizeof t, "%.6f", (double)default_density);  // densities as a voxel file would carry them
-    const float dq = strtof(t, nullptr);
-    for (int e = 0; e < D.palette_size && default_index < 0; ++e) {
-      int mc;
-      memcpy(&mc, &D.palette_host[2 * e + 1], 4);
-      if (mc == D.compact_of[default_material - 1] && D.palette_host[2 * e] == dq) default_index = e;
-    }
-  }
-  require(default_index >= 0, -5, "!!ERROR!! mcgpu_warp_geometry: the default (material, density) is not in the palette; use mcgpu_set_geometry_arrays");
   HIP_TRY(hipSetDevice(D.device_id));
   HIP_TRY(hipDeviceSynchronize());
-  const size_t nvox = H.voxels.count();
-  const size_t nsub = (size_t)D.sub_n[0] * D.sub_n[1] * D.sub_n[2];
-  if (!D.vol_base) {  // first call: what is resident now is the base geometry of every later warp
-    D.vol_base = D.put(std::vector<unsigned char>(D.vol_bytes, 0));
-    HIP_TRY(hipMemcpy(D.vol_base, D.vol, D.vol_bytes, hipMemcpyDeviceToDevice));
-    D.sub_first = D.put(std::vector<unsigned short>(nsub, 0));
-    D.brick_first = D.put(std::vector<unsigned short>((size_t)D.brick_count, 0));
-    D.code_of_dev = D.put(std::vector<unsigned char>(D.code_of, D.code_of + 256));
-    D.rebuild_out = D.put(std::vector<unsigned int>(32, 0u));
-    D.dvf = D.put(std::vector<float>(3 * nvox, 0.f));
+  drop_correspondence(D);  // whatever follows, the previous model is gone: after a failure none is resident
+  require(K <= kFieldModelMaxK, -5, "!!ERROR!! mcgpu_correspondence_set: more than 4 signal dimensions: predict on the host and use mcgpu_warp_geometry");
+  const size_t n = 3 * ctx->host.voxels.count();
+  try {
+    alloc_correspondence(D, n, K, mean_is_f64 != 0, frame, mean_signal);
+    HIP_TRY(hipMemcpy(D.corr_mean, mean, n * (mean_is_f64 ? 8 : 4), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(D.corr_coef, coefficients, n * K * 8, hipMemcpyHostToDevice));
+  } catch (...) {
+    drop_correspondence(D);
+    throw;
   }
-  HIP_TRY(hipMemcpy(D.dvf, displacement, 3 * nvox * 4, hipMemcpyHostToDevice));
-  GeometryRebuild g;
-  g.nx = H.voxels.n[0]; g.ny = H.voxels.n[1]; g.nz = H.voxels.n[2];
-  g.brick_shift = D.brick_shift;
-  for (int k = 0; k < 3; ++k) { g.bn[k] = D.brick_n[k]; g.sn[k] = D.sub_n[k]; }
-  g.base_idx = D.vol_base; g.dvf = D.dvf; g.default_index = (unsigned char)default_index;
-  g.idx = (unsigned char*)D.vol;
-  g.sub_first = D.sub_first; g.brick_first = D.brick_first;
-  g.sub = D.sub; g.bricks = D.bricks; g.code_of = D.code_of_dev; g.background = D.background;
-  g.rec = D.tile_rec;
-  for (int k = 0; k < 3; ++k) g.rn[k] = D.rec_n[k];
-  g.out = D.rebuild_out;
-  const bool allow_exterior = !D.knobs.no_exterior;
-  HIP_TRY(launch_geometry_rebuild(g, frame, allow_exterior, nullptr));
-  unsigned int out[17];
-  HIP_TRY(hipMemcpy(out, D.rebuild_out, sizeof out, hipMemcpyDeviceToHost));  // waits for the kernels
-  // largest density per material among the palette entries that occur -> Woodcock majorant (the only table that depends on it)
-  for (int m = 0; m < kMaxMaterials; ++m) H.voxels.density_max[m] = -999.0f;
-  for (int e = 0; e < D.palette_size; ++e)
-    if (out[e >> 5] & (1u << (e & 31))) {
-      int mc;
-      memcpy(&mc, &D.palette_host[2 * e + 1], 4);
-      for (int m = 0; m < kMaxMaterials; ++m)
-        if (D.compact_of[m] == mc) H.voxels.density_max[m] = std::max(H.voxels.density_max[m], D.palette_host[2 * e]);
+  return 0;
+  ABI_END
+}
+
+int mcgpu_correspondence_fit(mcgpu_ctx* ctx, const float* const* fields, int T, const double* pinv, const double* mean_signal, int K, int frame,
+                             float* mean_out, double* coefficients_out) {
+  ABI_BEGIN
+  require(ctx && ctx->has_device && fields && pinv && mean_signal && T >= 1 && K >= 1 && (frame == 0 || frame == 1), -1,
+          "!!ERROR!! mcgpu_correspondence_fit: bad argument (the context needs a device)");
+  for (int t = 0; t < T; ++t) require(fields[t] != nullptr, -1, "!!ERROR!! mcgpu_correspondence_fit: null field");
+  DeviceModel& D = ctx->dev;
+  HIP_TRY(hipSetDevice(D.device_id));
+  HIP_TRY(hipDeviceSynchronize());
+  drop_correspondence(D);
+  require(K <= kFieldModelMaxK && T <= kFitMaxTimesteps, -5,
+          "!!ERROR!! mcgpu_correspondence_fit: more than 4 signal dimensions or more than 64 time steps: fit on the host");
+  const size_t n = 3 * ctx->host.voxels.count();
+  // the T fields pass through the device in slabs of elements, [T][slab], so that the inputs take a bounded amount of memory
+  const size_t slab = std::min<size_t>(n, (size_t)std::max(1, knob_int("MCGPU_CORRESPONDENCE_SLAB", 1 << 22)));
+  float* stage = nullptr;
+  try {
+    alloc_correspondence(D, n, K, false, frame, mean_signal);
+    stage = (float*)D.mem.device_bytes((size_t)T * slab * 4);
+    for (size_t e0 = 0; e0 < n; e0 += slab) {
+      const size_t m = std::min(slab, n - e0);
+      for (int t = 0; t < T; ++t) HIP_TRY(hipMemcpy(stage + (size_t)t * m, fields[t] + e0, m * 4, hipMemcpyHostToDevice));
+      HIP_TRY(launch_fit_model(stage, m, T, pinv, K, (float*)D.corr_mean + e0, D.corr_coef + e0 * K, nullptr));
+      HIP_TRY(hipDeviceSynchronize());  // the next slab overwrites the stage
     }
-  rebuild_woodcock(H.mat, H.voxels.density_max);
-  refresh_woodcock(H, D);
-  D.sub_mixed = (int)out[16];
-  // The object region (box and, where it pays, elliptic cylinder) and the first-level codes follow from the bricks' classification
-  // exactly as at upload (brick_codes): 64 KB of `brick_first` come down, 16 KB of codes go up.
-  std::vector<unsigned short> bf((size_t)D.brick_count);
-  HIP_TRY(hipMemcpy(bf.data(), D.brick_first, bf.size() * 2, hipMemcpyDeviceToHost));
-  const std::vector<unsigned char> bricks = brick_codes(H, D, bf, true);
-  HIP_TRY(hipMemcpy(D.bricks, bricks.data(), bricks.size(), hipMemcpyHostToDevice));
-  refresh_cold_geometry(D);
-  ctx->host_voxels_stale = true;
-  ctx->table_cache.clear();
+    D.mem.free(stage);
+    stage = nullptr;
+    if (mean_out) HIP_TRY(hipMemcpy(mean_out, D.corr_mean, n * 4, hipMemcpyDeviceToHost));
+    if (coefficients_out) HIP_TRY(hipMemcpy(coefficients_out, D.corr_coef, n * K * 8, hipMemcpyDeviceToHost));
+  } catch (...) {
+    if (stage) D.mem.free(stage);
+    drop_correspondence(D);
+    throw;
+  }
+  return 0;
+  ABI_END
+}
+
+int mcgpu_correspondence_predict(mcgpu_ctx* ctx, const double* signal, int K, float* field_out) {
+  ABI_BEGIN
+  require(ctx && ctx->has_device && signal && field_out && K >= 1, -1, "!!ERROR!! mcgpu_correspondence_predict: bad argument (the context needs a device)");
+  DeviceModel& D = ctx->dev;
+  require(D.corr_coef != nullptr, -5, "!!ERROR!! mcgpu_correspondence_predict: no correspondence model is resident (mcgpu_correspondence_set)");
+  require(K == D.corr_k, -1, "!!ERROR!! mcgpu_correspondence_predict: the signal does not have the model's number of dimensions");
+  HIP_TRY(hipSetDevice(D.device_id));
+  const size_t n = 3 * ctx->host.voxels.count();
+  float* out = (float*)D.mem.device_bytes(n * 4);
+  try {
+    HIP_TRY(launch_predict_field(correspondence_args(D, signal), n, out, nullptr));
+    HIP_TRY(hipMemcpy(field_out, out, n * 4, hipMemcpyDeviceToHost));  // waits for the kernel
+  } catch (...) {
+    D.mem.free(out);
+    throw;
+  }
+  D.mem.free(out);
+  return 0;
+  ABI_END
+}
+
+int mcgpu_warp_geometry_signal(mcgpu_ctx* ctx, const double* signal, int K, int default_material, float default_density) {
+  ABI_BEGIN
+  require(ctx && ctx->has_device && signal && K >= 1, -1, "!!ERROR!! mcgpu_warp_geometry_signal: bad argument (the context needs a device)");
+  DeviceModel& D = ctx->dev;
+  require(D.corr_coef != nullptr, -5, "!!ERROR!! mcgpu_warp_geometry_signal: no correspondence model is resident (mcgpu_correspondence_set)");
+  require(K == D.corr_k, -1, "!!ERROR!! mcgpu_warp_geometry_signal: the signal does not have the model's number of dimensions");
+  warp_resident_geometry(ctx, "mcgpu_warp_geometry_signal", nullptr, signal, D.corr_frame, default_material, default_density);
   return 0;
   ABI_END
 }

@@ -105,7 +105,17 @@ struct DeviceModel {
   unsigned short *sub_first = nullptr, *brick_first = nullptr;
   unsigned char* code_of_dev = nullptr;
   unsigned int* rebuild_out = nullptr;
-  float* dvf = nullptr;
+  float* dvf = nullptr;            // the field of mcgpu_warp_geometry (allocated on its first call; the model route has none)
+  hipEvent_t warp_ev[2] = {nullptr, nullptr};  // around the warp kernel of the last geometry warp
+  float warp_kernel_ms = 0.f;      // its time (config key "warp_kernel_ms")
+  float warp_field_copy_ms = 0.f;  // host time of the field's copy to the device in the last geometry warp (0: no field was copied)
+  size_t warp_field_bytes = 0;     // field bytes the last geometry warp copied from the host (0: evaluated from the resident model)
+  // the correspondence model resident on the device (mcgpu_correspondence_set / _fit; geometry_device.hpp: FieldModelArgs):
+  // mean [3N] float or double, coefficients double[3N][corr_k], in the layout of frame `corr_frame`; null: none
+  void* corr_mean = nullptr;
+  double* corr_coef = nullptr;
+  int corr_k = 0, corr_mean_is_f64 = 0, corr_frame = 0;
+  double corr_mean_signal[4] = {0, 0, 0, 0};
   std::vector<float> palette_host;  // {density, bits(compact material)} pairs
   unsigned char code_of[256];
   int background = 0;

@@ -7,7 +7,8 @@
 // nearest-neighbour warp only moves voxels around: the set of (material, density) pairs is the base geometry's (plus the
 // default, air), so the palette stays and what is warped is the 1-byte palette index volume.  Everything derived from the
 // voxels is then recomputed here:
-//   warp_index_kernel      out[x] = base[nearest(x + u(x))] or the default's palette index   (torch's arithmetic, warp.hip)
+//   warp_index_kernel      out[x] = base[nearest(x + u(x))] or the default's palette index   (torch's arithmetic, warp.hip; the
+//                          kernel lives in field_source.hpp: u from a field in memory here, from the correspondence model in correspondence.hip)
 //   classify_sub_kernel    per sub-brick of 4^3 voxels: its palette entry or "mixed"; which palette entries occur at all
 //   classify_brick_kernel  per brick of (2^k)^3 voxels: the same from its sub-bricks; bounding box of the non-background bricks
 //   pack_codes_kernel      the 4-bit code tables of both levels (EXTERIOR outside the bounding box)
@@ -18,55 +19,13 @@
 #include <cstdint>
 
 #include "device_model.hpp"
+#include "field_source.hpp"
 #include "geometry_device.hpp"
 
 namespace mcgpu {
 namespace {
 
 constexpr unsigned short kMixed = 0x100;
-
-// identity + displacement -> normalised -> grid_sample(align_corners=True) un-normalisation -> nearbyint, in float32 like
-// torch (see warp.hip; known answers tests/golden/warp_kat.npz)
-__device__ __forceinline__ float nearest_sample(float loc, int n) {
-  const float t = 2.0f * (__fdiv_rn(loc, (float)(n - 1)) - 0.5f);
-  return rintf(((t + 1.0f) / 2.0f) * (float)(n - 1));
-}
-
-// FRAME 0: the field is given in the engine's frame, [3][nz][ny][nx], components (x, y, z).
-// FRAME 1: the field is given in the frame of the reference's MCGeometry arrays, [3][gx][gy][gz] with the engine volume =
-//          rot90(k=3) of them in the x/y plane (create_mcgpu_geometry, cbctmc/mc/geometry.py:589-599): engine voxel
-//          (x, y, z) is geometry voxel (gx, gy, gz) = (ny - 1 - y, x, z).  The warp is evaluated in the geometry's frame,
-//          where the reference evaluates it (ties and border samples do not survive a mirrored axis), and only the
-//          result is addressed in the engine's layout.
-// Source and destination are TILED index volumes (device_model.hpp: tiled_voxel).  One thread per voxel of the padded
-// grid, in tile order: a wave writes one whole 64-byte tile (the padding voxels of edge tiles get the default).
-template <int FRAME>
-__global__ __launch_bounds__(256) void warp_index_kernel(int nx, int ny, int nz, int snx, int sny, int snz, const unsigned char* __restrict__ base,
-                                                         const float* __restrict__ dvf, unsigned char default_index, unsigned char* __restrict__ out) {
-  const size_t nvox = (size_t)nx * ny * nz, ncell = (size_t)snx * sny * snz * 64;
-  const unsigned int snxy = (unsigned int)(snx * sny);
-  for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < ncell; c += (size_t)gridDim.x * blockDim.x) {
-    const size_t t = c >> 6;
-    const int x = ((int)(t % snx) << 2) | (int)(c & 3), y = ((int)((t / snx) % sny) << 2) | (int)((c >> 2) & 3), z = ((int)(t / snxy) << 2) | (int)((c >> 4) & 3);
-    unsigned char v = default_index;
-    if (x < nx && y < ny && z < nz) {
-      if (FRAME == 0) {
-        const size_t i = (size_t)x + (size_t)y * nx + (size_t)z * nx * ny;
-        const float sx = nearest_sample((float)x + dvf[i], nx), sy = nearest_sample((float)y + dvf[nvox + i], ny), sz = nearest_sample((float)z + dvf[2 * nvox + i], nz);
-        if (sx >= 0.f && sx <= (float)(nx - 1) && sy >= 0.f && sy <= (float)(ny - 1) && sz >= 0.f && sz <= (float)(nz - 1))
-          v = base[tiled_voxel((unsigned int)(int)sx, (unsigned int)(int)sy, (unsigned int)(int)sz, (unsigned int)snx, snxy)];
-      } else {
-        const int g0 = ny, g1 = nx, g2 = nz;  // extents of the geometry arrays
-        const int gx = ny - 1 - y, gy = x, gz = z;
-        const size_t f = ((size_t)gx * g1 + gy) * g2 + gz;
-        const float sx = nearest_sample((float)gx + dvf[f], g0), sy = nearest_sample((float)gy + dvf[nvox + f], g1), sz = nearest_sample((float)gz + dvf[2 * nvox + f], g2);
-        if (sx >= 0.f && sx <= (float)(g0 - 1) && sy >= 0.f && sy <= (float)(g1 - 1) && sz >= 0.f && sz <= (float)(g2 - 1))
-          v = base[tiled_voxel((unsigned int)(int)sy, (unsigned int)(ny - 1 - (int)sx), (unsigned int)(int)sz, (unsigned int)snx, snxy)];
-      }
-    }
-    out[c] = v;
-  }
-}
 
 // one thread per sub-brick of 4^3 voxels
 __global__ __launch_bounds__(256) void classify_sub_kernel(GeometryRebuild g) {
@@ -183,13 +142,21 @@ __global__ void init_out_kernel(unsigned int* out) {
 
 }  // namespace
 
-hipError_t launch_geometry_rebuild(const GeometryRebuild& g, int warp_frame, bool allow_exterior, hipStream_t stream) {
-  const size_t ncell = (size_t)g.sn[0] * g.sn[1] * g.sn[2] * 64;
-  const unsigned wblocks = (unsigned)std::min<size_t>((ncell + 255) / 256, 256u * 64u);
-  if (warp_frame == 0)
-    hipLaunchKernelGGL(warp_index_kernel<0>, dim3(wblocks), dim3(256), 0, stream, g.nx, g.ny, g.nz, g.sn[0], g.sn[1], g.sn[2], g.base_idx, g.dvf, g.default_index, g.idx);
-  else if (warp_frame == 1)
-    hipLaunchKernelGGL(warp_index_kernel<1>, dim3(wblocks), dim3(256), 0, stream, g.nx, g.ny, g.nz, g.sn[0], g.sn[1], g.sn[2], g.base_idx, g.dvf, g.default_index, g.idx);
+hipError_t launch_geometry_rebuild(const GeometryRebuild& g, int warp_frame, bool allow_exterior, hipStream_t stream, hipEvent_t warp_begin, hipEvent_t warp_end) {
+  if (warp_begin) (void)hipEventRecord(warp_begin, stream);
+  if (warp_frame >= 0 && g.model.coef) {  // the field of the resident correspondence model, evaluated in the warp (correspondence.hip)
+    const hipError_t e = launch_warp_index_model(g, warp_frame, stream);
+    if (e != hipSuccess) return e;
+  } else if (warp_frame >= 0) {
+    const unsigned wblocks = warp_index_blocks((size_t)g.sn[0] * g.sn[1] * g.sn[2] * 64);
+    if (!wblocks) return hipErrorInvalidValue;
+    const FieldInMemory field{g.dvf, (size_t)g.nx * g.ny * g.nz};
+    if (warp_frame == 0)
+      hipLaunchKernelGGL((warp_index_kernel<0, FieldInMemory>), dim3(wblocks), dim3(256), 0, stream, g.nx, g.ny, g.nz, g.sn[0], g.sn[1], g.sn[2], g.base_idx, field, g.default_index, g.idx);
+    else if (warp_frame == 1)
+      hipLaunchKernelGGL((warp_index_kernel<1, FieldInMemory>), dim3(wblocks), dim3(256), 0, stream, g.nx, g.ny, g.nz, g.sn[0], g.sn[1], g.sn[2], g.base_idx, field, g.default_index, g.idx);
+  }
+  if (warp_end) (void)hipEventRecord(warp_end, stream);
   hipLaunchKernelGGL(init_out_kernel, dim3(1), dim3(32), 0, stream, g.out);
   const int nsub = g.sn[0] * g.sn[1] * g.sn[2], nb = g.bn[0] * g.bn[1] * g.bn[2];
   hipLaunchKernelGGL(classify_sub_kernel, dim3((nsub + 255) / 256), dim3(256), 0, stream, g);

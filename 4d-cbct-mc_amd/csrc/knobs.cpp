@@ -51,6 +51,7 @@ const KnobSpec kKnobs[] = {
     {"MCGPU_ASCII_WRITERS", 'i', 'H', "slots", "ASCII files in flight (1..MCGPU_ASCII_SLOTS)"},
     {"MCGPU_PINNED_COHERENT", 'b', 'H', "off", "coherent pinned host buffers for the downloads (default: non-coherent)"},
     {"MCGPU_FDK_DIRECT_RAMP", 'b', 'H', "off", "FDK ramp filter as a direct LDS convolution instead of hipFFT"},
+    {"MCGPU_CORRESPONDENCE_SLAB", 'i', 'H', "4194304", "device fit of a correspondence model: field elements per slab (T slabs of 4 bytes per element are staged on the device at a time)"},
     {"MCGPU_REDUCE", 's', 'H', "auto", "multi-device tally sum: `rccl` = one ncclReduce per projection; default: tally exchange, else projection sharding"},
     {"MCGPU_RCCL_LIBRARY", 's', 'H', "librccl.so.1", "RCCL library the reduction route opens with dlopen"},
     {"MCGPU_EXCHANGE_POLICY", 'i', 'H', "1", "tally exchange: 1 the owner of a projection rotates over the ranks, 0 rank 0 owns every projection"},

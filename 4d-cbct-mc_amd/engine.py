@@ -29,6 +29,7 @@ ABI_SYMBOLS = (
     "mcgpu_finalize_projection", "mcgpu_finalize_projection_host", "mcgpu_stack_create", "mcgpu_stack_append", "mcgpu_stack_write_slice", "mcgpu_stack_finish",
     "mcgpu_stack_read", "mcgpu_normalize_stack", "mcgpu_run_scan", "mcgpu_run_scan_multi", "mcgpu_set_projection_angles", "mcgpu_set_geometry_arrays",
     "mcgpu_warp_volume", "mcgpu_warp_geometry",
+    "mcgpu_correspondence_set", "mcgpu_correspondence_fit", "mcgpu_correspondence_predict", "mcgpu_warp_geometry_signal", "mcgpu_correspondence_clear",
     "mcgpu_write_voxel_file", "mcgpu_write_voxel_binary", "mcgpu_kat_rng", "mcgpu_kat_rng_streams", "mcgpu_microbench", "mcgpu_kat_math", "mcgpu_kat_expf", "mcgpu_kat_f32", "mcgpu_kat_fast64", "mcgpu_kat_tile_records", "mcgpu_fdk_reconstruct", "mcgpu_forward_project", "mcgpu_forward_project_context", "mcgpu_rooster4d_reconstruct", "mcgpu_rooster4d_stage", "mcgpu_set_fast_schedule", "mcgpu_reload_env_knobs",
     "mcgpu_exchange_shared_bytes", "mcgpu_exchange_card_bytes", "mcgpu_exchange_create", "mcgpu_exchange_card", "mcgpu_exchange_connect",
     "mcgpu_exchange_connect_local", "mcgpu_exchange_probe", "mcgpu_exchange_owner", "mcgpu_exchange_begin", "mcgpu_exchange_submit", "mcgpu_exchange_collect",
@@ -123,6 +124,11 @@ def load_library(path: Optional[os.PathLike] = None):
     lib.mcgpu_set_geometry_arrays.argtypes = [vp, C.POINTER(ci), C.POINTER(C.c_float), vp, vp]
     lib.mcgpu_warp_volume.argtypes = [vp, C.POINTER(ci), vp, vp, vp, ci, C.c_float, vp, vp]
     lib.mcgpu_warp_geometry.argtypes = [vp, vp, ci, ci, C.c_float]
+    lib.mcgpu_correspondence_set.argtypes = [vp, vp, ci, vp, vp, ci, ci]
+    lib.mcgpu_correspondence_fit.argtypes = [vp, C.POINTER(vp), ci, vp, vp, ci, ci, vp, vp]
+    lib.mcgpu_correspondence_predict.argtypes = [vp, vp, ci, vp]
+    lib.mcgpu_warp_geometry_signal.argtypes = [vp, vp, ci, ci, C.c_float]
+    lib.mcgpu_correspondence_clear.argtypes = [vp]
     lib.mcgpu_stack_finish.argtypes = [vp, ci, C.POINTER(C.c_float)]
     lib.mcgpu_stack_read.argtypes = [cp, C.POINTER(ci), vp, C.c_size_t]
     lib.mcgpu_normalize_stack.argtypes = [cp, cp, C.c_double, C.c_double, cp, C.c_double, C.c_double]
@@ -365,6 +371,7 @@ class Context:
         self.h = h
         self.device = device
         self.input_path = str(input_path)
+        self._correspondence_model = None  # the CorrespondenceModel resident on this context's device (set_correspondence_model)
 
     def clone(self, device: int = 0) -> "Context":
         """The same simulation on another device without parsing the input files again (mcgpu_clone)."""
@@ -524,6 +531,7 @@ class Context:
         m = np.ascontiguousarray(material_zyx, dtype=np.uint8)
         d = np.ascontiguousarray(density_zyx, dtype=np.float32)
         assert m.size == d.size == int(n[0]) * int(n[1]) * int(n[2])
+        self._correspondence_model = None  # the device model is built anew: a resident correspondence model goes with the old one
         _check(self.lib.mcgpu_set_geometry_arrays(self.h, (C.c_int * 3)(*map(int, n)), (C.c_float * 3)(*map(float, spacing_cm)),
                                                   m.ctypes.data, d.ctypes.data))
 
@@ -544,6 +552,71 @@ class Context:
         if u.shape != want:
             raise ValueError(f"displacement of shape {u.shape}, expected {want} for frame '{frame}'")
         _check(self.lib.mcgpu_warp_geometry(self.h, u.ctypes.data, 1 if frame == "geometry" else 0, int(default_material), float(default_density)))
+
+    # -- the correspondence model resident on the device (correspondence.py: CorrespondenceModel; mcgpu_correspondence_*)
+    def _field_shape(self, frame: str):
+        nx, ny, nz = self.geti("num_voxels_x"), self.geti("num_voxels_y"), self.geti("num_voxels_z")
+        return (ny, nx, nz) if frame == "geometry" else (nz, ny, nx)
+
+    def set_correspondence_model(self, model, frame: str = "geometry"):
+        """Upload a fitted `CorrespondenceModel` (mean float32 or float64, coefficients float64 [3N, K]); it stays resident until
+        `clear_correspondence_model`, another upload, `set_geometry` or `close`.  frame as for `warp_geometry`: the model's
+        `spatial_shape` is (gx, gy, gz) for "geometry", (nz, ny, nx) for "engine".  EngineError(-5) when K > 4."""
+        if not model.is_fitted:
+            raise RuntimeError("Correspondence model is not fitted")
+        want = self._field_shape(frame)
+        if tuple(model.spatial_shape) != want:
+            raise ValueError(f"model of spatial shape {tuple(model.spatial_shape)}, expected {want} for frame '{frame}'")
+        n, k = 3 * int(np.prod(want)), int(model.signal_n_dims)
+        mean = np.asarray(model.mean_vector_field)
+        mean = np.ascontiguousarray(mean, dtype=np.float32 if mean.dtype == np.float32 else np.float64).reshape(-1)
+        coef = np.ascontiguousarray(model.coefficients, dtype=np.float64)
+        ms = np.ascontiguousarray(model.mean_signal, dtype=np.float64).reshape(-1)
+        if mean.size != n or coef.shape != (n, k) or ms.size != k:
+            raise ValueError(f"model arrays of shapes {mean.shape}, {coef.shape}, {ms.shape} do not describe {n} elements and {k} signal dimensions")
+        self._correspondence_model = None
+        _check(self.lib.mcgpu_correspondence_set(self.h, mean.ctypes.data, int(mean.dtype == np.float64), coef.ctypes.data, ms.ctypes.data, k,
+                                                 1 if frame == "geometry" else 0))
+        self._correspondence_model = model
+
+    def fit_correspondence_model(self, fields, pinv, mean_signal, frame: str = "geometry"):
+        """The large part of `CorrespondenceModel.fit` on the device: `fields` [T, 3, *shape] float32 (or T such arrays), `pinv`
+        [T, K] the pseudo-inverse of the centred signals -> (mean float32 [3N], coefficients float64 [3N, K]); the model stays
+        resident.  EngineError(-5) when K > 4 or T > 64: fit on the host."""
+        want = (3,) + self._field_shape(frame)
+        fs = [np.ascontiguousarray(f, dtype=np.float32) for f in fields]
+        for f in fs:
+            if f.shape != want:
+                raise ValueError(f"field of shape {f.shape}, expected {want} for frame '{frame}'")
+        p = np.ascontiguousarray(pinv, dtype=np.float64)
+        ms = np.ascontiguousarray(mean_signal, dtype=np.float64).reshape(-1)
+        if p.shape != (len(fs), ms.size):
+            raise ValueError(f"pseudo-inverse of shape {p.shape}, expected {(len(fs), ms.size)}")
+        n = int(np.prod(want))
+        mean, coef = np.empty(n, dtype=np.float32), np.empty((n, ms.size), dtype=np.float64)
+        ptrs = (C.c_void_p * len(fs))(*[f.ctypes.data for f in fs])
+        self._correspondence_model = None
+        _check(self.lib.mcgpu_correspondence_fit(self.h, ptrs, len(fs), p.ctypes.data, ms.ctypes.data, int(ms.size), 1 if frame == "geometry" else 0,
+                                                 mean.ctypes.data, coef.ctypes.data))
+        return mean, coef
+
+    def predict_field(self, signal, frame: str = "geometry") -> np.ndarray:
+        """float32 [3, *shape]: the field of `signal` evaluated from the resident model (`CorrespondenceModel.predict_field32`);
+        `frame` names the frame the model was set with (it only shapes the result)."""
+        s = np.ascontiguousarray(signal, dtype=np.float64).reshape(-1)
+        out = np.empty((3,) + self._field_shape(frame), dtype=np.float32)
+        _check(self.lib.mcgpu_correspondence_predict(self.h, s.ctypes.data, int(s.size), out.ctypes.data))
+        return out
+
+    def warp_geometry_by_signal(self, signal, default_material: int = 1, default_density: float = 0.0013):
+        """`warp_geometry(model.predict_field32(signal))` without the field: evaluated from the resident model inside the warp
+        kernel (mcgpu_warp_geometry_signal).  EngineError(-5): no model resident or not a palette volume -- take the host route."""
+        s = np.ascontiguousarray(signal, dtype=np.float64).reshape(-1)
+        _check(self.lib.mcgpu_warp_geometry_signal(self.h, s.ctypes.data, int(s.size), int(default_material), float(default_density)))
+
+    def clear_correspondence_model(self):
+        self._correspondence_model = None
+        _check(self.lib.mcgpu_correspondence_clear(self.h))
 
     def project_forward(self, angles_deg, detector_size=(1024, 768), detector_pixel_spacing=(0.388, 0.388), detector_offset_x=None,
                         detector_offset_y=0.0, source_to_isocenter=None, source_to_detector=None, spacing_iec=None, origin_iec=None):

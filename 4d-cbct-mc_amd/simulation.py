@@ -286,8 +286,9 @@ class MCSimulation4D:
     state the geometry is warped on the GPU, handed over as arrays, the state's angles are set, and the scan
     pipeline writes its projections straight into their slices of the three shared stacks.
 
-    `correspondence_model` is anything with `predict(np.array([signal, dt_signal])) -> displacement field
-    [3, x, y, z]` in voxels (the reference's CorrespondenceModel.predict, sim.py:477)."""
+    `correspondence_model` is a `correspondence.CorrespondenceModel` (kept resident on the device: a state change sends the
+    two signal values) or anything else with `predict(np.array([signal, dt_signal])) -> displacement field [3, x, y, z]` in
+    voxels (the reference's CorrespondenceModel.predict, sim.py:477; the field is predicted on the host and copied)."""
 
     def __init__(self, correspondence_model, geometry, material_filepaths, xray_spectrum_filepath, n_histories=DEFAULTS.n_histories,
                  n_projections=DEFAULTS.n_projections, frame_rate=15.0, angle_between_projections=DEFAULTS.angle_between_projections,
@@ -318,11 +319,24 @@ class MCSimulation4D:
         return MCGeometry(np.transpose(m, (2, 1, 0)), np.transpose(d, (2, 1, 0)), self.geometry.image_spacing)
 
     def apply_state(self, ctx, engine, signal: float, dt_signal: float):
-        """Geometry of one respiratory state on the resident context: warped on the device from the predicted field
-        (mcgpu_warp_geometry: nothing but the field crosses PCIe); volumes that are not palette volumes take the route
-        through host arrays (warp_volume + set_geometry)."""
+        """Geometry of one respiratory state on the resident context.  A `CorrespondenceModel` is uploaded once per context and
+        the field is evaluated inside the warp kernel (mcgpu_warp_geometry_signal: two doubles cross PCIe); where the engine
+        answers -5 (more than 4 signal dimensions, no palette volume) and for any other object with `predict`, the field is
+        predicted on the host and warped on the device (mcgpu_warp_geometry: nothing but the field crosses PCIe); volumes that
+        are not palette volumes take the route through host arrays (warp_volume + set_geometry)."""
         import numpy as np
-        field = np.asarray(self.correspondence_model.predict(np.array([signal, dt_signal])), dtype=np.float32)
+        from .correspondence import CorrespondenceModel
+        model = self.correspondence_model
+        if isinstance(model, CorrespondenceModel):
+            try:
+                if getattr(ctx, "_correspondence_model", None) is not model:
+                    ctx.set_correspondence_model(model, frame="geometry")
+                ctx.warp_geometry_by_signal(np.array([signal, dt_signal]))
+                return
+            except engine.EngineError as e:
+                if e.code != -5:
+                    raise
+        field = np.asarray(model.predict(np.array([signal, dt_signal])), dtype=np.float32)
         if field.ndim == 5:
             field = field[0]
         try:

@@ -310,6 +310,36 @@ void mcgpu_rccl_destroy(mcgpu_rccl *r);
  * Dose tallies keep accumulating across such changes. */
 int mcgpu_warp_geometry(mcgpu_ctx *ctx, const float *displacement, int frame, int default_material, float default_density);
 
+/* ---- The correspondence model resident on the device: the reference's CorrespondenceModel (cbctmc/registration/correspondence.py:
+ * 29-226), which turns a breathing signal s[K] into a displacement field, field = mean + coefficients (s - mean_signal), 3N
+ * elements for N voxels.  The reference predicts in numpy per respiratory state and warps the result; with the model here a
+ * state change sends K doubles and the field is evaluated inside the warp kernel (csrc/correspondence.hip), never stored.
+ * Layouts: mean [3N] float or double (mean_is_f64), coefficients double[3N][K] as the reference keeps them, element e = c N + f,
+ * c the component and f the voxel of frame 0 ([nz][ny][nx]) or frame 1 ([gx][gy][gz]) as for mcgpu_warp_geometry; N is the
+ * context's voxel count.  The field of a signal is float(double(mean[e]) + (coefficients[e][0] d[0] + coefficients[e][1] d[1] + ...)),
+ * d = s - mean_signal, summed left to right in double without fused multiply-add.  Device memory: 3N (4 or 8) + 3N K 8 bytes,
+ * owned by the context's device model: released by _clear, by a later _set / _fit (also one that fails: then no model is
+ * resident), by mcgpu_set_geometry_arrays and with the context; a clone does not inherit it.
+ * Return codes: 0; -1 bad argument (also: K is not the resident model's); -5 take the host route (predict on the host +
+ * mcgpu_warp_geometry, or fit on the host): K > 4, T > 64, no model resident, and for _warp_geometry_signal whatever makes
+ * mcgpu_warp_geometry return -5 (no palette volume, default not in the palette).
+ * mcgpu_correspondence_set: upload a fitted model (replaces CorrespondenceModel.load + keeping the arrays on the host).
+ * mcgpu_correspondence_fit: the large part of CorrespondenceModel.fit (:172-202): fields[t] are T <= 64 host arrays of [3][N]
+ *   floats, pinv the T x K pseudo-inverse of the centred signals computed on the host; per element v, in this order of operations,
+ *   mean[v] = float((sum_t double(u_t[v])) / T) and coefficients[v][k] = sum_t (double(u_t[v]) - double(mean[v])) pinv[t][k].
+ *   The fields pass through the device in slabs of elements (MCGPU_CORRESPONDENCE_SLAB); the results are written into the
+ *   resident model's buffers (float mean) and, where the pointers are not null, copied to mean_out [3N] and coefficients_out [3N][K].
+ * mcgpu_correspondence_predict: the field of `signal` as float [3][N] in the model's frame (CorrespondenceModel.predict, :206-226).
+ * mcgpu_warp_geometry_signal: mcgpu_warp_geometry with the field of `signal` evaluated from the resident model, in the frame the
+ *   model was set with: no field crosses the bus and none is stored.
+ * mcgpu_correspondence_clear: release the model (0 also when none is resident). */
+int mcgpu_correspondence_set(mcgpu_ctx *ctx, const void *mean, int mean_is_f64, const double *coefficients, const double *mean_signal, int K, int frame);
+int mcgpu_correspondence_fit(mcgpu_ctx *ctx, const float *const *fields, int T, const double *pinv, const double *mean_signal, int K, int frame,
+                             float *mean_out, double *coefficients_out);
+int mcgpu_correspondence_predict(mcgpu_ctx *ctx, const double *signal, int K, float *field_out);
+int mcgpu_warp_geometry_signal(mcgpu_ctx *ctx, const double *signal, int K, int default_material, float default_density);
+int mcgpu_correspondence_clear(mcgpu_ctx *ctx);
+
 /* ---- 4-D: one resident context for many (geometry, projection angles) jobs (cbctmc/mc/simulation.py:527-710 launches the
  * engine once per respiratory state) ----
  * mcgpu_set_projection_angles: the explicit-angle list of SECTION ANGLES OF PROJ (MC-GPU_v1.3.cu:1484-1533) replaced at run
