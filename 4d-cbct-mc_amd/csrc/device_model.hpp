@@ -30,6 +30,7 @@
 #include <cstdint>
 
 #include "host_model.hpp"
+#include "tally_stage.hpp"
 
 namespace mcgpu {
 
@@ -260,6 +261,7 @@ struct TrackArgs {
   int dose_flags;             // bit 0: material dose tally, bit 1: voxel dose tally (TrackCold holds the buffers)
   unsigned long long* stats;  // diagnostic build only (kNumStats counters), else null
   unsigned long long* work_counter;  // FAST: kNumCounters id dispensers, kCounterStride words apart (zeroed before each launch)
+  StageArgs stage;            // FAST: staging of the detector hits (tally_stage.hpp); region == null: direct atomics on `image`
 };
 
 }  // namespace mcgpu

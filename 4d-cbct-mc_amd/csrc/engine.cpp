@@ -52,6 +52,8 @@ int mcgpu_clone(const mcgpu_ctx* src, int device_id, mcgpu_ctx** out) {
 
 void mcgpu_destroy(mcgpu_ctx* ctx) { delete ctx; }
 
+static bool stage_wanted(const DeviceModel& D);  // below, with the staged launch
+
 int mcgpu_config_i64(const mcgpu_ctx* ctx, const char* key, long long* value) {
   ABI_BEGIN
   require(ctx && key && value, -1, "!!ERROR!! mcgpu_config_i64: null argument");
@@ -95,6 +97,30 @@ int mcgpu_config_i64(const mcgpu_ctx* ctx, const char* key, long long* value) {
   else if (k == "correspondence_dims") *value = ctx->dev.corr_coef ? ctx->dev.corr_k : 0;  // K of the resident correspondence model, 0: none
   else if (k == "blocks_per_cu") *value = ctx->dev.resident_fast;
   else if (k == "lds_bytes_fast") *value = ctx->dev.lds.total;
+  else if (k == "tally_stage_bins") *value = stage_wanted(ctx->dev) ? (long long)ctx->dev.stage_bins : 0;  // 0: direct atomics
+  else if (k == "tally_stage_capacity") *value = ctx->dev.stage_plan.cap;  // of the last staged (sub-)launch
+  else if (k == "tally_stage_bytes") *value = (long long)ctx->dev.stage_region_bytes;
+  else if (k == "tally_stage_fallback_hits") {  // hits that took the direct atomic since the context was created; waits for the device
+    unsigned long long n = 0;
+    if (ctx->has_device && ctx->dev.stage_fallback) {
+      HIP_TRY(hipSetDevice(ctx->dev.device_id));
+      HIP_TRY(hipDeviceSynchronize());
+      HIP_TRY(hipMemcpy(&n, ctx->dev.stage_fallback, 8, hipMemcpyDeviceToHost));
+    }
+    *value = (long long)n;
+  }
+  else if (k == "tally_stage_staged_hits") {  // test support (downloads the counts table): records the last staged (sub-)launch stored (its hits = these + its share of the fallback hits)
+    unsigned long long n = 0;
+    const size_t words = (size_t)ctx->dev.stage_plan.workgroups * ctx->dev.stage_plan.n_bins;
+    if (ctx->has_device && ctx->dev.stage_counts && words != 0) {
+      std::vector<unsigned int> c(words);
+      HIP_TRY(hipSetDevice(ctx->dev.device_id));
+      HIP_TRY(hipDeviceSynchronize());
+      HIP_TRY(hipMemcpy(c.data(), ctx->dev.stage_counts, words * 4, hipMemcpyDeviceToHost));
+      for (unsigned int v : c) n += v;
+    }
+    *value = (long long)n;
+  }
   else if (k == "sigma_bracket_shift") *value = ctx->dev.sig_shift;
   else if (k == "lds_bytes_compat") *value = ctx->dev.lds.slots + 14 * kTrackBlockThreads * 4;  // tables + one parked history per lane (track_kernel.inc)
   else return set_error(-2, std::string("unknown integer key: ") + key);
@@ -171,6 +197,98 @@ int mcgpu_advance_seed(int batch_number, unsigned long long total_histories, int
   return ranecu_advance_seed(batch_number, total_histories, seed);
 }
 
+// Whether this model's FAST launches stage their detector hits (MCGPU_TALLY_STAGE: 1 / 0 force it, default -1 = the rule below).
+// Staging pays where the scattered tally atomics bind the launch, i.e. where most histories are detected: a small object in a large
+// volume of background, which the engine knows as the share of EXTERIOR bricks (the source's photons that miss the object region
+// reach the detector unattenuated).  Measured (profiles/tally_stage_ab.md): the Catphan in its 512^3 of air gains 2.9-3.1 %, the body-sized
+// CIRS and thorax phantoms lose 1.7-6 % to the fold and the longer tally service -- they sit below the threshold and keep the atomics.
+static bool stage_wanted(const DeviceModel& D) {
+  if (D.stage_cursor < 0 || D.knobs.tally_stage == 0) return false;
+  if (D.knobs.tally_stage > 0) return true;
+  return D.brick_count > 0 && 100LL * D.bricks_exterior >= (long long)kStageExteriorPercent * D.brick_count;
+}
+
+// Buffers and launch arguments of one staged (sub-)launch of `blocks` workgroups and A.count histories.  The buffers belong to the
+// device model, are allocated at the first staged launch and only grow (launches of one context share them, as they share the id
+// dispensers: one launch at a time).  An allocation that fails leaves this and every later launch on the direct atomics.
+static void stage_prepare(mcgpu_ctx& C, TrackArgs& A, int blocks, hipStream_t stream) {
+  DeviceModel& D = C.dev;
+  if (D.stage_alloc_failed || blocks <= 0) return;
+  const TallyStagePlan P = tally_stage_plan(4ULL * (unsigned long long)C.host.detector[0].total_pixels, A.count, (unsigned int)blocks, D.stage_bins,
+                                            (unsigned int)D.knobs.stage_cap);
+  if (P.n_bins == 0u || P.n_bins != D.stage_bins) return;
+  const size_t counts_bytes = (size_t)blocks * P.n_bins * 4;
+  try {
+    if (!D.stage_fallback) D.stage_fallback = D.put(std::vector<unsigned long long>(2, 0ULL));
+    if (counts_bytes > D.stage_counts_bytes) {
+      if (D.stage_counts) { D.mem.free(D.stage_counts); D.stage_counts = nullptr; D.stage_counts_bytes = 0; }
+      D.stage_counts = (unsigned int*)D.mem.device_bytes(counts_bytes);
+      D.stage_counts_bytes = counts_bytes;
+    }
+    if (P.bytes > D.stage_region_bytes) {
+      if (D.stage_region) { D.mem.free(D.stage_region); D.stage_region = nullptr; D.stage_region_bytes = 0; }
+      D.stage_region = (unsigned long long*)D.mem.device_bytes((size_t)P.bytes);
+      D.stage_region_bytes = (size_t)P.bytes;
+    }
+  } catch (const Error&) {
+    (void)hipGetLastError();
+    D.stage_alloc_failed = true;
+    return;
+  }
+  StageArgs S{};
+  S.region = D.stage_region; S.counts = D.stage_counts; S.fallback = D.stage_fallback;
+  S.pixels = P.pixels; S.n_bins = P.n_bins; S.magic = P.magic; S.bin_pixels = P.bin_pixels; S.cap = P.cap;
+  S.cursor = D.stage_cursor;
+  if (!D.stage_fold_ready) {
+    HIP_TRY(prepare_tally_fold(S));
+    D.stage_fold_ready = true;
+  }
+  HIP_TRY(hipMemsetAsync(D.stage_counts, 0, counts_bytes, stream));
+  D.stage_plan = P;
+  A.stage = S;
+}
+
+// The plan of the staged tally for a detector of `detector_words` tally words, a launch of `histories` and `workgroups` workgroups
+// (`bins` = 0: the engine's own choice): out6 = {bins, words per bin, bin pixels, capacity, bytes, sub-launches at `limit`}.  Pure host
+// arithmetic: works without a context and on one created with device = -1.
+int mcgpu_tally_stage_plan(const mcgpu_ctx* ctx, unsigned long long detector_words, unsigned long long histories, int workgroups, int bins,
+                           unsigned long long limit, unsigned long long* out6) {
+  ABI_BEGIN
+  (void)ctx;
+  require(out6 && workgroups > 0 && bins >= 0 && limit > 0, -1, "!!ERROR!! mcgpu_tally_stage_plan: bad argument");
+  const TallyStagePlan P = tally_stage_plan(detector_words, std::min(histories, limit), (unsigned int)workgroups, (unsigned int)bins, 0u);
+  out6[0] = P.n_bins; out6[1] = P.words_per_bin; out6[2] = P.bin_pixels; out6[3] = P.cap; out6[4] = P.bytes;
+  out6[5] = stage_sub_launches(histories, limit);
+  return 0;
+  ABI_END
+}
+
+// Tally words first .. first + n - 1 of that plan -> bin and bin-relative word (the mapping the kernels use, tally_stage.hpp)
+int mcgpu_tally_stage_map(unsigned long long detector_words, int bins, unsigned long long first, unsigned long long n, unsigned int* bin_out,
+                          unsigned int* rel_out) {
+  ABI_BEGIN
+  require(bin_out && rel_out && bins >= 0 && first + n <= detector_words, -1, "!!ERROR!! mcgpu_tally_stage_map: bad argument");
+  const TallyStagePlan P = tally_stage_plan(detector_words, 1, 1, (unsigned int)bins, 0u);
+  require(P.n_bins != 0u, -2, "!!ERROR!! mcgpu_tally_stage_map: no staging plan for this detector");
+  for (unsigned long long i = 0; i < n; ++i) {
+    stage_map((unsigned int)(first + i), P.pixels, P.n_bins, P.magic, P.bin_pixels, bin_out[i], rel_out[i]);
+    require(stage_unmap(bin_out[i], rel_out[i], P.pixels, P.n_bins, P.bin_pixels) == (unsigned int)(first + i), -9,
+            "!!ERROR!! internal: stage_map and stage_unmap disagree");
+  }
+  return 0;
+  ABI_END
+}
+
+// Sub-launch k of a staged launch: its range of histories
+int mcgpu_tally_stage_sub_launch(unsigned long long first, unsigned long long count, unsigned long long limit, unsigned long long k,
+                                 unsigned long long* sub_first, unsigned long long* sub_count) {
+  ABI_BEGIN
+  require(sub_first && sub_count && limit > 0, -1, "!!ERROR!! mcgpu_tally_stage_sub_launch: bad argument");
+  stage_sub_launch(first, count, limit, k, *sub_first, *sub_count);
+  return 0;
+  ABI_END
+}
+
 int mcgpu_launch_projection(mcgpu_ctx* ctx, int p, int mode, int seed, unsigned long long first, unsigned long long count, int hpt,
                             void* image_dev, void* hip_stream) {
   ABI_BEGIN
@@ -203,23 +321,34 @@ int mcgpu_launch_projection(mcgpu_ctx* ctx, int p, int mode, int seed, unsigned 
         D.resident_fast = D.knobs.blocks_per_cu > 0 ? D.knobs.blocks_per_cu : std::min(occupancy_track_fast(A), occupancy_track_fast64(A));
         if (D.resident_fast <= 0) D.resident_fast = 1;
       }
-      const unsigned long long want = (count + kPoolBlockThreads - 1) / kPoolBlockThreads;
       unsigned long long resident = (unsigned long long)D.num_cus * (unsigned long long)D.resident_fast;
       resident += resident * (unsigned long long)D.knobs.grid_spare_percent / 100ULL;  // spare workgroups: see the kernel's prologue
-      HIP_TRY(hipMemsetAsync(D.work_counter, 0, (size_t)kNumCounters * kCounterStride * 8, stream));
       A.work_counter = D.work_counter;
-      if (mode == MCGPU_MODE_FAST_STATS) {
+      // Staged detector tally (tally_stage.hpp): the launch is cut into sub-launches of at most the knob's limit -- history ids are
+      // explicit (first + id), so a cut cannot move a result -- and each is followed by its fold, in this stream and inside the events.
+      const bool staged = stage_wanted(D);
+      const unsigned long long limit = staged ? D.knobs.stage_max_histories : count;
+      const unsigned long long n_sub = staged ? stage_sub_launches(count, limit) : 1ULL;
+      for (unsigned long long k = 0; k < n_sub; ++k) {
+        stage_sub_launch(first, count, limit, k, A.first, A.count);
+        const int blocks = (int)std::min((A.count + kPoolBlockThreads - 1) / kPoolBlockThreads, resident);
+        HIP_TRY(hipMemsetAsync(D.work_counter, 0, (size_t)kNumCounters * kCounterStride * 8, stream));
+        A.stage = StageArgs{};
+        if (staged) stage_prepare(*ctx, A, blocks, stream);  // leaves A.stage.region null where the buffers cannot be had
+        if (mode == MCGPU_MODE_FAST_STATS) {
 #if defined(MC_WITH_STATS) && MC_WITH_STATS
-        if (!D.stats) D.stats = D.put(std::vector<unsigned long long>(kNumStats + 3 * kWaveTrace, 0ULL));
-        A.stats = D.stats;
-        HIP_TRY(launch_track_stats(A, (int)std::min(want, resident), stream));
+          if (!D.stats) D.stats = D.put(std::vector<unsigned long long>(kNumStats + 3 * kWaveTrace, 0ULL));
+          A.stats = D.stats;
+          HIP_TRY(launch_track_stats(A, blocks, stream));
 #else
-        throw Error(-2, "!!ERROR!! mcgpu_launch_projection: MCGPU_MODE_FAST_STATS needs the diagnostic library (libmcgpu_amd_stats.so, MCGPU_AMD_LIB)");
+          throw Error(-2, "!!ERROR!! mcgpu_launch_projection: MCGPU_MODE_FAST_STATS needs the diagnostic library (libmcgpu_amd_stats.so, MCGPU_AMD_LIB)");
 #endif
-      } else if (mode == MCGPU_MODE_FAST_F64) {
-        HIP_TRY(launch_track_fast64(A, (int)std::min(want, resident), stream));
-      } else {
-        HIP_TRY(launch_track_fast(A, (int)std::min(want, resident), stream));
+        } else if (mode == MCGPU_MODE_FAST_F64) {
+          HIP_TRY(launch_track_fast64(A, blocks, stream));
+        } else {
+          HIP_TRY(launch_track_fast(A, blocks, stream));
+        }
+        if (A.stage.region != nullptr) HIP_TRY(launch_tally_fold(A.stage, (unsigned int)blocks, A.image, stream));
       }
     }
   }

@@ -35,6 +35,8 @@ hipError_t launch_kat_fast64(int n, const unsigned int* u, const double* a, cons
 #if defined(MC_WITH_STATS) && MC_WITH_STATS
 hipError_t launch_track_stats(const TrackArgs& args, int blocks, hipStream_t stream);  // diagnostic library only (track_stats.o)
 #endif
+hipError_t prepare_tally_fold(const StageArgs& S);  // tally_fold.hip
+hipError_t launch_tally_fold(const StageArgs& S, unsigned int workgroups, unsigned long long* image, hipStream_t stream);
 hipError_t microbench_valu_issue(int num_cus, double out3[3], hipStream_t stream);
 hipError_t microbench_atomic_rate(double* out, hipStream_t stream);
 hipError_t launch_kat_rng(int mode, int seed, int batch, int hpt, int n, float* out_dev, hipStream_t stream);
@@ -141,6 +143,17 @@ struct DeviceModel {
   int resident_fast = 0;  // workgroups per CU (occupancy query), 0 = not asked yet
   unsigned long long* stats = nullptr;  // kNumStats scheduler counters of the diagnostic build
   unsigned long long* work_counter = nullptr;  // history-id dispenser of the FAST kernel
+  // staged detector tally (tally_stage.hpp): the cursor table's place in the LDS image is fixed at upload (-1: it does not fit, this
+  // model runs the direct atomics); the buffers are allocated at the first staged launch and only grow
+  int stage_cursor = -1;
+  unsigned int stage_bins = 0;
+  unsigned long long* stage_region = nullptr;
+  size_t stage_region_bytes = 0;
+  unsigned int* stage_counts = nullptr;
+  size_t stage_counts_bytes = 0;
+  unsigned long long* stage_fallback = nullptr;
+  bool stage_alloc_failed = false, stage_fold_ready = false;
+  TallyStagePlan stage_plan{};  // of the last staged (sub-)launch
   unsigned long long* scratch_image = nullptr;  // device tally of mcgpu_run_projection (allocated on first use)
   float *woodcock = nullptr, *mfp = nullptr, *mfp_tot = nullptr;
   float* wood_coarse = nullptr;  // FAST: majorant per coarse energy bin (LdsLayout::wood), rebuilt with the Woodcock table
@@ -159,6 +172,9 @@ struct DeviceModel {
     int slot_trade = 3, hold_q = 6;                  // MCGPU_SLOT_TRADE, MCGPU_HOLD_Q
     bool no_exterior = false;                        // MCGPU_NO_EXTERIOR (also read by the geometry builders)
     int segment_loop = -1;                           // MCGPU_SEGMENT_LOOP: -1 chosen from the model (make_args), 0 / 1 forced
+    int tally_stage = -1;                            // MCGPU_TALLY_STAGE: detector hits staged and folded (tally_stage.hpp): 1 on, 0 direct atomics, -1 by the exterior share (engine.cpp: stage_wanted)
+    int stage_cap = 0;                               // MCGPU_TALLY_STAGE_CAP (test hook): records per (workgroup, bin), 0: from the plan
+    unsigned long long stage_max_histories = 1ULL << 27;  // MCGPU_TALLY_STAGE_MAX_HISTORIES: sub-launch limit of a staged launch
     int fast_sched = 0;                              // MCGPU_FAST_SCHED: 0 per-wave pools, 1 workgroup-level pool (fixes the LDS layout: read at upload)
   } knobs;
   int nmat = 0;

@@ -41,6 +41,8 @@ const KnobSpec kKnobs[] = {
     {"MCGPU_NO_AUTOTUNE", 'b', 'K', "off", "scan driver: keep the default schedule instead of probing the three presets on 6e6 histories"},
     {"MCGPU_BLOCKS_PER_CU", 'i', 'K', "occupancy", "resident FAST workgroups per CU (default: what the occupancy query reports, normally 2)"},
     {"MCGPU_GRID_SPARE_PERCENT", 'i', 'K', "0", "extra workgroups beyond the resident grid, in percent"},
+    {"MCGPU_TALLY_STAGE", 'i', 'K', "-1", "FAST kernels: detector hits are staged per (workgroup, bin) with plain stores and folded into the image by a second kernel (tally_fold.hip) instead of one 64-bit atomic each (bit-identical): 1 on, 0 off, -1 on where at least 50 % of the bricks are exterior (`bricks_exterior` / `brick_count`: Catphan 96 % +3 %; CIRS 26 %, thorax 43 %: 1.7-6 % slower, left on the atomics) ; in every setting only where the cursor table ((bins + 1) x 4 B) fits what the LDS image leaves of 80 KB -- otherwise the launch runs the direct atomics, also when forced on (`geti(\"tally_stage_bins\")` = 0 says so)"},
+    {"MCGPU_TALLY_STAGE_MAX_HISTORIES", 'i', 'K', "134217728", "staged launches above this many histories are split into sub-launches, each followed by its fold (the staging buffer takes about 10 bytes per history of a sub-launch)"},
     {"MCGPU_COMPAT_THRESH_COMPTON", 'i', 'K', "-1", "COMPAT kernel: lanes a Compton batch waits for (-1: built-in 32, or 48 when the materials average >= 20 electron shells)"},
     {"MCGPU_COMPAT_THRESH_RAYLEIGH", 'i', 'K', "-1", "COMPAT kernel: Rayleigh batch threshold (built-in 4 / 8)"},
     {"MCGPU_COMPAT_THRESH_NEW", 'i', 'K', "-1", "COMPAT kernel: tally + source batch threshold (built-in 24 / 16)"},
@@ -57,6 +59,7 @@ const KnobSpec kKnobs[] = {
     {"MCGPU_EXCHANGE_POLICY", 'i', 'H', "1", "tally exchange: 1 the owner of a projection rotates over the ranks, 0 rank 0 owns every projection"},
     {"MCGPU_EXCHANGE_TIMEOUT_S", 'f', 'H', "120", "seconds a rank waits for a peer's counter before the exchange gives up"},
     {"MCGPU_EXCHANGE_FAIL_PROBE", 'b', 'T', "off", "test hook: the exchange's set-up probe reports failure (exercises the fallback chain)"},
+    {"MCGPU_TALLY_STAGE_CAP", 'i', 'T', "0", "test hook: records per (workgroup, bin) of the staged tally (0: 1.25 x the expected hits + 16); a small value drives hits through the direct-atomic fallback"},
     {"MCGPU_RCCL_FAIL", 'b', 'T', "off", "test hook: the RCCL route's set-up reports failure"},
     {"MCGPU_RNG_TEST_LOG2", 'i', 'P', "20", "tests/test_fast_rng.py: log2 of the history ids of the statistical test"},
     {"MCGPU_TEST_CACHE", 's', 'P', "/tmp/mcgpu_amd_test_cache", "tests/cases.py: directory of the generated test inputs"},

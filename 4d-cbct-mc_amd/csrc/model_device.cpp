@@ -125,6 +125,10 @@ void read_env_knobs(DeviceModel& D) {
   k.no_exterior = knob_set("MCGPU_NO_EXTERIOR");
   k.fast_sched = env_int("MCGPU_FAST_SCHED", D.knobs.fast_sched) != 0 ? 1 : 0;
   k.segment_loop = env_int("MCGPU_SEGMENT_LOOP", -1);
+  k.tally_stage = env_int("MCGPU_TALLY_STAGE", -1);
+  k.tally_stage = k.tally_stage < 0 ? -1 : (k.tally_stage != 0 ? 1 : 0);
+  k.stage_cap = std::max(0, env_int("MCGPU_TALLY_STAGE_CAP", 0));
+  k.stage_max_histories = (unsigned long long)std::max(1, env_int("MCGPU_TALLY_STAGE_MAX_HISTORIES", 1 << 27));
   D.knobs = k;
 }
 
@@ -798,6 +802,19 @@ static void lay_out_lds_and_brackets(const HostModel& H, DeviceModel& D, const s
     for (int shift = 6; shift <= 12 && D.sig_shift < 0; ++shift)
       if (lay_out_lds(P, shift).total <= kLdsPerWorkgroup) D.sig_shift = shift;
   D.lds = lay_out_lds(P, D.sig_shift);
+  // The cursor table of the staged tally (tally_stage.hpp) takes what the image leaves of the workgroup's LDS -- laid out last, so that
+  // neither the brick grid nor the brackets ever give way to it; where it does not fit, this model runs the direct atomics.
+  {
+    const TallyStagePlan S = tally_stage_plan(4ULL * (unsigned long long)H.detector[0].total_pixels, 1, 1, 0, 0);
+    const int bytes = ((int)(S.n_bins + 1u) * 4 + 15) / 16 * 16;
+    D.stage_cursor = -1;
+    D.stage_bins = 0;
+    if (S.n_bins != 0u && D.lds.total + bytes <= kLdsPerWorkgroup) {
+      D.stage_cursor = D.lds.total;
+      D.stage_bins = S.n_bins;
+      D.lds.total += bytes;
+    }
+  }
   if (D.sig_shift < 0) return;
   const SigmaBrackets B = sigma_brackets(H, tot, D.nmat, D.sig_shift);
   D.cold_host.sig_mid = D.put(B.mid);

@@ -968,6 +968,40 @@ __device__ __forceinline__ int tally_pixel(const TrackArgs& A, Particle P, int s
   const int nx = DET(A)->nx, nz = DET(A)->nz, word = scatter_state * DET(A)->total_pixels + px + pz * nx;
   return (reaches && (px > -1) && (px < nx) && (pz > -1) && (pz < nz)) ? word : -1;
 }
+// FAST: score `value` in word `word` of the detector tally.  Staged (TrackArgs::stage, a wave-uniform launch argument): the hit takes
+// the next slot of its bin in this workgroup's block -- an LDS returning add, which also settles lanes of one batch that hit the same
+// bin -- and is written there with one plain 8-byte store; tally_fold.hip sums the blocks after the kernel.  A block that is full, or
+// a launch without staging, takes the direct 64-bit add at the memory side: the image never depends on the capacity or the plan.
+__device__ __forceinline__ void tally_score(const TrackArgs& A, int word, unsigned int value) {
+  unsigned long long* const region = LARG(A, stage.region);
+  if (region != nullptr) {
+    const unsigned int n_bins = LARG(A, stage.n_bins), cap = LARG(A, stage.cap);
+    unsigned int bin, rel;
+    stage_map((unsigned int)word, LARG(A, stage.pixels), n_bins, LARG(A, stage.magic), LARG(A, stage.bin_pixels), bin, rel);
+    unsigned int* const cursor = reinterpret_cast<unsigned int*>(lds_raw + LARG(A, stage.cursor));
+    const unsigned int slot = atomicAdd(cursor + bin, 1u);
+    if (slot < cap) {
+      ((GLOBAL_AS unsigned long long*)region)[(unsigned long long)(blockIdx.x * n_bins + bin) * cap + slot] = ((unsigned long long)rel << 32) | value;
+      return;
+    }
+    atomicAdd(cursor + n_bins, 1u);  // hits of this workgroup that fell back
+  }
+  atomicAdd((unsigned long long*)as_global(LARG(A, image)) + (unsigned int)word, (unsigned long long)value);
+}
+// every thread of the workgroup calls these once: before stage_tables() (whose barrier publishes the zeros) / after its history loop,
+// behind the barrier of finish_workgroup()
+__device__ __forceinline__ void stage_cursors_clear(const TrackArgs& A) {
+  if (A.stage.region == nullptr) return;
+  unsigned int* const cursor = reinterpret_cast<unsigned int*>(lds_raw + A.stage.cursor);
+  for (unsigned int i = threadIdx.x; i <= A.stage.n_bins; i += blockDim.x) cursor[i] = 0u;
+}
+__device__ __forceinline__ void stage_counts_publish(const TrackArgs& A) {
+  const unsigned int n_bins = LARG(A, stage.n_bins), cap = LARG(A, stage.cap);
+  const unsigned int* const cursor = reinterpret_cast<const unsigned int*>(lds_raw + LARG(A, stage.cursor));
+  unsigned int* const counts = LARG(A, stage.counts) + blockIdx.x * n_bins;
+  for (unsigned int i = threadIdx.x; i < n_bins; i += blockDim.x) counts[i] = min(cursor[i], cap);
+  if (threadIdx.x == 0 && cursor[n_bins] != 0u) atomicAdd(LARG(A, stage.fallback), (unsigned long long)cursor[n_bins]);
+}
 #endif
 
 __device__ __forceinline__ int energy_index(const TrackArgs& A, float E) {

@@ -34,6 +34,7 @@
 #include "track_common.inc"  // opens namespace mcgpu { namespace {
 
 constexpr int kPoolBlock = kPoolBlockThreads;
+static_assert(kStageWorkgroupSlack == 2u * (kPoolBlockThreads / 64) * kChunk, "tally_stage.hpp: the capacity's allowance is two id chunks per wave");
 constexpr int kParked = kPoolParked;                 // parked histories per lane (LDS slots)
 constexpr int kSlotStride = kParked * kPoolBlock;    // columns of the workgroup's slot array: word f of column t at slots[f * kSlotStride + t]
 
@@ -413,6 +414,20 @@ __device__ __forceinline__ void flight_steps(const TrackArgs& A, History& h, int
   }
 }
 
+// End of a FAST kernel: every wave of the workgroup arrives here exactly once -- both schedulers leave their loop by `break` only,
+// waves that run out of work early (PH_DONE), the panic and the cycle-bound exits included -- and the conditions are launch arguments,
+// the same for the whole grid.  Behind one barrier: the material dose accumulators (flush_dose) and the staging counts.
+__device__ __forceinline__ void finish_workgroup(const TrackArgs& A) {
+  const bool staged = LARG(A, stage.region) != nullptr, dose = (A.dose_flags & kDoseMaterials) != 0;
+  if (!staged && !dose) return;
+  __syncthreads();
+  if (dose && threadIdx.x < 2 * kMaxMaterials) {
+    const unsigned long long v = reinterpret_cast<unsigned long long*>(lds_raw + SLDS(A, dose_mat))[threadIdx.x];
+    if (v != 0ULL) atomicAdd((unsigned long long*)as_global(COLD(A)->dose_materials) + threadIdx.x, v);
+  }
+  if (staged) stage_counts_publish(A);
+}
+
 // kDouble: the arithmetic of this translation unit (MC_FAST_F64) as part of the kernel's NAME -- profilers tell track_fast.hip's
 // track_pool_kernel<VK, seg, 0> from track_fast64.hip's <VK, seg, 1> (the body does not use it: the arithmetic is chosen by the macro)
 template <int VK, bool kSegmentLoop, int kDouble = MC_FAST_F64>
@@ -431,6 +446,7 @@ __global__ __launch_bounds__(kPoolBlock, kPoolWavesPerSimd) void track_pool_kern
     }
   }
 #endif
+  stage_cursors_clear(A);
   stage_tables<is_u8(VK) ? (int)kVolU8 : VK>(A);
   // the slots this lane parks its other histories in: pointers, traded between the lanes of the wave (step 4 below).  Column t of
   // the workgroup's slot array: lane `threadIdx.x` starts with columns threadIdx.x + j * kPoolBlock, j < kParked.
@@ -786,11 +802,12 @@ __global__ __launch_bounds__(kPoolBlock, kPoolWavesPerSimd) void track_pool_kern
           phase = PH_DONE;  // every counter is exhausted (otherwise the lane stays NEW and asks again at the next service)
         }
       }
-      // One scattered 64-bit add per detected photon, executed at the memory side.  Measured on the Catphan workload
-      // (round-2 experiment, DESIGN.md 3.1): without it the kernel is 17 % faster, with a plain store in its place 15 %, with a 32-bit
-      // add 4 %; issuing it later (after the wave's next voxel wait, so that no load queues behind it) changes nothing --
-      // the cost is the read-modify-write traffic itself, not the wave's in-order memory counter.
-      if (tally_word >= 0) atomicAdd((unsigned long long*)as_global(LARG(A, image)) + (unsigned int)tally_word, (unsigned long long)tally_value);
+      // One scattered 64-bit add per detected photon, executed at the memory side, was the wall of the Catphan launch: 7.5e7 of them
+      // at 2.37e10/s = 3.18 ms of a 3.67 ms launch, whatever the kernel around them did (round-2 experiment, DESIGN.md 3.1: without
+      // the add 17 % faster, a plain store in its place 15 %, a 32-bit add 4 %; issuing it later changes nothing).  The hit is now
+      // STAGED (tally_score: an LDS add for its slot + one plain 8-byte store) and folded into the image after the kernel
+      // (tally_fold.hip); the add remains for a full block and for launches without staging (profiles/tally_stage_ab.md).
+      if (tally_word >= 0) tally_score(A, tally_word, tally_value);
       STAT_T1(14);
     }
     // (4) lanes that hold no flyable history get the spare one of a lane that holds two (trade_slots); measured before this
@@ -820,7 +837,7 @@ __global__ __launch_bounds__(kPoolBlock, kPoolWavesPerSimd) void track_pool_kern
     st[31] += __builtin_readcyclecounter() - t_sp;  // whole scheduling point (settle + services + exchanges)
 #endif
   }
-  flush_dose(A);
+  finish_workgroup(A);
 #if MC_STATS
   if ((threadIdx.x & 63) == 0 && A.stats != nullptr)
     for (int k = 0; k < kNumStats; ++k) atomicAdd(A.stats + k, st[k]);
@@ -908,6 +925,7 @@ __global__ __launch_bounds__(kPoolBlock, kPoolWavesPerSimd) void track_wg_kernel
     rings[kQNew * kRingEntries + t] = (unsigned short)t;
     if (t < 16u) ctl[t] = (t == (unsigned int)(kCtlTail + kQNew)) ? kRingEntries : 0u;
   }
+  stage_cursors_clear(A);
   stage_tables<is_u8(VK) ? (int)kVolU8 : VK>(A);  // ends with the workgroup barrier
 
   History h;
@@ -1237,7 +1255,7 @@ __global__ __launch_bounds__(kPoolBlock, kPoolWavesPerSimd) void track_wg_kernel
           phase = PH_DONE;
         }
       }
-      if (tally_word >= 0) atomicAdd((unsigned long long*)as_global(LARG(A, image)) + (unsigned int)tally_word, (unsigned long long)tally_value);
+      if (tally_word >= 0) tally_score(A, tally_word, tally_value);
       STAT_T1(14);
       STAT_T1(31);
     }
@@ -1251,7 +1269,7 @@ __global__ __launch_bounds__(kPoolBlock, kPoolWavesPerSimd) void track_wg_kernel
     A.image[14] = pn;
 #endif
   }
-  flush_dose(A);
+  finish_workgroup(A);
 #if MC_STATS
   if ((threadIdx.x & 63) == 0 && A.stats != nullptr)
     for (int k = 0; k < kNumStats; ++k) atomicAdd(A.stats + k, st[k]);

@@ -24,7 +24,7 @@ EXE_PATH = Path(__file__).resolve().parent / "MC-GPU_v1.3.x"
 ABI_SYMBOLS = (
     "mcgpu_abi_version", "mcgpu_knob_table", "mcgpu_last_error", "mcgpu_create", "mcgpu_clone", "mcgpu_destroy", "mcgpu_config_i64", "mcgpu_config_f64",
     "mcgpu_host_table", "mcgpu_projection_file_name", "mcgpu_image_words", "mcgpu_launch_shape", "mcgpu_advance_seed",
-    "mcgpu_launch_projection", "mcgpu_scheduler_stats", "mcgpu_scheduler_stats_ex", "mcgpu_last_kernel_ms", "mcgpu_clear_image", "mcgpu_run_projection",
+    "mcgpu_launch_projection", "mcgpu_tally_stage_plan", "mcgpu_tally_stage_map", "mcgpu_tally_stage_sub_launch", "mcgpu_scheduler_stats", "mcgpu_scheduler_stats_ex", "mcgpu_last_kernel_ms", "mcgpu_clear_image", "mcgpu_run_projection",
     "mcgpu_write_projection", "mcgpu_format_projection", "mcgpu_write_formatted_projection", "mcgpu_dose_info", "mcgpu_dose_read", "mcgpu_dose_clear", "mcgpu_write_dose_report",
     "mcgpu_finalize_projection", "mcgpu_finalize_projection_host", "mcgpu_stack_create", "mcgpu_stack_append", "mcgpu_stack_write_slice", "mcgpu_stack_finish",
     "mcgpu_stack_read", "mcgpu_normalize_stack", "mcgpu_run_scan", "mcgpu_run_scan_multi", "mcgpu_set_projection_angles", "mcgpu_set_geometry_arrays",
@@ -103,6 +103,9 @@ def load_library(path: Optional[os.PathLike] = None):
     lib.mcgpu_launch_shape.argtypes = [cull, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(cull)]
     lib.mcgpu_advance_seed.argtypes = [ci, cull, ci]
     lib.mcgpu_launch_projection.argtypes = [vp, ci, ci, ci, cull, cull, ci, vp, vp]
+    lib.mcgpu_tally_stage_plan.argtypes = [vp, cull, cull, ci, ci, cull, C.POINTER(cull)]
+    lib.mcgpu_tally_stage_map.argtypes = [cull, ci, cull, cull, vp, vp]
+    lib.mcgpu_tally_stage_sub_launch.argtypes = [cull, cull, cull, cull, C.POINTER(cull), C.POINTER(cull)]
     lib.mcgpu_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.mcgpu_scheduler_stats.argtypes = [vp, C.POINTER(cull), ci]
     lib.mcgpu_scheduler_stats_ex.argtypes = [vp, C.POINTER(cull), ci, ci]
@@ -177,6 +180,28 @@ def launch_shape(histories: int, threads_per_block: int, histories_per_thread: i
     b, h, t = C.c_int(), C.c_int(), C.c_ulonglong()
     _check(load_library().mcgpu_launch_shape(int(histories), threads_per_block, histories_per_thread, C.byref(b), C.byref(h), C.byref(t)))
     return b.value, h.value, t.value
+
+
+def tally_stage_plan(detector_words: int, histories: int, workgroups: int, bins: int = 0, limit: int = 1 << 27, ctx=None) -> dict:
+    """Plan of the staged detector tally (csrc/tally_stage.hpp): host arithmetic, no device needed."""
+    out = (C.c_ulonglong * 6)()
+    _check(load_library().mcgpu_tally_stage_plan(ctx.h if ctx is not None else None, int(detector_words), int(histories), int(workgroups), int(bins), int(limit), out))
+    return dict(zip(("bins", "words_per_bin", "bin_pixels", "capacity", "bytes", "sub_launches"), (int(v) for v in out)))
+
+
+def tally_stage_map(detector_words: int, bins: int = 0, first: int = 0, n: Optional[int] = None):
+    """(bin, bin-relative word) of the tally words first .. first+n-1, as uint32 arrays."""
+    n = int(detector_words) - int(first) if n is None else int(n)
+    b, r = np.empty(n, np.uint32), np.empty(n, np.uint32)
+    _check(load_library().mcgpu_tally_stage_map(int(detector_words), int(bins), int(first), n, b.ctypes.data, r.ctypes.data))
+    return b, r
+
+
+def tally_stage_sub_launch(first: int, count: int, limit: int, k: int):
+    """(first, count) of sub-launch k of a staged launch."""
+    f, c = C.c_ulonglong(), C.c_ulonglong()
+    _check(load_library().mcgpu_tally_stage_sub_launch(int(first), int(count), int(limit), int(k), C.byref(f), C.byref(c)))
+    return f.value, c.value
 
 
 def advance_seed(batch_number: int, total_histories: int, seed: int) -> int:

@@ -103,6 +103,20 @@ int mcgpu_advance_seed(int batch_number, unsigned long long total_histories, int
  * `seed` is the RNG seed for this projection; `hpt` is ignored in FAST mode. */
 int mcgpu_launch_projection(mcgpu_ctx *ctx, int p, int mode, int seed, unsigned long long first, unsigned long long count,
                             int hpt, void *image_dev, void *hip_stream);
+/* Staged detector tally of the FAST kernels (csrc/tally_stage.hpp; MCGPU_TALLY_STAGE): hits are stored per (workgroup, bin) and a
+ * second kernel folds them into the image, inside the launch's events.  The plan for a detector of `detector_words` tally words
+ * (4 * Nx * Nz), a launch of `histories` cut into sub-launches of at most `limit`, and `workgroups` workgroups; `bins` = 0: the
+ * engine's choice.  out6 = {bins (0: no staging), words per bin, pixels per bin, records per (workgroup, bin), bytes of the
+ * staging buffer = capacity * workgroups * bins * 8, sub-launches}.  Host arithmetic only: `ctx` may be NULL or have no device. */
+int mcgpu_tally_stage_plan(const mcgpu_ctx *ctx, unsigned long long detector_words, unsigned long long histories, int workgroups,
+                           int bins, unsigned long long limit, unsigned long long *out6);
+/* Test support (no caller in the engine or the drop-in needs these two; they exist so that the mapping and the split the kernels use
+ * can be checked on a machine without a GPU).  Tally words first .. first+n-1 -> their bin and bin-relative word under that plan. */
+int mcgpu_tally_stage_map(unsigned long long detector_words, int bins, unsigned long long first, unsigned long long n,
+                          unsigned int *bin_out, unsigned int *rel_out);
+/* History range of sub-launch k of a staged launch of [first, first+count) at sub-launch limit `limit`. */
+int mcgpu_tally_stage_sub_launch(unsigned long long first, unsigned long long count, unsigned long long limit, unsigned long long k,
+                                 unsigned long long *sub_first, unsigned long long *sub_count);
 /* Milliseconds between the HIP events recorded around the most recent launch on its stream
  * (synchronises on the stop event). */
 int mcgpu_last_kernel_ms(mcgpu_ctx *ctx, float *ms);
