@@ -9,7 +9,8 @@
 //   - samples where the ray crosses the voxel-centre planes k = ns..fs of the main axis; each is a bilinear interpolation in the
 //     other two axes with explicit float32 weights, taps outside the volume read 0; the first and last steps are weighted by the
 //     fraction of a step the clipped segment covers, and the sum is scaled by the length in mm of one main-axis step
-//   - float32 accumulation (RTK's float pixel type)
+//   - tap positions and the sum over the planes in float64, the samples in float32, the result rounded once to float32 (RTK's
+//     float pixel type): with both in float32 the 512^3 Catphan volume missed the restatement's tolerance fourfold (joseph_ray.inc)
 // The traversal runs in the index frame of the IEC volume [nz][ny][nx]; only the voxel fetch differs between volume sources
 // (template parameter): a float volume uploaded from the host, or the context's own representation (u8 tiled / u16 palette
 // indices with the palette densities in LDS, raw {density, material} float2), read in the .vox frame.  All sources run the same

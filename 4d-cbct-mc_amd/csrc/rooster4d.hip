@@ -7,7 +7,7 @@
 // optional water pre-correction (the polynomial sum_j c_j p^j of rtkfdk --wpc, fdk.hip: weight_kernel).
 //   S   (phase -> interpolation weights, host: interpolation_weights): phi_k in [0, 1], t = phi_k N, l = floor(t) mod N,
 //       h = (l + 1) mod N, w_h = t - floor(t), w_l = 1 - w_h.  S blends frames l and h for projection k, S^T distributes into them.
-//   R   Joseph forward projection (joseph_ray.inc, unchanged: float64 ray setup, float32 accumulation), reading the blend
+//   R   Joseph forward projection (joseph_ray.inc, unchanged: float64 ray setup, tap positions and sums, float32 samples), reading the blend
 //       w_l x_l + w_h x_h at every tap (SrcBlend).
 //   B   voxel-driven bilinear back-projection like fdk.hip's backproject_kernel (a detector sample counts only with both columns
 //       and both rows inside the detector), without ramp filter or angular-gap weights, with the weight (sdd / U)^2 sx sy sz / (du dv),

@@ -1,4 +1,5 @@
-"""Float64 numpy restatement of the Joseph forward projector (csrc/forward_project.hip), the oracle of tests/test_forward_projection.py.
+"""Float64 numpy restatement of the Joseph forward projector (csrc/forward_project.hip), the oracle of tests/test_forward_projection.py and
+tests/test_forward_projection_configs.py (`project`: whole stacks; `project_rays`: a chosen set of rays of a large stack).
 
 Geometry (RTK circular, as CircularGeometry.matrix): source at Ry(angle) (0, 0, sid); pixel (u, v) at rotated-frame position
 (u + offset_x, v + offset_y, sid - sdd).  Volume [nz][ny][nx] in the IEC frame, voxel (0,0,0) centred at `origin`; it spans half a
@@ -38,6 +39,23 @@ def project(vol, spacing, origin, angles, offsets_x, offsets_y, sid, sdd, nu, nv
         D = P - S
         Si, Di = (S - org) / sp, D / sp
         out[p] = _trace(vol, N, Si, Di, np.linalg.norm(D, axis=1)).reshape(nv, nu)
+    return out
+
+
+def project_rays(vol, spacing, origin, angles, offsets_x, offsets_y, sid, sdd, du, dv, u0, v0, p, iu, iv):
+    """Line integrals (float64, 1-D) of the rays (projection p[i], pixel column iu[i], row iv[i]) only: the same entries of
+    `project`, bit for bit, without tracing the rest of the stack.  `vol` is read as it is (a float32 volume is converted voxel by
+    voxel inside the gather, never as a whole)."""
+    vol = np.asarray(vol)
+    N = np.array(vol.shape[::-1])
+    sp, org = np.asarray(spacing, float), np.asarray(origin, float)
+    p, iu, iv = (np.asarray(v, dtype=np.int64).ravel() for v in (p, iu, iv))
+    out = np.zeros(p.size)
+    for q in np.unique(p):
+        sel = np.flatnonzero(p == q)
+        S, P = ray_endpoints(angles[q], offsets_x[q], offsets_y[q], sid, sdd, u0 + du * iu[sel], v0 + dv * iv[sel])
+        D = P - S
+        out[sel] = _trace(vol, N, (S - org) / sp, D / sp, np.linalg.norm(D, axis=1))
     return out
 
 
@@ -102,4 +120,16 @@ def ambiguous_main_axis(angles, offsets_x, offsets_y, sid, sdd, nu, nv, du, dv, 
         S, P = ray_endpoints(a, offsets_x[p], offsets_y[p], sid, sdd, uu.ravel(), vv.ravel())
         d = np.sort(np.abs((P - S) / np.asarray(spacing, float)), axis=1)
         out[p] = (d[:, 2] - d[:, 1] <= rel * d[:, 2]).reshape(nv, nu)
+    return out
+
+
+def ambiguous_main_axis_rays(angles, offsets_x, offsets_y, sid, sdd, du, dv, u0, v0, p, iu, iv, spacing, rel=1e-5):
+    """`ambiguous_main_axis` of the rays (p[i], iu[i], iv[i]) only (1-D bool)."""
+    p, iu, iv = (np.asarray(v, dtype=np.int64).ravel() for v in (p, iu, iv))
+    out = np.zeros(p.size, dtype=bool)
+    for q in np.unique(p):
+        sel = np.flatnonzero(p == q)
+        S, P = ray_endpoints(angles[q], offsets_x[q], offsets_y[q], sid, sdd, u0 + du * iu[sel], v0 + dv * iv[sel])
+        d = np.sort(np.abs((P - S) / np.asarray(spacing, float)), axis=1)
+        out[sel] = d[:, 2] - d[:, 1] <= rel * d[:, 2]
     return out
