@@ -2,6 +2,8 @@
 // voxel-file writers.
 #include "engine_internal.hpp"
 
+#include <cstddef>
+
 using namespace mcgpu;
 
 namespace {
@@ -116,9 +118,208 @@ void warp_resident_geometry(mcgpu_ctx* ctx, const char* who, const float* displa
   ctx->table_cache.clear();
 }
 
+// ---- CT image + segmentations -> geometry (image_map.hip)
+// The inputs of a mapping on the device, freed when the holder goes.
+struct MappedInputs {
+  std::vector<void*> buffers;
+  ImageMapArgs args{};
+  double ms_upload = 0.0;
+  size_t bytes = 0;
+  ~MappedInputs() { release(); }
+  void release() {
+    for (void* p : buffers) (void)hipFree(p);
+    buffers.clear();
+  }
+  void* device_copy(const void* host, size_t n) {
+    void* d = nullptr;
+    HIP_TRY(hipMalloc(&d, std::max<size_t>(n, 16)));
+    buffers.push_back(d);
+    if (host) HIP_TRY(hipMemcpy(d, host, n, hipMemcpyHostToDevice));
+    return d;
+  }
+  void upload(size_t nvox, const void* image, int image_dtype, const uint8_t* const* segmentations, const float* thresholds) {
+    const auto t0 = std::chrono::steady_clock::now();
+    args.image_is_f32 = image_dtype == MCGPU_IMAGE_FLOAT32 ? 1 : 0;
+    args.image = device_copy(image, nvox * (args.image_is_f32 ? 4 : 2));
+    bytes = nvox * (args.image_is_f32 ? 4 : 2);
+    for (int k = 0; k < kImageSegmentations; ++k) {
+      args.seg[k] = segmentations[k] ? (const unsigned char*)device_copy(segmentations[k], nvox) : nullptr;
+      if (segmentations[k]) bytes += nvox;
+    }
+    for (int k = 0; k < 3; ++k) args.threshold[k] = thresholds[k];
+    unsigned int words[kImageStatWords];
+    image_map_stats_init(words);
+    args.stats = (unsigned int*)device_copy(words, sizeof words);
+    ms_upload = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+};
+
+void fill_image_report(mcgpu_image_map_report* report, const unsigned int* words, double ms_kernel, double ms_upload, double ms_install, size_t kernel_bytes) {
+  if (!report) return;
+  mcgpu_image_map_report r;
+  memset(&r, 0, sizeof r);
+  r.struct_size = (unsigned int)sizeof r;
+  for (int c = 0; c < kImageClasses; ++c) {
+    r.count[c] = words[c];
+    r.first[c] = words[kImageClasses + c] == 0xFFFFFFFFu ? -1LL : (long long)words[kImageClasses + c];
+  }
+  r.unmapped = words[2 * kImageClasses];
+  r.ms_kernel = ms_kernel; r.ms_upload = ms_upload; r.ms_install = ms_install;
+  r.kernel_bytes = kernel_bytes;
+  const unsigned int want = report->struct_size;  // as the caller was compiled
+  memcpy(report, &r, std::min<size_t>(want, sizeof r));
+  report->struct_size = want;
+}
+
+void check_image_arguments(const char* who, const mcgpu_ctx* ctx, const int* n, const void* image, int image_dtype, const uint8_t* const* segmentations,
+                           const mcgpu_image_class* table, const float* thresholds, const mcgpu_image_map_report* report) {
+  const std::string pre = std::string("!!ERROR!! ") + who + ": ";
+  require(ctx && ctx->has_device && n && image && segmentations && table && thresholds && n[0] > 0 && n[1] > 0 && n[2] > 0 &&
+              (image_dtype == MCGPU_IMAGE_INT16 || image_dtype == MCGPU_IMAGE_FLOAT32),
+          -1, (pre + "bad argument (the context needs a device)").c_str());
+  require((unsigned long long)n[0] * n[1] * n[2] < (1ULL << 31), -2, "!!ERROR!! voxel grid too large for the 32-bit voxel index of the kernel");
+  require(!report || report->struct_size >= 8, -1, (pre + "set report->struct_size = sizeof(mcgpu_image_map_report)").c_str());
+}
+
+float density_as_in_a_voxel_file(float density) {  // "%.6f", cbctmc/mc/voxel_data.pyx:25
+  char t[64];
+  snprintf(t, sizeof t, "%.6f", (double)density);
+  return strtof(t, nullptr);
+}
+
 }  // namespace
 
 extern "C" {
+
+int mcgpu_map_image(mcgpu_ctx* ctx, const int n[3], const void* image, int image_dtype, const uint8_t* const segmentations[8],
+                    const mcgpu_image_class table[12], const float thresholds[3], uint8_t* material_out, float* density_out,
+                    mcgpu_image_map_report* report) {
+  ABI_BEGIN
+  check_image_arguments("mcgpu_map_image", ctx, n, image, image_dtype, segmentations, table, thresholds, report);
+  require(material_out && density_out, -1, "!!ERROR!! mcgpu_map_image: null output");
+  unsigned char material[kImageClasses];
+  float density[kImageClasses];
+  for (int c = 0; c < kImageClasses; ++c) {
+    require(table[c].material >= 0 && table[c].material <= 255, -1, "!!ERROR!! mcgpu_map_image: material number of a class out of range");
+    material[c] = (unsigned char)table[c].material;
+    density[c] = table[c].density;
+  }
+  DeviceModel& D = ctx->dev;
+  HIP_TRY(hipSetDevice(D.device_id));
+  const size_t nvox = (size_t)n[0] * n[1] * n[2];
+  MappedInputs in;
+  in.upload(nvox, image, image_dtype, segmentations, thresholds);
+  unsigned char* m_out = (unsigned char*)in.device_copy(nullptr, nvox);
+  float* d_out = (float*)in.device_copy(nullptr, nvox * 4);
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  HIP_TRY(hipEventCreate(&ev[0]));
+  hipError_t err = hipEventCreate(&ev[1]);
+  float ms = 0.f;
+  unsigned int words[kImageStatWords];
+  auto step = [&](hipError_t e) { if (err == hipSuccess) err = e; };
+  step(hipEventRecord(ev[0], nullptr));
+  if (err == hipSuccess) step(launch_image_map_plain(in.args, n[0], n[1], n[2], material, density, m_out, d_out, D.num_cus, nullptr));
+  step(hipEventRecord(ev[1], nullptr));
+  step(hipMemcpy(words, in.args.stats, sizeof words, hipMemcpyDeviceToHost));  // waits for the kernel
+  step(hipEventElapsedTime(&ms, ev[0], ev[1]));
+  step(hipMemcpy(material_out, m_out, nvox, hipMemcpyDeviceToHost));
+  step(hipMemcpy(density_out, d_out, nvox * 4, hipMemcpyDeviceToHost));
+  (void)hipEventDestroy(ev[0]);
+  if (ev[1]) (void)hipEventDestroy(ev[1]);
+  HIP_TRY(err);
+  fill_image_report(report, words, ms, in.ms_upload, 0.0, in.bytes + nvox * 5);
+  return 0;
+  ABI_END
+}
+
+int mcgpu_set_geometry_image(mcgpu_ctx* ctx, const int n[3], const float spacing_cm[3], const void* image, int image_dtype,
+                             const uint8_t* const segmentations[8], const mcgpu_image_class table[12], const float thresholds[3], int frame,
+                             mcgpu_image_map_report* report) {
+  ABI_BEGIN
+  check_image_arguments("mcgpu_set_geometry_image", ctx, n, image, image_dtype, segmentations, table, thresholds, report);
+  require(spacing_cm && (frame == 0 || frame == 1), -1, "!!ERROR!! mcgpu_set_geometry_image: bad argument");
+  HostModel& H = ctx->host;
+  const int device_id = ctx->dev.device_id, num_cus = ctx->dev.num_cus;
+  HIP_TRY(hipSetDevice(device_id));
+  HIP_TRY(hipDeviceSynchronize());
+  VoxelGrid v;  // its voxel arrays stay empty: the voxels exist on the device only (sync_host_voxels fills them on demand)
+  for (int k = 0; k < 3; ++k) {
+    v.n[k] = n[k];
+    v.voxel_size[k] = spacing_cm[k];
+    v.size_bbox[k] = v.n[k] * v.voxel_size[k];
+    v.inv_voxel_size[k] = 1.0f / v.voxel_size[k];
+  }
+  const size_t nvox = v.count();
+  const size_t tiled_bytes = (size_t)((n[0] + 3) >> 2) * ((n[1] + 3) >> 2) * ((n[2] + 3) >> 2) * 64;
+  // 1. the mapping, beside the live model: nothing of the context has changed when it fails
+  MappedInputs in;
+  in.upload(nvox, image, image_dtype, segmentations, thresholds);
+  unsigned char* classes = (unsigned char*)in.device_copy(nullptr, tiled_bytes);
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  HIP_TRY(hipEventCreate(&ev[0]));
+  hipError_t err = hipEventCreate(&ev[1]);
+  float ms = 0.f;
+  unsigned int words[kImageStatWords];
+  auto step = [&](hipError_t e) { if (err == hipSuccess) err = e; };
+  step(hipEventRecord(ev[0], nullptr));
+  if (err == hipSuccess) step(launch_image_map_tiled(in.args, frame, n[0], n[1], n[2], classes, num_cus, nullptr));
+  step(hipEventRecord(ev[1], nullptr));
+  step(hipMemcpy(words, in.args.stats, sizeof words, hipMemcpyDeviceToHost));  // waits for the kernel
+  step(hipEventElapsedTime(&ms, ev[0], ev[1]));
+  (void)hipEventDestroy(ev[0]);
+  if (ev[1]) (void)hipEventDestroy(ev[1]);
+  HIP_TRY(err);
+  const auto t_install = std::chrono::steady_clock::now();
+  fill_image_report(report, words, ms, in.ms_upload, 0.0, in.bytes + tiled_bytes);
+  if (words[2 * kImageClasses] != 0u) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "!!ERROR!! mcgpu_set_geometry_image: %u voxels are unmapped (no line of the mapping touches them: a body segmentation is missing)",
+             words[2 * kImageClasses]);
+    throw Error(-2, msg);
+  }
+  // 2. what mcgpu_set_geometry_arrays derives from the voxel arrays, from the statistics of the classes
+  DeviceVolumeSource src;
+  src.classes_tiled = classes;
+  src.bytes = tiled_bytes;
+  for (int k = 0; k < kMaxMaterials; ++k) v.density_max[k] = -999.0f;
+  for (int c = 0; c < kImageClasses; ++c) {
+    src.material[c] = table[c].material;
+    src.density[c] = density_as_in_a_voxel_file(table[c].density);  // once per class instead of once per voxel
+    src.first[c] = words[kImageClasses + c];
+    if (src.first[c] == 0xFFFFFFFFu) continue;
+    require(src.material[c] >= 1 && src.material[c] <= kMaxMaterials, -2, "!!ERROR load_voxels!! Voxel material number out of range!!");
+    require(src.density[c] >= 1.0e-9f, -2, "!!ERROR load_voxels!! Voxel density can not be 0 or negative");
+    v.density_max[src.material[c] - 1] = std::max(v.density_max[src.material[c] - 1], src.density[c]);
+  }
+  MaterialTables mat;
+  load_material_files(H.cfg.file_materials, v, mat);
+  int roi[6], roi_old[6];
+  for (int k = 0; k < 6; ++k) roi[k] = roi_old[k] = H.cfg.dose_roi[k];
+  if (roi[1] > -1)
+    for (int ax = 0; ax < 3; ++ax) roi[2 * ax + 1] = std::min(roi[2 * ax + 1], v.n[ax] - 1);
+  std::swap(H.voxels, v);
+  std::swap(H.mat, mat);
+  for (int k = 0; k < 6; ++k) H.cfg.dose_roi[k] = roi[k];
+  DeviceModel fresh;
+  try {
+    fresh = upload_model(H, device_id, &src);
+    for (int k = 0; k < 5; ++k) fresh.sched[k] = ctx->dev.sched[k];  // the tuned FAST schedule survives a geometry change
+    fresh.sched_set = ctx->dev.sched_set;
+    apply_schedule(fresh);
+  } catch (...) {
+    std::swap(H.voxels, v);
+    std::swap(H.mat, mat);
+    for (int k = 0; k < 6; ++k) H.cfg.dose_roi[k] = roi_old[k];
+    throw;
+  }
+  ctx->dev = std::move(fresh);  // with the superseded model go its correspondence model and its warp base
+  ctx->host_voxels_stale = true;
+  ctx->table_cache.clear();
+  if (report && report->struct_size >= offsetof(mcgpu_image_map_report, ms_install) + sizeof(double))
+    report->ms_install = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_install).count();
+  return 0;
+  ABI_END
+}
 
 // ---- 4-D support: one resident context, many (geometry, projection angle) jobs (cbctmc/mc/simulation.py:527-710)
 int mcgpu_set_projection_angles(mcgpu_ctx* ctx, int n, const float* angles_deg) {

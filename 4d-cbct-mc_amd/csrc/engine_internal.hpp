@@ -23,6 +23,7 @@
 #include "device_model.hpp"
 #include "ascii_device.hpp"
 #include "geometry_device.hpp"
+#include "image_map.hpp"
 
 namespace mcgpu {
 
@@ -39,6 +40,7 @@ hipError_t prepare_tally_fold(const StageArgs& S);  // tally_fold.hip
 hipError_t launch_tally_fold(const StageArgs& S, unsigned int workgroups, unsigned long long* image, hipStream_t stream);
 hipError_t microbench_valu_issue(int num_cus, double out3[3], hipStream_t stream);
 hipError_t microbench_atomic_rate(double* out, hipStream_t stream);
+hipError_t microbench_copy_rate(int num_cus, double* out, hipStream_t stream);
 hipError_t launch_kat_rng(int mode, int seed, int batch, int hpt, int n, float* out_dev, hipStream_t stream);
 hipError_t launch_kat_streams_fast(int generator, unsigned int seed, unsigned int stream_key, unsigned long long first_id,
                                    const unsigned long long* ids_dev, int n_ids, int n_draws, unsigned int* out_dev, hipStream_t stream);
@@ -198,7 +200,7 @@ struct mcgpu_ctx {
   mcgpu::HostModel host;
   mcgpu::DeviceModel dev;
   bool has_device = false;
-  bool host_voxels_stale = false;  // the device holds a geometry warped there (mcgpu_warp_geometry): H.voxels is downloaded on demand
+  bool host_voxels_stale = false;  // the device holds a geometry warped or mapped there (mcgpu_warp_geometry, mcgpu_set_geometry_image): H.voxels is downloaded on demand
   std::map<std::string, std::vector<unsigned char>> table_cache;
 };
 
@@ -213,7 +215,15 @@ void refresh_woodcock(const HostModel& H, DeviceModel& D);      // the Woodcock 
 void refresh_cold_geometry(DeviceModel& D);                     // object region and brick palette into TrackCold, uploaded if changed
 void read_env_knobs(DeviceModel& D);
 void apply_schedule(DeviceModel& D);
-DeviceModel upload_model(const HostModel& H, int device_id);
+// A u8 volume that is already on the device as classes (image_map.hip), for upload_model to build the model around instead of H.voxels' arrays
+struct DeviceVolumeSource {
+  const unsigned char* classes_tiled = nullptr;  // class per voxel, 4x4x4-tiled, padding as tiled_volume writes it
+  size_t bytes = 0;
+  int material[kImageClasses];                   // material number and density (as a voxel file would carry it) of every class
+  float density[kImageClasses];
+  unsigned int first[kImageClasses];             // smallest [z][y][x] index of the class, 0xFFFFFFFF: it does not occur
+};
+DeviceModel upload_model(const HostModel& H, int device_id, const DeviceVolumeSource* mapped = nullptr);
 void require(bool ok, int code, const char* msg);
 TrackArgs make_args(const mcgpu_ctx& C, int p);
 void sync_host_voxels(mcgpu_ctx& C);

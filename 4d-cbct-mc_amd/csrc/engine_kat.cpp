@@ -8,11 +8,12 @@ extern "C" {
 
 int mcgpu_microbench(mcgpu_ctx* ctx, int kind, double* out, int n_out) {
   ABI_BEGIN
-  require(ctx && ctx->has_device && out && ((kind == MCGPU_MICROBENCH_VALU_ISSUE && n_out >= 3) || (kind == MCGPU_MICROBENCH_ATOMIC_RATE && n_out >= 1)), -1,
+  require(ctx && ctx->has_device && out && ((kind == MCGPU_MICROBENCH_VALU_ISSUE && n_out >= 3) || ((kind == MCGPU_MICROBENCH_ATOMIC_RATE || kind == MCGPU_MICROBENCH_COPY_RATE) && n_out >= 1)), -1,
           "!!ERROR!! mcgpu_microbench: bad argument");
   HIP_TRY(hipSetDevice(ctx->dev.device_id));
   HIP_TRY(hipDeviceSynchronize());
   if (kind == MCGPU_MICROBENCH_VALU_ISSUE) HIP_TRY(microbench_valu_issue(ctx->dev.num_cus, out, nullptr));
+  else if (kind == MCGPU_MICROBENCH_COPY_RATE) HIP_TRY(microbench_copy_rate(ctx->dev.num_cus, out, nullptr));
   else HIP_TRY(microbench_atomic_rate(out, nullptr));
   return 0;
   ABI_END

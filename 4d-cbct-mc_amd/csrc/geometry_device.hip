@@ -142,6 +142,16 @@ __global__ void init_out_kernel(unsigned int* out) {
 
 }  // namespace
 
+// Classification alone, of a volume that is already on the device (model_device.cpp: a geometry mapped there from a CT image): g.idx,
+// the grids' extents, sub_first, brick_first, rec / rn and out are used; the object box words of `out` mean nothing here (no background yet).
+hipError_t launch_geometry_classify(const GeometryRebuild& g, hipStream_t stream) {
+  hipLaunchKernelGGL(init_out_kernel, dim3(1), dim3(32), 0, stream, g.out);
+  const int nsub = g.sn[0] * g.sn[1] * g.sn[2], nb = g.bn[0] * g.bn[1] * g.bn[2];
+  hipLaunchKernelGGL(classify_sub_kernel, dim3((nsub + 255) / 256), dim3(256), 0, stream, g);
+  hipLaunchKernelGGL(classify_brick_kernel, dim3((nb + 255) / 256), dim3(256), 0, stream, g);
+  return hipGetLastError();
+}
+
 hipError_t launch_geometry_rebuild(const GeometryRebuild& g, int warp_frame, bool allow_exterior, hipStream_t stream, hipEvent_t warp_begin, hipEvent_t warp_end) {
   if (warp_begin) (void)hipEventRecord(warp_begin, stream);
   if (warp_frame >= 0 && g.model.coef) {  // the field of the resident correspondence model, evaluated in the warp (correspondence.hip)

@@ -41,7 +41,8 @@ struct GeometryRebuild {
 // events recorded around the warp kernel alone (null: none)
 hipError_t launch_geometry_rebuild(const GeometryRebuild& g, int warp_frame, bool allow_exterior, hipStream_t stream, hipEvent_t warp_begin = nullptr,
                                    hipEvent_t warp_end = nullptr);
-
+// sub-brick and brick classification (+ tile records when g.rec is set) of the volume g.idx, without warp and without code tables
+hipError_t launch_geometry_classify(const GeometryRebuild& g, hipStream_t stream);
 
 // correspondence.hip: the kernels of the resident correspondence model (cbctmc/registration/correspondence.py:149-226)
 hipError_t launch_warp_index_model(const GeometryRebuild& g, int warp_frame, hipStream_t stream);  // the warp above with the model as field source

@@ -7,6 +7,9 @@
 //           55-60 % lane utilisation, i.e. between the first two.
 //   kind 1  scattered 64-bit atomic adds without return into a detector-sized tally (4 x 1848 x 768 words = 45 MB), the access
 //           pattern of tally_image (MC-GPU_kernel_v1.3.cu:482-604).  out[0] = adds per second, chip-wide.
+//   kind 2  streaming copy: 256 MiB read and 256 MiB written with 16-byte loads and stores, grid-stride.  out[0] = bytes moved (read +
+//           written) per second: what a kernel that touches every byte once can reach (tools/image_map_bench.py prices the CT mapping
+//           kernel against it).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -35,7 +38,39 @@ __global__ void scatter_add_kernel(unsigned long long* img, unsigned int words, 
   }
 }
 
+__global__ __launch_bounds__(256) void copy_kernel(const uint4* __restrict__ in, uint4* __restrict__ out, size_t n16) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) out[i] = in[i];
+}
+
 }  // namespace
+
+// out[0] = bytes read + written per second by a streaming copy
+hipError_t microbench_copy_rate(int num_cus, double* out, hipStream_t stream) {
+  const size_t bytes = 256ull << 20, n16 = bytes / 16;
+  uint4 *src = nullptr, *dst = nullptr;
+  hipError_t e = hipMalloc((void**)&src, bytes);
+  if (e == hipSuccess) e = hipMalloc((void**)&dst, bytes);
+  if (e == hipSuccess) e = hipMemsetAsync(src, 1, bytes, stream);
+  hipEvent_t a = nullptr, b = nullptr;
+  (void)hipEventCreate(&a);
+  (void)hipEventCreate(&b);
+  float best = 0.f;
+  for (int rep = 0; rep < 4 && e == hipSuccess; ++rep) {  // the first pass warms the clocks and maps the pages
+    (void)hipEventRecord(a, stream);
+    hipLaunchKernelGGL(copy_kernel, dim3((unsigned int)(num_cus > 0 ? num_cus : 256) * 16u), dim3(256), 0, stream, src, dst, n16);
+    (void)hipEventRecord(b, stream);
+    e = hipEventSynchronize(b);
+    float ms = 0.f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
+    if (rep > 0 && (best == 0.f || ms < best)) best = ms;
+  }
+  *out = best > 0.f ? 2.0 * (double)bytes / ((double)best * 1e-3) : 0.0;
+  (void)hipEventDestroy(a);
+  (void)hipEventDestroy(b);
+  (void)hipFree(src);
+  (void)hipFree(dst);
+  return e;
+}
 
 // out3 = wave-instructions per ns and SIMD {64 lanes, lanes 0-31, 32 lanes spread}
 hipError_t microbench_valu_issue(int num_cus, double out3[3], hipStream_t stream) {

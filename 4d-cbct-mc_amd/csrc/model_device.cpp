@@ -556,12 +556,9 @@ static void upload_sub_bricks(DeviceModel& D, const std::vector<unsigned short>&
   D.sub = on ? D.put(pack_codes(codes)) : nullptr;
 }
 
-static void upload_tile_records(const HostModel& H, DeviceModel& D, const std::vector<uint8_t>& idx8, const std::vector<unsigned short>& brick_first) {
-  // Tile records (device_model.hpp: TileRecord): the hot set of the voxel gathers is every 64-byte tile of every MIXED brick.
-  // Where that set is far beyond the L2 (4 MB per XCD) -- body-filling tissue volumes: thorax 22 MB -- the launch is bound by
-  // the line fills of those gathers (profiles/r04p_*: ONE more cold line per mixed step doubles the thorax's kernel time, one
-  // more load from the SAME line costs 2 %), and the records shrink the set fourfold.  MCGPU_TILE_RECORDS=0/1 overrides.
-  const int nx = H.voxels.n[0], ny = H.voxels.n[1], nz = H.voxels.n[2], k = D.brick_shift;
+// Whether this model keeps tile records (the comment in upload_tile_records says when they pay); sets D.tiles_in_mixed_bricks and D.rec_n.
+static bool want_tile_records(DeviceModel& D, const std::vector<unsigned short>& brick_first) {
+  const int k = D.brick_shift;
   const size_t nsub = (size_t)D.sub_n[0] * D.sub_n[1] * D.sub_n[2];
   long long hot_tiles = 0;
   for (size_t b = 0; b < nsub; ++b) {
@@ -569,11 +566,20 @@ static void upload_tile_records(const HostModel& H, DeviceModel& D, const std::v
     hot_tiles += brick_first[((size_t)bz * D.brick_n[1] + by) * D.brick_n[0] + bx] == kMixedBrick ? 1 : 0;
   }
   D.tiles_in_mixed_bricks = hot_tiles;
-  const char* knob = knob_str("MCGPU_TILE_RECORDS");
-  const bool on = knob ? atoi(knob) != 0 : hot_tiles * 64 > (8LL << 20);
   D.rec_n[0] = (D.sub_n[0] + 1) >> 1; D.rec_n[1] = (D.sub_n[1] + 1) >> 1; D.rec_n[2] = (D.sub_n[2] + 1) >> 1;
+  const char* knob = knob_str("MCGPU_TILE_RECORDS");
+  return knob ? atoi(knob) != 0 : hot_tiles * 64 > (8LL << 20);
+}
+
+static void upload_tile_records(const HostModel& H, DeviceModel& D, const std::vector<uint8_t>& idx8, const std::vector<unsigned short>& brick_first) {
+  // Tile records (device_model.hpp: TileRecord): the hot set of the voxel gathers is every 64-byte tile of every MIXED brick.
+  // Where that set is far beyond the L2 (4 MB per XCD) -- body-filling tissue volumes: thorax 22 MB -- the launch is bound by
+  // the line fills of those gathers (profiles/r04p_*: ONE more cold line per mixed step doubles the thorax's kernel time, one
+  // more load from the SAME line costs 2 %), and the records shrink the set fourfold.  MCGPU_TILE_RECORDS=0/1 overrides.
+  const int nx = H.voxels.n[0], ny = H.voxels.n[1], nz = H.voxels.n[2];
+  const size_t nsub = (size_t)D.sub_n[0] * D.sub_n[1] * D.sub_n[2];
   D.tile_rec = nullptr;
-  if (!on) return;
+  if (!want_tile_records(D, brick_first)) return;
   std::vector<TileRecord> rec((size_t)D.rec_n[0] * D.rec_n[1] * D.rec_n[2] * 8, TileRecord{0u, 0u, 0ULL});
   for (size_t t = 0; t < nsub; ++t) {
     const unsigned int tx = (unsigned int)(t % D.sub_n[0]), ty = (unsigned int)((t / D.sub_n[0]) % D.sub_n[1]), tz = (unsigned int)(t / ((size_t)D.sub_n[0] * D.sub_n[1]));
@@ -588,7 +594,7 @@ static void upload_tile_records(const HostModel& H, DeviceModel& D, const std::v
 }
 
 // u8 volumes: brick grid, first- and second-level codes, tile records
-static void upload_brick_grids(const HostModel& H, DeviceModel& D, const std::vector<uint8_t>& idx8) {
+static void size_brick_grids(const HostModel& H, DeviceModel& D) {
   const int k = choose_brick_shift(H, D);
   D.brick_shift = k;
   for (int a = 0; a < 3; ++a) {
@@ -597,6 +603,10 @@ static void upload_brick_grids(const HostModel& H, DeviceModel& D, const std::ve
   }
   D.brick_count = D.brick_n[0] * D.brick_n[1] * D.brick_n[2];
   D.brick_bytes = (D.brick_count + 1) / 2;
+}
+
+static void upload_brick_grids(const HostModel& H, DeviceModel& D, const std::vector<uint8_t>& idx8) {
+  size_brick_grids(H, D);
   const BrickClasses c = classify_bricks(H, D, idx8);
   const bool have_background = assign_codes(D, c.brick);
   D.bricks = D.put(brick_codes(H, D, c.brick, have_background));
@@ -631,6 +641,87 @@ static void upload_volume(const HostModel& H, DeviceModel& D) {
   D.vol = D.put(tiled);
   D.vol_bytes = tiled.size();
   upload_brick_grids(H, D, idx8);
+}
+
+// The same u8 volume from classes that are already on the device (mcgpu_set_geometry_image; image_map.hip): what upload_volume builds
+// from the host arrays of the same geometry, without a voxel-sized pass on the host.
+//   palette      : a voxel's (material, density) is its class's, so the first-occurrence order of the [z][y][x] scan (build_palette) is the
+//                  order of the classes' smallest voxel index; classes that share a (material, density) pair share an entry; air at
+//                  0.0013 is appended when absent, as there.
+//   volume       : class -> palette index in one pass (image_map.hip: remap_kernel); the padding of edge tiles was written by the mapping.
+//   brick grids  : sub-brick and brick classification and the tile records come from the kernels of the device-side geometry change
+//                  (geometry_device.hip; the warp tests hold them to the host's); the code assignment, the object region and the packed
+//                  code tables are the host's own functions on the downloaded per-brick results (2 bytes per 64 voxels).
+static void upload_volume_from_device(const HostModel& H, DeviceModel& D, const DeviceVolumeSource& src) {
+  const size_t tiles = (size_t)((H.voxels.n[0] + 3) >> 2) * ((H.voxels.n[1] + 3) >> 2) * ((H.voxels.n[2] + 3) >> 2);
+  if (tiles * 64 >= (1ULL << 31)) throw Error(-2, "!!ERROR!! voxel grid too large for the 32-bit voxel index of the kernel");
+  if (src.bytes != tiles * 64) throw Error(-9, "!!ERROR!! internal: the mapped volume does not have the size of the tiled grid");
+  int order[kImageClasses], present = 0;
+  for (int c = 0; c < kImageClasses; ++c)
+    if (src.first[c] != 0xFFFFFFFFu) order[present++] = c;
+  std::sort(order, order + present, [&](int a, int b) { return src.first[a] < src.first[b]; });
+  std::vector<float> entries;
+  std::vector<uint64_t> keys;
+  auto key_of = [](int material, float density) { uint32_t db; memcpy(&db, &density, 4); return ((uint64_t)material << 32) | db; };
+  auto add = [&](uint64_t key, float density, int mc) {
+    float mcf;
+    memcpy(&mcf, &mc, 4);
+    keys.push_back(key);
+    entries.push_back(density);
+    entries.push_back(mcf);
+  };
+  unsigned char lut[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int i = 0; i < present; ++i) {
+    const int c = order[i];
+    const uint64_t key = key_of(src.material[c], src.density[c]);
+    size_t at = std::find(keys.begin(), keys.end(), key) - keys.begin();
+    if (at == keys.size()) {
+      const int mc = D.compact_of[src.material[c] - 1];
+      if (mc < 0) throw Error(-2, "!!ERROR!! A voxel uses material " + std::to_string(src.material[c]) + " but no data file was given for it.");
+      add(key, src.density[c], mc);
+    }
+    lut[c] = (unsigned char)at;
+  }
+  const uint64_t air = key_of(1, 0.0013f);
+  if (D.compact_of[0] >= 0 && std::find(keys.begin(), keys.end(), air) == keys.end()) add(air, 0.0013f, D.compact_of[0]);
+  D.palette_size = (int)keys.size();
+  D.palette = D.put(entries);
+  D.vol_kind = kVolU8;
+  D.palette_host = entries;
+  D.vol = D.mem.device_bytes(src.bytes);
+  D.vol_bytes = src.bytes;
+  HIP_TRY(launch_image_remap(src.classes_tiled, (unsigned char*)D.vol, src.bytes, lut, nullptr));
+  size_brick_grids(H, D);
+  const size_t nsub = (size_t)D.sub_n[0] * D.sub_n[1] * D.sub_n[2];
+  const int rn[3] = {(D.sub_n[0] + 1) >> 1, (D.sub_n[1] + 1) >> 1, (D.sub_n[2] + 1) >> 1};
+  const size_t nrec = (size_t)rn[0] * rn[1] * rn[2] * 8;
+  unsigned short* sub_first = (unsigned short*)D.mem.device_bytes(nsub * 2);
+  unsigned short* brick_first = (unsigned short*)D.mem.device_bytes((size_t)D.brick_count * 2);
+  unsigned int* out = (unsigned int*)D.mem.device_bytes(32 * 4);
+  TileRecord* rec = (TileRecord*)D.mem.device_bytes(nrec * sizeof(TileRecord));  // kept only where the records pay (want_tile_records)
+  HIP_TRY(hipMemsetAsync(rec, 0, nrec * sizeof(TileRecord), nullptr));            // cubes beyond the grid: zero records, as on the host
+  GeometryRebuild g{};
+  g.nx = H.voxels.n[0]; g.ny = H.voxels.n[1]; g.nz = H.voxels.n[2];
+  g.brick_shift = D.brick_shift;
+  for (int k = 0; k < 3; ++k) { g.bn[k] = D.brick_n[k]; g.sn[k] = D.sub_n[k]; g.rn[k] = rn[k]; }
+  g.idx = (unsigned char*)D.vol;
+  g.sub_first = sub_first; g.brick_first = brick_first; g.rec = rec; g.out = out;
+  g.background = -1;
+  HIP_TRY(launch_geometry_classify(g, nullptr));
+  BrickClasses c;
+  c.brick.resize((size_t)D.brick_count);
+  c.sub.resize(nsub);
+  HIP_TRY(hipMemcpy(c.brick.data(), brick_first, c.brick.size() * 2, hipMemcpyDeviceToHost));  // waits for the kernels
+  HIP_TRY(hipMemcpy(c.sub.data(), sub_first, c.sub.size() * 2, hipMemcpyDeviceToHost));
+  D.mem.free(sub_first);
+  D.mem.free(brick_first);
+  D.mem.free(out);
+  const bool have_background = assign_codes(D, c.brick);
+  D.bricks = D.put(brick_codes(H, D, c.brick, have_background));
+  upload_sub_bricks(D, c.sub);
+  D.tile_rec = nullptr;
+  if (want_tile_records(D, c.brick)) D.tile_rec = rec;
+  else D.mem.free(rec);
 }
 
 // Cross-section records: 8 floats {a, b, pmax, 0} per (compact material, table bin), material-major rows (track_common.inc: table_row)
@@ -892,12 +983,13 @@ static void upload_cold(const HostModel& H, DeviceModel& D) {
 }
 
 // Build the palette-compressed volume and the compact-material tables and upload everything.
-DeviceModel upload_model(const HostModel& H, int device_id) {
+DeviceModel upload_model(const HostModel& H, int device_id, const DeviceVolumeSource* mapped) {
   DeviceModel D{};
   select_device(D, device_id);
   memset(&D.cold_host, 0, sizeof D.cold_host);
   D.nmat = compact_numbering(H, D.compact_of);
-  upload_volume(H, D);
+  if (mapped) upload_volume_from_device(H, D, *mapped);
+  else upload_volume(H, D);
   const std::vector<float> rec = cross_section_records(H, D.compact_of, D.nmat);
   const std::vector<float> tot = total_cross_sections(rec);
   refresh_woodcock(H, D);
@@ -993,6 +1085,8 @@ void sync_host_voxels(mcgpu_ctx& C) {
   DeviceModel& D = C.dev;
   HIP_TRY(hipSetDevice(D.device_id));
   const size_t nvox = H.voxels.count();
+  H.voxels.material.resize(nvox);  // a geometry mapped on the device (mcgpu_set_geometry_image) has had no host arrays yet
+  H.voxels.density.resize(nvox);
   std::vector<unsigned char> idx(nvox);
   {  // the device volume is tiled (device_model.hpp: tiled_voxel)
     std::vector<unsigned char> tiled(D.vol_bytes);
@@ -1059,6 +1153,7 @@ const void* host_table(mcgpu_ctx& C, const std::string& name, size_t& bytes) {
   if (name == "espc") return cache(H.spectrum.espc, sizeof H.spectrum.espc);
   if (name == "espc_cutoff") return cache(H.spectrum.cutoff, sizeof H.spectrum.cutoff);
   if (name == "espc_alias") return cache(H.spectrum.alias, sizeof H.spectrum.alias);
+  if (name == "palette") return cache(C.dev.palette_host.data(), C.dev.palette_host.size() * sizeof(float));  // u8 volumes: {density, bits(compact material)} per entry, in palette order
   if (name == "density_max") return cache(H.voxels.density_max, sizeof H.voxels.density_max);
   if (name == "density_nominal") return cache(H.mat.density_nominal, sizeof H.mat.density_nominal);
   if (name == "voxel_size") return cache(H.voxels.voxel_size, sizeof H.voxels.voxel_size);

@@ -28,7 +28,7 @@ ABI_SYMBOLS = (
     "mcgpu_write_projection", "mcgpu_format_projection", "mcgpu_write_formatted_projection", "mcgpu_dose_info", "mcgpu_dose_read", "mcgpu_dose_clear", "mcgpu_write_dose_report",
     "mcgpu_finalize_projection", "mcgpu_finalize_projection_host", "mcgpu_stack_create", "mcgpu_stack_append", "mcgpu_stack_write_slice", "mcgpu_stack_finish",
     "mcgpu_stack_read", "mcgpu_normalize_stack", "mcgpu_run_scan", "mcgpu_run_scan_multi", "mcgpu_set_projection_angles", "mcgpu_set_geometry_arrays",
-    "mcgpu_warp_volume", "mcgpu_warp_geometry",
+    "mcgpu_warp_volume", "mcgpu_warp_geometry", "mcgpu_map_image", "mcgpu_set_geometry_image",
     "mcgpu_correspondence_set", "mcgpu_correspondence_fit", "mcgpu_correspondence_predict", "mcgpu_warp_geometry_signal", "mcgpu_correspondence_clear",
     "mcgpu_write_voxel_file", "mcgpu_write_voxel_binary", "mcgpu_kat_rng", "mcgpu_kat_rng_streams", "mcgpu_microbench", "mcgpu_kat_math", "mcgpu_kat_expf", "mcgpu_kat_f32", "mcgpu_kat_fast64", "mcgpu_kat_tile_records", "mcgpu_fdk_reconstruct", "mcgpu_forward_project", "mcgpu_forward_project_context", "mcgpu_rooster4d_reconstruct", "mcgpu_rooster4d_stage", "mcgpu_set_fast_schedule", "mcgpu_reload_env_knobs",
     "mcgpu_exchange_shared_bytes", "mcgpu_exchange_card_bytes", "mcgpu_exchange_create", "mcgpu_exchange_card", "mcgpu_exchange_connect",
@@ -53,6 +53,21 @@ class ScanReport(C.Structure):
     _fields_ = [("projections", C.c_int), ("histories_per_projection", C.c_ulonglong), ("seconds_total", C.c_double),
                 ("seconds_kernels", C.c_double), ("seconds_after_last_kernel", C.c_double), ("zero_replacement", C.c_float * 3),
                 ("seconds_writer", C.c_double), ("kernel_ms_min", C.c_double), ("kernel_ms_max", C.c_double)]
+
+
+IMAGE_INT16, IMAGE_FLOAT32 = 0, 1
+
+
+class ImageClass(C.Structure):
+    """mcgpu_image_class (include/mcgpu_amd.h): one entry of the 12-class table of the CT -> material mapping."""
+    _fields_ = [("material", C.c_int), ("density", C.c_float)]
+
+
+class ImageMapReport(C.Structure):
+    """mcgpu_image_map_report (include/mcgpu_amd.h)."""
+    _fields_ = [("struct_size", C.c_uint), ("reserved", C.c_uint), ("count", C.c_ulonglong * 12), ("first", C.c_longlong * 12),
+                ("unmapped", C.c_ulonglong), ("ms_kernel", C.c_double), ("ms_upload", C.c_double), ("ms_install", C.c_double),
+                ("kernel_bytes", C.c_ulonglong)]
 
 
 def knob_table():
@@ -127,6 +142,9 @@ def load_library(path: Optional[os.PathLike] = None):
     lib.mcgpu_set_geometry_arrays.argtypes = [vp, C.POINTER(ci), C.POINTER(C.c_float), vp, vp]
     lib.mcgpu_warp_volume.argtypes = [vp, C.POINTER(ci), vp, vp, vp, ci, C.c_float, vp, vp]
     lib.mcgpu_warp_geometry.argtypes = [vp, vp, ci, ci, C.c_float]
+    lib.mcgpu_map_image.argtypes = [vp, C.POINTER(ci), vp, ci, C.POINTER(vp), C.POINTER(ImageClass), C.POINTER(C.c_float), vp, vp, C.POINTER(ImageMapReport)]
+    lib.mcgpu_set_geometry_image.argtypes = [vp, C.POINTER(ci), C.POINTER(C.c_float), vp, ci, C.POINTER(vp), C.POINTER(ImageClass), C.POINTER(C.c_float), ci,
+                                             C.POINTER(ImageMapReport)]
     lib.mcgpu_correspondence_set.argtypes = [vp, vp, ci, vp, vp, ci, ci]
     lib.mcgpu_correspondence_fit.argtypes = [vp, C.POINTER(vp), ci, vp, vp, ci, ci, vp, vp]
     lib.mcgpu_correspondence_predict.argtypes = [vp, vp, ci, vp]
@@ -566,6 +584,92 @@ class Context:
         nx, ny, nz = mats.shape
         self.set_geometry_arrays((nx, ny, nz), spacing_cm, np.transpose(mats, (2, 1, 0)), np.transpose(dens, (2, 1, 0)))
 
+    # -- CT image + segmentations -> geometry on the device (mcgpu_map_image / mcgpu_set_geometry_image; the rule: DESIGN.md row f8)
+    @staticmethod
+    def _image_arguments(image, segmentations, table, thresholds):
+        """The image as int16 or float32, the eight segmentation pointers in the engine's order, the class table and thresholds."""
+        from . import geometry
+        img = np.ascontiguousarray(geometry.image_values(image))
+        if img.ndim != 3:
+            raise ValueError(f"a 3-D image is needed, got shape {img.shape}")
+        unknown = set(segmentations) - set(geometry.SEGMENTATION_NAMES)
+        if unknown:
+            raise ValueError(f"unknown segmentations {sorted(unknown)}; known: {geometry.SEGMENTATION_NAMES}")
+        keep, ptrs = [img], (C.c_void_p * 8)()
+        for k, name in enumerate(geometry.SEGMENTATION_NAMES):
+            seg = segmentations.get(name)
+            if seg is None:
+                continue
+            a = np.asarray(seg)
+            a = np.ascontiguousarray(a if a.dtype == np.uint8 else a > 0, dtype=np.uint8)
+            if a.shape != img.shape:
+                raise ValueError(f"segmentation '{name}' of shape {a.shape}, the image has {img.shape}")
+            keep.append(a)
+            ptrs[k] = a.ctypes.data
+        entries = geometry.image_class_table() if table is None else list(table)
+        if len(entries) != 12:
+            raise ValueError("the class table has 12 (material number, density) entries")
+        tab = (ImageClass * 12)(*[ImageClass(int(m), float(d)) for m, d in entries])
+        thr = (C.c_float * 3)(*map(float, geometry.IMAGE_THRESHOLDS if thresholds is None else thresholds))
+        return img, ptrs, tab, thr, keep
+
+    @staticmethod
+    def _image_report(r: ImageMapReport) -> dict:
+        return {"count": [int(v) for v in r.count], "first": [int(v) for v in r.first], "unmapped": int(r.unmapped), "ms_kernel": r.ms_kernel,
+                "ms_upload": r.ms_upload, "ms_install": r.ms_install, "kernel_bytes": int(r.kernel_bytes)}
+
+    def map_image(self, image, segmentations: dict, table=None, thresholds=None):
+        """(materials uint8, densities float32) of a CT image and its segmentations {name of geometry.SEGMENTATION_NAMES: array},
+        mapped on the GPU by the rule of `geometry.MaterialMapperPipeline.execute`, in the image's own layout (any 3-D shape).
+        Raises ValueError with the number of unmapped voxels, like the host pipeline.  `self.last_image_report` has the counts."""
+        img, ptrs, tab, thr, keep = self._image_arguments(image, segmentations, table, thresholds)
+        mats, dens = np.empty(img.shape, dtype=np.uint8), np.empty(img.shape, dtype=np.float32)
+        rep = ImageMapReport(struct_size=C.sizeof(ImageMapReport))
+        _check(self.lib.mcgpu_map_image(self.h, (C.c_int * 3)(*img.shape[::-1]), img.ctypes.data, IMAGE_FLOAT32 if img.dtype == np.float32 else IMAGE_INT16,
+                                        ptrs, tab, thr, mats.ctypes.data, dens.ctypes.data, C.byref(rep)))
+        self.last_image_report = self._image_report(rep)
+        if rep.unmapped:
+            raise ValueError(f"{int(rep.unmapped)} voxels are unmapped: no line of the mapping touches them (a body segmentation is missing)")
+        return mats, dens
+
+    def set_geometry_image(self, image, segmentations: dict, frame: str = "geometry", image_spacing=(1.0, 1.0, 1.0), table=None, thresholds=None) -> dict:
+        """The context's geometry := the mapped CT image, built on the device (mcgpu_set_geometry_image): the context
+        `set_geometry(MCGeometry(*MaterialMapperPipeline.execute(image), image_spacing))` gives, without the host passes.
+        frame "geometry": arrays [gx, gy, gz] and `image_spacing` (mm) as an `MCGeometry` has them (the rot90 of the voxel file
+        happens on the device); frame "engine": arrays [nz, ny, nx], spacing (x, y, z).  Returns the report (counts per class,
+        kernel and host times).  EngineError(-2): unmapped voxels or a class without material file; the context is unchanged."""
+        img, ptrs, tab, thr, keep = self._image_arguments(image, segmentations, table, thresholds)
+        sp = [float(v) for v in image_spacing]
+        if frame == "geometry":
+            gx, gy, gz = img.shape
+            n, spacing_cm = (gy, gx, gz), (sp[1] / 10.0, sp[0] / 10.0, sp[2] / 10.0)
+        elif frame == "engine":
+            nz, ny, nx = img.shape
+            n, spacing_cm = (nx, ny, nz), (sp[0] / 10.0, sp[1] / 10.0, sp[2] / 10.0)
+        else:
+            raise ValueError(f"frame '{frame}': 'geometry' or 'engine'")
+        rep = ImageMapReport(struct_size=C.sizeof(ImageMapReport))
+        rc = self.lib.mcgpu_set_geometry_image(self.h, (C.c_int * 3)(*n), (C.c_float * 3)(*spacing_cm), img.ctypes.data,
+                                               IMAGE_FLOAT32 if img.dtype == np.float32 else IMAGE_INT16, ptrs, tab, thr, 1 if frame == "geometry" else 0,
+                                               C.byref(rep))
+        self.last_image_report = self._image_report(rep)
+        _check(rc)
+        self._correspondence_model = None  # the device model is built anew
+        return self.last_image_report
+
+    def set_geometry_from_image(self, image_filepath, segmenter=None, segmenter_kwargs=None, body_segmentation_filepath=None,
+                                bone_segmentation_filepath=None, muscle_segmentation_filepath=None, fat_segmentation_filepath=None,
+                                liver_segmentation_filepath=None, stomach_segmentation_filepath=None, lung_segmentation_filepath=None,
+                                lung_vessel_segmentation_filepath=None, image_spacing=None) -> dict:
+        """`set_geometry(MCGeometry.from_image(...))` with the same arguments, mapped and installed on the device."""
+        from . import geometry
+        image, spacing, segmentations = geometry.load_image_and_segmentations(
+            image_filepath, segmenter=segmenter, image_spacing=image_spacing, body=body_segmentation_filepath,
+            bone=bone_segmentation_filepath, muscle=muscle_segmentation_filepath, fat=fat_segmentation_filepath,
+            liver=liver_segmentation_filepath, stomach=stomach_segmentation_filepath, lung=lung_segmentation_filepath,
+            lung_vessel=lung_vessel_segmentation_filepath)
+        return self.set_geometry_image(image, segmentations, frame="geometry", image_spacing=spacing)
+
     def warp_geometry(self, displacement: np.ndarray, frame: str = "geometry", default_material: int = 1, default_density: float = 0.0013):
         """The context's geometry := warp(base geometry, displacement) entirely on the device (mcgpu_warp_geometry).
         frame "geometry": displacement [3, gx, gy, gz] in the frame of the MCGeometry arrays (what the reference's
@@ -754,9 +858,10 @@ class Context:
 
     def microbench(self, kind: str):
         """Hardware ceilings measured on this context's device (include/mcgpu_amd.h: mcgpu_microbench): kind "valu_issue" ->
-        wave-instructions per ns and SIMD {64 lanes, lanes 0-31, 32 lanes spread}; "atomic_rate" -> scattered 64-bit adds per second."""
+        wave-instructions per ns and SIMD {64 lanes, lanes 0-31, 32 lanes spread}; "atomic_rate" -> scattered 64-bit adds per second;
+        "copy_rate" -> bytes read + written per second by a streaming copy."""
         out = (C.c_double * 3)()
-        _check(self.lib.mcgpu_microbench(self.h, {"valu_issue": 0, "atomic_rate": 1}[kind], out, 3))
+        _check(self.lib.mcgpu_microbench(self.h, {"valu_issue": 0, "atomic_rate": 1, "copy_rate": 2}[kind], out, 3))
         return [float(v) for v in out] if kind == "valu_issue" else float(out[0])
 
     # -- known-answer hooks

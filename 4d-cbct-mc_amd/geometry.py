@@ -5,9 +5,13 @@ Host-side mirror of the parts of `cbctmc/mc/geometry.py` the engine path needs:
 the x/y plane and swapped x/y spacing before writing, x fastest), `MCAirGeometry` (geo.py:626-639),
 `MCCatPhan604Geometry` (recipe geo.py:902-1068), `pad_to_shape` (geo.py:340-374), `copy` / `warp`
 (geo.py:375-439; the warp runs on the GPU through the engine), `MCCIRSPhantomGeometry` (geo.py:642-878:
-bundled base geometry + tumour / line-pair inserts).  The CT -> material mapping pipeline of the reference
-(`from_image`) needs its segmentation networks and is out of scope.  `MCThoraxLikeGeometry` is NOT a reference
-class: it is the synthetic patient-like workload of SURVEY.md 8d (input 3) used by tests and benchmarks.
+bundled base geometry + tumour / line-pair inserts), and the CT -> material mapping of `MCGeometry.from_image`
+(geo.py:495-577) with its mapper classes and `MaterialMapperPipeline` (geo.py:35-309), written against the rule
+stated in DESIGN.md row f8 / csrc/image_map.hpp: segmentations come as arrays or uncompressed `.mha` files.  Only
+the reference's segmentation NETWORK (`segmenter=`) and image resampling (SimpleITK) are out of scope.  The pipeline
+here is the host statement of the rule; `engine.Context.map_image` / `set_geometry_image` run it on the GPU.
+`MCThoraxLikeGeometry` is NOT a reference class: it is the synthetic patient-like workload of SURVEY.md 8d (input 3)
+used by tests and benchmarks.
 """
 from __future__ import annotations
 
@@ -68,6 +72,27 @@ class MCGeometry:
                                           material_number("air"), MATERIALS_125KEV["air"])
         return MCGeometry(np.transpose(m, (2, 1, 0)), np.transpose(d, (2, 1, 0)), self.image_spacing)
 
+    @classmethod
+    def from_image(cls, image_filepath, segmenter=None, segmenter_kwargs=None, body_segmentation_filepath=None,
+                   bone_segmentation_filepath=None, muscle_segmentation_filepath=None, fat_segmentation_filepath=None,
+                   liver_segmentation_filepath=None, stomach_segmentation_filepath=None, lung_segmentation_filepath=None,
+                   lung_vessel_segmentation_filepath=None, image_spacing=None, engine_context=None) -> "MCGeometry":
+        """A CT image (uncompressed `.mha`, HU) and segmentation files -> geometry (`MCGeometry.from_image`, geo.py:495-577).
+        With `engine_context` (an open `engine.Context` with a device) the mapping runs on its GPU (`Context.map_image`), else
+        in numpy (`MaterialMapperPipeline.execute`); both give the same arrays.  A `segmenter` and an `image_spacing` that
+        differs from the file's raise NotImplementedError: the network and SimpleITK's resampler are not part of this package."""
+        image, spacing, segmentations = load_image_and_segmentations(
+            image_filepath, segmenter=segmenter, image_spacing=image_spacing, body=body_segmentation_filepath,
+            bone=bone_segmentation_filepath, muscle=muscle_segmentation_filepath, fat=fat_segmentation_filepath,
+            liver=liver_segmentation_filepath, stomach=stomach_segmentation_filepath, lung=lung_segmentation_filepath,
+            lung_vessel=lung_vessel_segmentation_filepath)
+        if engine_context is not None:
+            materials, densities = engine_context.map_image(image, segmentations)
+        else:
+            pipeline = MaterialMapperPipeline.create_default_pipeline(**{f"{k}_segmentation": v for k, v in segmentations.items()})
+            materials, densities = pipeline.execute(image)
+        return cls(materials, densities, spacing)
+
     def mcgpu_arrays(self):
         """(materials, densities, spacing_cm) exactly as written to the voxel file (x fastest)."""
         mats = np.rot90(self.materials, k=3, axes=(0, 1))
@@ -88,6 +113,224 @@ class MCGeometry:
             nx, ny, nz = mats.shape
             engine.write_voxel_binary(engine.voxel_sidecar_path(filepath), (nx, ny, nz), spacing_cm,
                                       np.transpose(mats, (2, 1, 0)), np.transpose(dens, (2, 1, 0)))
+
+
+# ---- CT image + segmentations -> (material, density): the rule of DESIGN.md row f8 (csrc/image_map.hpp), on the host
+# classes in the order of the engine's 12-entry table; segmentations in the order of its eight pointers
+IMAGE_CLASSES = ("air", "soft_tissue", "red_marrow", "bone_020", "bone_050", "bone_100", "lung", "liver", "stomach_intestines",
+                 "muscle_tissue", "adipose", "blood")
+SEGMENTATION_NAMES = ("body", "bone", "lung", "liver", "stomach", "muscle", "fat", "lung_vessel")
+IMAGE_THRESHOLDS = (150.0, 300.0, -900.0)  # red_marrow | bone_020 | bone_050 (HU), and the air line's
+UNMAPPED_CLASS = 255
+
+
+def image_class_table():
+    """[(material number, density)] of IMAGE_CLASSES: what the mappers below write and what the engine's table takes."""
+    return [(material_number(c), float(MATERIALS_125KEV[c])) for c in IMAGE_CLASSES]
+
+
+def image_values(image) -> np.ndarray:
+    """The image as the rule compares it: int16 stays (every value is exact in float32), anything else becomes float32."""
+    a = np.asarray(image)
+    return a if a.dtype == np.int16 else a.astype(np.float32, copy=False)
+
+
+def _inside(segmentation) -> np.ndarray:
+    return np.asarray(segmentation) > 0
+
+
+def bone_outline(mask: np.ndarray) -> np.ndarray:
+    """Voxels of `mask` that its erosion by the 6-neighbour cross removes, outside the volume counting as background."""
+    from scipy import ndimage
+    return mask & ~ndimage.binary_erosion(mask)
+
+
+def classify_image(image, segmentations: Dict[str, np.ndarray], thresholds=IMAGE_THRESHOLDS) -> np.ndarray:
+    """The CLOSED FORM of the rule: index into IMAGE_CLASSES per voxel (UNMAPPED_CLASS where no line applies), decided
+    from the last line down instead of by overwriting.  `segmentations`: name of SEGMENTATION_NAMES -> array; missing or
+    None = that line is skipped.  `MaterialMapperPipeline.execute` is the sequential statement of the same rule."""
+    v = image_values(image).astype(np.float32)
+    t0, t1, t2 = (np.float32(t) for t in thresholds)
+    s = {k: (_inside(segmentations[k]) if segmentations.get(k) is not None else None) for k in SEGMENTATION_NAMES}
+    cls = np.full(v.shape, UNMAPPED_CLASS, dtype=np.uint8)
+    todo = np.ones(v.shape, dtype=bool)
+
+    def decide(where, index):
+        nonlocal todo
+        hit = todo & where
+        cls[hit] = index
+        todo &= ~hit
+
+    c = IMAGE_CLASSES.index
+    if s["lung_vessel"] is not None:
+        decide(s["lung_vessel"], c("blood"))
+    if s["body"] is not None:
+        decide(s["body"] & (v < t2), c("air"))
+    for name, ident in (("fat", "adipose"), ("muscle", "muscle_tissue"), ("stomach", "stomach_intestines"), ("liver", "liver"), ("lung", "lung")):
+        if s[name] is not None:
+            decide(s[name], c(ident))
+    if s["bone"] is not None:
+        bone = s["bone"]
+        decide(bone & (v >= t1) & bone_outline(bone), c("bone_100"))
+        decide(bone & (v >= t1), c("bone_050"))
+        decide(bone & (t0 <= v) & (v < t1), c("bone_020"))
+        decide(bone & (v < t0), c("red_marrow"))
+    if s["body"] is not None:
+        decide(s["body"], c("soft_tissue"))
+        decide(~s["body"], c("air"))
+    return cls
+
+
+class BaseMaterialMapper:
+    """One line of the rule: `assignments(image, inside)` -> [(mask, material identifier)], written in that order."""
+
+    def assignments(self, image: np.ndarray, inside: np.ndarray):
+        raise NotImplementedError
+
+    def map(self, image, segmentation, materials_output=None, densities_output=None):
+        inside = _inside(segmentation)
+        materials = np.zeros(inside.shape, dtype=np.uint8) if materials_output is None else materials_output
+        densities = np.zeros(inside.shape, dtype=np.float32) if densities_output is None else densities_output
+        for mask, ident in self.assignments(image_values(image), inside):
+            materials[mask] = material_number(ident)
+            densities[mask] = np.float32(MATERIALS_125KEV[ident])
+        return materials, densities
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}()"
+
+
+class SingleMaterialMapper(BaseMaterialMapper):
+    def __init__(self, target_material: str):
+        self.target_material = target_material
+
+    def assignments(self, image, inside):
+        return [(inside, self.target_material)]
+
+
+class BodyROIMaterialMapper(BaseMaterialMapper):
+    def assignments(self, image, inside):
+        return [(inside, "soft_tissue"), (~inside, "air")]
+
+
+class BoneMaterialMapper(BaseMaterialMapper):
+    def __init__(self, marrow_below=IMAGE_THRESHOLDS[0], dense_from=IMAGE_THRESHOLDS[1]):
+        self.marrow_below, self.dense_from = np.float32(marrow_below), np.float32(dense_from)
+
+    def assignments(self, image, inside):
+        dense = inside & (image >= self.dense_from)
+        return [(inside & (image < self.marrow_below), "red_marrow"),
+                (inside & (self.marrow_below <= image) & (image < self.dense_from), "bone_020"),
+                (dense, "bone_050"), (dense & bone_outline(inside), "bone_100")]
+
+
+class AirMaterialMapper(BaseMaterialMapper):
+    def __init__(self, below=IMAGE_THRESHOLDS[2]):
+        self.below = np.float32(below)
+
+    def assignments(self, image, inside):
+        return [(inside & (image < self.below), "air")]
+
+
+class LungMaterialMapper(SingleMaterialMapper):
+    def __init__(self, use_air: bool = False):
+        super().__init__("air" if use_air else "lung")
+
+
+class LungVesselsMaterialMapper(SingleMaterialMapper):
+    def __init__(self):
+        super().__init__("blood")
+
+
+class LiverMaterialMapper(SingleMaterialMapper):
+    def __init__(self):
+        super().__init__("liver")
+
+
+class StomachMaterialMapper(SingleMaterialMapper):
+    def __init__(self):
+        super().__init__("stomach_intestines")
+
+
+class MuscleMaterialMapper(SingleMaterialMapper):
+    def __init__(self):
+        super().__init__("muscle_tissue")
+
+
+class FatMaterialMapper(SingleMaterialMapper):
+    def __init__(self):
+        super().__init__("adipose")
+
+
+def read_segmentation(path) -> np.ndarray:
+    """uint8 [x, y, z] of an uncompressed `.mha` segmentation (file order is x fastest)."""
+    from .reconstruction import read_mha
+    data, _, _ = read_mha(path)
+    return np.ascontiguousarray(np.asarray(data).swapaxes(0, 2), dtype=np.uint8)
+
+
+class MaterialMapperPipeline(list):
+    """[(mapper, segmentation array | file path | None)] executed in order, later entries overwriting earlier ones
+    (`MaterialMapperPipeline`, geo.py:237-309).  An entry without segmentation is skipped."""
+
+    def execute(self, image, image_spacing=None):
+        """(materials uint8, densities float32) of `image`, in its own layout.  Raises ValueError with the number of voxels
+        that no mapper touched (the reference would hand material 0 at density 0 on to the voxel file writer, which refuses it)."""
+        if image_spacing is not None:
+            raise NotImplementedError("resampling the segmentations to another spacing needs SimpleITK (the reference's resample_image_spacing, "
+                                      "cbctmc/utils.py:76-102); resample them first")
+        materials = densities = None
+        for mapper, segmentation in self:
+            if segmentation is None:
+                continue
+            if isinstance(segmentation, (str, Path)):
+                segmentation = read_segmentation(segmentation)
+            elif not isinstance(segmentation, np.ndarray):
+                raise ValueError("a segmentation is an array, a file path or None")
+            materials, densities = mapper.map(image, segmentation, materials, densities)
+        unmapped = int(np.asarray(image).size) if materials is None else int(np.count_nonzero(materials == 0))
+        if unmapped:
+            raise ValueError(f"{unmapped} voxels are unmapped: no mapper touches them (a body segmentation is missing)")
+        return materials, densities
+
+    @classmethod
+    def create_default_pipeline(cls, body_segmentation=None, bone_segmentation=None, muscle_segmentation=None, fat_segmentation=None,
+                                liver_segmentation=None, stomach_segmentation=None, lung_segmentation=None, lung_vessel_segmentation=None):
+        return cls([(BodyROIMaterialMapper(), body_segmentation), (BoneMaterialMapper(), bone_segmentation),
+                    (LungMaterialMapper(use_air=False), lung_segmentation), (LiverMaterialMapper(), liver_segmentation),
+                    (StomachMaterialMapper(), stomach_segmentation), (MuscleMaterialMapper(), muscle_segmentation),
+                    (FatMaterialMapper(), fat_segmentation), (AirMaterialMapper(), body_segmentation),
+                    (LungVesselsMaterialMapper(), lung_vessel_segmentation)])
+
+
+def load_image_and_segmentations(image_filepath, segmenter=None, image_spacing=None, **segmentation_filepaths):
+    """(image [x, y, z], spacing mm, {name: uint8 [x, y, z]}) of `.mha` files, as `from_image` takes them.  Keywords: the names of
+    SEGMENTATION_NAMES -> file path or None."""
+    from .reconstruction import read_mha
+    if segmenter is not None:
+        raise NotImplementedError("the segmentation network (cbctmc.segmentation.segmenter.MCSegmenter) is not part of this package: "
+                                  "pass the segmentations as files")
+    data, spacing, _ = read_mha(image_filepath)
+    if data.ndim != 3:
+        raise ValueError(f"{image_filepath}: a 3-D image is needed")
+    spacing = tuple(float(v) for v in spacing)
+    if image_spacing is not None and not np.allclose(np.asarray(image_spacing, dtype=np.float64), spacing, rtol=0.0, atol=1e-9):
+        raise NotImplementedError(f"resampling from spacing {spacing} to {tuple(image_spacing)} needs SimpleITK (the reference's "
+                                  "resample_image_spacing, cbctmc/utils.py:76-102); resample the files first")
+    image = np.ascontiguousarray(np.asarray(data).swapaxes(0, 2))
+    unknown = set(segmentation_filepaths) - set(SEGMENTATION_NAMES)
+    if unknown:
+        raise TypeError(f"unknown segmentations {sorted(unknown)}")
+    segmentations = {}
+    for name in SEGMENTATION_NAMES:
+        path = segmentation_filepaths.get(name)
+        if path is None:
+            continue
+        seg = read_segmentation(path)
+        if seg.shape != image.shape:
+            raise ValueError(f"{path}: shape {seg.shape} differs from the image's {image.shape}")
+        segmentations[name] = seg
+    return image, spacing, segmentations
 
 
 def write_vox(filepath, materials_xyz: np.ndarray, densities_xyz: np.ndarray, spacing_cm, compress=True, engine=None):

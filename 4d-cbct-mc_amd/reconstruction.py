@@ -149,9 +149,13 @@ def fdk(projections: np.ndarray, geometry: CircularGeometry, pixel_spacing: Tupl
     return vol, {"ms_filter": rep.ms_filter, "ms_backproject": rep.ms_backproject}
 
 
+_MHA_ELEMENT_TYPES = {"MET_FLOAT": "<f4", "MET_SHORT": "<i2", "MET_UCHAR": "u1"}
+
+
 def read_mha(path):
-    """(array [n2, n1, n0] float32, spacing, origin) of an uncompressed MetaImage written by this engine or SimpleITK; a 4-D
-    image gives [n3, n2, n1, n0] and 4 spacings and offsets."""
+    """(array [n2, n1, n0], spacing, origin) of an uncompressed MetaImage written by this engine or SimpleITK; a 4-D
+    image gives [n3, n2, n1, n0] and 4 spacings and offsets.  MET_FLOAT gives float32 (stacks, reconstructions), MET_SHORT int16
+    (CT images) and MET_UCHAR uint8 (segmentations)."""
     raw = Path(path).read_bytes()
     head_end = raw.index(b"ElementDataFile")
     head_end = raw.index(b"\n", head_end) + 1
@@ -160,27 +164,29 @@ def read_mha(path):
         if "=" in line:
             k, v = line.split("=", 1)
             meta[k.strip()] = v.strip()
-    if meta.get("ElementDataFile") != "LOCAL" or meta.get("ElementType") != "MET_FLOAT" or meta.get("CompressedData", "False") == "True":
-        raise ValueError(f"{path}: only uncompressed MET_FLOAT MetaImages with local data are supported")
+    if (meta.get("ElementDataFile") != "LOCAL" or meta.get("ElementType") not in _MHA_ELEMENT_TYPES or meta.get("CompressedData", "False") == "True"
+            or meta.get("BinaryDataByteOrderMSB", "False") == "True"):
+        raise ValueError(f"{path}: only uncompressed little-endian MET_FLOAT / MET_SHORT / MET_UCHAR MetaImages with local data are supported")
     dims = [int(v) for v in meta["DimSize"].split()]
     spacing = [float(v) for v in meta.get("ElementSpacing", "1 1 1").split()]
     origin = [float(v) for v in meta.get("Offset", meta.get("Origin", "0 0 0")).split()]
-    data = np.frombuffer(raw, dtype="<f4", offset=head_end, count=int(np.prod(dims))).reshape(dims[::-1])
+    data = np.frombuffer(raw, dtype=_MHA_ELEMENT_TYPES[meta["ElementType"]], offset=head_end, count=int(np.prod(dims))).reshape(dims[::-1])
     return data, spacing, origin
 
 
-def write_mha(path, volume: np.ndarray, spacing, origin) -> Path:
+def write_mha(path, volume: np.ndarray, spacing, origin, element_type: str = "MET_FLOAT") -> Path:
     """float32 [n2, n1, n0] -> uncompressed MetaImage (what SimpleITK.WriteImage produces for such an image).  A 4-D array
-    [n3, n2, n1, n0] (e.g. the frames of reconstruct_4d) is written with NDims = 4; spacing and origin then have 4 entries."""
+    [n3, n2, n1, n0] (e.g. the frames of reconstruct_4d) is written with NDims = 4; spacing and origin then have 4 entries.
+    element_type "MET_SHORT" / "MET_UCHAR" writes int16 / uint8 elements (CT images, segmentations)."""
     path = Path(path)
-    v = np.ascontiguousarray(volume, dtype="<f4")
+    v = np.ascontiguousarray(volume, dtype=_MHA_ELEMENT_TYPES[element_type])
     d = v.shape[::-1]
     if v.ndim == 3:
         head = ("ObjectType = Image\nNDims = 3\nBinaryData = True\nBinaryDataByteOrderMSB = False\nCompressedData = False\n"
                 "TransformMatrix = 1 0 0 0 1 0 0 0 1\n"
                 f"Offset = {origin[0]:.15g} {origin[1]:.15g} {origin[2]:.15g}\nCenterOfRotation = 0 0 0\nAnatomicalOrientation = RAI\n"
                 f"ElementSpacing = {spacing[0]:.15g} {spacing[1]:.15g} {spacing[2]:.15g}\nDimSize = {d[0]} {d[1]} {d[2]}\n"
-                "ElementType = MET_FLOAT\nElementDataFile = LOCAL\n")
+                f"ElementType = {element_type}\nElementDataFile = LOCAL\n")
     elif v.ndim == 4:
         if len(spacing) != 4 or len(origin) != 4:
             raise ValueError("a 4-D MetaImage needs 4 spacings and 4 offsets")
@@ -188,7 +194,7 @@ def write_mha(path, volume: np.ndarray, spacing, origin) -> Path:
         head = ("ObjectType = Image\nNDims = 4\nBinaryData = True\nBinaryDataByteOrderMSB = False\nCompressedData = False\n"
                 f"TransformMatrix = {eye}\nOffset = {' '.join(f'{float(o):.15g}' for o in origin)}\nCenterOfRotation = 0 0 0 0\n"
                 f"ElementSpacing = {' '.join(f'{float(x):.15g}' for x in spacing)}\nDimSize = {' '.join(str(n) for n in d)}\n"
-                "ElementType = MET_FLOAT\nElementDataFile = LOCAL\n")
+                f"ElementType = {element_type}\nElementDataFile = LOCAL\n")
     else:
         raise ValueError(f"write_mha: {v.ndim}-D arrays are not supported (3 or 4)")
     with open(path, "wb") as f:

@@ -19,6 +19,8 @@ import tempfile
 from pathlib import Path
 from typing import List
 
+import numpy as np
+
 from . import geometry, materials, simulation
 
 ASSETS = Path(__file__).resolve().parent / "assets"
@@ -87,3 +89,44 @@ def build_workload(workdir, workload: str, histories: int, n_proj: int, engine=N
     sim = simulation.MCSimulation(workload_geometry(workload, n_vox), material_files(), spectrum_file(), n_histories=histories,
                                   n_projections=n_proj, angle_between_projections=360.0 / n_proj)
     return sim.prepare_simulation(Path(workdir), compress_geometry=False, engine=engine, binary_sidecar=binary_sidecar)
+
+
+# nominal CT number (HU) of the materials the synthetic phantoms use, for synthetic_ct
+_NOMINAL_HU = {"air": -1000.0, "lung": -820.0, "adipose": -100.0, "soft_tissue": 40.0, "h2o": 0.0, "muscle_tissue": 50.0, "liver": 60.0,
+               "stomach_intestines": 30.0, "blood": 45.0, "glands_others": 35.0, "cartilage": 120.0, "red_marrow": 90.0, "bone_020": 230.0,
+               "bone_050": 420.0, "bone_100": 700.0}
+
+
+def synthetic_ct(geo, seed: int = 7, dtype=np.int16):
+    """(image [x, y, z] HU, {segmentation name: uint8 [x, y, z]}) that a segmented CT of the phantom `geo` (an `MCThoraxLikeGeometry` or
+    any geometry of the materials above) could look like: every material at its nominal CT number plus seeded noise -- 25 HU in
+    tissue, 70 HU in lung (a share of the lung voxels falls below the -900 HU of the air line) and 120 HU in bone (voxels of one bone
+    land on both sides of 150 and 300 HU) -- and the eight segmentations of `geometry.SEGMENTATION_NAMES` from the material classes:
+    body = everything but air with its holes filled, bone = marrow + the three bone classes + cartilage, lung = lung + the air
+    inside the body, the rest by material.  The input of the mapping's tests and of tools/image_map_bench.py; the mapped result
+    is NOT `geo` again (the HU noise re-draws the bone classes), it is whatever the rule makes of these arrays.
+    dtype float32 adds a fractional part to every value."""
+    from scipy import ndimage
+    num = materials.material_number
+    mats = geo.materials
+    rng = np.random.default_rng(seed)
+    hu = np.zeros(mats.shape, dtype=np.float32)
+    sigma = np.full(mats.shape, 25.0, dtype=np.float32)
+    for ident, value in _NOMINAL_HU.items():
+        m = mats == num(ident)
+        hu[m] = value
+        if ident == "lung":
+            sigma[m] = 70.0
+        elif ident in ("red_marrow", "bone_020", "bone_050", "bone_100", "cartilage"):
+            sigma[m] = 120.0
+        elif ident == "air":
+            sigma[m] = 5.0
+    hu += sigma * rng.standard_normal(mats.shape, dtype=np.float32)
+    is_ = lambda *idents: np.isin(mats, [num(i) for i in idents])
+    not_air = ~is_("air")
+    body = np.stack([ndimage.binary_fill_holes(not_air[:, :, k]) for k in range(mats.shape[2])], axis=2)
+    seg = {"body": body, "bone": is_("red_marrow", "bone_020", "bone_050", "bone_100", "cartilage"), "lung": is_("lung") | (body & ~not_air),
+           "liver": is_("liver"), "stomach": is_("stomach_intestines"), "muscle": is_("muscle_tissue"), "fat": is_("adipose"),
+           "lung_vessel": is_("blood")}
+    image = np.rint(hu).astype(np.int16) if np.dtype(dtype) == np.int16 else (hu + np.float32(0.25)).astype(np.float32)
+    return image, {k: v.astype(np.uint8) for k, v in seg.items()}

@@ -77,7 +77,8 @@ int mcgpu_config_f64(const mcgpu_ctx *ctx, const char *key, double *value);
  * reference/oracle: "source_data" (80 B x nproj), "detector_data" (100 B x nproj), "voxel_mat_dens"
  * (float2 x nvox, built on demand), "mfp_woodcock", "mfp_a", "mfp_b", "xco","pco","aco","bco","pmax",
  * "itlco","ituco","fco","uico","fj0","noscco","espc","espc_cutoff","espc_alias","density_max",
- * "density_nominal","voxel_size","inv_voxel_size","size_bbox".  The pointer stays valid until destroy. */
+ * "density_nominal","voxel_size","inv_voxel_size","size_bbox"; of the device model: "palette" (float2 {density, bits(compact material
+ * index)} per entry of a u8 palette volume, in palette order).  The pointer stays valid until destroy. */
 int mcgpu_host_table(mcgpu_ctx *ctx, const char *name, const void **data, size_t *bytes);
 
 /* Output file name of projection p: "<base>_%010.6fdeg" with the float32 angle (MC-GPU_v1.3.cu:2787-2803). */
@@ -333,7 +334,7 @@ int mcgpu_warp_geometry(mcgpu_ctx *ctx, const float *displacement, int frame, in
  * context's voxel count.  The field of a signal is float(double(mean[e]) + (coefficients[e][0] d[0] + coefficients[e][1] d[1] + ...)),
  * d = s - mean_signal, summed left to right in double without fused multiply-add.  Device memory: 3N (4 or 8) + 3N K 8 bytes,
  * owned by the context's device model: released by _clear, by a later _set / _fit (also one that fails: then no model is
- * resident), by mcgpu_set_geometry_arrays and with the context; a clone does not inherit it.
+ * resident), by mcgpu_set_geometry_arrays / mcgpu_set_geometry_image and with the context; a clone does not inherit it.
  * Return codes: 0; -1 bad argument (also: K is not the resident model's); -5 take the host route (predict on the host +
  * mcgpu_warp_geometry, or fit on the host): K > 4, T > 64, no model resident, and for _warp_geometry_signal whatever makes
  * mcgpu_warp_geometry return -5 (no palette volume, default not in the palette).
@@ -370,6 +371,56 @@ int mcgpu_set_geometry_arrays(mcgpu_ctx *ctx, const int n[3], const float spacin
 int mcgpu_warp_volume(mcgpu_ctx *ctx, const int n[3], const uint8_t *material, const float *density, const float *displacement,
                       int default_material, float default_density, uint8_t *material_out, float *density_out);
 
+/* ---- Row f8: a CT image and its tissue segmentations -> geometry, on the device (csrc/image_map.hip).  Replaces the reference's
+ * MaterialMapperPipeline.create_default_pipeline / execute (cbctmc/mc/geometry.py:237-309; the mappers :35-234) as MCGeometry.from_image
+ * calls it (:495-577), and -- for mcgpu_set_geometry_image -- the voxel file and engine start that follow it there.
+ * The rule (csrc/image_map.hpp states it in full): classes air, soft_tissue, red_marrow, bone_020, bone_050, bone_100, lung, liver,
+ * stomach_intestines, muscle_tissue, adipose, blood = table[0..11]; segmentations[0..7] = body, bone, lung, liver, stomach, muscle, fat,
+ * lung vessels (uint8, "> 0" is inside; NULL: that line is skipped); v = image value as float32; thresholds = {150, 300, -900} in the
+ * reference.  Later lines overwrite: body -> soft_tissue else air | bone: v < t0 red_marrow, t0 <= v < t1 bone_020, v >= t1 bone_050 or
+ * bone_100 on the one-voxel outline of the bone mask (6-neighbour erosion, outside the volume = background) | lung | liver | stomach |
+ * muscle | fat | body && v < t2 -> air | vessels -> blood.  A NaN fails every comparison.  A voxel no line touches is unmapped.
+ * image_dtype: MCGPU_IMAGE_INT16 or MCGPU_IMAGE_FLOAT32.  The C side knows no material: numbers and densities come from `table`.
+ * mcgpu_map_image: the mapping alone on the context's GPU (sibling of mcgpu_warp_volume): arrays [n[2]][n[1]][n[0]] in, material /
+ *   density out in the same layout with the table's densities as they are; an unmapped voxel gets (0, 0) and is counted in the report.
+ * mcgpu_set_geometry_image: replace the context's geometry by the mapped volume; the context is the one mcgpu_set_geometry_arrays
+ *   builds from the host-mapped arrays (palette in first-occurrence order of the [z][y][x] scan with air at 0.0013 appended when absent,
+ *   table densities through "%.6f" once each, density_max from the classes that occur, material tables and Woodcock majorant rebuilt)
+ *   without a voxel-sized pass on the host: the volume, both brick levels and the tile records are built on the device, the host voxel
+ *   arrays are downloaded only when someone asks for them.  n / spacing_cm: the ENGINE's grid (nx, ny, nz).  frame 0: inputs
+ *   [nz][ny][nx]; frame 1: inputs [gx][gy][gz] = [ny][nx][nz] in the frame of the MCGeometry arrays, engine voxel (x, y, z) = input
+ *   voxel (ny - 1 - y, x, z), as for mcgpu_warp_geometry; the permutation happens on the device.
+ *   Errors as mcgpu_set_geometry_arrays: -1 bad argument or no device, -2 unmapped voxels (the message carries their number), a class
+ *   that occurs with a material number outside 1..25, a density that prints as 0, or a material without data file; after any error the
+ *   context is what it was.  On success a resident correspondence model and the warp base are released, dose tallies restart.
+ * report (optional; zero it and set struct_size): per class the voxel count and the smallest linear index at which it occurs (-1:
+ *   nowhere; [z][y][x] of the engine's frame, for mcgpu_map_image of the input), unmapped voxels, and timings. */
+#define MCGPU_IMAGE_INT16 0
+#define MCGPU_IMAGE_FLOAT32 1
+#define MCGPU_IMAGE_CLASSES 12
+#define MCGPU_IMAGE_SEGMENTATIONS 8
+typedef struct mcgpu_image_class {
+  int material;   /* MC-GPU material number (position of its data file in the input file, from 1) */
+  float density;  /* g/cm^3 */
+} mcgpu_image_class;
+typedef struct mcgpu_image_map_report {
+  unsigned int struct_size;  /* sizeof(mcgpu_image_map_report) as the caller was compiled; smaller than 8 is refused */
+  unsigned int reserved;
+  unsigned long long count[MCGPU_IMAGE_CLASSES];
+  long long first[MCGPU_IMAGE_CLASSES];
+  unsigned long long unmapped;
+  double ms_kernel;                 /* the mapping kernel (HIP events) */
+  double ms_upload;                 /* host time of the copies of image and segmentations to the device */
+  double ms_install;                /* mcgpu_set_geometry_image: host time from the kernel's end to the context being ready */
+  unsigned long long kernel_bytes;  /* bytes the mapping kernel reads and writes once */
+} mcgpu_image_map_report;
+int mcgpu_map_image(mcgpu_ctx *ctx, const int n[3], const void *image, int image_dtype, const uint8_t *const segmentations[8],
+                    const mcgpu_image_class table[12], const float thresholds[3], uint8_t *material_out, float *density_out,
+                    mcgpu_image_map_report *report);
+int mcgpu_set_geometry_image(mcgpu_ctx *ctx, const int n[3], const float spacing_cm[3], const void *image, int image_dtype,
+                             const uint8_t *const segmentations[8], const mcgpu_image_class table[12], const float thresholds[3], int frame,
+                             mcgpu_image_map_report *report);
+
 /* Voxel geometry writer (cbctmc/mc/voxel_data.pyx:12-72 + mcgpu_geometry.jinja2 header fields):
  * material/density are [z][y][x] contiguous, spacing in cm. */
 int mcgpu_write_voxel_file(const char *path, const int n[3], const float spacing_cm[3], const uint8_t *material, const float *density,
@@ -384,9 +435,11 @@ int mcgpu_write_voxel_binary(const char *path, const int n[3], const float spaci
 /* Hardware ceilings the measurement prices the FAST kernel against, measured on the context's device (about 20 ms each; SURVEY.md
  * 8d; no reference counterpart).  MCGPU_MICROBENCH_VALU_ISSUE: out[0..2] = vector wave-instructions per ns and SIMD of a dense
  * dependent-FMA kernel at 8 waves/SIMD with 64 active lanes, with lanes 0-31, with 32 lanes spread over the wave.
- * MCGPU_MICROBENCH_ATOMIC_RATE: out[0] = scattered 64-bit atomic adds per second into a detector-sized (45 MB) tally. */
+ * MCGPU_MICROBENCH_ATOMIC_RATE: out[0] = scattered 64-bit atomic adds per second into a detector-sized (45 MB) tally.
+ * MCGPU_MICROBENCH_COPY_RATE: out[0] = bytes read + written per second by a streaming copy of 256 MiB (16-byte loads and stores). */
 #define MCGPU_MICROBENCH_VALU_ISSUE 0
 #define MCGPU_MICROBENCH_ATOMIC_RATE 1
+#define MCGPU_MICROBENCH_COPY_RATE 2
 int mcgpu_microbench(mcgpu_ctx *ctx, int kind, double *out, int n_out);
 
 /* Device-side known-answer hooks used by the parity tests (each runs a tiny kernel on the context's device). */
