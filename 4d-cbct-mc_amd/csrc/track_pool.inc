@@ -26,6 +26,10 @@
 //    at about 18 ns each, the 3.9e5 fetches of a 1e8-history launch took 7.2 ms, and no change to the kernel moved the
 //    Catphan time any more (thresholds, slot trading, fewer source instructions: all +-0.5 %) until the chunk size was
 //    varied.  With 64 addresses the same fetches cost nothing measurable: 7.25 -> 5.2 ms.
+//  * Two schedulers run this: track_pool_kernel (the per-wave pool described above, the default) and track_wg_kernel (a pool per
+//    workgroup, MCGPU_FAST_SCHED=1).  What they serve is defined ONCE, above both -- flight_iteration, serve_compton, serve_rayleigh,
+//    score_finished, deal_history_ids, start_history, exchange_history -- and a kernel holds only what is its own: who holds which
+//    history, when a batch runs, the settle step, and the counters about a batch as a whole.
 #if MC_COMPAT
 #error "track_pool.inc is the FAST kernel; the COMPAT kernel lives in track_kernel.inc"
 #endif
@@ -42,40 +46,47 @@ constexpr int kSlotStride = kParked * kPoolBlock;    // columns of the workgroup
 // diagnostic build: wave-cycles (s_memtime) per section, counters 12..15 = Compton, Rayleigh, tally+source, flight steps
 #define STAT_T0() const unsigned long long t_sec = __builtin_readcyclecounter()
 #define STAT_T1(slot) st[slot] += __builtin_readcyclecounter() - t_sec
+// the wave's counters: what STAT_ADD / STAT_T1 write as `st` (slots: include/mcgpu_amd.h, engine.py: scheduler_stats)
+struct Stats {
+  unsigned long long v[kNumStats] = {};
+  __device__ __forceinline__ unsigned long long& operator[](int slot) { return v[slot]; }
+};
 #else
 #define STAT_T0()
 #define STAT_T1(slot)
+struct Stats {};  // the product build counts nothing: the `st` the shared bodies take is empty
 #endif
 
 // the register-resident history of a lane
 struct History {
-  Particle P;
-  Rng rng;
-  int index;    // energy bin
-  float mfpW;   // Woodcock majorant mean free path at P.E
-  float aux;    // FLIGHT: total inverse mean free path of (P.E, mc_old), a register-only cache; SHELL: tau of the accepted angle
-  int mc;       // compact material of the last looked-up voxel (the interaction site when parked)
-  int scatter;  // 0 primary, 1 Compton, 2 Rayleigh, 3 multiple
+  Particle P = {0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f};
+  Rng rng = {1u, 1u};
+  int index = 0;      // energy bin
+  float mfpW = 0.f;   // Woodcock majorant mean free path at P.E
+  float aux = 0.f;    // FLIGHT: total inverse mean free path of (P.E, mc_old), a register-only cache; SHELL: tau of the accepted angle
+  int mc = 0;         // compact material of the last looked-up voxel (the interaction site when parked)
+  int scatter = 0;    // 0 primary, 1 Compton, 2 Rayleigh, 3 multiple
 };
 
-// Exchange the register history with the one in the lane's LDS slot (word f of this lane: slot[f * kPoolBlock], so a
-// wave-instruction touches 64 consecutive banks).  Phases travel in registers (phase <-> phS).
-__device__ __forceinline__ void exchange_history(unsigned int* slot, History& h, int& phase, int& phS) {
+// Exchange the register history with the one in an LDS slot: 12 words, word f of the slot at slot[f * kStride] (kStride: the
+// columns of the slot array, so a wave-instruction touches 64 consecutive banks).  Bits 28..31 of the packed word are the caller's:
+// `tag` goes into the slot, the slot's comes back.  The per-wave pool keeps its phases in registers and leaves them 0; the
+// workgroup-level pool's slots belong to nobody, so the phase of the history travels there.
+template <int kStride>
+__device__ __forceinline__ unsigned int exchange_history(unsigned int* slot, History& h, unsigned int tag) {
   // ds_wrxchg_rtn_b32: the LDS write-exchange returns the old word, so the 12 words swap in place without temporaries
-  auto xf = [&](int f, float& v) { v = __uint_as_float(atomicExch(slot + f * kSlotStride, __float_as_uint(v))); };
-  auto xu = [&](int f, unsigned int& v) { v = atomicExch(slot + f * kSlotStride, v); };
+  auto xf = [&](int f, float& v) { v = __uint_as_float(atomicExch(slot + f * kStride, __float_as_uint(v))); };
+  auto xu = [&](int f, unsigned int& v) { v = atomicExch(slot + f * kStride, v); };
   xf(0, h.P.x); xf(1, h.P.y); xf(2, h.P.z); xf(3, h.P.u); xf(4, h.P.v); xf(5, h.P.w); xf(6, h.P.E);
   xu(7, h.rng.x); xu(8, h.rng.c);
   xf(9, h.mfpW);
-  unsigned int packed = (unsigned int)h.index | ((unsigned int)h.mc << 16) | ((unsigned int)h.scatter << 24);
+  unsigned int packed = (unsigned int)h.index | ((unsigned int)h.mc << 16) | ((unsigned int)h.scatter << 24) | (tag << 28);
   xu(10, packed);
   h.index = (int)(packed & 0xFFFFu);
   h.mc = (int)((packed >> 16) & 0xFFu);
-  h.scatter = (int)(packed >> 24);
+  h.scatter = (int)((packed >> 24) & 0xFu);
   xf(11, h.aux);
-  const int p = phase;
-  phase = phS;
-  phS = p;
+  return packed >> 28;
 }
 
 // The region outside the object box is homogeneous background (device_model.hpp, brick code kBrickExterior): a photon
@@ -243,7 +254,7 @@ __device__ __forceinline__ bool in_compton(int ph) { return ph == PH_COMPTON || 
 // virtual) and requesting its voxel byte together with this one's -- two round trips in flight per lane, half as many
 // wave iterations.  The iterations halved and took twice as long each: with 8 waves per SIMD a flight iteration is bound
 // by instruction issue, not by the voxel round trip, and the dropped second steps (the first one ended the flight) made
-// the thorax workload 7 % slower (kFlightPairs = 2 re-enables it).
+// the thorax workload 7 % slower.
 //
 // flight_locate: position of the step from P, clamped to the bounding box (lanes that have just left the volume stay in
 // bounds), brick code, and the request for the voxel byte of a mixed brick.  flight_resolve: material, density and the
@@ -306,18 +317,10 @@ __device__ __forceinline__ void flight_locate(const TrackArgs& A, const Particle
       // sub-brick (4^3 voxels) of the step: index of its code in the second-level table AND of its 64-byte tile in the volume
       const unsigned int si = (ix >> 2) + __umul24(iy >> 2, (unsigned int)A.sub_nx) + __umul24(iz >> 2, (unsigned int)A.sub_nxy);
       // second level: the code of the sub-brick from the L2-resident table; the volume only for a mixed sub-brick
-#if defined(MC_SPEC_VOXEL) && MC_SPEC_VOXEL
-      // experiment: both requests in flight together (one round trip instead of two dependent ones, at the price of voxel
-      // bytes fetched for homogeneous sub-bricks)
-      unsigned int code = 0xFFu;
-      if (VK == kVolU8Sub) code = (unsigned int)A.sub[si >> 1];
-      s.raw = (unsigned int)((const unsigned char*)A.vol)[(si << 6) | ((iz & 3u) << 4) | ((iy & 3u) << 2) | (ix & 3u)];
-      asm volatile("" : "+v"(code), "+v"(s.raw));
-      s.e = ((int)code >> ((si & 1u) << 2)) & 0xF;
-#else
+      // (measured and NOT adopted: both requests in flight together -- one round trip instead of two dependent ones, at the price of
+      // voxel bytes fetched for homogeneous sub-bricks)
       if (VK == kVolU8Sub) s.e = ((int)A.sub[si >> 1] >> ((si & 1u) << 2)) & 0xF;
       if (s.e == kBrickMixed) s.raw = (unsigned int)((const unsigned char*)A.vol)[(si << 6) | ((iz & 3u) << 4) | ((iy & 3u) << 2) | (ix & 3u)];
-#endif
     }
   } else {
     const unsigned int vi = ix + __umul24(iy, (unsigned int)A.nx) + __umul24(iz, (unsigned int)A.nxy);
@@ -388,30 +391,19 @@ __device__ __forceinline__ int flight_resolve(const TrackArgs& A, History& h, co
   const int ph = is_virtual ? ((s.exterior && (A.has_exterior & 1)) ? PH_HOP : PH_FLIGHT) : PH_REAL;
   return s.out ? PH_ESCAPED : ph;
 }
-constexpr int kFlightPairs = 1;
 template <int VK>
 __device__ __forceinline__ void flight_steps(const TrackArgs& A, History& h, int& phase, int& mc_old, const float negl2, const float hi_x,
                                              const float hi_y, const float hi_z, const int nmat, bool& st_mixed, bool& st_sig,
                                              unsigned long long& t_loaded) {
   Particle& P = h.P;
-  StepSite a, b;
+  StepSite a;
   flight_locate<VK>(A, P, P.x, P.y, P.z, negl2 * __builtin_amdgcn_logf(rng_f(h.rng)), hi_x, hi_y, hi_z, a);  // step = -mfpW * ln(xi)
-  if (kFlightPairs == 2) {
-    flight_locate<VK>(A, P, a.x, a.y, a.z, negl2 * __builtin_amdgcn_logf(rng_f(h.rng)), hi_x, hi_y, hi_z, b);
-    // both requests are in flight; nothing above may wait for either (the compiler would otherwise sink the first use of
-    // a voxel byte into the branch that loads it, i.e. wait right behind the load)
-    if (VK != kVolRaw) asm volatile("" : "+v"(a.raw), "+v"(b.raw));
-  }
 #if MC_STATS
   if (VK != kVolRaw) asm volatile("" : "+v"(a.raw));
   t_loaded = __builtin_readcyclecounter();  // the voxel byte has arrived
 #endif
   P.x = a.x; P.y = a.y; P.z = a.z;
   phase = flight_resolve<VK>(A, h, a, mc_old, nmat, st_mixed, st_sig);
-  if (kFlightPairs == 2 && phase == PH_FLIGHT) {
-    P.x = b.x; P.y = b.y; P.z = b.z;
-    phase = flight_resolve<VK>(A, h, b, mc_old, nmat, st_mixed, st_sig);
-  }
 }
 
 // End of a FAST kernel: every wave of the workgroup arrives here exactly once -- both schedulers leave their loop by `break` only,
@@ -428,13 +420,205 @@ __device__ __forceinline__ void finish_workgroup(const TrackArgs& A) {
   if (staged) stage_counts_publish(A);
 }
 
+// ================================================================================================
+// What a scheduler serves: the bodies below are the physics of one batch, written once for both schedulers.  Each works on the
+// register history of the calling lane; which lanes hold what, when a batch is worth running and what is counted about the batch
+// as a whole is the calling scheduler's business.  `st`: the wave's counters (diagnostic build; empty otherwise).
+// ================================================================================================
+
+// One wave iteration of the flight loop: a Woodcock step (K.cu:249-279) for the lanes in FLIGHT.  Branch-free up to the two rare
+// memory paths (mixed brick, new cross-section record): the position clamped to the bounding box indexes the lookups, so lanes that
+// have just left the volume stay in bounds.  The caller takes the ballot of the lanes still in FLIGHT itself: taken in here, the
+// compiler carries its predicate as a boolean through the divergent step -- four more instructions in a flight loop of 87 ... 142,
+// the thorax workload 0.7 % slower (profiles/fast_services_refactor.md).
+template <int VK>
+__device__ __forceinline__ void flight_iteration(const TrackArgs& A, History& h, int& phase, int& mc_old, const float negl2, const float hi_x,
+                                                 const float hi_y, const float hi_z, const int nmat, Stats& st) {
+#if MC_STATS
+  const unsigned long long t_fl = __builtin_readcyclecounter();
+#endif
+  bool st_mixed = false, st_sig = false;  // diagnostic build only (dead otherwise)
+  unsigned long long t_loaded = 0;
+  STAT_ADD(23, __popcll(__ballot(phase == PH_FLIGHT)));  // lanes that take this flight step
+  if (phase == PH_FLIGHT) flight_steps<VK>(A, h, phase, mc_old, negl2, hi_x, hi_y, hi_z, nmat, st_mixed, st_sig, t_loaded);
+#if MC_STATS
+  {
+    const unsigned long long t_end = __builtin_readcyclecounter();
+    st[15] += t_end - t_fl;
+    // wave-level split: up to the arrival of the voxel bytes (first active lane's stamp) / the rest of the iteration
+    const unsigned long long act = __ballot(t_loaded != 0ULL);
+    if (act != 0ULL) {
+      const int l0 = __ffsll((long long)act) - 1;
+      const unsigned long long tl = ((unsigned long long)__shfl((unsigned int)(t_loaded >> 32), l0) << 32) | (unsigned long long)__shfl((unsigned int)t_loaded, l0);
+      st[28] += tl - t_fl;
+      st[29] += t_end - tl;
+    }
+  }
+#endif
+  STAT_ADD(0, 1);
+  STAT_ADD(1, __popcll(__ballot(phase == PH_FLIGHT)));
+  STAT_ADD(24, __ballot(st_mixed) != 0ULL ? 1 : 0);
+  STAT_ADD(25, __popcll(__ballot(st_mixed)));
+  STAT_ADD(26, __ballot(st_sig) != 0ULL ? 1 : 0);
+  STAT_ADD(27, __popcll(__ballot(st_sig)));
+}
+
+// Compton (K.cu:290-326): one straight pass for the lanes whose history is in COMPTON or SHELL (compton_draw: tau if not yet
+// accepted, one shell, its profile, the test; then the momentum trial).  A lane whose trial fails keeps its phase (COMPTON: new
+// angle; SHELL: new shell at the accepted angle) and takes part in a later batch.
+__device__ __forceinline__ void serve_compton(const TrackArgs& A, History& h, int& phase, int& mc_old, float& negl2, Stats& st) {
+  STAT_ADD(16, __popcll(__ballot(phase == PH_COMPTON)));
+  STAT_ADD(17, __popcll(__ballot(phase == PH_SHELL)));
+#if MC_STATS
+  const bool st_was_compton = in_compton(phase);
+#endif
+  if (in_compton(phase)) {
+    ComptonTrial c;
+    c.tau = h.aux;
+    if (compton_draw(A, h.P.E, h.mc, phase == PH_COMPTON, h.rng, c)) {
+      const float e_in = h.P.E;
+      polar_t omc;
+      h.aux = c.tau;
+      phase = PH_SHELL;
+      if (compton_momentum_trial(h.P.E, c, h.rng, omc)) {
+        rotate_dir(h.P, omc, h.rng);
+        if (A.dose_flags != 0 && (e_in - h.P.E) > 0.001f) tally_dose(A, h.P, e_in - h.P.E, h.mc);  // K.cu:299,356-367
+        h.index = energy_index(A, h.P.E);
+        if (h.index > -1) {
+          h.mfpW = LDS_F(SLDS(A, wood))[h.index >> kWoodShift];  // the coarse bin's majorant: no table fetch (LdsLayout::wood)
+          negl2 = -0.69314718055994531f * h.mfpW;
+          mc_old = -2;
+          h.scatter = (h.scatter == 0) ? 1 : 3;
+          phase = PH_FLIGHT;
+        } else {
+          h.index = 0;
+          phase = PH_NEW;  // below the table cut-off: absorbed
+        }
+      }
+    }
+  }
+#if MC_STATS
+  STAT_ADD(18, __popcll(__ballot(st_was_compton && !in_compton(phase))));  // events completed in this batch
+#endif
+}
+
+// Rayleigh (K.cu:329-347)
+__device__ __forceinline__ void serve_rayleigh(const TrackArgs& A, History& h, int& phase) {
+  if (phase == PH_RAYLEIGH) {
+    const float pmaxn = as_global(SARG(A, mfp))[8u * table_row(A, h.index, h.mc) + 6u];  // pmax of bin index + 1 (K.cu:336)
+    polar_t omc;
+    if (rayleigh_trial(A, h.P.E, h.mc, pmaxn, h.rng, omc)) {
+      rotate_dir(h.P, omc, h.rng);
+      h.scatter = (h.scatter == 0) ? 2 : 3;
+      phase = PH_FLIGHT;
+    }
+  }
+}
+
+// A finished history: an ESCAPED photon goes to the detector (tally_word: the word of the detector tally this lane scores in, -1 for
+// none; the caller issues tally_score at the end of its batch), an ABSORBED one leaves its energy in its voxel (photoelectric
+// absorption, K.cu:350-367).  Either way the lane wants a NEW history.
+__device__ __forceinline__ void score_finished(const TrackArgs& A, const History& h, int& phase, int& tally_word, unsigned int& tally_value) {
+  tally_word = -1;
+  tally_value = 0;
+  if (phase == PH_ESCAPED) {
+    tally_word = tally_pixel(A, h.P, h.scatter);
+    tally_value = __float2uint_rn(h.P.E * 100.0f);
+    phase = PH_NEW;
+  } else if (phase == PH_ABSORBED) {
+    if (A.dose_flags != 0 && h.P.E > 0.001f) tally_dose(A, h.P, h.P.E, h.mc);
+    phase = PH_NEW;
+  }
+}
+
+// Deal history ids to the lanes that need one (phase NEW): wave-uniform bookkeeping executed by every lane (callers enter on a
+// wave-uniform condition), ids ranked by ballot.  chunk_next / chunk_end: the unassigned ids of this wave's current chunk; ctr:
+// the counter it draws from next; ctr_exhausted: how many counters it has found exhausted (all of them: no work is left).
+// Returns the lane's id, or ~0 for none.
+__device__ __forceinline__ unsigned long long deal_history_ids(const TrackArgs& A, const int phase, unsigned long long& chunk_next, unsigned long long& chunk_end,
+                                                               unsigned int& ctr, unsigned int& ctr_exhausted) {
+  unsigned long long my_id = ~0ULL;
+  const unsigned long long need = __ballot(phase == PH_NEW);
+  const unsigned int n_need = (unsigned int)__popcll(need);
+  if (n_need != 0u) {
+    const unsigned int rank = __builtin_amdgcn_mbcnt_hi((unsigned int)(need >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)need, 0u));
+    const unsigned long long avail = chunk_end - chunk_next;
+    if (avail >= n_need) {
+      my_id = chunk_next + rank;
+      chunk_next += n_need;
+    } else {
+      // the rest of the old chunk, then a new one: from this wave's counter or, once that one is exhausted, from the
+      // next (at most kNumCounters failed fetches per wave, at the very end of the launch)
+      if (rank < avail) my_id = chunk_next + rank;
+      chunk_next = chunk_end;
+      const int leader = __ffsll((long long)need) - 1;
+      while (ctr_exhausted < (unsigned int)kNumCounters) {
+        const unsigned long long base = LARG(A, count) / kNumCounters * ctr + min((unsigned long long)ctr, LARG(A, count) % kNumCounters);
+        const unsigned long long size = LARG(A, count) / kNumCounters + (ctr < LARG(A, count) % kNumCounters ? 1ULL : 0ULL);
+        unsigned long long gv = 0;
+        if ((int)(threadIdx.x & 63) == leader) gv = atomicAdd(LARG(A, work_counter) + ctr * (unsigned int)kCounterStride, (unsigned long long)kChunk);
+        // wave-uniform from here on (scalar registers): the leader's value, read with a scalar lane index
+        const unsigned long long g = ((unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)(gv >> 32), leader) << 32) |
+                                     (unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)gv, leader);
+        if (g >= size) {
+          ++ctr_exhausted;
+          ctr = (ctr + 1u) % (unsigned int)kNumCounters;
+          continue;
+        }
+        const unsigned long long g_end = base + ((g + kChunk < size) ? g + kChunk : size);
+        const unsigned long long id = base + g + (rank - avail);
+        if (rank >= avail && id < g_end) my_id = id;
+        chunk_next = min(base + g + (n_need - avail), g_end);
+        chunk_end = g_end;
+        break;
+      }
+    }
+  }
+  return my_id;
+}
+
+// A lane in NEW starts history `my_id` (K.cu:206-247) -- or, given none, is DONE once every counter is exhausted (otherwise it stays
+// NEW and asks again at the next service).
+__device__ __forceinline__ void start_history(const TrackArgs& A, History& h, int& phase, int& mc_old, float& negl2, const unsigned long long my_id,
+                                              const unsigned int ctr_exhausted) {
+  if (phase == PH_NEW) {
+    if (my_id != ~0ULL) {
+      rng_init_history(h.rng, LARG(A, first) + my_id, (unsigned int)LARG(A, seed), LARG(A, stream_key));
+      // energy first (K.cu:1033-1040): the two records that depend on it are requested before the direction is
+      // sampled, so their latency is covered by that arithmetic
+      sample_source_energy(A, h.P, h.rng);
+      h.scatter = 0;
+      h.index = energy_index(A, h.P.E);
+      float2 t_ext = make_float2(0.f, 0.f);
+      if (A.has_exterior & 2) t_ext = exterior_record(A, h.index);
+      sample_source_direction(A, h.P, h.rng);
+      h.mfpW = LDS_F(SLDS(A, wood))[h.index >> kWoodShift];
+      negl2 = -0.69314718055994531f * h.mfpW;
+      mc_old = -1;
+      if (A.has_exterior & 2) {
+        // the source sits outside the object box: straight to its entry point (or through / past the volume)
+        source_entry(A, h, phase, t_ext);
+        if (phase == PH_REAL) {  // REAL lives in registers only: settle it before any exchange
+          const float4* rec = real_record(A, h);
+          classify_real(A, h, phase, rec[0], rec[1]);
+        }
+      } else {
+        bool miss;
+        move_to_bbox(A, h.P, miss);
+        phase = miss ? PH_ESCAPED : PH_FLIGHT;
+      }
+    } else if (ctr_exhausted >= (unsigned int)kNumCounters) {
+      phase = PH_DONE;  // every counter is exhausted
+    }
+  }
+}
+
 // kDouble: the arithmetic of this translation unit (MC_FAST_F64) as part of the kernel's NAME -- profilers tell track_fast.hip's
 // track_pool_kernel<VK, seg, 0> from track_fast64.hip's <VK, seg, 1> (the body does not use it: the arithmetic is chosen by the macro)
 template <int VK, bool kSegmentLoop, int kDouble = MC_FAST_F64>
 __global__ __launch_bounds__(kPoolBlock, kPoolWavesPerSimd) void track_pool_kernel(const TrackArgs A) {
+  [[maybe_unused]] Stats st;
 #if MC_STATS
-  unsigned long long st[kNumStats];
-  for (int k = 0; k < kNumStats; ++k) st[k] = 0;
   const unsigned long long t_wave0 = __builtin_readcyclecounter();
   {  // where and when this wave runs: HW_ID (wave/simd/cu/sh/se fields), XCC_ID, constant-rate clock
     const unsigned int w = blockIdx.x * (kPoolBlock / 64) + (threadIdx.x >> 6);
@@ -459,9 +643,6 @@ __global__ __launch_bounds__(kPoolBlock, kPoolWavesPerSimd) void track_pool_kern
   }
 
   History h;
-  h.P.x = h.P.y = h.P.z = 0.f; h.P.u = 0.f; h.P.v = 1.f; h.P.w = 0.f; h.P.E = 0.f;
-  h.rng.x = h.rng.c = 1u;
-  h.index = 0; h.mfpW = 0.f; h.aux = 0.f; h.mc = 0; h.scatter = 0;
   int phase = PH_NEW;
   // a parked history of this lane satisfies pred / how many of this lane's histories (register + parked) do
   auto parked = [&](auto pred) {
@@ -505,9 +686,10 @@ __global__ __launch_bounds__(kPoolBlock, kPoolWavesPerSimd) void track_pool_kern
     int ps = phS[0];
 #pragma unroll
     for (int k = 1; k < kParked; ++k) if (j == k) { sp = slot[k]; ps = phS[k]; }
-    exchange_history(sp, h, phase, ps);
+    exchange_history<kSlotStride>(sp, h, 0u);  // phases travel in registers
 #pragma unroll
-    for (int k = 0; k < kParked; ++k) if (j == k) phS[k] = ps;
+    for (int k = 0; k < kParked; ++k) if (j == k) phS[k] = phase;
+    phase = ps;
     mc_old = -1;
     negl2 = -0.69314718055994531f * h.mfpW;
   };
@@ -561,39 +743,8 @@ __global__ __launch_bounds__(kPoolBlock, kPoolWavesPerSimd) void track_pool_kern
     // chooses (TrackArgs::segment_loop: tile records, or materials of 20 and more electron shells on average): profiles/r05d_*, r05i_*.
     unsigned long long fR;
     do {
-    // ------------------------------------------------------------------ Woodcock flight step (K.cu:249-279)
-    // Branch-free up to the two rare memory paths (mixed brick, new cross-section record): the position clamped
-    // to the bounding box indexes the lookups, so lanes that have just left the volume stay in bounds.
-#if MC_STATS
-    const unsigned long long t_fl = __builtin_readcyclecounter();
-#endif
-    bool st_mixed = false, st_sig = false;  // diagnostic build only (dead otherwise)
-    unsigned long long t_loaded = 0;
-    STAT_ADD(23, __popcll(__ballot(phase == PH_FLIGHT)));  // lanes that take this flight step
-    if (phase == PH_FLIGHT) flight_steps<VK>(A, h, phase, mc_old, negl2, hi_x, hi_y, hi_z, nmat, st_mixed, st_sig, t_loaded);
-    fR = __ballot(phase == PH_FLIGHT);
-#if MC_STATS
-    {
-      const unsigned long long t_end = __builtin_readcyclecounter();
-      st[15] += t_end - t_fl;
-      // wave-level split: up to the arrival of the voxel bytes (first active lane's stamp) / the rest of the iteration
-      const unsigned long long act = __ballot(t_loaded != 0ULL);
-      if (act != 0ULL) {
-        const int l0 = __ffsll((long long)act) - 1;
-        const unsigned long long tl = ((unsigned long long)__shfl((unsigned int)(t_loaded >> 32), l0) << 32) | (unsigned long long)__shfl((unsigned int)t_loaded, l0);
-        st[28] += tl - t_fl;
-        st[29] += t_end - tl;
-      }
-    }
-#endif
-    STAT_ADD(0, 1);
-    STAT_ADD(1, __popcll(fR));
-#if MC_STATS
-    STAT_ADD(24, __ballot(st_mixed) != 0ULL ? 1 : 0);
-    STAT_ADD(25, __popcll(__ballot(st_mixed)));
-    STAT_ADD(26, __ballot(st_sig) != 0ULL ? 1 : 0);
-    STAT_ADD(27, __popcll(__ballot(st_sig)));
-#endif
+      flight_iteration<VK>(A, h, phase, mc_old, negl2, hi_x, hi_y, hi_z, nmat, st);
+      fR = __ballot(phase == PH_FLIGHT);
     } while (kSegmentLoop && __popcll(fR) > hold);
     if (!kSegmentLoop && __popcll(fR) > hold) continue;
 
@@ -642,48 +793,14 @@ __global__ __launch_bounds__(kPoolBlock, kPoolWavesPerSimd) void track_pool_kern
     STAT_ADD(8, 1);
     STAT_ADD(11, drain ? 1 : 0);
 
-    // (1) Compton (K.cu:290-326): one straight pass for the lanes with an event in R or S (compton_draw: tau if not yet
-    //     accepted, one shell, its profile, the test; then the momentum trial).  A lane whose trial fails keeps its
-    //     phase (COMPTON: new angle; SHELL: new shell at the accepted angle) and takes part in the next batch.
+    // (1) Compton: one pass for the lanes with an event in R or S (serve_compton)
     if (n_compton != 0 && ((drain && 2 * n_compton >= n_most) || n_compton >= t_compton)) {
       STAT_ADD(2, 1);
       STAT_ADD(3, n_compton);
       STAT_T0();
       if (trade & 2) trade_slots([](int p) { return in_compton(p); });
       swap_in([](int p) { return in_compton(p); });
-      STAT_ADD(16, __popcll(__ballot(phase == PH_COMPTON)));
-      STAT_ADD(17, __popcll(__ballot(phase == PH_SHELL)));
-#if MC_STATS
-      const bool st_was_compton = in_compton(phase);
-#endif
-      if (in_compton(phase)) {
-        ComptonTrial c;
-        c.tau = h.aux;
-        if (compton_draw(A, h.P.E, h.mc, phase == PH_COMPTON, h.rng, c)) {
-          const float e_in = h.P.E;
-          polar_t omc;
-          h.aux = c.tau;
-          phase = PH_SHELL;
-          if (compton_momentum_trial(h.P.E, c, h.rng, omc)) {
-            rotate_dir(h.P, omc, h.rng);
-            if (A.dose_flags != 0 && (e_in - h.P.E) > 0.001f) tally_dose(A, h.P, e_in - h.P.E, h.mc);  // K.cu:299,356-367
-            h.index = energy_index(A, h.P.E);
-            if (h.index > -1) {
-              h.mfpW = LDS_F(SLDS(A, wood))[h.index >> kWoodShift];  // the coarse bin's majorant: no table fetch (LdsLayout::wood)
-              negl2 = -0.69314718055994531f * h.mfpW;
-              mc_old = -2;
-              h.scatter = (h.scatter == 0) ? 1 : 3;
-              phase = PH_FLIGHT;
-            } else {
-              h.index = 0;
-              phase = PH_NEW;  // below the table cut-off: absorbed
-            }
-          }
-        }
-      }
-#if MC_STATS
-      STAT_ADD(18, __popcll(__ballot(st_was_compton && !in_compton(phase))));  // events completed in this batch
-#endif
+      serve_compton(A, h, phase, mc_old, negl2, st);
       STAT_T1(12);
     }
     // (2) Rayleigh (K.cu:329-347)
@@ -692,15 +809,7 @@ __global__ __launch_bounds__(kPoolBlock, kPoolWavesPerSimd) void track_pool_kern
       STAT_ADD(5, n_rayleigh);
       STAT_T0();
       swap_in([](int p) { return p == PH_RAYLEIGH; });
-      if (phase == PH_RAYLEIGH) {
-        const float pmaxn = as_global(SARG(A, mfp))[8u * table_row(A, h.index, h.mc) + 6u];  // pmax of bin index + 1 (K.cu:336)
-        polar_t omc;
-        if (rayleigh_trial(A, h.P.E, h.mc, pmaxn, h.rng, omc)) {
-          rotate_dir(h.P, omc, h.rng);
-          h.scatter = (h.scatter == 0) ? 2 : 3;
-          phase = PH_FLIGHT;
-        }
-      }
+      serve_rayleigh(A, h, phase);
       STAT_T1(13);
     }
     // (3) escaped photons -> detector; finished histories -> next history id
@@ -720,88 +829,11 @@ __global__ __launch_bounds__(kPoolBlock, kPoolWavesPerSimd) void track_pool_kern
           classify_real(A, h, phase, rec[0], rec[1]);
         }
       }
-      int tally_word = -1;         // word of the detector tally this lane scores in; the atomic is issued at the end of the batch
-      unsigned int tally_value = 0;
-      if (phase == PH_ESCAPED) {
-        tally_word = tally_pixel(A, h.P, h.scatter);
-        tally_value = __float2uint_rn(h.P.E * 100.0f);
-        phase = PH_NEW;
-      } else if (phase == PH_ABSORBED) {
-        // photoelectric absorption: the photon's energy stays in this voxel (K.cu:350-367)
-        if (A.dose_flags != 0 && h.P.E > 0.001f) tally_dose(A, h.P, h.P.E, h.mc);
-        phase = PH_NEW;
-      }
-      // deal history ids to the lanes that need one: wave-uniform bookkeeping executed by every lane
-      // (this region is entered on a wave-uniform condition), ids ranked by ballot
-      unsigned long long my_id = ~0ULL;
-      {
-        const unsigned long long need = __ballot(phase == PH_NEW);
-        const unsigned int n_need = (unsigned int)__popcll(need);
-        if (n_need != 0u) {
-          const unsigned int rank = __builtin_amdgcn_mbcnt_hi((unsigned int)(need >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)need, 0u));
-          const unsigned long long avail = chunk_end - chunk_next;
-          if (avail >= n_need) {
-            my_id = chunk_next + rank;
-            chunk_next += n_need;
-          } else {
-            // the rest of the old chunk, then a new one: from this wave's counter or, once that one is exhausted, from the
-            // next (at most kNumCounters failed fetches per wave, at the very end of the launch)
-            if (rank < avail) my_id = chunk_next + rank;
-            chunk_next = chunk_end;
-            const int leader = __ffsll((long long)need) - 1;
-            while (ctr_exhausted < (unsigned int)kNumCounters) {
-              const unsigned long long base = LARG(A, count) / kNumCounters * ctr + min((unsigned long long)ctr, LARG(A, count) % kNumCounters);
-              const unsigned long long size = LARG(A, count) / kNumCounters + (ctr < LARG(A, count) % kNumCounters ? 1ULL : 0ULL);
-              unsigned long long gv = 0;
-              if ((int)(threadIdx.x & 63) == leader) gv = atomicAdd(LARG(A, work_counter) + ctr * (unsigned int)kCounterStride, (unsigned long long)kChunk);
-              // wave-uniform from here on (scalar registers): the leader's value, read with a scalar lane index
-              const unsigned long long g = ((unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)(gv >> 32), leader) << 32) |
-                                           (unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)gv, leader);
-              if (g >= size) {
-                ++ctr_exhausted;
-                ctr = (ctr + 1u) % (unsigned int)kNumCounters;
-                continue;
-              }
-              const unsigned long long g_end = base + ((g + kChunk < size) ? g + kChunk : size);
-              const unsigned long long id = base + g + (rank - avail);
-              if (rank >= avail && id < g_end) my_id = id;
-              chunk_next = min(base + g + (n_need - avail), g_end);
-              chunk_end = g_end;
-              break;
-            }
-          }
-        }
-      }
-      if (phase == PH_NEW) {
-        if (my_id != ~0ULL) {
-          rng_init_history(h.rng, LARG(A, first) + my_id, (unsigned int)LARG(A, seed), LARG(A, stream_key));
-          // energy first (K.cu:1033-1040): the two records that depend on it are requested before the direction is
-          // sampled, so their latency is covered by that arithmetic
-          sample_source_energy(A, h.P, h.rng);
-          h.scatter = 0;
-          h.index = energy_index(A, h.P.E);
-          float2 t_ext = make_float2(0.f, 0.f);
-          if (A.has_exterior & 2) t_ext = exterior_record(A, h.index);
-          sample_source_direction(A, h.P, h.rng);
-          h.mfpW = LDS_F(SLDS(A, wood))[h.index >> kWoodShift];
-          negl2 = -0.69314718055994531f * h.mfpW;
-          mc_old = -1;
-          if (A.has_exterior & 2) {
-            // the source sits outside the object box: straight to its entry point (or through / past the volume)
-            source_entry(A, h, phase, t_ext);
-            if (phase == PH_REAL) {  // REAL lives in registers only: settle it before any exchange
-              const float4* rec = real_record(A, h);
-              classify_real(A, h, phase, rec[0], rec[1]);
-            }
-          } else {
-            bool miss;
-            move_to_bbox(A, h.P, miss);
-            phase = miss ? PH_ESCAPED : PH_FLIGHT;
-          }
-        } else if (ctr_exhausted >= (unsigned int)kNumCounters) {
-          phase = PH_DONE;  // every counter is exhausted (otherwise the lane stays NEW and asks again at the next service)
-        }
-      }
+      int tally_word;  // word of the detector tally this lane scores in (-1: none); the hit is scored at the end of the batch
+      unsigned int tally_value;
+      score_finished(A, h, phase, tally_word, tally_value);
+      const unsigned long long my_id = deal_history_ids(A, phase, chunk_next, chunk_end, ctr, ctr_exhausted);
+      start_history(A, h, phase, mc_old, negl2, my_id, ctr_exhausted);
       // One scattered 64-bit add per detected photon, executed at the memory side, was the wall of the Catphan launch: 7.5e7 of them
       // at 2.37e10/s = 3.18 ms of a 3.67 ms launch, whatever the kernel around them did (round-2 experiment, DESIGN.md 3.1: without
       // the add 17 % faster, a plain store in its place 15 %, a 32-bit add 4 %; issuing it later changes nothing).  The hit is now
@@ -890,28 +922,9 @@ __device__ __forceinline__ int kind_of(int ph) { return (int)((0x1774333210ULL >
 static_assert(PH_FLIGHT == 0 && PH_COMPTON == 1 && PH_RAYLEIGH == 2 && PH_ESCAPED == 3 && PH_ABSORBED == 4 && PH_NEW == 5 && PH_DONE == 6 &&
                   PH_SHELL == 9, "kind_of: the nibble table is written for these phase numbers");
 
-// register history <-> slot history; the slot's phase travels in the packed word (bits 28..31)
-__device__ __forceinline__ void exchange_slot(unsigned int* slot, History& h, int& phase) {
-  auto xf = [&](int f, float& v) { v = __uint_as_float(atomicExch(slot + f * kPoolBlock, __float_as_uint(v))); };
-  auto xu = [&](int f, unsigned int& v) { v = atomicExch(slot + f * kPoolBlock, v); };
-  xf(0, h.P.x); xf(1, h.P.y); xf(2, h.P.z); xf(3, h.P.u); xf(4, h.P.v); xf(5, h.P.w); xf(6, h.P.E);
-  xu(7, h.rng.x); xu(8, h.rng.c);
-  xf(9, h.mfpW);
-  unsigned int packed = (unsigned int)h.index | ((unsigned int)h.mc << 16) | ((unsigned int)h.scatter << 24) | ((unsigned int)phase << 28);
-  xu(10, packed);
-  h.index = (int)(packed & 0xFFFFu);
-  h.mc = (int)((packed >> 16) & 0xFFu);
-  h.scatter = (int)((packed >> 24) & 0xFu);
-  phase = (int)(packed >> 28);
-  xf(11, h.aux);
-}
-
 template <int VK>
 __global__ __launch_bounds__(kPoolBlock, kPoolWavesPerSimd) void track_wg_kernel(const TrackArgs A) {
-#if MC_STATS
-  unsigned long long st[kNumStats];
-  for (int k = 0; k < kNumStats; ++k) st[k] = 0;
-#endif
+  [[maybe_unused]] Stats st;
   unsigned int* const ctl = reinterpret_cast<unsigned int*>(lds_raw + A.lds.queues);
   unsigned short* const rings = reinterpret_cast<unsigned short*>(lds_raw + A.lds.queues + 64);
   unsigned int* const slots = reinterpret_cast<unsigned int*>(lds_raw + A.lds.slots);
@@ -929,9 +942,6 @@ __global__ __launch_bounds__(kPoolBlock, kPoolWavesPerSimd) void track_wg_kernel
   stage_tables<is_u8(VK) ? (int)kVolU8 : VK>(A);  // ends with the workgroup barrier
 
   History h;
-  h.P.x = h.P.y = h.P.z = 0.f; h.P.u = 0.f; h.P.v = 1.f; h.P.w = 0.f; h.P.E = 0.f;
-  h.rng.x = h.rng.c = 1u;
-  h.index = 0; h.mfpW = 0.f; h.aux = 0.f; h.mc = 0; h.scatter = 0;
   int phase = PH_NEW;
   int mc_old = -1;
   float negl2 = 0.f;
@@ -1062,7 +1072,7 @@ __global__ __launch_bounds__(kPoolBlock, kPoolWavesPerSimd) void track_wg_kernel
           my_kind = kKindNone;  // nothing was parked
         } else {
           *e_pop = (unsigned short)kRingEmpty;
-          exchange_slot(slots + id, h, phase);
+          phase = (int)exchange_history<kPoolBlock>(slots + id, h, (unsigned int)phase);  // the slot's phase travels in the packed word
           mc_old = -1;
           negl2 = -0.69314718055994531f * h.mfpW;
         }
@@ -1092,89 +1102,21 @@ __global__ __launch_bounds__(kPoolBlock, kPoolWavesPerSimd) void track_wg_kernel
       const int hold = max((flying_now > swap_batch) ? flying_now - swap_batch : 0, (flying_now * hold_q) >> 4);
       unsigned long long fR;
       do {
-#if MC_STATS
-        const unsigned long long t_fl = __builtin_readcyclecounter();
-#endif
-        bool st_mixed = false, st_sig = false;  // diagnostic build only (dead otherwise)
-        unsigned long long t_loaded = 0;
-        STAT_ADD(23, __popcll(__ballot(phase == PH_FLIGHT)));
-        if (phase == PH_FLIGHT) flight_steps<VK>(A, h, phase, mc_old, negl2, hi_x, hi_y, hi_z, nmat, st_mixed, st_sig, t_loaded);
+        flight_iteration<VK>(A, h, phase, mc_old, negl2, hi_x, hi_y, hi_z, nmat, st);
         fR = __ballot(phase == PH_FLIGHT);
-#if MC_STATS
-        {
-          const unsigned long long t_end = __builtin_readcyclecounter();
-          st[15] += t_end - t_fl;
-          const unsigned long long act = __ballot(t_loaded != 0ULL);
-          if (act != 0ULL) {
-            const int l0 = __ffsll((long long)act) - 1;
-            const unsigned long long tl = ((unsigned long long)__shfl((unsigned int)(t_loaded >> 32), l0) << 32) | (unsigned long long)__shfl((unsigned int)t_loaded, l0);
-            st[28] += tl - t_fl;
-            st[29] += t_end - tl;
-          }
-          STAT_ADD(24, __ballot(st_mixed) != 0ULL ? 1 : 0);
-          STAT_ADD(25, __popcll(__ballot(st_mixed)));
-          STAT_ADD(26, __ballot(st_sig) != 0ULL ? 1 : 0);
-          STAT_ADD(27, __popcll(__ballot(st_sig)));
-        }
-#endif
-        STAT_ADD(0, 1);
-        STAT_ADD(1, __popcll(fR));
       } while (__popcll(fR) > hold);
     } else if (task == kQCompton) {
-      // Compton (K.cu:290-326): one straight pass (compton_draw, then the momentum trial); a lane whose trial fails keeps its
-      // phase (COMPTON: new angle; SHELL: new shell at the accepted angle) and takes part in a later batch
       STAT_ADD(2, 1);
       STAT_ADD(3, __popcll(__ballot(in_compton(phase))));
       STAT_T0();
-      STAT_ADD(16, __popcll(__ballot(phase == PH_COMPTON)));
-      STAT_ADD(17, __popcll(__ballot(phase == PH_SHELL)));
-#if MC_STATS
-      const bool st_was_compton = in_compton(phase);
-#endif
-      if (in_compton(phase)) {
-        ComptonTrial c;
-        c.tau = h.aux;
-        if (compton_draw(A, h.P.E, h.mc, phase == PH_COMPTON, h.rng, c)) {
-          const float e_in = h.P.E;
-          polar_t omc;
-          h.aux = c.tau;
-          phase = PH_SHELL;
-          if (compton_momentum_trial(h.P.E, c, h.rng, omc)) {
-            rotate_dir(h.P, omc, h.rng);
-            if (A.dose_flags != 0 && (e_in - h.P.E) > 0.001f) tally_dose(A, h.P, e_in - h.P.E, h.mc);  // K.cu:299,356-367
-            h.index = energy_index(A, h.P.E);
-            if (h.index > -1) {
-              h.mfpW = LDS_F(SLDS(A, wood))[h.index >> kWoodShift];
-              negl2 = -0.69314718055994531f * h.mfpW;
-              mc_old = -2;
-              h.scatter = (h.scatter == 0) ? 1 : 3;
-              phase = PH_FLIGHT;
-            } else {
-              h.index = 0;
-              phase = PH_NEW;  // below the table cut-off: absorbed
-            }
-          }
-        }
-      }
-#if MC_STATS
-      STAT_ADD(18, __popcll(__ballot(st_was_compton && !in_compton(phase))));
-#endif
+      serve_compton(A, h, phase, mc_old, negl2, st);
       STAT_T1(12);
       STAT_T1(31);
     } else if (task == kQRayleigh) {
-      // Rayleigh (K.cu:329-347)
       STAT_ADD(4, 1);
       STAT_ADD(5, __popcll(__ballot(phase == PH_RAYLEIGH)));
       STAT_T0();
-      if (phase == PH_RAYLEIGH) {
-        const float pmaxn = as_global(SARG(A, mfp))[8u * table_row(A, h.index, h.mc) + 6u];  // pmax of bin index + 1 (K.cu:336)
-        polar_t omc;
-        if (rayleigh_trial(A, h.P.E, h.mc, pmaxn, h.rng, omc)) {
-          rotate_dir(h.P, omc, h.rng);
-          h.scatter = (h.scatter == 0) ? 2 : 3;
-          phase = PH_FLIGHT;
-        }
-      }
+      serve_rayleigh(A, h, phase);
       STAT_T1(13);
       STAT_T1(31);
     } else {
@@ -1182,79 +1124,11 @@ __global__ __launch_bounds__(kPoolBlock, kPoolWavesPerSimd) void track_wg_kernel
       STAT_ADD(6, 1);
       STAT_ADD(7, __popcll(__ballot(wants_new(phase))));
       STAT_T0();
-      int tally_word = -1;
-      unsigned int tally_value = 0;
-      if (phase == PH_ESCAPED) {
-        tally_word = tally_pixel(A, h.P, h.scatter);
-        tally_value = __float2uint_rn(h.P.E * 100.0f);
-        phase = PH_NEW;
-      } else if (phase == PH_ABSORBED) {
-        if (A.dose_flags != 0 && h.P.E > 0.001f) tally_dose(A, h.P, h.P.E, h.mc);
-        phase = PH_NEW;
-      }
-      unsigned long long my_hist = ~0ULL;
-      {
-        const unsigned long long need = __ballot(phase == PH_NEW);
-        const unsigned int n_need = (unsigned int)__popcll(need);
-        if (n_need != 0u) {
-          const unsigned int rank = (unsigned int)rank_in(need);
-          const unsigned long long avail = chunk_end - chunk_next;
-          if (avail >= n_need) {
-            my_hist = chunk_next + rank;
-            chunk_next += n_need;
-          } else {
-            if (rank < avail) my_hist = chunk_next + rank;
-            chunk_next = chunk_end;
-            const int leader = __ffsll((long long)need) - 1;
-            while (ctr_exhausted < (unsigned int)kNumCounters) {
-              const unsigned long long base = LARG(A, count) / kNumCounters * ctr + min((unsigned long long)ctr, LARG(A, count) % kNumCounters);
-              const unsigned long long size = LARG(A, count) / kNumCounters + (ctr < LARG(A, count) % kNumCounters ? 1ULL : 0ULL);
-              unsigned long long gv = 0;
-              if (lane == leader) gv = atomicAdd(LARG(A, work_counter) + ctr * (unsigned int)kCounterStride, (unsigned long long)kChunk);
-              const unsigned long long g = ((unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)(gv >> 32), leader) << 32) |
-                                           (unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)gv, leader);
-              if (g >= size) {
-                ++ctr_exhausted;
-                ctr = (ctr + 1u) % (unsigned int)kNumCounters;
-                continue;
-              }
-              const unsigned long long g_end = base + ((g + kChunk < size) ? g + kChunk : size);
-              const unsigned long long id = base + g + (rank - avail);
-              if (rank >= avail && id < g_end) my_hist = id;
-              chunk_next = min(base + g + (n_need - avail), g_end);
-              chunk_end = g_end;
-              break;
-            }
-          }
-        }
-      }
-      if (phase == PH_NEW) {
-        if (my_hist != ~0ULL) {
-          rng_init_history(h.rng, LARG(A, first) + my_hist, (unsigned int)LARG(A, seed), LARG(A, stream_key));
-          sample_source_energy(A, h.P, h.rng);
-          h.scatter = 0;
-          h.index = energy_index(A, h.P.E);
-          float2 t_ext = make_float2(0.f, 0.f);
-          if (A.has_exterior & 2) t_ext = exterior_record(A, h.index);
-          sample_source_direction(A, h.P, h.rng);
-          h.mfpW = LDS_F(SLDS(A, wood))[h.index >> kWoodShift];
-          negl2 = -0.69314718055994531f * h.mfpW;
-          mc_old = -1;
-          if (A.has_exterior & 2) {
-            source_entry(A, h, phase, t_ext);
-            if (phase == PH_REAL) {
-              const float4* rec = real_record(A, h);
-              classify_real(A, h, phase, rec[0], rec[1]);
-            }
-          } else {
-            bool miss;
-            move_to_bbox(A, h.P, miss);
-            phase = miss ? PH_ESCAPED : PH_FLIGHT;
-          }
-        } else if (ctr_exhausted >= (unsigned int)kNumCounters) {
-          phase = PH_DONE;
-        }
-      }
+      int tally_word;
+      unsigned int tally_value;
+      score_finished(A, h, phase, tally_word, tally_value);
+      const unsigned long long my_id = deal_history_ids(A, phase, chunk_next, chunk_end, ctr, ctr_exhausted);
+      start_history(A, h, phase, mc_old, negl2, my_id, ctr_exhausted);
       if (tally_word >= 0) tally_score(A, tally_word, tally_value);
       STAT_T1(14);
       STAT_T1(31);
@@ -1302,15 +1176,16 @@ static_assert(std::is_same<kernel_signature<decltype(&track_pool_kernel<kVolU8, 
 // resident workgroups per CU for this kernel variant (persistent grids must not over-subscribe)
 namespace {
 typedef void (*TrackKernel)(const TrackArgs);
+template <int VK>
+TrackKernel pick(bool wg, bool seg) {
+  return wg ? track_wg_kernel<VK> : (seg ? track_pool_kernel<VK, true> : track_pool_kernel<VK, false>);
+}
 TrackKernel pick_kernel(const TrackArgs& args) {
   const bool wg = args.sched_kind == 1, seg = args.segment_loop != 0;
   switch (args.vol_kind) {
-    case kVolU8:
-      if (args.sub_kind == 2) return wg ? track_wg_kernel<kVolU8Rec> : (seg ? track_pool_kernel<kVolU8Rec, true> : track_pool_kernel<kVolU8Rec, false>);
-      if (args.sub_kind == 1) return wg ? track_wg_kernel<kVolU8Sub> : (seg ? track_pool_kernel<kVolU8Sub, true> : track_pool_kernel<kVolU8Sub, false>);
-      return wg ? track_wg_kernel<kVolU8> : (seg ? track_pool_kernel<kVolU8, true> : track_pool_kernel<kVolU8, false>);
-    case kVolU16: return wg ? track_wg_kernel<kVolU16> : (seg ? track_pool_kernel<kVolU16, true> : track_pool_kernel<kVolU16, false>);
-    default: return wg ? track_wg_kernel<kVolRaw> : (seg ? track_pool_kernel<kVolRaw, true> : track_pool_kernel<kVolRaw, false>);
+    case kVolU8: return args.sub_kind == 2 ? pick<kVolU8Rec>(wg, seg) : (args.sub_kind == 1 ? pick<kVolU8Sub>(wg, seg) : pick<kVolU8>(wg, seg));
+    case kVolU16: return pick<kVolU16>(wg, seg);
+    default: return pick<kVolRaw>(wg, seg);
   }
 }
 }  // namespace
