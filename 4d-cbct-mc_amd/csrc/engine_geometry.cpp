@@ -294,9 +294,8 @@ int mcgpu_set_geometry_image(mcgpu_ctx* ctx, const int n[3], const float spacing
   MaterialTables mat;
   load_material_files(H.cfg.file_materials, v, mat);
   int roi[6], roi_old[6];
-  for (int k = 0; k < 6; ++k) roi[k] = roi_old[k] = H.cfg.dose_roi[k];
-  if (roi[1] > -1)
-    for (int ax = 0; ax < 3; ++ax) roi[2 * ax + 1] = std::min(roi[2 * ax + 1], v.n[ax] - 1);
+  for (int k = 0; k < 6; ++k) roi_old[k] = H.cfg.dose_roi[k];
+  clip_dose_roi(H.cfg.dose_roi_input, v.n, roi);  // from the input's ROI, whatever geometries came between; Error -2 when nothing of it is left
   std::swap(H.voxels, v);
   std::swap(H.mat, mat);
   for (int k = 0; k < 6; ++k) H.cfg.dose_roi[k] = roi[k];
@@ -391,9 +390,7 @@ int mcgpu_set_geometry_arrays(mcgpu_ctx* ctx, const int n[3], const float spacin
   MaterialTables mat;
   load_material_files(H.cfg.file_materials, v, mat);
   int roi[6];
-  for (int k = 0; k < 6; ++k) roi[k] = H.cfg.dose_roi[k];
-  if (roi[1] > -1)
-    for (int ax = 0; ax < 3; ++ax) roi[2 * ax + 1] = std::min(roi[2 * ax + 1], v.n[ax] - 1);
+  clip_dose_roi(H.cfg.dose_roi_input, v.n, roi);  // from the input's ROI, whatever geometries came between; Error -2 when nothing of it is left
   std::swap(H.voxels, v);
   std::swap(H.mat, mat);
   int roi_old[6];

@@ -288,6 +288,7 @@ void parse_input_file(const std::string& path, HostModel& m) {
     for (int ax = 0; ax < 3; ++ax)
       if (c.dose_roi[2 * ax] > c.dose_roi[2 * ax + 1] || c.dose_roi[2 * ax] < 0)
         fail(-2, "!!read_input ERROR!! The input region-of-interest in 'SECTION DOSE DEPOSITION' is not valid.");
+    for (int k = 0; k < 6; ++k) c.dose_roi_input[k] = c.dose_roi[k];
   } else if (starts_no(line)) {
     for (int ax = 0; ax < 3; ++ax) { c.dose_roi[2 * ax] = 32500; c.dose_roi[2 * ax + 1] = -32500; }
   } else {
@@ -864,6 +865,16 @@ void rebuild_woodcock(MaterialTables& t, const float density_max_in[kMaxMaterial
 }
 
 // ---------------------------------------------------------------------------------------------
+void clip_dose_roi(const int roi_input[6], const int n[3], int roi[6]) {
+  for (int k = 0; k < 6; ++k) roi[k] = roi_input[k];
+  if (roi_input[1] <= -1) return;  // no voxel tally
+  for (int ax = 0; ax < 3; ++ax) {
+    roi[2 * ax + 1] = std::min(roi_input[2 * ax + 1], n[ax] - 1);
+    if (roi[2 * ax] > roi[2 * ax + 1])
+      fail(-2, "!!read_input ERROR!! The input region-of-interest in 'SECTION DOSE DEPOSITION' is not valid.");
+  }
+}
+
 void load_model(const std::string& input_path, HostModel& m) {
   parse_input_file(input_path, m);
   load_spectrum(m.cfg.file_spectrum, m.spectrum);
@@ -879,9 +890,7 @@ void load_model(const std::string& input_path, HostModel& m) {
     else if (have_side && !knob_set("MCGPU_IGNORE_VOXBIN") && (!have_text || st_side.st_mtime >= st_text.st_mtime)) load_voxel_binary(side, m.voxels);
     else load_voxel_file(m.cfg.file_voxels, m.voxels);
   }
-  // the dose ROI may be given larger than the volume: clip its upper corner (load_voxels, :2058-2064)
-  if (m.cfg.dose_roi[1] > -1)
-    for (int ax = 0; ax < 3; ++ax) m.cfg.dose_roi[2 * ax + 1] = std::min(m.cfg.dose_roi[2 * ax + 1], m.voxels.n[ax] - 1);
+  clip_dose_roi(m.cfg.dose_roi_input, m.voxels.n, m.cfg.dose_roi);
   load_material_files(m.cfg.file_materials, m.voxels, m.mat);
   // consistency check of main() (:565-577)
   const float emax = m.mat.e0 + (m.mat.num_values - 1) / m.mat.ide;

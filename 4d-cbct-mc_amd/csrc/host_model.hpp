@@ -100,7 +100,8 @@ struct SimConfig {
   double D_angle = -1.0, angularROI_0 = 0.0, angularROI_1 = 360.0, initial_angle = 0.0;
   double SRotAxisD = -1.0, vertical_translation = 0.0;
   int flag_material_dose = 0;
-  int dose_roi[6] = {32500, -32500, 32500, -32500, 32500, -32500};  // xmin,xmax,ymin,ymax,zmin,zmax (0-based)
+  int dose_roi[6] = {32500, -32500, 32500, -32500, 32500, -32500};  // xmin,xmax,ymin,ymax,zmin,zmax (0-based), clipped to the volume in use
+  int dose_roi_input[6] = {32500, -32500, 32500, -32500, 32500, -32500};  // as the input file gave it: what every geometry's ROI is clipped from
   std::string file_voxels, file_output, file_dose_output, file_spectrum;
   std::vector<std::string> file_materials;  // up to 25, may contain empty strings
 };
@@ -121,6 +122,9 @@ void load_spectrum(const std::string& path, Spectrum& s);                  // in
 void load_voxel_file(const std::string& path, VoxelGrid& v, int n_threads = 0);  // load_voxels
 void load_material_files(const std::vector<std::string>& files, const VoxelGrid& v, MaterialTables& t);  // load_material
 void load_model(const std::string& input_path, HostModel& m);              // all of the above, reference order
+// The dose ROI in use for a volume of n[3] voxels: the input's ROI with its upper corner clipped to the volume (load_voxels,
+// :2058-2064).  A ROI that starts beyond the volume would come out inverted; here that is read_input's invalid ROI (Error -2).
+void clip_dose_roi(const int roi_input[6], const int n[3], int roi[6]);
 // Woodcock majorant table from the total mean free paths as read and the largest density of every material in the volume
 // (load_material :2294-2296 and :2433-2441): all a geometry change needs when the set of materials stays the same
 void rebuild_woodcock(MaterialTables& t, const float density_max[kMaxMaterials]);
