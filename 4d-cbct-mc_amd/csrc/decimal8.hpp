@@ -77,4 +77,26 @@ MCGPU_HD inline void finalize_pixel(uint64_t t0, uint64_t t1, uint64_t t2, uint6
   scattered = (f1 + f2) + f3;
 }
 
+// Variance of the value a plane of the projection reports for one pixel, from the pixel's tally words W = sum of the image words of
+// the plane's classes, Q = sum of their w2 words (tally_stage.hpp: squared weights in units of 2^20), N histories and
+// c = (1/100) * inv_px_X * inv_px_Z: the unbiased sample variance of the per-history score, over N -- in double, in exactly this order
+// (built without contraction on both sides, so host and device agree bit for bit).  A negative result (the truncation in w2 can
+// outweigh a single hit's spread) is 0, as is N < 2.
+MCGPU_HD inline float variance_value(uint64_t W, uint64_t Q, uint64_t N, double c) {
+  if (N < 2) return 0.0f;
+  const double w = (double)W, q = (double)Q, n = (double)N;
+  const double var = c * c * (1048576.0 * q - w * w / n) / (n * (n - 1.0));
+  return var > 0.0 ? (float)var : 0.0f;
+}
+
+// The three planes {total, unscattered, scattered} of one pixel: the class groups of finalize_pixel (integer sums: a history scores in
+// one class at most, so the moments of a group are the sums of its classes' moments).
+MCGPU_HD inline void variance_pixel(const uint64_t t[4], const uint64_t q[4], uint64_t N, double c, float& total, float& unscattered,
+                                    float& scattered) {
+  const uint64_t ws = t[1] + t[2] + t[3], qs = q[1] + q[2] + q[3];
+  total = variance_value(t[0] + ws, q[0] + qs, N, c);
+  unscattered = variance_value(t[0], q[0], N, c);
+  scattered = variance_value(ws, qs, N, c);
+}
+
 }  // namespace mcgpu

@@ -262,6 +262,7 @@ struct TrackArgs {
   unsigned long long* stats;  // diagnostic build only (kNumStats counters), else null
   unsigned long long* work_counter;  // FAST: kNumCounters id dispensers, kCounterStride words apart (zeroed before each launch)
   StageArgs stage;            // FAST: staging of the detector hits (tally_stage.hpp); region == null: direct atomics on `image`
+  unsigned long long* w2;     // second tally beside `image`: sum of tally_w2_term(w) per word (tally_stage.hpp), null: off.  Last: every other argument keeps its offset
 };
 
 }  // namespace mcgpu

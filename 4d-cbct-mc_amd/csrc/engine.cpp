@@ -143,6 +143,8 @@ int mcgpu_config_f64(const mcgpu_ctx* ctx, const char* key, double* value) {
   else if (k == "e0") *value = ctx->host.mat.e0;
   else if (k == "pixel_size_x_mm") *value = 10.0 / (double)ctx->host.detector[0].inv_pixel_size_X;
   else if (k == "pixel_size_z_mm") *value = 10.0 / (double)ctx->host.detector[0].inv_pixel_size_Z;
+  else if (k == "inv_pixel_size_x") *value = (double)ctx->host.detector[0].inv_pixel_size_X;  // [1/cm], the float32 the norms are built from
+  else if (k == "inv_pixel_size_z") *value = (double)ctx->host.detector[0].inv_pixel_size_Z;
   else if (k == "ide") *value = ctx->host.mat.ide;
   else if (k == "warp_kernel_ms") *value = ctx->dev.warp_kernel_ms;  // the warp kernel of the last mcgpu_warp_geometry / mcgpu_warp_geometry_signal (HIP events)
   else if (k == "warp_field_copy_ms") *value = ctx->dev.warp_field_copy_ms;  // host time of the field's copy in the last mcgpu_warp_geometry
@@ -291,6 +293,12 @@ int mcgpu_tally_stage_sub_launch(unsigned long long first, unsigned long long co
 
 int mcgpu_launch_projection(mcgpu_ctx* ctx, int p, int mode, int seed, unsigned long long first, unsigned long long count, int hpt,
                             void* image_dev, void* hip_stream) {
+  return mcgpu_launch_projection_w2(ctx, p, mode, seed, first, count, hpt, image_dev, nullptr, hip_stream);
+}
+
+// The launch, with the tally of squared weights `w2_dev` beside the image (tally_stage.hpp; null: none).
+int mcgpu_launch_projection_w2(mcgpu_ctx* ctx, int p, int mode, int seed, unsigned long long first, unsigned long long count, int hpt,
+                               void* image_dev, void* w2_dev, void* hip_stream) {
   ABI_BEGIN
   require(ctx && ctx->has_device, -1, "!!ERROR!! mcgpu_launch_projection: the context has no device (created with device_id < 0)");
   require(p >= 0 && p < ctx->host.cfg.num_projections, -1, "!!ERROR!! mcgpu_launch_projection: projection index out of range");
@@ -301,6 +309,7 @@ int mcgpu_launch_projection(mcgpu_ctx* ctx, int p, int mode, int seed, unsigned 
   hipStream_t stream = (hipStream_t)hip_stream;
   TrackArgs A = make_args(*ctx, p);
   A.image = (unsigned long long*)image_dev;
+  A.w2 = (unsigned long long*)w2_dev;
   A.seed = seed; A.hpt = hpt; A.first = first; A.count = count;
   HIP_TRY(hipEventRecord(D.ev_start, stream));
   if (count > 0) {
@@ -320,13 +329,20 @@ int mcgpu_launch_projection(mcgpu_ctx* ctx, int p, int mode, int seed, unsigned 
       if (D.resident_fast <= 0) {
         D.resident_fast = D.knobs.blocks_per_cu > 0 ? D.knobs.blocks_per_cu : std::min(occupancy_track_fast(A), occupancy_track_fast64(A));
         if (D.resident_fast <= 0) D.resident_fast = 1;
+        D.resident_covers_w2 = false;
+      }
+      if (A.w2 != nullptr && !D.resident_covers_w2) {  // one grid size for all instantiations of the context
+        if (D.knobs.blocks_per_cu <= 0) D.resident_fast = std::max(1, std::min(D.resident_fast, std::min(occupancy_track_fast_w2(A), occupancy_track_fast64_w2(A))));
+        D.resident_covers_w2 = true;
       }
       unsigned long long resident = (unsigned long long)D.num_cus * (unsigned long long)D.resident_fast;
       resident += resident * (unsigned long long)D.knobs.grid_spare_percent / 100ULL;  // spare workgroups: see the kernel's prologue
       A.work_counter = D.work_counter;
       // Staged detector tally (tally_stage.hpp): the launch is cut into sub-launches of at most the knob's limit -- history ids are
       // explicit (first + id), so a cut cannot move a result -- and each is followed by its fold, in this stream and inside the events.
-      const bool staged = stage_wanted(D);
+      // A launch with w2 stages wherever the model has a plan, against the default rule: its direct route is two atomics per hit,
+      // the fold's second pass over the records is cheaper (profiles/tally_variance_ab.md).  MCGPU_TALLY_STAGE=0 still forces the atomics.
+      const bool staged = A.w2 != nullptr ? (D.stage_cursor >= 0 && D.knobs.tally_stage != 0) : stage_wanted(D);
       const unsigned long long limit = staged ? D.knobs.stage_max_histories : count;
       const unsigned long long n_sub = staged ? stage_sub_launches(count, limit) : 1ULL;
       for (unsigned long long k = 0; k < n_sub; ++k) {
@@ -344,11 +360,14 @@ int mcgpu_launch_projection(mcgpu_ctx* ctx, int p, int mode, int seed, unsigned 
           throw Error(-2, "!!ERROR!! mcgpu_launch_projection: MCGPU_MODE_FAST_STATS needs the diagnostic library (libmcgpu_amd_stats.so, MCGPU_AMD_LIB)");
 #endif
         } else if (mode == MCGPU_MODE_FAST_F64) {
-          HIP_TRY(launch_track_fast64(A, blocks, stream));
+          HIP_TRY(A.w2 != nullptr ? launch_track_fast64_w2(A, blocks, stream) : launch_track_fast64(A, blocks, stream));
         } else {
-          HIP_TRY(launch_track_fast(A, blocks, stream));
+          HIP_TRY(A.w2 != nullptr ? launch_track_fast_w2(A, blocks, stream) : launch_track_fast(A, blocks, stream));
         }
-        if (A.stage.region != nullptr) HIP_TRY(launch_tally_fold(A.stage, (unsigned int)blocks, A.image, stream));
+        if (A.stage.region != nullptr) {
+          HIP_TRY(launch_tally_fold(A.stage, (unsigned int)blocks, A.image, stream));
+          if (A.w2 != nullptr) HIP_TRY(launch_tally_fold_squares(A.stage, (unsigned int)blocks, A.w2, stream));
+        }
       }
     }
   }
@@ -431,25 +450,29 @@ int mcgpu_copy_to_host(mcgpu_ctx* ctx, const void* src_dev, void* dst_host, size
 
 int mcgpu_run_projection(mcgpu_ctx* ctx, int p, int mode, int seed, unsigned long long first, unsigned long long count, int hpt,
                          uint64_t* image_host, double* kernel_seconds, unsigned long long* histories_done) {
+  return mcgpu_run_projection_w2(ctx, p, mode, seed, first, count, hpt, image_host, nullptr, kernel_seconds, histories_done);
+}
+
+int mcgpu_run_projection_w2(mcgpu_ctx* ctx, int p, int mode, int seed, unsigned long long first, unsigned long long count, int hpt,
+                            uint64_t* image_host, uint64_t* w2_host, double* kernel_seconds, unsigned long long* histories_done) {
   ABI_BEGIN
   require(ctx && ctx->has_device && image_host, -1, "!!ERROR!! mcgpu_run_projection: bad argument");
   HIP_TRY(hipSetDevice(ctx->dev.device_id));
   const size_t bytes = (size_t)32 * ctx->host.detector[0].total_pixels;
   if (!ctx->dev.scratch_image) ctx->dev.scratch_image = (unsigned long long*)ctx->dev.put(std::vector<unsigned char>(bytes, 0));  // kept for the next call
+  if (w2_host && !ctx->dev.scratch_w2) ctx->dev.scratch_w2 = (unsigned long long*)ctx->dev.put(std::vector<unsigned char>(bytes, 0));
   void* img = ctx->dev.scratch_image;
-  int rc = 0;
-  try {
-    HIP_TRY(hipMemset(img, 0, bytes));
-    rc = mcgpu_launch_projection(ctx, p, mode, seed, first, count, hpt, img, nullptr);
-    if (rc == 0) {
-      float ms = 0.f;
-      rc = mcgpu_last_kernel_ms(ctx, &ms);
-      if (kernel_seconds) *kernel_seconds = ms * 1e-3;
-      HIP_TRY(hipMemcpy(image_host, img, bytes, hipMemcpyDeviceToHost));
-      if (histories_done) *histories_done = (mode == MCGPU_MODE_COMPAT) ? count * (unsigned long long)hpt : count;
-    }
-  } catch (...) {
-    throw;
+  void* w2 = w2_host ? ctx->dev.scratch_w2 : nullptr;
+  HIP_TRY(hipMemset(img, 0, bytes));
+  if (w2) HIP_TRY(hipMemset(w2, 0, bytes));
+  int rc = mcgpu_launch_projection_w2(ctx, p, mode, seed, first, count, hpt, img, w2, nullptr);
+  if (rc == 0) {
+    float ms = 0.f;
+    rc = mcgpu_last_kernel_ms(ctx, &ms);
+    if (kernel_seconds) *kernel_seconds = ms * 1e-3;
+    HIP_TRY(hipMemcpy(image_host, img, bytes, hipMemcpyDeviceToHost));
+    if (w2) HIP_TRY(hipMemcpy(w2_host, w2, bytes, hipMemcpyDeviceToHost));
+    if (histories_done) *histories_done = (mode == MCGPU_MODE_COMPAT) ? count * (unsigned long long)hpt : count;
   }
   return rc;
   ABI_END
@@ -625,6 +648,28 @@ int mcgpu_finalize_projection_host(const mcgpu_ctx* ctx, const uint64_t* image_h
   ABI_BEGIN
   require(ctx && image_host && planes_host && total_histories > 0, -1, "!!ERROR!! mcgpu_finalize_projection_host: bad argument");
   finalize_projection_host(ctx->host, image_host, total_histories, crop_nx, planes_host);
+  return 0;
+  ABI_END
+}
+
+int mcgpu_finalize_variance(mcgpu_ctx* ctx, const void* image_dev, void* w2_dev, unsigned long long total_histories, int crop_nx, void* planes_dev,
+                            int clear_w2, void* hip_stream) {
+  ABI_BEGIN
+  require(ctx && ctx->has_device && image_dev && w2_dev && planes_dev, -1, "!!ERROR!! mcgpu_finalize_variance: bad argument");
+  HIP_TRY(hipSetDevice(ctx->dev.device_id));
+  const DetectorPose& d0 = ctx->host.detector[0];
+  const int cx = (crop_nx > 0 && crop_nx < d0.nx) ? crop_nx : d0.nx;
+  HIP_TRY(launch_finalize_variance((const unsigned long long*)image_dev, (unsigned long long*)w2_dev, d0.nx, d0.nz, cx, total_histories,
+                                   variance_scale(ctx->host), (float*)planes_dev, clear_w2, (hipStream_t)hip_stream));
+  return 0;
+  ABI_END
+}
+
+int mcgpu_finalize_variance_host(const mcgpu_ctx* ctx, const uint64_t* image_host, const uint64_t* w2_host, unsigned long long total_histories,
+                                 int crop_nx, float* planes_host) {
+  ABI_BEGIN
+  require(ctx && image_host && w2_host && planes_host, -1, "!!ERROR!! mcgpu_finalize_variance_host: bad argument");
+  finalize_variance_host(ctx->host, image_host, w2_host, total_histories, crop_nx, planes_host);
   return 0;
   ABI_END
 }

@@ -32,12 +32,18 @@ hipError_t launch_track_fast(const TrackArgs& args, int blocks, hipStream_t stre
 int occupancy_track_fast(const TrackArgs& args);
 hipError_t launch_track_fast64(const TrackArgs& args, int blocks, hipStream_t stream);  // MCGPU_MODE_FAST_F64 (track_fast64.hip)
 int occupancy_track_fast64(const TrackArgs& args);
+// the same kernels with the second add of the direct tally route, for launches with a w2 (track_fast_w2.hip, track_fast64_w2.hip)
+hipError_t launch_track_fast_w2(const TrackArgs& args, int blocks, hipStream_t stream);
+int occupancy_track_fast_w2(const TrackArgs& args);
+hipError_t launch_track_fast64_w2(const TrackArgs& args, int blocks, hipStream_t stream);
+int occupancy_track_fast64_w2(const TrackArgs& args);
 hipError_t launch_kat_fast64(int n, const unsigned int* u, const double* a, const double* b, const double* c, const float* dir, double* out, hipStream_t stream);
 #if defined(MC_WITH_STATS) && MC_WITH_STATS
 hipError_t launch_track_stats(const TrackArgs& args, int blocks, hipStream_t stream);  // diagnostic library only (track_stats.o)
 #endif
 hipError_t prepare_tally_fold(const StageArgs& S);  // tally_fold.hip
 hipError_t launch_tally_fold(const StageArgs& S, unsigned int workgroups, unsigned long long* image, hipStream_t stream);
+hipError_t launch_tally_fold_squares(const StageArgs& S, unsigned int workgroups, unsigned long long* w2, hipStream_t stream);
 hipError_t microbench_valu_issue(int num_cus, double out3[3], hipStream_t stream);
 hipError_t microbench_atomic_rate(double* out, hipStream_t stream);
 hipError_t microbench_copy_rate(int num_cus, double* out, hipStream_t stream);
@@ -50,7 +56,8 @@ hipError_t launch_kat_f32(int op, int n, const float* a, const float* b, float* 
 hipError_t launch_warp(int nx, int ny, int nz, const unsigned char* mat, const float* dens, const float* dvf, unsigned char default_mat,
                        float default_dens, unsigned char* out_mat, float* out_dens, hipStream_t stream);
 hipError_t launch_finalize(unsigned long long* image, int nx, int nz, int crop_nx, double norm, float* planes, int clear, hipStream_t stream);
-
+hipError_t launch_finalize_variance(const unsigned long long* image, unsigned long long* w2, int nx, int nz, int crop_nx, unsigned long long histories,
+                                    double c, float* planes, int clear, hipStream_t stream);
 
 int set_error(int code, const std::string& msg);  // engine.cpp: records the calling thread's last error, returns `code`
 
@@ -143,6 +150,7 @@ struct DeviceModel {
   SourcePose* src_all = nullptr;  // [num_projections]
   DetectorPose* det_all = nullptr;
   int resident_fast = 0;  // workgroups per CU (occupancy query), 0 = not asked yet
+  bool resident_covers_w2 = false;  // ... and the w2 instantiations have been asked too (at the first launch with a w2)
   unsigned long long* stats = nullptr;  // kNumStats scheduler counters of the diagnostic build
   unsigned long long* work_counter = nullptr;  // history-id dispenser of the FAST kernel
   // staged detector tally (tally_stage.hpp): the cursor table's place in the LDS image is fixed at upload (-1: it does not fit, this
@@ -157,6 +165,7 @@ struct DeviceModel {
   bool stage_alloc_failed = false, stage_fold_ready = false;
   TallyStagePlan stage_plan{};  // of the last staged (sub-)launch
   unsigned long long* scratch_image = nullptr;  // device tally of mcgpu_run_projection (allocated on first use)
+  unsigned long long* scratch_w2 = nullptr;     // ... and the squared weights of mcgpu_run_projection_w2
   float *woodcock = nullptr, *mfp = nullptr, *mfp_tot = nullptr;
   float* wood_coarse = nullptr;  // FAST: majorant per coarse energy bin (LdsLayout::wood), rebuilt with the Woodcock table
   int sig_shift = -1;            // cross-section brackets of the FAST flight step (model_device.cpp: sigma_brackets), -1: none

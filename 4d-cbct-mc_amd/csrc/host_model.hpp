@@ -161,6 +161,10 @@ void format_materials_dose_report(const HostModel& m, const uint64_t* materials_
 struct MhaStack;
 void finalize_projection_host(const HostModel& m, const uint64_t* image, unsigned long long total_histories, int crop_nx, float* planes,
                               int n_threads = 0);
+// c of the variance planes: the pixel value per unit of tally, NORM without the histories ((1/100) * inv_px_X * inv_px_Z)
+inline double variance_scale(const HostModel& m) { return (1.0 / 100.0) * m.detector[0].inv_pixel_size_X * m.detector[0].inv_pixel_size_Z; }
+void finalize_variance_host(const HostModel& m, const uint64_t* image, const uint64_t* w2, unsigned long long total_histories, int crop_nx,
+                            float* planes);
 MhaStack* mha_create(const std::string& path, int nx, int ny, int nslices, double sx, double sy);
 void mha_append(MhaStack* s, const float* plane);
 void mha_write_slice(MhaStack* s, int k, const float* plane);

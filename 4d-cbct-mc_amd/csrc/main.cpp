@@ -20,6 +20,8 @@
 //   --no-output          skip the ASCII projection files (timing runs, or stacks only)
 //   --stacks             also write projections_{total,unscattered,scattered}.mha next to the projection files
 //                        (what cbctmc/mc/simulation.py:235-277 builds from the ASCII files afterwards)
+//   --variance           with --stacks, one device: also write projections_{total,unscattered,scattered}_variance.mha, the per-pixel
+//                        variance of the stacks from the squared weights tallied in the same run (mcgpu_finalize_variance)
 //   --crop N             half-fan crop of the stacks (default 1024 when the detector has 1848 columns, else none)
 //   --air FILE           air scan's projections_total.mha: also write projections_total_normalized.mha
 // A value of --mode, --shard or --reduce outside these sets prints the usage and exits before anything is read.
@@ -51,7 +53,7 @@ static int choose(const char* option, const char* arg, const Choice* choices) {
   for (const Choice* c = choices; c->name; ++c)
     if (!strcmp(arg, c->name)) return c->value;
   printf("\n\n   !!ERROR!! unknown value '%s' of %s\n   usage: MC-GPU_v1.3.x <input.in> [--mode fast|fast64|compat] [--gpus N] [--devices a,b,...]\n"
-         "          [--shard histories|projections] [--reduce exchange|rccl] [--no-output] [--stacks] [--crop N] [--air FILE]\n\n", arg, option);
+         "          [--shard histories|projections] [--reduce exchange|rccl] [--no-output] [--stacks] [--variance] [--crop N] [--air FILE]\n\n", arg, option);
   exit(255);
 }
 
@@ -67,7 +69,7 @@ int main(int argc, char** argv) {
     return 0;
   }
   int mode = MCGPU_MODE_FAST, ngpu = 1, shard = MCGPU_SHARD_HISTORIES, reduce = MCGPU_REDUCE_AUTO;
-  bool write_out = true, stacks = false;
+  bool write_out = true, stacks = false, variance = false;
   int crop = -1;
   const char* air = nullptr;
   std::vector<int> device_list;
@@ -79,6 +81,7 @@ int main(int argc, char** argv) {
         if (*s == ',') ++s;
       }
     } else if (!strcmp(argv[i], "--stacks")) stacks = true;
+    else if (!strcmp(argv[i], "--variance")) variance = true;
     else if (!strcmp(argv[i], "--crop") && i + 1 < argc) crop = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--air") && i + 1 < argc) air = argv[++i];
     else if (!strcmp(argv[i], "--mode") && i + 1 < argc) { mode = choose(argv[i], argv[i + 1], kModes); ++i; }
@@ -130,12 +133,14 @@ int main(int argc, char** argv) {
   so.crop_nx = (crop > 0 && crop < det_nx) ? crop : (int)det_nx;
   so.write_ascii = write_out ? 1 : 0;
   so.write_stacks = stacks ? 1 : 0;
+  so.write_variance = variance ? 1 : 0;
   so.air_stack = air;
   so.air_sigma_y = so.air_sigma_x = 10.0;               // cbctmc/mc/simulation.py:239
   so.pixel_spacing_x = so.pixel_spacing_y = 0.776;      // cbctmc/mc/projection.py:73
   mcgpu_scan_report sr;
   memset(&sr, 0, sizeof sr);
-  if (mcgpu_run_scan_multi(ctx.data(), ngpu, &so, &sr) != 0) { printf("\n\n   %s\n\n", mcgpu_last_error()); return 253; }
+  // the variance stacks are a one-device output: the multi-device entry refuses them by name
+  if ((ngpu == 1 && variance ? mcgpu_run_scan(ctx[0], &so, &sr) : mcgpu_run_scan_multi(ctx.data(), ngpu, &so, &sr)) != 0) { printf("\n\n   %s\n\n", mcgpu_last_error()); return 253; }
   const unsigned long long total = sr.histories_per_projection;
   printf("          *** SCAN PERFORMANCE REPORT ***\n              Devices:             %d\n              Projections:         %d\n"
          "              Simulated x rays:    %llu per projection\n              Kernel time [s]:     %.3f\n"

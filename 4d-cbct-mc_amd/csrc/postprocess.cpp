@@ -50,6 +50,25 @@ void finalize_projection_host(const HostModel& m, const uint64_t* image, unsigne
   for (auto& x : th) x.join();
 }
 
+// The variance planes of the same projection (decimal8.hpp: variance_pixel), bit-identical to finalize.hip's variance_kernel
+void finalize_variance_host(const HostModel& m, const uint64_t* image, const uint64_t* w2, unsigned long long total_histories, int crop_nx,
+                            float* planes) {
+  const DetectorPose& d0 = m.detector[0];
+  const int nx = d0.nx, nz = d0.nz;
+  const int cx = (crop_nx > 0 && crop_nx < nx) ? crop_nx : nx;
+  const size_t npix = (size_t)nx * nz, plane = (size_t)cx * nz;
+  const double c = variance_scale(m);
+  for (int zo = 0; zo < nz; ++zo) {
+    const size_t src = (size_t)(nz - 1 - zo) * nx, dst = (size_t)zo * cx;
+    for (int x = 0; x < cx; ++x) {
+      const size_t i = src + x;
+      const uint64_t t[4] = {image[i], image[i + npix], image[i + 2 * npix], image[i + 3 * npix]};
+      const uint64_t q[4] = {w2[i], w2[i + npix], w2[i + 2 * npix], w2[i + 3 * npix]};
+      variance_pixel(t, q, total_histories, c, planes[dst + x], planes[plane + dst + x], planes[2 * plane + dst + x]);
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // MetaImage (.mha) float32 stack, written plane by plane.  Header fields as ITK's MetaImageIO writes them for
 // sitk.GetImageFromArray(stack) with SetSpacing((sx, sy, 1)) and SetOrigin((-nx*sx/2, -ny*sy/2, 0))

@@ -95,6 +95,11 @@ struct ScanPlan {
   std::vector<int> sim, ord;
   int cx = 0;                   // columns of the stacks (half-fan crop)
   size_t words = 0, plane = 0;  // uint64 words of one tally, floats of one cropped plane
+  // write_variance: the squared weights (mcgpu_launch_projection_w2) live directly behind the image in the same allocation -- one
+  // buffer of 2 x words that is zeroed, and would be exchanged, as one -- and the three variance planes directly behind the three planes
+  bool variance = false;
+  size_t tally_words() const { return variance ? 2 * words : words; }
+  size_t planes() const { return variance ? 6 : 3; }
   double sx = 0.0, sy = 0.0;    // MetaImage spacing
   std::string folder;
 
@@ -147,6 +152,7 @@ ScanPlan plan_scan(mcgpu_ctx* const* ctxs, int n_ctx, const mcgpu_scan_options* 
   s.cx = (opt->crop_nx > 0 && opt->crop_nx < s.nx) ? opt->crop_nx : (int)s.nx;
   s.words = (size_t)4 * s.nx * s.nz;
   s.plane = (size_t)s.cx * s.nz;
+  s.variance = opt->write_variance != 0;
   s.sx = opt->pixel_spacing_x > 0 ? opt->pixel_spacing_x : px_x;
   s.sy = opt->pixel_spacing_y > 0 ? opt->pixel_spacing_y : px_z;
   if (opt->output_folder) s.folder = opt->output_folder;
@@ -255,24 +261,37 @@ int side_by_side(const F& f) {
 // The scan's own MetaImage stacks {total, unscattered, scattered}: stacks that are not finished are closed when this goes.
 struct OutputStacks {
   mcgpu_stack* stack[3] = {nullptr, nullptr, nullptr};
+  mcgpu_stack* variance[3] = {nullptr, nullptr, nullptr};  // write_variance: the per-pixel variance of each stack
   ~OutputStacks() {
     for (mcgpu_stack* st : stack)
       if (st) (void)mcgpu_stack_finish(st, 0, nullptr);  // error path: close the files
+    for (mcgpu_stack* st : variance)
+      if (st) (void)mcgpu_stack_finish(st, 0, nullptr);
   }
   bool open() const { return stack[0] != nullptr; }
   void create(const ScanPlan& plan) {
     static const char* kNames[3] = {"projections_total.mha", "projections_unscattered.mha", "projections_scattered.mha"};
     for (int k = 0; k < 3; ++k) ABI_OK(mcgpu_stack_create((plan.folder + "/" + kNames[k]).c_str(), plan.cx, (int)plan.nz, plan.count(), plan.sx, plan.sy, &stack[k]));
+    static const char* kVariance[3] = {"projections_total_variance.mha", "projections_unscattered_variance.mha", "projections_scattered_variance.mha"};
+    for (int k = 0; k < 3 && plan.variance; ++k)
+      ABI_OK(mcgpu_stack_create((plan.folder + "/" + kVariance[k]).c_str(), plan.cx, (int)plan.nz, plan.count(), plan.sx, plan.sy, &variance[k]));
   }
   // a projection's three planes, side by side (each append scans its plane for zeros and copies it into the page cache)
   int append(const float* planes, size_t plane) {
-    return side_by_side([&](int k) { return mcgpu_stack_append(stack[k], planes + (size_t)k * plane); });
+    if (const int rc = side_by_side([&](int k) { return mcgpu_stack_append(stack[k], planes + (size_t)k * plane); })) return rc;
+    if (!variance[0]) return 0;
+    return side_by_side([&](int k) { return mcgpu_stack_append(variance[k], planes + (size_t)(3 + k) * plane); });
   }
   // zero replacement and close side by side, then the air normalisation of the total stack
   void finish(const ScanPlan& plan, const mcgpu_scan_options* opt, float repl[3]) {
     mcgpu_stack* st[3] = {stack[0], stack[1], stack[2]};
     stack[0] = stack[1] = stack[2] = nullptr;
     if (const int rc = side_by_side([&](int k) { return mcgpu_stack_finish(st[k], 1, &repl[k]); })) throw ScanError{rc, mcgpu_last_error()};
+    if (variance[0]) {  // a variance of zero is a value: no replacement
+      mcgpu_stack* sv[3] = {variance[0], variance[1], variance[2]};
+      variance[0] = variance[1] = variance[2] = nullptr;
+      if (const int rc = side_by_side([&](int k) { return mcgpu_stack_finish(sv[k], 0, nullptr); })) throw ScanError{rc, mcgpu_last_error()};
+    }
     if (opt->air_stack)
       ABI_OK(mcgpu_normalize_stack((plan.folder + "/projections_total.mha").c_str(), opt->air_stack, opt->air_sigma_y, opt->air_sigma_x,
                                    (plan.folder + "/projections_total_normalized.mha").c_str(), plan.sx, plan.sy));
@@ -488,11 +507,11 @@ struct HistoryScan {
       HIP_OK(hipSetDevice(l.dev));
       HIP_OK(hipStreamCreate(l.stream.make(l.dev)));
       if (!use_rccl) {
-        ABI_OK(mcgpu_exchange_create(l.dev, g, n, plan.words, policy, mailboxes.data(), &l.x));
+        ABI_OK(mcgpu_exchange_create(l.dev, g, n, plan.tally_words(), policy, mailboxes.data(), &l.x));
         continue;
       }
       // every device keeps its double-buffered tally in an exchange end of its own (a world of one: begin / submit / collect stay local)
-      ABI_OK(mcgpu_exchange_create(l.dev, 0, 1, plan.words, MCGPU_EXCHANGE_LOCAL, mailboxes.data() + (size_t)g * shared_bytes, &l.x));
+      ABI_OK(mcgpu_exchange_create(l.dev, 0, 1, plan.tally_words(), MCGPU_EXCHANGE_LOCAL, mailboxes.data() + (size_t)g * shared_bytes, &l.x));
       HIP_OK(hipStreamCreateWithFlags(l.reduce.make(l.dev), hipStreamNonBlocking));
       for (int b = 0; b < 2; ++b) {
         HIP_OK(hipEventCreateWithFlags(l.tracked[b].make(l.dev), hipEventDisableTiming));
@@ -526,7 +545,7 @@ struct HistoryScan {
       HIP_OK(hipStreamCreateWithFlags(l.copy.make(l.dev), hipStreamNonBlocking));
       for (int b = 0; b < 2; ++b) {
         HIP_OK(hipEventCreateWithFlags(l.finalized[b].make(l.dev), hipEventDisableTiming));
-        HIP_OK(hipMalloc(l.planes_dev[b].make(l.dev), 3 * plan.plane * 4));
+        HIP_OK(hipMalloc(l.planes_dev[b].make(l.dev), plan.planes() * plan.plane * 4));
         // the writer thread reads non-coherent pinned memory after waiting on this event: that needs a SYSTEM-scope release,
         // which a default event does not promise (device scope only)
         HIP_OK(hipEventCreateWithFlags(l.done[b].make(l.dev), hipEventDisableTiming | hipEventReleaseToSystem));
@@ -538,7 +557,7 @@ struct HistoryScan {
     const int dev0 = lanes[0].dev;
     HIP_OK(hipSetDevice(dev0));
     for (int b = 0; b < 2; ++b) {
-      HIP_OK(hipHostMalloc(planes_host[b].make(dev0), 3 * plan.plane * 4, pinned_flags));
+      HIP_OK(hipHostMalloc(planes_host[b].make(dev0), plan.planes() * plan.plane * 4, pinned_flags));
       if (opt->write_ascii && out.ascii_on_host) HIP_OK(hipHostMalloc(image_host[b].make(dev0), plan.words * 8, pinned_flags));
     }
     if (opt->write_stacks && !opt->shared_stacks && plan.count() > 0) stacks.create(plan);
@@ -557,7 +576,8 @@ struct HistoryScan {
       void* tally = nullptr;
       if (use_rccl && l.reduced_valid[b]) HIP_OK(hipStreamWaitEvent(l.stream, l.reduced[b], 0));  // begin() zeroes the buffer the collective of i - 2 read
       ABI_OK(mcgpu_exchange_begin(l.x, i, l.stream, &tally));
-      ABI_OK(mcgpu_launch_projection(l.ctx, p, plan.mode, seed, l.lo, l.hi - l.lo, shape.hpt, tally, l.stream));
+      void* const w2 = plan.variance ? (void*)((unsigned long long*)tally + plan.words) : nullptr;
+      ABI_OK(mcgpu_launch_projection_w2(l.ctx, p, plan.mode, seed, l.lo, l.hi - l.lo, shape.hpt, tally, w2, l.stream));
       ABI_OK(mcgpu_exchange_submit(l.x, i, l.stream));
       if (use_rccl) {
         l.tally[b] = tally;
@@ -580,7 +600,7 @@ struct HistoryScan {
         bufs[(size_t)g] = lanes[g].tally[b];
         streams[(size_t)g] = (void*)(hipStream_t)lanes[g].reduce;
       }
-      ABI_OK(mcgpu_rccl_reduce_u64(rccl, bufs.data(), plan.words, o, streams.data()));
+      ABI_OK(mcgpu_rccl_reduce_u64(rccl, bufs.data(), plan.tally_words(), o, streams.data()));
       for (Lane& l : lanes) {
         HIP_OK(hipSetDevice(l.dev));
         HIP_OK(hipEventRecord(l.reduced[b], l.reduce));
@@ -606,11 +626,13 @@ struct HistoryScan {
     // planes_dev[b] was last downloaded two projections ago (by this device, if it owned that one)
     if (l.done_valid[b]) HIP_OK(hipStreamWaitEvent(so, l.done[b], 0));
     ABI_OK(mcgpu_finalize_projection(l.ctx, tally, shape.total, plan.cx, l.planes_dev[b], 0, so));  // begin() zeroes the buffer for its next user
+    if (plan.variance)
+      ABI_OK(mcgpu_finalize_variance(l.ctx, tally, (unsigned long long*)tally + plan.words, shape.total, plan.cx, (float*)(void*)l.planes_dev[b] + 3 * plan.plane, 0, so));
     // the 9 MB of planes go to the host on a copy engine, beside the next tracking kernel (on the tracking stream the copy held
     // the next launch back by 0.17 ms per projection)
     HIP_OK(hipEventRecord(l.finalized[b], so));
     HIP_OK(hipStreamWaitEvent(l.copy, l.finalized[b], 0));
-    HIP_OK(hipMemcpyAsync(planes_host[b], l.planes_dev[b], 3 * plan.plane * 4, hipMemcpyDeviceToHost, l.copy));
+    HIP_OK(hipMemcpyAsync(planes_host[b], l.planes_dev[b], plan.planes() * plan.plane * 4, hipMemcpyDeviceToHost, l.copy));
     HIP_OK(hipEventRecord(l.done[b], l.copy));
     l.done_valid[b] = true;
   }
@@ -772,7 +794,12 @@ int run_scan_sharing_projections(mcgpu_ctx* const* ctxs, int n_ctx, const mcgpu_
 
 }  // namespace
 
-extern "C" int mcgpu_run_scan_multi(mcgpu_ctx* const* ctxs, int n_ctx, const mcgpu_scan_options* caller_opt, mcgpu_scan_report* report) {
+namespace {
+int refuse(const char* message) { mcgpu_set_last_error_(message); return -1; }
+}  // namespace
+
+// Both entry points; `multi`: through mcgpu_run_scan_multi
+static int run_scan_entry(mcgpu_ctx* const* ctxs, int n_ctx, const mcgpu_scan_options* caller_opt, mcgpu_scan_report* report, bool multi) {
   if (!ctxs || n_ctx < 1 || !caller_opt || !ctxs[0]) { mcgpu_set_last_error_("!!ERROR!! mcgpu_run_scan: null argument"); return -1; }
   // a caller built against an older header passes a shorter struct: what it does not have reads as zero
   if (caller_opt->struct_size < sizeof(unsigned int) + sizeof(int)) {
@@ -784,6 +811,13 @@ extern "C" int mcgpu_run_scan_multi(mcgpu_ctx* const* ctxs, int n_ctx, const mcg
   memcpy(&local, caller_opt, std::min<size_t>(caller_opt->struct_size, sizeof local));
   local.struct_size = (unsigned int)sizeof local;
   const mcgpu_scan_options* opt = &local;
+  // the variance stacks: an output of the one-device scan's own stacks (4-D and multi-device variance are not built yet); an unknown
+  // mode is still reported first, by plan_scan
+  if (opt->write_variance && (opt->mode == MCGPU_MODE_FAST || opt->mode == MCGPU_MODE_COMPAT || opt->mode == MCGPU_MODE_FAST_F64)) {
+    if (multi) return refuse("!!ERROR!! mcgpu_run_scan_multi: write_variance is an option of mcgpu_run_scan (one device)");
+    if (!opt->write_stacks) return refuse("!!ERROR!! mcgpu_run_scan: write_variance needs write_stacks (the variance stacks are written beside the stacks)");
+    if (opt->shared_stacks) return refuse("!!ERROR!! mcgpu_run_scan: write_variance cannot be combined with shared_stacks");
+  }
   for (int g = 0; g < n_ctx; ++g)
     if (!ctxs[g]) { mcgpu_set_last_error_("!!ERROR!! mcgpu_run_scan: null context"); return -1; }
   if (n_ctx > 1 && opt->shard == MCGPU_SHARD_PROJECTIONS) return run_scan_sharing_projections(ctxs, n_ctx, opt, report);
@@ -829,6 +863,10 @@ extern "C" int mcgpu_run_scan_multi(mcgpu_ctx* const* ctxs, int n_ctx, const mcg
   return run_scan_sharing_projections(ctxs, n_ctx, opt, report);
 }
 
+extern "C" int mcgpu_run_scan_multi(mcgpu_ctx* const* ctxs, int n_ctx, const mcgpu_scan_options* options, mcgpu_scan_report* report) {
+  return run_scan_entry(ctxs, n_ctx, options, report, true);
+}
+
 extern "C" int mcgpu_run_scan(mcgpu_ctx* ctx, const mcgpu_scan_options* opt, mcgpu_scan_report* report) {
-  return mcgpu_run_scan_multi(&ctx, 1, opt, report);
+  return run_scan_entry(&ctx, 1, opt, report, false);
 }

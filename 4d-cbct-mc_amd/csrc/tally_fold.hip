@@ -5,7 +5,10 @@
 // producing workgroups are spread over the waves, read with 16-byte loads (a block starts on 16 bytes: the capacity is even) and
 // added with ds_add_u64.  Then every non-zero counter is added to its tally word with a plain load, add and store: bins are
 // disjoint, the fold runs in the stream behind the track kernel, and that kernel's own (fallback) atomics are complete at the
-// kernel boundary.  The name keeps clear of "track_..._kernel", the pattern by which the PMC tools select the track kernel's rows.
+// kernel boundary.  A launch that tallies squared weights runs the same walk a second time over the same records with kSquares, adding
+// tally_w2_term(value) into the same counters and those into `w2`: a second launch, not a second counter set in one kernel -- two sets
+// are 256 KiB at the plan's largest bin (4096 pixels; 160 KiB of LDS hold both only up to 2560), and the plain fold stays the
+// instruction stream it was (profiles/tally_variance_ab.md).  The name keeps clear of "track_..._kernel", the pattern by which the PMC tools select the track kernel's rows.
 #include <hip/hip_runtime.h>
 
 #include "tally_stage.hpp"
@@ -16,11 +19,14 @@ namespace {
 constexpr int kFoldThreads = 1024;
 extern __shared__ __attribute__((aligned(16))) unsigned long long fold_lds[];
 
+template <bool kSquares>
 __device__ __forceinline__ void fold_add(unsigned long long record, unsigned int words) {
   const unsigned int rel = (unsigned int)(record >> 32);
-  if (rel < words) atomicAdd(fold_lds + rel, record & 0xFFFFFFFFULL);
+  const unsigned long long value = record & 0xFFFFFFFFULL;
+  if (rel < words) atomicAdd(fold_lds + rel, kSquares ? tally_w2_term(value) : value);
 }
 
+template <bool kSquares>
 __global__ __launch_bounds__(kFoldThreads) void tally_stage_fold(const StageArgs S, const unsigned int workgroups, unsigned long long* __restrict__ image) {
   const unsigned int bin = blockIdx.x, words = 4u * S.bin_pixels;
   for (unsigned int i = threadIdx.x; i < words; i += kFoldThreads) fold_lds[i] = 0ULL;
@@ -55,16 +61,16 @@ __global__ __launch_bounds__(kFoldThreads) void tally_stage_fold(const StageArgs
       for (unsigned int u = 0; u < kGroup; ++u) {
 #pragma unroll
         for (unsigned int j = 0; j < kDeep; ++j) {
-          fold_add(r[u][j].x, words);
-          fold_add(r[u][j].y, words);
+          fold_add<kSquares>(r[u][j].x, words);
+          fold_add<kSquares>(r[u][j].y, words);
         }
         const ulonglong2* const src2 = reinterpret_cast<const ulonglong2*>(src[u]);
         for (unsigned int i = lane + 64u * kDeep; i < (n[u] >> 1); i += 64u) {  // blocks beyond 512 records
           const ulonglong2 a = src2[i];
-          fold_add(a.x, words);
-          fold_add(a.y, words);
+          fold_add<kSquares>(a.x, words);
+          fold_add<kSquares>(a.y, words);
         }
-        if ((n[u] & 1u) != 0u && lane == 0u) fold_add(src[u][n[u] - 1u], words);
+        if ((n[u] & 1u) != 0u && lane == 0u) fold_add<kSquares>(src[u][n[u] - 1u], words);
       }
     }
   }
@@ -83,11 +89,19 @@ __global__ __launch_bounds__(kFoldThreads) void tally_stage_fold(const StageArgs
 hipError_t prepare_tally_fold(const StageArgs& S) {
   const size_t lds = (size_t)4 * S.bin_pixels * 8;
   if (lds <= 64 * 1024) return hipSuccess;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(&tally_stage_fold), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&tally_stage_fold<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(&tally_stage_fold<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 }
 
 hipError_t launch_tally_fold(const StageArgs& S, unsigned int workgroups, unsigned long long* image, hipStream_t stream) {
-  hipLaunchKernelGGL(tally_stage_fold, dim3(S.n_bins), dim3(kFoldThreads), (size_t)4 * S.bin_pixels * 8, stream, S, workgroups, image);
+  hipLaunchKernelGGL(tally_stage_fold<false>, dim3(S.n_bins), dim3(kFoldThreads), (size_t)4 * S.bin_pixels * 8, stream, S, workgroups, image);
+  return hipGetLastError();
+}
+
+// the squares of the same records into `w2`
+hipError_t launch_tally_fold_squares(const StageArgs& S, unsigned int workgroups, unsigned long long* w2, hipStream_t stream) {
+  hipLaunchKernelGGL(tally_stage_fold<true>, dim3(S.n_bins), dim3(kFoldThreads), (size_t)4 * S.bin_pixels * 8, stream, S, workgroups, w2);
   return hipGetLastError();
 }
 

@@ -10,6 +10,13 @@
 //   * a bin holds its pixels in all four planes: bin-relative word = plane * bin_pixels + offset  (< words_per_bin = 4 * bin_pixels);
 //   * a record is {value = round(E * 100) in the low dword, bin-relative word in the high dword}.
 // Integer sums commute: the image is the same, bit for bit, as with the direct atomics.
+//
+// The second tally `w2` (same shape as the image, uint64; null = off): a history that scores w in word i also adds (w >> 10)^2 to
+// w2[i] -- tally_w2_term below, one definition for the COMPAT kernel, the FAST kernels' direct add and the fold's squares pass (which
+// reads the same records), and the CPU oracle's.  w <= 1.25e7 (125 keV in 0.01 eV), so a term is at most 12207^2 = 1.5e8 and 2^64 holds
+// 1.2e11 of the largest terms in ONE word: no history count the engine accepts can overflow a sum.  The shift drops at most
+// 2 * 1024 / w of a term: 0.4 % at w_min = 5e5 (the 5 keV floor of the tables), 0.03 % at the mean energy.  A history scores at most
+// one word, so sums of w2 over any set of words (a scatter class, a block, the detector) are the second moments of that set's score.
 #pragma once
 #include <cstdint>
 
@@ -21,6 +28,7 @@
 
 namespace mcgpu {
 
+constexpr unsigned int kTallyW2Shift = 10;       // w2 += (w >> kTallyW2Shift)^2
 constexpr unsigned int kStageRun = 64;           // pixels of a run
 constexpr unsigned int kStageRunsPerBin = 64;    // a bin's words as 64-bit counters fill at most 128 KiB of the fold's LDS
 constexpr int kStageExteriorPercent = 50;        // default rule: stage where at least this share of the bricks is exterior (engine.cpp: stage_wanted)
@@ -29,6 +37,8 @@ constexpr unsigned int kStageCapSlack = 16;      // records added to every block
 // kChunk), and in a launch of few chunks the waves that ask first get them all -- a workgroup of 16 waves then holds one or two chunks
 // per wave whatever the mean share is.  Two chunks per wave; negligible beside the share of a large launch (1e8 histories: 3 %).
 constexpr unsigned int kStageWorkgroupSlack = 2u * 16u * 256u;
+
+MC_STAGE_HD inline unsigned long long tally_w2_term(unsigned long long w) { return (w >> kTallyW2Shift) * (w >> kTallyW2Shift); }
 
 struct TallyStagePlan {
   unsigned int pixels;         // pixels of one plane

@@ -70,6 +70,12 @@ __device__ __forceinline__ const GLOBAL_AS T* as_global(const T* p) { return (co
 #else
 #define LARG(A, field) (((const CONST_AS TrackArgs*)__builtin_amdgcn_kernarg_segment_ptr())->field)
 #endif
+// ... and one that every kernel reads that way, COMPAT included: the pointer of the optional second tally (TrackArgs::w2) is wanted only
+// where a photon scores; as a launch argument proper it would hold a pair of scalar registers for the whole kernel
+#define KARG(field) (((const CONST_AS TrackArgs*)__builtin_amdgcn_kernarg_segment_ptr())->field)
+#ifndef MC_TALLY_W2
+#define MC_TALLY_W2 0  // FAST: 1 in the instantiations that launches with a w2 run (tally_score)
+#endif
 #define SRC(A) ((const CONST_AS SourcePose*)LARG(A, src))
 #define DET(A) ((const CONST_AS DetectorPose*)LARG(A, det))
 // byte offset of a SERVICE-side table in the LDS image (TrackCold::lds)
@@ -922,16 +928,23 @@ __device__ void tally_image(const TrackArgs& A, Particle P, int scatter_state) {
     const float pz = (float)floor((double)zd);
     if ((pz > -0.1f) && (pz < ((float)DET(A)->nz - 0.1f))) {
       const int idx = (int)(((float)scatter_state) * (float)DET(A)->total_pixels + px + pz * (float)DET(A)->nx + 0.0001f);
-      atomicAdd(A.image + idx, (unsigned long long)(P.E * 100.0f + 0.5f));
+      const unsigned long long w = (unsigned long long)(P.E * 100.0f + 0.5f);
+      atomicAdd(A.image + idx, w);
+      unsigned long long* const w2 = KARG(w2);
+      if (w2 != nullptr) atomicAdd(w2 + idx, tally_w2_term(w));
     }
   }
 #else
   const int px = __float2int_rd(xd);
   if ((px > -1) && (px < DET(A)->nx)) {
     const int pz = __float2int_rd(zd);
-    if ((pz > -1) && (pz < DET(A)->nz))
-      atomicAdd(A.image + ((size_t)scatter_state * DET(A)->total_pixels + (size_t)px + (size_t)pz * DET(A)->nx),
-                (unsigned long long)__float2ull_rn(P.E * 100.0f));
+    if ((pz > -1) && (pz < DET(A)->nz)) {
+      const size_t idx = (size_t)scatter_state * DET(A)->total_pixels + (size_t)px + (size_t)pz * DET(A)->nx;
+      const unsigned long long w = (unsigned long long)__float2ull_rn(P.E * 100.0f);
+      atomicAdd(A.image + idx, w);
+      unsigned long long* const w2 = KARG(w2);
+      if (w2 != nullptr) atomicAdd(w2 + idx, tally_w2_term(w));
+    }
   }
 #endif
 }
@@ -972,6 +985,10 @@ __device__ __forceinline__ int tally_pixel(const TrackArgs& A, Particle P, int s
 // the next slot of its bin in this workgroup's block -- an LDS returning add, which also settles lanes of one batch that hit the same
 // bin -- and is written there with one plain 8-byte store; tally_fold.hip sums the blocks after the kernel.  A block that is full, or
 // a launch without staging, takes the direct 64-bit add at the memory side: the image never depends on the capacity or the plan.
+// In the instantiations with MC_TALLY_W2 (track_fast_w2.hip, track_fast64_w2.hip, the diagnostic build) that direct route also adds
+// the hit's squared weight to TrackArgs::w2 (wave-uniform, null = off); a staged hit needs nothing here: the fold takes the square
+// from the same record.  The production instantiations carry no trace of it: the test alone cost the CIRS workload, whose every hit
+// takes the direct route, 0.2 % (profiles/tally_variance_ab.md).
 __device__ __forceinline__ void tally_score(const TrackArgs& A, int word, unsigned int value) {
   unsigned long long* const region = LARG(A, stage.region);
   if (region != nullptr) {
@@ -987,6 +1004,10 @@ __device__ __forceinline__ void tally_score(const TrackArgs& A, int word, unsign
     atomicAdd(cursor + n_bins, 1u);  // hits of this workgroup that fell back
   }
   atomicAdd((unsigned long long*)as_global(LARG(A, image)) + (unsigned int)word, (unsigned long long)value);
+#if MC_TALLY_W2
+  unsigned long long* const w2 = KARG(w2);
+  if (w2 != nullptr) atomicAdd((unsigned long long*)as_global(w2) + (unsigned int)word, tally_w2_term(value));
+#endif
 }
 // every thread of the workgroup calls these once: before stage_tables() (whose barrier publishes the zeros) / after its history loop,
 // behind the barrier of finish_workgroup()

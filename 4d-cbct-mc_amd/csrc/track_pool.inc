@@ -1165,9 +1165,15 @@ static_assert(std::is_same<kernel_signature<decltype(&track_pool_kernel<kVolU8, 
 #if MC_STATS
 #define MC_LAUNCH_NAME launch_track_stats
 #define MC_OCC_NAME occupancy_track_stats
+#elif MC_FAST_F64 && MC_TALLY_W2
+#define MC_LAUNCH_NAME launch_track_fast64_w2
+#define MC_OCC_NAME occupancy_track_fast64_w2
 #elif MC_FAST_F64
 #define MC_LAUNCH_NAME launch_track_fast64
 #define MC_OCC_NAME occupancy_track_fast64
+#elif MC_TALLY_W2
+#define MC_LAUNCH_NAME launch_track_fast_w2
+#define MC_OCC_NAME occupancy_track_fast_w2
 #else
 #define MC_LAUNCH_NAME launch_track_fast
 #define MC_OCC_NAME occupancy_track_fast

@@ -3,4 +3,5 @@
 // 4/5 Rayleigh rounds / lanes, 6/7 tally+source rounds / lanes.
 #define MC_COMPAT 0
 #define MC_STATS 1
+#define MC_TALLY_W2 1  // one diagnostic kernel for launches with and without squared weights
 #include "track_pool.inc"

@@ -24,7 +24,7 @@ EXE_PATH = Path(__file__).resolve().parent / "MC-GPU_v1.3.x"
 ABI_SYMBOLS = (
     "mcgpu_abi_version", "mcgpu_knob_table", "mcgpu_last_error", "mcgpu_create", "mcgpu_clone", "mcgpu_destroy", "mcgpu_config_i64", "mcgpu_config_f64",
     "mcgpu_host_table", "mcgpu_projection_file_name", "mcgpu_image_words", "mcgpu_launch_shape", "mcgpu_advance_seed",
-    "mcgpu_launch_projection", "mcgpu_tally_stage_plan", "mcgpu_tally_stage_map", "mcgpu_tally_stage_sub_launch", "mcgpu_scheduler_stats", "mcgpu_scheduler_stats_ex", "mcgpu_last_kernel_ms", "mcgpu_clear_image", "mcgpu_run_projection",
+    "mcgpu_launch_projection", "mcgpu_launch_projection_w2", "mcgpu_run_projection_w2", "mcgpu_finalize_variance", "mcgpu_finalize_variance_host", "mcgpu_tally_stage_plan", "mcgpu_tally_stage_map", "mcgpu_tally_stage_sub_launch", "mcgpu_scheduler_stats", "mcgpu_scheduler_stats_ex", "mcgpu_last_kernel_ms", "mcgpu_clear_image", "mcgpu_run_projection",
     "mcgpu_write_projection", "mcgpu_format_projection", "mcgpu_write_formatted_projection", "mcgpu_dose_info", "mcgpu_dose_read", "mcgpu_dose_clear", "mcgpu_write_dose_report",
     "mcgpu_finalize_projection", "mcgpu_finalize_projection_host", "mcgpu_stack_create", "mcgpu_stack_append", "mcgpu_stack_write_slice", "mcgpu_stack_finish",
     "mcgpu_stack_read", "mcgpu_normalize_stack", "mcgpu_run_scan", "mcgpu_run_scan_multi", "mcgpu_set_projection_angles", "mcgpu_set_geometry_arrays",
@@ -45,7 +45,8 @@ class ScanOptions(C.Structure):
                 ("output_folder", C.c_char_p), ("air_stack", C.c_char_p), ("air_sigma_y", C.c_double), ("air_sigma_x", C.c_double),
                 ("pixel_spacing_x", C.c_double), ("pixel_spacing_y", C.c_double),
                 ("shared_stacks", C.POINTER(C.c_void_p)), ("slice_of_projection", C.POINTER(C.c_int)), ("progress", C.c_int),
-                ("shard", C.c_int), ("projection_stride", C.c_int), ("projection_phase", C.c_int), ("reduce", C.c_int)]
+                ("shard", C.c_int), ("projection_stride", C.c_int), ("projection_phase", C.c_int), ("reduce", C.c_int),
+                ("write_variance", C.c_int)]
 
 
 class ScanReport(C.Structure):
@@ -118,6 +119,10 @@ def load_library(path: Optional[os.PathLike] = None):
     lib.mcgpu_launch_shape.argtypes = [cull, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(cull)]
     lib.mcgpu_advance_seed.argtypes = [ci, cull, ci]
     lib.mcgpu_launch_projection.argtypes = [vp, ci, ci, ci, cull, cull, ci, vp, vp]
+    lib.mcgpu_launch_projection_w2.argtypes = [vp, ci, ci, ci, cull, cull, ci, vp, vp, vp]
+    lib.mcgpu_run_projection_w2.argtypes = [vp, ci, ci, ci, cull, cull, ci, vp, vp, C.POINTER(C.c_double), C.POINTER(cull)]
+    lib.mcgpu_finalize_variance.argtypes = [vp, vp, vp, cull, ci, vp, ci, vp]
+    lib.mcgpu_finalize_variance_host.argtypes = [vp, vp, vp, cull, ci, vp]
     lib.mcgpu_tally_stage_plan.argtypes = [vp, cull, cull, ci, ci, cull, C.POINTER(cull)]
     lib.mcgpu_tally_stage_map.argtypes = [cull, ci, cull, cull, vp, vp]
     lib.mcgpu_tally_stage_sub_launch.argtypes = [cull, cull, cull, cull, C.POINTER(cull), C.POINTER(cull)]
@@ -476,12 +481,13 @@ class Context:
 
     # -- running
     def launch(self, p: int, image_dev_ptr: int, count: int, mode="fast", seed: Optional[int] = None, first: int = 0,
-               hpt: Optional[int] = None, stream: int = 0):
-        """Asynchronous launch adding into a caller-owned device buffer (e.g. a torch int64 tensor's data_ptr())."""
+               hpt: Optional[int] = None, stream: int = 0, w2_dev_ptr: int = 0):
+        """Asynchronous launch adding into a caller-owned device buffer (e.g. a torch int64 tensor's data_ptr()).
+        `w2_dev_ptr`: a second buffer of the same shape that receives the squared tally weights (mcgpu_launch_projection_w2), 0: none."""
         seed = self.geti("seed") if seed is None else seed
         hpt = self.geti("histories_per_thread") if hpt is None else hpt
-        _check(self.lib.mcgpu_launch_projection(self.h, p, _MODES[mode], int(seed), int(first), int(count), int(hpt),
-                                                C.c_void_p(image_dev_ptr), C.c_void_p(stream)))
+        _check(self.lib.mcgpu_launch_projection_w2(self.h, p, _MODES[mode], int(seed), int(first), int(count), int(hpt),
+                                                   C.c_void_p(image_dev_ptr), C.c_void_p(w2_dev_ptr or None), C.c_void_p(stream)))
 
     def clear(self, image_dev_ptr: int, stream: int = 0):
         _check(self.lib.mcgpu_clear_image(self.h, C.c_void_p(image_dev_ptr), C.c_void_p(stream)))
@@ -524,6 +530,19 @@ class Context:
         nz, nx = self.detector_shape
         return img.reshape(4, nz, nx), secs.value, done.value
 
+    def run_projection_with_variance(self, p: int, count: int, mode="fast", seed: Optional[int] = None, first: int = 0, hpt: Optional[int] = None):
+        """Synchronous: returns (image, w2, kernel_seconds, histories_done); w2 uint64[4, Nz, Nx] holds, per tally word, the sum of
+        (w >> 10)^2 over the histories that scored w there (mcgpu_run_projection_w2)."""
+        seed = self.geti("seed") if seed is None else seed
+        hpt = self.geti("histories_per_thread") if hpt is None else hpt
+        img = np.zeros(self.image_words, dtype=np.uint64)
+        w2 = np.zeros(self.image_words, dtype=np.uint64)
+        secs, done = C.c_double(), C.c_ulonglong()
+        _check(self.lib.mcgpu_run_projection_w2(self.h, p, _MODES[mode], int(seed), int(first), int(count), int(hpt), img.ctypes.data,
+                                                w2.ctypes.data, C.byref(secs), C.byref(done)))
+        nz, nx = self.detector_shape
+        return img.reshape(4, nz, nx), w2.reshape(4, nz, nx), secs.value, done.value
+
     def reference_shape(self, histories: Optional[int] = None):
         """(batches, hpt, total_histories) the reference would launch for `histories` (COMPAT mode units)."""
         histories = self.geti("total_histories") if histories is None else histories
@@ -561,6 +580,22 @@ class Context:
     def finalize_device(self, image_dev_ptr: int, total_histories: int, planes_dev_ptr: int, crop_nx: int = 0, clear: bool = False, stream: int = 0):
         _check(self.lib.mcgpu_finalize_projection(self.h, C.c_void_p(image_dev_ptr), int(total_histories), int(crop_nx), C.c_void_p(planes_dev_ptr),
                                                   int(clear), C.c_void_p(stream)))
+
+    def finalize_variance_host(self, image: np.ndarray, w2: np.ndarray, total_histories: int, crop_nx: int = 0) -> np.ndarray:
+        """float32 [3, Nz, crop]: the variance of every pixel of finalize_host's planes, from the tally and its squared weights."""
+        img = np.ascontiguousarray(image, dtype=np.uint64).reshape(-1)
+        sq = np.ascontiguousarray(w2, dtype=np.uint64).reshape(-1)
+        assert img.size == self.image_words and sq.size == self.image_words
+        nz, nx = self.detector_shape
+        cx = crop_nx if 0 < crop_nx < nx else nx
+        out = np.zeros((3, nz, cx), dtype=np.float32)
+        _check(self.lib.mcgpu_finalize_variance_host(self.h, img.ctypes.data, sq.ctypes.data, int(total_histories), int(crop_nx), out.ctypes.data))
+        return out
+
+    def finalize_variance_device(self, image_dev_ptr: int, w2_dev_ptr: int, total_histories: int, planes_dev_ptr: int, crop_nx: int = 0,
+                                 clear_w2: bool = False, stream: int = 0):
+        _check(self.lib.mcgpu_finalize_variance(self.h, C.c_void_p(image_dev_ptr), C.c_void_p(w2_dev_ptr), int(total_histories), int(crop_nx),
+                                                C.c_void_p(planes_dev_ptr), int(clear_w2), C.c_void_p(stream)))
 
     # -- 4-D: several (geometry, projection angles) jobs on one resident context (cbctmc/mc/simulation.py:527-710)
     def set_projection_angles(self, angles_deg):
@@ -779,12 +814,14 @@ class Context:
 
     def run_scan(self, mode="fast", first_projection=0, num_projections=0, histories=0, crop_nx=0, write_ascii=False, write_stacks=True,
                  output_folder=None, air_stack=None, air_sigma=(10.0, 10.0), pixel_spacing=(0.0, 0.0), shared_stacks=None,
-                 slice_of_projection=None, peers=(), shard="histories", projection_stride=0, projection_phase=0, reduce="auto") -> dict:
+                 slice_of_projection=None, peers=(), shard="histories", projection_stride=0, projection_phase=0, reduce="auto", write_variance=False) -> dict:
         """The whole projection loop as a device/host pipeline (mcgpu_run_scan); returns the timing report.
         `shared_stacks` = three open StackWriters (total, unscattered, scattered) filled by slice index (4-D scans).
         `peers` + shard="histories": the reference's split (tallies summed through the exchange); shard="projections": every
         context simulates whole projections, nothing crosses between devices (SURVEY 8e fallback).  reduce="rccl": the tallies of the
-        peers are summed with one ncclReduce per projection instead of the exchange (then projection sharding if RCCL cannot be set up)."""
+        peers are summed with one ncclReduce per projection instead of the exchange (then projection sharding if RCCL cannot be set up).
+        `write_variance` (with write_stacks, one context): also projections_{total,unscattered,scattered}_variance.mha, the per-pixel
+        variance of the stacks from the squared weights tallied in the same run."""
         o = ScanOptions()
         o.struct_size = C.sizeof(ScanOptions)
         o.shard = {"histories": 0, "projections": 1}[shard]
@@ -795,7 +832,7 @@ class Context:
             o.shared_stacks, o.slice_of_projection = self._keep[0], self._keep[1]
         o.mode, o.first_projection, o.num_projections = _MODES[mode], int(first_projection), int(num_projections)
         o.histories_per_projection, o.crop_nx = int(histories), int(crop_nx)
-        o.write_ascii, o.write_stacks = int(bool(write_ascii)), int(bool(write_stacks))
+        o.write_ascii, o.write_stacks, o.write_variance = int(bool(write_ascii)), int(bool(write_stacks)), int(bool(write_variance))
         o.output_folder = str(output_folder).encode() if output_folder else None
         o.air_stack = str(air_stack).encode() if air_stack else None
         o.air_sigma_y, o.air_sigma_x = (float(air_sigma[0]), float(air_sigma[1])) if air_sigma else (0.0, 0.0)

@@ -211,12 +211,14 @@ class MCSimulation:
 
     def run_simulation(self, output_folder, engine, gpu_ids=(0,), mode="fast", run_air_simulation=False,
                        air_projection_denoise_kernel_size=(10, 10), clean=True, stack_projections=True, force_rerun=False,
-                       air_n_histories=int(5e10), forward_projection=False, **prepare_kwargs):
+                       air_n_histories=int(5e10), forward_projection=False, variance=False, **prepare_kwargs):
         """`BaseMCSimulation.run_simulation` (sim.py:370-427) on the in-process engine: the docker/mpirun launch and the
         ASCII -> numpy -> SimpleITK post-processing are replaced by the engine's scan pipeline, which writes
         projections_{total,unscattered,scattered}.mha (and projections_total_normalized.mha with an air scan) directly.
         `clean=False` additionally keeps the reference's per-projection ASCII files.  `forward_projection=True` also writes
-        geometry.xml and density_fp.mha into `output_folder` (write_forward_projection).  Returns the scan report."""
+        geometry.xml and density_fp.mha into `output_folder` (write_forward_projection).  `variance=True` (with
+        `stack_projections`) also writes projections_{total,unscattered,scattered}_variance.mha: the per-pixel variance of the stacks,
+        tallied in the same run.  Returns the scan report."""
         output_folder = Path(output_folder)
         if forward_projection:
             self.write_forward_projection(output_folder, engine, gpu_id=gpu_ids if isinstance(gpu_ids, int) else gpu_ids[0])
@@ -240,7 +242,7 @@ class MCSimulation:
         try:
             return ctx.run_scan(mode=mode, crop_nx=half_fan, write_ascii=not clean, write_stacks=stack_projections,
                                 output_folder=output_folder, air_stack=air_stack, air_sigma=air_projection_denoise_kernel_size,
-                                pixel_spacing=self.STACK_PIXEL_SPACING)
+                                pixel_spacing=self.STACK_PIXEL_SPACING, write_variance=variance)
         finally:
             ctx.close()
 

@@ -104,6 +104,15 @@ int mcgpu_advance_seed(int batch_number, unsigned long long total_histories, int
  * `seed` is the RNG seed for this projection; `hpt` is ignored in FAST mode. */
 int mcgpu_launch_projection(mcgpu_ctx *ctx, int p, int mode, int seed, unsigned long long first, unsigned long long count,
                             int hpt, void *image_dev, void *hip_stream);
+/* The same launch with a second tally beside the image: w2_dev[4*Nx*Nz] (uint64, the image's layout), ADDED into like the image.  A
+ * history that scores w (round(E * 100), 0.01 eV) in word i also adds (w >> 10)^2 to w2[i] -- the sum of squared weights in units of
+ * (1024 * 0.01 eV)^2, from which mcgpu_finalize_variance gives the variance of every pixel of the projection out of the one run that is
+ * made anyway.  All modes; the image is bit for bit the one of the launch without w2; disjoint ranges sum as the image's do.  No
+ * sum can overflow (a term is at most 1.5e8); the shift costs at most 0.4 % of a term at the 5 keV table floor, 0.03 % at the mean
+ * energy.  A FAST launch with w2 stages its hits wherever the detector has a staging plan (MCGPU_TALLY_STAGE=0 still forces the direct
+ * atomics).  w2_dev == NULL is mcgpu_launch_projection. */
+int mcgpu_launch_projection_w2(mcgpu_ctx *ctx, int p, int mode, int seed, unsigned long long first, unsigned long long count,
+                               int hpt, void *image_dev, void *w2_dev, void *hip_stream);
 /* Staged detector tally of the FAST kernels (csrc/tally_stage.hpp; MCGPU_TALLY_STAGE): hits are stored per (workgroup, bin) and a
  * second kernel folds them into the image, inside the launch's events.  The plan for a detector of `detector_words` tally words
  * (4 * Nx * Nz), a launch of `histories` cut into sub-launches of at most `limit`, and `workgroups` workgroups; `bins` = 0: the
@@ -151,6 +160,10 @@ int mcgpu_clear_image(mcgpu_ctx *ctx, void *image_dev, void *hip_stream);
 int mcgpu_run_projection(mcgpu_ctx *ctx, int p, int mode, int seed, unsigned long long first, unsigned long long count, int hpt,
                          uint64_t *image_host, double *kernel_seconds, unsigned long long *histories_done);
 
+/* The same with the squared weights of mcgpu_launch_projection_w2 copied to w2_host[4*Nx*Nz] (NULL: mcgpu_run_projection). */
+int mcgpu_run_projection_w2(mcgpu_ctx *ctx, int p, int mode, int seed, unsigned long long first, unsigned long long count, int hpt,
+                            uint64_t *image_host, uint64_t *w2_host, double *kernel_seconds, unsigned long long *histories_done);
+
 /* report_image (MC-GPU_v1.3.cu:2783-2953): write the ASCII projection file (file_name NULL = the
  * reference's name for projection p).  Values = image * (1/100) * inv_px_X * inv_px_Z / total_histories. */
 int mcgpu_write_projection(mcgpu_ctx *ctx, int p, const uint64_t *image_host, unsigned long long total_histories, double seconds,
@@ -193,6 +206,17 @@ int mcgpu_finalize_projection(mcgpu_ctx *ctx, void *image_dev, unsigned long lon
                               int clear_image, void *hip_stream);
 int mcgpu_finalize_projection_host(const mcgpu_ctx *ctx, const uint64_t *image_host, unsigned long long total_histories, int crop_nx,
                                    float *planes_host);
+/* Per-pixel variance of those planes from the image and the squared weights tallied beside it (mcgpu_launch_projection_w2): same
+ * flip, crop and plane order.  Per pixel and plane, with W the sum of the plane's image words, Q the sum of its w2 words, N =
+ * total_histories and c = (1/100) * inv_px_X * inv_px_Z:
+ *     var = c^2 * (1048576 * Q - W * W / N) / (N * (N - 1))
+ * in double, in that order, as float32 -- the unbiased estimate of the variance of the value the plane reports; negative results
+ * are 0, N < 2 gives 0.  The device kernel and the host function agree bit for bit.  clear_w2 zeroes w2 in the same pass (the image is
+ * only read). */
+int mcgpu_finalize_variance(mcgpu_ctx *ctx, const void *image_dev, void *w2_dev, unsigned long long total_histories, int crop_nx,
+                            void *planes_dev, int clear_w2, void *hip_stream);
+int mcgpu_finalize_variance_host(const mcgpu_ctx *ctx, const uint64_t *image_host, const uint64_t *w2_host,
+                                 unsigned long long total_histories, int crop_nx, float *planes_host);
 /* MetaImage float32 stack written plane by plane (projections_to_itk, projection.py:118-166: spacing (sx, sy, 1), origin
  * (-nx*sx/2, -ny*sy/2, 0)).  finish(replace_zeros != 0) applies np.where(stack == 0, stack[stack > 0].min(), stack). */
 typedef struct mcgpu_stack mcgpu_stack;
@@ -243,6 +267,11 @@ typedef struct mcgpu_scan_options {
    * MCGPU_REDUCE_RCCL: one ncclReduce(uint64, sum, root = the projection's owner) per projection on a stream of
    * its own beside the next projection's kernel (then projection sharding if RCCL cannot be set up).  Same output bytes on every route. */
   int reduce;
+  /* mcgpu_run_scan with write_stacks: every projection also tallies its squared weights (mcgpu_launch_projection_w2; kept directly
+   * behind the image in one allocation) and projections_{total,unscattered,scattered}_variance.mha are written beside the stacks
+   * (mcgpu_finalize_variance; same spacing, no zero replacement).  Every other output keeps its bytes.  Refused (-1) without
+   * write_stacks, with shared_stacks and by mcgpu_run_scan_multi. */
+  int write_variance;
 } mcgpu_scan_options;
 #define MCGPU_SHARD_HISTORIES 0
 #define MCGPU_SHARD_PROJECTIONS 1
