@@ -211,22 +211,18 @@ int mcgpu_map_image(mcgpu_ctx* ctx, const int n[3], const void* image, int image
   in.upload(nvox, image, image_dtype, segmentations, thresholds);
   unsigned char* m_out = (unsigned char*)in.device_copy(nullptr, nvox);
   float* d_out = (float*)in.device_copy(nullptr, nvox * 4);
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  HIP_TRY(hipEventCreate(&ev[0]));
-  hipError_t err = hipEventCreate(&ev[1]);
+  Event ev[2];
+  HIP_TRY(hipEventCreate(ev[0].make(D.device_id)));
+  HIP_TRY(hipEventCreate(ev[1].make(D.device_id)));
   float ms = 0.f;
   unsigned int words[kImageStatWords];
-  auto step = [&](hipError_t e) { if (err == hipSuccess) err = e; };
-  step(hipEventRecord(ev[0], nullptr));
-  if (err == hipSuccess) step(launch_image_map_plain(in.args, n[0], n[1], n[2], material, density, m_out, d_out, D.num_cus, nullptr));
-  step(hipEventRecord(ev[1], nullptr));
-  step(hipMemcpy(words, in.args.stats, sizeof words, hipMemcpyDeviceToHost));  // waits for the kernel
-  step(hipEventElapsedTime(&ms, ev[0], ev[1]));
-  step(hipMemcpy(material_out, m_out, nvox, hipMemcpyDeviceToHost));
-  step(hipMemcpy(density_out, d_out, nvox * 4, hipMemcpyDeviceToHost));
-  (void)hipEventDestroy(ev[0]);
-  if (ev[1]) (void)hipEventDestroy(ev[1]);
-  HIP_TRY(err);
+  HIP_TRY(hipEventRecord(ev[0], nullptr));
+  HIP_TRY(launch_image_map_plain(in.args, n[0], n[1], n[2], material, density, m_out, d_out, D.num_cus, nullptr));
+  HIP_TRY(hipEventRecord(ev[1], nullptr));
+  HIP_TRY(hipMemcpy(words, in.args.stats, sizeof words, hipMemcpyDeviceToHost));  // waits for the kernel
+  HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+  HIP_TRY(hipMemcpy(material_out, m_out, nvox, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(density_out, d_out, nvox * 4, hipMemcpyDeviceToHost));
   fill_image_report(report, words, ms, in.ms_upload, 0.0, in.bytes + nvox * 5);
   return 0;
   ABI_END
@@ -255,20 +251,18 @@ int mcgpu_set_geometry_image(mcgpu_ctx* ctx, const int n[3], const float spacing
   MappedInputs in;
   in.upload(nvox, image, image_dtype, segmentations, thresholds);
   unsigned char* classes = (unsigned char*)in.device_copy(nullptr, tiled_bytes);
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  HIP_TRY(hipEventCreate(&ev[0]));
-  hipError_t err = hipEventCreate(&ev[1]);
   float ms = 0.f;
   unsigned int words[kImageStatWords];
-  auto step = [&](hipError_t e) { if (err == hipSuccess) err = e; };
-  step(hipEventRecord(ev[0], nullptr));
-  if (err == hipSuccess) step(launch_image_map_tiled(in.args, frame, n[0], n[1], n[2], classes, num_cus, nullptr));
-  step(hipEventRecord(ev[1], nullptr));
-  step(hipMemcpy(words, in.args.stats, sizeof words, hipMemcpyDeviceToHost));  // waits for the kernel
-  step(hipEventElapsedTime(&ms, ev[0], ev[1]));
-  (void)hipEventDestroy(ev[0]);
-  if (ev[1]) (void)hipEventDestroy(ev[1]);
-  HIP_TRY(err);
+  {
+    Event ev[2];
+    HIP_TRY(hipEventCreate(ev[0].make(device_id)));
+    HIP_TRY(hipEventCreate(ev[1].make(device_id)));
+    HIP_TRY(hipEventRecord(ev[0], nullptr));
+    HIP_TRY(launch_image_map_tiled(in.args, frame, n[0], n[1], n[2], classes, num_cus, nullptr));
+    HIP_TRY(hipEventRecord(ev[1], nullptr));
+    HIP_TRY(hipMemcpy(words, in.args.stats, sizeof words, hipMemcpyDeviceToHost));  // waits for the kernel
+    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+  }
   const auto t_install = std::chrono::steady_clock::now();
   fill_image_report(report, words, ms, in.ms_upload, 0.0, in.bytes + tiled_bytes);
   if (words[2 * kImageClasses] != 0u) {
@@ -536,22 +530,15 @@ int mcgpu_warp_volume(mcgpu_ctx* ctx, const int n[3], const uint8_t* material, c
           "!!ERROR!! mcgpu_warp_volume: bad argument (the context needs a device)");
   HIP_TRY(hipSetDevice(ctx->dev.device_id));
   const size_t nvox = (size_t)n[0] * n[1] * n[2];
-  unsigned char *m_in = nullptr, *m_out = nullptr;
-  float *d_in = nullptr, *d_out = nullptr, *u = nullptr;
-  hipError_t err = hipSuccess;
-  auto step = [&](hipError_t e) { if (err == hipSuccess) err = e; };
-  step(hipMalloc((void**)&m_in, nvox)); step(hipMalloc((void**)&m_out, nvox));
-  step(hipMalloc((void**)&d_in, nvox * 4)); step(hipMalloc((void**)&d_out, nvox * 4)); step(hipMalloc((void**)&u, nvox * 12));
-  if (err == hipSuccess) {
-    step(hipMemcpy(m_in, material, nvox, hipMemcpyHostToDevice));
-    step(hipMemcpy(d_in, density, nvox * 4, hipMemcpyHostToDevice));
-    step(hipMemcpy(u, displacement, nvox * 12, hipMemcpyHostToDevice));
-    if (err == hipSuccess) step(launch_warp(n[0], n[1], n[2], m_in, d_in, u, (unsigned char)default_material, default_density, m_out, d_out, nullptr));
-    step(hipMemcpy(material_out, m_out, nvox, hipMemcpyDeviceToHost));
-    step(hipMemcpy(density_out, d_out, nvox * 4, hipMemcpyDeviceToHost));
-  }
-  (void)hipFree(m_in); (void)hipFree(m_out); (void)hipFree(d_in); (void)hipFree(d_out); (void)hipFree(u);
-  HIP_TRY(err);
+  CallDevice dev;
+  unsigned char *m_in = dev.alloc<unsigned char>(nvox), *m_out = dev.alloc<unsigned char>(nvox);
+  float *d_in = dev.alloc<float>(nvox * 4), *d_out = dev.alloc<float>(nvox * 4), *u = dev.alloc<float>(nvox * 12);
+  HIP_TRY(hipMemcpy(m_in, material, nvox, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_in, density, nvox * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(u, displacement, nvox * 12, hipMemcpyHostToDevice));
+  HIP_TRY(launch_warp(n[0], n[1], n[2], m_in, d_in, u, (unsigned char)default_material, default_density, m_out, d_out, nullptr));
+  HIP_TRY(hipMemcpy(material_out, m_out, nvox, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(density_out, d_out, nvox * 4, hipMemcpyDeviceToHost));
   return 0;
   ABI_END
 }

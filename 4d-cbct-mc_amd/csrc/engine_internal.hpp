@@ -1,5 +1,6 @@
 #pragma once
-// engine_internal.hpp -- what the translation units of the engine library share: the device model, the context, error plumbing.
+// engine_internal.hpp -- what the translation units of the engine library share: the device model and the context (the error
+// plumbing and the per-call owners are hip_host.hpp's).
 // (engine.cpp: the C ABI of a context; model_device.cpp: the device model's memory, its upload in stages (upload_model) and launch
 // arguments; engine_geometry.cpp: geometry changes of a resident context; engine_kat.cpp: known-answer and micro-benchmark hooks.)
 //
@@ -20,6 +21,7 @@
 
 #include "../../include/mcgpu_amd.h"
 #include "knobs.hpp"
+#include "hip_host.hpp"
 #include "device_model.hpp"
 #include "ascii_device.hpp"
 #include "geometry_device.hpp"
@@ -58,14 +60,6 @@ hipError_t launch_warp(int nx, int ny, int nz, const unsigned char* mat, const f
 hipError_t launch_finalize(unsigned long long* image, int nx, int nz, int crop_nx, double norm, float* planes, int clear, hipStream_t stream);
 hipError_t launch_finalize_variance(const unsigned long long* image, unsigned long long* w2, int nx, int nz, int crop_nx, unsigned long long histories,
                                     double c, float* planes, int clear, hipStream_t stream);
-
-int set_error(int code, const std::string& msg);  // engine.cpp: records the calling thread's last error, returns `code`
-
-#define HIP_TRY(expr)                                                                                   \
-  do {                                                                                                  \
-    hipError_t _e = (expr);                                                                             \
-    if (_e != hipSuccess) throw Error(-1, std::string("!!HIP ERROR!! ") + #expr + ": " + hipGetErrorString(_e)); \
-  } while (0)
 
 // What a device model allocated -- device buffers, pinned host buffers, streams, events -- released on its device (the one current at
 // the first allocation) when the owner goes.  Move-only: a move assignment hands the previous contents to the source, which frees them.
@@ -233,17 +227,8 @@ struct DeviceVolumeSource {
   unsigned int first[kImageClasses];             // smallest [z][y][x] index of the class, 0xFFFFFFFF: it does not occur
 };
 DeviceModel upload_model(const HostModel& H, int device_id, const DeviceVolumeSource* mapped = nullptr);
-void require(bool ok, int code, const char* msg);
 TrackArgs make_args(const mcgpu_ctx& C, int p);
 void sync_host_voxels(mcgpu_ctx& C);
 const void* host_table(mcgpu_ctx& C, const std::string& name, size_t& bytes);
 }  // namespace mcgpu
-
-
-#define ABI_BEGIN try {
-#define ABI_END                                               \
-  }                                                           \
-  catch (const Error& e) { return set_error(e.code, e.what()); } \
-  catch (const std::exception& e) { return set_error(-2, e.what()); } \
-  catch (...) { return set_error(-2, "unknown failure"); }
 

@@ -15,7 +15,6 @@
 //                 the filtered projections of a batch (5.7 MB each, padded) stay L2 / Infinity-Cache resident.  One voxel step
 //                 is 3.9 detector pixels, so the 4 loads of a wave touch ~32 cache lines for 64 updates: the vector L1
 //                 (64 B/clk/CU) bounds the kernel at ~1 update/clk/CU; measured 0.78                              (L1/L2 gather)
-#include <hip/hip_runtime.h>
 #include <hipfft/hipfft.h>
 
 #include <algorithm>
@@ -27,9 +26,8 @@
 #include <vector>
 
 #include "../../include/mcgpu_amd.h"
+#include "hip_host.hpp"
 #include "knobs.hpp"
-
-extern "C" void mcgpu_set_last_error_(const char* message);
 
 namespace {
 
@@ -285,258 +283,274 @@ void displaced_weights(int nu, double du, double u0, double off_x, double sdd, f
   }
 }
 
-struct FdkError { std::string msg; };
-#define FDK_HIP(expr)                                                                                     \
-  do {                                                                                                    \
-    hipError_t _e = (expr);                                                                               \
-    if (_e != hipSuccess) throw FdkError{std::string("!!HIP ERROR!! ") + #expr + ": " + hipGetErrorString(_e)}; \
-  } while (0)
+// ---- what a reconstruction derives from its options on the host, before any device call ---------------------------------------
+struct FdkPlan {
+  int n, nu, nv;
+  size_t plane, nvox;
+  std::vector<ProjParam> pp;  // with the angular gaps
+  std::vector<float> ky, wdis, wext, wpc;
+  std::vector<float> h;       // direct: the ramp kernel's taps; else its spectrum H[nk] with scale / L folded in
+  double ox0, oy0, oz0, u0_p, scale;
+  int pad_l, pad_r, nu_p, next, nu_e, max_lag, L, stride, nk, chunk;
+  bool direct;
+  size_t plane_p, lds_ramp;
+};
+
+FdkPlan plan_fdk(const mcgpu_fdk_options& opt) {
+  const mcgpu_fdk_options* o = &opt;
+  FdkPlan P;
+  const int n = P.n = o->n_proj, nu = P.nu = o->nu, nv = P.nv = o->nv;
+  P.plane = (size_t)nu * nv;
+  P.nvox = (size_t)o->nx * o->ny * o->nz;
+  const std::vector<double> kyd = hann_y_kernel(o->hann_y);
+  P.ky = std::vector<float>(kyd.begin(), kyd.end());
+  std::vector<ProjParam>& pp = P.pp = std::vector<ProjParam>(n);
+  P.wdis = std::vector<float>((size_t)n * nu);
+  for (int k = 0; k < n; ++k) {
+    const mcgpu::ProjectionPose q = mcgpu::projection_pose(*o, k);
+    pp[k] = {(float)q.c, (float)q.s, (float)q.off_x, (float)q.off_y, 0.f};
+    displaced_weights(nu, o->du, o->u0, q.off_x, o->sdd, &P.wdis[(size_t)k * nu]);
+  }
+  {
+    // Angular weight of a projection = half the distance to its two neighbours on the circle (what rtkfdk takes from
+    // the geometry file: ThreeDCircularProjectionGeometry::GetAngularGaps); 2 pi / n only for a uniform full arc.
+    // Projections at the same angle share their gap.
+    std::vector<std::pair<double, int>> by_angle(n);
+    for (int k = 0; k < n; ++k) {
+      double a = std::fmod(o->gantry_deg[k], 360.0);
+      if (a < 0) a += 360.0;
+      by_angle[k] = {a, k};
+    }
+    std::sort(by_angle.begin(), by_angle.end());
+    std::vector<double> uniq;
+    std::vector<int> count;
+    for (int k = 0; k < n; ++k) {
+      if (uniq.empty() || by_angle[k].first - uniq.back() > 1e-9) { uniq.push_back(by_angle[k].first); count.push_back(1); }
+      else ++count.back();
+    }
+    const int m = (int)uniq.size();
+    int u = -1;
+    double last = -1.0;
+    for (int k = 0; k < n; ++k) {
+      if (u < 0 || by_angle[k].first - last > 1e-9) { ++u; last = uniq[u]; }
+      double gap = 360.0;
+      if (m > 1) {
+        const double prev = uniq[(u + m - 1) % m], next = uniq[(u + 1) % m];
+        double d = next - prev;
+        if (d <= 0) d += 360.0;
+        gap = 0.5 * d;
+        if (m == 2) gap = 180.0;
+      }
+      pp[by_angle[k].second].gap = (float)(gap * M_PI / 180.0 / count[u]);
+    }
+  }
+  P.ox0 = mcgpu::centred_origin(o->nx, o->sx, o->ox);
+  P.oy0 = mcgpu::centred_origin(o->ny, o->sy, o->oy);
+  P.oz0 = mcgpu::centred_origin(o->nz, o->sz, o->oz);
+  // symmetric padding of an off-centre detector (oracle/fdk_oracle.py: symmetric_padding), from the double offsets as the Wang
+  // weights take them: the float offsets of pp[] can move the ceiling by one column where -2 off / du is an integer (the reference's
+  // -159.856 mm at 0.388 mm pixels)
+  int pad_l = 0, pad_r = 0;
+  {
+    double off_min = 1e300, off_max = -1e300;
+    for (int k = 0; k < n; ++k) {
+      const double ox = mcgpu::offset_x(*o, k);
+      off_min = std::min(off_min, ox);
+      off_max = std::max(off_max, ox);
+    }
+    const double last = o->u0 + (nu - 1) * o->du;
+    const double lo = o->u0 + off_min, hi = last + off_max;
+    if (lo < 0.0 && hi > 0.0) {
+      const double extent = std::max(std::max(-(o->u0 + off_min), -(o->u0 + off_max)), std::max(last + off_min, last + off_max));
+      pad_l = std::max(0, (int)std::ceil((extent + (o->u0 + off_min)) / o->du - 1e-9));
+      pad_r = std::max(0, (int)std::ceil((extent - (last + off_max)) / o->du - 1e-9));
+    }
+  }
+  P.pad_l = pad_l; P.pad_r = pad_r;
+  const int nu_p = P.nu_p = nu + pad_l + pad_r;
+  P.u0_p = o->u0 - pad_l * o->du;
+  // rtkfdk --pad: the ramp sees rows of nu_e = nu_p + 2 next columns (extend_rows_kernel); the back-projector only the nu_p
+  // detector columns in their middle
+  const int next = P.next = (o->pad > 0.0) ? std::min((int)std::ceil(o->pad * nu_p), nu_p - 1) : 0;
+  const int nu_e = P.nu_e = nu_p + 2 * next;
+  // Ramp filter: FFT (hipFFT, rows zero-extended to L >= 2 nu_p - 1: no wrap-around inside the nu_p columns that are used) or,
+  // with MCGPU_FDK_DIRECT_RAMP, the direct LDS convolution (same result up to float rounding; tests compare both to the oracle)
+  const bool direct = P.direct = mcgpu::knob_set("MCGPU_FDK_DIRECT_RAMP");
+  // The ramp is a linear convolution evaluated as a circular one of length L.  Only the nu_p detector columns in the middle of
+  // a row are ever read, and for those the lag between an output and any of the nu_e data columns is at most M = nu_p + next - 1:
+  // with the kernel cut to |lag| <= M, L >= 2 M + 1 keeps every lag distinct (and L >= nu_e holds the row).  L = the smallest
+  // even 2^a 3^b 5^c at or above that -- 7500 for the reference's half-fan rows with pad = 1 (nu_e = 5545, M = 3696), where
+  // L >= 2 nu_e - 1 rounded up to a power of two would be 16384.
+  const int max_lag = P.max_lag = nu_p + next - 1;
+  int L = std::max(2 * max_lag + 1, nu_e);
+  for (;; ++L) {
+    if (L & 1) continue;
+    int m = L;
+    for (int f : {2, 3, 5})
+      while (m % f == 0) m /= f;
+    if (m == 1) break;
+  }
+  P.L = L;
+  P.stride = direct ? nu_e : L;        // floats per detector row in the filtered buffers
+  const int nk = P.nk = L / 2 + 1;
+  P.plane_p = (size_t)P.stride * nv;
+  P.chunk = std::min(n, direct ? 64 : 32);  // projections resident on the device at a time (multiple of kBatch)
+  const std::vector<double> hd = ramp_kernel(nu_e - 1, o->hann);
+  if (next > 0) {
+    P.wext = std::vector<float>((size_t)next + 1, 0.f);
+    for (int d = 1; d <= next; ++d) P.wext[(size_t)d] = next > 1 ? (float)std::pow(std::sin((double)(next - d) * M_PI / (2.0 * next - 2.0)), 0.75) : 0.f;
+  }
+  const double scale = P.scale = (o->sdd / o->sid) / o->du;
+  if (direct) {
+    P.h = std::vector<float>(hd.begin(), hd.end());
+  } else {
+    // spectrum of the kernel laid out circularly (lag n at index n mod L); real because the kernel is even;
+    // the scale of the filter and hipFFT's missing 1/L are folded in
+    // L is not a power of two: the (real, even) kernel's spectrum by its cosine sum, H[k] = h[0] + 2 sum_lag h[lag] cos(2 pi k lag / L),
+    // with one table of cosines (30 M multiply-adds in double: tens of milliseconds, once per reconstruction)
+    std::vector<double> cosine((size_t)L);
+    for (int t = 0; t < L; ++t) cosine[(size_t)t] = std::cos(2.0 * M_PI * (double)t / (double)L);
+    P.h = std::vector<float>((size_t)nk);
+    const double* h0 = hd.data() + (nu_e - 1);  // h0[lag], lag = -(nu_e - 1) .. nu_e - 1
+    for (int k = 0; k < nk; ++k) {
+      double acc = h0[0];
+      size_t t = 0;  // (k * lag) mod L
+      for (int lag = 1; lag <= max_lag; ++lag) {
+        t += (size_t)k;
+        if (t >= (size_t)L) t -= (size_t)L;
+        acc += 2.0 * h0[lag] * cosine[t];
+      }
+      P.h[(size_t)k] = (float)(acc * scale / (double)L);
+    }
+  }
+  for (int j = 0; j < o->n_wpc; ++j) P.wpc.push_back((float)o->wpc[j]);
+  P.lds_ramp = ((size_t)nu_e + 2 * nu_e + 2) * 4;
+  return P;
+}
+
+struct FftPlans {  // the batched R2C / C2R pair of one chunk size (hipfftDestroy returns hipfftResult: no mcgpu::Owned)
+  hipfftHandle fwd = 0, inv = 0;
+  int rows = 0;
+  FftPlans() = default;
+  FftPlans(const FftPlans&) = delete;
+  ~FftPlans() { reset(); }
+  void reset() {
+    if (fwd) hipfftDestroy(fwd);
+    if (inv) hipfftDestroy(inv);
+    fwd = inv = 0;
+    rows = 0;
+  }
+  void make(int L, int nk, int n_rows) {
+    if (rows == n_rows) return;
+    reset();
+    int len[1] = {L};
+    if (hipfftPlanMany(&fwd, 1, len, nullptr, 1, L, nullptr, 1, nk, HIPFFT_R2C, n_rows) != HIPFFT_SUCCESS ||
+        hipfftPlanMany(&inv, 1, len, nullptr, 1, nk, nullptr, 1, L, HIPFFT_C2R, n_rows) != HIPFFT_SUCCESS)
+      throw mcgpu::Error(-1, "!!ERROR!! mcgpu_fdk_reconstruct: hipfftPlanMany failed");
+    rows = n_rows;
+  }
+};
+
+// one reconstruction on the device: the plan's tables and a chunk of projections resident, the volume accumulated there
+struct FdkProblem {
+  const mcgpu_fdk_options& o;
+  const FdkPlan& P;
+  mcgpu::CallDevice dev;
+  FftPlans fft;
+  mcgpu_fdk_report rep = {0.0, 0.0};
+  float *d_raw = nullptr, *d_in = nullptr, *d_tmp = nullptr, *d_vol = nullptr, *d_wext = nullptr, *d_h = nullptr, *d_ky = nullptr, *d_wdis = nullptr, *d_wpc = nullptr;
+  float2* d_spec = nullptr;
+  ProjParam* d_pp = nullptr;
+  const float* filtered = nullptr;  // what filter() left for backproject(): d_tmp, or d_in after the hannY pass
+
+  FdkProblem(const mcgpu_fdk_options& opt, const FdkPlan& plan) : o(opt), P(plan) {}
+
+  void upload() {
+    d_raw = dev.alloc<float>((size_t)P.chunk * P.plane * 4);
+    d_in = dev.alloc<float>((size_t)P.chunk * P.plane_p * 4);
+    d_tmp = dev.alloc<float>((size_t)P.chunk * P.plane_p * 4);
+    d_vol = dev.alloc_zeroed<float>(P.nvox * 4);
+    if (P.next > 0) d_wext = dev.upload(P.wext);
+    d_h = dev.upload(P.h);
+    if (!P.direct) d_spec = dev.alloc<float2>((size_t)P.chunk * P.nv * P.nk * sizeof(float2));
+    d_ky = dev.upload(P.ky);
+    d_wdis = dev.upload(P.wdis);
+    d_pp = dev.upload(P.pp);
+    if (!P.wpc.empty()) d_wpc = dev.upload(P.wpc);
+    dev.events();
+    if (P.direct && P.lds_ramp > 64 * 1024)
+      HIP_TRY(hipFuncSetAttribute((const void*)ramp_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_ramp));
+  }
+
+  // projections [first, first + m) onto the device, weighted, extended, ramp-filtered and smoothed along v
+  void filter(const float* projections, int first, int m) {
+    const int nu = P.nu, nv = P.nv, next = P.next, nu_e = P.nu_e, stride = P.stride, nk = P.nk;
+    const size_t elems = (size_t)m * P.plane_p;
+    HIP_TRY(hipMemcpy(d_raw, projections + (size_t)first * P.plane, (size_t)m * P.plane * 4, hipMemcpyHostToDevice));
+    if (!P.direct) fft.make(P.L, nk, m * nv);  // one batched plan per chunk size (at most two: full chunks and the last one)
+    mcgpu::Stage st(dev, rep.ms_filter);
+    const unsigned gb = (unsigned)((elems + 255) / 256);
+    hipLaunchKernelGGL(weight_kernel, dim3(gb), dim3(256), 0, nullptr, d_raw, d_in, nu, nv, m, stride, next + P.pad_l, (float)o.du, (float)o.dv, (float)o.u0,
+                       (float)o.v0, (float)o.sdd, d_pp + first, d_wdis + (size_t)first * nu, d_wpc, (int)P.wpc.size());
+    if (next > 0) {
+      const size_t ne = (size_t)m * nv * next;
+      hipLaunchKernelGGL(extend_rows_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, nullptr, d_in, stride, P.nu_p, next, (size_t)m * nv, d_wext);
+    }
+    if (P.direct) {
+      hipLaunchKernelGGL(ramp_rows_kernel, dim3((unsigned)(m * nv)), dim3(256), P.lds_ramp, nullptr, d_in, d_tmp, d_h, nu_e, (float)P.scale, next > 0 ? 0 : P.pad_l,
+                         next > 0 ? nu_e : P.pad_l + nu);
+    } else {
+      if (hipfftExecR2C(fft.fwd, d_in, (hipfftComplex*)d_spec) != HIPFFT_SUCCESS) throw mcgpu::Error(-1, "!!ERROR!! mcgpu_fdk_reconstruct: hipfftExecR2C failed");
+      const size_t ns = (size_t)m * nv * nk;
+      hipLaunchKernelGGL(spectrum_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, nullptr, d_spec, d_h, nk, ns);
+      if (hipfftExecC2R(fft.inv, (hipfftComplex*)d_spec, d_tmp) != HIPFFT_SUCCESS) throw mcgpu::Error(-1, "!!ERROR!! mcgpu_fdk_reconstruct: hipfftExecC2R failed");
+    }
+    filtered = d_tmp;
+    if (P.ky.size() > 1) {
+      const size_t na = (size_t)m * nv * nu_e;
+      hipLaunchKernelGGL(smooth_cols_kernel, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, nullptr, d_tmp, d_in, nu_e, stride, nv, m, d_ky, (int)P.ky.size());
+      filtered = d_in;
+    }
+    st.done();
+  }
+
+  void backproject(int first, int m) {
+    mcgpu::Stage st(dev, rep.ms_backproject);
+    for (int b = 0; b < m; b += kBatch) {
+      BackArgs A;
+      A.nx = o.nx; A.ny = o.ny; A.nz = o.nz; A.nu = P.nu_p; A.u_first = P.next; A.stride = P.stride; A.nv = P.nv; A.nb = std::min(kBatch, m - b);
+      A.x0 = (float)P.ox0; A.y0 = (float)P.oy0; A.z0 = (float)P.oz0; A.sx = (float)o.sx; A.sy = (float)o.sy; A.sz = (float)o.sz;
+      A.sid = (float)o.sid; A.sdd = (float)o.sdd; A.inv_du = (float)(1.0 / o.du); A.inv_dv = (float)(1.0 / o.dv);
+      A.u0 = (float)P.u0_p; A.v0 = (float)o.v0;
+      for (int k = 0; k < kBatch; ++k) A.pp[k] = (k < A.nb) ? P.pp[first + b + k] : ProjParam{1.f, 0.f, 0.f, 0.f, 0.f};
+      hipLaunchKernelGGL(backproject_kernel, dim3((unsigned)((o.nx + 255) / 256), (unsigned)o.nz), dim3(256), 0, nullptr, d_vol,
+                         filtered + (size_t)b * P.plane_p, A);
+    }
+    st.done();
+  }
+};
 
 }  // namespace
 
 extern "C" int mcgpu_fdk_reconstruct(const mcgpu_fdk_options* caller_o, const float* projections, float* volume, mcgpu_fdk_report* report) {
-  if (!caller_o || caller_o->struct_size < 2 * sizeof(int)) {
-    mcgpu_set_last_error_("!!ERROR!! mcgpu_fdk_reconstruct: set mcgpu_fdk_options.struct_size = sizeof(mcgpu_fdk_options)");
-    return -1;
-  }
-  // a caller built against an older header passes a shorter struct: what it does not have (e.g. `pad`) reads as zero
+  ABI_BEGIN
   mcgpu_fdk_options local;
-  memset(&local, 0, sizeof local);
-  memcpy(&local, caller_o, std::min<size_t>(caller_o->struct_size, sizeof local));
+  mcgpu::read_options("mcgpu_fdk_reconstruct", "mcgpu_fdk_options", caller_o, local);
   const mcgpu_fdk_options* o = &local;
   if (!projections || !volume || o->n_proj < 1 || o->nu < 2 || o->nv < 2 || o->nx < 1 || o->ny < 1 || o->nz < 1 || !o->gantry_deg ||
-      !(o->du > 0) || !(o->dv > 0) || !(o->sid > 0) || !(o->sdd > 0)) {
-    mcgpu_set_last_error_("!!ERROR!! mcgpu_fdk_reconstruct: bad argument");
-    return -1;
+      !(o->du > 0) || !(o->dv > 0) || !(o->sid > 0) || !(o->sdd > 0))
+    throw mcgpu::Error(-1, "!!ERROR!! mcgpu_fdk_reconstruct: bad argument");
+  HIP_TRY(hipSetDevice(o->device));
+  const FdkPlan plan = plan_fdk(local);
+  FdkProblem P(local, plan);
+  P.upload();
+  for (int first = 0; first < plan.n; first += plan.chunk) {
+    const int m = std::min(plan.chunk, plan.n - first);
+    P.filter(projections, first, m);
+    P.backproject(first, m);
   }
-  float2* d_spec = nullptr;
-  hipfftHandle plan_fwd = 0, plan_inv = 0;
-  float *d_free_raw = nullptr, *d_free_wext = nullptr, *d_in = nullptr, *d_tmp = nullptr, *d_vol = nullptr, *d_h = nullptr, *d_ky = nullptr, *d_wdis = nullptr, *d_wpc = nullptr;
-  ProjParam* d_pp = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
-  int rc = 0;
-  try {
-    FDK_HIP(hipSetDevice(o->device));
-    const int n = o->n_proj, nu = o->nu, nv = o->nv;
-    const size_t plane = (size_t)nu * nv, nvox = (size_t)o->nx * o->ny * o->nz;
-    const std::vector<double> kyd = hann_y_kernel(o->hann_y);
-    std::vector<float> ky(kyd.begin(), kyd.end());
-    std::vector<ProjParam> pp(n);
-    std::vector<float> wdis((size_t)n * nu);
-    for (int k = 0; k < n; ++k) {
-      const double t = o->gantry_deg[k] * M_PI / 180.0;
-      const double ox = o->proj_offset_x ? o->proj_offset_x[k] : 0.0, oy = o->proj_offset_y ? o->proj_offset_y[k] : 0.0;
-      pp[k] = {(float)std::cos(t), (float)std::sin(t), (float)ox, (float)oy, 0.f};
-      displaced_weights(nu, o->du, o->u0, ox, o->sdd, &wdis[(size_t)k * nu]);
-    }
-    {
-      // Angular weight of a projection = half the distance to its two neighbours on the circle (what rtkfdk takes from
-      // the geometry file: ThreeDCircularProjectionGeometry::GetAngularGaps); 2 pi / n only for a uniform full arc.
-      // Projections at the same angle share their gap.
-      std::vector<std::pair<double, int>> by_angle(n);
-      for (int k = 0; k < n; ++k) {
-        double a = std::fmod(o->gantry_deg[k], 360.0);
-        if (a < 0) a += 360.0;
-        by_angle[k] = {a, k};
-      }
-      std::sort(by_angle.begin(), by_angle.end());
-      std::vector<double> uniq;
-      std::vector<int> count;
-      for (int k = 0; k < n; ++k) {
-        if (uniq.empty() || by_angle[k].first - uniq.back() > 1e-9) { uniq.push_back(by_angle[k].first); count.push_back(1); }
-        else ++count.back();
-      }
-      const int m = (int)uniq.size();
-      int u = -1;
-      double last = -1.0;
-      for (int k = 0; k < n; ++k) {
-        if (u < 0 || by_angle[k].first - last > 1e-9) { ++u; last = uniq[u]; }
-        double gap = 360.0;
-        if (m > 1) {
-          const double prev = uniq[(u + m - 1) % m], next = uniq[(u + 1) % m];
-          double d = next - prev;
-          if (d <= 0) d += 360.0;
-          gap = 0.5 * d;
-          if (m == 2) gap = 180.0;
-        }
-        pp[by_angle[k].second].gap = (float)(gap * M_PI / 180.0 / count[u]);
-      }
-    }
-    const double ox0 = std::isnan(o->ox) ? -(o->nx - 1) / 2.0 * o->sx : o->ox, oy0 = std::isnan(o->oy) ? -(o->ny - 1) / 2.0 * o->sy : o->oy,
-                 oz0 = std::isnan(o->oz) ? -(o->nz - 1) / 2.0 * o->sz : o->oz;
-    // symmetric padding of an off-centre detector (oracle/fdk_oracle.py: symmetric_padding), from the double offsets as the Wang
-    // weights take them: the float offsets of pp[] can move the ceiling by one column where -2 off / du is an integer (the reference's
-    // -159.856 mm at 0.388 mm pixels)
-    int pad_l = 0, pad_r = 0;
-    {
-      double off_min = 1e300, off_max = -1e300;
-      for (int k = 0; k < n; ++k) {
-        const double ox = o->proj_offset_x ? o->proj_offset_x[k] : 0.0;
-        off_min = std::min(off_min, ox);
-        off_max = std::max(off_max, ox);
-      }
-      const double last = o->u0 + (nu - 1) * o->du;
-      const double lo = o->u0 + off_min, hi = last + off_max;
-      if (lo < 0.0 && hi > 0.0) {
-        const double extent = std::max(std::max(-(o->u0 + off_min), -(o->u0 + off_max)), std::max(last + off_min, last + off_max));
-        pad_l = std::max(0, (int)std::ceil((extent + (o->u0 + off_min)) / o->du - 1e-9));
-        pad_r = std::max(0, (int)std::ceil((extent - (last + off_max)) / o->du - 1e-9));
-      }
-    }
-    const int nu_p = nu + pad_l + pad_r;
-    const double u0_p = o->u0 - pad_l * o->du;
-    // rtkfdk --pad: the ramp sees rows of nu_e = nu_p + 2 next columns (extend_rows_kernel); the back-projector only the nu_p
-    // detector columns in their middle
-    const int next = (o->pad > 0.0) ? std::min((int)std::ceil(o->pad * nu_p), nu_p - 1) : 0;
-    const int nu_e = nu_p + 2 * next;
-    // Ramp filter: FFT (hipFFT, rows zero-extended to L >= 2 nu_p - 1: no wrap-around inside the nu_p columns that are used) or,
-    // with MCGPU_FDK_DIRECT_RAMP, the direct LDS convolution (same result up to float rounding; tests compare both to the oracle)
-    const bool direct = mcgpu::knob_set("MCGPU_FDK_DIRECT_RAMP");
-    // The ramp is a linear convolution evaluated as a circular one of length L.  Only the nu_p detector columns in the middle of
-    // a row are ever read, and for those the lag between an output and any of the nu_e data columns is at most M = nu_p + next - 1:
-    // with the kernel cut to |lag| <= M, L >= 2 M + 1 keeps every lag distinct (and L >= nu_e holds the row).  L = the smallest
-    // even 2^a 3^b 5^c at or above that -- 7500 for the reference's half-fan rows with pad = 1 (nu_e = 5545, M = 3696), where
-    // L >= 2 nu_e - 1 rounded up to a power of two would be 16384.
-    const int max_lag = nu_p + next - 1;
-    int L = std::max(2 * max_lag + 1, nu_e);
-    for (;; ++L) {
-      if (L & 1) continue;
-      int m = L;
-      for (int f : {2, 3, 5})
-        while (m % f == 0) m /= f;
-      if (m == 1) break;
-    }
-    const int stride = direct ? nu_e : L;        // floats per detector row in the filtered buffers
-    const int nk = L / 2 + 1;
-    const size_t plane_p = (size_t)stride * nv;
-    const int chunk = std::min(n, direct ? 64 : 32);  // projections resident on the device at a time (multiple of kBatch)
-    float* d_raw = nullptr;
-    FDK_HIP(hipMalloc(&d_raw, (size_t)chunk * plane * 4));
-    d_free_raw = d_raw;
-    FDK_HIP(hipMalloc(&d_in, (size_t)chunk * plane_p * 4));
-    FDK_HIP(hipMalloc(&d_tmp, (size_t)chunk * plane_p * 4));
-    FDK_HIP(hipMalloc(&d_vol, nvox * 4));
-    FDK_HIP(hipMemset(d_vol, 0, nvox * 4));
-    const std::vector<double> hd = ramp_kernel(nu_e - 1, o->hann);
-    float* d_wext = nullptr;
-    if (next > 0) {
-      std::vector<float> wext((size_t)next + 1, 0.f);
-      for (int d = 1; d <= next; ++d) wext[(size_t)d] = next > 1 ? (float)std::pow(std::sin((double)(next - d) * M_PI / (2.0 * next - 2.0)), 0.75) : 0.f;
-      FDK_HIP(hipMalloc(&d_wext, wext.size() * 4));
-      d_free_wext = d_wext;
-      FDK_HIP(hipMemcpy(d_wext, wext.data(), wext.size() * 4, hipMemcpyHostToDevice));
-    }
-    const double scale = (o->sdd / o->sid) / o->du;
-    if (direct) {
-      std::vector<float> h(hd.begin(), hd.end());
-      FDK_HIP(hipMalloc(&d_h, h.size() * 4));
-      FDK_HIP(hipMemcpy(d_h, h.data(), h.size() * 4, hipMemcpyHostToDevice));
-    } else {
-      // spectrum of the kernel laid out circularly (lag n at index n mod L); real because the kernel is even;
-      // the scale of the filter and hipFFT's missing 1/L are folded in
-      // L is not a power of two: the (real, even) kernel's spectrum by its cosine sum, H[k] = h[0] + 2 sum_lag h[lag] cos(2 pi k lag / L),
-      // with one table of cosines (30 M multiply-adds in double: tens of milliseconds, once per reconstruction)
-      std::vector<double> cosine((size_t)L);
-      for (int t = 0; t < L; ++t) cosine[(size_t)t] = std::cos(2.0 * M_PI * (double)t / (double)L);
-      std::vector<float> H((size_t)nk);
-      const double* h0 = hd.data() + (nu_e - 1);  // h0[lag], lag = -(nu_e - 1) .. nu_e - 1
-      for (int k = 0; k < nk; ++k) {
-        double acc = h0[0];
-        size_t t = 0;  // (k * lag) mod L
-        for (int lag = 1; lag <= max_lag; ++lag) {
-          t += (size_t)k;
-          if (t >= (size_t)L) t -= (size_t)L;
-          acc += 2.0 * h0[lag] * cosine[t];
-        }
-        H[(size_t)k] = (float)(acc * scale / (double)L);
-      }
-      FDK_HIP(hipMalloc(&d_h, H.size() * 4));
-      FDK_HIP(hipMemcpy(d_h, H.data(), H.size() * 4, hipMemcpyHostToDevice));
-      FDK_HIP(hipMalloc(&d_spec, (size_t)chunk * nv * nk * sizeof(float2)));
-    }
-    FDK_HIP(hipMalloc(&d_ky, ky.size() * 4));
-    FDK_HIP(hipMemcpy(d_ky, ky.data(), ky.size() * 4, hipMemcpyHostToDevice));
-    FDK_HIP(hipMalloc(&d_wdis, wdis.size() * 4));
-    FDK_HIP(hipMemcpy(d_wdis, wdis.data(), wdis.size() * 4, hipMemcpyHostToDevice));
-    FDK_HIP(hipMalloc(&d_pp, pp.size() * sizeof(ProjParam)));
-    FDK_HIP(hipMemcpy(d_pp, pp.data(), pp.size() * sizeof(ProjParam), hipMemcpyHostToDevice));
-    std::vector<float> wpc;
-    for (int j = 0; j < o->n_wpc; ++j) wpc.push_back((float)o->wpc[j]);
-    if (!wpc.empty()) {
-      FDK_HIP(hipMalloc(&d_wpc, wpc.size() * 4));
-      FDK_HIP(hipMemcpy(d_wpc, wpc.data(), wpc.size() * 4, hipMemcpyHostToDevice));
-    }
-    FDK_HIP(hipEventCreate(&e0)); FDK_HIP(hipEventCreate(&e1)); FDK_HIP(hipEventCreate(&e2)); FDK_HIP(hipEventCreate(&e3));
-    double ms_filter = 0.0, ms_back = 0.0;
-    const size_t lds_ramp = ((size_t)nu_e + 2 * nu_e + 2) * 4;
-    if (direct && lds_ramp > 64 * 1024)
-      FDK_HIP(hipFuncSetAttribute((const void*)ramp_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ramp));
-    int planned_rows = 0;
-    for (int first = 0; first < n; first += chunk) {
-      const int m = std::min(chunk, n - first);
-      const size_t elems = (size_t)m * plane_p;
-      FDK_HIP(hipMemcpy(d_raw, projections + (size_t)first * plane, (size_t)m * plane * 4, hipMemcpyHostToDevice));
-      if (!direct && planned_rows != m * nv) {  // one batched plan per chunk size (at most two: full chunks and the last one)
-        if (plan_fwd) { hipfftDestroy(plan_fwd); hipfftDestroy(plan_inv); plan_fwd = plan_inv = 0; }
-        int len[1] = {L};
-        if (hipfftPlanMany(&plan_fwd, 1, len, nullptr, 1, L, nullptr, 1, nk, HIPFFT_R2C, m * nv) != HIPFFT_SUCCESS ||
-            hipfftPlanMany(&plan_inv, 1, len, nullptr, 1, nk, nullptr, 1, L, HIPFFT_C2R, m * nv) != HIPFFT_SUCCESS)
-          throw FdkError{"!!ERROR!! mcgpu_fdk_reconstruct: hipfftPlanMany failed"};
-        planned_rows = m * nv;
-      }
-      FDK_HIP(hipEventRecord(e0, nullptr));
-      const unsigned gb = (unsigned)((elems + 255) / 256);
-      hipLaunchKernelGGL(weight_kernel, dim3(gb), dim3(256), 0, nullptr, d_raw, d_in, nu, nv, m, stride, next + pad_l, (float)o->du, (float)o->dv, (float)o->u0,
-                         (float)o->v0, (float)o->sdd, d_pp + first, d_wdis + (size_t)first * nu, d_wpc, (int)wpc.size());
-      if (next > 0) {
-        const size_t ne = (size_t)m * nv * next;
-        hipLaunchKernelGGL(extend_rows_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, nullptr, d_in, stride, nu_p, next, (size_t)m * nv, d_wext);
-      }
-      if (direct) {
-        hipLaunchKernelGGL(ramp_rows_kernel, dim3((unsigned)(m * nv)), dim3(256), lds_ramp, nullptr, d_in, d_tmp, d_h, nu_e, (float)scale, next > 0 ? 0 : pad_l,
-                           next > 0 ? nu_e : pad_l + nu);
-      } else {
-        if (hipfftExecR2C(plan_fwd, d_in, (hipfftComplex*)d_spec) != HIPFFT_SUCCESS) throw FdkError{"!!ERROR!! mcgpu_fdk_reconstruct: hipfftExecR2C failed"};
-        const size_t ns = (size_t)m * nv * nk;
-        hipLaunchKernelGGL(spectrum_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, nullptr, d_spec, d_h, nk, ns);
-        if (hipfftExecC2R(plan_inv, (hipfftComplex*)d_spec, d_tmp) != HIPFFT_SUCCESS) throw FdkError{"!!ERROR!! mcgpu_fdk_reconstruct: hipfftExecC2R failed"};
-      }
-      const float* filtered = d_tmp;
-      if (ky.size() > 1) {
-        const size_t na = (size_t)m * nv * nu_e;
-        hipLaunchKernelGGL(smooth_cols_kernel, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, nullptr, d_tmp, d_in, nu_e, stride, nv, m, d_ky, (int)ky.size());
-        filtered = d_in;
-      }
-      FDK_HIP(hipEventRecord(e1, nullptr));
-      for (int b = 0; b < m; b += kBatch) {
-        BackArgs A;
-        A.nx = o->nx; A.ny = o->ny; A.nz = o->nz; A.nu = nu_p; A.u_first = next; A.stride = stride; A.nv = nv; A.nb = std::min(kBatch, m - b);
-        A.x0 = (float)ox0; A.y0 = (float)oy0; A.z0 = (float)oz0; A.sx = (float)o->sx; A.sy = (float)o->sy; A.sz = (float)o->sz;
-        A.sid = (float)o->sid; A.sdd = (float)o->sdd; A.inv_du = (float)(1.0 / o->du); A.inv_dv = (float)(1.0 / o->dv);
-        A.u0 = (float)u0_p; A.v0 = (float)o->v0;
-        for (int k = 0; k < kBatch; ++k) A.pp[k] = (k < A.nb) ? pp[first + b + k] : ProjParam{1.f, 0.f, 0.f, 0.f, 0.f};
-        hipLaunchKernelGGL(backproject_kernel, dim3((unsigned)((o->nx + 255) / 256), (unsigned)o->nz), dim3(256), 0, nullptr, d_vol,
-                           filtered + (size_t)b * plane_p, A);
-      }
-      FDK_HIP(hipEventRecord(e2, nullptr));
-      FDK_HIP(hipEventSynchronize(e2));
-      float a = 0.f, bms = 0.f;
-      FDK_HIP(hipEventElapsedTime(&a, e0, e1));
-      FDK_HIP(hipEventElapsedTime(&bms, e1, e2));
-      ms_filter += a; ms_back += bms;
-    }
-    FDK_HIP(hipGetLastError());
-    FDK_HIP(hipMemcpy(volume, d_vol, nvox * 4, hipMemcpyDeviceToHost));
-    if (report) { report->ms_filter = ms_filter; report->ms_backproject = ms_back; }
-  } catch (const FdkError& e) {
-    mcgpu_set_last_error_(e.msg.c_str());
-    rc = -1;
-  }
-  if (plan_fwd) hipfftDestroy(plan_fwd);
-  if (plan_inv) hipfftDestroy(plan_inv);
-  for (void* p : {(void*)d_spec, (void*)d_free_raw, (void*)d_in, (void*)d_tmp, (void*)d_vol, (void*)d_h, (void*)d_ky, (void*)d_wdis, (void*)d_wpc, (void*)d_pp, (void*)d_free_wext})
-    if (p) (void)hipFree(p);
-  for (hipEvent_t e : {e0, e1, e2, e3})
-    if (e) (void)hipEventDestroy(e);
-  return rc;
+  HIP_TRY(hipMemcpy(volume, P.d_vol, plan.nvox * 4, hipMemcpyDeviceToHost));
+  if (report) *report = P.rep;
+  return 0;
+  ABI_END
 }

@@ -25,8 +25,6 @@
 #include "engine_internal.hpp"
 #include "joseph_ray.inc"
 
-extern "C" void mcgpu_set_last_error_(const char* message);
-
 namespace {
 
 using namespace mcgpu;
@@ -117,25 +115,10 @@ __global__ __launch_bounds__(256) void joseph_fp_kernel(float* __restrict__ out 
   out[((size_t)blockIdx.z * A.nv + iv) * A.nu + iu] = acc;
 }
 
-struct FpError { int code; std::string msg; };
-#define FP_HIP(expr)                                                                                      \
-  do {                                                                                                    \
-    hipError_t _e = (expr);                                                                               \
-    if (_e != hipSuccess) throw FpError{-1, std::string("!!HIP ERROR!! ") + #expr + ": " + hipGetErrorString(_e)}; \
-  } while (0)
-
-bool read_options(const char* fn, const mcgpu_fp_options* caller, mcgpu_fp_options& o) {
-  if (!caller || caller->struct_size == 0) {
-    mcgpu_set_last_error_((std::string("!!ERROR!! ") + fn + ": set mcgpu_fp_options.struct_size = sizeof(mcgpu_fp_options)").c_str());
-    return false;
-  }
-  memset(&o, 0, sizeof o);  // a caller built against an older header passes a shorter struct: what it does not have reads as zero
-  memcpy(&o, caller, std::min<size_t>(caller->struct_size, sizeof o));
-  if (o.n_proj < 1 || o.nu < 1 || o.nv < 1 || !o.gantry_deg || !(o.du > 0) || !(o.dv > 0) || !(o.sid > 0) || !(o.sdd > 0)) {
-    mcgpu_set_last_error_((std::string("!!ERROR!! ") + fn + ": bad argument").c_str());
-    return false;
-  }
-  return true;
+void read_fp_options(const char* fn, const mcgpu_fp_options* caller, mcgpu_fp_options& o) {
+  read_options(fn, "mcgpu_fp_options", caller, o);
+  if (o.n_proj < 1 || o.nu < 1 || o.nv < 1 || !o.gantry_deg || !(o.du > 0) || !(o.dv > 0) || !(o.sid > 0) || !(o.sdd > 0))
+    throw Error(-1, std::string("!!ERROR!! ") + fn + ": bad argument");
 }
 
 // FpArgs of the volume; the per-projection block is filled per launch
@@ -147,7 +130,7 @@ FpArgs volume_args(const mcgpu_fp_options& o, const int n[3], const double sp[3]
   for (int a = 0; a < 3; ++a) {
     A.n[a] = n[a];
     A.sp[a] = sp[a];
-    A.o[a] = std::isnan(org[a]) ? -(n[a] - 1) / 2.0 * sp[a] : org[a];
+    A.o[a] = centred_origin(n[a], sp[a], org[a]);
   }
   A.u0 = o.u0; A.v0 = o.v0; A.du = o.du; A.dv = o.dv; A.sid = o.sid; A.sdd = o.sdd;
   return A;
@@ -155,122 +138,88 @@ FpArgs volume_args(const mcgpu_fp_options& o, const int n[3], const double sp[3]
 
 // all projections through one source; projections [n_proj][nv][nu] on the host
 template <class Src>
-void project_all(const mcgpu_fp_options& o, FpArgs A, const Src& src, const float* pal2, int pal_n, float* projections, double& ms_kernel) {
+void project_all(CallDevice& dev, const mcgpu_fp_options& o, FpArgs A, const Src& src, const float* pal2, int pal_n, float* projections, double& ms_kernel) {
   const size_t plane = (size_t)o.nu * o.nv;
   const int chunk = std::min(o.n_proj, kChunk);
-  float* d_out = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  try {
-    FP_HIP(hipMalloc(&d_out, (size_t)chunk * plane * 4));
-    FP_HIP(hipEventCreate(&e0));
-    FP_HIP(hipEventCreate(&e1));
-    for (int first = 0; first < o.n_proj; first += chunk) {
-      const int m = std::min(chunk, o.n_proj - first);
-      FP_HIP(hipEventRecord(e0, nullptr));
-      for (int b = 0; b < m; b += kBatch) {
-        A.nb = std::min(kBatch, m - b);
-        for (int k = 0; k < A.nb; ++k) {
-          const int p = first + b + k;
-          const double t = o.gantry_deg[p] * M_PI / 180.0;
-          A.pp[k] = {std::cos(t), std::sin(t), o.proj_offset_x ? o.proj_offset_x[p] : 0.0, o.proj_offset_y ? o.proj_offset_y[p] : 0.0};
-        }
-        hipLaunchKernelGGL(joseph_fp_kernel<Src>, dim3((unsigned)((o.nu + 15) / 16), (unsigned)((o.nv + 15) / 16), (unsigned)A.nb), dim3(256), 0, nullptr,
-                           d_out + (size_t)b * plane, A, src, pal2, pal_n);
+  float* d_out = dev.alloc<float>((size_t)chunk * plane * 4);
+  dev.events();
+  for (int first = 0; first < o.n_proj; first += chunk) {
+    const int m = std::min(chunk, o.n_proj - first);
+    Stage st(dev, ms_kernel);
+    for (int b = 0; b < m; b += kBatch) {
+      A.nb = std::min(kBatch, m - b);
+      for (int k = 0; k < A.nb; ++k) {
+        const ProjectionPose q = projection_pose(o, first + b + k);
+        A.pp[k] = {q.c, q.s, q.off_x, q.off_y};
       }
-      FP_HIP(hipGetLastError());
-      FP_HIP(hipEventRecord(e1, nullptr));
-      FP_HIP(hipEventSynchronize(e1));
-      float ms = 0.f;
-      FP_HIP(hipEventElapsedTime(&ms, e0, e1));
-      ms_kernel += ms;
-      FP_HIP(hipMemcpy(projections + (size_t)first * plane, d_out, (size_t)m * plane * 4, hipMemcpyDeviceToHost));
+      hipLaunchKernelGGL(joseph_fp_kernel<Src>, dim3((unsigned)((o.nu + 15) / 16), (unsigned)((o.nv + 15) / 16), (unsigned)A.nb), dim3(256), 0, nullptr,
+                         d_out + (size_t)b * plane, A, src, pal2, pal_n);
     }
-  } catch (...) {
-    if (d_out) (void)hipFree(d_out);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    throw;
+    st.done();
+    HIP_TRY(hipMemcpy(projections + (size_t)first * plane, d_out, (size_t)m * plane * 4, hipMemcpyDeviceToHost));
   }
-  (void)hipFree(d_out);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
 }
 
 }  // namespace
 
 extern "C" int mcgpu_forward_project(const mcgpu_fp_options* caller_o, const float* volume, float* projections, mcgpu_fp_report* report) {
+  ABI_BEGIN
   mcgpu_fp_options o;
-  if (!read_options("mcgpu_forward_project", caller_o, o)) return -1;
-  if (!volume || !projections || o.nx < 1 || o.ny < 1 || o.nz < 1 || !(o.sx > 0) || !(o.sy > 0) || !(o.sz > 0)) {
-    mcgpu_set_last_error_("!!ERROR!! mcgpu_forward_project: bad volume argument");
-    return -1;
-  }
-  float* d_vol = nullptr;
-  int rc = 0;
-  try {
-    FP_HIP(hipSetDevice(o.device));
-    const size_t nvox = (size_t)o.nx * o.ny * o.nz;
-    const auto t0 = std::chrono::steady_clock::now();
-    FP_HIP(hipMalloc(&d_vol, nvox * 4));
-    FP_HIP(hipMemcpy(d_vol, volume, nvox * 4, hipMemcpyHostToDevice));
-    const double ms_upload = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    const int n[3] = {o.nx, o.ny, o.nz};
-    const double sp[3] = {o.sx, o.sy, o.sz};
-    SrcFloat src{d_vol, o.nx, o.nx * o.ny};
-    double ms_kernel = 0.0;
-    project_all(o, volume_args(o, n, sp), src, nullptr, 0, projections, ms_kernel);
-    if (report) { report->ms_kernel = ms_kernel; report->ms_upload = ms_upload; }
-  } catch (const FpError& e) {
-    mcgpu_set_last_error_(e.msg.c_str());
-    rc = e.code;
-  }
-  if (d_vol) (void)hipFree(d_vol);
-  return rc;
+  read_fp_options("mcgpu_forward_project", caller_o, o);
+  if (!volume || !projections || o.nx < 1 || o.ny < 1 || o.nz < 1 || !(o.sx > 0) || !(o.sy > 0) || !(o.sz > 0))
+    throw Error(-1, "!!ERROR!! mcgpu_forward_project: bad volume argument");
+  HIP_TRY(hipSetDevice(o.device));
+  CallDevice dev;
+  const size_t nvox = (size_t)o.nx * o.ny * o.nz;
+  const auto t0 = std::chrono::steady_clock::now();
+  const float* d_vol = dev.upload(volume, nvox);
+  const double ms_upload = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  const int n[3] = {o.nx, o.ny, o.nz};
+  const double sp[3] = {o.sx, o.sy, o.sz};
+  SrcFloat src{d_vol, o.nx, o.nx * o.ny};
+  double ms_kernel = 0.0;
+  project_all(dev, o, volume_args(o, n, sp), src, nullptr, 0, projections, ms_kernel);
+  if (report) { report->ms_kernel = ms_kernel; report->ms_upload = ms_upload; }
+  return 0;
+  ABI_END
 }
 
 extern "C" int mcgpu_forward_project_context(mcgpu_ctx* ctx, const mcgpu_fp_options* caller_o, float* projections, mcgpu_fp_report* report) {
+  ABI_BEGIN
   mcgpu_fp_options o;
-  if (!read_options("mcgpu_forward_project_context", caller_o, o)) return -1;
-  if (!ctx || !ctx->has_device || !projections) {
-    mcgpu_set_last_error_("!!ERROR!! mcgpu_forward_project_context: bad argument (the context needs a device)");
-    return -1;
-  }
+  read_fp_options("mcgpu_forward_project_context", caller_o, o);
+  require(ctx && ctx->has_device && projections, -1, "!!ERROR!! mcgpu_forward_project_context: bad argument (the context needs a device)");
   const HostModel& H = ctx->host;
   const DeviceModel& D = ctx->dev;
   const int vn[3] = {H.voxels.n[0], H.voxels.n[1], H.voxels.n[2]};
   const int n[3] = {vn[1], vn[2], vn[0]};  // IEC (X, Y, Z) = (vox y, vox z, vox x), each reversed
   if ((o.nx || o.ny || o.nz) && (o.nx != n[0] || o.ny != n[1] || o.nz != n[2])) {
-    mcgpu_set_last_error_(("!!ERROR!! mcgpu_forward_project_context: volume size " + std::to_string(o.nx) + "x" + std::to_string(o.ny) + "x" +
-                           std::to_string(o.nz) + " is not the context's IEC size " + std::to_string(n[0]) + "x" + std::to_string(n[1]) + "x" +
-                           std::to_string(n[2])).c_str());
-    return -1;
+    throw Error(-1, "!!ERROR!! mcgpu_forward_project_context: volume size " + std::to_string(o.nx) + "x" + std::to_string(o.ny) + "x" +
+                        std::to_string(o.nz) + " is not the context's IEC size " + std::to_string(n[0]) + "x" + std::to_string(n[1]) + "x" +
+                        std::to_string(n[2]));
   }
   // spacing: the caller's (mm, IEC order) when given, else the context's voxel size (cm)
   const double sp[3] = {o.sx > 0 ? o.sx : 10.0 * H.voxels.voxel_size[1], o.sy > 0 ? o.sy : 10.0 * H.voxels.voxel_size[2],
                         o.sz > 0 ? o.sz : 10.0 * H.voxels.voxel_size[0]};
-  int rc = 0;
-  try {
-    FP_HIP(hipSetDevice(D.device_id));
-    const FpArgs A = volume_args(o, n, sp);
-    const VoxFrame f{vn[0], vn[1], vn[2]};
-    double ms_kernel = 0.0;
-    if (D.vol_kind == kVolU8) {
-      SrcU8 src{(const unsigned char*)D.vol, f, (unsigned)((vn[0] + 3) >> 2), (unsigned)(((vn[0] + 3) >> 2) * ((vn[1] + 3) >> 2))};
-      project_all(o, A, src, D.palette, D.palette_size, projections, ms_kernel);
-    } else if (D.vol_kind == kVolU16 && D.palette_size <= kPalLds) {
-      SrcU16<true> src{(const unsigned short*)D.vol, D.palette, f};
-      project_all(o, A, src, D.palette, D.palette_size, projections, ms_kernel);
-    } else if (D.vol_kind == kVolU16) {
-      SrcU16<false> src{(const unsigned short*)D.vol, D.palette, f};
-      project_all(o, A, src, D.palette, D.palette_size, projections, ms_kernel);
-    } else {
-      SrcRaw src{(const float2*)D.vol, f};
-      project_all(o, A, src, nullptr, 0, projections, ms_kernel);
-    }
-    if (report) { report->ms_kernel = ms_kernel; report->ms_upload = 0.0; }
-  } catch (const FpError& e) {
-    mcgpu_set_last_error_(e.msg.c_str());
-    rc = e.code;
+  HIP_TRY(hipSetDevice(D.device_id));
+  CallDevice dev;
+  const FpArgs A = volume_args(o, n, sp);
+  const VoxFrame f{vn[0], vn[1], vn[2]};
+  double ms_kernel = 0.0;
+  if (D.vol_kind == kVolU8) {
+    SrcU8 src{(const unsigned char*)D.vol, f, (unsigned)((vn[0] + 3) >> 2), (unsigned)(((vn[0] + 3) >> 2) * ((vn[1] + 3) >> 2))};
+    project_all(dev, o, A, src, D.palette, D.palette_size, projections, ms_kernel);
+  } else if (D.vol_kind == kVolU16 && D.palette_size <= kPalLds) {
+    SrcU16<true> src{(const unsigned short*)D.vol, D.palette, f};
+    project_all(dev, o, A, src, D.palette, D.palette_size, projections, ms_kernel);
+  } else if (D.vol_kind == kVolU16) {
+    SrcU16<false> src{(const unsigned short*)D.vol, D.palette, f};
+    project_all(dev, o, A, src, D.palette, D.palette_size, projections, ms_kernel);
+  } else {
+    SrcRaw src{(const float2*)D.vol, f};
+    project_all(dev, o, A, src, nullptr, 0, projections, ms_kernel);
   }
-  return rc;
+  if (report) { report->ms_kernel = ms_kernel; report->ms_upload = 0.0; }
+  return 0;
+  ABI_END
 }

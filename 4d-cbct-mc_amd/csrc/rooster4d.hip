@@ -29,8 +29,6 @@
 // float4 loads and the dot-product stages, positivity, tv_space_div / tv_space_grad (per frame: the spatial dual is 3 x one
 // frame) and tv_time_kernel (a voxel's whole series and its dual in registers: one read and one write of the 4-D volume).
 // Residency: the projection stack and the 4-D vectors x, b, r, d, A d stay on the device for the whole run.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -39,11 +37,13 @@
 #include <vector>
 
 #include "../../include/mcgpu_amd.h"
+#include "hip_host.hpp"
 #include "joseph_ray.inc"
 
-extern "C" void mcgpu_set_last_error_(const char* message);
-
 namespace {
+
+using mcgpu::CallDevice;
+using mcgpu::Stage;
 
 constexpr int kFpBatch = 16;     // projections per forward launch (blockIdx.z)
 constexpr int kBpBatch = 8;      // projections per back-projection launch (fdk.hip's measured optimum)
@@ -313,13 +313,6 @@ __global__ __launch_bounds__(256) void tv_time_kernel(float* __restrict__ x4, si
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
-struct RsError { std::string msg; };
-#define RS_HIP(expr)                                                                                      \
-  do {                                                                                                    \
-    hipError_t _e = (expr);                                                                               \
-    if (_e != hipSuccess) throw RsError{std::string("!!HIP ERROR!! ") + #expr + ": " + hipGetErrorString(_e)}; \
-  } while (0)
-
 // RTK's signal-to-weights rule for a periodic N-frame sequence: phase phi in [0, 1] lies between frames l = floor(phi N) mod N and
 // h = l + 1 mod N with linear weights; phi = 1 is frame 0 again.  This is the rule as RTK documents it (rtkfourdrooster --signal,
 // rtk::PhasesToInterpolationWeights); its exact match with RTK's code cannot be checked here (RTK is absent).
@@ -331,70 +324,22 @@ void interpolation_weights(double phase, int N, int& l, int& h, double& wl, doub
   wl = 1.0 - wh;
 }
 
-bool fail(const char* fn, const std::string& what) {
-  mcgpu_set_last_error_((std::string("!!ERROR!! ") + fn + ": " + what).c_str());
-  return false;
-}
+[[noreturn]] void refuse(const char* fn, const std::string& what) { throw mcgpu::Error(-1, std::string("!!ERROR!! ") + fn + ": " + what); }
 
-bool read_options(const char* fn, const mcgpu_rooster4d_options* caller, mcgpu_rooster4d_options& o) {
-  if (!caller || caller->struct_size == 0) return fail(fn, "set mcgpu_rooster4d_options.struct_size = sizeof(mcgpu_rooster4d_options)");
-  memset(&o, 0, sizeof o);  // a caller built against an older header passes a shorter struct: what it does not have reads as zero
-  memcpy(&o, caller, std::min<size_t>(caller->struct_size, sizeof o));
+void read_options(const char* fn, const mcgpu_rooster4d_options* caller, mcgpu_rooster4d_options& o) {
+  mcgpu::read_options(fn, "mcgpu_rooster4d_options", caller, o);
   if (o.n_proj < 1 || o.nu < 2 || o.nv < 2 || !o.gantry_deg || !(o.du > 0) || !(o.dv > 0) || !(o.sid > 0) || !(o.sdd > 0))
-    return fail(fn, "bad geometry argument");
-  if (o.nx < 1 || o.ny < 1 || o.nz < 1 || !(o.sx > 0) || !(o.sy > 0) || !(o.sz > 0)) return fail(fn, "bad volume argument");
-  if (o.n_frames < 1 || o.n_frames > kMaxFrames) return fail(fn, "n_frames must be 1.." + std::to_string(kMaxFrames));
-  if (!o.phase) return fail(fn, "phase is NULL");
+    refuse(fn, "bad geometry argument");
+  if (o.nx < 1 || o.ny < 1 || o.nz < 1 || !(o.sx > 0) || !(o.sy > 0) || !(o.sz > 0)) refuse(fn, "bad volume argument");
+  if (o.n_frames < 1 || o.n_frames > kMaxFrames) refuse(fn, "n_frames must be 1.." + std::to_string(kMaxFrames));
+  if (!o.phase) refuse(fn, "phase is NULL");
   for (int k = 0; k < o.n_proj; ++k)
-    if (!(o.phase[k] >= 0.0 && o.phase[k] <= 1.0)) return fail(fn, "phase[" + std::to_string(k) + "] is not in [0, 1]");
-  if (o.niter < 0 || o.cgiter < 0 || o.tviter < 0) return fail(fn, "niter, cgiter and tviter must be >= 0");
+    if (!(o.phase[k] >= 0.0 && o.phase[k] <= 1.0)) refuse(fn, "phase[" + std::to_string(k) + "] is not in [0, 1]");
+  if (o.niter < 0 || o.cgiter < 0 || o.tviter < 0) refuse(fn, "niter, cgiter and tviter must be >= 0");
   if (!(o.gamma_space >= 0.0) || !(o.gamma_time >= 0.0) || !std::isfinite(o.gamma_space) || !std::isfinite(o.gamma_time))
-    return fail(fn, "gamma_space and gamma_time must be finite and >= 0");
-  if (o.n_wpc < 0 || (o.n_wpc > 0 && !o.wpc)) return fail(fn, "bad wpc argument");
-  return true;
+    refuse(fn, "gamma_space and gamma_time must be finite and >= 0");
+  if (o.n_wpc < 0 || (o.n_wpc > 0 && !o.wpc)) refuse(fn, "bad wpc argument");
 }
-
-// device buffers and events of one call; frees everything it made, tracks the peak of the bytes it holds
-struct Device {
-  std::vector<void*> bufs;
-  std::vector<size_t> sizes;
-  size_t held = 0, peak = 0;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  template <class T>
-  T* alloc(size_t bytes) {
-    void* p = nullptr;
-    RS_HIP(hipMalloc(&p, bytes));
-    bufs.push_back(p);
-    sizes.push_back(bytes);
-    held += bytes;
-    peak = std::max(peak, held);
-    RS_HIP(hipMemset(p, 0, bytes));
-    return (T*)p;
-  }
-  void release(void* p) {
-    for (size_t i = 0; i < bufs.size(); ++i)
-      if (bufs[i] == p) { (void)hipFree(p); held -= sizes[i]; bufs.erase(bufs.begin() + i); sizes.erase(sizes.begin() + i); return; }
-  }
-  ~Device() {
-    for (void* p : bufs) (void)hipFree(p);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-  }
-};
-
-struct Stage {  // times a block of launches on the null stream into one report field
-  Device& dev;
-  double& ms;
-  Stage(Device& d, double& m) : dev(d), ms(m) { RS_HIP(hipEventRecord(dev.e0, nullptr)); }
-  void done() {
-    RS_HIP(hipGetLastError());
-    RS_HIP(hipEventRecord(dev.e1, nullptr));
-    RS_HIP(hipEventSynchronize(dev.e1));
-    float t = 0.f;
-    RS_HIP(hipEventElapsedTime(&t, dev.e0, dev.e1));
-    ms += t;
-  }
-};
 
 struct Problem {
   mcgpu_rooster4d_options o;
@@ -406,7 +351,7 @@ struct Problem {
   std::vector<Bp4Args> bp;              // one per back-projection batch, with the first projection of each
   std::vector<int> bp_first;
   mcgpu_rooster4d_report rep;
-  Device dev;
+  CallDevice dev;
   double* d_part = nullptr;
   double* d_sum = nullptr;
 
@@ -424,7 +369,7 @@ struct Problem {
     memset(&fa, 0, sizeof fa);
     fa.nu = o.nu; fa.nv = o.nv;
     for (int a = 0; a < 3; ++a) {
-      origin[a] = std::isnan(org[a]) ? -(n[a] - 1) / 2.0 * sp[a] : org[a];
+      origin[a] = mcgpu::centred_origin(n[a], sp[a], org[a]);
       fa.n[a] = n[a]; fa.sp[a] = sp[a]; fa.o[a] = origin[a];
     }
     fa.u0 = o.u0; fa.v0 = o.v0; fa.du = o.du; fa.dv = o.dv; fa.sid = o.sid; fa.sdd = o.sdd;
@@ -440,10 +385,10 @@ struct Problem {
       int m = 0;
       while (k + m < o.n_proj && m < kBpBatch && fl[k + m] == A.fl && fh[k + m] == A.fh) {
         const int p = k + m;
-        const double t = o.gantry_deg[p] * M_PI / 180.0;
-        A.c[m] = std::cos(t); A.s[m] = std::sin(t);
-        A.off_x[m] = o.proj_offset_x ? o.proj_offset_x[p] : 0.0;
-        A.av_b[m] = (float)((-(o.proj_offset_y ? o.proj_offset_y[p] : 0.0) - o.v0) / o.dv);
+        const mcgpu::ProjectionPose q = mcgpu::projection_pose(o, p);
+        A.c[m] = q.c; A.s[m] = q.s;
+        A.off_x[m] = q.off_x;
+        A.av_b[m] = (float)((-q.off_y - o.v0) / o.dv);
         A.wl[m] = (float)wl[p]; A.wh[m] = (float)wh[p];
         ++m;
       }
@@ -455,14 +400,13 @@ struct Problem {
   }
 
   void init() {
-    RS_HIP(hipSetDevice(o.device));
-    RS_HIP(hipEventCreate(&dev.e0));
-    RS_HIP(hipEventCreate(&dev.e1));
-    d_part = dev.alloc<double>(kRedBlocks * sizeof(double));
-    d_sum = dev.alloc<double>(sizeof(double));
+    HIP_TRY(hipSetDevice(o.device));
+    dev.events();
+    d_part = dev.alloc_zeroed<double>(kRedBlocks * sizeof(double));
+    d_sum = dev.alloc_zeroed<double>(sizeof(double));
   }
-  float* alloc4d() { return dev.alloc<float>(n4 * 16); }
-  float* alloc_proj() { return dev.alloc<float>((size_t)o.n_proj * plane * 4); }
+  float* alloc4d() { return dev.alloc_zeroed<float>(n4 * 16); }
+  float* alloc_proj() { return dev.alloc_zeroed<float>((size_t)o.n_proj * plane * 4); }
 
   // proj = R S x4
   void forward(const float* x4, float* proj) {
@@ -472,8 +416,8 @@ struct Problem {
       A.nb = std::min(kFpBatch, o.n_proj - b);
       for (int k = 0; k < A.nb; ++k) {
         const int p = b + k;
-        const double t = o.gantry_deg[p] * M_PI / 180.0;
-        A.pp[k] = {std::cos(t), std::sin(t), o.proj_offset_x ? o.proj_offset_x[p] : 0.0, o.proj_offset_y ? o.proj_offset_y[p] : 0.0};
+        const mcgpu::ProjectionPose q = mcgpu::projection_pose(o, p);
+        A.pp[k] = {q.c, q.s, q.off_x, q.off_y};
         A.fl[k] = fl[p]; A.fh[k] = fh[p]; A.wl[k] = (float)wl[p]; A.wh[k] = (float)wh[p];
       }
       hipLaunchKernelGGL(fp4_kernel, dim3((unsigned)((o.nu + 15) / 16), (unsigned)((o.nv + 15) / 16), (unsigned)A.nb), dim3(256), 0, nullptr,
@@ -485,7 +429,7 @@ struct Problem {
   // x4 = S^T B proj
   void back(const float* proj, float* x4) {
     Stage st(dev, rep.ms_back);
-    RS_HIP(hipMemsetAsync(x4, 0, n4 * 16, nullptr));
+    HIP_TRY(hipMemsetAsync(x4, 0, n4 * 16, nullptr));
     for (size_t i = 0; i < bp.size(); ++i)
       hipLaunchKernelGGL(bp4_kernel, dim3((unsigned)((o.nx + 255) / 256), (unsigned)o.nz), dim3(256), 0, nullptr, x4, frame,
                          proj + (size_t)bp_first[i] * plane, bp[i]);
@@ -495,7 +439,7 @@ struct Problem {
   double reduce() {  // second stage of a dot product whose partials are in d_part
     hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(kThreads), 0, nullptr, d_part, d_sum);
     double s = 0.0;
-    RS_HIP(hipMemcpy(&s, d_sum, sizeof s, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&s, d_sum, sizeof s, hipMemcpyDeviceToHost));
     return s;
   }
 
@@ -514,7 +458,7 @@ struct Problem {
     const unsigned g = (unsigned)std::min<size_t>((frame + kThreads - 1) / kThreads, 65536);
     for (int f = 0; f < N; ++f) {
       float* x = x4 + (size_t)f * frame;
-      RS_HIP(hipMemsetAsync(work, 0, 3 * frame * 4, nullptr));
+      HIP_TRY(hipMemsetAsync(work, 0, 3 * frame * 4, nullptr));
       for (int it = 0; it < iters; ++it) {
         hipLaunchKernelGGL(tv_space_div_kernel, dim3(g), dim3(kThreads), 0, nullptr, x, px, py, pz, u, o.nx, o.ny, o.nz);
         hipLaunchKernelGGL(tv_space_grad_kernel, dim3(g), dim3(kThreads), 0, nullptr, u, px, py, pz, o.nx, o.ny, o.nz, tau, gamma);
@@ -535,14 +479,14 @@ struct Problem {
   float* upload_projections(const float* projections, bool wpc) {
     const auto t0 = std::chrono::steady_clock::now();
     float* d = alloc_proj();
-    RS_HIP(hipMemcpy(d, projections, (size_t)o.n_proj * plane * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d, projections, (size_t)o.n_proj * plane * 4, hipMemcpyHostToDevice));
     if (wpc && o.n_wpc > 0) {
       std::vector<float> c(o.wpc, o.wpc + o.n_wpc);
-      float* d_c = dev.alloc<float>(c.size() * 4);
-      RS_HIP(hipMemcpy(d_c, c.data(), c.size() * 4, hipMemcpyHostToDevice));
+      float* d_c = dev.alloc_zeroed<float>(c.size() * 4);
+      HIP_TRY(hipMemcpy(d_c, c.data(), c.size() * 4, hipMemcpyHostToDevice));
       hipLaunchKernelGGL(wpc_kernel, dim3(kRedBlocks), dim3(kThreads), 0, nullptr, d, (size_t)o.n_proj * plane, d_c, o.n_wpc);
-      RS_HIP(hipGetLastError());
-      RS_HIP(hipDeviceSynchronize());
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipDeviceSynchronize());
     }
     rep.ms_upload += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return d;
@@ -551,7 +495,7 @@ struct Problem {
   float* upload_4d(const float* v) {
     const auto t0 = std::chrono::steady_clock::now();
     float* d = alloc4d();
-    RS_HIP(hipMemcpy(d, v, n4d * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d, v, n4d * 4, hipMemcpyHostToDevice));
     rep.ms_upload += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return d;
   }
@@ -563,14 +507,14 @@ struct Problem {
     float* r = alloc4d();
     float* d = alloc4d();
     float* Ad = alloc4d();
-    float* work = dev.alloc<float>(4 * frame * 4);
+    float* work = dev.alloc_zeroed<float>(4 * frame * 4);
     back(q, b);
     const unsigned g = kRedBlocks;
     bool x_zero = true;
     for (int it = 0; it < o.niter; ++it) {
       double* res = o.residuals ? o.residuals + (size_t)it * (o.cgiter + 1) : nullptr;
       if (x_zero) {
-        RS_HIP(hipMemsetAsync(Ad, 0, n4 * 16, nullptr));  // A 0 = 0
+        HIP_TRY(hipMemsetAsync(Ad, 0, n4 * 16, nullptr));  // A 0 = 0
       } else {
         forward(x, q);
         back(q, Ad);
@@ -614,7 +558,7 @@ struct Problem {
         tv_time(x, o.tviter, (float)o.gamma_time);
       }
     }
-    RS_HIP(hipMemcpy(volume4d, x, n4d * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(volume4d, x, n4d * 4, hipMemcpyDeviceToHost));
   }
 
   void stage(int which, const float* in, float* out) {
@@ -622,65 +566,58 @@ struct Problem {
       float* x = upload_4d(in);
       float* q = alloc_proj();
       forward(x, q);
-      RS_HIP(hipMemcpy(out, q, (size_t)o.n_proj * plane * 4, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(out, q, (size_t)o.n_proj * plane * 4, hipMemcpyDeviceToHost));
       return;
     }
     if (which == MCGPU_ROOSTER4D_STAGE_BACK) {
       float* q = upload_projections(in, false);
       float* x = alloc4d();
       back(q, x);
-      RS_HIP(hipMemcpy(out, x, n4d * 4, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(out, x, n4d * 4, hipMemcpyDeviceToHost));
       return;
     }
     float* x = upload_4d(in);
     if (which == MCGPU_ROOSTER4D_STAGE_TV_SPACE) {
-      float* work = dev.alloc<float>(4 * frame * 4);
+      float* work = dev.alloc_zeroed<float>(4 * frame * 4);
       tv_space(x, work, o.tviter, (float)o.gamma_space);
     } else {
       tv_time(x, o.tviter, (float)o.gamma_time);
     }
-    RS_HIP(hipMemcpy(out, x, n4d * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, x, n4d * 4, hipMemcpyDeviceToHost));
   }
 };
 
 }  // namespace
 
 extern "C" int mcgpu_rooster4d_reconstruct(const mcgpu_rooster4d_options* caller_o, const float* projections, float* volume4d, mcgpu_rooster4d_report* report) {
+  ABI_BEGIN
   mcgpu_rooster4d_options o;
-  if (!read_options("mcgpu_rooster4d_reconstruct", caller_o, o)) return -1;
-  if (!projections || !volume4d) return fail("mcgpu_rooster4d_reconstruct", "projections or volume is NULL"), -1;
-  try {
-    const auto t0 = std::chrono::steady_clock::now();
-    Problem P(o);
-    P.init();
-    P.run(projections, volume4d);
-    P.rep.peak_device_bytes = P.dev.peak;
-    P.rep.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (report) *report = P.rep;
-  } catch (const RsError& e) {
-    mcgpu_set_last_error_(e.msg.c_str());
-    return -1;
-  }
+  read_options("mcgpu_rooster4d_reconstruct", caller_o, o);
+  if (!projections || !volume4d) refuse("mcgpu_rooster4d_reconstruct", "projections or volume is NULL");
+  const auto t0 = std::chrono::steady_clock::now();
+  Problem P(o);
+  P.init();
+  P.run(projections, volume4d);
+  P.rep.peak_device_bytes = P.dev.peak;
+  P.rep.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (report) *report = P.rep;
   return 0;
+  ABI_END
 }
 
 extern "C" int mcgpu_rooster4d_stage(const mcgpu_rooster4d_options* caller_o, int stage, const float* in, float* out, mcgpu_rooster4d_report* report) {
+  ABI_BEGIN
   mcgpu_rooster4d_options o;
-  if (!read_options("mcgpu_rooster4d_stage", caller_o, o)) return -1;
-  if (stage < MCGPU_ROOSTER4D_STAGE_FORWARD || stage > MCGPU_ROOSTER4D_STAGE_TV_TIME)
-    return fail("mcgpu_rooster4d_stage", "unknown stage " + std::to_string(stage)), -1;
-  if (!in || !out) return fail("mcgpu_rooster4d_stage", "in or out is NULL"), -1;
-  try {
-    const auto t0 = std::chrono::steady_clock::now();
-    Problem P(o);
-    P.init();
-    P.stage(stage, in, out);
-    P.rep.peak_device_bytes = P.dev.peak;
-    P.rep.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (report) *report = P.rep;
-  } catch (const RsError& e) {
-    mcgpu_set_last_error_(e.msg.c_str());
-    return -1;
-  }
+  read_options("mcgpu_rooster4d_stage", caller_o, o);
+  if (stage < MCGPU_ROOSTER4D_STAGE_FORWARD || stage > MCGPU_ROOSTER4D_STAGE_TV_TIME) refuse("mcgpu_rooster4d_stage", "unknown stage " + std::to_string(stage));
+  if (!in || !out) refuse("mcgpu_rooster4d_stage", "in or out is NULL");
+  const auto t0 = std::chrono::steady_clock::now();
+  Problem P(o);
+  P.init();
+  P.stage(stage, in, out);
+  P.rep.peak_device_bytes = P.dev.peak;
+  P.rep.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (report) *report = P.rep;
   return 0;
+  ABI_END
 }

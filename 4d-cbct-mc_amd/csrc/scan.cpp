@@ -19,8 +19,6 @@
 // of two: 9.2 -> 12.5 ms, tools/placement_probe.py).  With one device the lag is zero.
 // History sharding keeps per-history RNG streams and integer tallies, so the result is identical for any number of
 // devices (tests run several "devices" on one).
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -35,13 +33,18 @@
 #include <vector>
 
 #include "../../include/mcgpu_amd.h"
+#include "hip_host.hpp"
 #include "knobs.hpp"
 using mcgpu::knob_set;
 using mcgpu::knob_str;
 
-extern "C" void mcgpu_set_last_error_(const char* message);  // engine.cpp (not part of the public ABI)
-
 namespace {
+
+using mcgpu::DeviceBuffer;
+using mcgpu::Error;
+using mcgpu::Event;
+using mcgpu::PinnedBuffer;
+using mcgpu::Stream;
 
 constexpr int kAsciiSlots = MCGPU_ASCII_SLOTS;
 constexpr int kExchangeUnavailable = -7;  // the devices of a multi-device scan cannot reach each other (set-up phase only)
@@ -49,37 +52,11 @@ constexpr int kRcclUnavailable = -8;      // the RCCL route cannot be set up on 
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-struct ScanError {
-  int code;
-  std::string msg;
-};
-#define HIP_OK(expr)                                                                                                \
-  do {                                                                                                              \
-    hipError_t _e = (expr);                                                                                         \
-    if (_e != hipSuccess) throw ScanError{-1, std::string("!!HIP ERROR!! ") + #expr + ": " + hipGetErrorString(_e)}; \
+#define ABI_OK(expr)                                             \
+  do {                                                           \
+    const int _rc = (expr);                                      \
+    if (_rc != 0) throw Error(_rc, std::string(mcgpu_last_error())); \
   } while (0)
-#define ABI_OK(expr)                                                    \
-  do {                                                                  \
-    const int _rc = (expr);                                             \
-    if (_rc != 0) throw ScanError{_rc, std::string(mcgpu_last_error())}; \
-  } while (0)
-
-// A HIP object that remembers its device and is released there.  make(dev) hands the create call its out-parameter.
-template <class T, hipError_t (*Release)(T)>
-struct Owned {
-  T h = nullptr;
-  int dev = -1;
-  Owned() = default;
-  Owned(const Owned&) = delete;
-  ~Owned() { reset(); }
-  T* make(int device) { reset(); dev = device; return &h; }
-  void reset() { if (h) { (void)hipSetDevice(dev); (void)Release(h); h = nullptr; } }
-  operator T() const { return h; }
-};
-using DeviceBuffer = Owned<void*, hipFree>;
-using PinnedBuffer = Owned<void*, hipHostFree>;
-using Event = Owned<hipEvent_t, hipEventDestroy>;
-using Stream = Owned<hipStream_t, hipStreamDestroy>;
 
 // ---- what both sharding paths derive from the contexts' configuration and the options, validated once
 struct ScanPlan {
@@ -115,15 +92,15 @@ struct ScanPlan {
 // Checks in this order: the mode, the devices, then the range and the stride / phase.
 ScanPlan plan_scan(mcgpu_ctx* const* ctxs, int n_ctx, const mcgpu_scan_options* opt) {
   if (opt->mode != MCGPU_MODE_FAST && opt->mode != MCGPU_MODE_COMPAT && opt->mode != MCGPU_MODE_FAST_F64)
-    throw ScanError{-1, "!!ERROR!! mcgpu_run_scan: unknown mode " + std::to_string(opt->mode) +
-                            " (MCGPU_MODE_FAST, MCGPU_MODE_COMPAT or MCGPU_MODE_FAST_F64)"};
+    throw Error(-1, "!!ERROR!! mcgpu_run_scan: unknown mode " + std::to_string(opt->mode) +
+                        " (MCGPU_MODE_FAST, MCGPU_MODE_COMPAT or MCGPU_MODE_FAST_F64)");
   ScanPlan s;
   s.mode = opt->mode;
   s.ctxs.assign(ctxs, ctxs + n_ctx);
   for (mcgpu_ctx* c : s.ctxs) {
     long long dev = -1;
     ABI_OK(mcgpu_config_i64(c, "device_id", &dev));
-    if (dev < 0) throw ScanError{-1, "!!ERROR!! mcgpu_run_scan: a context has no device"};
+    if (dev < 0) throw Error(-1, "!!ERROR!! mcgpu_run_scan: a context has no device");
     s.devs.push_back((int)dev);
   }
   mcgpu_ctx* const ctx = ctxs[0];
@@ -136,11 +113,11 @@ ScanPlan plan_scan(mcgpu_ctx* const* ctxs, int n_ctx, const mcgpu_scan_options* 
   for (const auto& c : f64) ABI_OK(mcgpu_config_f64(ctx, c.first, c.second));
   s.first = opt->first_projection > 0 ? opt->first_projection : 0;
   s.range = (opt->num_projections > 0) ? opt->num_projections : (int)s.nproj_all - s.first;
-  if (s.first + s.range > s.nproj_all || s.range <= 0) throw ScanError{-1, "!!ERROR!! mcgpu_run_scan: projection range outside the trajectory"};
+  if (s.first + s.range > s.nproj_all || s.range <= 0) throw Error(-1, "!!ERROR!! mcgpu_run_scan: projection range outside the trajectory");
   const int stride = opt->projection_stride > 1 ? opt->projection_stride : 1;
   s.phase = stride > 1 ? opt->projection_phase : 0;
-  if (s.phase < 0 || s.phase >= stride) throw ScanError{-1, "!!ERROR!! mcgpu_run_scan: projection_phase outside [0, projection_stride)"};
-  if (opt->shared_stacks && !opt->slice_of_projection) throw ScanError{-1, "!!ERROR!! mcgpu_run_scan: shared_stacks needs slice_of_projection"};
+  if (s.phase < 0 || s.phase >= stride) throw Error(-1, "!!ERROR!! mcgpu_run_scan: projection_phase outside [0, projection_stride)");
+  if (opt->shared_stacks && !opt->slice_of_projection) throw Error(-1, "!!ERROR!! mcgpu_run_scan: shared_stacks needs slice_of_projection");
   int before = 0;  // simulated projections of the trajectory before the range
   for (int p = 0; p < s.first; ++p) before += !s.outside_roi(p);
   for (int k = 0, n_sim = 0; k < s.range; ++k)
@@ -185,15 +162,15 @@ unsigned long long budget_histories(const ScanPlan& plan, hipStream_t stream, in
   const unsigned long long probe_units = plan.mode == MCGPU_MODE_COMPAT ? (probe + (unsigned long long)plan.hpt - 1) / (unsigned long long)plan.hpt : probe;
   DeviceBuffer tally;
   float ms = 0.f;
-  HIP_OK(hipSetDevice(plan.devs[0]));
-  HIP_OK(hipMalloc(tally.make(plan.devs[0]), plan.words * 8));
-  HIP_OK(hipMemsetAsync(tally, 0, plan.words * 8, stream));
+  HIP_TRY(hipSetDevice(plan.devs[0]));
+  HIP_TRY(hipMalloc(tally.make(plan.devs[0]), plan.words * 8));
+  HIP_TRY(hipMemsetAsync(tally, 0, plan.words * 8, stream));
   for (int rep = 0; rep < 2; ++rep) {  // the first launch pays one-off costs
     ABI_OK(mcgpu_launch_projection(plan.ctxs[0], plan.first, plan.mode, (int)plan.seed, 0, probe_units, (int)plan.hpt, tally, stream));
     ABI_OK(mcgpu_last_kernel_ms(plan.ctxs[0], &ms));
   }
   ABI_OK(mcgpu_dose_clear(plan.ctxs[0]));
-  HIP_OK(hipStreamSynchronize(stream));
+  HIP_TRY(hipStreamSynchronize(stream));
   const double rate = (double)probe / (ms > 0.f ? ms * 1e-3 : 1e-3) * n_share;
   const unsigned long long H = std::max(100000ULL, (unsigned long long)(rate * (double)plan.hist_in));
   if (progress) {
@@ -217,9 +194,9 @@ void choose_fast_preset(const ScanPlan& plan, unsigned long long total, hipStrea
   mcgpu_ctx* const ctx = plan.ctxs[0];
   const int p = plan.first + (plan.count() > 0 ? plan.sim[0] : 0);
   DeviceBuffer tally;
-  HIP_OK(hipSetDevice(plan.devs[0]));
-  HIP_OK(hipMalloc(tally.make(plan.devs[0]), plan.words * 8));
-  HIP_OK(hipMemsetAsync(tally, 0, plan.words * 8, stream));
+  HIP_TRY(hipSetDevice(plan.devs[0]));
+  HIP_TRY(hipMalloc(tally.make(plan.devs[0]), plan.words * 8));
+  HIP_TRY(hipMemsetAsync(tally, 0, plan.words * 8, stream));
   int best = 0;
   float best_ms = 1e30f;
   for (int c = 0; c < 3; ++c) {
@@ -233,14 +210,14 @@ void choose_fast_preset(const ScanPlan& plan, unsigned long long total, hipStrea
     if (fastest < best_ms) { best_ms = fastest; best = c; }
   }
   for (mcgpu_ctx* c : plan.ctxs) ABI_OK(mcgpu_set_fast_schedule(c, presets[best][0], presets[best][1], presets[best][2], presets[best][3], presets[best][4]));
-  HIP_OK(hipSetDevice(plan.devs[0]));
+  HIP_TRY(hipSetDevice(plan.devs[0]));
   ABI_OK(mcgpu_dose_clear(ctx));
   if (progress) {
     printf("       FAST batching preset %d of 3 (thresholds %d/%d/%d, %d, %d)\n", best + 1, presets[best][0], presets[best][1], presets[best][2],
            presets[best][3], presets[best][4]);
     fflush(stdout);
   }
-  HIP_OK(hipStreamSynchronize(stream));
+  HIP_TRY(hipStreamSynchronize(stream));
 }
 
 // f(0), f(1), f(2) side by side (page-cache work on three different files): 0, or the code of the first that failed with its
@@ -254,7 +231,7 @@ int side_by_side(const F& f) {
   one(0);
   for (auto& t : side) t.join();
   for (int k = 0; k < 3; ++k)
-    if (rc[k] != 0) { mcgpu_set_last_error_(err[k].c_str()); return rc[k]; }
+    if (rc[k] != 0) return mcgpu::set_error(rc[k], err[k]);
   return 0;
 }
 
@@ -286,11 +263,11 @@ struct OutputStacks {
   void finish(const ScanPlan& plan, const mcgpu_scan_options* opt, float repl[3]) {
     mcgpu_stack* st[3] = {stack[0], stack[1], stack[2]};
     stack[0] = stack[1] = stack[2] = nullptr;
-    if (const int rc = side_by_side([&](int k) { return mcgpu_stack_finish(st[k], 1, &repl[k]); })) throw ScanError{rc, mcgpu_last_error()};
+    if (const int rc = side_by_side([&](int k) { return mcgpu_stack_finish(st[k], 1, &repl[k]); })) throw Error(rc, mcgpu_last_error());
     if (variance[0]) {  // a variance of zero is a value: no replacement
       mcgpu_stack* sv[3] = {variance[0], variance[1], variance[2]};
       variance[0] = variance[1] = variance[2] = nullptr;
-      if (const int rc = side_by_side([&](int k) { return mcgpu_stack_finish(sv[k], 0, nullptr); })) throw ScanError{rc, mcgpu_last_error()};
+      if (const int rc = side_by_side([&](int k) { return mcgpu_stack_finish(sv[k], 0, nullptr); })) throw Error(rc, mcgpu_last_error());
     }
     if (opt->air_stack)
       ABI_OK(mcgpu_normalize_stack((plan.folder + "/projections_total.mha").c_str(), opt->air_stack, opt->air_sigma_y, opt->air_sigma_x,
@@ -350,7 +327,7 @@ struct Output {
     const int handed = j - std::min(1, n_ascii - 1);
     std::unique_lock<std::mutex> lk(mu);
     cv.wait(lk, [&] { return (written >= handed && !ascii_busy[j % n_ascii]) || aborted; });
-    if (aborted) throw ScanError{-3, error};
+    if (aborted) throw Error(-3, error);
   }
   void publish(int j, const Projection& pr) {
     std::lock_guard<std::mutex> lk(mu);
@@ -363,7 +340,7 @@ struct Output {
     writer.join();
     stop(ascii_quit);
     std::lock_guard<std::mutex> lk(mu);
-    if (aborted) throw ScanError{-3, error};
+    if (aborted) throw Error(-3, error);
   }
   void abort() { stop(aborted); }  // error path: the threads stop where they are
   void stop(bool& flag) {
@@ -504,35 +481,35 @@ struct HistoryScan {
     mailboxes.assign(shared_bytes * (size_t)(use_rccl ? n : 1), 0);
     for (int g = 0; g < n; ++g) {
       Lane& l = lanes[g];
-      HIP_OK(hipSetDevice(l.dev));
-      HIP_OK(hipStreamCreate(l.stream.make(l.dev)));
+      HIP_TRY(hipSetDevice(l.dev));
+      HIP_TRY(hipStreamCreate(l.stream.make(l.dev)));
       if (!use_rccl) {
         ABI_OK(mcgpu_exchange_create(l.dev, g, n, plan.tally_words(), policy, mailboxes.data(), &l.x));
         continue;
       }
       // every device keeps its double-buffered tally in an exchange end of its own (a world of one: begin / submit / collect stay local)
       ABI_OK(mcgpu_exchange_create(l.dev, 0, 1, plan.tally_words(), MCGPU_EXCHANGE_LOCAL, mailboxes.data() + (size_t)g * shared_bytes, &l.x));
-      HIP_OK(hipStreamCreateWithFlags(l.reduce.make(l.dev), hipStreamNonBlocking));
+      HIP_TRY(hipStreamCreateWithFlags(l.reduce.make(l.dev), hipStreamNonBlocking));
       for (int b = 0; b < 2; ++b) {
-        HIP_OK(hipEventCreateWithFlags(l.tracked[b].make(l.dev), hipEventDisableTiming));
-        HIP_OK(hipEventCreateWithFlags(l.reduced[b].make(l.dev), hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(l.tracked[b].make(l.dev), hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(l.reduced[b].make(l.dev), hipEventDisableTiming));
       }
     }
     if (use_rccl) {
-      if (mcgpu_rccl_create(plan.devs.data(), n, &rccl) != 0) throw ScanError{kRcclUnavailable, mcgpu_last_error()};
+      if (mcgpu_rccl_create(plan.devs.data(), n, &rccl) != 0) throw Error(kRcclUnavailable, mcgpu_last_error());
       return;
     }
     try {
       // peer access between every pair of devices, and one small copy-engine transfer into every peer's landing buffer: a node
       // on which either fails is reported with kExchangeUnavailable BEFORE anything has been simulated or written, and
       // mcgpu_run_scan_multi then shards the scan by projection instead (same output bytes, nothing crosses between devices)
-      if (n > 1 && knob_set("MCGPU_EXCHANGE_FAIL_PROBE")) throw ScanError{-1, "!!ERROR!! tally exchange: probe failure requested (MCGPU_EXCHANGE_FAIL_PROBE)"};  // test hook
+      if (n > 1 && knob_set("MCGPU_EXCHANGE_FAIL_PROBE")) throw Error(-1, "!!ERROR!! tally exchange: probe failure requested (MCGPU_EXCHANGE_FAIL_PROBE)");  // test hook
       for (int g = 0; g < n; ++g)
         for (int h = 0; h < n; ++h)
           if (g != h) ABI_OK(mcgpu_exchange_connect_local(lanes[g].x, lanes[h].x));
       for (Lane& l : lanes) ABI_OK(mcgpu_exchange_probe(l.x));
-    } catch (const ScanError& e) {
-      throw ScanError{kExchangeUnavailable, e.msg};
+    } catch (const Error& e) {
+      throw Error(kExchangeUnavailable, e.what());
     }
   }
 
@@ -541,24 +518,24 @@ struct HistoryScan {
     for (int g = 0; g < n; ++g) {
       if (g > 0 && !(policy & MCGPU_EXCHANGE_ROTATE)) break;
       Lane& l = lanes[g];
-      HIP_OK(hipSetDevice(l.dev));
-      HIP_OK(hipStreamCreateWithFlags(l.copy.make(l.dev), hipStreamNonBlocking));
+      HIP_TRY(hipSetDevice(l.dev));
+      HIP_TRY(hipStreamCreateWithFlags(l.copy.make(l.dev), hipStreamNonBlocking));
       for (int b = 0; b < 2; ++b) {
-        HIP_OK(hipEventCreateWithFlags(l.finalized[b].make(l.dev), hipEventDisableTiming));
-        HIP_OK(hipMalloc(l.planes_dev[b].make(l.dev), plan.planes() * plan.plane * 4));
+        HIP_TRY(hipEventCreateWithFlags(l.finalized[b].make(l.dev), hipEventDisableTiming));
+        HIP_TRY(hipMalloc(l.planes_dev[b].make(l.dev), plan.planes() * plan.plane * 4));
         // the writer thread reads non-coherent pinned memory after waiting on this event: that needs a SYSTEM-scope release,
         // which a default event does not promise (device scope only)
-        HIP_OK(hipEventCreateWithFlags(l.done[b].make(l.dev), hipEventDisableTiming | hipEventReleaseToSystem));
+        HIP_TRY(hipEventCreateWithFlags(l.done[b].make(l.dev), hipEventDisableTiming | hipEventReleaseToSystem));
       }
     }
     // non-coherent (CPU-cacheable) pinned memory: the writer thread reads every byte (ordering: see the event above); portable:
     // it is filled from whichever device owns the projection
     const unsigned int pinned_flags = (knob_set("MCGPU_PINNED_COHERENT") ? hipHostMallocDefault : hipHostMallocNonCoherent) | hipHostMallocPortable;
     const int dev0 = lanes[0].dev;
-    HIP_OK(hipSetDevice(dev0));
+    HIP_TRY(hipSetDevice(dev0));
     for (int b = 0; b < 2; ++b) {
-      HIP_OK(hipHostMalloc(planes_host[b].make(dev0), plan.planes() * plan.plane * 4, pinned_flags));
-      if (opt->write_ascii && out.ascii_on_host) HIP_OK(hipHostMalloc(image_host[b].make(dev0), plan.words * 8, pinned_flags));
+      HIP_TRY(hipHostMalloc(planes_host[b].make(dev0), plan.planes() * plan.plane * 4, pinned_flags));
+      if (opt->write_ascii && out.ascii_on_host) HIP_TRY(hipHostMalloc(image_host[b].make(dev0), plan.words * 8, pinned_flags));
     }
     if (opt->write_stacks && !opt->shared_stacks && plan.count() > 0) stacks.create(plan);
   }
@@ -572,16 +549,16 @@ struct HistoryScan {
   void track(int i, int seed) {
     const int b = i & 1, p = plan.first + plan.sim[i];
     for (Lane& l : lanes) {
-      HIP_OK(hipSetDevice(l.dev));
+      HIP_TRY(hipSetDevice(l.dev));
       void* tally = nullptr;
-      if (use_rccl && l.reduced_valid[b]) HIP_OK(hipStreamWaitEvent(l.stream, l.reduced[b], 0));  // begin() zeroes the buffer the collective of i - 2 read
+      if (use_rccl && l.reduced_valid[b]) HIP_TRY(hipStreamWaitEvent(l.stream, l.reduced[b], 0));  // begin() zeroes the buffer the collective of i - 2 read
       ABI_OK(mcgpu_exchange_begin(l.x, i, l.stream, &tally));
       void* const w2 = plan.variance ? (void*)((unsigned long long*)tally + plan.words) : nullptr;
       ABI_OK(mcgpu_launch_projection_w2(l.ctx, p, plan.mode, seed, l.lo, l.hi - l.lo, shape.hpt, tally, w2, l.stream));
       ABI_OK(mcgpu_exchange_submit(l.x, i, l.stream));
       if (use_rccl) {
         l.tally[b] = tally;
-        HIP_OK(hipEventRecord(l.tracked[b], l.stream));
+        HIP_TRY(hipEventRecord(l.tracked[b], l.stream));
       }
     }
   }
@@ -595,45 +572,45 @@ struct HistoryScan {
       // MC-GPU_v1.3.cu:1019), on the reduce streams: behind kernel j of each device, beside its kernel j + 1
       std::vector<void*> bufs((size_t)n), streams((size_t)n);
       for (int g = 0; g < n; ++g) {
-        HIP_OK(hipSetDevice(lanes[g].dev));
-        HIP_OK(hipStreamWaitEvent(lanes[g].reduce, lanes[g].tracked[b], 0));
+        HIP_TRY(hipSetDevice(lanes[g].dev));
+        HIP_TRY(hipStreamWaitEvent(lanes[g].reduce, lanes[g].tracked[b], 0));
         bufs[(size_t)g] = lanes[g].tally[b];
         streams[(size_t)g] = (void*)(hipStream_t)lanes[g].reduce;
       }
       ABI_OK(mcgpu_rccl_reduce_u64(rccl, bufs.data(), plan.tally_words(), o, streams.data()));
       for (Lane& l : lanes) {
-        HIP_OK(hipSetDevice(l.dev));
-        HIP_OK(hipEventRecord(l.reduced[b], l.reduce));
+        HIP_TRY(hipSetDevice(l.dev));
+        HIP_TRY(hipEventRecord(l.reduced[b], l.reduce));
         l.reduced_valid[b] = true;
       }
-      HIP_OK(hipSetDevice(lanes[o].dev));
-      HIP_OK(hipStreamWaitEvent(lanes[o].stream, lanes[o].reduced[b], 0));  // the owner's tracking stream goes on with the summed tally
+      HIP_TRY(hipSetDevice(lanes[o].dev));
+      HIP_TRY(hipStreamWaitEvent(lanes[o].stream, lanes[o].reduced[b], 0));  // the owner's tracking stream goes on with the summed tally
       for (int g = 0; g < n; ++g)
         if (g != o) { void* unused = nullptr; ABI_OK(mcgpu_exchange_collect(lanes[g].x, j, lanes[g].stream, &unused)); }  // bookkeeping of the local ends
     }
     Lane& l = lanes[o];
-    HIP_OK(hipSetDevice(l.dev));
+    HIP_TRY(hipSetDevice(l.dev));
     hipStream_t const so = l.stream;
     void* tally = nullptr;
     ABI_OK(mcgpu_exchange_collect(l.x, j, so, &tally));  // exchange: the landed tallies of the other devices, added in one pass
-    if (!tally) throw ScanError{-1, "!!ERROR!! mcgpu_run_scan: the owner of a projection got no tally"};
+    if (!tally) throw Error(-1, "!!ERROR!! mcgpu_run_scan: the owner of a projection got no tally");
     // the reference's ASCII file: its 63 MB of text are formatted on the device (ascii_device.hip) while the tally is there; the
     // writer thread downloads and writes them while the next projection is tracked
     if (opt->write_ascii) {
-      if (out.ascii_on_host) HIP_OK(hipMemcpyAsync(image_host[b], tally, plan.words * 8, hipMemcpyDeviceToHost, so));
+      if (out.ascii_on_host) HIP_TRY(hipMemcpyAsync(image_host[b], tally, plan.words * 8, hipMemcpyDeviceToHost, so));
       else ABI_OK(mcgpu_format_projection(l.ctx, tally, shape.total, j % out.n_ascii, so));
     }
     // planes_dev[b] was last downloaded two projections ago (by this device, if it owned that one)
-    if (l.done_valid[b]) HIP_OK(hipStreamWaitEvent(so, l.done[b], 0));
+    if (l.done_valid[b]) HIP_TRY(hipStreamWaitEvent(so, l.done[b], 0));
     ABI_OK(mcgpu_finalize_projection(l.ctx, tally, shape.total, plan.cx, l.planes_dev[b], 0, so));  // begin() zeroes the buffer for its next user
     if (plan.variance)
       ABI_OK(mcgpu_finalize_variance(l.ctx, tally, (unsigned long long*)tally + plan.words, shape.total, plan.cx, (float*)(void*)l.planes_dev[b] + 3 * plan.plane, 0, so));
     // the 9 MB of planes go to the host on a copy engine, beside the next tracking kernel (on the tracking stream the copy held
     // the next launch back by 0.17 ms per projection)
-    HIP_OK(hipEventRecord(l.finalized[b], so));
-    HIP_OK(hipStreamWaitEvent(l.copy, l.finalized[b], 0));
-    HIP_OK(hipMemcpyAsync(planes_host[b], l.planes_dev[b], plan.planes() * plan.plane * 4, hipMemcpyDeviceToHost, l.copy));
-    HIP_OK(hipEventRecord(l.done[b], l.copy));
+    HIP_TRY(hipEventRecord(l.finalized[b], so));
+    HIP_TRY(hipStreamWaitEvent(l.copy, l.finalized[b], 0));
+    HIP_TRY(hipMemcpyAsync(planes_host[b], l.planes_dev[b], plan.planes() * plan.plane * 4, hipMemcpyDeviceToHost, l.copy));
+    HIP_TRY(hipEventRecord(l.done[b], l.copy));
     l.done_valid[b] = true;
   }
 
@@ -652,7 +629,7 @@ struct HistoryScan {
 
   void run(mcgpu_scan_report* report) {
     connect();
-    HIP_OK(hipSetDevice(lanes[0].dev));
+    HIP_TRY(hipSetDevice(lanes[0].dev));
     unsigned long long H = opt->histories_per_projection ? opt->histories_per_projection : (unsigned long long)plan.hist_in;
     if (plan.by_time) H = budget_histories(plan, lanes[0].stream, n, false, opt->progress);  // calibrated on device 0
     shape = launch_shape(plan, H);
@@ -712,13 +689,10 @@ struct HistoryScan {
 };
 
 int run_scan_sharing_histories(mcgpu_ctx* const* ctxs, int n_ctx, const mcgpu_scan_options* opt, mcgpu_scan_report* report, bool use_rccl = false) {
-  try {
-    HistoryScan(ctxs, n_ctx, opt, use_rccl).run(report);
-    return 0;
-  } catch (const ScanError& e) {
-    mcgpu_set_last_error_(e.msg.c_str());
-    return e.code ? e.code : -1;
-  }
+  ABI_BEGIN  // the code chooses the caller's next route: nothing is thrown past here (this also runs on threads of its own)
+  HistoryScan(ctxs, n_ctx, opt, use_rccl).run(report);
+  return 0;
+  ABI_END
 }
 
 // Projection sharding (SURVEY.md 8e's fallback mode; the reference has no counterpart -- its ranks always share a projection,
@@ -727,9 +701,9 @@ int run_scan_sharing_histories(mcgpu_ctx* const* ctxs, int n_ctx, const mcgpu_sc
 // collective.  The MetaImage stacks are shared and filled by slice index; ASCII files are per projection anyway.  Every output
 // byte equals a one-device scan's (per-history streams / per-projection seeds do not depend on who simulates a projection).
 int run_scan_sharing_projections(mcgpu_ctx* const* ctxs, int n_ctx, const mcgpu_scan_options* opt, mcgpu_scan_report* report) {
-  try {
+  ABI_BEGIN
     const ScanPlan plan = plan_scan(ctxs, n_ctx, opt);
-    if (opt->projection_stride > 1) throw ScanError{-1, "!!ERROR!! mcgpu_run_scan_multi: MCGPU_SHARD_PROJECTIONS sets the projection stride itself"};
+    if (opt->projection_stride > 1) throw Error(-1, "!!ERROR!! mcgpu_run_scan_multi: MCGPU_SHARD_PROJECTIONS sets the projection stride itself");
     const int count = plan.count();
     // slice of every offset of the range: its ordinal among the simulated projections (the order a one-device scan appends in)
     std::vector<int> slice_of((size_t)plan.range, -1);
@@ -764,7 +738,7 @@ int run_scan_sharing_projections(mcgpu_ctx* const* ctxs, int n_ctx, const mcgpu_
     }
     for (auto& t : th) t.join();
     for (int g = 0; g < n_ctx; ++g)
-      if (rcs[(size_t)g] != 0) throw ScanError{rcs[(size_t)g], errs[(size_t)g]};
+      if (rcs[(size_t)g] != 0) throw Error(rcs[(size_t)g], errs[(size_t)g]);
     float repl[3] = {0.f, 0.f, 0.f};
     if (stacks.open()) stacks.finish(plan, opt, repl);
     if (report) {
@@ -786,30 +760,19 @@ int run_scan_sharing_projections(mcgpu_ctx* const* ctxs, int n_ctx, const mcgpu_
       for (int k = 0; k < 3; ++k) report->zero_replacement[k] = repl[k];
     }
     return 0;
-  } catch (const ScanError& e) {
-    mcgpu_set_last_error_(e.msg.c_str());
-    return e.code ? e.code : -1;
-  }
+  ABI_END
 }
 
-}  // namespace
+int refuse(const char* message) { return mcgpu::set_error(-1, message); }
 
-namespace {
-int refuse(const char* message) { mcgpu_set_last_error_(message); return -1; }
 }  // namespace
 
 // Both entry points; `multi`: through mcgpu_run_scan_multi
 static int run_scan_entry(mcgpu_ctx* const* ctxs, int n_ctx, const mcgpu_scan_options* caller_opt, mcgpu_scan_report* report, bool multi) {
-  if (!ctxs || n_ctx < 1 || !caller_opt || !ctxs[0]) { mcgpu_set_last_error_("!!ERROR!! mcgpu_run_scan: null argument"); return -1; }
-  // a caller built against an older header passes a shorter struct: what it does not have reads as zero
-  if (caller_opt->struct_size < sizeof(unsigned int) + sizeof(int)) {
-    mcgpu_set_last_error_("!!ERROR!! mcgpu_run_scan: set mcgpu_scan_options.struct_size = sizeof(mcgpu_scan_options)");
-    return -1;
-  }
+  ABI_BEGIN
+  if (!ctxs || n_ctx < 1 || !caller_opt || !ctxs[0]) return refuse("!!ERROR!! mcgpu_run_scan: null argument");
   mcgpu_scan_options local;
-  memset(&local, 0, sizeof local);
-  memcpy(&local, caller_opt, std::min<size_t>(caller_opt->struct_size, sizeof local));
-  local.struct_size = (unsigned int)sizeof local;
+  mcgpu::read_options("mcgpu_run_scan", "mcgpu_scan_options", caller_opt, local);
   const mcgpu_scan_options* opt = &local;
   // the variance stacks: an output of the one-device scan's own stacks (4-D and multi-device variance are not built yet); an unknown
   // mode is still reported first, by plan_scan
@@ -819,7 +782,7 @@ static int run_scan_entry(mcgpu_ctx* const* ctxs, int n_ctx, const mcgpu_scan_op
     if (opt->shared_stacks) return refuse("!!ERROR!! mcgpu_run_scan: write_variance cannot be combined with shared_stacks");
   }
   for (int g = 0; g < n_ctx; ++g)
-    if (!ctxs[g]) { mcgpu_set_last_error_("!!ERROR!! mcgpu_run_scan: null context"); return -1; }
+    if (!ctxs[g]) return refuse("!!ERROR!! mcgpu_run_scan: null context");
   if (n_ctx > 1 && opt->shard == MCGPU_SHARD_PROJECTIONS) return run_scan_sharing_projections(ctxs, n_ctx, opt, report);
   // Routes of the per-projection tally sum between the devices (each is tried in its set-up phase, before anything is simulated or
   // written; every route gives the same output bytes):
@@ -861,6 +824,7 @@ static int run_scan_entry(mcgpu_ctx* const* ctxs, int n_ctx, const mcgpu_scan_op
   }
   say("The RCCL reduction that was asked for is not available: every device simulates whole projections instead");
   return run_scan_sharing_projections(ctxs, n_ctx, opt, report);
+  ABI_END
 }
 
 extern "C" int mcgpu_run_scan_multi(mcgpu_ctx* const* ctxs, int n_ctx, const mcgpu_scan_options* options, mcgpu_scan_report* report) {

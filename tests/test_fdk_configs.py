@@ -386,3 +386,60 @@ def test_old_header_reads_pad_as_zero(engine, monkeypatch):
     assert np.abs(one - zero).max() > 1e-3 * np.abs(zero).max()
     vol, _ = recon.fdk(proj, c.geo, (c.du, c.dv), (c.u0, c.v0), c.dim, c.spacing, None, c.hann, c.hann_y, pad=0.0)
     assert vol.tobytes() == zero.tobytes()
+
+
+# ---------------------------------------------------------------------------------------------------------------- the C ABI's refusals
+class _Tiny:
+    """mcgpu_fdk_reconstruct through ctypes on the smallest valid problem (one projection, 2 x 2 pixels, one voxel); keyword
+    arguments replace fields of mcgpu_fdk_options."""
+
+    def __init__(self):
+        self.lib = cases.pkg.engine.load_library()
+        self.lib.mcgpu_fdk_reconstruct.argtypes = [C.POINTER(recon._FdkOptions), C.c_void_p, C.c_void_p, C.POINTER(recon._FdkReport)]
+        self.lib.mcgpu_fdk_reconstruct.restype = C.c_int
+        self.angle = np.array([30.0])
+        self.proj = np.array([[[1.0, 2.0], [3.0, 4.0]]], np.float32)
+
+    def options(self, **fields):
+        o = recon._FdkOptions(C.sizeof(recon._FdkOptions), 1, 2, 2, 4.0, 4.0, -2.0, -2.0, 1000.0, 1500.0, self.angle.ctypes.data_as(C.POINTER(C.c_double)),
+                              None, None, 1, 1, 1, 1.0, 1.0, 1.0, *(float("nan"),) * 3, 0.0, 0.0, None, 0, 0, 0.0)
+        for k, v in fields.items():
+            setattr(o, k, v)
+        return o
+
+    def __call__(self, o, projections=True, volume=True):
+        vol = np.full((1, 1, 1), -1.0, np.float32)
+        rc = self.lib.mcgpu_fdk_reconstruct(C.byref(o) if o is not None else None, self.proj.ctypes.data if projections else None,
+                                            vol.ctypes.data if volume else None, None)
+        return rc, vol, self.lib.mcgpu_last_error().decode(errors="replace")
+
+
+_SET_SIZE = "!!ERROR!! mcgpu_fdk_reconstruct: set mcgpu_fdk_options.struct_size = sizeof(mcgpu_fdk_options)"
+_BAD = "!!ERROR!! mcgpu_fdk_reconstruct: bad argument"
+
+
+@pytest.mark.parametrize("what, message", [("options", _SET_SIZE), ("struct_size", _SET_SIZE), ("projections", _BAD), ("volume", _BAD), ("n_proj", _BAD),
+                                           ("nu", _BAD), ("du", _BAD), ("gantry_deg", _BAD)])
+def test_abi_refuses_before_any_hip_call(engine, what, message):
+    """-1 and the message, with the volume untouched; runs without a device, so nothing of HIP was asked."""
+    call = _Tiny()
+    over = {"struct_size": dict(struct_size=0), "n_proj": dict(n_proj=0), "nu": dict(nu=1), "du": dict(du=0.0),
+            "gantry_deg": dict(gantry_deg=C.POINTER(C.c_double)())}.get(what, {})
+    rc, vol, msg = call(None if what == "options" else call.options(**over), projections=what != "projections", volume=what != "volume")
+    assert rc == -1 and msg == message and np.all(vol == -1.0)
+
+
+def test_abi_a_device_that_does_not_exist_is_an_error_return(engine):
+    """Device 9999: the runtime's refusal comes back as -1 with the failing call in the message (no GPU is needed to be refused)."""
+    call = _Tiny()
+    rc, vol, msg = call(call.options(device=9999))
+    assert rc == -1 and "!!HIP ERROR!! hipSetDevice" in msg and np.all(vol == -1.0)
+
+
+@pytest.mark.gpu
+def test_abi_a_valid_call_follows_a_refused_device(engine):
+    call = _Tiny()
+    assert call(call.options(device=9999))[0] == -1
+    rc, vol, msg = call(call.options())
+    assert rc == 0, msg
+    assert np.isfinite(vol).all() and vol[0, 0, 0] > 0

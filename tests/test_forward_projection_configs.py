@@ -581,3 +581,27 @@ def test_abi_context_refuses_another_volume_size(engine, tmp_path):
         rc, out, msg = call.context(ctx, call.options(nx=23, ny=13, nz=18, sx=0.0, sy=0.0, sz=0.0))
         assert rc == 0, msg
         assert np.isfinite(out).all() and (out > 0).mean() > 0.1
+
+
+def _tiny_call(device):
+    """mcgpu_forward_project on the smallest valid problem: one projection of 2 x 2 pixels through one voxel of 5 mm."""
+    call = _Call()
+    angle, vol, out = np.array([30.0]), np.ones((1, 1, 1), np.float32), np.full((1, 2, 2), -1.0, np.float32)
+    o = fp._FpOptions(C.sizeof(fp._FpOptions), 1, 2, 2, 4.0, 4.0, -2.0, -2.0, SID, SDD, angle.ctypes.data_as(C.POINTER(C.c_double)), None, None,
+                      1, 1, 1, 5.0, 5.0, 5.0, *(float("nan"),) * 3, device)
+    rc = call.lib.mcgpu_forward_project(C.byref(o), vol.ctypes.data, out.ctypes.data, None)
+    return rc, out, call.lib.mcgpu_last_error().decode(errors="replace")
+
+
+def test_abi_a_device_that_does_not_exist_is_an_error_return(engine):
+    """Device 9999: the runtime's refusal comes back as -1 with the failing call in the message (no GPU is needed to be refused)."""
+    rc, out, msg = _tiny_call(9999)
+    assert rc == -1 and "!!HIP ERROR!! hipSetDevice" in msg and np.all(out == -1.0)
+
+
+@pytest.mark.gpu
+def test_abi_a_valid_call_follows_a_refused_device(engine):
+    assert _tiny_call(9999)[0] == -1
+    rc, out, msg = _tiny_call(0)
+    assert rc == 0, msg
+    assert np.isfinite(out).all() and (out > 0).all()  # every ray of the 2 x 2 detector passes through the voxel

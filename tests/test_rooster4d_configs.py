@@ -427,3 +427,47 @@ def test_reconstruct_4d_takes_the_pixel_origin_from_the_stack(engine, tmp_path):
     default, _ = recon.rooster4d(p, geo, (PIX, PIX), None, ph, dim, spacing, **kw)
     assert vol.tobytes() == direct.tobytes()
     assert vol.tobytes() != default.tobytes()
+
+
+# ---------------------------------------------------------------------------------------------------------------- the C ABI
+def _tiny_call(struct_size=None, **over):
+    """mcgpu_rooster4d_reconstruct on the smallest valid problem (one projection of 2 x 2 pixels, one voxel, one frame, one CG step);
+    -> (rc, volume, residuals, message).  struct_size: what the caller says its struct holds; the memory holds every field."""
+    geo = recon.CircularGeometry(SID, SDD)
+    geo.add_projection(30.0, 0.0, 0.0)
+    lib, o, keep = recon._rooster_call(1, 2, 2, geo, (PIX, PIX), None, [0.0], (1, 1, 1), (4.0, 4.0, 4.0), None, 1, 1, 1, 0, 0.0, 0.0, None, True, 0)
+    for k, v in over.items():
+        setattr(o, k, v)
+    if struct_size is not None:
+        o.struct_size = struct_size
+    p, vol = np.full((1, 2, 2), 3.0, np.float32), np.full((1, 1, 1, 1), -1.0, np.float32)
+    rc = lib.mcgpu_rooster4d_reconstruct(C.byref(o), p.ctypes.data, vol.ctypes.data, None)
+    return rc, vol, keep["residuals"].copy(), lib.mcgpu_last_error().decode(errors="replace")
+
+
+def test_abi_a_device_that_does_not_exist_is_an_error_return(engine):
+    """Device 9999: the runtime's refusal comes back as -1 with the failing call in the message (no GPU is needed to be refused)."""
+    rc, vol, _, msg = _tiny_call(device=9999)
+    assert rc == -1 and "!!HIP ERROR!! hipSetDevice" in msg and np.all(vol == -1.0)
+
+
+@pytest.mark.gpu
+def test_abi_a_valid_call_follows_a_refused_device(engine):
+    assert _tiny_call(device=9999)[0] == -1
+    rc, vol, res, msg = _tiny_call()
+    assert rc == 0, msg
+    assert np.isfinite(vol).all() and vol[0, 0, 0, 0] > 0 and res[0] > 0
+
+
+@pytest.mark.gpu
+def test_abi_old_header_reads_residuals_as_null(engine):
+    """A caller built against a header that ends before `residuals` passes a shorter struct: the pointer that lies beyond reads as
+    NULL, so nothing is written through it and the volume is bit for bit the one of the full struct with residuals = NULL."""
+    full, cut = C.sizeof(recon._RoosterOptions), recon._RoosterOptions.residuals.offset
+    assert cut + 8 == full
+    rc0, want, _, msg = _tiny_call(residuals=C.POINTER(C.c_double)())
+    assert rc0 == 0, msg
+    rc1, got, res, msg = _tiny_call(struct_size=cut)
+    assert rc1 == 0, msg
+    assert got.tobytes() == want.tobytes() and (res == 0.0).all()
+    assert (_tiny_call()[2] != 0.0).any()  # the full struct does write them
