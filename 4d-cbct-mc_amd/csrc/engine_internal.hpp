@@ -40,6 +40,11 @@ int occupancy_track_fast_w2(const TrackArgs& args);
 hipError_t launch_track_fast64_w2(const TrackArgs& args, int blocks, hipStream_t stream);
 int occupancy_track_fast64_w2(const TrackArgs& args);
 hipError_t launch_kat_fast64(int n, const unsigned int* u, const double* a, const double* b, const double* c, const float* dir, double* out, hipStream_t stream);
+// kat_scatter.inc, once per arithmetic (track_fast.hip / track_fast64.hip)
+hipError_t launch_kat_scatter_fast(const TrackArgs& args, int kind, int n, unsigned int seed, unsigned int stream_key, const float* in4,
+                                   const unsigned long long* in_u64, const int* mc, float* out4, unsigned int* out_u4, hipStream_t stream);
+hipError_t launch_kat_scatter_fast64(const TrackArgs& args, int kind, int n, unsigned int seed, unsigned int stream_key, const float* in4,
+                                     const unsigned long long* in_u64, const int* mc, float* out4, unsigned int* out_u4, hipStream_t stream);
 #if defined(MC_WITH_STATS) && MC_WITH_STATS
 hipError_t launch_track_stats(const TrackArgs& args, int blocks, hipStream_t stream);  // diagnostic library only (track_stats.o)
 #endif

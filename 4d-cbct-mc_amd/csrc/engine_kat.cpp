@@ -86,6 +86,44 @@ int mcgpu_kat_fast64(mcgpu_ctx* ctx, int n, const uint32_t* u, const double* a, 
   ABI_END
 }
 
+int mcgpu_kat_scatter(mcgpu_ctx* ctx, int mode, int kind, int n, unsigned int seed, unsigned int stream_key, const float* in4,
+                      const unsigned long long* in_u64, const int* material, float* out4, uint32_t* out_u4) {
+  ABI_BEGIN
+  require(ctx && ctx->has_device && in4 && in_u64 && out4 && out_u4 && n > 0 && n <= (1 << 24), -1, "!!ERROR!! mcgpu_kat_scatter: bad argument");
+  require(mode == MCGPU_MODE_FAST || mode == MCGPU_MODE_FAST_F64, -1, "!!ERROR!! mcgpu_kat_scatter: the hook exists in the FAST arithmetics only");
+  require(kind == MCGPU_KAT_ROTATE || kind == MCGPU_KAT_RAYLEIGH || kind == MCGPU_KAT_COMPTON, -1, "!!ERROR!! mcgpu_kat_scatter: unknown kind");
+  require(kind != MCGPU_KAT_ROTATE || mode == MCGPU_MODE_FAST, -1, "!!ERROR!! mcgpu_kat_scatter: the rotation of MCGPU_MODE_FAST_F64 is mcgpu_kat_fast64's");
+  const DeviceModel& D = ctx->dev;
+  std::vector<int> mc((size_t)n, 0);
+  if (kind != MCGPU_KAT_ROTATE) {
+    // what the kernel indexes its tables with is checked here: a material the model holds, an energy inside the tables
+    require(material != nullptr, -1, "!!ERROR!! mcgpu_kat_scatter: no materials");
+    const float e0 = ctx->host.mat.e0, ide = ctx->host.mat.ide, top = (float)(ctx->host.mat.num_values - 1);
+    for (int i = 0; i < n; ++i) {
+      require(material[i] >= 0 && material[i] < kMaxMaterials && D.compact_of[material[i]] >= 0, -2,
+              "!!ERROR!! mcgpu_kat_scatter: a material that no voxel of the context's geometry holds");
+      mc[(size_t)i] = D.compact_of[material[i]];
+      const float t = (in4[4 * (size_t)i + 3] - e0) * ide;
+      require(t >= 0.0f && t < top, -2, "!!ERROR!! mcgpu_kat_scatter: an energy outside the cross-section tables");
+    }
+  }
+  HIP_TRY(hipSetDevice(D.device_id));
+  TrackArgs A = make_args(*ctx, 0);
+  A.dose_flags = 0;
+  CallDevice dev;
+  const size_t n16 = (size_t)n * 16;
+  float* d_in = dev.upload(in4, (size_t)n * 4);
+  const unsigned long long* d_u64 = dev.upload(in_u64, (size_t)n);
+  const int* d_mc = dev.upload(mc.data(), (size_t)n);
+  float* d_out = dev.alloc_zeroed<float>(n16);
+  unsigned int* d_out_u = dev.alloc_zeroed<unsigned int>(n16);
+  HIP_TRY((mode == MCGPU_MODE_FAST_F64 ? launch_kat_scatter_fast64 : launch_kat_scatter_fast)(A, kind, n, seed, stream_key, d_in, d_u64, d_mc, d_out, d_out_u, nullptr));
+  HIP_TRY(hipMemcpy(out4, d_out, n16, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_u4, d_out_u, n16, hipMemcpyDeviceToHost));
+  return 0;
+  ABI_END
+}
+
 int mcgpu_kat_f32(mcgpu_ctx* ctx, int op, int n, const float* a, const float* b, float* inout) {
   ABI_BEGIN
   require(ctx && ctx->has_device && a && b && inout && n > 0 && op >= 0 && op <= 4, -1, "!!ERROR!! mcgpu_kat_f32: bad argument");

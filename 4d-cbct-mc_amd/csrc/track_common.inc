@@ -367,7 +367,12 @@ __device__ __forceinline__ void rotate_dir(Particle& P, float omc, Rng& rng) {
   dxy = P.u * P.u + P.v * P.v;
   const float st2 = fmaxf(omc * (2.0f - omc), 0.0f);
   // one square root serves both cases (the argument is selected, not the result: same bits, one transcendental fewer)
-  const bool tilted = dxy > 1.0e-12f;
+  // The reference's switch (K.cu:1127).  A float keeps the relative precision of u and v down to its smallest normal number, and
+  // 1 / dxy <= 1e28 stays in range: the tilted formulas are as exact for a direction 1e-14 off the z axis as for any other.  With
+  // the switch at 1e-12, where it first sat, a direction within 1e-6 of the axis was turned about the x axis instead of about its own
+  // transverse axes -- the azimuth of the result off by the azimuth of (u, v), harmless to every tally (the azimuth is uniform) and
+  // wrong against the rotation this function states (tests/test_scatter_gpu.py: test_rotate_f32_against_float64).
+  const bool tilted = dxy > 1.0e-28f;
   const float sdt = __builtin_amdgcn_sqrtf(tilted ? st2 * __builtin_amdgcn_rcpf(dxy) : st2);
   if (tilted) {
     const float xin = P.u, yin = P.v;
@@ -437,7 +442,16 @@ __device__ bool rayleigh_trial(const TrackArgs& A, float energy, int mc, float p
   }
   const GLOBAL_AS float* pco = as_global(COLD(A)->pco) + mc * kRayleighPoints;
   const GLOBAL_AS float* xco = as_global(COLD(A)->xco) + mc * kRayleighPoints;
-  const float ru = rng_f(rng) * pmax_current;
+  // The deviate of the table look-up is the whole 32-bit word, (w + 1/2) 2^-32 -- the value rng_d gives the double build -- carried as
+  // two floats: hi = the 24 upper bits (exact), lo = the 8 lower ones and the half (exact).  GRAa inverts a distribution whose tail is
+  // steep at the top of the tables: around ru = 0.9998 in water at 124.5 keV an interval of the table 1.1e-4 wide in ru spans 0.19 in
+  // omc, so the 2^-24 grid of rng_f was a grid of 1e-4 .. 3.5e-4 in omc there, and rounding the product ru another 1e-4
+  // (tests/test_scatter_gpu.py: test_rayleigh_replay, test_fast_and_fast64_take_the_same_decisions).  The search runs on the rounded
+  // float ru as before; ru - p0 is then taken from the unrounded products -- one fused multiply-add and one multiply-add -- and where
+  // that puts the point outside the interval the search chose (a table point within 2^-24 of ru) the interval moves with it.
+  const unsigned int word = rng_u32(rng);
+  const float hi = (float)(word >> 8) * 5.9604644775390625e-08f, lo = ((float)(word & 255u) + 0.5f) * 2.3283064365386963e-10f;
+  const float ru = fmaf((float)(word >> 8), 5.9604644775390625e-08f, 1.4901161193847656e-08f) * pmax_current;  // rng_f's value
   const int itn = (int)(ru * (kRayleighPoints - 1));
   int i = (int)as_global(COLD(A)->itl)[itn + mc * kRayleighPoints];
   int j = (int)as_global(COLD(A)->itu)[itn + mc * kRayleighPoints];
@@ -445,11 +459,13 @@ __device__ bool rayleigh_trial(const TrackArgs& A, float energy, int mc, float p
     const int k = (i + j) >> 1;
     if (ru > pco[k - 1]) i = k; else j = k;
   }
-  const int q = i - 1;
-  const float p0 = pco[q], rr = ru - p0;
+  int q = i - 1;
+  float p0 = pco[q], d = pco[q + 1] - p0;
+  float rr = fmaf(hi, pmax_current, -p0) + lo * pmax_current;
+  while (rr < 0.0f && q > 0) { --q; p0 = pco[q]; d = pco[q + 1] - p0; rr = fmaf(hi, pmax_current, -p0) + lo * pmax_current; }
+  while (rr > d && q < kRayleighPoints - 2) { ++q; p0 = pco[q]; d = pco[q + 1] - p0; rr = fmaf(hi, pmax_current, -p0) + lo * pmax_current; }
   float xx = xco[q];
   if (rr > 1e-16f) {
-    const float d = pco[q + 1] - p0;
     const float a = as_global(COLD(A)->aco)[q + mc * kRayleighPoints], b = as_global(COLD(A)->bco)[q + mc * kRayleighPoints];
     xx = xx + MC_DIV((a + 1.0f + b) * d * rr, d * d + (a * d + b * rr) * rr) * (xco[q + 1] - xx);
   }

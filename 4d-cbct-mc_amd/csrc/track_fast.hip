@@ -53,3 +53,5 @@ hipError_t launch_kat_streams_fast(int generator, unsigned int seed, unsigned in
   return hipGetLastError();
 }
 }  // namespace mcgpu
+
+#include "kat_scatter.inc"  // mcgpu_kat_scatter: the production service bodies, one event per thread

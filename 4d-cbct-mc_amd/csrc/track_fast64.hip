@@ -34,3 +34,5 @@ hipError_t launch_kat_fast64(int n, const unsigned int* u, const double* a, cons
   return hipGetLastError();
 }
 }  // namespace mcgpu
+
+#include "kat_scatter.inc"  // mcgpu_kat_scatter: the production service bodies, one event per thread

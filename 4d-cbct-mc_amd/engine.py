@@ -30,7 +30,7 @@ ABI_SYMBOLS = (
     "mcgpu_stack_read", "mcgpu_normalize_stack", "mcgpu_run_scan", "mcgpu_run_scan_multi", "mcgpu_set_projection_angles", "mcgpu_set_geometry_arrays",
     "mcgpu_warp_volume", "mcgpu_warp_geometry", "mcgpu_map_image", "mcgpu_set_geometry_image",
     "mcgpu_correspondence_set", "mcgpu_correspondence_fit", "mcgpu_correspondence_predict", "mcgpu_warp_geometry_signal", "mcgpu_correspondence_clear",
-    "mcgpu_write_voxel_file", "mcgpu_write_voxel_binary", "mcgpu_kat_rng", "mcgpu_kat_rng_streams", "mcgpu_microbench", "mcgpu_kat_math", "mcgpu_kat_expf", "mcgpu_kat_f32", "mcgpu_kat_fast64", "mcgpu_kat_tile_records", "mcgpu_fdk_reconstruct", "mcgpu_forward_project", "mcgpu_forward_project_context", "mcgpu_rooster4d_reconstruct", "mcgpu_rooster4d_stage", "mcgpu_set_fast_schedule", "mcgpu_reload_env_knobs",
+    "mcgpu_write_voxel_file", "mcgpu_write_voxel_binary", "mcgpu_kat_rng", "mcgpu_kat_rng_streams", "mcgpu_microbench", "mcgpu_kat_math", "mcgpu_kat_expf", "mcgpu_kat_f32", "mcgpu_kat_fast64", "mcgpu_kat_scatter", "mcgpu_kat_tile_records", "mcgpu_fdk_reconstruct", "mcgpu_forward_project", "mcgpu_forward_project_context", "mcgpu_rooster4d_reconstruct", "mcgpu_rooster4d_stage", "mcgpu_set_fast_schedule", "mcgpu_reload_env_knobs",
     "mcgpu_exchange_shared_bytes", "mcgpu_exchange_card_bytes", "mcgpu_exchange_create", "mcgpu_exchange_card", "mcgpu_exchange_connect",
     "mcgpu_exchange_connect_local", "mcgpu_exchange_probe", "mcgpu_exchange_owner", "mcgpu_exchange_begin", "mcgpu_exchange_submit", "mcgpu_exchange_collect",
     "mcgpu_exchange_stats", "mcgpu_exchange_destroy", "mcgpu_copy_to_host",
@@ -187,6 +187,7 @@ def load_library(path: Optional[os.PathLike] = None):
     lib.mcgpu_kat_expf.argtypes = [vp, ci, vp, vp]
     lib.mcgpu_kat_f32.argtypes = [vp, ci, ci, vp, vp, vp]
     lib.mcgpu_kat_fast64.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
+    lib.mcgpu_kat_scatter.argtypes = [vp, ci, ci, ci, C.c_uint, C.c_uint, vp, vp, vp, vp, vp]
     lib.mcgpu_kat_tile_records.argtypes = [ci, vp, vp]
     if path is None:
         _lib = lib
@@ -932,6 +933,24 @@ class Context:
         out = np.zeros((u.size, 8), dtype=np.float64)
         _check(self.lib.mcgpu_kat_fast64(self.h, u.size, u.ctypes.data, a.ctypes.data, b.ctypes.data, c.ctypes.data, d.ctypes.data, out.ctypes.data))
         return out
+
+    def kat_scatter(self, mode, kind: str, directions, values, ids, materials=None, seed: int = 0, stream_key: int = 0):
+        """The FAST scattering samplers as the photon kernels run them (include/mcgpu_amd.h: mcgpu_kat_scatter), one event per item.
+        kind "rayleigh" / "compton": values = photon energies [eV], ids = history ids, materials = material numbers - 1;
+        kind "rotate" (mode "fast"): values = 1 - cos(theta), ids = the azimuth's 32-bit deviates.
+        Returns (energy float32[n], direction float32[n, 3], service calls, final phase, generator state uint32[n, 2])."""
+        d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+        n = d.shape[0]
+        in4 = np.empty((n, 4), dtype=np.float32)
+        in4[:, :3] = d
+        in4[:, 3] = np.broadcast_to(np.asarray(values, dtype=np.float32), (n,))
+        u64 = np.ascontiguousarray(np.broadcast_to(np.asarray(ids, dtype=np.uint64), (n,)))
+        mat = None if materials is None else np.ascontiguousarray(np.broadcast_to(np.asarray(materials, dtype=np.int32), (n,)))
+        out4, out_u4 = np.zeros((n, 4), dtype=np.float32), np.zeros((n, 4), dtype=np.uint32)
+        _check(self.lib.mcgpu_kat_scatter(self.h, _MODES[mode], {"rotate": 0, "rayleigh": 1, "compton": 2}[kind], n, int(seed), int(stream_key),
+                                          in4.ctypes.data, u64.ctypes.data, None if mat is None else mat.ctypes.data, out4.ctypes.data,
+                                          out_u4.ctypes.data))
+        return out4[:, 0].copy(), out4[:, 1:].copy(), out_u4[:, 0].copy(), out_u4[:, 1].copy(), out_u4[:, 2:].copy()
 
     def kat_f32(self, op: int, a, b=None, c=None):
         """Float operations of the COMPAT kernel (include/mcgpu_amd.h: mcgpu_kat_f32)."""

@@ -488,6 +488,21 @@ int mcgpu_kat_f32(mcgpu_ctx *ctx, int op, int n, const float *a, const float *b,
  * 2 pi (u[i] + 1/2) 2^-32; 1 / sqrt(a[i]); sqrt(a[i] / b[i]); cdt1 of MC-GPU_kernel_v1.3.cu:1329 at tau = (float)a[i], E = (float)b[i] 1e5;
  * the direction dir3[3 i ..] rotated by polar cosine c[i] and the azimuth of u[i] (rotate_double, :1103-1148). */
 int mcgpu_kat_fast64(mcgpu_ctx *ctx, int n, const uint32_t *u, const double *a, const double *b, const double *c, const float *dir3, double *out8);
+/* The scattering samplers of MCGPU_MODE_FAST / MCGPU_MODE_FAST_F64 as the photon kernels run them (csrc/kat_scatter.inc: the service
+ * bodies of csrc/track_pool.inc, one event per item), from the per-history stream of mcgpu_kat_rng_streams so that a test can replay
+ * every deviate.  in4[4 i ..] = {direction u, v, w, photon energy [eV]}, in_u64[i] = history id, material[i] = material number - 1 (one
+ * that the context's geometry holds); the stream is that of (id, seed, stream_key).
+ *   MCGPU_KAT_RAYLEIGH  Rayleigh events (GRAa, MC-GPU_kernel_v1.3.cu:1181-1246, one trial per service call)
+ *   MCGPU_KAT_COMPTON   Compton events (GCOa, :1287-1515, as the shell-first trials of csrc/track_common.inc)
+ *   MCGPU_KAT_ROTATE    MCGPU_MODE_FAST only: rotate_dir alone; in4[4 i + 3] = 1 - cos(theta), in_u64[i] = the 32-bit deviate of the
+ *                       azimuth (turn fraction: the float nearest to ((u >> 8) + 1/4) 2^-24), material ignored (may be NULL)
+ * out4[4 i ..] = {energy, direction u, v, w} after the event; out_u4[4 i ..] = {service calls, final phase (0 = in flight, 5 = below the
+ * tables' lowest energy: absorbed), generator state x, c}. */
+#define MCGPU_KAT_ROTATE 0
+#define MCGPU_KAT_RAYLEIGH 1
+#define MCGPU_KAT_COMPTON 2
+int mcgpu_kat_scatter(mcgpu_ctx *ctx, int mode, int kind, int n, unsigned int seed, unsigned int stream_key, const float *in4,
+                      const unsigned long long *in_u64, const int *material, float *out4, uint32_t *out_u4);
 /* The 16-byte record of a 4x4x4 tile of a u8-palette volume as the host and the device build it (csrc/device_model.hpp:
  * encode_tile_record; no reference counterpart -- the reference gathers the voxel itself, MC-GPU_kernel_v1.3.cu:262-266).  Host code
  * only, no context: indices[t * 64 + v] = palette index of voxel v = (iz & 3) 16 + (iy & 3) 4 + (ix & 3) of tile t, negative = padding

@@ -64,7 +64,7 @@ def streams_u32(ids, seed: int, projection: int, n_draws: int) -> np.ndarray:
 
 
 def to_float(u32) -> np.ndarray:
-    """rng_f: the 24 upper bits as k 2^-24 + 2^-26 in float32 (one fused multiply-add, exact in float32 for every k)."""
+    """rng_f: the 24 upper bits as k 2^-24 + 2^-26, one fused multiply-add rounded to float32 (exact below k = 2^22; above, the nearest float32)."""
     k = (np.asarray(u32, dtype=np.uint32) >> np.uint32(8)).astype(np.float64)
     return (k * 2.0 ** -24 + 2.0 ** -26).astype(np.float32)
 

@@ -537,6 +537,20 @@ float oracle_compton_s(const oracle_tables *T, float E, float cdt, int mat, int 
 }
 void oracle_gcoa(const oracle_tables *T, float *energy, double *costh, int mat, int *seed2, int math_mode)
 { i2 s = { seed2[0], seed2[1] }; uint64_t c = 0; gcoa(T, energy, costh, mat, &s, math_mode, &c); seed2[0] = s.x; seed2[1] = s.y; }
+/* n calls of oracle_gcoa / oracle_graa at one energy from ONE stream (seed2: in, and advanced on return): the batches behind the
+ * histograms of tests/golden/scatter_law.npz (oracle/gen_scatter_golden.py) */
+void oracle_gcoa_many(const oracle_tables *T, float energy, int mat, int *seed2, int math_mode, long n, float *energy_out, double *costh_out)
+{
+  i2 s = { seed2[0], seed2[1] }; uint64_t c = 0;
+  for (long k = 0; k < n; k++) { energy_out[k] = energy; gcoa(T, &energy_out[k], &costh_out[k], mat, &s, math_mode, &c); }
+  seed2[0] = s.x; seed2[1] = s.y;
+}
+void oracle_graa_many(const oracle_tables *T, float energy, int mat, int index, int *seed2, long n, double *costh_out)
+{
+  i2 s = { seed2[0], seed2[1] }; uint64_t c = 0;
+  for (long k = 0; k < n; k++) graa(T, energy, &costh_out[k], mat, T->pmax[(index + 1) * MAXMAT + mat], &s, &c);
+  seed2[0] = s.x; seed2[1] = s.y;
+}
 void oracle_source(const oracle_tables *T, int num_p, int *seed2, float *pos3, float *dir3, float *energy, int *absvox, int math_mode)
 {
   i2 s = { seed2[0], seed2[1] }; uint64_t c = 0; f3 p, d;

@@ -83,6 +83,8 @@ def oracle():
         lib.oracle_rotate.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int]
         lib.oracle_gcoa.argtypes = [C.POINTER(OracleTables), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
         lib.oracle_graa.argtypes = [C.POINTER(OracleTables), C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        lib.oracle_gcoa_many.argtypes = [C.POINTER(OracleTables), C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_void_p, C.c_void_p]
+        lib.oracle_graa_many.argtypes = [C.POINTER(OracleTables), C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_void_p]
         lib.oracle_source.argtypes = [C.POINTER(OracleTables), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_int]
         _oracle = lib
