@@ -27,6 +27,8 @@
 //   rayleigh  : xco,pco,aco,bco f32[128*nmat], itl,itu u8[128*nmat] (compact materials only)
 //   compton   : fco,uico,fj0 f32[40][nmat] (shell-major: lanes in different materials hit different LDS banks)
 #pragma once
+#include <hip/hip_runtime_api.h>
+
 #include <cstdint>
 
 #include "host_model.hpp"
@@ -264,5 +266,10 @@ struct TrackArgs {
   StageArgs stage;            // FAST: staging of the detector hits (tally_stage.hpp); region == null: direct atomics on `image`
   unsigned long long* w2;     // second tally beside `image`: sum of tally_w2_term(w) per word (tally_stage.hpp), null: off.  Last: every other argument keeps its offset
 };
+
+// The FAST kernels as the host sees them: one entry per translation unit that includes track_pool.inc, named by that unit's {MC_FAST_F64,
+// MC_TALLY_W2, MC_STATS} and defined at the tail of track_pool.inc (the product library's <0, 1, 1>: track_stats_absent.cpp).
+struct FastKernels { hipError_t (*launch)(const TrackArgs&, int blocks, hipStream_t); int (*occupancy)(const TrackArgs&); };
+template <int kDouble, int kW2, int kStats> const FastKernels& fast_kernels();  // no primary definition
 
 }  // namespace mcgpu

@@ -1,5 +1,5 @@
-// engine.cpp -- the C ABI (include/mcgpu_amd.h) of an engine context: creation, configuration, launches, projection output,
-// dose tallies, stacks.  Replaces the per-projection driver of main() (docker/mcgpu/MC-GPU_v1.3.cu:667-1056).  Compiled with hipcc.
+// engine.cpp -- the C ABI (include/mcgpu_amd.h) of an engine context: creation, configuration, projection output, dose tallies,
+// finalize, stacks (the tracking launch: engine_launch.cpp).  Compiled with hipcc.
 #include "engine_internal.hpp"
 
 using namespace mcgpu;
@@ -52,8 +52,6 @@ int mcgpu_clone(const mcgpu_ctx* src, int device_id, mcgpu_ctx** out) {
 
 void mcgpu_destroy(mcgpu_ctx* ctx) { delete ctx; }
 
-static bool stage_wanted(const DeviceModel& D);  // below, with the staged launch
-
 int mcgpu_config_i64(const mcgpu_ctx* ctx, const char* key, long long* value) {
   ABI_BEGIN
   require(ctx && key && value, -1, "!!ERROR!! mcgpu_config_i64: null argument");
@@ -97,30 +95,11 @@ int mcgpu_config_i64(const mcgpu_ctx* ctx, const char* key, long long* value) {
   else if (k == "correspondence_dims") *value = ctx->dev.corr_coef ? ctx->dev.corr_k : 0;  // K of the resident correspondence model, 0: none
   else if (k == "blocks_per_cu") *value = ctx->dev.resident_fast;
   else if (k == "lds_bytes_fast") *value = ctx->dev.lds.total;
-  else if (k == "tally_stage_bins") *value = stage_wanted(ctx->dev) ? (long long)ctx->dev.stage_bins : 0;  // 0: direct atomics
-  else if (k == "tally_stage_capacity") *value = ctx->dev.stage_plan.cap;  // of the last staged (sub-)launch
-  else if (k == "tally_stage_bytes") *value = (long long)ctx->dev.stage_region_bytes;
-  else if (k == "tally_stage_fallback_hits") {  // hits that took the direct atomic since the context was created; waits for the device
-    unsigned long long n = 0;
-    if (ctx->has_device && ctx->dev.stage_fallback) {
-      HIP_TRY(hipSetDevice(ctx->dev.device_id));
-      HIP_TRY(hipDeviceSynchronize());
-      HIP_TRY(hipMemcpy(&n, ctx->dev.stage_fallback, 8, hipMemcpyDeviceToHost));
-    }
-    *value = (long long)n;
-  }
-  else if (k == "tally_stage_staged_hits") {  // test support (downloads the counts table): records the last staged (sub-)launch stored (its hits = these + its share of the fallback hits)
-    unsigned long long n = 0;
-    const size_t words = (size_t)ctx->dev.stage_plan.workgroups * ctx->dev.stage_plan.n_bins;
-    if (ctx->has_device && ctx->dev.stage_counts && words != 0) {
-      std::vector<unsigned int> c(words);
-      HIP_TRY(hipSetDevice(ctx->dev.device_id));
-      HIP_TRY(hipDeviceSynchronize());
-      HIP_TRY(hipMemcpy(c.data(), ctx->dev.stage_counts, words * 4, hipMemcpyDeviceToHost));
-      for (unsigned int v : c) n += v;
-    }
-    *value = (long long)n;
-  }
+  else if (k == "tally_stage_bins") *value = ctx->dev.stage.wanted(ctx->dev, false) ? (long long)ctx->dev.stage.bins : 0;  // 0: direct atomics
+  else if (k == "tally_stage_capacity") *value = ctx->dev.stage.plan.cap;  // of the last staged (sub-)launch
+  else if (k == "tally_stage_bytes") *value = (long long)ctx->dev.stage.region_bytes;
+  else if (k == "tally_stage_fallback_hits") *value = (long long)ctx->dev.stage.fallback_hits(ctx->dev);  // since the context was created; waits for the device
+  else if (k == "tally_stage_staged_hits") *value = (long long)ctx->dev.stage.staged_hits(ctx->dev);  // test support: of the last staged (sub-)launch; waits for the device
   else if (k == "sigma_bracket_shift") *value = ctx->dev.sig_shift;
   else if (k == "lds_bytes_compat") *value = ctx->dev.lds.slots + 14 * kTrackBlockThreads * 4;  // tables + one parked history per lane (track_kernel.inc)
   else return set_error(-2, std::string("unknown integer key: ") + key);
@@ -199,236 +178,6 @@ int mcgpu_advance_seed(int batch_number, unsigned long long total_histories, int
   return ranecu_advance_seed(batch_number, total_histories, seed);
 }
 
-// Whether this model's FAST launches stage their detector hits (MCGPU_TALLY_STAGE: 1 / 0 force it, default -1 = the rule below).
-// Staging pays where the scattered tally atomics bind the launch, i.e. where most histories are detected: a small object in a large
-// volume of background, which the engine knows as the share of EXTERIOR bricks (the source's photons that miss the object region
-// reach the detector unattenuated).  Measured (profiles/tally_stage_ab.md): the Catphan in its 512^3 of air gains 2.9-3.1 %, the body-sized
-// CIRS and thorax phantoms lose 1.7-6 % to the fold and the longer tally service -- they sit below the threshold and keep the atomics.
-static bool stage_wanted(const DeviceModel& D) {
-  if (D.stage_cursor < 0 || D.knobs.tally_stage == 0) return false;
-  if (D.knobs.tally_stage > 0) return true;
-  return D.brick_count > 0 && 100LL * D.bricks_exterior >= (long long)kStageExteriorPercent * D.brick_count;
-}
-
-// Buffers and launch arguments of one staged (sub-)launch of `blocks` workgroups and A.count histories.  The buffers belong to the
-// device model, are allocated at the first staged launch and only grow (launches of one context share them, as they share the id
-// dispensers: one launch at a time).  An allocation that fails leaves this and every later launch on the direct atomics.
-static void stage_prepare(mcgpu_ctx& C, TrackArgs& A, int blocks, hipStream_t stream) {
-  DeviceModel& D = C.dev;
-  if (D.stage_alloc_failed || blocks <= 0) return;
-  const TallyStagePlan P = tally_stage_plan(4ULL * (unsigned long long)C.host.detector[0].total_pixels, A.count, (unsigned int)blocks, D.stage_bins,
-                                            (unsigned int)D.knobs.stage_cap);
-  if (P.n_bins == 0u || P.n_bins != D.stage_bins) return;
-  const size_t counts_bytes = (size_t)blocks * P.n_bins * 4;
-  try {
-    if (!D.stage_fallback) D.stage_fallback = D.put(std::vector<unsigned long long>(2, 0ULL));
-    if (counts_bytes > D.stage_counts_bytes) {
-      if (D.stage_counts) { D.mem.free(D.stage_counts); D.stage_counts = nullptr; D.stage_counts_bytes = 0; }
-      D.stage_counts = (unsigned int*)D.mem.device_bytes(counts_bytes);
-      D.stage_counts_bytes = counts_bytes;
-    }
-    if (P.bytes > D.stage_region_bytes) {
-      if (D.stage_region) { D.mem.free(D.stage_region); D.stage_region = nullptr; D.stage_region_bytes = 0; }
-      D.stage_region = (unsigned long long*)D.mem.device_bytes((size_t)P.bytes);
-      D.stage_region_bytes = (size_t)P.bytes;
-    }
-  } catch (const Error&) {
-    (void)hipGetLastError();
-    D.stage_alloc_failed = true;
-    return;
-  }
-  StageArgs S{};
-  S.region = D.stage_region; S.counts = D.stage_counts; S.fallback = D.stage_fallback;
-  S.pixels = P.pixels; S.n_bins = P.n_bins; S.magic = P.magic; S.bin_pixels = P.bin_pixels; S.cap = P.cap;
-  S.cursor = D.stage_cursor;
-  if (!D.stage_fold_ready) {
-    HIP_TRY(prepare_tally_fold(S));
-    D.stage_fold_ready = true;
-  }
-  HIP_TRY(hipMemsetAsync(D.stage_counts, 0, counts_bytes, stream));
-  D.stage_plan = P;
-  A.stage = S;
-}
-
-// The plan of the staged tally for a detector of `detector_words` tally words, a launch of `histories` and `workgroups` workgroups
-// (`bins` = 0: the engine's own choice): out6 = {bins, words per bin, bin pixels, capacity, bytes, sub-launches at `limit`}.  Pure host
-// arithmetic: works without a context and on one created with device = -1.
-int mcgpu_tally_stage_plan(const mcgpu_ctx* ctx, unsigned long long detector_words, unsigned long long histories, int workgroups, int bins,
-                           unsigned long long limit, unsigned long long* out6) {
-  ABI_BEGIN
-  (void)ctx;
-  require(out6 && workgroups > 0 && bins >= 0 && limit > 0, -1, "!!ERROR!! mcgpu_tally_stage_plan: bad argument");
-  const TallyStagePlan P = tally_stage_plan(detector_words, std::min(histories, limit), (unsigned int)workgroups, (unsigned int)bins, 0u);
-  out6[0] = P.n_bins; out6[1] = P.words_per_bin; out6[2] = P.bin_pixels; out6[3] = P.cap; out6[4] = P.bytes;
-  out6[5] = stage_sub_launches(histories, limit);
-  return 0;
-  ABI_END
-}
-
-// Tally words first .. first + n - 1 of that plan -> bin and bin-relative word (the mapping the kernels use, tally_stage.hpp)
-int mcgpu_tally_stage_map(unsigned long long detector_words, int bins, unsigned long long first, unsigned long long n, unsigned int* bin_out,
-                          unsigned int* rel_out) {
-  ABI_BEGIN
-  require(bin_out && rel_out && bins >= 0 && first + n <= detector_words, -1, "!!ERROR!! mcgpu_tally_stage_map: bad argument");
-  const TallyStagePlan P = tally_stage_plan(detector_words, 1, 1, (unsigned int)bins, 0u);
-  require(P.n_bins != 0u, -2, "!!ERROR!! mcgpu_tally_stage_map: no staging plan for this detector");
-  for (unsigned long long i = 0; i < n; ++i) {
-    stage_map((unsigned int)(first + i), P.pixels, P.n_bins, P.magic, P.bin_pixels, bin_out[i], rel_out[i]);
-    require(stage_unmap(bin_out[i], rel_out[i], P.pixels, P.n_bins, P.bin_pixels) == (unsigned int)(first + i), -9,
-            "!!ERROR!! internal: stage_map and stage_unmap disagree");
-  }
-  return 0;
-  ABI_END
-}
-
-// Sub-launch k of a staged launch: its range of histories
-int mcgpu_tally_stage_sub_launch(unsigned long long first, unsigned long long count, unsigned long long limit, unsigned long long k,
-                                 unsigned long long* sub_first, unsigned long long* sub_count) {
-  ABI_BEGIN
-  require(sub_first && sub_count && limit > 0, -1, "!!ERROR!! mcgpu_tally_stage_sub_launch: bad argument");
-  stage_sub_launch(first, count, limit, k, *sub_first, *sub_count);
-  return 0;
-  ABI_END
-}
-
-int mcgpu_launch_projection(mcgpu_ctx* ctx, int p, int mode, int seed, unsigned long long first, unsigned long long count, int hpt,
-                            void* image_dev, void* hip_stream) {
-  return mcgpu_launch_projection_w2(ctx, p, mode, seed, first, count, hpt, image_dev, nullptr, hip_stream);
-}
-
-// The launch, with the tally of squared weights `w2_dev` beside the image (tally_stage.hpp; null: none).
-int mcgpu_launch_projection_w2(mcgpu_ctx* ctx, int p, int mode, int seed, unsigned long long first, unsigned long long count, int hpt,
-                               void* image_dev, void* w2_dev, void* hip_stream) {
-  ABI_BEGIN
-  require(ctx && ctx->has_device, -1, "!!ERROR!! mcgpu_launch_projection: the context has no device (created with device_id < 0)");
-  require(p >= 0 && p < ctx->host.cfg.num_projections, -1, "!!ERROR!! mcgpu_launch_projection: projection index out of range");
-  require(image_dev != nullptr, -1, "!!ERROR!! mcgpu_launch_projection: null image buffer");
-  require(mode == MCGPU_MODE_FAST || mode == MCGPU_MODE_COMPAT || mode == MCGPU_MODE_FAST_STATS || mode == MCGPU_MODE_FAST_F64, -1, "!!ERROR!! mcgpu_launch_projection: unknown mode");
-  DeviceModel& D = ctx->dev;
-  HIP_TRY(hipSetDevice(D.device_id));
-  hipStream_t stream = (hipStream_t)hip_stream;
-  TrackArgs A = make_args(*ctx, p);
-  A.image = (unsigned long long*)image_dev;
-  A.w2 = (unsigned long long*)w2_dev;
-  A.seed = seed; A.hpt = hpt; A.first = first; A.count = count;
-  HIP_TRY(hipEventRecord(D.ev_start, stream));
-  if (count > 0) {
-    if (mode == MCGPU_MODE_COMPAT) {
-      require(hpt > 0, -2, "!!ERROR!! mcgpu_launch_projection: histories per thread must be positive in COMPAT mode");
-      require(seed > 0 && seed < 2147483399, -2, "!!ERROR!! mcgpu_launch_projection: RANECU seed out of range");
-      const unsigned long long blocks = (count + kTrackBlockThreads - 1) / kTrackBlockThreads;
-      require(blocks <= 0x7fffffffULL, -2, "!!ERROR!! mcgpu_launch_projection: too many batches");
-      if (D.knobs.compat_stats) {  // diagnostic build only (-DMC_COMPAT_STATS): the kernel's wave-level counters
-        if (!D.stats) D.stats = D.put(std::vector<unsigned long long>(kNumStats + 3 * kWaveTrace, 0ULL));
-        A.stats = D.stats;
-      }
-      HIP_TRY(launch_track_compat(A, (int)blocks, stream));
-    } else {
-      // persistent grid: exactly the resident workgroups (an over-subscribed grid would run a second, thin round).  No
-      // environment read and no synchronisation here: the scheduler's parameters were uploaded by apply_schedule.
-      if (D.resident_fast <= 0) {
-        D.resident_fast = D.knobs.blocks_per_cu > 0 ? D.knobs.blocks_per_cu : std::min(occupancy_track_fast(A), occupancy_track_fast64(A));
-        if (D.resident_fast <= 0) D.resident_fast = 1;
-        D.resident_covers_w2 = false;
-      }
-      if (A.w2 != nullptr && !D.resident_covers_w2) {  // one grid size for all instantiations of the context
-        if (D.knobs.blocks_per_cu <= 0) D.resident_fast = std::max(1, std::min(D.resident_fast, std::min(occupancy_track_fast_w2(A), occupancy_track_fast64_w2(A))));
-        D.resident_covers_w2 = true;
-      }
-      unsigned long long resident = (unsigned long long)D.num_cus * (unsigned long long)D.resident_fast;
-      resident += resident * (unsigned long long)D.knobs.grid_spare_percent / 100ULL;  // spare workgroups: see the kernel's prologue
-      A.work_counter = D.work_counter;
-      // Staged detector tally (tally_stage.hpp): the launch is cut into sub-launches of at most the knob's limit -- history ids are
-      // explicit (first + id), so a cut cannot move a result -- and each is followed by its fold, in this stream and inside the events.
-      // A launch with w2 stages wherever the model has a plan, against the default rule: its direct route is two atomics per hit,
-      // the fold's second pass over the records is cheaper (profiles/tally_variance_ab.md).  MCGPU_TALLY_STAGE=0 still forces the atomics.
-      const bool staged = A.w2 != nullptr ? (D.stage_cursor >= 0 && D.knobs.tally_stage != 0) : stage_wanted(D);
-      const unsigned long long limit = staged ? D.knobs.stage_max_histories : count;
-      const unsigned long long n_sub = staged ? stage_sub_launches(count, limit) : 1ULL;
-      for (unsigned long long k = 0; k < n_sub; ++k) {
-        stage_sub_launch(first, count, limit, k, A.first, A.count);
-        const int blocks = (int)std::min((A.count + kPoolBlockThreads - 1) / kPoolBlockThreads, resident);
-        HIP_TRY(hipMemsetAsync(D.work_counter, 0, (size_t)kNumCounters * kCounterStride * 8, stream));
-        A.stage = StageArgs{};
-        if (staged) stage_prepare(*ctx, A, blocks, stream);  // leaves A.stage.region null where the buffers cannot be had
-        if (mode == MCGPU_MODE_FAST_STATS) {
-#if defined(MC_WITH_STATS) && MC_WITH_STATS
-          if (!D.stats) D.stats = D.put(std::vector<unsigned long long>(kNumStats + 3 * kWaveTrace, 0ULL));
-          A.stats = D.stats;
-          HIP_TRY(launch_track_stats(A, blocks, stream));
-#else
-          throw Error(-2, "!!ERROR!! mcgpu_launch_projection: MCGPU_MODE_FAST_STATS needs the diagnostic library (libmcgpu_amd_stats.so, MCGPU_AMD_LIB)");
-#endif
-        } else if (mode == MCGPU_MODE_FAST_F64) {
-          HIP_TRY(A.w2 != nullptr ? launch_track_fast64_w2(A, blocks, stream) : launch_track_fast64(A, blocks, stream));
-        } else {
-          HIP_TRY(A.w2 != nullptr ? launch_track_fast_w2(A, blocks, stream) : launch_track_fast(A, blocks, stream));
-        }
-        if (A.stage.region != nullptr) {
-          HIP_TRY(launch_tally_fold(A.stage, (unsigned int)blocks, A.image, stream));
-          if (A.w2 != nullptr) HIP_TRY(launch_tally_fold_squares(A.stage, (unsigned int)blocks, A.w2, stream));
-        }
-      }
-    }
-  }
-  HIP_TRY(hipEventRecord(D.ev_stop, stream));
-  D.timed = true;
-  return 0;
-  ABI_END
-}
-
-int mcgpu_set_fast_schedule(mcgpu_ctx* ctx, int thresh_compton, int thresh_rayleigh, int thresh_new, int flyable_low, int swap_batch) {
-  ABI_BEGIN
-  require(ctx && ctx->has_device, -1, "!!ERROR!! mcgpu_set_fast_schedule: no device context");
-  require(thresh_compton >= 1 && thresh_rayleigh >= 1 && thresh_new >= 1 && flyable_low >= 1 && swap_batch >= 1 && thresh_compton <= 64 &&
-              thresh_rayleigh <= 64 && thresh_new <= 64 && flyable_low <= 64 && swap_batch <= 64,
-          -2, "!!ERROR!! mcgpu_set_fast_schedule: thresholds are lane counts in 1..64");
-  const int v[5] = {thresh_compton, thresh_rayleigh, thresh_new, flyable_low, swap_batch};
-  for (int k = 0; k < 5; ++k) ctx->dev.sched[k] = v[k];
-  ctx->dev.sched_set = true;
-  apply_schedule(ctx->dev);
-  return 0;
-  ABI_END
-}
-
-int mcgpu_reload_env_knobs(mcgpu_ctx* ctx) {
-  ABI_BEGIN
-  require(ctx && ctx->has_device, -1, "!!ERROR!! mcgpu_reload_env_knobs: no device context");
-  const int sched_kind = ctx->dev.knobs.fast_sched;  // fixed when the model was uploaded (it shapes the LDS image)
-  read_env_knobs(ctx->dev);
-  ctx->dev.knobs.fast_sched = sched_kind;
-  ctx->dev.resident_fast = 0;  // MCGPU_BLOCKS_PER_CU may have changed: asked again at the next launch
-  apply_schedule(ctx->dev);
-  return 0;
-  ABI_END
-}
-
-int mcgpu_scheduler_stats_ex(mcgpu_ctx* ctx, unsigned long long* out, int capacity, int reset) {
-  ABI_BEGIN
-  require(ctx && ctx->has_device && out && capacity > 0, -1, "!!ERROR!! mcgpu_scheduler_stats: bad argument");
-  HIP_TRY(hipSetDevice(ctx->dev.device_id));
-  const int n = std::min(capacity, kNumStats + 3 * kWaveTrace);  // counters, then the wave trace (device_model.hpp)
-  for (int k = 0; k < capacity; ++k) out[k] = 0;
-  if (!ctx->dev.stats) return 0;
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(out, ctx->dev.stats, (size_t)n * 8, hipMemcpyDeviceToHost));
-  if (reset) HIP_TRY(hipMemset(ctx->dev.stats, 0, (size_t)(kNumStats + 3 * kWaveTrace) * 8));
-  return 0;
-  ABI_END
-}
-
-int mcgpu_scheduler_stats(mcgpu_ctx* ctx, unsigned long long* out8, int reset) { return mcgpu_scheduler_stats_ex(ctx, out8, 8, reset); }
-
-int mcgpu_last_kernel_ms(mcgpu_ctx* ctx, float* ms) {
-  ABI_BEGIN
-  require(ctx && ctx->has_device && ms, -1, "!!ERROR!! mcgpu_last_kernel_ms: bad argument");
-  require(ctx->dev.timed, -1, "!!ERROR!! mcgpu_last_kernel_ms: nothing launched yet");
-  HIP_TRY(hipEventSynchronize(ctx->dev.ev_stop));
-  HIP_TRY(hipEventElapsedTime(ms, ctx->dev.ev_start, ctx->dev.ev_stop));
-  return 0;
-  ABI_END
-}
-
 int mcgpu_clear_image(mcgpu_ctx* ctx, void* image_dev, void* hip_stream) {
   ABI_BEGIN
   require(ctx && ctx->has_device && image_dev, -1, "!!ERROR!! mcgpu_clear_image: bad argument");
@@ -445,36 +194,6 @@ int mcgpu_copy_to_host(mcgpu_ctx* ctx, const void* src_dev, void* dst_host, size
   HIP_TRY(hipMemcpyAsync(dst_host, src_dev, bytes, hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
   HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));
   return 0;
-  ABI_END
-}
-
-int mcgpu_run_projection(mcgpu_ctx* ctx, int p, int mode, int seed, unsigned long long first, unsigned long long count, int hpt,
-                         uint64_t* image_host, double* kernel_seconds, unsigned long long* histories_done) {
-  return mcgpu_run_projection_w2(ctx, p, mode, seed, first, count, hpt, image_host, nullptr, kernel_seconds, histories_done);
-}
-
-int mcgpu_run_projection_w2(mcgpu_ctx* ctx, int p, int mode, int seed, unsigned long long first, unsigned long long count, int hpt,
-                            uint64_t* image_host, uint64_t* w2_host, double* kernel_seconds, unsigned long long* histories_done) {
-  ABI_BEGIN
-  require(ctx && ctx->has_device && image_host, -1, "!!ERROR!! mcgpu_run_projection: bad argument");
-  HIP_TRY(hipSetDevice(ctx->dev.device_id));
-  const size_t bytes = (size_t)32 * ctx->host.detector[0].total_pixels;
-  if (!ctx->dev.scratch_image) ctx->dev.scratch_image = (unsigned long long*)ctx->dev.put(std::vector<unsigned char>(bytes, 0));  // kept for the next call
-  if (w2_host && !ctx->dev.scratch_w2) ctx->dev.scratch_w2 = (unsigned long long*)ctx->dev.put(std::vector<unsigned char>(bytes, 0));
-  void* img = ctx->dev.scratch_image;
-  void* w2 = w2_host ? ctx->dev.scratch_w2 : nullptr;
-  HIP_TRY(hipMemset(img, 0, bytes));
-  if (w2) HIP_TRY(hipMemset(w2, 0, bytes));
-  int rc = mcgpu_launch_projection_w2(ctx, p, mode, seed, first, count, hpt, img, w2, nullptr);
-  if (rc == 0) {
-    float ms = 0.f;
-    rc = mcgpu_last_kernel_ms(ctx, &ms);
-    if (kernel_seconds) *kernel_seconds = ms * 1e-3;
-    HIP_TRY(hipMemcpy(image_host, img, bytes, hipMemcpyDeviceToHost));
-    if (w2) HIP_TRY(hipMemcpy(w2_host, w2, bytes, hipMemcpyDeviceToHost));
-    if (histories_done) *histories_done = (mode == MCGPU_MODE_COMPAT) ? count * (unsigned long long)hpt : count;
-  }
-  return rc;
   ABI_END
 }
 

@@ -1,8 +1,9 @@
 #pragma once
 // engine_internal.hpp -- what the translation units of the engine library share: the device model and the context (the error
 // plumbing and the per-call owners are hip_host.hpp's).
-// (engine.cpp: the C ABI of a context; model_device.cpp: the device model's memory, its upload in stages (upload_model) and launch
-// arguments; engine_geometry.cpp: geometry changes of a resident context; engine_kat.cpp: known-answer and micro-benchmark hooks.)
+// (engine.cpp: the C ABI of a context -- creation, configuration, files, dose, finalize, stacks; engine_launch.cpp: the tracking launch,
+// its arguments and the staged tally's host state; model_device.cpp: the device model's memory and its upload in stages (upload_model);
+// engine_geometry.cpp: geometry changes of a resident context; engine_kat.cpp: known-answer and micro-benchmark hooks.)
 //
 // Replaces init_CUDA_device (docker/mcgpu/MC-GPU_v1.3.cu:2454-2724) and the per-projection driver of
 // main() (:667-1056).  Compiled with hipcc; every HIP call lives here or in the kernel TUs.
@@ -30,24 +31,13 @@
 namespace mcgpu {
 
 hipError_t launch_track_compat(const TrackArgs& args, int blocks, hipStream_t stream);
-hipError_t launch_track_fast(const TrackArgs& args, int blocks, hipStream_t stream);
-int occupancy_track_fast(const TrackArgs& args);
-hipError_t launch_track_fast64(const TrackArgs& args, int blocks, hipStream_t stream);  // MCGPU_MODE_FAST_F64 (track_fast64.hip)
-int occupancy_track_fast64(const TrackArgs& args);
-// the same kernels with the second add of the direct tally route, for launches with a w2 (track_fast_w2.hip, track_fast64_w2.hip)
-hipError_t launch_track_fast_w2(const TrackArgs& args, int blocks, hipStream_t stream);
-int occupancy_track_fast_w2(const TrackArgs& args);
-hipError_t launch_track_fast64_w2(const TrackArgs& args, int blocks, hipStream_t stream);
-int occupancy_track_fast64_w2(const TrackArgs& args);
+// the FAST kernels: device_model.hpp: fast_kernels<kDouble, kW2, kStats>()
 hipError_t launch_kat_fast64(int n, const unsigned int* u, const double* a, const double* b, const double* c, const float* dir, double* out, hipStream_t stream);
 // kat_scatter.inc, once per arithmetic (track_fast.hip / track_fast64.hip)
 hipError_t launch_kat_scatter_fast(const TrackArgs& args, int kind, int n, unsigned int seed, unsigned int stream_key, const float* in4,
                                    const unsigned long long* in_u64, const int* mc, float* out4, unsigned int* out_u4, hipStream_t stream);
 hipError_t launch_kat_scatter_fast64(const TrackArgs& args, int kind, int n, unsigned int seed, unsigned int stream_key, const float* in4,
                                      const unsigned long long* in_u64, const int* mc, float* out4, unsigned int* out_u4, hipStream_t stream);
-#if defined(MC_WITH_STATS) && MC_WITH_STATS
-hipError_t launch_track_stats(const TrackArgs& args, int blocks, hipStream_t stream);  // diagnostic library only (track_stats.o)
-#endif
 hipError_t prepare_tally_fold(const StageArgs& S);  // tally_fold.hip
 hipError_t launch_tally_fold(const StageArgs& S, unsigned int workgroups, unsigned long long* image, hipStream_t stream);
 hipError_t launch_tally_fold_squares(const StageArgs& S, unsigned int workgroups, unsigned long long* w2, hipStream_t stream);
@@ -89,6 +79,27 @@ class DeviceOwner {
   std::vector<void*> buffers_, pinned_;
   std::vector<hipStream_t> streams_;
   std::vector<hipEvent_t> events_;
+};
+
+// Host state of the staged detector tally (tally_stage.hpp) and the code that reads and writes it (engine_launch.cpp).  The cursor table's
+// place in the LDS image is fixed at upload (-1: it does not fit, this model runs the direct atomics); the buffers belong to the device
+// model's owner `mem`, are allocated at the first staged launch and only grow.
+struct DeviceModel;
+struct TallyStage {
+  int cursor = -1;
+  unsigned int bins = 0;
+  unsigned long long* region = nullptr;
+  size_t region_bytes = 0;
+  unsigned int* counts = nullptr;
+  size_t counts_bytes = 0;
+  unsigned long long* fallback = nullptr;
+  bool alloc_failed = false, fold_ready = false;
+  TallyStagePlan plan{};  // of the last staged (sub-)launch
+
+  bool wanted(const DeviceModel& D, bool has_w2) const;  // whether a launch of this model stages its hits
+  void prepare(DeviceModel& D, unsigned long long detector_words, TrackArgs& A, int blocks, hipStream_t stream);
+  unsigned long long fallback_hits(const DeviceModel& D) const;  // both wait for the device
+  unsigned long long staged_hits(const DeviceModel& D) const;
 };
 
 struct DeviceModel {
@@ -152,17 +163,7 @@ struct DeviceModel {
   bool resident_covers_w2 = false;  // ... and the w2 instantiations have been asked too (at the first launch with a w2)
   unsigned long long* stats = nullptr;  // kNumStats scheduler counters of the diagnostic build
   unsigned long long* work_counter = nullptr;  // history-id dispenser of the FAST kernel
-  // staged detector tally (tally_stage.hpp): the cursor table's place in the LDS image is fixed at upload (-1: it does not fit, this
-  // model runs the direct atomics); the buffers are allocated at the first staged launch and only grow
-  int stage_cursor = -1;
-  unsigned int stage_bins = 0;
-  unsigned long long* stage_region = nullptr;
-  size_t stage_region_bytes = 0;
-  unsigned int* stage_counts = nullptr;
-  size_t stage_counts_bytes = 0;
-  unsigned long long* stage_fallback = nullptr;
-  bool stage_alloc_failed = false, stage_fold_ready = false;
-  TallyStagePlan stage_plan{};  // of the last staged (sub-)launch
+  TallyStage stage;  // staged detector tally: its host state, above
   unsigned long long* scratch_image = nullptr;  // device tally of mcgpu_run_projection (allocated on first use)
   unsigned long long* scratch_w2 = nullptr;     // ... and the squared weights of mcgpu_run_projection_w2
   float *woodcock = nullptr, *mfp = nullptr, *mfp_tot = nullptr;
@@ -182,7 +183,7 @@ struct DeviceModel {
     int slot_trade = 3, hold_q = 6;                  // MCGPU_SLOT_TRADE, MCGPU_HOLD_Q
     bool no_exterior = false;                        // MCGPU_NO_EXTERIOR (also read by the geometry builders)
     int segment_loop = -1;                           // MCGPU_SEGMENT_LOOP: -1 chosen from the model (make_args), 0 / 1 forced
-    int tally_stage = -1;                            // MCGPU_TALLY_STAGE: detector hits staged and folded (tally_stage.hpp): 1 on, 0 direct atomics, -1 by the exterior share (engine.cpp: stage_wanted)
+    int tally_stage = -1;                            // MCGPU_TALLY_STAGE: detector hits staged and folded (tally_stage.hpp): 1 on, 0 direct atomics, -1 by the exterior share (engine_launch.cpp: TallyStage::wanted)
     int stage_cap = 0;                               // MCGPU_TALLY_STAGE_CAP (test hook): records per (workgroup, bin), 0: from the plan
     unsigned long long stage_max_histories = 1ULL << 27;  // MCGPU_TALLY_STAGE_MAX_HISTORIES: sub-launch limit of a staged launch
     int fast_sched = 0;                              // MCGPU_FAST_SCHED: 0 per-wave pools, 1 workgroup-level pool (fixes the LDS layout: read at upload)
@@ -232,7 +233,7 @@ struct DeviceVolumeSource {
   unsigned int first[kImageClasses];             // smallest [z][y][x] index of the class, 0xFFFFFFFF: it does not occur
 };
 DeviceModel upload_model(const HostModel& H, int device_id, const DeviceVolumeSource* mapped = nullptr);
-TrackArgs make_args(const mcgpu_ctx& C, int p);
+TrackArgs make_args(const mcgpu_ctx& C, int p);  // engine_launch.cpp
 void sync_host_voxels(mcgpu_ctx& C);
 const void* host_table(mcgpu_ctx& C, const std::string& name, size_t& bytes);
 }  // namespace mcgpu

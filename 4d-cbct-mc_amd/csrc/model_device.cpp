@@ -1,4 +1,4 @@
-// model_device.cpp -- the device-resident model of a context: tables, volume, brick grids, LDS layout, launch arguments.
+// model_device.cpp -- the device-resident model of a context: tables, volume, brick grids, LDS layout.
 // Replaces init_CUDA_device (docker/mcgpu/MC-GPU_v1.3.cu:2454-2724).
 #include "engine_internal.hpp"
 
@@ -898,11 +898,11 @@ static void lay_out_lds_and_brackets(const HostModel& H, DeviceModel& D, const s
   {
     const TallyStagePlan S = tally_stage_plan(4ULL * (unsigned long long)H.detector[0].total_pixels, 1, 1, 0, 0);
     const int bytes = ((int)(S.n_bins + 1u) * 4 + 15) / 16 * 16;
-    D.stage_cursor = -1;
-    D.stage_bins = 0;
+    D.stage.cursor = -1;
+    D.stage.bins = 0;
     if (S.n_bins != 0u && D.lds.total + bytes <= kLdsPerWorkgroup) {
-      D.stage_cursor = D.lds.total;
-      D.stage_bins = S.n_bins;
+      D.stage.cursor = D.lds.total;
+      D.stage.bins = S.n_bins;
       D.lds.total += bytes;
     }
   }
@@ -1010,73 +1010,6 @@ DeviceModel upload_model(const HostModel& H, int device_id, const DeviceVolumeSo
 }
 
 void require(bool ok, int code, const char* msg) { if (!ok) throw Error(code, msg); }
-
-TrackArgs make_args(const mcgpu_ctx& C, int p) {
-  const HostModel& H = C.host;
-  const DeviceModel& D = C.dev;
-  TrackArgs A;
-  memset(&A, 0, sizeof A);
-  A.vol = D.vol; A.palette = D.palette; A.vol_kind = D.vol_kind; A.palette_size = D.palette_size;
-  A.brick_shift = D.brick_shift; A.brick_nx = D.brick_n[0]; A.brick_nxy = D.brick_n[0] * D.brick_n[1];
-  A.brick_bytes = D.vol_kind == kVolU8 ? D.brick_bytes : 0;
-  A.sub = D.vol_kind == kVolU8 ? D.sub : nullptr; A.sub_nx = D.sub_n[0]; A.sub_nxy = D.sub_n[0] * D.sub_n[1];
-  A.sub_kind = A.sub ? 1 : 0;
-  A.rec_nx = D.rec_n[0]; A.rec_nxy = D.rec_n[0] * D.rec_n[1];
-  if (D.vol_kind == kVolU8 && D.tile_rec) { A.sub = reinterpret_cast<const unsigned char*>(D.tile_rec); A.sub_kind = 2; }  // the records win over the code table
-  A.lds = D.lds;
-  A.nx = H.voxels.n[0]; A.ny = H.voxels.n[1]; A.nz = H.voxels.n[2]; A.nxy = A.nx * A.ny;
-  for (int k = 0; k < 3; ++k) {
-    A.inv_vs[k] = H.voxels.inv_voxel_size[k];
-    A.bbox[k] = H.voxels.size_bbox[k];
-    // upper clamp of the FAST kernel: bbox - EPS_SOURCE (MC-GPU_v1.3.h:87), lowered until it indexes the last voxel
-    float hi = A.bbox[k] - 0.000015f;
-    while ((int)(hi * A.inv_vs[k]) > H.voxels.n[k] - 1) hi = std::nextafter(hi, 0.0f);
-    A.bbox_hi[k] = hi;
-  }
-  require((long long)A.nx * A.ny < (1LL << 24) && (long long)H.voxels.count() < (1LL << 31), -2,
-          "!!ERROR!! voxel grid too large for the 32-bit voxel index of the kernel");
-  A.e0 = H.mat.e0; A.ide = H.mat.ide; A.num_values = H.mat.num_values; A.nmat = D.nmat;
-  A.woodcock = D.woodcock; A.mfp = D.mfp; A.mfp_tot = D.mfp_tot; A.sig_shift = D.sig_shift;
-  A.cold = D.cold;
-  A.nbins = H.spectrum.num_bins;
-  A.src = D.src_all + p; A.det = D.det_all + p;
-  A.stream_key = (unsigned)p;
-  A.dose_flags = D.dose_flags;
-
-  A.sched_kind = D.knobs.fast_sched;
-  A.has_exterior = (D.vol_kind == kVolU8 && D.has_exterior) ? D.knobs.exterior_mode : 0;  // bit 0: hop during flight, bit 1: hop at the source
-  // batching thresholds of the COMPAT kernel (lanes of a wave64 holding such a history in their registers or their parking slot)
-  // The Compton batch of the COMPAT kernel walks every electron shell of the material several times in the reference's own
-  // arithmetic: with tissue tables (29-40 shells) it is 60-73 % of the kernel and wants FULL batches -- threshold 40 of 64 lanes
-  // instead of 20: thorax +39 %, CIRS +32 % (tools/compat_sweep.py) -- while the 4-12 shells of the Catphan's plastics prefer
-  // photons back in flight early (40: -21 %).  Chosen from the mean shell count of the materials in use; tallies do not depend on it.
-  // Second sweep: the tally/source batch is cheap and should not hold lanes back (24 -> 12..16 lanes), which in turn lets the
-  // Compton batch wait for 48: thorax 1.9e8 -> 2.95e8, CIRS 4.6e8 -> 6.5e8, Catphan 1.58e9 -> 1.66e9 histories/s.
-  // Round 3, with resumable Compton trials and two batches per lane (track_kernel.inc), the same thresholds are still the best of
-  // the sweep (profiles/r03u_compat_sweep.txt): thorax 4.1e8, CIRS 9.2e8, Catphan 1.8e9; exchanging the two histories of a lane
-  // pays from 1-8 takers on (thresh_take), 16+ loses.
-  // Later in round 3 the Compton batch lost two thirds of its cost (S0 bounds, in-place Klein-Nishina rejections) and the wave takes
-  // four flight steps between two looks at its state: 48 / 8 / 16 on tissue and 32 / 4 / 24 on plastics sit on flat optima
-  // (profiles/r03y_compat_sweep.txt).
-  int shells = 0, used = 0;
-  for (int m = 0; m < kMaxMaterials; ++m)
-    if (D.compact_of[m] >= 0) { shells += std::min(H.mat.noscco[m], kMaxShells); ++used; }
-  const bool many_shells = used > 0 && shells >= 20 * used;
-  A.segment_loop = D.knobs.segment_loop >= 0 ? D.knobs.segment_loop : ((A.sub_kind == 2 || many_shells) ? 1 : 0);  // track_pool.inc: kSegmentLoop
-  A.thresh_compton = D.knobs.compat_thresh[0] >= 0 ? D.knobs.compat_thresh[0] : (many_shells ? 48 : 32);
-  A.thresh_rayleigh = D.knobs.compat_thresh[1] >= 0 ? D.knobs.compat_thresh[1] : (many_shells ? 8 : 4);
-  A.thresh_new = D.knobs.compat_thresh[2] >= 0 ? D.knobs.compat_thresh[2] : (many_shells ? 16 : 24);
-  A.thresh_take = D.knobs.compat_thresh[3] >= 0 ? D.knobs.compat_thresh[3] : 2;
-  // One source of truth: the FAST kernel reads mfp / e0 / ide / bbox / lds from TrackCold, written once in upload_model
-  // (they would otherwise sit in scalar registers for the whole persistent loop); the COMPAT kernel reads the copies above.
-  if (D.cold) {
-    const TrackCold& ch = D.cold_host;
-    require(ch.mfp == A.mfp && ch.e0 == A.e0 && ch.ide == A.ide && memcmp(ch.bbox, A.bbox, sizeof A.bbox) == 0 && memcmp(&ch.lds, &A.lds, sizeof A.lds) == 0, -9,
-            "!!ERROR!! internal: TrackCold and the launch arguments disagree on mfp / e0 / ide / bbox / lds (upload_model and make_args have drifted apart)");
-  }
-  return A;
-}
-
 
 // After mcgpu_warp_geometry the voxels exist on the device only; whoever needs them on the host calls this first.
 void sync_host_voxels(mcgpu_ctx& C) {

@@ -31,7 +31,7 @@ namespace mcgpu {
 constexpr unsigned int kTallyW2Shift = 10;       // w2 += (w >> kTallyW2Shift)^2
 constexpr unsigned int kStageRun = 64;           // pixels of a run
 constexpr unsigned int kStageRunsPerBin = 64;    // a bin's words as 64-bit counters fill at most 128 KiB of the fold's LDS
-constexpr int kStageExteriorPercent = 50;        // default rule: stage where at least this share of the bricks is exterior (engine.cpp: stage_wanted)
+constexpr int kStageExteriorPercent = 50;        // default rule: stage where at least this share of the bricks is exterior (engine_launch.cpp: TallyStage::wanted)
 constexpr unsigned int kStageCapSlack = 16;      // records added to every block's capacity
 // Histories a workgroup may run beyond its even share of the launch: history ids are dealt in chunks of 256 per wave (track_common.inc:
 // kChunk), and in a launch of few chunks the waves that ask first get them all -- a workgroup of 16 waves then holds one or two chunks

@@ -73,9 +73,6 @@ __device__ __forceinline__ const GLOBAL_AS T* as_global(const T* p) { return (co
 // ... and one that every kernel reads that way, COMPAT included: the pointer of the optional second tally (TrackArgs::w2) is wanted only
 // where a photon scores; as a launch argument proper it would hold a pair of scalar registers for the whole kernel
 #define KARG(field) (((const CONST_AS TrackArgs*)__builtin_amdgcn_kernarg_segment_ptr())->field)
-#ifndef MC_TALLY_W2
-#define MC_TALLY_W2 0  // FAST: 1 in the instantiations that launches with a w2 run (tally_score)
-#endif
 #define SRC(A) ((const CONST_AS SourcePose*)LARG(A, src))
 #define DET(A) ((const CONST_AS DetectorPose*)LARG(A, det))
 // byte offset of a SERVICE-side table in the LDS image (TrackCold::lds)
@@ -271,6 +268,12 @@ __device__ void rotate_dir(Particle& P, double costh, double phi) {
 //      (-use_fast_math) computes in float as well.
 #ifndef MC_FAST_F64
 #define MC_FAST_F64 0
+#endif
+#ifndef MC_TALLY_W2
+#define MC_TALLY_W2 0  // FAST: 1 in the instantiations that launches with a w2 run (tally_score)
+#endif
+#ifndef MC_STATS
+#define MC_STATS 0  // FAST: 1 in the diagnostic build (track_stats.hip)
 #endif
 #if MC_FAST_F64
 typedef double polar_t;  // cos(theta), as the reference carries it
@@ -1170,10 +1173,7 @@ __device__ __forceinline__ void stage_tables(const TrackArgs& A) {
   __syncthreads();
 }
 
-#ifndef MC_STATS
-#define MC_STATS 0
-#endif
-#if MC_STATS
+#if defined(MC_STATS) && MC_STATS
 // diagnostic build only (track_stats.hip): scheduler statistics, one atomic per wave and counter at exit
 #define STAT_ADD(slot, v) st[slot] += (unsigned long long)(v)
 #else

@@ -1161,25 +1161,7 @@ static_assert(std::is_same<kernel_signature<decltype(&track_pool_kernel<kVolU8, 
 
 }  // namespace
 
-// host-side launchers of this personality
-#if MC_STATS
-#define MC_LAUNCH_NAME launch_track_stats
-#define MC_OCC_NAME occupancy_track_stats
-#elif MC_FAST_F64 && MC_TALLY_W2
-#define MC_LAUNCH_NAME launch_track_fast64_w2
-#define MC_OCC_NAME occupancy_track_fast64_w2
-#elif MC_FAST_F64
-#define MC_LAUNCH_NAME launch_track_fast64
-#define MC_OCC_NAME occupancy_track_fast64
-#elif MC_TALLY_W2
-#define MC_LAUNCH_NAME launch_track_fast_w2
-#define MC_OCC_NAME occupancy_track_fast_w2
-#else
-#define MC_LAUNCH_NAME launch_track_fast
-#define MC_OCC_NAME occupancy_track_fast
-#endif
-
-// resident workgroups per CU for this kernel variant (persistent grids must not over-subscribe)
+// host-side launchers of this personality: this translation unit's entry of the table of FAST kernels (device_model.hpp)
 namespace {
 typedef void (*TrackKernel)(const TrackArgs);
 template <int VK>
@@ -1194,15 +1176,21 @@ TrackKernel pick_kernel(const TrackArgs& args) {
     default: return pick<kVolRaw>(wg, seg);
   }
 }
-}  // namespace
-int MC_OCC_NAME(const TrackArgs& args) {
+// resident workgroups per CU for this kernel variant (persistent grids must not over-subscribe)
+int occupancy(const TrackArgs& args) {
   int n = 0;
   const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pick_kernel(args), kPoolBlock, (size_t)args.lds.total);
   return (e == hipSuccess && n > 0) ? n : 1;
 }
-hipError_t MC_LAUNCH_NAME(const TrackArgs& args, int blocks, hipStream_t stream) {
+hipError_t launch(const TrackArgs& args, int blocks, hipStream_t stream) {
   hipLaunchKernelGGL(pick_kernel(args), dim3((unsigned)blocks), dim3(kPoolBlock), (size_t)args.lds.total, stream, args);
   return hipGetLastError();
+}
+}  // namespace
+template <>
+const FastKernels& fast_kernels<MC_FAST_F64, MC_TALLY_W2, MC_STATS>() {
+  static const FastKernels table = {launch, occupancy};
+  return table;
 }
 
 }  // namespace mcgpu

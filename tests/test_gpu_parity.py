@@ -173,6 +173,34 @@ def test_fast_history_sharding_and_determinism(gpu_engine, case_dir):
         assert not np.array_equal(whole, other)
 
 
+def test_fast_grid_size_is_asked_once_shrinks_for_w2_and_is_asked_again_after_a_reload(gpu_engine, case_dir, monkeypatch):
+    """"blocks_per_cu" over the life of a context: 0 until the first FAST launch asks the occupancy of the f32 and f64 kernels, the
+    same for both arithmetics, at most that once the first launch with squared weights has asked their w2 instantiations too, 0
+    again after reload_env_knobs, then what MCGPU_BLOCKS_PER_CU says.  The grid size never moves a tally word."""
+    monkeypatch.delenv("MCGPU_BLOCKS_PER_CU", raising=False)
+    n, images = 20_000, []
+    with gpu_engine.create(case_dir("catphan64"), device=0) as ctx:
+        assert ctx.geti("blocks_per_cu") == 0
+        images.append(ctx.run_projection(0, n, mode="fast", seed=5)[0])
+        b1 = ctx.geti("blocks_per_cu")
+        assert b1 >= 1
+        f64 = ctx.run_projection(0, n, mode="fast64", seed=5)[0]
+        assert ctx.geti("blocks_per_cu") == b1 and int(f64.sum()) > 0
+        images.append(ctx.run_projection_with_variance(0, n, mode="fast", seed=5)[0])
+        b2 = ctx.geti("blocks_per_cu")
+        assert 1 <= b2 <= b1
+        images.append(ctx.run_projection(0, n, mode="fast", seed=5)[0])
+        assert ctx.geti("blocks_per_cu") == b2
+        monkeypatch.setenv("MCGPU_BLOCKS_PER_CU", "1")
+        ctx.reload_env_knobs()
+        assert ctx.geti("blocks_per_cu") == 0
+        images.append(ctx.run_projection(0, n, mode="fast", seed=5)[0])
+        assert ctx.geti("blocks_per_cu") == 1
+    assert int(images[0].sum()) > 0
+    for k, img in enumerate(images[1:], 1):
+        assert np.array_equal(img, images[0]), k
+
+
 def test_volume_storage_kinds_are_exercised(gpu_engine, case_dir):
     """u8 palette / u16 palette / raw float2 voxels (device_model.hpp): the graded cases reach the two wider kinds."""
     kinds = {}

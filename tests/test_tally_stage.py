@@ -67,6 +67,18 @@ def test_plan_needs_no_device(engine, case_dir):
     assert a == engine.tally_stage_plan(nx * nz * 4, 60_000, 512)
 
 
+def test_a_context_without_a_device_stages_nothing_and_refuses_to_launch(engine, case_dir):
+    """The staged tally's host state of a context created with device = -1 is the empty one: every key that reads it answers 0
+    without touching a device, no grid size has been asked, and a launch is refused before anything else is looked at."""
+    with engine.create(case_dir("catphan64"), device=-1) as ctx:
+        for key in ("tally_stage_bins", "tally_stage_capacity", "tally_stage_bytes", "tally_stage_fallback_hits", "tally_stage_staged_hits",
+                    "blocks_per_cu"):
+            assert ctx.geti(key) == 0, key
+        with pytest.raises(engine.EngineError) as e:
+            ctx.launch(0, 0, 1000, mode="fast", seed=3)
+        assert e.value.code == -1 and "has no device" in e.value.message
+
+
 @pytest.mark.parametrize("limit", [1, 7, 1000, 1 << 27])
 def test_sub_launches_tile_the_launch(engine, limit):
     first = 2 ** 32 - 5

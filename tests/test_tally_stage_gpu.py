@@ -115,6 +115,26 @@ def test_sub_launches_give_the_unsplit_image(engine, case_dir, monkeypatch):
         assert done == n and np.array_equal(whole, ref) and np.array_equal(split, ref)
 
 
+@pytest.mark.parametrize("stage", [None, 1])
+def test_a_refused_stats_launch_leaves_the_context_usable(engine, case_dir, monkeypatch, stage):
+    """The product library carries no diagnostic kernel: a "stats" launch is refused -- after the launch has prepared its staging
+    buffers -- and the context goes on giving the image it gave before.  Default knobs and staging forced on."""
+    if "stats" in Path(engine.LIB_PATH).name:
+        pytest.skip("MCGPU_AMD_LIB points at the diagnostic library, which runs the stats mode")
+    for k in KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    if stage is not None:
+        monkeypatch.setenv("MCGPU_TALLY_STAGE", str(stage))
+    with engine.create(case_dir("catphan64"), device=0) as ctx:
+        ref, _, done = ctx.run_projection(0, 20_000, mode="fast", seed=3)
+        assert done == 20_000 and int(ref.sum()) > 0
+        with pytest.raises(engine.EngineError) as e:
+            ctx.run_projection(0, 20_000, mode="stats", seed=3)
+        assert e.value.code == -2 and "libmcgpu_amd_stats.so" in e.value.message
+        again, _, _ = ctx.run_projection(0, 20_000, mode="fast", seed=3)
+        assert np.array_equal(again, ref)
+
+
 def test_dose_tallies_share_the_final_barrier(engine, case_dir, monkeypatch):
     with engine.create(case_dir("catphan64_dose"), device=0) as ctx:
         assert ctx.dose_info()[0] == 3
