@@ -621,6 +621,62 @@ int mcgpu_rooster4d_reconstruct(const mcgpu_rooster4d_options *options, const fl
 enum { MCGPU_ROOSTER4D_STAGE_FORWARD = 0, MCGPU_ROOSTER4D_STAGE_BACK = 1, MCGPU_ROOSTER4D_STAGE_TV_SPACE = 2, MCGPU_ROOSTER4D_STAGE_TV_TIME = 3 };
 int mcgpu_rooster4d_stage(const mcgpu_rooster4d_options *options, int stage, const float *in, float *out, mcgpu_rooster4d_report *report);
 
+/* ------------------------------------------------------------------------------------------------
+ * The speed-up network (what the reference obtains from cbctmc/speedup/inference.py: MCSpeedup; csrc/speedup_net.hip, whose
+ * header restates the network).  Two U-Nets of 3 x 3 convolutions (replicate padding, bias), instance norm and LeakyReLU(0.01),
+ * in float32: the mean net sees the low-photon projection and the forward projection (matched to it in mean and unbiased
+ * std per projection), the variance net sees the mean.  mean = relu(low_photon + 10 tanh(mean_net)), variance = mean x 0.10
+ * sigmoid(var_net(mean)) + 1e-6, sample = mean + sqrt(variance) z.  z is standard normal by Box-Muller from Philox4x32-10 with
+ * key (seed low, seed high) and counter (x, y, first_projection + p, 0): u1 = ((w0 >> 8) + 1) 2^-24, u2 = (w1 >> 8) 2^-24,
+ * z = sqrt(-2 ln u1) cos(2 pi u2).  Projections are independent: the result does not depend on how a stack is split into calls.
+ * `weights` is one flat float32 buffer: for the mean net, then the variance net, the tensors init_conv, final_conv, enc_0 ..
+ * enc_{L-1} (first, second convolution), dec_{L-1} .. dec_0 (first, second), each as weight [c_out][c_in][3][3] then bias
+ * [c_out] (the order of the reference's state dict without var_scale; tests/golden/speedup_state_dict.json).
+ * Refused before any device call (-1, mcgpu_last_error): a null input, an n_weights that is not the architecture's, nu or nv
+ * not divisible by 2^levels of the deeper net, a net whose bottleneck would have fewer than 2 pixels, and a forward-projection
+ * slice of zero variance (the reference divides by zero there and returns NaN). */
+typedef struct mcgpu_speedup_options {
+  unsigned int struct_size;     /* sizeof(mcgpu_speedup_options) as the caller was compiled (later fields read as zero); 0 is refused */
+  int device;
+  int n, nu, nv;                /* stacks are [n][nv][nu] */
+  int mean_in_channels;         /* 2: low photon + forward projection; 1: low photon alone (forward_projection must then be NULL) */
+  int mean_levels, mean_filter_base;   /* the reference's: 4, 64 */
+  int var_in_channels;          /* 1 */
+  int var_levels, var_filter_base;     /* the reference's: 2, 16 */
+  const float *weights;
+  unsigned long long n_weights; /* 13,401,586 for the reference's architecture */
+  unsigned long long seed;
+  int first_projection;         /* projection index of slice 0 in the sampler's counter */
+} mcgpu_speedup_options;
+typedef struct mcgpu_speedup_report {
+  double ms_upload;             /* host <-> device copies and the repacking of the weights */
+  double ms_preprocess;         /* statistics and matching of the forward projection */
+  double ms_conv;               /* convolution kernels */
+  double ms_norm;               /* instance norm + LeakyReLU kernels */
+  double ms_other;              /* max-pool, head, sampler */
+  double ms_total;              /* wall time of the call */
+  unsigned long long peak_device_bytes;  /* most device memory the call held at once */
+} mcgpu_speedup_report;
+/* All stacks are host pointers to [n][nv][nu] float32; any of mean, variance, sample may be NULL. */
+int mcgpu_speedup_run(const mcgpu_speedup_options *options, const float *low_photon, const float *forward_projection, float *mean,
+                      float *variance, float *sample, mcgpu_speedup_report *report);
+/* One operator alone (for tests), on images of nv rows x nu columns; the options' architecture, weights and n_weights are not
+ * used.  CONV: in [c1][nv][nu] and optionally in2 [c2][nv2][nu2] (concatenated after in; with `upsample` in2 is read through the
+ * x 2 nearest upsample and has nv2 = (nv + 1) / 2 rows and nu2 = (nu + 1) / 2 columns, else the size of in), weight
+ * [c_out][c1 + c2][3][3], bias [c_out] -> out [c_out][nv][nu].  NORM_LRELU: in [c1][nv][nu] -> out.  MAXPOOL: in [c1][nv][nu] ->
+ * out [c1][nv / 2][nu / 2].  PREPROCESS: in = low photon [n][nv][nu], in2 = forward projection -> out = the matched forward
+ * projection.  NORMALS: out = z [n][nv][nu] of the options' seed and first_projection. */
+enum { MCGPU_SPEEDUP_STAGE_CONV = 0, MCGPU_SPEEDUP_STAGE_NORM_LRELU = 1, MCGPU_SPEEDUP_STAGE_MAXPOOL = 2, MCGPU_SPEEDUP_STAGE_PREPROCESS = 3,
+       MCGPU_SPEEDUP_STAGE_NORMALS = 4 };
+typedef struct mcgpu_speedup_stage_args {
+  unsigned int struct_size;     /* sizeof(mcgpu_speedup_stage_args); 0 is refused */
+  int upsample;
+  int c1, c2, c_out;
+  const float *in, *in2, *weight, *bias;
+  float *out;
+} mcgpu_speedup_stage_args;
+int mcgpu_speedup_stage(const mcgpu_speedup_options *options, int stage, const mcgpu_speedup_stage_args *args, mcgpu_speedup_report *report);
+
 #ifdef __cplusplus
 }
 #endif
