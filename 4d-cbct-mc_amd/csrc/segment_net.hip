@@ -1,0 +1,866 @@
+// segment_net.hip -- the reference's CT segmentation network (cbctmc/segmentation/segmenter.py: MCSegmenter around a 3-D FlexUNet),
+// inferred patch by patch in float32, stitched and thresholded on the device.
+//
+// The network.  FlexUNet(1 channel, 9 classes, L levels, filters [init, enc_0 .. enc_{L-1}, dec_{L-1} .. dec_0, final]); every
+// convolution 3 x 3 x 3 with ZERO padding and bias (the 2-D sibling of speedup_net.hip pads by replication; this one does not):
+//   out_0 = init_conv(x)                                                     1 -> init, full size, no norm
+//   out_{i+1} = enc_i(out_i), i = 0 .. L-1:  max-pool 2 x 2 x 2, then twice [conv -> instance norm -> LeakyReLU(0.01)]
+//   dec_i, i = L-1 .. 0:  cat([out_i, nearest-upsample x 2 of the running tensor]), then twice [conv -> norm -> LeakyReLU]
+//   final_conv                                                               final -> 9, no norm
+// Instance norm: per channel over the volume, biased variance, eps 1e-5, no affine parameters.
+// The procedure.  The image is rescaled [in_min, in_max] -> [out_min, out_max] and clipped, in float32; where an axis is shorter than
+// the patch it is padded with 0.0 (left = pad / 2).  Patch starts per axis: min(i s, N - P) for i s in range(0, N - P + s + 1, s), all
+// combinations with the last axis fastest.  Per patch: logits -> softmax over channels 0 .. 7, sigmoid on channel 8.  Stitching keeps
+// per voxel the first value k, the float32 sum of (value - k) and the count n; mean = k + sum / n.  Channel 8 becomes mean > 0.5,
+// channels 0 .. 7 the one-hot of their argmax (first maximum wins).  The reference runs the convolutions in float16 under autocast;
+// this is float32 throughout.
+// A start that the rule gives m times is inferred once and stitched m times in a row at its first place in the order: the network is
+// deterministic, so the values are those of the m runs; k is unchanged (the order of first arrivals is), only the order of the float32
+// sum differs from the reference's where patches overlap, and nothing differs where they do not (value - k = 0).
+//
+// Tensors are [C][d0][d1][d2], d2 fastest (the image's x, y, z as torch sees the reference's [x, y, z] array).  All offsets are 64-bit.
+//
+// conv3x3x3_mfma_kernel: an implicit GEMM on v_mfma_f32_32x32x2_f32 (float32 in, float32 accumulate), K = 27 C_in, on the plan of
+//   conv3x3_mfma_kernel in speedup_net.hip.  The MFMA tile is transposed: rows = 32 output channels, columns = 32 voxels along d2, so a
+//   lane's accumulators are one voxel of 16 channels and a store instruction writes 32 consecutive voxels.
+//   The tile: a workgroup of 4 waves owns 2 (d0) x 4 (d1) x 32 (d2) voxels and 32 output channels (more output channels: more
+//   workgroups); a wave owns two d1-neighbours, so one weight read feeds two MFMAs.  K runs in chunks of 8 input channels: the
+//   4 x 6 x 34 halo of the chunk is staged in LDS, positions outside the tensor masked to zero (= zero padding), read from up to two
+//   channel-concatenated sources, the second optionally through the x 2 nearest upsample (>> 1 on all three axes) -- neither the
+//   concatenated nor the upsampled tensor exists in memory.  The global loads of chunk k + 1 go into registers before the MFMAs of
+//   chunk k and to LDS after them.  Weights are packed once per call (pack_weights3d_kernel): per block of 32 output channels and chunk,
+//   [channel pair][tap][channel of the pair][output channel], zero where a channel does not exist.  Input channels past C_in are
+//   staged as zeros, output channels past C_out are not stored.  NO layer takes a VALU kernel: init (1 -> F) and final (F -> 9) run
+//   here with their padding.
+//   Summation: the 54 products of a channel pair (27 taps x 2 channels) run as one fma chain from zero and the pairs are added up
+//   in order.  One chain over all 27 C_in products (864 at 32 channels) put the whole network 2 - 3.2 x the float32 CPU error of torch
+//   away from float64; with the pairs it is below that error (profiles/segment_ab.md).  The cost is 32 v_add_f32 per 54 MFMAs.
+//   Resources (compiler's report, gfx950): 196 VGPRs + 32 AGPRs, no scratch, LDS 53,760 B per workgroup (halo 8 x 816 floats =
+//   26,112 B, weights 216 x 32 floats = 27,648 B): the registers hold 2 waves per SIMD, so 2 workgroups are resident per CU (the
+//   160 KiB of LDS would hold 3).  Tried and rejected: staging the halo as one flat run of 8 x 816 floats over the threads (the
+//   compiler keeps a 64-bit offset and a mask per element across the chunks: 245 VGPRs, 95 spilled SGPRs, 1 wave per SIMD); now a
+//   thread keeps the same 4 halo positions in every channel and one 32-bit offset per position and source.
+//   Rejected without a measurement, on arithmetic alone: 64 output channels per workgroup (the reference has 32 everywhere: half of
+//   every MFMA would multiply zeros); a 2 x 2 x 64 tile (halo 4 x 4 x 66 = 1056 floats per channel against 816 for the same 256
+//   voxels); chunks of 16 channels (107 KB of LDS: one workgroup per CU).
+// stats_kernel + norm_lrelu_kernel: as in speedup_net.hip (float64 sums over fixed segments and a fixed tree, normalised in float64,
+//   rounded once; the same input gives the same bytes), stated again here so that speedup_net.hip's code object stays as it is.
+// maxpool3d_kernel, stage_patch_kernel (reads the image as float32 or int16, rescales, 0.0 outside the image: no padded copy of the
+//   image exists), head_kernel (softmax and sigmoid evaluated in float64, rounded once), stitch_kernel (k, sum, n of the padded volume;
+//   patches run one after the other on one stream: no atomics), mean_kernel, labels_kernel.
+#include <chrono>
+#include <memory>
+
+#include "../../include/mcgpu_amd.h"
+#include "hip_host.hpp"
+
+namespace {
+
+using mcgpu::CallDevice;
+using mcgpu::Stage;
+
+[[noreturn]] void refuse(const char* fn, const std::string& what) { throw mcgpu::Error(-1, std::string("!!ERROR!! ") + fn + ": " + what); }
+
+// ---------------------------------------------------------------------------------------------------------------- convolution
+constexpr int kT0 = 2, kT1 = 4, kT2 = 32;                        // voxels of a workgroup: 4 waves x 2 d1-rows x 32
+constexpr int kCK = 8;                                           // input channels per K chunk
+constexpr int kH0 = kT0 + 2, kH1 = kT1 + 2, kH2 = kT2 + 2;       // the staged tile
+constexpr int kHalo = kH0 * kH1 * kH2;
+constexpr int kTaps = 27;
+constexpr int kKK = kCK * kTaps;                                 // K of a chunk
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+struct ConvArgs {
+  const float* src1;   // [c1][D0][D1][D2]
+  const float* src2;   // [c2][E0][E1][E2] or nullptr
+  int c1, c2, D0, D1, D2, E0, E1, E2, ups;
+  const float* wpack;  // [blocks of 32 output channels][n_chunks][kKK][32]
+  const float* bias;   // [c_out]
+  float* out;          // [c_out][D0][D1][D2]
+  int c_out, n_chunks, nb2;  // nb2: workgroups along d2; blockIdx.x = block along d2 + nb2 * block of output channels
+};
+
+// w [c_out][c_in][3][3][3] -> the staging order of conv3x3x3_mfma_kernel, zero where the channel does not exist
+__global__ __launch_bounds__(256) void pack_weights3d_kernel(const float* w, float* wpack, int c_in, int c_out, int n_chunks, size_t total) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= total) return;
+  const int co_local = (int)(e % 32);
+  size_t r = e / 32;
+  const int kk = (int)(r % kKK);
+  r /= kKK;
+  const int ch = (int)(r % n_chunks), cb = (int)(r / n_chunks);
+  const int hh = kk & 1, tap = (kk >> 1) % kTaps, cp = (kk >> 1) / kTaps;
+  const int ci = ch * kCK + cp * 2 + hh, co = cb * 32 + co_local;
+  wpack[e] = (ci < c_in && co < c_out) ? w[((size_t)co * c_in + ci) * kTaps + tap] : 0.f;
+}
+
+constexpr int kSlots = (kHalo + 255) / 256;                      // halo positions of one channel a thread moves
+constexpr int kStageW = kKK * 32 / 256;                          // floats of the weights a thread moves per chunk
+static_assert(kKK * 32 % 256 == 0, "the weights of a chunk are whole words per thread");
+
+struct Staged {
+  float in[kCK * kSlots];
+  float w[kStageW];
+};
+
+// Where a thread's halo positions lie in a channel of either source (32-bit: a channel has fewer than 2^31 voxels, the host checks),
+// worked out once: the chunks differ only in the channel, which is uniform over the workgroup.
+struct HaloMap {
+  unsigned off1[kSlots], off2[kSlots];
+  unsigned ok;  // bit j: a position of the halo that lies inside the tensor: the others are the zero padding
+};
+
+__device__ __forceinline__ void map_halo(const ConvArgs& a, int tid, int x0, int y0, int z0, HaloMap& m) {
+  m.ok = 0;
+#pragma unroll
+  for (int j = 0; j < kSlots; ++j) {
+    const int r = min(tid + j * 256, kHalo - 1);
+    const int zz = r / (kH1 * kH2), r2 = r - zz * (kH1 * kH2), yy = r2 / kH2, xx = r2 - yy * kH2;
+    const int z = z0 + zz - 1, y = y0 + yy - 1, x = x0 + xx - 1;
+    if (tid + j * 256 < kHalo && z >= 0 && z < a.D0 && y >= 0 && y < a.D1 && x >= 0 && x < a.D2) m.ok |= 1u << j;
+    const int zc = min(max(z, 0), a.D0 - 1), yc = min(max(y, 0), a.D1 - 1), xc = min(max(x, 0), a.D2 - 1);
+    m.off1[j] = ((unsigned)zc * a.D1 + yc) * a.D2 + xc;
+    m.off2[j] = ((unsigned)(zc >> a.ups) * a.E1 + (yc >> a.ups)) * a.E2 + (xc >> a.ups);
+  }
+}
+
+// Every load is unconditional (clamped index, value masked), so that the loads of a chunk go out together.
+__device__ __forceinline__ void load_chunk(const ConvArgs& a, const float* wp, int ch, int tid, const HaloMap& m, Staged& s) {
+  const size_t n1 = ((size_t)a.D0 * a.D1) * a.D2, n2 = ((size_t)a.E0 * a.E1) * a.E2;
+#pragma unroll
+  for (int c = 0; c < kCK; ++c) {
+    const int gc = ch * kCK + c;
+    const bool first = gc < a.c1, any = gc < a.c1 + a.c2;
+    const float* base = first ? a.src1 + (size_t)gc * n1 : any ? a.src2 + (size_t)(gc - a.c1) * n2 : a.src1;  // past the last: any valid address
+    if (first || !any) {  // uniform over the workgroup
+#pragma unroll
+      for (int j = 0; j < kSlots; ++j) s.in[c * kSlots + j] = base[m.off1[j]];
+    } else {
+#pragma unroll
+      for (int j = 0; j < kSlots; ++j) s.in[c * kSlots + j] = base[m.off2[j]];
+    }
+#pragma unroll
+    for (int j = 0; j < kSlots; ++j)
+      if (!(any && (m.ok >> j & 1u))) s.in[c * kSlots + j] = 0.f;
+  }
+  const float* wsrc = wp + (size_t)ch * (kKK * 32);
+#pragma unroll
+  for (int i = 0; i < kStageW; ++i) s.w[i] = wsrc[tid + i * 256];
+}
+
+__device__ __forceinline__ void store_chunk(const Staged& s, int tid, float* s_in, float* s_w) {
+#pragma unroll
+  for (int c = 0; c < kCK; ++c)
+#pragma unroll
+    for (int j = 0; j < kSlots; ++j)
+      if (tid + j * 256 < kHalo) s_in[c * kHalo + tid + j * 256] = s.in[c * kSlots + j];
+#pragma unroll
+  for (int i = 0; i < kStageW; ++i) s_w[tid + i * 256] = s.w[i];
+}
+
+__global__ __launch_bounds__(256) void conv3x3x3_mfma_kernel(ConvArgs a) {
+  __shared__ float s_in[kCK * kHalo];
+  __shared__ float s_w[kKK * 32];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int col = lane & 31, h = lane >> 5;
+  const int xb = (int)(blockIdx.x % (unsigned)a.nb2), cb = (int)(blockIdx.x / (unsigned)a.nb2);
+  const int x0 = xb * kT2, y0 = blockIdx.y * kT1, z0 = blockIdx.z * kT0;
+  const int zl = wave >> 1, yl = (wave & 1) * 2;  // the wave's d0 plane and the first of its two d1 rows
+  f32x16 acc[2];
+#pragma unroll
+  for (int rs = 0; rs < 2; ++rs)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[rs][r] = 0.f;
+  const float* wp = a.wpack + (size_t)cb * a.n_chunks * (kKK * 32);
+  const float* pin = s_in + h * kHalo + (zl * kH1 + yl) * kH2 + col;  // lane half h takes the odd channel of a pair
+  const float* pw = s_w + h * 32 + col;
+  HaloMap hm;
+  map_halo(a, tid, x0, y0, z0, hm);
+  Staged st;
+  load_chunk(a, wp, 0, tid, hm, st);
+  for (int ch = 0; ch < a.n_chunks; ++ch) {
+    store_chunk(st, tid, s_in, s_w);
+    __syncthreads();
+    if (ch + 1 < a.n_chunks) load_chunk(a, wp, ch + 1, tid, hm, st);
+#pragma unroll
+    for (int cp = 0; cp < kCK / 2; ++cp) {
+      f32x16 part[2];  // the 54 products of one channel pair start from zero: chains of 54, not of 27 C_in
+#pragma unroll
+      for (int rs = 0; rs < 2; ++rs)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) part[rs][r] = 0.f;
+#pragma unroll
+      for (int tap = 0; tap < kTaps; ++tap) {
+        const int dz = tap / 9, dy = (tap / 3) % 3, dx = tap % 3;
+        const float b0 = pin[cp * 2 * kHalo + (dz * kH1 + dy) * kH2 + dx];
+        const float b1 = pin[cp * 2 * kHalo + (dz * kH1 + dy + 1) * kH2 + dx];
+        const float wv = pw[(cp * kTaps + tap) * 2 * 32];
+        part[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv, b0, part[0], 0, 0, 0);
+        part[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv, b1, part[1], 0, 0, 0);
+      }
+      acc[0] += part[0];
+      acc[1] += part[1];
+    }
+    __syncthreads();
+  }
+  const int x = x0 + col, z = z0 + zl;
+  if (x >= a.D2 || z >= a.D0) return;
+  float bias[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) bias[r] = a.bias[min(cb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h, a.c_out - 1)];
+#pragma unroll
+  for (int rs = 0; rs < 2; ++rs) {
+    const int y = y0 + yl + rs;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int co = cb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;  // the 32x32 C/D map: row of register r in lane half h
+      if (y < a.D1 && co < a.c_out) a.out[(((size_t)co * a.D0 + z) * a.D1 + y) * a.D2 + x] = acc[rs][r] + bias[r];
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------- instance norm + LeakyReLU
+constexpr int kMaxSegments = 64;
+constexpr size_t kSegmentVoxels = 16384;
+
+int segments_of(size_t n) { return (int)std::min<size_t>(kMaxSegments, (n + kSegmentVoxels - 1) / kSegmentVoxels); }
+
+// part[c][s] = (sum, sum of squares) of segment s of channel c, in float64 and in a fixed order
+__global__ __launch_bounds__(256) void stats3d_kernel(const float* x, size_t n, int S, double2* part) {
+  __shared__ double s_sum[256], s_sq[256];
+  const int c = blockIdx.y, s = blockIdx.x, tid = threadIdx.x;
+  const size_t seg = (n + S - 1) / S, lo = (size_t)s * seg, hi = min(lo + seg, n);
+  const float* p = x + (size_t)c * n;
+  double sum[4] = {0.0, 0.0, 0.0, 0.0}, sq[4] = {0.0, 0.0, 0.0, 0.0};  // four chains: four loads in flight, the order still fixed
+  size_t i = lo + tid;
+  for (; i + 768 < hi; i += 1024) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const double v = p[i + 256 * k];
+      sum[k] += v;
+      sq[k] += v * v;
+    }
+  }
+  for (; i < hi; i += 256) {
+    const double v = p[i];
+    sum[0] += v;
+    sq[0] += v * v;
+  }
+  s_sum[tid] = (sum[0] + sum[1]) + (sum[2] + sum[3]);
+  s_sq[tid] = (sq[0] + sq[1]) + (sq[2] + sq[3]);
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) {
+      s_sum[tid] += s_sum[tid + w];
+      s_sq[tid] += s_sq[tid + w];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) part[(size_t)c * S + s] = make_double2(s_sum[0], s_sq[0]);
+}
+
+__global__ __launch_bounds__(256) void norm_lrelu3d_kernel(const float* x, float* y, size_t n, int S, const double2* part) {
+  __shared__ double s_mean, s_rstd;
+  const int c = blockIdx.y;
+  if (threadIdx.x == 0) {
+    double sum = 0.0, sq = 0.0;
+    for (int s = 0; s < S; ++s) {
+      sum += part[(size_t)c * S + s].x;
+      sq += part[(size_t)c * S + s].y;
+    }
+    const double m = sum / (double)n, var = fmax(sq / (double)n - m * m, 0.0);
+    s_mean = m;
+    s_rstd = 1.0 / sqrt(var + 1e-5);
+  }
+  __syncthreads();
+  const double m = s_mean, rstd = s_rstd;
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float v = (float)(((double)x[(size_t)c * n + i] - m) * rstd);
+  y[(size_t)c * n + i] = v > 0.f ? v : 0.01f * v;
+}
+
+// ------------------------------------------------------------------------------------------------------------- small kernels
+__global__ __launch_bounds__(256) void maxpool3d_kernel(const float* x, float* y, int C, int D0, int D1, int D2) {
+  const int O0 = D0 >> 1, O1 = D1 >> 1, O2 = D2 >> 1;
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)C * O0 * O1 * O2) return;
+  const int xo = (int)(i % O2), yo = (int)((i / O2) % O1);
+  const size_t cz = i / ((size_t)O2 * O1);
+  const int zo = (int)(cz % O0), c = (int)(cz / O0);
+  const float* p = x + (((size_t)c * D0 + 2 * zo) * D1 + 2 * yo) * D2 + 2 * xo;
+  const size_t sy = (size_t)D2, sz = (size_t)D1 * D2;
+  const float a = fmaxf(fmaxf(p[0], p[1]), fmaxf(p[sy], p[sy + 1]));
+  const float b = fmaxf(fmaxf(p[sz], p[sz + 1]), fmaxf(p[sz + sy], p[sz + sy + 1]));
+  y[i] = fmaxf(a, b);
+}
+
+struct Rescale { float in_min, in_span, out_min, out_span, out_max; int on; };  // on = 0: the ranges are equal, values pass
+
+// patch [P0][P1][P2] at `start` of the padded volume = the rescaled image where it exists (padded position - left), else 0.0
+template <class T>
+__global__ __launch_bounds__(256) void stage_patch_kernel(const T* image, int N0, int N1, int N2, int l0, int l1, int l2, int s0, int s1, int s2, int P0,
+                                                          int P1, int P2, Rescale r, float* out) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)P0 * P1 * P2) return;
+  const int x = (int)(i % P2) + s2 - l2, y = (int)((i / P2) % P1) + s1 - l1, z = (int)(i / ((size_t)P2 * P1)) + s0 - l0;
+  float v = 0.f;
+  if (z >= 0 && z < N0 && y >= 0 && y < N1 && x >= 0 && x < N2) {
+    v = (float)image[((size_t)z * N1 + y) * N2 + x];
+    if (r.on) {
+      v = ((v - r.in_min) * r.out_span) / r.in_span + r.out_min;
+      v = fminf(fmaxf(v, r.out_min), r.out_max);
+    }
+  }
+  out[i] = v;
+}
+
+// logits [9][n] -> softmax over channels 0 .. 7 and sigmoid of channel 8, evaluated in float64 and rounded once
+__global__ __launch_bounds__(256) void head_kernel(const float* logits, float* prob, size_t n) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  double v[8], m = -INFINITY, sum = 0.0;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    v[c] = (double)logits[(size_t)c * n + i];
+    m = fmax(m, v[c]);
+  }
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    v[c] = exp(v[c] - m);
+    sum += v[c];
+  }
+#pragma unroll
+  for (int c = 0; c < 8; ++c) prob[(size_t)c * n + i] = (float)(v[c] / sum);
+  prob[8 * n + i] = (float)(1.0 / (1.0 + exp(-(double)logits[8 * n + i])));
+}
+
+// `times` additions of one patch [C][P0][P1][P2] at `start` into (k, sum) [C][V0][V1][V2] and count [V0][V1][V2]
+__global__ __launch_bounds__(256) void stitch_kernel(const float* patch, int C, int P0, int P1, int P2, int s0, int s1, int s2, int V0, int V1, int V2,
+                                                     int times, float* k, float* sum, unsigned* count) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, np = (size_t)P0 * P1 * P2, nv = (size_t)V0 * V1 * V2;
+  if (i >= np) return;
+  const int x = (int)(i % P2) + s2, y = (int)((i / P2) % P1) + s1, z = (int)(i / ((size_t)P2 * P1)) + s0;
+  const size_t g = ((size_t)z * V1 + y) * V2 + x;
+  const unsigned have = count[g];
+  for (int c = 0; c < C; ++c) {
+    const float d = patch[(size_t)c * np + i];
+    const size_t gc = (size_t)c * nv + g;
+    const float first = have ? k[gc] : d;
+    if (!have) k[gc] = d;
+    float s = sum[gc];
+    const float diff = d - first;
+    for (int t = 0; t < times; ++t) s += diff;
+    sum[gc] = s;
+  }
+  count[g] = have + (unsigned)times;
+}
+
+// mean = k + sum / n (0 where nothing arrived), written over sum
+__global__ __launch_bounds__(256) void mean_kernel(const float* k, float* sum, const unsigned* count, int C, size_t nv) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nv) return;
+  const unsigned n = count[i];
+  for (int c = 0; c < C; ++c) {
+    const size_t g = (size_t)c * nv + i;
+    sum[g] = n ? k[g] + sum[g] / (float)n : 0.f;
+  }
+}
+
+// mean [9][nv] -> labels: one-hot of the argmax of channels 0 .. 7 (first maximum wins), channel 8 > 0.5
+__global__ __launch_bounds__(256) void labels_kernel(const float* mean, unsigned char* labels, size_t nv) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nv) return;
+  int best = 0;
+  float top = mean[i];
+  for (int c = 1; c < 8; ++c) {
+    const float v = mean[(size_t)c * nv + i];
+    if (v > top) {
+      top = v;
+      best = c;
+    }
+  }
+  for (int c = 0; c < 8; ++c) labels[(size_t)c * nv + i] = c == best ? 1 : 0;
+  labels[8 * nv + i] = mean[8 * nv + i] > 0.5f ? 1 : 0;
+}
+
+unsigned blocks_of(size_t n) { return (unsigned)((n + 255) / 256); }
+
+// -------------------------------------------------------------------------------------------------------------------- host
+struct Dims {
+  int d[3];
+  size_t voxels() const { return (size_t)d[0] * d[1] * d[2]; }
+  Dims shifted(int s) const { return {{d[0] >> s, d[1] >> s, d[2] >> s}}; }
+  Dims halved_up() const { return {{(d[0] + 1) / 2, (d[1] + 1) / 2, (d[2] + 1) / 2}}; }
+};
+
+struct ConvLayer {
+  int c_in = 0, c_out = 0;
+  size_t w_off = 0, b_off = 0;  // in the flat weights
+  int n_chunks = 0;
+  float* wpack = nullptr;
+  const float* bias = nullptr;
+  size_t pack_floats() const { return (size_t)((c_out + 31) / 32) * n_chunks * kKK * 32; }
+};
+
+ConvLayer conv_layer(int c_in, int c_out, size_t& cursor) {
+  ConvLayer l;
+  l.c_in = c_in;
+  l.c_out = c_out;
+  l.w_off = cursor;
+  cursor += (size_t)c_out * c_in * kTaps;
+  l.b_off = cursor;
+  cursor += (size_t)c_out;
+  l.n_chunks = (c_in + kCK - 1) / kCK;
+  return l;
+}
+
+// the convolutions in the state dict's order: init, final, enc_0 .. enc_{L-1}, dec_{L-1} .. dec_0
+struct NetLayers {
+  int L;
+  std::vector<int> skip_c;  // channels of out_0 .. out_L
+  std::vector<int> dec_c;   // channels of dec_i's output, by level
+  ConvLayer init, final;
+  std::vector<ConvLayer> enc, dec;  // [2 i], [2 i + 1] of level i
+  NetLayers(int levels, const int* f, int n_classes, size_t& cursor) : L(levels), skip_c(levels + 1), dec_c(levels), enc(2 * levels), dec(2 * levels) {
+    skip_c[0] = f[0];
+    for (int i = 0; i < L; ++i) skip_c[i + 1] = f[1 + i];
+    for (int j = 0; j < L; ++j) dec_c[L - 1 - j] = f[1 + L + j];
+    init = conv_layer(1, f[0], cursor);
+    final = conv_layer(f[2 * L + 1], n_classes, cursor);
+    for (int i = 0; i < L; ++i) {
+      enc[2 * i] = conv_layer(skip_c[i], skip_c[i + 1], cursor);
+      enc[2 * i + 1] = conv_layer(skip_c[i + 1], skip_c[i + 1], cursor);
+    }
+    for (int i = L - 1; i >= 0; --i) {
+      const int below = i == L - 1 ? skip_c[L] : dec_c[i + 1];
+      dec[2 * i] = conv_layer(skip_c[i] + below, dec_c[i], cursor);
+      dec[2 * i + 1] = conv_layer(dec_c[i], dec_c[i], cursor);
+    }
+  }
+  template <class F>
+  void each(F f) {
+    f(init);
+    f(final);
+    for (auto& l : enc) f(l);
+    for (auto& l : dec) f(l);
+  }
+  int widest() const {
+    int w = 1;
+    for (int c : skip_c) w = std::max(w, c);
+    for (int c : dec_c) w = std::max(w, c);
+    return w;
+  }
+};
+
+// Launches and buffers of one call.  With `dry` nothing touches the device: alloc() only adds up what the call would hold.
+struct Runner {
+  CallDevice dev;
+  mcgpu_segment_report rep;
+  bool dry = false;
+  size_t planned = 0;
+  double2* d_part = nullptr;
+
+  Runner() { memset(&rep, 0, sizeof rep); }
+  void init(int device, int channels) {
+    if (!dry) {
+      HIP_TRY(hipSetDevice(device));
+      dev.events();
+    }
+    d_part = (double2*)alloc_bytes((size_t)std::max(channels, 1) * kMaxSegments * sizeof(double2), true);
+  }
+  void* alloc_bytes(size_t bytes, bool zero) {
+    bytes = std::max<size_t>(bytes, 4);
+    if (dry) {
+      planned += bytes;
+      return nullptr;
+    }
+    return zero ? dev.alloc_zeroed<char>(bytes) : dev.alloc<char>(bytes);
+  }
+  float* alloc(size_t floats) { return (float*)alloc_bytes(floats * sizeof(float), true); }
+  template <class T>
+  T* upload(const T* host, size_t n) {
+    T* p = (T*)alloc_bytes(n * sizeof(T), false);
+    if (!dry) HIP_TRY(hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice));
+    return p;
+  }
+
+  void pack(ConvLayer& l, const float* d_weights) {
+    const size_t total = l.pack_floats();
+    l.wpack = (float*)alloc_bytes(total * sizeof(float), false);
+    if (dry) return;
+    l.bias = d_weights + l.b_off;
+    hipLaunchKernelGGL(pack_weights3d_kernel, dim3(blocks_of(total)), dim3(256), 0, nullptr, d_weights + l.w_off, l.wpack, l.c_in, l.c_out, l.n_chunks, total);
+  }
+
+  // out [c_out][D] = conv(cat(src1 [c1], src2 [c_in - c1] (upsampled when ups))) + bias
+  void conv(const ConvLayer& l, const float* src1, int c1, const float* src2, int ups, const Dims& D, float* out) {
+    Stage st(dev, rep.ms_conv);
+    const Dims E = ups ? D.halved_up() : D;
+    ConvArgs a;
+    a.src1 = src1; a.src2 = src2; a.c1 = c1; a.c2 = l.c_in - c1; a.ups = ups ? 1 : 0;
+    a.D0 = D.d[0]; a.D1 = D.d[1]; a.D2 = D.d[2]; a.E0 = E.d[0]; a.E1 = E.d[1]; a.E2 = E.d[2];
+    a.wpack = l.wpack; a.bias = l.bias; a.out = out; a.c_out = l.c_out; a.n_chunks = l.n_chunks;
+    a.nb2 = (D.d[2] + kT2 - 1) / kT2;
+    const dim3 grid((unsigned)a.nb2 * (unsigned)((l.c_out + 31) / 32), (unsigned)((D.d[1] + kT1 - 1) / kT1), (unsigned)((D.d[0] + kT0 - 1) / kT0));
+    hipLaunchKernelGGL(conv3x3x3_mfma_kernel, grid, dim3(256), 0, nullptr, a);
+    st.done();
+  }
+  void norm_lrelu(const float* x, float* y, int C, size_t n) {
+    Stage st(dev, rep.ms_norm);
+    const int S = segments_of(n);
+    hipLaunchKernelGGL(stats3d_kernel, dim3((unsigned)S, (unsigned)C), dim3(256), 0, nullptr, x, n, S, d_part);
+    hipLaunchKernelGGL(norm_lrelu3d_kernel, dim3(blocks_of(n), (unsigned)C), dim3(256), 0, nullptr, x, y, n, S, d_part);
+    st.done();
+  }
+  void maxpool(const float* x, float* y, int C, const Dims& D) {
+    Stage st(dev, rep.ms_other);
+    const size_t n = (size_t)C * D.shifted(1).voxels();
+    if (n) hipLaunchKernelGGL(maxpool3d_kernel, dim3(blocks_of(n)), dim3(256), 0, nullptr, x, y, C, D.d[0], D.d[1], D.d[2]);
+    st.done();
+  }
+  void head(const float* logits, float* prob, size_t n) {
+    Stage st(dev, rep.ms_other);
+    hipLaunchKernelGGL(head_kernel, dim3(blocks_of(n)), dim3(256), 0, nullptr, logits, prob, n);
+    st.done();
+  }
+  void stitch(const float* patch, int C, const Dims& P, const int* start, const Dims& V, int times, float* k, float* sum, unsigned* count) {
+    Stage st(dev, rep.ms_other);
+    hipLaunchKernelGGL(stitch_kernel, dim3(blocks_of(P.voxels())), dim3(256), 0, nullptr, patch, C, P.d[0], P.d[1], P.d[2], start[0], start[1], start[2],
+                       V.d[0], V.d[1], V.d[2], times, k, sum, count);
+    st.done();
+  }
+  void mean(const float* k, float* sum, const unsigned* count, int C, size_t nv) {
+    Stage st(dev, rep.ms_other);
+    hipLaunchKernelGGL(mean_kernel, dim3(blocks_of(nv)), dim3(256), 0, nullptr, k, sum, count, C, nv);
+    st.done();
+  }
+  void labels(const float* mean, unsigned char* out, size_t nv) {
+    Stage st(dev, rep.ms_other);
+    hipLaunchKernelGGL(labels_kernel, dim3(blocks_of(nv)), dim3(256), 0, nullptr, mean, out, nv);
+    st.done();
+  }
+};
+
+// The network at one patch shape: its buffers, made once, and the launches of a forward pass
+struct NetPass {
+  NetLayers& net;
+  Runner& run;
+  Dims P;
+  std::vector<float*> skip, pooled, enc_a, dec_a, dec_b;
+  float* out = nullptr;
+  NetPass(NetLayers& n, Runner& r, const Dims& p) : net(n), run(r), P(p) {
+    const int L = net.L;
+    skip.resize(L + 1); pooled.resize(L); enc_a.resize(L); dec_a.resize(L); dec_b.resize(L);
+    skip[0] = run.alloc((size_t)net.skip_c[0] * P.voxels());
+    for (int i = 0; i < L; ++i) {
+      const size_t below = P.shifted(i + 1).voxels(), here = P.shifted(i).voxels();
+      pooled[i] = run.alloc((size_t)net.skip_c[i] * below);
+      enc_a[i] = run.alloc((size_t)net.skip_c[i + 1] * below);
+      skip[i + 1] = run.alloc((size_t)net.skip_c[i + 1] * below);
+      dec_a[i] = run.alloc((size_t)net.dec_c[i] * here);
+      dec_b[i] = run.alloc((size_t)net.dec_c[i] * here);
+    }
+    out = run.alloc((size_t)net.final.c_out * P.voxels());
+  }
+  const float* forward(const float* x) {
+    const int L = net.L;
+    run.conv(net.init, x, 1, nullptr, 0, P, skip[0]);
+    for (int i = 0; i < L; ++i) {
+      const Dims D = P.shifted(i + 1);
+      const int c = net.skip_c[i + 1];
+      run.maxpool(skip[i], pooled[i], net.skip_c[i], P.shifted(i));
+      run.conv(net.enc[2 * i], pooled[i], net.skip_c[i], nullptr, 0, D, enc_a[i]);
+      run.norm_lrelu(enc_a[i], enc_a[i], c, D.voxels());
+      run.conv(net.enc[2 * i + 1], enc_a[i], c, nullptr, 0, D, skip[i + 1]);
+      run.norm_lrelu(skip[i + 1], skip[i + 1], c, D.voxels());
+    }
+    const float* cur = skip[L];
+    for (int i = L - 1; i >= 0; --i) {
+      const Dims D = P.shifted(i);
+      const int c = net.dec_c[i];
+      run.conv(net.dec[2 * i], skip[i], net.skip_c[i], cur, 1, D, dec_a[i]);
+      run.norm_lrelu(dec_a[i], dec_a[i], c, D.voxels());
+      run.conv(net.dec[2 * i + 1], dec_a[i], c, nullptr, 0, D, dec_b[i]);
+      run.norm_lrelu(dec_b[i], dec_b[i], c, D.voxels());
+      cur = dec_b[i];
+    }
+    run.conv(net.final, cur, net.final.c_in, nullptr, 0, P, out);
+    return out;
+  }
+};
+
+constexpr int kMaxLevels = 8;
+constexpr int kClasses = 9;
+
+struct Patch { int start[3]; int times; };
+
+std::string triple(const int* v) { return std::to_string(v[0]) + " x " + std::to_string(v[1]) + " x " + std::to_string(v[2]); }
+
+// everything mcgpu_segment_run refuses from its arguments alone; fills the padded shape, the left pads and the patches in their order
+void check_run(const mcgpu_segment_options& o, const void* image, const unsigned char* labels, Dims& V, int* left, std::vector<Patch>& patches,
+               size_t& n_rule) {
+  const char* fn = "mcgpu_segment_run";
+  if (!image) refuse(fn, "image is NULL");
+  if (!labels) refuse(fn, "labels is NULL");
+  if (!o.weights) refuse(fn, "weights is NULL");
+  if (o.image_type != MCGPU_IMAGE_INT16 && o.image_type != MCGPU_IMAGE_FLOAT32) refuse(fn, "image_type " + std::to_string(o.image_type) + ": MCGPU_IMAGE_INT16 or MCGPU_IMAGE_FLOAT32");
+  for (int a = 0; a < 3; ++a)
+    if (o.shape[a] < 1 || o.patch_shape[a] < 1) refuse(fn, "shape and patch_shape must be >= 1: " + triple(o.shape) + ", " + triple(o.patch_shape));
+  if (o.levels < 1 || o.levels > kMaxLevels) refuse(fn, "levels is " + std::to_string(o.levels) + ", expected 1.." + std::to_string(kMaxLevels));
+  const int L = o.levels;
+  for (int i = 0; i < 2 * L + 2; ++i)
+    if (o.n_filters[i] < 1 || o.n_filters[i] > 65535) refuse(fn, "n_filters[" + std::to_string(i) + "] is " + std::to_string(o.n_filters[i]) + ", expected 1..65535");
+  if (o.n_classes != kClasses)
+    refuse(fn, "the final convolution has " + std::to_string(o.n_classes) + " outputs, expected 9 (8 softmax labels and the lung vessels)");
+  if (o.n_filters[2 * L + 1] != o.n_filters[2 * L])
+    refuse(fn, "inconsistent weight shapes: final_conv takes " + std::to_string(o.n_filters[2 * L + 1]) + " channels but dec_0 gives " + std::to_string(o.n_filters[2 * L]));
+  size_t expect = 0;
+  NetLayers(L, o.n_filters, o.n_classes, expect);
+  if (o.n_weights != expect)
+    refuse(fn, "inconsistent weight shapes: n_weights is " + std::to_string(o.n_weights) + " but the architecture has " + std::to_string(expect) + " values");
+  for (int a = 0; a < 3; ++a)
+    if (o.patch_shape[a] % (1 << L))
+      refuse(fn, "patch axis " + std::to_string(a) + " is " + std::to_string(o.patch_shape[a]) + ", not divisible by " + std::to_string(1 << L) + " (2^levels)");
+  if (o.patch_shape[0] > 2 * 65535 || o.patch_shape[1] > 4 * 65535 || ((size_t)o.patch_shape[0] * o.patch_shape[1]) * o.patch_shape[2] > 0x7fffffffull)
+    refuse(fn, "a patch of " + triple(o.patch_shape) + " is too large: at most 2^31 - 1 voxels");
+  if (((size_t)(o.patch_shape[0] >> L) * (o.patch_shape[1] >> L)) * (o.patch_shape[2] >> L) < 2)
+    refuse(fn, "the bottleneck of a " + triple(o.patch_shape) + " patch has fewer than 2 voxels: instance norm is undefined");
+  int stride[3];
+  for (int a = 0; a < 3; ++a) {
+    const double s = (1.0 - o.patch_overlap) * o.patch_shape[a];
+    if (!(s >= 1.0) || s != std::floor(s) || s > 2147483647.0)
+      refuse(fn, "patch_overlap " + std::to_string(o.patch_overlap) + " gives a stride of " + std::to_string(s) + " on patch axis " + std::to_string(a) +
+                     " (" + std::to_string(o.patch_shape[a]) + "): a whole number >= 1 is needed (the reference truncates silently)");
+    stride[a] = (int)s;
+  }
+  if (o.in_max == o.in_min && !(o.in_min == o.out_min && o.in_max == o.out_max)) refuse(fn, "input_value_range is empty");
+  std::vector<int> starts[3];
+  for (int a = 0; a < 3; ++a) {
+    V.d[a] = std::max(o.shape[a], o.patch_shape[a]);
+    left[a] = (V.d[a] - o.shape[a]) / 2;
+    const long long top = (long long)V.d[a] - o.patch_shape[a];
+    for (long long v = 0; v < top + stride[a] + 1; v += stride[a]) starts[a].push_back((int)std::min(v, top));
+  }
+  if (V.voxels() > 0x7fffffffull * 64) refuse(fn, "the padded volume " + triple(V.d) + " is too large");
+  n_rule = 0;
+  for (int i : starts[0])
+    for (int j : starts[1])
+      for (int k : starts[2]) {
+        ++n_rule;
+        bool seen = false;
+        for (auto& p : patches)
+          if (p.start[0] == i && p.start[1] == j && p.start[2] == k) {
+            ++p.times;
+            seen = true;
+            break;
+          }
+        if (!seen) patches.push_back({{i, j, k}, 1});
+      }
+}
+
+size_t image_bytes(const mcgpu_segment_options& o) {
+  return ((size_t)o.shape[0] * o.shape[1]) * o.shape[2] * (o.image_type == MCGPU_IMAGE_INT16 ? 2 : 4);
+}
+
+struct RunBuffers {
+  const void* d_image = nullptr;
+  const float* d_weights = nullptr;
+  float *d_x = nullptr, *d_prob = nullptr, *d_k = nullptr, *d_sum = nullptr;
+  unsigned* d_count = nullptr;
+  unsigned char* d_labels = nullptr;
+};
+
+// every buffer of a run, in one place: made on the device, or (Runner::dry) only added up
+void make_buffers(Runner& R, const mcgpu_segment_options& o, const void* image, NetLayers& net, const Dims& P, const Dims& V, RunBuffers& b,
+                  std::unique_ptr<NetPass>& pass) {
+  R.init(o.device, net.widest());
+  b.d_weights = R.upload(o.weights, (size_t)o.n_weights);
+  net.each([&](ConvLayer& l) { R.pack(l, b.d_weights); });
+  b.d_image = R.upload((const char*)image, image_bytes(o));
+  b.d_x = R.alloc(P.voxels());
+  pass.reset(new NetPass(net, R, P));
+  b.d_prob = R.alloc((size_t)kClasses * P.voxels());
+  b.d_k = R.alloc((size_t)kClasses * V.voxels());
+  b.d_sum = R.alloc((size_t)kClasses * V.voxels());
+  b.d_count = (unsigned*)R.alloc_bytes(V.voxels() * sizeof(unsigned), true);
+  b.d_labels = (unsigned char*)R.alloc_bytes((size_t)kClasses * V.voxels(), true);
+}
+
+void finish(Runner& R, const std::chrono::steady_clock::time_point& t0, mcgpu_segment_report* report) {
+  R.rep.peak_device_bytes = R.dev.peak;
+  R.rep.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (report) *report = R.rep;
+}
+
+}  // namespace
+
+extern "C" int mcgpu_segment_run(const mcgpu_segment_options* caller_o, const void* image, unsigned char* labels, float* raw, mcgpu_segment_report* report) {
+  ABI_BEGIN
+  const char* fn = "mcgpu_segment_run";
+  mcgpu_segment_options o;
+  mcgpu::read_options(fn, "mcgpu_segment_options", caller_o, o);
+  Dims V, P{{o.patch_shape[0], o.patch_shape[1], o.patch_shape[2]}};
+  int left[3];
+  std::vector<Patch> patches;
+  size_t n_rule = 0;
+  check_run(o, image, labels, V, left, patches, n_rule);
+  const auto t0 = std::chrono::steady_clock::now();
+  size_t cursor = 0;
+  NetLayers net(o.levels, o.n_filters, o.n_classes, cursor);
+  size_t needed = 0;
+  {
+    Runner plan;
+    plan.dry = true;
+    RunBuffers b;
+    std::unique_ptr<NetPass> pass;
+    make_buffers(plan, o, image, net, P, V, b, pass);
+    needed = plan.planned;
+  }
+  if (o.memory_limit_bytes && needed > o.memory_limit_bytes)
+    refuse(fn, "the call needs " + std::to_string(needed) + " bytes of device memory, above the limit of " + std::to_string(o.memory_limit_bytes));
+  Runner R;
+  HIP_TRY(hipSetDevice(o.device));
+  size_t free_bytes = 0, total_bytes = 0;
+  HIP_TRY(hipMemGetInfo(&free_bytes, &total_bytes));
+  if (needed > free_bytes)
+    refuse(fn, "the call needs " + std::to_string(needed) + " bytes of device memory, the device has " + std::to_string(free_bytes) + " free");
+  RunBuffers b;
+  std::unique_ptr<NetPass> pass;
+  {
+    const auto u0 = std::chrono::steady_clock::now();
+    make_buffers(R, o, image, net, P, V, b, pass);
+    HIP_TRY(hipDeviceSynchronize());
+    R.rep.ms_upload += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
+  }
+  Rescale rs;
+  rs.in_min = (float)o.in_min; rs.in_span = (float)(o.in_max - o.in_min); rs.out_min = (float)o.out_min; rs.out_span = (float)(o.out_max - o.out_min);
+  rs.out_max = (float)o.out_max;
+  rs.on = !(o.in_min == o.out_min && o.in_max == o.out_max);
+  for (const Patch& p : patches) {
+    {
+      Stage st(R.dev, R.rep.ms_other);
+      const dim3 grid(blocks_of(P.voxels()));
+      if (o.image_type == MCGPU_IMAGE_INT16)
+        hipLaunchKernelGGL(stage_patch_kernel<short>, grid, dim3(256), 0, nullptr, (const short*)b.d_image, o.shape[0], o.shape[1], o.shape[2], left[0], left[1],
+                           left[2], p.start[0], p.start[1], p.start[2], P.d[0], P.d[1], P.d[2], rs, b.d_x);
+      else
+        hipLaunchKernelGGL(stage_patch_kernel<float>, grid, dim3(256), 0, nullptr, (const float*)b.d_image, o.shape[0], o.shape[1], o.shape[2], left[0], left[1],
+                           left[2], p.start[0], p.start[1], p.start[2], P.d[0], P.d[1], P.d[2], rs, b.d_x);
+      st.done();
+    }
+    const float* logits = pass->forward(b.d_x);
+    R.head(logits, b.d_prob, P.voxels());
+    R.stitch(b.d_prob, kClasses, P, p.start, V, p.times, b.d_k, b.d_sum, b.d_count);
+  }
+  R.mean(b.d_k, b.d_sum, b.d_count, kClasses, V.voxels());
+  R.labels(b.d_sum, b.d_labels, V.voxels());
+  {
+    Stage st(R.dev, R.rep.ms_upload);
+    HIP_TRY(hipMemcpy(labels, b.d_labels, (size_t)kClasses * V.voxels(), hipMemcpyDeviceToHost));
+    if (raw) HIP_TRY(hipMemcpy(raw, b.d_sum, (size_t)kClasses * V.voxels() * 4, hipMemcpyDeviceToHost));
+    st.done();
+  }
+  R.rep.patches_run = (unsigned long long)patches.size();
+  R.rep.patches_skipped = (unsigned long long)(n_rule - patches.size());
+  R.rep.planned_device_bytes = needed;
+  finish(R, t0, report);
+  return 0;
+  ABI_END
+}
+
+extern "C" int mcgpu_segment_stage(const mcgpu_segment_options* caller_o, int stage, const mcgpu_segment_stage_args* caller_a, mcgpu_segment_report* report) {
+  ABI_BEGIN
+  const char* fn = "mcgpu_segment_stage";
+  mcgpu_segment_options o;
+  mcgpu::read_options(fn, "mcgpu_segment_options", caller_o, o);
+  mcgpu_segment_stage_args a;
+  mcgpu::read_options(fn, "mcgpu_segment_stage_args", caller_a, a);
+  if (stage < MCGPU_SEGMENT_STAGE_CONV || stage > MCGPU_SEGMENT_STAGE_FINALIZE) refuse(fn, "unknown stage " + std::to_string(stage));
+  if (!a.out) refuse(fn, "out is NULL");
+  if (!a.in) refuse(fn, "in is NULL");
+  for (int i = 0; i < 3; ++i)
+    if (a.shape[i] < 1) refuse(fn, "shape must be >= 1: " + triple(a.shape));
+  const Dims D{{a.shape[0], a.shape[1], a.shape[2]}};
+  const size_t n = D.voxels();
+  if ((size_t)((D.d[0] + kT0 - 1) / kT0) > 65535 || (size_t)((D.d[1] + kT1 - 1) / kT1) > 65535 || n > 0x7fffffffull)
+    refuse(fn, "shape " + triple(a.shape) + " is too large: at most 2^31 - 1 voxels");
+  if (stage <= MCGPU_SEGMENT_STAGE_MAXPOOL || stage == MCGPU_SEGMENT_STAGE_STITCH)
+    if (a.c1 < 1 || a.c1 > 65535) refuse(fn, "c1 must be 1..65535");
+  if (stage == MCGPU_SEGMENT_STAGE_CONV) {
+    if (a.c2 < 0 || a.c2 > 65535 || a.c_out < 1 || a.c_out > 65535) refuse(fn, "c2 must be 0..65535 and c_out 1..65535");
+    if (!a.weight || !a.bias) refuse(fn, "weight or bias is NULL");
+    if (a.c2 > 0 && !a.in2) refuse(fn, "in2 is NULL");
+  }
+  if (stage == MCGPU_SEGMENT_STAGE_NORM_LRELU && n < 2) refuse(fn, "instance norm needs at least 2 voxels");
+  if (stage == MCGPU_SEGMENT_STAGE_STITCH) {
+    if (a.n_patches < 1 || !a.starts) refuse(fn, "n_patches must be >= 1 and starts given");
+    for (int p = 0; p < a.n_patches; ++p)
+      for (int i = 0; i < 3; ++i)
+        if (a.patch_shape[i] < 1 || a.starts[3 * p + i] < 0 || a.starts[3 * p + i] + a.patch_shape[i] > a.shape[i])
+          refuse(fn, "patch " + std::to_string(p) + " at " + triple(a.starts + 3 * p) + " of shape " + triple(a.patch_shape) + " leaves the volume " + triple(a.shape));
+  }
+  const auto t0 = std::chrono::steady_clock::now();
+  Runner R;
+  R.init(o.device, stage == MCGPU_SEGMENT_STAGE_NORM_LRELU ? a.c1 : 1);
+  switch (stage) {
+    case MCGPU_SEGMENT_STAGE_CONV: {
+      const Dims E = a.upsample ? D.halved_up() : D;
+      size_t cursor = 0;
+      ConvLayer l = conv_layer(a.c1 + a.c2, a.c_out, cursor);
+      std::vector<float> flat(cursor);
+      memcpy(flat.data() + l.w_off, a.weight, (size_t)l.c_out * l.c_in * kTaps * sizeof(float));
+      memcpy(flat.data() + l.b_off, a.bias, (size_t)l.c_out * sizeof(float));
+      const float* d_weights = R.upload(flat.data(), flat.size());
+      R.pack(l, d_weights);
+      const float* d_in = R.upload(a.in, (size_t)a.c1 * n);
+      const float* d_in2 = a.c2 ? R.upload(a.in2, (size_t)a.c2 * E.voxels()) : nullptr;
+      float* d_out = R.alloc((size_t)a.c_out * n);
+      R.conv(l, d_in, a.c1, d_in2, a.upsample, D, d_out);
+      HIP_TRY(hipMemcpy(a.out, d_out, (size_t)a.c_out * n * 4, hipMemcpyDeviceToHost));
+      break;
+    }
+    case MCGPU_SEGMENT_STAGE_NORM_LRELU: {
+      const float* d_in = R.upload(a.in, (size_t)a.c1 * n);
+      float* d_out = R.alloc((size_t)a.c1 * n);
+      R.norm_lrelu(d_in, d_out, a.c1, n);
+      HIP_TRY(hipMemcpy(a.out, d_out, (size_t)a.c1 * n * 4, hipMemcpyDeviceToHost));
+      break;
+    }
+    case MCGPU_SEGMENT_STAGE_MAXPOOL: {
+      const size_t n_out = (size_t)a.c1 * D.shifted(1).voxels();
+      const float* d_in = R.upload(a.in, (size_t)a.c1 * n);
+      float* d_out = R.alloc(n_out);
+      R.maxpool(d_in, d_out, a.c1, D);
+      if (n_out) HIP_TRY(hipMemcpy(a.out, d_out, n_out * 4, hipMemcpyDeviceToHost));
+      break;
+    }
+    case MCGPU_SEGMENT_STAGE_HEAD: {
+      const float* d_in = R.upload(a.in, (size_t)kClasses * n);
+      float* d_out = R.alloc((size_t)kClasses * n);
+      R.head(d_in, d_out, n);
+      HIP_TRY(hipMemcpy(a.out, d_out, (size_t)kClasses * n * 4, hipMemcpyDeviceToHost));
+      break;
+    }
+    case MCGPU_SEGMENT_STAGE_STITCH: {
+      const Dims P{{a.patch_shape[0], a.patch_shape[1], a.patch_shape[2]}};
+      const size_t per = (size_t)a.c1 * P.voxels();
+      const float* d_in = R.upload(a.in, per * a.n_patches);
+      float *d_k = R.alloc((size_t)a.c1 * n), *d_sum = R.alloc((size_t)a.c1 * n);
+      unsigned* d_count = (unsigned*)R.alloc_bytes(n * sizeof(unsigned), true);
+      for (int p = 0; p < a.n_patches; ++p) R.stitch(d_in + per * p, a.c1, P, a.starts + 3 * p, D, 1, d_k, d_sum, d_count);
+      R.mean(d_k, d_sum, d_count, a.c1, n);
+      HIP_TRY(hipMemcpy(a.out, d_sum, (size_t)a.c1 * n * 4, hipMemcpyDeviceToHost));
+      break;
+    }
+    default: {
+      const float* d_in = R.upload(a.in, (size_t)kClasses * n);
+      unsigned char* d_out = (unsigned char*)R.alloc_bytes((size_t)kClasses * n, true);
+      R.labels(d_in, d_out, n);
+      HIP_TRY(hipMemcpy(a.out, d_out, (size_t)kClasses * n, hipMemcpyDeviceToHost));
+    }
+  }
+  finish(R, t0, report);
+  return 0;
+  ABI_END
+}

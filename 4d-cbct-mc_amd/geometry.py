@@ -7,8 +7,9 @@ the x/y plane and swapped x/y spacing before writing, x fastest), `MCAirGeometry
 (geo.py:375-439; the warp runs on the GPU through the engine), `MCCIRSPhantomGeometry` (geo.py:642-878:
 bundled base geometry + tumour / line-pair inserts), and the CT -> material mapping of `MCGeometry.from_image`
 (geo.py:495-577) with its mapper classes and `MaterialMapperPipeline` (geo.py:35-309), written against the rule
-stated in DESIGN.md row f8 / csrc/image_map.hpp: segmentations come as arrays or uncompressed `.mha` files.  Only
-the reference's segmentation NETWORK (`segmenter=`) and image resampling (SimpleITK) are out of scope.  The pipeline
+stated in DESIGN.md row f8 / csrc/image_map.hpp: segmentations come as arrays, as uncompressed `.mha` files or from the
+segmentation network (`segmenter=`: segmentation.MCSegmenter, csrc/segment_net.hip).  Only image resampling (SimpleITK) is out
+of scope.  The pipeline
 here is the host statement of the rule; `engine.Context.map_image` / `set_geometry_image` run it on the GPU.
 `MCThoraxLikeGeometry` is NOT a reference class: it is the synthetic patient-like workload of SURVEY.md 8d (input 3)
 used by tests and benchmarks.
@@ -79,8 +80,10 @@ class MCGeometry:
                    lung_vessel_segmentation_filepath=None, image_spacing=None, engine_context=None) -> "MCGeometry":
         """A CT image (uncompressed `.mha`, HU) and segmentation files -> geometry (`MCGeometry.from_image`, geo.py:495-577).
         With `engine_context` (an open `engine.Context` with a device) the mapping runs on its GPU (`Context.map_image`), else
-        in numpy (`MaterialMapperPipeline.execute`); both give the same arrays.  A `segmenter` and an `image_spacing` that
-        differs from the file's raise NotImplementedError: the network and SimpleITK's resampler are not part of this package."""
+        in numpy (`MaterialMapperPipeline.execute`); both give the same arrays.  A `segmenter` (segmentation.MCSegmenter, or any
+        object with its `segment`) predicts the segmentations; a given file wins over its prediction.  `segmenter_kwargs` is
+        accepted for the reference's signature and not read (the reference does not read it either).  An `image_spacing` that
+        differs from the file's raises NotImplementedError: SimpleITK's resampler is not part of this package."""
         image, spacing, segmentations = load_image_and_segmentations(
             image_filepath, segmenter=segmenter, image_spacing=image_spacing, body=body_segmentation_filepath,
             bone=bone_segmentation_filepath, muscle=muscle_segmentation_filepath, fat=fat_segmentation_filepath,
@@ -303,13 +306,35 @@ class MaterialMapperPipeline(list):
                     (LungVesselsMaterialMapper(), lung_vessel_segmentation)])
 
 
+PREDICTED_LABELS = {"bone": "upper_body_bones", "muscle": "upper_body_muscles", "fat": "upper_body_fat", "liver": "liver", "stomach": "stomach",
+                    "lung": "lung", "lung_vessel": "lung_vessels"}  # name of SEGMENTATION_NAMES -> label of segmentation.LABELS; body: not background
+
+
+def predict_segmentations(image, segmenter) -> dict:
+    """{name: uint8 [x, y, z]} of all SEGMENTATION_NAMES from `segmenter.segment(image)` as `from_image` uses it (geo.py:530-542):
+    body = (background == 0), the others by their label index.  The prediction comes in the padded shape (every axis at least the
+    patch); it is cropped back to the image (left = pad // 2) -- the reference would fail there on the shape mismatch."""
+    from .segmentation import get_label_index
+    prediction = np.asarray(segmenter.segment(image)[0])
+    if callable(getattr(segmenter, "clear_cache", None)):
+        segmenter.clear_cache()
+    if prediction.ndim != 4 or any(have < want for have, want in zip(prediction.shape[1:], image.shape)):
+        raise ValueError(f"the segmenter returned shape {prediction.shape} for an image of shape {image.shape}")
+    crop = tuple(slice((have - want) // 2, (have - want) // 2 + want) for have, want in zip(prediction.shape[1:], image.shape))
+    out = {"body": prediction[get_label_index("background")][crop] == 0}
+    for name, label in PREDICTED_LABELS.items():
+        out[name] = prediction[get_label_index(label)][crop]
+    return {name: np.ascontiguousarray(seg, dtype=np.uint8) for name, seg in out.items()}
+
+
 def load_image_and_segmentations(image_filepath, segmenter=None, image_spacing=None, **segmentation_filepaths):
     """(image [x, y, z], spacing mm, {name: uint8 [x, y, z]}) of `.mha` files, as `from_image` takes them.  Keywords: the names of
-    SEGMENTATION_NAMES -> file path or None."""
+    SEGMENTATION_NAMES -> file path or None.  A `segmenter` (an object with a callable `segment`, such as
+    `segmentation.MCSegmenter`) predicts all eight; a given file wins over its prediction."""
     from .reconstruction import read_mha
-    if segmenter is not None:
-        raise NotImplementedError("the segmentation network (cbctmc.segmentation.segmenter.MCSegmenter) is not part of this package: "
-                                  "pass the segmentations as files")
+    if segmenter is not None and not callable(getattr(segmenter, "segment", None)):
+        raise NotImplementedError("the segmentation network is given as an object with a `segment(image)` method "
+                                  "(segmentation.MCSegmenter); anything else is not understood: pass that, or the segmentations as files")
     data, spacing, _ = read_mha(image_filepath)
     if data.ndim != 3:
         raise ValueError(f"{image_filepath}: a 3-D image is needed")
@@ -321,7 +346,7 @@ def load_image_and_segmentations(image_filepath, segmenter=None, image_spacing=N
     unknown = set(segmentation_filepaths) - set(SEGMENTATION_NAMES)
     if unknown:
         raise TypeError(f"unknown segmentations {sorted(unknown)}")
-    segmentations = {}
+    segmentations = predict_segmentations(image, segmenter) if segmenter is not None else {}
     for name in SEGMENTATION_NAMES:
         path = segmentation_filepaths.get(name)
         if path is None:

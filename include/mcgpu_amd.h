@@ -677,6 +677,70 @@ typedef struct mcgpu_speedup_stage_args {
 } mcgpu_speedup_stage_args;
 int mcgpu_speedup_stage(const mcgpu_speedup_options *options, int stage, const mcgpu_speedup_stage_args *args, mcgpu_speedup_report *report);
 
+/* ------------------------------------------------------------------------------------------------
+ * The CT segmentation network (what the reference obtains from cbctmc/segmentation/segmenter.py: MCSegmenter.segment;
+ * csrc/segment_net.hip, whose header restates the network and the procedure).  A 3-D U-Net of 3 x 3 x 3 convolutions (zero
+ * padding, bias), instance norm and LeakyReLU(0.01) in float32, run patch by patch; softmax over channels 0..7 and sigmoid on
+ * channel 8 per patch, stitched as k + sum / n, then one-hot of the argmax (first maximum wins) and > 0.5.  The image is a host
+ * array [shape[0]][shape[1]][shape[2]] (last axis fastest) of int16 or float32; it is rescaled [in_min, in_max] -> [out_min,
+ * out_max] with clipping (not at all when the two ranges are equal) and padded with 0.0 up to the patch shape (left = pad / 2).
+ * labels (uint8) and raw (float32, may be NULL) are [9][padded shape], padded = max(shape, patch_shape) per axis.
+ * `weights` is one flat float32 buffer in the order of the reference's state dict: init_conv, final_conv, enc_0 .. enc_{L-1}
+ * (first, second convolution), dec_{L-1} .. dec_0, each as weight [c_out][c_in][3][3][3] then bias [c_out]
+ * (tests/golden/segment_state_dict.json).  n_filters = [init, enc_0 .. enc_{L-1}, dec_{L-1} .. dec_0, final], 2 levels + 2 values.
+ * Refused before any device call (-1, mcgpu_last_error): a null pointer, a patch axis not divisible by 2^levels, a bottleneck of
+ * fewer than 2 voxels, n_classes other than 9, a stride (1 - patch_overlap) x patch axis that is not a whole number >= 1,
+ * filters or n_weights that do not fit together, and a footprint above memory_limit_bytes; a footprint above the device's free
+ * memory is refused before anything is allocated. */
+typedef struct mcgpu_segment_options {
+  unsigned int struct_size;     /* sizeof(mcgpu_segment_options) as the caller was compiled (later fields read as zero); 0 is refused */
+  int device;
+  int shape[3];                 /* the image */
+  int image_type;               /* MCGPU_IMAGE_INT16 or MCGPU_IMAGE_FLOAT32 */
+  int patch_shape[3];
+  double patch_overlap;         /* stride = (1 - patch_overlap) x patch axis */
+  int levels;                   /* 1..8; the reference's: 4 */
+  int n_filters[18];            /* the reference's: 32 everywhere */
+  int n_classes;                /* 9 */
+  const float *weights;
+  unsigned long long n_weights;
+  double in_min, in_max;        /* the reference's: -1024, 3071 */
+  double out_min, out_max;      /* the reference's: 0, 1; spans are taken in double and rounded to float32, as numpy does */
+  unsigned long long memory_limit_bytes;  /* 0: the device's free memory alone decides */
+} mcgpu_segment_options;
+typedef struct mcgpu_segment_report {
+  double ms_upload;             /* allocation, host <-> device copies and the repacking of the weights */
+  double ms_conv;               /* convolution kernels */
+  double ms_norm;               /* instance norm + LeakyReLU kernels */
+  double ms_other;              /* patch staging, max-pool, head, stitching, mean and labels */
+  double ms_total;              /* wall time of the call */
+  unsigned long long patches_run;        /* distinct patch starts: each inferred once */
+  unsigned long long patches_skipped;    /* repeats of a start that the rule gives: stitched again, not inferred again */
+  unsigned long long peak_device_bytes;  /* most device memory the call held at once */
+  unsigned long long planned_device_bytes;  /* what the call worked out before it allocated anything */
+} mcgpu_segment_report;
+int mcgpu_segment_run(const mcgpu_segment_options *options, const void *image, unsigned char *labels, float *raw, mcgpu_segment_report *report);
+/* One operator alone (for tests), on tensors [c][shape[0]][shape[1]][shape[2]]; of the options only `device` is used.  CONV: in
+ * [c1][shape] and optionally in2 [c2][shape2] (concatenated after in; with `upsample` in2 is read through the x 2 nearest upsample
+ * and has (shape + 1) / 2 per axis, else shape), weight [c_out][c1 + c2][3][3][3], bias [c_out] -> out [c_out][shape].
+ * NORM_LRELU: in [c1][shape] -> out.  MAXPOOL: in [c1][shape] -> out [c1][shape / 2].  HEAD: in = logits [9][shape] -> out.
+ * STITCH: in = n_patches patches [c1][patch_shape] one after the other, starts [n_patches][3] in the volume `shape` -> out = mean
+ * [c1][shape] (0 where no patch arrived).  FINALIZE: in = mean [9][shape] -> out = labels uint8 [9][shape]. */
+enum { MCGPU_SEGMENT_STAGE_CONV = 0, MCGPU_SEGMENT_STAGE_NORM_LRELU = 1, MCGPU_SEGMENT_STAGE_MAXPOOL = 2, MCGPU_SEGMENT_STAGE_HEAD = 3,
+       MCGPU_SEGMENT_STAGE_STITCH = 4, MCGPU_SEGMENT_STAGE_FINALIZE = 5 };
+typedef struct mcgpu_segment_stage_args {
+  unsigned int struct_size;     /* sizeof(mcgpu_segment_stage_args); 0 is refused */
+  int upsample;
+  int c1, c2, c_out;
+  int shape[3];
+  int patch_shape[3];
+  int n_patches;
+  const int *starts;
+  const float *in, *in2, *weight, *bias;
+  void *out;
+} mcgpu_segment_stage_args;
+int mcgpu_segment_stage(const mcgpu_segment_options *options, int stage, const mcgpu_segment_stage_args *args, mcgpu_segment_report *report);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,375 @@
+"""The CT segmentation network without a GPU (4d-cbct-mc_amd/segmentation.py, csrc/segment_net.hip): the float64 restatement
+(segment_ref.py) against the reference class (recorded in golden/segment_pin.npz by gen_segment_golden.py, and directly where a
+reference tree is present), the patch rule in plain integers, the stitcher, the loader of weights, every refusal of the C ABI, the
+ctypes mirrors, and `MCGeometry.from_image(..., segmenter=...)` with a stand-in segmenter."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import cases
+import segment_ref
+
+torch = pytest.importorskip("torch")
+seg = cases.pkg.segmentation
+geo = cases.geometry
+recon = cases.pkg.reconstruction
+ROOT = Path(__file__).resolve().parents[1]
+REFERENCE = Path(os.environ.get("CBCTMC_REFERENCE", "/root/reference"))  # where oracle/Makefile looks for it too
+
+
+@pytest.fixture(scope="module")
+def weights7():
+    return segment_ref.seeded_weights(7)
+
+
+# ------------------------------------------------------------------------------------------------------------- the network
+def test_restatement_reproduces_the_reference_class_pin(weights7):
+    pin = np.load(segment_ref.GOLDEN / "segment_pin.npz")["logits"]
+    patch = segment_ref.rescale(segment_ref.seeded_image(segment_ref.PIN_SEED, segment_ref.PIN_PATCH))
+    assert patch.dtype == np.float32 and patch.min() == 0.0 and patch.max() == 1.0  # the clipping is exercised at both ends
+    got = segment_ref.logits_of(weights7, patch)
+    assert pin.shape == (9, 16, 16, 32) and pin.dtype == np.float64
+    assert np.abs(got - pin).max() <= 1e-9 * np.abs(pin).max()
+
+
+def test_state_dict_order_of_the_package_is_the_reference_class_order(weights7):
+    golden = segment_ref.golden_tensors()
+    assert len(golden) == 36
+    assert golden[:3] == [("init_conv.weight", (32, 1, 3, 3, 3)), ("init_conv.bias", (32,)), ("final_conv.weight", (9, 32, 3, 3, 3))]
+    assert seg.unet_tensors([32] * 10, 4) == golden == segment_ref.tensors()
+    assert [(k, v.shape) for k, v in weights7.items()] == golden
+
+
+@pytest.mark.skipif(not (REFERENCE / "cbctmc" / "speedup" / "models.py").exists(), reason="no reference tree")
+def test_restatement_equals_the_reference_class_with_unequal_filters():
+    """L = 2 and filters [8, 12, 16, 12, 8, 8]: which count feeds which convolution cannot hide behind 32 everywhere."""
+    import gen_segment_golden
+    filters = [8, 12, 16, 12, 8, 8]
+    weights = segment_ref.seeded_weights(11, filters, 2)
+    patch = segment_ref.rescale(segment_ref.seeded_image(11, (8, 12, 16)))
+    want = gen_segment_golden.reference_logits(REFERENCE, weights, patch, filters, 2)
+    got = segment_ref.logits_of(weights, patch)
+    assert np.abs(got - want).max() <= 1e-9 * np.abs(want).max()
+    assert seg.unet_tensors(filters, 2) == segment_ref.tensors(filters, 2)
+    model = seg.MCSegmenter(weights)
+    assert (model.levels, model.n_filters, model.n_classes) == (2, filters, 9)
+
+
+def test_labels_are_the_reference_names():
+    assert seg.N_LABELS == 9 and list(seg.LABELS) == list(range(9))
+    assert [seg.LABELS[i] for i in range(9)] == ["background", "upper_body_bones", "upper_body_muscles", "upper_body_fat", "liver", "stomach", "lung",
+                                                 "other", "lung_vessels"]
+    assert seg.get_label_index("lung_vessels") == 8 and seg.get_label_index("background") == 0
+    with pytest.raises(ValueError):
+        seg.get_label_index("heart")
+
+
+# ----------------------------------------------------------------------------------------------------------------- patches
+@pytest.mark.parametrize("shape, patch, overlap, axes", [
+    ((16, 24, 40), (16, 16, 16), 0.0, ([0, 0], [0, 8], [0, 16, 24])),
+    ((24, 20, 72), (16, 16, 32), 0.0, ([0, 8], [0, 4], [0, 32, 40])),
+    ((24, 20, 72), (16, 16, 32), 0.5, ([0, 8, 8], [0, 4], [0, 16, 32, 40])),
+    ((10, 16, 20), (16, 16, 32), 0.0, ([0, 0], [0, 0], [0, 0])),          # an image smaller than the patch: padded to (16, 16, 32)
+])
+def test_patch_starts_are_the_rule_in_plain_integers(shape, patch, overlap, axes):
+    padded = seg.padded_shape(shape, patch)
+    assert padded == tuple(max(n, p) for n, p in zip(shape, patch))
+    stride = seg.whole_stride(patch, overlap)
+    starts = seg.patch_starts(padded, patch, stride)
+    want = [(i, j, k) for i in axes[0] for j in axes[1] for k in axes[2]]  # meshgrid "ij": the last axis fastest
+    assert starts == want == segment_ref.patch_starts(padded, patch, stride)
+    assert all(isinstance(v, int) for s in starts for v in s)
+    covered = np.zeros(padded, bool)
+    for s in starts:
+        assert all(0 <= v and v + p <= n for v, p, n in zip(s, patch, padded))
+        covered[tuple(slice(v, v + p) for v, p in zip(s, patch))] = True
+    assert covered.all()
+
+
+def test_padding_and_stride_rules():
+    assert seg.padded_shape((10, 16, 21), (16, 16, 32)) == (16, 16, 32) and seg.padding_left((10, 16, 21), (16, 16, 32)) == (3, 0, 5)
+    assert seg.padding_left((24, 20, 72), (16, 16, 32)) == (0, 0, 0)
+    assert seg.whole_stride((128, 128, 128), 0.0) == (128, 128, 128) and seg.whole_stride((16, 16, 32), 0.5) == (8, 8, 16)
+    with pytest.raises(ValueError, match=r"stride of 115\.2 on patch axis 0 \(128\)"):
+        seg.whole_stride((128, 128, 128), 0.1)
+    with pytest.raises(ValueError, match="whole number >= 1"):
+        seg.whole_stride((16, 16, 32), 1.0)
+    image = np.arange(24, dtype=np.float32).reshape(2, 3, 4)
+    padded = segment_ref.pad_image(image, (5, 3, 7))
+    assert padded.shape == (5, 3, 7) and np.array_equal(padded[1:3, :, 1:5], image) and padded.sum() == image.sum()
+
+
+def test_stitcher_restatement_on_overlapping_and_repeated_patches():
+    """mean = k + sum / n: against the plain float64 mean of what arrived per voxel; a patch that arrives twice where nothing else
+    does leaves its own values bit for bit (value - k = 0)."""
+    rng = np.random.default_rng(4)
+    shape, patch = (2, 6, 5, 9), (4, 4, 6)
+    starts = [(0, 0, 0), (0, 0, 3), (2, 1, 3), (2, 1, 3), (1, 0, 2), (2, 1, 0), (0, 1, 0)]
+    data = [rng.random((2,) + patch).astype(np.float32) for _ in starts]
+    data[3] = data[2]                                     # the repeat of a start carries the same values
+    st32, st64 = segment_ref.Stitcher(shape), segment_ref.Stitcher(shape, np.float64)
+    total, count = np.zeros(shape), np.zeros(shape[1:])
+    for d, s in zip(data, starts):
+        st32.add(d, s)
+        st64.add(d, s)
+        where = tuple(slice(v, v + p) for v, p in zip(s, patch))
+        total[(slice(None),) + where] += d
+        count[where] += 1
+    assert count.min() == 0 and count.max() >= 4           # some voxels see no patch: their mean is 0
+    want = np.where(count > 0, total / np.maximum(count, 1), 0.0)
+    assert st32.mean().dtype == np.float32 and np.array_equal(st32.n[0], count) and np.array_equal(st32.n[1], count)
+    np.testing.assert_allclose(st64.mean(), want, rtol=0, atol=1e-15)
+    np.testing.assert_allclose(st32.mean(), want, rtol=0, atol=8 * 2.0 ** -24)  # at most 7 float32 additions below 1
+    alone = segment_ref.Stitcher(shape)
+    for _ in range(3):
+        alone.add(data[0], (1, 1, 2))
+    got = alone.mean()
+    assert np.array_equal(got[:, 1:5, 1:5, 2:8], data[0]) and got.sum(dtype=np.float64) == data[0].sum(dtype=np.float64)  # 0 elsewhere
+    fin = segment_ref.finalize(np.stack([np.full((1, 1, 1), v, np.float32) for v in (0.2, 0.3, 0.3, 0.1, 0, 0, 0, 0.1, 0.5)]))
+    assert fin[:, 0, 0, 0].tolist() == [0, 1, 0, 0, 0, 0, 0, 0, 0]  # the first maximum wins; exactly 0.5 is not above 0.5
+
+
+# ------------------------------------------------------------------------------------------------------------------ loader
+def test_loader_accepts_pth_and_npz_and_reads_the_architecture(tmp_path, weights7):
+    torch.save({"model": {k: torch.as_tensor(v) for k, v in weights7.items()}}, tmp_path / "w.pth")
+    np.savez(tmp_path / "w.npz", **weights7)
+    a = seg.MCSegmenter.from_filepath(tmp_path / "w.pth")
+    b = seg.MCSegmenter.from_filepath(tmp_path / "w.npz", patch_shape=(16, 16, 32), patch_overlap=0.5)
+    assert (a.levels, a.n_filters, a.n_classes) == (b.levels, b.n_filters, b.n_classes) == (4, [32] * 10, 9)
+    assert a.patch_shape == (128, 128, 128) and a.patch_overlap == 0.0 and a.input_value_range == (-1024, 3071) and a.output_value_range == (0, 1)
+    assert b.patch_shape == (16, 16, 32) and b.patch_overlap == 0.5
+    want = np.concatenate([weights7[n].ravel() for n, _ in segment_ref.golden_tensors()])
+    assert a.flat.dtype == np.float32 and a.flat.size == 562_153 and np.array_equal(a.flat, want) and np.array_equal(b.flat, want)
+    assert a.clear_cache() is None and a.last_report is None
+
+
+def test_loader_refuses_each_kind_of_bad_key_by_name(weights7):
+    with pytest.raises(ValueError, match=r"missing key dec_2\.convs\.3\.bias"):
+        seg.MCSegmenter({k: v for k, v in weights7.items() if k != "dec_2.convs.3.bias"})
+    with pytest.raises(ValueError, match=r"missing key init_conv\.weight"):
+        seg.MCSegmenter({k: v for k, v in weights7.items() if k != "init_conv.weight"})
+    with pytest.raises(ValueError, match=r"unexpected key extra\.weight"):
+        seg.MCSegmenter({**weights7, "extra.weight": np.zeros(3, np.float32)})
+    with pytest.raises(ValueError, match=r"inconsistent weight shapes: enc_1\.convs\.3\.weight has shape \(32, 16, 3, 3, 3\), expected \(32, 32, 3, 3, 3\)"):
+        seg.MCSegmenter({**weights7, "enc_1.convs.3.weight": np.zeros((32, 16, 3, 3, 3), np.float32)})
+    with pytest.raises(ValueError, match=r"enc_0\.convs\.0\.weight has shape \(32, 32, 3, 3\)"):
+        seg.MCSegmenter({**weights7, "enc_0.convs.0.weight": np.zeros((32, 32, 3, 3), np.float32)})
+    eight = {**weights7, "final_conv.weight": np.zeros((8, 32, 3, 3, 3), np.float32), "final_conv.bias": np.zeros(8, np.float32)}
+    with pytest.raises(ValueError, match="the final convolution has 8 outputs"):
+        seg.MCSegmenter(eight)
+    with pytest.raises(ValueError, match="one input channel"):
+        seg.MCSegmenter({**weights7, "init_conv.weight": np.zeros((32, 2, 3, 3, 3), np.float32)})
+    with pytest.raises(ValueError, match="Please pass a 3D image"):
+        seg.MCSegmenter(weights7).segment(np.zeros((4, 4), np.float32))
+
+
+# ----------------------------------------------------------------------------------------------------- refusals of the C ABI
+N_WEIGHTS = 562_153
+
+
+def _options(shape=(24, 20, 72), patch=(16, 16, 32), overlap=0.0, levels=4, filters=(32,) * 10, n_classes=9, weights=None, n_weights=N_WEIGHTS,
+             image_type=0, limit=0):
+    o = seg._SegmentOptions(struct_size=C.sizeof(seg._SegmentOptions), device=0, image_type=image_type, patch_overlap=overlap, levels=levels,
+                            n_classes=n_classes, weights=weights, n_weights=n_weights, in_min=-1024, in_max=3071, out_min=0, out_max=1,
+                            memory_limit_bytes=limit)
+    o.shape[:] = shape
+    o.patch_shape[:] = patch
+    o.n_filters[:len(filters)] = filters
+    return o
+
+
+def _refused(o, text, image=True, labels=True):
+    lib = seg._library()
+    img = np.zeros(tuple(o.shape), np.int16)
+    out = np.zeros((9,) + seg.padded_shape(tuple(o.shape), tuple(o.patch_shape)), np.uint8)
+    assert lib.mcgpu_segment_run(C.byref(o), img.ctypes.data if image else None, out.ctypes.data if labels else None, None, None) == -1
+    message = lib.mcgpu_last_error().decode()
+    assert re.search(text, message), message
+    return message
+
+
+def test_abi_refusals_before_any_device_call(engine):
+    """Every refusal names the value it objects to, and none needs a device: this test runs where there is none."""
+    flat = np.zeros(N_WEIGHTS, np.float32)
+    w = flat.ctypes.data
+    lib = seg._library()
+    assert lib.mcgpu_segment_run(None, None, None, None, None) == -1
+    assert "struct_size" in lib.mcgpu_last_error().decode()
+    _refused(_options(weights=w), "image is NULL", image=False)
+    _refused(_options(weights=w), "labels is NULL", labels=False)
+    _refused(_options(weights=None), "weights is NULL")
+    _refused(_options(weights=w, image_type=7), "image_type 7")
+    _refused(_options(weights=w, patch=(16, 24, 32)), r"patch axis 1 is 24, not divisible by 16 \(2\^levels\)")
+    _refused(_options(weights=w, patch=(16, 16, 16)), r"the bottleneck of a 16 x 16 x 16 patch has fewer than 2 voxels")
+    _refused(_options(weights=w, n_classes=8, n_weights=N_WEIGHTS - 32 * 27 - 1), "the final convolution has 8 outputs, expected 9")
+    _refused(_options(weights=w, patch=(16, 16, 32), overlap=0.3), r"patch_overlap 0\.3\d* gives a stride of 11\.2\d* on patch axis 0 \(16\)")
+    _refused(_options(weights=w, overlap=1.0), r"gives a stride of 0\.0+ on patch axis 0")
+    _refused(_options(weights=w, overlap=-0.03125), r"stride of 16\.5")
+    _refused(_options(weights=w, n_weights=N_WEIGHTS - 1), "inconsistent weight shapes: n_weights is 562152 but the architecture has 562153")
+    _refused(_options(weights=w, filters=(32,) * 9 + (16,)), "inconsistent weight shapes: final_conv takes 16 channels but dec_0 gives 32")
+    _refused(_options(weights=w, filters=(32,) * 4 + (0,) + (32,) * 5), r"n_filters\[4\] is 0")
+    _refused(_options(weights=w, levels=0), "levels is 0")
+    _refused(_options(weights=w, shape=(24, 0, 72)), "shape and patch_shape must be >= 1: 24 x 0 x 72")
+    message = _refused(_options(weights=w, limit=1 << 20), r"needs \d+ bytes of device memory, above the limit of 1048576")
+    needed = int(re.search(r"needs (\d+) bytes", message).group(1))
+    stitched = 2 * 9 * 24 * 20 * 72 * 4                      # k and sum of the padded volume alone
+    skip0 = 3 * 32 * 16 * 16 * 32 * 4                        # the three full-size 32-channel tensors of a patch
+    assert stitched + skip0 + 4 * N_WEIGHTS < needed < 4 * (stitched + skip0 + 4 * N_WEIGHTS)
+    # unequal filters are counted from the shapes
+    filters = [8, 12, 16, 12, 8, 8]
+    n = sum(int(np.prod(s)) for _, s in seg.unet_tensors(filters, 2))
+    _refused(_options(weights=w, levels=2, filters=filters, n_weights=n + 5), f"n_weights is {n + 5} but the architecture has {n} values")
+
+
+def test_stage_refusals_before_any_device_call(engine):
+    lib = seg._library()
+    buf = np.zeros(64, np.float32)
+    starts = np.array([0, 0, 3], np.int32)
+    o = seg._SegmentOptions(struct_size=C.sizeof(seg._SegmentOptions))
+    p = buf.ctypes.data
+
+    def args(shape=(2, 2, 2), patch=(0, 0, 0), **kw):
+        a = seg._SegmentStageArgs(struct_size=C.sizeof(seg._SegmentStageArgs), **kw)
+        a.shape[:] = shape
+        a.patch_shape[:] = patch
+        return a
+
+    for stage, a, text in [(9, args(in_=p, out=p, c1=1), "unknown stage 9"),
+                           (0, args(in_=p, c1=1), "out is NULL"),
+                           (1, args(out=p, c1=1), "in is NULL"),
+                           (0, args(in_=p, out=p, c1=1, shape=(2, 0, 2)), "shape must be >= 1: 2 x 0 x 2"),
+                           (0, args(in_=p, out=p, c1=1, c_out=1), "weight or bias is NULL"),
+                           (0, args(in_=p, out=p, c1=1, c2=1, c_out=1, weight=p, bias=p), "in2 is NULL"),
+                           (2, args(in_=p, out=p, c1=0), "c1 must be"),
+                           (1, args(in_=p, out=p, c1=1, shape=(1, 1, 1)), "at least 2 voxels"),
+                           (4, args(in_=p, out=p, c1=1, patch=(2, 2, 2)), "n_patches must be >= 1"),
+                           (4, args(in_=p, out=p, c1=1, shape=(2, 2, 4), patch=(2, 2, 2), n_patches=1, starts=starts.ctypes.data),
+                            "patch 0 at 0 x 0 x 3 of shape 2 x 2 x 2 leaves the volume 2 x 2 x 4")]:
+        assert lib.mcgpu_segment_stage(C.byref(o), stage, C.byref(a), None) == -1
+        assert text in lib.mcgpu_last_error().decode(), lib.mcgpu_last_error().decode()
+    assert lib.mcgpu_segment_stage(C.byref(o), 0, None, None) == -1
+    assert "mcgpu_segment_stage_args" in lib.mcgpu_last_error().decode()
+
+
+def test_segment_reports_the_refusal_of_the_library(engine, weights7):
+    model = seg.MCSegmenter(weights7, patch_shape=(16, 24, 32))
+    with pytest.raises(engine.EngineError) as e:
+        model.segment(np.zeros((24, 24, 32), np.int16))
+    assert e.value.code == -1 and "patch axis 1 is 24, not divisible by 16" in e.value.message
+
+
+def test_ctypes_mirrors_match_the_c_layout(engine, tmp_path):
+    """sizeof and every field offset of the three structs as a C compiler lays them out from the header."""
+    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
+    assert cc, "a C compiler is needed (the oracle is built with one)"
+    structs = {"mcgpu_segment_options": seg._SegmentOptions, "mcgpu_segment_report": seg._SegmentReport, "mcgpu_segment_stage_args": seg._SegmentStageArgs}
+    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{ROOT / "include" / "mcgpu_amd.h"}"', "int main(void) {"]
+    for cname, mirror in structs.items():
+        lines.append(f'  printf("{cname} sizeof %zu\\n", sizeof({cname}));')
+        for field, _ in mirror._fields_:
+            lines.append(f'  printf("{cname} {field} %zu\\n", offsetof({cname}, {field.rstrip("_")}));')
+    lines += ["  return 0;", "}"]
+    (tmp_path / "layout.c").write_text("\n".join(lines))
+    subprocess.run([cc, "-o", str(tmp_path / "layout"), str(tmp_path / "layout.c")], check=True)
+    out = subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout
+    seen = 0
+    for cname, field, value in re.findall(r"(\w+) (\w+) (\d+)", out):
+        mirror = structs[cname]
+        assert int(value) == (C.sizeof(mirror) if field == "sizeof" else getattr(mirror, field).offset), (cname, field)
+        seen += 1
+    assert seen == sum(len(m._fields_) + 1 for m in structs.values())
+    header = (ROOT / "include" / "mcgpu_amd.h").read_text()
+    for name, code in seg.SEGMENT_STAGES.items():
+        assert f"MCGPU_SEGMENT_STAGE_{name.upper()} = {code}" in header
+    assert (seg.IMAGE_INT16, seg.IMAGE_FLOAT32) == (engine.IMAGE_INT16, engine.IMAGE_FLOAT32)
+    assert "mcgpu_segment_run" in engine.ABI_SYMBOLS and "mcgpu_segment_stage" in engine.ABI_SYMBOLS
+
+
+# ------------------------------------------------------------------------------------------- from_image with a segmenter
+class StandIn:
+    """A segmenter whose `segment` returns fixed arrays in the padded shape, as MCSegmenter does."""
+
+    def __init__(self, prediction):
+        self.prediction, self.seen, self.cleared = prediction, None, 0
+
+    def segment(self, image):
+        self.seen = image
+        return self.prediction, self.prediction.astype(np.float32)
+
+    def clear_cache(self):
+        self.cleared += 1
+
+
+def _case(tmp_path):
+    rng = np.random.default_rng(21)
+    shape, patch = (10, 8, 6), (16, 8, 8)
+    image = rng.integers(-1100, 900, size=shape).astype(np.int16)
+    segs = {"body": (rng.random(shape) < 0.9).astype(np.uint8)}
+    for name in geo.SEGMENTATION_NAMES[1:]:
+        segs[name] = (rng.random(shape) < 0.3).astype(np.uint8)
+    segs["body"][0, 0, 0] = 1
+    padded, left = seg.padded_shape(shape, patch), seg.padding_left(shape, patch)
+    assert padded == (16, 8, 8) and left == (3, 0, 1)
+    crop = tuple(slice(a, a + n) for a, n in zip(left, shape))
+    prediction = np.ones((9,) + padded, np.uint8)                       # outside the image: everything set, so a wrong crop shows
+    prediction[0][crop] = 1 - segs["body"]
+    prediction[seg.get_label_index("other")] = 0
+    for name, label in geo.PREDICTED_LABELS.items():
+        prediction[seg.get_label_index(label)][crop] = segs[name]
+    path = tmp_path / "ct.mha"
+    recon.write_mha(path, image.swapaxes(0, 2), (1.5, 2.0, 2.5), (0.0, 0.0, 0.0), element_type="MET_SHORT")
+    return image, segs, prediction, path
+
+
+def _execute(image, segs):
+    return geo.MaterialMapperPipeline.create_default_pipeline(**{f"{k}_segmentation": v for k, v in segs.items()}).execute(image)
+
+
+def test_from_image_with_a_segmenter_gives_the_geometry_of_its_prediction(tmp_path):
+    image, segs, prediction, path = _case(tmp_path)
+    standin = StandIn(prediction)
+    g = geo.MCGeometry.from_image(path, segmenter=standin)
+    m, d = _execute(image, segs)
+    assert np.array_equal(g.materials, m) and np.array_equal(g.densities, d) and g.image_spacing == (1.5, 2.0, 2.5)
+    assert standin.cleared == 1 and standin.seen.dtype == np.int16 and np.array_equal(standin.seen, image)
+    assert len(set(np.unique(m))) >= 6                                   # the case is not trivial
+    # the crop after padding: the same prediction one voxel off gives another geometry
+    predicted = geo.predict_segmentations(image, StandIn(prediction))
+    assert sorted(predicted) == sorted(geo.SEGMENTATION_NAMES)
+    for name in geo.SEGMENTATION_NAMES:
+        assert predicted[name].dtype == np.uint8 and np.array_equal(predicted[name] > 0, segs[name] > 0), name
+    # an unpadded prediction passes through as it is
+    exact = np.ascontiguousarray(prediction[:, 3:13, :, 1:7])
+    g2 = geo.MCGeometry.from_image(path, segmenter=StandIn(exact))
+    assert np.array_equal(g2.materials, m)
+    with pytest.raises(ValueError, match=r"returned shape \(9, 9, 8, 6\) for an image of shape \(10, 8, 6\)"):
+        geo.MCGeometry.from_image(path, segmenter=StandIn(exact[:, :9]))
+
+
+def test_segmentation_files_override_the_prediction(tmp_path):
+    image, segs, prediction, path = _case(tmp_path)
+    other = dict(segs)
+    other["bone"] = 1 - segs["bone"]
+    other["lung_vessel"] = np.zeros_like(segs["lung_vessel"])
+    for name in ("bone", "lung_vessel"):
+        recon.write_mha(tmp_path / f"{name}.mha", other[name].swapaxes(0, 2), (1.5, 2.0, 2.5), (0.0, 0.0, 0.0), element_type="MET_UCHAR")
+    g = geo.MCGeometry.from_image(path, segmenter=StandIn(prediction), bone_segmentation_filepath=tmp_path / "bone.mha",
+                                  lung_vessel_segmentation_filepath=tmp_path / "lung_vessel.mha")
+    m, d = _execute(image, other)
+    assert np.array_equal(g.materials, m) and np.array_equal(g.densities, d)
+    assert not np.array_equal(m, _execute(image, segs)[0])
+
+
+def test_anything_without_a_segment_method_is_still_refused(tmp_path):
+    _, _, _, path = _case(tmp_path)
+    for bad in (object(), "weights.pth", 3):
+        with pytest.raises(NotImplementedError, match="segmentation network"):
+            geo.MCGeometry.from_image(path, segmenter=bad)
+        with pytest.raises(NotImplementedError, match="segmentation network"):
+            geo.load_image_and_segmentations(path, segmenter=bad)
