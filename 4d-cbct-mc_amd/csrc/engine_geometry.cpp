@@ -1,6 +1,7 @@
 // engine_geometry.cpp -- C ABI of geometry changes on a resident context (4-D scans, cbctmc/mc/simulation.py:527-710) and of the
 // voxel-file writers.
 #include "engine_internal.hpp"
+#include "resample.hpp"
 
 #include <cstddef>
 
@@ -137,20 +138,25 @@ struct MappedInputs {
     if (host) HIP_TRY(hipMemcpy(d, host, n, hipMemcpyHostToDevice));
     return d;
   }
-  void upload(size_t nvox, const void* image, int image_dtype, const uint8_t* const* segmentations, const float* thresholds) {
+  // The mapping's inputs as buffers of this holder: copies of the host arrays (`copy`), or buffers a kernel fills later, one for the
+  // image and one for every segmentation whose pointer is not null (the resampled inputs of mcgpu_set_geometry_image_resampled).
+  void place(size_t nvox, const void* image, int image_dtype, const uint8_t* const* segmentations, const float* thresholds, bool copy) {
     const auto t0 = std::chrono::steady_clock::now();
     args.image_is_f32 = image_dtype == MCGPU_IMAGE_FLOAT32 ? 1 : 0;
-    args.image = device_copy(image, nvox * (args.image_is_f32 ? 4 : 2));
+    args.image = device_copy(copy ? image : nullptr, nvox * (args.image_is_f32 ? 4 : 2));
     bytes = nvox * (args.image_is_f32 ? 4 : 2);
     for (int k = 0; k < kImageSegmentations; ++k) {
-      args.seg[k] = segmentations[k] ? (const unsigned char*)device_copy(segmentations[k], nvox) : nullptr;
+      args.seg[k] = segmentations[k] ? (const unsigned char*)device_copy(copy ? segmentations[k] : nullptr, nvox) : nullptr;
       if (segmentations[k]) bytes += nvox;
     }
     for (int k = 0; k < 3; ++k) args.threshold[k] = thresholds[k];
     unsigned int words[kImageStatWords];
     image_map_stats_init(words);
     args.stats = (unsigned int*)device_copy(words, sizeof words);
-    ms_upload = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ms_upload = copy ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() : 0.0;
+  }
+  void upload(size_t nvox, const void* image, int image_dtype, const uint8_t* const* segmentations, const float* thresholds) {
+    place(nvox, image, image_dtype, segmentations, thresholds, true);
   }
 };
 
@@ -185,6 +191,83 @@ float density_as_in_a_voxel_file(float density) {  // "%.6f", cbctmc/mc/voxel_da
   char t[64];
   snprintf(t, sizeof t, "%.6f", (double)density);
   return strtof(t, nullptr);
+}
+
+// What mcgpu_set_geometry_image and mcgpu_set_geometry_image_resampled share: the inputs are on the device (`in`), of the engine's grid
+// `n`; map them, derive the model and swap it in.  Nothing of the context has changed when it throws.
+void install_mapped_image(mcgpu_ctx* ctx, const char* who, const int n[3], const float spacing_cm[3], MappedInputs& in, const mcgpu_image_class* table,
+                          int frame, mcgpu_image_map_report* report) {
+  HostModel& H = ctx->host;
+  const int device_id = ctx->dev.device_id, num_cus = ctx->dev.num_cus;
+  VoxelGrid v;  // its voxel arrays stay empty: the voxels exist on the device only (sync_host_voxels fills them on demand)
+  for (int k = 0; k < 3; ++k) {
+    v.n[k] = n[k];
+    v.voxel_size[k] = spacing_cm[k];
+    v.size_bbox[k] = v.n[k] * v.voxel_size[k];
+    v.inv_voxel_size[k] = 1.0f / v.voxel_size[k];
+  }
+  const size_t tiled_bytes = (size_t)((n[0] + 3) >> 2) * ((n[1] + 3) >> 2) * ((n[2] + 3) >> 2) * 64;
+  // 1. the mapping, beside the live model
+  unsigned char* classes = (unsigned char*)in.device_copy(nullptr, tiled_bytes);
+  float ms = 0.f;
+  unsigned int words[kImageStatWords];
+  {
+    Event ev[2];
+    HIP_TRY(hipEventCreate(ev[0].make(device_id)));
+    HIP_TRY(hipEventCreate(ev[1].make(device_id)));
+    HIP_TRY(hipEventRecord(ev[0], nullptr));
+    HIP_TRY(launch_image_map_tiled(in.args, frame, n[0], n[1], n[2], classes, num_cus, nullptr));
+    HIP_TRY(hipEventRecord(ev[1], nullptr));
+    HIP_TRY(hipMemcpy(words, in.args.stats, sizeof words, hipMemcpyDeviceToHost));  // waits for the kernel
+    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+  }
+  const auto t_install = std::chrono::steady_clock::now();
+  fill_image_report(report, words, ms, in.ms_upload, 0.0, in.bytes + tiled_bytes);
+  if (words[2 * kImageClasses] != 0u) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "!!ERROR!! %s: %u voxels are unmapped (no line of the mapping touches them: a body segmentation is missing)", who,
+             words[2 * kImageClasses]);
+    throw Error(-2, msg);
+  }
+  // 2. what mcgpu_set_geometry_arrays derives from the voxel arrays, from the statistics of the classes
+  DeviceVolumeSource src;
+  src.classes_tiled = classes;
+  src.bytes = tiled_bytes;
+  for (int k = 0; k < kMaxMaterials; ++k) v.density_max[k] = -999.0f;
+  for (int c = 0; c < kImageClasses; ++c) {
+    src.material[c] = table[c].material;
+    src.density[c] = density_as_in_a_voxel_file(table[c].density);  // once per class instead of once per voxel
+    src.first[c] = words[kImageClasses + c];
+    if (src.first[c] == 0xFFFFFFFFu) continue;
+    require(src.material[c] >= 1 && src.material[c] <= kMaxMaterials, -2, "!!ERROR load_voxels!! Voxel material number out of range!!");
+    require(src.density[c] >= 1.0e-9f, -2, "!!ERROR load_voxels!! Voxel density can not be 0 or negative");
+    v.density_max[src.material[c] - 1] = std::max(v.density_max[src.material[c] - 1], src.density[c]);
+  }
+  MaterialTables mat;
+  load_material_files(H.cfg.file_materials, v, mat);
+  int roi[6], roi_old[6];
+  for (int k = 0; k < 6; ++k) roi_old[k] = H.cfg.dose_roi[k];
+  clip_dose_roi(H.cfg.dose_roi_input, v.n, roi);  // from the input's ROI, whatever geometries came between; Error -2 when nothing of it is left
+  std::swap(H.voxels, v);
+  std::swap(H.mat, mat);
+  for (int k = 0; k < 6; ++k) H.cfg.dose_roi[k] = roi[k];
+  DeviceModel fresh;
+  try {
+    fresh = upload_model(H, device_id, &src);
+    for (int k = 0; k < 5; ++k) fresh.sched[k] = ctx->dev.sched[k];  // the tuned FAST schedule survives a geometry change
+    fresh.sched_set = ctx->dev.sched_set;
+    apply_schedule(fresh);
+  } catch (...) {
+    std::swap(H.voxels, v);
+    std::swap(H.mat, mat);
+    for (int k = 0; k < 6; ++k) H.cfg.dose_roi[k] = roi_old[k];
+    throw;
+  }
+  ctx->dev = std::move(fresh);  // with the superseded model go its correspondence model and its warp base
+  ctx->host_voxels_stale = true;
+  ctx->table_cache.clear();
+  if (report && report->struct_size >= offsetof(mcgpu_image_map_report, ms_install) + sizeof(double))
+    report->ms_install = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_install).count();
 }
 
 }  // namespace
@@ -234,82 +317,62 @@ int mcgpu_set_geometry_image(mcgpu_ctx* ctx, const int n[3], const float spacing
   ABI_BEGIN
   check_image_arguments("mcgpu_set_geometry_image", ctx, n, image, image_dtype, segmentations, table, thresholds, report);
   require(spacing_cm && (frame == 0 || frame == 1), -1, "!!ERROR!! mcgpu_set_geometry_image: bad argument");
-  HostModel& H = ctx->host;
-  const int device_id = ctx->dev.device_id, num_cus = ctx->dev.num_cus;
-  HIP_TRY(hipSetDevice(device_id));
+  HIP_TRY(hipSetDevice(ctx->dev.device_id));
   HIP_TRY(hipDeviceSynchronize());
-  VoxelGrid v;  // its voxel arrays stay empty: the voxels exist on the device only (sync_host_voxels fills them on demand)
-  for (int k = 0; k < 3; ++k) {
-    v.n[k] = n[k];
-    v.voxel_size[k] = spacing_cm[k];
-    v.size_bbox[k] = v.n[k] * v.voxel_size[k];
-    v.inv_voxel_size[k] = 1.0f / v.voxel_size[k];
-  }
-  const size_t nvox = v.count();
-  const size_t tiled_bytes = (size_t)((n[0] + 3) >> 2) * ((n[1] + 3) >> 2) * ((n[2] + 3) >> 2) * 64;
-  // 1. the mapping, beside the live model: nothing of the context has changed when it fails
   MappedInputs in;
-  in.upload(nvox, image, image_dtype, segmentations, thresholds);
-  unsigned char* classes = (unsigned char*)in.device_copy(nullptr, tiled_bytes);
-  float ms = 0.f;
-  unsigned int words[kImageStatWords];
+  in.upload((size_t)n[0] * n[1] * n[2], image, image_dtype, segmentations, thresholds);
+  install_mapped_image(ctx, "mcgpu_set_geometry_image", n, spacing_cm, in, table, frame, report);
+  return 0;
+  ABI_END
+}
+
+int mcgpu_set_geometry_image_resampled(mcgpu_ctx* ctx, const int n_in[3], const double spacing_in_mm[3], const double spacing_out_mm[3],
+                                       const void* image, int image_dtype, const uint8_t* const segmentations[8],
+                                       const mcgpu_image_class table[12], const float thresholds[3], int frame, double image_default,
+                                       mcgpu_image_map_report* image_report, mcgpu_resample_report* resample_report) {
+  ABI_BEGIN
+  const char* who = "mcgpu_set_geometry_image_resampled";
+  check_image_arguments(who, ctx, n_in, image, image_dtype, segmentations, table, thresholds, image_report);
+  require(spacing_in_mm && spacing_out_mm && (frame == 0 || frame == 1), -1, "!!ERROR!! mcgpu_set_geometry_image_resampled: bad argument");
+  require(!resample_report || resample_report->struct_size >= 8, -1,
+          "!!ERROR!! mcgpu_set_geometry_image_resampled: set resample_report->struct_size = sizeof(mcgpu_resample_report)");
+  const ResamplePlan plan = make_resample_plan(who, n_in, spacing_in_mm, spacing_out_mm);
+  // the engine's grid and voxel size from the arrays' axes: frame 0 [nz][ny][nx], frame 1 [gx][gy][gz] = [ny][nx][nz]
+  const int ax[3] = {frame == 0 ? 2 : 1, frame == 0 ? 1 : 0, frame == 0 ? 0 : 2};
+  int n[3];
+  float spacing_cm[3];
+  for (int k = 0; k < 3; ++k) {
+    n[k] = plan.n_out[ax[k]];
+    spacing_cm[k] = (float)(spacing_out_mm[ax[k]] / 10.0);
+  }
+  HIP_TRY(hipSetDevice(ctx->dev.device_id));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t nvox_in = plan.voxels_in(), nvox_out = plan.voxels_out(), image_size = resample_element_size(image_dtype);
+  MappedInputs in;
+  in.place(nvox_out, image, image_dtype, segmentations, thresholds, false);
+  double ms_kernel = 0.0;
+  size_t kernel_bytes = 0;
+  const auto t0 = std::chrono::steady_clock::now();
   {
-    Event ev[2];
-    HIP_TRY(hipEventCreate(ev[0].make(device_id)));
-    HIP_TRY(hipEventCreate(ev[1].make(device_id)));
-    HIP_TRY(hipEventRecord(ev[0], nullptr));
-    HIP_TRY(launch_image_map_tiled(in.args, frame, n[0], n[1], n[2], classes, num_cus, nullptr));
-    HIP_TRY(hipEventRecord(ev[1], nullptr));
-    HIP_TRY(hipMemcpy(words, in.args.stats, sizeof words, hipMemcpyDeviceToHost));  // waits for the kernel
-    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    CallDevice native;  // the arrays at their own spacing and the plan: gone before the mapping starts
+    native.events();
+    const ResampleArgs args = upload_resample_plan(native, plan);
+    const void* d_image = native.upload((const unsigned char*)image, nvox_in * image_size);
+    const unsigned char* d_seg[kImageSegmentations];
+    for (int k = 0; k < kImageSegmentations; ++k) d_seg[k] = segmentations[k] ? native.upload(segmentations[k], nvox_in) : nullptr;
+    const double ms_upload = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    Stage stage(native, ms_kernel);
+    HIP_TRY(launch_resample(args, image_dtype, kResampleLinear, image_default, d_image, const_cast<void*>(in.args.image), nullptr));
+    kernel_bytes += (nvox_in + nvox_out) * image_size;
+    for (int k = 0; k < kImageSegmentations; ++k) {
+      if (!d_seg[k]) continue;
+      HIP_TRY(launch_resample(args, MCGPU_IMAGE_UINT8, kResampleNearest, 0.0, d_seg[k], const_cast<unsigned char*>(in.args.seg[k]), nullptr));
+      kernel_bytes += nvox_in + nvox_out;
+    }
+    stage.done();
+    fill_resample_report(resample_report, ms_kernel, ms_upload, 0.0, kernel_bytes);
   }
-  const auto t_install = std::chrono::steady_clock::now();
-  fill_image_report(report, words, ms, in.ms_upload, 0.0, in.bytes + tiled_bytes);
-  if (words[2 * kImageClasses] != 0u) {
-    char msg[160];
-    snprintf(msg, sizeof msg, "!!ERROR!! mcgpu_set_geometry_image: %u voxels are unmapped (no line of the mapping touches them: a body segmentation is missing)",
-             words[2 * kImageClasses]);
-    throw Error(-2, msg);
-  }
-  // 2. what mcgpu_set_geometry_arrays derives from the voxel arrays, from the statistics of the classes
-  DeviceVolumeSource src;
-  src.classes_tiled = classes;
-  src.bytes = tiled_bytes;
-  for (int k = 0; k < kMaxMaterials; ++k) v.density_max[k] = -999.0f;
-  for (int c = 0; c < kImageClasses; ++c) {
-    src.material[c] = table[c].material;
-    src.density[c] = density_as_in_a_voxel_file(table[c].density);  // once per class instead of once per voxel
-    src.first[c] = words[kImageClasses + c];
-    if (src.first[c] == 0xFFFFFFFFu) continue;
-    require(src.material[c] >= 1 && src.material[c] <= kMaxMaterials, -2, "!!ERROR load_voxels!! Voxel material number out of range!!");
-    require(src.density[c] >= 1.0e-9f, -2, "!!ERROR load_voxels!! Voxel density can not be 0 or negative");
-    v.density_max[src.material[c] - 1] = std::max(v.density_max[src.material[c] - 1], src.density[c]);
-  }
-  MaterialTables mat;
-  load_material_files(H.cfg.file_materials, v, mat);
-  int roi[6], roi_old[6];
-  for (int k = 0; k < 6; ++k) roi_old[k] = H.cfg.dose_roi[k];
-  clip_dose_roi(H.cfg.dose_roi_input, v.n, roi);  // from the input's ROI, whatever geometries came between; Error -2 when nothing of it is left
-  std::swap(H.voxels, v);
-  std::swap(H.mat, mat);
-  for (int k = 0; k < 6; ++k) H.cfg.dose_roi[k] = roi[k];
-  DeviceModel fresh;
-  try {
-    fresh = upload_model(H, device_id, &src);
-    for (int k = 0; k < 5; ++k) fresh.sched[k] = ctx->dev.sched[k];  // the tuned FAST schedule survives a geometry change
-    fresh.sched_set = ctx->dev.sched_set;
-    apply_schedule(fresh);
-  } catch (...) {
-    std::swap(H.voxels, v);
-    std::swap(H.mat, mat);
-    for (int k = 0; k < 6; ++k) H.cfg.dose_roi[k] = roi_old[k];
-    throw;
-  }
-  ctx->dev = std::move(fresh);  // with the superseded model go its correspondence model and its warp base
-  ctx->host_voxels_stale = true;
-  ctx->table_cache.clear();
-  if (report && report->struct_size >= offsetof(mcgpu_image_map_report, ms_install) + sizeof(double))
-    report->ms_install = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_install).count();
+  install_mapped_image(ctx, who, n, spacing_cm, in, table, frame, image_report);
   return 0;
   ABI_END
 }

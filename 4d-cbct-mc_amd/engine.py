@@ -29,6 +29,7 @@ ABI_SYMBOLS = (
     "mcgpu_finalize_projection", "mcgpu_finalize_projection_host", "mcgpu_stack_create", "mcgpu_stack_append", "mcgpu_stack_write_slice", "mcgpu_stack_finish",
     "mcgpu_stack_read", "mcgpu_normalize_stack", "mcgpu_run_scan", "mcgpu_run_scan_multi", "mcgpu_set_projection_angles", "mcgpu_set_geometry_arrays",
     "mcgpu_warp_volume", "mcgpu_warp_geometry", "mcgpu_map_image", "mcgpu_set_geometry_image",
+    "mcgpu_resample_plan", "mcgpu_resample_volume", "mcgpu_set_geometry_image_resampled",
     "mcgpu_correspondence_set", "mcgpu_correspondence_fit", "mcgpu_correspondence_predict", "mcgpu_warp_geometry_signal", "mcgpu_correspondence_clear",
     "mcgpu_write_voxel_file", "mcgpu_write_voxel_binary", "mcgpu_kat_rng", "mcgpu_kat_rng_streams", "mcgpu_microbench", "mcgpu_kat_math", "mcgpu_kat_expf", "mcgpu_kat_f32", "mcgpu_kat_fast64", "mcgpu_kat_scatter", "mcgpu_kat_tile_records", "mcgpu_fdk_reconstruct", "mcgpu_forward_project", "mcgpu_forward_project_context", "mcgpu_rooster4d_reconstruct", "mcgpu_rooster4d_stage", "mcgpu_speedup_run", "mcgpu_speedup_stage", "mcgpu_segment_run", "mcgpu_segment_stage", "mcgpu_set_fast_schedule", "mcgpu_reload_env_knobs",
     "mcgpu_exchange_shared_bytes", "mcgpu_exchange_card_bytes", "mcgpu_exchange_create", "mcgpu_exchange_card", "mcgpu_exchange_connect",
@@ -57,6 +58,10 @@ class ScanReport(C.Structure):
 
 
 IMAGE_INT16, IMAGE_FLOAT32 = 0, 1
+IMAGE_UINT8 = 2  # the resampler only
+RESAMPLE_NEAREST, RESAMPLE_LINEAR = 0, 1
+_RESAMPLE_DTYPES = {np.dtype(np.uint8): IMAGE_UINT8, np.dtype(np.int16): IMAGE_INT16, np.dtype(np.float32): IMAGE_FLOAT32}
+_INTERPOLATORS = {"nearest": RESAMPLE_NEAREST, "linear": RESAMPLE_LINEAR}
 
 
 class ImageClass(C.Structure):
@@ -68,6 +73,18 @@ class ImageMapReport(C.Structure):
     """mcgpu_image_map_report (include/mcgpu_amd.h)."""
     _fields_ = [("struct_size", C.c_uint), ("reserved", C.c_uint), ("count", C.c_ulonglong * 12), ("first", C.c_longlong * 12),
                 ("unmapped", C.c_ulonglong), ("ms_kernel", C.c_double), ("ms_upload", C.c_double), ("ms_install", C.c_double),
+                ("kernel_bytes", C.c_ulonglong)]
+
+
+class ResampleOptions(C.Structure):
+    """mcgpu_resample_options (include/mcgpu_amd.h)."""
+    _fields_ = [("struct_size", C.c_uint), ("n_in", C.c_int * 3), ("spacing_in", C.c_double * 3), ("spacing_out", C.c_double * 3),
+                ("dtype", C.c_int), ("interpolator", C.c_int), ("default_value", C.c_double)]
+
+
+class ResampleReport(C.Structure):
+    """mcgpu_resample_report (include/mcgpu_amd.h)."""
+    _fields_ = [("struct_size", C.c_uint), ("ms_kernel", C.c_double), ("ms_upload", C.c_double), ("ms_download", C.c_double),
                 ("kernel_bytes", C.c_ulonglong)]
 
 
@@ -150,6 +167,11 @@ def load_library(path: Optional[os.PathLike] = None):
     lib.mcgpu_map_image.argtypes = [vp, C.POINTER(ci), vp, ci, C.POINTER(vp), C.POINTER(ImageClass), C.POINTER(C.c_float), vp, vp, C.POINTER(ImageMapReport)]
     lib.mcgpu_set_geometry_image.argtypes = [vp, C.POINTER(ci), C.POINTER(C.c_float), vp, ci, C.POINTER(vp), C.POINTER(ImageClass), C.POINTER(C.c_float), ci,
                                              C.POINTER(ImageMapReport)]
+    lib.mcgpu_resample_plan.argtypes = [C.POINTER(ResampleOptions), C.POINTER(ci), vp, vp, vp, vp, vp]
+    lib.mcgpu_resample_volume.argtypes = [vp, C.POINTER(ResampleOptions), vp, vp, C.POINTER(ResampleReport)]
+    lib.mcgpu_set_geometry_image_resampled.argtypes = [vp, C.POINTER(ci), C.POINTER(C.c_double), C.POINTER(C.c_double), vp, ci, C.POINTER(vp),
+                                                       C.POINTER(ImageClass), C.POINTER(C.c_float), ci, C.c_double, C.POINTER(ImageMapReport),
+                                                       C.POINTER(ResampleReport)]
     lib.mcgpu_correspondence_set.argtypes = [vp, vp, ci, vp, vp, ci, ci]
     lib.mcgpu_correspondence_fit.argtypes = [vp, C.POINTER(vp), ci, vp, vp, ci, ci, vp, vp]
     lib.mcgpu_correspondence_predict.argtypes = [vp, vp, ci, vp]
@@ -226,6 +248,31 @@ def tally_stage_sub_launch(first: int, count: int, limit: int, k: int):
     f, c = C.c_ulonglong(), C.c_ulonglong()
     _check(load_library().mcgpu_tally_stage_sub_launch(int(first), int(count), int(limit), int(k), C.byref(f), C.byref(c)))
     return f.value, c.value
+
+
+def _resample_options(shape, spacing, new_spacing, dtype=IMAGE_INT16, interpolator="linear", default_value=0.0) -> ResampleOptions:
+    if interpolator not in _INTERPOLATORS:
+        raise ValueError(f"interpolator '{interpolator}': 'linear' or 'nearest'")
+    if len(shape) != 3 or len(spacing) != 3 or len(new_spacing) != 3:
+        raise ValueError("a 3-D shape and one spacing per array axis are needed")
+    return ResampleOptions(C.sizeof(ResampleOptions), (C.c_int * 3)(*map(int, shape)), (C.c_double * 3)(*map(float, spacing)),
+                           (C.c_double * 3)(*map(float, new_spacing)), int(dtype), _INTERPOLATORS[interpolator], float(default_value))
+
+
+def resample_plan(shape, spacing, new_spacing) -> dict:
+    """The resampling rule per output index of every axis (mcgpu_resample_plan; csrc/resample.hpp states the rule): host arithmetic, no
+    device needed.  {"shape": the resampled shape, "base", "next", "frac", "nearest", "inside": one array per axis}."""
+    lib = load_library()
+    o = _resample_options(shape, spacing, new_spacing)
+    n_out = (C.c_int * 3)()
+    _check(lib.mcgpu_resample_plan(C.byref(o), n_out, None, None, None, None, None))
+    total = sum(n_out)
+    base, nxt, nearest = (np.empty(total, dtype=np.int32) for _ in range(3))
+    frac, inside = np.empty(total, dtype=np.float64), np.empty(total, dtype=np.uint8)
+    _check(lib.mcgpu_resample_plan(C.byref(o), n_out, base.ctypes.data, nxt.ctypes.data, frac.ctypes.data, nearest.ctypes.data, inside.ctypes.data))
+    cuts = np.cumsum(list(n_out))[:-1]
+    return {"shape": tuple(n_out), "base": np.split(base, cuts), "next": np.split(nxt, cuts), "frac": np.split(frac, cuts),
+            "nearest": np.split(nearest, cuts), "inside": [a.astype(bool) for a in np.split(inside, cuts)]}
 
 
 def advance_seed(batch_number: int, total_histories: int, seed: int) -> int:
@@ -693,17 +740,67 @@ class Context:
         self._correspondence_model = None  # the device model is built anew
         return self.last_image_report
 
+    # -- image resampling on the device (mcgpu_resample_volume / mcgpu_set_geometry_image_resampled; the rule: DESIGN.md row f12)
+    @staticmethod
+    def _resample_report(r: ResampleReport) -> dict:
+        return {"ms_kernel": r.ms_kernel, "ms_upload": r.ms_upload, "ms_download": r.ms_download, "kernel_bytes": int(r.kernel_bytes)}
+
+    def resample_volume(self, array, spacing, new_spacing, interpolator="linear", default_value=0.0) -> np.ndarray:
+        """`array` (3-D; uint8, int16 or float32) at `spacing` -> the same element type at `new_spacing`, one spacing per array axis,
+        resampled on the GPU as SimpleITK's Resample does for the reference's `resample_image_spacing` (csrc/resample.hpp states the
+        rule).  The lerps of "linear" run along the last array axis first.  `self.last_resample_report` has the times."""
+        a = np.ascontiguousarray(array)
+        if a.ndim != 3 or a.dtype not in _RESAMPLE_DTYPES:
+            raise ValueError(f"a 3-D uint8, int16 or float32 array is needed, got {a.dtype} of shape {a.shape}")
+        o = _resample_options(a.shape, spacing, new_spacing, _RESAMPLE_DTYPES[a.dtype], interpolator, default_value)
+        n_out = (C.c_int * 3)()
+        _check(self.lib.mcgpu_resample_plan(C.byref(o), n_out, None, None, None, None, None))
+        out = np.empty(tuple(n_out), dtype=a.dtype)
+        rep = ResampleReport(struct_size=C.sizeof(ResampleReport))
+        _check(self.lib.mcgpu_resample_volume(self.h, C.byref(o), a.ctypes.data, out.ctypes.data, C.byref(rep)))
+        self.last_resample_report = self._resample_report(rep)
+        return out
+
+    def set_geometry_image_resampled(self, image, segmentations: dict, spacing, new_spacing, frame: str = "geometry", image_default: float = -1000.0,
+                                     table=None, thresholds=None) -> dict:
+        """`set_geometry_image` of the image and segmentations resampled from `spacing` to `new_spacing` (mm, one per array axis), all on
+        the device (mcgpu_set_geometry_image_resampled): the image linearly with `image_default` outside, the segmentations by nearest
+        neighbour with 0 outside, as `MCGeometry.from_image(image_spacing=...)` resamples them.  Returns the mapping's report;
+        `self.last_resample_report` has the resampler's.  After an EngineError the context is unchanged."""
+        img, ptrs, tab, thr, keep = self._image_arguments(image, segmentations, table, thresholds)
+        if frame not in ("geometry", "engine"):
+            raise ValueError(f"frame '{frame}': 'geometry' or 'engine'")
+        rep, rrep = ImageMapReport(struct_size=C.sizeof(ImageMapReport)), ResampleReport(struct_size=C.sizeof(ResampleReport))
+        rc = self.lib.mcgpu_set_geometry_image_resampled(self.h, (C.c_int * 3)(*img.shape), (C.c_double * 3)(*map(float, spacing)),
+                                                         (C.c_double * 3)(*map(float, new_spacing)), img.ctypes.data,
+                                                         IMAGE_FLOAT32 if img.dtype == np.float32 else IMAGE_INT16, ptrs, tab, thr,
+                                                         1 if frame == "geometry" else 0, float(image_default), C.byref(rep), C.byref(rrep))
+        self.last_image_report, self.last_resample_report = self._image_report(rep), self._resample_report(rrep)
+        _check(rc)
+        self._correspondence_model = None  # the device model is built anew
+        return self.last_image_report
+
     def set_geometry_from_image(self, image_filepath, segmenter=None, segmenter_kwargs=None, body_segmentation_filepath=None,
                                 bone_segmentation_filepath=None, muscle_segmentation_filepath=None, fat_segmentation_filepath=None,
                                 liver_segmentation_filepath=None, stomach_segmentation_filepath=None, lung_segmentation_filepath=None,
                                 lung_vessel_segmentation_filepath=None, image_spacing=None) -> dict:
-        """`set_geometry(MCGeometry.from_image(...))` with the same arguments, mapped and installed on the device."""
+        """`set_geometry(MCGeometry.from_image(..., engine_context=self))` with the same arguments, mapped and installed on the device.
+        An `image_spacing` that differs from the file's resamples there too: without a segmenter in one call
+        (`set_geometry_image_resampled`: the native files go up, nothing comes back); with one, the image is resampled first
+        (`resample_volume`), because the segmenter sees the resampled image, and given files after it."""
         from . import geometry
-        image, spacing, segmentations = geometry.load_image_and_segmentations(
-            image_filepath, segmenter=segmenter, image_spacing=image_spacing, body=body_segmentation_filepath,
-            bone=bone_segmentation_filepath, muscle=muscle_segmentation_filepath, fat=fat_segmentation_filepath,
-            liver=liver_segmentation_filepath, stomach=stomach_segmentation_filepath, lung=lung_segmentation_filepath,
-            lung_vessel=lung_vessel_segmentation_filepath)
+        paths = dict(body=body_segmentation_filepath, bone=bone_segmentation_filepath, muscle=muscle_segmentation_filepath,
+                     fat=fat_segmentation_filepath, liver=liver_segmentation_filepath, stomach=stomach_segmentation_filepath,
+                     lung=lung_segmentation_filepath, lung_vessel=lung_vessel_segmentation_filepath)
+        if segmenter is None:
+            image, spacing, segmentations = geometry.load_image_and_segmentations(image_filepath, **paths)  # at the file's spacing
+            if not geometry.spacing_differs(image_spacing, spacing):
+                return self.set_geometry_image(image, segmentations, frame="geometry", image_spacing=spacing)
+            if image.dtype in (np.int16, np.float32):  # the mapping's own element types; a uint8 CT is resampled as uint8, below
+                return self.set_geometry_image_resampled(image, segmentations, spacing, image_spacing, frame="geometry",
+                                                         image_default=geometry.IMAGE_DEFAULT_HU)
+        image, spacing, segmentations = geometry.load_image_and_segmentations(image_filepath, segmenter=segmenter, image_spacing=image_spacing,
+                                                                              engine_context=self, **paths)
         return self.set_geometry_image(image, segmentations, frame="geometry", image_spacing=spacing)
 
     def warp_geometry(self, displacement: np.ndarray, frame: str = "geometry", default_material: int = 1, default_density: float = 0.0013):

@@ -8,9 +8,11 @@ the x/y plane and swapped x/y spacing before writing, x fastest), `MCAirGeometry
 bundled base geometry + tumour / line-pair inserts), and the CT -> material mapping of `MCGeometry.from_image`
 (geo.py:495-577) with its mapper classes and `MaterialMapperPipeline` (geo.py:35-309), written against the rule
 stated in DESIGN.md row f8 / csrc/image_map.hpp: segmentations come as arrays, as uncompressed `.mha` files or from the
-segmentation network (`segmenter=`: segmentation.MCSegmenter, csrc/segment_net.hip).  Only image resampling (SimpleITK) is out
-of scope.  The pipeline
+segmentation network (`segmenter=`: segmentation.MCSegmenter, csrc/segment_net.hip).  The pipeline
 here is the host statement of the rule; `engine.Context.map_image` / `set_geometry_image` run it on the GPU.
+`resample_image_spacing` (cbctmc/utils.py:76-102: SimpleITK's Resample to another voxel spacing, which `from_image(image_spacing=...)`
+applies to the CT and to every segmentation file) runs on the GPU only (`engine.Context.resample_volume`, csrc/resample.hip; the rule:
+DESIGN.md row f12 / csrc/resample.hpp); like `MCGeometry.warp` it has no host implementation and needs an `engine_context`.
 `MCThoraxLikeGeometry` is NOT a reference class: it is the synthetic patient-like workload of SURVEY.md 8d (input 3)
 used by tests and benchmarks.
 """
@@ -82,10 +84,13 @@ class MCGeometry:
         With `engine_context` (an open `engine.Context` with a device) the mapping runs on its GPU (`Context.map_image`), else
         in numpy (`MaterialMapperPipeline.execute`); both give the same arrays.  A `segmenter` (segmentation.MCSegmenter, or any
         object with its `segment`) predicts the segmentations; a given file wins over its prediction.  `segmenter_kwargs` is
-        accepted for the reference's signature and not read (the reference does not read it either).  An `image_spacing` that
-        differs from the file's raises NotImplementedError: SimpleITK's resampler is not part of this package."""
+        accepted for the reference's signature and not read (the reference does not read it either).  With an `image_spacing` that
+        differs from the file's, the image (linear, -1000 outside) and every segmentation file (nearest neighbour, 0 outside) are
+        resampled to it on the GPU of `engine_context` (`resample_image_spacing`), a segmenter sees the resampled image and the
+        geometry carries `image_spacing`; without `engine_context` that raises NotImplementedError: the resampler has no host
+        implementation."""
         image, spacing, segmentations = load_image_and_segmentations(
-            image_filepath, segmenter=segmenter, image_spacing=image_spacing, body=body_segmentation_filepath,
+            image_filepath, segmenter=segmenter, image_spacing=image_spacing, engine_context=engine_context, body=body_segmentation_filepath,
             bone=bone_segmentation_filepath, muscle=muscle_segmentation_filepath, fat=fat_segmentation_filepath,
             liver=liver_segmentation_filepath, stomach=stomach_segmentation_filepath, lung=lung_segmentation_filepath,
             lung_vessel=lung_vessel_segmentation_filepath)
@@ -280,8 +285,8 @@ class MaterialMapperPipeline(list):
         """(materials uint8, densities float32) of `image`, in its own layout.  Raises ValueError with the number of voxels
         that no mapper touched (the reference would hand material 0 at density 0 on to the voxel file writer, which refuses it)."""
         if image_spacing is not None:
-            raise NotImplementedError("resampling the segmentations to another spacing needs SimpleITK (the reference's resample_image_spacing, "
-                                      "cbctmc/utils.py:76-102); resample them first")
+            raise NotImplementedError("the host pipeline has no resampler: the reference's resample_image_spacing (cbctmc/utils.py:76-102) runs on the "
+                                      "GPU here; resample the segmentations first (geometry.resample_image_spacing with engine_context=)")
         materials = densities = None
         for mapper, segmentation in self:
             if segmentation is None:
@@ -327,10 +332,33 @@ def predict_segmentations(image, segmenter) -> dict:
     return {name: np.ascontiguousarray(seg, dtype=np.uint8) for name, seg in out.items()}
 
 
-def load_image_and_segmentations(image_filepath, segmenter=None, image_spacing=None, **segmentation_filepaths):
+IMAGE_DEFAULT_HU = -1000.0  # of resampled CT voxels outside the file's volume (geo.py:514-519); segmentations get 0 (geo.py:252-261)
+
+
+def spacing_differs(image_spacing, spacing) -> bool:
+    """Whether a requested `image_spacing` (None: none requested) asks for another grid than the file's `spacing`."""
+    return image_spacing is not None and not np.allclose(np.asarray(image_spacing, dtype=np.float64), spacing, rtol=0.0, atol=1e-9)
+
+
+def resample_image_spacing(image, spacing, new_spacing, resampler="linear", default_voxel_value=0.0, engine_context=None) -> np.ndarray:
+    """`image` (3-D array; uint8, int16 or float32) at `spacing` -> the same element type at `new_spacing`, one spacing per array axis
+    (`resample_image_spacing`, cbctmc/utils.py:76-102, on arrays instead of SimpleITK images; `resampler`: "linear" or "nearest").
+    `new_spacing=None` returns the input.  Runs on the GPU of `engine_context` (an open `engine.Context` with a device); there is no
+    host implementation.  The rule, and what of it is not pinned against SimpleITK: DESIGN.md row f12 / csrc/resample.hpp."""
+    if new_spacing is None:
+        return image
+    if engine_context is None:
+        raise NotImplementedError("the resampler (the reference's resample_image_spacing, cbctmc/utils.py:76-102) runs on the GPU and has no host "
+                                  "implementation: pass engine_context= (an open engine.Context with a device)")
+    return engine_context.resample_volume(image, spacing, new_spacing, interpolator=resampler, default_value=default_voxel_value)
+
+
+def load_image_and_segmentations(image_filepath, segmenter=None, image_spacing=None, engine_context=None, **segmentation_filepaths):
     """(image [x, y, z], spacing mm, {name: uint8 [x, y, z]}) of `.mha` files, as `from_image` takes them.  Keywords: the names of
     SEGMENTATION_NAMES -> file path or None.  A `segmenter` (an object with a callable `segment`, such as
-    `segmentation.MCSegmenter`) predicts all eight; a given file wins over its prediction."""
+    `segmentation.MCSegmenter`) predicts all eight; a given file wins over its prediction.  With an `image_spacing` other than the
+    file's, the image (linear, -1000 outside) and every segmentation file (nearest neighbour, 0 outside) are resampled to it on the GPU
+    of `engine_context` -- the segmenter sees the resampled image -- and the returned spacing is `image_spacing`."""
     from .reconstruction import read_mha
     if segmenter is not None and not callable(getattr(segmenter, "segment", None)):
         raise NotImplementedError("the segmentation network is given as an object with a `segment(image)` method "
@@ -339,10 +367,13 @@ def load_image_and_segmentations(image_filepath, segmenter=None, image_spacing=N
     if data.ndim != 3:
         raise ValueError(f"{image_filepath}: a 3-D image is needed")
     spacing = tuple(float(v) for v in spacing)
-    if image_spacing is not None and not np.allclose(np.asarray(image_spacing, dtype=np.float64), spacing, rtol=0.0, atol=1e-9):
-        raise NotImplementedError(f"resampling from spacing {spacing} to {tuple(image_spacing)} needs SimpleITK (the reference's "
-                                  "resample_image_spacing, cbctmc/utils.py:76-102); resample the files first")
+    resample_to = tuple(float(v) for v in image_spacing) if spacing_differs(image_spacing, spacing) else None
+    if resample_to is not None and engine_context is None:
+        raise NotImplementedError(f"resampling from spacing {spacing} to {resample_to} (the reference's resample_image_spacing, "
+                                  "cbctmc/utils.py:76-102) runs on the GPU and has no host implementation: pass engine_context= "
+                                  "(an open engine.Context with a device), or resample the files first")
     image = np.ascontiguousarray(np.asarray(data).swapaxes(0, 2))
+    image = resample_image_spacing(image, spacing, resample_to, "linear", IMAGE_DEFAULT_HU, engine_context)
     unknown = set(segmentation_filepaths) - set(SEGMENTATION_NAMES)
     if unknown:
         raise TypeError(f"unknown segmentations {sorted(unknown)}")
@@ -351,11 +382,11 @@ def load_image_and_segmentations(image_filepath, segmenter=None, image_spacing=N
         path = segmentation_filepaths.get(name)
         if path is None:
             continue
-        seg = read_segmentation(path)
+        seg = resample_image_spacing(read_segmentation(path), spacing, resample_to, "nearest", 0.0, engine_context)
         if seg.shape != image.shape:
             raise ValueError(f"{path}: shape {seg.shape} differs from the image's {image.shape}")
         segmentations[name] = seg
-    return image, spacing, segmentations
+    return image, spacing if resample_to is None else resample_to, segmentations
 
 
 def write_vox(filepath, materials_xyz: np.ndarray, densities_xyz: np.ndarray, spacing_cm, compress=True, engine=None):

@@ -450,6 +450,54 @@ int mcgpu_set_geometry_image(mcgpu_ctx *ctx, const int n[3], const float spacing
                              const uint8_t *const segmentations[8], const mcgpu_image_class table[12], const float thresholds[3], int frame,
                              mcgpu_image_map_report *report);
 
+/* ---- Row f12: a 3-D image to another voxel spacing, on the device (csrc/resample.hip).  Replaces the reference's resample_image_spacing
+ * (cbctmc/utils.py:76-102: SimpleITK's Resample with the identity transform, origin and direction unchanged) as MCGeometry.from_image
+ * calls it for the CT (linear, default -1000) and for every segmentation file (nearest neighbour, default 0; cbctmc/mc/geometry.py:252-261).
+ * The rule (csrc/resample.hpp states it in full, with what is NOT pinned against SimpleITK): arrays [n[0]][n[1]][n[2]], the last axis
+ * fastest, one spacing per ARRAY axis.  Per axis, in double: M = nearbyint(N * (os / ns)); c = (i * ns) / os; inside iff -0.5 <= c <
+ * N - 0.5, else the default value; nearest: floor(c + 0.5); linear: b = clamp(floor(c), 0, N - 1), b1 = min(b + 1, N - 1), d =
+ * max(c - b, 0), lerps a + (b - a) * d along the last axis, then the middle, then the first; double -> float32 rounds, double -> int16 /
+ * uint8 clamps and truncates toward zero.  Output element type = input element type.
+ * mcgpu_resample_plan: the rule per output index, on the host (no device needed): n_out, and -- each NULL or of n_out[0] + n_out[1] +
+ *   n_out[2] entries, axis after axis -- base (b), next (b1), frac (d), nearest (clamped into the axis where the output is outside) and
+ *   inside.  Call it with NULL arrays first to learn n_out.
+ * mcgpu_resample_volume: host arrays in and out ([n_in] -> [n_out] of the plan), resampled on the context's GPU (sibling of
+ *   mcgpu_warp_volume and mcgpu_map_image).
+ * mcgpu_set_geometry_image_resampled: mcgpu_set_geometry_image of the RESAMPLED image and segmentations without their passing through
+ *   the host: the native arrays are uploaded, the image is resampled linearly with image_default outside, every present segmentation by
+ *   nearest neighbour with 0 outside, and the mapping kernel and the install run on those device buffers.  n_in and the spacings (mm)
+ *   follow the ARRAYS' axes: frame 0: arrays [nz][ny][nx], spacings (z, y, x); frame 1: arrays [gx][gy][gz] of the MCGeometry frame,
+ *   spacings (gx, gy, gz).  The engine's grid is the plan's n_out, its spacing_cm spacing_out_mm / 10 as float, both permuted as for
+ *   mcgpu_set_geometry_image.  Errors of either part; after any error the context is what it was.  In image_report ms_upload is 0: the
+ *   copies to the device are resample_report's.
+ * Errors: -1 before any device call: a null pointer, a struct_size below 8, an unknown dtype or interpolator, a size below 1, a
+ *   non-finite or non-positive spacing, an axis of the result that rounds to 0 voxels; -2 before any device call: more than 2^31 - 1
+ *   voxels on either side. */
+#define MCGPU_IMAGE_UINT8 2 /* accepted by the resampler only */
+typedef struct mcgpu_resample_options {
+  unsigned int struct_size; /* sizeof(mcgpu_resample_options) as the caller was compiled */
+  int n_in[3];              /* the input array's shape, slowest axis first */
+  double spacing_in[3];     /* per array axis */
+  double spacing_out[3];
+  int dtype;                /* MCGPU_IMAGE_UINT8, MCGPU_IMAGE_INT16 or MCGPU_IMAGE_FLOAT32 */
+  int interpolator;         /* 0 nearest, 1 linear */
+  double default_value;     /* of output voxels outside the input; cast like every result */
+} mcgpu_resample_options;
+typedef struct mcgpu_resample_report {
+  unsigned int struct_size;         /* sizeof(mcgpu_resample_report) as the caller was compiled; smaller than 8 is refused */
+  double ms_kernel;                 /* the resampling kernels (HIP events) */
+  double ms_upload;                 /* host time of allocating on the device and copying the inputs and the plan there */
+  double ms_download;               /* host time of copying the result back (mcgpu_resample_volume) */
+  unsigned long long kernel_bytes;  /* bytes of the input and output arrays: what the kernels read and write at least once */
+} mcgpu_resample_report;
+int mcgpu_resample_plan(const mcgpu_resample_options *options, int n_out[3], int *base, int *next, double *frac, int *nearest,
+                        unsigned char *inside);
+int mcgpu_resample_volume(mcgpu_ctx *ctx, const mcgpu_resample_options *options, const void *in, void *out, mcgpu_resample_report *report);
+int mcgpu_set_geometry_image_resampled(mcgpu_ctx *ctx, const int n_in[3], const double spacing_in_mm[3], const double spacing_out_mm[3],
+                                       const void *image, int image_dtype, const uint8_t *const segmentations[8],
+                                       const mcgpu_image_class table[12], const float thresholds[3], int frame, double image_default,
+                                       mcgpu_image_map_report *image_report, mcgpu_resample_report *resample_report);
+
 /* Voxel geometry writer (cbctmc/mc/voxel_data.pyx:12-72 + mcgpu_geometry.jinja2 header fields):
  * material/density are [z][y][x] contiguous, spacing in cm. */
 int mcgpu_write_voxel_file(const char *path, const int n[3], const float spacing_cm[3], const uint8_t *material, const float *density,
