@@ -46,3 +46,9 @@ class MCDefaults:
 
 
 DEFAULTS = MCDefaults()
+
+# Linear attenuation [1/mm] of water and air at 63.140 keV, the mean energy of the spectrum above: the two values the reference's
+# scripts/fit_wpc.py:47-53 records from xraydb (Chantler's tables).  The template of the water pre-correction fit
+# (water_precorrection.py); no fitted polynomial is kept here: coefficients calibrate one pair of simulator and reconstructor.
+MU_WATER_63KEV = 0.02011970928851904
+MU_AIR_63KEV = 2.2416145024763944e-05

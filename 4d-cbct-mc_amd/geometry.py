@@ -483,6 +483,26 @@ class MCCatPhan604Geometry(MCGeometry):
         super().__init__(mats, dens, image_spacing)
 
 
+class MCWaterPhantomGeometry(MCGeometry):
+    """Water cylinder in air: the phantom of the water pre-correction fit (geo.py:1106-1165; scripts/fit_wpc.py).  Radius 100 mm and
+    length 150 mm along z unless given, centred at shape / 2 (voxel indices, as the reference centres it); isotropic spacing only."""
+
+    RADIUS, LENGTH = 100.0, 150.0  # mm
+
+    def __init__(self, shape=(500, 500, 500), image_spacing=(1.0, 1.0, 1.0), radius: float | None = None, length: float | None = None):
+        if len(set(image_spacing)) > 1:
+            raise ValueError("Image spacing must be isotropic")
+        s = float(image_spacing[0])
+        center = np.array(shape, dtype=np.float64) / 2
+        mats = np.full(shape, material_number("air"), dtype=np.uint8)
+        dens = np.full(shape, MATERIALS_125KEV["air"], dtype=np.float32)
+        disk, zsel = _cylinder(shape, center, (radius or self.RADIUS) / s, (length or self.LENGTH) / s)
+        body = disk[:, :, None] & zsel[None, None, :]
+        mats[body] = material_number("h2o")
+        dens[body] = np.float32(MATERIALS_125KEV["h2o"])
+        super().__init__(mats, dens, image_spacing)
+
+
 class MCBoxGeometry(MCGeometry):
     """Uniform block of one material (test geometry)."""
 

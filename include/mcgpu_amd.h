@@ -593,6 +593,44 @@ typedef struct mcgpu_fdk_report {
 int mcgpu_fdk_reconstruct(const mcgpu_fdk_options *options, const float *projections, float *volume, mcgpu_fdk_report *report);
 
 /* ------------------------------------------------------------------------------------------------
+ * Row f13: the normal equations of the empirical water pre-correction (Sourbelle et al. 2005; what the reference's
+ * scripts/fit_wpc.py computes from N + 1 rtkfdk runs), fused on the device (csrc/wpc_fit.hip; the rule: DESIGN.md row f13).
+ * With q the normalised projections of a water phantom, f_n = FDK(q^n) is what mcgpu_fdk_reconstruct gives for the wpc
+ * polynomial e_n, n = 0..order.  The call forms the slab means fbar_n[z][x] = sum_{y in [y_first, y_first + y_count)} f_n[z][y][x]
+ * / y_count (float32) without ever holding a volume, and B[i][j] = sum_pixels weight fbar_i fbar_j, a[i] = sum_pixels weight
+ * fbar_i template in double, summed in a fixed order: two calls give the same bytes.  The coefficients c = inv(B) a are left to
+ * the caller.  All fields but order, y_first, y_count and channel_layout mean what they mean in mcgpu_fdk_options. */
+typedef struct mcgpu_wpc_fit_options {
+  unsigned int struct_size;     /* sizeof(mcgpu_wpc_fit_options) as the caller was compiled (later fields read as zero); 0 is refused */
+  int n_proj, nu, nv;
+  double du, dv, u0, v0;
+  double sid, sdd;
+  const double *gantry_deg;     /* [n_proj] */
+  const double *proj_offset_x;  /* [n_proj] or NULL (0) */
+  const double *proj_offset_y;  /* [n_proj] or NULL (0) */
+  int nx, ny, nz;
+  double sx, sy, sz, ox, oy, oz;
+  double hann, hann_y, pad;
+  int order;                    /* N, 1..7: the powers q^0 .. q^N */
+  int y_first, y_count;         /* the slab of the volume's y axis: y_count >= 1, inside [0, ny) */
+  int device;
+  int channel_layout;           /* of the filtered powers the back-projector samples: 0 = the faster one as measured
+                                   (profiles/wpc_fit_ab.md), 1 = one plane per power, 2 = the powers interleaved per pixel; the
+                                   results are the same bit for bit */
+} mcgpu_wpc_fit_options;
+typedef struct mcgpu_wpc_fit_report {
+  double ms_upload;             /* host -> device copies of the projections (wall time) */
+  double ms_filter;             /* power-basis weighting, extension, ramp, hannY (and the interleaving pass) */
+  double ms_backproject;        /* slab-mean back-projection kernels */
+  double ms_reduce;             /* the normal-equation kernel */
+  double ms_total;              /* wall time of the call */
+  unsigned long long peak_device_bytes;  /* most device memory the call held at once, hipFFT's work areas included */
+} mcgpu_wpc_fit_report;
+int mcgpu_wpc_fit(const mcgpu_wpc_fit_options *options, const float *projections /*[n_proj][nv][nu]*/, const float *weight /*[nz][nx]*/,
+                  const float *template_ /*[nz][nx]*/, double *B /*[order + 1][order + 1]*/, double *a /*[order + 1]*/,
+                  float *basis_mean /*[order + 1][nz][nx], may be NULL*/, mcgpu_wpc_fit_report *report);
+
+/* ------------------------------------------------------------------------------------------------
  * Joseph forward projection on the circular cone-beam geometry of the FDK options above: what the reference obtains from RTK's
  * JosephForwardProjectionImageFilter, cbctmc/forward_projection.py: project_forward (csrc/forward_project.hip).  Output
  * [n_proj][nv][nu] line integrals (sum of density x mm), pixel (i, j) centred at (u0 + i du, v0 + j dv).  The volume
