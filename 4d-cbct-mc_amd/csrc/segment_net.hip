@@ -28,7 +28,7 @@
 //   4 x 6 x 34 halo of the chunk is staged in LDS, positions outside the tensor masked to zero (= zero padding), read from up to two
 //   channel-concatenated sources, the second optionally through the x 2 nearest upsample (>> 1 on all three axes) -- neither the
 //   concatenated nor the upsampled tensor exists in memory.  The global loads of chunk k + 1 go into registers before the MFMAs of
-//   chunk k and to LDS after them.  Weights are packed once per call (pack_weights3d_kernel): per block of 32 output channels and chunk,
+//   chunk k and to LDS after them.  Weights are packed once per call (pack_weights_kernel): per block of 32 output channels and chunk,
 //   [channel pair][tap][channel of the pair][output channel], zero where a channel does not exist.  Input channels past C_in are
 //   staged as zeros, output channels past C_out are not stored.  NO layer takes a VALU kernel: init (1 -> F) and final (F -> 9) run
 //   here with their padding.
@@ -43,8 +43,9 @@
 //   Rejected without a measurement, on arithmetic alone: 64 output channels per workgroup (the reference has 32 everywhere: half of
 //   every MFMA would multiply zeros); a 2 x 2 x 64 tile (halo 4 x 4 x 66 = 1056 floats per channel against 816 for the same 256
 //   voxels); chunks of 16 channels (107 KB of LDS: one workgroup per CU).
-// stats_kernel + norm_lrelu_kernel: as in speedup_net.hip (float64 sums over fixed segments and a fixed tree, normalised in float64,
-//   rounded once; the same input gives the same bytes), stated again here so that speedup_net.hip's code object stays as it is.
+// Instance norm (stats_kernel + norm_lrelu_kernel: float64 sums over fixed segments and a fixed tree, normalised in float64, rounded
+//   once; the same input gives the same bytes), the packing of the weights, the plan of the layers and the launches of a forward pass
+//   are unet_common.inc's, shared with speedup_net.hip.
 // maxpool3d_kernel, stage_patch_kernel (reads the image as float32 or int16, rescales, 0.0 outside the image: no padded copy of the
 //   image exists), head_kernel (softmax and sigmoid evaluated in float64, rounded once), stitch_kernel (k, sum, n of the padded volume;
 //   patches run one after the other on one stream: no atomics), mean_kernel, labels_kernel.
@@ -56,19 +57,13 @@
 
 namespace {
 
-using mcgpu::CallDevice;
-using mcgpu::Stage;
-
-[[noreturn]] void refuse(const char* fn, const std::string& what) { throw mcgpu::Error(-1, std::string("!!ERROR!! ") + fn + ": " + what); }
+constexpr int kTaps = 27;  // 3 x 3 x 3: what unet_common.inc sizes a K chunk and counts the weights with
+#include "unet_common.inc"
 
 // ---------------------------------------------------------------------------------------------------------------- convolution
 constexpr int kT0 = 2, kT1 = 4, kT2 = 32;                        // voxels of a workgroup: 4 waves x 2 d1-rows x 32
-constexpr int kCK = 8;                                           // input channels per K chunk
 constexpr int kH0 = kT0 + 2, kH1 = kT1 + 2, kH2 = kT2 + 2;       // the staged tile
 constexpr int kHalo = kH0 * kH1 * kH2;
-constexpr int kTaps = 27;
-constexpr int kKK = kCK * kTaps;                                 // K of a chunk
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct ConvArgs {
   const float* src1;   // [c1][D0][D1][D2]
@@ -79,20 +74,6 @@ struct ConvArgs {
   float* out;          // [c_out][D0][D1][D2]
   int c_out, n_chunks, nb2;  // nb2: workgroups along d2; blockIdx.x = block along d2 + nb2 * block of output channels
 };
-
-// w [c_out][c_in][3][3][3] -> the staging order of conv3x3x3_mfma_kernel, zero where the channel does not exist
-__global__ __launch_bounds__(256) void pack_weights3d_kernel(const float* w, float* wpack, int c_in, int c_out, int n_chunks, size_t total) {
-  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= total) return;
-  const int co_local = (int)(e % 32);
-  size_t r = e / 32;
-  const int kk = (int)(r % kKK);
-  r /= kKK;
-  const int ch = (int)(r % n_chunks), cb = (int)(r / n_chunks);
-  const int hh = kk & 1, tap = (kk >> 1) % kTaps, cp = (kk >> 1) / kTaps;
-  const int ci = ch * kCK + cp * 2 + hh, co = cb * 32 + co_local;
-  wpack[e] = (ci < c_in && co < c_out) ? w[((size_t)co * c_in + ci) * kTaps + tap] : 0.f;
-}
 
 constexpr int kSlots = (kHalo + 255) / 256;                      // halo positions of one channel a thread moves
 constexpr int kStageW = kKK * 32 / 256;                          // floats of the weights a thread moves per chunk
@@ -219,67 +200,6 @@ __global__ __launch_bounds__(256) void conv3x3x3_mfma_kernel(ConvArgs a) {
   }
 }
 
-// ------------------------------------------------------------------------------------------------- instance norm + LeakyReLU
-constexpr int kMaxSegments = 64;
-constexpr size_t kSegmentVoxels = 16384;
-
-int segments_of(size_t n) { return (int)std::min<size_t>(kMaxSegments, (n + kSegmentVoxels - 1) / kSegmentVoxels); }
-
-// part[c][s] = (sum, sum of squares) of segment s of channel c, in float64 and in a fixed order
-__global__ __launch_bounds__(256) void stats3d_kernel(const float* x, size_t n, int S, double2* part) {
-  __shared__ double s_sum[256], s_sq[256];
-  const int c = blockIdx.y, s = blockIdx.x, tid = threadIdx.x;
-  const size_t seg = (n + S - 1) / S, lo = (size_t)s * seg, hi = min(lo + seg, n);
-  const float* p = x + (size_t)c * n;
-  double sum[4] = {0.0, 0.0, 0.0, 0.0}, sq[4] = {0.0, 0.0, 0.0, 0.0};  // four chains: four loads in flight, the order still fixed
-  size_t i = lo + tid;
-  for (; i + 768 < hi; i += 1024) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const double v = p[i + 256 * k];
-      sum[k] += v;
-      sq[k] += v * v;
-    }
-  }
-  for (; i < hi; i += 256) {
-    const double v = p[i];
-    sum[0] += v;
-    sq[0] += v * v;
-  }
-  s_sum[tid] = (sum[0] + sum[1]) + (sum[2] + sum[3]);
-  s_sq[tid] = (sq[0] + sq[1]) + (sq[2] + sq[3]);
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (tid < w) {
-      s_sum[tid] += s_sum[tid + w];
-      s_sq[tid] += s_sq[tid + w];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) part[(size_t)c * S + s] = make_double2(s_sum[0], s_sq[0]);
-}
-
-__global__ __launch_bounds__(256) void norm_lrelu3d_kernel(const float* x, float* y, size_t n, int S, const double2* part) {
-  __shared__ double s_mean, s_rstd;
-  const int c = blockIdx.y;
-  if (threadIdx.x == 0) {
-    double sum = 0.0, sq = 0.0;
-    for (int s = 0; s < S; ++s) {
-      sum += part[(size_t)c * S + s].x;
-      sq += part[(size_t)c * S + s].y;
-    }
-    const double m = sum / (double)n, var = fmax(sq / (double)n - m * m, 0.0);
-    s_mean = m;
-    s_rstd = 1.0 / sqrt(var + 1e-5);
-  }
-  __syncthreads();
-  const double m = s_mean, rstd = s_rstd;
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const float v = (float)(((double)x[(size_t)c * n + i] - m) * rstd);
-  y[(size_t)c * n + i] = v > 0.f ? v : 0.01f * v;
-}
-
 // ------------------------------------------------------------------------------------------------------------- small kernels
 __global__ __launch_bounds__(256) void maxpool3d_kernel(const float* x, float* y, int C, int D0, int D1, int D2) {
   const int O0 = D0 >> 1, O1 = D1 >> 1, O2 = D2 >> 1;
@@ -384,8 +304,6 @@ __global__ __launch_bounds__(256) void labels_kernel(const float* mean, unsigned
   labels[8 * nv + i] = mean[8 * nv + i] > 0.5f ? 1 : 0;
 }
 
-unsigned blocks_of(size_t n) { return (unsigned)((n + 255) / 256); }
-
 // -------------------------------------------------------------------------------------------------------------------- host
 struct Dims {
   int d[3];
@@ -394,104 +312,8 @@ struct Dims {
   Dims halved_up() const { return {{(d[0] + 1) / 2, (d[1] + 1) / 2, (d[2] + 1) / 2}}; }
 };
 
-struct ConvLayer {
-  int c_in = 0, c_out = 0;
-  size_t w_off = 0, b_off = 0;  // in the flat weights
-  int n_chunks = 0;
-  float* wpack = nullptr;
-  const float* bias = nullptr;
-  size_t pack_floats() const { return (size_t)((c_out + 31) / 32) * n_chunks * kKK * 32; }
-};
-
-ConvLayer conv_layer(int c_in, int c_out, size_t& cursor) {
-  ConvLayer l;
-  l.c_in = c_in;
-  l.c_out = c_out;
-  l.w_off = cursor;
-  cursor += (size_t)c_out * c_in * kTaps;
-  l.b_off = cursor;
-  cursor += (size_t)c_out;
-  l.n_chunks = (c_in + kCK - 1) / kCK;
-  return l;
-}
-
-// the convolutions in the state dict's order: init, final, enc_0 .. enc_{L-1}, dec_{L-1} .. dec_0
-struct NetLayers {
-  int L;
-  std::vector<int> skip_c;  // channels of out_0 .. out_L
-  std::vector<int> dec_c;   // channels of dec_i's output, by level
-  ConvLayer init, final;
-  std::vector<ConvLayer> enc, dec;  // [2 i], [2 i + 1] of level i
-  NetLayers(int levels, const int* f, int n_classes, size_t& cursor) : L(levels), skip_c(levels + 1), dec_c(levels), enc(2 * levels), dec(2 * levels) {
-    skip_c[0] = f[0];
-    for (int i = 0; i < L; ++i) skip_c[i + 1] = f[1 + i];
-    for (int j = 0; j < L; ++j) dec_c[L - 1 - j] = f[1 + L + j];
-    init = conv_layer(1, f[0], cursor);
-    final = conv_layer(f[2 * L + 1], n_classes, cursor);
-    for (int i = 0; i < L; ++i) {
-      enc[2 * i] = conv_layer(skip_c[i], skip_c[i + 1], cursor);
-      enc[2 * i + 1] = conv_layer(skip_c[i + 1], skip_c[i + 1], cursor);
-    }
-    for (int i = L - 1; i >= 0; --i) {
-      const int below = i == L - 1 ? skip_c[L] : dec_c[i + 1];
-      dec[2 * i] = conv_layer(skip_c[i] + below, dec_c[i], cursor);
-      dec[2 * i + 1] = conv_layer(dec_c[i], dec_c[i], cursor);
-    }
-  }
-  template <class F>
-  void each(F f) {
-    f(init);
-    f(final);
-    for (auto& l : enc) f(l);
-    for (auto& l : dec) f(l);
-  }
-  int widest() const {
-    int w = 1;
-    for (int c : skip_c) w = std::max(w, c);
-    for (int c : dec_c) w = std::max(w, c);
-    return w;
-  }
-};
-
-// Launches and buffers of one call.  With `dry` nothing touches the device: alloc() only adds up what the call would hold.
-struct Runner {
-  CallDevice dev;
-  mcgpu_segment_report rep;
-  bool dry = false;
-  size_t planned = 0;
-  double2* d_part = nullptr;
-
-  Runner() { memset(&rep, 0, sizeof rep); }
-  void init(int device, int channels) {
-    if (!dry) {
-      HIP_TRY(hipSetDevice(device));
-      dev.events();
-    }
-    d_part = (double2*)alloc_bytes((size_t)std::max(channels, 1) * kMaxSegments * sizeof(double2), true);
-  }
-  void* alloc_bytes(size_t bytes, bool zero) {
-    bytes = std::max<size_t>(bytes, 4);
-    if (dry) {
-      planned += bytes;
-      return nullptr;
-    }
-    return zero ? dev.alloc_zeroed<char>(bytes) : dev.alloc<char>(bytes);
-  }
-  float* alloc(size_t floats) { return (float*)alloc_bytes(floats * sizeof(float), true); }
-  template <class T>
-  T* upload(const T* host, size_t n) {
-    T* p = (T*)alloc_bytes(n * sizeof(T), false);
-    if (!dry) HIP_TRY(hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice));
-    return p;
-  }
-
-  void pack(ConvLayer& l, const float* d_weights) {
-    const size_t total = l.pack_floats();
-    l.wpack = (float*)alloc_bytes(total * sizeof(float), false);
-    if (dry) return;
-    l.bias = d_weights + l.b_off;
-    hipLaunchKernelGGL(pack_weights3d_kernel, dim3(blocks_of(total)), dim3(256), 0, nullptr, d_weights + l.w_off, l.wpack, l.c_in, l.c_out, l.n_chunks, total);
-  }
+// Launches of one call; RunnerBase's dry mode plans the buffers of mcgpu_segment_run without touching the device
+struct Runner : RunnerBase<mcgpu_segment_report> {
 
   // out [c_out][D] = conv(cat(src1 [c1], src2 [c_in - c1] (upsampled when ups))) + bias
   void conv(const ConvLayer& l, const float* src1, int c1, const float* src2, int ups, const Dims& D, float* out) {
@@ -504,13 +326,6 @@ struct Runner {
     a.nb2 = (D.d[2] + kT2 - 1) / kT2;
     const dim3 grid((unsigned)a.nb2 * (unsigned)((l.c_out + 31) / 32), (unsigned)((D.d[1] + kT1 - 1) / kT1), (unsigned)((D.d[0] + kT0 - 1) / kT0));
     hipLaunchKernelGGL(conv3x3x3_mfma_kernel, grid, dim3(256), 0, nullptr, a);
-    st.done();
-  }
-  void norm_lrelu(const float* x, float* y, int C, size_t n) {
-    Stage st(dev, rep.ms_norm);
-    const int S = segments_of(n);
-    hipLaunchKernelGGL(stats3d_kernel, dim3((unsigned)S, (unsigned)C), dim3(256), 0, nullptr, x, n, S, d_part);
-    hipLaunchKernelGGL(norm_lrelu3d_kernel, dim3(blocks_of(n), (unsigned)C), dim3(256), 0, nullptr, x, y, n, S, d_part);
     st.done();
   }
   void maxpool(const float* x, float* y, int C, const Dims& D) {
@@ -542,54 +357,6 @@ struct Runner {
   }
 };
 
-// The network at one patch shape: its buffers, made once, and the launches of a forward pass
-struct NetPass {
-  NetLayers& net;
-  Runner& run;
-  Dims P;
-  std::vector<float*> skip, pooled, enc_a, dec_a, dec_b;
-  float* out = nullptr;
-  NetPass(NetLayers& n, Runner& r, const Dims& p) : net(n), run(r), P(p) {
-    const int L = net.L;
-    skip.resize(L + 1); pooled.resize(L); enc_a.resize(L); dec_a.resize(L); dec_b.resize(L);
-    skip[0] = run.alloc((size_t)net.skip_c[0] * P.voxels());
-    for (int i = 0; i < L; ++i) {
-      const size_t below = P.shifted(i + 1).voxels(), here = P.shifted(i).voxels();
-      pooled[i] = run.alloc((size_t)net.skip_c[i] * below);
-      enc_a[i] = run.alloc((size_t)net.skip_c[i + 1] * below);
-      skip[i + 1] = run.alloc((size_t)net.skip_c[i + 1] * below);
-      dec_a[i] = run.alloc((size_t)net.dec_c[i] * here);
-      dec_b[i] = run.alloc((size_t)net.dec_c[i] * here);
-    }
-    out = run.alloc((size_t)net.final.c_out * P.voxels());
-  }
-  const float* forward(const float* x) {
-    const int L = net.L;
-    run.conv(net.init, x, 1, nullptr, 0, P, skip[0]);
-    for (int i = 0; i < L; ++i) {
-      const Dims D = P.shifted(i + 1);
-      const int c = net.skip_c[i + 1];
-      run.maxpool(skip[i], pooled[i], net.skip_c[i], P.shifted(i));
-      run.conv(net.enc[2 * i], pooled[i], net.skip_c[i], nullptr, 0, D, enc_a[i]);
-      run.norm_lrelu(enc_a[i], enc_a[i], c, D.voxels());
-      run.conv(net.enc[2 * i + 1], enc_a[i], c, nullptr, 0, D, skip[i + 1]);
-      run.norm_lrelu(skip[i + 1], skip[i + 1], c, D.voxels());
-    }
-    const float* cur = skip[L];
-    for (int i = L - 1; i >= 0; --i) {
-      const Dims D = P.shifted(i);
-      const int c = net.dec_c[i];
-      run.conv(net.dec[2 * i], skip[i], net.skip_c[i], cur, 1, D, dec_a[i]);
-      run.norm_lrelu(dec_a[i], dec_a[i], c, D.voxels());
-      run.conv(net.dec[2 * i + 1], dec_a[i], c, nullptr, 0, D, dec_b[i]);
-      run.norm_lrelu(dec_b[i], dec_b[i], c, D.voxels());
-      cur = dec_b[i];
-    }
-    run.conv(net.final, cur, net.final.c_in, nullptr, 0, P, out);
-    return out;
-  }
-};
-
 constexpr int kMaxLevels = 8;
 constexpr int kClasses = 9;
 
@@ -616,7 +383,7 @@ void check_run(const mcgpu_segment_options& o, const void* image, const unsigned
   if (o.n_filters[2 * L + 1] != o.n_filters[2 * L])
     refuse(fn, "inconsistent weight shapes: final_conv takes " + std::to_string(o.n_filters[2 * L + 1]) + " channels but dec_0 gives " + std::to_string(o.n_filters[2 * L]));
   size_t expect = 0;
-  NetLayers(L, o.n_filters, o.n_classes, expect);
+  NetLayers(1, L, o.n_filters, o.n_classes, expect);
   if (o.n_weights != expect)
     refuse(fn, "inconsistent weight shapes: n_weights is " + std::to_string(o.n_weights) + " but the architecture has " + std::to_string(expect) + " values");
   for (int a = 0; a < 3; ++a)
@@ -673,13 +440,13 @@ struct RunBuffers {
 
 // every buffer of a run, in one place: made on the device, or (Runner::dry) only added up
 void make_buffers(Runner& R, const mcgpu_segment_options& o, const void* image, NetLayers& net, const Dims& P, const Dims& V, RunBuffers& b,
-                  std::unique_ptr<NetPass>& pass) {
+                  std::unique_ptr<NetPass<Runner, Dims>>& pass) {
   R.init(o.device, net.widest());
   b.d_weights = R.upload(o.weights, (size_t)o.n_weights);
   net.each([&](ConvLayer& l) { R.pack(l, b.d_weights); });
   b.d_image = R.upload((const char*)image, image_bytes(o));
   b.d_x = R.alloc(P.voxels());
-  pass.reset(new NetPass(net, R, P));
+  pass.reset(new NetPass<Runner, Dims>(net, R, P));
   b.d_prob = R.alloc((size_t)kClasses * P.voxels());
   b.d_k = R.alloc((size_t)kClasses * V.voxels());
   b.d_sum = R.alloc((size_t)kClasses * V.voxels());
@@ -687,11 +454,6 @@ void make_buffers(Runner& R, const mcgpu_segment_options& o, const void* image, 
   b.d_labels = (unsigned char*)R.alloc_bytes((size_t)kClasses * V.voxels(), true);
 }
 
-void finish(Runner& R, const std::chrono::steady_clock::time_point& t0, mcgpu_segment_report* report) {
-  R.rep.peak_device_bytes = R.dev.peak;
-  R.rep.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  if (report) *report = R.rep;
-}
 
 }  // namespace
 
@@ -707,13 +469,13 @@ extern "C" int mcgpu_segment_run(const mcgpu_segment_options* caller_o, const vo
   check_run(o, image, labels, V, left, patches, n_rule);
   const auto t0 = std::chrono::steady_clock::now();
   size_t cursor = 0;
-  NetLayers net(o.levels, o.n_filters, o.n_classes, cursor);
+  NetLayers net(1, o.levels, o.n_filters, o.n_classes, cursor);
   size_t needed = 0;
   {
     Runner plan;
     plan.dry = true;
     RunBuffers b;
-    std::unique_ptr<NetPass> pass;
+    std::unique_ptr<NetPass<Runner, Dims>> pass;
     make_buffers(plan, o, image, net, P, V, b, pass);
     needed = plan.planned;
   }
@@ -726,7 +488,7 @@ extern "C" int mcgpu_segment_run(const mcgpu_segment_options* caller_o, const vo
   if (needed > free_bytes)
     refuse(fn, "the call needs " + std::to_string(needed) + " bytes of device memory, the device has " + std::to_string(free_bytes) + " free");
   RunBuffers b;
-  std::unique_ptr<NetPass> pass;
+  std::unique_ptr<NetPass<Runner, Dims>> pass;
   {
     const auto u0 = std::chrono::steady_clock::now();
     make_buffers(R, o, image, net, P, V, b, pass);
@@ -804,37 +566,9 @@ extern "C" int mcgpu_segment_stage(const mcgpu_segment_options* caller_o, int st
   Runner R;
   R.init(o.device, stage == MCGPU_SEGMENT_STAGE_NORM_LRELU ? a.c1 : 1);
   switch (stage) {
-    case MCGPU_SEGMENT_STAGE_CONV: {
-      const Dims E = a.upsample ? D.halved_up() : D;
-      size_t cursor = 0;
-      ConvLayer l = conv_layer(a.c1 + a.c2, a.c_out, cursor);
-      std::vector<float> flat(cursor);
-      memcpy(flat.data() + l.w_off, a.weight, (size_t)l.c_out * l.c_in * kTaps * sizeof(float));
-      memcpy(flat.data() + l.b_off, a.bias, (size_t)l.c_out * sizeof(float));
-      const float* d_weights = R.upload(flat.data(), flat.size());
-      R.pack(l, d_weights);
-      const float* d_in = R.upload(a.in, (size_t)a.c1 * n);
-      const float* d_in2 = a.c2 ? R.upload(a.in2, (size_t)a.c2 * E.voxels()) : nullptr;
-      float* d_out = R.alloc((size_t)a.c_out * n);
-      R.conv(l, d_in, a.c1, d_in2, a.upsample, D, d_out);
-      HIP_TRY(hipMemcpy(a.out, d_out, (size_t)a.c_out * n * 4, hipMemcpyDeviceToHost));
-      break;
-    }
-    case MCGPU_SEGMENT_STAGE_NORM_LRELU: {
-      const float* d_in = R.upload(a.in, (size_t)a.c1 * n);
-      float* d_out = R.alloc((size_t)a.c1 * n);
-      R.norm_lrelu(d_in, d_out, a.c1, n);
-      HIP_TRY(hipMemcpy(a.out, d_out, (size_t)a.c1 * n * 4, hipMemcpyDeviceToHost));
-      break;
-    }
-    case MCGPU_SEGMENT_STAGE_MAXPOOL: {
-      const size_t n_out = (size_t)a.c1 * D.shifted(1).voxels();
-      const float* d_in = R.upload(a.in, (size_t)a.c1 * n);
-      float* d_out = R.alloc(n_out);
-      R.maxpool(d_in, d_out, a.c1, D);
-      if (n_out) HIP_TRY(hipMemcpy(a.out, d_out, n_out * 4, hipMemcpyDeviceToHost));
-      break;
-    }
+    case MCGPU_SEGMENT_STAGE_CONV: stage_conv(R, a, D); break;
+    case MCGPU_SEGMENT_STAGE_NORM_LRELU: stage_norm_lrelu(R, a, n); break;
+    case MCGPU_SEGMENT_STAGE_MAXPOOL: stage_maxpool(R, a, D); break;
     case MCGPU_SEGMENT_STAGE_HEAD: {
       const float* d_in = R.upload(a.in, (size_t)kClasses * n);
       float* d_out = R.alloc((size_t)kClasses * n);

@@ -28,9 +28,9 @@
 //   Thin ends: NO layer takes a VALU kernel.  init_conv (C_in <= 2), the two final_conv (C_out = 1) and the 16/32-channel
 //     variance net run on the same MFMA kernel with zero padding (C_out <= 32 takes the 32-channel variant).  Their padded
 //     arithmetic is under 4 % of the mean net's; profiles/speedup_ab.md has the per-layer table.
-//   stats_kernel + norm_lrelu_kernel: sum and sum of squares per channel in float64, over fixed segments and a fixed tree (no
-//     atomics: the same input gives the same bytes), the normalisation applied in float64 and rounded once.  A pass of its own;
-//     applying it when the next convolution stages its input was not tried.
+//   Instance norm (stats_kernel + norm_lrelu_kernel: float64 sums over fixed segments and a fixed tree, normalised in float64, rounded
+//     once), the packing of the weights, the plan of the layers and the launches of a forward pass are unet_common.inc's, shared with
+//     segment_net.hip.  The norm is a pass of its own; applying it when the next convolution stages its input was not tried.
 //   maxpool_kernel, preprocess_kernel (statistics in float64 by stats_kernel, applied in float32), head_mean_kernel,
 //     head_variance_kernel, sample_kernel.
 // One projection at a time (the reference runs batch size 1 per sample in effect: instance norm keeps samples independent); the
@@ -42,19 +42,13 @@
 
 namespace {
 
-using mcgpu::CallDevice;
-using mcgpu::Stage;
-
-[[noreturn]] void refuse(const char* fn, const std::string& what) { throw mcgpu::Error(-1, std::string("!!ERROR!! ") + fn + ": " + what); }
+constexpr int kTaps = 9;  // 3 x 3: what unet_common.inc sizes a K chunk and counts the weights with
+#include "unet_common.inc"
 
 // ---------------------------------------------------------------------------------------------------------------- convolution
 constexpr int kTileW = 32, kTileH = 8;                   // pixels of a workgroup: 4 waves x 2 rows x 32 columns
-constexpr int kCK = 8;                                   // input channels per K chunk
 constexpr int kHaloW = kTileW + 2, kHaloH = kTileH + 2;  // the staged tile
 constexpr int kHalo = kHaloW * kHaloH;
-constexpr int kKK = kCK * 9;                             // K of a chunk
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct ConvArgs {
   const float* src1;   // [c1][H][W]
@@ -65,20 +59,6 @@ struct ConvArgs {
   float* out;          // [c_out][H][W]
   int c_out, n_chunks;
 };
-
-// w [c_out][c_in][3][3] -> the staging order of conv3x3_mfma_kernel<NB>, zero where the channel does not exist
-__global__ __launch_bounds__(256) void pack_weights_kernel(const float* w, float* wpack, int c_in, int c_out, int n_chunks, int ncol, size_t total) {
-  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= total) return;
-  const int co_local = (int)(e % ncol);
-  size_t r = e / ncol;
-  const int kk = (int)(r % kKK);
-  r /= kKK;
-  const int ch = (int)(r % n_chunks), cb = (int)(r / n_chunks);
-  const int hh = kk & 1, tap = (kk >> 1) % 9, cp = (kk >> 1) / 9;
-  const int ci = ch * kCK + cp * 2 + hh, co = cb * ncol + co_local;
-  wpack[e] = (ci < c_in && co < c_out) ? w[((size_t)co * c_in + ci) * 9 + tap] : 0.f;
-}
 
 // What one thread moves per K chunk, global -> registers -> LDS.  The loads of chunk k + 1 are issued before the MFMAs of chunk k and
 // land during them; every load is unconditional (clamped index, value masked), so that they go out together and not one per wait.
@@ -185,72 +165,6 @@ __global__ __launch_bounds__(256) void conv3x3_mfma_kernel(ConvArgs a) {
   }
 }
 
-// ------------------------------------------------------------------------------------------------- instance norm + LeakyReLU
-constexpr int kMaxSegments = 64;
-constexpr size_t kSegmentPixels = 16384;
-
-int segments_of(size_t hw) { return (int)std::min<size_t>(kMaxSegments, (hw + kSegmentPixels - 1) / kSegmentPixels); }
-
-// part[c][s] = (sum, sum of squares) of segment s of channel c, in float64 and in a fixed order
-__global__ __launch_bounds__(256) void stats_kernel(const float* x, size_t hw, int S, double2* part) {
-  __shared__ double s_sum[256], s_sq[256];
-  const int c = blockIdx.y, s = blockIdx.x, tid = threadIdx.x;
-  const size_t seg = (hw + S - 1) / S, lo = (size_t)s * seg, hi = min(lo + seg, hw);
-  const float* p = x + (size_t)c * hw;
-  double sum[4] = {0.0, 0.0, 0.0, 0.0}, sq[4] = {0.0, 0.0, 0.0, 0.0};  // four chains: four loads in flight, the order still fixed
-  size_t i = lo + tid;
-  for (; i + 768 < hi; i += 1024) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const double v = p[i + 256 * k];
-      sum[k] += v;
-      sq[k] += v * v;
-    }
-  }
-  for (; i < hi; i += 256) {
-    const double v = p[i];
-    sum[0] += v;
-    sq[0] += v * v;
-  }
-  s_sum[tid] = (sum[0] + sum[1]) + (sum[2] + sum[3]);
-  s_sq[tid] = (sq[0] + sq[1]) + (sq[2] + sq[3]);
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (tid < w) {
-      s_sum[tid] += s_sum[tid + w];
-      s_sq[tid] += s_sq[tid + w];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) part[(size_t)c * S + s] = make_double2(s_sum[0], s_sq[0]);
-}
-
-__device__ double2 fold_segments(const double2* part, int S) {
-  double sum = 0.0, sq = 0.0;
-  for (int s = 0; s < S; ++s) {
-    sum += part[s].x;
-    sq += part[s].y;
-  }
-  return make_double2(sum, sq);
-}
-
-__global__ __launch_bounds__(256) void norm_lrelu_kernel(const float* x, float* y, size_t hw, int S, const double2* part) {
-  __shared__ double s_mean, s_rstd;
-  const int c = blockIdx.y;
-  if (threadIdx.x == 0) {
-    const double2 t = fold_segments(part + (size_t)c * S, S);
-    const double m = t.x / (double)hw, var = fmax(t.y / (double)hw - m * m, 0.0);
-    s_mean = m;
-    s_rstd = 1.0 / sqrt(var + 1e-5);
-  }
-  __syncthreads();
-  const double m = s_mean, rstd = s_rstd;
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= hw) return;
-  const float v = (float)(((double)x[(size_t)c * hw + i] - m) * rstd);
-  y[(size_t)c * hw + i] = v > 0.f ? v : 0.01f * v;
-}
-
 // ------------------------------------------------------------------------------------------------------------- small kernels
 __global__ __launch_bounds__(256) void maxpool_kernel(const float* x, float* y, int C, int H, int W) {
   const int Ho = H >> 1, Wo = W >> 1;
@@ -319,112 +233,58 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* mean, const fl
   out[i] = mean ? mean[i] + sqrtf(variance[i]) * z : z;
 }
 
-unsigned blocks_of(size_t n) { return (unsigned)((n + 255) / 256); }
-
 // -------------------------------------------------------------------------------------------------------------------- host
+struct Dims {
+  int H, W;
+  size_t voxels() const { return (size_t)H * W; }
+  Dims shifted(int s) const { return {H >> s, W >> s}; }
+  Dims halved_up() const { return {(H + 1) / 2, (W + 1) / 2}; }
+};
+
 struct NetShape { int in_channels, levels, base; };
 
-struct ConvLayer {
-  int c_in = 0, c_out = 0;
-  size_t w_off = 0, b_off = 0;  // in the flat weights
-  int nb = 1, n_chunks = 0;
-  float* wpack = nullptr;
-  const float* bias = nullptr;
-  size_t pack_floats() const { return (size_t)((c_out + 32 * nb - 1) / (32 * nb)) * n_chunks * kKK * 32 * nb; }
-};
-
-ConvLayer conv_layer(int c_in, int c_out, size_t& cursor) {
-  ConvLayer l;
-  l.c_in = c_in;
-  l.c_out = c_out;
-  l.w_off = cursor;
-  cursor += (size_t)c_out * c_in * 9;
-  l.b_off = cursor;
-  cursor += (size_t)c_out;
-  l.nb = c_out > 32 ? 2 : 1;
-  l.n_chunks = (c_in + kCK - 1) / kCK;
-  return l;
+// FlexUNet(C, L, base F) as unet_common.inc's NetLayers: init F, enc_i and dec_i F 2^i, final F, one class
+NetLayers layers_of(const NetShape& s, size_t& cursor) {
+  std::vector<int> f{s.base};
+  for (int i = 0; i < s.levels; ++i) f.push_back(s.base << i);
+  for (int i = s.levels - 1; i >= 0; --i) f.push_back(s.base << i);
+  f.push_back(s.base);
+  return NetLayers(s.in_channels, s.levels, f.data(), 1, cursor);
 }
 
-// the convolutions of one FlexUNet in the state dict's order: init, final, enc_0 .. enc_{L-1}, dec_{L-1} .. dec_0
-struct NetLayers {
-  NetShape s;
-  ConvLayer init, final;
-  std::vector<ConvLayer> enc, dec;  // [2 i], [2 i + 1] of level i
-  NetLayers(const NetShape& shape, size_t& cursor) : s(shape), enc(2 * shape.levels), dec(2 * shape.levels) {
-    const int F = s.base, L = s.levels;
-    init = conv_layer(s.in_channels, F, cursor);
-    final = conv_layer(F, 1, cursor);
-    for (int i = 0; i < L; ++i) {
-      const int out = F << i, in = i ? F << (i - 1) : F;
-      enc[2 * i] = conv_layer(in, out, cursor);
-      enc[2 * i + 1] = conv_layer(out, out, cursor);
-    }
-    for (int i = L - 1; i >= 0; --i) {
-      const int out = F << i, skip = i ? F << (i - 1) : F, below = i == L - 1 ? F << (L - 1) : F << (i + 1);
-      dec[2 * i] = conv_layer(skip + below, out, cursor);
-      dec[2 * i + 1] = conv_layer(out, out, cursor);
-    }
-  }
-  template <class F>
-  void each(F f) {
-    f(init);
-    f(final);
-    for (auto& l : enc) f(l);
-    for (auto& l : dec) f(l);
-  }
-};
+int blocks_per_workgroup(int c_out) { return c_out > 32 ? 2 : 1; }  // of 32 output channels: the variant of conv3x3_mfma_kernel
 
-struct Runner {
-  CallDevice dev;
-  mcgpu_speedup_report rep;
-  double2* d_part = nullptr;   // statistics of the widest layer
+struct Runner : RunnerBase<mcgpu_speedup_report> {
   double2* d_part2 = nullptr;  // the second image of the preprocessing
-  int max_channels = 1;
 
-  Runner() { memset(&rep, 0, sizeof rep); }
   void init(int device, int channels) {
-    HIP_TRY(hipSetDevice(device));
-    dev.events();
-    max_channels = std::max(channels, 1);
-    d_part = dev.alloc_zeroed<double2>((size_t)max_channels * kMaxSegments * sizeof(double2));
-    d_part2 = dev.alloc_zeroed<double2>(kMaxSegments * sizeof(double2));
+    RunnerBase::init(device, channels);
+    d_part2 = (double2*)alloc_bytes(kMaxSegments * sizeof(double2), true);
   }
-  float* alloc(size_t floats) { return dev.alloc_zeroed<float>(std::max<size_t>(floats, 1) * sizeof(float)); }
-
-  void pack(ConvLayer& l, const float* d_weights) {
-    const size_t total = l.pack_floats();
-    l.wpack = dev.alloc<float>(total * sizeof(float));
-    l.bias = d_weights + l.b_off;
-    hipLaunchKernelGGL(pack_weights_kernel, dim3(blocks_of(total)), dim3(256), 0, nullptr, d_weights + l.w_off, l.wpack, l.c_in, l.c_out, l.n_chunks,
-                       32 * l.nb, total);
+  void pack_net(NetLayers& net, const float* d_weights) {
+    net.each([&](ConvLayer& l) {
+      l.nb = blocks_per_workgroup(l.c_out);
+      pack(l, d_weights);
+    });
   }
 
   // out [c_out][H][W] = conv(cat(src1 [c1], src2 [c_in - c1] (upsampled when ups))) + bias
-  void conv(const ConvLayer& l, const float* src1, int c1, const float* src2, int ups, int H, int W, float* out) {
+  void conv(const ConvLayer& l, const float* src1, int c1, const float* src2, int ups, const Dims& D, float* out) {
     Stage st(dev, rep.ms_conv);
+    const Dims E = ups ? D.halved_up() : D;
     ConvArgs a;
-    a.src1 = src1; a.src2 = src2; a.c1 = c1; a.c2 = l.c_in - c1; a.H = H; a.W = W; a.ups = ups ? 1 : 0;
-    a.H2 = ups ? (H + 1) / 2 : H; a.W2 = ups ? (W + 1) / 2 : W;
+    a.src1 = src1; a.src2 = src2; a.c1 = c1; a.c2 = l.c_in - c1; a.H = D.H; a.W = D.W; a.ups = ups ? 1 : 0;
+    a.H2 = E.H; a.W2 = E.W;
     a.wpack = l.wpack; a.bias = l.bias; a.out = out; a.c_out = l.c_out; a.n_chunks = l.n_chunks;
-    const dim3 grid((unsigned)((W + kTileW - 1) / kTileW), (unsigned)((H + kTileH - 1) / kTileH), (unsigned)((l.c_out + 32 * l.nb - 1) / (32 * l.nb)));
+    const dim3 grid((unsigned)((D.W + kTileW - 1) / kTileW), (unsigned)((D.H + kTileH - 1) / kTileH), (unsigned)((l.c_out + 32 * l.nb - 1) / (32 * l.nb)));
     if (l.nb == 2) hipLaunchKernelGGL(conv3x3_mfma_kernel<2>, grid, dim3(256), 0, nullptr, a);
     else hipLaunchKernelGGL(conv3x3_mfma_kernel<1>, grid, dim3(256), 0, nullptr, a);
     st.done();
   }
-  void stats(const float* x, int C, size_t hw, double2* part) {
-    hipLaunchKernelGGL(stats_kernel, dim3((unsigned)segments_of(hw), (unsigned)C), dim3(256), 0, nullptr, x, hw, segments_of(hw), part);
-  }
-  void norm_lrelu(const float* x, float* y, int C, size_t hw) {
-    Stage st(dev, rep.ms_norm);
-    stats(x, C, hw, d_part);
-    hipLaunchKernelGGL(norm_lrelu_kernel, dim3(blocks_of(hw), (unsigned)C), dim3(256), 0, nullptr, x, y, hw, segments_of(hw), d_part);
-    st.done();
-  }
-  void maxpool(const float* x, float* y, int C, int H, int W) {
+  void maxpool(const float* x, float* y, int C, const Dims& D) {
     Stage st(dev, rep.ms_other);
-    const size_t n = (size_t)C * (H / 2) * (W / 2);
-    if (n) hipLaunchKernelGGL(maxpool_kernel, dim3(blocks_of(n)), dim3(256), 0, nullptr, x, y, C, H, W);
+    const size_t n = (size_t)C * D.shifted(1).voxels();
+    if (n) hipLaunchKernelGGL(maxpool_kernel, dim3(blocks_of(n)), dim3(256), 0, nullptr, x, y, C, D.H, D.W);
     st.done();
   }
   void preprocess(const float* lp, const float* fp, float* out, size_t hw) {
@@ -438,52 +298,6 @@ struct Runner {
     Stage st(dev, rep.ms_other);
     hipLaunchKernelGGL(sample_kernel, dim3(blocks_of(hw)), dim3(256), 0, nullptr, mean, variance, out, W, hw, projection, seed);
     st.done();
-  }
-};
-
-// One FlexUNet at one image size: its buffers, made once, and the launches of a forward pass
-struct NetPass {
-  NetLayers& net;
-  Runner& run;
-  int H, W;
-  std::vector<float*> skip, pooled, enc_a, dec_a, dec_b;
-  float* out = nullptr;
-  NetPass(NetLayers& n, Runner& r, int h, int w) : net(n), run(r), H(h), W(w) {
-    const int L = net.s.levels, F = net.s.base;
-    skip.resize(L + 1); pooled.resize(L); enc_a.resize(L); dec_a.resize(L); dec_b.resize(L);
-    skip[0] = run.alloc((size_t)F * H * W);
-    for (int i = 0; i < L; ++i) {
-      const size_t px = (size_t)(H >> (i + 1)) * (W >> (i + 1));
-      pooled[i] = run.alloc((size_t)(i ? F << (i - 1) : F) * px);
-      enc_a[i] = run.alloc((size_t)(F << i) * px);
-      skip[i + 1] = run.alloc((size_t)(F << i) * px);
-      dec_a[i] = run.alloc((size_t)(F << i) * (H >> i) * (W >> i));
-      dec_b[i] = run.alloc((size_t)(F << i) * (H >> i) * (W >> i));
-    }
-    out = run.alloc((size_t)H * W);
-  }
-  const float* forward(const float* x) {
-    const int L = net.s.levels, F = net.s.base;
-    run.conv(net.init, x, net.s.in_channels, nullptr, 0, H, W, skip[0]);
-    for (int i = 0; i < L; ++i) {
-      const int h = H >> (i + 1), w = W >> (i + 1), c_in = i ? F << (i - 1) : F, c = F << i;
-      run.maxpool(skip[i], pooled[i], c_in, H >> i, W >> i);
-      run.conv(net.enc[2 * i], pooled[i], c_in, nullptr, 0, h, w, enc_a[i]);
-      run.norm_lrelu(enc_a[i], enc_a[i], c, (size_t)h * w);
-      run.conv(net.enc[2 * i + 1], enc_a[i], c, nullptr, 0, h, w, skip[i + 1]);
-      run.norm_lrelu(skip[i + 1], skip[i + 1], c, (size_t)h * w);
-    }
-    const float* cur = skip[L];
-    for (int i = L - 1; i >= 0; --i) {
-      const int h = H >> i, w = W >> i, c_skip = i ? F << (i - 1) : F, c = F << i;
-      run.conv(net.dec[2 * i], skip[i], c_skip, cur, 1, h, w, dec_a[i]);
-      run.norm_lrelu(dec_a[i], dec_a[i], c, (size_t)h * w);
-      run.conv(net.dec[2 * i + 1], dec_a[i], c, nullptr, 0, h, w, dec_b[i]);
-      run.norm_lrelu(dec_b[i], dec_b[i], c, (size_t)h * w);
-      cur = dec_b[i];
-    }
-    run.conv(net.final, cur, F, nullptr, 0, H, W, out);
-    return out;
   }
 };
 
@@ -505,8 +319,8 @@ void check_run(const mcgpu_speedup_options& o, const float* low_photon, const fl
   if (m.in_channels == 2 && !forward_projection) refuse(fn, "forward_projection is NULL but the mean net has 2 input channels");
   if (m.in_channels == 1 && forward_projection) refuse(fn, "the mean net has 1 input channel: forward_projection must be NULL");
   size_t expect = 0;
-  NetLayers(m, expect);
-  NetLayers(v, expect);
+  layers_of(m, expect);
+  layers_of(v, expect);
   if (o.n_weights != expect)
     refuse(fn, "n_weights is " + std::to_string(o.n_weights) + " but the architecture has " + std::to_string(expect) + " values");
   const int deep = std::max(m.levels, v.levels);
@@ -525,12 +339,6 @@ void check_run(const mcgpu_speedup_options& o, const float* low_photon, const fl
   }
 }
 
-void finish(Runner& R, const std::chrono::steady_clock::time_point& t0, mcgpu_speedup_report* report) {
-  R.rep.peak_device_bytes = R.dev.peak;
-  R.rep.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  if (report) *report = R.rep;
-}
-
 }  // namespace
 
 extern "C" int mcgpu_speedup_run(const mcgpu_speedup_options* caller_o, const float* low_photon, const float* forward_projection, float* mean,
@@ -541,18 +349,18 @@ extern "C" int mcgpu_speedup_run(const mcgpu_speedup_options* caller_o, const fl
   check_run(o, low_photon, forward_projection);
   const auto t0 = std::chrono::steady_clock::now();
   size_t cursor = 0;
-  NetLayers mean_net({o.mean_in_channels, o.mean_levels, o.mean_filter_base}, cursor);
-  NetLayers var_net({o.var_in_channels, o.var_levels, o.var_filter_base}, cursor);
+  NetLayers mean_net = layers_of({o.mean_in_channels, o.mean_levels, o.mean_filter_base}, cursor);
+  NetLayers var_net = layers_of({o.var_in_channels, o.var_levels, o.var_filter_base}, cursor);
   Runner R;
-  R.init(o.device, std::max(o.mean_filter_base << (o.mean_levels - 1), o.var_filter_base << (o.var_levels - 1)));
-  const int H = o.nv, W = o.nu;
-  const size_t hw = (size_t)H * W;
+  R.init(o.device, std::max(mean_net.widest(), var_net.widest()));
+  const Dims D{o.nv, o.nu};
+  const size_t hw = D.voxels();
   float *d_x, *d_fp, *d_mean, *d_var, *d_sample;
   {
     Stage st(R.dev, R.rep.ms_upload);
-    const float* d_weights = R.dev.upload(o.weights, (size_t)o.n_weights);
-    mean_net.each([&](ConvLayer& l) { R.pack(l, d_weights); });
-    var_net.each([&](ConvLayer& l) { R.pack(l, d_weights); });
+    const float* d_weights = R.upload(o.weights, (size_t)o.n_weights);
+    R.pack_net(mean_net, d_weights);
+    R.pack_net(var_net, d_weights);
     st.done();
   }
   d_x = R.alloc(2 * hw);  // channel 0: the low-photon projection, channel 1: the matched forward projection
@@ -560,7 +368,7 @@ extern "C" int mcgpu_speedup_run(const mcgpu_speedup_options* caller_o, const fl
   d_mean = R.alloc(hw);
   d_var = R.alloc(hw);
   d_sample = R.alloc(hw);
-  NetPass mean_pass(mean_net, R, H, W), var_pass(var_net, R, H, W);
+  NetPass<Runner, Dims> mean_pass(mean_net, R, D), var_pass(var_net, R, D);
   for (int p = 0; p < o.n; ++p) {
     {
       Stage st(R.dev, R.rep.ms_upload);
@@ -581,7 +389,7 @@ extern "C" int mcgpu_speedup_run(const mcgpu_speedup_options* caller_o, const fl
       hipLaunchKernelGGL(head_variance_kernel, dim3(blocks_of(hw)), dim3(256), 0, nullptr, d_mean, net_var, d_var, hw);
       st.done();
     }
-    if (sample) R.normals(d_mean, d_var, d_sample, W, hw, (unsigned)(o.first_projection + p), o.seed);
+    if (sample) R.normals(d_mean, d_var, d_sample, D.W, hw, (unsigned)(o.first_projection + p), o.seed);
     {
       Stage st(R.dev, R.rep.ms_upload);
       if (mean) HIP_TRY(hipMemcpy(mean + (size_t)p * hw, d_mean, hw * 4, hipMemcpyDeviceToHost));
@@ -605,8 +413,8 @@ extern "C" int mcgpu_speedup_stage(const mcgpu_speedup_options* caller_o, int st
   if (stage < MCGPU_SPEEDUP_STAGE_CONV || stage > MCGPU_SPEEDUP_STAGE_NORMALS) refuse(fn, "unknown stage " + std::to_string(stage));
   if (!a.out) refuse(fn, "out is NULL");
   if (stage != MCGPU_SPEEDUP_STAGE_NORMALS && !a.in) refuse(fn, "in is NULL");
-  const int H = o.nv, W = o.nu;
-  const size_t hw = (size_t)H * W;
+  const Dims D{o.nv, o.nu};
+  const size_t hw = D.voxels();
   if (stage <= MCGPU_SPEEDUP_STAGE_MAXPOOL && (a.c1 < 1 || a.c1 > 65536)) refuse(fn, "c1 must be 1..65536");
   if (stage == MCGPU_SPEEDUP_STAGE_CONV) {
     if (a.c2 < 0 || a.c2 > 65536 || a.c_out < 1 || a.c_out > 65536) refuse(fn, "c2 must be 0..65536 and c_out 1..65536");
@@ -619,40 +427,12 @@ extern "C" int mcgpu_speedup_stage(const mcgpu_speedup_options* caller_o, int st
   Runner R;
   R.init(o.device, stage == MCGPU_SPEEDUP_STAGE_NORM_LRELU ? a.c1 : 1);
   switch (stage) {
-    case MCGPU_SPEEDUP_STAGE_CONV: {
-      const int H2 = a.upsample ? (H + 1) / 2 : H, W2 = a.upsample ? (W + 1) / 2 : W;
-      size_t cursor = 0;
-      ConvLayer l = conv_layer(a.c1 + a.c2, a.c_out, cursor);
-      std::vector<float> flat(cursor);
-      memcpy(flat.data() + l.w_off, a.weight, (size_t)l.c_out * l.c_in * 9 * sizeof(float));
-      memcpy(flat.data() + l.b_off, a.bias, (size_t)l.c_out * sizeof(float));
-      const float* d_weights = R.dev.upload(flat);
-      R.pack(l, d_weights);
-      const float* d_in = R.dev.upload(a.in, (size_t)a.c1 * hw);
-      const float* d_in2 = a.c2 ? R.dev.upload(a.in2, (size_t)a.c2 * H2 * W2) : nullptr;
-      float* d_out = R.alloc((size_t)a.c_out * hw);
-      R.conv(l, d_in, a.c1, d_in2, a.upsample, H, W, d_out);
-      HIP_TRY(hipMemcpy(a.out, d_out, (size_t)a.c_out * hw * 4, hipMemcpyDeviceToHost));
-      break;
-    }
-    case MCGPU_SPEEDUP_STAGE_NORM_LRELU: {
-      const float* d_in = R.dev.upload(a.in, (size_t)a.c1 * hw);
-      float* d_out = R.alloc((size_t)a.c1 * hw);
-      R.norm_lrelu(d_in, d_out, a.c1, hw);
-      HIP_TRY(hipMemcpy(a.out, d_out, (size_t)a.c1 * hw * 4, hipMemcpyDeviceToHost));
-      break;
-    }
-    case MCGPU_SPEEDUP_STAGE_MAXPOOL: {
-      const size_t n_out = (size_t)a.c1 * (H / 2) * (W / 2);
-      const float* d_in = R.dev.upload(a.in, (size_t)a.c1 * hw);
-      float* d_out = R.alloc(n_out);
-      R.maxpool(d_in, d_out, a.c1, H, W);
-      if (n_out) HIP_TRY(hipMemcpy(a.out, d_out, n_out * 4, hipMemcpyDeviceToHost));
-      break;
-    }
+    case MCGPU_SPEEDUP_STAGE_CONV: stage_conv(R, a, D, blocks_per_workgroup(a.c_out)); break;
+    case MCGPU_SPEEDUP_STAGE_NORM_LRELU: stage_norm_lrelu(R, a, hw); break;
+    case MCGPU_SPEEDUP_STAGE_MAXPOOL: stage_maxpool(R, a, D); break;
     case MCGPU_SPEEDUP_STAGE_PREPROCESS: {
-      const float* d_lp = R.dev.upload(a.in, (size_t)o.n * hw);
-      const float* d_fp = R.dev.upload(a.in2, (size_t)o.n * hw);
+      const float* d_lp = R.upload(a.in, (size_t)o.n * hw);
+      const float* d_fp = R.upload(a.in2, (size_t)o.n * hw);
       float* d_out = R.alloc((size_t)o.n * hw);
       for (int p = 0; p < o.n; ++p) R.preprocess(d_lp + (size_t)p * hw, d_fp + (size_t)p * hw, d_out + (size_t)p * hw, hw);
       HIP_TRY(hipMemcpy(a.out, d_out, (size_t)o.n * hw * 4, hipMemcpyDeviceToHost));
@@ -660,7 +440,7 @@ extern "C" int mcgpu_speedup_stage(const mcgpu_speedup_options* caller_o, int st
     }
     default: {
       float* d_out = R.alloc((size_t)o.n * hw);
-      for (int p = 0; p < o.n; ++p) R.normals(nullptr, nullptr, d_out + (size_t)p * hw, W, hw, (unsigned)(o.first_projection + p), o.seed);
+      for (int p = 0; p < o.n; ++p) R.normals(nullptr, nullptr, d_out + (size_t)p * hw, D.W, hw, (unsigned)(o.first_projection + p), o.seed);
       HIP_TRY(hipMemcpy(a.out, d_out, (size_t)o.n * hw * 4, hipMemcpyDeviceToHost));
     }
   }

@@ -15,10 +15,11 @@ from __future__ import annotations
 
 import ctypes as C
 import re
-from pathlib import Path
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
+
+from . import _unet
 
 LABELS = {0: "background", 1: "upper_body_bones", 2: "upper_body_muscles", 3: "upper_body_fat", 4: "liver", 5: "stomach", 6: "lung", 7: "other",
           8: "lung_vessels"}  # 0 .. 7: one softmax group; 8: sigmoid
@@ -64,10 +65,6 @@ def _library():
     return lib
 
 
-def _report(rep: _SegmentReport) -> dict:
-    return {name: getattr(rep, name) for name, _ in _SegmentReport._fields_}
-
-
 # ---------------------------------------------------------------------------------------------------------------- patches
 def padded_shape(array_shape: Sequence[int], patch_shape: Sequence[int]) -> Tuple[int, ...]:
     """The shape after the reference's `pad_image`: every axis at least as long as the patch."""
@@ -107,24 +104,8 @@ def patch_starts(array_shape: Sequence[int], patch_shape: Sequence[int], stride:
 
 # ---------------------------------------------------------------------------------------------------------------- weights
 def unet_tensors(n_filters: Sequence[int], levels: int, n_classes: int = N_LABELS, in_channels: int = 1) -> List[Tuple[str, Tuple[int, ...]]]:
-    """(name, shape) of FlexUNet(n_channels, n_classes, n_levels, n_filters=[init, enc_0.., dec_{L-1}.., final]).state_dict(), in its
-    order: init_conv, final_conv, enc_0 .. enc_{L-1}, dec_{L-1} .. dec_0; each block holds its two convolutions as convs.0, convs.3."""
-    f = [int(v) for v in n_filters]
-    if len(f) != 2 * levels + 2:
-        raise ValueError(f"{len(f)} filter counts for {levels} levels, expected {2 * levels + 2}")
-
-    def conv(name, c_in, c_out):
-        return [(f"{name}.weight", (c_out, c_in, 3, 3, 3)), (f"{name}.bias", (c_out,))]
-    skip = [f[0]] + f[1:1 + levels]
-    out = conv("init_conv", in_channels, f[0]) + conv("final_conv", f[-1], n_classes)
-    for i in range(levels):
-        out += conv(f"enc_{i}.convs.0", skip[i], skip[i + 1]) + conv(f"enc_{i}.convs.3", skip[i + 1], skip[i + 1])
-    below = skip[levels]
-    for j, i in enumerate(reversed(range(levels))):
-        c = f[1 + levels + j]
-        out += conv(f"dec_{i}.convs.0", skip[i] + below, c) + conv(f"dec_{i}.convs.3", c, c)
-        below = c
-    return out
+    """(name, shape) of the 3-D FlexUNet's state dict in its order; n_filters = [init, enc_0.., dec_{L-1}.., final] (_unet.unet_tensors)."""
+    return _unet.unet_tensors(n_filters, levels, n_classes, in_channels, 3)
 
 
 def _architecture(weights: Dict[str, np.ndarray]) -> Tuple[int, List[int], int]:
@@ -157,16 +138,7 @@ class MCSegmenter:
         init_shape = tuple(np.shape(weights["init_conv.weight"]))
         if init_shape[1] != 1:
             raise ValueError(f"init_conv.weight has shape {init_shape}: the segmenter takes one input channel")
-        expected = unet_tensors(self.n_filters, self.levels, self.n_classes)
-        names = {name for name, _ in expected}
-        for name, shape in expected:
-            if name not in weights:
-                raise ValueError(f"missing key {name}")
-            if tuple(np.shape(weights[name])) != shape:
-                raise ValueError(f"inconsistent weight shapes: {name} has shape {tuple(np.shape(weights[name]))}, expected {shape}")
-        extra = sorted(set(weights) - names)
-        if extra:
-            raise ValueError(f"unexpected key {extra[0]}")
+        self.flat = _unet.flatten(weights, unet_tensors(self.n_filters, self.levels, self.n_classes), "inconsistent weight shapes: ")
         if self.n_classes != N_LABELS or int(n_labels) != N_LABELS:
             raise ValueError(f"the final convolution has {self.n_classes} outputs and n_labels is {n_labels}: both must be {N_LABELS} "
                              "(8 softmax labels and the lung vessels)")
@@ -178,23 +150,13 @@ class MCSegmenter:
         self.n_labels = int(n_labels)
         self.input_value_range = tuple(input_value_range)
         self.output_value_range = tuple(output_value_range)
-        self.flat = np.concatenate([np.asarray(weights[name], dtype=np.float32).ravel() for name, _ in expected])
         self.memory_limit_bytes = 0
         self.last_report: Optional[dict] = None
 
     @classmethod
     def from_filepath(cls, model_filepath, device: int = 0, **kwargs) -> "MCSegmenter":
-        """A `.pth` as the reference's trainer writes it ({"model": state dict}; read with torch) or a `.npz` with the same names
-        (read without torch)."""
-        path = Path(model_filepath)
-        if path.suffix == ".npz":
-            with np.load(path) as f:
-                weights = {k: f[k] for k in f.files}
-        else:
-            import torch
-            state = torch.load(path, map_location="cpu")["model"]
-            weights = {k: v.detach().cpu().numpy() for k, v in state.items()}
-        return cls(weights, device, **kwargs)
+        """A `.pth` as the reference's trainer writes it or a `.npz` with the same names (_unet.read_weights)."""
+        return cls(_unet.read_weights(model_filepath), device, **kwargs)
 
     @staticmethod
     def clear_cache():
@@ -224,7 +186,7 @@ class MCSegmenter:
         o = self._options(image.shape, IMAGE_INT16 if image.dtype == np.int16 else IMAGE_FLOAT32)
         rep = _SegmentReport()
         engine._check(_library().mcgpu_segment_run(C.byref(o), image.ctypes.data, labels.ctypes.data, raw.ctypes.data, C.byref(rep)))
-        self.last_report = _report(rep)
+        self.last_report = _unet.report_dict(rep)
         return labels, raw
 
 
@@ -235,8 +197,7 @@ def segment_stage(stage: str, data, in2=None, weight=None, bias=None, upsample: 
     -> mean [c, shape]; 'finalize': mean [9, d0, d1, d2] -> uint8 labels."""
     from . import engine
     code = SEGMENT_STAGES[stage]
-    f32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32)  # noqa: E731
-    data, in2, weight, bias = f32(data), f32(in2), f32(weight), f32(bias)
+    data, in2, weight, bias = map(_unet.f32, (data, in2, weight, bias))
     a = _SegmentStageArgs(struct_size=C.sizeof(_SegmentStageArgs), upsample=int(bool(upsample)))
     out_dtype = np.float32
     if stage == "stitch":
@@ -269,9 +230,8 @@ def segment_stage(stage: str, data, in2=None, weight=None, bias=None, upsample: 
             out_dtype = np.uint8 if stage == "finalize" else np.float32
     a.shape[:] = vol
     out = np.zeros(out_shape, dtype=out_dtype)
-    ptr = lambda v: None if v is None else v.ctypes.data  # noqa: E731
-    a.in_, a.in2, a.weight, a.bias, a.out = ptr(data), ptr(in2), ptr(weight), ptr(bias), out.ctypes.data
+    a.in_, a.in2, a.weight, a.bias, a.out = *map(_unet.ptr, (data, in2, weight, bias)), out.ctypes.data
     o = _SegmentOptions(struct_size=C.sizeof(_SegmentOptions), device=int(device))
     rep = _SegmentReport()
     engine._check(_library().mcgpu_segment_stage(C.byref(o), code, C.byref(a), C.byref(rep)))
-    return out, _report(rep)
+    return out, _unet.report_dict(rep)

@@ -20,6 +20,8 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
+from . import _unet
+
 
 class _SpeedupOptions(C.Structure):
     """mcgpu_speedup_options (include/mcgpu_amd.h)."""
@@ -52,23 +54,11 @@ def _library():
     return lib
 
 
-def _report(rep: _SpeedupReport) -> dict:
-    return {name: getattr(rep, name) for name, _ in _SpeedupReport._fields_}
-
-
 def unet_tensors(prefix: str, in_channels: int, levels: int, base: int) -> List[Tuple[str, Tuple[int, ...]]]:
     """(name, shape) of one FlexUNet's tensors in the state dict's order: init_conv, final_conv, enc_0 .. enc_{L-1},
     dec_{L-1} .. dec_0; each block holds its two convolutions as convs.0 and convs.3."""
-    def conv(name, c_in, c_out):
-        return [(f"{prefix}.{name}.weight", (c_out, c_in, 3, 3)), (f"{prefix}.{name}.bias", (c_out,))]
-    out = conv("init_conv", in_channels, base) + conv("final_conv", base, 1)
-    for i in range(levels):
-        c_in, c = (base << (i - 1) if i else base), base << i
-        out += conv(f"enc_{i}.convs.0", c_in, c) + conv(f"enc_{i}.convs.3", c, c)
-    for i in reversed(range(levels)):
-        skip, below, c = (base << (i - 1) if i else base), base << (levels - 1 if i == levels - 1 else i + 1), base << i
-        out += conv(f"dec_{i}.convs.0", skip + below, c) + conv(f"dec_{i}.convs.3", c, c)
-    return out
+    by_level = [base << i for i in range(levels)]
+    return _unet.unet_tensors([base] + by_level + by_level[::-1] + [base], levels, 1, in_channels, 2, prefix + ".")
 
 
 def state_dict_tensors(mean_net=(2, 4, 64), var_net=(1, 2, 16)) -> List[Tuple[str, Tuple[int, ...]]]:
@@ -101,18 +91,8 @@ class MCSpeedup:
         if self.mean_net[0] not in (1, 2) or self.var_net[0] != 1:
             raise ValueError(f"mean_net.init_conv.weight / var_net.init_conv.weight: {self.mean_net[0]} / {self.var_net[0]} input channels, "
                              "expected 1 or 2 / 1")
-        expected = state_dict_tensors(self.mean_net, self.var_net)
-        names = {name for name, _ in expected}
-        for name, shape in expected:
-            if name not in weights:
-                raise ValueError(f"missing key {name}")
-            if tuple(np.shape(weights[name])) != shape:
-                raise ValueError(f"{name} has shape {tuple(np.shape(weights[name]))}, expected {shape}")
-        extra = sorted(set(weights) - names)
-        if extra:
-            raise ValueError(f"unexpected key {extra[0]}")
         self.device = int(device)
-        self.flat = np.concatenate([np.asarray(weights[name], dtype=np.float32).ravel() for name, _ in expected])
+        self.flat = _unet.flatten(weights, state_dict_tensors(self.mean_net, self.var_net))
 
     @property
     def in_channels(self) -> int:
@@ -120,17 +100,8 @@ class MCSpeedup:
 
     @classmethod
     def from_filepath(cls, model_filepath, device: int = 0) -> "MCSpeedup":
-        """A `.pth` as the reference's trainer writes it ({"model": state dict}; read with torch) or a `.npz` with the same
-        names (read without torch)."""
-        path = Path(model_filepath)
-        if path.suffix == ".npz":
-            with np.load(path) as f:
-                weights = {k: f[k] for k in f.files}
-        else:
-            import torch
-            state = torch.load(path, map_location="cpu")["model"]
-            weights = {k: v.detach().cpu().numpy() for k, v in state.items()}
-        return cls(weights, device)
+        """A `.pth` as the reference's trainer writes it or a `.npz` with the same names (_unet.read_weights)."""
+        return cls(_unet.read_weights(model_filepath), device)
 
     # ------------------------------------------------------------------------------------------------------------------
     def _options(self, n, nv, nu, seed=0, first_projection=0) -> _SpeedupOptions:
@@ -165,7 +136,7 @@ class MCSpeedup:
         rep = _SpeedupReport()
         engine._check(_library().mcgpu_speedup_run(C.byref(o), lp.ctypes.data, fp.ctypes.data if fp is not None else None, mean.ctypes.data,
                                                    variance.ctypes.data, sample.ctypes.data if want_sample else None, C.byref(rep)))
-        return mean, variance, sample, _report(rep)
+        return mean, variance, sample, _unet.report_dict(rep)
 
     @staticmethod
     def preprocess_inputs(low_photon, forward_projection=None):
@@ -229,8 +200,7 @@ def speedup_stage(stage: str, data=None, in2=None, weight=None, bias=None, upsam
     shape = (n, H, W), seed, first_projection."""
     from . import engine
     code = SPEEDUP_STAGES[stage]
-    f32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32)  # noqa: E731
-    data, in2, weight, bias = f32(data), f32(in2), f32(weight), f32(bias)
+    data, in2, weight, bias = map(_unet.f32, (data, in2, weight, bias))
     lead, H, W = (tuple(shape) if stage == "normals" else data.shape)
     n, c1, c2, c_out = 1, 0, 0, 0
     if stage in ("preprocess", "normals"):
@@ -246,14 +216,13 @@ def speedup_stage(stage: str, data=None, in2=None, weight=None, bias=None, upsam
     else:
         c1, out_shape = lead, ((lead, H, W) if stage == "norm_lrelu" else (lead, H // 2, W // 2))
     out = np.zeros(out_shape, dtype=np.float32)
-    ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
     o = _SpeedupOptions(struct_size=C.sizeof(_SpeedupOptions), device=int(device), n=int(n), nu=int(W), nv=int(H), seed=int(seed) & (2 ** 64 - 1),
                         first_projection=int(first_projection))
-    a = _SpeedupStageArgs(C.sizeof(_SpeedupStageArgs), int(bool(upsample)), int(c1), int(c2), int(c_out), ptr(data), ptr(in2), ptr(weight), ptr(bias),
+    a = _SpeedupStageArgs(C.sizeof(_SpeedupStageArgs), int(bool(upsample)), int(c1), int(c2), int(c_out), *map(_unet.ptr, (data, in2, weight, bias)),
                           out.ctypes.data)
     rep = _SpeedupReport()
     engine._check(_library().mcgpu_speedup_stage(C.byref(o), code, C.byref(a), C.byref(rep)))
-    return out, _report(rep)
+    return out, _unet.report_dict(rep)
 
 
 def speedup_simulation(simulation_folder, config_name: str, weights_filepath, gpu_id: int = 0, is_4d: bool = False, seed: Optional[int] = None):

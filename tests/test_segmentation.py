@@ -227,6 +227,19 @@ def test_abi_refusals_before_any_device_call(engine):
     _refused(_options(weights=w, levels=2, filters=filters, n_weights=n + 5), f"n_weights is {n + 5} but the architecture has {n} values")
 
 
+@pytest.mark.parametrize("levels, filters", [(2, [8, 12, 16, 12, 8, 8]), (4, [32] * 10)])
+def test_library_counts_the_weights_as_the_package_does(engine, levels, filters):
+    """n_weights is checked before divisibility: with the package's total the library goes on to refuse a patch axis of
+    2^levels + 1, with one value less it refuses the count and names the total."""
+    n = sum(int(np.prod(s)) for _, s in seg.unet_tensors(filters, levels))
+    axis = 2 ** levels + 1
+    flat = np.zeros(n, np.float32)
+    shapes = dict(weights=flat.ctypes.data, levels=levels, filters=filters, shape=(axis,) * 3, patch=(axis,) * 3)
+    message = _refused(_options(n_weights=n, **shapes), rf"patch axis 0 is {axis}, not divisible by {2 ** levels} ")
+    assert "n_weights" not in message
+    _refused(_options(n_weights=n - 1, **shapes), f"n_weights is {n - 1} but the architecture has {n} values")
+
+
 def test_stage_refusals_before_any_device_call(engine):
     lib = seg._library()
     buf = np.zeros(64, np.float32)

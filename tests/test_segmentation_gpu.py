@@ -135,6 +135,18 @@ def test_norm_lrelu_is_as_close_to_float64_as_the_float32_operator_of_torch(engi
     assert np.array_equal(got, again)
 
 
+def test_both_networks_share_one_instance_norm(engine):
+    """speedup_stage on [c, H, W] and segment_stage on the same data as [c, 1, H, W] return the same bytes; 130 x 130 is past the
+    16384 elements of a segment, so the fold over segments runs."""
+    rng = np.random.default_rng(5)
+    for shape in [(3, 5, 7), (2, 130, 130)]:
+        x = rng.normal(2.0, 3.0, size=shape).astype(np.float32)
+        flat, _ = cases.pkg.speedup.speedup_stage("norm_lrelu", x)
+        deep, _ = seg.segment_stage("norm_lrelu", x[:, None])
+        assert flat.shape == shape and deep.shape == (shape[0], 1) + shape[1:] and np.ptp(flat) > 0
+        assert flat.tobytes() == deep.tobytes()
+
+
 def test_head_is_as_close_to_float64_as_the_float32_operators_of_torch(engine):
     """softmax over channels 0 .. 7 and sigmoid on channel 8: error at most 2 x torch's float32 CPU error per channel, floor 4 x 2^-24."""
     logits = (np.random.default_rng(5).normal(size=(9, 5, 7, 11)) * 3.0).astype(np.float32)

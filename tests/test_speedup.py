@@ -156,6 +156,23 @@ def test_abi_refusals_before_any_device_call(engine):
     _refused(engine, _options(weights=w, n=2), lp4, fp4, "forward_projection slice 1 has zero variance")
 
 
+@pytest.mark.parametrize("mean, var", [((1, 1, 4), (1, 1, 4)), ((2, 3, 8), (1, 2, 4)), ((2, 4, 64), (1, 2, 16))])
+def test_library_counts_the_weights_as_the_package_does(engine, mean, var):
+    """n_weights is checked before divisibility: with the package's total the library goes on to refuse an image side of
+    2^levels + 1, with one value less it refuses the count and names the total."""
+    n = sum(int(np.prod(s)) for _, s in speedup.state_dict_tensors(mean, var))
+    deep = max(mean[1], var[1])
+    side = 2 ** deep + 1
+    flat = np.zeros(n, np.float32)
+    lp, fp = speedup_ref.seeded_inputs(1, 1, side, side)
+    fp = fp if mean[0] == 2 else None
+    lib = speedup._library()
+    _refused(engine, _options(weights=flat.ctypes.data, nu=side, nv=side, n_weights=n, mean=mean, var=var), lp, fp, f"must be divisible by {2 ** deep} ")
+    assert "n_weights" not in lib.mcgpu_last_error().decode()
+    _refused(engine, _options(weights=flat.ctypes.data, nu=side, nv=side, n_weights=n - 1, mean=mean, var=var), lp, fp,
+             f"n_weights is {n - 1} but the architecture has {n} values")
+
+
 def test_stage_refusals_before_any_device_call(engine):
     lib = speedup._library()
     buf = np.zeros(64, np.float32)
