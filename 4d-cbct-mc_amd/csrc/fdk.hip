@@ -1,9 +1,9 @@
 // fdk.hip -- circular cone-beam FDK reconstruction for MI355X (what `rtkfdk --hardware cuda` does for
 // the reference, cbctmc/reconstruction/reconstruction.py:22-69, reconstructors.py).  RTK itself is an un-vendored
 // third-party dependency of the reference; the algorithm and RTK's geometry conventions are restated in oracle/fdk_oracle.py
-// (parity unpinned against RTK, pinned by analytic phantoms) and implemented here as four kernels:
-//   weight      : water pre-correction polynomial, cosine weight, displaced-detector (half-fan) weight, zero padding of the
-//                 short side to a detector symmetric about the central ray                                     (streaming)
+// (parity unpinned against RTK, pinned by analytic phantoms) and implemented here and in fdk_common.inc (the row kernels) as:
+//   weight      : water pre-correction polynomial, cosine weight, displaced-detector (half-fan) weight (backproject_column.inc),
+//                 zero padding of the short side to a detector symmetric about the central ray                 (streaming)
 //   ramp        : rows zero-extended to L (7500 at the reference's size), batched hipFFT R2C -> multiply by the real spectrum of
 //                 the (Hann-apodised) ramp -> C2R (HBM streaming); ramp_rows = the direct LDS convolution kept for A/B
 //                 (MCGPU_FDK_DIRECT_RAMP)
@@ -11,7 +11,7 @@
 //                 the feathered point reflection 2 p(border) - p(mirror), so that a truncated edge does not ring     (streaming)
 //   smooth_cols : --hannY low-pass along v (3 taps for 1.0)                                                     (streaming)
 //   backproject : voxel-driven, bilinear; a thread owns one (x, z) column of the volume, precomputes everything that does
-//                 not depend on y for a batch of 8 projections in registers, then walks y: 4 loads + 10 flops per update;
+//                 not depend on y for a batch of 8 projections in registers, then walks y (backproject_column.inc): 4 loads + 10 flops per update;
 //                 the filtered projections of a batch (5.7 MB each, padded) stay L2 / Infinity-Cache resident.  One voxel step
 //                 is 3.9 detector pixels, so the 4 loads of a wave touch ~32 cache lines for 64 updates: the vector L1
 //                 (64 B/clk/CU) bounds the kernel at ~1 update/clk/CU; measured 0.78                              (L1/L2 gather)
@@ -46,13 +46,8 @@ __global__ void weight_kernel(const float* __restrict__ in, float* __restrict__ 
   float v = 0.f;
   if (iu >= 0 && iu < nu) {
     v = in[((size_t)k * nv + iv) * nu + iu];
-    if (n_wpc > 0) {  // rtkfdk --wpc: sum_k c_k p^k
-      float acc = 0.f, pw = 1.f;
-      for (int j = 0; j < n_wpc; ++j) { acc += wpc[j] * pw; pw *= v; }
-      v = acc;
-    }
-    const float up = u0 + du * iu + pp[k].off_x, vp = v0 + dv * iv + pp[k].off_y;
-    v *= sdd / sqrtf(sdd * sdd + up * up + vp * vp) * w_dis[(size_t)k * nu + iu];
+    if (n_wpc > 0) v = wpc_polynomial(wpc, n_wpc, v);
+    v *= detector_weight(sdd, u0 + du * iu + pp[k].off_x, v0 + dv * iv + pp[k].off_y, w_dis[(size_t)k * nu + iu]);
   }
   out[i] = v;
 }
@@ -61,27 +56,9 @@ __global__ __launch_bounds__(256, 4) void backproject_kernel(float* __restrict__
   const int ix = blockIdx.x * blockDim.x + threadIdx.x, iz = blockIdx.y;
   if (ix >= A.nx) return;
   const float X = A.x0 + A.sx * ix, Z = A.z0 + A.sz * iz;
-  int iu[kBatch];
-  float au[kBatch], wg[kBatch], av_a[kBatch], av_b[kBatch];
+  Column col[kBatch];
 #pragma unroll
-  for (int k = 0; k < kBatch; ++k) {
-    iu[k] = -1; au[k] = 0.f; wg[k] = 0.f; av_a[k] = 0.f; av_b[k] = 0.f;
-    if (k < A.nb) {
-      const float xr = X * A.pp[k].c - Z * A.pp[k].s, zr = X * A.pp[k].s + Z * A.pp[k].c;
-      const float U = A.sid - zr, mag = A.sdd / U;
-      const float fu = (mag * xr - A.pp[k].off_x - A.u0) * A.inv_du;
-      const float fl = floorf(fu);
-      const int i = (int)fl;
-      if (i >= 0 && i < A.nu - 1) {
-        iu[k] = i;
-        au[k] = fu - fl;
-        const float r = A.sid / U;
-        wg[k] = A.pp[k].gap * r * r;
-        av_a[k] = mag * A.inv_dv;                                  // fv = av_a * Y + av_b
-        av_b[k] = (-A.pp[k].off_y - A.v0) * A.inv_dv;
-      }
-    }
-  }
+  for (int k = 0; k < kBatch; ++k) col[k] = column_setup<true>(A, k, X, Z);
   const size_t plane = (size_t)A.stride * A.nv;
   float* out = vol + ((size_t)iz * A.ny) * A.nx + ix;
   for (int iy = 0; iy < A.ny; ++iy) {
@@ -89,21 +66,11 @@ __global__ __launch_bounds__(256, 4) void backproject_kernel(float* __restrict__
     float acc = 0.f;
 #pragma unroll
     for (int k = 0; k < kBatch; ++k) {
-      if (iu[k] >= 0) {
-        const float fv = fmaf(av_a[k], Y, av_b[k]);
-        const float fl = floorf(fv);
-        const int iv = (int)fl;
-        if (iv >= 0 && iv < A.nv - 1) {
-          const float av = fv - fl;
-          const float* r0 = q + (size_t)k * plane + (size_t)iv * A.stride + A.u_first + iu[k];
-          float2 lo, hi;  // (iu, iu + 1) of both rows with one 8-byte load each (4-byte aligned: global loads need no more)
-          __builtin_memcpy(&lo, r0, 8);
-          __builtin_memcpy(&hi, r0 + A.stride, 8);
-          const float v00 = lo.x, v01 = lo.y, v10 = hi.x, v11 = hi.y;
-          const float top = fmaf(au[k], v01 - v00, v00), bot = fmaf(au[k], v11 - v10, v10);
-          acc = fmaf(wg[k], fmaf(av, bot - top, top), acc);
-        }
-      }
+      const Column& c = col[k];
+      int iv;
+      float av;
+      if (c.iu >= 0 && detector_rows(fmaf(c.av_a, Y, c.av_b), A.nv, iv, av))
+        acc = fmaf(c.wg, detector_sample(q + (size_t)k * plane + (size_t)iv * A.stride + A.u_first + c.iu, A.stride, c.au, av), acc);
     }
     out[(size_t)iy * A.nx] += acc;
   }

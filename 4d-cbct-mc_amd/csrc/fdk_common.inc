@@ -1,16 +1,9 @@
 // fdk_common.inc -- what fdk.hip and wpc_fit.hip share of the FDK chain: the plan a reconstruction derives from its options on the
-// host, the hipFFT plan pair, and the row kernels between the weighting and the back-projection (extension, ramp, spectrum, hannY).
+// host, the hipFFT plan pair, the row kernels between the weighting and the back-projection (extension, ramp, spectrum, hannY), and,
+// through backproject_column.inc, the back-projector's column and the rules of the weighting pass.
 // Included inside each file's unnamed namespace, after hip_host.hpp, knobs.hpp and <hipfft/hipfft.h>.
 
-// projections per back-projection launch.  Measured at the reference's size (tools/fdk_bench.py): 8 projections and 4 waves per
-// SIMD (78 VGPRs) 101 ms; 16 / 4 waves (128 VGPRs + scratch) 133 ms; 8 / 8 waves (scratch) 132 ms; 32 / 2 waves 215 ms
-constexpr int kBatch = 8;
-
-struct ProjParam {  // per projection, wave-uniform in the kernels
-  float c, s;       // cos / sin of the gantry angle
-  float off_x, off_y;
-  float gap;        // angular weight [rad]: half the distance to both neighbouring projections (RTK GetAngularGaps)
-};
+#include "backproject_column.inc"  // kBatch, ProjParam, BackArgs and the back-projector's column
 
 // rtkfdk --pad (rtk::FFTProjectionsConvolutionImageFilter::PadInputImageRegion with TruncationCorrection > 0; restated in
 // oracle/fdk_oracle.py: truncation_extension).  A row occupies columns [next, next + n) of its buffer row; the columns at
@@ -79,15 +72,6 @@ __global__ void spectrum_kernel(float2* __restrict__ spec, const float* __restri
   v.x *= h; v.y *= h;
   spec[i] = v;
 }
-
-struct BackArgs {
-  int nx, ny, nz, nu, nv, nb;  // nb = projections in this batch; nu = usable columns
-  int u_first;                 // column of the buffer rows that holds detector column 0 (the --pad extension lies before it)
-  int stride;                  // floats per detector row in q
-  float x0, y0, z0, sx, sy, sz;
-  float sid, sdd, inv_du, inv_dv, u0, v0;
-  ProjParam pp[kBatch];
-};
 
 // ---- host helpers ------------------------------------------------------------------------------------------------
 void fft(std::vector<std::complex<double>>& a, bool inverse) {  // radix 2, in place

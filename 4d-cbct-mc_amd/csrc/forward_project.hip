@@ -14,9 +14,9 @@
 // The traversal runs in the index frame of the IEC volume [nz][ny][nx]; only the voxel fetch differs between volume sources
 // (template parameter): a float volume uploaded from the host, or the context's own representation (u8 tiled / u16 palette
 // indices with the palette densities in LDS, raw {density, material} float2), read in the .vox frame.  All sources run the same
-// arithmetic, so the same densities give bit-identical sums.  The per-ray body lives in joseph_ray.inc, shared with rooster4d.hip.
+// arithmetic, so the same densities give bit-identical sums.  The per-ray body, the volume arguments and the pixel tile live in
+// joseph_ray.inc, shared with rooster4d.hip.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -33,11 +33,8 @@ constexpr int kBatch = 16;       // projections per launch (blockIdx.z)
 constexpr int kChunk = 64;       // projections resident in the device output buffer (downloaded per chunk)
 constexpr int kPalLds = 8192;    // palette densities staged in LDS up to this many entries (32 KB)
 
-struct FpArgs {
-  int nu, nv, nb;
-  int n[3];                        // IEC volume size (x fastest)
-  double u0, v0, du, dv, sid, sdd;
-  double o[3], sp[3];              // origin (centre of voxel 0) and spacing, mm
+struct FpArgs : FpVolume {
+  int nb;
   FpProj pp[kBatch];
 };
 
@@ -108,9 +105,8 @@ __global__ __launch_bounds__(256) void joseph_fp_kernel(float* __restrict__ out 
     for (int i = threadIdx.x; i < pal_n; i += blockDim.x) pal[i] = pal2[2 * i];
     __syncthreads();
   }
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  const int iu = blockIdx.x * 16 + (w & 1) * 8 + (l & 7), iv = blockIdx.y * 16 + (w >> 1) * 8 + (l >> 3);
-  if (iu >= A.nu || iv >= A.nv) return;
+  int iu, iv;
+  if (!fp_pixel(A, iu, iv)) return;
   const float acc = joseph_ray(A, A.pp[blockIdx.z], iu, iv, src, pal);
   out[((size_t)blockIdx.z * A.nv + iv) * A.nu + iu] = acc;
 }
@@ -121,39 +117,21 @@ void read_fp_options(const char* fn, const mcgpu_fp_options* caller, mcgpu_fp_op
     throw Error(-1, std::string("!!ERROR!! ") + fn + ": bad argument");
 }
 
-// FpArgs of the volume; the per-projection block is filled per launch
-FpArgs volume_args(const mcgpu_fp_options& o, const int n[3], const double sp[3]) {
-  FpArgs A;
-  memset(&A, 0, sizeof A);
-  A.nu = o.nu; A.nv = o.nv;
-  const double org[3] = {o.ox, o.oy, o.oz};
-  for (int a = 0; a < 3; ++a) {
-    A.n[a] = n[a];
-    A.sp[a] = sp[a];
-    A.o[a] = centred_origin(n[a], sp[a], org[a]);
-  }
-  A.u0 = o.u0; A.v0 = o.v0; A.du = o.du; A.dv = o.dv; A.sid = o.sid; A.sdd = o.sdd;
-  return A;
-}
-
 // all projections through one source; projections [n_proj][nv][nu] on the host
 template <class Src>
-void project_all(CallDevice& dev, const mcgpu_fp_options& o, FpArgs A, const Src& src, const float* pal2, int pal_n, float* projections, double& ms_kernel) {
+void project_all(CallDevice& dev, const mcgpu_fp_options& o, const FpVolume& V, const Src& src, const float* pal2, int pal_n, float* projections, double& ms_kernel) {
   const size_t plane = (size_t)o.nu * o.nv;
   const int chunk = std::min(o.n_proj, kChunk);
   float* d_out = dev.alloc<float>((size_t)chunk * plane * 4);
   dev.events();
+  FpArgs A{V};  // the per-projection block is filled per launch
   for (int first = 0; first < o.n_proj; first += chunk) {
     const int m = std::min(chunk, o.n_proj - first);
     Stage st(dev, ms_kernel);
     for (int b = 0; b < m; b += kBatch) {
       A.nb = std::min(kBatch, m - b);
-      for (int k = 0; k < A.nb; ++k) {
-        const ProjectionPose q = projection_pose(o, first + b + k);
-        A.pp[k] = {q.c, q.s, q.off_x, q.off_y};
-      }
-      hipLaunchKernelGGL(joseph_fp_kernel<Src>, dim3((unsigned)((o.nu + 15) / 16), (unsigned)((o.nv + 15) / 16), (unsigned)A.nb), dim3(256), 0, nullptr,
-                         d_out + (size_t)b * plane, A, src, pal2, pal_n);
+      fp_poses(o, first + b, A.nb, A.pp);
+      hipLaunchKernelGGL(joseph_fp_kernel<Src>, fp_grid(o.nu, o.nv, A.nb), dim3(256), 0, nullptr, d_out + (size_t)b * plane, A, src, pal2, pal_n);
     }
     st.done();
     HIP_TRY(hipMemcpy(projections + (size_t)first * plane, d_out, (size_t)m * plane * 4, hipMemcpyDeviceToHost));
@@ -171,14 +149,14 @@ extern "C" int mcgpu_forward_project(const mcgpu_fp_options* caller_o, const flo
   HIP_TRY(hipSetDevice(o.device));
   CallDevice dev;
   const size_t nvox = (size_t)o.nx * o.ny * o.nz;
-  const auto t0 = std::chrono::steady_clock::now();
+  const Stopwatch clock;
   const float* d_vol = dev.upload(volume, nvox);
-  const double ms_upload = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  const double ms_upload = clock.ms();
   const int n[3] = {o.nx, o.ny, o.nz};
   const double sp[3] = {o.sx, o.sy, o.sz};
   SrcFloat src{d_vol, o.nx, o.nx * o.ny};
   double ms_kernel = 0.0;
-  project_all(dev, o, volume_args(o, n, sp), src, nullptr, 0, projections, ms_kernel);
+  project_all(dev, o, fp_volume(o, n, sp), src, nullptr, 0, projections, ms_kernel);
   if (report) { report->ms_kernel = ms_kernel; report->ms_upload = ms_upload; }
   return 0;
   ABI_END
@@ -203,7 +181,7 @@ extern "C" int mcgpu_forward_project_context(mcgpu_ctx* ctx, const mcgpu_fp_opti
                         o.sz > 0 ? o.sz : 10.0 * H.voxels.voxel_size[0]};
   HIP_TRY(hipSetDevice(D.device_id));
   CallDevice dev;
-  const FpArgs A = volume_args(o, n, sp);
+  const FpVolume A = fp_volume(o, n, sp);
   const VoxFrame f{vn[0], vn[1], vn[2]};
   double ms_kernel = 0.0;
   if (D.vol_kind == kVolU8) {

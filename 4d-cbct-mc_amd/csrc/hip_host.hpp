@@ -1,10 +1,11 @@
 #pragma once
 // hip_host.hpp -- what the host code around the device routines shares (engine*.cpp, scan.cpp, fdk.hip, wpc_fit.hip, forward_project.hip,
 // rooster4d.hip, resample.hip, speedup_net.hip, segment_net.hip): the HIP check, the exception boundary of the C ABI, owners of HIP handles and of one call's device memory, the
-// stage timer, the reader of struct_size-versioned options and the small rules of the circular cone-beam geometry.
+// stage timer, the host stopwatch, the reader of struct_size-versioned options and the small rules of the circular cone-beam geometry.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -119,6 +120,11 @@ struct Stage {  // times a block of launches on the null stream into one report 
   }
 };
 
+struct Stopwatch {  // host milliseconds since it was made: the uploads and whole calls that no Stage brackets
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+
 // Options structs of the C ABI begin with `unsigned int struct_size` and an int.  A caller built against an older header passes a
 // shorter struct: what it does not have reads as zero.  Refused: no struct, or a size that does not reach past those two fields.
 template <class T>
@@ -138,7 +144,8 @@ template <class O>
 double offset_x(const O& o, int p) { return o.proj_offset_x ? o.proj_offset_x[p] : 0.0; }
 template <class O>
 double offset_y(const O& o, int p) { return o.proj_offset_y ? o.proj_offset_y[p] : 0.0; }
-struct ProjectionPose { double c, s, off_x, off_y; };  // cos / sin of the gantry angle, detector offsets [mm]
+// cos / sin of the gantry angle, detector offsets [mm].  Also a kernel argument (joseph_ray.inc: FpProj): its layout is the kernels'
+struct ProjectionPose { double c, s, off_x, off_y; };
 template <class O>
 ProjectionPose projection_pose(const O& o, int p) {
   const double t = o.gantry_deg[p] * M_PI / 180.0;

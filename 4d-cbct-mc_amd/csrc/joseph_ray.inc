@@ -1,20 +1,52 @@
 // joseph_ray.inc -- the per-ray body of the Joseph forward projector, shared by forward_project.hip (3-D volumes) and rooster4d.hip
 // (phase-blended 4-D frames).  Scheme and geometry: forward_project.hip's header.  The voxel fetch is a template parameter
 // (src(x, y, z, pal) = density at IEC index (x, y, z), always inside the volume); everything else is the same arithmetic for every
-// source, so the same densities give bit-identical sums.  Args needs the fields n[3], u0, v0, du, dv, sid, sdd, o[3], sp[3].
+// source, so the same densities give bit-identical sums.  With it what both kernels and both hosts said around the ray: the volume
+// and detector part of the kernel arguments (FpVolume) and its fill from an options struct, the pixel a lane takes of its workgroup's
+// tile, and the poses of one launch.  Included after hip_host.hpp.
 #pragma once
 
-struct FpProj {
-  double c, s, off_x, off_y;
+using FpProj = mcgpu::ProjectionPose;  // c, s, off_x, off_y of one projection, in double
+
+struct FpVolume {                  // what joseph_ray reads of its arguments; the kernels' argument structs derive from it
+  int nu, nv;
+  int n[3];                        // IEC volume size (x fastest)
+  double u0, v0, du, dv, sid, sdd;
+  double o[3], sp[3];              // origin (centre of voxel 0) and spacing, mm
 };
+
+// the FpVolume of a volume of n voxels of sp mm under the cone-beam fields of o (any options struct that has them)
+template <class O>
+FpVolume fp_volume(const O& o, const int n[3], const double sp[3]) {
+  FpVolume A = {o.nu, o.nv, {n[0], n[1], n[2]}, o.u0, o.v0, o.du, o.dv, o.sid, o.sdd, {}, {sp[0], sp[1], sp[2]}};
+  const double org[3] = {o.ox, o.oy, o.oz};
+  for (int a = 0; a < 3; ++a) A.o[a] = mcgpu::centred_origin(n[a], sp[a], org[a]);
+  return A;
+}
+
+// the poses of projections [first, first + nb) of o: the per-launch block of the kernel arguments
+template <class O>
+void fp_poses(const O& o, int first, int nb, FpProj* pp) {
+  for (int k = 0; k < nb; ++k) pp[k] = mcgpu::projection_pose(o, first + k);
+}
+
+// One lane per detector pixel: a wave covers an 8 x 8 pixel tile, a workgroup of 256 lanes 2 x 2 tiles, blockIdx.z a projection of
+// the batch.  fp_grid is the grid of nb projections, fp_pixel the lane's pixel; false beyond the detector's edge.
+inline dim3 fp_grid(int nu, int nv, int nb) { return dim3((unsigned)((nu + 15) / 16), (unsigned)((nv + 15) / 16), (unsigned)nb); }
+__device__ inline bool fp_pixel(const FpVolume& A, int& iu, int& iv) {
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  iu = blockIdx.x * 16 + (w & 1) * 8 + (l & 7);
+  iv = blockIdx.y * 16 + (w >> 1) * 8 + (l >> 3);
+  return iu < A.nu && iv < A.nv;
+}
 
 // element m of (v0, v1, v2) by selects: a per-lane index into a private array would put the array in scratch
 template <class T>
 __device__ inline T sel3(int m, T v0, T v1, T v2) { return m == 0 ? v0 : (m == 1 ? v1 : v2); }
 
 // line integral of detector pixel (iu, iv) of the projection P
-template <class Args, class Src>
-__device__ inline float joseph_ray(const Args& A, const FpProj& P, int iu, int iv, const Src& src, const float* pal) {
+template <class Src>
+__device__ inline float joseph_ray(const FpVolume& A, const FpProj& P, int iu, int iv, const Src& src, const float* pal) {
   // ray source -> pixel in world coordinates, then in index coordinates of the volume
   const double xr = A.u0 + A.du * iu + P.off_x, yr = A.v0 + A.dv * iv + P.off_y, zr = A.sid - A.sdd;
   const double S[3] = {P.s * A.sid, 0.0, P.c * A.sid};

@@ -4,12 +4,12 @@
 // tests/rooster_ref.py.  Parity against rtkfourdrooster itself is unpinned: RTK is absent here.
 //
 // Unknowns: N frames x_f, f = 0..N-1, each on the FDK grid [nz][ny][nx] (IEC frame); projections p_k are line integrals after the
-// optional water pre-correction (the polynomial sum_j c_j p^j of rtkfdk --wpc, fdk.hip: weight_kernel).
+// optional water pre-correction (the polynomial sum_j c_j p^j of rtkfdk --wpc, backproject_column.inc: wpc_polynomial).
 //   S   (phase -> interpolation weights, host: interpolation_weights): phi_k in [0, 1], t = phi_k N, l = floor(t) mod N,
 //       h = (l + 1) mod N, w_h = t - floor(t), w_l = 1 - w_h.  S blends frames l and h for projection k, S^T distributes into them.
-//   R   Joseph forward projection (joseph_ray.inc, unchanged: float64 ray setup, tap positions and sums, float32 samples), reading the blend
+//   R   Joseph forward projection (joseph_ray.inc: float64 ray setup, tap positions and sums, float32 samples), reading the blend
 //       w_l x_l + w_h x_h at every tap (SrcBlend).
-//   B   voxel-driven bilinear back-projection like fdk.hip's backproject_kernel (a detector sample counts only with both columns
+//   B   voxel-driven bilinear back-projection with backproject_column.inc's detector sample (it counts only with both columns
 //       and both rows inside the detector), without ramp filter or angular-gap weights, with the weight (sdd / U)^2 sx sy sz / (du dv),
 //       U = sid - z_rot.  That weight makes B ~ R^T (the Joseph sum over the rays through a voxel, per unit of detector area at the
 //       voxel's magnification), so the CG operator below is close to symmetric -- a deliberate departure from RTK's unweighted
@@ -30,7 +30,6 @@
 // frame) and tv_time_kernel (a voxel's whole series and its dual in registers: one read and one write of the 4-D volume).
 // Residency: the projection stack and the 4-D vectors x, b, r, d, A d stay on the device for the whole run.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -38,6 +37,7 @@
 
 #include "../../include/mcgpu_amd.h"
 #include "hip_host.hpp"
+#include "backproject_column.inc"
 #include "joseph_ray.inc"
 
 namespace {
@@ -46,17 +46,14 @@ using mcgpu::CallDevice;
 using mcgpu::Stage;
 
 constexpr int kFpBatch = 16;     // projections per forward launch (blockIdx.z)
-constexpr int kBpBatch = 8;      // projections per back-projection launch (fdk.hip's measured optimum)
+constexpr int kBpBatch = kBatch; // projections per back-projection launch (backproject_column.inc's measured optimum)
 constexpr int kMaxFrames = 32;   // frames of the temporal TV kernel's register arrays
 constexpr int kRedBlocks = 1024; // blocks of the first reduction stage (fixed: the summation order does not depend on the device)
 constexpr int kThreads = 256;
 
 // ---- R S -----------------------------------------------------------------------------------------------------------------
-struct Fp4Args {  // field names as joseph_ray.inc expects them
-  int nu, nv, nb;
-  int n[3];
-  double u0, v0, du, dv, sid, sdd;
-  double o[3], sp[3];
+struct Fp4Args : FpVolume {
+  int nb;
   FpProj pp[kFpBatch];
   int fl[kFpBatch], fh[kFpBatch];  // frame pair of each projection
   float wl[kFpBatch], wh[kFpBatch];
@@ -74,9 +71,8 @@ struct SrcBlend {  // w_l x_l + w_h x_h at IEC index (x, y, z)
 };
 
 __global__ __launch_bounds__(256) void fp4_kernel(float* __restrict__ out /*[nb][nv][nu]*/, const Fp4Args A, const float* __restrict__ x4, size_t frame) {
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  const int iu = blockIdx.x * 16 + (w & 1) * 8 + (l & 7), iv = blockIdx.y * 16 + (w >> 1) * 8 + (l >> 3);
-  if (iu >= A.nu || iv >= A.nv) return;
+  int iu, iv;
+  if (!fp_pixel(A, iu, iv)) return;
   const int k = blockIdx.z;
   const SrcBlend src{x4 + (size_t)A.fl[k] * frame, x4 + (size_t)A.fh[k] * frame, A.wl[k], A.wh[k], A.n[0], A.n[0] * A.n[1]};
   out[((size_t)k * A.nv + iv) * A.nu + iu] = joseph_ray(A, A.pp[k], iu, iv, src, nullptr);
@@ -95,7 +91,7 @@ struct Bp4Args {
   float wl[kBpBatch], wh[kBpBatch];
 };
 
-// a thread owns one (x, z) column and walks y (fdk.hip: backproject_kernel); x4 += S^T B q for the batch
+// a thread owns one (x, z) column and walks y (backproject_column.inc; the setup in double is this kernel's own); x4 += S^T B q for the batch
 __global__ __launch_bounds__(256, 4) void bp4_kernel(float* __restrict__ x4, size_t frame, const float* __restrict__ q /*[nb][nv][nu]*/, const Bp4Args A) {
   const int ix = blockIdx.x * blockDim.x + threadIdx.x, iz = blockIdx.y;
   if (ix >= A.nx) return;
@@ -130,22 +126,12 @@ __global__ __launch_bounds__(256, 4) void bp4_kernel(float* __restrict__ x4, siz
     float acc_l = 0.f, acc_h = 0.f;
 #pragma unroll
     for (int k = 0; k < kBpBatch; ++k) {
-      if (iu[k] >= 0) {
-        const float fv = fmaf(av_a[k], Y, A.av_b[k]);
-        const float fl = floorf(fv);
-        const int iv = (int)fl;
-        if (iv >= 0 && iv < A.nv - 1) {
-          const float av = fv - fl;
-          const float* r0 = q + (size_t)k * plane + (size_t)iv * A.nu + iu[k];
-          float2 lo, hi;  // (iu, iu + 1) of both rows with one 8-byte load each
-          __builtin_memcpy(&lo, r0, 8);
-          __builtin_memcpy(&hi, r0 + A.nu, 8);
-          const float top = fmaf(au[k], lo.y - lo.x, lo.x), bot = fmaf(au[k], hi.y - hi.x, hi.x);
-          const float val = fmaf(av, bot - top, top);
-          const float gv = g[k] * val;
-          acc_l = fmaf(A.wl[k], gv, acc_l);
-          acc_h = fmaf(A.wh[k], gv, acc_h);
-        }
+      int iv;
+      float av;
+      if (iu[k] >= 0 && detector_rows(fmaf(av_a[k], Y, A.av_b[k]), A.nv, iv, av)) {
+        const float gv = g[k] * detector_sample(q + (size_t)k * plane + (size_t)iv * A.nu + iu[k], A.nu, au[k], av);
+        acc_l = fmaf(A.wl[k], gv, acc_l);
+        acc_h = fmaf(A.wh[k], gv, acc_h);
       }
     }
     const size_t o = (size_t)iy * A.nx;
@@ -237,13 +223,10 @@ __global__ __launch_bounds__(256) void positivity_kernel(float4* __restrict__ x,
   }
 }
 
-// rtkfdk --wpc on the resident projections: p <- sum_j c_j p^j (fdk.hip: weight_kernel)
+// rtkfdk --wpc on the resident projections: p <- sum_j c_j p^j
 __global__ __launch_bounds__(256) void wpc_kernel(float* __restrict__ p, size_t n, const float* __restrict__ wpc, int n_wpc) {
   for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (size_t)kRedBlocks * kThreads) {
-    const float v = p[i];
-    float acc = 0.f, pw = 1.f;
-    for (int j = 0; j < n_wpc; ++j) { acc += wpc[j] * pw; pw *= v; }
-    p[i] = acc;
+    p[i] = wpc_polynomial(wpc, n_wpc, p[i]);
   }
 }
 
@@ -363,23 +346,16 @@ struct Problem {
     plane = (size_t)o.nu * o.nv;
     fl.resize(o.n_proj); fh.resize(o.n_proj); wl.resize(o.n_proj); wh.resize(o.n_proj);
     for (int k = 0; k < o.n_proj; ++k) interpolation_weights(o.phase[k], N, fl[k], fh[k], wl[k], wh[k]);
-    const double org[3] = {o.ox, o.oy, o.oz}, sp[3] = {o.sx, o.sy, o.sz};
+    const double sp[3] = {o.sx, o.sy, o.sz};
     const int n[3] = {o.nx, o.ny, o.nz};
-    double origin[3];
-    memset(&fa, 0, sizeof fa);
-    fa.nu = o.nu; fa.nv = o.nv;
-    for (int a = 0; a < 3; ++a) {
-      origin[a] = mcgpu::centred_origin(n[a], sp[a], org[a]);
-      fa.n[a] = n[a]; fa.sp[a] = sp[a]; fa.o[a] = origin[a];
-    }
-    fa.u0 = o.u0; fa.v0 = o.v0; fa.du = o.du; fa.dv = o.dv; fa.sid = o.sid; fa.sdd = o.sdd;
+    fa = Fp4Args{fp_volume(o, n, sp)};
     // back-projection batches: consecutive projections with the same frame pair, at most kBpBatch
     for (int k = 0; k < o.n_proj;) {
       Bp4Args A;
       memset(&A, 0, sizeof A);
       A.nx = o.nx; A.ny = o.ny; A.nz = o.nz; A.nu = o.nu; A.nv = o.nv;
       A.fl = fl[k]; A.fh = fh[k];
-      A.x0 = origin[0]; A.z0 = origin[2]; A.sx = o.sx; A.sz = o.sz; A.y0 = (float)origin[1]; A.sy = (float)o.sy;
+      A.x0 = fa.o[0]; A.z0 = fa.o[2]; A.sx = o.sx; A.sz = o.sz; A.y0 = (float)fa.o[1]; A.sy = (float)o.sy;
       A.sid = o.sid; A.sdd = o.sdd; A.inv_du = 1.0 / o.du; A.inv_dv = 1.0 / o.dv; A.u0 = o.u0; A.v0 = o.v0;
       A.K = o.sx * o.sy * o.sz / (o.du * o.dv);
       int m = 0;
@@ -414,14 +390,12 @@ struct Problem {
     Fp4Args A = fa;
     for (int b = 0; b < o.n_proj; b += kFpBatch) {
       A.nb = std::min(kFpBatch, o.n_proj - b);
+      fp_poses(o, b, A.nb, A.pp);
       for (int k = 0; k < A.nb; ++k) {
         const int p = b + k;
-        const mcgpu::ProjectionPose q = mcgpu::projection_pose(o, p);
-        A.pp[k] = {q.c, q.s, q.off_x, q.off_y};
         A.fl[k] = fl[p]; A.fh[k] = fh[p]; A.wl[k] = (float)wl[p]; A.wh[k] = (float)wh[p];
       }
-      hipLaunchKernelGGL(fp4_kernel, dim3((unsigned)((o.nu + 15) / 16), (unsigned)((o.nv + 15) / 16), (unsigned)A.nb), dim3(256), 0, nullptr,
-                         proj + (size_t)b * plane, A, x4, frame);
+      hipLaunchKernelGGL(fp4_kernel, fp_grid(o.nu, o.nv, A.nb), dim3(256), 0, nullptr, proj + (size_t)b * plane, A, x4, frame);
     }
     st.done();
   }
@@ -477,7 +451,7 @@ struct Problem {
   }
 
   float* upload_projections(const float* projections, bool wpc) {
-    const auto t0 = std::chrono::steady_clock::now();
+    const mcgpu::Stopwatch upload;
     float* d = alloc_proj();
     HIP_TRY(hipMemcpy(d, projections, (size_t)o.n_proj * plane * 4, hipMemcpyHostToDevice));
     if (wpc && o.n_wpc > 0) {
@@ -488,15 +462,15 @@ struct Problem {
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipDeviceSynchronize());
     }
-    rep.ms_upload += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    rep.ms_upload += upload.ms();
     return d;
   }
 
   float* upload_4d(const float* v) {
-    const auto t0 = std::chrono::steady_clock::now();
+    const mcgpu::Stopwatch upload;
     float* d = alloc4d();
     HIP_TRY(hipMemcpy(d, v, n4d * 4, hipMemcpyHostToDevice));
-    rep.ms_upload += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    rep.ms_upload += upload.ms();
     return d;
   }
 
@@ -594,12 +568,12 @@ extern "C" int mcgpu_rooster4d_reconstruct(const mcgpu_rooster4d_options* caller
   mcgpu_rooster4d_options o;
   read_options("mcgpu_rooster4d_reconstruct", caller_o, o);
   if (!projections || !volume4d) refuse("mcgpu_rooster4d_reconstruct", "projections or volume is NULL");
-  const auto t0 = std::chrono::steady_clock::now();
+  const mcgpu::Stopwatch call;
   Problem P(o);
   P.init();
   P.run(projections, volume4d);
   P.rep.peak_device_bytes = P.dev.peak;
-  P.rep.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  P.rep.ms_total = call.ms();
   if (report) *report = P.rep;
   return 0;
   ABI_END
@@ -611,12 +585,12 @@ extern "C" int mcgpu_rooster4d_stage(const mcgpu_rooster4d_options* caller_o, in
   read_options("mcgpu_rooster4d_stage", caller_o, o);
   if (stage < MCGPU_ROOSTER4D_STAGE_FORWARD || stage > MCGPU_ROOSTER4D_STAGE_TV_TIME) refuse("mcgpu_rooster4d_stage", "unknown stage " + std::to_string(stage));
   if (!in || !out) refuse("mcgpu_rooster4d_stage", "in or out is NULL");
-  const auto t0 = std::chrono::steady_clock::now();
+  const mcgpu::Stopwatch call;
   Problem P(o);
   P.init();
   P.stage(stage, in, out);
   P.rep.peak_device_bytes = P.dev.peak;
-  P.rep.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  P.rep.ms_total = call.ms();
   if (report) *report = P.rep;
   return 0;
   ABI_END

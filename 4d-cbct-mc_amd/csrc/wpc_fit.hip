@@ -3,11 +3,11 @@
 // central slices of each and solves the weighted normal equations against a template of known attenuation).  DESIGN.md row f13 states
 // the rule; tests/wpc_ref.py restates it in float64.  The N + 1 reconstructions share everything but the power, and the fit reads
 // only a slab mean of each, so one pass does them all and no volume is ever formed:
-//   power_weight   : reads each raw pixel once and writes the C = N + 1 weighted planes q^n x cosine weight x displaced-detector
-//                    weight, padded as fdk.hip's weight_kernel pads; q^n by that kernel's chain pw *= v           (streaming)
+//   power_weight   : reads each raw pixel once and writes the C = N + 1 weighted planes q^n x detector weight (backproject_column.inc),
+//                    padded as fdk.hip's weight_kernel pads; q^n by wpc_polynomial's chain pw *= v                (streaming)
 //   extension, ramp, hannY : fdk_common.inc's row kernels, on C planes per projection instead of one
 //   interleave     : [projection][power][v][u] -> [projection][v][u][power] for the back-projector (layout 2)     (streaming)
-//   slab_backproject<C> : fdk.hip's back-projector with the y walk cut to the slab and C accumulators per thread: the bilinear
+//   slab_backproject<C> : backproject_column.inc's column with the y walk cut to the slab and C accumulators per thread: the bilinear
 //                    weights of a sample are computed once and applied to every power; adds into fbar[c][z][x] once per launch
 //                    (layout 1: two 8-byte loads per power and row; layout 2: the 2 C floats of a row are contiguous)  (L1/L2 gather)
 //   normal_equations<C> : B and a in double from fbar, weight and template: a fixed grid, a fixed tree per block, the blocks'
@@ -15,7 +15,6 @@
 #include <hipfft/hipfft.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <complex>
 #include <cstdlib>
@@ -51,8 +50,7 @@ __global__ void power_weight_kernel(const float* __restrict__ in, float* __restr
   float v = 0.f, w = 0.f;
   if (iu >= 0 && iu < nu) {
     v = in[((size_t)k * nv + iv) * nu + iu];
-    const float up = u0 + du * iu + pp[k].off_x, vp = v0 + dv * iv + pp[k].off_y;
-    w = sdd / sqrtf(sdd * sdd + up * up + vp * vp) * w_dis[(size_t)k * nu + iu];
+    w = detector_weight(sdd, u0 + du * iu + pp[k].off_x, v0 + dv * iv + pp[k].off_y, w_dis[(size_t)k * nu + iu]);
   }
   const size_t plane = (size_t)nv * stride;
   float* o = out + (size_t)k * C * plane + (size_t)iv * stride + ip;
@@ -80,27 +78,9 @@ __global__ __launch_bounds__(256, C <= 7 ? 4 : 2) void slab_backproject_kernel(f
   const int ix = blockIdx.x * blockDim.x + threadIdx.x, iz = blockIdx.y;
   if (ix >= A.nx) return;
   const float X = A.x0 + A.sx * ix, Z = A.z0 + A.sz * iz;
-  int iu[kBatch];
-  float au[kBatch], wg[kBatch], av_a[kBatch], av_b[kBatch];
+  Column col[kBatch];
 #pragma unroll
-  for (int k = 0; k < kBatch; ++k) {
-    iu[k] = -1; au[k] = 0.f; wg[k] = 0.f; av_a[k] = 0.f; av_b[k] = 0.f;
-    {  // an empty slot of the batch (k >= nb) holds the identity pose: computed too, never taken -- a scalar branch here costs registers
-      const float xr = X * A.pp[k].c - Z * A.pp[k].s, zr = X * A.pp[k].s + Z * A.pp[k].c;
-      const float U = A.sid - zr, mag = A.sdd / U;
-      const float fu = (mag * xr - A.pp[k].off_x - A.u0) * A.inv_du;
-      const float fl = floorf(fu);
-      const int i = (int)fl;
-      if (k < A.nb && i >= 0 && i < A.nu - 1) {
-        iu[k] = i;
-        au[k] = fu - fl;
-        const float r = A.sid / U;
-        wg[k] = A.pp[k].gap * r * r;
-        av_a[k] = mag * A.inv_dv;                                  // fv = av_a * Y + av_b
-        av_b[k] = (-A.pp[k].off_y - A.v0) * A.inv_dv;
-      }
-    }
-  }
+  for (int k = 0; k < kBatch; ++k) col[k] = column_setup<false>(A, k, X, Z);
   const size_t plane = (size_t)A.stride * A.nv;
   float acc[C];
 #pragma unroll
@@ -109,34 +89,22 @@ __global__ __launch_bounds__(256, C <= 7 ? 4 : 2) void slab_backproject_kernel(f
     const float Y = A.y0 + A.sy * iy;
 #pragma unroll
     for (int k = 0; k < kBatch; ++k) {
-      if (iu[k] >= 0) {
-        const float fv = fmaf(av_a[k], Y, av_b[k]);
-        const float fl = floorf(fv);
-        const int iv = (int)fl;
-        if (iv >= 0 && iv < A.nv - 1) {
-          const float av = fv - fl, w = wg[k];
-          if (kInterleaved) {
-            // pixels (iu, iu + 1) of a row are 2 C contiguous floats (4-byte aligned: global loads need no more)
-            const float* r0 = q + (size_t)k * plane + (size_t)iv * A.stride + (size_t)iu[k] * C;
-            float lo[2 * C], hi[2 * C];
-            __builtin_memcpy(lo, r0, 8 * C);
-            __builtin_memcpy(hi, r0 + A.stride, 8 * C);
+      int iv;
+      float av;
+      if (col[k].iu >= 0 && detector_rows(fmaf(col[k].av_a, Y, col[k].av_b), A.nv, iv, av)) {
+        const float au = col[k].au, w = col[k].wg;
+        if (kInterleaved) {
+          // pixels (iu, iu + 1) of a row are 2 C contiguous floats (4-byte aligned: global loads need no more)
+          const float* r0 = q + (size_t)k * plane + (size_t)iv * A.stride + (size_t)col[k].iu * C;
+          float lo[2 * C], hi[2 * C];
+          __builtin_memcpy(lo, r0, 8 * C);
+          __builtin_memcpy(hi, r0 + A.stride, 8 * C);
 #pragma unroll
-            for (int c = 0; c < C; ++c) {
-              const float top = fmaf(au[k], lo[C + c] - lo[c], lo[c]), bot = fmaf(au[k], hi[C + c] - hi[c], hi[c]);
-              acc[c] = fmaf(w, fmaf(av, bot - top, top), acc[c]);
-            }
-          } else {
-            const float* r0 = q + (size_t)k * C * plane + (size_t)iv * A.stride + A.u_first + iu[k];
+          for (int c = 0; c < C; ++c) acc[c] = fmaf(w, detector_lerp(au, av, lo[c], lo[C + c], hi[c], hi[C + c]), acc[c]);
+        } else {
+          const float* r0 = q + (size_t)k * C * plane + (size_t)iv * A.stride + A.u_first + col[k].iu;
 #pragma unroll
-            for (int c = 0; c < C; ++c) {
-              float2 lo, hi;
-              __builtin_memcpy(&lo, r0 + (size_t)c * plane, 8);
-              __builtin_memcpy(&hi, r0 + (size_t)c * plane + A.stride, 8);
-              const float top = fmaf(au[k], lo.y - lo.x, lo.x), bot = fmaf(au[k], hi.y - hi.x, hi.x);
-              acc[c] = fmaf(w, fmaf(av, bot - top, top), acc[c]);
-            }
-          }
+          for (int c = 0; c < C; ++c) acc[c] = fmaf(w, detector_sample(r0 + (size_t)c * plane, A.stride, au, av), acc[c]);
         }
       }
     }
@@ -218,10 +186,6 @@ void launch_reduce(const float* fbar, const float* weight, const float* tmpl, si
     default: refuse("no kernel for " + std::to_string(C) + " powers"); \
   }
 
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // device bytes of a call that keeps `chunk` projections resident.  hipFFT's work areas are not known before its plans exist: they
 // are counted as one more spectrum buffer (what the 2^a 3^b 5^c lengths of plan_fdk took at the reference's size)
 size_t footprint(const FdkPlan& P, const mcgpu_fdk_options& o, int C, bool interleaved, int chunk) {
@@ -239,7 +203,7 @@ size_t footprint(const FdkPlan& P, const mcgpu_fdk_options& o, int C, bool inter
 extern "C" int mcgpu_wpc_fit(const mcgpu_wpc_fit_options* caller_o, const float* projections, const float* weight, const float* template_, double* B, double* a,
                              float* basis_mean, mcgpu_wpc_fit_report* report) {
   ABI_BEGIN
-  const auto t_call = std::chrono::steady_clock::now();
+  const mcgpu::Stopwatch call;
   mcgpu_wpc_fit_options w;
   mcgpu::read_options(kFn, "mcgpu_wpc_fit_options", caller_o, w);
   for (const auto& arg : {std::make_pair((const void*)projections, "projections"), std::make_pair((const void*)weight, "weight"),
@@ -296,9 +260,9 @@ extern "C" int mcgpu_wpc_fit(const mcgpu_wpc_fit_options* caller_o, const float*
   for (int first = 0; first < P.n; first += chunk) {
     const int m = std::min(chunk, P.n - first);
     {
-      const auto t0 = std::chrono::steady_clock::now();
+      const mcgpu::Stopwatch upload;
       HIP_TRY(hipMemcpy(d_raw, projections + (size_t)first * P.plane, (size_t)m * P.plane * 4, hipMemcpyHostToDevice));
-      rep.ms_upload += ms_since(t0);
+      rep.ms_upload += upload.ms();
     }
     rows.prepare(m * C);
     fft_work = std::max(fft_work, rows.fft.work_bytes());
@@ -347,7 +311,7 @@ extern "C" int mcgpu_wpc_fit(const mcgpu_wpc_fit_options* caller_o, const float*
   for (int i = 0; i < C; ++i) a[i] = sum[t++];
   if (basis_mean) HIP_TRY(hipMemcpy(basis_mean, d_fbar, (size_t)C * npix * 4, hipMemcpyDeviceToHost));
   rep.peak_device_bytes = (unsigned long long)(dev.peak + fft_work);
-  rep.ms_total = ms_since(t_call);
+  rep.ms_total = call.ms();
   if (report) *report = rep;
   return 0;
   ABI_END

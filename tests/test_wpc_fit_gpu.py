@@ -5,7 +5,8 @@ oracle/fdk_oracle.py).  The slab means fbar_n are held to TOL = 2e-4 x max|oracl
 
   centred          chunks 32 + 8; orders 1, 3, 5; the reduction, the coefficients, the public chain, determinism
   half_fan         offset -80 mm, pad 0.5, n = 41: chunks 32 + 9 and a last batch of one projection; slabs (0, 1), (0, 30), (27, 3);
-                   orders 1 and 7; both ramp routes; the parent's route (N + 1 fdk() calls) beside the fused one
+                   orders 1 and 7; both ramp routes; the parent's route (N + 1 fdk() calls) beside the fused one; one slice of
+                   the fused call against the same slice of fdk(), bit for bit
   wide             nx = 300 (a partial second x-block), ny = 1, off-centre origin; order 2
   varying_offsets  per-projection off_x and off_y; order 3"""
 import numpy as np
@@ -100,6 +101,23 @@ def test_fused_route_against_the_composed_one(engine, monkeypatch):
     print(f"composed: {np.array2string(e_composed, precision=2)}\nfused:    {np.array2string(e_fused, precision=2)}")
     assert (e_composed < W.TOL_REL).all() and (e_fused < W.TOL_REL).all()
     assert (e_fused <= 2.0 * e_composed).all()
+
+
+@pytest.mark.parametrize("layout", [1, 2], ids=["planes", "interleaved"])
+@pytest.mark.parametrize("y", [0, 29])
+def test_one_slice_equals_the_fdk_slice_bit_for_bit(engine, y, layout, monkeypatch):
+    """A slab of one slice, order 1, direct ramp (so that hipFFT's batch size plays no part): basis_mean[n] has the bytes of
+    fdk(..., water_pre_correction=e_n)[0][:, y, :].  Both routes cut the 41 projections into batches of 8, 8, 8, 8, 8, 1 in order and
+    add one accumulator per launch; the division by y_count = 1 is exact; row filters, detector weight, power chain, column setup and
+    detector sample are the same functions (csrc/backproject_column.inc, csrc/fdk_common.inc)."""
+    _route(monkeypatch, True)
+    p = W.problem("half_fan")
+    basis = _call("half_fan", (y, 1), 1, layout)[2]
+    for n in range(2):
+        want = recon.fdk(*p.fdk_args(), p.origin, p.hann, p.hann_y, W.unit(n), pad=p.pad)[0][:, y, :]
+        differing = int((basis[n].view(np.uint32) != np.ascontiguousarray(want).view(np.uint32)).sum())
+        print(f"y {y} layout {layout} power {n}: {differing} of {want.size} words differ")
+        assert differing == 0
 
 
 # ---------------------------------------------------------------------------------------------------------------- reduction, coefficients
