@@ -1,8 +1,9 @@
 """The reference's `CorrespondenceModel` (cbctmc/registration/correspondence.py:29-226): a linear model that turns a breathing
 signal into a displacement field, `field = mean + coefficients (signal - mean_signal)`, fitted by ordinary least squares
 (Wilms et al. 2014, https://doi.org/10.1088/0031-9155/59/5/1147).  Same attributes, same pickle, same hash, so that files pass
-between the two projects.  The registration that produces the fields (`build_default`) is not part of this package: fields and
-signals are inputs.
+between the two projects.  `build_default` produces the fields as the reference does: it registers every phase image of a 4D-CT
+to the reference phase (`registration.register`, demons registration on the device: DESIGN.md row f14) and fits the model to the
+result; `fit` takes fields and signals from anywhere.
 
 The small part of `fit` (K x K or T x T matrices) runs on the host in float64 and follows the reference step by step.  The large
 part is DEFINED by its order of operations, which the numpy route below and the device route (csrc/correspondence.hip) both
@@ -179,6 +180,50 @@ class CorrespondenceModel:
                     acc[:, k] = acc[:, k] + centred * pinv[t, k]
             coefficients[a:a + _CHUNK] = acc
         return mean, coefficients
+
+    # -- build
+    @classmethod
+    def build_default(cls, images, signals=None, masks=None, timepoints=None, reference_phase: int = 2, masked_registration: bool = True, ctx=None,
+                      gpu_id: int = 0, **register_parameters) -> "CorrespondenceModel":
+        """The reference's `build_default` (correspondence.py:277-356): images [T, x, y, z] of a 4D-CT (arrays as an MCGeometry holds
+        them) -> a fitted model.
+
+        signals [T, K] as `fit` takes them, or None: then amplitude and rate of change come from `masks` [T, x, y, z] (lung masks)
+        and `timepoints` [T] through `RespiratorySignal.from_masks`, interpolated at the timepoints, one (amplitude, rate) row per
+        phase.  (The reference stacks the two curves as [2, T] and leaves it to the reshape(T, -1) in its `fit` to make rows of them,
+        which pairs values of different phases; that is not repeated here.)  Every phase t, the reference phase included (its field is exactly zero), is registered with
+        moving = images[reference_phase] and fixed = images[t], so that field t takes the reference phase to phase t: what `fit`,
+        `MCGeometry.warp` and the engine's warp expect.  With masked_registration and masks, masks[t] is the fixed mask; the moving
+        mask of the reference's call has no counterpart in the rule of row f14 and is not used.  There is no affine stage.
+        register_parameters go to `registration.register` (iterations, tau, sigma, n_levels; the reference's values are the
+        defaults).  With an engine context the fit runs on the device and leaves the model resident there.  The lung segmentation
+        shortcut of the reference (`_segment_lungs`, which loads a network from a fixed path) is not part of this package: masks are
+        inputs."""
+        from . import registration
+        from .respiratory import RespiratorySignal
+        if signals is None:
+            if masks is None:
+                raise ValueError("Either signals or masks must be given")
+            if timepoints is None:
+                raise ValueError("timepoints must be given if masks are given")
+            respiratory_signal = RespiratorySignal.from_masks(masks=masks, timepoints=timepoints)
+            signal = np.interp(timepoints, respiratory_signal.time, respiratory_signal.signal)
+            dt_signal = np.interp(timepoints, respiratory_signal.time, respiratory_signal.dt_signal)
+            signals = np.stack([signal, dt_signal], axis=1)
+        timesteps = len(images)
+        if not 0 <= int(reference_phase) < timesteps:
+            raise ValueError(f"reference_phase {reference_phase} is outside the {timesteps} images")
+        if masks is not None and len(masks) != timesteps:
+            raise ValueError(f"{len(masks)} masks for {timesteps} images")
+        if np.shape(signals)[0] != timesteps:
+            raise ValueError(f"{np.shape(signals)[0]} signals for {timesteps} images")
+        moving = images[int(reference_phase)]
+        vector_fields = []
+        for t in range(timesteps):
+            fixed_mask = masks[t] if masked_registration and masks is not None else None
+            field, _ = registration.register(images[t], moving, fixed_mask=fixed_mask, gpu_id=gpu_id, **register_parameters)
+            vector_fields.append(field)
+        return cls().fit(np.stack(vector_fields, axis=0), signals, reference_phase=reference_phase, ctx=ctx)
 
     # -- predict
     def _predict64(self, signal: np.ndarray) -> np.ndarray:

@@ -12,6 +12,7 @@ on the resident context.  The numerical rules are the reference's (they decide w
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, List, Tuple
 
 import numpy as np
@@ -61,6 +62,36 @@ class RespiratorySignal:
         for begin, end in zip(starts, np.r_[starts[1:], len(order)]):
             groups[(float(ranked[begin, 0]), float(ranked[begin, 1]))] = order[begin:end].tolist()
         return groups
+
+    @staticmethod
+    def _repeat_signal(signal, sampling_frequency: float, total_seconds: float) -> np.ndarray:
+        """`signal` tiled until it fills int(total_seconds sampling_frequency) samples (respiratory.py:125-131)."""
+        n_target = int(total_seconds * sampling_frequency)
+        return np.tile(signal, math.ceil(total_seconds * sampling_frequency / len(signal)))[:n_target]
+
+    @classmethod
+    def from_masks(cls, masks, timepoints, target_total_seconds: float = 60.0, target_sampling_frequency: float = 25.0, smooth_window_seconds=None,
+                   smooth_order=3, output_range: Tuple[float, float] = (-1, 1)) -> "RespiratorySignal":
+        """A breathing curve from the volumes of the masks of a 4D-CT's phases (lung masks), respiratory.py:158-209 step by step, on the
+        host: voxels > 0 per mask; linear interpolation from `timepoints` (which need not be regular) to int(range x frequency)
+        equidistant instants over their range; that cycle repeated to `target_total_seconds`; Savitzky-Golay smoothing
+        (scipy.signal.savgol_filter, mode "mirror") over `smooth_window_seconds` (None: the range of the timepoints; 0, or
+        smooth_order None: no smoothing); rescaled and clipped to `output_range`."""
+        volumes = np.array([np.sum(np.asarray(mask) > 0) for mask in masks])
+        timepoints = np.array(timepoints)
+        timepoints_range = timepoints.max() - timepoints.min()
+        regular = np.linspace(timepoints.min(), timepoints.max(), int(timepoints_range * target_sampling_frequency))
+        signal = cls._repeat_signal(np.interp(regular, timepoints, volumes), target_sampling_frequency, target_total_seconds)
+        if smooth_window_seconds != 0 and smooth_order is not None:
+            from scipy.signal import savgol_filter  # the only use of scipy in the package: imported where it is needed
+            if smooth_window_seconds is None:
+                smooth_window_seconds = timepoints_range
+            signal = savgol_filter(signal, window_length=int(smooth_window_seconds * target_sampling_frequency), polyorder=smooth_order, mode="mirror")
+        lo, hi = signal.min(), signal.max()
+        out_lo, out_hi = output_range
+        if (lo, hi) != (out_lo, out_hi):  # cbctmc.utils.rescale_range with clip=True
+            signal = np.clip(((signal - lo) * (out_hi - out_lo)) / (hi - lo) + out_lo, out_lo, out_hi)
+        return cls(signal, sampling_frequency=target_sampling_frequency)
 
     @classmethod
     def _fourth_power(cls, wave, total_seconds, period, amplitude, sampling_frequency):

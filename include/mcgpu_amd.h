@@ -708,6 +708,52 @@ enum { MCGPU_ROOSTER4D_STAGE_FORWARD = 0, MCGPU_ROOSTER4D_STAGE_BACK = 1, MCGPU_
 int mcgpu_rooster4d_stage(const mcgpu_rooster4d_options *options, int stage, const float *in, float *out, mcgpu_rooster4d_report *report);
 
 /* ------------------------------------------------------------------------------------------------
+ * Row f14: demons registration of two volumes (what the reference's CorrespondenceModel.build_default obtains from vroc's
+ * variational registration, cbctmc/registration/correspondence.py:315-345; csrc/registration.hip, whose header states the rule;
+ * float64 restatement: tests/registration_ref.py).  fixed, moving and the mask are [nx][ny][nz] (nz fastest in memory: the arrays
+ * of an MCGeometry and of CorrespondenceModel.fit(frame="geometry")); the result is a displacement field [3][nx][ny][nz] in
+ * voxels on the fixed grid with moving(x + u(x)) ~ fixed(x), component i along array axis i: what mcgpu_warp_geometry(frame 1)
+ * and mcgpu_correspondence_fit take.  Every kernel is a fixed function of its inputs: two calls give the same bytes.  Parity
+ * against vroc itself is unpinned (vroc is absent here). */
+enum { MCGPU_REGISTER_MAX_LEVELS = 8 };
+typedef struct mcgpu_register_options {
+  unsigned int struct_size;     /* sizeof(mcgpu_register_options) as the caller was compiled (later fields read as zero); 0 is refused */
+  int nx, ny, nz;               /* the volumes' shape; fewer than 2^31 voxels */
+  int iterations;               /* per level, >= 0; no early stop */
+  int n_levels;                 /* 1..MCGPU_REGISTER_MAX_LEVELS: level l = n_levels - 1 .. 0 has shape ceil(n / 2^l) */
+  int device;
+  int out_nx, out_ny, out_nz;   /* mcgpu_register_stage, the two resize stages only: the shape of `out` */
+  double tau;                   /* step width */
+  double sigma[3];              /* of the Gaussian that smooths the field after every step, in voxels per axis: 0 skips the axis's
+                                   pass, more than 4 is refused (radius int(4 sigma + 0.5) <= 16) */
+  float *differences;           /* optional: for every level, coarsest first, warped moving - fixed of the level [sx][sy][sz] before
+                                   its first iteration and then after its last: what the report's mean squares are the means of */
+} mcgpu_register_options;
+typedef struct mcgpu_register_report {
+  unsigned int struct_size;     /* sizeof(mcgpu_register_report) as the caller was compiled; only that many bytes are written */
+  int n_levels;
+  double msd_before[MCGPU_REGISTER_MAX_LEVELS];  /* [l]: mean over the level's voxels of double(float32(warped moving - fixed))^2 */
+  double msd_after[MCGPU_REGISTER_MAX_LEVELS];   /* before the first and after the last iteration of level l (0 = finest); summed in double in a fixed order */
+  double ms_upload;             /* host <-> device copies (wall time) */
+  double ms_resize;             /* images, mask and field to a level's shape */
+  double ms_force;              /* steps 1 to 5: warp, difference, gradient, update */
+  double ms_smooth;             /* the Gaussian passes */
+  double ms_reduce;             /* the mean squared differences */
+  double ms_total;              /* wall time of the call */
+  unsigned long long peak_device_bytes;  /* most device memory the call held at once */
+} mcgpu_register_report;
+int mcgpu_register(const mcgpu_register_options *options, const float *fixed, const float *moving, const unsigned char *fixed_mask_or_null,
+                   float *field_out /*[3][nx][ny][nz]*/, mcgpu_register_report *report);
+/* One operator alone (for tests).  RESIZE_LINEAR: moving [nx][ny][nz] -> out float [out_nx][out_ny][out_nz]; RESIZE_NEAREST:
+ * fixed_mask -> out uint8 of that shape; WARP_LINEAR: moving, field -> out float [nx][ny][nz] = moving(x + u); FORCE_STEP: fixed,
+ * moving, field, fixed_mask (or NULL) -> out [3][nx][ny][nz] = u + tau v; SMOOTH: field -> out [3][nx][ny][nz].  Arguments a
+ * stage does not read may be NULL; iterations, n_levels and differences are not used. */
+enum { MCGPU_REGISTER_STAGE_RESIZE_LINEAR = 0, MCGPU_REGISTER_STAGE_RESIZE_NEAREST = 1, MCGPU_REGISTER_STAGE_WARP_LINEAR = 2,
+       MCGPU_REGISTER_STAGE_FORCE_STEP = 3, MCGPU_REGISTER_STAGE_SMOOTH = 4 };
+int mcgpu_register_stage(const mcgpu_register_options *options, int stage, const float *fixed, const float *moving, const float *field,
+                         const unsigned char *fixed_mask_or_null, void *out, mcgpu_register_report *report);
+
+/* ------------------------------------------------------------------------------------------------
  * The speed-up network (what the reference obtains from cbctmc/speedup/inference.py: MCSpeedup; csrc/speedup_net.hip, whose
  * header restates the network).  Two U-Nets of 3 x 3 convolutions (replicate padding, bias), instance norm and LeakyReLU(0.01),
  * in float32: the mean net sees the low-photon projection and the forward projection (matched to it in mean and unbiased
