@@ -184,7 +184,7 @@ class CorrespondenceModel:
     # -- build
     @classmethod
     def build_default(cls, images, signals=None, masks=None, timepoints=None, reference_phase: int = 2, masked_registration: bool = True, ctx=None,
-                      gpu_id: int = 0, **register_parameters) -> "CorrespondenceModel":
+                      gpu_id: int = 0, inverse: bool = False, **register_parameters) -> "CorrespondenceModel":
         """The reference's `build_default` (correspondence.py:277-356): images [T, x, y, z] of a 4D-CT (arrays as an MCGeometry holds
         them) -> a fitted model.
 
@@ -198,7 +198,15 @@ class CorrespondenceModel:
         register_parameters go to `registration.register` (iterations, tau, sigma, n_levels; the reference's values are the
         defaults).  With an engine context the fit runs on the device and leaves the model resident there.  The lung segmentation
         shortcut of the reference (`_segment_lungs`, which loads a network from a fixed path) is not part of this package: masks are
-        inputs."""
+        inputs.
+
+        DIRECTION.  The default (inverse=False) gives pull-back fields: phase_t(x) ~ ref(x + u_t(x)), field t says where in the
+        reference phase the content of phase t's voxel x comes from -- what the warps of the simulation consume.  inverse=True
+        registers every phase t with moving = images[t] and fixed = images[reference_phase] (fixed mask: masks[reference_phase]),
+        so that ref(x) ~ phase_t(x + u_t(x)): the fitted model then takes a voxel of the reference phase to the position of its
+        material at a state, which is what `reconstruction.MotionModel.from_correspondence_model` (motion-compensated FDK)
+        expects.  The two are different models; neither is derived from the other, and a pull-back model handed to the
+        reconstruction is NOT silently inverted."""
         from . import registration
         from .respiratory import RespiratorySignal
         if signals is None:
@@ -217,11 +225,15 @@ class CorrespondenceModel:
             raise ValueError(f"{len(masks)} masks for {timesteps} images")
         if np.shape(signals)[0] != timesteps:
             raise ValueError(f"{np.shape(signals)[0]} signals for {timesteps} images")
-        moving = images[int(reference_phase)]
+        reference = images[int(reference_phase)]
         vector_fields = []
         for t in range(timesteps):
-            fixed_mask = masks[t] if masked_registration and masks is not None else None
-            field, _ = registration.register(images[t], moving, fixed_mask=fixed_mask, gpu_id=gpu_id, **register_parameters)
+            if inverse:
+                fixed_mask = masks[int(reference_phase)] if masked_registration and masks is not None else None
+                field, _ = registration.register(reference, images[t], fixed_mask=fixed_mask, gpu_id=gpu_id, **register_parameters)
+            else:
+                fixed_mask = masks[t] if masked_registration and masks is not None else None
+                field, _ = registration.register(images[t], reference, fixed_mask=fixed_mask, gpu_id=gpu_id, **register_parameters)
             vector_fields.append(field)
         return cls().fit(np.stack(vector_fields, axis=0), signals, reference_phase=reference_phase, ctx=ctx)
 

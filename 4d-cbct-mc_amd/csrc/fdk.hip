@@ -15,6 +15,8 @@
 //                 the filtered projections of a batch (5.7 MB each, padded) stay L2 / Infinity-Cache resident.  One voxel step
 //                 is 3.9 detector pixels, so the 4 loads of a wave touch ~32 cache lines for 64 updates: the vector L1
 //                 (64 B/clk/CU) bounds the kernel at ~1 update/clk/CU; measured 0.78                              (L1/L2 gather)
+//   backproject_motion : the same sample taken where a linear motion model puts the voxel at the projection's breathing state
+//                 (row f15, mcgpu_fdk_reconstruct_motion; the rule stands above backproject_motion_kernel)         (L1/L2 gather)
 #include <hipfft/hipfft.h>
 
 #include <algorithm>
@@ -22,6 +24,7 @@
 #include <complex>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -76,6 +79,86 @@ __global__ __launch_bounds__(256, 4) void backproject_kernel(float* __restrict__
   }
 }
 
+// ---- motion-compensated back-projection ------------------------------------------------------------------
+// The rule.  The grid is the FDK grid [nz][ny][nx] in RTK's IEC frame.  A motion model on it is mean [3][nz][ny][nx] (mm, components
+// along IEC X, Y, Z), coefficients [K][3][nz][ny][nx] (mm per signal unit, 1 <= K <= 4) and, per projection i, delta[i][k] =
+// signal_i[k] - mean_signal[k], given in double and rounded once to float32.  For the voxel at P = (X, Y, Z) and projection i every
+// component of the displacement is float32 with explicit fmaf, k ascending:
+//     acc = mean;  for k in 0..K-1: acc = fmaf(coefficients[k], delta[i][k], acc);  P' = P + acc
+// and projection i gives the voxel what plain FDK gives at P':  xr = X'c - Z's, zr = X's + Z'c, U = sid - zr, mag = sdd / U,
+// fu = (mag xr - off_x - u0_p) / du, fv = (mag Y' - off_y - v0) / dv, weight gap_i (sid / U)^2, and the bilinear sample of the
+// filtered, padded row buffer through detector_rows / detector_sample.  A sample counts only when U > 0, columns iu, iu + 1 lie
+// inside the padded detector and rows iv, iv + 1 inside the detector.  The model says where the material of a reference-phase voxel
+// IS at the projection's state (the inverse of a pull-back field); nothing here inverts a model.
+//
+// With motion every voxel has its own (fu, fv): the column trick of backproject_kernel is gone.  One thread per voxel, x fastest
+// (model loads and the volume's read-modify-write coalesce; neighbouring lanes hit neighbouring detector columns); the thread loads
+// its 3 (K + 1) model values once per launch and loops over the projections of the batch, whose poses and deltas are wave-uniform
+// kernel arguments (scalar loads).  A voxel has one owner and the projections are summed in order: no atomics, two calls give the
+// same bytes.  K is a template parameter: the thread loads exactly the model it has and the fmaf chain is straight-line code.  (The
+// K = 4 code with a uniform bound and zero-filled slots measured the same time, 191.6 against 191.2 ms at 16 projections per
+// launch, and the same bytes: it was not kept.)
+//
+// projections per launch of the motion kernel.  The per-projection state is scalar, so the batch only sets how often the model
+// (3 (K + 1) floats per voxel) is re-read and the volume re-written.  Measured at the reference's size with K = 2 on one MI355X, all
+// in one process (profiles/fdk_motion.md; 30 VGPRs, no scratch, 8 waves per SIMD; 28 - 38 VGPRs over K = 1..4): 8 projections
+// 206.3 ms, 16 191.2 ms, 32 (one launch per resident chunk) 184.2 ms, against 105.1 ms of backproject_kernel; as committed 185.2 ms,
+// 1.76 x.
+constexpr int kMotionBatch = 32;
+constexpr int kMotionMaxK = 4;
+
+struct MotionArgs {  // a sibling of BackArgs: the three column kernels' layout is untouched
+  int nx, ny, nz, nu, nv, nb;
+  int u_first, stride;
+  float x0, y0, z0, sx, sy, sz;
+  float sid, sdd, inv_du, inv_dv, u0, v0;
+  ProjParam pp[kMotionBatch];
+  float delta[kMotionBatch][kMotionMaxK];  // [p][k], k < K
+};
+
+template <int K>
+__global__ __launch_bounds__(256) void backproject_motion_kernel(float* __restrict__ vol, const float* __restrict__ q /*[nb][nv][stride]*/,
+                                                                 const float* __restrict__ mean, const float* __restrict__ coef, const MotionArgs A) {
+  const size_t nvox = (size_t)A.nx * A.ny * A.nz;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nvox) return;
+  const int ix = (int)(i % A.nx), iy = (int)((i / A.nx) % A.ny), iz = (int)(i / ((size_t)A.nx * A.ny));
+  const float X = A.x0 + A.sx * ix, Y = A.y0 + A.sy * iy, Z = A.z0 + A.sz * iz;
+  const float mx = mean[i], my = mean[nvox + i], mz = mean[2 * nvox + i];
+  float cx[K], cy[K], cz[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    cx[k] = coef[((size_t)3 * k + 0) * nvox + i];
+    cy[k] = coef[((size_t)3 * k + 1) * nvox + i];
+    cz[k] = coef[((size_t)3 * k + 2) * nvox + i];
+  }
+  const size_t plane = (size_t)A.stride * A.nv;
+  float acc = 0.f;
+  for (int p = 0; p < A.nb; ++p) {
+    const ProjParam& pp = A.pp[p];
+    float dx = mx, dy = my, dz = mz;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const float d = A.delta[p][k];
+      dx = fmaf(cx[k], d, dx);
+      dy = fmaf(cy[k], d, dy);
+      dz = fmaf(cz[k], d, dz);
+    }
+    const float Xp = X + dx, Yp = Y + dy, Zp = Z + dz;
+    const float xr = fmaf(Xp, pp.c, -(Zp * pp.s)), zr = fmaf(Xp, pp.s, Zp * pp.c);
+    const float U = A.sid - zr;
+    const float inv_U = 1.0f / U;  // the one reciprocal of an update, correctly rounded
+    const float mag = A.sdd * inv_U, r = A.sid * inv_U;
+    int iu, iv;
+    float au, av;
+    const bool in_u = detector_rows((fmaf(mag, xr, -pp.off_x) - A.u0) * A.inv_du, A.nu, iu, au);  // the same rule along u: iu, iu + 1 inside
+    const bool in_v = detector_rows((fmaf(mag, Yp, -pp.off_y) - A.v0) * A.inv_dv, A.nv, iv, av);
+    if (U > 0.f && in_u && in_v)
+      acc = fmaf(pp.gap * r * r, detector_sample(q + (size_t)p * plane + (size_t)iv * A.stride + A.u_first + iu, A.stride, au, av), acc);
+  }
+  vol[i] += acc;
+}
+
 // one reconstruction on the device: the plan's tables and a chunk of projections resident, the volume accumulated there
 struct FdkProblem {
   const mcgpu_fdk_options& o;
@@ -86,8 +169,13 @@ struct FdkProblem {
   float *d_raw = nullptr, *d_in = nullptr, *d_tmp = nullptr, *d_vol = nullptr, *d_wdis = nullptr, *d_wpc = nullptr;
   ProjParam* d_pp = nullptr;
   const float* filtered = nullptr;  // what filter() left for backproject(): d_tmp, or d_in after the hannY pass
+  // the motion model of mcgpu_fdk_reconstruct_motion, resident for the call
+  int motion_K = 0;
+  float *d_mean = nullptr, *d_coef = nullptr;
+  std::vector<float> delta32;  // [n][K]
+  double ms_upload_model = 0.0;
 
-  FdkProblem(const mcgpu_fdk_options& opt, const FdkPlan& plan) : o(opt), P(plan), rows(plan, "mcgpu_fdk_reconstruct") {}
+  FdkProblem(const mcgpu_fdk_options& opt, const FdkPlan& plan, const char* fn = "mcgpu_fdk_reconstruct") : o(opt), P(plan), rows(plan, fn) {}
 
   void upload() {
     d_raw = dev.alloc<float>((size_t)P.chunk * P.plane * 4);
@@ -123,6 +211,45 @@ struct FdkProblem {
     }
     st.done();
   }
+
+  // the model onto the device once, as float32; delta rounded once to float32
+  void upload_model(const mcgpu_fdk_motion& M) {
+    mcgpu::Stopwatch sw;
+    motion_K = M.n_signal_dims;
+    d_mean = dev.upload(M.mean, 3 * P.nvox);
+    d_coef = dev.upload(M.coefficients, (size_t)motion_K * 3 * P.nvox);
+    delta32.resize((size_t)P.n * motion_K);
+    for (size_t j = 0; j < delta32.size(); ++j) delta32[j] = (float)M.delta[j];
+    ms_upload_model = sw.ms();
+  }
+
+  // backproject(first, m) with moving voxels
+  void backproject_motion(int first, int m) {
+    mcgpu::Stage st(dev, rep.ms_backproject);
+    const unsigned blocks = (unsigned)((P.nvox + 255) / 256);
+    for (int b = 0; b < m; b += kMotionBatch) {
+      MotionArgs A;
+      memset(&A, 0, sizeof A);
+      A.nx = o.nx; A.ny = o.ny; A.nz = o.nz; A.nu = P.nu_p; A.nv = P.nv; A.nb = std::min(kMotionBatch, m - b);
+      A.u_first = P.next; A.stride = P.stride;
+      A.x0 = (float)P.ox0; A.y0 = (float)P.oy0; A.z0 = (float)P.oz0; A.sx = (float)o.sx; A.sy = (float)o.sy; A.sz = (float)o.sz;
+      A.sid = (float)o.sid; A.sdd = (float)o.sdd; A.inv_du = (float)(1.0 / o.du); A.inv_dv = (float)(1.0 / o.dv);
+      A.u0 = (float)P.u0_p; A.v0 = (float)o.v0;
+      for (int p = 0; p < A.nb; ++p) {
+        A.pp[p] = P.pp[first + b + p];
+        for (int k = 0; k < motion_K; ++k) A.delta[p][k] = delta32[(size_t)(first + b + p) * motion_K + k];
+      }
+      const float* q = filtered + (size_t)b * P.plane_p;
+      auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, nullptr, d_vol, q, d_mean, d_coef, A); };
+      switch (motion_K) {
+        case 1: launch(backproject_motion_kernel<1>); break;
+        case 2: launch(backproject_motion_kernel<2>); break;
+        case 3: launch(backproject_motion_kernel<3>); break;
+        default: launch(backproject_motion_kernel<4>); break;
+      }
+    }
+    st.done();
+  }
 };
 
 }  // namespace
@@ -143,6 +270,35 @@ extern "C" int mcgpu_fdk_reconstruct(const mcgpu_fdk_options* caller_o, const fl
   }
   HIP_TRY(hipMemcpy(volume, P.d_vol, plan.nvox * 4, hipMemcpyDeviceToHost));
   if (report) *report = P.rep;
+  return 0;
+  ABI_END
+}
+
+extern "C" int mcgpu_fdk_reconstruct_motion(const mcgpu_fdk_options* caller_o, const mcgpu_fdk_motion* caller_m, const float* projections, float* volume,
+                                            mcgpu_fdk_motion_report* report) {
+  ABI_BEGIN
+  const char* fn = "mcgpu_fdk_reconstruct_motion";
+  mcgpu_fdk_options local;
+  mcgpu::read_options(fn, "mcgpu_fdk_options", caller_o, local);
+  mcgpu_fdk_motion motion;
+  mcgpu::read_options(fn, "mcgpu_fdk_motion", caller_m, motion);
+  if (!projections || !volume || !fdk_options_ok(local)) throw mcgpu::Error(-1, std::string("!!ERROR!! ") + fn + ": bad argument");
+  if (motion.n_signal_dims < 1 || motion.n_signal_dims > kMotionMaxK) throw mcgpu::Error(-1, std::string("!!ERROR!! ") + fn + ": n_signal_dims must lie in 1..4");
+  if (!motion.mean || !motion.coefficients || !motion.delta) throw mcgpu::Error(-1, std::string("!!ERROR!! ") + fn + ": bad argument");
+  for (size_t j = 0; j < (size_t)local.n_proj * motion.n_signal_dims; ++j)  // NaN, infinite, or infinite once it is float32
+    if (!(std::fabs(motion.delta[j]) <= (double)std::numeric_limits<float>::max())) throw mcgpu::Error(-1, std::string("!!ERROR!! ") + fn + ": delta is not finite");
+  HIP_TRY(hipSetDevice(local.device));
+  const FdkPlan plan = plan_fdk(local);
+  FdkProblem P(local, plan, fn);
+  P.upload();
+  P.upload_model(motion);
+  for (int first = 0; first < plan.n; first += plan.chunk) {
+    const int m = std::min(plan.chunk, plan.n - first);
+    P.filter(projections, first, m);
+    P.backproject_motion(first, m);
+  }
+  HIP_TRY(hipMemcpy(volume, P.d_vol, plan.nvox * 4, hipMemcpyDeviceToHost));
+  if (report) *report = {P.rep.ms_filter, P.rep.ms_backproject, P.ms_upload_model, (unsigned long long)P.dev.peak};
   return 0;
   ABI_END
 }

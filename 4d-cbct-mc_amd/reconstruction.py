@@ -127,6 +127,15 @@ def fdk(projections: np.ndarray, geometry: CircularGeometry, pixel_spacing: Tupl
     lib = engine.load_library()
     lib.mcgpu_fdk_reconstruct.argtypes = [C.POINTER(_FdkOptions), C.c_void_p, C.c_void_p, C.POINTER(_FdkReport)]
     lib.mcgpu_fdk_reconstruct.restype = C.c_int
+    p, o, keep = _fdk_options(projections, geometry, pixel_spacing, pixel_origin, dimension, spacing, origin, hann, hann_y, water_pre_correction, gpu_id, pad)
+    vol = np.zeros((int(dimension[2]), int(dimension[1]), int(dimension[0])), dtype=np.float32)
+    rep = _FdkReport()
+    engine._check(lib.mcgpu_fdk_reconstruct(C.byref(o), p.ctypes.data, vol.ctypes.data, C.byref(rep)))
+    return vol, {"ms_filter": rep.ms_filter, "ms_backproject": rep.ms_backproject}
+
+
+def _fdk_options(projections, geometry, pixel_spacing, pixel_origin, dimension, spacing, origin, hann, hann_y, water_pre_correction, gpu_id, pad):
+    """(float32 stack, mcgpu_fdk_options, the arrays it points into) of fdk() and fdk_motion()."""
     p = np.ascontiguousarray(projections, dtype=np.float32)
     n, nv, nu = p.shape
     if n != len(geometry.gantry_angles):
@@ -143,10 +152,135 @@ def fdk(projections: np.ndarray, geometry: CircularGeometry, pixel_spacing: Tupl
                     float(spacing[0]), float(spacing[1]), float(spacing[2]),
                     *(tuple(float(v) for v in origin) if origin is not None else (float("nan"),) * 3), float(hann), float(hann_y),
                     wpc.ctypes.data_as(dp) if wpc.size else None, int(wpc.size), int(gpu_id), float(pad))
+    return p, o, (ang, ox, oy, wpc)
+
+
+# ------------------------------------------------------------------------------------------------ motion-compensated FDK
+MAX_SIGNAL_DIMS = 4
+
+
+class _FdkMotion(C.Structure):
+    """mcgpu_fdk_motion (include/mcgpu_amd.h)."""
+    _fields_ = [("struct_size", C.c_uint), ("n_signal_dims", C.c_int), ("mean", C.POINTER(C.c_float)), ("coefficients", C.POINTER(C.c_float)),
+                ("delta", C.POINTER(C.c_double))]
+
+
+class _FdkMotionReport(C.Structure):
+    _fields_ = [("ms_filter", C.c_double), ("ms_backproject", C.c_double), ("ms_upload_model", C.c_double), ("peak_device_bytes", C.c_ulonglong)]
+
+
+class MotionModel:
+    """A linear motion model on the FDK grid (csrc/fdk.hip states the rule): for the voxel at P of the
+    reference-phase volume and a breathing state with signal s, the material of that voxel is at
+    P + mean(P) + sum_k coefficients[k](P) (s[k] - mean_signal[k]).
+
+    mean [3, nz, ny, nx] float32 in mm, components along IEC X, Y, Z; coefficients [K, 3, nz, ny, nx] float32 in mm per signal unit,
+    1 <= K <= 4; mean_signal [K] float64.  dimension = (nx, ny, nz); spacing (mm, optional) is what from_correspondence_model
+    derived the grid's from, and fdk_motion refuses another one."""
+
+    def __init__(self, mean, coefficients, mean_signal, spacing=None):
+        self.mean = np.ascontiguousarray(mean, dtype=np.float32)
+        self.coefficients = np.ascontiguousarray(coefficients, dtype=np.float32)
+        self.mean_signal = np.asarray(mean_signal, dtype=np.float64).reshape(-1)
+        self.spacing = tuple(float(v) for v in spacing) if spacing is not None else None
+        if self.mean.ndim != 4 or self.mean.shape[0] != 3:
+            raise ValueError(f"mean of shape {self.mean.shape}, expected (3, nz, ny, nx)")
+        if self.coefficients.ndim != 5 or self.coefficients.shape[1:] != self.mean.shape:
+            raise ValueError(f"coefficients of shape {self.coefficients.shape}, expected (K, 3, nz, ny, nx) on the grid of mean")
+        if not 1 <= self.n_signal_dims <= MAX_SIGNAL_DIMS:
+            raise ValueError(f"{self.n_signal_dims} signal dimensions: 1 to {MAX_SIGNAL_DIMS} are supported")
+        if self.mean_signal.size != self.n_signal_dims:
+            raise ValueError(f"{self.mean_signal.size} mean signal values for {self.n_signal_dims} signal dimensions")
+
+    @property
+    def n_signal_dims(self) -> int:
+        return int(self.coefficients.shape[0])
+
+    @property
+    def dimension(self) -> Tuple[int, int, int]:
+        return tuple(int(n) for n in self.mean.shape[:0:-1])
+
+    def check_grid(self, dimension, spacing):
+        """ValueError unless (dimension, spacing) is the grid the model lives on: a model is not resampled."""
+        if tuple(int(n) for n in dimension) != self.dimension:
+            raise ValueError(f"the motion model lives on the grid {self.dimension}, the reconstruction on {tuple(dimension)}: resample the model first")
+        if self.spacing is not None and not np.allclose(self.spacing, [float(v) for v in spacing], rtol=1e-9, atol=0.0):
+            raise ValueError(f"the motion model's grid has spacing {self.spacing} mm, the reconstruction {tuple(spacing)}: resample the model first")
+
+    def delta(self, signals) -> np.ndarray:
+        """signals [n, K] -> float64 [n, K]: signal - mean_signal, what mcgpu_fdk_motion.delta takes."""
+        s = np.asarray(signals, dtype=np.float64)
+        if s.ndim == 1:
+            s = s[:, None]
+        if s.ndim != 2 or s.shape[1] != self.n_signal_dims:
+            raise ValueError(f"signals of shape {np.shape(signals)}, expected (n, {self.n_signal_dims})")
+        return np.ascontiguousarray(s - self.mean_signal[None, :])
+
+    @classmethod
+    def from_correspondence_model(cls, model, voxel_spacing_mm, dimension=None, spacing=None) -> "MotionModel":
+        """A fitted `CorrespondenceModel` -> the model in the FDK frame.
+
+        DIRECTION.  The model must take a voxel of the reference phase to the place of its material at a state: build it with
+        `CorrespondenceModel.build_default(..., inverse=True)`.  The default `build_default` gives pull-back fields (ref(x + u_t(x))
+        ~ phase_t(x)), the inverse of what is needed; such a model is NOT detected and NOT silently inverted here -- the
+        reconstruction it drives is blurred more, not less.
+
+        The model's fields are [3, gx, gy, gz] in voxel units in the MCGeometry frame, voxel_spacing_mm = (sx, sy, sz) of that
+        geometry.  Arrays go through the axis rule of `water_precorrection.to_fdk_frame` (IEC X = MC x, IEC Y = -MC z, IEC Z = -MC y),
+        components are permuted, signed and scaled accordingly, (ux sx, -uz sz, -uy sy), in float64, and then rounded to float32;
+        the coefficients likewise.  The result lives on the grid dimension (gx, gz, gy), spacing (sx, sz, sy); with `dimension` /
+        `spacing` given (the reconstruction's) anything else raises ValueError -- a model is not resampled onto another grid."""
+        from .water_precorrection import to_fdk_frame
+        if not model.is_fitted:
+            raise RuntimeError("Correspondence model is not fitted")
+        sx, sy, sz = (float(v) for v in voxel_spacing_mm)
+        shape = tuple(int(n) for n in model.spatial_shape)
+        k_dims = int(model.signal_n_dims)
+        grid_dimension, grid_spacing = (shape[0], shape[2], shape[1]), (sx, sz, sy)
+        if dimension is not None and tuple(int(n) for n in dimension) != grid_dimension:
+            raise ValueError(f"the correspondence model gives the FDK grid {grid_dimension}, the reconstruction has {tuple(dimension)}: resample the model first")
+        if spacing is not None and not np.allclose(grid_spacing, [float(v) for v in spacing], rtol=1e-9, atol=0.0):
+            raise ValueError(f"the correspondence model gives the FDK spacing {grid_spacing} mm, the reconstruction has {tuple(spacing)}: resample the model first")
+
+        def convert(field):  # [3, gx, gy, gz] voxels -> [3, nz, ny, nx] mm
+            field = np.asarray(field, dtype=np.float64)
+            return np.stack([to_fdk_frame(field[0] * sx), to_fdk_frame(-field[2] * sz), to_fdk_frame(-field[1] * sy)]).astype(np.float32)
+
+        mean = convert(np.asarray(model.mean_vector_field).reshape(3, *shape))
+        coefficients = np.asarray(model.coefficients).reshape(3, *shape, k_dims)
+        coefficients = np.stack([convert(coefficients[..., k]) for k in range(k_dims)])
+        return cls(mean, coefficients, np.asarray(model.mean_signal, dtype=np.float64).reshape(-1), spacing=grid_spacing)
+
+
+def fdk_motion(projections: np.ndarray, geometry: CircularGeometry, pixel_spacing: Tuple[float, float], pixel_origin: Optional[Tuple[float, float]],
+               motion: MotionModel, signals, dimension: Tuple[int, int, int], spacing: Tuple[float, float, float],
+               origin: Optional[Tuple[float, float, float]] = None, hann: float = 0.0, hann_y: float = 0.0,
+               water_pre_correction: Optional[Sequence[float]] = None, gpu_id: int = 0, pad: float = 0.0):
+    """Motion-compensated FDK (Rit et al. 2009; RTK's FDKWarpBackProjectionImageFilter, `rtkfdk --signal --dvf`): fdk() with every
+    projection back-projected along the trajectories `motion` predicts for its breathing state, so that all projections sharpen one
+    volume at the reference phase.  projections [n, nv, nu], signals [n, K] (one row per projection) -> (volume [nz, ny, nx]
+    float32, report dict: ms_filter, ms_backproject, ms_upload_model, peak_device_bytes).  The filter chain and every other argument
+    are those of fdk(); the arithmetic is csrc/fdk.hip: backproject_motion_kernel, whose header states the rule.  `motion` must
+    live on the reconstruction grid (ValueError otherwise) and map the reference phase forward (MotionModel.from_correspondence_model).
+    Parity against RTK's warp back-projector is unpinned (RTK is absent here); tests/fdk_motion_ref.py restates the rule in float64."""
+    from . import engine
+    lib = engine.load_library()
+    lib.mcgpu_fdk_reconstruct_motion.argtypes = [C.POINTER(_FdkOptions), C.POINTER(_FdkMotion), C.c_void_p, C.c_void_p, C.POINTER(_FdkMotionReport)]
+    lib.mcgpu_fdk_reconstruct_motion.restype = C.c_int
+    motion.check_grid(dimension, spacing)
+    p, o, keep = _fdk_options(projections, geometry, pixel_spacing, pixel_origin, dimension, spacing, origin, hann, hann_y, water_pre_correction, gpu_id, pad)
+    delta = motion.delta(signals)
+    if delta.shape[0] != p.shape[0]:
+        raise ValueError(f"{p.shape[0]} projections but {delta.shape[0]} signals")
+    if not np.isfinite(delta).all():
+        raise ValueError("the signals are not finite")
+    fp = C.POINTER(C.c_float)
+    m = _FdkMotion(C.sizeof(_FdkMotion), motion.n_signal_dims, motion.mean.ctypes.data_as(fp), motion.coefficients.ctypes.data_as(fp),
+                   delta.ctypes.data_as(C.POINTER(C.c_double)))
     vol = np.zeros((int(dimension[2]), int(dimension[1]), int(dimension[0])), dtype=np.float32)
-    rep = _FdkReport()
-    engine._check(lib.mcgpu_fdk_reconstruct(C.byref(o), p.ctypes.data, vol.ctypes.data, C.byref(rep)))
-    return vol, {"ms_filter": rep.ms_filter, "ms_backproject": rep.ms_backproject}
+    rep = _FdkMotionReport()
+    engine._check(lib.mcgpu_fdk_reconstruct_motion(C.byref(o), C.byref(m), p.ctypes.data, vol.ctypes.data, C.byref(rep)))
+    return vol, {name: getattr(rep, name) for name, _ in _FdkMotionReport._fields_}
 
 
 _MHA_ELEMENT_TYPES = {"MET_FLOAT": "<f4", "MET_SHORT": "<i2", "MET_UCHAR": "u1"}
@@ -231,6 +365,37 @@ def reconstruct_3d(projections_filepath, geometry_filepath, output_folder=None, 
     params = dict(path=str(projections_filepath.parent), regexp=projections_filepath.name, geometry=str(geometry_filepath), hardware="hip", pad=pad,
                   hann=hann, hannY=hann_y, dimension=list(dimension), spacing=list(spacing),
                   wpc=list(water_pre_correction) if water_pre_correction is not None else None, short=360,
+                  output_filepath=str(output_folder / output_filename), **kwargs)
+    with open((output_folder / output_filename).with_suffix(".yaml"), "w") as f:
+        yaml.dump(params, f)
+    return output_folder / output_filename, report
+
+
+def reconstruct_3d_mc(projections_filepath, geometry_filepath, correspondence_model, signals, voxel_spacing_mm, output_folder=None,
+                      output_filename: Optional[str] = None, dimension: Tuple[int, int, int] = (464, 250, 464),
+                      spacing: Tuple[float, float, float] = (1.0, 1.0, 1.0), pad: float = 1.0, hann: float = 1.0, hann_y: float = 1.0,
+                      water_pre_correction: Optional[Sequence[float]] = None, gpu_id: int = 0, **kwargs):
+    """reconstruct_3d with the motion of a fitted `CorrespondenceModel` compensated (fdk_motion): same defaults, same file flow.
+    correspondence_model: built with `build_default(..., inverse=True)` on the reconstruction grid (see
+    MotionModel.from_correspondence_model for the direction and the frame); voxel_spacing_mm: the spacing of the MCGeometry its
+    fields live on; signals [n, K]: the breathing signal of every projection, in the model's units.  Writes `recon_fdk3d_mc.mha`
+    and a .yaml that also records `motion` (the first 7 hex digits of the model's hash) and `signal_n_dims` (K)."""
+    projections_filepath, geometry_filepath = Path(projections_filepath), Path(geometry_filepath)
+    output_folder = Path(output_folder) if output_folder else projections_filepath.parent / "reconstructions"
+    output_filename = output_filename or "recon_fdk3d_mc.mha"
+    motion = MotionModel.from_correspondence_model(correspondence_model, voxel_spacing_mm, dimension=dimension, spacing=spacing)
+    output_folder.mkdir(parents=True, exist_ok=True)
+    proj, pspacing, porigin = read_mha(projections_filepath)
+    geometry = CircularGeometry.read(geometry_filepath)
+    vol, report = fdk_motion(proj, geometry, (pspacing[0], pspacing[1]), (porigin[0], porigin[1]), motion, signals, dimension, spacing, None, hann, hann_y,
+                             water_pre_correction, gpu_id, pad=pad)
+    origin = tuple(-(n - 1) / 2 * s for n, s in zip(dimension, spacing))
+    write_mha(output_folder / output_filename, vol, spacing, origin)
+    import yaml
+    params = dict(path=str(projections_filepath.parent), regexp=projections_filepath.name, geometry=str(geometry_filepath), hardware="hip", pad=pad,
+                  hann=hann, hannY=hann_y, dimension=list(dimension), spacing=list(spacing),
+                  wpc=list(water_pre_correction) if water_pre_correction is not None else None, short=360,
+                  motion=correspondence_model.model_hash[:7], signal_n_dims=motion.n_signal_dims,
                   output_filepath=str(output_folder / output_filename), **kwargs)
     with open((output_folder / output_filename).with_suffix(".yaml"), "w") as f:
         yaml.dump(params, f)

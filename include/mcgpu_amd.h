@@ -592,6 +592,29 @@ typedef struct mcgpu_fdk_report {
 } mcgpu_fdk_report;
 int mcgpu_fdk_reconstruct(const mcgpu_fdk_options *options, const float *projections, float *volume, mcgpu_fdk_report *report);
 
+/* Row f15: motion-compensated FDK (Rit et al., Med. Phys. 36 (2009); what RTK's FDKWarpBackProjectionImageFilter does for
+ * `rtkfdk --signal --dvf`; csrc/fdk.hip: backproject_motion_kernel, whose header states the rule).  The filter chain is that of
+ * mcgpu_fdk_reconstruct; the back-projector takes the sample of projection i for the voxel at P at P + mean(P) + sum_k
+ * coefficients[k](P) delta[i][k], the place where the model puts that voxel's material at the projection's breathing state.
+ * mean [3][nz][ny][nx] and coefficients [K][3][nz][ny][nx] live on the reconstruction grid, in mm (mm per signal unit), components
+ * along IEC X, Y, Z; delta[i][k] = signal_i[k] - mean_signal[k] (rounded once to float32).  The model maps the reference-phase
+ * volume forward; a pull-back model is NOT inverted.  Parity against RTK's warp back-projector is unpinned (RTK is absent here). */
+typedef struct mcgpu_fdk_motion {
+  unsigned int struct_size;     /* sizeof(mcgpu_fdk_motion) as the caller was compiled; 0 is refused */
+  int n_signal_dims;            /* K, 1..4 */
+  const float *mean;            /* [3][nz][ny][nx] */
+  const float *coefficients;    /* [K][3][nz][ny][nx] */
+  const double *delta;          /* [n_proj][K], finite */
+} mcgpu_fdk_motion;
+typedef struct mcgpu_fdk_motion_report {
+  double ms_filter;       /* as mcgpu_fdk_report */
+  double ms_backproject;  /* the motion back-projection kernels */
+  double ms_upload_model; /* host clock around the model's upload */
+  unsigned long long peak_device_bytes;
+} mcgpu_fdk_motion_report;
+int mcgpu_fdk_reconstruct_motion(const mcgpu_fdk_options *options, const mcgpu_fdk_motion *motion, const float *projections, float *volume,
+                                 mcgpu_fdk_motion_report *report);
+
 /* ------------------------------------------------------------------------------------------------
  * Row f13: the normal equations of the empirical water pre-correction (Sourbelle et al. 2005; what the reference's
  * scripts/fit_wpc.py computes from N + 1 rtkfdk runs), fused on the device (csrc/wpc_fit.hip; the rule: DESIGN.md row f13).
