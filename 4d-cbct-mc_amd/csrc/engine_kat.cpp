@@ -124,6 +124,52 @@ int mcgpu_kat_scatter(mcgpu_ctx* ctx, int mode, int kind, int n, unsigned int se
   ABI_END
 }
 
+int mcgpu_kat_history(mcgpu_ctx* ctx, int mode, int kind, int projection, int n, unsigned int seed, const float* in8, const unsigned long long* in_u64,
+                      float* out8, uint32_t* out_u8) {
+  ABI_BEGIN
+  require(ctx && ctx->has_device && out8 && out_u8 && n > 0 && n <= (1 << 24), -1, "!!ERROR!! mcgpu_kat_history: bad argument");
+  require(mode == MCGPU_MODE_FAST || mode == MCGPU_MODE_FAST_F64, -1, "!!ERROR!! mcgpu_kat_history: the hook exists in the FAST arithmetics only");
+  require(kind == MCGPU_KAT_SOURCE || kind == MCGPU_KAT_TALLY || kind == MCGPU_KAT_HOP, -1, "!!ERROR!! mcgpu_kat_history: unknown kind");
+  require(projection >= 0 && projection < ctx->host.cfg.num_projections, -1, "!!ERROR!! mcgpu_kat_history: a projection outside the context");
+  require((kind == MCGPU_KAT_SOURCE || in8 != nullptr) && (kind == MCGPU_KAT_TALLY || in_u64 != nullptr), -1, "!!ERROR!! mcgpu_kat_history: an input of this kind is missing");
+  const DeviceModel& D = ctx->dev;
+  HIP_TRY(hipSetDevice(D.device_id));
+  TrackArgs A = make_args(*ctx, projection);
+  A.dose_flags = 0;
+  A.first = 0;  // the id an item passes is its stream's id
+  A.seed = (int)seed;
+  // what the kernel indexes its tables with is checked here.  None of the three kinds indexes anything by the photon's position (the
+  // exterior is crossed analytically, the detector is a plane); positions and directions only have to be numbers.
+  const float e0 = ctx->host.mat.e0, ide = ctx->host.mat.ide, top = (float)(ctx->host.mat.num_values - 1);
+  auto in_tables = [&](float e) { const float t = (e - e0) * ide; return t >= 0.0f && t < top; };
+  if (kind == MCGPU_KAT_SOURCE) {  // every energy the spectrum can hand out (below its last edge): the record of its bin
+    const Spectrum& S = ctx->host.spectrum;
+    require(S.num_bins > 0 && in_tables(S.espc[0]) && (S.espc[S.num_bins] - e0) * ide <= top, -2,
+            "!!ERROR!! mcgpu_kat_history: a spectrum energy outside the cross-section tables");
+  } else {
+    require(kind != MCGPU_KAT_HOP || (A.has_exterior & 2) != 0, -2, "!!ERROR!! mcgpu_kat_history: the context's geometry has no homogeneous exterior to hop across");
+    for (int i = 0; i < n; ++i) {
+      const float* p = in8 + 8 * (size_t)i;
+      for (int k = 0; k < 7; ++k) require(std::isfinite(p[k]), -2, "!!ERROR!! mcgpu_kat_history: an input that is not a number");
+      if (kind == MCGPU_KAT_HOP) require(in_tables(p[6]), -2, "!!ERROR!! mcgpu_kat_history: an energy outside the cross-section tables");
+      else  // the tally looks nothing up by energy: its value must fit the 32-bit word the kernels hand to tally_score
+        require(p[6] >= 0.0f && p[6] < 4.0e7f && p[7] >= 0.0f && p[7] <= 3.0f && p[7] == (float)(int)p[7], -2,
+                "!!ERROR!! mcgpu_kat_history: a tally energy or scatter state out of range");
+    }
+  }
+  CallDevice dev;
+  const size_t n32 = (size_t)n * 32;
+  const float* d_in = in8 ? dev.upload(in8, (size_t)n * 8) : nullptr;
+  const unsigned long long* d_u64 = in_u64 ? dev.upload(in_u64, (size_t)n) : nullptr;
+  float* d_out = dev.alloc_zeroed<float>(n32);
+  unsigned int* d_out_u = dev.alloc_zeroed<unsigned int>(n32);
+  HIP_TRY((mode == MCGPU_MODE_FAST_F64 ? launch_kat_history_fast64 : launch_kat_history_fast)(A, kind, n, d_in, d_u64, d_out, d_out_u, nullptr));
+  HIP_TRY(hipMemcpy(out8, d_out, n32, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_u8, d_out_u, n32, hipMemcpyDeviceToHost));
+  return 0;
+  ABI_END
+}
+
 int mcgpu_kat_f32(mcgpu_ctx* ctx, int op, int n, const float* a, const float* b, float* inout) {
   ABI_BEGIN
   require(ctx && ctx->has_device && a && b && inout && n > 0 && op >= 0 && op <= 4, -1, "!!ERROR!! mcgpu_kat_f32: bad argument");

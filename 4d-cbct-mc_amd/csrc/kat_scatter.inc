@@ -73,3 +73,7 @@ hipError_t MC_KAT_SCATTER_NAME(const TrackArgs& args, int kind, int n, unsigned 
   return hipGetLastError();
 }
 }  // namespace mcgpu
+
+// the sibling hook of the two ends of a history (mcgpu_kat_history), included from here so that both arithmetics get it wherever they
+// get this one, and the text of track_fast.hip -- part of the kernel-build stamp of the committed counter summaries -- stays what it was
+#include "kat_history.inc"

@@ -1087,6 +1087,25 @@ const void* host_table(mcgpu_ctx& C, const std::string& name, size_t& bytes) {
   if (name == "espc_cutoff") return cache(H.spectrum.cutoff, sizeof H.spectrum.cutoff);
   if (name == "espc_alias") return cache(H.spectrum.alias, sizeof H.spectrum.alias);
   if (name == "palette") return cache(C.dev.palette_host.data(), C.dev.palette_host.size() * sizeof(float));  // u8 volumes: {density, bits(compact material)} per entry, in palette order
+  if (name == "track_cold" && C.has_device) {
+    // the TrackCold scalars a restatement of the source, the exterior hop and the tally needs (tests/source_ref.py), read-only, as
+    // 19 floats: fan_ratio_lo, fan_ratio_hi, objbox_lo[3], objbox_hi[3], ell_c[2], ell_inv[2], bbox[3], then the homogeneous exterior:
+    // 1 if the geometry has one, its density, its material number - 1 and its compact material index (else 0, 0, -1, -1)
+    const DeviceModel& D = C.dev;
+    const TrackCold& ch = D.cold_host;
+    float v[19] = {ch.fan_ratio_lo, ch.fan_ratio_hi, ch.objbox_lo[0], ch.objbox_lo[1], ch.objbox_lo[2], ch.objbox_hi[0], ch.objbox_hi[1], ch.objbox_hi[2],
+                   ch.ell_c[0], ch.ell_c[1], ch.ell_inv[0], ch.ell_inv[1], ch.bbox[0], ch.bbox[1], ch.bbox[2], 0.f, 0.f, -1.f, -1.f};
+    if (D.vol_kind == kVolU8 && D.has_exterior && 2 * (size_t)D.background + 1 < D.palette_host.size()) {
+      int mc;
+      memcpy(&mc, &D.palette_host[2 * (size_t)D.background + 1], 4);
+      v[15] = 1.f;
+      v[16] = D.palette_host[2 * (size_t)D.background];
+      v[18] = (float)mc;
+      for (int m = 0; m < kMaxMaterials; ++m)
+        if (D.compact_of[m] == mc) v[17] = (float)m;
+    }
+    return cache(v, sizeof v);
+  }
   if (name == "density_max") return cache(H.voxels.density_max, sizeof H.voxels.density_max);
   if (name == "density_nominal") return cache(H.mat.density_nominal, sizeof H.mat.density_nominal);
   if (name == "voxel_size") return cache(H.voxels.voxel_size, sizeof H.voxels.voxel_size);

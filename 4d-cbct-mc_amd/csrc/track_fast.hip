@@ -54,4 +54,4 @@ hipError_t launch_kat_streams_fast(int generator, unsigned int seed, unsigned in
 }
 }  // namespace mcgpu
 
-#include "kat_scatter.inc"  // mcgpu_kat_scatter: the production service bodies, one event per thread
+#include "kat_scatter.inc"  // mcgpu_kat_scatter: the production service bodies, one event per thread (and, behind it, kat_history.inc)

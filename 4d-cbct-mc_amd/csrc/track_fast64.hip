@@ -35,4 +35,4 @@ hipError_t launch_kat_fast64(int n, const unsigned int* u, const double* a, cons
 }
 }  // namespace mcgpu
 
-#include "kat_scatter.inc"  // mcgpu_kat_scatter: the production service bodies, one event per thread
+#include "kat_scatter.inc"  // mcgpu_kat_scatter: the production service bodies, one event per thread (and, behind it, kat_history.inc)

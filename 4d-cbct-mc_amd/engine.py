@@ -31,7 +31,7 @@ ABI_SYMBOLS = (
     "mcgpu_warp_volume", "mcgpu_warp_geometry", "mcgpu_map_image", "mcgpu_set_geometry_image",
     "mcgpu_resample_plan", "mcgpu_resample_volume", "mcgpu_set_geometry_image_resampled",
     "mcgpu_correspondence_set", "mcgpu_correspondence_fit", "mcgpu_correspondence_predict", "mcgpu_warp_geometry_signal", "mcgpu_correspondence_clear",
-    "mcgpu_write_voxel_file", "mcgpu_write_voxel_binary", "mcgpu_kat_rng", "mcgpu_kat_rng_streams", "mcgpu_microbench", "mcgpu_kat_math", "mcgpu_kat_expf", "mcgpu_kat_f32", "mcgpu_kat_fast64", "mcgpu_kat_scatter", "mcgpu_kat_tile_records", "mcgpu_fdk_reconstruct", "mcgpu_fdk_reconstruct_motion", "mcgpu_wpc_fit", "mcgpu_forward_project", "mcgpu_forward_project_context", "mcgpu_rooster4d_reconstruct", "mcgpu_rooster4d_stage", "mcgpu_register", "mcgpu_register_stage", "mcgpu_speedup_run", "mcgpu_speedup_stage", "mcgpu_segment_run", "mcgpu_segment_stage", "mcgpu_set_fast_schedule", "mcgpu_reload_env_knobs",
+    "mcgpu_write_voxel_file", "mcgpu_write_voxel_binary", "mcgpu_kat_rng", "mcgpu_kat_rng_streams", "mcgpu_microbench", "mcgpu_kat_math", "mcgpu_kat_expf", "mcgpu_kat_f32", "mcgpu_kat_fast64", "mcgpu_kat_scatter", "mcgpu_kat_history", "mcgpu_kat_tile_records", "mcgpu_fdk_reconstruct", "mcgpu_fdk_reconstruct_motion", "mcgpu_wpc_fit", "mcgpu_forward_project", "mcgpu_forward_project_context", "mcgpu_rooster4d_reconstruct", "mcgpu_rooster4d_stage", "mcgpu_register", "mcgpu_register_stage", "mcgpu_speedup_run", "mcgpu_speedup_stage", "mcgpu_segment_run", "mcgpu_segment_stage", "mcgpu_set_fast_schedule", "mcgpu_reload_env_knobs",
     "mcgpu_exchange_shared_bytes", "mcgpu_exchange_card_bytes", "mcgpu_exchange_create", "mcgpu_exchange_card", "mcgpu_exchange_connect",
     "mcgpu_exchange_connect_local", "mcgpu_exchange_probe", "mcgpu_exchange_owner", "mcgpu_exchange_begin", "mcgpu_exchange_submit", "mcgpu_exchange_collect",
     "mcgpu_exchange_stats", "mcgpu_exchange_destroy", "mcgpu_copy_to_host",
@@ -210,6 +210,7 @@ def load_library(path: Optional[os.PathLike] = None):
     lib.mcgpu_kat_f32.argtypes = [vp, ci, ci, vp, vp, vp]
     lib.mcgpu_kat_fast64.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
     lib.mcgpu_kat_scatter.argtypes = [vp, ci, ci, ci, C.c_uint, C.c_uint, vp, vp, vp, vp, vp]
+    lib.mcgpu_kat_history.argtypes = [vp, ci, ci, ci, ci, C.c_uint, vp, vp, vp, vp]
     lib.mcgpu_kat_tile_records.argtypes = [ci, vp, vp]
     if path is None:
         _lib = lib
@@ -1048,6 +1049,29 @@ class Context:
                                           in4.ctypes.data, u64.ctypes.data, None if mat is None else mat.ctypes.data, out4.ctypes.data,
                                           out_u4.ctypes.data))
         return out4[:, 0].copy(), out4[:, 1:].copy(), out_u4[:, 0].copy(), out_u4[:, 1].copy(), out_u4[:, 2:].copy()
+
+    def kat_history(self, mode, kind: str, projection: int, items=None, ids=None, seed: int = 0):
+        """The two ends of a FAST history as the photon kernels run them (include/mcgpu_amd.h: mcgpu_kat_history), one item per thread,
+        under the pose of `projection`.  kind "source": ids = history ids; "tally": items = float32[n, 8] {x, y, z, u, v, w, E, scatter
+        state}; "hop": items = {x, y, z, u, v, w, E, -} and ids.  Returns a dict: energy float32[n], direction and position float32[n, 3],
+        mfpW, and phase, index, mc, scatter, state uint32[n, 2], word (int64, -1: none), value."""
+        in8 = None if items is None else np.ascontiguousarray(items, dtype=np.float32).reshape(-1, 8)
+        u64 = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        if kind not in ("source", "tally", "hop"):
+            raise ValueError(f"kind '{kind}': 'source', 'tally' or 'hop'")
+        if (kind != "source" and in8 is None) or (kind != "tally" and u64 is None):
+            raise ValueError(f"kind '{kind}' needs " + ("ids" if kind == "source" else "items" if kind == "tally" else "items and ids"))
+        n = in8.shape[0] if in8 is not None else u64.size
+        if (in8 is not None and in8.shape[0] != n) or (u64 is not None and u64.size != n) or n == 0:
+            raise ValueError("items and ids must hold the same, non-zero, number of entries")
+        out8, out_u8 = np.zeros((n, 8), dtype=np.float32), np.zeros((n, 8), dtype=np.uint32)
+        _check(self.lib.mcgpu_kat_history(self.h, _MODES[mode], {"source": 0, "tally": 1, "hop": 2}[kind], int(projection), n, int(seed),
+                                          None if in8 is None else in8.ctypes.data, None if u64 is None else u64.ctypes.data,
+                                          out8.ctypes.data, out_u8.ctypes.data))
+        return dict(e=out8[:, 0].copy(), d=out8[:, 1:4].copy(), pos=out8[:, 4:7].copy(), mfpw=out8[:, 7].copy(),
+                    phase=out_u8[:, 0].astype(np.int64), index=out_u8[:, 1].astype(np.int64), mc=out_u8[:, 2].astype(np.int64),
+                    scatter=out_u8[:, 3].astype(np.int64), state=out_u8[:, 4:6].copy(), word=out_u8[:, 6].view(np.int32).astype(np.int64),
+                    value=out_u8[:, 7].astype(np.int64))
 
     def kat_f32(self, op: int, a, b=None, c=None):
         """Float operations of the COMPAT kernel (include/mcgpu_amd.h: mcgpu_kat_f32)."""

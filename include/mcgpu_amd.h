@@ -66,7 +66,7 @@ int mcgpu_clone(const mcgpu_ctx *src, int device_id, mcgpu_ctx **out);
  * "gpu_id", "threads_per_block", "histories_per_thread", "num_projections", "enable_specific_angles",
  * "num_voxels_x|y|z", "num_pixels_x|z", "num_materials_used", "num_energy_values", "palette_size",
  * "volume_bytes_device"; of the device model (diagnostic): "volume_kind", "brick_shift", "brick_count", "bricks_mixed",
- * "bricks_exterior", "exterior_cylinder", "tile_records", "sub_brick_table", "fast_scheduler", "segment_loop", "tiles_in_mixed_bricks", "sigma_bracket_shift", "lds_bytes_fast",
+ * "bricks_exterior", "exterior_cylinder", "exterior_mode" (bit 0: hop across the homogeneous exterior during flight, bit 1: at the source), "tile_records", "sub_brick_table", "fast_scheduler", "segment_loop", "tiles_in_mixed_bricks", "sigma_bracket_shift", "lds_bytes_fast",
  * "lds_bytes_compat", "blocks_per_cu", "num_cus", "device_id". */
 int mcgpu_config_i64(const mcgpu_ctx *ctx, const char *key, long long *value);
 /* Keys: "D_angle", "initial_angle", "angularROI_0", "angularROI_1", "SRotAxisD", "vertical_translation",
@@ -78,7 +78,10 @@ int mcgpu_config_f64(const mcgpu_ctx *ctx, const char *key, double *value);
  * (float2 x nvox, built on demand), "mfp_woodcock", "mfp_a", "mfp_b", "xco","pco","aco","bco","pmax",
  * "itlco","ituco","fco","uico","fj0","noscco","espc","espc_cutoff","espc_alias","density_max",
  * "density_nominal","voxel_size","inv_voxel_size","size_bbox"; of the device model: "palette" (float2 {density, bits(compact material
- * index)} per entry of a u8 palette volume, in palette order).  The pointer stays valid until destroy. */
+ * index)} per entry of a u8 palette volume, in palette order), "track_cold" (contexts with a device; 19 floats the FAST kernels read at their
+ * scheduling points: fan_ratio_lo, fan_ratio_hi, object box lo[3] / hi[3], elliptic cylinder centre[2] / inverse squared semi-axes[2] (0: none),
+ * bounding box[3], then the homogeneous exterior: 1 if there is one, its density, its material number - 1, its compact material index).
+ * The pointer stays valid until destroy. */
 int mcgpu_host_table(mcgpu_ctx *ctx, const char *name, const void **data, size_t *bytes);
 
 /* Output file name of projection p: "<base>_%010.6fdeg" with the float32 angle (MC-GPU_v1.3.cu:2787-2803). */
@@ -551,6 +554,25 @@ int mcgpu_kat_fast64(mcgpu_ctx *ctx, int n, const uint32_t *u, const double *a, 
 #define MCGPU_KAT_COMPTON 2
 int mcgpu_kat_scatter(mcgpu_ctx *ctx, int mode, int kind, int n, unsigned int seed, unsigned int stream_key, const float *in4,
                       const unsigned long long *in_u64, const int *material, float *out4, uint32_t *out_u4);
+/* The two ends of a history of MCGPU_MODE_FAST / MCGPU_MODE_FAST_F64 as the photon kernels run them (csrc/kat_history.inc: the functions
+ * of csrc/track_pool.inc themselves, one item per thread), under the pose of projection `projection` of the context and from the
+ * per-history stream of (id, seed, projection), so that a test can replay every deviate.  Nothing is tallied.
+ *   MCGPU_KAT_SOURCE  in_u64[i] = history id (in8 may be NULL): a new history -- spectrum energy, direction in the fan, then the entry
+ *                     into the volume: across the homogeneous exterior to the object region where the geometry has one (an interaction
+ *                     in the background is classified), else the reference's move_to_bbox (MC-GPU_kernel_v1.3.cu:626-686, :714-805)
+ *   MCGPU_KAT_TALLY   in8[8 i ..] = {x, y, z, u, v, w, E, scatter state 0..3} (in_u64 may be NULL): an escaped photon is projected onto
+ *                     the detector (tally_image, :482-604)
+ *   MCGPU_KAT_HOP     in8[8 i ..] = {x, y, z, u, v, w, E, -}, in_u64[i] = history id: one hop across the homogeneous exterior (geometries
+ *                     that have one only: others are refused with -2)
+ * out8[8 i ..] = {E, u, v, w, x, y, z, Woodcock majorant mean free path}; out_u8[8 i ..] = {final phase (0 in flight, 1 Compton, 2 Rayleigh,
+ * 3 escaped, 4 absorbed, 5 new), energy bin, compact material, scatter state, generator state x, c, tally word (0xFFFFFFFF: none), tally
+ * value}.  Refused before any launch: a projection outside the context (-1); an energy outside the cross-section tables, an input
+ * that is not a number, a scatter state outside 0..3 (-2). */
+#define MCGPU_KAT_SOURCE 0
+#define MCGPU_KAT_TALLY 1
+#define MCGPU_KAT_HOP 2
+int mcgpu_kat_history(mcgpu_ctx *ctx, int mode, int kind, int projection, int n, unsigned int seed, const float *in8,
+                      const unsigned long long *in_u64, float *out8, uint32_t *out_u8);
 /* The 16-byte record of a 4x4x4 tile of a u8-palette volume as the host and the device build it (csrc/device_model.hpp:
  * encode_tile_record; no reference counterpart -- the reference gathers the voxel itself, MC-GPU_kernel_v1.3.cu:262-266).  Host code
  * only, no context: indices[t * 64 + v] = palette index of voxel v = (iz & 3) 16 + (iy & 3) 4 + (ix & 3) of tile t, negative = padding

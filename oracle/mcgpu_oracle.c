@@ -575,14 +575,13 @@ static inline void tally_pixel(uint64_t *image, uint64_t *w2, int word, float en
   if (w2) tally_add(&w2[word], (w >> 10) * (w >> 10), shared);
 }
 
-static void tally_image(float energy, f3 *pos, const f3 *dir, int scatter_state, uint64_t *image, uint64_t *w2, const src_t *S, const det_t *D,
-                        oracle_counters *C, int shared)
+/* word of the image the photon scores in, or -1: cannot reach the detector plane, or misses the detector */
+static int tally_word(f3 *pos, const f3 *dir, int scatter_state, const src_t *S, const det_t *D)
 {
   float dist, rot;
-  C->tally_calls++;
   if (D->rotation_flag == 1) {
     float cosang = dir->x * S->direction.x + (dir->y * S->direction.y + (dir->z * S->direction.z));
-    if (cosang < 0.025f) return;
+    if (cosang < 0.025f) return -1;
     dist = (S->direction.x * (D->center.x - pos->x) + (S->direction.y * (D->center.y - pos->y) + (S->direction.z * (D->center.z - pos->z)))) / cosang;
     pos->x = pos->x + dist * dir->x;
     pos->y = pos->y + dist * dir->y;
@@ -592,23 +591,45 @@ static void tally_image(float energy, f3 *pos, const f3 *dir, int scatter_state,
     if ((px > -0.1f) && (px < (D->num_pixels_x - 0.1f))) {
       rot = D->rot_inv[6] * pos->x + D->rot_inv[7] * pos->y + D->rot_inv[8] * pos->z;
       float pz = floor((rot - D->corner_min_rotated_to_Y.z) * D->inv_pixel_size_Z);
-      if ((pz > -0.1f) && (pz < (D->num_pixels_y - 0.1f))) {
-        tally_pixel(image, w2, (int)(((float)scatter_state) * D->total_num_pixels + px + pz * D->num_pixels_x + 0.0001f), energy, shared);
-        C->tally_hits++;
-      }
+      if ((pz > -0.1f) && (pz < (D->num_pixels_y - 0.1f)))
+        return (int)(((float)scatter_state) * D->total_num_pixels + px + pz * D->num_pixels_x + 0.0001f);
     }
   } else {
-    if (dir->y < 0.0001f) return;
+    if (dir->y < 0.0001f) return -1;
     dist = (D->center.y - pos->y) / (dir->y);
     float px = floor((pos->x + dist * dir->x - D->corner_min_rotated_to_Y.x) * D->inv_pixel_size_X);
     if ((px > -0.1f) && (px < (D->num_pixels_x - 0.1f))) {
       float pz = floor((pos->z + dist * dir->z - D->corner_min_rotated_to_Y.z) * D->inv_pixel_size_Z);
-      if ((pz > -0.1f) && (pz < (D->num_pixels_y - 0.1f))) {
-        tally_pixel(image, w2, (int)(((float)scatter_state) * D->total_num_pixels + px + pz * D->num_pixels_x + 0.0001f), energy, shared);
-        C->tally_hits++;
-      }
+      if ((pz > -0.1f) && (pz < (D->num_pixels_y - 0.1f)))
+        return (int)(((float)scatter_state) * D->total_num_pixels + px + pz * D->num_pixels_x + 0.0001f);
     }
   }
+  return -1;
+}
+
+static void tally_image(float energy, f3 *pos, const f3 *dir, int scatter_state, uint64_t *image, uint64_t *w2, const src_t *S, const det_t *D,
+                        oracle_counters *C, int shared)
+{
+  C->tally_calls++;
+  const int word = tally_word(pos, dir, scatter_state, S, D);
+  if (word >= 0) {
+    tally_pixel(image, w2, word, energy, shared);
+    C->tally_hits++;
+  }
+}
+
+/* one event of tally_image for projection num_p: the image word (-1: none) and the weight it would add */
+int oracle_tally_image(const oracle_tables *T, int num_p, const float *pos3, const float *dir3, float energy, int scatter_state, unsigned long long *weight)
+{
+  f3 p = { pos3[0], pos3[1], pos3[2] }, d = { dir3[0], dir3[1], dir3[2] };
+  *weight = (unsigned long long)(energy * 100.0f + 0.5f);
+  return tally_word(&p, &d, scatter_state, (const src_t *)T->source_data + num_p, (const det_t *)T->detector_data + num_p);
+}
+
+void oracle_tally_image_many(const oracle_tables *T, int num_p, long n, const float *pos3, const float *dir3, const float *energy, const int *scatter_state,
+                             int *word_out, unsigned long long *weight_out)
+{
+  for (long k = 0; k < n; k++) word_out[k] = oracle_tally_image(T, num_p, pos3 + 3 * k, dir3 + 3 * k, energy[k], scatter_state[k], &weight_out[k]);
 }
 
 /* tally_materials_dose (K.cu:1547-1563) + tally_voxel_energy_deposition (K.cu:418-443), CPU-build rounding */

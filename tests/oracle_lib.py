@@ -87,6 +87,11 @@ def oracle():
         lib.oracle_graa_many.argtypes = [C.POINTER(OracleTables), C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_void_p]
         lib.oracle_source.argtypes = [C.POINTER(OracleTables), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_int]
+        lib.oracle_tally_image.restype = C.c_int
+        lib.oracle_tally_image.argtypes = [C.POINTER(OracleTables), C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p]
+        lib.oracle_tally_image_many.restype = None
+        lib.oracle_tally_image_many.argtypes = [C.POINTER(OracleTables), C.c_int, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]
         _oracle = lib
     return _oracle
 
@@ -151,6 +156,17 @@ class TableSet:
         finally:
             self.ct.image_w2 = None
         return image, cnt
+
+    def tally_events(self, num_p, pos, direction, energy, scatter_state):
+        """tally_image of projection num_p, event by event: (image word or -1 as int64[n], weight uint64[n])."""
+        pos, direction = (np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 3) for v in (pos, direction))
+        n = pos.shape[0]
+        energy = np.ascontiguousarray(np.broadcast_to(np.asarray(energy, dtype=np.float32), (n,)))
+        state = np.ascontiguousarray(np.broadcast_to(np.asarray(scatter_state, dtype=np.int32), (n,)))
+        word, weight = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.uint64)
+        oracle().oracle_tally_image_many(C.byref(self.ct), int(num_p), n, pos.ctypes.data, direction.ctypes.data, energy.ctypes.data,
+                                         state.ctypes.data, word.ctypes.data, weight.ctypes.data)
+        return word.astype(np.int64), weight
 
     def track_with_variance(self, num_p, seed, batch0, nbatches, hpt, math_mode=MATH_LIBM, n_threads=1):
         """(image, sum of squared weights in the image's units squared as float64, counters)."""
