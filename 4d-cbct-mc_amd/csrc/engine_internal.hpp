@@ -43,6 +43,11 @@ hipError_t launch_kat_history_fast(const TrackArgs& args, int kind, int n, const
                                    unsigned int* out_u8, hipStream_t stream);
 hipError_t launch_kat_history_fast64(const TrackArgs& args, int kind, int n, const float* in8, const unsigned long long* in_u64, float* out8,
                                      unsigned int* out_u8, hipStream_t stream);
+// kat_flight.inc, once per arithmetic (track_fast.hip / track_fast64.hip)
+hipError_t launch_kat_flight_fast(const TrackArgs& args, int kind, int n, int max_steps, const float* in8, const unsigned long long* in_u64,
+                                  unsigned int* out, hipStream_t stream);
+hipError_t launch_kat_flight_fast64(const TrackArgs& args, int kind, int n, int max_steps, const float* in8, const unsigned long long* in_u64,
+                                    unsigned int* out, hipStream_t stream);
 hipError_t prepare_tally_fold(const StageArgs& S);  // tally_fold.hip
 hipError_t launch_tally_fold(const StageArgs& S, unsigned int workgroups, unsigned long long* image, hipStream_t stream);
 hipError_t launch_tally_fold_squares(const StageArgs& S, unsigned int workgroups, unsigned long long* w2, hipStream_t stream);

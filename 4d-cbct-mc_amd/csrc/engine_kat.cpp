@@ -170,6 +170,47 @@ int mcgpu_kat_history(mcgpu_ctx* ctx, int mode, int kind, int projection, int n,
   ABI_END
 }
 
+int mcgpu_kat_flight(mcgpu_ctx* ctx, int mode, int kind, int projection, int n, int max_steps, unsigned int seed, const float* in8,
+                     const unsigned long long* in_u64, uint32_t* out_u32) {
+  ABI_BEGIN
+  require(ctx && ctx->has_device && in8 && out_u32 && n > 0 && n <= (1 << 20), -1, "!!ERROR!! mcgpu_kat_flight: bad argument");
+  require(mode == MCGPU_MODE_FAST || mode == MCGPU_MODE_FAST_F64, -1, "!!ERROR!! mcgpu_kat_flight: the hook exists in the FAST arithmetics only");
+  require(kind == MCGPU_KAT_LOOKUP || kind == MCGPU_KAT_FLIGHT, -1, "!!ERROR!! mcgpu_kat_flight: unknown kind");
+  require(projection >= 0 && projection < ctx->host.cfg.num_projections, -1, "!!ERROR!! mcgpu_kat_flight: a projection outside the context");
+  const bool flight = kind == MCGPU_KAT_FLIGHT;
+  if (flight) {
+    require(in_u64 != nullptr, -1, "!!ERROR!! mcgpu_kat_flight: an input of this kind is missing");
+    require(max_steps >= 1 && max_steps <= 32 && (long long)n * max_steps <= (1LL << 22), -1, "!!ERROR!! mcgpu_kat_flight: step count out of range");
+  }
+  // what the kernel indexes its tables with is checked here, before any HIP call.  A position only has to be a number: the flight step
+  // clamps it to the volume before it indexes anything.  The step count is bounded by the argument.
+  const float e0 = ctx->host.mat.e0, ide = ctx->host.mat.ide, top = (float)(ctx->host.mat.num_values - 1);
+  for (int i = 0; i < n; ++i) {
+    const float* p = in8 + 8 * (size_t)i;
+    for (int k = 0; k < (flight ? 7 : 3); ++k) require(std::isfinite(p[k]), -2, "!!ERROR!! mcgpu_kat_flight: an input that is not a number");
+    if (flight) {
+      require(p[3] != 0.0f || p[4] != 0.0f || p[5] != 0.0f, -2, "!!ERROR!! mcgpu_kat_flight: a direction of length zero");
+      const float t = (p[6] - e0) * ide;
+      require(t >= 0.0f && t < top, -2, "!!ERROR!! mcgpu_kat_flight: an energy outside the cross-section tables");
+    }
+  }
+  const DeviceModel& D = ctx->dev;
+  HIP_TRY(hipSetDevice(D.device_id));
+  TrackArgs A = make_args(*ctx, projection);
+  A.dose_flags = 0;
+  A.first = 0;  // the id an item passes is its stream's id
+  A.seed = (int)seed;
+  CallDevice dev;
+  const size_t words = (size_t)n * 8 * (flight ? (size_t)max_steps + 1 : 1);
+  const float* d_in = dev.upload(in8, (size_t)n * 8);
+  const unsigned long long* d_u64 = in_u64 ? dev.upload(in_u64, (size_t)n) : nullptr;
+  unsigned int* d_out = dev.alloc_zeroed<unsigned int>(words * 4);
+  HIP_TRY((mode == MCGPU_MODE_FAST_F64 ? launch_kat_flight_fast64 : launch_kat_flight_fast)(A, kind, n, flight ? max_steps : 0, d_in, d_u64, d_out, nullptr));
+  HIP_TRY(hipMemcpy(out_u32, d_out, words * 4, hipMemcpyDeviceToHost));
+  return 0;
+  ABI_END
+}
+
 int mcgpu_kat_f32(mcgpu_ctx* ctx, int op, int n, const float* a, const float* b, float* inout) {
   ABI_BEGIN
   require(ctx && ctx->has_device && a && b && inout && n > 0 && op >= 0 && op <= 4, -1, "!!ERROR!! mcgpu_kat_f32: bad argument");

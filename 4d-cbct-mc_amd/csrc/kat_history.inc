@@ -71,3 +71,7 @@ hipError_t MC_KAT_HISTORY_NAME(const TrackArgs& args, int kind, int n, const flo
   return hipGetLastError();
 }
 }  // namespace mcgpu
+
+// the sibling hook of the middle of a history, the Woodcock flight step (mcgpu_kat_flight), included from here for the reason this file
+// hangs off kat_scatter.inc: both arithmetics get it, and the text of track_fast.hip stays what it was
+#include "kat_flight.inc"

@@ -1106,6 +1106,30 @@ const void* host_table(mcgpu_ctx& C, const std::string& name, size_t& bytes) {
     }
     return cache(v, sizeof v);
   }
+  if (C.has_device) {
+    // what the FAST flight step reads (track_pool.inc: flight_locate, flight_resolve), downloaded from the device as it stands there
+    // (tests/flight_ref.py): the total cross sections, the brackets, the brick grid and the second level as tile records
+    const DeviceModel& D = C.dev;
+    auto download = [&](const void* dev_ptr, size_t n) -> const void* {
+      auto& v = C.table_cache[name];
+      v.assign(n, 0);
+      bytes = n;
+      if (n != 0 && dev_ptr != nullptr) {
+        HIP_TRY(hipSetDevice(D.device_id));
+        HIP_TRY(hipMemcpy(v.data(), dev_ptr, n, hipMemcpyDeviceToHost));
+      }
+      return v.data();
+    };
+    const size_t nc = D.sig_shift >= 0 ? (size_t)coarse_bins(H.mat.num_values, D.sig_shift) : 0;
+    if (name == "mfp_tot") return download(D.mfp_tot, (size_t)D.nmat * (size_t)H.mat.num_values * 2 * sizeof(float));  // float2 {a_tot, b_tot} per row mc * num_values + bin
+    if (name == "sigma_bracket_mid") return download(D.cold_host.sig_mid, nc * (size_t)D.nmat * 2);  // fp16 words [coarse bin * nmat + mc]; empty: no brackets
+    if (name == "sigma_bracket_w") return download(D.cold_host.sig_w, nc * sizeof(float));
+    if (name == "compact_of") return cache(D.compact_of, sizeof D.compact_of);  // int[25]: compact material of material number - 1, -1: unused
+    if (name == "brick_palette") return cache(D.cold_host.brick_palette, sizeof D.cold_host.brick_palette);  // int[16]: palette index of brick code c
+    if (name == "brick_codes") return download(D.vol_kind == kVolU8 ? D.bricks : nullptr, D.vol_kind == kVolU8 ? (size_t)D.brick_bytes : 0);  // two 4-bit codes per byte
+    if (name == "tile_record_words")  // uint32[4] {ab, code, mask low, mask high} per tile, in tile_record_index order; empty: no records
+      return download(D.tile_rec, D.tile_rec ? (size_t)D.rec_n[0] * D.rec_n[1] * D.rec_n[2] * 8 * sizeof(TileRecord) : 0);
+  }
   if (name == "density_max") return cache(H.voxels.density_max, sizeof H.voxels.density_max);
   if (name == "density_nominal") return cache(H.mat.density_nominal, sizeof H.mat.density_nominal);
   if (name == "voxel_size") return cache(H.voxels.voxel_size, sizeof H.voxels.voxel_size);

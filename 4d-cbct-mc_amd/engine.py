@@ -31,7 +31,7 @@ ABI_SYMBOLS = (
     "mcgpu_warp_volume", "mcgpu_warp_geometry", "mcgpu_map_image", "mcgpu_set_geometry_image",
     "mcgpu_resample_plan", "mcgpu_resample_volume", "mcgpu_set_geometry_image_resampled",
     "mcgpu_correspondence_set", "mcgpu_correspondence_fit", "mcgpu_correspondence_predict", "mcgpu_warp_geometry_signal", "mcgpu_correspondence_clear",
-    "mcgpu_write_voxel_file", "mcgpu_write_voxel_binary", "mcgpu_kat_rng", "mcgpu_kat_rng_streams", "mcgpu_microbench", "mcgpu_kat_math", "mcgpu_kat_expf", "mcgpu_kat_f32", "mcgpu_kat_fast64", "mcgpu_kat_scatter", "mcgpu_kat_history", "mcgpu_kat_tile_records", "mcgpu_fdk_reconstruct", "mcgpu_fdk_reconstruct_motion", "mcgpu_wpc_fit", "mcgpu_forward_project", "mcgpu_forward_project_context", "mcgpu_rooster4d_reconstruct", "mcgpu_rooster4d_stage", "mcgpu_register", "mcgpu_register_stage", "mcgpu_speedup_run", "mcgpu_speedup_stage", "mcgpu_segment_run", "mcgpu_segment_stage", "mcgpu_set_fast_schedule", "mcgpu_reload_env_knobs",
+    "mcgpu_write_voxel_file", "mcgpu_write_voxel_binary", "mcgpu_kat_rng", "mcgpu_kat_rng_streams", "mcgpu_microbench", "mcgpu_kat_math", "mcgpu_kat_expf", "mcgpu_kat_f32", "mcgpu_kat_fast64", "mcgpu_kat_scatter", "mcgpu_kat_history", "mcgpu_kat_flight", "mcgpu_kat_tile_records", "mcgpu_fdk_reconstruct", "mcgpu_fdk_reconstruct_motion", "mcgpu_wpc_fit", "mcgpu_forward_project", "mcgpu_forward_project_context", "mcgpu_rooster4d_reconstruct", "mcgpu_rooster4d_stage", "mcgpu_register", "mcgpu_register_stage", "mcgpu_speedup_run", "mcgpu_speedup_stage", "mcgpu_segment_run", "mcgpu_segment_stage", "mcgpu_set_fast_schedule", "mcgpu_reload_env_knobs",
     "mcgpu_exchange_shared_bytes", "mcgpu_exchange_card_bytes", "mcgpu_exchange_create", "mcgpu_exchange_card", "mcgpu_exchange_connect",
     "mcgpu_exchange_connect_local", "mcgpu_exchange_probe", "mcgpu_exchange_owner", "mcgpu_exchange_begin", "mcgpu_exchange_submit", "mcgpu_exchange_collect",
     "mcgpu_exchange_stats", "mcgpu_exchange_destroy", "mcgpu_copy_to_host",
@@ -211,6 +211,7 @@ def load_library(path: Optional[os.PathLike] = None):
     lib.mcgpu_kat_fast64.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
     lib.mcgpu_kat_scatter.argtypes = [vp, ci, ci, ci, C.c_uint, C.c_uint, vp, vp, vp, vp, vp]
     lib.mcgpu_kat_history.argtypes = [vp, ci, ci, ci, ci, C.c_uint, vp, vp, vp, vp]
+    lib.mcgpu_kat_flight.argtypes = [vp, ci, ci, ci, ci, ci, C.c_uint, vp, vp, vp]
     lib.mcgpu_kat_tile_records.argtypes = [ci, vp, vp]
     if path is None:
         _lib = lib
@@ -1072,6 +1073,37 @@ class Context:
                     phase=out_u8[:, 0].astype(np.int64), index=out_u8[:, 1].astype(np.int64), mc=out_u8[:, 2].astype(np.int64),
                     scatter=out_u8[:, 3].astype(np.int64), state=out_u8[:, 4:6].copy(), word=out_u8[:, 6].view(np.int32).astype(np.int64),
                     value=out_u8[:, 7].astype(np.int64))
+
+    def kat_flight(self, mode, kind: str, projection: int, items, ids=None, max_steps: int = 1, seed: int = 0):
+        """The Woodcock flight step of a FAST history as the photon kernels run it (include/mcgpu_amd.h: mcgpu_kat_flight), one item per
+        thread, in the kernel variant this context's launches take.  kind "lookup": items = float32[n, 3] points; returns a dict density
+        (float32), mc, code, raw, out, exterior, variant.  kind "flight": items = float32[n, 7 or 8] {x, y, z, u, v, w, E}, ids = history
+        ids, max_steps in 1..32; returns a dict of the trace -- pos float32[n, max_steps, 3], phase, mc, aux_bits, state uint32[n,
+        max_steps, 2] (rows of steps not taken are zero) -- and of the end: final, steps, index, mfpw (float32), end_state, variant, mc_old
+        (the material whose cross section is cached, -1: none)."""
+        if kind not in ("lookup", "flight"):
+            raise ValueError(f"kind '{kind}': 'lookup' or 'flight'")
+        it = np.ascontiguousarray(items, dtype=np.float32)
+        it = it.reshape(-1, it.shape[-1]) if it.ndim > 1 else it.reshape(-1, 3 if kind == "lookup" else 7)
+        n = it.shape[0]
+        in8 = np.zeros((n, 8), dtype=np.float32)
+        in8[:, :min(it.shape[1], 8)] = it[:, :8]
+        u64 = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        if kind == "flight" and (u64 is None or u64.size != n):
+            raise ValueError("kind 'flight' needs one id per item")
+        rows = int(max_steps) + 1 if kind == "flight" else 1
+        out = np.zeros((max(n, 1), max(rows, 1), 8), dtype=np.uint32)
+        _check(self.lib.mcgpu_kat_flight(self.h, _MODES[mode], {"lookup": 0, "flight": 1}[kind], int(projection), n, int(max_steps), int(seed),
+                                         in8.ctypes.data, None if u64 is None else u64.ctypes.data, out.ctypes.data))
+        if kind == "lookup":
+            o = out[:, 0]
+            return dict(density=o[:, 0].copy().view(np.float32), mc=o[:, 1].astype(np.int64), code=o[:, 2].astype(np.int64), raw=o[:, 3].astype(np.int64),
+                        out=o[:, 4] != 0, exterior=o[:, 5] != 0, variant=o[:, 6].astype(np.int64))
+        t, e = out[:, :-1], out[:, -1]
+        return dict(pos=np.ascontiguousarray(t[:, :, :3]).view(np.float32), phase=t[:, :, 3].astype(np.int64), mc=t[:, :, 4].astype(np.int64),
+                    aux_bits=t[:, :, 5].copy(), state=t[:, :, 6:8].copy(), final=e[:, 0].astype(np.int64), steps=e[:, 1].astype(np.int64),
+                    index=e[:, 2].astype(np.int64), mfpw=e[:, 3].copy().view(np.float32), end_state=e[:, 4:6].copy(), variant=e[:, 6].astype(np.int64),
+                    mc_old=e[:, 7].copy().view(np.int32).astype(np.int64))
 
     def kat_f32(self, op: int, a, b=None, c=None):
         """Float operations of the COMPAT kernel (include/mcgpu_amd.h: mcgpu_kat_f32)."""

@@ -80,7 +80,13 @@ int mcgpu_config_f64(const mcgpu_ctx *ctx, const char *key, double *value);
  * "density_nominal","voxel_size","inv_voxel_size","size_bbox"; of the device model: "palette" (float2 {density, bits(compact material
  * index)} per entry of a u8 palette volume, in palette order), "track_cold" (contexts with a device; 19 floats the FAST kernels read at their
  * scheduling points: fan_ratio_lo, fan_ratio_hi, object box lo[3] / hi[3], elliptic cylinder centre[2] / inverse squared semi-axes[2] (0: none),
- * bounding box[3], then the homogeneous exterior: 1 if there is one, its density, its material number - 1, its compact material index).
+ * bounding box[3], then the homogeneous exterior: 1 if there is one, its density, its material number - 1, its compact material index);
+ * contexts with a device, what the FAST flight step reads, downloaded from the device: "mfp_tot" (float2 {a, b} of the total cross section
+ * per row compact material * num_energy_values + bin), "sigma_bracket_mid" (fp16 words [coarse bin * materials used + compact material]) and
+ * "sigma_bracket_w" (float per coarse bin of 2^sigma_bracket_shift bins; both empty without brackets), "compact_of" (int[25]: compact
+ * material of material number - 1, -1 unused), "brick_codes" (two 4-bit codes per byte, brick x fastest; u8 volumes), "brick_palette"
+ * (int[16]: palette index of brick code c), "tile_record_words" (uint32[4] {entries, code, mask low, mask high} per 4x4x4 tile, eight
+ * tiles of a 2x2x2 cube contiguous; empty without tile records).
  * The pointer stays valid until destroy. */
 int mcgpu_host_table(mcgpu_ctx *ctx, const char *name, const void **data, size_t *bytes);
 
@@ -573,6 +579,26 @@ int mcgpu_kat_scatter(mcgpu_ctx *ctx, int mode, int kind, int n, unsigned int se
 #define MCGPU_KAT_HOP 2
 int mcgpu_kat_history(mcgpu_ctx *ctx, int mode, int kind, int projection, int n, unsigned int seed, const float *in8,
                       const unsigned long long *in_u64, float *out8, uint32_t *out_u8);
+/* The middle of a history of MCGPU_MODE_FAST / MCGPU_MODE_FAST_F64, the Woodcock flight step, as the photon kernels run it
+ * (csrc/kat_flight.inc: flight_locate, flight_steps, real_record and classify_real of csrc/track_pool.inc themselves, one item per thread, in
+ * the kernel variant the context's launches take: out word `variant` = 0 u8, 1 u16, 2 raw float2, 3 u8 with second-level codes, 4 u8 with
+ * tile records).  Nothing is tallied.
+ *   MCGPU_KAT_LOOKUP  in8[8 i ..] = {x, y, z, ...} (in_u64 may be NULL, max_steps is ignored): the voxel look-up of a step that ends at that
+ *                     point, no deviate drawn.  out_u32[8 i ..] = {bits(density), compact material, brick code or 15 = mixed, voxel's palette
+ *                     index (mixed only), 1 if the point was clamped into the volume (outside), 1 if the brick is exterior, variant, 0}
+ *   MCGPU_KAT_FLIGHT  in8[8 i ..] = {x, y, z, u, v, w, E, -}, in_u64[i] = history id, max_steps in 1..32: flight steps from that state (energy
+ *                     bin and coarse majorant of E, no cached cross section, the stream of (id, seed, projection)) while the history is in
+ *                     flight, at most max_steps; a real interaction then draws its kind.  out_u32[(max_steps + 1) 8 i ..] = one row {bits(x),
+ *                     bits(y), bits(z), phase (0 in flight, 3 escaped, 7 real, 8 virtual in the exterior), compact material, bits(cached total
+ *                     cross section), generator state x, c} after every step taken (the others stay zero), then {final phase (0, 3, 8, or the
+ *                     kind: 1 Compton, 2 Rayleigh, 4 absorbed), steps taken, energy bin, bits(majorant mean free path), generator state x, c,
+ *                     variant, the compact material whose total cross section is cached (0xFFFFFFFF: none)}
+ * Refused before any HIP call: n above 2^20, max_steps outside 1..32 or n * max_steps above 2^22, a projection outside the context (-1);
+ * an input that is not a number, an energy outside the cross-section tables, a direction of length zero (-2). */
+#define MCGPU_KAT_LOOKUP 0
+#define MCGPU_KAT_FLIGHT 1
+int mcgpu_kat_flight(mcgpu_ctx *ctx, int mode, int kind, int projection, int n, int max_steps, unsigned int seed, const float *in8,
+                     const unsigned long long *in_u64, uint32_t *out_u32);
 /* The 16-byte record of a 4x4x4 tile of a u8-palette volume as the host and the device build it (csrc/device_model.hpp:
  * encode_tile_record; no reference counterpart -- the reference gathers the voxel itself, MC-GPU_kernel_v1.3.cu:262-266).  Host code
  * only, no context: indices[t * 64 + v] = palette index of voxel v = (iz & 3) 16 + (iy & 3) 4 + (ix & 3) of tile t, negative = padding

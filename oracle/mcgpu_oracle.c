@@ -559,6 +559,61 @@ void oracle_source(const oracle_tables *T, int num_p, int *seed2, float *pos3, f
   pos3[0] = p.x; pos3[1] = p.y; pos3[2] = p.z; dir3[0] = d.x; dir3[1] = d.y; dir3[2] = d.z; seed2[0] = s.x; seed2[1] = s.y;
 }
 
+/* n flights of track_batch's Woodcock loop (K.cu:249-279) and its interaction draw (:289-354), each from a given state
+ * state7[7 k ..] = {x, y, z, u, v, w, E} and its own RANECU seeds seed2[2 k ..] (advanced on return), at most max_steps steps each.
+ * pos3_out: where the loop ended; absvox_out: the absolute voxel there (-1: left the volume); kind_out: 1 Compton, 2 Rayleigh,
+ * 4 photoelectric absorption (the cumulative test on the deviate that ended the loop), 3 escaped, 0 still in flight after max_steps;
+ * steps_out: steps taken.  The statements are track_batch's; the energy must lie inside the tables. */
+void oracle_flight_many(const oracle_tables *T, long n, const float *state7, int *seed2, int max_steps, int math_mode, float *pos3_out,
+                        int *absvox_out, int *kind_out, int *steps_out)
+{
+  const float *vox = T->voxel_mat_dens, *Wt = T->mfp_woodcock, *A = T->mfp_a, *B = T->mfp_b;
+  for (long k = 0; k < n; k++) {
+    const float *s7 = state7 + 7 * k;
+    f3 pos = { s7[0], s7[1], s7[2] }, dir = { s7[3], s7[4], s7[5] };
+    const float energy = s7[6];
+    i2 seed = { seed2[2 * k], seed2[2 * k + 1] };
+    uint64_t cnt = 0;
+    float step, prob = 0.f, randno = 0.f, mfp_density = 0.f, ax = 0, ay = 0, az = 0, bx = 0, by = 0, bz = 0;
+    int absvox = 1, mat = 0, mat_old = -1, steps = 0, kind = 0;
+    const int index = (int)((energy - T->e0) * T->ide + 0.00001f);
+    const float mfpW = Wt[2 * index] + energy * Wt[2 * index + 1];
+    do {
+      if (steps >= max_steps) { randno = -1.0f; break; }  /* (not the reference's: the caller's bound) */
+      step = -(mfpW)*m_logf(ranecu(&seed, &cnt), math_mode);
+      steps++;
+      pos.x += step * dir.x;
+      pos.y += step * dir.y;
+      pos.z += step * dir.z;
+      absvox = locate_voxel(T, &pos);
+      if (absvox < 0) break;
+      mat = (int)(vox[2 * (size_t)absvox] - 1);
+      const float dens = vox[2 * (size_t)absvox + 1];
+      if (mat != mat_old) {
+        const float *a = A + 3 * ((size_t)index * MAXMAT + mat), *b = B + 3 * ((size_t)index * MAXMAT + mat);
+        ax = a[0]; ay = a[1]; az = a[2]; bx = b[0]; by = b[1]; bz = b[2];
+        mat_old = mat;
+      }
+      mfp_density = mfpW * dens;
+      prob = 1.0f - mfp_density * (ax + energy * bx);
+      randno = ranecu(&seed, &cnt);
+    } while (randno < prob);
+    if (absvox < 0) kind = 3;
+    else if (randno < 0.0f) kind = 0;
+    else {
+      prob += mfp_density * (ay + energy * by);
+      if (randno < prob) kind = 1;
+      else {
+        prob += mfp_density * (az + energy * bz);
+        kind = (randno < prob) ? 2 : 4;
+      }
+    }
+    pos3_out[3 * k] = pos.x; pos3_out[3 * k + 1] = pos.y; pos3_out[3 * k + 2] = pos.z;
+    absvox_out[k] = absvox; kind_out[k] = kind; steps_out[k] = steps;
+    seed2[2 * k] = seed.x; seed2[2 * k + 1] = seed.y;
+  }
+}
+
 /* ------------------------------------------------------------------------------------------
  * tally_image (K.cu:482-604), CPU branches (:553-565 rotated detector, :589-600 detector at +Y)
  * ------------------------------------------------------------------------------------------ */

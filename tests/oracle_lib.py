@@ -92,6 +92,9 @@ def oracle():
         lib.oracle_tally_image_many.restype = None
         lib.oracle_tally_image_many.argtypes = [C.POINTER(OracleTables), C.c_int, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p]
+        lib.oracle_flight_many.restype = None
+        lib.oracle_flight_many.argtypes = [C.POINTER(OracleTables), C.c_long, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]
         _oracle = lib
     return _oracle
 
@@ -167,6 +170,18 @@ class TableSet:
         oracle().oracle_tally_image_many(C.byref(self.ct), int(num_p), n, pos.ctypes.data, direction.ctypes.data, energy.ctypes.data,
                                          state.ctypes.data, word.ctypes.data, weight.ctypes.data)
         return word.astype(np.int64), weight
+
+    def flight_events(self, state7, seeds, max_steps, math_mode=MATH_LIBM):
+        """The Woodcock loop and the interaction draw from given states float32[n, 7] {x, y, z, u, v, w, E} and RANECU seeds int32[n, 2]:
+        (end point float32[n, 3], absolute voxel or -1, kind: 1 Compton / 2 Rayleigh / 4 absorbed / 3 escaped / 0 still in flight, steps,
+        the seeds afterwards)."""
+        state7 = np.ascontiguousarray(state7, dtype=np.float32).reshape(-1, 7)
+        n = state7.shape[0]
+        seeds = np.ascontiguousarray(seeds, dtype=np.int32).reshape(n, 2).copy()
+        pos, vox, kind, steps = np.zeros((n, 3), dtype=np.float32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        oracle().oracle_flight_many(C.byref(self.ct), n, state7.ctypes.data, seeds.ctypes.data, int(max_steps), int(math_mode), pos.ctypes.data,
+                                    vox.ctypes.data, kind.ctypes.data, steps.ctypes.data)
+        return pos, vox.astype(np.int64), kind.astype(np.int64), steps.astype(np.int64), seeds
 
     def track_with_variance(self, num_p, seed, batch0, nbatches, hpt, math_mode=MATH_LIBM, n_threads=1):
         """(image, sum of squared weights in the image's units squared as float64, counters)."""
