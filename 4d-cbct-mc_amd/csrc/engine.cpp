@@ -91,9 +91,9 @@ int mcgpu_config_i64(const mcgpu_ctx* ctx, const char* key, long long* value) {
   else if (k == "segment_loop") *value = make_args(*ctx, 0).segment_loop;  // FAST per-wave kernel variant: flight segment as an inner loop (tissue volumes)
   else if (k == "fast_scheduler") *value = ctx->dev.knobs.fast_sched;  // 0: per-wave pools, 1: workgroup-level pool (MCGPU_FAST_SCHED at upload)
   else if (k == "tiles_in_mixed_bricks") *value = ctx->dev.tiles_in_mixed_bricks;
-  else if (k == "warp_field_bytes") *value = (long long)ctx->dev.warp_field_bytes;  // field bytes the last geometry warp copied from the host
-  else if (k == "warp_field_buffer") *value = ctx->dev.dvf ? 1 : 0;                  // the device buffer of mcgpu_warp_geometry's field exists
-  else if (k == "correspondence_dims") *value = ctx->dev.corr_coef ? ctx->dev.corr_k : 0;  // K of the resident correspondence model, 0: none
+  else if (k == "warp_field_bytes") *value = (long long)ctx->dev.warp.field_bytes;  // field bytes the last geometry warp copied from the host
+  else if (k == "warp_field_buffer") *value = ctx->dev.warp.dvf ? 1 : 0;                  // the device buffer of mcgpu_warp_geometry's field exists
+  else if (k == "correspondence_dims") *value = ctx->dev.corr.resident() ? ctx->dev.corr.k : 0;  // K of the resident correspondence model, 0: none
   else if (k == "blocks_per_cu") *value = ctx->dev.resident_fast;
   else if (k == "lds_bytes_fast") *value = ctx->dev.lds.total;
   else if (k == "tally_stage_bins") *value = ctx->dev.stage.wanted(ctx->dev, false) ? (long long)ctx->dev.stage.bins : 0;  // 0: direct atomics
@@ -126,8 +126,8 @@ int mcgpu_config_f64(const mcgpu_ctx* ctx, const char* key, double* value) {
   else if (k == "inv_pixel_size_x") *value = (double)ctx->host.detector[0].inv_pixel_size_X;  // [1/cm], the float32 the norms are built from
   else if (k == "inv_pixel_size_z") *value = (double)ctx->host.detector[0].inv_pixel_size_Z;
   else if (k == "ide") *value = ctx->host.mat.ide;
-  else if (k == "warp_kernel_ms") *value = ctx->dev.warp_kernel_ms;  // the warp kernel of the last mcgpu_warp_geometry / mcgpu_warp_geometry_signal (HIP events)
-  else if (k == "warp_field_copy_ms") *value = ctx->dev.warp_field_copy_ms;  // host time of the field's copy in the last mcgpu_warp_geometry
+  else if (k == "warp_kernel_ms") *value = ctx->dev.warp.kernel_ms;  // the warp kernel of the last mcgpu_warp_geometry / mcgpu_warp_geometry_signal (HIP events)
+  else if (k == "warp_field_copy_ms") *value = ctx->dev.warp.field_copy_ms;  // host time of the field's copy in the last mcgpu_warp_geometry
   else return set_error(-2, std::string("unknown float key: ") + key);
   return 0;
   ABI_END

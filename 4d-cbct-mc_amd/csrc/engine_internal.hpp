@@ -112,6 +112,58 @@ struct TallyStage {
   unsigned long long staged_hits(const DeviceModel& D) const;
 };
 
+// On-device geometry changes (mcgpu_warp_geometry, mcgpu_warp_geometry_signal): the base geometry that every warp starts from, the
+// scratch of the rebuild and what the last warp measured.  The device memory and the events belong to the device model's owner `mem`.
+#pragma GCC visibility push(hidden)  // used inside the library only: nothing of the two joins its dynamic symbols
+struct WarpBase {
+  unsigned char* vol = nullptr;  // the base geometry's palette index volume; null: nothing has been warped yet
+  unsigned short *sub_first = nullptr, *brick_first = nullptr;  // scratch of the rebuild
+  unsigned char* code_of = nullptr;  // the code assignment of the base geometry
+  unsigned int* rebuild_out = nullptr;
+  float* dvf = nullptr;            // the field of mcgpu_warp_geometry (allocated on its first call; the model route has none)
+  hipEvent_t ev[2] = {nullptr, nullptr};  // around the warp kernel of the last geometry warp
+  float kernel_ms = 0.f;      // its time (config key "warp_kernel_ms")
+  float field_copy_ms = 0.f;  // host time of the field's copy to the device in the last geometry warp (0: no field was copied)
+  size_t field_bytes = 0;     // field bytes the last geometry warp copied from the host (0: evaluated from the resident model)
+
+  void make(DeviceModel& D);  // at the first warp: what is resident now is the base geometry of every later one
+  void copy_field(DeviceModel& D, const float* displacement, size_t nvox);  // the host's field into `dvf`, timed
+};
+
+// The correspondence model resident on the device (mcgpu_correspondence_set / _fit; geometry_device.hpp: FieldModelArgs): mean [3N]
+// float or double, coefficients double[3N][k], in the layout of `frame`
+struct ResidentCorrespondence {
+  void* mean = nullptr;
+  double* coef = nullptr;
+  int k = 0, mean_is_f64 = 0, frame = 0;
+  double mean_signal[4] = {0, 0, 0, 0};
+
+  bool resident() const { return coef != nullptr; }
+  void alloc(DeviceOwner& mem, size_t n, int K, bool f64_mean, int in_frame, const double* signal_mean) {
+    mean = mem.device_bytes(n * (f64_mean ? 8 : 4));
+    coef = (double*)mem.device_bytes(n * K * 8);
+    k = K;
+    mean_is_f64 = f64_mean ? 1 : 0;
+    frame = in_frame;
+    for (int j = 0; j < K; ++j) mean_signal[j] = signal_mean[j];
+  }
+  void drop(DeviceOwner& mem) {
+    if (mean) mem.free(mean);
+    if (coef) mem.free(coef);
+    mean = nullptr;
+    coef = nullptr;
+    k = 0;
+  }
+  // the model as the field source of one respiratory state: d = signal - mean_signal, in double on the host
+  FieldModelArgs args(const double* signal) const {
+    FieldModelArgs m;
+    m.mean = mean; m.coef = coef; m.k = k; m.mean_is_f64 = mean_is_f64;
+    for (int j = 0; j < k; ++j) m.d[j] = signal[j] - mean_signal[j];
+    return m;
+  }
+};
+#pragma GCC visibility pop
+
 struct DeviceModel {
   int device_id = -1;
   void* vol = nullptr;
@@ -130,23 +182,8 @@ struct DeviceModel {
     hipEvent_t ready = nullptr;               // recorded behind the formatter and the download of the row block
   } ascii[MCGPU_ASCII_SLOTS];
   unsigned long long ascii_capacity = 0;
-  // on-device geometry changes (mcgpu_warp_geometry): the base geometry's palette index volume, scratch, the palette on the
-  // host and the code assignment of the base geometry
-  unsigned char* vol_base = nullptr;
-  unsigned short *sub_first = nullptr, *brick_first = nullptr;
-  unsigned char* code_of_dev = nullptr;
-  unsigned int* rebuild_out = nullptr;
-  float* dvf = nullptr;            // the field of mcgpu_warp_geometry (allocated on its first call; the model route has none)
-  hipEvent_t warp_ev[2] = {nullptr, nullptr};  // around the warp kernel of the last geometry warp
-  float warp_kernel_ms = 0.f;      // its time (config key "warp_kernel_ms")
-  float warp_field_copy_ms = 0.f;  // host time of the field's copy to the device in the last geometry warp (0: no field was copied)
-  size_t warp_field_bytes = 0;     // field bytes the last geometry warp copied from the host (0: evaluated from the resident model)
-  // the correspondence model resident on the device (mcgpu_correspondence_set / _fit; geometry_device.hpp: FieldModelArgs):
-  // mean [3N] float or double, coefficients double[3N][corr_k], in the layout of frame `corr_frame`; null: none
-  void* corr_mean = nullptr;
-  double* corr_coef = nullptr;
-  int corr_k = 0, corr_mean_is_f64 = 0, corr_frame = 0;
-  double corr_mean_signal[4] = {0, 0, 0, 0};
+  WarpBase warp;               // on-device geometry changes, above
+  ResidentCorrespondence corr;  // the correspondence model resident on the device, above
   std::vector<float> palette_host;  // {density, bits(compact material)} pairs
   unsigned char code_of[256];
   int background = 0;

@@ -1,7 +1,7 @@
 #pragma once
 // hip_host.hpp -- what the host code around the device routines shares (engine*.cpp, scan.cpp, fdk.hip, wpc_fit.hip, forward_project.hip,
 // rooster4d.hip, resample.hip, speedup_net.hip, segment_net.hip): the HIP check, the exception boundary of the C ABI, owners of HIP handles and of one call's device memory, the
-// stage timer, the host stopwatch, the reader of struct_size-versioned options and the small rules of the circular cone-beam geometry.
+// stage timer, the host stopwatch, the reader of struct_size-versioned options, the writer of such reports and the small rules of the circular cone-beam geometry.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -134,6 +134,23 @@ void read_options(const char* fn, const char* struct_name, const T* caller, T& o
   memset(&out, 0, sizeof out);
   memcpy(&out, caller, std::min<size_t>(caller->struct_size, sizeof out));
   out.struct_size = (unsigned int)sizeof out;
+}
+
+// Reports of the C ABI that begin with `unsigned int struct_size` go back the other way: the caller gets the first
+// min(its struct_size, sizeof) bytes of the filled report and keeps the struct_size it passed.  A null report is none wanted; one
+// that does not reach past 8 bytes is refused before any work (`argument`: the parameter's name in the message).
+template <class T>
+void check_report(const char* fn, const char* argument, const char* struct_name, const T* caller) {
+  if (caller && caller->struct_size < 8)
+    throw Error(-1, std::string("!!ERROR!! ") + fn + ": set " + argument + "->struct_size = sizeof(" + struct_name + ")");
+}
+template <class T>
+void write_report(T* caller, T filled) {
+  if (!caller) return;
+  filled.struct_size = (unsigned int)sizeof filled;
+  const unsigned int want = caller->struct_size;  // as the caller was compiled
+  memcpy(caller, &filled, std::min<size_t>(want, sizeof filled));
+  caller->struct_size = want;
 }
 
 // ---- the circular cone-beam geometry of mcgpu_fdk_options, mcgpu_fp_options and mcgpu_rooster4d_options ----------------------

@@ -639,6 +639,12 @@ void load_voxel_file(const std::string& path, VoxelGrid& v, int n_threads) {
     for (int k = 0; k < kMaxMaterials; ++k) v.density_max[k] = std::max(v.density_max[k], dmax[t][k]);
 }
 
+float density_as_in_a_voxel_file(float density) {
+  char t[64];
+  snprintf(t, sizeof t, "%.6f", (double)density);
+  return strtof(t, nullptr);
+}
+
 // Binary sidecar written by write_voxel_binary (report.cpp): same VoxelGrid as the text parse, without the parse.
 void load_voxel_binary(const std::string& path, VoxelGrid& v) {
   FILE* fp = fopen(path.c_str(), "rb");

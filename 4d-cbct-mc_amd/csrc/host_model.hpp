@@ -8,8 +8,10 @@
 // the resulting tables are bit-identical to the reference's; the code itself is new.
 #pragma once
 #include <cstdint>
+#include <cstring>
 #include <stdexcept>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 namespace mcgpu {
@@ -174,11 +176,24 @@ void gaussian_filter_2d(float* img, int ny, int nx, double sigma_y, double sigma
 void normalize_stack(const std::string& total_path, const std::string& air_path, double sigma_y, double sigma_x, const std::string& out_path,
                      double sx, double sy);
 
+// A density as a voxel file would carry it: printed with six decimals and read back (cbctmc/mc/voxel_data.pyx:25,
+// MC-GPU_v1.3.cu:2117), so that arrays handed over in-process give the tables -- and therefore the tallies -- of the file-based flow
+float density_as_in_a_voxel_file(float density);
+struct VoxelFileDensities {  // the same for every voxel of a volume: a value is printed once, however often it occurs (inline: once per voxel)
+  std::unordered_map<uint32_t, float> seen;
+  float operator()(float density) {
+    uint32_t bits;
+    memcpy(&bits, &density, 4);
+    const auto it = seen.find(bits);
+    return it != seen.end() ? it->second : seen.emplace(bits, density_as_in_a_voxel_file(density)).first->second;
+  }
+};
+
 // Fast text/binary voxel writers (cbctmc/mc/voxel_data.pyx + mcgpu_geometry header fields)
 size_t write_voxel_file(const std::string& path, const int n[3], const float spacing_cm[3], const uint8_t* material,
                         const float* density, bool gzip);
 // Binary sidecar `<name>.voxbin` of a voxel file: the arrays the text parse would yield
-// (densities quantised through "%.6f" like the text), palette-compressed when the volume holds <= 65536 distinct
+// (densities as density_as_in_a_voxel_file gives them), palette-compressed when the volume holds <= 65536 distinct
 // (material, density) pairs.  load_model() prefers a sidecar that is not older than the text file.
 size_t write_voxel_binary(const std::string& path, const int n[3], const float spacing_cm[3], const uint8_t* material,
                           const float* density);

@@ -408,18 +408,6 @@ mcgpu_register_options checked_options(const char* fn, const mcgpu_register_opti
   return o;
 }
 
-void write_report(mcgpu_register_report* report, mcgpu_register_report r) {
-  if (!report) return;
-  r.struct_size = (unsigned int)sizeof r;
-  const unsigned int want = report->struct_size;  // as the caller was compiled
-  memcpy(report, &r, std::min<size_t>(want, sizeof r));
-  report->struct_size = want;
-}
-
-void require_report(const char* fn, const mcgpu_register_report* report) {
-  if (report && report->struct_size < 8) refuse(fn, "set report->struct_size = sizeof(mcgpu_register_report)");
-}
-
 // the mean of double(d)^2 over the level; d goes to diff_host where that is given
 double mean_squared_difference(const float* fixed, const float* moving, const float* u, const Shape& s, float* d_diff, float* diff_host,
                                double* d_partial) {
@@ -441,7 +429,7 @@ extern "C" int mcgpu_register(const mcgpu_register_options* caller_o, const floa
   ABI_BEGIN
   const mcgpu::Stopwatch call;
   const mcgpu_register_options o = checked_options(fn, caller_o, true);
-  require_report(fn, report);
+  mcgpu::check_report(fn, "report", "mcgpu_register_report", report);
   if (!fixed || !moving || !field_out) refuse(fn, "null pointer: fixed, moving and field_out are required");
   const Shape full{o.nx, o.ny, o.nz};
   const size_t n_full = full.voxels();
@@ -558,7 +546,7 @@ extern "C" int mcgpu_register(const mcgpu_register_options* caller_o, const floa
   }
   rep.peak_device_bytes = (unsigned long long)dev.peak;
   rep.ms_total = call.ms();
-  write_report(report, rep);
+  mcgpu::write_report(report, rep);
   return 0;
   ABI_END
 }
@@ -569,7 +557,7 @@ extern "C" int mcgpu_register_stage(const mcgpu_register_options* caller_o, int 
   ABI_BEGIN
   const mcgpu::Stopwatch call;
   const mcgpu_register_options o = checked_options(fn, caller_o, false);
-  require_report(fn, report);
+  mcgpu::check_report(fn, "report", "mcgpu_register_report", report);
   if (!out) refuse(fn, "null pointer: out");
   if (stage < MCGPU_REGISTER_STAGE_RESIZE_LINEAR || stage > MCGPU_REGISTER_STAGE_SMOOTH) refuse(fn, "stage " + std::to_string(stage) + " is outside 0..4");
   const Shape s{o.nx, o.ny, o.nz};
@@ -653,7 +641,7 @@ extern "C" int mcgpu_register_stage(const mcgpu_register_options* caller_o, int 
   }
   rep.peak_device_bytes = (unsigned long long)dev.peak;
   rep.ms_total = call.ms();
-  write_report(report, rep);
+  mcgpu::write_report(report, rep);
   return 0;
   ABI_END
 }

@@ -424,19 +424,7 @@ std::string voxel_sidecar_path(const std::string& voxel_file) {
 size_t write_voxel_binary(const std::string& path, const int n[3], const float spacing_cm[3], const uint8_t* material,
                           const float* density) {
   const size_t nvox = (size_t)n[0] * n[1] * n[2];
-  // densities as the text file carries them: "%.6f", read back with %f (voxel_data.pyx:25, MC-GPU_v1.3.cu:2117)
-  std::unordered_map<uint32_t, float> quantised;
-  auto q6 = [&](float d) {
-    uint32_t b;
-    memcpy(&b, &d, 4);
-    auto it = quantised.find(b);
-    if (it != quantised.end()) return it->second;
-    char t[64];
-    snprintf(t, sizeof t, "%.6f", (double)d);
-    const float v = strtof(t, nullptr);
-    quantised.emplace(b, v);
-    return v;
-  };
+  VoxelFileDensities q6;  // densities as the text file carries them
   std::unordered_map<uint64_t, uint32_t> index_of;
   std::vector<uint32_t> pal_mat;
   std::vector<float> pal_dens;

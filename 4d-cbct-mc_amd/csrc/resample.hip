@@ -197,18 +197,6 @@ hipError_t launch_resample(const ResampleArgs& a, int dtype, int interpolator, d
   return hipErrorInvalidValue;
 }
 
-void fill_resample_report(mcgpu_resample_report* report, double ms_kernel, double ms_upload, double ms_download, size_t kernel_bytes) {
-  if (!report) return;
-  mcgpu_resample_report r;
-  memset(&r, 0, sizeof r);
-  r.struct_size = (unsigned int)sizeof r;
-  r.ms_kernel = ms_kernel; r.ms_upload = ms_upload; r.ms_download = ms_download;
-  r.kernel_bytes = kernel_bytes;
-  const unsigned int want = report->struct_size;  // as the caller was compiled
-  memcpy(report, &r, std::min<size_t>(want, sizeof r));
-  report->struct_size = want;
-}
-
 }  // namespace mcgpu
 
 using namespace mcgpu;
@@ -233,28 +221,30 @@ int mcgpu_resample_plan(const mcgpu_resample_options* options, int n_out[3], int
 int mcgpu_resample_volume(mcgpu_ctx* ctx, const mcgpu_resample_options* options, const void* in, void* out, mcgpu_resample_report* report) {
   ABI_BEGIN
   require(ctx && ctx->has_device && options && in && out, -1, "!!ERROR!! mcgpu_resample_volume: bad argument (the context needs a device)");
-  require(!report || report->struct_size >= 8, -1, "!!ERROR!! mcgpu_resample_volume: set report->struct_size = sizeof(mcgpu_resample_report)");
+  check_report("mcgpu_resample_volume", "report", "mcgpu_resample_report", report);
   const mcgpu_resample_options o = checked_options("mcgpu_resample_volume", options);
   const ResamplePlan plan = make_resample_plan("mcgpu_resample_volume", o.n_in, o.spacing_in, o.spacing_out);
   const size_t size = resample_element_size(o.dtype), bytes_in = plan.voxels_in() * size, bytes_out = plan.voxels_out() * size;
   HIP_TRY(hipSetDevice(ctx->dev.device_id));
   CallDevice dev;
   dev.events();
-  double ms_kernel = 0.0;
-  auto t0 = std::chrono::steady_clock::now();
+  mcgpu_resample_report rep;
+  memset(&rep, 0, sizeof rep);
+  rep.kernel_bytes = bytes_in + bytes_out;
+  const Stopwatch upload;
   const ResampleArgs args = upload_resample_plan(dev, plan);
   const unsigned char* d_in = dev.upload((const unsigned char*)in, bytes_in);
   unsigned char* d_out = dev.alloc<unsigned char>(bytes_out);
-  const double ms_upload = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  rep.ms_upload = upload.ms();
   {
-    Stage stage(dev, ms_kernel);
+    Stage stage(dev, rep.ms_kernel);
     HIP_TRY(launch_resample(args, o.dtype, o.interpolator, o.default_value, d_in, d_out, nullptr));
     stage.done();
   }
-  t0 = std::chrono::steady_clock::now();
+  const Stopwatch download;
   HIP_TRY(hipMemcpy(out, d_out, bytes_out, hipMemcpyDeviceToHost));
-  const double ms_download = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  fill_resample_report(report, ms_kernel, ms_upload, ms_download, bytes_in + bytes_out);
+  rep.ms_download = download.ms();
+  write_report(report, rep);
   return 0;
   ABI_END
 }

@@ -76,6 +76,5 @@ struct ResampleArgs {  // the plan on the device
 ResampleArgs upload_resample_plan(CallDevice& dev, const ResamplePlan& plan);
 // `in` [n_in] -> `out` [n_out], device memory of element type `dtype` (MCGPU_IMAGE_*), on `stream`
 hipError_t launch_resample(const ResampleArgs& a, int dtype, int interpolator, double default_value, const void* in, void* out, hipStream_t stream);
-void fill_resample_report(mcgpu_resample_report* report, double ms_kernel, double ms_upload, double ms_download, size_t kernel_bytes);
 
 }  // namespace mcgpu

@@ -659,9 +659,9 @@ class Context:
         m = np.ascontiguousarray(material_zyx, dtype=np.uint8)
         d = np.ascontiguousarray(density_zyx, dtype=np.float32)
         assert m.size == d.size == int(n[0]) * int(n[1]) * int(n[2])
-        self._correspondence_model = None  # the device model is built anew: a resident correspondence model goes with the old one
         _check(self.lib.mcgpu_set_geometry_arrays(self.h, (C.c_int * 3)(*map(int, n)), (C.c_float * 3)(*map(float, spacing_cm)),
                                                   m.ctypes.data, d.ctypes.data))
+        self._correspondence_model = None  # the device model is built anew: a resident correspondence model goes with the old one
 
     def set_geometry(self, geometry):
         """An `MCGeometry` of the Python mirror, in the orientation its voxel file would have (geo.py:589-599)."""

@@ -257,3 +257,50 @@ def test_a_state_change_copies_no_field_and_the_model_goes_with_its_context(engi
         with pytest.raises(engine.EngineError) as e:
             ctx.warp_geometry_by_signal(s)
         assert e.value.code == -5
+
+
+def test_a_refused_geometry_change_keeps_the_warp_base_and_the_model(engine, tmp_path):
+    """A geometry change that is refused -- an image without body segmentation (unmapped voxels), arrays with a material the input
+    names no data file for (the file's odd box; the context starts from the same box with muscle in place of the bone) -- leaves the resident model, the warp base and the Python context's record of the model where they were:
+    the same warp and the same 100 000 FAST histories give the same tally word for word.  A change that succeeds takes the model
+    with the superseded device model, on the device and in Python."""
+    g, with_bone = _odd_box(), _odd_box()
+    g.materials[g.materials == cases.materials.material_number("bone_050")] = cases.materials.material_number("muscle_tissue")
+    shape = g.materials.shape
+    files = cases.material_files()[:cases.materials.material_number("blood") - 1]  # the input names no file for blood and beyond: none for bone_050
+    inp = cases.simulation.MCSimulation(g, files, cases.spectrum_file(), **KW).prepare_simulation(tmp_path / "odd_box")
+    model = _random_model(shape, 1, np.float32, seed=4)
+    model.coefficients *= 0.2
+    s = np.array([0.5])
+    rng = np.random.default_rng(6)
+    image = rng.integers(-1100, 900, size=shape).astype(np.int16)
+    no_body = {"bone": (rng.random(shape) < 0.25).astype(np.uint8)}
+    with engine.create(inp, device=0) as ctx:
+        ctx.set_correspondence_model(model)
+
+        def warp_and_run():
+            ctx.warp_geometry_by_signal(s)
+            return ctx.run_projection(0, 100_000, mode="fast", seed=3)[0]
+
+        tally = warp_and_run()
+        assert tally.sum() > 0
+        field_buffer = ctx.geti("warp_field_buffer")
+
+        def refuse(change, *args):
+            with pytest.raises(engine.EngineError) as e:
+                change(*args)
+            assert e.value.code == -2
+            assert ctx.geti("correspondence_dims") == 1
+            assert ctx.geti("warp_field_buffer") == field_buffer
+            assert ctx._correspondence_model is model
+            assert np.array_equal(warp_and_run(), tally)
+            return e.value.message
+
+        assert "voxels are unmapped" in refuse(ctx.set_geometry_image, image, no_body)
+        assert "no data file" in refuse(ctx.set_geometry, with_bone)
+        mats, dens, spacing_cm = g.mcgpu_arrays()
+        ctx.set_geometry_arrays(mats.shape, spacing_cm, np.transpose(mats, (2, 1, 0)), np.transpose(dens, (2, 1, 0)))
+        assert ctx.geti("correspondence_dims") == 0 and ctx._correspondence_model is None
+        with pytest.raises(engine.EngineError) as e:
+            ctx.warp_geometry_by_signal(s)
+        assert e.value.code == -5
