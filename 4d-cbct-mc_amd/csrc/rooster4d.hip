@@ -29,9 +29,35 @@
 // float4 loads and the dot-product stages, positivity, tv_space_div / tv_space_grad (per frame: the spatial dual is 3 x one
 // frame) and tv_time_kernel (a voxel's whole series and its dual in registers: one read and one write of the 4-D volume).
 // Residency: the projection stack and the 4-D vectors x, b, r, d, A d stay on the device for the whole run.
+//
+// Motion-aware ROOSTER (mcgpu_rooster4d_reconstruct_motion; Mory, Janssens, Rit, PMB 2016; what RTK's
+// `rtkfourdrooster --dvf --idvf` is for).  The rule.  Two linear motion models live on the reconstruction grid, both in the layout
+// of row f15 (fdk.hip): mean [3][nz][ny][nx] and coefficients [K][3][nz][ny][nx], float32, mm along IEC X, Y, Z, 1 <= K <= 4.
+//   to_reference   (forward model): the material of reference-phase voxel P is at P + F(P; s) at state s.
+//   from_reference (pull-back model): frame_s(Q) = ref(Q + G(Q; s)).
+// Frame f has a state s_f that enters as delta_to[f][k] = s_f[k] - mean_signal_to[k] and delta_from[f][k] likewise, given in
+// double and rounded once to float32.  The sampling operator Sigma(model, delta) of a volume v at the voxel P = (ix, iy, iz):
+//   displacement  d = mean(P) + sum_k coefficients[k](P) delta[k] per component, as an fmaf chain, k ascending;
+//   position      per axis fx = fmaf(d_x, 1 / sx, (float)ix), clamped: fminf(fmaxf(fx, 0), nx - 1) -- the border is replicated and
+//                 every index is in bounds for any float input, NaN and Inf included;
+//   cell          i0 = (int)floorf(fx), t = fx - i0, i1 = min(i0 + 1, nx - 1);
+//   value         trilinear with nested lerp(a, b, t) = fmaf(t, b - a, a) along x, then y, then z: a zero displacement returns
+//                 the voxel bit for bit.
+// (W x)_f = Sigma(to_reference, delta_to[f]) x_f carries every frame to the reference phase, (U c)_f = Sigma(from_reference,
+// delta_from[f]) c_f carries it back.  Steps 1 - 3 are unchanged; step 4 becomes, with TVtime the temporal TV above,
+//     y = W x;  c = TVtime(y) - y;  x = x + U c
+// so only the regulariser's correction is resampled, never x itself: with gamma_time = 0 or tviter = 0 x is left untouched, and a
+// displacement that is no whole number of voxels does not blur x.  A deliberate departure from RTK, which replaces x by
+// U TVtime(W x) and so resamples the volume twice per main iteration.  Nothing here derives one model from the other, and a
+// swapped pair is not detected.  Kernels: warp4_kernel (one thread per voxel, x fastest; it loads its 3 (K + 1) model values once
+// and loops over the frames, whose deltas are wave-uniform kernel arguments; 8 gathers per frame; it stores W x twice, as y and as
+// the input of TVtime, or adds U c to x) and subtract_kernel.  y and c are the CG vectors A d and r, free at step 4: no new 4-D
+// allocation, peak memory grows by the two resident models, 2 x 3 (K + 1) frames.  Restated in float64 by tests/rooster_motion_ref.py.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <limits>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -295,6 +321,85 @@ __global__ __launch_bounds__(256) void tv_time_kernel(float* __restrict__ x4, si
   for (int t = 0; t < NM; ++t) if (t < N) x4[(size_t)t * frame + i] = u[t];
 }
 
+// ---- motion-aware temporal step (the rule stands in this file's header) -------------------------------------
+constexpr int kWarpMaxK = 4;
+
+struct WarpArgs {
+  int nx, ny, nz, N;
+  float inv_sx, inv_sy, inv_sz;
+  float delta[kMaxFrames][kWarpMaxK];  // [f][k], k < K: wave-uniform, read through scalar loads
+};
+
+// index position along one axis -> cell (i0, i1) and weight t.  The float clamp alone keeps every index in bounds for any input
+// (fmaxf and fminf return the operand that is not NaN); the integer clamp states the same bound again where the addresses are formed.
+__device__ inline void warp_cell(float d, float inv_s, int i, int n, int& i0, int& i1, float& t) {
+  const float f = fminf(fmaxf(fmaf(d, inv_s, (float)i), 0.f), (float)(n - 1));
+  const float fl = floorf(f);
+  i0 = min(max((int)fl, 0), n - 1);
+  t = f - fl;
+  i1 = min(i0 + 1, n - 1);
+}
+
+__device__ inline float lerp(float a, float b, float t) { return fmaf(t, b - a, a); }
+
+// dst_f(P) = [dst_f(P) +] Sigma(model, delta[f]) src_f (P) for every frame f; dst2 (optional, store mode) gets the same values.
+// One thread per voxel, x fastest: the model loads and the stores coalesce, neighbouring lanes gather neighbouring voxels.  A voxel
+// has one owner: no atomics.  src must not overlap dst or dst2.
+template <int K, bool ACCUMULATE>
+__global__ __launch_bounds__(256) void warp4_kernel(float* __restrict__ dst, float* __restrict__ dst2, const float* __restrict__ src, size_t frame,
+                                                    const float* __restrict__ mean, const float* __restrict__ coef, const WarpArgs A) {
+  const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= frame) return;
+  const int ix = (int)(i % A.nx), iy = (int)((i / A.nx) % A.ny), iz = (int)(i / ((size_t)A.nx * A.ny));
+  const float mx = mean[i], my = mean[frame + i], mz = mean[2 * frame + i];
+  float cx[K], cy[K], cz[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    cx[k] = coef[((size_t)3 * k + 0) * frame + i];
+    cy[k] = coef[((size_t)3 * k + 1) * frame + i];
+    cz[k] = coef[((size_t)3 * k + 2) * frame + i];
+  }
+  const size_t nx = (size_t)A.nx, nxy = nx * A.ny;
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+  for (int f = 0; f < A.N; ++f) {
+    float dx = mx, dy = my, dz = mz;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const float d = A.delta[f][k];
+      dx = fmaf(cx[k], d, dx);
+      dy = fmaf(cy[k], d, dy);
+      dz = fmaf(cz[k], d, dz);
+    }
+    int x0, x1, y0, y1, z0, z1;
+    float tx, ty, tz;
+    warp_cell(dx, A.inv_sx, ix, A.nx, x0, x1, tx);
+    warp_cell(dy, A.inv_sy, iy, A.ny, y0, y1, ty);
+    warp_cell(dz, A.inv_sz, iz, A.nz, z0, z1, tz);
+    const float* s = src + (size_t)f * frame;
+    const size_t r00 = z0 * nxy + y0 * nx, r01 = z0 * nxy + y1 * nx, r10 = z1 * nxy + y0 * nx, r11 = z1 * nxy + y1 * nx;
+    const float a00 = lerp(s[r00 + x0], s[r00 + x1], tx), a01 = lerp(s[r01 + x0], s[r01 + x1], tx);
+    const float a10 = lerp(s[r10 + x0], s[r10 + x1], tx), a11 = lerp(s[r11 + x0], s[r11 + x1], tx);
+    const float v = lerp(lerp(a00, a01, ty), lerp(a10, a11, ty), tz);
+    const size_t o = (size_t)f * frame + i;
+    if (ACCUMULATE) {
+      dst[o] += v;
+    } else {
+      dst[o] = v;
+      if (dst2) dst2[o] = v;
+    }
+  }
+}
+
+// a -= b
+__global__ __launch_bounds__(256) void subtract_kernel(float4* __restrict__ a, const float4* __restrict__ b, size_t n4) {
+  for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n4; i += (size_t)kRedBlocks * kThreads) {
+    float4 v = a[i];
+    const float4 w = b[i];
+    v.x -= w.x; v.y -= w.y; v.z -= w.z; v.w -= w.w;
+    a[i] = v;
+  }
+}
+
 // ---- host --------------------------------------------------------------------------------------------------------------------
 // RTK's signal-to-weights rule for a periodic N-frame sequence: phase phi in [0, 1] lies between frames l = floor(phi N) mod N and
 // h = l + 1 mod N with linear weights; phi = 1 is frame 0 again.  This is the rule as RTK documents it (rtkfourdrooster --signal,
@@ -337,6 +442,15 @@ struct Problem {
   CallDevice dev;
   double* d_part = nullptr;
   double* d_sum = nullptr;
+  // the two motion models of mcgpu_rooster4d_reconstruct_motion, resident for the call; null: plain ROOSTER, which launches
+  // exactly what it launched without this member
+  struct Motion {
+    int K = 0;
+    const float *to_mean = nullptr, *to_coef = nullptr, *from_mean = nullptr, *from_coef = nullptr;  // device
+    WarpArgs to, from;  // grid, 1 / spacing and the frames' deltas (rounded once to float32) of W and of U
+  };
+  std::unique_ptr<Motion> motion;
+  double ms_warp = 0.0, ms_upload_model = 0.0;
 
   explicit Problem(const mcgpu_rooster4d_options& opt) : o(opt), N(opt.n_frames) {
     memset(&rep, 0, sizeof rep);
@@ -450,6 +564,63 @@ struct Problem {
     st.done();
   }
 
+  // both models onto the device once, as float32; the deltas rounded once to float32
+  void upload_model(const mcgpu_rooster4d_motion& M) {
+    const mcgpu::Stopwatch sw;
+    motion = std::make_unique<Motion>();
+    Motion& m = *motion;
+    m.K = M.n_signal_dims;
+    m.to_mean = dev.upload(M.to_reference_mean, 3 * frame);
+    m.to_coef = dev.upload(M.to_reference_coefficients, (size_t)m.K * 3 * frame);
+    m.from_mean = dev.upload(M.from_reference_mean, 3 * frame);
+    m.from_coef = dev.upload(M.from_reference_coefficients, (size_t)m.K * 3 * frame);
+    memset(&m.to, 0, sizeof m.to);
+    m.to.nx = o.nx; m.to.ny = o.ny; m.to.nz = o.nz; m.to.N = N;
+    m.to.inv_sx = (float)(1.0 / o.sx); m.to.inv_sy = (float)(1.0 / o.sy); m.to.inv_sz = (float)(1.0 / o.sz);
+    m.from = m.to;
+    for (int f = 0; f < N; ++f)
+      for (int k = 0; k < m.K; ++k) {
+        m.to.delta[f][k] = (float)M.delta_to[(size_t)f * m.K + k];
+        m.from.delta[f][k] = (float)M.delta_from[(size_t)f * m.K + k];
+      }
+    ms_upload_model += sw.ms();
+  }
+
+  // dst = W src (to_reference) or U src (from reference); accumulate: dst += ...; dst2: a second copy of a stored result, or null
+  void warp(bool to_reference, bool accumulate, float* dst, float* dst2, const float* src) {
+    const Motion& m = *motion;
+    const float* mean = to_reference ? m.to_mean : m.from_mean;
+    const float* coef = to_reference ? m.to_coef : m.from_coef;
+    const WarpArgs& A = to_reference ? m.to : m.from;
+    const dim3 g((unsigned)((frame + kThreads - 1) / kThreads));
+    auto launch = [&](auto store, auto add) {
+      if (accumulate) hipLaunchKernelGGL(add, g, dim3(kThreads), 0, nullptr, dst, dst2, src, frame, mean, coef, A);
+      else hipLaunchKernelGGL(store, g, dim3(kThreads), 0, nullptr, dst, dst2, src, frame, mean, coef, A);
+    };
+    switch (m.K) {
+      case 1: launch(warp4_kernel<1, false>, warp4_kernel<1, true>); break;
+      case 2: launch(warp4_kernel<2, false>, warp4_kernel<2, true>); break;
+      case 3: launch(warp4_kernel<3, false>, warp4_kernel<3, true>); break;
+      default: launch(warp4_kernel<4, false>, warp4_kernel<4, true>); break;
+    }
+  }
+
+  // step 4 along the model's trajectories: y = W x; c = TVtime(y) - y; x += U c.  y and c are two 4-D vectors the caller lends
+  // (the CG vectors A d and r, both rewritten at the next restart).  gamma = 0 or no iterations: c = 0, x is left untouched.
+  void tv_time_motion(float* x4, float* y, float* c, int iters, float gamma) {
+    if (iters <= 0 || !(gamma > 0.f)) return;
+    {
+      Stage st(dev, ms_warp);
+      warp(true, false, y, c, x4);
+      st.done();
+    }
+    tv_time(c, iters, gamma);
+    Stage st(dev, ms_warp);
+    hipLaunchKernelGGL(subtract_kernel, dim3(kRedBlocks), dim3(kThreads), 0, nullptr, (float4*)c, (const float4*)y, n4);
+    warp(false, true, x4, nullptr, c);
+    st.done();
+  }
+
   float* upload_projections(const float* projections, bool wpc) {
     const mcgpu::Stopwatch upload;
     float* d = alloc_proj();
@@ -529,7 +700,8 @@ struct Problem {
       }
       if (o.tviter > 0) {
         tv_space(x, work, o.tviter, (float)o.gamma_space);
-        tv_time(x, o.tviter, (float)o.gamma_time);
+        if (motion) tv_time_motion(x, Ad, r, o.tviter, (float)o.gamma_time);
+        else tv_time(x, o.tviter, (float)o.gamma_time);
       }
     }
     HIP_TRY(hipMemcpy(volume4d, x, n4d * 4, hipMemcpyDeviceToHost));
@@ -559,7 +731,39 @@ struct Problem {
     }
     HIP_TRY(hipMemcpy(out, x, n4d * 4, hipMemcpyDeviceToHost));
   }
+
+  void motion_stage(int which, const float* in, float* out) {
+    float* x = upload_4d(in);
+    float* y = alloc4d();
+    if (which == MCGPU_ROOSTER4D_MOTION_STAGE_TV_TIME_MOTION) {
+      float* c = alloc4d();
+      tv_time_motion(x, y, c, o.tviter, (float)o.gamma_time);
+      HIP_TRY(hipMemcpy(out, x, n4d * 4, hipMemcpyDeviceToHost));
+      return;
+    }
+    Stage st(dev, ms_warp);
+    warp(which == MCGPU_ROOSTER4D_MOTION_STAGE_WARP, false, y, nullptr, x);
+    st.done();
+    HIP_TRY(hipMemcpy(out, y, n4d * 4, hipMemcpyDeviceToHost));
+  }
+
+  mcgpu_rooster4d_motion_report motion_report(double ms_total) const {
+    return {rep.ms_forward, rep.ms_back, rep.ms_cg_vectors, rep.ms_tv_space, rep.ms_tv_time, rep.ms_upload, ms_total,
+            (unsigned long long)dev.peak, ms_warp, ms_upload_model};
+  }
 };
+
+// the checks of a mcgpu_rooster4d_motion that need no device: refused with -1 before any HIP call
+void read_motion(const char* fn, const mcgpu_rooster4d_motion* caller, int n_frames, mcgpu_rooster4d_motion& m) {
+  mcgpu::read_options(fn, "mcgpu_rooster4d_motion", caller, m);
+  if (m.n_signal_dims < 1 || m.n_signal_dims > kWarpMaxK) refuse(fn, "n_signal_dims must lie in 1..4");
+  if (!m.to_reference_mean || !m.to_reference_coefficients || !m.from_reference_mean || !m.from_reference_coefficients)
+    refuse(fn, "a motion model array is NULL");
+  if (!m.delta_to || !m.delta_from) refuse(fn, "delta_to or delta_from is NULL");
+  for (size_t j = 0; j < (size_t)n_frames * m.n_signal_dims; ++j)  // NaN, infinite, or infinite once it is float32
+    if (!(std::fabs(m.delta_to[j]) <= (double)std::numeric_limits<float>::max()) || !(std::fabs(m.delta_from[j]) <= (double)std::numeric_limits<float>::max()))
+      refuse(fn, "delta is not finite");
+}
 
 }  // namespace
 
@@ -592,6 +796,45 @@ extern "C" int mcgpu_rooster4d_stage(const mcgpu_rooster4d_options* caller_o, in
   P.rep.peak_device_bytes = P.dev.peak;
   P.rep.ms_total = call.ms();
   if (report) *report = P.rep;
+  return 0;
+  ABI_END
+}
+
+extern "C" int mcgpu_rooster4d_reconstruct_motion(const mcgpu_rooster4d_options* caller_o, const mcgpu_rooster4d_motion* caller_m, const float* projections,
+                                                  float* volume4d, mcgpu_rooster4d_motion_report* report) {
+  ABI_BEGIN
+  const char* fn = "mcgpu_rooster4d_reconstruct_motion";
+  mcgpu_rooster4d_options o;
+  read_options(fn, caller_o, o);
+  mcgpu_rooster4d_motion m;
+  read_motion(fn, caller_m, o.n_frames, m);
+  if (!projections || !volume4d) refuse(fn, "projections or volume is NULL");
+  const mcgpu::Stopwatch call;
+  Problem P(o);
+  P.init();
+  P.upload_model(m);
+  P.run(projections, volume4d);
+  if (report) *report = P.motion_report(call.ms());
+  return 0;
+  ABI_END
+}
+
+extern "C" int mcgpu_rooster4d_motion_stage(const mcgpu_rooster4d_options* caller_o, const mcgpu_rooster4d_motion* caller_m, int stage, const float* in, float* out,
+                                            mcgpu_rooster4d_motion_report* report) {
+  ABI_BEGIN
+  const char* fn = "mcgpu_rooster4d_motion_stage";
+  mcgpu_rooster4d_options o;
+  read_options(fn, caller_o, o);
+  mcgpu_rooster4d_motion m;
+  read_motion(fn, caller_m, o.n_frames, m);
+  if (stage < MCGPU_ROOSTER4D_MOTION_STAGE_WARP || stage > MCGPU_ROOSTER4D_MOTION_STAGE_TV_TIME_MOTION) refuse(fn, "unknown stage " + std::to_string(stage));
+  if (!in || !out) refuse(fn, "in or out is NULL");
+  const mcgpu::Stopwatch call;
+  Problem P(o);
+  P.init();
+  P.upload_model(m);
+  P.motion_stage(stage, in, out);
+  if (report) *report = P.motion_report(call.ms());
   return 0;
   ABI_END
 }

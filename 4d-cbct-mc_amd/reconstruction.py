@@ -509,6 +509,22 @@ def rooster4d_stage(stage: str, data: np.ndarray, geometry: CircularGeometry, de
     return out, _rooster_report(rep)
 
 
+def _unit_phase(amplitude_signal, phase_signal) -> np.ndarray:
+    """The phase of reconstruct_4d and reconstruct_4d_mc: exactly one of the two signals is given (ValueError otherwise); an
+    amplitude goes through phase.calculate_phase; the phase is min-max scaled to [0, 1]."""
+    from . import phase as phase_mod
+    if (amplitude_signal is None) == (phase_signal is None):
+        raise ValueError("give exactly one of amplitude_signal and phase_signal")
+    if phase_signal is None:
+        phase_signal = np.hstack(phase_mod.calculate_phase(np.asarray(amplitude_signal)))
+    ph = np.array(phase_signal, dtype=np.float64)
+    ph -= ph.min()
+    span = ph.max()
+    if not span > 0:
+        raise ValueError("the phase signal is constant: it cannot be scaled to [0, 1]")
+    return ph / span
+
+
 def reconstruct_4d(projections_filepath, geometry_filepath, output_folder=None, output_filename: Optional[str] = None,
                    dimension: Tuple[int, int, int] = (464, 250, 464), spacing: Tuple[float, float, float] = (1.0, 1.0, 1.0),
                    amplitude_signal: Optional[np.ndarray] = None, phase_signal: Optional[np.ndarray] = None,
@@ -520,17 +536,7 @@ def reconstruct_4d(projections_filepath, geometry_filepath, output_folder=None, 
     gamma_space 0.00007 (keyword arguments override them, as do `frames` and `positivity`).  Writes `recon_rooster4d.mha`, a 4-D
     MetaImage [frames][nz][ny][nx] with spacing (sx, sy, sz, 1) and offset (ox, oy, oz, 0) in the frame of reconstruct_3d's
     output, and a .yaml of the parameters next to it (fp / bp record what ran: Joseph / VoxelBased)."""
-    from . import phase as phase_mod
-    if (amplitude_signal is None) == (phase_signal is None):
-        raise ValueError("give exactly one of amplitude_signal and phase_signal")
-    if phase_signal is None:
-        phase_signal = np.hstack(phase_mod.calculate_phase(np.asarray(amplitude_signal)))
-    ph = np.array(phase_signal, dtype=np.float64)
-    ph -= ph.min()
-    span = ph.max()
-    if not span > 0:
-        raise ValueError("the phase signal is constant: it cannot be scaled to [0, 1]")
-    ph /= span
+    ph = _unit_phase(amplitude_signal, phase_signal)
     projections_filepath, geometry_filepath = Path(projections_filepath), Path(geometry_filepath)
     output_folder = Path(output_folder) if output_folder else projections_filepath.parent / "reconstructions"
     output_filename = output_filename or "recon_rooster4d.mha"
@@ -548,6 +554,182 @@ def reconstruct_4d(projections_filepath, geometry_filepath, output_folder=None, 
     record = dict(path=str(projections_filepath.parent), regexp=projections_filepath.name, geometry=str(geometry_filepath), fp="Joseph",
                   bp="VoxelBased", hardware="hip", dimension=list(dimension), spacing=list(spacing),
                   wpc=list(water_pre_correction) if water_pre_correction is not None else None, output_filepath=str(out), **params, **kwargs)
+    with open(out.with_suffix(".yaml"), "w") as f:
+        yaml.dump(record, f)
+    return out, report
+
+
+# ------------------------------------------------------------------------------------------------ motion-aware 4-D ROOSTER
+class _RoosterMotion(C.Structure):
+    """mcgpu_rooster4d_motion (include/mcgpu_amd.h)."""
+    _fields_ = [("struct_size", C.c_uint), ("n_signal_dims", C.c_int), ("to_reference_mean", C.POINTER(C.c_float)),
+                ("to_reference_coefficients", C.POINTER(C.c_float)), ("from_reference_mean", C.POINTER(C.c_float)),
+                ("from_reference_coefficients", C.POINTER(C.c_float)), ("delta_to", C.POINTER(C.c_double)), ("delta_from", C.POINTER(C.c_double))]
+
+
+class _RoosterMotionReport(C.Structure):
+    _fields_ = _RoosterReport._fields_ + [("ms_warp", C.c_double), ("ms_upload_model", C.c_double)]
+
+
+ROOSTER4D_MOTION_STAGES = {"warp": 0, "unwarp": 1, "tv_time_motion": 2}
+
+
+def frame_signals(phase, signals, frames: int) -> np.ndarray:
+    """The breathing state of every frame of a 4-D reconstruction: phase [n] in [0, 1], signals [n, K] (or [n]) -> float64 [frames, K].
+
+    Projection k lies between frames l = floor(phase N) mod N and h = (l + 1) mod N with the weights w_h = phase N - floor(phase N),
+    w_l = 1 - w_h (the S rule of rooster4d, csrc/rooster4d.hip: interpolation_weights).  The state of frame f is the mean of the
+    signals of the projections that touch it, weighted by those weights.  A frame that no projection touches has no state:
+    ValueError."""
+    N = int(frames)
+    ph = np.asarray(phase, dtype=np.float64).ravel()
+    s = np.asarray(signals, dtype=np.float64)
+    if s.ndim == 1:
+        s = s[:, None]
+    if s.ndim != 2 or s.shape[0] != ph.size:
+        raise ValueError(f"{ph.size} phase values but signals of shape {np.shape(signals)}")
+    t = ph * N
+    ft = np.floor(t)
+    l = np.mod(ft.astype(np.int64), N)
+    h = (l + 1) % N
+    wh = t - ft
+    wl = 1.0 - wh
+    total = np.zeros(N)
+    acc = np.zeros((N, s.shape[1]))
+    np.add.at(total, l, wl)
+    np.add.at(total, h, wh)
+    np.add.at(acc, l, wl[:, None] * s)
+    np.add.at(acc, h, wh[:, None] * s)
+    if not (total > 0).all():
+        raise ValueError(f"no projection touches frame(s) {np.flatnonzero(~(total > 0)).tolist()} of {N}: they have no breathing state")
+    return acc / total[:, None]
+
+
+def _rooster_motion(lib, frames, dimension, spacing, motion_to_reference: MotionModel, motion_from_reference: MotionModel, states):
+    """(mcgpu_rooster4d_motion, the arrays it points into) for the frame states [frames, K]."""
+    lib.mcgpu_rooster4d_reconstruct_motion.argtypes = [C.POINTER(_RoosterOptions), C.POINTER(_RoosterMotion), C.c_void_p, C.c_void_p,
+                                                       C.POINTER(_RoosterMotionReport)]
+    lib.mcgpu_rooster4d_motion_stage.argtypes = [C.POINTER(_RoosterOptions), C.POINTER(_RoosterMotion), C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.POINTER(_RoosterMotionReport)]
+    motion_to_reference.check_grid(dimension, spacing)
+    motion_from_reference.check_grid(dimension, spacing)
+    if motion_to_reference.n_signal_dims != motion_from_reference.n_signal_dims:
+        raise ValueError(f"the model to the reference has {motion_to_reference.n_signal_dims} signal dimensions, the model from it "
+                         f"{motion_from_reference.n_signal_dims}")
+    delta_to, delta_from = motion_to_reference.delta(states), motion_from_reference.delta(states)
+    if delta_to.shape[0] != int(frames):
+        raise ValueError(f"{int(frames)} frames but {delta_to.shape[0]} frame states")
+    if not (np.isfinite(delta_to).all() and np.isfinite(delta_from).all()):
+        raise ValueError("the signals are not finite")
+    fp, dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
+    m = _RoosterMotion(C.sizeof(_RoosterMotion), motion_to_reference.n_signal_dims, motion_to_reference.mean.ctypes.data_as(fp),
+                       motion_to_reference.coefficients.ctypes.data_as(fp), motion_from_reference.mean.ctypes.data_as(fp),
+                       motion_from_reference.coefficients.ctypes.data_as(fp), delta_to.ctypes.data_as(dp), delta_from.ctypes.data_as(dp))
+    return m, (delta_to, delta_from)
+
+
+def rooster4d_motion(projections: np.ndarray, geometry: CircularGeometry, pixel_spacing: Tuple[float, float], pixel_origin: Optional[Tuple[float, float]],
+                     phase: Sequence[float], motion_to_reference: MotionModel, motion_from_reference: MotionModel, signals,
+                     dimension: Tuple[int, int, int] = (464, 250, 464), spacing: Tuple[float, float, float] = (1.0, 1.0, 1.0),
+                     origin: Optional[Tuple[float, float, float]] = None, frames: int = 10, niter: int = 10, cgiter: int = 4, tviter: int = 10,
+                     gamma_time: float = 0.0002, gamma_space: float = 0.00007, water_pre_correction: Optional[Sequence[float]] = None,
+                     positivity: bool = True, gpu_id: int = 0):
+    """Motion-aware 4-D ROOSTER (Mory, Janssens, Rit, PMB 2016; csrc/rooster4d.hip states the rule): rooster4d()
+    with the temporal TV run along the trajectories of two motion models instead of along the time axis of every voxel, so that a
+    strong `gamma_time` averages the same tissue over the frames and does not smear what moves.
+
+    DIRECTION of the two models, both `MotionModel`s on the reconstruction grid with the same K (ValueError otherwise):
+      motion_to_reference    the FORWARD model: the material of reference-phase voxel P is at P + F(P; s) at state s.
+                             `MotionModel.from_correspondence_model(CorrespondenceModel.build_default(..., inverse=True), ...)`.
+      motion_from_reference  the PULL-BACK model: frame_s(Q) = ref(Q + G(Q; s)).  The default `build_default(...)`, converted the
+                             same way.
+    Neither is derived from the other, and a swapped pair is NOT detected: it moves every frame twice the wrong way.
+    signals [n, K]: the breathing signal of every projection in the models' units; frame f is given the state
+    `frame_signals(phase, signals, frames)[f]`.
+
+    Step 4 of a main iteration becomes  y = W x;  c = TVtime(y) - y;  x = x + U c  (W warps every frame to the reference phase, U
+    back): the increment form, which resamples only the regulariser's correction.  RTK replaces x by U TVtime(W x), which blurs x
+    whenever a displacement is no whole number of voxels -- a deliberate departure (profiles/rooster4d_motion.md has the figures).
+    Everything else, the remaining arguments and the defaults are those of rooster4d().  Parity against RTK is unpinned (RTK is
+    absent here); tests/rooster_motion_ref.py restates the rule in float64.
+
+    -> (volume [frames, nz, ny, nx] float32, report dict: that of rooster4d plus ms_warp, ms_upload_model and frame_signals)."""
+    from . import engine
+    p = np.ascontiguousarray(projections, dtype=np.float32)
+    n, nv, nu = p.shape
+    lib, o, keep = _rooster_call(n, nu, nv, geometry, pixel_spacing, pixel_origin, phase, dimension, spacing, origin, frames, niter, cgiter, tviter,
+                                 gamma_time, gamma_space, water_pre_correction, positivity, gpu_id)
+    s = np.asarray(signals, dtype=np.float64)
+    if s.shape[0] != n:
+        raise ValueError(f"{n} projections but {s.shape[0]} signals")
+    states = frame_signals(keep["phase"], s, frames)
+    m, keep_m = _rooster_motion(lib, frames, dimension, spacing, motion_to_reference, motion_from_reference, states)
+    vol = np.zeros((int(frames), int(dimension[2]), int(dimension[1]), int(dimension[0])), dtype=np.float32)
+    rep = _RoosterMotionReport()
+    engine._check(lib.mcgpu_rooster4d_reconstruct_motion(C.byref(o), C.byref(m), p.ctypes.data, vol.ctypes.data, C.byref(rep)))
+    out = {name: getattr(rep, name) for name, _ in _RoosterMotionReport._fields_}
+    out["residuals"] = keep["residuals"].reshape(max(int(niter), 0), max(int(cgiter), 0) + 1).copy()
+    out["frame_signals"] = states
+    return vol, out
+
+
+def rooster4d_motion_stage(stage: str, data: np.ndarray, motion_to_reference: MotionModel, motion_from_reference: MotionModel, frame_states,
+                           dimension, spacing, tviter: int = 10, gamma_time: float = 0.0002, gpu_id: int = 0):
+    """One operator of rooster4d_motion alone (mcgpu_rooster4d_motion_stage), [frames, nz, ny, nx] -> the same shape: 'warp' (W, every
+    frame to the reference phase with motion_to_reference), 'unwarp' (U, back with motion_from_reference), 'tv_time_motion'
+    (x + U (TVtime(W x) - W x) with `tviter` iterations and `gamma_time`).  frame_states [frames, K]: the state of every frame (what
+    frame_signals gives).  -> (result float32, report dict)."""
+    from . import engine
+    src = np.ascontiguousarray(data, dtype=np.float32)
+    shape4 = (src.shape[0] if src.ndim == 4 else -1, int(dimension[2]), int(dimension[1]), int(dimension[0]))
+    if src.shape != shape4:
+        raise ValueError(f"rooster4d_motion_stage {stage}: input shape {src.shape}")
+    frames = src.shape[0]
+    placeholder = CircularGeometry(1000.0, 1500.0, [0.0], [0.0], [0.0])  # the stages use no projection geometry; the options need a valid one
+    lib, o, keep = _rooster_call(1, 2, 2, placeholder, (1.0, 1.0), None, [0.0], dimension, spacing, None, frames, 0, 0, tviter, gamma_time, 0.0,
+                                 None, True, gpu_id)
+    m, keep_m = _rooster_motion(lib, frames, dimension, spacing, motion_to_reference, motion_from_reference, frame_states)
+    out = np.zeros(shape4, dtype=np.float32)
+    rep = _RoosterMotionReport()
+    engine._check(lib.mcgpu_rooster4d_motion_stage(C.byref(o), C.byref(m), ROOSTER4D_MOTION_STAGES[stage], src.ctypes.data, out.ctypes.data, C.byref(rep)))
+    return out, {name: getattr(rep, name) for name, _ in _RoosterMotionReport._fields_}
+
+
+def reconstruct_4d_mc(projections_filepath, geometry_filepath, model_to_reference, model_from_reference, signals, voxel_spacing_mm,
+                      amplitude_signal: Optional[np.ndarray] = None, phase_signal: Optional[np.ndarray] = None, output_folder=None,
+                      output_filename: Optional[str] = None, dimension: Tuple[int, int, int] = (464, 250, 464),
+                      spacing: Tuple[float, float, float] = (1.0, 1.0, 1.0), water_pre_correction: Optional[Sequence[float]] = None, gpu_id: int = 0,
+                      **kwargs):
+    """reconstruct_4d with the motion of two fitted `CorrespondenceModel`s followed by the temporal regulariser (rooster4d_motion):
+    the signal handling and the parameters of reconstruct_4d, the file flow of reconstruct_3d_mc.
+    model_to_reference: built with `build_default(..., inverse=True)` (reference-phase voxels forward to a state);
+    model_from_reference: the default `build_default(...)` (pull-back fields); both on the reconstruction grid (see
+    MotionModel.from_correspondence_model for the frame).  A swapped pair is not detected.  voxel_spacing_mm: the spacing of the
+    MCGeometry the fields live on; signals [n, K]: the breathing signal of every projection, in the models' units.  Writes
+    `recon_rooster4d_mc.mha` (4-D, as reconstruct_4d) and a .yaml that also records `motion_to_reference` / `motion_from_reference`
+    (the first 7 hex digits of each model's hash), `signal_n_dims` (K) and `temporal_update: increment`."""
+    ph = _unit_phase(amplitude_signal, phase_signal)
+    projections_filepath, geometry_filepath = Path(projections_filepath), Path(geometry_filepath)
+    output_folder = Path(output_folder) if output_folder else projections_filepath.parent / "reconstructions"
+    output_filename = output_filename or "recon_rooster4d_mc.mha"
+    to_reference = MotionModel.from_correspondence_model(model_to_reference, voxel_spacing_mm, dimension=dimension, spacing=spacing)
+    from_reference = MotionModel.from_correspondence_model(model_from_reference, voxel_spacing_mm, dimension=dimension, spacing=spacing)
+    output_folder.mkdir(parents=True, exist_ok=True)
+    params = dict(niter=10, cgiter=4, tviter=10, gamma_time=0.0002, gamma_space=0.00007, frames=10, positivity=True)
+    params.update({k: kwargs.pop(k) for k in list(kwargs) if k in params})
+    proj, pspacing, porigin = read_mha(projections_filepath)
+    geometry = CircularGeometry.read(geometry_filepath)
+    vol, report = rooster4d_motion(proj, geometry, (pspacing[0], pspacing[1]), (porigin[0], porigin[1]), ph, to_reference, from_reference, signals,
+                                   dimension, spacing, None, water_pre_correction=water_pre_correction, gpu_id=gpu_id, **params)
+    origin = tuple(-(n - 1) / 2 * s for n, s in zip(dimension, spacing))
+    out = output_folder / output_filename
+    write_mha(out, vol, tuple(spacing) + (1.0,), origin + (0.0,))
+    import yaml
+    record = dict(path=str(projections_filepath.parent), regexp=projections_filepath.name, geometry=str(geometry_filepath), fp="Joseph",
+                  bp="VoxelBased", hardware="hip", dimension=list(dimension), spacing=list(spacing),
+                  wpc=list(water_pre_correction) if water_pre_correction is not None else None, output_filepath=str(out),
+                  motion_to_reference=model_to_reference.model_hash[:7], motion_from_reference=model_from_reference.model_hash[:7],
+                  signal_n_dims=to_reference.n_signal_dims, temporal_update="increment", **params, **kwargs)
     with open(out.with_suffix(".yaml"), "w") as f:
         yaml.dump(record, f)
     return out, report

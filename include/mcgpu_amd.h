@@ -778,6 +778,48 @@ int mcgpu_rooster4d_reconstruct(const mcgpu_rooster4d_options *options, const fl
 enum { MCGPU_ROOSTER4D_STAGE_FORWARD = 0, MCGPU_ROOSTER4D_STAGE_BACK = 1, MCGPU_ROOSTER4D_STAGE_TV_SPACE = 2, MCGPU_ROOSTER4D_STAGE_TV_TIME = 3 };
 int mcgpu_rooster4d_stage(const mcgpu_rooster4d_options *options, int stage, const float *in, float *out, mcgpu_rooster4d_report *report);
 
+/* Row f16: motion-aware 4-D ROOSTER (Mory, Janssens, Rit, PMB 2016; what RTK's `rtkfourdrooster --dvf --idvf` is for;
+ * csrc/rooster4d.hip, whose header states the rule).  Row f6 with its temporal TV run along the trajectories of two linear motion
+ * models on the reconstruction grid, both in the layout of row f15: mean [3][nz][ny][nx] and coefficients [K][3][nz][ny][nx], mm
+ * (mm per signal unit) along IEC X, Y, Z, the same K for both.
+ *   to_reference   (forward model): the material of reference-phase voxel P is at P + F(P; s) at state s;
+ *   from_reference (pull-back model): frame_s(Q) = ref(Q + G(Q; s)).
+ * Frame f has a state s_f; delta_to[f][k] = s_f[k] - mean_signal_to[k], delta_from[f][k] likewise (rounded once to float32).
+ * The sampling operator Sigma(model, delta) of a volume at voxel (ix, iy, iz): displacement d = mean + sum_k coefficients[k]
+ * delta[k] (fmaf chain, k ascending); per axis fx = fmaf(d_x, 1 / sx, (float)ix) clamped to [0, nx - 1] by fminf(fmaxf(fx, 0),
+ * nx - 1) (the border is replicated; every index is in bounds for any float input), i0 = (int)floorf(fx), t = fx - i0, i1 =
+ * min(i0 + 1, nx - 1); trilinear with nested lerp(a, b, t) = fmaf(t, b - a, a) along x, y, z.  W applies Sigma(to_reference,
+ * delta_to[f]) to frame f, U applies Sigma(from_reference, delta_from[f]).  Steps 1 - 3 of a main iteration are those of row f6;
+ * step 4 is  y = W x;  c = TVtime(y) - y;  x = x + U c  (the increment form: only the correction is resampled; RTK replaces x by
+ * U TVtime(W x)).  With gamma_time = 0 or tviter = 0 step 4 leaves x untouched.  No model is derived from the other and a swapped
+ * pair is not detected.  Parity against RTK is unpinned (RTK is absent here). */
+typedef struct mcgpu_rooster4d_motion {
+  unsigned int struct_size;     /* sizeof(mcgpu_rooster4d_motion) as the caller was compiled; 0 is refused */
+  int n_signal_dims;            /* K, 1..4 */
+  const float *to_reference_mean;            /* [3][nz][ny][nx] */
+  const float *to_reference_coefficients;    /* [K][3][nz][ny][nx] */
+  const float *from_reference_mean;          /* [3][nz][ny][nx] */
+  const float *from_reference_coefficients;  /* [K][3][nz][ny][nx] */
+  const double *delta_to;       /* [n_frames][K], finite */
+  const double *delta_from;     /* [n_frames][K], finite */
+} mcgpu_rooster4d_motion;
+typedef struct mcgpu_rooster4d_motion_report {
+  double ms_forward, ms_back, ms_cg_vectors, ms_tv_space, ms_tv_time, ms_upload, ms_total;  /* as mcgpu_rooster4d_report */
+  unsigned long long peak_device_bytes;
+  double ms_warp;               /* the W and U kernels and the subtraction between them */
+  double ms_upload_model;       /* host clock around the upload of the two models */
+} mcgpu_rooster4d_motion_report;
+/* Refused with -1 before any device call: what mcgpu_rooster4d_reconstruct refuses, a null model or delta pointer, K outside 1..4,
+ * a delta that is not finite (as float32), an unknown stage. */
+int mcgpu_rooster4d_reconstruct_motion(const mcgpu_rooster4d_options *options, const mcgpu_rooster4d_motion *motion,
+                                       const float *projections /*[n_proj][nv][nu]*/, float *volume4d /*[n_frames][nz][ny][nx]*/,
+                                       mcgpu_rooster4d_motion_report *report);
+/* One operator alone (for tests), 4-D volume -> 4-D volume: WARP out = W in; UNWARP out = U in; TV_TIME_MOTION out = in +
+ * U (TVtime(W in) - W in) with tviter iterations and gamma_time.  The geometry fields of the options are checked and not used. */
+enum { MCGPU_ROOSTER4D_MOTION_STAGE_WARP = 0, MCGPU_ROOSTER4D_MOTION_STAGE_UNWARP = 1, MCGPU_ROOSTER4D_MOTION_STAGE_TV_TIME_MOTION = 2 };
+int mcgpu_rooster4d_motion_stage(const mcgpu_rooster4d_options *options, const mcgpu_rooster4d_motion *motion, int stage, const float *in,
+                                 float *out, mcgpu_rooster4d_motion_report *report);
+
 /* ------------------------------------------------------------------------------------------------
  * Row f14: demons registration of two volumes (what the reference's CorrespondenceModel.build_default obtains from vroc's
  * variational registration, cbctmc/registration/correspondence.py:315-345; csrc/registration.hip, whose header states the rule;
