@@ -16,16 +16,18 @@
 //                 is 3.9 detector pixels, so the 4 loads of a wave touch ~32 cache lines for 64 updates: the vector L1
 //                 (64 B/clk/CU) bounds the kernel at ~1 update/clk/CU; measured 0.78                              (L1/L2 gather)
 //   backproject_motion : the same sample taken where a linear motion model puts the voxel at the projection's breathing state
-//                 (row f15, mcgpu_fdk_reconstruct_motion; the rule stands above backproject_motion_kernel)         (L1/L2 gather)
+//                 (row f15, mcgpu_fdk_reconstruct_motion; the model is motion_model.inc's, P' stands above backproject_motion_kernel)         (L1/L2 gather)
 #include <hipfft/hipfft.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <complex>
 #include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mcgpu_amd.h"
@@ -35,6 +37,7 @@
 namespace {
 
 #include "fdk_common.inc"
+#include "motion_model.inc"
 
 // in: [n][nv][nu] raw line integrals; out: [n][nv][nu_p] weighted rows, padded with pad_l zero columns on the left (and zeros on the
 // right) so that an off-centre detector becomes symmetric about the central ray (RTK: DisplacedDetectorImageFilter)
@@ -80,24 +83,17 @@ __global__ __launch_bounds__(256, 4) void backproject_kernel(float* __restrict__
 }
 
 // ---- motion-compensated back-projection ------------------------------------------------------------------
-// The rule.  The grid is the FDK grid [nz][ny][nx] in RTK's IEC frame.  A motion model on it is mean [3][nz][ny][nx] (mm, components
-// along IEC X, Y, Z), coefficients [K][3][nz][ny][nx] (mm per signal unit, 1 <= K <= 4) and, per projection i, delta[i][k] =
-// signal_i[k] - mean_signal[k], given in double and rounded once to float32.  For the voxel at P = (X, Y, Z) and projection i every
-// component of the displacement is float32 with explicit fmaf, k ascending:
-//     acc = mean;  for k in 0..K-1: acc = fmaf(coefficients[k], delta[i][k], acc);  P' = P + acc
-// and projection i gives the voxel what plain FDK gives at P':  xr = X'c - Z's, zr = X's + Z'c, U = sid - zr, mag = sdd / U,
-// fu = (mag xr - off_x - u0_p) / du, fv = (mag Y' - off_y - v0) / dv, weight gap_i (sid / U)^2, and the bilinear sample of the
-// filtered, padded row buffer through detector_rows / detector_sample.  A sample counts only when U > 0, columns iu, iu + 1 lie
-// inside the padded detector and rows iv, iv + 1 inside the detector.  The model says where the material of a reference-phase voxel
-// IS at the projection's state (the inverse of a pull-back field); nothing here inverts a model.
+// The model, its layout and the displacement d of a voxel for a projection's delta are motion_model.inc's.  What is this kernel's own:
+// the model says where the material of a reference-phase voxel IS at the projection's state (the inverse of a pull-back field; nothing
+// here inverts a model), so for the voxel at P = (X, Y, Z) projection i gives what plain FDK gives at P' = P + d:  xr = X'c - Z's,
+// zr = X's + Z'c, U = sid - zr, mag = sdd / U, fu = (mag xr - off_x - u0_p) / du, fv = (mag Y' - off_y - v0) / dv, weight
+// gap_i (sid / U)^2, and the bilinear sample of the filtered, padded row buffer through detector_rows / detector_sample.  A sample
+// counts only when U > 0, columns iu, iu + 1 lie inside the padded detector and rows iv, iv + 1 inside the detector.
 //
 // With motion every voxel has its own (fu, fv): the column trick of backproject_kernel is gone.  One thread per voxel, x fastest
 // (model loads and the volume's read-modify-write coalesce; neighbouring lanes hit neighbouring detector columns); the thread loads
-// its 3 (K + 1) model values once per launch and loops over the projections of the batch, whose poses and deltas are wave-uniform
-// kernel arguments (scalar loads).  A voxel has one owner and the projections are summed in order: no atomics, two calls give the
-// same bytes.  K is a template parameter: the thread loads exactly the model it has and the fmaf chain is straight-line code.  (The
-// K = 4 code with a uniform bound and zero-filled slots measured the same time, 191.6 against 191.2 ms at 16 projections per
-// launch, and the same bytes: it was not kept.)
+// its model once per launch and loops over the projections of the batch, whose poses and deltas are wave-uniform kernel arguments
+// (scalar loads).  A voxel has one owner and the projections are summed in order: no atomics, two calls give the same bytes.
 //
 // projections per launch of the motion kernel.  The per-projection state is scalar, so the batch only sets how often the model
 // (3 (K + 1) floats per voxel) is re-read and the volume re-written.  Measured at the reference's size with K = 2 on one MI355X, all
@@ -105,7 +101,6 @@ __global__ __launch_bounds__(256, 4) void backproject_kernel(float* __restrict__
 // 206.3 ms, 16 191.2 ms, 32 (one launch per resident chunk) 184.2 ms, against 105.1 ms of backproject_kernel; as committed 185.2 ms,
 // 1.76 x.
 constexpr int kMotionBatch = 32;
-constexpr int kMotionMaxK = 4;
 
 struct MotionArgs {  // a sibling of BackArgs: the three column kernels' layout is untouched
   int nx, ny, nz, nu, nv, nb;
@@ -122,28 +117,17 @@ __global__ __launch_bounds__(256) void backproject_motion_kernel(float* __restri
   const size_t nvox = (size_t)A.nx * A.ny * A.nz;
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nvox) return;
-  const int ix = (int)(i % A.nx), iy = (int)((i / A.nx) % A.ny), iz = (int)(i / ((size_t)A.nx * A.ny));
+  int ix, iy, iz;
+  voxel_index(i, A.nx, A.ny, ix, iy, iz);
   const float X = A.x0 + A.sx * ix, Y = A.y0 + A.sy * iy, Z = A.z0 + A.sz * iz;
-  const float mx = mean[i], my = mean[nvox + i], mz = mean[2 * nvox + i];
-  float cx[K], cy[K], cz[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    cx[k] = coef[((size_t)3 * k + 0) * nvox + i];
-    cy[k] = coef[((size_t)3 * k + 1) * nvox + i];
-    cz[k] = coef[((size_t)3 * k + 2) * nvox + i];
-  }
+  MotionVoxel<K> model;
+  model.load(mean, coef, nvox, i);
   const size_t plane = (size_t)A.stride * A.nv;
   float acc = 0.f;
   for (int p = 0; p < A.nb; ++p) {
     const ProjParam& pp = A.pp[p];
-    float dx = mx, dy = my, dz = mz;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      const float d = A.delta[p][k];
-      dx = fmaf(cx[k], d, dx);
-      dy = fmaf(cy[k], d, dy);
-      dz = fmaf(cz[k], d, dz);
-    }
+    float dx, dy, dz;
+    model.displacement(A.delta[p], dx, dy, dz);
     const float Xp = X + dx, Yp = Y + dy, Zp = Z + dz;
     const float xr = fmaf(Xp, pp.c, -(Zp * pp.s)), zr = fmaf(Xp, pp.s, Zp * pp.c);
     const float U = A.sid - zr;
@@ -171,8 +155,8 @@ struct FdkProblem {
   const float* filtered = nullptr;  // what filter() left for backproject(): d_tmp, or d_in after the hannY pass
   // the motion model of mcgpu_fdk_reconstruct_motion, resident for the call
   int motion_K = 0;
-  float *d_mean = nullptr, *d_coef = nullptr;
-  std::vector<float> delta32;  // [n][K]
+  DeviceMotionModel model;
+  std::vector<std::array<float, kMotionMaxK>> delta32;  // [n]
   double ms_upload_model = 0.0;
 
   FdkProblem(const mcgpu_fdk_options& opt, const FdkPlan& plan, const char* fn = "mcgpu_fdk_reconstruct") : o(opt), P(plan), rows(plan, fn) {}
@@ -212,17 +196,6 @@ struct FdkProblem {
     st.done();
   }
 
-  // the model onto the device once, as float32; delta rounded once to float32
-  void upload_model(const mcgpu_fdk_motion& M) {
-    mcgpu::Stopwatch sw;
-    motion_K = M.n_signal_dims;
-    d_mean = dev.upload(M.mean, 3 * P.nvox);
-    d_coef = dev.upload(M.coefficients, (size_t)motion_K * 3 * P.nvox);
-    delta32.resize((size_t)P.n * motion_K);
-    for (size_t j = 0; j < delta32.size(); ++j) delta32[j] = (float)M.delta[j];
-    ms_upload_model = sw.ms();
-  }
-
   // backproject(first, m) with moving voxels
   void backproject_motion(int first, int m) {
     mcgpu::Stage st(dev, rep.ms_backproject);
@@ -235,20 +208,33 @@ struct FdkProblem {
       A.x0 = (float)P.ox0; A.y0 = (float)P.oy0; A.z0 = (float)P.oz0; A.sx = (float)o.sx; A.sy = (float)o.sy; A.sz = (float)o.sz;
       A.sid = (float)o.sid; A.sdd = (float)o.sdd; A.inv_du = (float)(1.0 / o.du); A.inv_dv = (float)(1.0 / o.dv);
       A.u0 = (float)P.u0_p; A.v0 = (float)o.v0;
-      for (int p = 0; p < A.nb; ++p) {
-        A.pp[p] = P.pp[first + b + p];
-        for (int k = 0; k < motion_K; ++k) A.delta[p][k] = delta32[(size_t)(first + b + p) * motion_K + k];
-      }
+      std::copy_n(&P.pp[first + b], A.nb, A.pp);
+      memcpy(A.delta, &delta32[first + b], A.nb * sizeof delta32[0]);
       const float* q = filtered + (size_t)b * P.plane_p;
-      auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, nullptr, d_vol, q, d_mean, d_coef, A); };
-      switch (motion_K) {
-        case 1: launch(backproject_motion_kernel<1>); break;
-        case 2: launch(backproject_motion_kernel<2>); break;
-        case 3: launch(backproject_motion_kernel<3>); break;
-        default: launch(backproject_motion_kernel<4>); break;
-      }
+      dispatch_motion_k(motion_K, [&](auto k) {
+        hipLaunchKernelGGL(backproject_motion_kernel<decltype(k)::value>, dim3(blocks), dim3(256), 0, nullptr, d_vol, q, model.mean, model.coef, A);
+      });
     }
     st.done();
+  }
+
+  // the whole reconstruction: tables (and the model) up, every resident chunk filtered and back-projected, the volume down
+  void run(const float* projections, float* volume, const mcgpu_fdk_motion* motion) {
+    upload();
+    if (motion) {  // the model onto the device once, as float32; delta rounded once to float32
+      mcgpu::Stopwatch sw;
+      motion_K = motion->n_signal_dims;
+      model = upload_motion_model(dev, motion->mean, motion->coefficients, motion_K, P.nvox);
+      delta32 = round_deltas(motion->delta, P.n, motion_K);
+      ms_upload_model = sw.ms();
+    }
+    for (int first = 0; first < P.n; first += P.chunk) {
+      const int m = std::min(P.chunk, P.n - first);
+      filter(projections, first, m);
+      if (motion) backproject_motion(first, m);
+      else backproject(first, m);
+    }
+    HIP_TRY(hipMemcpy(volume, d_vol, P.nvox * 4, hipMemcpyDeviceToHost));
   }
 };
 
@@ -262,13 +248,7 @@ extern "C" int mcgpu_fdk_reconstruct(const mcgpu_fdk_options* caller_o, const fl
   HIP_TRY(hipSetDevice(local.device));
   const FdkPlan plan = plan_fdk(local);
   FdkProblem P(local, plan);
-  P.upload();
-  for (int first = 0; first < plan.n; first += plan.chunk) {
-    const int m = std::min(plan.chunk, plan.n - first);
-    P.filter(projections, first, m);
-    P.backproject(first, m);
-  }
-  HIP_TRY(hipMemcpy(volume, P.d_vol, plan.nvox * 4, hipMemcpyDeviceToHost));
+  P.run(projections, volume, nullptr);
   if (report) *report = P.rep;
   return 0;
   ABI_END
@@ -278,26 +258,19 @@ extern "C" int mcgpu_fdk_reconstruct_motion(const mcgpu_fdk_options* caller_o, c
                                             mcgpu_fdk_motion_report* report) {
   ABI_BEGIN
   const char* fn = "mcgpu_fdk_reconstruct_motion";
+  const std::string bad_argument = std::string("!!ERROR!! ") + fn + ": bad argument";
   mcgpu_fdk_options local;
   mcgpu::read_options(fn, "mcgpu_fdk_options", caller_o, local);
   mcgpu_fdk_motion motion;
   mcgpu::read_options(fn, "mcgpu_fdk_motion", caller_m, motion);
-  if (!projections || !volume || !fdk_options_ok(local)) throw mcgpu::Error(-1, std::string("!!ERROR!! ") + fn + ": bad argument");
-  if (motion.n_signal_dims < 1 || motion.n_signal_dims > kMotionMaxK) throw mcgpu::Error(-1, std::string("!!ERROR!! ") + fn + ": n_signal_dims must lie in 1..4");
-  if (!motion.mean || !motion.coefficients || !motion.delta) throw mcgpu::Error(-1, std::string("!!ERROR!! ") + fn + ": bad argument");
-  for (size_t j = 0; j < (size_t)local.n_proj * motion.n_signal_dims; ++j)  // NaN, infinite, or infinite once it is float32
-    if (!(std::fabs(motion.delta[j]) <= (double)std::numeric_limits<float>::max())) throw mcgpu::Error(-1, std::string("!!ERROR!! ") + fn + ": delta is not finite");
+  if (!projections || !volume || !fdk_options_ok(local)) throw mcgpu::Error(-1, bad_argument);
+  check_motion_k(fn, motion.n_signal_dims);
+  if (!motion.mean || !motion.coefficients || !motion.delta) throw mcgpu::Error(-1, bad_argument);
+  check_delta(fn, motion.delta, (size_t)local.n_proj * motion.n_signal_dims);
   HIP_TRY(hipSetDevice(local.device));
   const FdkPlan plan = plan_fdk(local);
   FdkProblem P(local, plan, fn);
-  P.upload();
-  P.upload_model(motion);
-  for (int first = 0; first < plan.n; first += plan.chunk) {
-    const int m = std::min(plan.chunk, plan.n - first);
-    P.filter(projections, first, m);
-    P.backproject_motion(first, m);
-  }
-  HIP_TRY(hipMemcpy(volume, P.d_vol, plan.nvox * 4, hipMemcpyDeviceToHost));
+  P.run(projections, volume, &motion);
   if (report) *report = {P.rep.ms_filter, P.rep.ms_backproject, P.ms_upload_model, (unsigned long long)P.dev.peak};
   return 0;
   ABI_END

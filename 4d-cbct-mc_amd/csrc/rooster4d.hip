@@ -31,13 +31,12 @@
 // Residency: the projection stack and the 4-D vectors x, b, r, d, A d stay on the device for the whole run.
 //
 // Motion-aware ROOSTER (mcgpu_rooster4d_reconstruct_motion; Mory, Janssens, Rit, PMB 2016; what RTK's
-// `rtkfourdrooster --dvf --idvf` is for).  The rule.  Two linear motion models live on the reconstruction grid, both in the layout
-// of row f15 (fdk.hip): mean [3][nz][ny][nx] and coefficients [K][3][nz][ny][nx], float32, mm along IEC X, Y, Z, 1 <= K <= 4.
+// `rtkfourdrooster --dvf --idvf` is for).  Two linear motion models live on the reconstruction grid; their layout and the
+// displacement d of a voxel for a state's delta are motion_model.inc's.
 //   to_reference   (forward model): the material of reference-phase voxel P is at P + F(P; s) at state s.
 //   from_reference (pull-back model): frame_s(Q) = ref(Q + G(Q; s)).
-// Frame f has a state s_f that enters as delta_to[f][k] = s_f[k] - mean_signal_to[k] and delta_from[f][k] likewise, given in
-// double and rounded once to float32.  The sampling operator Sigma(model, delta) of a volume v at the voxel P = (ix, iy, iz):
-//   displacement  d = mean(P) + sum_k coefficients[k](P) delta[k] per component, as an fmaf chain, k ascending;
+// Frame f has a state s_f that enters as delta_to[f][k] = s_f[k] - mean_signal_to[k] and delta_from[f][k] likewise.  What is this
+// file's own is where P + d goes, the sampling operator Sigma(model, delta) of a volume v at the voxel P = (ix, iy, iz):
 //   position      per axis fx = fmaf(d_x, 1 / sx, (float)ix), clamped: fminf(fmaxf(fx, 0), nx - 1) -- the border is replicated and
 //                 every index is in bounds for any float input, NaN and Inf included;
 //   cell          i0 = (int)floorf(fx), t = fx - i0, i1 = min(i0 + 1, nx - 1);
@@ -49,16 +48,17 @@
 // so only the regulariser's correction is resampled, never x itself: with gamma_time = 0 or tviter = 0 x is left untouched, and a
 // displacement that is no whole number of voxels does not blur x.  A deliberate departure from RTK, which replaces x by
 // U TVtime(W x) and so resamples the volume twice per main iteration.  Nothing here derives one model from the other, and a
-// swapped pair is not detected.  Kernels: warp4_kernel (one thread per voxel, x fastest; it loads its 3 (K + 1) model values once
+// swapped pair is not detected.  Kernels: warp4_kernel (one thread per voxel, x fastest; it loads its model once
 // and loops over the frames, whose deltas are wave-uniform kernel arguments; 8 gathers per frame; it stores W x twice, as y and as
 // the input of TVtime, or adds U c to x) and subtract_kernel.  y and c are the CG vectors A d and r, free at step 4: no new 4-D
 // allocation, peak memory grows by the two resident models, 2 x 3 (K + 1) frames.  Restated in float64 by tests/rooster_motion_ref.py.
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstring>
 #include <limits>
-#include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mcgpu_amd.h"
@@ -67,6 +67,8 @@
 #include "joseph_ray.inc"
 
 namespace {
+
+#include "motion_model.inc"
 
 using mcgpu::CallDevice;
 using mcgpu::Stage;
@@ -322,12 +324,10 @@ __global__ __launch_bounds__(256) void tv_time_kernel(float* __restrict__ x4, si
 }
 
 // ---- motion-aware temporal step (the rule stands in this file's header) -------------------------------------
-constexpr int kWarpMaxK = 4;
-
 struct WarpArgs {
   int nx, ny, nz, N;
   float inv_sx, inv_sy, inv_sz;
-  float delta[kMaxFrames][kWarpMaxK];  // [f][k], k < K: wave-uniform, read through scalar loads
+  float delta[kMaxFrames][kMotionMaxK];  // [f][k], k < K: wave-uniform, read through scalar loads
 };
 
 // index position along one axis -> cell (i0, i1) and weight t.  The float clamp alone keeps every index in bounds for any input
@@ -350,26 +350,15 @@ __global__ __launch_bounds__(256) void warp4_kernel(float* __restrict__ dst, flo
                                                     const float* __restrict__ mean, const float* __restrict__ coef, const WarpArgs A) {
   const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
   if (i >= frame) return;
-  const int ix = (int)(i % A.nx), iy = (int)((i / A.nx) % A.ny), iz = (int)(i / ((size_t)A.nx * A.ny));
-  const float mx = mean[i], my = mean[frame + i], mz = mean[2 * frame + i];
-  float cx[K], cy[K], cz[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    cx[k] = coef[((size_t)3 * k + 0) * frame + i];
-    cy[k] = coef[((size_t)3 * k + 1) * frame + i];
-    cz[k] = coef[((size_t)3 * k + 2) * frame + i];
-  }
+  int ix, iy, iz;
+  voxel_index(i, A.nx, A.ny, ix, iy, iz);
+  MotionVoxel<K> model;
+  model.load(mean, coef, frame, i);
   const size_t nx = (size_t)A.nx, nxy = nx * A.ny;
 #pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
   for (int f = 0; f < A.N; ++f) {
-    float dx = mx, dy = my, dz = mz;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      const float d = A.delta[f][k];
-      dx = fmaf(cx[k], d, dx);
-      dy = fmaf(cy[k], d, dy);
-      dz = fmaf(cz[k], d, dz);
-    }
+    float dx, dy, dz;
+    model.displacement(A.delta[f], dx, dy, dz);
     int x0, x1, y0, y1, z0, z1;
     float tx, ty, tz;
     warp_cell(dx, A.inv_sx, ix, A.nx, x0, x1, tx);
@@ -442,14 +431,14 @@ struct Problem {
   CallDevice dev;
   double* d_part = nullptr;
   double* d_sum = nullptr;
-  // the two motion models of mcgpu_rooster4d_reconstruct_motion, resident for the call; null: plain ROOSTER, which launches
-  // exactly what it launched without this member
-  struct Motion {
-    int K = 0;
-    const float *to_mean = nullptr, *to_coef = nullptr, *from_mean = nullptr, *from_coef = nullptr;  // device
-    WarpArgs to, from;  // grid, 1 / spacing and the frames' deltas (rounded once to float32) of W and of U
+  // the two motion models of mcgpu_rooster4d_reconstruct_motion, resident for the call; motion_K == 0: plain ROOSTER, which launches
+  // exactly what it launched without these members
+  struct Warp {
+    DeviceMotionModel model;
+    WarpArgs args;  // grid, 1 / spacing and the frames' deltas (rounded once to float32)
   };
-  std::unique_ptr<Motion> motion;
+  int motion_K = 0;
+  Warp to, from;  // W and U
   double ms_warp = 0.0, ms_upload_model = 0.0;
 
   explicit Problem(const mcgpu_rooster4d_options& opt) : o(opt), N(opt.n_frames) {
@@ -567,42 +556,27 @@ struct Problem {
   // both models onto the device once, as float32; the deltas rounded once to float32
   void upload_model(const mcgpu_rooster4d_motion& M) {
     const mcgpu::Stopwatch sw;
-    motion = std::make_unique<Motion>();
-    Motion& m = *motion;
-    m.K = M.n_signal_dims;
-    m.to_mean = dev.upload(M.to_reference_mean, 3 * frame);
-    m.to_coef = dev.upload(M.to_reference_coefficients, (size_t)m.K * 3 * frame);
-    m.from_mean = dev.upload(M.from_reference_mean, 3 * frame);
-    m.from_coef = dev.upload(M.from_reference_coefficients, (size_t)m.K * 3 * frame);
-    memset(&m.to, 0, sizeof m.to);
-    m.to.nx = o.nx; m.to.ny = o.ny; m.to.nz = o.nz; m.to.N = N;
-    m.to.inv_sx = (float)(1.0 / o.sx); m.to.inv_sy = (float)(1.0 / o.sy); m.to.inv_sz = (float)(1.0 / o.sz);
-    m.from = m.to;
-    for (int f = 0; f < N; ++f)
-      for (int k = 0; k < m.K; ++k) {
-        m.to.delta[f][k] = (float)M.delta_to[(size_t)f * m.K + k];
-        m.from.delta[f][k] = (float)M.delta_from[(size_t)f * m.K + k];
-      }
+    motion_K = M.n_signal_dims;
+    to.model = upload_motion_model(dev, M.to_reference_mean, M.to_reference_coefficients, motion_K, frame);
+    from.model = upload_motion_model(dev, M.from_reference_mean, M.from_reference_coefficients, motion_K, frame);
+    memset(&to.args, 0, sizeof to.args);
+    to.args.nx = o.nx; to.args.ny = o.ny; to.args.nz = o.nz; to.args.N = N;
+    to.args.inv_sx = (float)(1.0 / o.sx); to.args.inv_sy = (float)(1.0 / o.sy); to.args.inv_sz = (float)(1.0 / o.sz);
+    from.args = to.args;
+    memcpy(to.args.delta, round_deltas(M.delta_to, N, motion_K).data(), N * sizeof to.args.delta[0]);
+    memcpy(from.args.delta, round_deltas(M.delta_from, N, motion_K).data(), N * sizeof from.args.delta[0]);
     ms_upload_model += sw.ms();
   }
 
   // dst = W src (to_reference) or U src (from reference); accumulate: dst += ...; dst2: a second copy of a stored result, or null
   void warp(bool to_reference, bool accumulate, float* dst, float* dst2, const float* src) {
-    const Motion& m = *motion;
-    const float* mean = to_reference ? m.to_mean : m.from_mean;
-    const float* coef = to_reference ? m.to_coef : m.from_coef;
-    const WarpArgs& A = to_reference ? m.to : m.from;
+    const Warp& w = to_reference ? to : from;
     const dim3 g((unsigned)((frame + kThreads - 1) / kThreads));
-    auto launch = [&](auto store, auto add) {
-      if (accumulate) hipLaunchKernelGGL(add, g, dim3(kThreads), 0, nullptr, dst, dst2, src, frame, mean, coef, A);
-      else hipLaunchKernelGGL(store, g, dim3(kThreads), 0, nullptr, dst, dst2, src, frame, mean, coef, A);
-    };
-    switch (m.K) {
-      case 1: launch(warp4_kernel<1, false>, warp4_kernel<1, true>); break;
-      case 2: launch(warp4_kernel<2, false>, warp4_kernel<2, true>); break;
-      case 3: launch(warp4_kernel<3, false>, warp4_kernel<3, true>); break;
-      default: launch(warp4_kernel<4, false>, warp4_kernel<4, true>); break;
-    }
+    dispatch_motion_k(motion_K, [&](auto k) {
+      constexpr int K = decltype(k)::value;
+      if (accumulate) hipLaunchKernelGGL((warp4_kernel<K, true>), g, dim3(kThreads), 0, nullptr, dst, dst2, src, frame, w.model.mean, w.model.coef, w.args);
+      else hipLaunchKernelGGL((warp4_kernel<K, false>), g, dim3(kThreads), 0, nullptr, dst, dst2, src, frame, w.model.mean, w.model.coef, w.args);
+    });
   }
 
   // step 4 along the model's trajectories: y = W x; c = TVtime(y) - y; x += U c.  y and c are two 4-D vectors the caller lends
@@ -700,7 +674,7 @@ struct Problem {
       }
       if (o.tviter > 0) {
         tv_space(x, work, o.tviter, (float)o.gamma_space);
-        if (motion) tv_time_motion(x, Ad, r, o.tviter, (float)o.gamma_time);
+        if (motion_K) tv_time_motion(x, Ad, r, o.tviter, (float)o.gamma_time);
         else tv_time(x, o.tviter, (float)o.gamma_time);
       }
     }
@@ -747,8 +721,14 @@ struct Problem {
     HIP_TRY(hipMemcpy(out, y, n4d * 4, hipMemcpyDeviceToHost));
   }
 
-  mcgpu_rooster4d_motion_report motion_report(double ms_total) const {
-    return {rep.ms_forward, rep.ms_back, rep.ms_cg_vectors, rep.ms_tv_space, rep.ms_tv_time, rep.ms_upload, ms_total,
+  // the report of a call that took ms_total on the host, plain or with the two motion fields
+  void write(double ms_total, mcgpu_rooster4d_report* out) {
+    rep.peak_device_bytes = dev.peak;
+    rep.ms_total = ms_total;
+    *out = rep;
+  }
+  void write(double ms_total, mcgpu_rooster4d_motion_report* out) const {
+    *out = {rep.ms_forward, rep.ms_back, rep.ms_cg_vectors, rep.ms_tv_space, rep.ms_tv_time, rep.ms_upload, ms_total,
             (unsigned long long)dev.peak, ms_warp, ms_upload_model};
   }
 };
@@ -756,85 +736,63 @@ struct Problem {
 // the checks of a mcgpu_rooster4d_motion that need no device: refused with -1 before any HIP call
 void read_motion(const char* fn, const mcgpu_rooster4d_motion* caller, int n_frames, mcgpu_rooster4d_motion& m) {
   mcgpu::read_options(fn, "mcgpu_rooster4d_motion", caller, m);
-  if (m.n_signal_dims < 1 || m.n_signal_dims > kWarpMaxK) refuse(fn, "n_signal_dims must lie in 1..4");
+  check_motion_k(fn, m.n_signal_dims);
   if (!m.to_reference_mean || !m.to_reference_coefficients || !m.from_reference_mean || !m.from_reference_coefficients)
     refuse(fn, "a motion model array is NULL");
   if (!m.delta_to || !m.delta_from) refuse(fn, "delta_to or delta_from is NULL");
-  for (size_t j = 0; j < (size_t)n_frames * m.n_signal_dims; ++j)  // NaN, infinite, or infinite once it is float32
-    if (!(std::fabs(m.delta_to[j]) <= (double)std::numeric_limits<float>::max()) || !(std::fabs(m.delta_from[j]) <= (double)std::numeric_limits<float>::max()))
-      refuse(fn, "delta is not finite");
+  check_delta(fn, m.delta_to, (size_t)n_frames * m.n_signal_dims);
+  check_delta(fn, m.delta_from, (size_t)n_frames * m.n_signal_dims);
+}
+
+void check_stage(const char* fn, int stage, int first, int last, const float* in, const float* out) {
+  if (stage < first || stage > last) refuse(fn, "unknown stage " + std::to_string(stage));
+  if (!in || !out) refuse(fn, "in or out is NULL");
+}
+
+// What the four entry points share: the options (and, with_motion, the motion struct) read and checked, the entry point's own
+// argument checks, then the host clock, Problem, init, the models, the body and the report.  Nothing before Problem touches HIP.
+template <class Report, class Check, class Body>
+int entry(const char* fn, const mcgpu_rooster4d_options* caller_o, bool with_motion, const mcgpu_rooster4d_motion* caller_m, Report* report, Check check, Body body) {
+  ABI_BEGIN
+  mcgpu_rooster4d_options o;
+  read_options(fn, caller_o, o);
+  mcgpu_rooster4d_motion m = {};
+  if (with_motion) read_motion(fn, caller_m, o.n_frames, m);
+  check();
+  const mcgpu::Stopwatch call;
+  Problem P(o);
+  P.init();
+  if (with_motion) P.upload_model(m);
+  body(P);
+  if (report) P.write(call.ms(), report);
+  return 0;
+  ABI_END
 }
 
 }  // namespace
 
-extern "C" int mcgpu_rooster4d_reconstruct(const mcgpu_rooster4d_options* caller_o, const float* projections, float* volume4d, mcgpu_rooster4d_report* report) {
-  ABI_BEGIN
-  mcgpu_rooster4d_options o;
-  read_options("mcgpu_rooster4d_reconstruct", caller_o, o);
-  if (!projections || !volume4d) refuse("mcgpu_rooster4d_reconstruct", "projections or volume is NULL");
-  const mcgpu::Stopwatch call;
-  Problem P(o);
-  P.init();
-  P.run(projections, volume4d);
-  P.rep.peak_device_bytes = P.dev.peak;
-  P.rep.ms_total = call.ms();
-  if (report) *report = P.rep;
-  return 0;
-  ABI_END
+extern "C" int mcgpu_rooster4d_reconstruct(const mcgpu_rooster4d_options* o, const float* projections, float* volume4d, mcgpu_rooster4d_report* report) {
+  const char* fn = "mcgpu_rooster4d_reconstruct";
+  return entry(fn, o, false, nullptr, report, [&] { if (!projections || !volume4d) refuse(fn, "projections or volume is NULL"); },
+               [&](Problem& P) { P.run(projections, volume4d); });
 }
 
-extern "C" int mcgpu_rooster4d_stage(const mcgpu_rooster4d_options* caller_o, int stage, const float* in, float* out, mcgpu_rooster4d_report* report) {
-  ABI_BEGIN
-  mcgpu_rooster4d_options o;
-  read_options("mcgpu_rooster4d_stage", caller_o, o);
-  if (stage < MCGPU_ROOSTER4D_STAGE_FORWARD || stage > MCGPU_ROOSTER4D_STAGE_TV_TIME) refuse("mcgpu_rooster4d_stage", "unknown stage " + std::to_string(stage));
-  if (!in || !out) refuse("mcgpu_rooster4d_stage", "in or out is NULL");
-  const mcgpu::Stopwatch call;
-  Problem P(o);
-  P.init();
-  P.stage(stage, in, out);
-  P.rep.peak_device_bytes = P.dev.peak;
-  P.rep.ms_total = call.ms();
-  if (report) *report = P.rep;
-  return 0;
-  ABI_END
+extern "C" int mcgpu_rooster4d_stage(const mcgpu_rooster4d_options* o, int stage, const float* in, float* out, mcgpu_rooster4d_report* report) {
+  const char* fn = "mcgpu_rooster4d_stage";
+  return entry(fn, o, false, nullptr, report, [&] { check_stage(fn, stage, MCGPU_ROOSTER4D_STAGE_FORWARD, MCGPU_ROOSTER4D_STAGE_TV_TIME, in, out); },
+               [&](Problem& P) { P.stage(stage, in, out); });
 }
 
-extern "C" int mcgpu_rooster4d_reconstruct_motion(const mcgpu_rooster4d_options* caller_o, const mcgpu_rooster4d_motion* caller_m, const float* projections,
-                                                  float* volume4d, mcgpu_rooster4d_motion_report* report) {
-  ABI_BEGIN
+extern "C" int mcgpu_rooster4d_reconstruct_motion(const mcgpu_rooster4d_options* o, const mcgpu_rooster4d_motion* m, const float* projections, float* volume4d,
+                                                  mcgpu_rooster4d_motion_report* report) {
   const char* fn = "mcgpu_rooster4d_reconstruct_motion";
-  mcgpu_rooster4d_options o;
-  read_options(fn, caller_o, o);
-  mcgpu_rooster4d_motion m;
-  read_motion(fn, caller_m, o.n_frames, m);
-  if (!projections || !volume4d) refuse(fn, "projections or volume is NULL");
-  const mcgpu::Stopwatch call;
-  Problem P(o);
-  P.init();
-  P.upload_model(m);
-  P.run(projections, volume4d);
-  if (report) *report = P.motion_report(call.ms());
-  return 0;
-  ABI_END
+  return entry(fn, o, true, m, report, [&] { if (!projections || !volume4d) refuse(fn, "projections or volume is NULL"); },
+               [&](Problem& P) { P.run(projections, volume4d); });
 }
 
-extern "C" int mcgpu_rooster4d_motion_stage(const mcgpu_rooster4d_options* caller_o, const mcgpu_rooster4d_motion* caller_m, int stage, const float* in, float* out,
+extern "C" int mcgpu_rooster4d_motion_stage(const mcgpu_rooster4d_options* o, const mcgpu_rooster4d_motion* m, int stage, const float* in, float* out,
                                             mcgpu_rooster4d_motion_report* report) {
-  ABI_BEGIN
   const char* fn = "mcgpu_rooster4d_motion_stage";
-  mcgpu_rooster4d_options o;
-  read_options(fn, caller_o, o);
-  mcgpu_rooster4d_motion m;
-  read_motion(fn, caller_m, o.n_frames, m);
-  if (stage < MCGPU_ROOSTER4D_MOTION_STAGE_WARP || stage > MCGPU_ROOSTER4D_MOTION_STAGE_TV_TIME_MOTION) refuse(fn, "unknown stage " + std::to_string(stage));
-  if (!in || !out) refuse(fn, "in or out is NULL");
-  const mcgpu::Stopwatch call;
-  Problem P(o);
-  P.init();
-  P.upload_model(m);
-  P.motion_stage(stage, in, out);
-  if (report) *report = P.motion_report(call.ms());
-  return 0;
-  ABI_END
+  return entry(fn, o, true, m, report, [&] { check_stage(fn, stage, MCGPU_ROOSTER4D_MOTION_STAGE_WARP, MCGPU_ROOSTER4D_MOTION_STAGE_TV_TIME_MOTION, in, out); },
+               [&](Problem& P) { P.motion_stage(stage, in, out); });
 }

@@ -102,6 +102,9 @@ def save_geometry(geometry: CircularGeometry, output_filepath) -> Path:
     return geometry.write(output_filepath)
 
 
+_DP, _FP = C.POINTER(C.c_double), C.POINTER(C.c_float)
+
+
 class _FdkOptions(C.Structure):
     _fields_ = [("struct_size", C.c_uint), ("n_proj", C.c_int), ("nu", C.c_int), ("nv", C.c_int), ("du", C.c_double), ("dv", C.c_double), ("u0", C.c_double), ("v0", C.c_double),
                 ("sid", C.c_double), ("sdd", C.c_double), ("gantry_deg", C.POINTER(C.c_double)), ("proj_offset_x", C.POINTER(C.c_double)),
@@ -114,6 +117,49 @@ class _FdkReport(C.Structure):
     _fields_ = [("ms_filter", C.c_double), ("ms_backproject", C.c_double)]
 
 
+_bound = None  # the library whose prototypes _library() has declared
+
+
+def _library():
+    """The engine's library with the prototypes of this module's entry points declared, once per loaded library."""
+    global _bound
+    from . import engine
+    lib = engine.load_library()
+    if lib is not _bound:
+        P, vp, ci = C.POINTER, C.c_void_p, C.c_int
+        fo, ro, rm, rr, rmr = P(_FdkOptions), P(_RoosterOptions), P(_RoosterMotion), P(_RoosterReport), P(_RoosterMotionReport)
+        for name, argtypes in dict(mcgpu_fdk_reconstruct=[fo, vp, vp, P(_FdkReport)], mcgpu_fdk_reconstruct_motion=[fo, P(_FdkMotion), vp, vp, P(_FdkMotionReport)],
+                                   mcgpu_rooster4d_reconstruct=[ro, vp, vp, rr], mcgpu_rooster4d_stage=[ro, ci, vp, vp, rr],
+                                   mcgpu_rooster4d_reconstruct_motion=[ro, rm, vp, vp, rmr], mcgpu_rooster4d_motion_stage=[ro, rm, ci, vp, vp, rmr]).items():
+            getattr(lib, name).argtypes, getattr(lib, name).restype = argtypes, ci
+        _bound = lib
+    return lib
+
+
+def _report_dict(rep) -> dict:
+    return {name: getattr(rep, name) for name, _ in rep._fields_}
+
+
+def _volume(dimension, frames=None) -> np.ndarray:
+    """Zeros [nz, ny, nx], or [frames, nz, ny, nx], float32."""
+    shape = (int(dimension[2]), int(dimension[1]), int(dimension[0]))
+    return np.zeros(shape if frames is None else (int(frames),) + shape, dtype=np.float32)
+
+
+def _geometry_fields(n, nu, nv, geometry, pixel_spacing, pixel_origin, dimension, spacing, origin):
+    """What mcgpu_fdk_options and mcgpu_rooster4d_options share: the 21 fields n_proj .. oz that follow struct_size, in order, and the
+    arrays they point into.  No pixel origin: the detector is centred; no volume origin: NaN, which the library reads as centred."""
+    if n != len(geometry.gantry_angles):
+        raise ValueError(f"{n} projections but {len(geometry.gantry_angles)} geometry entries")
+    du, dv = float(pixel_spacing[0]), float(pixel_spacing[1])
+    u0, v0 = pixel_origin if pixel_origin is not None else (-(nu - 1) / 2 * du, -(nv - 1) / 2 * dv)
+    arrays = tuple(np.ascontiguousarray(a, dtype=np.float64) for a in (geometry.gantry_angles, geometry.projection_offsets_x, geometry.projection_offsets_y))
+    fields = (int(n), int(nu), int(nv), du, dv, float(u0), float(v0), float(geometry.source_to_isocenter), float(geometry.source_to_detector),
+              *(a.ctypes.data_as(_DP) for a in arrays), int(dimension[0]), int(dimension[1]), int(dimension[2]),
+              float(spacing[0]), float(spacing[1]), float(spacing[2]), *(tuple(float(v) for v in origin) if origin is not None else (float("nan"),) * 3))
+    return fields, arrays
+
+
 def fdk(projections: np.ndarray, geometry: CircularGeometry, pixel_spacing: Tuple[float, float], pixel_origin: Optional[Tuple[float, float]] = None,
         dimension: Tuple[int, int, int] = (464, 250, 464), spacing: Tuple[float, float, float] = (1.0, 1.0, 1.0),
         origin: Optional[Tuple[float, float, float]] = None, hann: float = 0.0, hann_y: float = 0.0,
@@ -124,35 +170,22 @@ def fdk(projections: np.ndarray, geometry: CircularGeometry, pixel_spacing: Tupl
     mirror limited by the zero extension) could not be checked against RTK here -- on a truncated half-fan scan the feathered edge
     may differ from rtkfdk's (parity unpinned)."""
     from . import engine
-    lib = engine.load_library()
-    lib.mcgpu_fdk_reconstruct.argtypes = [C.POINTER(_FdkOptions), C.c_void_p, C.c_void_p, C.POINTER(_FdkReport)]
-    lib.mcgpu_fdk_reconstruct.restype = C.c_int
+    lib = _library()
     p, o, keep = _fdk_options(projections, geometry, pixel_spacing, pixel_origin, dimension, spacing, origin, hann, hann_y, water_pre_correction, gpu_id, pad)
-    vol = np.zeros((int(dimension[2]), int(dimension[1]), int(dimension[0])), dtype=np.float32)
-    rep = _FdkReport()
+    vol, rep = _volume(dimension), _FdkReport()
     engine._check(lib.mcgpu_fdk_reconstruct(C.byref(o), p.ctypes.data, vol.ctypes.data, C.byref(rep)))
-    return vol, {"ms_filter": rep.ms_filter, "ms_backproject": rep.ms_backproject}
+    return vol, _report_dict(rep)
 
 
 def _fdk_options(projections, geometry, pixel_spacing, pixel_origin, dimension, spacing, origin, hann, hann_y, water_pre_correction, gpu_id, pad):
     """(float32 stack, mcgpu_fdk_options, the arrays it points into) of fdk() and fdk_motion()."""
     p = np.ascontiguousarray(projections, dtype=np.float32)
     n, nv, nu = p.shape
-    if n != len(geometry.gantry_angles):
-        raise ValueError(f"{n} projections but {len(geometry.gantry_angles)} geometry entries")
-    du, dv = float(pixel_spacing[0]), float(pixel_spacing[1])
-    u0, v0 = pixel_origin if pixel_origin is not None else (-(nu - 1) / 2 * du, -(nv - 1) / 2 * dv)
-    ang = np.ascontiguousarray(geometry.gantry_angles, dtype=np.float64)
-    ox = np.ascontiguousarray(geometry.projection_offsets_x, dtype=np.float64)
-    oy = np.ascontiguousarray(geometry.projection_offsets_y, dtype=np.float64)
+    fields, arrays = _geometry_fields(n, nu, nv, geometry, pixel_spacing, pixel_origin, dimension, spacing, origin)
     wpc = np.ascontiguousarray(water_pre_correction if water_pre_correction is not None else [], dtype=np.float64)
-    dp = C.POINTER(C.c_double)
-    o = _FdkOptions(C.sizeof(_FdkOptions), n, nu, nv, du, dv, float(u0), float(v0), float(geometry.source_to_isocenter), float(geometry.source_to_detector),
-                    ang.ctypes.data_as(dp), ox.ctypes.data_as(dp), oy.ctypes.data_as(dp), int(dimension[0]), int(dimension[1]), int(dimension[2]),
-                    float(spacing[0]), float(spacing[1]), float(spacing[2]),
-                    *(tuple(float(v) for v in origin) if origin is not None else (float("nan"),) * 3), float(hann), float(hann_y),
-                    wpc.ctypes.data_as(dp) if wpc.size else None, int(wpc.size), int(gpu_id), float(pad))
-    return p, o, (ang, ox, oy, wpc)
+    o = _FdkOptions(C.sizeof(_FdkOptions), *fields, float(hann), float(hann_y), wpc.ctypes.data_as(_DP) if wpc.size else None, int(wpc.size), int(gpu_id),
+                    float(pad))
+    return p, o, arrays + (wpc,)
 
 
 # ------------------------------------------------------------------------------------------------ motion-compensated FDK
@@ -170,13 +203,10 @@ class _FdkMotionReport(C.Structure):
 
 
 class MotionModel:
-    """A linear motion model on the FDK grid (csrc/fdk.hip states the rule): for the voxel at P of the
-    reference-phase volume and a breathing state with signal s, the material of that voxel is at
-    P + mean(P) + sum_k coefficients[k](P) (s[k] - mean_signal[k]).
-
-    mean [3, nz, ny, nx] float32 in mm, components along IEC X, Y, Z; coefficients [K, 3, nz, ny, nx] float32 in mm per signal unit,
-    1 <= K <= 4; mean_signal [K] float64.  dimension = (nx, ny, nz); spacing (mm, optional) is what from_correspondence_model
-    derived the grid's from, and fdk_motion refuses another one."""
+    """A linear motion model on the FDK grid: mean [3, nz, ny, nx], coefficients [K, 3, nz, ny, nx] (both float32) and mean_signal
+    [K] float64.  csrc/motion_model.inc states the layout and the displacement rule; what a displacement means is its user's
+    (fdk_motion: where the material of a reference-phase voxel is; rooster4d_motion: one model each way).  dimension = (nx, ny, nz);
+    spacing (mm, optional) is what from_correspondence_model derived the grid's from, and fdk_motion refuses another one."""
 
     def __init__(self, mean, coefficients, mean_signal, spacing=None):
         self.mean = np.ascontiguousarray(mean, dtype=np.float32)
@@ -199,6 +229,10 @@ class MotionModel:
     @property
     def dimension(self) -> Tuple[int, int, int]:
         return tuple(int(n) for n in self.mean.shape[:0:-1])
+
+    def pointers(self):
+        """(mean, coefficients) as the float pointers of mcgpu_fdk_motion and mcgpu_rooster4d_motion."""
+        return self.mean.ctypes.data_as(_FP), self.coefficients.ctypes.data_as(_FP)
 
     def check_grid(self, dimension, spacing):
         """ValueError unless (dimension, spacing) is the grid the model lives on: a model is not resampled."""
@@ -264,9 +298,7 @@ def fdk_motion(projections: np.ndarray, geometry: CircularGeometry, pixel_spacin
     live on the reconstruction grid (ValueError otherwise) and map the reference phase forward (MotionModel.from_correspondence_model).
     Parity against RTK's warp back-projector is unpinned (RTK is absent here); tests/fdk_motion_ref.py restates the rule in float64."""
     from . import engine
-    lib = engine.load_library()
-    lib.mcgpu_fdk_reconstruct_motion.argtypes = [C.POINTER(_FdkOptions), C.POINTER(_FdkMotion), C.c_void_p, C.c_void_p, C.POINTER(_FdkMotionReport)]
-    lib.mcgpu_fdk_reconstruct_motion.restype = C.c_int
+    lib = _library()
     motion.check_grid(dimension, spacing)
     p, o, keep = _fdk_options(projections, geometry, pixel_spacing, pixel_origin, dimension, spacing, origin, hann, hann_y, water_pre_correction, gpu_id, pad)
     delta = motion.delta(signals)
@@ -274,13 +306,10 @@ def fdk_motion(projections: np.ndarray, geometry: CircularGeometry, pixel_spacin
         raise ValueError(f"{p.shape[0]} projections but {delta.shape[0]} signals")
     if not np.isfinite(delta).all():
         raise ValueError("the signals are not finite")
-    fp = C.POINTER(C.c_float)
-    m = _FdkMotion(C.sizeof(_FdkMotion), motion.n_signal_dims, motion.mean.ctypes.data_as(fp), motion.coefficients.ctypes.data_as(fp),
-                   delta.ctypes.data_as(C.POINTER(C.c_double)))
-    vol = np.zeros((int(dimension[2]), int(dimension[1]), int(dimension[0])), dtype=np.float32)
-    rep = _FdkMotionReport()
+    m = _FdkMotion(C.sizeof(_FdkMotion), motion.n_signal_dims, *motion.pointers(), delta.ctypes.data_as(_DP))
+    vol, rep = _volume(dimension), _FdkMotionReport()
     engine._check(lib.mcgpu_fdk_reconstruct_motion(C.byref(o), C.byref(m), p.ctypes.data, vol.ctypes.data, C.byref(rep)))
-    return vol, {name: getattr(rep, name) for name, _ in _FdkMotionReport._fields_}
+    return vol, _report_dict(rep)
 
 
 _MHA_ELEMENT_TYPES = {"MET_FLOAT": "<f4", "MET_SHORT": "<i2", "MET_UCHAR": "u1"}
@@ -337,6 +366,30 @@ def write_mha(path, volume: np.ndarray, spacing, origin, element_type: str = "ME
     return path
 
 
+def _reconstruct_to_file(projections_filepath, geometry_filepath, output_folder, output_filename, dimension, spacing, water_pre_correction, compute, record):
+    """The file flow of the four reconstruct_* functions: stack (.mha) + RTK geometry (.xml) in; compute(projections, geometry, pixel
+    spacing, pixel origin) -> (volume, report); the volume out at the centred origin (a 4-D one with spacing 1 and offset 0 along
+    the frames) and, next to it, a .yaml of what every flow records plus `record`.  -> (path of the volume, report)."""
+    projections_filepath, geometry_filepath = Path(projections_filepath), Path(geometry_filepath)
+    output_folder = Path(output_folder) if output_folder else projections_filepath.parent / "reconstructions"
+    out = output_folder / output_filename
+    output_folder.mkdir(parents=True, exist_ok=True)
+    proj, pspacing, porigin = read_mha(projections_filepath)
+    geometry = CircularGeometry.read(geometry_filepath)
+    vol, report = compute(proj, geometry, (pspacing[0], pspacing[1]), (porigin[0], porigin[1]))
+    origin = tuple(-(n - 1) / 2 * s for n, s in zip(dimension, spacing))
+    if vol.ndim == 4:
+        write_mha(out, vol, tuple(spacing) + (1.0,), origin + (0.0,))
+    else:
+        write_mha(out, vol, spacing, origin)
+    import yaml
+    with open(out.with_suffix(".yaml"), "w") as f:
+        yaml.dump(dict(path=str(projections_filepath.parent), regexp=projections_filepath.name, geometry=str(geometry_filepath), hardware="hip",
+                       dimension=list(dimension), spacing=list(spacing), wpc=list(water_pre_correction) if water_pre_correction is not None else None,
+                       output_filepath=str(out), **record), f)
+    return out, report
+
+
 def reconstruct_3d(projections_filepath, geometry_filepath, output_folder=None, output_filename: Optional[str] = None,
                    dimension: Tuple[int, int, int] = (464, 250, 464), spacing: Tuple[float, float, float] = (1.0, 1.0, 1.0), pad: float = 1.0,
                    hann: float = 1.0, hann_y: float = 1.0, water_pre_correction: Optional[Sequence[float]] = None, gpu_id: int = 0, **kwargs):
@@ -351,24 +404,10 @@ def reconstruct_3d(projections_filepath, geometry_filepath, output_folder=None, 
     columns with the feathered point reflection of the data before the ramp; csrc/fdk.hip: extend_rows_kernel, restated in
     oracle/fdk_oracle.py: truncation_extension).  Parity against RTK itself is unpinned (RTK is absent here; DESIGN.md
     section 2): the restatement is pinned by an analytic truncated cylinder (tests/test_fdk.py)."""
-    projections_filepath, geometry_filepath = Path(projections_filepath), Path(geometry_filepath)
-    output_folder = Path(output_folder) if output_folder else projections_filepath.parent / "reconstructions"
-    output_filename = output_filename or "recon_fdk3d.mha"
-    output_folder.mkdir(parents=True, exist_ok=True)
-    proj, pspacing, porigin = read_mha(projections_filepath)
-    geometry = CircularGeometry.read(geometry_filepath)
-    vol, report = fdk(proj, geometry, (pspacing[0], pspacing[1]), (porigin[0], porigin[1]), dimension, spacing, None, hann, hann_y,
-                      water_pre_correction, gpu_id, pad=pad)
-    origin = tuple(-(n - 1) / 2 * s for n, s in zip(dimension, spacing))
-    write_mha(output_folder / output_filename, vol, spacing, origin)
-    import yaml
-    params = dict(path=str(projections_filepath.parent), regexp=projections_filepath.name, geometry=str(geometry_filepath), hardware="hip", pad=pad,
-                  hann=hann, hannY=hann_y, dimension=list(dimension), spacing=list(spacing),
-                  wpc=list(water_pre_correction) if water_pre_correction is not None else None, short=360,
-                  output_filepath=str(output_folder / output_filename), **kwargs)
-    with open((output_folder / output_filename).with_suffix(".yaml"), "w") as f:
-        yaml.dump(params, f)
-    return output_folder / output_filename, report
+    return _reconstruct_to_file(
+        projections_filepath, geometry_filepath, output_folder, output_filename or "recon_fdk3d.mha", dimension, spacing, water_pre_correction,
+        lambda proj, geometry, ds, org: fdk(proj, geometry, ds, org, dimension, spacing, None, hann, hann_y, water_pre_correction, gpu_id, pad=pad),
+        dict(pad=pad, hann=hann, hannY=hann_y, short=360, **kwargs))
 
 
 def reconstruct_3d_mc(projections_filepath, geometry_filepath, correspondence_model, signals, voxel_spacing_mm, output_folder=None,
@@ -380,26 +419,12 @@ def reconstruct_3d_mc(projections_filepath, geometry_filepath, correspondence_mo
     MotionModel.from_correspondence_model for the direction and the frame); voxel_spacing_mm: the spacing of the MCGeometry its
     fields live on; signals [n, K]: the breathing signal of every projection, in the model's units.  Writes `recon_fdk3d_mc.mha`
     and a .yaml that also records `motion` (the first 7 hex digits of the model's hash) and `signal_n_dims` (K)."""
-    projections_filepath, geometry_filepath = Path(projections_filepath), Path(geometry_filepath)
-    output_folder = Path(output_folder) if output_folder else projections_filepath.parent / "reconstructions"
-    output_filename = output_filename or "recon_fdk3d_mc.mha"
     motion = MotionModel.from_correspondence_model(correspondence_model, voxel_spacing_mm, dimension=dimension, spacing=spacing)
-    output_folder.mkdir(parents=True, exist_ok=True)
-    proj, pspacing, porigin = read_mha(projections_filepath)
-    geometry = CircularGeometry.read(geometry_filepath)
-    vol, report = fdk_motion(proj, geometry, (pspacing[0], pspacing[1]), (porigin[0], porigin[1]), motion, signals, dimension, spacing, None, hann, hann_y,
-                             water_pre_correction, gpu_id, pad=pad)
-    origin = tuple(-(n - 1) / 2 * s for n, s in zip(dimension, spacing))
-    write_mha(output_folder / output_filename, vol, spacing, origin)
-    import yaml
-    params = dict(path=str(projections_filepath.parent), regexp=projections_filepath.name, geometry=str(geometry_filepath), hardware="hip", pad=pad,
-                  hann=hann, hannY=hann_y, dimension=list(dimension), spacing=list(spacing),
-                  wpc=list(water_pre_correction) if water_pre_correction is not None else None, short=360,
-                  motion=correspondence_model.model_hash[:7], signal_n_dims=motion.n_signal_dims,
-                  output_filepath=str(output_folder / output_filename), **kwargs)
-    with open((output_folder / output_filename).with_suffix(".yaml"), "w") as f:
-        yaml.dump(params, f)
-    return output_folder / output_filename, report
+    return _reconstruct_to_file(
+        projections_filepath, geometry_filepath, output_folder, output_filename or "recon_fdk3d_mc.mha", dimension, spacing, water_pre_correction,
+        lambda proj, geometry, ds, org: fdk_motion(proj, geometry, ds, org, motion, signals, dimension, spacing, None, hann, hann_y, water_pre_correction,
+                                                   gpu_id, pad=pad),
+        dict(pad=pad, hann=hann, hannY=hann_y, short=360, motion=correspondence_model.model_hash[:7], signal_n_dims=motion.n_signal_dims, **kwargs))
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4-D ROOSTER
@@ -424,35 +449,23 @@ ROOSTER4D_STAGES = {"forward": 0, "back": 1, "tv_space": 2, "tv_time": 3}
 
 def _rooster_call(n_proj, nu, nv, geometry, pixel_spacing, pixel_origin, phase, dimension, spacing, origin, frames, niter, cgiter, tviter,
                   gamma_time, gamma_space, water_pre_correction, positivity, gpu_id):
-    """(options, the arrays it points into) for mcgpu_rooster4d_*."""
-    from . import engine
-    lib = engine.load_library()
-    lib.mcgpu_rooster4d_reconstruct.argtypes = [C.POINTER(_RoosterOptions), C.c_void_p, C.c_void_p, C.POINTER(_RoosterReport)]
-    lib.mcgpu_rooster4d_stage.argtypes = [C.POINTER(_RoosterOptions), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(_RoosterReport)]
-    if n_proj != len(geometry.gantry_angles):
-        raise ValueError(f"{n_proj} projections but {len(geometry.gantry_angles)} geometry entries")
+    """(library, options, the arrays it points into) for mcgpu_rooster4d_*."""
+    lib = _library()
+    fields, arrays = _geometry_fields(n_proj, nu, nv, geometry, pixel_spacing, pixel_origin, dimension, spacing, origin)
     ph = np.ascontiguousarray(phase, dtype=np.float64).ravel()
     if ph.size != n_proj:
         raise ValueError(f"{n_proj} projections but {ph.size} phase values")
-    du, dv = float(pixel_spacing[0]), float(pixel_spacing[1])
-    u0, v0 = pixel_origin if pixel_origin is not None else (-(nu - 1) / 2 * du, -(nv - 1) / 2 * dv)
-    keep = dict(ang=np.ascontiguousarray(geometry.gantry_angles, dtype=np.float64), ox=np.ascontiguousarray(geometry.projection_offsets_x, dtype=np.float64),
-                oy=np.ascontiguousarray(geometry.projection_offsets_y, dtype=np.float64), phase=ph,
-                wpc=np.ascontiguousarray(water_pre_correction if water_pre_correction is not None else [], dtype=np.float64),
+    keep = dict(geometry=arrays, phase=ph, wpc=np.ascontiguousarray(water_pre_correction if water_pre_correction is not None else [], dtype=np.float64),
                 residuals=np.zeros(max(int(niter), 0) * (max(int(cgiter), 0) + 1), dtype=np.float64))
-    dp = C.POINTER(C.c_double)
-    o = _RoosterOptions(C.sizeof(_RoosterOptions), int(n_proj), int(nu), int(nv), du, dv, float(u0), float(v0), float(geometry.source_to_isocenter),
-                        float(geometry.source_to_detector), keep["ang"].ctypes.data_as(dp), keep["ox"].ctypes.data_as(dp), keep["oy"].ctypes.data_as(dp),
-                        int(dimension[0]), int(dimension[1]), int(dimension[2]), float(spacing[0]), float(spacing[1]), float(spacing[2]),
-                        *(tuple(float(v) for v in origin) if origin is not None else (float("nan"),) * 3), int(frames), keep["phase"].ctypes.data_as(dp),
-                        int(niter), int(cgiter), int(tviter), float(gamma_space), float(gamma_time), int(bool(positivity)),
-                        keep["wpc"].ctypes.data_as(dp) if keep["wpc"].size else None, int(keep["wpc"].size), int(gpu_id),
-                        keep["residuals"].ctypes.data_as(dp) if keep["residuals"].size else None)
+    o = _RoosterOptions(C.sizeof(_RoosterOptions), *fields, int(frames), ph.ctypes.data_as(_DP), int(niter), int(cgiter), int(tviter), float(gamma_space),
+                        float(gamma_time), int(bool(positivity)), keep["wpc"].ctypes.data_as(_DP) if keep["wpc"].size else None, int(keep["wpc"].size),
+                        int(gpu_id), keep["residuals"].ctypes.data_as(_DP) if keep["residuals"].size else None)
     return lib, o, keep
 
 
-def _rooster_report(rep: _RoosterReport) -> dict:
-    return {name: getattr(rep, name) for name, _ in _RoosterReport._fields_}
+def _rooster_result(rep, keep, niter, cgiter, **more) -> dict:
+    """The report dict of a whole reconstruction: the report's fields, residuals [niter][cgiter + 1] and `more`."""
+    return dict(_report_dict(rep), residuals=keep["residuals"].reshape(max(int(niter), 0), max(int(cgiter), 0) + 1).copy(), **more)
 
 
 def rooster4d(projections: np.ndarray, geometry: CircularGeometry, pixel_spacing: Tuple[float, float], pixel_origin: Optional[Tuple[float, float]],
@@ -480,12 +493,9 @@ def rooster4d(projections: np.ndarray, geometry: CircularGeometry, pixel_spacing
     n, nv, nu = p.shape
     lib, o, keep = _rooster_call(n, nu, nv, geometry, pixel_spacing, pixel_origin, phase, dimension, spacing, origin, frames, niter, cgiter, tviter,
                                  gamma_time, gamma_space, water_pre_correction, positivity, gpu_id)
-    vol = np.zeros((int(frames), int(dimension[2]), int(dimension[1]), int(dimension[0])), dtype=np.float32)
-    rep = _RoosterReport()
+    vol, rep = _volume(dimension, frames), _RoosterReport()
     engine._check(lib.mcgpu_rooster4d_reconstruct(C.byref(o), p.ctypes.data, vol.ctypes.data, C.byref(rep)))
-    out = _rooster_report(rep)
-    out["residuals"] = keep["residuals"].reshape(max(int(niter), 0), max(int(cgiter), 0) + 1).copy()
-    return vol, out
+    return vol, _rooster_result(rep, keep, niter, cgiter)
 
 
 def rooster4d_stage(stage: str, data: np.ndarray, geometry: CircularGeometry, detector: Tuple[int, int], pixel_spacing, pixel_origin, phase,
@@ -503,10 +513,9 @@ def rooster4d_stage(stage: str, data: np.ndarray, geometry: CircularGeometry, de
     src = np.ascontiguousarray(data, dtype=np.float32)
     if src.shape != ((n, nv, nu) if stage == "back" else shape4):
         raise ValueError(f"rooster4d_stage {stage}: input shape {src.shape}")
-    out = np.zeros((n, nv, nu) if stage == "forward" else shape4, dtype=np.float32)
-    rep = _RoosterReport()
+    out, rep = np.zeros((n, nv, nu) if stage == "forward" else shape4, dtype=np.float32), _RoosterReport()
     engine._check(lib.mcgpu_rooster4d_stage(C.byref(o), code, src.ctypes.data, out.ctypes.data, C.byref(rep)))
-    return out, _rooster_report(rep)
+    return out, _report_dict(rep)
 
 
 def _unit_phase(amplitude_signal, phase_signal) -> np.ndarray:
@@ -537,26 +546,19 @@ def reconstruct_4d(projections_filepath, geometry_filepath, output_folder=None, 
     MetaImage [frames][nz][ny][nx] with spacing (sx, sy, sz, 1) and offset (ox, oy, oz, 0) in the frame of reconstruct_3d's
     output, and a .yaml of the parameters next to it (fp / bp record what ran: Joseph / VoxelBased)."""
     ph = _unit_phase(amplitude_signal, phase_signal)
-    projections_filepath, geometry_filepath = Path(projections_filepath), Path(geometry_filepath)
-    output_folder = Path(output_folder) if output_folder else projections_filepath.parent / "reconstructions"
-    output_filename = output_filename or "recon_rooster4d.mha"
-    output_folder.mkdir(parents=True, exist_ok=True)
+    params = _rooster_parameters(kwargs)
+    return _reconstruct_to_file(
+        projections_filepath, geometry_filepath, output_folder, output_filename or "recon_rooster4d.mha", dimension, spacing, water_pre_correction,
+        lambda proj, geometry, ds, org: rooster4d(proj, geometry, ds, org, ph, dimension, spacing, None, water_pre_correction=water_pre_correction,
+                                                  gpu_id=gpu_id, **params),
+        dict(fp="Joseph", bp="VoxelBased", **params, **kwargs))
+
+
+def _rooster_parameters(kwargs) -> dict:
+    """The reference's ROOSTER parameters, each replaced by the keyword argument of its name, which is taken out of `kwargs`."""
     params = dict(niter=10, cgiter=4, tviter=10, gamma_time=0.0002, gamma_space=0.00007, frames=10, positivity=True)
     params.update({k: kwargs.pop(k) for k in list(kwargs) if k in params})
-    proj, pspacing, porigin = read_mha(projections_filepath)
-    geometry = CircularGeometry.read(geometry_filepath)
-    vol, report = rooster4d(proj, geometry, (pspacing[0], pspacing[1]), (porigin[0], porigin[1]), ph, dimension, spacing, None,
-                            water_pre_correction=water_pre_correction, gpu_id=gpu_id, **params)
-    origin = tuple(-(n - 1) / 2 * s for n, s in zip(dimension, spacing))
-    out = output_folder / output_filename
-    write_mha(out, vol, tuple(spacing) + (1.0,), origin + (0.0,))
-    import yaml
-    record = dict(path=str(projections_filepath.parent), regexp=projections_filepath.name, geometry=str(geometry_filepath), fp="Joseph",
-                  bp="VoxelBased", hardware="hip", dimension=list(dimension), spacing=list(spacing),
-                  wpc=list(water_pre_correction) if water_pre_correction is not None else None, output_filepath=str(out), **params, **kwargs)
-    with open(out.with_suffix(".yaml"), "w") as f:
-        yaml.dump(record, f)
-    return out, report
+    return params
 
 
 # ------------------------------------------------------------------------------------------------ motion-aware 4-D ROOSTER
@@ -606,11 +608,8 @@ def frame_signals(phase, signals, frames: int) -> np.ndarray:
 
 
 def _rooster_motion(lib, frames, dimension, spacing, motion_to_reference: MotionModel, motion_from_reference: MotionModel, states):
-    """(mcgpu_rooster4d_motion, the arrays it points into) for the frame states [frames, K]."""
-    lib.mcgpu_rooster4d_reconstruct_motion.argtypes = [C.POINTER(_RoosterOptions), C.POINTER(_RoosterMotion), C.c_void_p, C.c_void_p,
-                                                       C.POINTER(_RoosterMotionReport)]
-    lib.mcgpu_rooster4d_motion_stage.argtypes = [C.POINTER(_RoosterOptions), C.POINTER(_RoosterMotion), C.c_int, C.c_void_p, C.c_void_p,
-                                                 C.POINTER(_RoosterMotionReport)]
+    """(mcgpu_rooster4d_motion, the arrays it points into) for the frame states [frames, K].  lib: what _rooster_call returned (callers
+    pass it since this function declared the motion prototypes; _library() does now)."""
     motion_to_reference.check_grid(dimension, spacing)
     motion_from_reference.check_grid(dimension, spacing)
     if motion_to_reference.n_signal_dims != motion_from_reference.n_signal_dims:
@@ -621,10 +620,8 @@ def _rooster_motion(lib, frames, dimension, spacing, motion_to_reference: Motion
         raise ValueError(f"{int(frames)} frames but {delta_to.shape[0]} frame states")
     if not (np.isfinite(delta_to).all() and np.isfinite(delta_from).all()):
         raise ValueError("the signals are not finite")
-    fp, dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
-    m = _RoosterMotion(C.sizeof(_RoosterMotion), motion_to_reference.n_signal_dims, motion_to_reference.mean.ctypes.data_as(fp),
-                       motion_to_reference.coefficients.ctypes.data_as(fp), motion_from_reference.mean.ctypes.data_as(fp),
-                       motion_from_reference.coefficients.ctypes.data_as(fp), delta_to.ctypes.data_as(dp), delta_from.ctypes.data_as(dp))
+    m = _RoosterMotion(C.sizeof(_RoosterMotion), motion_to_reference.n_signal_dims, *motion_to_reference.pointers(), *motion_from_reference.pointers(),
+                       delta_to.ctypes.data_as(_DP), delta_from.ctypes.data_as(_DP))
     return m, (delta_to, delta_from)
 
 
@@ -664,13 +661,9 @@ def rooster4d_motion(projections: np.ndarray, geometry: CircularGeometry, pixel_
         raise ValueError(f"{n} projections but {s.shape[0]} signals")
     states = frame_signals(keep["phase"], s, frames)
     m, keep_m = _rooster_motion(lib, frames, dimension, spacing, motion_to_reference, motion_from_reference, states)
-    vol = np.zeros((int(frames), int(dimension[2]), int(dimension[1]), int(dimension[0])), dtype=np.float32)
-    rep = _RoosterMotionReport()
+    vol, rep = _volume(dimension, frames), _RoosterMotionReport()
     engine._check(lib.mcgpu_rooster4d_reconstruct_motion(C.byref(o), C.byref(m), p.ctypes.data, vol.ctypes.data, C.byref(rep)))
-    out = {name: getattr(rep, name) for name, _ in _RoosterMotionReport._fields_}
-    out["residuals"] = keep["residuals"].reshape(max(int(niter), 0), max(int(cgiter), 0) + 1).copy()
-    out["frame_signals"] = states
-    return vol, out
+    return vol, _rooster_result(rep, keep, niter, cgiter, frame_signals=states)
 
 
 def rooster4d_motion_stage(stage: str, data: np.ndarray, motion_to_reference: MotionModel, motion_from_reference: MotionModel, frame_states,
@@ -689,10 +682,9 @@ def rooster4d_motion_stage(stage: str, data: np.ndarray, motion_to_reference: Mo
     lib, o, keep = _rooster_call(1, 2, 2, placeholder, (1.0, 1.0), None, [0.0], dimension, spacing, None, frames, 0, 0, tviter, gamma_time, 0.0,
                                  None, True, gpu_id)
     m, keep_m = _rooster_motion(lib, frames, dimension, spacing, motion_to_reference, motion_from_reference, frame_states)
-    out = np.zeros(shape4, dtype=np.float32)
-    rep = _RoosterMotionReport()
+    out, rep = np.zeros(shape4, dtype=np.float32), _RoosterMotionReport()
     engine._check(lib.mcgpu_rooster4d_motion_stage(C.byref(o), C.byref(m), ROOSTER4D_MOTION_STAGES[stage], src.ctypes.data, out.ctypes.data, C.byref(rep)))
-    return out, {name: getattr(rep, name) for name, _ in _RoosterMotionReport._fields_}
+    return out, _report_dict(rep)
 
 
 def reconstruct_4d_mc(projections_filepath, geometry_filepath, model_to_reference, model_from_reference, signals, voxel_spacing_mm,
@@ -709,27 +701,12 @@ def reconstruct_4d_mc(projections_filepath, geometry_filepath, model_to_referenc
     `recon_rooster4d_mc.mha` (4-D, as reconstruct_4d) and a .yaml that also records `motion_to_reference` / `motion_from_reference`
     (the first 7 hex digits of each model's hash), `signal_n_dims` (K) and `temporal_update: increment`."""
     ph = _unit_phase(amplitude_signal, phase_signal)
-    projections_filepath, geometry_filepath = Path(projections_filepath), Path(geometry_filepath)
-    output_folder = Path(output_folder) if output_folder else projections_filepath.parent / "reconstructions"
-    output_filename = output_filename or "recon_rooster4d_mc.mha"
     to_reference = MotionModel.from_correspondence_model(model_to_reference, voxel_spacing_mm, dimension=dimension, spacing=spacing)
     from_reference = MotionModel.from_correspondence_model(model_from_reference, voxel_spacing_mm, dimension=dimension, spacing=spacing)
-    output_folder.mkdir(parents=True, exist_ok=True)
-    params = dict(niter=10, cgiter=4, tviter=10, gamma_time=0.0002, gamma_space=0.00007, frames=10, positivity=True)
-    params.update({k: kwargs.pop(k) for k in list(kwargs) if k in params})
-    proj, pspacing, porigin = read_mha(projections_filepath)
-    geometry = CircularGeometry.read(geometry_filepath)
-    vol, report = rooster4d_motion(proj, geometry, (pspacing[0], pspacing[1]), (porigin[0], porigin[1]), ph, to_reference, from_reference, signals,
-                                   dimension, spacing, None, water_pre_correction=water_pre_correction, gpu_id=gpu_id, **params)
-    origin = tuple(-(n - 1) / 2 * s for n, s in zip(dimension, spacing))
-    out = output_folder / output_filename
-    write_mha(out, vol, tuple(spacing) + (1.0,), origin + (0.0,))
-    import yaml
-    record = dict(path=str(projections_filepath.parent), regexp=projections_filepath.name, geometry=str(geometry_filepath), fp="Joseph",
-                  bp="VoxelBased", hardware="hip", dimension=list(dimension), spacing=list(spacing),
-                  wpc=list(water_pre_correction) if water_pre_correction is not None else None, output_filepath=str(out),
-                  motion_to_reference=model_to_reference.model_hash[:7], motion_from_reference=model_from_reference.model_hash[:7],
-                  signal_n_dims=to_reference.n_signal_dims, temporal_update="increment", **params, **kwargs)
-    with open(out.with_suffix(".yaml"), "w") as f:
-        yaml.dump(record, f)
-    return out, report
+    params = _rooster_parameters(kwargs)
+    return _reconstruct_to_file(
+        projections_filepath, geometry_filepath, output_folder, output_filename or "recon_rooster4d_mc.mha", dimension, spacing, water_pre_correction,
+        lambda proj, geometry, ds, org: rooster4d_motion(proj, geometry, ds, org, ph, to_reference, from_reference, signals, dimension, spacing, None,
+                                                         water_pre_correction=water_pre_correction, gpu_id=gpu_id, **params),
+        dict(fp="Joseph", bp="VoxelBased", motion_to_reference=model_to_reference.model_hash[:7], motion_from_reference=model_from_reference.model_hash[:7],
+             signal_n_dims=to_reference.n_signal_dims, temporal_update="increment", **params, **kwargs))

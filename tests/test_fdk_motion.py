@@ -4,13 +4,11 @@ GPU: backproject_motion_kernel through `fdk_motion` against the restatement, its
 of `reconstruct_3d_mc`.  Parity against RTK's warp back-projector is unpinned (RTK is absent)."""
 import ctypes as C
 import functools
-import shutil
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import abi_layout
 import cases
 import fdk_motion_ref as mr
 import registration_ref as R
@@ -19,7 +17,6 @@ from fdk_motion_ref import fo
 pkg = cases.pkg
 recon = pkg.reconstruction
 CorrespondenceModel = pkg.correspondence.CorrespondenceModel
-HEADER = Path(__file__).resolve().parents[1] / "include" / "mcgpu_amd.h"
 
 BATCH = 32                 # kMotionBatch of csrc/fdk.hip
 TOLERANCE = 2e-4           # x max|want|: the project's figure for float32 kernels against the float64 restatement (tests/test_fdk.py)
@@ -186,6 +183,7 @@ CASES = {
     "k4_right_hann": dict(K=4, off_x=150.0, hann=1.0, hann_y=1.0),
     "batch_plus_one": dict(n=BATCH + 1, hann=1.0),
     "below_one_batch": dict(n=5, K=1, hann_y=1.0),
+    "k3_below_one_batch": dict(K=3, n=7, dim=(45, 7, 11)),
     "odd_grid": dict(dim=(45, 7, 11), K=4, pad=0.3),                        # 3465 voxels: 13 blocks and 137 threads
     "one_column": dict(dim=(1, 30, 40), hann=1.0),
     "off_the_detector": dict(offset=(110.0, 45.0, -30.0), hann=1.0, hann_y=1.0),  # the range test refuses samples along u and along v
@@ -286,46 +284,15 @@ def test_fdk_motion_sharpens_a_moving_sphere(engine):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the C ABI
-def _c_compiler():
-    for cc in ("cc", "gcc", "clang", "/opt/rocm/llvm/bin/clang"):
-        if shutil.which(cc):
-            return shutil.which(cc)
-    return None
-
-
 def test_ctypes_mirrors_match_the_c_layout(tmp_path):
     """mcgpu_fdk_motion and mcgpu_fdk_motion_report: the header's field names in order, sizeof and every offsetof as the C compiler
-    lays them out, against the ctypes mirrors (the way tests/test_rooster4d_configs.py checks its own)."""
-    import re
+    lays them out, against the ctypes mirrors (tests/abi_layout.py)."""
     mirrors = [("mcgpu_fdk_motion", recon._FdkMotion), ("mcgpu_fdk_motion_report", recon._FdkMotionReport)]
-    text = re.sub(r"/\*.*?\*/", " ", HEADER.read_text(), flags=re.S)
-    for struct, cls in mirrors:
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), text, re.S)
-        assert body, struct
-        names = []
-        for decl in body.group(1).split(";"):
-            parts = [p.replace("*", " ").split() for p in decl.split(",")]
-            if parts[0]:
-                names += [parts[0][-1]] + [p[0] for p in parts[1:]]
-        assert names == [f[0] for f in cls._fields_], struct
-    cc = _c_compiler()
+    abi_layout.assert_field_names(mirrors)
+    cc = abi_layout.c_compiler()
     assert cc is not None, "no C compiler"
-    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "mcgpu_amd.h"', "int main(void) {"]
-    for struct, cls in mirrors:
-        lines.append(f'  printf("{struct} %zu\\n", sizeof({struct}));')
-        for name, _ in cls._fields_:
-            lines.append(f'  printf("{struct}.{name} %zu %zu\\n", offsetof({struct}, {name}), sizeof((({struct} *)0)->{name}));')
-    lines += ["  return 0;", "}"]
-    (tmp_path / "layout.c").write_text("\n".join(lines) + "\n")
-    subprocess.run([cc, "-std=c99", "-Wall", "-I", str(HEADER.parent), str(tmp_path / "layout.c"), "-o", str(tmp_path / "layout")], check=True)
-    c_side = dict(line.split(" ", 1) for line in subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout.splitlines())
-    py_side = {}
-    for struct, cls in mirrors:
-        py_side[struct] = str(C.sizeof(cls))
-        for name, _ in cls._fields_:
-            f = getattr(cls, name)
-            py_side[f"{struct}.{name}"] = f"{f.offset} {f.size}"
-    assert c_side == py_side and c_side["mcgpu_fdk_motion"] == "32"
+    c_side = abi_layout.assert_sizes_and_offsets(mirrors, cc, tmp_path)
+    assert c_side["mcgpu_fdk_motion"] == "32"
 
 
 class _Tiny:

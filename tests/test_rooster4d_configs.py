@@ -12,15 +12,12 @@ and the whole loop with water pre-correction and with and without positivity, th
 grid-stride loop of tv_space on a frame of more than 65536 x 256 voxels and the pixel origin reconstruct_4d reads from the stack.
 CPU: the ctypes mirrors of the C ABI against the layout the C compiler gives include/mcgpu_amd.h."""
 import ctypes as C
-import re
-import shutil
-import subprocess
 from functools import lru_cache
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import abi_layout
 import cases
 import joseph_ref as jr
 import rooster_ref as rr
@@ -28,7 +25,6 @@ import rooster_ref as rr
 pkg = cases.pkg
 recon = pkg.reconstruction
 phase_mod = pkg.phase
-HEADER = Path(__file__).resolve().parents[1] / "include" / "mcgpu_amd.h"
 
 SID, SDD, PIX = 300.0, 500.0, 3.5
 HALF_FAN = 0.4026  # detector offset over detector width of the reference's half-fan scan (create_geometry's default)
@@ -135,13 +131,6 @@ def test_restated_water_precorrection():
     np.testing.assert_array_equal(rr.water_precorrection(p, (0.0, 1.0)), p)
 
 
-def _c_compiler():
-    for cc in ("cc", "gcc", "clang"):
-        if shutil.which(cc):
-            return shutil.which(cc)
-    return None
-
-
 def _mirrors():
     return [("mcgpu_scan_options", pkg.engine.ScanOptions), ("mcgpu_scan_report", pkg.engine.ScanReport),
             ("mcgpu_fdk_options", recon._FdkOptions), ("mcgpu_fdk_report", recon._FdkReport),
@@ -149,47 +138,16 @@ def _mirrors():
             ("mcgpu_rooster4d_options", recon._RoosterOptions), ("mcgpu_rooster4d_report", recon._RoosterReport)]
 
 
-def _header_fields(struct):
-    """Field names of `typedef struct <struct> { ... } <struct>;` in the header, in order."""
-    text = re.sub(r"/\*.*?\*/", " ", HEADER.read_text(), flags=re.S)
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), text, re.S)
-    assert body, struct
-    names = []
-    for decl in body.group(1).split(";"):
-        parts = [re.sub(r"\[.*?\]", "", p).replace("*", " ").split() for p in decl.split(",")]
-        if parts[0]:
-            names += [parts[0][-1]] + [p[0] for p in parts[1:]]
-    return names
-
-
 def test_ctypes_mirrors_match_the_c_layout(tmp_path):
     """Every struct Python hands to or reads from the C ABI: the header's field names in order, and sizeof plus each field's
-    offsetof and size as the C compiler lays them out, equal the ctypes mirror's.  A swap of two fields of one type (ox / oy, wpc /
-    residuals) keeps the size and is caught only by the names."""
+    offsetof and size as the C compiler lays them out, equal the ctypes mirror's (tests/abi_layout.py).  A swap of two fields of one
+    type (ox / oy, wpc / residuals) keeps the size and is caught only by the names."""
     mirrors = _mirrors()
-    for struct, cls in mirrors:
-        assert _header_fields(struct) == [f[0] for f in cls._fields_], struct
-    cc = _c_compiler()
+    abi_layout.assert_field_names(mirrors)
+    cc = abi_layout.c_compiler()
     if cc is None:
         pytest.skip("no C compiler")
-    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "mcgpu_amd.h"', "int main(void) {"]
-    for struct, cls in mirrors:
-        lines.append(f'  printf("{struct} %zu\\n", sizeof({struct}));')
-        for name, _ in cls._fields_:
-            lines.append(f'  printf("{struct}.{name} %zu %zu\\n", offsetof({struct}, {name}), sizeof((({struct} *)0)->{name}));')
-    lines += ["  return 0;", "}"]
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines) + "\n")
-    exe = tmp_path / "layout"
-    subprocess.run([cc, "-std=c99", "-Wall", "-I", str(HEADER.parent), str(src), "-o", str(exe)], check=True)
-    c_side = dict(line.split(" ", 1) for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    py_side = {}
-    for struct, cls in mirrors:
-        py_side[struct] = str(C.sizeof(cls))
-        for name, _ in cls._fields_:
-            f = getattr(cls, name)
-            py_side[f"{struct}.{name}"] = f"{f.offset} {f.size}"
-    assert c_side == py_side
+    c_side = abi_layout.assert_sizes_and_offsets(mirrors, cc, tmp_path)
     assert c_side["mcgpu_rooster4d_options"] == "232"
 
 

@@ -6,14 +6,11 @@ GPU: the three stages against the restatement, the whole loop, a moving sphere a
 Parity against RTK's rtkfourdrooster --dvf --idvf is unpinned (RTK is absent here), and RTK's replace form is not what runs."""
 import ctypes as C
 import functools
-import re
-import shutil
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import abi_layout
 import cases
 import joseph_ref as jr
 import rooster_motion_ref as mr
@@ -22,7 +19,6 @@ import test_rooster4d as base  # the small problem of the plain ROOSTER tests: g
 
 pkg = cases.pkg
 recon = pkg.reconstruction
-HEADER = Path(__file__).resolve().parents[1] / "include" / "mcgpu_amd.h"
 DIM, SPACING, FRAMES, NU, NV, PIX = base.DIM, base.SPACING, base.FRAMES, base.NU, base.NV, base.PIX
 STAGE_TOLERANCE = 1e-5   # the project's figure for one float32 operator against its float64 restatement (test_rooster4d.py)
 FLOOR_CAP = 2.5e-6       # the float32-coordinate floor up to which STAGE_TOLERANCE is kept; beyond it the bound is 4 x the floor
@@ -128,49 +124,19 @@ def test_restated_zero_model_is_the_identity_and_gamma_zero_returns_the_input():
 
 
 # ---------------------------------------------------------------------------------------------------------------- CPU: the C ABI
-def _c_compiler():
-    for cc in ("cc", "gcc", "clang", "/opt/rocm/llvm/bin/clang"):
-        if shutil.which(cc):
-            return shutil.which(cc)
-    return None
-
-
 def test_ctypes_mirrors_match_the_c_layout(tmp_path):
     """mcgpu_rooster4d_motion and mcgpu_rooster4d_motion_report: the header's field names in order, sizeof and every offsetof as the
-    C compiler lays them out, against the ctypes mirrors (the way tests/test_rooster4d_configs.py checks its own).  The report
-    begins with the fields of mcgpu_rooster4d_report."""
+    C compiler lays them out, against the ctypes mirrors (tests/abi_layout.py).  The report begins with the fields of
+    mcgpu_rooster4d_report."""
     mirrors = [("mcgpu_rooster4d_motion", recon._RoosterMotion), ("mcgpu_rooster4d_motion_report", recon._RoosterMotionReport)]
-    text = re.sub(r"/\*.*?\*/", " ", HEADER.read_text(), flags=re.S)
-    for struct, cls in mirrors:
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), text, re.S)
-        assert body, struct
-        names = []
-        for decl in body.group(1).split(";"):
-            parts = [p.replace("*", " ").split() for p in decl.split(",")]
-            if parts[0]:
-                names += [parts[0][-1]] + [p[0] for p in parts[1:]]
-        assert names == [f[0] for f in cls._fields_], struct
+    abi_layout.assert_field_names(mirrors)
     n_plain = len(recon._RoosterReport._fields_)
     assert recon._RoosterMotionReport._fields_[:n_plain] == recon._RoosterReport._fields_
     assert [f[0] for f in recon._RoosterMotionReport._fields_[n_plain:]] == ["ms_warp", "ms_upload_model"]
-    cc = _c_compiler()
+    cc = abi_layout.c_compiler()
     assert cc is not None, "no C compiler"
-    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "mcgpu_amd.h"', "int main(void) {"]
-    for struct, cls in mirrors:
-        lines.append(f'  printf("{struct} %zu\\n", sizeof({struct}));')
-        for name, _ in cls._fields_:
-            lines.append(f'  printf("{struct}.{name} %zu %zu\\n", offsetof({struct}, {name}), sizeof((({struct} *)0)->{name}));')
-    lines += ["  return 0;", "}"]
-    (tmp_path / "layout.c").write_text("\n".join(lines) + "\n")
-    subprocess.run([cc, "-std=c99", "-Wall", "-I", str(HEADER.parent), str(tmp_path / "layout.c"), "-o", str(tmp_path / "layout")], check=True)
-    c_side = dict(line.split(" ", 1) for line in subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout.splitlines())
-    py_side = {}
-    for struct, cls in mirrors:
-        py_side[struct] = str(C.sizeof(cls))
-        for name, _ in cls._fields_:
-            f = getattr(cls, name)
-            py_side[f"{struct}.{name}"] = f"{f.offset} {f.size}"
-    assert c_side == py_side and c_side["mcgpu_rooster4d_motion"] == "56" and c_side["mcgpu_rooster4d_motion_report"] == "80"
+    c_side = abi_layout.assert_sizes_and_offsets(mirrors, cc, tmp_path)
+    assert c_side["mcgpu_rooster4d_motion"] == "56" and c_side["mcgpu_rooster4d_motion_report"] == "80"
 
 
 class _Tiny:
@@ -301,7 +267,7 @@ def _small_case(K):
     return x, mean, coef, states, want, floor
 
 
-@pytest.mark.parametrize("K", [1, 2, 4])
+@pytest.mark.parametrize("K", [1, 2, 3, 4])
 def test_the_small_case_reaches_every_face_and_the_last_cell(K):
     """Checked without a GPU: what _small_case promises, and the float32-coordinate floor that sets the GPU tolerance."""
     x, mean, coef, states, want, floor = _small_case(K)
@@ -321,11 +287,11 @@ def test_the_small_case_reaches_every_face_and_the_last_cell(K):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("K", [1, 2, 4])
+@pytest.mark.parametrize("K", [1, 2, 3, 4])
 def test_warp_and_unwarp_equal_the_restatement_on_the_small_grid(engine, K):
-    """13 x 5 x 7 voxels of (2, 1.5, 3) mm, displacements past all six faces and exact whole voxels, K = 1, 2, 4, W and U (the same
+    """13 x 5 x 7 voxels of (2, 1.5, 3) mm, displacements past all six faces and exact whole voxels, K = 1 .. 4, W and U (the same
     operator on the other model).  Tolerance 1e-5 relative: the restatement evaluated with float32 coordinates stays within 1e-7
-    of the float64 one (K = 1: 9.3e-8, K = 2: 8.7e-8, K = 4: 9.2e-8), below the 2.5e-6 up to which the project's 1e-5 is kept.
+    of the float64 one (K = 1: 9.3e-8, K = 2: 8.7e-8, K = 3: 8.4e-8, K = 4: 9.2e-8), below the 2.5e-6 up to which the project's 1e-5 is kept.
     Measured on an MI355X: 1.0e-7, 8.9e-8, 9.8e-8."""
     x, mean, coef, states, want, floor = _small_case(K)
     tol = _stage_tolerance(floor)

@@ -8,6 +8,10 @@ comparable only within one installation.  The cases are the tests' own builders 
   rooster  rooster4d_stage "back" and "forward" on every test_rooster4d_configs.CONFIGS, and one rooster4d call at `odd` with a
            water pre-correction
   fp       project_forward on the thin_* and deg45 cases of test_forward_projection_configs
+  fdk_motion      reconstruction.fdk_motion on every entry of test_fdk_motion.CASES
+  rooster_motion  rooster4d_motion_stage "warp", "unwarp" and "tv_time_motion" (5 iterations, gamma 0.05, the negated model back) on
+                  test_rooster4d_motion's 13 x 5 x 7 small case at K = 1, 2, 3 and 4, and one rooster4d_motion call on the case of
+                  test_rooster4d_motion_equals_the_restated_loop_and_repeats_bit_for_bit (volume and residuals)
 --one-slice adds, on "half_fan" with the direct ramp at order 1, slabs (0, 1) and (29, 1), both layouts: the number of float32 words
 in which basis_mean[n] of the fused call differs from fdk(..., water_pre_correction=e_n)[0][:, y, :] (tests/test_wpc_fit_gpu.py).
 Usage: [MCGPU_AMD_LIB=other.so] python tools/recon_digest.py [--one-slice] [--out FILE.json]"""
@@ -53,7 +57,9 @@ def main():
     pkg.engine.load_library()
     recon, wp = pkg.reconstruction, pkg.water_precorrection
     import test_fdk_configs as F
+    import test_fdk_motion as FM
     import test_forward_projection_configs as J
+    import test_rooster4d_motion as RM
     import test_rooster4d_configs as R
     import wpc_ref as W
     out = {}
@@ -87,6 +93,19 @@ def main():
 
     for name in ["thin_%d_%d_%d" % s for s in J.THIN_SHAPES] + ["deg45"]:
         out[f"fp {name}"] = sha(J.case(name).hip())
+
+    for name in FM.CASES:
+        out[f"fdk_motion {name}"] = sha(FM._fdk_motion(name)[0])
+
+    for K in (1, 2, 3, 4):
+        x, mean, coef, states = RM._small_case(K)[:4]
+        model, back, zero = (recon.MotionModel(f * mean, f * coef, np.zeros(K), spacing=RM.SMALL_SPACING) for f in (1.0, -1.0, 0.0))
+        for stage, pair, kw in (("warp", (model, zero), {}), ("unwarp", (zero, model), {}), ("tv_time_motion", (model, back), dict(tviter=5, gamma_time=0.05))):
+            out[f"rooster_motion small K {K} {stage}"] = sha(recon.rooster4d_motion_stage(stage, x, *pair, states, RM.SMALL_DIM, RM.SMALL_SPACING, **kw)[0])
+    geo, ph = RM.base._geometry(), RM.base._phase()
+    vol, rep = recon.rooster4d_motion(RM.base._projections(geo, ph), geo, (RM.PIX, RM.PIX), None, ph, *RM._motion_models(RM._k2_models()), RM._signals(ph), RM.DIM,
+                                      RM.SPACING, frames=RM.FRAMES, niter=2, cgiter=3, tviter=5, gamma_space=0.002, gamma_time=0.002)
+    out["rooster_motion whole call"] = sha(vol, rep["residuals"])
 
     if args.one_slice:
         ramp(True)
