@@ -31,7 +31,7 @@ ABI_SYMBOLS = (
     "mcgpu_warp_volume", "mcgpu_warp_geometry", "mcgpu_map_image", "mcgpu_set_geometry_image",
     "mcgpu_resample_plan", "mcgpu_resample_volume", "mcgpu_set_geometry_image_resampled",
     "mcgpu_correspondence_set", "mcgpu_correspondence_fit", "mcgpu_correspondence_predict", "mcgpu_warp_geometry_signal", "mcgpu_correspondence_clear",
-    "mcgpu_write_voxel_file", "mcgpu_write_voxel_binary", "mcgpu_kat_rng", "mcgpu_kat_rng_streams", "mcgpu_microbench", "mcgpu_kat_math", "mcgpu_kat_expf", "mcgpu_kat_f32", "mcgpu_kat_fast64", "mcgpu_kat_scatter", "mcgpu_kat_history", "mcgpu_kat_flight", "mcgpu_kat_tile_records", "mcgpu_fdk_reconstruct", "mcgpu_fdk_reconstruct_motion", "mcgpu_wpc_fit", "mcgpu_forward_project", "mcgpu_forward_project_context", "mcgpu_rooster4d_reconstruct", "mcgpu_rooster4d_stage", "mcgpu_rooster4d_reconstruct_motion", "mcgpu_rooster4d_motion_stage", "mcgpu_register", "mcgpu_register_stage", "mcgpu_speedup_run", "mcgpu_speedup_stage", "mcgpu_segment_run", "mcgpu_segment_stage", "mcgpu_set_fast_schedule", "mcgpu_reload_env_knobs",
+    "mcgpu_write_voxel_file", "mcgpu_write_voxel_binary", "mcgpu_kat_rng", "mcgpu_kat_rng_streams", "mcgpu_microbench", "mcgpu_kat_math", "mcgpu_kat_expf", "mcgpu_kat_f32", "mcgpu_kat_fast64", "mcgpu_kat_scatter", "mcgpu_kat_history", "mcgpu_kat_flight", "mcgpu_kat_tile_records", "mcgpu_fdk_reconstruct", "mcgpu_fdk_reconstruct_motion", "mcgpu_wpc_fit", "mcgpu_forward_project", "mcgpu_forward_project_context", "mcgpu_primary_project", "mcgpu_smooth_planes", "mcgpu_rooster4d_reconstruct", "mcgpu_rooster4d_stage", "mcgpu_rooster4d_reconstruct_motion", "mcgpu_rooster4d_motion_stage", "mcgpu_register", "mcgpu_register_stage", "mcgpu_speedup_run", "mcgpu_speedup_stage", "mcgpu_segment_run", "mcgpu_segment_stage", "mcgpu_set_fast_schedule", "mcgpu_reload_env_knobs",
     "mcgpu_exchange_shared_bytes", "mcgpu_exchange_card_bytes", "mcgpu_exchange_create", "mcgpu_exchange_card", "mcgpu_exchange_connect",
     "mcgpu_exchange_connect_local", "mcgpu_exchange_probe", "mcgpu_exchange_owner", "mcgpu_exchange_begin", "mcgpu_exchange_submit", "mcgpu_exchange_collect",
     "mcgpu_exchange_stats", "mcgpu_exchange_destroy", "mcgpu_copy_to_host",
@@ -86,6 +86,18 @@ class ResampleReport(C.Structure):
     """mcgpu_resample_report (include/mcgpu_amd.h)."""
     _fields_ = [("struct_size", C.c_uint), ("ms_kernel", C.c_double), ("ms_upload", C.c_double), ("ms_download", C.c_double),
                 ("kernel_bytes", C.c_ulonglong)]
+
+
+class PrimaryOptions(C.Structure):
+    """mcgpu_primary_options (include/mcgpu_amd.h)."""
+    _fields_ = [("struct_size", C.c_uint), ("first_projection", C.c_int), ("n_projections", C.c_int), ("su", C.c_int), ("sv", C.c_int),
+                ("energy_points", C.c_int), ("crop_nx", C.c_int)]
+
+
+class PrimaryReport(C.Structure):
+    """mcgpu_primary_report (include/mcgpu_amd.h)."""
+    _fields_ = [("struct_size", C.c_uint), ("n_materials", C.c_int), ("ms_kernel", C.c_double), ("ms_tables", C.c_double),
+                ("solid_angle", C.c_double), ("n_energy_points", C.c_int), ("reserved", C.c_int)]
 
 
 def knob_table():
@@ -213,6 +225,8 @@ def load_library(path: Optional[os.PathLike] = None):
     lib.mcgpu_kat_history.argtypes = [vp, ci, ci, ci, ci, C.c_uint, vp, vp, vp, vp]
     lib.mcgpu_kat_flight.argtypes = [vp, ci, ci, ci, ci, ci, C.c_uint, vp, vp, vp]
     lib.mcgpu_kat_tile_records.argtypes = [ci, vp, vp]
+    lib.mcgpu_primary_project.argtypes = [vp, C.POINTER(PrimaryOptions), vp, C.POINTER(PrimaryReport)]
+    lib.mcgpu_smooth_planes.argtypes = [ci, vp, vp, ci, ci, ci, C.c_double, C.c_double, C.POINTER(C.c_double)]
     if path is None:
         _lib = lib
     return lib
@@ -357,6 +371,19 @@ def normalize_stack(total_stack, air_stack, out_stack, sigma=(10.0, 10.0), spaci
     sy, sx = (0.0, 0.0) if not sigma else (float(sigma[0]), float(sigma[1]))
     _check(load_library().mcgpu_normalize_stack(str(total_stack).encode(), str(air_stack).encode(), sy, sx, str(out_stack).encode(),
                                                 float(spacing[0]), float(spacing[1])))
+
+
+def smooth_planes(planes: np.ndarray, sigma=(10.0, 10.0), device: int = 0) -> np.ndarray:
+    """scipy.ndimage.gaussian_filter(plane, sigma, truncate=4, mode="reflect") of every plane of a float32 array [..., ny, nx], on the
+    device (mcgpu_smooth_planes).  sigma = (along y, along x); a sigma of 0 leaves its axis alone, both 0 return the planes bit for bit."""
+    a = np.ascontiguousarray(planes, dtype=np.float32)
+    if a.ndim < 2:
+        raise ValueError("planes of at least two dimensions are needed")
+    sy, sx = (0.0, 0.0) if not sigma else (float(sigma[0]), float(sigma[1]))
+    out = np.empty_like(a)
+    ny, nx = a.shape[-2:]
+    _check(load_library().mcgpu_smooth_planes(int(device), a.ctypes.data, out.ctypes.data, int(a.size // (ny * nx)), int(ny), int(nx), sy, sx, None))
+    return out
 
 
 EXCHANGE_ROOT0, EXCHANGE_ROTATE, EXCHANGE_LOCAL = 0, 1, 2
@@ -646,6 +673,27 @@ class Context:
                                  clear_w2: bool = False, stream: int = 0):
         _check(self.lib.mcgpu_finalize_variance(self.h, C.c_void_p(image_dev_ptr), C.c_void_p(w2_dev_ptr), int(total_histories), int(crop_nx),
                                                 C.c_void_p(planes_dev_ptr), int(clear_w2), C.c_void_p(stream)))
+
+    # -- the ray-traced primary (csrc/primary_project.hip states the rule)
+    def primary_scan(self, first_projection: int = 0, n_projections: Optional[int] = None, subsamples=(1, 1), energy_points: int = 2,
+                     crop_nx: int = 0):
+        """The expectation of the `unscattered` plane of projections first_projection .. + n_projections - 1 (default: to the last) of
+        the resident geometry: (float32 [n_projections, nz, crop_nx or nx] in finalize's layout and unit, report dict).
+        subsamples = (su, sv): sub-points per pixel along x / z, 1..8; energy_points: Gauss-Legendre points per spectrum bin, 1..4."""
+        n = self.num_projections - int(first_projection) if n_projections is None else int(n_projections)
+        nz, nx = self.detector_shape
+        cx = crop_nx if 0 < crop_nx < nx else nx
+        o = PrimaryOptions(C.sizeof(PrimaryOptions), int(first_projection), n, int(subsamples[0]), int(subsamples[1]), int(energy_points), int(crop_nx))
+        r = PrimaryReport(C.sizeof(PrimaryReport))
+        out = np.zeros((max(n, 1), nz, cx), dtype=np.float32)
+        _check(self.lib.mcgpu_primary_project(self.h, C.byref(o), out.ctypes.data, C.byref(r)))
+        return out, {"ms_kernel": r.ms_kernel, "ms_tables": r.ms_tables, "solid_angle": r.solid_angle, "n_materials": r.n_materials,
+                     "n_energy_points": r.n_energy_points}
+
+    def primary_projection(self, p: int, subsamples=(1, 1), energy_points: int = 2, crop_nx: int = 0):
+        """primary_scan of the one projection p: (float32 [nz, crop_nx or nx], report dict)."""
+        out, report = self.primary_scan(p, 1, subsamples, energy_points, crop_nx)
+        return out[0], report
 
     # -- 4-D: several (geometry, projection angles) jobs on one resident context (cbctmc/mc/simulation.py:527-710)
     def set_projection_angles(self, angles_deg):

@@ -211,15 +211,19 @@ class MCSimulation:
 
     def run_simulation(self, output_folder, engine, gpu_ids=(0,), mode="fast", run_air_simulation=False,
                        air_projection_denoise_kernel_size=(10, 10), clean=True, stack_projections=True, force_rerun=False,
-                       air_n_histories=int(5e10), forward_projection=False, variance=False, **prepare_kwargs):
+                       air_n_histories=int(5e10), forward_projection=False, variance=False, analytic_primary=False, scatter_sigma=(10, 10),
+                       primary_subsamples=(1, 1), primary_energy_points=2, **prepare_kwargs):
         """`BaseMCSimulation.run_simulation` (sim.py:370-427) on the in-process engine: the docker/mpirun launch and the
         ASCII -> numpy -> SimpleITK post-processing are replaced by the engine's scan pipeline, which writes
         projections_{total,unscattered,scattered}.mha (and projections_total_normalized.mha with an air scan) directly.
         `clean=False` additionally keeps the reference's per-projection ASCII files.  `forward_projection=True` also writes
         geometry.xml and density_fp.mha into `output_folder` (write_forward_projection).  `variance=True` (with
         `stack_projections`) also writes projections_{total,unscattered,scattered}_variance.mha: the per-pixel variance of the stacks,
-        tallied in the same run.  Returns the scan report."""
+        tallied in the same run.  `analytic_primary=True` (with `stack_projections`) also writes the hybrid products after the scan
+        (write_hybrid_products): the ray-traced primary, the smoothed Monte Carlo scatter and their sum.  Returns the scan report."""
         output_folder = Path(output_folder)
+        if analytic_primary and not stack_projections:
+            raise ValueError("The hybrid products are made of the projection stacks: analytic_primary needs stack_projections")
         if forward_projection:
             self.write_forward_projection(output_folder, engine, gpu_id=gpu_ids if isinstance(gpu_ids, int) else gpu_ids[0])
         if self._already_simulated(output_folder) and not force_rerun:
@@ -240,11 +244,44 @@ class MCSimulation:
         half_fan = DEFAULTS.n_detector_pixels_half_fan[0] if tuple(self.n_detector_pixels) == tuple(DEFAULTS.n_detector_pixels) else 0
         ctx = engine.create(str(input_filepath), device=gpu_ids[0])
         try:
-            return ctx.run_scan(mode=mode, crop_nx=half_fan, write_ascii=not clean, write_stacks=stack_projections,
-                                output_folder=output_folder, air_stack=air_stack, air_sigma=air_projection_denoise_kernel_size,
-                                pixel_spacing=self.STACK_PIXEL_SPACING, write_variance=variance)
+            report = ctx.run_scan(mode=mode, crop_nx=half_fan, write_ascii=not clean, write_stacks=stack_projections,
+                                  output_folder=output_folder, air_stack=air_stack, air_sigma=air_projection_denoise_kernel_size,
+                                  pixel_spacing=self.STACK_PIXEL_SPACING, write_variance=variance)
+            if analytic_primary:
+                self.write_hybrid_products(ctx, engine, output_folder, crop_nx=half_fan, scatter_sigma=scatter_sigma, air_stack=air_stack,
+                                           air_sigma=air_projection_denoise_kernel_size, subsamples=primary_subsamples,
+                                           energy_points=primary_energy_points)
+            return report
         finally:
             ctx.close()
+
+    @staticmethod
+    def write_hybrid_products(ctx, engine, output_folder, crop_nx=0, scatter_sigma=(10, 10), air_stack=None, air_sigma=(10, 10),
+                              subsamples=(1, 1), energy_points=2):
+        """"Ray-traced primary + smoothed Monte Carlo scatter" beside the stacks of a finished scan, with their metadata:
+          projections_unscattered_analytic.mha     the expectation of projections_unscattered.mha (Context.primary_scan)
+          projections_scattered_smoothed.mha       projections_scattered.mha through a 2-D Gaussian on the device (engine.smooth_planes:
+                                                   scipy.ndimage.gaussian_filter, truncate 4, reflect)
+          projections_total_hybrid.mha             their sum in float32
+          projections_total_hybrid_normalized.mha  with an air scan: engine.normalize_stack of the hybrid total, unchanged
+        `scatter_sigma=(10, 10)` [pixels, (rows, columns)] is the convention of the air projection's denoising kernel, not a tuned value.
+        Zeros are kept as they are (no replacement), so the sum holds bit for bit in the files."""
+        output_folder = Path(output_folder)
+        analytic, _ = ctx.primary_scan(0, None, subsamples=subsamples, energy_points=energy_points, crop_nx=crop_nx)
+        scattered = engine.stack_read(output_folder / "projections_scattered.mha")
+        if scattered.shape != analytic.shape:
+            raise ValueError(f"projections_scattered.mha holds {scattered.shape}, the analytic primary {analytic.shape}")
+        smoothed = engine.smooth_planes(scattered, scatter_sigma, device=ctx.device)
+        hybrid = analytic + smoothed
+        n, nz, cx = analytic.shape
+        for name, stack in (("unscattered_analytic", analytic), ("scattered_smoothed", smoothed), ("total_hybrid", hybrid)):
+            w = engine.StackWriter(output_folder / f"projections_{name}.mha", cx, nz, n, MCSimulation.STACK_PIXEL_SPACING)
+            for plane in stack:
+                w.append(plane)
+            w.finish(replace_zeros=False)
+        if air_stack is not None:
+            engine.normalize_stack(output_folder / "projections_total_hybrid.mha", air_stack, output_folder / "projections_total_hybrid_normalized.mha",
+                                   sigma=air_sigma, spacing=MCSimulation.STACK_PIXEL_SPACING)
 
     @staticmethod
     def postprocess_simulation(folder, engine, n_detector_pixels=DEFAULTS.n_detector_pixels,
@@ -351,8 +388,11 @@ class MCSimulation4D:
     def run_simulation(self, respiratory_signal, respiratory_signal_quantization, output_folder, engine, gpu_ids=(0,), mode="fast",
                        run_air_simulation=False, air_projection_denoise_kernel_size=(10, 10), air_n_histories=int(5e10), start_angle=270.0,
                        force_rerun=False, forward_projection=False, fp_detector_size=DEFAULTS.n_detector_pixels_half_fan,
-                       fp_detector_pixel_spacing=DEFAULTS.detector_pixel_size):
-        """`forward_projection=True`: also density_fp_4d.mha (scripts/run_mc_simulations.py:491-556), one slice per projection:
+                       fp_detector_pixel_spacing=DEFAULTS.detector_pixel_size, analytic_primary=False, primary_subsamples=(1, 1),
+                       primary_energy_points=2):
+        """`analytic_primary=True`: also projections_unscattered_analytic.mha, one slice per projection: the ray-traced primary
+        (Context.primary_scan) of that projection's warped geometry and pose, computed right after the state is applied.
+        `forward_projection=True`: also density_fp_4d.mha (scripts/run_mc_simulations.py:491-556), one slice per projection:
         the Joseph forward projection of that projection's warped geometry at FP angle = MC angle - 180 degrees, projected from
         the resident context right after the state is applied (the warped volume never leaves the device)."""
         import numpy as np
@@ -394,6 +434,9 @@ class MCSimulation4D:
             fp_stack = engine.StackWriter(output_folder / "density_fp_4d.mha", int(fp_detector_size[0]), int(fp_detector_size[1]), n_proj,
                                           fp_detector_pixel_spacing)
             fp_frame = rtk_frame(self.geometry.image_shape, self.geometry.image_spacing)
+        primary_stack = None
+        if analytic_primary:
+            primary_stack = engine.StackWriter(output_folder / "projections_unscattered_analytic.mha", cx, nz_det, n_proj, MCSimulation.STACK_PIXEL_SPACING)
         ctx = engine.create(str(input_filepath), device=gpu_ids[0])
         try:
             for (s, ds), indices in unique.items():
@@ -406,6 +449,10 @@ class MCSimulation4D:
                         fp_stack.write_slice(i, plane)
                 angles = [start_angle + i * self.angle_between_projections for i in indices]
                 ctx.set_projection_angles(angles[0:1] + angles)  # pose 0 is the input file's: skipped below (sim.py:658-660)
+                if primary_stack is not None:
+                    planes, _ = ctx.primary_scan(1, len(angles), subsamples=primary_subsamples, energy_points=primary_energy_points, crop_nx=half_fan)
+                    for i, plane in zip(indices, planes):
+                        primary_stack.write_slice(i, plane)
                 ctx.run_scan(mode=mode, first_projection=1, num_projections=len(angles), crop_nx=half_fan, write_stacks=False,
                              output_folder=output_folder, shared_stacks=stacks, slice_of_projection=indices)
                 for a in angles:
@@ -416,6 +463,8 @@ class MCSimulation4D:
             w.finish(replace_zeros=True)
         if fp_stack is not None:
             fp_stack.finish(replace_zeros=False)
+        if primary_stack is not None:
+            primary_stack.finish(replace_zeros=False)
         if air_stack is not None:
             engine.normalize_stack(output_folder / "projections_total.mha", air_stack, output_folder / "projections_total_normalized.mha",
                                    sigma=air_projection_denoise_kernel_size, spacing=MCSimulation.STACK_PIXEL_SPACING)

@@ -732,6 +732,37 @@ int mcgpu_forward_project(const mcgpu_fp_options *options, const float *volume, 
 int mcgpu_forward_project_context(mcgpu_ctx *ctx, const mcgpu_fp_options *options, float *projections, mcgpu_fp_report *report);
 
 /* ------------------------------------------------------------------------------------------------
+ * Row f17: the ray-traced primary (csrc/primary_project.hip, whose header states the rule).  The expectation of the `unscattered`
+ * plane of projections first_projection .. + n_projections - 1 of the geometry, poses, detector and spectrum resident in the
+ * context: source spectrum x Beer-Lambert attenuation along the line focal spot -> pixel through the context's voxels, with the
+ * cross-section tables of the flight step.  planes: [n_projections][nz][crop_nx] float32 in finalize's layout and unit (eV / cm^2
+ * per history, z flipped, the first crop_nx columns).  Refused with -1 before any device work: a context without a device, a
+ * projection range outside the context's, su / sv outside 1..8, energy_points outside 1..4. */
+typedef struct mcgpu_primary_options {
+  unsigned int struct_size;  /* sizeof(mcgpu_primary_options) as the caller was compiled (later fields read as zero); 0 is refused */
+  int first_projection;
+  int n_projections;         /* 0: one */
+  int su, sv;                /* sub-points per pixel along x / z, 1..8 (0: 1) */
+  int energy_points;         /* Gauss-Legendre points per spectrum bin, 1..4 (0: 2) */
+  int crop_nx;               /* as mcgpu_finalize_projection: outside 1 .. nx - 1 = the full width */
+} mcgpu_primary_options;
+typedef struct mcgpu_primary_report {
+  unsigned int struct_size;  /* sizeof(mcgpu_primary_report) as the caller was compiled: that many bytes are written */
+  int n_materials;           /* materials of the device model (columns of the cross-section table) */
+  double ms_kernel;          /* projection kernels */
+  double ms_tables;          /* spectrum nodes, cross-sections, poses and the solid angle on the host, and their upload */
+  double solid_angle;        /* of the source aperture [sr] */
+  int n_energy_points;       /* spectrum nodes in all */
+  int reserved;
+} mcgpu_primary_report;
+int mcgpu_primary_project(mcgpu_ctx *ctx, const mcgpu_primary_options *options, float *planes, mcgpu_primary_report *report);
+/* scipy.ndimage.gaussian_filter(plane, (sigma_y, sigma_x), truncate = 4, mode = "reflect") of n_planes float32 planes [ny][nx] on
+ * `device` (host pointers; planes_out may be planes_in).  A sigma of 0 skips its axis; both 0 copy the planes bit for bit without
+ * touching the device.  ms_kernel (may be NULL): the passes' device time. */
+int mcgpu_smooth_planes(int device, const float *planes_in, float *planes_out, int n_planes, int ny, int nx, double sigma_y, double sigma_x,
+                        double *ms_kernel);
+
+/* ------------------------------------------------------------------------------------------------
  * Row f6: 4-D ROOSTER reconstruction (what the reference obtains from RTK's `rtkfourdrooster`,
  * cbctmc/reconstruction/reconstruction.py: reconstruct_4d; csrc/rooster4d.hip, whose header spells out the algorithm).
  * Geometry, detector grid, volume grid and wpc as mcgpu_fdk_options; the result is n_frames volumes [n_frames][nz][ny][nx]
