@@ -1,0 +1,1003 @@
+// speedup_train.hip -- training of the speed-up network on the device: the backward half of speedup_net.hip, the two losses of the
+// reference's trainer (cbctmc/speedup/trainer.py: MCSpeedUpTrainer._train_or_test_on_batch) and Adam, in float32.
+//
+// The rule.  A batch is B samples (low_photon lp, forward_projection or none, high_photon t), each [nv][nu]; N = B nv nu.
+//   Forward: exactly mcgpu_speedup_run's (speedup_net.hip's header): preprocessing, mean net, m = relu(lp + 10 tanh(net_m)),
+//     variance net on m, v = m 0.1 sigmoid(s) + 1e-6.  Instance norm keeps samples independent: every sample runs alone, the batch
+//     gradient is the sum of the per-sample gradients added in sample order (float32), and the losses are sums over samples in
+//     float64 divided by N.  No atomics anywhere: the same call gives the same bytes.  1 / N = 1 / (nv nu) x 1 / B is applied in two
+//     places: a sample's backward pass runs on the gradient of its own mean loss, 1 / (nv nu), so that it is the same bytes in any
+//     batch, and 1 / B multiplies the sample's float64-folded weight gradient where it is rounded to float32 and added.
+//   Phase mean:      loss = mean |m - t|;  dL/dm = sign(m - t) / N (sign 0 = 0);  dL/dnet_m = dL/dm [m > 0] 10 (1 - tanh^2(net_m)).
+//                    Only the mean net's weights get gradients.
+//   Phase variance:  loss = mean 0.5 (log v' + (m - t)^2 / v'), v' = max(v, 1e-6);  dL/dv = 0.5 (1 / v' - (m - t)^2 / v'^2) / N where
+//                    v > 1e-6, else 0;  dL/ds = dL/dv m 0.1 sigmoid(s) (1 - sigmoid(s)).  The mean net is frozen and no gradient is
+//                    taken through m (the reference's second stage); only the variance net's weights get gradients.
+//     The reference's joint stage (n_pretrain_steps = None) is not built.  The reference trains under float16 autocast with a
+//     gradient scaler; here everything is float32 and nothing is scaled.
+//   Backward of one FlexUNet: NetPass::forward walked in reverse.
+//     LeakyReLU + instance norm:  d xh = dy (xh > 0 ? 1 : 0.01);  dx = rstd (d xh - mean(d xh) - xh mean(d xh xh)).  The two means are
+//       float64 sums over stats_kernel's segments and a 256-wide tree; dx is computed in float64 and rounded once.  The forward pass
+//       normalises in place, so the pass keeps y and every layer's own sums (mean, rstd); xh is recovered from y through the inverse
+//       of the LeakyReLU (y > 0 ? y : y / 0.01f, in float64): within half a spacing of the xh that the forward rounded, against
+//       keeping a second copy of every normed tensor (profiles/speedup_train.md has the measured gradient error of both).
+//     Convolution, weights:  dW[co][ci][tap] = sum over pixels of dY[co][y][x] X~[ci][y + dy - 1][x + dx - 1], X~ what the forward
+//       stages (clamped coordinates, two concatenated sources, the second through >> 1).
+//     Convolution, bias:  db[co] = sum dY for init_conv and final_conv (float64 sums, rounded once); defined as exactly 0 for a
+//       convolution that feeds an instance norm (mathematically 0; autograd gives rounding noise there) -- those biases never move.
+//     Convolution, input:  the adjoint of clamp-then-convolve: the zero-padded correlation of dY with the weights transposed in
+//       (co, ci) and flipped in the taps, on rows -1 .. H and columns -1 .. W; row -1 folds into row 0, row H into row H - 1, columns
+//       alike (corners twice); channels of the first source go to the skip's gradient, channels of the second are summed over each
+//       2 x 2 block into the half-size gradient (the adjoint of the nearest upsample).  init_conv needs none.
+//     Max-pool:  the gradient goes to the first maximal element of the window in the order (0,0), (0,1), (1,0), (1,1), recomputed
+//       from the saved input, and is added to what the decoder path left in the skip's gradient.
+//   Adam (no weight decay):  m <- b1 m + (1 - b1) g;  v <- b2 v + (1 - b2) g^2;  w <- w - lr / (1 - b1^t) m / (sqrt(v) / sqrt(1 - b2^t) +
+//     1e-8), per element in float64 from the float32 state, each result rounded once; t counts the updates of the phase's net; lr <- lr
+//     gamma after every update.  A gradient of 0 on zero moments leaves w, m and v as they are.
+//
+// The kernels.
+//   conv_wgrad_mfma_kernel: a GEMM on v_mfma_f32_32x32x2_f32 with M = C_out, N = C_in per tap, K = pixels.  A workgroup of 4 waves owns
+//     32 output channels x 32 input channels x 9 taps and a range of pixel tiles (4 rows x 32 columns; a wave owns one row).  Per tile
+//     the 6 x 34 halo of the 32 input channels is staged in LDS exactly as the forward stages it (the concatenated or upsampled input
+//     never exists in memory) beside the 4 x 32 tile of dY, zero outside the image; channel strides are odd (205, 129), so that the 32
+//     channels a wave reads at one pixel lie in 32 banks.  One MFMA k-step is two neighbouring pixels of a row; the nine taps are nine
+//     accumulators fed from one dY value and nine shifted reads.  K is split across workgroups and waves into float32 partials
+//     [partial][C_out][C_in][9]; wgrad_fold_kernel adds them in float64 in the order of the partials and rounds once.
+//   Input gradient: conv3x3_mfma_kernel<NB, true> of speedup_conv.inc -- the forward's implicit GEMM with zero-filled staging --
+//     with a second packing of the weights (pack_dgrad_weights_kernel: transposed, taps flipped) into an extended
+//     [C_in][H + 2][W + 2] buffer, then dgrad_fold_kernel (fold of the border, split into the two sources, 2 x 2 sums; float64, rounded
+//     once).
+//   norm_backward_stats_kernel + norm_backward_kernel, maxpool_backward_kernel, metrics_kernel (the four float64 sums of a sample:
+//     |m - t|, the Gaussian term, (lp - t)^2, (m - t)^2), l1_grad_kernel, nll_grad_kernel, bias_grad_kernel, adam_kernel.
+// The weights, both moments, both packings and all buffers of a pass live on the device between steps behind a handle; both packings
+// of the phase's net are redone on the device after each update.
+#include <chrono>
+#include <map>
+#include <memory>
+
+#include "../../include/mcgpu_amd.h"
+#include "hip_host.hpp"
+
+namespace {
+
+constexpr int kTaps = 9;
+#include "unet_common.inc"
+#include "speedup_conv.inc"
+
+// ------------------------------------------------------------------------------------------------ convolution, weight gradient
+constexpr int kWgH = 4;                                      // rows of a pixel tile: one per wave
+constexpr int kWgHalo = (kWgH + 2) * kHaloW;                 // 204
+constexpr int kWgXStride = kWgHalo + 1, kWgYStride = kWgH * kTileW + 1;  // odd: 32 channels at one pixel lie in 32 banks
+constexpr int kWgTarget = 500;                               // workgroups to aim for when K is split
+
+struct WgradArgs {
+  const float* src1;  // [c1][H][W]
+  const float* src2;  // [c2][H2][W2] or nullptr
+  int c1, c2, H, W, H2, W2, ups;
+  const float* dy;    // [c_out][H][W]
+  int c_out;
+  float* part;        // [4 splits][c_out][c1 + c2][9]
+  int tiles_x, n_tiles, tiles_per_split;
+};
+
+__global__ __launch_bounds__(256) void conv_wgrad_mfma_kernel(WgradArgs a) {
+  __shared__ float s_x[32 * kWgXStride];
+  __shared__ float s_dy[32 * kWgYStride];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int col = lane & 31, h = lane >> 5;
+  const int split = blockIdx.x, cob = blockIdx.y, cib = blockIdx.z;
+  const int c_in = a.c1 + a.c2;
+  f32x16 acc[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+  const float* pa = s_dy + col * kWgYStride + wave * kTileW + h;  // A[co = col][pixel 2 k + h] of the wave's row
+  const float* pb = s_x + col * kWgXStride + wave * kHaloW + h;   // B[pixel][ci = col]
+  const int t_end = min((split + 1) * a.tiles_per_split, a.n_tiles);
+  for (int t = split * a.tiles_per_split; t < t_end; ++t) {
+    const int x0 = (t % a.tiles_x) * kTileW, y0 = (t / a.tiles_x) * kWgH;
+    __syncthreads();  // the reads of the tile before
+    for (int e = tid; e < 32 * kWgHalo; e += 256) {
+      const int c = e / kWgHalo, r = e - c * kWgHalo, yy = r / kHaloW, xx = r - yy * kHaloW;
+      const int gc = cib * 32 + c;
+      const int y = min(max(y0 + yy - 1, 0), a.H - 1), x = min(max(x0 + xx - 1, 0), a.W - 1);  // replicate padding, as the forward
+      float v = 0.f;
+      if (gc < a.c1) v = a.src1[((size_t)gc * a.H + y) * a.W + x];
+      else if (gc < c_in) v = a.src2[((size_t)(gc - a.c1) * a.H2 + (y >> a.ups)) * a.W2 + (x >> a.ups)];
+      s_x[c * kWgXStride + r] = v;
+    }
+    for (int e = tid; e < 32 * kWgH * kTileW; e += 256) {
+      const int c = e / (kWgH * kTileW), r = e - c * (kWgH * kTileW), yy = r / kTileW, xx = r - yy * kTileW;
+      const int co = cob * 32 + c, y = y0 + yy, x = x0 + xx;
+      s_dy[c * kWgYStride + r] = (co < a.c_out && y < a.H && x < a.W) ? a.dy[((size_t)co * a.H + y) * a.W + x] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int k = 0; k < kTileW / 2; ++k) {
+      const float av = pa[2 * k];
+#pragma unroll
+      for (int tap = 0; tap < 9; ++tap) {
+        const float bv = pb[(tap / 3) * kHaloW + 2 * k + tap % 3];
+        acc[tap] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[tap], 0, 0, 0);
+      }
+    }
+  }
+  const int ci = cib * 32 + col;
+  if (ci >= c_in) return;
+  float* out = a.part + (size_t)(split * 4 + wave) * ((size_t)a.c_out * c_in * 9);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int co = cob * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;  // the 32x32 C/D map: row of register r in lane half h
+    if (co < a.c_out) {
+#pragma unroll
+      for (int tap = 0; tap < 9; ++tap) out[((size_t)co * c_in + ci) * 9 + tap] = acc[tap][r];
+    }
+  }
+}
+
+// grad[e] += scale x the partials of e added in float64 in their order, rounded once
+__global__ __launch_bounds__(256) void wgrad_fold_kernel(const float* part, int n_part, size_t n_w, float* grad, double scale) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n_w) return;
+  double s = 0.0;
+  for (int p = 0; p < n_part; ++p) s += (double)part[(size_t)p * n_w + e];
+  grad[e] += (float)(s * scale);
+}
+
+// grad[c] += scale x sum of dY[c]: stats_kernel's float64 sums, folded in order
+__global__ __launch_bounds__(256) void bias_grad_kernel(const double2* part, int S, int C, float* grad, double scale) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c < C) grad[c] += (float)(fold_segments(part + (size_t)c * S, S).x * scale);
+}
+
+// ------------------------------------------------------------------------------------------------- convolution, input gradient
+// The forward packing (unet_common.inc: pack_weights_kernel) of W'[ci][co][tap] = W[co][ci][8 - tap]: the GEMM's input channels
+// are the layer's output channels
+__global__ __launch_bounds__(256) void pack_dgrad_weights_kernel(const float* w, float* wpack, int c_in, int c_out, int n_chunks, int ncol, size_t total) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= total) return;
+  const int out_local = (int)(e % ncol);
+  size_t r = e / ncol;
+  const int kk = (int)(r % kKK);
+  r /= kKK;
+  const int ch = (int)(r % n_chunks), cb = (int)(r / n_chunks);
+  const int hh = kk & 1, tap = (kk >> 1) % 9, cp = (kk >> 1) / 9;
+  const int co = ch * kCK + cp * 2 + hh, ci = cb * ncol + out_local;  // of the layer
+  wpack[e] = (ci < c_in && co < c_out) ? w[((size_t)co * c_in + ci) * 9 + (8 - tap)] : 0.f;
+}
+
+// one pixel of the folded gradient of channel image e [(H + 2)][(W + 2)]: what the clamp sent to (y, x), added in float64
+__device__ double folded(const float* e, int H, int W, int y, int x) {
+  const int ya = y == 0 ? 0 : y + 1, yb = y == H - 1 ? H + 1 : y + 1;
+  const int xa = x == 0 ? 0 : x + 1, xb = x == W - 1 ? W + 1 : x + 1;
+  double s = 0.0;
+  for (int yy = ya; yy <= yb; ++yy)
+    for (int xx = xa; xx <= xb; ++xx) s += (double)e[(size_t)yy * (W + 2) + xx];
+  return s;
+}
+
+// out1 [c1][H][W] = fold(ext channels 0 .. c1); out2 [c2][H2][W2] = fold(ext channels c1 ..), summed over 2 x 2 blocks when ups
+__global__ __launch_bounds__(256) void dgrad_fold_kernel(const float* ext, int c1, int c2, int H, int W, int H2, int W2, int ups, float* out1, float* out2) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t n1 = (size_t)c1 * H * W, n2 = (size_t)c2 * H2 * W2, plane = (size_t)(H + 2) * (W + 2);
+  if (i < n1) {
+    const int x = (int)(i % W), y = (int)((i / W) % H), c = (int)(i / ((size_t)W * H));
+    out1[i] = (float)folded(ext + (size_t)c * plane, H, W, y, x);
+  } else if (i < n1 + n2) {
+    const size_t j = i - n1;
+    const int x2 = (int)(j % W2), y2 = (int)((j / W2) % H2), c = (int)(j / ((size_t)W2 * H2));
+    const float* e = ext + (size_t)(c1 + c) * plane;
+    double s = 0.0;
+    if (ups) {
+      for (int dy = 0; dy < 2; ++dy)
+        for (int dx = 0; dx < 2; ++dx)
+          if (2 * y2 + dy < H && 2 * x2 + dx < W) s += folded(e, H, W, 2 * y2 + dy, 2 * x2 + dx);
+    } else {
+      s = folded(e, H, W, y2, x2);
+    }
+    out2[j] = (float)s;
+  }
+}
+
+// ------------------------------------------------------------------------------------- instance norm + LeakyReLU, backward
+__device__ __forceinline__ double xhat_of(float y) { return y > 0.f ? (double)y : (double)y / (double)0.01f; }
+__device__ __forceinline__ double dxhat_of(float y, float dy) { return y > 0.f ? (double)dy : (double)0.01f * (double)dy; }
+
+// part[c][s] = (sum of d xh, sum of d xh xh) of segment s of channel c: stats_kernel's segments and tree
+__global__ __launch_bounds__(256) void norm_backward_stats_kernel(const float* y, const float* dy, size_t hw, int S, double2* part) {
+  __shared__ double s_a[256], s_b[256];
+  const int c = blockIdx.y, s = blockIdx.x, tid = threadIdx.x;
+  const size_t seg = (hw + S - 1) / S, lo = (size_t)s * seg, hi = min(lo + seg, hw);
+  const float* py = y + (size_t)c * hw;
+  const float* pd = dy + (size_t)c * hw;
+  double a = 0.0, b = 0.0;
+  for (size_t i = lo + tid; i < hi; i += 256) {
+    const double d = dxhat_of(py[i], pd[i]);
+    a += d;
+    b += d * xhat_of(py[i]);
+  }
+  s_a[tid] = a;
+  s_b[tid] = b;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) {
+      s_a[tid] += s_a[tid + w];
+      s_b[tid] += s_b[tid + w];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) part[(size_t)c * S + s] = make_double2(s_a[0], s_b[0]);
+}
+
+// dy <- dx, in place; fpart: the forward's sums of the layer (mean, rstd), bpart: norm_backward_stats_kernel's
+__global__ __launch_bounds__(256) void norm_backward_kernel(const float* y, float* dy, size_t hw, int S, const double2* fpart, const double2* bpart) {
+  __shared__ double s_rstd, s_m1, s_m2;
+  const int c = blockIdx.y;
+  if (threadIdx.x == 0) {
+    const double2 t = fold_segments(fpart + (size_t)c * S, S);
+    const double m = t.x / (double)hw, var = fmax(t.y / (double)hw - m * m, 0.0);
+    s_rstd = 1.0 / sqrt(var + 1e-5);
+    const double2 b = fold_segments(bpart + (size_t)c * S, S);
+    s_m1 = b.x / (double)hw;
+    s_m2 = b.y / (double)hw;
+  }
+  __syncthreads();
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= hw) return;
+  const size_t j = (size_t)c * hw + i;
+  dy[j] = (float)(s_rstd * (dxhat_of(y[j], dy[j]) - s_m1 - xhat_of(y[j]) * s_m2));
+}
+
+// ------------------------------------------------------------------------------------------------------------ small kernels
+// dx[first maximum of the window] += dy
+__global__ __launch_bounds__(256) void maxpool_backward_kernel(const float* x, const float* dy, float* dx, int C, int H, int W) {
+  const int Ho = H >> 1, Wo = W >> 1;
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)C * Ho * Wo) return;
+  const int xo = (int)(i % Wo), yo = (int)((i / Wo) % Ho), c = (int)(i / ((size_t)Wo * Ho));
+  const size_t base = ((size_t)c * H + 2 * yo) * W + 2 * xo;
+  const float* p = x + base;
+  const float m = fmaxf(fmaxf(p[0], p[1]), fmaxf(p[W], p[W + 1]));
+  const size_t at = p[0] == m ? 0 : p[1] == m ? 1 : p[W] == m ? (size_t)W : (size_t)W + 1;
+  dx[base + at] += dy[i];
+}
+
+struct Sums4 { double v[4]; };
+
+// part[s] = float64 sums over segment s of |m - t|, 0.5 (log v' + (m - t)^2 / v'), (lp - t)^2, (m - t)^2
+__global__ __launch_bounds__(256) void metrics_kernel(const float* lp, const float* m, const float* v, const float* t, size_t hw, int S, Sums4* part) {
+  __shared__ double s_v[4][256];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const size_t seg = (hw + S - 1) / S, lo = (size_t)s * seg, hi = min(lo + seg, hw);
+  double a[4] = {0.0, 0.0, 0.0, 0.0};
+  for (size_t i = lo + tid; i < hi; i += 256) {
+    const double d = (double)m[i] - (double)t[i], e = (double)lp[i] - (double)t[i];
+    a[0] += fabs(d);
+    if (v) {
+      const double vv = fmax((double)v[i], 1e-6);
+      a[1] += 0.5 * (log(vv) + d * d / vv);
+    }
+    a[2] += e * e;
+    a[3] += d * d;
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) s_v[k][tid] = a[k];
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) s_v[k][tid] += s_v[k][tid + w];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    Sums4 o;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o.v[k] = s_v[k][0];
+    part[s] = o;
+  }
+}
+
+// dL/dnet of the L1 loss through m = relu(lp + 10 tanh(net)); inv_n = 1 / N
+__global__ __launch_bounds__(256) void l1_grad_kernel(const float* m, const float* t, const float* net, float* g, size_t hw, double inv_n) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= hw) return;
+  const double d = (double)m[i] - (double)t[i], th = tanh((double)net[i]);
+  const double sign = d > 0.0 ? 1.0 : d < 0.0 ? -1.0 : 0.0;
+  g[i] = m[i] > 0.f ? (float)(sign * inv_n * 10.0 * (1.0 - th * th)) : 0.f;
+}
+
+// dL/ds of the Gaussian loss through v = m 0.1 sigmoid(s) + 1e-6, m held fixed
+__global__ __launch_bounds__(256) void nll_grad_kernel(const float* m, const float* v, const float* t, const float* s, float* g, size_t hw, double inv_n) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= hw) return;
+  float out = 0.f;
+  if ((double)v[i] > 1e-6) {
+    const double d = (double)m[i] - (double)t[i], vv = (double)v[i], sg = 1.0 / (1.0 + exp(-(double)s[i]));
+    out = (float)(0.5 * (1.0 / vv - d * d / (vv * vv)) * inv_n * (double)m[i] * 0.1 * sg * (1.0 - sg));
+  }
+  g[i] = out;
+}
+
+// step_size = lr / (1 - b1^t), inv_sqrt_bc2 = 1 / sqrt(1 - b2^t)
+__global__ __launch_bounds__(256) void adam_kernel(float* w, const float* g, float* m1, float* m2, size_t n, double b1, double b2, double step_size,
+                                                   double inv_sqrt_bc2) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double gv = g[i];
+  const double a = b1 * (double)m1[i] + (1.0 - b1) * gv, b = b2 * (double)m2[i] + (1.0 - b2) * gv * gv;
+  m1[i] = (float)a;
+  m2[i] = (float)b;
+  w[i] = (float)((double)w[i] - step_size * a / (sqrt(b) * inv_sqrt_bc2 + 1e-8));
+}
+
+// -------------------------------------------------------------------------------------------------------------------- host
+using Report = mcgpu_speedup_train_report;
+
+// Launches of the trainer.  The forward pass is NetPass::forward with this runner: norm_lrelu gives every normed layer of the pass
+// its own sums, in the order of the pass, for the backward to find.  Whole passes are timed, not single launches.
+struct TrainRunner : RunnerBase<Report> {
+  double2* d_part2 = nullptr;                       // the second image of the preprocessing
+  std::vector<double2*>* norm_parts = nullptr;      // of the net whose forward runs
+  size_t norm_i = 0;
+
+  void init(int device, int channels) {
+    RunnerBase::init(device, channels);
+    d_part2 = (double2*)alloc_bytes(kMaxSegments * sizeof(double2), true);
+  }
+  void conv(const ConvLayer& l, const float* src1, int c1, const float* src2, int ups, const Dims& D, float* out) { launch_conv(l, src1, c1, src2, ups, D, out); }
+  void maxpool(const float* x, float* y, int C, const Dims& D) { launch_maxpool(x, y, C, D); }
+  void norm_lrelu(const float* x, float* y, int C, size_t n) {
+    double2* part = norm_parts ? (*norm_parts)[norm_i++] : d_part;
+    stats(x, C, n, part);
+    hipLaunchKernelGGL(norm_lrelu_kernel, dim3(blocks_of(n), (unsigned)C), dim3(256), 0, nullptr, x, y, n, segments_of(n), part);
+  }
+  void preprocess(const float* lp, const float* fp, float* out, size_t hw) {
+    stats(lp, 1, hw, d_part);
+    stats(fp, 1, hw, d_part2);
+    hipLaunchKernelGGL(preprocess_kernel, dim3(blocks_of(hw)), dim3(256), 0, nullptr, fp, out, hw, segments_of(hw), d_part, d_part2);
+  }
+};
+
+// how K of a layer's weight gradient is split: tiles of 4 x 32 pixels per workgroup, 4 partials (waves) per workgroup
+struct WgradPlan {
+  int tiles_x, n_tiles, tiles_per_split, splits;
+  int partials() const { return 4 * splits; }
+};
+WgradPlan wgrad_plan(int c_in, int c_out, const Dims& D) {
+  WgradPlan p;
+  p.tiles_x = (D.W + kTileW - 1) / kTileW;
+  p.n_tiles = p.tiles_x * ((D.H + kWgH - 1) / kWgH);
+  const int blocks = ((c_out + 31) / 32) * ((c_in + 31) / 32);
+  const int want = std::min(p.n_tiles, std::max(1, (kWgTarget + blocks - 1) / blocks));
+  p.tiles_per_split = (p.n_tiles + want - 1) / want;
+  p.splits = (p.n_tiles + p.tiles_per_split - 1) / p.tiles_per_split;
+  return p;
+}
+size_t wgrad_part_floats(int c_in, int c_out, const Dims& D) { return (size_t)wgrad_plan(c_in, c_out, D).partials() * c_out * c_in * 9; }
+size_t dgrad_ext_floats(int c_in, const Dims& D) { return (size_t)c_in * (D.H + 2) * (D.W + 2); }
+
+// grad_w [c_out][c_in][9] += scale dW; grad_b [c_out] += scale db when grad_b
+void launch_wgrad(TrainRunner& R, int c_out, const float* src1, int c1, const float* src2, int c2, int ups, const Dims& D, const float* dy, float* part,
+                  float* grad_w, float* grad_b, double scale) {
+  const Dims E = ups ? D.halved_up() : D;
+  const WgradPlan p = wgrad_plan(c1 + c2, c_out, D);
+  WgradArgs a;
+  a.src1 = src1; a.src2 = src2; a.c1 = c1; a.c2 = c2; a.H = D.H; a.W = D.W; a.H2 = E.H; a.W2 = E.W; a.ups = ups ? 1 : 0;
+  a.dy = dy; a.c_out = c_out; a.part = part; a.tiles_x = p.tiles_x; a.n_tiles = p.n_tiles; a.tiles_per_split = p.tiles_per_split;
+  hipLaunchKernelGGL(conv_wgrad_mfma_kernel, dim3((unsigned)p.splits, (unsigned)((c_out + 31) / 32), (unsigned)((c1 + c2 + 31) / 32)), dim3(256), 0, nullptr, a);
+  const size_t n_w = (size_t)c_out * (c1 + c2) * 9;
+  hipLaunchKernelGGL(wgrad_fold_kernel, dim3(blocks_of(n_w)), dim3(256), 0, nullptr, part, p.partials(), n_w, grad_w, scale);
+  if (grad_b) {
+    R.stats(dy, c_out, D.voxels(), R.d_part);
+    hipLaunchKernelGGL(bias_grad_kernel, dim3(blocks_of((size_t)c_out)), dim3(256), 0, nullptr, R.d_part, segments_of(D.voxels()), c_out, grad_b, scale);
+  }
+}
+
+// the input-gradient GEMM of a layer: its input channels are the layer's output channels
+ConvLayer dgrad_layer(const ConvLayer& l) {
+  ConvLayer d;
+  d.c_in = l.c_out;
+  d.c_out = l.c_in;
+  d.nb = blocks_per_workgroup(d.c_out);
+  d.n_chunks = (d.c_in + kCK - 1) / kCK;
+  return d;
+}
+void launch_pack_dgrad(const ConvLayer& l, const ConvLayer& d, const float* d_w) {
+  const size_t total = d.pack_floats();
+  hipLaunchKernelGGL(pack_dgrad_weights_kernel, dim3(blocks_of(total)), dim3(256), 0, nullptr, d_w, d.wpack, l.c_in, l.c_out, d.n_chunks, 32 * d.nb, total);
+}
+void launch_pack_forward(const ConvLayer& l, const float* d_w) {
+  const size_t total = l.pack_floats();
+  hipLaunchKernelGGL(pack_weights_kernel<kTaps>, dim3(blocks_of(total)), dim3(256), 0, nullptr, d_w, l.wpack, l.c_in, l.c_out, l.n_chunks, 32 * l.nb, total);
+}
+
+// out1 [c1][H][W], out2 [c_in - c1][..] = the gradient of the layer's two sources; d: the layer's dgrad_layer, packed; d.bias: zeros
+void launch_dgrad(const ConvLayer& d, const float* dy, const Dims& D, float* ext, int c1, int ups, float* out1, float* out2) {
+  const Dims E = ups ? D.halved_up() : D;
+  ConvArgs a;
+  a.src1 = dy; a.src2 = nullptr; a.c1 = d.c_in; a.c2 = 0; a.H = D.H + 2; a.W = D.W + 2; a.H2 = D.H; a.W2 = D.W; a.ups = 0;
+  a.wpack = d.wpack; a.bias = d.bias; a.out = ext; a.c_out = d.c_out; a.n_chunks = d.n_chunks;
+  const dim3 grid((unsigned)((a.W + kTileW - 1) / kTileW), (unsigned)((a.H + kTileH - 1) / kTileH), (unsigned)((d.c_out + 32 * d.nb - 1) / (32 * d.nb)));
+  if (d.nb == 2) hipLaunchKernelGGL((conv3x3_mfma_kernel<2, true>), grid, dim3(256), 0, nullptr, a);
+  else hipLaunchKernelGGL((conv3x3_mfma_kernel<1, true>), grid, dim3(256), 0, nullptr, a);
+  const int c2 = d.c_out - c1;
+  const size_t n = (size_t)c1 * D.voxels() + (size_t)c2 * E.voxels();
+  hipLaunchKernelGGL(dgrad_fold_kernel, dim3(blocks_of(n)), dim3(256), 0, nullptr, ext, c1, c2, D.H, D.W, E.H, E.W, ups ? 1 : 0, out1, out2);
+}
+
+void launch_norm_backward(const float* y, float* dy, int C, size_t n, const double2* fpart, double2* bpart) {
+  const int S = segments_of(n);
+  hipLaunchKernelGGL(norm_backward_stats_kernel, dim3((unsigned)S, (unsigned)C), dim3(256), 0, nullptr, y, dy, n, S, bpart);
+  hipLaunchKernelGGL(norm_backward_kernel, dim3(blocks_of(n), (unsigned)C), dim3(256), 0, nullptr, y, dy, n, S, fpart, bpart);
+}
+
+void launch_maxpool_backward(const float* x, const float* dy, float* dx, int C, const Dims& D) {
+  const size_t n = (size_t)C * D.shifted(1).voxels();
+  if (n) hipLaunchKernelGGL(maxpool_backward_kernel, dim3(blocks_of(n)), dim3(256), 0, nullptr, x, dy, dx, C, D.H, D.W);
+}
+
+void launch_adam(float* w, const float* g, float* m1, float* m2, size_t n, double lr, double b1, double b2, unsigned long long t) {
+  const double step_size = lr / (1.0 - std::pow(b1, (double)t)), inv_sqrt_bc2 = 1.0 / std::sqrt(1.0 - std::pow(b2, (double)t));
+  hipLaunchKernelGGL(adam_kernel, dim3(blocks_of(n)), dim3(256), 0, nullptr, w, g, m1, m2, n, b1, b2, step_size, inv_sqrt_bc2);
+}
+
+// One FlexUNet of the trainer: its layers with both packings, the buffers of a forward pass and, mirrored, of the gradients
+struct TrainNet {
+  NetLayers layers;
+  size_t w_begin, w_end;  // its range of the flat weights
+  std::map<const ConvLayer*, ConvLayer> dgrad;
+  std::vector<double2*> parts;  // the sums of each normed layer, in the order of the forward pass
+  std::unique_ptr<NetPass<TrainRunner, Dims>> act, grad;
+  size_t part_floats = 0, ext_floats = 0;
+
+  TrainNet(const NetShape& s, size_t& cursor, TrainRunner& R, const Dims& P, float* d_w, const float* d_zero) : layers(layers_of(s, cursor)) {
+    w_end = cursor;
+    w_begin = layers.init.w_off;
+    layers.each([&](ConvLayer& l) {
+      l.nb = blocks_per_workgroup(l.c_out);
+      l.wpack = (float*)R.alloc_bytes(l.pack_floats() * sizeof(float), false);
+      l.bias = d_w + l.b_off;
+      ConvLayer d = dgrad_layer(l);
+      d.wpack = (float*)R.alloc_bytes(d.pack_floats() * sizeof(float), false);
+      d.bias = d_zero;
+      dgrad[&l] = d;
+    });
+    act.reset(new NetPass<TrainRunner, Dims>(layers, R, P));
+    grad.reset(new NetPass<TrainRunner, Dims>(layers, R, P));
+    auto sums = [&](int c) { parts.push_back((double2*)R.alloc_bytes((size_t)c * kMaxSegments * sizeof(double2), true)); };
+    for (int i = 0; i < layers.L; ++i) { sums(layers.skip_c[i + 1]); sums(layers.skip_c[i + 1]); }
+    for (int i = layers.L - 1; i >= 0; --i) { sums(layers.dec_c[i]); sums(layers.dec_c[i]); }
+    auto need = [&](const ConvLayer& l, const Dims& D) {
+      part_floats = std::max(part_floats, wgrad_part_floats(l.c_in, l.c_out, D));
+      ext_floats = std::max(ext_floats, dgrad_ext_floats(l.c_in, D));
+    };
+    need(layers.init, P);
+    need(layers.final, P);
+    for (int i = 0; i < layers.L; ++i) {
+      need(layers.enc[2 * i], P.shifted(i + 1)); need(layers.enc[2 * i + 1], P.shifted(i + 1));
+      need(layers.dec[2 * i], P.shifted(i)); need(layers.dec[2 * i + 1], P.shifted(i));
+    }
+  }
+  void pack(const float* d_w) {
+    layers.each([&](ConvLayer& l) {
+      launch_pack_forward(l, d_w + l.w_off);
+      launch_pack_dgrad(l, dgrad[&l], d_w + l.w_off);
+    });
+  }
+  // the sums of the k-th normed layer of the forward pass: enc_i first, second = 2 i, 2 i + 1; dec_i = 2 L + 2 (L - 1 - i) (+ 1)
+  double2* enc_part(int i, int second) { return parts[2 * i + second]; }
+  double2* dec_part(int i, int second) { return parts[2 * layers.L + 2 * (layers.L - 1 - i) + second]; }
+};
+
+}  // namespace
+
+struct mcgpu_speedup_trainer {
+  mcgpu_speedup_train_options o;
+  TrainRunner R;
+  Dims P;
+  size_t hw = 0, n_w = 0;
+  float *d_w = nullptr, *d_m1 = nullptr, *d_m2 = nullptr, *d_grad = nullptr, *d_zero = nullptr;
+  float *d_x = nullptr, *d_fp = nullptr, *d_t = nullptr, *d_mean = nullptr, *d_var = nullptr, *d_part = nullptr, *d_ext = nullptr;
+  double2* d_bpart = nullptr;
+  Sums4* d_sums = nullptr;
+  std::unique_ptr<TrainNet> mean_net, var_net;
+  unsigned long long step_mean = 0, step_var = 0;
+  double lr = 0.0;
+};
+
+namespace {
+
+using Trainer = mcgpu_speedup_trainer;
+
+void check_create(const char* fn, const mcgpu_speedup_train_options& o) {
+  if (o.nu < 1 || o.nv < 1 || o.max_batch < 1) refuse(fn, "nu, nv and max_batch must be >= 1");
+  if ((unsigned long long)o.nu * (unsigned long long)o.nv > 0x7fffffffull) refuse(fn, "nu x nv must be below 2^31");
+  if (!o.weights) refuse(fn, "weights is NULL");
+  const NetShape m{o.mean_in_channels, o.mean_levels, o.mean_filter_base}, v{o.var_in_channels, o.var_levels, o.var_filter_base};
+  if (!shape_ok(m) || !shape_ok(v) || m.in_channels > 2 || v.in_channels != 1)
+    refuse(fn, "bad architecture: mean_in_channels 1 or 2, var_in_channels 1, levels 1..8, filter_base 1..1024");
+  size_t expect = 0;
+  layers_of(m, expect);
+  layers_of(v, expect);
+  if (o.n_weights != expect)
+    refuse(fn, "n_weights is " + std::to_string(o.n_weights) + " but the architecture has " + std::to_string(expect) + " values");
+  const int deep = std::max(m.levels, v.levels);
+  if (o.nu % (1 << deep) || o.nv % (1 << deep))
+    refuse(fn, "nu and nv must be divisible by " + std::to_string(1 << deep) + " (2^levels): " + std::to_string(o.nu) + " x " + std::to_string(o.nv));
+  if ((size_t)(o.nu >> deep) * (o.nv >> deep) < 2)
+    refuse(fn, "the bottleneck of a " + std::to_string(o.nu) + " x " + std::to_string(o.nv) + " image has fewer than 2 pixels: instance norm is undefined");
+  if (!(o.lr > 0.0) || !(o.gamma > 0.0 && o.gamma <= 1.0)) refuse(fn, "lr must be > 0 and gamma in (0, 1]");
+  if (!(o.beta1 >= 0.0 && o.beta1 < 1.0) || !(o.beta2 >= 0.0 && o.beta2 < 1.0)) refuse(fn, "beta1 and beta2 must be in [0, 1)");
+}
+
+void check_batch(const char* fn, const Trainer* T, int phase, int n, const float* lp, const float* fp, const float* t, bool need_target) {
+  if (!T) refuse(fn, "handle is NULL");
+  if (phase != MCGPU_SPEEDUP_PHASE_MEAN && phase != MCGPU_SPEEDUP_PHASE_VARIANCE) refuse(fn, "unknown phase " + std::to_string(phase));
+  if (n < 1 || n > T->o.max_batch) refuse(fn, "n is " + std::to_string(n) + " but the trainer was created for 1.." + std::to_string(T->o.max_batch));
+  if (!lp) refuse(fn, "low_photon is NULL");
+  if (need_target && !t) refuse(fn, "high_photon is NULL");
+  if (T->o.mean_in_channels == 2 && !fp) refuse(fn, "forward_projection is NULL but the mean net has 2 input channels");
+  if (T->o.mean_in_channels == 1 && fp) refuse(fn, "the mean net has 1 input channel: forward_projection must be NULL");
+  if (fp) {
+    const int p = constant_slice(fp, n, T->hw);
+    if (p >= 0) refuse(fn, "forward_projection slice " + std::to_string(p) + " has zero variance: it cannot be matched to the low-photon projection");
+  }
+}
+
+void check_live(const char* fn, Trainer* T) {
+  if (T->R.dry) refuse(fn, "the handle is a dry plan: nothing runs on it");
+  HIP_TRY(hipSetDevice(T->o.device));
+}
+
+// mean and variance of sample p on the device (d_x, d_mean, d_var), every layer's output and sums kept for the backward
+void forward_sample(Trainer& T, const float* lp, const float* fp, int p) {
+  TrainRunner& R = T.R;
+  const size_t hw = T.hw;
+  HIP_TRY(hipMemcpy(T.d_x, lp + (size_t)p * hw, hw * 4, hipMemcpyHostToDevice));
+  if (fp) {
+    HIP_TRY(hipMemcpy(T.d_fp, fp + (size_t)p * hw, hw * 4, hipMemcpyHostToDevice));
+    R.preprocess(T.d_x, T.d_fp, T.d_x + hw, hw);
+  }
+  R.norm_parts = &T.mean_net->parts;
+  R.norm_i = 0;
+  const float* net_mean = T.mean_net->act->forward(T.d_x);
+  hipLaunchKernelGGL(head_mean_kernel, dim3(blocks_of(hw)), dim3(256), 0, nullptr, T.d_x, net_mean, T.d_mean, hw);
+  R.norm_parts = &T.var_net->parts;
+  R.norm_i = 0;
+  const float* net_var = T.var_net->act->forward(T.d_mean);
+  hipLaunchKernelGGL(head_variance_kernel, dim3(blocks_of(hw)), dim3(256), 0, nullptr, T.d_mean, net_var, T.d_var, hw);
+  R.norm_parts = nullptr;
+}
+
+// The gradient of one sample added to d_grad: NetPass::forward walked in reverse.  x: the net's input; grad->out holds dL/d(output).
+void backward_sample(Trainer& T, TrainNet& N, const float* x, double scale) {
+  TrainRunner& R = T.R;
+  NetLayers& net = N.layers;
+  auto& A = *N.act;
+  auto& G = *N.grad;
+  const int L = net.L;
+  const Dims P = T.P;
+  auto wgrad = [&](const ConvLayer& l, const float* s1, int c1, const float* s2, int ups, const Dims& D, const float* dy, bool bias) {
+    Stage st(R.dev, R.rep.ms_wgrad);
+    launch_wgrad(R, l.c_out, s1, c1, s2, l.c_in - c1, ups, D, dy, T.d_part, T.d_grad + l.w_off, bias ? T.d_grad + l.b_off : nullptr, scale);
+    st.done();
+  };
+  auto dgrad = [&](const ConvLayer& l, const float* dy, const Dims& D, int c1, int ups, float* o1, float* o2) {
+    Stage st(R.dev, R.rep.ms_dgrad);
+    launch_dgrad(N.dgrad[&l], dy, D, T.d_ext, c1, ups, o1, o2);
+    st.done();
+  };
+  auto norm = [&](const float* y, float* dy, int c, const Dims& D, const double2* fpart) {
+    Stage st(R.dev, R.rep.ms_norm);
+    launch_norm_backward(y, dy, c, D.voxels(), fpart, T.d_bpart);
+    st.done();
+  };
+  wgrad(net.final, A.dec_b[0], net.final.c_in, nullptr, 0, P, G.out, true);
+  dgrad(net.final, G.out, P, net.final.c_in, 0, G.dec_b[0], nullptr);
+  for (int i = 0; i < L; ++i) {
+    const Dims D = P.shifted(i);
+    const int c = net.dec_c[i];
+    const float* cur = i == L - 1 ? A.skip[L] : A.dec_b[i + 1];
+    float* g_cur = i == L - 1 ? G.skip[L] : G.dec_b[i + 1];
+    norm(A.dec_b[i], G.dec_b[i], c, D, N.dec_part(i, 1));
+    wgrad(net.dec[2 * i + 1], A.dec_a[i], c, nullptr, 0, D, G.dec_b[i], false);
+    dgrad(net.dec[2 * i + 1], G.dec_b[i], D, c, 0, G.dec_a[i], nullptr);
+    norm(A.dec_a[i], G.dec_a[i], c, D, N.dec_part(i, 0));
+    wgrad(net.dec[2 * i], A.skip[i], net.skip_c[i], cur, 1, D, G.dec_a[i], false);
+    dgrad(net.dec[2 * i], G.dec_a[i], D, net.skip_c[i], 1, G.skip[i], g_cur);
+  }
+  for (int i = L - 1; i >= 0; --i) {
+    const Dims D = P.shifted(i + 1);
+    const int c = net.skip_c[i + 1];
+    norm(A.skip[i + 1], G.skip[i + 1], c, D, N.enc_part(i, 1));
+    wgrad(net.enc[2 * i + 1], A.enc_a[i], c, nullptr, 0, D, G.skip[i + 1], false);
+    dgrad(net.enc[2 * i + 1], G.skip[i + 1], D, c, 0, G.enc_a[i], nullptr);
+    norm(A.enc_a[i], G.enc_a[i], c, D, N.enc_part(i, 0));
+    wgrad(net.enc[2 * i], A.pooled[i], net.skip_c[i], nullptr, 0, D, G.enc_a[i], false);
+    dgrad(net.enc[2 * i], G.enc_a[i], D, net.skip_c[i], 0, G.pooled[i], nullptr);
+    {
+      Stage st(R.dev, R.rep.ms_dgrad);
+      launch_maxpool_backward(A.skip[i], G.pooled[i], G.skip[i], net.skip_c[i], P.shifted(i));
+      st.done();
+    }
+  }
+  wgrad(net.init, x, net.in_channels, nullptr, 0, P, G.skip[0], true);
+}
+
+struct BatchSums { double v[4] = {0.0, 0.0, 0.0, 0.0}; };
+
+// forward of every sample, its sums, and (with `gradient`) its gradient of the phase's loss added to d_grad
+void run_batch(Trainer& T, int phase, int n, const float* lp, const float* fp, const float* t, bool gradient, BatchSums& sums) {
+  TrainRunner& R = T.R;
+  const size_t hw = T.hw;
+  const int S = segments_of(hw);
+  // A sample's backward pass runs on the gradient of ITS mean loss (1 / (nv nu)) and is the same bytes in any batch; the share 1 / B
+  // of the batch is applied where the sample's gradient is rounded to float32 and added to the batch's
+  const double inv_hw = 1.0 / (double)hw, inv_b = 1.0 / (double)n;
+  if (gradient) HIP_TRY(hipMemset(T.d_grad, 0, T.n_w * 4));
+  std::vector<Sums4> host((size_t)S * n);
+  for (int p = 0; p < n; ++p) {
+    {
+      Stage st(R.dev, R.rep.ms_forward);
+      forward_sample(T, lp, fp, p);
+      HIP_TRY(hipMemcpy(T.d_t, t + (size_t)p * hw, hw * 4, hipMemcpyHostToDevice));
+      hipLaunchKernelGGL(metrics_kernel, dim3((unsigned)S), dim3(256), 0, nullptr, T.d_x, T.d_mean, T.d_var, T.d_t, hw, S, T.d_sums + (size_t)p * S);
+      st.done();
+    }
+    if (!gradient) continue;
+    if (phase == MCGPU_SPEEDUP_PHASE_MEAN) {
+      hipLaunchKernelGGL(l1_grad_kernel, dim3(blocks_of(hw)), dim3(256), 0, nullptr, T.d_mean, T.d_t, T.mean_net->act->out, T.mean_net->grad->out, hw, inv_hw);
+      backward_sample(T, *T.mean_net, T.d_x, inv_b);
+    } else {
+      hipLaunchKernelGGL(nll_grad_kernel, dim3(blocks_of(hw)), dim3(256), 0, nullptr, T.d_mean, T.d_var, T.d_t, T.var_net->act->out, T.var_net->grad->out, hw,
+                         inv_hw);
+      backward_sample(T, *T.var_net, T.d_mean, inv_b);
+    }
+  }
+  HIP_TRY(hipMemcpy(host.data(), T.d_sums, host.size() * sizeof(Sums4), hipMemcpyDeviceToHost));  // once per batch; waits for the device
+  for (size_t s = 0; s < host.size(); ++s)  // samples in order, segments in order
+    for (int k = 0; k < 4; ++k) sums.v[k] += host[s].v[k];
+}
+
+void fill_report(Trainer& T, int phase, int n, const BatchSums& s, const std::chrono::steady_clock::time_point& t0, Report* report) {
+  const double N = (double)n * (double)T.hw;
+  Report& r = T.R.rep;
+  r.phase = phase;
+  r.l1_loss = s.v[0] / N;
+  r.gaussian_nll_loss = s.v[1] / N;
+  r.loss = phase == MCGPU_SPEEDUP_PHASE_MEAN ? r.l1_loss : r.gaussian_nll_loss;
+  r.psnr_before = 20.0 * std::log10(8.711442 / std::sqrt(s.v[2] / N));
+  r.psnr_after = 20.0 * std::log10(8.711442 / std::sqrt(s.v[3] / N));
+  r.step = T.step_mean + T.step_var;
+  r.lr = T.lr;
+  r.peak_device_bytes = T.R.dev.peak;
+  r.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  mcgpu::write_report(report, r);
+}
+
+void clear_times(Report& r) { r.ms_forward = r.ms_wgrad = r.ms_dgrad = r.ms_norm = r.ms_optimizer = r.ms_total = 0.0; }
+
+void check_state(const char* fn, const Trainer* T, const mcgpu_speedup_train_state& s) {
+  if ((s.weights || s.moment1 || s.moment2) && s.n_weights != T->n_w)
+    refuse(fn, "n_weights is " + std::to_string(s.n_weights) + " but the trainer has " + std::to_string(T->n_w) + " values");
+}
+
+}  // namespace
+
+extern "C" int mcgpu_speedup_train_create(const mcgpu_speedup_train_options* caller_o, mcgpu_speedup_trainer** handle) {
+  ABI_BEGIN
+  const char* fn = "mcgpu_speedup_train_create";
+  if (!handle) refuse(fn, "handle is NULL");
+  *handle = nullptr;
+  std::unique_ptr<Trainer> T(new Trainer);
+  mcgpu::read_options(fn, "mcgpu_speedup_train_options", caller_o, T->o);
+  const mcgpu_speedup_train_options& o = T->o;
+  check_create(fn, o);
+  TrainRunner& R = T->R;
+  R.dry = o.dry != 0;
+  T->P = Dims{o.nv, o.nu};
+  T->hw = T->P.voxels();
+  T->n_w = (size_t)o.n_weights;
+  T->lr = o.lr;
+  const size_t hw = T->hw;
+  const NetShape ms{o.mean_in_channels, o.mean_levels, o.mean_filter_base}, vs{o.var_in_channels, o.var_levels, o.var_filter_base};
+  int widest = 1;
+  {
+    size_t c = 0;
+    widest = std::max(layers_of(ms, c).widest(), layers_of(vs, c).widest());
+  }
+  R.init(o.device, widest);
+  T->d_w = R.upload(o.weights, T->n_w);
+  T->d_m1 = R.alloc(T->n_w);
+  T->d_m2 = R.alloc(T->n_w);
+  T->d_grad = R.alloc(T->n_w);
+  T->d_zero = R.alloc((size_t)2 * widest + 2);  // the bias of the input-gradient GEMMs: as many as the widest concatenated input has channels
+  T->d_x = R.alloc(2 * hw);  // channel 0: the low-photon projection, channel 1: the matched forward projection
+  T->d_fp = R.alloc(hw);
+  T->d_t = R.alloc(hw);
+  T->d_mean = R.alloc(hw);
+  T->d_var = R.alloc(hw);
+  T->d_bpart = (double2*)R.alloc_bytes((size_t)widest * kMaxSegments * sizeof(double2), true);
+  T->d_sums = (Sums4*)R.alloc_bytes((size_t)o.max_batch * kMaxSegments * sizeof(Sums4), true);  // of every sample of a batch
+  size_t cursor = 0;
+  T->mean_net.reset(new TrainNet(ms, cursor, R, T->P, T->d_w, T->d_zero));
+  T->var_net.reset(new TrainNet(vs, cursor, R, T->P, T->d_w, T->d_zero));
+  T->d_part = R.alloc(std::max(T->mean_net->part_floats, T->var_net->part_floats));
+  T->d_ext = R.alloc(std::max(T->mean_net->ext_floats, T->var_net->ext_floats));
+  if (!R.dry) {
+    T->mean_net->pack(T->d_w);
+    T->var_net->pack(T->d_w);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+  }
+  *handle = T.release();
+  return 0;
+  ABI_END
+}
+
+extern "C" int mcgpu_speedup_train_step(mcgpu_speedup_trainer* T, int phase, int n, const float* low_photon, const float* forward_projection,
+                                        const float* high_photon, int update, mcgpu_speedup_train_report* report) {
+  ABI_BEGIN
+  const char* fn = "mcgpu_speedup_train_step";
+  check_batch(fn, T, phase, n, low_photon, forward_projection, high_photon, true);
+  mcgpu::check_report(fn, "report", "mcgpu_speedup_train_report", report);
+  check_live(fn, T);
+  const auto t0 = std::chrono::steady_clock::now();
+  clear_times(T->R.rep);
+  BatchSums sums;
+  run_batch(*T, phase, n, low_photon, forward_projection, high_photon, update != 0, sums);
+  if (update) {
+    Stage st(T->R.dev, T->R.rep.ms_optimizer);
+    TrainNet& N = phase == MCGPU_SPEEDUP_PHASE_MEAN ? *T->mean_net : *T->var_net;
+    unsigned long long& t = phase == MCGPU_SPEEDUP_PHASE_MEAN ? T->step_mean : T->step_var;
+    ++t;
+    launch_adam(T->d_w + N.w_begin, T->d_grad + N.w_begin, T->d_m1 + N.w_begin, T->d_m2 + N.w_begin, N.w_end - N.w_begin, T->lr, T->o.beta1, T->o.beta2, t);
+    N.pack(T->d_w);
+    st.done();
+    T->lr *= T->o.gamma;
+  }
+  fill_report(*T, phase, n, sums, t0, report);
+  return 0;
+  ABI_END
+}
+
+extern "C" int mcgpu_speedup_train_gradients(mcgpu_speedup_trainer* T, int phase, int n, const float* low_photon, const float* forward_projection,
+                                             const float* high_photon, float* flat_gradient, mcgpu_speedup_train_report* report) {
+  ABI_BEGIN
+  const char* fn = "mcgpu_speedup_train_gradients";
+  check_batch(fn, T, phase, n, low_photon, forward_projection, high_photon, true);
+  if (!flat_gradient) refuse(fn, "flat_gradient is NULL");
+  mcgpu::check_report(fn, "report", "mcgpu_speedup_train_report", report);
+  check_live(fn, T);
+  const auto t0 = std::chrono::steady_clock::now();
+  clear_times(T->R.rep);
+  BatchSums sums;
+  run_batch(*T, phase, n, low_photon, forward_projection, high_photon, true, sums);
+  HIP_TRY(hipMemcpy(flat_gradient, T->d_grad, T->n_w * 4, hipMemcpyDeviceToHost));
+  fill_report(*T, phase, n, sums, t0, report);
+  return 0;
+  ABI_END
+}
+
+extern "C" int mcgpu_speedup_train_predict(mcgpu_speedup_trainer* T, int n, const float* low_photon, const float* forward_projection, float* mean,
+                                           float* variance) {
+  ABI_BEGIN
+  const char* fn = "mcgpu_speedup_train_predict";
+  check_batch(fn, T, MCGPU_SPEEDUP_PHASE_MEAN, n, low_photon, forward_projection, nullptr, false);
+  check_live(fn, T);
+  for (int p = 0; p < n; ++p) {
+    forward_sample(*T, low_photon, forward_projection, p);
+    HIP_TRY(hipGetLastError());
+    if (mean) HIP_TRY(hipMemcpy(mean + (size_t)p * T->hw, T->d_mean, T->hw * 4, hipMemcpyDeviceToHost));
+    if (variance) HIP_TRY(hipMemcpy(variance + (size_t)p * T->hw, T->d_var, T->hw * 4, hipMemcpyDeviceToHost));
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  return 0;
+  ABI_END
+}
+
+extern "C" int mcgpu_speedup_train_get_state(mcgpu_speedup_trainer* T, mcgpu_speedup_train_state* caller_s) {
+  ABI_BEGIN
+  const char* fn = "mcgpu_speedup_train_get_state";
+  if (!T) refuse(fn, "handle is NULL");
+  mcgpu_speedup_train_state s;
+  mcgpu::read_options(fn, "mcgpu_speedup_train_state", caller_s, s);
+  check_state(fn, T, s);
+  if (s.weights || s.moment1 || s.moment2) {
+    check_live(fn, T);
+    if (s.weights) HIP_TRY(hipMemcpy(s.weights, T->d_w, T->n_w * 4, hipMemcpyDeviceToHost));
+    if (s.moment1) HIP_TRY(hipMemcpy(s.moment1, T->d_m1, T->n_w * 4, hipMemcpyDeviceToHost));
+    if (s.moment2) HIP_TRY(hipMemcpy(s.moment2, T->d_m2, T->n_w * 4, hipMemcpyDeviceToHost));
+  }
+  s.n_weights = T->n_w;
+  s.step_mean = T->step_mean;
+  s.step_variance = T->step_var;
+  s.lr = T->lr;
+  s.planned_device_bytes = T->R.dry ? T->R.planned : T->R.dev.held;
+  mcgpu::write_report(caller_s, s);
+  return 0;
+  ABI_END
+}
+
+extern "C" int mcgpu_speedup_train_set_state(mcgpu_speedup_trainer* T, const mcgpu_speedup_train_state* caller_s) {
+  ABI_BEGIN
+  const char* fn = "mcgpu_speedup_train_set_state";
+  if (!T) refuse(fn, "handle is NULL");
+  mcgpu_speedup_train_state s;
+  mcgpu::read_options(fn, "mcgpu_speedup_train_state", caller_s, s);
+  check_state(fn, T, s);
+  if (!(s.lr > 0.0)) refuse(fn, "lr must be > 0");
+  if (s.weights || s.moment1 || s.moment2) {
+    check_live(fn, T);
+    if (s.weights) HIP_TRY(hipMemcpy(T->d_w, s.weights, T->n_w * 4, hipMemcpyHostToDevice));
+    if (s.moment1) HIP_TRY(hipMemcpy(T->d_m1, s.moment1, T->n_w * 4, hipMemcpyHostToDevice));
+    if (s.moment2) HIP_TRY(hipMemcpy(T->d_m2, s.moment2, T->n_w * 4, hipMemcpyHostToDevice));
+    if (s.weights) {
+      T->mean_net->pack(T->d_w);
+      T->var_net->pack(T->d_w);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipDeviceSynchronize());
+    }
+  }
+  T->step_mean = s.step_mean;
+  T->step_var = s.step_variance;
+  T->lr = s.lr;
+  return 0;
+  ABI_END
+}
+
+extern "C" int mcgpu_speedup_train_destroy(mcgpu_speedup_trainer* T) {
+  ABI_BEGIN
+  if (!T) return 0;
+  if (!T->R.dry) (void)hipSetDevice(T->o.device);
+  delete T;
+  return 0;
+  ABI_END
+}
+
+extern "C" int mcgpu_speedup_train_stage(int stage, const mcgpu_speedup_train_stage_args* caller_a, mcgpu_speedup_train_report* report) {
+  ABI_BEGIN
+  const char* fn = "mcgpu_speedup_train_stage";
+  mcgpu_speedup_train_stage_args a;
+  mcgpu::read_options(fn, "mcgpu_speedup_train_stage_args", caller_a, a);
+  mcgpu::check_report(fn, "report", "mcgpu_speedup_train_report", report);
+  if (stage < MCGPU_SPEEDUP_TRAIN_STAGE_CONV_WGRAD || stage > MCGPU_SPEEDUP_TRAIN_STAGE_ADAM) refuse(fn, "unknown stage " + std::to_string(stage));
+  if (!a.in || !a.out) refuse(fn, "in or out is NULL");
+  const bool conv = stage <= MCGPU_SPEEDUP_TRAIN_STAGE_CONV_DGRAD, loss = stage == MCGPU_SPEEDUP_TRAIN_STAGE_LOSS_L1 || stage == MCGPU_SPEEDUP_TRAIN_STAGE_LOSS_NLL;
+  if (stage != MCGPU_SPEEDUP_TRAIN_STAGE_ADAM) {
+    if (a.nu < 1 || a.nv < 1 || (unsigned long long)a.nu * (unsigned long long)a.nv > 0x7fffffffull) refuse(fn, "nu and nv must be >= 1 and nu x nv below 2^31");
+    if (!a.in2 && stage != MCGPU_SPEEDUP_TRAIN_STAGE_CONV_WGRAD) refuse(fn, "in2 is NULL");
+  }
+  if (stage <= MCGPU_SPEEDUP_TRAIN_STAGE_MAXPOOL_BACKWARD && (a.c1 < 1 || a.c1 > 65536)) refuse(fn, "c1 must be 1..65536");
+  if (conv && (a.c2 < 0 || a.c2 > 65536 || a.c_out < 1 || a.c_out > 65536)) refuse(fn, "c2 must be 0..65536 and c_out 1..65536");
+  if (stage == MCGPU_SPEEDUP_TRAIN_STAGE_CONV_WGRAD && (!a.in3 || (a.c2 > 0 && !a.in2))) refuse(fn, "in2 or in3 is NULL");
+  if (stage == MCGPU_SPEEDUP_TRAIN_STAGE_CONV_DGRAD && a.c2 > 0 && !a.out2) refuse(fn, "out2 is NULL");
+  if (stage == MCGPU_SPEEDUP_TRAIN_STAGE_NORM_LRELU_BACKWARD && (size_t)a.nu * a.nv < 2) refuse(fn, "instance norm needs at least 2 pixels");
+  if (loss && (!a.in3 || !a.values || a.n < 1)) refuse(fn, "in3 or values is NULL, or n is 0");
+  if (stage == MCGPU_SPEEDUP_TRAIN_STAGE_ADAM) {
+    if (!a.out2 || !a.out3 || a.n < 1 || a.step < 1) refuse(fn, "out2 or out3 is NULL, or n or step is 0");
+    if (!(a.beta1 >= 0.0 && a.beta1 < 1.0) || !(a.beta2 >= 0.0 && a.beta2 < 1.0)) refuse(fn, "beta1 and beta2 must be in [0, 1)");
+  }
+  const auto t0 = std::chrono::steady_clock::now();
+  TrainRunner R;
+  R.init(a.device, std::max(std::max(a.c1, a.c_out), 1));
+  const Dims D{a.nv, a.nu};
+  const size_t hw = D.voxels();
+  switch (stage) {
+    case MCGPU_SPEEDUP_TRAIN_STAGE_CONV_WGRAD: {
+      const Dims E = a.upsample ? D.halved_up() : D;
+      const int c_in = a.c1 + a.c2;
+      const float* d_in = R.upload(a.in, (size_t)a.c1 * hw);
+      const float* d_in2 = a.c2 ? R.upload(a.in2, (size_t)a.c2 * E.voxels()) : nullptr;
+      const float* d_dy = R.upload(a.in3, (size_t)a.c_out * hw);
+      float* d_part = R.alloc(wgrad_part_floats(c_in, a.c_out, D));
+      const size_t n_w = (size_t)a.c_out * c_in * 9;
+      float* d_grad = R.alloc(n_w + a.c_out);
+      Stage st(R.dev, R.rep.ms_wgrad);
+      launch_wgrad(R, a.c_out, d_in, a.c1, d_in2, a.c2, a.upsample, D, d_dy, d_part, d_grad, d_grad + n_w, 1.0);
+      st.done();
+      HIP_TRY(hipMemcpy(a.out, d_grad, n_w * 4, hipMemcpyDeviceToHost));
+      if (a.out2) HIP_TRY(hipMemcpy(a.out2, d_grad + n_w, (size_t)a.c_out * 4, hipMemcpyDeviceToHost));
+      if (a.values) a.values[0] = (double)wgrad_plan(c_in, a.c_out, D).partials();
+      break;
+    }
+    case MCGPU_SPEEDUP_TRAIN_STAGE_CONV_DGRAD: {
+      const Dims E = a.upsample ? D.halved_up() : D;
+      size_t cursor = 0;
+      ConvLayer l = conv_layer(a.c1 + a.c2, a.c_out, cursor);
+      ConvLayer d = dgrad_layer(l);
+      const float* d_dy = R.upload(a.in, (size_t)a.c_out * hw);
+      const float* d_w = R.upload(a.in2, (size_t)a.c_out * l.c_in * 9);
+      d.wpack = R.alloc(d.pack_floats());
+      d.bias = R.alloc((size_t)d.c_out);
+      float* d_ext = R.alloc(dgrad_ext_floats(l.c_in, D));
+      float* d_o1 = R.alloc((size_t)a.c1 * hw);
+      float* d_o2 = R.alloc((size_t)std::max(a.c2, 1) * E.voxels());
+      launch_pack_dgrad(l, d, d_w);
+      Stage st(R.dev, R.rep.ms_dgrad);
+      launch_dgrad(d, d_dy, D, d_ext, a.c1, a.upsample, d_o1, d_o2);
+      st.done();
+      HIP_TRY(hipMemcpy(a.out, d_o1, (size_t)a.c1 * hw * 4, hipMemcpyDeviceToHost));
+      if (a.c2) HIP_TRY(hipMemcpy(a.out2, d_o2, (size_t)a.c2 * E.voxels() * 4, hipMemcpyDeviceToHost));
+      break;
+    }
+    case MCGPU_SPEEDUP_TRAIN_STAGE_NORM_LRELU_BACKWARD: {
+      const float* d_x = R.upload(a.in, (size_t)a.c1 * hw);
+      float* d_dy = R.upload(a.in2, (size_t)a.c1 * hw);
+      float* d_y = R.alloc((size_t)a.c1 * hw);
+      double2* d_bpart = (double2*)R.alloc_bytes((size_t)a.c1 * kMaxSegments * sizeof(double2), true);
+      R.norm_lrelu(d_x, d_y, a.c1, hw);
+      Stage st(R.dev, R.rep.ms_norm);
+      launch_norm_backward(d_y, d_dy, a.c1, hw, R.d_part, d_bpart);
+      st.done();
+      HIP_TRY(hipMemcpy(a.out, d_dy, (size_t)a.c1 * hw * 4, hipMemcpyDeviceToHost));
+      break;
+    }
+    case MCGPU_SPEEDUP_TRAIN_STAGE_MAXPOOL_BACKWARD: {
+      const float* d_x = R.upload(a.in, (size_t)a.c1 * hw);
+      const size_t n_dy = (size_t)a.c1 * D.shifted(1).voxels();
+      const float* d_dy = R.upload(a.in2, std::max<size_t>(n_dy, 1));
+      float* d_dx = R.alloc((size_t)a.c1 * hw);
+      Stage st(R.dev, R.rep.ms_dgrad);
+      launch_maxpool_backward(d_x, d_dy, d_dx, a.c1, D);
+      st.done();
+      HIP_TRY(hipMemcpy(a.out, d_dx, (size_t)a.c1 * hw * 4, hipMemcpyDeviceToHost));
+      break;
+    }
+    case MCGPU_SPEEDUP_TRAIN_STAGE_LOSS_L1:
+    case MCGPU_SPEEDUP_TRAIN_STAGE_LOSS_NLL: {
+      const bool l1 = stage == MCGPU_SPEEDUP_TRAIN_STAGE_LOSS_L1;
+      const size_t n = (size_t)a.n;
+      const float* d_a = R.upload(a.in, n * hw);   // low_photon | mean
+      const float* d_s = R.upload(a.in2, n * hw);  // the net's output
+      const float* d_t = R.upload(a.in3, n * hw);
+      float* d_head = R.alloc(n * hw);
+      float* d_g = R.alloc(n * hw);
+      Sums4* d_sums = (Sums4*)R.alloc_bytes(kMaxSegments * sizeof(Sums4), true);
+      const int S = segments_of(hw);
+      const double inv_n = 1.0 / ((double)n * (double)hw);
+      std::vector<Sums4> host(S);
+      double sum = 0.0;
+      Stage st(R.dev, R.rep.ms_forward);
+      for (size_t p = 0; p < n; ++p) {
+        const size_t o = p * hw;
+        if (l1) {
+          hipLaunchKernelGGL(head_mean_kernel, dim3(blocks_of(hw)), dim3(256), 0, nullptr, d_a + o, d_s + o, d_head + o, hw);
+          hipLaunchKernelGGL(metrics_kernel, dim3((unsigned)S), dim3(256), 0, nullptr, d_a + o, d_head + o, (const float*)nullptr, d_t + o, hw, S, d_sums);
+          hipLaunchKernelGGL(l1_grad_kernel, dim3(blocks_of(hw)), dim3(256), 0, nullptr, d_head + o, d_t + o, d_s + o, d_g + o, hw, inv_n);
+        } else {
+          hipLaunchKernelGGL(head_variance_kernel, dim3(blocks_of(hw)), dim3(256), 0, nullptr, d_a + o, d_s + o, d_head + o, hw);
+          hipLaunchKernelGGL(metrics_kernel, dim3((unsigned)S), dim3(256), 0, nullptr, d_a + o, d_a + o, d_head + o, d_t + o, hw, S, d_sums);
+          hipLaunchKernelGGL(nll_grad_kernel, dim3(blocks_of(hw)), dim3(256), 0, nullptr, d_a + o, d_head + o, d_t + o, d_s + o, d_g + o, hw, inv_n);
+        }
+        HIP_TRY(hipMemcpy(host.data(), d_sums, S * sizeof(Sums4), hipMemcpyDeviceToHost));
+        for (int s = 0; s < S; ++s) sum += host[s].v[l1 ? 0 : 1];
+      }
+      st.done();
+      a.values[0] = sum * inv_n;
+      HIP_TRY(hipMemcpy(a.out, d_g, n * hw * 4, hipMemcpyDeviceToHost));
+      if (a.out2) HIP_TRY(hipMemcpy(a.out2, d_head, n * hw * 4, hipMemcpyDeviceToHost));
+      break;
+    }
+    default: {
+      const size_t n = (size_t)a.n;
+      const float* d_g = R.upload(a.in, n);
+      float* d_w = R.upload(a.out, n);
+      float* d_m1 = R.upload(a.out2, n);
+      float* d_m2 = R.upload(a.out3, n);
+      Stage st(R.dev, R.rep.ms_optimizer);
+      launch_adam(d_w, d_g, d_m1, d_m2, n, a.lr, a.beta1, a.beta2, a.step);
+      st.done();
+      HIP_TRY(hipMemcpy(a.out, d_w, n * 4, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(a.out2, d_m1, n * 4, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(a.out3, d_m2, n * 4, hipMemcpyDeviceToHost));
+    }
+  }
+  R.rep.peak_device_bytes = R.dev.peak;
+  R.rep.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  mcgpu::write_report(report, R.rep);
+  return 0;
+  ABI_END
+}

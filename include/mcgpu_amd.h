@@ -954,6 +954,112 @@ typedef struct mcgpu_speedup_stage_args {
 int mcgpu_speedup_stage(const mcgpu_speedup_options *options, int stage, const mcgpu_speedup_stage_args *args, mcgpu_speedup_report *report);
 
 /* ------------------------------------------------------------------------------------------------
+ * Training of the speed-up network on the device (what the reference obtains from cbctmc/speedup/trainer.py: MCSpeedUpTrainer;
+ * csrc/speedup_train.hip, whose header states the rule).  A trainer is a handle: the flat weights (the order of
+ * mcgpu_speedup_options.weights), both Adam moments, both packings of the weights and every buffer of a pass stay on the device
+ * between steps.  A batch is n <= max_batch samples (low_photon, forward_projection or NULL, high_photon), host pointers to
+ * [n][nv][nu] float32.  The forward pass is mcgpu_speedup_run's; the losses are means over n nv nu elements.
+ *   phase MEAN:      loss = mean |m - t|; only the mean net's weights get gradients and move.
+ *   phase VARIANCE:  loss = mean 0.5 (log v' + (m - t)^2 / v'), v' = max(v, 1e-6); the mean net is frozen, no gradient is taken
+ *                    through m; only the variance net's weights get gradients and move.
+ * Everything is float32 (no reduced-precision pass, no gradient scaling).  The batch gradient is the sum of the per-sample
+ * gradients in sample order; nothing is accumulated atomically: the same call gives the same bytes.  The bias of a convolution
+ * that feeds an instance norm has gradient exactly 0 by definition here (mathematically it is 0) and never
+ * moves.  Adam: m <- b1 m + (1 - b1) g, v <- b2 v + (1 - b2) g^2, w <- w - lr / (1 - b1^t) m / (sqrt(v) / sqrt(1 - b2^t) + 1e-8), no
+ * weight decay; t counts the updates of the phase's net; lr <- lr gamma after every update.
+ * Refused before any device call (-1, mcgpu_last_error): a null handle or array, an unknown phase, n outside 1..max_batch, a
+ * forward projection given to (or missing from) the architecture, a forward-projection slice of zero variance; by
+ * mcgpu_speedup_train_create: a bad architecture, n_weights that is not the architecture's, nu or nv not divisible by 2^levels of
+ * the deeper net, a bottleneck of fewer than 2 pixels, lr, gamma or betas out of range.
+ * With `dry` set the handle is a plan: nothing touches the device, mcgpu_speedup_train_get_state reports planned_device_bytes,
+ * and calls that would run refuse after their other checks. */
+typedef struct mcgpu_speedup_trainer mcgpu_speedup_trainer;
+enum { MCGPU_SPEEDUP_PHASE_MEAN = 0, MCGPU_SPEEDUP_PHASE_VARIANCE = 1 };
+typedef struct mcgpu_speedup_train_options {
+  unsigned int struct_size;     /* sizeof(mcgpu_speedup_train_options); 0 is refused */
+  int device;
+  int nu, nv, max_batch;        /* samples are [nv][nu]; the largest n of a later call */
+  int mean_in_channels, mean_levels, mean_filter_base;   /* as mcgpu_speedup_options */
+  int var_in_channels, var_levels, var_filter_base;
+  int dry;                      /* 1: plan only */
+  const float *weights;         /* the initial flat weights */
+  unsigned long long n_weights;
+  double lr, gamma;             /* the reference's: 1e-3, 0.99999 */
+  double beta1, beta2;          /* 0.9, 0.999 */
+} mcgpu_speedup_train_options;
+typedef struct mcgpu_speedup_train_report {
+  unsigned int struct_size;     /* sizeof(mcgpu_speedup_train_report) as the caller was compiled */
+  int phase;
+  double loss;                  /* the phase's: l1_loss or gaussian_nll_loss */
+  double l1_loss, gaussian_nll_loss;
+  double psnr_before, psnr_after;  /* 20 log10(8.711442 / sqrt(mse)) of low_photon and of the mean against high_photon */
+  unsigned long long step;      /* updates done so far, both phases */
+  double lr;                    /* the learning rate the next update will use */
+  double ms_forward;            /* the copies of each sample to the device (they wait for it), preprocessing, both nets, heads, loss sums */
+  double ms_wgrad;              /* weight- and bias-gradient kernels */
+  double ms_dgrad;              /* input-gradient kernels, their fold, max-pool backward */
+  double ms_norm;               /* backward of instance norm + LeakyReLU */
+  double ms_optimizer;          /* Adam and the repacking of the weights */
+  double ms_total;              /* wall time of the call */
+  unsigned long long peak_device_bytes;  /* most device memory the trainer has held */
+} mcgpu_speedup_train_report;
+typedef struct mcgpu_speedup_train_state {
+  unsigned int struct_size;     /* sizeof(mcgpu_speedup_train_state); 0 is refused */
+  int reserved;
+  float *weights, *moment1, *moment2;  /* host, [n_weights] each; a NULL array is not transferred */
+  unsigned long long n_weights;
+  unsigned long long step_mean, step_variance;  /* updates of each net: Adam's t */
+  double lr;
+  unsigned long long planned_device_bytes;      /* get: what the trainer holds (a dry handle: would hold) */
+} mcgpu_speedup_train_state;
+int mcgpu_speedup_train_create(const mcgpu_speedup_train_options *options, mcgpu_speedup_trainer **handle);
+/* One batch.  update = 1: gradient of the phase's loss, one Adam update, both packings redone; update = 0: the losses alone
+ * (the reference's validate_on_batch), nothing changes. */
+int mcgpu_speedup_train_step(mcgpu_speedup_trainer *handle, int phase, int n, const float *low_photon, const float *forward_projection,
+                             const float *high_photon, int update, mcgpu_speedup_train_report *report);
+/* The batch gradient of the phase's loss, [n_weights] in the order of the flat weights (zero outside the phase's net); changes
+ * nothing. */
+int mcgpu_speedup_train_gradients(mcgpu_speedup_trainer *handle, int phase, int n, const float *low_photon, const float *forward_projection,
+                                  const float *high_photon, float *flat_gradient, mcgpu_speedup_train_report *report);
+/* mean and variance [n][nv][nu] of the trainer's forward pass with its present weights (either may be NULL); changes nothing */
+int mcgpu_speedup_train_predict(mcgpu_speedup_trainer *handle, int n, const float *low_photon, const float *forward_projection, float *mean,
+                                float *variance);
+/* Weights, moments, step counts and learning rate, device -> host and back: a run resumed from them continues bit for bit.
+ * set: n_weights must be the trainer's (unless all three arrays are NULL); step counts and lr are always taken. */
+int mcgpu_speedup_train_get_state(mcgpu_speedup_trainer *handle, mcgpu_speedup_train_state *state);
+int mcgpu_speedup_train_set_state(mcgpu_speedup_trainer *handle, const mcgpu_speedup_train_state *state);
+int mcgpu_speedup_train_destroy(mcgpu_speedup_trainer *handle);
+/* One backward operator alone (for tests), on images of nv rows x nu columns; all arrays are host float32.
+ *   CONV_WGRAD: in [c1][nv][nu], in2 [c2][nv2][nu2] or NULL (as MCGPU_SPEEDUP_STAGE_CONV, `upsample` included), in3 = dY
+ *     [c_out][nv][nu] -> out = dW [c_out][c1 + c2][3][3], out2 = db [c_out] (may be NULL); values[0] = number of partials.
+ *   CONV_DGRAD: in = dY [c_out][nv][nu], in2 = weight [c_out][c1 + c2][3][3] -> out = d in [c1][nv][nu], out2 = d in2
+ *     [c2][nv2][nu2] (c2 > 0).
+ *   NORM_LRELU_BACKWARD: in = x [c1][nv][nu] (before the norm), in2 = dy -> out = dx.
+ *   MAXPOOL_BACKWARD: in = x [c1][nv][nu], in2 = dy [c1][nv / 2][nu / 2] -> out = dx.
+ *   LOSS_L1: in = low_photon, in2 = the mean net's output, in3 = high_photon, each [n][nv][nu] -> out = dL/d(net output),
+ *     out2 = mean (may be NULL), values[0] = loss.
+ *   LOSS_NLL: in = mean, in2 = the variance net's output, in3 = high_photon -> out = dL/d(net output), out2 = variance (may be
+ *     NULL), values[0] = loss.
+ *   ADAM: in = gradient [n]; out = weights, out2 = moment 1, out3 = moment 2, each [n], updated in place by update number
+ *     `step` (>= 1) with lr, beta1, beta2. */
+enum { MCGPU_SPEEDUP_TRAIN_STAGE_CONV_WGRAD = 0, MCGPU_SPEEDUP_TRAIN_STAGE_CONV_DGRAD = 1, MCGPU_SPEEDUP_TRAIN_STAGE_NORM_LRELU_BACKWARD = 2,
+       MCGPU_SPEEDUP_TRAIN_STAGE_MAXPOOL_BACKWARD = 3, MCGPU_SPEEDUP_TRAIN_STAGE_LOSS_L1 = 4, MCGPU_SPEEDUP_TRAIN_STAGE_LOSS_NLL = 5,
+       MCGPU_SPEEDUP_TRAIN_STAGE_ADAM = 6 };
+typedef struct mcgpu_speedup_train_stage_args {
+  unsigned int struct_size;     /* sizeof(mcgpu_speedup_train_stage_args); 0 is refused */
+  int device;
+  int nu, nv;
+  int upsample, c1, c2, c_out;
+  const float *in, *in2, *in3;
+  float *out, *out2, *out3;
+  double *values;               /* [4] or NULL */
+  unsigned long long n;         /* losses: samples; ADAM: elements */
+  unsigned long long step;
+  double lr, beta1, beta2;
+} mcgpu_speedup_train_stage_args;
+int mcgpu_speedup_train_stage(int stage, const mcgpu_speedup_train_stage_args *args, mcgpu_speedup_train_report *report);
+
+/* ------------------------------------------------------------------------------------------------
  * The CT segmentation network (what the reference obtains from cbctmc/segmentation/segmenter.py: MCSegmenter.segment;
  * csrc/segment_net.hip, whose header restates the network and the procedure).  A 3-D U-Net of 3 x 3 x 3 convolutions (zero
  * padding, bias), instance norm and LeakyReLU(0.01) in float32, run patch by patch; softmax over channels 0..7 and sigmoid on
