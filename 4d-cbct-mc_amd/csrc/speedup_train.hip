@@ -47,8 +47,9 @@
 //     with a second packing of the weights (pack_dgrad_weights_kernel: transposed, taps flipped) into an extended
 //     [C_in][H + 2][W + 2] buffer, then dgrad_fold_kernel (fold of the border, split into the two sources, 2 x 2 sums; float64, rounded
 //     once).
-//   norm_backward_stats_kernel + norm_backward_kernel, maxpool_backward_kernel, metrics_kernel (the four float64 sums of a sample:
-//     |m - t|, the Gaussian term, (lp - t)^2, (m - t)^2), l1_grad_kernel, nll_grad_kernel, bias_grad_kernel, adam_kernel.
+//   maxpool_backward_kernel, metrics_kernel (the four float64 sums of a sample: |m - t|, the Gaussian term, (lp - t)^2, (m - t)^2),
+//     l1_grad_kernel, nll_grad_kernel; from unet_train_common.inc, shared with segment_train.hip: norm_backward_stats_kernel +
+//     norm_backward_kernel, wgrad_fold_kernel, bias_grad_kernel, adam_kernel.
 // The weights, both moments, both packings and all buffers of a pass live on the device between steps behind a handle; both packings
 // of the phase's net are redone on the device after each update.
 #include <chrono>
@@ -63,6 +64,7 @@ namespace {
 constexpr int kTaps = 9;
 #include "unet_common.inc"
 #include "speedup_conv.inc"
+#include "unet_train_common.inc"
 
 // ------------------------------------------------------------------------------------------------ convolution, weight gradient
 constexpr int kWgH = 4;                                      // rows of a pixel tile: one per wave
@@ -136,21 +138,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_mfma_kernel(WgradArgs a) {
   }
 }
 
-// grad[e] += scale x the partials of e added in float64 in their order, rounded once
-__global__ __launch_bounds__(256) void wgrad_fold_kernel(const float* part, int n_part, size_t n_w, float* grad, double scale) {
-  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n_w) return;
-  double s = 0.0;
-  for (int p = 0; p < n_part; ++p) s += (double)part[(size_t)p * n_w + e];
-  grad[e] += (float)(s * scale);
-}
-
-// grad[c] += scale x sum of dY[c]: stats_kernel's float64 sums, folded in order
-__global__ __launch_bounds__(256) void bias_grad_kernel(const double2* part, int S, int C, float* grad, double scale) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c < C) grad[c] += (float)(fold_segments(part + (size_t)c * S, S).x * scale);
-}
-
 // ------------------------------------------------------------------------------------------------- convolution, input gradient
 // The forward packing (unet_common.inc: pack_weights_kernel) of W'[ci][co][tap] = W[co][ci][8 - tap]: the GEMM's input channels
 // are the layer's output channels
@@ -198,55 +185,6 @@ __global__ __launch_bounds__(256) void dgrad_fold_kernel(const float* ext, int c
     }
     out2[j] = (float)s;
   }
-}
-
-// ------------------------------------------------------------------------------------- instance norm + LeakyReLU, backward
-__device__ __forceinline__ double xhat_of(float y) { return y > 0.f ? (double)y : (double)y / (double)0.01f; }
-__device__ __forceinline__ double dxhat_of(float y, float dy) { return y > 0.f ? (double)dy : (double)0.01f * (double)dy; }
-
-// part[c][s] = (sum of d xh, sum of d xh xh) of segment s of channel c: stats_kernel's segments and tree
-__global__ __launch_bounds__(256) void norm_backward_stats_kernel(const float* y, const float* dy, size_t hw, int S, double2* part) {
-  __shared__ double s_a[256], s_b[256];
-  const int c = blockIdx.y, s = blockIdx.x, tid = threadIdx.x;
-  const size_t seg = (hw + S - 1) / S, lo = (size_t)s * seg, hi = min(lo + seg, hw);
-  const float* py = y + (size_t)c * hw;
-  const float* pd = dy + (size_t)c * hw;
-  double a = 0.0, b = 0.0;
-  for (size_t i = lo + tid; i < hi; i += 256) {
-    const double d = dxhat_of(py[i], pd[i]);
-    a += d;
-    b += d * xhat_of(py[i]);
-  }
-  s_a[tid] = a;
-  s_b[tid] = b;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (tid < w) {
-      s_a[tid] += s_a[tid + w];
-      s_b[tid] += s_b[tid + w];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) part[(size_t)c * S + s] = make_double2(s_a[0], s_b[0]);
-}
-
-// dy <- dx, in place; fpart: the forward's sums of the layer (mean, rstd), bpart: norm_backward_stats_kernel's
-__global__ __launch_bounds__(256) void norm_backward_kernel(const float* y, float* dy, size_t hw, int S, const double2* fpart, const double2* bpart) {
-  __shared__ double s_rstd, s_m1, s_m2;
-  const int c = blockIdx.y;
-  if (threadIdx.x == 0) {
-    const double2 t = fold_segments(fpart + (size_t)c * S, S);
-    const double m = t.x / (double)hw, var = fmax(t.y / (double)hw - m * m, 0.0);
-    s_rstd = 1.0 / sqrt(var + 1e-5);
-    const double2 b = fold_segments(bpart + (size_t)c * S, S);
-    s_m1 = b.x / (double)hw;
-    s_m2 = b.y / (double)hw;
-  }
-  __syncthreads();
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= hw) return;
-  const size_t j = (size_t)c * hw + i;
-  dy[j] = (float)(s_rstd * (dxhat_of(y[j], dy[j]) - s_m1 - xhat_of(y[j]) * s_m2));
 }
 
 // ------------------------------------------------------------------------------------------------------------ small kernels
@@ -320,18 +258,6 @@ __global__ __launch_bounds__(256) void nll_grad_kernel(const float* m, const flo
   g[i] = out;
 }
 
-// step_size = lr / (1 - b1^t), inv_sqrt_bc2 = 1 / sqrt(1 - b2^t)
-__global__ __launch_bounds__(256) void adam_kernel(float* w, const float* g, float* m1, float* m2, size_t n, double b1, double b2, double step_size,
-                                                   double inv_sqrt_bc2) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const double gv = g[i];
-  const double a = b1 * (double)m1[i] + (1.0 - b1) * gv, b = b2 * (double)m2[i] + (1.0 - b2) * gv * gv;
-  m1[i] = (float)a;
-  m2[i] = (float)b;
-  w[i] = (float)((double)w[i] - step_size * a / (sqrt(b) * inv_sqrt_bc2 + 1e-8));
-}
-
 // -------------------------------------------------------------------------------------------------------------------- host
 using Report = mcgpu_speedup_train_report;
 
@@ -387,12 +313,7 @@ void launch_wgrad(TrainRunner& R, int c_out, const float* src1, int c1, const fl
   a.src1 = src1; a.src2 = src2; a.c1 = c1; a.c2 = c2; a.H = D.H; a.W = D.W; a.H2 = E.H; a.W2 = E.W; a.ups = ups ? 1 : 0;
   a.dy = dy; a.c_out = c_out; a.part = part; a.tiles_x = p.tiles_x; a.n_tiles = p.n_tiles; a.tiles_per_split = p.tiles_per_split;
   hipLaunchKernelGGL(conv_wgrad_mfma_kernel, dim3((unsigned)p.splits, (unsigned)((c_out + 31) / 32), (unsigned)((c1 + c2 + 31) / 32)), dim3(256), 0, nullptr, a);
-  const size_t n_w = (size_t)c_out * (c1 + c2) * 9;
-  hipLaunchKernelGGL(wgrad_fold_kernel, dim3(blocks_of(n_w)), dim3(256), 0, nullptr, part, p.partials(), n_w, grad_w, scale);
-  if (grad_b) {
-    R.stats(dy, c_out, D.voxels(), R.d_part);
-    hipLaunchKernelGGL(bias_grad_kernel, dim3(blocks_of((size_t)c_out)), dim3(256), 0, nullptr, R.d_part, segments_of(D.voxels()), c_out, grad_b, scale);
-  }
+  launch_wgrad_fold(part, p.partials(), (size_t)c_out * (c1 + c2) * 9, grad_w, dy, c_out, D.voxels(), R.d_part, grad_b, scale);
 }
 
 // the input-gradient GEMM of a layer: its input channels are the layer's output channels
@@ -427,20 +348,9 @@ void launch_dgrad(const ConvLayer& d, const float* dy, const Dims& D, float* ext
   hipLaunchKernelGGL(dgrad_fold_kernel, dim3(blocks_of(n)), dim3(256), 0, nullptr, ext, c1, c2, D.H, D.W, E.H, E.W, ups ? 1 : 0, out1, out2);
 }
 
-void launch_norm_backward(const float* y, float* dy, int C, size_t n, const double2* fpart, double2* bpart) {
-  const int S = segments_of(n);
-  hipLaunchKernelGGL(norm_backward_stats_kernel, dim3((unsigned)S, (unsigned)C), dim3(256), 0, nullptr, y, dy, n, S, bpart);
-  hipLaunchKernelGGL(norm_backward_kernel, dim3(blocks_of(n), (unsigned)C), dim3(256), 0, nullptr, y, dy, n, S, fpart, bpart);
-}
-
 void launch_maxpool_backward(const float* x, const float* dy, float* dx, int C, const Dims& D) {
   const size_t n = (size_t)C * D.shifted(1).voxels();
   if (n) hipLaunchKernelGGL(maxpool_backward_kernel, dim3(blocks_of(n)), dim3(256), 0, nullptr, x, dy, dx, C, D.H, D.W);
-}
-
-void launch_adam(float* w, const float* g, float* m1, float* m2, size_t n, double lr, double b1, double b2, unsigned long long t) {
-  const double step_size = lr / (1.0 - std::pow(b1, (double)t)), inv_sqrt_bc2 = 1.0 / std::sqrt(1.0 - std::pow(b2, (double)t));
-  hipLaunchKernelGGL(adam_kernel, dim3(blocks_of(n)), dim3(256), 0, nullptr, w, g, m1, m2, n, b1, b2, step_size, inv_sqrt_bc2);
 }
 
 // One FlexUNet of the trainer: its layers with both packings, the buffers of a forward pass and, mirrored, of the gradients

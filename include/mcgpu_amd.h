@@ -1123,6 +1123,100 @@ typedef struct mcgpu_segment_stage_args {
 } mcgpu_segment_stage_args;
 int mcgpu_segment_stage(const mcgpu_segment_options *options, int stage, const mcgpu_segment_stage_args *args, mcgpu_segment_report *report);
 
+/* ------------------------------------------------------------------------------------------------
+ * Training of the segmentation network on the device (what the reference obtains from cbctmc/segmentation/trainer.py:
+ * CTSegmentationTrainer with the driver's SegmentationLoss(use_dice=True); csrc/segment_train.hip, whose header states the rule).
+ * A trainer is a handle: the flat weights (the order of mcgpu_segment_options.weights), both Adam moments, both packings of the
+ * weights and every buffer of a pass stay on the device between steps.  A batch is n <= max_batch samples: image, host float32
+ * [n][P0][P1][P2], already rescaled, and target, host [n][9][P0][P1][P2], uint8 or float32 (target_type MCGPU_TARGET_*).
+ *   p = softmax over channels 0..7 of the logits, sigmoid on channel 8 (float64, rounded once); per sample b and channel c
+ *   I = sum t p, G = sum t, P = sum p (float64); f[b][c] = 1 - (2 I + 1e-5) / (G + P + 1e-5); loss = mean of f over b and c;
+ *   loss_label[c] = mean of f over b.
+ * Everything is float32 (the reference's trainer disables autocast for its forward pass; no gradient scaling).  The batch gradient
+ * is the sum of the per-sample gradients in sample order; nothing is accumulated atomically: the same call gives the same bytes.
+ * The bias of a convolution that feeds an instance norm has gradient exactly 0 by definition here and never
+ * moves.  Adam as mcgpu_speedup_train_*; the learning rate is an argument of every step (the host's scheduler owns it).
+ * Refused before any device call (-1, mcgpu_last_error): a null handle or array, n outside 1..max_batch, an unknown target_type,
+ * lr <= 0 with update set; by mcgpu_segment_train_create: levels outside 1..8, filters outside 1..65535, n_classes other than 9,
+ * filters or n_weights that do not fit together, a patch axis not divisible by 2^levels, a bottleneck of fewer than 2 voxels, a
+ * patch of 2^31 voxels or more, betas out of range.
+ * With `dry` set the handle is a plan: nothing touches the device, mcgpu_segment_train_get_state reports planned_device_bytes,
+ * and calls that would run refuse after their other checks. */
+typedef struct mcgpu_segment_trainer mcgpu_segment_trainer;
+enum { MCGPU_TARGET_UINT8 = 0, MCGPU_TARGET_FLOAT32 = 1 };
+typedef struct mcgpu_segment_train_options {
+  unsigned int struct_size;     /* sizeof(mcgpu_segment_train_options); 0 is refused */
+  int device;
+  int patch_shape[3];           /* samples are [P0][P1][P2], last axis fastest */
+  int max_batch;                /* the largest n of a later call */
+  int levels;                   /* 1..8; the reference's: 4 */
+  int n_filters[18];            /* as mcgpu_segment_options; the reference's: 32 everywhere */
+  int n_classes;                /* 9 */
+  int dry;                      /* 1: plan only */
+  const float *weights;         /* the initial flat weights */
+  unsigned long long n_weights;
+  double beta1, beta2;          /* 0.9, 0.999 */
+} mcgpu_segment_train_options;
+typedef struct mcgpu_segment_train_report {
+  unsigned int struct_size;     /* sizeof(mcgpu_segment_train_report) as the caller was compiled */
+  int n;                        /* samples of the batch */
+  double loss;                  /* mean of f over samples and labels */
+  double loss_label[9];         /* mean of f over samples, by label (segmentation.LABELS) */
+  unsigned long long step;      /* updates done so far: Adam's t */
+  double ms_forward;            /* the copies of each sample to the device (they wait for it), the net, the Dice sums */
+  double ms_wgrad;              /* weight- and bias-gradient kernels */
+  double ms_dgrad;              /* head gradient, input-gradient kernels, their 2 x 2 x 2 sums, max-pool backward */
+  double ms_norm;               /* backward of instance norm + LeakyReLU */
+  double ms_optimizer;          /* Adam and the repacking of the weights */
+  double ms_total;              /* wall time of the call */
+  unsigned long long peak_device_bytes;  /* most device memory the trainer has held */
+} mcgpu_segment_train_report;
+typedef struct mcgpu_segment_train_state {
+  unsigned int struct_size;     /* sizeof(mcgpu_segment_train_state); 0 is refused */
+  int reserved;
+  float *weights, *moment1, *moment2;  /* host, [n_weights] each; a NULL array is not transferred */
+  unsigned long long n_weights;
+  unsigned long long step;      /* updates done: Adam's t */
+  unsigned long long planned_device_bytes;  /* get: what the trainer holds (a dry handle: would hold) */
+} mcgpu_segment_train_state;
+int mcgpu_segment_train_create(const mcgpu_segment_train_options *options, mcgpu_segment_trainer **handle);
+/* One batch.  update = 1: gradient of the loss, one Adam update with `lr`, both packings redone; update = 0: the losses alone
+ * (the reference's validate_on_batch), nothing changes and lr is not read. */
+int mcgpu_segment_train_step(mcgpu_segment_trainer *handle, int n, const float *image, const void *target, int target_type, double lr, int update,
+                             mcgpu_segment_train_report *report);
+/* The batch gradient of the loss, [n_weights] in the order of the flat weights; changes nothing. */
+int mcgpu_segment_train_gradients(mcgpu_segment_trainer *handle, int n, const float *image, const void *target, int target_type, float *flat_gradient,
+                                  mcgpu_segment_train_report *report);
+/* logits [n][9][P0][P1][P2] of the trainer's forward pass with its present weights; changes nothing */
+int mcgpu_segment_train_predict(mcgpu_segment_trainer *handle, int n, const float *image, float *logits);
+/* Weights, moments and the step count, device -> host and back: a run resumed from them continues bit for bit.
+ * set: n_weights must be the trainer's (unless all three arrays are NULL); the step count is always taken. */
+int mcgpu_segment_train_get_state(mcgpu_segment_trainer *handle, mcgpu_segment_train_state *state);
+int mcgpu_segment_train_set_state(mcgpu_segment_trainer *handle, const mcgpu_segment_train_state *state);
+int mcgpu_segment_train_destroy(mcgpu_segment_trainer *handle);
+/* One backward operator alone (for tests), on tensors [c][shape[0]][shape[1]][shape[2]]; all arrays are host float32 unless said.
+ *   CONV_WGRAD: in [c1][shape], in2 [c2][shape2] or NULL (as MCGPU_SEGMENT_STAGE_CONV, `upsample` included), in3 = dY [c_out][shape]
+ *     -> out = dW [c_out][c1 + c2][3][3][3], out2 = db [c_out] (may be NULL); values[0] = number of partials.
+ *   CONV_DGRAD: in = dY [c_out][shape], in2 = weight [c_out][c1 + c2][3][3][3] -> out = d in [c1][shape], out2 = d in2 [c2][shape2]
+ *     (c2 > 0; with `upsample` the sum over each 2 x 2 x 2 block).
+ *   MAXPOOL_BACKWARD: in = x [c1][shape], in2 = dy [c1][shape / 2], in3 = what dx holds before, [c1][shape], or NULL for zeros
+ *     -> out = dx.
+ *   LOSS: in = logits [n][9][shape], in2 = target [n][9][shape] -> out = dL/d logits [n][9][shape] of the batch loss, values =
+ *     double [1 + 9 n]: the loss, then f [n][9]. */
+enum { MCGPU_SEGMENT_TRAIN_STAGE_CONV_WGRAD = 0, MCGPU_SEGMENT_TRAIN_STAGE_CONV_DGRAD = 1, MCGPU_SEGMENT_TRAIN_STAGE_MAXPOOL_BACKWARD = 2,
+       MCGPU_SEGMENT_TRAIN_STAGE_LOSS = 3 };
+typedef struct mcgpu_segment_train_stage_args {
+  unsigned int struct_size;     /* sizeof(mcgpu_segment_train_stage_args); 0 is refused */
+  int device;
+  int shape[3];
+  int upsample, c1, c2, c_out;
+  const float *in, *in2, *in3;
+  float *out, *out2;
+  double *values;
+  unsigned long long n;         /* LOSS: samples */
+} mcgpu_segment_train_stage_args;
+int mcgpu_segment_train_stage(int stage, const mcgpu_segment_train_stage_args *args, mcgpu_segment_train_report *report);
+
 #ifdef __cplusplus
 }
 #endif
