@@ -55,7 +55,6 @@
 // The weights, both moments, both packings and all buffers of a pass live on the device between steps behind a handle; both packings
 // are redone on the device after each update.
 #include <chrono>
-#include <map>
 #include <memory>
 
 #include "../../include/mcgpu_amd.h"
@@ -292,21 +291,6 @@ __global__ __launch_bounds__(256) void head_grad_kernel(const float* logits, con
 // -------------------------------------------------------------------------------------------------------------------- host
 using Report = mcgpu_segment_train_report;
 
-// Launches of the trainer.  The forward pass is NetPass::forward with this runner: norm_lrelu gives every normed layer of the pass
-// its own sums, in the order of the pass, for the backward to find.  Whole passes are timed, not single launches.
-struct TrainRunner : RunnerBase<Report> {
-  std::vector<double2*>* norm_parts = nullptr;
-  size_t norm_i = 0;
-
-  void conv(const ConvLayer& l, const float* src1, int c1, const float* src2, int ups, const Dims& D, float* out) { launch_conv(l, src1, c1, src2, ups, D, out); }
-  void maxpool(const float* x, float* y, int C, const Dims& D) { launch_maxpool(x, y, C, D); }
-  void norm_lrelu(const float* x, float* y, int C, size_t n) {
-    double2* part = norm_parts ? (*norm_parts)[norm_i++] : d_part;
-    stats(x, C, n, part);
-    hipLaunchKernelGGL(norm_lrelu_kernel, dim3(blocks_of(n), (unsigned)C), dim3(256), 0, nullptr, x, y, n, segments_of(n), part);
-  }
-};
-
 std::string triple(const int* v) { return std::to_string(v[0]) + " x " + std::to_string(v[1]) + " x " + std::to_string(v[2]); }
 
 // how K of a layer's weight gradient is split: tiles of 1 x 4 x 32 voxels per workgroup, 4 partials (waves) per workgroup
@@ -328,7 +312,7 @@ WgradPlan wgrad_plan(int c_in, int c_out, const Dims& D) {
 size_t wgrad_part_floats(int c_in, int c_out, const Dims& D) { return (size_t)wgrad_plan(c_in, c_out, D).partials() * c_out * c_in * kTaps; }
 
 // grad_w [c_out][c_in][27] += scale dW; grad_b [c_out] += scale db when grad_b
-void launch_wgrad(TrainRunner& R, int c_out, const float* src1, int c1, const float* src2, int c2, int ups, const Dims& D, const float* dy, float* part,
+void launch_wgrad(RunnerBase<Report>& R, int c_out, const float* src1, int c1, const float* src2, int c2, int ups, const Dims& D, const float* dy, float* part,
                   float* grad_w, float* grad_b, double scale) {
   const Dims E = ups ? D.halved_up() : D;
   const WgradPlan p = wgrad_plan(c1 + c2, c_out, D);
@@ -343,29 +327,38 @@ void launch_wgrad(TrainRunner& R, int c_out, const float* src1, int c1, const fl
 }
 
 // The input-gradient GEMMs of a layer, one per source: their input channels are the layer's output channels
-struct DgradPair {
-  ConvLayer first, second;  // second.c_out = 0: the layer has one source
+struct Dgrad {
+  ConvLayer first, second;  // second.c_out = 0: the layer has one source; first.c_out = 0: none
   int ci0 = 0;              // where the second source's channels begin
+  Dgrad() = default;
+  Dgrad(const ConvLayer& l, int c1) : first(gemm(l, c1)), second(gemm(l, l.c_in - c1)), ci0(c1) {}
+  static ConvLayer gemm(const ConvLayer& l, int cn) {
+    ConvLayer d;
+    d.c_in = l.c_out;
+    d.c_out = cn;
+    d.nb = 1;
+    d.n_chunks = (d.c_in + kCK - 1) / kCK;
+    return d;
+  }
+  template <class F>
+  void each(F f) {
+    if (first.c_out) f(first);
+    if (second.c_out) f(second);
+  }
+  void pack(const ConvLayer& l, const float* d_w) const {
+    pack_one(l, first, 0, d_w);
+    pack_one(l, second, ci0, d_w);
+  }
+  static void pack_one(const ConvLayer& l, const ConvLayer& d, int ci0, const float* d_w) {
+    const size_t total = d.pack_floats();
+    if (total) hipLaunchKernelGGL(pack_dgrad_weights_kernel, dim3(blocks_of(total)), dim3(256), 0, nullptr, d_w, d.wpack, l.c_in, l.c_out, ci0, d.c_out, d.n_chunks, total);
+  }
 };
-ConvLayer dgrad_layer(const ConvLayer& l, int cn) {
-  ConvLayer d;
-  d.c_in = l.c_out;
-  d.c_out = cn;
-  d.nb = 1;
-  d.n_chunks = (d.c_in + kCK - 1) / kCK;
-  return d;
-}
-void launch_pack_dgrad(const ConvLayer& l, const ConvLayer& d, int ci0, const float* d_w) {
-  const size_t total = d.pack_floats();
-  if (total) hipLaunchKernelGGL(pack_dgrad_weights_kernel, dim3(blocks_of(total)), dim3(256), 0, nullptr, d_w, d.wpack, l.c_in, l.c_out, ci0, d.c_out, d.n_chunks, total);
-}
-void launch_pack_forward(const ConvLayer& l, const float* d_w) {
-  const size_t total = l.pack_floats();
-  hipLaunchKernelGGL(pack_weights_kernel<kTaps>, dim3(blocks_of(total)), dim3(256), 0, nullptr, d_w, l.wpack, l.c_in, l.c_out, l.n_chunks, 32 * l.nb, total);
-}
+// of the second source at full size, before it is summed into the half-size gradient
+size_t dgrad_ext_floats(const ConvLayer& l, int c1, const Dims& D) { return (size_t)(l.c_in - c1) * D.voxels(); }
 
 // out1 [c1][D] and out2 [c2][D or its half] = the gradient of the layer's two sources; ext: room for [c2][D] when ups
-void launch_dgrad(const DgradPair& d, const float* dy, const Dims& D, float* ext, int ups, float* out1, float* out2) {
+void launch_dgrad(const Dgrad& d, const float* dy, const Dims& D, float* ext, int ups, float* out1, float* out2) {
   launch_conv(d.first, dy, d.first.c_in, nullptr, 0, D, out1);
   if (!d.second.c_out) return;
   if (!ups) {
@@ -390,67 +383,7 @@ void launch_dice(const float* logits, const float* t, size_t n, double* d_dice, 
   hipLaunchKernelGGL(dice_fold_kernel, dim3(1), dim3(64), 0, nullptr, d_dice, S, d_f, d_coef);
 }
 
-// The FlexUNet of the trainer: its layers with both packings, the buffers of a forward pass and, mirrored, of the gradients
-struct TrainNet {
-  NetLayers layers;
-  std::map<const ConvLayer*, DgradPair> dgrad;
-  std::vector<double2*> parts;  // the sums of each normed layer, in the order of the forward pass
-  std::unique_ptr<NetPass<TrainRunner, Dims>> act, grad;
-  size_t part_floats = 0, ext_floats = 0;
-
-  TrainNet(const mcgpu_segment_train_options& o, size_t& cursor, TrainRunner& R, const Dims& P, float* d_w, const float* d_zero)
-      : layers(1, o.levels, o.n_filters, o.n_classes, cursor) {
-    const int L = layers.L;
-    auto pair = [&](ConvLayer& l, int c1) {  // c1: channels of the first source; 0: no input gradient is needed
-      l.wpack = (float*)R.alloc_bytes(l.pack_floats() * sizeof(float), false);
-      l.bias = d_w + l.b_off;
-      if (!c1) return;
-      DgradPair d;
-      d.ci0 = c1;
-      d.first = dgrad_layer(l, c1);
-      d.second = dgrad_layer(l, l.c_in - c1);
-      for (ConvLayer* g : {&d.first, &d.second}) {
-        if (!g->c_out) continue;
-        g->wpack = (float*)R.alloc_bytes(g->pack_floats() * sizeof(float), false);
-        g->bias = d_zero;
-      }
-      dgrad[&l] = d;
-    };
-    pair(layers.init, 0);
-    pair(layers.final, layers.final.c_in);
-    for (int i = 0; i < L; ++i) {
-      pair(layers.enc[2 * i], layers.enc[2 * i].c_in);
-      pair(layers.enc[2 * i + 1], layers.enc[2 * i + 1].c_in);
-      pair(layers.dec[2 * i], layers.skip_c[i]);
-      pair(layers.dec[2 * i + 1], layers.dec[2 * i + 1].c_in);
-    }
-    act.reset(new NetPass<TrainRunner, Dims>(layers, R, P));
-    grad.reset(new NetPass<TrainRunner, Dims>(layers, R, P));
-    auto sums = [&](int c) { parts.push_back((double2*)R.alloc_bytes((size_t)c * kMaxSegments * sizeof(double2), true)); };
-    for (int i = 0; i < L; ++i) { sums(layers.skip_c[i + 1]); sums(layers.skip_c[i + 1]); }
-    for (int i = L - 1; i >= 0; --i) { sums(layers.dec_c[i]); sums(layers.dec_c[i]); }
-    auto need = [&](const ConvLayer& l, const Dims& D) { part_floats = std::max(part_floats, wgrad_part_floats(l.c_in, l.c_out, D)); };
-    need(layers.init, P);
-    need(layers.final, P);
-    for (int i = 0; i < L; ++i) {
-      need(layers.enc[2 * i], P.shifted(i + 1)); need(layers.enc[2 * i + 1], P.shifted(i + 1));
-      need(layers.dec[2 * i], P.shifted(i)); need(layers.dec[2 * i + 1], P.shifted(i));
-      ext_floats = std::max(ext_floats, (size_t)(layers.dec[2 * i].c_in - layers.skip_c[i]) * P.shifted(i).voxels());
-    }
-  }
-  void pack(const float* d_w) {
-    layers.each([&](ConvLayer& l) {
-      launch_pack_forward(l, d_w + l.w_off);
-      auto it = dgrad.find(&l);
-      if (it == dgrad.end()) return;
-      launch_pack_dgrad(l, it->second.first, 0, d_w + l.w_off);
-      if (it->second.second.c_out) launch_pack_dgrad(l, it->second.second, it->second.ci0, d_w + l.w_off);
-    });
-  }
-  // the sums of the k-th normed layer of the forward pass: enc_i first, second = 2 i, 2 i + 1; dec_i = 2 L + 2 (L - 1 - i) (+ 1)
-  double2* enc_part(int i, int second) { return parts[2 * i + second]; }
-  double2* dec_part(int i, int second) { return parts[2 * layers.L + 2 * (layers.L - 1 - i) + second]; }
-};
+#include "unet_train_host.inc"
 
 }  // namespace
 
@@ -458,11 +391,11 @@ struct mcgpu_segment_trainer {
   mcgpu_segment_train_options o;
   TrainRunner R;
   Dims P;
-  size_t n = 0, n_w = 0;  // voxels of a patch, values of the flat weights
-  float *d_w = nullptr, *d_m1 = nullptr, *d_m2 = nullptr, *d_grad = nullptr, *d_zero = nullptr;
-  float *d_x = nullptr, *d_t = nullptr, *d_part = nullptr, *d_ext = nullptr;
+  TrainCore core;
+  size_t n = 0;  // voxels of a patch
+  float *d_x = nullptr, *d_t = nullptr;
   unsigned char* d_traw = nullptr;
-  double2 *d_bpart = nullptr, *d_coef = nullptr;
+  double2* d_coef = nullptr;
   double *d_dice = nullptr, *d_f = nullptr;
   std::unique_ptr<TrainNet> net;
   unsigned long long step = 0;
@@ -511,11 +444,6 @@ void check_batch(const char* fn, const Trainer* T, int n, const float* image, co
   }
 }
 
-void check_live(const char* fn, Trainer* T) {
-  if (T->R.dry) refuse(fn, "the handle is a dry plan: nothing runs on it");
-  HIP_TRY(hipSetDevice(T->o.device));
-}
-
 // logits of sample p on the device (net->act->out), every layer's output and sums kept for the backward
 const float* forward_sample(Trainer& T, const float* image, int p) {
   HIP_TRY(hipMemcpy(T.d_x, image + (size_t)p * T.n, T.n * 4, hipMemcpyHostToDevice));
@@ -536,69 +464,13 @@ void upload_target(Trainer& T, const void* target, int target_type, int p) {
   }
 }
 
-// The gradient of one sample added to d_grad: NetPass::forward walked in reverse.  grad->out holds dL/d(logits).
-void backward_sample(Trainer& T, double scale) {
-  TrainRunner& R = T.R;
-  TrainNet& N = *T.net;
-  NetLayers& net = N.layers;
-  auto& A = *N.act;
-  auto& G = *N.grad;
-  const int L = net.L;
-  const Dims P = T.P;
-  auto wgrad = [&](const ConvLayer& l, const float* s1, int c1, const float* s2, int ups, const Dims& D, const float* dy, bool bias) {
-    Stage st(R.dev, R.rep.ms_wgrad);
-    launch_wgrad(R, l.c_out, s1, c1, s2, l.c_in - c1, ups, D, dy, T.d_part, T.d_grad + l.w_off, bias ? T.d_grad + l.b_off : nullptr, scale);
-    st.done();
-  };
-  auto dgrad = [&](const ConvLayer& l, const float* dy, const Dims& D, int ups, float* o1, float* o2) {
-    Stage st(R.dev, R.rep.ms_dgrad);
-    launch_dgrad(N.dgrad[&l], dy, D, T.d_ext, ups, o1, o2);
-    st.done();
-  };
-  auto norm = [&](const float* y, float* dy, int c, const Dims& D, const double2* fpart) {
-    Stage st(R.dev, R.rep.ms_norm);
-    launch_norm_backward(y, dy, c, D.voxels(), fpart, T.d_bpart);
-    st.done();
-  };
-  wgrad(net.final, A.dec_b[0], net.final.c_in, nullptr, 0, P, G.out, true);
-  dgrad(net.final, G.out, P, 0, G.dec_b[0], nullptr);
-  for (int i = 0; i < L; ++i) {
-    const Dims D = P.shifted(i);
-    const int c = net.dec_c[i];
-    const float* cur = i == L - 1 ? A.skip[L] : A.dec_b[i + 1];
-    float* g_cur = i == L - 1 ? G.skip[L] : G.dec_b[i + 1];
-    norm(A.dec_b[i], G.dec_b[i], c, D, N.dec_part(i, 1));
-    wgrad(net.dec[2 * i + 1], A.dec_a[i], c, nullptr, 0, D, G.dec_b[i], false);
-    dgrad(net.dec[2 * i + 1], G.dec_b[i], D, 0, G.dec_a[i], nullptr);
-    norm(A.dec_a[i], G.dec_a[i], c, D, N.dec_part(i, 0));
-    wgrad(net.dec[2 * i], A.skip[i], net.skip_c[i], cur, 1, D, G.dec_a[i], false);
-    dgrad(net.dec[2 * i], G.dec_a[i], D, 1, G.skip[i], g_cur);
-  }
-  for (int i = L - 1; i >= 0; --i) {
-    const Dims D = P.shifted(i + 1);
-    const int c = net.skip_c[i + 1];
-    norm(A.skip[i + 1], G.skip[i + 1], c, D, N.enc_part(i, 1));
-    wgrad(net.enc[2 * i + 1], A.enc_a[i], c, nullptr, 0, D, G.skip[i + 1], false);
-    dgrad(net.enc[2 * i + 1], G.skip[i + 1], D, 0, G.enc_a[i], nullptr);
-    norm(A.enc_a[i], G.enc_a[i], c, D, N.enc_part(i, 0));
-    wgrad(net.enc[2 * i], A.pooled[i], net.skip_c[i], nullptr, 0, D, G.enc_a[i], false);
-    dgrad(net.enc[2 * i], G.enc_a[i], D, 0, G.pooled[i], nullptr);
-    {
-      Stage st(R.dev, R.rep.ms_dgrad);
-      launch_maxpool_backward(A.skip[i], G.pooled[i], G.skip[i], net.skip_c[i], P.shifted(i));
-      st.done();
-    }
-  }
-  wgrad(net.init, T.d_x, net.in_channels, nullptr, 0, P, G.skip[0], true);
-}
-
 // forward of every sample, its f, and (with `gradient`) its gradient of the loss added to d_grad; f [n][9] comes back to the host
 void run_batch(Trainer& T, int n, const float* image, const void* target, int target_type, bool gradient, std::vector<double>& f) {
   TrainRunner& R = T.R;
   // A sample's backward pass runs on the gradient of ITS loss (1 / 9) and is the same bytes in any batch; the share 1 / B of the
   // batch is applied where the sample's gradient is rounded to float32 and added to the batch's
   const double inv_b = 1.0 / (double)n;
-  if (gradient) HIP_TRY(hipMemset(T.d_grad, 0, T.n_w * 4));
+  if (gradient) HIP_TRY(hipMemset(T.core.d_grad, 0, T.core.n_w * 4));
   for (int p = 0; p < n; ++p) {
     const float* logits = nullptr;
     {
@@ -614,7 +486,7 @@ void run_batch(Trainer& T, int n, const float* image, const void* target, int ta
       hipLaunchKernelGGL(head_grad_kernel, dim3(blocks_of(T.n)), dim3(256), 0, nullptr, logits, T.d_t, T.d_coef, T.n, 1.0 / (double)kClasses, T.net->grad->out);
       st.done();
     }
-    backward_sample(T, inv_b);
+    backward_sample(R, *T.net, T.d_x, T.core, inv_b);
   }
   f.resize((size_t)n * kClasses);
   HIP_TRY(hipMemcpy(f.data(), T.d_f, f.size() * sizeof(double), hipMemcpyDeviceToHost));  // once per batch; waits for the device
@@ -638,16 +510,7 @@ void fill_report(Trainer& T, int n, const std::vector<double>& f, const std::chr
   Report& r = T.R.rep;
   fill_losses(r, n, f.data());
   r.step = T.step;
-  r.peak_device_bytes = T.R.dev.peak;
-  r.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  mcgpu::write_report(report, r);
-}
-
-void clear_times(Report& r) { r.ms_forward = r.ms_wgrad = r.ms_dgrad = r.ms_norm = r.ms_optimizer = r.ms_total = 0.0; }
-
-void check_state(const char* fn, const Trainer* T, const mcgpu_segment_train_state& s) {
-  if ((s.weights || s.moment1 || s.moment2) && s.n_weights != T->n_w)
-    refuse(fn, "n_weights is " + std::to_string(s.n_weights) + " but the trainer has " + std::to_string(T->n_w) + " values");
+  finish_report(T.R, t0, report);
 }
 
 }  // namespace
@@ -665,34 +528,21 @@ extern "C" int mcgpu_segment_train_create(const mcgpu_segment_train_options* cal
   R.dry = o.dry != 0;
   T->P = Dims{{o.patch_shape[0], o.patch_shape[1], o.patch_shape[2]}};
   T->n = T->P.voxels();
-  T->n_w = (size_t)o.n_weights;
-  int widest = kClasses;
-  {
-    size_t c = 0;
-    widest = std::max(widest, NetLayers(1, o.levels, o.n_filters, o.n_classes, c).widest());
-  }
+  size_t cursor = 0;
+  NetLayers layers(1, o.levels, o.n_filters, o.n_classes, cursor);
+  const int widest = std::max(kClasses, layers.widest());
   R.init(o.device, widest);
-  T->d_w = R.upload(o.weights, T->n_w);
-  T->d_m1 = R.alloc(T->n_w);
-  T->d_m2 = R.alloc(T->n_w);
-  T->d_grad = R.alloc(T->n_w);
-  T->d_zero = R.alloc((size_t)2 * widest + 2);  // the bias of the input-gradient GEMMs
+  TrainCore& C = T->core;
+  C.alloc(R, o.device, o.weights, (size_t)o.n_weights, widest);
   T->d_x = R.alloc(T->n);
   T->d_t = R.alloc((size_t)kClasses * T->n);
   T->d_traw = (unsigned char*)R.alloc_bytes((size_t)kClasses * T->n, true);
-  T->d_bpart = (double2*)R.alloc_bytes((size_t)widest * kMaxSegments * sizeof(double2), true);
   T->d_dice = (double*)R.alloc_bytes((size_t)kMaxSegments * kDiceSums * kClasses * sizeof(double), true);
   T->d_f = (double*)R.alloc_bytes((size_t)o.max_batch * kClasses * sizeof(double), true);
   T->d_coef = (double2*)R.alloc_bytes((size_t)kClasses * sizeof(double2), true);
-  size_t cursor = 0;
-  T->net.reset(new TrainNet(o, cursor, R, T->P, T->d_w, T->d_zero));
-  T->d_part = R.alloc(T->net->part_floats);
-  T->d_ext = R.alloc(T->net->ext_floats);
-  if (!R.dry) {
-    T->net->pack(T->d_w);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-  }
+  T->net.reset(new TrainNet(std::move(layers), R, T->P, C.d_w, C.d_zero));
+  C.alloc_scratch(T->net->part_floats, T->net->ext_floats);
+  if (!R.dry) C.repack({T->net.get()});
   *handle = T.release();
   return 0;
   ABI_END
@@ -705,7 +555,7 @@ extern "C" int mcgpu_segment_train_step(mcgpu_segment_trainer* T, int n, const f
   check_batch(fn, T, n, image, target, target_type, true);
   if (update && !(lr > 0.0)) refuse(fn, "lr is " + std::to_string(lr) + ", expected > 0");
   mcgpu::check_report(fn, "report", "mcgpu_segment_train_report", report);
-  check_live(fn, T);
+  T->core.check_live(fn);
   const auto t0 = std::chrono::steady_clock::now();
   clear_times(T->R.rep);
   std::vector<double> f;
@@ -713,8 +563,7 @@ extern "C" int mcgpu_segment_train_step(mcgpu_segment_trainer* T, int n, const f
   if (update) {
     Stage st(T->R.dev, T->R.rep.ms_optimizer);
     ++T->step;
-    launch_adam(T->d_w, T->d_grad, T->d_m1, T->d_m2, T->n_w, lr, T->o.beta1, T->o.beta2, T->step);
-    T->net->pack(T->d_w);
+    T->core.update(*T->net, lr, T->o.beta1, T->o.beta2, T->step);
     st.done();
   }
   fill_report(*T, n, f, t0, report);
@@ -729,12 +578,12 @@ extern "C" int mcgpu_segment_train_gradients(mcgpu_segment_trainer* T, int n, co
   check_batch(fn, T, n, image, target, target_type, true);
   if (!flat_gradient) refuse(fn, "flat_gradient is NULL");
   mcgpu::check_report(fn, "report", "mcgpu_segment_train_report", report);
-  check_live(fn, T);
+  T->core.check_live(fn);
   const auto t0 = std::chrono::steady_clock::now();
   clear_times(T->R.rep);
   std::vector<double> f;
   run_batch(*T, n, image, target, target_type, true, f);
-  HIP_TRY(hipMemcpy(flat_gradient, T->d_grad, T->n_w * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(flat_gradient, T->core.d_grad, T->core.n_w * 4, hipMemcpyDeviceToHost));
   fill_report(*T, n, f, t0, report);
   return 0;
   ABI_END
@@ -745,7 +594,7 @@ extern "C" int mcgpu_segment_train_predict(mcgpu_segment_trainer* T, int n, cons
   const char* fn = "mcgpu_segment_train_predict";
   check_batch(fn, T, n, image, nullptr, 0, false);
   if (!logits) refuse(fn, "logits is NULL");
-  check_live(fn, T);
+  T->core.check_live(fn);
   const size_t m = (size_t)kClasses * T->n;
   for (int p = 0; p < n; ++p) {
     const float* d_logits = forward_sample(*T, image, p);
@@ -763,16 +612,11 @@ extern "C" int mcgpu_segment_train_get_state(mcgpu_segment_trainer* T, mcgpu_seg
   if (!T) refuse(fn, "handle is NULL");
   mcgpu_segment_train_state s;
   mcgpu::read_options(fn, "mcgpu_segment_train_state", caller_s, s);
-  check_state(fn, T, s);
-  if (s.weights || s.moment1 || s.moment2) {
-    check_live(fn, T);
-    if (s.weights) HIP_TRY(hipMemcpy(s.weights, T->d_w, T->n_w * 4, hipMemcpyDeviceToHost));
-    if (s.moment1) HIP_TRY(hipMemcpy(s.moment1, T->d_m1, T->n_w * 4, hipMemcpyDeviceToHost));
-    if (s.moment2) HIP_TRY(hipMemcpy(s.moment2, T->d_m2, T->n_w * 4, hipMemcpyDeviceToHost));
-  }
-  s.n_weights = T->n_w;
+  T->core.check_state(fn, s);
+  T->core.get_arrays(fn, s);
+  s.n_weights = T->core.n_w;
   s.step = T->step;
-  s.planned_device_bytes = T->R.dry ? T->R.planned : T->R.dev.held;
+  s.planned_device_bytes = T->core.planned_bytes();
   mcgpu::write_report(caller_s, s);
   return 0;
   ABI_END
@@ -784,18 +628,8 @@ extern "C" int mcgpu_segment_train_set_state(mcgpu_segment_trainer* T, const mcg
   if (!T) refuse(fn, "handle is NULL");
   mcgpu_segment_train_state s;
   mcgpu::read_options(fn, "mcgpu_segment_train_state", caller_s, s);
-  check_state(fn, T, s);
-  if (s.weights || s.moment1 || s.moment2) {
-    check_live(fn, T);
-    if (s.weights) HIP_TRY(hipMemcpy(T->d_w, s.weights, T->n_w * 4, hipMemcpyHostToDevice));
-    if (s.moment1) HIP_TRY(hipMemcpy(T->d_m1, s.moment1, T->n_w * 4, hipMemcpyHostToDevice));
-    if (s.moment2) HIP_TRY(hipMemcpy(T->d_m2, s.moment2, T->n_w * 4, hipMemcpyHostToDevice));
-    if (s.weights) {
-      T->net->pack(T->d_w);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipDeviceSynchronize());
-    }
-  }
+  T->core.check_state(fn, s);
+  T->core.set_arrays(fn, s, {T->net.get()});
   T->step = s.step;
   return 0;
   ABI_END
@@ -836,31 +670,14 @@ extern "C" int mcgpu_segment_train_stage(int stage, const mcgpu_segment_train_st
   TrainRunner R;
   R.init(a.device, std::max(std::max(a.c1, a.c_out), 1));
   switch (stage) {
-    case MCGPU_SEGMENT_TRAIN_STAGE_CONV_WGRAD: {
-      const Dims E = a.upsample ? D.halved_up() : D;
-      const int c_in = a.c1 + a.c2;
-      const float* d_in = R.upload(a.in, (size_t)a.c1 * n);
-      const float* d_in2 = a.c2 ? R.upload(a.in2, (size_t)a.c2 * E.voxels()) : nullptr;
-      const float* d_dy = R.upload(a.in3, (size_t)a.c_out * n);
-      float* d_part = R.alloc(wgrad_part_floats(c_in, a.c_out, D));
-      const size_t n_w = (size_t)a.c_out * c_in * kTaps;
-      float* d_grad = R.alloc(n_w + a.c_out);
-      Stage st(R.dev, R.rep.ms_wgrad);
-      launch_wgrad(R, a.c_out, d_in, a.c1, d_in2, a.c2, a.upsample, D, d_dy, d_part, d_grad, d_grad + n_w, 1.0);
-      st.done();
-      HIP_TRY(hipMemcpy(a.out, d_grad, n_w * 4, hipMemcpyDeviceToHost));
-      if (a.out2) HIP_TRY(hipMemcpy(a.out2, d_grad + n_w, (size_t)a.c_out * 4, hipMemcpyDeviceToHost));
-      if (a.values) a.values[0] = (double)wgrad_plan(c_in, a.c_out, D).partials();
+    case MCGPU_SEGMENT_TRAIN_STAGE_CONV_WGRAD:
+      stage_wgrad(R, a, D);
       break;
-    }
     case MCGPU_SEGMENT_TRAIN_STAGE_CONV_DGRAD: {
       const Dims E = a.upsample ? D.halved_up() : D;
       size_t cursor = 0;
       ConvLayer l = conv_layer(a.c1 + a.c2, a.c_out, cursor);
-      DgradPair d;
-      d.ci0 = a.c1;
-      d.first = dgrad_layer(l, a.c1);
-      d.second = dgrad_layer(l, a.c2);
+      Dgrad d(l, a.c1);
       const float* d_dy = R.upload(a.in, (size_t)a.c_out * n);
       const float* d_w = R.upload(a.in2, (size_t)a.c_out * l.c_in * kTaps);
       const float* d_zero = R.alloc((size_t)l.c_in + 1);
@@ -871,8 +688,7 @@ extern "C" int mcgpu_segment_train_stage(int stage, const mcgpu_segment_train_st
       float* d_ext = R.alloc((size_t)std::max(a.c2, 1) * n);
       float* d_o1 = R.alloc((size_t)a.c1 * n);
       float* d_o2 = R.alloc((size_t)std::max(a.c2, 1) * E.voxels());
-      launch_pack_dgrad(l, d.first, 0, d_w);
-      if (a.c2) launch_pack_dgrad(l, d.second, a.c1, d_w);
+      d.pack(l, d_w);
       Stage st(R.dev, R.rep.ms_dgrad);
       launch_dgrad(d, d_dy, D, d_ext, a.upsample, d_o1, d_o2);
       st.done();
@@ -880,17 +696,9 @@ extern "C" int mcgpu_segment_train_stage(int stage, const mcgpu_segment_train_st
       if (a.c2) HIP_TRY(hipMemcpy(a.out2, d_o2, (size_t)a.c2 * E.voxels() * 4, hipMemcpyDeviceToHost));
       break;
     }
-    case MCGPU_SEGMENT_TRAIN_STAGE_MAXPOOL_BACKWARD: {
-      const float* d_x = R.upload(a.in, (size_t)a.c1 * n);
-      const size_t n_dy = (size_t)a.c1 * D.shifted(1).voxels();
-      const float* d_dy = R.upload(a.in2, std::max<size_t>(n_dy, 1));
-      float* d_dx = a.in3 ? R.upload(a.in3, (size_t)a.c1 * n) : R.alloc((size_t)a.c1 * n);
-      Stage st(R.dev, R.rep.ms_dgrad);
-      launch_maxpool_backward(d_x, d_dy, d_dx, a.c1, D);
-      st.done();
-      HIP_TRY(hipMemcpy(a.out, d_dx, (size_t)a.c1 * n * 4, hipMemcpyDeviceToHost));
+    case MCGPU_SEGMENT_TRAIN_STAGE_MAXPOOL_BACKWARD:
+      stage_maxpool_backward(R, a, D, a.in3);
       break;
-    }
     default: {
       const size_t B = (size_t)a.n, m = (size_t)kClasses * n;
       const float* d_z = R.upload(a.in, B * m);
@@ -912,9 +720,7 @@ extern "C" int mcgpu_segment_train_stage(int stage, const mcgpu_segment_train_st
       HIP_TRY(hipMemcpy(a.out, d_g, B * m * 4, hipMemcpyDeviceToHost));
     }
   }
-  R.rep.peak_device_bytes = R.dev.peak;
-  R.rep.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  mcgpu::write_report(report, R.rep);
+  finish_report(R, t0, report);
   return 0;
   ABI_END
 }

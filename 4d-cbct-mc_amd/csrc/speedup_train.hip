@@ -53,7 +53,6 @@
 // The weights, both moments, both packings and all buffers of a pass live on the device between steps behind a handle; both packings
 // of the phase's net are redone on the device after each update.
 #include <chrono>
-#include <map>
 #include <memory>
 
 #include "../../include/mcgpu_amd.h"
@@ -261,31 +260,6 @@ __global__ __launch_bounds__(256) void nll_grad_kernel(const float* m, const flo
 // -------------------------------------------------------------------------------------------------------------------- host
 using Report = mcgpu_speedup_train_report;
 
-// Launches of the trainer.  The forward pass is NetPass::forward with this runner: norm_lrelu gives every normed layer of the pass
-// its own sums, in the order of the pass, for the backward to find.  Whole passes are timed, not single launches.
-struct TrainRunner : RunnerBase<Report> {
-  double2* d_part2 = nullptr;                       // the second image of the preprocessing
-  std::vector<double2*>* norm_parts = nullptr;      // of the net whose forward runs
-  size_t norm_i = 0;
-
-  void init(int device, int channels) {
-    RunnerBase::init(device, channels);
-    d_part2 = (double2*)alloc_bytes(kMaxSegments * sizeof(double2), true);
-  }
-  void conv(const ConvLayer& l, const float* src1, int c1, const float* src2, int ups, const Dims& D, float* out) { launch_conv(l, src1, c1, src2, ups, D, out); }
-  void maxpool(const float* x, float* y, int C, const Dims& D) { launch_maxpool(x, y, C, D); }
-  void norm_lrelu(const float* x, float* y, int C, size_t n) {
-    double2* part = norm_parts ? (*norm_parts)[norm_i++] : d_part;
-    stats(x, C, n, part);
-    hipLaunchKernelGGL(norm_lrelu_kernel, dim3(blocks_of(n), (unsigned)C), dim3(256), 0, nullptr, x, y, n, segments_of(n), part);
-  }
-  void preprocess(const float* lp, const float* fp, float* out, size_t hw) {
-    stats(lp, 1, hw, d_part);
-    stats(fp, 1, hw, d_part2);
-    hipLaunchKernelGGL(preprocess_kernel, dim3(blocks_of(hw)), dim3(256), 0, nullptr, fp, out, hw, segments_of(hw), d_part, d_part2);
-  }
-};
-
 // how K of a layer's weight gradient is split: tiles of 4 x 32 pixels per workgroup, 4 partials (waves) per workgroup
 struct WgradPlan {
   int tiles_x, n_tiles, tiles_per_split, splits;
@@ -302,10 +276,9 @@ WgradPlan wgrad_plan(int c_in, int c_out, const Dims& D) {
   return p;
 }
 size_t wgrad_part_floats(int c_in, int c_out, const Dims& D) { return (size_t)wgrad_plan(c_in, c_out, D).partials() * c_out * c_in * 9; }
-size_t dgrad_ext_floats(int c_in, const Dims& D) { return (size_t)c_in * (D.H + 2) * (D.W + 2); }
 
 // grad_w [c_out][c_in][9] += scale dW; grad_b [c_out] += scale db when grad_b
-void launch_wgrad(TrainRunner& R, int c_out, const float* src1, int c1, const float* src2, int c2, int ups, const Dims& D, const float* dy, float* part,
+void launch_wgrad(RunnerBase<Report>& R, int c_out, const float* src1, int c1, const float* src2, int c2, int ups, const Dims& D, const float* dy, float* part,
                   float* grad_w, float* grad_b, double scale) {
   const Dims E = ups ? D.halved_up() : D;
   const WgradPlan p = wgrad_plan(c1 + c2, c_out, D);
@@ -316,26 +289,30 @@ void launch_wgrad(TrainRunner& R, int c_out, const float* src1, int c1, const fl
   launch_wgrad_fold(part, p.partials(), (size_t)c_out * (c1 + c2) * 9, grad_w, dy, c_out, D.voxels(), R.d_part, grad_b, scale);
 }
 
-// the input-gradient GEMM of a layer: its input channels are the layer's output channels
-ConvLayer dgrad_layer(const ConvLayer& l) {
-  ConvLayer d;
-  d.c_in = l.c_out;
-  d.c_out = l.c_in;
-  d.nb = blocks_per_workgroup(d.c_out);
-  d.n_chunks = (d.c_in + kCK - 1) / kCK;
-  return d;
-}
-void launch_pack_dgrad(const ConvLayer& l, const ConvLayer& d, const float* d_w) {
-  const size_t total = d.pack_floats();
-  hipLaunchKernelGGL(pack_dgrad_weights_kernel, dim3(blocks_of(total)), dim3(256), 0, nullptr, d_w, d.wpack, l.c_in, l.c_out, d.n_chunks, 32 * d.nb, total);
-}
-void launch_pack_forward(const ConvLayer& l, const float* d_w) {
-  const size_t total = l.pack_floats();
-  hipLaunchKernelGGL(pack_weights_kernel<kTaps>, dim3(blocks_of(total)), dim3(256), 0, nullptr, d_w, l.wpack, l.c_in, l.c_out, l.n_chunks, 32 * l.nb, total);
-}
+// The input-gradient GEMM of a layer: its input channels are the layer's output channels.  c1: the channels of the layer's first source
+struct Dgrad {
+  ConvLayer g;  // c_out 0: none
+  int c1 = 0;
+  Dgrad() = default;
+  Dgrad(const ConvLayer& l, int c1_) : c1(c1_) {
+    g.c_in = l.c_out;
+    g.c_out = l.c_in;
+    g.nb = blocks_per_workgroup(g.c_out);
+    g.n_chunks = (g.c_in + kCK - 1) / kCK;
+  }
+  template <class F>
+  void each(F f) { if (g.c_out) f(g); }
+  void pack(const ConvLayer& l, const float* d_w) const {
+    const size_t total = g.pack_floats();
+    if (total) hipLaunchKernelGGL(pack_dgrad_weights_kernel, dim3(blocks_of(total)), dim3(256), 0, nullptr, d_w, g.wpack, l.c_in, l.c_out, g.n_chunks, 32 * g.nb, total);
+  }
+};
+size_t dgrad_ext_floats(const ConvLayer& l, int, const Dims& D) { return (size_t)l.c_in * (D.H + 2) * (D.W + 2); }
 
-// out1 [c1][H][W], out2 [c_in - c1][..] = the gradient of the layer's two sources; d: the layer's dgrad_layer, packed; d.bias: zeros
-void launch_dgrad(const ConvLayer& d, const float* dy, const Dims& D, float* ext, int c1, int ups, float* out1, float* out2) {
+// out1 [c1][H][W], out2 [c_in - c1][..] = the gradient of the layer's two sources; d: packed, its bias zeros; ext: dgrad_ext_floats
+void launch_dgrad(const Dgrad& dg, const float* dy, const Dims& D, float* ext, int ups, float* out1, float* out2) {
+  const ConvLayer& d = dg.g;
+  const int c1 = dg.c1;
   const Dims E = ups ? D.halved_up() : D;
   ConvArgs a;
   a.src1 = dy; a.src2 = nullptr; a.c1 = d.c_in; a.c2 = 0; a.H = D.H + 2; a.W = D.W + 2; a.H2 = D.H; a.W2 = D.W; a.ups = 0;
@@ -353,64 +330,39 @@ void launch_maxpool_backward(const float* x, const float* dy, float* dx, int C, 
   if (n) hipLaunchKernelGGL(maxpool_backward_kernel, dim3(blocks_of(n)), dim3(256), 0, nullptr, x, dy, dx, C, D.H, D.W);
 }
 
-// One FlexUNet of the trainer: its layers with both packings, the buffers of a forward pass and, mirrored, of the gradients
-struct TrainNet {
-  NetLayers layers;
-  size_t w_begin, w_end;  // its range of the flat weights
-  std::map<const ConvLayer*, ConvLayer> dgrad;
-  std::vector<double2*> parts;  // the sums of each normed layer, in the order of the forward pass
-  std::unique_ptr<NetPass<TrainRunner, Dims>> act, grad;
-  size_t part_floats = 0, ext_floats = 0;
+#include "unet_train_host.inc"
 
-  TrainNet(const NetShape& s, size_t& cursor, TrainRunner& R, const Dims& P, float* d_w, const float* d_zero) : layers(layers_of(s, cursor)) {
-    w_end = cursor;
-    w_begin = layers.init.w_off;
-    layers.each([&](ConvLayer& l) {
-      l.nb = blocks_per_workgroup(l.c_out);
-      l.wpack = (float*)R.alloc_bytes(l.pack_floats() * sizeof(float), false);
-      l.bias = d_w + l.b_off;
-      ConvLayer d = dgrad_layer(l);
-      d.wpack = (float*)R.alloc_bytes(d.pack_floats() * sizeof(float), false);
-      d.bias = d_zero;
-      dgrad[&l] = d;
-    });
-    act.reset(new NetPass<TrainRunner, Dims>(layers, R, P));
-    grad.reset(new NetPass<TrainRunner, Dims>(layers, R, P));
-    auto sums = [&](int c) { parts.push_back((double2*)R.alloc_bytes((size_t)c * kMaxSegments * sizeof(double2), true)); };
-    for (int i = 0; i < layers.L; ++i) { sums(layers.skip_c[i + 1]); sums(layers.skip_c[i + 1]); }
-    for (int i = layers.L - 1; i >= 0; --i) { sums(layers.dec_c[i]); sums(layers.dec_c[i]); }
-    auto need = [&](const ConvLayer& l, const Dims& D) {
-      part_floats = std::max(part_floats, wgrad_part_floats(l.c_in, l.c_out, D));
-      ext_floats = std::max(ext_floats, dgrad_ext_floats(l.c_in, D));
-    };
-    need(layers.init, P);
-    need(layers.final, P);
-    for (int i = 0; i < layers.L; ++i) {
-      need(layers.enc[2 * i], P.shifted(i + 1)); need(layers.enc[2 * i + 1], P.shifted(i + 1));
-      need(layers.dec[2 * i], P.shifted(i)); need(layers.dec[2 * i + 1], P.shifted(i));
-    }
+// the preprocessing of the mean net's second channel needs the sums of two images
+struct SpeedupRunner : TrainRunner {
+  double2* d_part2 = nullptr;  // the second image of the preprocessing
+
+  void init(int device, int channels) {
+    TrainRunner::init(device, channels);
+    d_part2 = (double2*)alloc_bytes(kMaxSegments * sizeof(double2), true);
   }
-  void pack(const float* d_w) {
-    layers.each([&](ConvLayer& l) {
-      launch_pack_forward(l, d_w + l.w_off);
-      launch_pack_dgrad(l, dgrad[&l], d_w + l.w_off);
-    });
+  void preprocess(const float* lp, const float* fp, float* out, size_t hw) {
+    stats(lp, 1, hw, d_part);
+    stats(fp, 1, hw, d_part2);
+    hipLaunchKernelGGL(preprocess_kernel, dim3(blocks_of(hw)), dim3(256), 0, nullptr, fp, out, hw, segments_of(hw), d_part, d_part2);
   }
-  // the sums of the k-th normed layer of the forward pass: enc_i first, second = 2 i, 2 i + 1; dec_i = 2 L + 2 (L - 1 - i) (+ 1)
-  double2* enc_part(int i, int second) { return parts[2 * i + second]; }
-  double2* dec_part(int i, int second) { return parts[2 * layers.L + 2 * (layers.L - 1 - i) + second]; }
 };
+
+// the layers of one net, each with the variant of the forward convolution that speedup_net.hip runs it with
+NetLayers train_layers(const NetShape& s, size_t& cursor) {
+  NetLayers net = layers_of(s, cursor);
+  net.each([](ConvLayer& l) { l.nb = blocks_per_workgroup(l.c_out); });
+  return net;
+}
 
 }  // namespace
 
 struct mcgpu_speedup_trainer {
   mcgpu_speedup_train_options o;
-  TrainRunner R;
+  SpeedupRunner R;
+  TrainCore core;
   Dims P;
-  size_t hw = 0, n_w = 0;
-  float *d_w = nullptr, *d_m1 = nullptr, *d_m2 = nullptr, *d_grad = nullptr, *d_zero = nullptr;
-  float *d_x = nullptr, *d_fp = nullptr, *d_t = nullptr, *d_mean = nullptr, *d_var = nullptr, *d_part = nullptr, *d_ext = nullptr;
-  double2* d_bpart = nullptr;
+  size_t hw = 0;
+  float *d_x = nullptr, *d_fp = nullptr, *d_t = nullptr, *d_mean = nullptr, *d_var = nullptr;
   Sums4* d_sums = nullptr;
   std::unique_ptr<TrainNet> mean_net, var_net;
   unsigned long long step_mean = 0, step_var = 0;
@@ -456,14 +408,9 @@ void check_batch(const char* fn, const Trainer* T, int phase, int n, const float
   }
 }
 
-void check_live(const char* fn, Trainer* T) {
-  if (T->R.dry) refuse(fn, "the handle is a dry plan: nothing runs on it");
-  HIP_TRY(hipSetDevice(T->o.device));
-}
-
 // mean and variance of sample p on the device (d_x, d_mean, d_var), every layer's output and sums kept for the backward
 void forward_sample(Trainer& T, const float* lp, const float* fp, int p) {
-  TrainRunner& R = T.R;
+  SpeedupRunner& R = T.R;
   const size_t hw = T.hw;
   HIP_TRY(hipMemcpy(T.d_x, lp + (size_t)p * hw, hw * 4, hipMemcpyHostToDevice));
   if (fp) {
@@ -481,72 +428,17 @@ void forward_sample(Trainer& T, const float* lp, const float* fp, int p) {
   R.norm_parts = nullptr;
 }
 
-// The gradient of one sample added to d_grad: NetPass::forward walked in reverse.  x: the net's input; grad->out holds dL/d(output).
-void backward_sample(Trainer& T, TrainNet& N, const float* x, double scale) {
-  TrainRunner& R = T.R;
-  NetLayers& net = N.layers;
-  auto& A = *N.act;
-  auto& G = *N.grad;
-  const int L = net.L;
-  const Dims P = T.P;
-  auto wgrad = [&](const ConvLayer& l, const float* s1, int c1, const float* s2, int ups, const Dims& D, const float* dy, bool bias) {
-    Stage st(R.dev, R.rep.ms_wgrad);
-    launch_wgrad(R, l.c_out, s1, c1, s2, l.c_in - c1, ups, D, dy, T.d_part, T.d_grad + l.w_off, bias ? T.d_grad + l.b_off : nullptr, scale);
-    st.done();
-  };
-  auto dgrad = [&](const ConvLayer& l, const float* dy, const Dims& D, int c1, int ups, float* o1, float* o2) {
-    Stage st(R.dev, R.rep.ms_dgrad);
-    launch_dgrad(N.dgrad[&l], dy, D, T.d_ext, c1, ups, o1, o2);
-    st.done();
-  };
-  auto norm = [&](const float* y, float* dy, int c, const Dims& D, const double2* fpart) {
-    Stage st(R.dev, R.rep.ms_norm);
-    launch_norm_backward(y, dy, c, D.voxels(), fpart, T.d_bpart);
-    st.done();
-  };
-  wgrad(net.final, A.dec_b[0], net.final.c_in, nullptr, 0, P, G.out, true);
-  dgrad(net.final, G.out, P, net.final.c_in, 0, G.dec_b[0], nullptr);
-  for (int i = 0; i < L; ++i) {
-    const Dims D = P.shifted(i);
-    const int c = net.dec_c[i];
-    const float* cur = i == L - 1 ? A.skip[L] : A.dec_b[i + 1];
-    float* g_cur = i == L - 1 ? G.skip[L] : G.dec_b[i + 1];
-    norm(A.dec_b[i], G.dec_b[i], c, D, N.dec_part(i, 1));
-    wgrad(net.dec[2 * i + 1], A.dec_a[i], c, nullptr, 0, D, G.dec_b[i], false);
-    dgrad(net.dec[2 * i + 1], G.dec_b[i], D, c, 0, G.dec_a[i], nullptr);
-    norm(A.dec_a[i], G.dec_a[i], c, D, N.dec_part(i, 0));
-    wgrad(net.dec[2 * i], A.skip[i], net.skip_c[i], cur, 1, D, G.dec_a[i], false);
-    dgrad(net.dec[2 * i], G.dec_a[i], D, net.skip_c[i], 1, G.skip[i], g_cur);
-  }
-  for (int i = L - 1; i >= 0; --i) {
-    const Dims D = P.shifted(i + 1);
-    const int c = net.skip_c[i + 1];
-    norm(A.skip[i + 1], G.skip[i + 1], c, D, N.enc_part(i, 1));
-    wgrad(net.enc[2 * i + 1], A.enc_a[i], c, nullptr, 0, D, G.skip[i + 1], false);
-    dgrad(net.enc[2 * i + 1], G.skip[i + 1], D, c, 0, G.enc_a[i], nullptr);
-    norm(A.enc_a[i], G.enc_a[i], c, D, N.enc_part(i, 0));
-    wgrad(net.enc[2 * i], A.pooled[i], net.skip_c[i], nullptr, 0, D, G.enc_a[i], false);
-    dgrad(net.enc[2 * i], G.enc_a[i], D, net.skip_c[i], 0, G.pooled[i], nullptr);
-    {
-      Stage st(R.dev, R.rep.ms_dgrad);
-      launch_maxpool_backward(A.skip[i], G.pooled[i], G.skip[i], net.skip_c[i], P.shifted(i));
-      st.done();
-    }
-  }
-  wgrad(net.init, x, net.in_channels, nullptr, 0, P, G.skip[0], true);
-}
-
 struct BatchSums { double v[4] = {0.0, 0.0, 0.0, 0.0}; };
 
 // forward of every sample, its sums, and (with `gradient`) its gradient of the phase's loss added to d_grad
 void run_batch(Trainer& T, int phase, int n, const float* lp, const float* fp, const float* t, bool gradient, BatchSums& sums) {
-  TrainRunner& R = T.R;
+  SpeedupRunner& R = T.R;
   const size_t hw = T.hw;
   const int S = segments_of(hw);
   // A sample's backward pass runs on the gradient of ITS mean loss (1 / (nv nu)) and is the same bytes in any batch; the share 1 / B
   // of the batch is applied where the sample's gradient is rounded to float32 and added to the batch's
   const double inv_hw = 1.0 / (double)hw, inv_b = 1.0 / (double)n;
-  if (gradient) HIP_TRY(hipMemset(T.d_grad, 0, T.n_w * 4));
+  if (gradient) HIP_TRY(hipMemset(T.core.d_grad, 0, T.core.n_w * 4));
   std::vector<Sums4> host((size_t)S * n);
   for (int p = 0; p < n; ++p) {
     {
@@ -559,11 +451,11 @@ void run_batch(Trainer& T, int phase, int n, const float* lp, const float* fp, c
     if (!gradient) continue;
     if (phase == MCGPU_SPEEDUP_PHASE_MEAN) {
       hipLaunchKernelGGL(l1_grad_kernel, dim3(blocks_of(hw)), dim3(256), 0, nullptr, T.d_mean, T.d_t, T.mean_net->act->out, T.mean_net->grad->out, hw, inv_hw);
-      backward_sample(T, *T.mean_net, T.d_x, inv_b);
+      backward_sample(R, *T.mean_net, T.d_x, T.core, inv_b);
     } else {
       hipLaunchKernelGGL(nll_grad_kernel, dim3(blocks_of(hw)), dim3(256), 0, nullptr, T.d_mean, T.d_var, T.d_t, T.var_net->act->out, T.var_net->grad->out, hw,
                          inv_hw);
-      backward_sample(T, *T.var_net, T.d_mean, inv_b);
+      backward_sample(R, *T.var_net, T.d_mean, T.core, inv_b);
     }
   }
   HIP_TRY(hipMemcpy(host.data(), T.d_sums, host.size() * sizeof(Sums4), hipMemcpyDeviceToHost));  // once per batch; waits for the device
@@ -582,16 +474,7 @@ void fill_report(Trainer& T, int phase, int n, const BatchSums& s, const std::ch
   r.psnr_after = 20.0 * std::log10(8.711442 / std::sqrt(s.v[3] / N));
   r.step = T.step_mean + T.step_var;
   r.lr = T.lr;
-  r.peak_device_bytes = T.R.dev.peak;
-  r.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  mcgpu::write_report(report, r);
-}
-
-void clear_times(Report& r) { r.ms_forward = r.ms_wgrad = r.ms_dgrad = r.ms_norm = r.ms_optimizer = r.ms_total = 0.0; }
-
-void check_state(const char* fn, const Trainer* T, const mcgpu_speedup_train_state& s) {
-  if ((s.weights || s.moment1 || s.moment2) && s.n_weights != T->n_w)
-    refuse(fn, "n_weights is " + std::to_string(s.n_weights) + " but the trainer has " + std::to_string(T->n_w) + " values");
+  finish_report(T.R, t0, report);
 }
 
 }  // namespace
@@ -605,43 +488,29 @@ extern "C" int mcgpu_speedup_train_create(const mcgpu_speedup_train_options* cal
   mcgpu::read_options(fn, "mcgpu_speedup_train_options", caller_o, T->o);
   const mcgpu_speedup_train_options& o = T->o;
   check_create(fn, o);
-  TrainRunner& R = T->R;
+  SpeedupRunner& R = T->R;
   R.dry = o.dry != 0;
   T->P = Dims{o.nv, o.nu};
   T->hw = T->P.voxels();
-  T->n_w = (size_t)o.n_weights;
   T->lr = o.lr;
   const size_t hw = T->hw;
   const NetShape ms{o.mean_in_channels, o.mean_levels, o.mean_filter_base}, vs{o.var_in_channels, o.var_levels, o.var_filter_base};
-  int widest = 1;
-  {
-    size_t c = 0;
-    widest = std::max(layers_of(ms, c).widest(), layers_of(vs, c).widest());
-  }
+  size_t cursor = 0;
+  NetLayers mean_layers = train_layers(ms, cursor), var_layers = train_layers(vs, cursor);
+  const int widest = std::max(mean_layers.widest(), var_layers.widest());
   R.init(o.device, widest);
-  T->d_w = R.upload(o.weights, T->n_w);
-  T->d_m1 = R.alloc(T->n_w);
-  T->d_m2 = R.alloc(T->n_w);
-  T->d_grad = R.alloc(T->n_w);
-  T->d_zero = R.alloc((size_t)2 * widest + 2);  // the bias of the input-gradient GEMMs: as many as the widest concatenated input has channels
+  TrainCore& C = T->core;
+  C.alloc(R, o.device, o.weights, (size_t)o.n_weights, widest);
   T->d_x = R.alloc(2 * hw);  // channel 0: the low-photon projection, channel 1: the matched forward projection
   T->d_fp = R.alloc(hw);
   T->d_t = R.alloc(hw);
   T->d_mean = R.alloc(hw);
   T->d_var = R.alloc(hw);
-  T->d_bpart = (double2*)R.alloc_bytes((size_t)widest * kMaxSegments * sizeof(double2), true);
   T->d_sums = (Sums4*)R.alloc_bytes((size_t)o.max_batch * kMaxSegments * sizeof(Sums4), true);  // of every sample of a batch
-  size_t cursor = 0;
-  T->mean_net.reset(new TrainNet(ms, cursor, R, T->P, T->d_w, T->d_zero));
-  T->var_net.reset(new TrainNet(vs, cursor, R, T->P, T->d_w, T->d_zero));
-  T->d_part = R.alloc(std::max(T->mean_net->part_floats, T->var_net->part_floats));
-  T->d_ext = R.alloc(std::max(T->mean_net->ext_floats, T->var_net->ext_floats));
-  if (!R.dry) {
-    T->mean_net->pack(T->d_w);
-    T->var_net->pack(T->d_w);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-  }
+  T->mean_net.reset(new TrainNet(std::move(mean_layers), R, T->P, C.d_w, C.d_zero));
+  T->var_net.reset(new TrainNet(std::move(var_layers), R, T->P, C.d_w, C.d_zero));
+  C.alloc_scratch(std::max(T->mean_net->part_floats, T->var_net->part_floats), std::max(T->mean_net->ext_floats, T->var_net->ext_floats));
+  if (!R.dry) C.repack({T->mean_net.get(), T->var_net.get()});
   *handle = T.release();
   return 0;
   ABI_END
@@ -653,7 +522,7 @@ extern "C" int mcgpu_speedup_train_step(mcgpu_speedup_trainer* T, int phase, int
   const char* fn = "mcgpu_speedup_train_step";
   check_batch(fn, T, phase, n, low_photon, forward_projection, high_photon, true);
   mcgpu::check_report(fn, "report", "mcgpu_speedup_train_report", report);
-  check_live(fn, T);
+  T->core.check_live(fn);
   const auto t0 = std::chrono::steady_clock::now();
   clear_times(T->R.rep);
   BatchSums sums;
@@ -663,8 +532,7 @@ extern "C" int mcgpu_speedup_train_step(mcgpu_speedup_trainer* T, int phase, int
     TrainNet& N = phase == MCGPU_SPEEDUP_PHASE_MEAN ? *T->mean_net : *T->var_net;
     unsigned long long& t = phase == MCGPU_SPEEDUP_PHASE_MEAN ? T->step_mean : T->step_var;
     ++t;
-    launch_adam(T->d_w + N.w_begin, T->d_grad + N.w_begin, T->d_m1 + N.w_begin, T->d_m2 + N.w_begin, N.w_end - N.w_begin, T->lr, T->o.beta1, T->o.beta2, t);
-    N.pack(T->d_w);
+    T->core.update(N, T->lr, T->o.beta1, T->o.beta2, t);
     st.done();
     T->lr *= T->o.gamma;
   }
@@ -680,12 +548,12 @@ extern "C" int mcgpu_speedup_train_gradients(mcgpu_speedup_trainer* T, int phase
   check_batch(fn, T, phase, n, low_photon, forward_projection, high_photon, true);
   if (!flat_gradient) refuse(fn, "flat_gradient is NULL");
   mcgpu::check_report(fn, "report", "mcgpu_speedup_train_report", report);
-  check_live(fn, T);
+  T->core.check_live(fn);
   const auto t0 = std::chrono::steady_clock::now();
   clear_times(T->R.rep);
   BatchSums sums;
   run_batch(*T, phase, n, low_photon, forward_projection, high_photon, true, sums);
-  HIP_TRY(hipMemcpy(flat_gradient, T->d_grad, T->n_w * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(flat_gradient, T->core.d_grad, T->core.n_w * 4, hipMemcpyDeviceToHost));
   fill_report(*T, phase, n, sums, t0, report);
   return 0;
   ABI_END
@@ -696,7 +564,7 @@ extern "C" int mcgpu_speedup_train_predict(mcgpu_speedup_trainer* T, int n, cons
   ABI_BEGIN
   const char* fn = "mcgpu_speedup_train_predict";
   check_batch(fn, T, MCGPU_SPEEDUP_PHASE_MEAN, n, low_photon, forward_projection, nullptr, false);
-  check_live(fn, T);
+  T->core.check_live(fn);
   for (int p = 0; p < n; ++p) {
     forward_sample(*T, low_photon, forward_projection, p);
     HIP_TRY(hipGetLastError());
@@ -714,18 +582,13 @@ extern "C" int mcgpu_speedup_train_get_state(mcgpu_speedup_trainer* T, mcgpu_spe
   if (!T) refuse(fn, "handle is NULL");
   mcgpu_speedup_train_state s;
   mcgpu::read_options(fn, "mcgpu_speedup_train_state", caller_s, s);
-  check_state(fn, T, s);
-  if (s.weights || s.moment1 || s.moment2) {
-    check_live(fn, T);
-    if (s.weights) HIP_TRY(hipMemcpy(s.weights, T->d_w, T->n_w * 4, hipMemcpyDeviceToHost));
-    if (s.moment1) HIP_TRY(hipMemcpy(s.moment1, T->d_m1, T->n_w * 4, hipMemcpyDeviceToHost));
-    if (s.moment2) HIP_TRY(hipMemcpy(s.moment2, T->d_m2, T->n_w * 4, hipMemcpyDeviceToHost));
-  }
-  s.n_weights = T->n_w;
+  T->core.check_state(fn, s);
+  T->core.get_arrays(fn, s);
+  s.n_weights = T->core.n_w;
   s.step_mean = T->step_mean;
   s.step_variance = T->step_var;
   s.lr = T->lr;
-  s.planned_device_bytes = T->R.dry ? T->R.planned : T->R.dev.held;
+  s.planned_device_bytes = T->core.planned_bytes();
   mcgpu::write_report(caller_s, s);
   return 0;
   ABI_END
@@ -737,20 +600,9 @@ extern "C" int mcgpu_speedup_train_set_state(mcgpu_speedup_trainer* T, const mcg
   if (!T) refuse(fn, "handle is NULL");
   mcgpu_speedup_train_state s;
   mcgpu::read_options(fn, "mcgpu_speedup_train_state", caller_s, s);
-  check_state(fn, T, s);
+  T->core.check_state(fn, s);
   if (!(s.lr > 0.0)) refuse(fn, "lr must be > 0");
-  if (s.weights || s.moment1 || s.moment2) {
-    check_live(fn, T);
-    if (s.weights) HIP_TRY(hipMemcpy(T->d_w, s.weights, T->n_w * 4, hipMemcpyHostToDevice));
-    if (s.moment1) HIP_TRY(hipMemcpy(T->d_m1, s.moment1, T->n_w * 4, hipMemcpyHostToDevice));
-    if (s.moment2) HIP_TRY(hipMemcpy(T->d_m2, s.moment2, T->n_w * 4, hipMemcpyHostToDevice));
-    if (s.weights) {
-      T->mean_net->pack(T->d_w);
-      T->var_net->pack(T->d_w);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipDeviceSynchronize());
-    }
-  }
+  T->core.set_arrays(fn, s, {T->mean_net.get(), T->var_net.get()});
   T->step_mean = s.step_mean;
   T->step_var = s.step_variance;
   T->lr = s.lr;
@@ -791,43 +643,29 @@ extern "C" int mcgpu_speedup_train_stage(int stage, const mcgpu_speedup_train_st
     if (!(a.beta1 >= 0.0 && a.beta1 < 1.0) || !(a.beta2 >= 0.0 && a.beta2 < 1.0)) refuse(fn, "beta1 and beta2 must be in [0, 1)");
   }
   const auto t0 = std::chrono::steady_clock::now();
-  TrainRunner R;
+  SpeedupRunner R;
   R.init(a.device, std::max(std::max(a.c1, a.c_out), 1));
   const Dims D{a.nv, a.nu};
   const size_t hw = D.voxels();
   switch (stage) {
-    case MCGPU_SPEEDUP_TRAIN_STAGE_CONV_WGRAD: {
-      const Dims E = a.upsample ? D.halved_up() : D;
-      const int c_in = a.c1 + a.c2;
-      const float* d_in = R.upload(a.in, (size_t)a.c1 * hw);
-      const float* d_in2 = a.c2 ? R.upload(a.in2, (size_t)a.c2 * E.voxels()) : nullptr;
-      const float* d_dy = R.upload(a.in3, (size_t)a.c_out * hw);
-      float* d_part = R.alloc(wgrad_part_floats(c_in, a.c_out, D));
-      const size_t n_w = (size_t)a.c_out * c_in * 9;
-      float* d_grad = R.alloc(n_w + a.c_out);
-      Stage st(R.dev, R.rep.ms_wgrad);
-      launch_wgrad(R, a.c_out, d_in, a.c1, d_in2, a.c2, a.upsample, D, d_dy, d_part, d_grad, d_grad + n_w, 1.0);
-      st.done();
-      HIP_TRY(hipMemcpy(a.out, d_grad, n_w * 4, hipMemcpyDeviceToHost));
-      if (a.out2) HIP_TRY(hipMemcpy(a.out2, d_grad + n_w, (size_t)a.c_out * 4, hipMemcpyDeviceToHost));
-      if (a.values) a.values[0] = (double)wgrad_plan(c_in, a.c_out, D).partials();
+    case MCGPU_SPEEDUP_TRAIN_STAGE_CONV_WGRAD:
+      stage_wgrad(R, a, D);
       break;
-    }
     case MCGPU_SPEEDUP_TRAIN_STAGE_CONV_DGRAD: {
       const Dims E = a.upsample ? D.halved_up() : D;
       size_t cursor = 0;
       ConvLayer l = conv_layer(a.c1 + a.c2, a.c_out, cursor);
-      ConvLayer d = dgrad_layer(l);
+      Dgrad d(l, a.c1);
       const float* d_dy = R.upload(a.in, (size_t)a.c_out * hw);
       const float* d_w = R.upload(a.in2, (size_t)a.c_out * l.c_in * 9);
-      d.wpack = R.alloc(d.pack_floats());
-      d.bias = R.alloc((size_t)d.c_out);
-      float* d_ext = R.alloc(dgrad_ext_floats(l.c_in, D));
+      d.g.wpack = R.alloc(d.g.pack_floats());
+      d.g.bias = R.alloc((size_t)d.g.c_out);
+      float* d_ext = R.alloc(dgrad_ext_floats(l, a.c1, D));
       float* d_o1 = R.alloc((size_t)a.c1 * hw);
       float* d_o2 = R.alloc((size_t)std::max(a.c2, 1) * E.voxels());
-      launch_pack_dgrad(l, d, d_w);
+      d.pack(l, d_w);
       Stage st(R.dev, R.rep.ms_dgrad);
-      launch_dgrad(d, d_dy, D, d_ext, a.c1, a.upsample, d_o1, d_o2);
+      launch_dgrad(d, d_dy, D, d_ext, a.upsample, d_o1, d_o2);
       st.done();
       HIP_TRY(hipMemcpy(a.out, d_o1, (size_t)a.c1 * hw * 4, hipMemcpyDeviceToHost));
       if (a.c2) HIP_TRY(hipMemcpy(a.out2, d_o2, (size_t)a.c2 * E.voxels() * 4, hipMemcpyDeviceToHost));
@@ -845,17 +683,9 @@ extern "C" int mcgpu_speedup_train_stage(int stage, const mcgpu_speedup_train_st
       HIP_TRY(hipMemcpy(a.out, d_dy, (size_t)a.c1 * hw * 4, hipMemcpyDeviceToHost));
       break;
     }
-    case MCGPU_SPEEDUP_TRAIN_STAGE_MAXPOOL_BACKWARD: {
-      const float* d_x = R.upload(a.in, (size_t)a.c1 * hw);
-      const size_t n_dy = (size_t)a.c1 * D.shifted(1).voxels();
-      const float* d_dy = R.upload(a.in2, std::max<size_t>(n_dy, 1));
-      float* d_dx = R.alloc((size_t)a.c1 * hw);
-      Stage st(R.dev, R.rep.ms_dgrad);
-      launch_maxpool_backward(d_x, d_dy, d_dx, a.c1, D);
-      st.done();
-      HIP_TRY(hipMemcpy(a.out, d_dx, (size_t)a.c1 * hw * 4, hipMemcpyDeviceToHost));
+    case MCGPU_SPEEDUP_TRAIN_STAGE_MAXPOOL_BACKWARD:
+      stage_maxpool_backward(R, a, D, nullptr);
       break;
-    }
     case MCGPU_SPEEDUP_TRAIN_STAGE_LOSS_L1:
     case MCGPU_SPEEDUP_TRAIN_STAGE_LOSS_NLL: {
       const bool l1 = stage == MCGPU_SPEEDUP_TRAIN_STAGE_LOSS_L1;
@@ -905,9 +735,7 @@ extern "C" int mcgpu_speedup_train_stage(int stage, const mcgpu_speedup_train_st
       HIP_TRY(hipMemcpy(a.out3, d_m2, n * 4, hipMemcpyDeviceToHost));
     }
   }
-  R.rep.peak_device_bytes = R.dev.peak;
-  R.rep.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  mcgpu::write_report(report, R.rep);
+  finish_report(R, t0, report);
   return 0;
   ABI_END
 }

@@ -23,6 +23,7 @@ from typing import Dict, Iterable, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _unet
+from ._unet_training import DeviceTrainer
 from .segmentation import LABELS, N_LABELS, unet_tensors
 
 logger = logging.getLogger(__name__)
@@ -160,11 +161,14 @@ def _targets(a, images: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(a if a.dtype == np.uint8 else a.astype(np.float32, copy=False))
 
 
-class CTSegmentationTrainer:
+class CTSegmentationTrainer(DeviceTrainer):
     """Mirror of cbctmc/segmentation/trainer.py: CTSegmentationTrainer on a device-resident trainer, with the driver's loss
     (Dice, `use_dice=True`) and optimizer (Adam, lr 1e-4).  `weights`: a state dict by the reference's names, a path to one
     (`.pth` / `.npz`) or None for `initial_weights(seed, n_filters, levels)`.  `lr_scheduler`: a `ReduceLROnPlateau` of this
     module or None; it is stepped on `loss` after every update, as the reference's post-hook does."""
+
+    ABI = "mcgpu_segment_train_"
+    _library = staticmethod(_library)
 
     def __init__(self, weights=None, seed: int = 0, lr: float = 1e-4, lr_scheduler: Optional[ReduceLROnPlateau] = None,
                  n_filters: Sequence[int] = (32,) * 10, levels: int = 4, device: int = 0, betas=(0.9, 0.999),
@@ -182,13 +186,10 @@ class CTSegmentationTrainer:
         elif not isinstance(weights, dict):
             weights = _unet.read_weights(weights)
         weights = {k: (v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)) for k, v in weights.items()}
-        self._flat = _unet.flatten(weights, self.tensors, "inconsistent weight shapes: ")
-        self._moment1 = self._moment2 = None
+        self._init_state(_unet.flatten(weights, self.tensors, "inconsistent weight shapes: "))
         self.device, self.betas = int(device), (float(betas[0]), float(betas[1]))
         self.lr, self.lr_scheduler = float(lr), lr_scheduler
         self.i_step = 0
-        self._handle, self._shape = None, None
-        self.last_report: dict = {}
 
     # ------------------------------------------------------------------------------------------------------------ the handle
     def _options(self, n: int, patch_shape, dry: bool = False) -> _TrainOptions:
@@ -206,60 +207,12 @@ class CTSegmentationTrainer:
             s.weights, s.moment1, s.moment2 = self._flat.ctypes.data, self._moment1.ctypes.data, self._moment2.ctypes.data
         return s
 
-    def _pull(self):
-        """Weights, moments and the step count from the device into this object."""
-        from . import engine
-        if self._handle is None:
-            return
-        if self._moment1 is None:
-            self._moment1, self._moment2 = np.zeros_like(self._flat), np.zeros_like(self._flat)
-        s = self._state(True)
-        engine._check(_library().mcgpu_segment_train_get_state(self._handle, C.byref(s)))
+    def _read_state(self, s: _TrainState):
         self.i_step = int(s.step)
-
-    def _push(self):
-        from . import engine
-        if self._handle is not None:
-            s = self._state(self._moment1 is not None)
-            engine._check(_library().mcgpu_segment_train_set_state(self._handle, C.byref(s)))
-
-    def close(self):
-        """Brings the state to the host and frees the device."""
-        if self._handle is not None:
-            self._pull()
-            _library().mcgpu_segment_train_destroy(self._handle)
-            self._handle, self._shape = None, None
-
-    def __del__(self):
-        try:
-            if self._handle is not None:
-                _library().mcgpu_segment_train_destroy(self._handle)
-                self._handle = None
-        except Exception:
-            pass
-
-    def _ensure(self, n: int, patch_shape):
-        """A handle for [n <= max_batch][patch]; a batch of another extent or a larger one makes a new handle with the state kept."""
-        from . import engine
-        if self._handle is not None and self._shape[1:] == tuple(patch_shape) and n <= self._shape[0]:
-            return
-        self.close()
-        handle = C.c_void_p()
-        engine._check(_library().mcgpu_segment_train_create(C.byref(self._options(n, patch_shape)), C.byref(handle)))
-        self._handle, self._shape = handle, (n,) + tuple(patch_shape)
-        self._push()
 
     def planned_device_bytes(self, n: int, patch_shape) -> int:
         """What a trainer for batches [n][patch] holds on the device, planned without touching it."""
-        from . import engine
-        lib, handle = _library(), C.c_void_p()
-        engine._check(lib.mcgpu_segment_train_create(C.byref(self._options(n, patch_shape, dry=True)), C.byref(handle)))
-        s = _TrainState(struct_size=C.sizeof(_TrainState))
-        try:
-            engine._check(lib.mcgpu_segment_train_get_state(handle, C.byref(s)))
-        finally:
-            lib.mcgpu_segment_train_destroy(handle)
-        return int(s.planned_device_bytes)
+        return self._planned(n, patch_shape)
 
     # ----------------------------------------------------------------------------------------------------------- the batches
     def _inputs(self, data: dict, need_target: bool = True):
@@ -322,14 +275,6 @@ class CTSegmentationTrainer:
         return logits
 
     # ------------------------------------------------------------------------------------------------------------- the files
-    def _named(self, flat: np.ndarray) -> Dict[str, np.ndarray]:
-        out, at = {}, 0
-        for name, shape in self.tensors:
-            n = int(np.prod(shape))
-            out[name] = flat[at:at + n].reshape(shape).copy()
-            at += n
-        return out
-
     def state_dict(self) -> Dict[str, np.ndarray]:
         """The weights by the reference's names: what the reference's `load_state_dict` accepts."""
         self._pull()
@@ -338,46 +283,23 @@ class CTSegmentationTrainer:
     def save(self, path) -> Path:
         """`.npz` by the state dict's names, or `.pth` as {"model": state dict} (needs torch): both load with
         `MCSegmenter.from_filepath`."""
-        path = Path(path)
-        state = self.state_dict()
-        path.parent.mkdir(parents=True, exist_ok=True)
-        if path.suffix == ".npz":
-            np.savez(path, **state)
-        elif path.suffix == ".pth":
-            import torch
-            torch.save({"model": {k: torch.as_tensor(v) for k, v in state.items()}}, path)
-        else:
-            raise ValueError(f"{path}: expected .npz or .pth")
-        return path
+        return super().save(path)
 
-    def save_checkpoint(self, path) -> Path:
-        """Weights, both moments, the step count, the learning rate and the scheduler's state (`.npz`): a run resumed from it
-        continues bit for bit."""
-        self._pull()
-        if self._moment1 is None:
-            self._moment1, self._moment2 = np.zeros_like(self._flat), np.zeros_like(self._flat)
-        path = Path(path)
-        path.parent.mkdir(parents=True, exist_ok=True)
+    def _checkpoint_extra(self) -> dict:
+        """Beside weights and moments: the step count, the learning rate, the architecture and the scheduler's state."""
         sched = self.lr_scheduler.state_dict() if self.lr_scheduler is not None else {}
-        np.savez(path, weights=self._flat, moment1=self._moment1, moment2=self._moment2, i_step=np.int64(self.i_step), lr=np.float64(self.lr),
-                 n_filters=np.asarray(self.n_filters), levels=np.int64(self.levels), scheduler_keys=np.asarray(list(sched.keys()), dtype=str),
-                 scheduler_values=np.asarray(list(sched.values()), dtype=np.float64))
-        return path
+        return dict(i_step=np.int64(self.i_step), lr=np.float64(self.lr), n_filters=np.asarray(self.n_filters), levels=np.int64(self.levels),
+                    scheduler_keys=np.asarray(list(sched.keys()), dtype=str), scheduler_values=np.asarray(list(sched.values()), dtype=np.float64))
 
-    def load_checkpoint(self, path):
-        with np.load(Path(path)) as f:
-            if tuple(int(v) for v in f["n_filters"]) != self.n_filters or int(f["levels"]) != self.levels:
-                raise ValueError(f"{path}: architecture {tuple(f['n_filters'])} / {int(f['levels'])} levels, this trainer has {self.n_filters} / {self.levels}")
-            self._flat = np.ascontiguousarray(f["weights"], dtype=np.float32)
-            self._moment1 = np.ascontiguousarray(f["moment1"], dtype=np.float32)
-            self._moment2 = np.ascontiguousarray(f["moment2"], dtype=np.float32)
-            self.i_step, self.lr = int(f["i_step"]), float(f["lr"])
-            sched = dict(zip([str(k) for k in f["scheduler_keys"]], [float(v) for v in f["scheduler_values"]]))
+    def _load_checkpoint_extra(self, path, f):
+        if tuple(int(v) for v in f["n_filters"]) != self.n_filters or int(f["levels"]) != self.levels:
+            raise ValueError(f"{path}: architecture {tuple(f['n_filters'])} / {int(f['levels'])} levels, this trainer has {self.n_filters} / {self.levels}")
+        self.i_step, self.lr = int(f["i_step"]), float(f["lr"])
+        sched = dict(zip([str(k) for k in f["scheduler_keys"]], [float(v) for v in f["scheduler_values"]]))
         if sched:
             if self.lr_scheduler is None:
                 self.lr_scheduler = ReduceLROnPlateau()
             self.lr_scheduler.load_state_dict(sched)
-        self._push()
 
 
 # ------------------------------------------------------------------------------------------------------------------ the data

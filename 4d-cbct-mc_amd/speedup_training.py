@@ -20,6 +20,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import _unet
+from ._unet_training import DeviceTrainer
 from .speedup import state_dict_tensors
 
 logger = logging.getLogger(__name__)
@@ -113,11 +114,14 @@ def _batch(a, name: str) -> Optional[np.ndarray]:
     return np.ascontiguousarray(a)
 
 
-class MCSpeedupTrainer:
+class MCSpeedupTrainer(DeviceTrainer):
     """Mirror of cbctmc/speedup/trainer.py: MCSpeedUpTrainer on a device-resident trainer.  `weights`: a state dict by the
     reference's names (None: `initial_weights(seed, ...)`); the architecture is `mean_net` / `var_net` = (input channels, levels,
     filter base).  The phase is "mean" while `i_step < n_pretrain_steps` and "variance" afterwards; at the switch the learning
     rate goes back to `lr`, as the reference resets it."""
+
+    ABI = "mcgpu_speedup_train_"
+    _library = staticmethod(_library)
 
     def __init__(self, weights: Optional[Dict[str, np.ndarray]] = None, mean_net=(2, 4, 64), var_net=(1, 2, 16), device: int = 0, seed: int = 0,
                  lr: float = 1e-3, gamma: float = 0.99999, n_pretrain_steps: Optional[int] = 5000, betas=(0.9, 0.999)):
@@ -128,15 +132,12 @@ class MCSpeedupTrainer:
         if weights is None:
             weights = initial_weights(seed, self.mean_net, self.var_net)
         weights = {k: (v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)) for k, v in weights.items() if k != "var_scale"}
-        self._flat = _unet.flatten(weights, self.tensors)
-        self._moment1 = self._moment2 = None
+        self._init_state(_unet.flatten(weights, self.tensors))
         self._steps = [0, 0]
         self.device, self.lr0, self.gamma, self.betas = int(device), float(lr), float(gamma), (float(betas[0]), float(betas[1]))
         self._lr = self.lr0
         self.n_pretrain_steps = int(n_pretrain_steps)
         self.i_step = 0
-        self._handle, self._shape = None, None
-        self.last_report: dict = {}
 
     # ------------------------------------------------------------------------------------------------------------ the handle
     @property
@@ -147,7 +148,8 @@ class MCSpeedupTrainer:
     def phase(self) -> str:
         return "mean" if self.i_step < self.n_pretrain_steps else "variance"
 
-    def _options(self, nv: int, nu: int, max_batch: int, dry: bool = False) -> _TrainOptions:
+    def _options(self, max_batch: int, extent, dry: bool = False) -> _TrainOptions:
+        nv, nu = extent
         return _TrainOptions(C.sizeof(_TrainOptions), self.device, int(nu), int(nv), int(max_batch), *self.mean_net, *self.var_net, int(dry),
                              self._flat.ctypes.data, self._flat.size, self._lr, self.gamma, *self.betas)
 
@@ -157,60 +159,12 @@ class MCSpeedupTrainer:
             s.weights, s.moment1, s.moment2 = self._flat.ctypes.data, self._moment1.ctypes.data, self._moment2.ctypes.data
         return s
 
-    def _pull(self):
-        """Weights, moments, step counts and learning rate from the device into this object."""
-        from . import engine
-        if self._handle is None:
-            return
-        if self._moment1 is None:
-            self._moment1, self._moment2 = np.zeros_like(self._flat), np.zeros_like(self._flat)
-        s = self._state(True)
-        engine._check(_library().mcgpu_speedup_train_get_state(self._handle, C.byref(s)))
+    def _read_state(self, s: _TrainState):
         self._steps, self._lr = [int(s.step_mean), int(s.step_variance)], float(s.lr)
-
-    def _push(self, arrays: bool = True):
-        from . import engine
-        if self._handle is not None:
-            s = self._state(arrays and self._moment1 is not None)
-            engine._check(_library().mcgpu_speedup_train_set_state(self._handle, C.byref(s)))
-
-    def close(self):
-        """Brings the state to the host and frees the device."""
-        if self._handle is not None:
-            self._pull()
-            _library().mcgpu_speedup_train_destroy(self._handle)
-            self._handle, self._shape = None, None
-
-    def __del__(self):
-        try:
-            if self._handle is not None:
-                _library().mcgpu_speedup_train_destroy(self._handle)
-                self._handle = None
-        except Exception:
-            pass
-
-    def _ensure(self, n: int, nv: int, nu: int):
-        """A handle for [n <= max_batch][nv][nu]; a batch of another extent or a larger one makes a new handle with the state kept."""
-        from . import engine
-        if self._handle is not None and self._shape[1:] == (nv, nu) and n <= self._shape[0]:
-            return
-        self.close()
-        handle = C.c_void_p()
-        engine._check(_library().mcgpu_speedup_train_create(C.byref(self._options(nv, nu, n)), C.byref(handle)))
-        self._handle, self._shape = handle, (n, nv, nu)
-        self._push()
 
     def planned_device_bytes(self, n: int, nv: int, nu: int) -> int:
         """What a trainer for batches [n][nv][nu] holds on the device, planned without touching it."""
-        from . import engine
-        lib, handle = _library(), C.c_void_p()
-        engine._check(lib.mcgpu_speedup_train_create(C.byref(self._options(nv, nu, n, dry=True)), C.byref(handle)))
-        s = _TrainState(struct_size=C.sizeof(_TrainState))
-        try:
-            engine._check(lib.mcgpu_speedup_train_get_state(handle, C.byref(s)))
-        finally:
-            lib.mcgpu_speedup_train_destroy(handle)
-        return int(s.planned_device_bytes)
+        return self._planned(n, (nv, nu))
 
     # ----------------------------------------------------------------------------------------------------------- the batches
     def _inputs(self, data: dict, need_target: bool = True):
@@ -224,14 +178,14 @@ class MCSpeedupTrainer:
                 raise ValueError(f"{name} has shape {a.shape}, low_photon {lp.shape}")
         if need_target and t is None:
             raise ValueError("data['high_photon'] is missing")
-        self._ensure(*lp.shape)
+        self._ensure(lp.shape[0], lp.shape[1:])
         return lp, fp, t
 
     def _step(self, data: dict, update: bool) -> dict:
         from . import engine
         lp, fp, t = self._inputs(data)
         if update and self.i_step == self.n_pretrain_steps and self.i_step > 0:
-            self._pull_counters()
+            self._pull(arrays=False)
             self._lr = self.lr0  # the reference sets the learning rate back at the switch to the variance stage
             self._push(arrays=False)
         rep = _TrainReport(struct_size=C.sizeof(_TrainReport))
@@ -241,12 +195,6 @@ class MCSpeedupTrainer:
             self.i_step += 1
         self.last_report = _unet.report_dict(rep)
         return {k: float(getattr(rep, k)) for k in METRICS}
-
-    def _pull_counters(self):
-        from . import engine
-        s = _TrainState(struct_size=C.sizeof(_TrainState))
-        engine._check(_library().mcgpu_speedup_train_get_state(self._handle, C.byref(s)))
-        self._steps, self._lr = [int(s.step_mean), int(s.step_variance)], float(s.lr)
 
     def train_on_batch(self, data: dict) -> dict:
         """One update on a batch {"low_photon", "forward_projection", "high_photon"} -> the reference's five metrics."""
@@ -277,14 +225,6 @@ class MCSpeedupTrainer:
         return mean, variance
 
     # ------------------------------------------------------------------------------------------------------------- the files
-    def _named(self, flat: np.ndarray) -> Dict[str, np.ndarray]:
-        out, at = {}, 0
-        for name, shape in self.tensors:
-            n = int(np.prod(shape))
-            out[name] = flat[at:at + n].reshape(shape).copy()
-            at += n
-        return out
-
     def state_dict(self) -> Dict[str, np.ndarray]:
         """The weights by the reference's names, `var_scale` included: what the reference's `load_state_dict` accepts."""
         self._pull()
@@ -295,38 +235,17 @@ class MCSpeedupTrainer:
     def save(self, path) -> Path:
         """`.npz` by the state dict's names, or `.pth` as {"model": state dict} (needs torch): both load with
         `MCSpeedup.from_filepath`."""
-        path = Path(path)
-        state = self.state_dict()
-        path.parent.mkdir(parents=True, exist_ok=True)
-        if path.suffix == ".npz":
-            np.savez(path, **state)
-        elif path.suffix == ".pth":
-            import torch
-            torch.save({"model": {k: torch.as_tensor(v) for k, v in state.items()}}, path)
-        else:
-            raise ValueError(f"{path}: expected .npz or .pth")
-        return path
+        return super().save(path)
 
-    def save_checkpoint(self, path) -> Path:
-        """Weights, both moments, the step counts and the learning rate (`.npz`): a run resumed from it continues bit for bit."""
-        self._pull()
-        if self._moment1 is None:
-            self._moment1, self._moment2 = np.zeros_like(self._flat), np.zeros_like(self._flat)
-        path = Path(path)
-        path.parent.mkdir(parents=True, exist_ok=True)
-        np.savez(path, weights=self._flat, moment1=self._moment1, moment2=self._moment2, steps=np.asarray(self._steps, dtype=np.int64),
-                 i_step=np.int64(self.i_step), lr=np.float64(self._lr), mean_net=np.asarray(self.mean_net), var_net=np.asarray(self.var_net))
-        return path
+    def _checkpoint_extra(self) -> dict:
+        """Beside weights and moments: the step counts, the learning rate and the architecture."""
+        return dict(steps=np.asarray(self._steps, dtype=np.int64), i_step=np.int64(self.i_step), lr=np.float64(self._lr), mean_net=np.asarray(self.mean_net),
+                    var_net=np.asarray(self.var_net))
 
-    def load_checkpoint(self, path):
-        with np.load(Path(path)) as f:
-            if tuple(f["mean_net"]) != self.mean_net or tuple(f["var_net"]) != self.var_net:
-                raise ValueError(f"{path}: architecture {tuple(f['mean_net'])} / {tuple(f['var_net'])}, this trainer has {self.mean_net} / {self.var_net}")
-            self._flat = np.ascontiguousarray(f["weights"], dtype=np.float32)
-            self._moment1 = np.ascontiguousarray(f["moment1"], dtype=np.float32)
-            self._moment2 = np.ascontiguousarray(f["moment2"], dtype=np.float32)
-            self._steps, self.i_step, self._lr = [int(v) for v in f["steps"]], int(f["i_step"]), float(f["lr"])
-        self._push()
+    def _load_checkpoint_extra(self, path, f):
+        if tuple(f["mean_net"]) != self.mean_net or tuple(f["var_net"]) != self.var_net:
+            raise ValueError(f"{path}: architecture {tuple(f['mean_net'])} / {tuple(f['var_net'])}, this trainer has {self.mean_net} / {self.var_net}")
+        self._steps, self.i_step, self._lr = [int(v) for v in f["steps"]], int(f["i_step"]), float(f["lr"])
 
 
 # ------------------------------------------------------------------------------------------------------------------ the data

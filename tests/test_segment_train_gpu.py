@@ -329,6 +329,35 @@ def test_validation_changes_nothing_and_a_checkpoint_splits_a_run_bit_for_bit(en
     resumed.close()
 
 
+def test_a_handle_made_anew_for_a_larger_batch_carries_the_whole_state(engine):
+    """Trainer A takes two updates at batch 1, then one at batch 2: the larger batch closes the handle (state to the host), makes one
+    for batches of 2 and pushes the state into it.  Trainer B validates a batch of 2 first, so its one handle serves all three updates.
+    A sample's backward pass does not depend on the batch it is in and validation changes nothing (both asserted above), so A and B
+    end with the same bytes: weights, both moments, the step count and the learning rate."""
+    c = _gradient_case("L2_8x8x8")
+    one = c["data"]
+    two = {"image": np.concatenate([one["image"], one["image"][:, :, ::-1]]), "segmentation": np.concatenate([one["segmentation"], one["segmentation"][:, :, ::-1]])}
+    a, b = (training.CTSegmentationTrainer(weights=c["weights"], n_filters=c["filters"], levels=c["levels"], lr=1e-3) for _ in range(2))
+    b.validate_on_batch(two)
+    runs, sizes = [], []
+    for t in (a, b):
+        metrics = []
+        for batch in (one, one, two):
+            metrics.append(t.train_on_batch(batch))
+            sizes.append(t._shape[0])
+        runs.append(metrics)
+    assert sizes == [1, 1, 2, 2, 2, 2]  # A's handle was made anew, B's was not
+    assert runs[0] == runs[1]
+    end_a, end_b = a.state_dict(), b.state_dict()
+    assert all(end_a[k].tobytes() == end_b[k].tobytes() for k in end_a)
+    assert a._moment1.tobytes() == b._moment1.tobytes() and a._moment2.tobytes() == b._moment2.tobytes()
+    assert a._moment1.any() and a._moment2.any()
+    assert a.i_step == b.i_step == 3 and a.lr == b.lr == 1e-3
+    assert a.last_report["step"] == b.last_report["step"] == 3  # the device's own count came through the hand-over
+    a.close()
+    b.close()
+
+
 def test_saved_weights_load_with_the_segmenter_and_segment_gives_predict_plus_head(engine, tmp_path):
     c = _gradient_case("L2_8x8x8")
     trainer = training.CTSegmentationTrainer(weights=c["weights"], n_filters=c["filters"], levels=c["levels"], lr=1e-3)

@@ -406,6 +406,36 @@ def test_validation_changes_nothing_and_a_split_run_equals_a_whole_one(engine, t
     assert abs(whole._lr - 1e-3 * 0.99999 ** 2) < 1e-18  # set back to 1e-3 at the switch to the variance stage
 
 
+def test_a_handle_made_anew_for_a_larger_batch_carries_the_whole_state(engine):
+    """Trainer A takes two updates at batch 1, then one at batch 2: the larger batch closes the handle (state to the host), makes one
+    for batches of 2 and pushes the state into it.  Trainer B validates a batch of 2 first, so its one handle serves all three updates.
+    A sample's backward pass does not depend on the batch it is in and validation changes nothing (both asserted above), so A and B
+    end with the same bytes: weights, both moments, step counts, learning rate.  n_pretrain_steps = 2: the third update is also the
+    first of the variance net."""
+    nets = dict(mean_net=(2, 1, 4), var_net=(1, 1, 4))
+    lp, fp = speedup_ref.seeded_inputs(5, 2, 8, 12)
+    data = {"low_photon": lp, "forward_projection": fp, "high_photon": lp + np.float32(0.3) * np.sign(fp - np.float32(2.5))}
+    one = {k: v[:1] for k, v in data.items()}
+    a, b = (training.MCSpeedupTrainer(seed=4, n_pretrain_steps=2, **nets) for _ in range(2))
+    b.validate_on_batch(data)
+    runs, sizes = [], []
+    for t in (a, b):
+        metrics = []
+        for batch in (one, one, data):
+            metrics.append(t.train_on_batch(batch))
+            sizes.append(t._shape[0])
+        runs.append(metrics)
+    assert sizes == [1, 1, 2, 2, 2, 2]  # A's handle was made anew, B's was not
+    assert runs[0] == runs[1]
+    end_a, end_b = a.state_dict(), b.state_dict()
+    assert all(end_a[k].tobytes() == end_b[k].tobytes() for k in end_a)
+    assert a._moment1.tobytes() == b._moment1.tobytes() and a._moment2.tobytes() == b._moment2.tobytes()
+    assert a._moment1.any() and a._moment2.any()
+    assert a._steps == b._steps == [2, 1] and a._lr == b._lr and a.i_step == b.i_step == 3
+    a.close()
+    b.close()
+
+
 def test_saved_weights_predict_what_the_trainer_validated(engine, trained, tmp_path):
     trainer, data = trained["trainer"], trained["data"]
     mean, variance = trainer.predict(data["low_photon"], data["forward_projection"])
@@ -419,7 +449,7 @@ def test_saved_weights_predict_what_the_trainer_validated(engine, trained, tmp_p
 
 def test_one_update_at_full_size(engine):
     """1024 x 768, batch 1, golden architecture: a finite loss and the peak of the device memory.
-    Measured on the MI355X: peak_device_bytes 4,022,982,440 (3837 MiB); ms_forward 11.9, ms_wgrad 22.3, ms_dgrad 11.8, ms_norm 2.6,
+    Measured on the MI355X: peak_device_bytes 4,022,890,280 (3837 MiB); ms_forward 11.9, ms_wgrad 22.3, ms_dgrad 11.8, ms_norm 2.6,
     ms_optimizer 0.25, ms_total 49.6 (warm medians at the batch of 10: profiles/speedup_train.md)."""
     lp, fp = speedup_ref.seeded_inputs(4, 1, 768, 1024)
     trainer = training.MCSpeedupTrainer(seed=0)
