@@ -1,7 +1,8 @@
 // primary_project.hip -- the ray-traced primary: the expectation of the engine's `unscattered` plane, computed as a ray integral
 // (source spectrum x Beer-Lambert attenuation along the straight line focal spot -> pixel) through the piecewise-constant voxels the
 // context holds on the device, with the cross-section tables the flight step reads; and the small separable Gaussian that smooths
-// the Monte Carlo scatter beside it (mcgpu_smooth_planes).  Restated in float64 by tests/primary_ref.py.
+// the Monte Carlo scatter beside it (mcgpu_smooth_planes).  Restated in float64 by tests/primary_ref.py.  Its noise -- the moment planes of
+// the compound Poisson tally and a seeded draw from them, stated after the rule -- is restated by tests/primary_noise_ref.py.
 //
 // THE RULE, for projection p of a context (resident geometry, pose, detector, spectrum) and pixel (px, pz) of the tally image [nz][nx]:
 //  1 sub-points   The pixel is split into su x sv equal cells (1..8 each).  The centre of cell (i, j) has detector coordinates
@@ -37,6 +38,28 @@
 // Kernel shape: one lane per pixel (sub-points in sequence), a wave covers an 8x8 pixel tile, a workgroup 16x16, blockIdx.z the
 // projection.  A lane's t_m live in LDS as [m][lane] (a dynamically indexed private array would land in scratch: joseph_ray.inc), the
 // current run in registers.  W, K and the per-projection block are read at wave-uniform addresses (scalar loads).
+//
+// MOMENT PLANES (mcgpu_primary_moments).  The engine's detector is an ideal energy absorber, so the tally of a pixel is a compound
+// Poisson sum: a Poisson number of photons, each adding its energy.  For k = 0, 1, 2 the plane M_k is steps 1 - 5 with the weights
+// W_q^(k) = P_b g_j E_q^k in step 4: photons / cm^2, eV / cm^2 and eV^2 / cm^2 per history.  M_1 is the plane above; primary_kernel<VK, 3>
+// forms the three sums from one traversal, one exponent and one expf per sub-point and node (primary_kernel<VK, 1> is the kernel of
+// mcgpu_primary_project, instruction for instruction what it was before the moments existed).  Layout [projection][k][nz][crop_nx].
+// With a = the pixel area [cm^2] and N histories, N a M_0 is the expected number of photons in a pixel and M_2 / (N a) the variance
+// of the `unscattered` plane, up to the relative term a M_0 (about 1e-6) that the Poisson limit of the binomial count drops.
+//
+// THE NOISE RULE (mcgpu_primary_noisy, mcgpu_sample_compound_poisson), per pixel (x, y) = (column, row) of the plane as laid out above,
+// in double from the float32 planes:
+//  inputs   lambda = N a M_0, mu = M_1 / M_0, s2 = max(M_2 / M_0 - mu^2, 0).  A pixel whose M_0 is not > 0 gives exactly 0.
+//  draws    philox_normal.inc: key = seed, counter (x, y, first_projection + p, k).  Draw k = 0 gives u (= u1 of word 0) and z0 (the
+//           normal of words 0 and 1); draw k = 1 gives z1; draw k = 2 gives z2.
+//  count    lambda < 64: inversion by sequential search, p = exp(-lambda), F = p, n = 0; while u > F and n < 1024: n += 1,
+//           p *= lambda / n, F += p.  lambda >= 64: n = max(0, floor(lambda + sqrt(lambda) z0 + (z0^2 - 1) / 6 + 1/2)), the normal with
+//           its first skewness correction (Cornish-Fisher).
+//  value    max(0, n mu + sqrt(n s2) z1) / (N a), rounded once to float32; n = 0 gives exactly 0.
+// The mean of the rule is M_1 and its variance M_2 / (N a); shadows get true zeros and integer-count statistics.  What it is not: the
+// energy sum given n is a Gaussian of the right mean and variance, not the exact n-fold mixture of the transmitted spectrum, and
+// u and z0 share their words (a pixel uses one of the two).
+// mcgpu_sample_gaussian: max(0, mean + sqrt(max(variance, 0)) z2), rounded once to float32.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -90,8 +113,9 @@ __device__ __forceinline__ void close_run(const PrimaryVol& A, unsigned long lon
   t_lane[m * kLanes] = fmaf(pd.x, len, t_lane[m * kLanes]);
 }
 
-template <int VK>
-__global__ __launch_bounds__(kLanes) void primary_kernel(float* __restrict__ out /*[nb][nz][crop_nx]*/, const PrimaryVol A,
+// NM = 1: the plane M_1 from W [nq].  NM = 3: the planes M_0, M_1, M_2 from W = [W^(1) | W^(0) | W^(2)], nq each.
+template <int VK, int NM>
+__global__ __launch_bounds__(kLanes) void primary_kernel(float* __restrict__ out /*[nb][NM][nz][crop_nx]*/, const PrimaryVol A,
                                                          const PrimaryProj* __restrict__ proj, const double* __restrict__ W,
                                                          const double* __restrict__ K) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -108,7 +132,7 @@ __global__ __launch_bounds__(kLanes) void primary_kernel(float* __restrict__ out
   float* const t_lane = t_lds + threadIdx.x;
   const double bx = A.n[0] * A.vs[0], by = A.n[1] * A.vs[1], bz = A.n[2] * A.vs[2];
   const int max_steps = A.n[0] + A.n[1] + A.n[2] + 4;
-  double sum = 0.0;
+  double sum = 0.0, sum0 = 0.0, sum2 = 0.0;
   for (int sj = 0; sj < A.sv; ++sj) {
     for (int si = 0; si < A.su; ++si) {
       const double xd = (double)px + ((double)si + 0.5) / (double)A.su, zd = (double)pz + ((double)sj + 0.5) / (double)A.sv;
@@ -165,18 +189,99 @@ __global__ __launch_bounds__(kLanes) void primary_kernel(float* __restrict__ out
         if (have) close_run<VK>(A, run, (float)(tc - ts), pal_lds, t_lane);
       }
       // spectrum
-      double s = 0.0;
+      double s = 0.0, s0 = 0.0, s2 = 0.0;
       for (int q = 0; q < A.nq; ++q) {
         double x = 0.0;
         for (int m = 0; m < A.nmat; ++m) x = fma(K[q * A.nmat + m], (double)t_lane[m * kLanes], x);
         const float xh = (float)x, xl = (float)(x - (double)xh);
-        s = fma(W[q], (double)(expf(-xh) * (1.0f - xl)), s);
+        if (NM == 1) {
+          s = fma(W[q], (double)(expf(-xh) * (1.0f - xl)), s);
+        } else {
+          const double e = (double)(expf(-xh) * (1.0f - xl));
+          s = fma(W[q], e, s);
+          s0 = fma(W[A.nq + q], e, s0);
+          s2 = fma(W[2 * A.nq + q], e, s2);
+        }
       }
       sum += s * cospsi / r2;
+      if (NM == 3) {
+        sum0 += s0 * cospsi / r2;
+        sum2 += s2 * cospsi / r2;
+      }
     }
   }
   const double value = sum / (double)(A.su * A.sv) * P.inv_omega;
-  out[((size_t)blockIdx.z * A.nz + (size_t)(A.nz - 1 - pz)) * A.crop_nx + px] = (float)value;
+  if (NM == 1) {
+    out[((size_t)blockIdx.z * A.nz + (size_t)(A.nz - 1 - pz)) * A.crop_nx + px] = (float)value;
+  } else {
+    const size_t plane = (size_t)A.nz * A.crop_nx, at = (size_t)blockIdx.z * 3 * plane + (size_t)(A.nz - 1 - pz) * A.crop_nx + px;
+    out[at] = (float)(sum0 / (double)(A.su * A.sv) * P.inv_omega);
+    out[at + plane] = (float)value;
+    out[at + 2 * plane] = (float)(sum2 / (double)(A.su * A.sv) * P.inv_omega);
+  }
+}
+
+// ---- the samplers ---------------------------------------------------------------------------------------------------------------
+#include "philox_normal.inc"
+
+// one draw of the rule: words of counter (x, y, projection, k)
+__device__ __forceinline__ double draw_normal(int x, int y, unsigned projection, unsigned k, unsigned long long seed, double& u) {
+  unsigned w0, w1;
+  philox10((unsigned)x, (unsigned)y, projection, k, (unsigned)seed, (unsigned)(seed >> 32), w0, w1);
+  return normal_of_words(w0, w1, u);
+}
+
+// THE NOISE RULE of the header.  m0, m1, m2: planes [ny][nx] of plane blockIdx.y, `stride` floats from one plane to the next; na = N a
+__global__ __launch_bounds__(256) void compound_poisson_kernel(const float* __restrict__ m0, const float* __restrict__ m1, const float* __restrict__ m2,
+                                                               size_t stride, float* __restrict__ out, int nx, unsigned int hw, double na,
+                                                               unsigned long long seed, unsigned first_projection) {
+  const unsigned int i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= hw) return;
+  const size_t at = (size_t)blockIdx.y * stride + i;
+  const double M0 = (double)m0[at], M1 = (double)m1[at], M2 = (double)m2[at];
+  float value = 0.0f;
+  if (M0 > 0.0) {
+    const int x = (int)(i % (unsigned)nx), y = (int)(i / (unsigned)nx);
+    const unsigned projection = first_projection + blockIdx.y;
+    const double lambda = na * M0, mu = M1 / M0, s2 = fmax(M2 / M0 - mu * mu, 0.0);
+    double u;
+    const double z0 = draw_normal(x, y, projection, 0u, seed, u);
+    double n = 0.0;
+    if (lambda < 64.0) {
+      double p = exp(-lambda), F = p;
+      while (u > F && n < 1024.0) {
+        n += 1.0;
+        p *= lambda / n;
+        F += p;
+      }
+    } else {
+      n = fmax(0.0, floor(lambda + sqrt(lambda) * z0 + (z0 * z0 - 1.0) / 6.0 + 0.5));
+    }
+    if (n > 0.0) {
+      double unused;
+      const double z1 = draw_normal(x, y, projection, 1u, seed, unused);
+      value = (float)(fmax(0.0, n * mu + sqrt(n * s2) * z1) / na);
+    }
+  }
+  out[(size_t)blockIdx.y * hw + i] = value;
+}
+
+// max(0, mean + sqrt(max(variance, 0)) z2)
+__global__ __launch_bounds__(256) void gaussian_sample_kernel(const float* __restrict__ mean, const float* __restrict__ variance, float* __restrict__ out,
+                                                              int nx, unsigned int hw, unsigned long long seed, unsigned first_projection) {
+  const unsigned int i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= hw) return;
+  const size_t at = (size_t)blockIdx.y * hw + i;
+  double unused;
+  const double z2 = draw_normal((int)(i % (unsigned)nx), (int)(i / (unsigned)nx), first_projection + blockIdx.y, 2u, seed, unused);
+  out[at] = (float)fmax(0.0, (double)mean[at] + sqrt(fmax((double)variance[at], 0.0)) * z2);
+}
+
+void launch_compound_poisson(const float* m0, const float* m1, const float* m2, size_t stride, float* out, int n_planes, int ny, int nx, double na,
+                             unsigned long long seed, unsigned first_projection) {
+  const unsigned int hw = (unsigned int)ny * (unsigned int)nx;
+  hipLaunchKernelGGL(compound_poisson_kernel, dim3((hw + 255u) / 256u, (unsigned)n_planes), dim3(256), 0, nullptr, m0, m1, m2, stride, out, nx, hw, na, seed,
+                     first_projection);
 }
 
 // ---- the separable Gaussian of mcgpu_smooth_planes: scipy.ndimage.gaussian_filter, truncate 4, mode reflect ----------------
@@ -319,8 +424,8 @@ PrimaryProj primary_pose(const SourcePose& s, const DetectorPose& d) {
   return P;
 }
 
-// W[q] and K[q][compact material] of the context's spectrum and tables
-void spectrum_tables(const HostModel& H, const DeviceModel& D, int qn, std::vector<double>& W, std::vector<double>& K) {
+// W[q] and K[q][compact material] of the context's spectrum and tables; moments == 3: W = [W^(1) | W^(0) | W^(2)], W^(k)_q = P_b g_j E_q^k
+void spectrum_tables(const HostModel& H, const DeviceModel& D, int qn, int moments, std::vector<double>& W, std::vector<double>& K) {
   const Spectrum& sp = H.spectrum;
   const int nb = sp.num_bins;
   std::vector<double> prob(nb, 0.0);
@@ -338,6 +443,7 @@ void spectrum_tables(const HostModel& H, const DeviceModel& D, int qn, std::vect
     if (D.compact_of[m] >= 0 && D.compact_of[m] < D.nmat) material_of[D.compact_of[m]] = m;
   W.clear();
   K.clear();
+  std::vector<double> W0, W2;
   const double e0 = H.mat.e0, ide = H.mat.ide;
   for (int b = 0; b < nb; ++b) {
     if (!(prob[b] > 0.0)) continue;
@@ -345,6 +451,8 @@ void spectrum_tables(const HostModel& H, const DeviceModel& D, int qn, std::vect
     for (int j = 0; j < qn; ++j) {
       const double E = 0.5 * (lo + hi) + 0.5 * (hi - lo) * gx[j];
       W.push_back(prob[b] * 0.5 * gw[j] * E);
+      W0.push_back(prob[b] * 0.5 * gw[j]);
+      W2.push_back(prob[b] * 0.5 * gw[j] * E * E);
       const int bin = std::min(std::max((int)floor((E - e0) * ide), 0), H.mat.num_values - 1);
       for (int mc = 0; mc < D.nmat; ++mc) {
         const size_t row = (size_t)bin * kMaxMaterials + material_of[mc];
@@ -352,39 +460,57 @@ void spectrum_tables(const HostModel& H, const DeviceModel& D, int qn, std::vect
       }
     }
   }
+  if (moments == 3) {
+    W.insert(W.end(), W0.begin(), W0.end());
+    W.insert(W.end(), W2.begin(), W2.end());
+  }
 }
 
-template <int VK>
+template <int VK, int NM>
 void launch_primary(float* d_out, const PrimaryVol& A, const PrimaryProj* d_proj, const double* d_W, const double* d_K, int nb) {
   const size_t lds = (size_t)A.nmat * kLanes * 4 + (VK == kVolU8 ? 256 * sizeof(float2) : 0);
-  hipLaunchKernelGGL(primary_kernel<VK>, dim3((A.crop_nx + 15) / 16, (A.nz + 15) / 16, nb), dim3(kLanes), lds, nullptr, d_out, A, d_proj, d_W, d_K);
+  hipLaunchKernelGGL((primary_kernel<VK, NM>), dim3((A.crop_nx + 15) / 16, (A.nz + 15) / 16, nb), dim3(kLanes), lds, nullptr, d_out, A, d_proj, d_W, d_K);
+}
+template <int NM>
+void launch_primary_of(int vol_kind, float* d_out, const PrimaryVol& A, const PrimaryProj* d_proj, const double* d_W, const double* d_K, int nb) {
+  if (vol_kind == kVolU8) launch_primary<kVolU8, NM>(d_out, A, d_proj, d_W, d_K, nb);
+  else if (vol_kind == kVolU16) launch_primary<kVolU16, NM>(d_out, A, d_proj, d_W, d_K, nb);
+  else launch_primary<kVolRaw, NM>(d_out, A, d_proj, d_W, d_K, nb);
 }
 
-}  // namespace
+[[noreturn]] void refuse(const char* fn, const std::string& what) { throw Error(-1, std::string("!!ERROR!! ") + fn + ": " + what); }
 
-extern "C" int mcgpu_primary_project(mcgpu_ctx* ctx, const mcgpu_primary_options* caller_o, float* planes, mcgpu_primary_report* report) {
-  ABI_BEGIN
-  mcgpu_primary_options o;
-  read_options("mcgpu_primary_project", "mcgpu_primary_options", caller_o, o);
-  check_report("mcgpu_primary_project", "report", "mcgpu_primary_report", report);
-  require(ctx && ctx->has_device && planes, -1, "!!ERROR!! mcgpu_primary_project: bad argument (the context needs a device)");
+struct Noise {  // of mcgpu_primary_noisy: the moments stay on the device, the sampled plane comes back
+  double histories;
+  unsigned long long seed;
+};
+
+// The three entry points on a context: `moments` planes per projection (1: M_1, 3: M_0, M_1, M_2) to `planes`, or with `noise` the
+// sampled plane alone.  Every refusal stands before the first HIP call.
+void primary_run(const char* fn, mcgpu_ctx* ctx, const mcgpu_primary_options& o, int moments, const Noise* noise, float* planes,
+                 mcgpu_primary_report* report) {
+  check_report(fn, "report", "mcgpu_primary_report", report);
+  if (!(ctx && ctx->has_device && planes)) refuse(fn, "bad argument (the context needs a device)");
+  if (noise && !(std::isfinite(noise->histories) && noise->histories > 0.0)) refuse(fn, "histories must be finite and > 0");
   const HostModel& H = ctx->host;
   const DeviceModel& D = ctx->dev;
   const int np = (int)H.source.size();
   const int n_proj = o.n_projections > 0 ? o.n_projections : 1;
   if (o.first_projection < 0 || o.n_projections < 0 || o.first_projection + n_proj > np)
-    throw Error(-1, "!!ERROR!! mcgpu_primary_project: projections " + std::to_string(o.first_projection) + " .. " +
-                        std::to_string(o.first_projection + n_proj - 1) + " are not within the context's " + std::to_string(np));
+    refuse(fn, "projections " + std::to_string(o.first_projection) + " .. " + std::to_string(o.first_projection + n_proj - 1) +
+                   " are not within the context's " + std::to_string(np));
   const int su = o.su ? o.su : 1, sv = o.sv ? o.sv : 1, qn = o.energy_points ? o.energy_points : 2;
-  require(su >= 1 && su <= 8 && sv >= 1 && sv <= 8, -1, "!!ERROR!! mcgpu_primary_project: su and sv must be within 1 .. 8 (0: 1)");
-  require(qn >= 1 && qn <= 4, -1, "!!ERROR!! mcgpu_primary_project: energy_points must be within 1 .. 4 (0: 2)");
-  require(D.nmat >= 1 && D.nmat <= kMaxMaterials, -1, "!!ERROR!! mcgpu_primary_project: the context holds no material");
+  if (!(su >= 1 && su <= 8 && sv >= 1 && sv <= 8)) refuse(fn, "su and sv must be within 1 .. 8 (0: 1)");
+  if (!(qn >= 1 && qn <= 4)) refuse(fn, "energy_points must be within 1 .. 4 (0: 2)");
+  if (!(D.nmat >= 1 && D.nmat <= kMaxMaterials)) refuse(fn, "the context holds no material");
   const DetectorPose& d0 = H.detector[o.first_projection];
   const int nx = d0.nx, nz = d0.nz, crop = (o.crop_nx > 0 && o.crop_nx < nx) ? o.crop_nx : nx;
+  const double na = noise ? noise->histories / ((double)d0.inv_pixel_size_X * (double)d0.inv_pixel_size_Z) : 0.0;  // N a
+  if (noise && !(std::isfinite(na) && na > 0.0)) refuse(fn, "the pixel area of the context's detector is not positive");
 
   const Stopwatch clock;
   std::vector<double> W, K;
-  spectrum_tables(H, D, qn, W, K);
+  spectrum_tables(H, D, qn, moments, W, K);
   std::vector<PrimaryProj> poses(n_proj);
   for (int k = 0; k < n_proj; ++k) poses[k] = primary_pose(H.source[o.first_projection + k], H.detector[o.first_projection + k]);
   double ms_tables = clock.ms();
@@ -403,29 +529,116 @@ extern "C" int mcgpu_primary_project(mcgpu_ctx* ctx, const mcgpu_primary_options
   for (int k = 0; k < 3; ++k) { A.n[k] = H.voxels.n[k]; A.vs[k] = H.voxels.voxel_size[k]; }
   A.sub_nx = (unsigned)((A.n[0] + 3) >> 2);
   A.sub_nxy = A.sub_nx * (unsigned)((A.n[1] + 3) >> 2);
-  A.nx = nx; A.nz = nz; A.crop_nx = crop; A.su = su; A.sv = sv; A.nq = (int)W.size(); A.nmat = D.nmat;
-  require(D.vol_kind != kVolU8 || D.palette_size <= 256, -1, "!!ERROR!! mcgpu_primary_project: a u8 volume with more than 256 palette entries");
+  A.nx = nx; A.nz = nz; A.crop_nx = crop; A.su = su; A.sv = sv; A.nq = (int)W.size() / moments; A.nmat = D.nmat;
+  if (!(D.vol_kind != kVolU8 || D.palette_size <= 256)) refuse(fn, "a u8 volume with more than 256 palette entries");
   const size_t plane = (size_t)crop * nz;
   const int chunk = std::min(n_proj, kChunk);
-  float* d_out = dev.alloc_zeroed<float>((size_t)chunk * plane * 4);
+  float* d_out = dev.alloc_zeroed<float>((size_t)chunk * moments * plane * 4);
+  float* d_noisy = noise ? dev.alloc_zeroed<float>((size_t)chunk * plane * 4) : nullptr;
   dev.events();
-  double ms_kernel = 0.0;
+  double ms_kernel = 0.0, ms_sample = 0.0;
   for (int first = 0; first < n_proj; first += chunk) {
     const int m = std::min(chunk, n_proj - first);
     Stage st(dev, ms_kernel);
-    if (D.vol_kind == kVolU8) launch_primary<kVolU8>(d_out, A, d_proj + first, d_W, d_K, m);
-    else if (D.vol_kind == kVolU16) launch_primary<kVolU16>(d_out, A, d_proj + first, d_W, d_K, m);
-    else launch_primary<kVolRaw>(d_out, A, d_proj + first, d_W, d_K, m);
+    if (moments == 3) launch_primary_of<3>(D.vol_kind, d_out, A, d_proj + first, d_W, d_K, m);
+    else launch_primary_of<1>(D.vol_kind, d_out, A, d_proj + first, d_W, d_K, m);
     st.done();
-    HIP_TRY(hipMemcpy(planes + (size_t)first * plane, d_out, (size_t)m * plane * 4, hipMemcpyDeviceToHost));
+    if (noise) {
+      Stage sample(dev, ms_sample);
+      launch_compound_poisson(d_out, d_out + plane, d_out + 2 * plane, 3 * plane, d_noisy, m, nz, crop, na, noise->seed, (unsigned)(o.first_projection + first));
+      sample.done();
+      HIP_TRY(hipMemcpy(planes + (size_t)first * plane, d_noisy, (size_t)m * plane * 4, hipMemcpyDeviceToHost));
+    } else {
+      HIP_TRY(hipMemcpy(planes + (size_t)first * moments * plane, d_out, (size_t)m * moments * plane * 4, hipMemcpyDeviceToHost));
+    }
   }
   mcgpu_primary_report r{};
   r.ms_kernel = ms_kernel;
   r.ms_tables = ms_tables;
   r.solid_angle = 1.0 / poses[0].inv_omega;
   r.n_materials = D.nmat;
-  r.n_energy_points = (int)W.size();
+  r.n_energy_points = A.nq;
+  r.ms_sample = ms_sample;
   write_report(report, r);
+}
+
+// what the two samplers on host planes refuse
+void check_sampler(const char* fn, bool pointers, int n_planes, int ny, int nx, int first_projection) {
+  if (!pointers) refuse(fn, "a plane pointer is NULL");
+  if (!(n_planes >= 1 && n_planes <= 65535 && ny >= 1 && nx >= 1 && (unsigned long long)ny * (unsigned long long)nx <= 0x7fffffffull))
+    refuse(fn, "n_planes must be within 1 .. 65535, ny and nx >= 1 and ny x nx below 2^31");
+  if (first_projection < 0 || (long long)first_projection + n_planes > 0x7fffffffLL) refuse(fn, "first_projection must be >= 0");
+}
+
+}  // namespace
+
+extern "C" int mcgpu_primary_project(mcgpu_ctx* ctx, const mcgpu_primary_options* caller_o, float* planes, mcgpu_primary_report* report) {
+  ABI_BEGIN
+  mcgpu_primary_options o;
+  read_options("mcgpu_primary_project", "mcgpu_primary_options", caller_o, o);
+  primary_run("mcgpu_primary_project", ctx, o, 1, nullptr, planes, report);
+  return 0;
+  ABI_END
+}
+
+extern "C" int mcgpu_primary_moments(mcgpu_ctx* ctx, const mcgpu_primary_options* caller_o, float* planes, mcgpu_primary_report* report) {
+  ABI_BEGIN
+  mcgpu_primary_options o;
+  read_options("mcgpu_primary_moments", "mcgpu_primary_options", caller_o, o);
+  primary_run("mcgpu_primary_moments", ctx, o, 3, nullptr, planes, report);
+  return 0;
+  ABI_END
+}
+
+extern "C" int mcgpu_primary_noisy(mcgpu_ctx* ctx, const mcgpu_primary_noisy_options* caller_o, float* planes, mcgpu_primary_report* report) {
+  ABI_BEGIN
+  mcgpu_primary_noisy_options n;
+  read_options("mcgpu_primary_noisy", "mcgpu_primary_noisy_options", caller_o, n);
+  mcgpu_primary_options o{};
+  o.struct_size = (unsigned int)sizeof o;
+  o.first_projection = n.first_projection; o.n_projections = n.n_projections; o.su = n.su; o.sv = n.sv;
+  o.energy_points = n.energy_points; o.crop_nx = n.crop_nx;
+  const Noise noise{n.histories, n.seed};
+  primary_run("mcgpu_primary_noisy", ctx, o, 3, &noise, planes, report);
+  return 0;
+  ABI_END
+}
+
+extern "C" int mcgpu_sample_compound_poisson(int device, const float* m0, const float* m1, const float* m2, float* out, int n_planes, int ny, int nx,
+                                             double histories, double pixel_area, unsigned long long seed, int first_projection) {
+  ABI_BEGIN
+  const char* fn = "mcgpu_sample_compound_poisson";
+  check_sampler(fn, m0 && m1 && m2 && out, n_planes, ny, nx, first_projection);
+  if (!(std::isfinite(histories) && histories > 0.0)) refuse(fn, "histories must be finite and > 0");
+  const double na = histories * pixel_area;
+  if (!(std::isfinite(pixel_area) && pixel_area > 0.0 && std::isfinite(na) && na > 0.0)) refuse(fn, "pixel_area must be finite and > 0");
+  const size_t n = (size_t)n_planes * ny * nx;
+  HIP_TRY(hipSetDevice(device));
+  CallDevice dev;
+  const float *d0 = dev.upload(m0, n), *d1 = dev.upload(m1, n), *d2 = dev.upload(m2, n);
+  float* d_out = dev.alloc<float>(n * 4);
+  launch_compound_poisson(d0, d1, d2, (size_t)ny * nx, d_out, n_planes, ny, nx, na, seed, (unsigned)first_projection);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, d_out, n * 4, hipMemcpyDeviceToHost));
+  return 0;
+  ABI_END
+}
+
+extern "C" int mcgpu_sample_gaussian(int device, const float* mean, const float* variance, float* out, int n_planes, int ny, int nx,
+                                     unsigned long long seed, int first_projection) {
+  ABI_BEGIN
+  const char* fn = "mcgpu_sample_gaussian";
+  check_sampler(fn, mean && variance && out, n_planes, ny, nx, first_projection);
+  const size_t n = (size_t)n_planes * ny * nx;
+  HIP_TRY(hipSetDevice(device));
+  CallDevice dev;
+  const float *d_mean = dev.upload(mean, n), *d_var = dev.upload(variance, n);
+  float* d_out = dev.alloc<float>(n * 4);
+  const unsigned int hw = (unsigned int)ny * (unsigned int)nx;
+  hipLaunchKernelGGL(gaussian_sample_kernel, dim3((hw + 255u) / 256u, (unsigned)n_planes), dim3(256), 0, nullptr, d_mean, d_var, d_out, nx, hw, seed,
+                     (unsigned)first_projection);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, d_out, n * 4, hipMemcpyDeviceToHost));
   return 0;
   ABI_END
 }

@@ -48,29 +48,7 @@ constexpr int kTaps = 9;  // 3 x 3: what unet_common.inc sizes a K chunk and cou
 #include "unet_common.inc"
 #include "speedup_conv.inc"  // the convolution, the small kernels of the forward pass and their launches: shared with speedup_train.hip
 
-// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3"): words 0 and 1 of the block
-__device__ void philox10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned& w0, unsigned& w1) {
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (unsigned)p1;
-    c3 = (unsigned)p0;
-    c0 = n0;
-    c2 = n2;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  w0 = c0;
-  w1 = c1;
-}
-
-__device__ float standard_normal(int x, int y, unsigned projection, unsigned long long seed) {
-  unsigned w0, w1;
-  philox10((unsigned)x, (unsigned)y, projection, 0u, (unsigned)seed, (unsigned)(seed >> 32), w0, w1);
-  const float u1 = (float)((w0 >> 8) + 1u) * 0x1p-24f, u2 = (float)(w1 >> 8) * 0x1p-24f;  // u1 in (0, 1], u2 in [0, 1)
-  return sqrtf(-2.f * logf(u1)) * cospif(2.f * u2);
-}
+#include "philox_normal.inc"  // philox10, standard_normal: shared with the samplers of primary_project.hip
 
 // sample = mean + sqrt(variance) z; with mean == nullptr: z alone
 __global__ __launch_bounds__(256) void sample_kernel(const float* mean, const float* variance, float* out, int W, size_t hw, unsigned projection,

@@ -31,7 +31,7 @@ ABI_SYMBOLS = (
     "mcgpu_warp_volume", "mcgpu_warp_geometry", "mcgpu_map_image", "mcgpu_set_geometry_image",
     "mcgpu_resample_plan", "mcgpu_resample_volume", "mcgpu_set_geometry_image_resampled",
     "mcgpu_correspondence_set", "mcgpu_correspondence_fit", "mcgpu_correspondence_predict", "mcgpu_warp_geometry_signal", "mcgpu_correspondence_clear",
-    "mcgpu_write_voxel_file", "mcgpu_write_voxel_binary", "mcgpu_kat_rng", "mcgpu_kat_rng_streams", "mcgpu_microbench", "mcgpu_kat_math", "mcgpu_kat_expf", "mcgpu_kat_f32", "mcgpu_kat_fast64", "mcgpu_kat_scatter", "mcgpu_kat_history", "mcgpu_kat_flight", "mcgpu_kat_tile_records", "mcgpu_fdk_reconstruct", "mcgpu_fdk_reconstruct_motion", "mcgpu_wpc_fit", "mcgpu_forward_project", "mcgpu_forward_project_context", "mcgpu_primary_project", "mcgpu_smooth_planes", "mcgpu_rooster4d_reconstruct", "mcgpu_rooster4d_stage", "mcgpu_rooster4d_reconstruct_motion", "mcgpu_rooster4d_motion_stage", "mcgpu_register", "mcgpu_register_stage", "mcgpu_speedup_run", "mcgpu_speedup_stage", "mcgpu_speedup_train_create", "mcgpu_speedup_train_step", "mcgpu_speedup_train_gradients", "mcgpu_speedup_train_predict", "mcgpu_speedup_train_get_state", "mcgpu_speedup_train_set_state", "mcgpu_speedup_train_destroy", "mcgpu_speedup_train_stage", "mcgpu_segment_run", "mcgpu_segment_stage", "mcgpu_segment_train_create", "mcgpu_segment_train_step", "mcgpu_segment_train_gradients", "mcgpu_segment_train_predict", "mcgpu_segment_train_get_state", "mcgpu_segment_train_set_state", "mcgpu_segment_train_destroy", "mcgpu_segment_train_stage", "mcgpu_set_fast_schedule", "mcgpu_reload_env_knobs",
+    "mcgpu_write_voxel_file", "mcgpu_write_voxel_binary", "mcgpu_kat_rng", "mcgpu_kat_rng_streams", "mcgpu_microbench", "mcgpu_kat_math", "mcgpu_kat_expf", "mcgpu_kat_f32", "mcgpu_kat_fast64", "mcgpu_kat_scatter", "mcgpu_kat_history", "mcgpu_kat_flight", "mcgpu_kat_tile_records", "mcgpu_fdk_reconstruct", "mcgpu_fdk_reconstruct_motion", "mcgpu_wpc_fit", "mcgpu_forward_project", "mcgpu_forward_project_context", "mcgpu_primary_project", "mcgpu_smooth_planes", "mcgpu_primary_moments", "mcgpu_primary_noisy", "mcgpu_sample_compound_poisson", "mcgpu_sample_gaussian", "mcgpu_rooster4d_reconstruct", "mcgpu_rooster4d_stage", "mcgpu_rooster4d_reconstruct_motion", "mcgpu_rooster4d_motion_stage", "mcgpu_register", "mcgpu_register_stage", "mcgpu_speedup_run", "mcgpu_speedup_stage", "mcgpu_speedup_train_create", "mcgpu_speedup_train_step", "mcgpu_speedup_train_gradients", "mcgpu_speedup_train_predict", "mcgpu_speedup_train_get_state", "mcgpu_speedup_train_set_state", "mcgpu_speedup_train_destroy", "mcgpu_speedup_train_stage", "mcgpu_segment_run", "mcgpu_segment_stage", "mcgpu_segment_train_create", "mcgpu_segment_train_step", "mcgpu_segment_train_gradients", "mcgpu_segment_train_predict", "mcgpu_segment_train_get_state", "mcgpu_segment_train_set_state", "mcgpu_segment_train_destroy", "mcgpu_segment_train_stage", "mcgpu_set_fast_schedule", "mcgpu_reload_env_knobs",
     "mcgpu_exchange_shared_bytes", "mcgpu_exchange_card_bytes", "mcgpu_exchange_create", "mcgpu_exchange_card", "mcgpu_exchange_connect",
     "mcgpu_exchange_connect_local", "mcgpu_exchange_probe", "mcgpu_exchange_owner", "mcgpu_exchange_begin", "mcgpu_exchange_submit", "mcgpu_exchange_collect",
     "mcgpu_exchange_stats", "mcgpu_exchange_destroy", "mcgpu_copy_to_host",
@@ -97,7 +97,13 @@ class PrimaryOptions(C.Structure):
 class PrimaryReport(C.Structure):
     """mcgpu_primary_report (include/mcgpu_amd.h)."""
     _fields_ = [("struct_size", C.c_uint), ("n_materials", C.c_int), ("ms_kernel", C.c_double), ("ms_tables", C.c_double),
-                ("solid_angle", C.c_double), ("n_energy_points", C.c_int), ("reserved", C.c_int)]
+                ("solid_angle", C.c_double), ("n_energy_points", C.c_int), ("reserved", C.c_int), ("ms_sample", C.c_double)]
+
+
+class PrimaryNoisyOptions(C.Structure):
+    """mcgpu_primary_noisy_options (include/mcgpu_amd.h)."""
+    _fields_ = [("struct_size", C.c_uint), ("first_projection", C.c_int), ("n_projections", C.c_int), ("su", C.c_int), ("sv", C.c_int),
+                ("energy_points", C.c_int), ("crop_nx", C.c_int), ("reserved", C.c_int), ("histories", C.c_double), ("seed", C.c_ulonglong)]
 
 
 def knob_table():
@@ -227,6 +233,10 @@ def load_library(path: Optional[os.PathLike] = None):
     lib.mcgpu_kat_tile_records.argtypes = [ci, vp, vp]
     lib.mcgpu_primary_project.argtypes = [vp, C.POINTER(PrimaryOptions), vp, C.POINTER(PrimaryReport)]
     lib.mcgpu_smooth_planes.argtypes = [ci, vp, vp, ci, ci, ci, C.c_double, C.c_double, C.POINTER(C.c_double)]
+    lib.mcgpu_primary_moments.argtypes = [vp, C.POINTER(PrimaryOptions), vp, C.POINTER(PrimaryReport)]
+    lib.mcgpu_primary_noisy.argtypes = [vp, C.POINTER(PrimaryNoisyOptions), vp, C.POINTER(PrimaryReport)]
+    lib.mcgpu_sample_compound_poisson.argtypes = [ci, vp, vp, vp, vp, ci, ci, ci, C.c_double, C.c_double, C.c_ulonglong, ci]
+    lib.mcgpu_sample_gaussian.argtypes = [ci, vp, vp, vp, ci, ci, ci, C.c_ulonglong, ci]
     if path is None:
         _lib = lib
     return lib
@@ -383,6 +393,36 @@ def smooth_planes(planes: np.ndarray, sigma=(10.0, 10.0), device: int = 0) -> np
     out = np.empty_like(a)
     ny, nx = a.shape[-2:]
     _check(load_library().mcgpu_smooth_planes(int(device), a.ctypes.data, out.ctypes.data, int(a.size // (ny * nx)), int(ny), int(nx), sy, sx, None))
+    return out
+
+
+def _sampler_planes(*planes):
+    """float32 C-contiguous copies of planes [..., ny, nx] of one shape, and (n_planes, ny, nx)."""
+    a = [np.ascontiguousarray(p, dtype=np.float32) for p in planes]
+    if a[0].ndim < 2 or any(p.shape != a[0].shape for p in a):
+        raise ValueError("planes of one shape with at least two dimensions are needed")
+    ny, nx = a[0].shape[-2:]
+    return a, (int(a[0].size // (ny * nx)), int(ny), int(nx))
+
+
+def sample_compound_poisson(m0, m1, m2, histories: float, pixel_area: float, seed: int, first_projection: int = 0, device: int = 0) -> np.ndarray:
+    """THE NOISE RULE of csrc/primary_project.hip on moment planes a caller brings (float32 [..., ny, nx]: photons, eV and eV^2 per
+    cm^2 and history): a plane with the mean m1 and the variance m2 / (histories x pixel_area), sampled on the device
+    (mcgpu_sample_compound_poisson).  pixel_area in cm^2; plane p draws with the counter (x, y, first_projection + p, k)."""
+    (a0, a1, a2), (n, ny, nx) = _sampler_planes(m0, m1, m2)
+    out = np.empty_like(a0)
+    _check(load_library().mcgpu_sample_compound_poisson(int(device), a0.ctypes.data, a1.ctypes.data, a2.ctypes.data, out.ctypes.data, n, ny, nx,
+                                                        float(histories), float(pixel_area), int(seed) & (2 ** 64 - 1), int(first_projection)))
+    return out
+
+
+def sample_gaussian(mean, variance, seed: int, first_projection: int = 0, device: int = 0) -> np.ndarray:
+    """max(0, mean + sqrt(max(variance, 0)) z) of float32 planes [..., ny, nx] on the device (mcgpu_sample_gaussian), z the normal of
+    draw k = 2 of the noise rule at (x, y, first_projection + p)."""
+    (a, v), (n, ny, nx) = _sampler_planes(mean, variance)
+    out = np.empty_like(a)
+    _check(load_library().mcgpu_sample_gaussian(int(device), a.ctypes.data, v.ctypes.data, out.ctypes.data, n, ny, nx, int(seed) & (2 ** 64 - 1),
+                                                int(first_projection)))
     return out
 
 
@@ -693,6 +733,56 @@ class Context:
     def primary_projection(self, p: int, subsamples=(1, 1), energy_points: int = 2, crop_nx: int = 0):
         """primary_scan of the one projection p: (float32 [nz, crop_nx or nx], report dict)."""
         out, report = self.primary_scan(p, 1, subsamples, energy_points, crop_nx)
+        return out[0], report
+
+    # -- its noise: moment planes and a seeded draw (csrc/primary_project.hip: MOMENT PLANES, THE NOISE RULE)
+    @property
+    def pixel_area(self) -> float:
+        """Area of a detector pixel [cm^2]: the `a` of the noise rule."""
+        return 1.0 / (self.getf("inv_pixel_size_x") * self.getf("inv_pixel_size_z"))
+
+    def primary_moments_scan(self, first_projection: int = 0, n_projections: Optional[int] = None, subsamples=(1, 1), energy_points: int = 2,
+                             crop_nx: int = 0):
+        """The moment planes M_0, M_1, M_2 of the `unscattered` plane (photons, eV, eV^2 per cm^2 and history) of projections
+        first_projection .. + n_projections - 1, from one traversal: (float32 [n_projections, 3, nz, crop_nx or nx], report dict).
+        Plane 1 is primary_scan's, bit for bit.  Arguments as primary_scan."""
+        n = self.num_projections - int(first_projection) if n_projections is None else int(n_projections)
+        nz, nx = self.detector_shape
+        cx = crop_nx if 0 < crop_nx < nx else nx
+        o = PrimaryOptions(C.sizeof(PrimaryOptions), int(first_projection), n, int(subsamples[0]), int(subsamples[1]), int(energy_points), int(crop_nx))
+        r = PrimaryReport(C.sizeof(PrimaryReport))
+        out = np.zeros((max(n, 1), 3, nz, cx), dtype=np.float32)
+        _check(self.lib.mcgpu_primary_moments(self.h, C.byref(o), out.ctypes.data, C.byref(r)))
+        return out, {"ms_kernel": r.ms_kernel, "ms_tables": r.ms_tables, "solid_angle": r.solid_angle, "n_materials": r.n_materials,
+                     "n_energy_points": r.n_energy_points}
+
+    def primary_moments(self, p: int, subsamples=(1, 1), energy_points: int = 2, crop_nx: int = 0):
+        """primary_moments_scan of the one projection p: (float32 [3, nz, crop_nx or nx], report dict)."""
+        out, report = self.primary_moments_scan(p, 1, subsamples, energy_points, crop_nx)
+        return out[0], report
+
+    def primary_noisy_scan(self, histories: float, seed: Optional[int] = None, first_projection: int = 0, n_projections: Optional[int] = None,
+                           subsamples=(1, 1), energy_points: int = 2, crop_nx: int = 0):
+        """The `unscattered` plane of those projections with the mean and the variance that `histories` histories would give it:
+        the moments and the compound Poisson sampler run on the device, only the sampled planes come back: (float32 [n_projections,
+        nz, crop_nx or nx], report dict with the `seed` used).  A function of (seed, projection, pixel): the same seed gives the same
+        bytes and a scan made in two calls equals one call.  seed=None draws one from os.urandom."""
+        if seed is None:
+            seed = int.from_bytes(os.urandom(8), "little")
+        n = self.num_projections - int(first_projection) if n_projections is None else int(n_projections)
+        nz, nx = self.detector_shape
+        cx = crop_nx if 0 < crop_nx < nx else nx
+        o = PrimaryNoisyOptions(C.sizeof(PrimaryNoisyOptions), int(first_projection), n, int(subsamples[0]), int(subsamples[1]), int(energy_points),
+                                int(crop_nx), 0, float(histories), int(seed) & (2 ** 64 - 1))
+        r = PrimaryReport(C.sizeof(PrimaryReport))
+        out = np.zeros((max(n, 1), nz, cx), dtype=np.float32)
+        _check(self.lib.mcgpu_primary_noisy(self.h, C.byref(o), out.ctypes.data, C.byref(r)))
+        return out, {"ms_kernel": r.ms_kernel, "ms_tables": r.ms_tables, "ms_sample": r.ms_sample, "solid_angle": r.solid_angle,
+                     "n_materials": r.n_materials, "n_energy_points": r.n_energy_points, "seed": int(seed)}
+
+    def primary_noisy_projection(self, p: int, histories: float, seed: Optional[int] = None, subsamples=(1, 1), energy_points: int = 2, crop_nx: int = 0):
+        """primary_noisy_scan of the one projection p: (float32 [nz, crop_nx or nx], report dict)."""
+        out, report = self.primary_noisy_scan(histories, seed, p, 1, subsamples, energy_points, crop_nx)
         return out[0], report
 
     # -- 4-D: several (geometry, projection angles) jobs on one resident context (cbctmc/mc/simulation.py:527-710)

@@ -212,7 +212,8 @@ class MCSimulation:
     def run_simulation(self, output_folder, engine, gpu_ids=(0,), mode="fast", run_air_simulation=False,
                        air_projection_denoise_kernel_size=(10, 10), clean=True, stack_projections=True, force_rerun=False,
                        air_n_histories=int(5e10), forward_projection=False, variance=False, analytic_primary=False, scatter_sigma=(10, 10),
-                       primary_subsamples=(1, 1), primary_energy_points=2, **prepare_kwargs):
+                       primary_subsamples=(1, 1), primary_energy_points=2, hybrid_noise_histories=None, hybrid_noise_seed=None,
+                       **prepare_kwargs):
         """`BaseMCSimulation.run_simulation` (sim.py:370-427) on the in-process engine: the docker/mpirun launch and the
         ASCII -> numpy -> SimpleITK post-processing are replaced by the engine's scan pipeline, which writes
         projections_{total,unscattered,scattered}.mha (and projections_total_normalized.mha with an air scan) directly.
@@ -220,10 +221,20 @@ class MCSimulation:
         geometry.xml and density_fp.mha into `output_folder` (write_forward_projection).  `variance=True` (with
         `stack_projections`) also writes projections_{total,unscattered,scattered}_variance.mha: the per-pixel variance of the stacks,
         tallied in the same run.  `analytic_primary=True` (with `stack_projections`) also writes the hybrid products after the scan
-        (write_hybrid_products): the ray-traced primary, the smoothed Monte Carlo scatter and their sum.  Returns the scan report."""
+        (write_hybrid_products): the ray-traced primary, the smoothed Monte Carlo scatter and their sum.
+        `hybrid_noise_histories=N` (with `analytic_primary` and `variance`) also writes their noisy forms (write_noisy_hybrid_products):
+        hybrid projections with the quantum noise of N histories, drawn with `hybrid_noise_seed` (None: from os.urandom).  Returns the
+        scan report."""
         output_folder = Path(output_folder)
         if analytic_primary and not stack_projections:
             raise ValueError("The hybrid products are made of the projection stacks: analytic_primary needs stack_projections")
+        if hybrid_noise_histories is not None:
+            if not analytic_primary:
+                raise ValueError("hybrid_noise_histories gives the hybrid products their noise: it needs analytic_primary")
+            if not variance:
+                raise ValueError("The noise of the smoothed scatter comes from projections_scattered_variance.mha: hybrid_noise_histories needs variance=True")
+            if not float(hybrid_noise_histories) > 0:
+                raise ValueError("hybrid_noise_histories must be > 0")
         if forward_projection:
             self.write_forward_projection(output_folder, engine, gpu_id=gpu_ids if isinstance(gpu_ids, int) else gpu_ids[0])
         if self._already_simulated(output_folder) and not force_rerun:
@@ -251,6 +262,13 @@ class MCSimulation:
                 self.write_hybrid_products(ctx, engine, output_folder, crop_nx=half_fan, scatter_sigma=scatter_sigma, air_stack=air_stack,
                                            air_sigma=air_projection_denoise_kernel_size, subsamples=primary_subsamples,
                                            energy_points=primary_energy_points)
+                if hybrid_noise_histories is not None:
+                    used = self.write_noisy_hybrid_products(ctx, engine, output_folder, float(hybrid_noise_histories), hybrid_noise_seed,
+                                                            scan_histories=self.n_histories, crop_nx=half_fan, scatter_sigma=scatter_sigma,
+                                                            air_stack=air_stack, air_sigma=air_projection_denoise_kernel_size,
+                                                     subsamples=primary_subsamples, energy_points=primary_energy_points)
+                    if isinstance(report, dict):
+                        report["hybrid_noise_seed"] = used
             return report
         finally:
             ctx.close()
@@ -282,6 +300,43 @@ class MCSimulation:
         if air_stack is not None:
             engine.normalize_stack(output_folder / "projections_total_hybrid.mha", air_stack, output_folder / "projections_total_hybrid_normalized.mha",
                                    sigma=air_sigma, spacing=MCSimulation.STACK_PIXEL_SPACING)
+
+    @staticmethod
+    def write_noisy_hybrid_products(ctx, engine, output_folder, histories, seed=None, scan_histories=None, crop_nx=0, scatter_sigma=(10, 10),
+                                    air_stack=None, air_sigma=(10, 10), subsamples=(1, 1), energy_points=2):
+        """The hybrid products with the quantum noise of `histories` histories, beside those of write_hybrid_products (which must have
+        run: projections_scattered_smoothed.mha is read back) and the variance stacks of the scan:
+          projections_unscattered_analytic_noisy.mha   Context.primary_noisy_scan: the compound Poisson draw of the ray-traced moments
+          projections_scattered_smoothed_noisy.mha     engine.sample_gaussian of the smoothed scatter; its variance is
+                                                       projections_scattered_variance.mha smoothed with the same sigma, times
+                                                       scan_histories / histories
+          projections_total_hybrid_noisy.mha           their sum in float32
+          projections_total_hybrid_noisy_normalized.mha  with an air scan
+        One seed serves both draws (they take different draw numbers of the same counter).  Returns the seed used."""
+        import os
+        output_folder = Path(output_folder)
+        if seed is None:
+            seed = int.from_bytes(os.urandom(8), "little")
+        noisy, _ = ctx.primary_noisy_scan(histories, seed, 0, None, subsamples=subsamples, energy_points=energy_points, crop_nx=crop_nx)
+        smoothed = engine.stack_read(output_folder / "projections_scattered_smoothed.mha")
+        variance = engine.stack_read(output_folder / "projections_scattered_variance.mha")
+        if not (smoothed.shape == variance.shape == noisy.shape):
+            raise ValueError(f"the scatter stacks hold {smoothed.shape} and {variance.shape}, the noisy primary {noisy.shape}")
+        import numpy as np
+        scale = np.float32(float(scan_histories) / float(histories))
+        scatter = engine.sample_gaussian(smoothed, engine.smooth_planes(variance, scatter_sigma, device=ctx.device) * scale, seed, device=ctx.device)
+        total = noisy + scatter
+        n, nz, cx = noisy.shape
+        for name, stack in (("unscattered_analytic_noisy", noisy), ("scattered_smoothed_noisy", scatter), ("total_hybrid_noisy", total)):
+            w = engine.StackWriter(output_folder / f"projections_{name}.mha", cx, nz, n, MCSimulation.STACK_PIXEL_SPACING)
+            for plane in stack:
+                w.append(plane)
+            w.finish(replace_zeros=False)
+        if air_stack is not None:
+            engine.normalize_stack(output_folder / "projections_total_hybrid_noisy.mha", air_stack,
+                                   output_folder / "projections_total_hybrid_noisy_normalized.mha", sigma=air_sigma,
+                                   spacing=MCSimulation.STACK_PIXEL_SPACING)
+        return int(seed)
 
     @staticmethod
     def postprocess_simulation(folder, engine, n_detector_pixels=DEFAULTS.n_detector_pixels,
@@ -389,15 +444,23 @@ class MCSimulation4D:
                        run_air_simulation=False, air_projection_denoise_kernel_size=(10, 10), air_n_histories=int(5e10), start_angle=270.0,
                        force_rerun=False, forward_projection=False, fp_detector_size=DEFAULTS.n_detector_pixels_half_fan,
                        fp_detector_pixel_spacing=DEFAULTS.detector_pixel_size, analytic_primary=False, primary_subsamples=(1, 1),
-                       primary_energy_points=2):
+                       primary_energy_points=2, hybrid_noise_histories=None, hybrid_noise_seed=None):
         """`analytic_primary=True`: also projections_unscattered_analytic.mha, one slice per projection: the ray-traced primary
         (Context.primary_scan) of that projection's warped geometry and pose, computed right after the state is applied.
+        `hybrid_noise_histories=N` (with `analytic_primary`): also projections_unscattered_analytic_noisy.mha, that slice with the quantum
+        noise of N histories: the moment planes of the state (Context.primary_moments_scan, whose plane 1 is the analytic slice) through
+        engine.sample_compound_poisson with the slice's number in the scan as the projection of the counter, so that no two slices share
+        their draws; `hybrid_noise_seed=None` draws the seed from os.urandom.  Nothing is written for the scatter here.
         `forward_projection=True`: also density_fp_4d.mha (scripts/run_mc_simulations.py:491-556), one slice per projection:
         the Joseph forward projection of that projection's warped geometry at FP angle = MC angle - 180 degrees, projected from
         the resident context right after the state is applied (the warped volume never leaves the device)."""
         import numpy as np
         from .respiratory import RespiratorySignal
         output_folder = Path(output_folder)
+        if hybrid_noise_histories is not None and not analytic_primary:
+            raise ValueError("hybrid_noise_histories gives the analytic slices their noise: it needs analytic_primary")
+        if hybrid_noise_histories is not None and not float(hybrid_noise_histories) > 0:
+            raise ValueError("hybrid_noise_histories must be > 0")
         if MCSimulation._already_simulated(output_folder) and not force_rerun:
             return None
         output_folder.mkdir(parents=True, exist_ok=True)
@@ -437,6 +500,12 @@ class MCSimulation4D:
         primary_stack = None
         if analytic_primary:
             primary_stack = engine.StackWriter(output_folder / "projections_unscattered_analytic.mha", cx, nz_det, n_proj, MCSimulation.STACK_PIXEL_SPACING)
+        noisy_stack = None
+        if hybrid_noise_histories is not None:
+            import os
+            noise_seed = int.from_bytes(os.urandom(8), "little") if hybrid_noise_seed is None else int(hybrid_noise_seed)
+            noisy_stack = engine.StackWriter(output_folder / "projections_unscattered_analytic_noisy.mha", cx, nz_det, n_proj,
+                                             MCSimulation.STACK_PIXEL_SPACING)
         ctx = engine.create(str(input_filepath), device=gpu_ids[0])
         try:
             for (s, ds), indices in unique.items():
@@ -449,7 +518,14 @@ class MCSimulation4D:
                         fp_stack.write_slice(i, plane)
                 angles = [start_angle + i * self.angle_between_projections for i in indices]
                 ctx.set_projection_angles(angles[0:1] + angles)  # pose 0 is the input file's: skipped below (sim.py:658-660)
-                if primary_stack is not None:
+                if noisy_stack is not None:
+                    moments, _ = ctx.primary_moments_scan(1, len(angles), subsamples=primary_subsamples, energy_points=primary_energy_points,
+                                                          crop_nx=half_fan)
+                    for i, m in zip(indices, moments):
+                        primary_stack.write_slice(i, m[1])
+                        noisy_stack.write_slice(i, engine.sample_compound_poisson(m[0], m[1], m[2], float(hybrid_noise_histories), ctx.pixel_area,
+                                                                                  noise_seed, first_projection=int(i), device=ctx.device))
+                elif primary_stack is not None:
                     planes, _ = ctx.primary_scan(1, len(angles), subsamples=primary_subsamples, energy_points=primary_energy_points, crop_nx=half_fan)
                     for i, plane in zip(indices, planes):
                         primary_stack.write_slice(i, plane)
@@ -465,10 +541,15 @@ class MCSimulation4D:
             fp_stack.finish(replace_zeros=False)
         if primary_stack is not None:
             primary_stack.finish(replace_zeros=False)
+        if noisy_stack is not None:
+            noisy_stack.finish(replace_zeros=False)
         if air_stack is not None:
             engine.normalize_stack(output_folder / "projections_total.mha", air_stack, output_folder / "projections_total_normalized.mha",
                                    sigma=air_projection_denoise_kernel_size, spacing=MCSimulation.STACK_PIXEL_SPACING)
         import yaml
         with open(output_folder / "projection_geometries.yaml", "wt") as f:
             yaml.dump(dict(sorted(geometries.items())), f)
-        return {"unique_states": len(unique), "projections": n_proj}
+        report = {"unique_states": len(unique), "projections": n_proj}
+        if noisy_stack is not None:
+            report["hybrid_noise_seed"] = noise_seed
+        return report

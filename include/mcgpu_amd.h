@@ -754,8 +754,41 @@ typedef struct mcgpu_primary_report {
   double solid_angle;        /* of the source aperture [sr] */
   int n_energy_points;       /* spectrum nodes in all */
   int reserved;
+  double ms_sample;          /* mcgpu_primary_noisy: the sampler's kernels (0 for the other calls) */
 } mcgpu_primary_report;
 int mcgpu_primary_project(mcgpu_ctx *ctx, const mcgpu_primary_options *options, float *planes, mcgpu_primary_report *report);
+/* Row f20: the noise of the ray-traced primary (the header of csrc/primary_project.hip states the moment planes and THE NOISE RULE).
+ * mcgpu_primary_moments: the planes M_0, M_1, M_2 of every projection -- photons / cm^2, eV / cm^2, eV^2 / cm^2 per history; M_1 is
+ * mcgpu_primary_project's plane, bit for bit -- from one traversal: planes [n_projections][3][nz][crop_nx].  Same options, report
+ * and refusals as mcgpu_primary_project. */
+int mcgpu_primary_moments(mcgpu_ctx *ctx, const mcgpu_primary_options *options, float *planes, mcgpu_primary_report *report);
+/* mcgpu_primary_noisy: the `unscattered` plane with the mean and the variance that `histories` histories of the engine would give
+ * it: the moments and the compound Poisson sampler run on the device, only the sampled planes [n_projections][nz][crop_nx] come
+ * back.  The pixel area is the context's detector's.  A function of (seed, first_projection + p, pixel): the same seed gives the
+ * same bytes, and a scan made in two calls equals one call.  Refused as mcgpu_primary_project refuses, and histories <= 0 or not
+ * finite. */
+typedef struct mcgpu_primary_noisy_options {
+  unsigned int struct_size;  /* sizeof(mcgpu_primary_noisy_options) as the caller was compiled; 0 is refused */
+  int first_projection;
+  int n_projections;         /* 0: one */
+  int su, sv;                /* as mcgpu_primary_options */
+  int energy_points;
+  int crop_nx;
+  int reserved;
+  double histories;          /* N > 0: the history count whose noise the plane carries (need not be whole) */
+  unsigned long long seed;   /* key of the Philox4x32-10 draws */
+} mcgpu_primary_noisy_options;
+int mcgpu_primary_noisy(mcgpu_ctx *ctx, const mcgpu_primary_noisy_options *options, float *planes, mcgpu_primary_report *report);
+/* The sampler alone, on host planes [n_planes][ny][nx] of `device`: THE NOISE RULE with the moments m0, m1, m2, N = histories and
+ * a = pixel_area [cm^2]; plane p draws with counter (x, y, first_projection + p, k).  Refused with -1 before any device call: a
+ * null plane, n_planes outside 1 .. 65535, ny or nx < 1, ny x nx of 2^31 and more, first_projection < 0, histories or pixel_area
+ * not finite or <= 0. */
+int mcgpu_sample_compound_poisson(int device, const float *m0, const float *m1, const float *m2, float *out, int n_planes, int ny, int nx,
+                                  double histories, double pixel_area, unsigned long long seed, int first_projection);
+/* out = max(0, mean + sqrt(max(variance, 0)) z2), z2 the normal of draw k = 2 at counter (x, y, first_projection + p, 2): the noise
+ * of a smoothed scatter plane.  Same shapes and refusals as mcgpu_sample_compound_poisson. */
+int mcgpu_sample_gaussian(int device, const float *mean, const float *variance, float *out, int n_planes, int ny, int nx,
+                          unsigned long long seed, int first_projection);
 /* scipy.ndimage.gaussian_filter(plane, (sigma_y, sigma_x), truncate = 4, mode = "reflect") of n_planes float32 planes [ny][nx] on
  * `device` (host pointers; planes_out may be planes_in).  A sigma of 0 skips its axis; both 0 copy the planes bit for bit without
  * touching the device.  ms_kernel (may be NULL): the passes' device time. */

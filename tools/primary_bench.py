@@ -10,11 +10,16 @@ Per workload, for `--projections` projections spread over the trajectory:
   sigma     : median over the lit pixels of sqrt(variance) / value of the unscattered plane of a second launch that also tallies the
               squared weights, and N(1 %) = histories x
               (median / 0.01)^2
+  noise     : `--noise-rounds R` (default 0: off) rounds of primary_scan, primary_moments_scan and primary_noisy_scan of the same
+              projections at 1 x 1 sub-points, alternated call by call (and, with `--parent-lib PATH`, the primary_scan of another build
+              of the library -- the parent commit's -- on a context of its own in the same process, alternated with them): kernel ms per
+              projection of each, min / median / max over the rounds, and the sampler's ms (`profiles/primary_ab.md`)
 Prints one line per measurement and a final JSON line.  Usage: python tools/primary_bench.py [--workloads catphan cirs]
-[--projections 4] [--histories 1e8] [--n-vox 512]"""
+[--projections 4] [--histories 1e8] [--n-vox 512] [--noise-rounds 5] [--parent-lib build/ab/parent.so] [--skip-fast]"""
 from __future__ import annotations
 
 import argparse
+import ctypes as C
 import json
 import sys
 import time
@@ -27,6 +32,62 @@ sys.path.insert(0, str(ROOT))
 from __graft_entry__ import load_package  # noqa: E402
 
 
+class OtherBuild:
+    """primary_scan of another build of the library (one that may lack the newer entry points), on a context of its own."""
+
+    def __init__(self, eng, path, input_path, device=0):
+        self.eng, self.lib = eng, C.CDLL(str(path))
+        self.lib.mcgpu_create.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
+        self.lib.mcgpu_destroy.argtypes = [C.c_void_p]
+        self.lib.mcgpu_destroy.restype = None
+        self.lib.mcgpu_primary_project.argtypes = [C.c_void_p, C.POINTER(eng.PrimaryOptions), C.c_void_p, C.POINTER(eng.PrimaryReport)]
+        self.h = C.c_void_p()
+        if self.lib.mcgpu_create(str(input_path).encode(), device, C.byref(self.h)) != 0:
+            raise RuntimeError(f"{path}: mcgpu_create failed")
+
+    def primary_ms(self, p, shape, crop):
+        o = self.eng.PrimaryOptions(C.sizeof(self.eng.PrimaryOptions), int(p), 1, 1, 1, 2, int(crop))
+        r = self.eng.PrimaryReport(C.sizeof(self.eng.PrimaryReport))
+        out = np.zeros(shape, dtype=np.float32)
+        if self.lib.mcgpu_primary_project(self.h, C.byref(o), out.ctypes.data, C.byref(r)) != 0:
+            raise RuntimeError("mcgpu_primary_project of the other build failed")
+        return r.ms_kernel, out
+
+    def close(self):
+        self.lib.mcgpu_destroy(self.h)
+
+
+def noise_rounds(eng, ctx, inp, which, crop, rounds, parent_lib, histories):
+    """Kernel ms per projection of primary_scan, primary_moments_scan and primary_noisy_scan (and the other build's primary_scan),
+    alternated call by call; every call is one projection."""
+    other = OtherBuild(eng, parent_lib, inp) if parent_lib else None
+    ms = {"primary": [], "moments": [], "noisy": [], "noisy_sample": []}
+    if other:
+        ms["parent_primary"] = []
+    try:
+        for r in range(rounds + 1):                                             # round 0 warms every code object up and is dropped
+            acc = {k: [] for k in ms}
+            for p in which:
+                if other:
+                    t, theirs = other.primary_ms(p, (ctx.detector_shape[0], crop), crop)
+                    acc["parent_primary"].append(t)
+                plane, rep = ctx.primary_projection(p, crop_nx=crop)
+                acc["primary"].append(rep["ms_kernel"])
+                if other and r == 0:
+                    assert theirs.tobytes() == plane.tobytes(), "the two builds disagree on primary_projection"
+                acc["moments"].append(ctx.primary_moments(p, crop_nx=crop)[1]["ms_kernel"])
+                rep = ctx.primary_noisy_projection(p, histories, seed=1 + r, crop_nx=crop)[1]
+                acc["noisy"].append(rep["ms_kernel"])
+                acc["noisy_sample"].append(rep["ms_sample"])
+            if r:
+                for k in ms:
+                    ms[k].append(float(np.mean(acc[k])))
+    finally:
+        if other:
+            other.close()
+    return {k: dict(min=float(np.min(v)), median=float(np.median(v)), max=float(np.max(v)), rounds=v) for k, v in ms.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", nargs="+", default=["catphan", "cirs"])
@@ -34,6 +95,9 @@ def main():
     ap.add_argument("--histories", type=float, default=1e8)
     ap.add_argument("--n-vox", type=int, default=512)
     ap.add_argument("--n-proj", type=int, default=894)
+    ap.add_argument("--noise-rounds", type=int, default=0)
+    ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--skip-fast", action="store_true", help="leave out the FAST launches and the sigma measurement")
     args = ap.parse_args()
     pkg = load_package()
     eng, wl, d = pkg.engine, pkg.workloads, pkg.defaults.DEFAULTS
@@ -63,6 +127,14 @@ def main():
                                                        ms_tables=float(np.mean(tables)), n_materials=rep["n_materials"], n_energy_points=rep["n_energy_points"])
                 print(f"{workload}: primary {ss[0]} x {ss[1]}: {np.mean(ms):.2f} ms per projection (min {np.min(ms):.2f}, max {np.max(ms):.2f}), "
                       f"tables {np.mean(tables):.2f} ms, {rep['n_materials']} materials, {rep['n_energy_points']} energy points", flush=True)
+            if args.noise_rounds > 0:
+                row["noise"] = noise_rounds(eng, ctx, inp, which, crop, args.noise_rounds, args.parent_lib, float(n_hist))
+                for k, v in row["noise"].items():
+                    print(f"{workload}: {k}: {v['median']:.3f} ms per projection (min {v['min']:.3f}, max {v['max']:.3f} over {args.noise_rounds} rounds)",
+                          flush=True)
+            if args.skip_fast:
+                result[workload] = row
+                continue
             ctx.run_projection(which[0], 1_000_000)                              # warm-up of the tracking kernel
             fast_ms, rel = [], []
             for p in which:
