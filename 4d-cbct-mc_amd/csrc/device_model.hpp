@@ -32,6 +32,7 @@
 #include <cstdint>
 
 #include "host_model.hpp"
+#include "id_tickets.hpp"
 #include "tally_stage.hpp"
 
 namespace mcgpu {
@@ -129,7 +130,6 @@ constexpr int kPoolBlockThreads = 1024;   // FAST kernel: 16 waves per workgroup
 constexpr int kPoolParked = 1;            // FAST kernel: histories a lane parks in LDS slots beside the one in its registers
 constexpr int kPoolWavesPerSimd = 2 * kPoolBlockThreads / 64 / 4;  // two workgroups per CU (each gets half of the 160 KB of LDS)
 constexpr int kMaxBricks = 32768;         // brick grid budget: 4 bits each -> 16 KiB of LDS
-constexpr int kNumCounters = 64, kCounterStride = 32;  // FAST: history-id dispensers (u64 each, 256 B apart)
 constexpr int kWoodShift = 6;             // FAST: coarse Woodcock bins of 64 table bins (320 eV): 376 floats of LDS
 constexpr int kPoolKinds = 4;             // FAST, workgroup-level pool: kinds of work a parked history can wait for
 constexpr int kPoolQueueBytes = 64 + kPoolKinds * kPoolBlockThreads * 2;  // control block + rings (LdsLayout::queues)
@@ -262,7 +262,7 @@ struct TrackArgs {
   int thresh_take;  // COMPAT: lanes whose parked history could fly while their register history cannot, to exchange the two
   int dose_flags;             // bit 0: material dose tally, bit 1: voxel dose tally (TrackCold holds the buffers)
   unsigned long long* stats;  // diagnostic build only (kNumStats counters), else null
-  unsigned long long* work_counter;  // FAST: kNumCounters id dispensers, kCounterStride words apart (zeroed before each launch)
+  unsigned long long* work_counter;  // FAST: kNumCounters id dispensers, kCounterStride words apart, and their exhaustion mask (id_tickets.hpp; the block is zeroed before each launch)
   StageArgs stage;            // FAST: staging of the detector hits (tally_stage.hpp); region == null: direct atomics on `image`
   unsigned long long* w2;     // second tally beside `image`: sum of tally_w2_term(w) per word (tally_stage.hpp), null: off.  Last: every other argument keeps its offset
 };

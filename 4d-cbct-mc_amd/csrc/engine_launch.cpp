@@ -118,7 +118,8 @@ void TallyStage::prepare(DeviceModel& D, unsigned long long detector_words, Trac
     HIP_TRY(prepare_tally_fold(S));
     fold_ready = true;
   }
-  HIP_TRY(hipMemsetAsync(counts, 0, counts_needed, stream));
+  // `counts` is not cleared: every launched workgroup overwrites all its entries behind its final barrier (stage_counts_publish),
+  // and the fold reads the entries of the launched workgroups only
   plan = P;
   A.stage = S;
 }
@@ -199,13 +200,15 @@ void launch_fast(mcgpu_ctx& C, TrackArgs& A, int mode, hipStream_t stream) {
   const unsigned long long resident = resident_workgroups(D, A, has_w2);
   A.work_counter = D.work_counter;
   const unsigned long long first = A.first, count = A.count;
+  // the kernels draw their tickets from the low dword of a counter (id_tickets.hpp): 2^40 histories are 2^26 tickets per counter
+  require(count <= (1ULL << 40), -2, "!!ERROR!! mcgpu_launch_projection: more than 2^40 histories in one FAST launch");
   const bool staged = D.stage.wanted(D, has_w2);
   const unsigned long long limit = staged ? D.knobs.stage_max_histories : count;
   const unsigned long long n_sub = staged ? stage_sub_launches(count, limit) : 1ULL;
   for (unsigned long long k = 0; k < n_sub; ++k) {
     stage_sub_launch(first, count, limit, k, A.first, A.count);
     const int blocks = (int)std::min((A.count + kPoolBlockThreads - 1) / kPoolBlockThreads, resident);
-    HIP_TRY(hipMemsetAsync(D.work_counter, 0, (size_t)kNumCounters * kCounterStride * 8, stream));
+    HIP_TRY(hipMemsetAsync(D.work_counter, 0, (size_t)kNumCounters * kCounterStride * 8, stream));  // the ticket counters and their exhaustion mask
     A.stage = StageArgs{};
     if (staged) D.stage.prepare(D, 4ULL * (unsigned long long)C.host.detector[0].total_pixels, A, blocks, stream);  // leaves A.stage.region null where the buffers cannot be had
     if (mode == MCGPU_MODE_FAST_STATS) {
@@ -264,6 +267,31 @@ int mcgpu_tally_stage_sub_launch(unsigned long long first, unsigned long long co
   stage_sub_launch(first, count, limit, k, *sub_first, *sub_count);
   return 0;
   ABI_END
+}
+
+// Tickets first_ticket .. first_ticket + n - 1 of id dispenser `counter` in a FAST launch of `count` histories (id_tickets.hpp, the
+// functions the kernels use): ids lo_out[i] .. hi_out[i] - 1 of the launch, lo == hi for a ticket past the dispenser's last.
+// *n_tickets (may be null): the dispenser's non-empty tickets.
+int mcgpu_id_tickets(unsigned long long count, int counter, unsigned long long first_ticket, unsigned long long n, unsigned long long* lo_out,
+                     unsigned long long* hi_out, unsigned long long* n_tickets) {
+  ABI_BEGIN
+  require(counter >= 0 && counter < kNumCounters && (n == 0 || (lo_out && hi_out)), -1, "!!ERROR!! mcgpu_id_tickets: bad argument");
+  unsigned long long base, size;
+  id_counter_part(count, (unsigned int)counter, base, size);
+  for (unsigned long long i = 0; i < n; ++i) {
+    id_ticket_range(size, first_ticket + i, lo_out[i], hi_out[i]);
+    lo_out[i] += base;
+    hi_out[i] += base;
+  }
+  if (n_tickets) *n_tickets = id_ticket_count(size);
+  return 0;
+  ABI_END
+}
+
+// The dispenser a wave asks after `counter` given the exhaustion mask `mask` (id_tickets.hpp), or the number of dispensers when none is left
+int mcgpu_id_next_counter(unsigned long long mask, int counter) {
+  if (counter < 0 || counter >= kNumCounters) return -1;
+  return (int)id_next_counter(mask, (unsigned int)counter);
 }
 
 int mcgpu_launch_projection(mcgpu_ctx* ctx, int p, int mode, int seed, unsigned long long first, unsigned long long count, int hpt,

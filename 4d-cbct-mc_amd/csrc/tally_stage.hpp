@@ -119,7 +119,7 @@ inline unsigned long long stage_sub_launches(unsigned long long count, unsigned 
 // What the FAST kernels and the fold read (TrackArgs::stage): region == null selects the direct atomics
 struct StageArgs {
   unsigned long long* region;    // records: [(workgroup * n_bins + bin) * cap + slot]
-  unsigned int* counts;          // records written per (workgroup, bin): [workgroup * n_bins + bin], zeroed before each launch
+  unsigned int* counts;          // records written per (workgroup, bin): [workgroup * n_bins + bin]; every launched workgroup writes all of its entries, nothing clears them
   unsigned long long* fallback;  // hits that took the direct atomic (all launches since the last reset)
   unsigned int pixels, n_bins, magic, bin_pixels, cap;
   int cursor;                    // byte offset of the workgroup's cursors in the LDS image: u32[n_bins], then the fallback counter

@@ -30,8 +30,8 @@ namespace {
 constexpr int kBlock = kTrackBlockThreads;
 constexpr float kEps = 0.000015f;  // EPS_SOURCE, MC-GPU_v1.3.h:87
 // FAST: history ids are dealt from kNumCounters global counters, each owning a contiguous 1/kNumCounters of the launch, in
-// chunks of kChunk ids (track_pool.inc: id dealing); counters sit kCounterStride words apart (different memory channels)
-constexpr unsigned int kChunk = 256;
+// tickets of at most kChunk ids (id_tickets.hpp; track_pool.inc: id dealing); counters sit kCounterStride words apart (different memory channels)
+constexpr unsigned int kChunk = kIdChunk;
 constexpr int kBrickMixed = 0xF;      // brick code: look in the volume
 constexpr int kBrickExterior = 14;    // brick code: background outside the object box (palette slot 14)
 constexpr int kPaletteBase = 16;      // LDS palette: entries 0..14 = brick codes, 16.. = palette indices

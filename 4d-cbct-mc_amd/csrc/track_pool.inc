@@ -21,8 +21,11 @@
 //  * A history's RNG stream depends only on its id and moves with it; tallies are integer atomics.  The image is
 //    therefore independent of this schedule, of the thresholds and of the rank split (bit for bit).
 //  * History ids are dealt dynamically, 256 at a time, from 64 global counters that each own a contiguous 1/64 of the
-//    launch: a wave draws from its home counter and, once that is exhausted, from the next ones (so all waves finish
-//    together).  ONE counter was the first design -- and the bottleneck nobody saw: atomics on one address are serialised
+//    launch (id_tickets.hpp: a counter hands out tickets, ticket t is its t-th 256 ids).  A wave draws from its home counter
+//    and, once that is exhausted, from the next one that no wave has reported exhausted in the counters' shared mask word:
+//    all waves finish together, and the last moments of a launch are not spent on up to 63 empty tickets per wave -- 5e5
+//    atomics over the headline grid, serialised per counter, which cost 3 % of the Catphan launch (profiles/launch_end_ab.md).
+//    ONE counter was the first design -- and the bottleneck nobody saw: atomics on one address are serialised
 //    at about 18 ns each, the 3.9e5 fetches of a 1e8-history launch took 7.2 ms, and no change to the kernel moved the
 //    Catphan time any more (thresholds, slot trading, fewer source instructions: all +-0.5 %) until the chunk size was
 //    varied.  With 64 addresses the same fetches cost nothing measurable: 7.25 -> 5.2 ms.
@@ -532,44 +535,61 @@ __device__ __forceinline__ void score_finished(const TrackArgs& A, const History
 }
 
 // Deal history ids to the lanes that need one (phase NEW): wave-uniform bookkeeping executed by every lane (callers enter on a
-// wave-uniform condition), ids ranked by ballot.  chunk_next / chunk_end: the unassigned ids of this wave's current chunk; ctr:
-// the counter it draws from next; ctr_exhausted: how many counters it has found exhausted (all of them: no work is left).
-// Returns the lane's id, or ~0 for none.
-__device__ __forceinline__ unsigned long long deal_history_ids(const TrackArgs& A, const int phase, unsigned long long& chunk_next, unsigned long long& chunk_end,
-                                                               unsigned int& ctr, unsigned int& ctr_exhausted) {
+// wave-uniform condition), ids ranked by ballot.  chunk_next / chunk_left: the first unassigned id of this wave's current ticket and
+// how many follow it (at most kChunk: one register instead of the ticket's end); walk: the counter it draws from next (bits 0..7) and
+// how many counters it has found exhausted (bits 8.., kWalkDone = all of them: no work is left) in one register.  Returns the lane's
+// id, or ~0 for none.
+constexpr unsigned int kWalkDone = (unsigned int)kNumCounters << 8;
+__device__ __forceinline__ unsigned long long deal_history_ids(const TrackArgs& A, const int phase, unsigned long long& chunk_next, unsigned int& chunk_left,
+                                                               unsigned int& walk) {
   unsigned long long my_id = ~0ULL;
   const unsigned long long need = __ballot(phase == PH_NEW);
   const unsigned int n_need = (unsigned int)__popcll(need);
   if (n_need != 0u) {
     const unsigned int rank = __builtin_amdgcn_mbcnt_hi((unsigned int)(need >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)need, 0u));
-    const unsigned long long avail = chunk_end - chunk_next;
+    const unsigned int avail = chunk_left;
     if (avail >= n_need) {
       my_id = chunk_next + rank;
       chunk_next += n_need;
+      chunk_left -= n_need;
     } else {
-      // the rest of the old chunk, then a new one: from this wave's counter or, once that one is exhausted, from the
-      // next (at most kNumCounters failed fetches per wave, at the very end of the launch)
+      // the rest of the old ticket, then a new one (id_tickets.hpp): from this wave's counter or, once that one is exhausted, from
+      // the next one that no wave has reported exhausted yet.  The last ticket of a counter may hold fewer ids than lanes ask: the
+      // others stay NEW and ask again at the next service.
       if (rank < avail) my_id = chunk_next + rank;
-      chunk_next = chunk_end;
+      chunk_left = 0u;
       const int leader = __ffsll((long long)need) - 1;
-      while (ctr_exhausted < (unsigned int)kNumCounters) {
-        const unsigned long long base = LARG(A, count) / kNumCounters * ctr + min((unsigned long long)ctr, LARG(A, count) % kNumCounters);
-        const unsigned long long size = LARG(A, count) / kNumCounters + (ctr < LARG(A, count) % kNumCounters ? 1ULL : 0ULL);
-        unsigned long long gv = 0;
-        if ((int)(threadIdx.x & 63) == leader) gv = atomicAdd(LARG(A, work_counter) + ctr * (unsigned int)kCounterStride, (unsigned long long)kChunk);
-        // wave-uniform from here on (scalar registers): the leader's value, read with a scalar lane index
-        const unsigned long long g = ((unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)(gv >> 32), leader) << 32) |
-                                     (unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)gv, leader);
-        if (g >= size) {
-          ++ctr_exhausted;
-          ctr = (ctr + 1u) % (unsigned int)kNumCounters;
+      const bool leads = (int)(threadIdx.x & 63) == leader;
+      while (walk < kWalkDone) {
+        const unsigned int ctr = walk & 0xFFu;
+        // a ticket: the counter's low dword, one 32-bit atomic (the host refuses a launch whose ticket numbers could pass 2^32); the
+        // leader's value, wave-uniform from here on (scalar registers), read with a scalar lane index
+        unsigned long long base, size, lo, hi;
+        unsigned int tv = 0u;
+        id_counter_part(LARG(A, count), ctr, base, size);
+        if (leads) tv = atomicAdd(reinterpret_cast<unsigned int*>(LARG(A, work_counter) + ctr * (unsigned int)kCounterStride), 1u);
+        id_ticket_range(size, (unsigned int)__builtin_amdgcn_readlane((int)tv, leader), lo, hi);
+        if (lo >= hi) {
+          // Exhausted: say so in the mask (only a wave that drew an empty ticket sets a bit, and no bit is cleared during a launch) and
+          // go on with the first counter nobody has reported.  A bit not seen yet costs one more empty ticket, and the wave's own
+          // empty tickets still end the walk at kNumCounters: nothing here waits for another wave.  The OR returns nothing -- a
+          // returning one by every wave would be the serialised same-address traffic the mask removes -- and touches the bit's dword only.
+          unsigned long long* const mask_word = LARG(A, work_counter) + kIdMaskWord;
+          unsigned long long mv = 0;
+          if (leads) mv = __hip_atomic_load(mask_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          unsigned long long mask = ((unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)(mv >> 32), leader) << 32) |
+                                    (unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)mv, leader);
+          if (leads && ((mask >> ctr) & 1ULL) == 0ULL) atomicOr(reinterpret_cast<unsigned int*>(mask_word) + (ctr >> 5), 1u << (ctr & 31u));
+          mask |= 1ULL << ctr;
+          const unsigned int next = id_next_counter(mask, ctr);  // kNumCounters: every counter is known to be exhausted
+          walk = next < (unsigned int)kNumCounters ? ((walk & ~0xFFu) + 0x100u) | next : kWalkDone;
           continue;
         }
-        const unsigned long long g_end = base + ((g + kChunk < size) ? g + kChunk : size);
-        const unsigned long long id = base + g + (rank - avail);
-        if (rank >= avail && id < g_end) my_id = id;
-        chunk_next = min(base + g + (n_need - avail), g_end);
-        chunk_end = g_end;
+        // the ticket's first ids to the lanes the old one left out, the rest for later
+        const unsigned int got = (unsigned int)(hi - lo), taken = min(n_need - avail, got);
+        if (rank >= avail && rank - avail < got) my_id = base + lo + (rank - avail);
+        chunk_next = base + lo + taken;
+        chunk_left = got - taken;
         break;
       }
     }
@@ -580,7 +600,7 @@ __device__ __forceinline__ unsigned long long deal_history_ids(const TrackArgs& 
 // A lane in NEW starts history `my_id` (K.cu:206-247) -- or, given none, is DONE once every counter is exhausted (otherwise it stays
 // NEW and asks again at the next service).
 __device__ __forceinline__ void start_history(const TrackArgs& A, History& h, int& phase, int& mc_old, float& negl2, const unsigned long long my_id,
-                                              const unsigned int ctr_exhausted) {
+                                              const unsigned int walk) {
   if (phase == PH_NEW) {
     if (my_id != ~0ULL) {
       rng_init_history(h.rng, LARG(A, first) + my_id, (unsigned int)LARG(A, seed), LARG(A, stream_key));
@@ -607,7 +627,7 @@ __device__ __forceinline__ void start_history(const TrackArgs& A, History& h, in
         move_to_bbox(A, h.P, miss);
         phase = miss ? PH_ESCAPED : PH_FLIGHT;
       }
-    } else if (ctr_exhausted >= (unsigned int)kNumCounters) {
+    } else if (walk >= kWalkDone) {
       phase = PH_DONE;  // every counter is exhausted
     }
   }
@@ -668,11 +688,12 @@ __global__ __launch_bounds__(kPoolBlock, kPoolWavesPerSimd) void track_pool_kern
   int mc_old = -1;
   float negl2 = 0.f;  // -ln(2) * h.mfpW: flight step = negl2 * log2(xi)
   const float hi_x = A.bbox_hi[0], hi_y = A.bbox_hi[1], hi_z = A.bbox_hi[2];
-  unsigned long long chunk_next = 0, chunk_end = 0;  // wave-uniform: unassigned ids of this wave's current chunk
+  unsigned long long chunk_next = 0;  // wave-uniform: unassigned ids of this wave's current ticket: the first ...
+  unsigned int chunk_left = 0u;      // ... and how many
   // wave-uniform: the counter this wave draws from next, and how many counters it has found exhausted (all: no work left)
   // (the compiler cannot know that threadIdx.x >> 6 is wave-uniform: the counter, the chunk bounds and the branches on them live in vector
   // registers.  Telling it -- readfirstlane -- moves them to scalar registers the kernel does not have: 11 more spills, CIRS 3 % slower.)
-  unsigned int ctr = (blockIdx.x * (unsigned int)(kPoolBlock / 64) + (threadIdx.x >> 6)) % (unsigned int)kNumCounters, ctr_exhausted = 0u;
+  unsigned int walk = (blockIdx.x * (unsigned int)(kPoolBlock / 64) + (threadIdx.x >> 6)) % (unsigned int)kNumCounters;
   const int nmat = A.nmat;
   int hold = 0;  // wave-uniform: keep flying while more than `hold` lanes are in flight
   // the register history does not satisfy pred but a parked one does: exchange them (the first such slot)
@@ -832,8 +853,8 @@ __global__ __launch_bounds__(kPoolBlock, kPoolWavesPerSimd) void track_pool_kern
       int tally_word;  // word of the detector tally this lane scores in (-1: none); the hit is scored at the end of the batch
       unsigned int tally_value;
       score_finished(A, h, phase, tally_word, tally_value);
-      const unsigned long long my_id = deal_history_ids(A, phase, chunk_next, chunk_end, ctr, ctr_exhausted);
-      start_history(A, h, phase, mc_old, negl2, my_id, ctr_exhausted);
+      const unsigned long long my_id = deal_history_ids(A, phase, chunk_next, chunk_left, walk);
+      start_history(A, h, phase, mc_old, negl2, my_id, walk);
       // One scattered 64-bit add per detected photon, executed at the memory side, was the wall of the Catphan launch: 7.5e7 of them
       // at 2.37e10/s = 3.18 ms of a 3.67 ms launch, whatever the kernel around them did (round-2 experiment, DESIGN.md 3.1: without
       // the add 17 % faster, a plain store in its place 15 %, a 32-bit add 4 %; issuing it later changes nothing).  The hit is now
@@ -946,11 +967,11 @@ __global__ __launch_bounds__(kPoolBlock, kPoolWavesPerSimd) void track_wg_kernel
   int mc_old = -1;
   float negl2 = 0.f;
   const float hi_x = A.bbox_hi[0], hi_y = A.bbox_hi[1], hi_z = A.bbox_hi[2];
-  unsigned long long chunk_next = 0, chunk_end = 0;
+  unsigned long long chunk_next = 0;
+  unsigned int chunk_left = 0u;
   // (readfirstlane: threadIdx.x >> 6 is the same in every lane of a wave, which the compiler cannot know -- without it the counter, the chunk
   // bounds and every branch on them live in vector registers and run as divergent code)
-  unsigned int ctr = (unsigned int)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * (unsigned int)(kPoolBlock / 64) + (threadIdx.x >> 6)) % (unsigned int)kNumCounters));
-  unsigned int ctr_exhausted = 0u;
+  unsigned int walk = (unsigned int)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * (unsigned int)(kPoolBlock / 64) + (threadIdx.x >> 6)) % (unsigned int)kNumCounters));
   const int nmat = A.nmat;
   const int lane = (int)(threadIdx.x & 63u);
   auto rank_in = [](unsigned long long m) { return (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)m, 0u)); };
@@ -1127,8 +1148,8 @@ __global__ __launch_bounds__(kPoolBlock, kPoolWavesPerSimd) void track_wg_kernel
       int tally_word;
       unsigned int tally_value;
       score_finished(A, h, phase, tally_word, tally_value);
-      const unsigned long long my_id = deal_history_ids(A, phase, chunk_next, chunk_end, ctr, ctr_exhausted);
-      start_history(A, h, phase, mc_old, negl2, my_id, ctr_exhausted);
+      const unsigned long long my_id = deal_history_ids(A, phase, chunk_next, chunk_left, walk);
+      start_history(A, h, phase, mc_old, negl2, my_id, walk);
       if (tally_word >= 0) tally_score(A, tally_word, tally_value);
       STAT_T1(14);
       STAT_T1(31);

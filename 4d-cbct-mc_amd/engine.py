@@ -24,7 +24,7 @@ EXE_PATH = Path(__file__).resolve().parent / "MC-GPU_v1.3.x"
 ABI_SYMBOLS = (
     "mcgpu_abi_version", "mcgpu_knob_table", "mcgpu_last_error", "mcgpu_create", "mcgpu_clone", "mcgpu_destroy", "mcgpu_config_i64", "mcgpu_config_f64",
     "mcgpu_host_table", "mcgpu_projection_file_name", "mcgpu_image_words", "mcgpu_launch_shape", "mcgpu_advance_seed",
-    "mcgpu_launch_projection", "mcgpu_launch_projection_w2", "mcgpu_run_projection_w2", "mcgpu_finalize_variance", "mcgpu_finalize_variance_host", "mcgpu_tally_stage_plan", "mcgpu_tally_stage_map", "mcgpu_tally_stage_sub_launch", "mcgpu_scheduler_stats", "mcgpu_scheduler_stats_ex", "mcgpu_last_kernel_ms", "mcgpu_clear_image", "mcgpu_run_projection",
+    "mcgpu_launch_projection", "mcgpu_launch_projection_w2", "mcgpu_run_projection_w2", "mcgpu_finalize_variance", "mcgpu_finalize_variance_host", "mcgpu_tally_stage_plan", "mcgpu_tally_stage_map", "mcgpu_tally_stage_sub_launch", "mcgpu_id_tickets", "mcgpu_id_next_counter", "mcgpu_scheduler_stats", "mcgpu_scheduler_stats_ex", "mcgpu_last_kernel_ms", "mcgpu_clear_image", "mcgpu_run_projection",
     "mcgpu_write_projection", "mcgpu_format_projection", "mcgpu_write_formatted_projection", "mcgpu_dose_info", "mcgpu_dose_read", "mcgpu_dose_clear", "mcgpu_write_dose_report",
     "mcgpu_finalize_projection", "mcgpu_finalize_projection_host", "mcgpu_stack_create", "mcgpu_stack_append", "mcgpu_stack_write_slice", "mcgpu_stack_finish",
     "mcgpu_stack_read", "mcgpu_normalize_stack", "mcgpu_run_scan", "mcgpu_run_scan_multi", "mcgpu_set_projection_angles", "mcgpu_set_geometry_arrays",
@@ -161,6 +161,8 @@ def load_library(path: Optional[os.PathLike] = None):
     lib.mcgpu_tally_stage_plan.argtypes = [vp, cull, cull, ci, ci, cull, C.POINTER(cull)]
     lib.mcgpu_tally_stage_map.argtypes = [cull, ci, cull, cull, vp, vp]
     lib.mcgpu_tally_stage_sub_launch.argtypes = [cull, cull, cull, cull, C.POINTER(cull), C.POINTER(cull)]
+    lib.mcgpu_id_tickets.argtypes = [cull, ci, cull, cull, vp, vp, C.POINTER(cull)]
+    lib.mcgpu_id_next_counter.argtypes = [cull, ci]
     lib.mcgpu_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.mcgpu_scheduler_stats.argtypes = [vp, C.POINTER(cull), ci]
     lib.mcgpu_scheduler_stats_ex.argtypes = [vp, C.POINTER(cull), ci, ci]
@@ -267,6 +269,27 @@ def tally_stage_map(detector_words: int, bins: int = 0, first: int = 0, n: Optio
     b, r = np.empty(n, np.uint32), np.empty(n, np.uint32)
     _check(load_library().mcgpu_tally_stage_map(int(detector_words), int(bins), int(first), n, b.ctypes.data, r.ctypes.data))
     return b, r
+
+
+def id_tickets(count: int, counter: int, first_ticket: int = 0, n: Optional[int] = None):
+    """How a FAST launch of `count` histories deals its ids: (lo, hi, n_tickets) of tickets first_ticket .. first_ticket+n-1 of id
+    dispenser `counter` -- ids lo[i] .. hi[i]-1 of the launch as uint64 arrays (lo == hi: exhausted) and the dispenser's non-empty
+    tickets; n = None: all of those and one more."""
+    lib, total = load_library(), C.c_ulonglong()
+    if n is None:
+        _check(lib.mcgpu_id_tickets(int(count), int(counter), 0, 0, None, None, C.byref(total)))
+        n = total.value + 1 - int(first_ticket)
+    lo, hi = np.empty(int(n), np.uint64), np.empty(int(n), np.uint64)
+    _check(lib.mcgpu_id_tickets(int(count), int(counter), int(first_ticket), int(n), lo.ctypes.data, hi.ctypes.data, C.byref(total)))
+    return lo, hi, total.value
+
+
+def id_next_counter(mask: int, counter: int) -> int:
+    """The id dispenser a wave asks after `counter` when `mask` has a bit for every dispenser reported exhausted (64: none is left)."""
+    nxt = load_library().mcgpu_id_next_counter(int(mask), int(counter))
+    if nxt < 0:
+        raise ValueError(f"id_next_counter: no dispenser {counter}")
+    return nxt
 
 
 def tally_stage_sub_launch(first: int, count: int, limit: int, k: int):

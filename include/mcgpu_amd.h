@@ -136,6 +136,14 @@ int mcgpu_tally_stage_map(unsigned long long detector_words, int bins, unsigned 
 /* History range of sub-launch k of a staged launch of [first, first+count) at sub-launch limit `limit`. */
 int mcgpu_tally_stage_sub_launch(unsigned long long first, unsigned long long count, unsigned long long limit, unsigned long long k,
                                  unsigned long long *sub_first, unsigned long long *sub_count);
+/* How a FAST launch of `count` histories deals its ids: tickets first_ticket .. first_ticket+n-1 of id dispenser `counter`
+ * (0..63) are the ids lo_out[i] .. hi_out[i]-1 of the launch (relative to its first history; lo == hi: the dispenser is exhausted).
+ * *n_tickets (may be NULL): the dispenser's non-empty tickets.  Pure host arithmetic, the functions the kernels use. */
+int mcgpu_id_tickets(unsigned long long count, int counter, unsigned long long first_ticket, unsigned long long n,
+                     unsigned long long *lo_out, unsigned long long *hi_out, unsigned long long *n_tickets);
+/* The dispenser a wave asks after `counter` when `mask` holds a bit for every dispenser reported exhausted: the first one after
+ * it, cyclically, whose bit is clear; 64 when none is; -1 for a bad `counter`. */
+int mcgpu_id_next_counter(unsigned long long mask, int counter);
 /* Milliseconds between the HIP events recorded around the most recent launch on its stream
  * (synchronises on the stop event). */
 int mcgpu_last_kernel_ms(mcgpu_ctx *ctx, float *ms);
