@@ -8,9 +8,9 @@ the Python modules mirror the reference's host-side interface for this path
 (`cbctmc/mc/simulation.py`, `geometry.py`, `materials.py`, `defaults.py`, `projection.py`,
 `cbctmc/registration/correspondence.py`).
 """
-from . import correspondence, defaults, forward_projection, geometry, materials, phase, reconstruction, registration, respiratory, segmentation, segmentation_training, sharding, simulation, speedup, speedup_training, water_precorrection, workloads  # noqa: F401
+from . import correspondence, defaults, forward_projection, geometry, materials, phase, reconstruction, registration, respiratory, segmentation, segmentation_training, sharding, shroud, simulation, speedup, speedup_training, water_precorrection, workloads  # noqa: F401
 
-__all__ = ["correspondence", "defaults", "forward_projection", "geometry", "materials", "phase", "reconstruction", "registration", "respiratory", "segmentation", "segmentation_training", "sharding", "simulation", "speedup", "speedup_training", "water_precorrection", "workloads", "engine"]
+__all__ = ["correspondence", "defaults", "forward_projection", "geometry", "materials", "phase", "reconstruction", "registration", "respiratory", "segmentation", "segmentation_training", "sharding", "shroud", "simulation", "speedup", "speedup_training", "water_precorrection", "workloads", "engine"]
 
 
 def __getattr__(name):

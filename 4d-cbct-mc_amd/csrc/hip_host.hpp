@@ -1,6 +1,6 @@
 #pragma once
 // hip_host.hpp -- what the host code around the device routines shares (engine*.cpp, scan.cpp, fdk.hip, wpc_fit.hip, forward_project.hip,
-// rooster4d.hip, resample.hip, speedup_net.hip, speedup_train.hip, segment_net.hip): the HIP check, the exception boundary of the C ABI, owners of HIP handles and of one call's device memory, the
+// rooster4d.hip, shroud.hip, resample.hip, speedup_net.hip, speedup_train.hip, segment_net.hip): the HIP check, the exception boundary of the C ABI, owners of HIP handles and of one call's device memory, the
 // stage timer, the host stopwatch, the reader of struct_size-versioned options, the writer of such reports and the small rules of the circular cone-beam geometry.
 #include <hip/hip_runtime.h>
 

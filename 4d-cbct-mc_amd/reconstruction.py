@@ -537,21 +537,40 @@ def _unit_phase(amplitude_signal, phase_signal) -> np.ndarray:
 def reconstruct_4d(projections_filepath, geometry_filepath, output_folder=None, output_filename: Optional[str] = None,
                    dimension: Tuple[int, int, int] = (464, 250, 464), spacing: Tuple[float, float, float] = (1.0, 1.0, 1.0),
                    amplitude_signal: Optional[np.ndarray] = None, phase_signal: Optional[np.ndarray] = None,
-                   water_pre_correction: Optional[Sequence[float]] = None, gpu_id: int = 0, **kwargs):
+                   water_pre_correction: Optional[Sequence[float]] = None, gpu_id: int = 0, extract_signal: bool = False,
+                   shroud: Optional[dict] = None, **kwargs):
     """cbctmc/reconstruction/reconstruction.py:72-125 with `rtkfourdrooster` replaced by the in-process kernels (rooster4d).
     Exactly one of `amplitude_signal` (one breathing amplitude per projection; its phase comes from phase.calculate_phase) and
     `phase_signal` is given, else ValueError.  The phase is min-max scaled to [0, 1] as the reference does before it hands the
     signal to RTK (reconstructors.py:150-151).  The reference's parameters: niter 10, cgiter 4, tviter 10, gamma_time 0.0002,
     gamma_space 0.00007 (keyword arguments override them, as do `frames` and `positivity`).  Writes `recon_rooster4d.mha`, a 4-D
     MetaImage [frames][nz][ny][nx] with spacing (sx, sy, sz, 1) and offset (ox, oy, oz, 0) in the frame of reconstruct_3d's
-    output, and a .yaml of the parameters next to it (fp / bp record what ran: Joseph / VoxelBased)."""
-    ph = _unit_phase(amplitude_signal, phase_signal)
+    output, and a .yaml of the parameters next to it (fp / bp record what ran: Joseph / VoxelBased).
+
+    extract_signal=True takes the amplitude from the projections themselves, `shroud.extract_signal(projections, **(shroud or {}))`
+    (the Amsterdam shroud; its amplitude is not calibrated, which the phase does not need), and neither signal may then be given
+    (ValueError); the .yaml records `signal: shroud` and the extraction parameters under `shroud`."""
+    from . import shroud as shroud_mod
+    if extract_signal and (amplitude_signal is not None or phase_signal is not None):
+        raise ValueError("extract_signal=True takes the signal from the projections: give neither amplitude_signal nor phase_signal")
+    ph = None if extract_signal else _unit_phase(amplitude_signal, phase_signal)
     params = _rooster_parameters(kwargs)
-    return _reconstruct_to_file(
-        projections_filepath, geometry_filepath, output_folder, output_filename or "recon_rooster4d.mha", dimension, spacing, water_pre_correction,
-        lambda proj, geometry, ds, org: rooster4d(proj, geometry, ds, org, ph, dimension, spacing, None, water_pre_correction=water_pre_correction,
-                                                  gpu_id=gpu_id, **params),
-        dict(fp="Joseph", bp="VoxelBased", **params, **kwargs))
+    shroud_parameters = {"gpu_id": gpu_id, **(shroud or {})}
+
+    def compute(proj, geometry, ds, org):
+        phase = _unit_phase(shroud_mod.extract_signal(proj, **shroud_parameters), None) if extract_signal else ph
+        return rooster4d(proj, geometry, ds, org, phase, dimension, spacing, None, water_pre_correction=water_pre_correction, gpu_id=gpu_id, **params)
+
+    record = {}
+    if extract_signal:  # what ran, the defaults included
+        import inspect
+        defaults = {k: p.default for k, p in inspect.signature(shroud_mod.extract_signal).parameters.items() if p.default is not inspect.Parameter.empty}
+        unknown = set(shroud_parameters) - set(defaults)
+        if unknown:
+            raise ValueError(f"shroud: unknown extraction parameters {sorted(unknown)}")
+        record = dict(signal="shroud", shroud={k: (list(v) if isinstance(v, (tuple, list)) else v) for k, v in {**defaults, **shroud_parameters}.items()})
+    return _reconstruct_to_file(projections_filepath, geometry_filepath, output_folder, output_filename or "recon_rooster4d.mha", dimension, spacing,
+                                water_pre_correction, compute, dict(fp="Joseph", bp="VoxelBased", **params, **record, **kwargs))
 
 
 def _rooster_parameters(kwargs) -> dict:

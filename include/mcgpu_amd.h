@@ -939,6 +939,44 @@ int mcgpu_register_stage(const mcgpu_register_options *options, int stage, const
                          const unsigned char *fixed_mask_or_null, void *out, mcgpu_register_report *report);
 
 /* ------------------------------------------------------------------------------------------------
+ * Row f21: the breathing signal from the projections alone (what RTK does with rtkamsterdamshroud followed by
+ * rtkextractshroudsignal; csrc/shroud.hip, whose header states the rule; float64 restatement: tests/shroud_ref.py).  Stage A forms
+ * the Amsterdam shroud A[n_proj][m] (float32) from the projections, stage B the costs c_i(s) of shifting column i against column
+ * i - 1 by s rows, stage C the signal x[n_proj] in rows (x_0 = 0; positive: toward larger v).  Every kernel is a fixed function of
+ * its inputs: two calls give the same bytes.  The amplitude is not calibrated: the signal serves for the phase.  Parity against RTK
+ * itself is unpinned (RTK is absent here). */
+typedef struct mcgpu_shroud_options {
+  unsigned int struct_size;     /* sizeof(mcgpu_shroud_options) as the caller was compiled (later fields read as zero); 0 is refused */
+  int n_proj, nu, nv;           /* the stack [n_proj][nv][nu]; mcgpu_shroud_signal: n_proj columns */
+  int u_first, u_count;         /* the columns that are summed; u_count 0: all columns from u_first on */
+  int v_first, v_count;         /* the rows that make the shroud, m = v_count; v_count 0: all rows from v_first on */
+  int unsharp;                  /* width of the unsharp mask along the projection axis: odd, or 0 for none; an even one is refused */
+  int max_shift;                /* S: shifts -S .. S rows are tried; 2 S < m is required */
+  int device;
+} mcgpu_shroud_options;
+typedef struct mcgpu_shroud_report {
+  unsigned int struct_size;     /* sizeof(mcgpu_shroud_report) as the caller was compiled; only that many bytes are written */
+  int reserved;
+  double ms_upload;             /* host -> device copies (wall time) */
+  double ms_shroud;             /* stage A: row sums, their combination, the unsharp mask */
+  double ms_cost;               /* stage B */
+  double ms_total;              /* wall time of the call */
+  unsigned long long peak_device_bytes;  /* most device memory the call held at once: the stack goes up 32 projections at a time */
+} mcgpu_shroud_report;
+/* Stages A to C.  Refused with -1 before any device call: a size below 1, columns or rows outside the image, an even unsharp, a
+ * negative max_shift or 2 max_shift >= m, a null projections or signal pointer. */
+int mcgpu_shroud_extract(const mcgpu_shroud_options *options, const float *projections /*[n_proj][nv][nu]*/, float *shroud /*[n_proj][m] or NULL*/,
+                         double *costs /*[n_proj - 1][2 S + 1] or NULL*/, double *signal /*[n_proj]*/, mcgpu_shroud_report *report);
+/* Stages B and C alone from a shroud on the host (for tests with crafted columns): n_proj and v_count give its shape and max_shift
+ * gives S; nu, nv, u_first, u_count, v_first and unsharp are not read. */
+int mcgpu_shroud_signal(const mcgpu_shroud_options *options, const float *shroud /*[n_proj][v_count]*/, double *costs /*[n_proj - 1][2 S + 1] or NULL*/,
+                        double *signal /*[n_proj]*/, mcgpu_shroud_report *report);
+/* The row sums D[n_proj][m] (float64, before the mask) of a stack that is resident on options->device, written to device memory:
+ * what tools/shroud_bench.py times.  unsharp and max_shift are not used; the call returns when the kernels have finished. */
+int mcgpu_shroud_rows_device(const mcgpu_shroud_options *options, const float *projections_device, double *rows_device /*[n_proj][m]*/,
+                             mcgpu_shroud_report *report);
+
+/* ------------------------------------------------------------------------------------------------
  * The speed-up network (what the reference obtains from cbctmc/speedup/inference.py: MCSpeedup; csrc/speedup_net.hip, whose
  * header restates the network).  Two U-Nets of 3 x 3 convolutions (replicate padding, bias), instance norm and LeakyReLU(0.01),
  * in float32: the mean net sees the low-photon projection and the forward projection (matched to it in mean and unbiased
