@@ -31,7 +31,7 @@ ABI_SYMBOLS = (
     "mcgpu_warp_volume", "mcgpu_warp_geometry", "mcgpu_map_image", "mcgpu_set_geometry_image",
     "mcgpu_resample_plan", "mcgpu_resample_volume", "mcgpu_set_geometry_image_resampled",
     "mcgpu_correspondence_set", "mcgpu_correspondence_fit", "mcgpu_correspondence_predict", "mcgpu_warp_geometry_signal", "mcgpu_correspondence_clear",
-    "mcgpu_write_voxel_file", "mcgpu_write_voxel_binary", "mcgpu_kat_rng", "mcgpu_kat_rng_streams", "mcgpu_microbench", "mcgpu_kat_math", "mcgpu_kat_expf", "mcgpu_kat_f32", "mcgpu_kat_fast64", "mcgpu_kat_scatter", "mcgpu_kat_history", "mcgpu_kat_flight", "mcgpu_kat_tile_records", "mcgpu_fdk_reconstruct", "mcgpu_fdk_reconstruct_motion", "mcgpu_wpc_fit", "mcgpu_forward_project", "mcgpu_forward_project_context", "mcgpu_primary_project", "mcgpu_smooth_planes", "mcgpu_primary_moments", "mcgpu_primary_noisy", "mcgpu_sample_compound_poisson", "mcgpu_sample_gaussian", "mcgpu_rooster4d_reconstruct", "mcgpu_rooster4d_stage", "mcgpu_rooster4d_reconstruct_motion", "mcgpu_rooster4d_motion_stage", "mcgpu_register", "mcgpu_register_stage", "mcgpu_shroud_extract", "mcgpu_shroud_signal", "mcgpu_shroud_rows_device", "mcgpu_speedup_run", "mcgpu_speedup_stage", "mcgpu_speedup_train_create", "mcgpu_speedup_train_step", "mcgpu_speedup_train_gradients", "mcgpu_speedup_train_predict", "mcgpu_speedup_train_get_state", "mcgpu_speedup_train_set_state", "mcgpu_speedup_train_destroy", "mcgpu_speedup_train_stage", "mcgpu_segment_run", "mcgpu_segment_stage", "mcgpu_segment_train_create", "mcgpu_segment_train_step", "mcgpu_segment_train_gradients", "mcgpu_segment_train_predict", "mcgpu_segment_train_get_state", "mcgpu_segment_train_set_state", "mcgpu_segment_train_destroy", "mcgpu_segment_train_stage", "mcgpu_set_fast_schedule", "mcgpu_reload_env_knobs",
+    "mcgpu_write_voxel_file", "mcgpu_write_voxel_binary", "mcgpu_kat_rng", "mcgpu_kat_rng_streams", "mcgpu_microbench", "mcgpu_kat_math", "mcgpu_kat_expf", "mcgpu_kat_f32", "mcgpu_kat_fast64", "mcgpu_kat_scatter", "mcgpu_kat_history", "mcgpu_kat_flight", "mcgpu_kat_tile_records", "mcgpu_fdk_reconstruct", "mcgpu_fdk_reconstruct_motion", "mcgpu_wpc_fit", "mcgpu_forward_project", "mcgpu_forward_project_context", "mcgpu_primary_project", "mcgpu_smooth_planes", "mcgpu_primary_moments", "mcgpu_primary_noisy", "mcgpu_sample_compound_poisson", "mcgpu_sample_gaussian", "mcgpu_rooster4d_reconstruct", "mcgpu_rooster4d_stage", "mcgpu_rooster4d_reconstruct_motion", "mcgpu_rooster4d_motion_stage", "mcgpu_register", "mcgpu_register_stage", "mcgpu_invert_field", "mcgpu_field_residual", "mcgpu_shroud_extract", "mcgpu_shroud_signal", "mcgpu_shroud_rows_device", "mcgpu_speedup_run", "mcgpu_speedup_stage", "mcgpu_speedup_train_create", "mcgpu_speedup_train_step", "mcgpu_speedup_train_gradients", "mcgpu_speedup_train_predict", "mcgpu_speedup_train_get_state", "mcgpu_speedup_train_set_state", "mcgpu_speedup_train_destroy", "mcgpu_speedup_train_stage", "mcgpu_segment_run", "mcgpu_segment_stage", "mcgpu_segment_train_create", "mcgpu_segment_train_step", "mcgpu_segment_train_gradients", "mcgpu_segment_train_predict", "mcgpu_segment_train_get_state", "mcgpu_segment_train_set_state", "mcgpu_segment_train_destroy", "mcgpu_segment_train_stage", "mcgpu_set_fast_schedule", "mcgpu_reload_env_knobs",
     "mcgpu_exchange_shared_bytes", "mcgpu_exchange_card_bytes", "mcgpu_exchange_create", "mcgpu_exchange_card", "mcgpu_exchange_connect",
     "mcgpu_exchange_connect_local", "mcgpu_exchange_probe", "mcgpu_exchange_owner", "mcgpu_exchange_begin", "mcgpu_exchange_submit", "mcgpu_exchange_collect",
     "mcgpu_exchange_stats", "mcgpu_exchange_destroy", "mcgpu_copy_to_host",

@@ -939,6 +939,45 @@ int mcgpu_register_stage(const mcgpu_register_options *options, int stage, const
                          const unsigned char *fixed_mask_or_null, void *out, mcgpu_register_report *report);
 
 /* ------------------------------------------------------------------------------------------------
+ * Row f22: the inverse of a displacement field by fixed-point iteration, and the residual of a pair of fields
+ * (csrc/field_inverse.hip, whose header states the rule; float64 restatement: tests/field_inverse_ref.py).  Fields are
+ * [3][nx][ny][nz] float32 in voxels, component i along array axis i, nz fastest in memory: mcgpu_register's result.  The inverse v
+ * of u satisfies u(x + v(x)) + v(x) ~ 0: if moving(x + u(x)) ~ fixed(x) then fixed(y + v(y)) ~ moving(y).  One step is
+ * v <- v - relaxation r with the residual r(x) = v(x) + u(x + v(x)) (u sampled as mcgpu_register samples the moving image:
+ * trilinear, coordinates clamped), Jacobi, no early stop: the result is a function of (u, initial, iterations, relaxation), two
+ * calls give the same bytes.  The fields must be finite (not checked here; the Python layer refuses others).
+ * Refused with -1 before any device call: struct_size 0, a null pointer, a size below 1, 2^31 voxels or more, negative iterations,
+ * a relaxation that is not finite or outside (0, 1], a negative device. */
+typedef struct mcgpu_invert_options {
+  unsigned int struct_size;     /* sizeof(mcgpu_invert_options) as the caller was compiled (later fields read as zero); 0 is refused */
+  int nx, ny, nz;               /* the fields' shape; fewer than 2^31 voxels */
+  int iterations;               /* steps, >= 0; mcgpu_field_residual takes none */
+  int device;
+  double relaxation;            /* 0 < relaxation <= 1, rounded to float32; 1 converges only where the finite differences of u stay
+                                   below 1, 0.5 takes differences up to 3 */
+  const float *initial;         /* v_0 [3][nx][ny][nz], or NULL for zeros; mcgpu_field_residual does not read it */
+} mcgpu_invert_options;
+typedef struct mcgpu_invert_report {
+  unsigned int struct_size;     /* sizeof(mcgpu_invert_report) as the caller was compiled; only that many bytes are written */
+  int iterations;               /* the steps that were taken */
+  double residual_max_before;   /* max over components and voxels of |r_i(x)| before the first step */
+  double residual_rms_before;   /* sqrt(sum double(r_i)^2 / (3 N)), summed in double in a fixed order */
+  double residual_max_after;    /* the same two after the last step (mcgpu_field_residual leaves them 0) */
+  double residual_rms_after;
+  double ms_upload;             /* host <-> device copies (wall time) */
+  double ms_step;               /* the steps */
+  double ms_reduce;             /* the residuals */
+  double ms_total;              /* wall time of the call */
+  unsigned long long peak_device_bytes;  /* most device memory the call held at once: 9 N floats and the partial sums */
+} mcgpu_invert_report;
+int mcgpu_invert_field(const mcgpu_invert_options *options, const float *field /*[3][nx][ny][nz]*/, float *inverse_out /*[3][nx][ny][nz]*/,
+                       mcgpu_invert_report *report);
+/* r(x) = v(x) + u(x + v(x)) of two fields, no steps: fills residual_max_before and residual_rms_before, and residual_out where
+ * that is given.  About zero where v is the inverse of u; about 2 |u| where v = u. */
+int mcgpu_field_residual(const mcgpu_invert_options *options, const float *u, const float *v, float *residual_out_or_null /*[3][nx][ny][nz]*/,
+                         mcgpu_invert_report *report);
+
+/* ------------------------------------------------------------------------------------------------
  * Row f21: the breathing signal from the projections alone (what RTK does with rtkamsterdamshroud followed by
  * rtkextractshroudsignal; csrc/shroud.hip, whose header states the rule; float64 restatement: tests/shroud_ref.py).  Stage A forms
  * the Amsterdam shroud A[n_proj][m] (float32) from the projections, stage B the costs c_i(s) of shifting column i against column
