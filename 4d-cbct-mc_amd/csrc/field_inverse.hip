@@ -42,6 +42,11 @@
 
 namespace {
 
+using mcgpu::blocks_of;
+using mcgpu::refuse;
+
+#include "fixed_sum.inc"
+
 constexpr int kReduceBlocks = 256;    // the fixed grid of field_residual_kernel
 constexpr int kIterationChunk = 128;  // steps between two waits of the host
 
@@ -75,8 +80,8 @@ __global__ __launch_bounds__(256) void invert_step_kernel(const float* __restric
 }
 
 // partial_sum[block] = sum of double(r_i)^2, partial_max[block] = max |r_i|; every thread takes the voxels block x 256 + thread + m x grid
-// x 256 in rising m (components 0, 1, 2 of a voxel in that order), a block combines its 256 values by one fixed tree.  r is also stored
-// where r_out is given
+// x 256 in rising m (components 0, 1, 2 of a voxel in that order), a block combines its 256 (sum, maximum) pairs by the fixed tree
+// (fixed_sum.inc).  r is also stored where r_out is given
 __global__ __launch_bounds__(256) void field_residual_kernel(const float* __restrict__ u, const float* __restrict__ v, const Shape s, float* __restrict__ r_out,
                                                              double* __restrict__ partial_sum, float* __restrict__ partial_max) {
   double sum = 0.0;
@@ -94,28 +99,14 @@ __global__ __launch_bounds__(256) void field_residual_kernel(const float* __rest
       top = fmaxf(top, fabsf(r[c]));
     }
   }
-  __shared__ double lds_sum[256];
-  __shared__ float lds_max[256];
-  lds_sum[threadIdx.x] = sum;
-  lds_max[threadIdx.x] = top;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) {
-      lds_sum[threadIdx.x] += lds_sum[threadIdx.x + h];
-      lds_max[threadIdx.x] = fmaxf(lds_max[threadIdx.x], lds_max[threadIdx.x + h]);
-    }
-    __syncthreads();
-  }
+  const SumMax total = block_tree(SumMax{sum, top});
   if (threadIdx.x == 0) {
-    partial_sum[blockIdx.x] = lds_sum[0];
-    partial_max[blockIdx.x] = lds_max[0];
+    partial_sum[blockIdx.x] = total.sum;
+    partial_max[blockIdx.x] = total.top;
   }
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
-[[noreturn]] void refuse(const char* fn, const std::string& what) { throw mcgpu::Error(-1, std::string("!!ERROR!! ") + fn + ": " + what); }
-
-unsigned int blocks_of(size_t n) { return (unsigned int)((n + 255) / 256); }
 
 mcgpu_invert_options checked_options(const char* fn, const mcgpu_invert_options* caller) {
   mcgpu_invert_options o;
@@ -140,16 +131,12 @@ struct Reducer {
   void run(const float* u, const float* v, const Shape& s, float* d_r, double& residual_max, double& residual_rms) const {
     hipLaunchKernelGGL(field_residual_kernel, dim3(kReduceBlocks), dim3(256), 0, nullptr, u, v, s, d_r, d_sum, d_max);
     HIP_TRY(hipGetLastError());
-    double sums[kReduceBlocks];
+    double sum;
+    fold_blocks(d_sum, kReduceBlocks, 1, &sum);
     float maxima[kReduceBlocks];
-    HIP_TRY(hipMemcpy(sums, d_sum, sizeof sums, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(maxima, d_max, sizeof maxima, hipMemcpyDeviceToHost));
-    double sum = 0.0;
     float top = 0.f;
-    for (int b = 0; b < kReduceBlocks; ++b) {
-      sum += sums[b];
-      top = std::max(top, maxima[b]);
-    }
+    for (int b = 0; b < kReduceBlocks; ++b) top = std::max(top, maxima[b]);
     residual_max = (double)top;
     residual_rms = std::sqrt(sum / (3.0 * (double)s.voxels()));
   }

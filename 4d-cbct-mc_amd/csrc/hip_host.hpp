@@ -1,7 +1,9 @@
 #pragma once
-// hip_host.hpp -- what the host code around the device routines shares (engine*.cpp, scan.cpp, fdk.hip, wpc_fit.hip, forward_project.hip,
-// rooster4d.hip, shroud.hip, resample.hip, speedup_net.hip, speedup_train.hip, segment_net.hip): the HIP check, the exception boundary of the C ABI, owners of HIP handles and of one call's device memory, the
-// stage timer, the host stopwatch, the reader of struct_size-versioned options, the writer of such reports and the small rules of the circular cone-beam geometry.
+// hip_host.hpp -- what the host code around the device routines shares (engine*.cpp, scan.cpp, fdk.hip, wpc_fit.hip, registration.hip,
+// field_inverse.hip, shroud.hip, forward_project.hip, primary_project.hip, rooster4d.hip, resample.hip, speedup_net.hip, speedup_train.hip,
+// segment_net.hip, segment_train.hip): the HIP check, the exception boundary of the C ABI, owners of HIP handles and of one call's device
+// memory, the stage timer, the refusal of an argument, the block count of a one-thread-per-element launch, the host stopwatch, the reader
+// of struct_size-versioned options, the writer of such reports and the small rules of the circular cone-beam geometry.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -119,6 +121,12 @@ struct Stage {  // times a block of launches on the null stream into one report 
     ms += t;
   }
 };
+
+// what an entry point throws at an argument or a size it does not take: the message the C ABI's callers see
+[[noreturn]] inline void refuse(const char* fn, const std::string& what) { throw Error(-1, std::string("!!ERROR!! ") + fn + ": " + what); }
+
+// blocks of 256 threads that cover n elements
+inline unsigned int blocks_of(size_t n) { return (unsigned int)((n + 255) / 256); }
 
 struct Stopwatch {  // host milliseconds since it was made: the uploads and whole calls that no Stage brackets
   std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();

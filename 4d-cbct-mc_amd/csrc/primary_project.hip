@@ -478,7 +478,6 @@ void launch_primary_of(int vol_kind, float* d_out, const PrimaryVol& A, const Pr
   else launch_primary<kVolRaw, NM>(d_out, A, d_proj, d_W, d_K, nb);
 }
 
-[[noreturn]] void refuse(const char* fn, const std::string& what) { throw Error(-1, std::string("!!ERROR!! ") + fn + ": " + what); }
 
 struct Noise {  // of mcgpu_primary_noisy: the moments stay on the device, the sampled plane comes back
   double histories;

@@ -54,6 +54,11 @@
 
 namespace {
 
+using mcgpu::blocks_of;
+using mcgpu::refuse;
+
+#include "fixed_sum.inc"
+
 constexpr int kMaxRadius = 16;
 constexpr int kRowTile = 64, kRowsPerBlock = 4, kRowGroups = 4;  // smooth_row: 256 threads, a wave per row, 16 rows per block
 constexpr int kSegment = 32;                      // smooth_line: outputs per thread along the axis
@@ -189,7 +194,7 @@ __global__ __launch_bounds__(256) void smooth_line_kernel(const float* __restric
 }
 
 // partial[block] = sum of double(d)^2, d = float32(moving(x + u) - fixed); every thread takes the voxels block x 256 + thread + m x grid x 256
-// in rising m, a block adds its 256 sums by one fixed tree.  d is also stored where diff is given
+// in rising m, a block adds its 256 sums by the fixed tree (fixed_sum.inc).  d is also stored where diff is given
 __global__ __launch_bounds__(256) void msd_kernel(const float* __restrict__ fixed, const float* __restrict__ moving, const float* __restrict__ u, const Shape s,
                                                   float* __restrict__ diff, double* __restrict__ partial) {
   double sum = 0.0;
@@ -201,20 +206,11 @@ __global__ __launch_bounds__(256) void msd_kernel(const float* __restrict__ fixe
     if (diff) diff[i] = d;
     sum += (double)d * (double)d;
   }
-  __shared__ double lds[256];
-  lds[threadIdx.x] = sum;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) lds[threadIdx.x] += lds[threadIdx.x + h];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x] = lds[0];
+  const double total = block_tree(sum);
+  if (threadIdx.x == 0) partial[blockIdx.x] = total;
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
-[[noreturn]] void refuse(const char* fn, const std::string& what) { throw mcgpu::Error(-1, std::string("!!ERROR!! ") + fn + ": " + what); }
-
-unsigned int blocks_of(size_t n) { return (unsigned int)((n + 255) / 256); }
 
 Shape level_shape(const Shape& s, int level) {
   auto up = [level](int n) { return (int)(((long long)n + (1LL << level) - 1) >> level); };
@@ -371,11 +367,9 @@ double mean_squared_difference(const float* fixed, const float* moving, const fl
                                double* d_partial) {
   hipLaunchKernelGGL(msd_kernel, dim3(kReduceBlocks), dim3(256), 0, nullptr, fixed, moving, u, s, diff_host ? d_diff : nullptr, d_partial);
   HIP_TRY(hipGetLastError());
-  double partial[kReduceBlocks];
-  HIP_TRY(hipMemcpy(partial, d_partial, sizeof partial, hipMemcpyDeviceToHost));
+  double sum;
+  fold_blocks(d_partial, kReduceBlocks, 1, &sum);
   if (diff_host) HIP_TRY(hipMemcpy(diff_host, d_diff, s.voxels() * 4, hipMemcpyDeviceToHost));
-  double sum = 0.0;
-  for (int b = 0; b < kReduceBlocks; ++b) sum += partial[b];
   return sum / (double)s.voxels();
 }
 

@@ -72,6 +72,9 @@ namespace {
 
 using mcgpu::CallDevice;
 using mcgpu::Stage;
+using mcgpu::refuse;
+
+#include "fixed_sum.inc"
 
 constexpr int kFpBatch = 16;     // projections per forward launch (blockIdx.z)
 constexpr int kBpBatch = kBatch; // projections per back-projection launch (backproject_column.inc's measured optimum)
@@ -173,23 +176,11 @@ __device__ inline double dot4(float4 a, float4 b) {
   return (double)a.x * b.x + (double)a.y * b.y + (double)a.z * b.z + (double)a.w * b.w;
 }
 
-// fixed-order block sum of one double per thread (tree in LDS); thread 0 gets the total
-__device__ inline double block_sum(double v) {
-  __shared__ double red[kThreads];
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = kThreads / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 // part[block] = sum of a . b over the block's grid-stride share
 __global__ __launch_bounds__(256) void dot_partial_kernel(const float4* __restrict__ a, const float4* __restrict__ b, size_t n4, double* __restrict__ part) {
   double acc = 0.0;
   for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n4; i += (size_t)kRedBlocks * kThreads) acc += dot4(a[i], b[i]);
-  const double s = block_sum(acc);
+  const double s = block_tree(acc);  // fixed_sum.inc: thread 0 gets the total
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
@@ -197,7 +188,7 @@ __global__ __launch_bounds__(256) void dot_partial_kernel(const float4* __restri
 __global__ __launch_bounds__(256) void sum_partials_kernel(const double* __restrict__ part, double* __restrict__ out) {
   double acc = 0.0;
   for (int i = threadIdx.x; i < kRedBlocks; i += kThreads) acc += part[i];
-  const double s = block_sum(acc);
+  const double s = block_tree(acc);  // fixed_sum.inc: thread 0 gets the total
   if (threadIdx.x == 0) *out = s;
 }
 
@@ -212,7 +203,7 @@ __global__ __launch_bounds__(256) void cg_restart_kernel(const float4* __restric
     d[i] = v;
     acc += dot4(v, v);
   }
-  const double s = block_sum(acc);
+  const double s = block_tree(acc);  // fixed_sum.inc: thread 0 gets the total
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
@@ -229,7 +220,7 @@ __global__ __launch_bounds__(256) void cg_update_kernel(float4* __restrict__ x, 
     r[i] = rv;
     acc += dot4(rv, rv);
   }
-  const double s = block_sum(acc);
+  const double s = block_tree(acc);  // fixed_sum.inc: thread 0 gets the total
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
@@ -401,7 +392,6 @@ void interpolation_weights(double phase, int N, int& l, int& h, double& wl, doub
   wl = 1.0 - wh;
 }
 
-[[noreturn]] void refuse(const char* fn, const std::string& what) { throw mcgpu::Error(-1, std::string("!!ERROR!! ") + fn + ": " + what); }
 
 void read_options(const char* fn, const mcgpu_rooster4d_options* caller, mcgpu_rooster4d_options& o) {
   mcgpu::read_options(fn, "mcgpu_rooster4d_options", caller, o);

@@ -224,13 +224,12 @@ __global__ __launch_bounds__(256) void target_kernel(const unsigned char* raw, f
 // instead of reading nine float64 probabilities per voxel back from memory.
 constexpr int kDiceSums = 5;
 __global__ __launch_bounds__(256) void dice_sums_kernel(const float* logits, const float* t, size_t n, int S, double* part) {
-  __shared__ double s_v[256];
   const int s = blockIdx.x, tid = threadIdx.x;
-  const size_t seg = (n + S - 1) / S, lo = (size_t)s * seg, hi = min(lo + seg, n);
+  const Segment g = segment_of(n, S, s);
   double acc[kDiceSums * kClasses];
 #pragma unroll
   for (int k = 0; k < kDiceSums * kClasses; ++k) acc[k] = 0.0;
-  for (size_t i = lo + tid; i < hi; i += 256) {
+  for (size_t i = g.lo + tid; i < g.hi; i += 256) {
     double p[kClasses];
     head_of(logits, n, i, p);
 #pragma unroll
@@ -245,14 +244,8 @@ __global__ __launch_bounds__(256) void dice_sums_kernel(const float* logits, con
   }
 #pragma unroll
   for (int k = 0; k < kDiceSums * kClasses; ++k) {
-    s_v[tid] = acc[k];
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-      if (tid < w) s_v[tid] += s_v[tid + w];
-      __syncthreads();
-    }
-    if (tid == 0) part[(size_t)s * (kDiceSums * kClasses) + k] = s_v[0];
-    __syncthreads();
+    const double total = block_tree(acc[k]);
+    if (tid == 0) part[(size_t)s * (kDiceSums * kClasses) + k] = total;
   }
 }
 

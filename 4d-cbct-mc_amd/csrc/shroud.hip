@@ -46,6 +46,9 @@
 
 namespace {
 
+using mcgpu::blocks_of;  // kThreads is its 256
+using mcgpu::refuse;
+
 constexpr int kThreads = 256;
 constexpr int kSpan = kThreads * 4;  // the columns of a row that one workgroup takes
 constexpr int kBand = 32;            // the rows that one workgroup walks (a multiple of 4)
@@ -184,9 +187,6 @@ __global__ __launch_bounds__(kThreads) void cost_kernel(const float* __restrict_
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
-[[noreturn]] void refuse(const char* fn, const std::string& what) { throw mcgpu::Error(-1, std::string("!!ERROR!! ") + fn + ": " + what); }
-
-unsigned blocks_of(size_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
 // the options of a call that reads projections, with the counts of 0 resolved; everything is refused here, before the first HIP call
 mcgpu_shroud_options checked_projection_options(const char* fn, const mcgpu_shroud_options* caller) {

@@ -200,15 +200,14 @@ __global__ __launch_bounds__(256) void maxpool_backward_kernel(const float* x, c
   dx[base + at] += dy[i];
 }
 
-struct Sums4 { double v[4]; };
+using Sums4 = Sums<4>;
 
 // part[s] = float64 sums over segment s of |m - t|, 0.5 (log v' + (m - t)^2 / v'), (lp - t)^2, (m - t)^2
 __global__ __launch_bounds__(256) void metrics_kernel(const float* lp, const float* m, const float* v, const float* t, size_t hw, int S, Sums4* part) {
-  __shared__ double s_v[4][256];
   const int s = blockIdx.x, tid = threadIdx.x;
-  const size_t seg = (hw + S - 1) / S, lo = (size_t)s * seg, hi = min(lo + seg, hw);
+  const Segment g = segment_of(hw, S, s);
   double a[4] = {0.0, 0.0, 0.0, 0.0};
-  for (size_t i = lo + tid; i < hi; i += 256) {
+  for (size_t i = g.lo + tid; i < g.hi; i += 256) {
     const double d = (double)m[i] - (double)t[i], e = (double)lp[i] - (double)t[i];
     a[0] += fabs(d);
     if (v) {
@@ -218,22 +217,8 @@ __global__ __launch_bounds__(256) void metrics_kernel(const float* lp, const flo
     a[2] += e * e;
     a[3] += d * d;
   }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) s_v[k][tid] = a[k];
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (tid < w) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) s_v[k][tid] += s_v[k][tid + w];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    Sums4 o;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) o.v[k] = s_v[k][0];
-    part[s] = o;
-  }
+  const Sums4 total = block_tree(Sums4{{a[0], a[1], a[2], a[3]}});
+  if (tid == 0) part[s] = total;
 }
 
 // dL/dnet of the L1 loss through m = relu(lp + 10 tanh(net)); inv_n = 1 / N

@@ -7,15 +7,15 @@
 
 using mcgpu::CallDevice;
 using mcgpu::Stage;
+using mcgpu::blocks_of;
+using mcgpu::refuse;
 
-[[noreturn]] void refuse(const char* fn, const std::string& what) { throw mcgpu::Error(-1, std::string("!!ERROR!! ") + fn + ": " + what); }
+#include "fixed_sum.inc"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kCK = 8;             // input channels per K chunk
 constexpr int kKK = kCK * kTaps;   // K of a chunk
-
-unsigned blocks_of(size_t n) { return (unsigned)((n + 255) / 256); }
 
 // ------------------------------------------------------------------------------------------------- instance norm + LeakyReLU
 // Sum and sum of squares per channel in float64, over fixed segments and a fixed tree (no atomics: the same input gives the same
@@ -26,15 +26,21 @@ constexpr size_t kSegmentLength = 16384;
 
 int segments_of(size_t n) { return (int)std::min<size_t>(kMaxSegments, (n + kSegmentLength - 1) / kSegmentLength); }
 
+// segment s of S over n elements: [lo, hi)
+struct Segment { size_t lo, hi; };
+__device__ __forceinline__ Segment segment_of(size_t n, int S, int s) {
+  const size_t seg = (n + S - 1) / S, lo = (size_t)s * seg;
+  return {lo, min(lo + seg, n)};
+}
+
 // part[c][s] = (sum, sum of squares) of segment s of channel c, in float64 and in a fixed order
 __global__ __launch_bounds__(256) void stats_kernel(const float* x, size_t hw, int S, double2* part) {
-  __shared__ double s_sum[256], s_sq[256];
   const int c = blockIdx.y, s = blockIdx.x, tid = threadIdx.x;
-  const size_t seg = (hw + S - 1) / S, lo = (size_t)s * seg, hi = min(lo + seg, hw);
+  const Segment g = segment_of(hw, S, s);
   const float* p = x + (size_t)c * hw;
   double sum[4] = {0.0, 0.0, 0.0, 0.0}, sq[4] = {0.0, 0.0, 0.0, 0.0};  // four chains: four loads in flight, the order still fixed
-  size_t i = lo + tid;
-  for (; i + 768 < hi; i += 1024) {
+  size_t i = g.lo + tid;
+  for (; i + 768 < g.hi; i += 1024) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const double v = p[i + 256 * k];
@@ -42,22 +48,13 @@ __global__ __launch_bounds__(256) void stats_kernel(const float* x, size_t hw, i
       sq[k] += v * v;
     }
   }
-  for (; i < hi; i += 256) {
+  for (; i < g.hi; i += 256) {
     const double v = p[i];
     sum[0] += v;
     sq[0] += v * v;
   }
-  s_sum[tid] = (sum[0] + sum[1]) + (sum[2] + sum[3]);
-  s_sq[tid] = (sq[0] + sq[1]) + (sq[2] + sq[3]);
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (tid < w) {
-      s_sum[tid] += s_sum[tid + w];
-      s_sq[tid] += s_sq[tid + w];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) part[(size_t)c * S + s] = make_double2(s_sum[0], s_sq[0]);
+  const Sums<2> total = block_tree(Sums<2>{{(sum[0] + sum[1]) + (sum[2] + sum[3]), (sq[0] + sq[1]) + (sq[2] + sq[3])}});
+  if (tid == 0) part[(size_t)c * S + s] = make_double2(total.v[0], total.v[1]);
 }
 
 __device__ double2 fold_segments(const double2* part, int S) {

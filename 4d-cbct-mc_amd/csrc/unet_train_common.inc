@@ -1,6 +1,6 @@
 // unet_train_common.inc -- what speedup_train.hip (2-D) and segment_train.hip (3-D) share of the backward pass: the kernels that work
 // on flat [C][n] data and do not know the dimension of the net.  Included inside each file's unnamed namespace, after
-// unet_common.inc (stats_kernel's segments, fold_segments, blocks_of).  Each file's header states the rule these kernels follow.
+// unet_common.inc (stats_kernel's segments, fold_segments, fixed_sum.inc's tree).  Each file's header states the rule these kernels follow.
 //   norm_backward_stats_kernel + norm_backward_kernel: instance norm + LeakyReLU, backward (float64 sums, dx rounded once);
 //   wgrad_fold_kernel: the float32 partials of a weight gradient added in float64 in their order, scaled, rounded once, added;
 //   bias_grad_kernel: the same for the sums of dY; adam_kernel: one update in float64 per element, each result rounded once.
@@ -26,28 +26,18 @@ __device__ __forceinline__ double dxhat_of(float y, float dy) { return y > 0.f ?
 
 // part[c][s] = (sum of d xh, sum of d xh xh) of segment s of channel c: stats_kernel's segments and tree
 __global__ __launch_bounds__(256) void norm_backward_stats_kernel(const float* y, const float* dy, size_t hw, int S, double2* part) {
-  __shared__ double s_a[256], s_b[256];
   const int c = blockIdx.y, s = blockIdx.x, tid = threadIdx.x;
-  const size_t seg = (hw + S - 1) / S, lo = (size_t)s * seg, hi = min(lo + seg, hw);
+  const Segment g = segment_of(hw, S, s);
   const float* py = y + (size_t)c * hw;
   const float* pd = dy + (size_t)c * hw;
   double a = 0.0, b = 0.0;
-  for (size_t i = lo + tid; i < hi; i += 256) {
+  for (size_t i = g.lo + tid; i < g.hi; i += 256) {
     const double d = dxhat_of(py[i], pd[i]);
     a += d;
     b += d * xhat_of(py[i]);
   }
-  s_a[tid] = a;
-  s_b[tid] = b;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (tid < w) {
-      s_a[tid] += s_a[tid + w];
-      s_b[tid] += s_b[tid + w];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) part[(size_t)c * S + s] = make_double2(s_a[0], s_b[0]);
+  const Sums<2> total = block_tree(Sums<2>{{a, b}});
+  if (tid == 0) part[(size_t)c * S + s] = make_double2(total.v[0], total.v[1]);
 }
 
 // dy <- dx, in place; fpart: the forward's sums of the layer (mean, rstd), bpart: norm_backward_stats_kernel's

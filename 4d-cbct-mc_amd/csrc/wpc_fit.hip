@@ -30,6 +30,7 @@
 namespace {
 
 #include "fdk_common.inc"
+#include "fixed_sum.inc"
 
 constexpr int kMaxOrder = 7;
 constexpr int kChunk = 32;          // projections resident at a time when they fit (a multiple of kBatch; halved down to kBatch when not)
@@ -122,7 +123,7 @@ __global__ void slab_mean_kernel(float* __restrict__ fbar, size_t total, float y
 }
 
 // partial[block][t]: t runs over B[i][j], j >= i, row by row, then a[i].  Every thread takes the pixels block * 256 + thread + m * grid
-// * 256 in rising m, a block adds its 256 sums by one fixed tree: the same bytes on every call
+// * 256 in rising m, a block adds its 256 sums of a term by the fixed tree, term after term (fixed_sum.inc): the same bytes on every call
 template <int C>
 __global__ __launch_bounds__(256) void normal_equations_kernel(const float* __restrict__ fbar /*[C][npix]*/, const float* __restrict__ weight, const float* __restrict__ tmpl,
                                                                size_t npix, double* __restrict__ partial) {
@@ -145,24 +146,17 @@ __global__ __launch_bounds__(256) void normal_equations_kernel(const float* __re
 #pragma unroll
     for (int i = 0; i < C; ++i) s[t++] += w * f[i] * tp;
   }
-  __shared__ double lds[256];
 #pragma unroll
   for (int t = 0; t < T; ++t) {
-    lds[threadIdx.x] = s[t];
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-      if ((int)threadIdx.x < h) lds[threadIdx.x] += lds[threadIdx.x + h];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[(size_t)blockIdx.x * T + t] = lds[0];
-    __syncthreads();
+    const double total = block_tree(s[t]);
+    if (threadIdx.x == 0) partial[(size_t)blockIdx.x * T + t] = total;
   }
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
 const char* const kFn = "mcgpu_wpc_fit";
 
-[[noreturn]] void refuse(const std::string& what) { throw mcgpu::Error(-1, std::string("!!ERROR!! ") + kFn + ": " + what); }
+[[noreturn]] void refuse(const std::string& what) { mcgpu::refuse(kFn, what); }
 
 // the launches that depend on the compile-time number of powers
 template <int C>
@@ -298,13 +292,8 @@ extern "C" int mcgpu_wpc_fit(const mcgpu_wpc_fit_options* caller_o, const float*
     WPC_FOR_C(C, launch_reduce, (d_fbar, d_weight, d_tmpl, npix, d_partial));
     st.done();
   }
-  double partial[kReduceBlocks * kMaxTerms];
-  HIP_TRY(hipMemcpy(partial, d_partial, (size_t)kReduceBlocks * T * 8, hipMemcpyDeviceToHost));
   double sum[kMaxTerms];
-  for (int t = 0; t < T; ++t) {
-    sum[t] = 0.0;
-    for (int b = 0; b < kReduceBlocks; ++b) sum[t] += partial[b * T + t];
-  }
+  fold_blocks(d_partial, kReduceBlocks, T, sum);
   int t = 0;
   for (int i = 0; i < C; ++i)
     for (int j = i; j < C; ++j) B[i * C + j] = B[j * C + i] = sum[t++];

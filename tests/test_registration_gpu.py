@@ -7,6 +7,7 @@ import pytest
 
 import cases
 import registration_ref as R
+from fixed_sum_ref import grid_sum
 
 pytestmark = pytest.mark.gpu
 
@@ -89,15 +90,31 @@ def _sphere_pair(shape, centre, shift, radius):
     return fixed, moving
 
 
-def test_whole_loop(engine):
-    """(24, 20, 16), two levels, 10 iterations, masked: the field against the float64 restatement, two calls, the report."""
+def _noisy_sphere_pair(shape, centre, radius):
+    """A sphere shifted by 2 voxels along axis 2, the fixed image with noise of 0.02."""
+    fixed, moving = _sphere_pair(shape, centre, 2, radius)
+    return fixed + 0.02 * np.random.default_rng(8).normal(size=shape).astype(np.float32), moving
+
+
+def _whole_loop_case():
+    """(24, 20, 16), two levels, 10 iterations, masked."""
     shape = (24, 20, 16)
-    fixed, moving = _sphere_pair(shape, (12, 10, 9), 2, 5.0)
-    rng = np.random.default_rng(8)
-    fixed = fixed + 0.02 * rng.normal(size=shape).astype(np.float32)
+    fixed, moving = _noisy_sphere_pair(shape, (12, 10, 9), 5.0)
     mask = np.ones(shape, dtype=np.uint8)
     mask[:3] = 0
-    kw = dict(fixed_mask=mask, iterations=10, tau=2.25, sigma=(1.25, 1.25, 1.25), n_levels=2)
+    return fixed, moving, dict(fixed_mask=mask, iterations=10, tau=2.25, sigma=(1.25, 1.25, 1.25), n_levels=2)
+
+
+def _sum_order_case():
+    """(41, 40, 41): 67 240 voxels, 1 704 more than one sweep of the 256 x 256 reduce grid.  One level, one iteration."""
+    fixed, moving = _noisy_sphere_pair((41, 40, 41), (20, 20, 21), 8.0)
+    return fixed, moving, dict(iterations=1, tau=2.25, sigma=(1.25, 1.25, 1.25), n_levels=1)
+
+
+def test_whole_loop(engine):
+    """(24, 20, 16), two levels, 10 iterations, masked: the field against the float64 restatement, two calls, the report."""
+    fixed, moving, kw = _whole_loop_case()
+    shape = fixed.shape
     got, report = reg.register(fixed, moving, return_differences=True, **kw)
     again, report2 = reg.register(fixed, moving, **kw)
     assert got.dtype == np.float32 and got.shape == (3,) + shape and got.tobytes() == again.tobytes()
@@ -118,6 +135,21 @@ def test_whole_loop(engine):
     # identical images: exact zeros
     zero, report = reg.register(fixed, fixed, **kw)
     assert not zero.any() and report["msd_after"] == [0.0, 0.0]
+
+
+def test_msd_is_the_sum_in_the_order_of_the_reduce_grid(engine):
+    """The report's mean squared differences are the float32 differences the call returns, squared and added in float64 in the order
+    of csrc/fixed_sum.inc: some threads of the grid add a second voxel."""
+    fixed, moving, kw = _sum_order_case()
+    shape = fixed.shape
+    _, report = reg.register(fixed, moving, return_differences=True, **kw)
+    (before, after), = report["differences"]
+    for name, d in (("msd_before", before), ("msd_after", after)):
+        assert d.dtype == np.float32 and d.shape == shape
+        terms = d.astype(np.float64).ravel() ** 2
+        print(f"{name}: {report[name][0]!r}, in the grid's order {grid_sum(terms, 256) / d.size!r}, numpy's {float(terms.sum()) / d.size!r}")
+        assert report[name][0] == grid_sum(terms, 256) / d.size
+    assert report["msd_after"][0] < report["msd_before"][0]
 
 
 def test_sphere_recovery_on_the_device(engine):

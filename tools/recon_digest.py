@@ -12,6 +12,9 @@ comparable only within one installation.  The cases are the tests' own builders 
   rooster_motion  rooster4d_motion_stage "warp", "unwarp" and "tv_time_motion" (5 iterations, gamma 0.05, the negated model back) on
                   test_rooster4d_motion's 13 x 5 x 7 small case at K = 1, 2, 3 and 4, and one rooster4d_motion call on the case of
                   test_rooster4d_motion_equals_the_restated_loop_and_repeats_bit_for_bit (volume and residuals)
+  register        registration.register on test_registration_gpu's whole-loop case and its (41, 40, 41) case: field, msd_before, msd_after
+  invert          registration.invert_field (initial v_0, 5 steps) on test_field_inverse_gpu._fields at (17, 13, 11) and (41, 40, 41):
+                  the inverse and the four norms; composition_residual on the same: r and its two norms
 --one-slice adds, on "half_fan" with the direct ramp at order 1, slabs (0, 1) and (29, 1), both layouts: the number of float32 words
 in which basis_mean[n] of the fused call differs from fdk(..., water_pre_correction=e_n)[0][:, y, :] (tests/test_wpc_fit_gpu.py).
 Usage: [MCGPU_AMD_LIB=other.so] python tools/recon_digest.py [--one-slice] [--out FILE.json]"""
@@ -57,8 +60,10 @@ def main():
     pkg.engine.load_library()
     recon, wp = pkg.reconstruction, pkg.water_precorrection
     import test_fdk_configs as F
+    import test_field_inverse_gpu as FI
     import test_fdk_motion as FM
     import test_forward_projection_configs as J
+    import test_registration_gpu as RG
     import test_rooster4d_motion as RM
     import test_rooster4d_configs as R
     import wpc_ref as W
@@ -106,6 +111,17 @@ def main():
     vol, rep = recon.rooster4d_motion(RM.base._projections(geo, ph), geo, (RM.PIX, RM.PIX), None, ph, *RM._motion_models(RM._k2_models()), RM._signals(ph), RM.DIM,
                                       RM.SPACING, frames=RM.FRAMES, niter=2, cgiter=3, tviter=5, gamma_space=0.002, gamma_time=0.002)
     out["rooster_motion whole call"] = sha(vol, rep["residuals"])
+
+    reg = pkg.registration
+    for name, (fixed, moving, kw) in (("whole loop", RG._whole_loop_case()), ("41x40x41", RG._sum_order_case())):
+        u, rep = reg.register(fixed, moving, **kw)
+        out[f"register {name}"] = sha(u, np.float64(rep["msd_before"]), np.float64(rep["msd_after"]))
+    for shape in ((17, 13, 11), (41, 40, 41)):
+        u, v0 = FI._fields(shape)
+        v, rep = reg.invert_field(u, iterations=5, initial=v0)
+        out[f"invert {FI.ids(shape)}"] = sha(v, np.float64([rep[k] for k in ("residual_max_before", "residual_rms_before", "residual_max_after", "residual_rms_after")]))
+        r, rep = reg.composition_residual(u, v0)
+        out[f"invert {FI.ids(shape)} residual"] = sha(r, np.float64([rep["residual_max"], rep["residual_rms"]]))
 
     if args.one_slice:
         ramp(True)

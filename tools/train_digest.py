@@ -8,6 +8,9 @@ in one session on one box and compare the two objects key for key.  The cases ar
   <net> stage <operator>   conv_wgrad, conv_dgrad and maxpool_backward of both stage entry points on float data: (5, 3) -> 7 at
                            33 x 70 and (4, 6) -> 4 at 4 x 10 x 66, the second source upsampled; the 3-D max-pool with and without
                            an initial dx
+  <net> run / norm         the inference entry points, whose objects hold their own copy of the instance norm: MCSpeedup.predict
+                           on test_speedup_gpu's 1 x 32 x 32 case, MCSegmenter.segment on test_segmentation_gpu's "unequal" net, and
+                           the norm_lrelu stage of both on their tests' "segments" input
 Usage: [MCGPU_AMD_LIB=other.so] python tools/train_digest.py [--out FILE.json]"""
 from __future__ import annotations
 
@@ -83,6 +86,16 @@ def main():
     out["segment stage conv_dgrad"] = sha(*G.stage("conv_dgrad", dy, in2=w, c1=4, upsample=True)[0])
     out["segment stage maxpool_backward"] = sha(G.stage("maxpool_backward", x1, in2=dy[:, :2, :5, :33])[0])
     out["segment stage maxpool_backward onto dx"] = sha(G.stage("maxpool_backward", x1, in2=dy[:, :2, :5, :33], in3=dy)[0])
+
+    import test_segmentation_gpu as N3
+    import test_speedup_gpu as N2
+    lp, fp = N2.speedup_ref.seeded_inputs(7, *N2.NETWORK_SHAPES[0])
+    out["speedup run"] = sha(*N2.speedup.MCSpeedup(N2.speedup_ref.seeded_weights(7)).predict(lp, fp))
+    out["speedup norm"] = sha(N2.speedup.speedup_stage("norm_lrelu", N2._norm_inputs()["segments"])[0])
+    filters, levels = N3.NETWORKS["unequal"]
+    model = N3.seg.MCSegmenter(N3.segment_ref.seeded_weights(7, filters, levels), patch_shape=N3.PATCH)
+    out["segment run"] = sha(*model.segment(N3.segment_ref.seeded_image(7, N3.PATCH)))
+    out["segment norm"] = sha(N3.seg.segment_stage("norm_lrelu", N3._norm_inputs()["segments"])[0])
 
     print(json.dumps(out, sort_keys=True))
     if args.out:
